@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- aggregated range-proof verifies/sec on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c5]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps of the headline and prints the result line (with `roofline` and
+`stage_ms` from the HIP events of those steps).  `--dump-outputs DIR` also writes what the last timed step computed:
+DIR/verdicts.npy, the per-proof verdict words of the batch as float32 (0 = Ok), and DIR/mulvec_scalars.npy, the
+verifier's MulVec scalars (reference MulVec order) of a seeded sample of up to 256 proofs, float64 of shape
+(proofs, terms, 8): every 256-bit scalar as eight little-endian 32-bit words; DIR/mulvec_scalars_proofs.npy holds the
+indices of the sampled proofs.  Ranks r > 0 add the suffix _rank<r>.  The inputs are the same from run to run for the
+same arguments.  The tamper check, the side legs and the CPU
+baseline listed below run only under `--full`, where the options of those legs apply.
 
 A "step" is one pass of the hot path (RangeProof::verify for every proof of a resident batch:
 verifier scalars -> fixed-generator MSM through the window tables -> proof-point MSM -> is_zero) over a
@@ -56,6 +65,16 @@ CONFIGS = {
     "c3": (64, 1, 4096, 16),
     "c5": (64, 1, 8192, 16),
 }
+
+# options of the checks and side legs beyond the headline, with their values under --full (a plain run runs none of them)
+FULL_DEFAULTS = {"cpu_seconds": 5.0, "combined_steps": -1, "pipeline_streams": 2, "grouped_steps": 5, "other_curves_steps": 3,
+                 "hard_steps": 4, "c3_steps": 5, "latency_steps": 5, "prove_steps": 2, "serialized_steps": 3, "sustained_steps": 0,
+                 "production_steps": 3, "single_call_reps": 5, "msm_steps": 5, "tampered": 64}
+
+# --dump-outputs stays under 64 MB: at most 4 Mi verdicts (float32) and the MulVec scalars of at most 256 proofs (float64)
+# in 40 MB; larger outputs are written as a fixed, seeded sample
+DUMP_VERDICTS = 4 << 20
+DUMP_SCALAR_BYTES = 40 << 20
 
 
 MSM_ORDER = {"bls12_381": 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001,
@@ -297,36 +316,47 @@ def main():
     ap.add_argument("--m", type=int, default=0)
     ap.add_argument("--window", type=int, default=0,
                     help="window bits of the fixed-generator tables (c2: 17 = 204 GB for n=64, m=16 on BLS12-381)")
-    ap.add_argument("--cpu-seconds", type=float, default=5.0, help="wall seconds per CPU-baseline sample; 0 disables the CPU leg")
-    ap.add_argument("--combined-steps", type=int, default=-1,
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the verdicts and a sample of the MulVec scalars of the last timed step to DIR (see module doc)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the tamper check, the side legs and the CPU baseline; the options below apply only with it")
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="wall seconds per CPU-baseline sample; 0 disables the CPU leg")
+    ap.add_argument("--combined-steps", type=int, default=None,
                     help="extra (separately timed) steps of the combined batch check; -1 = same as --steps, 0 = skip")
-    ap.add_argument("--pipeline-streams", type=int, default=2,
+    ap.add_argument("--pipeline-streams", type=int, default=None,
                     help="streams of the `pipelined` leg (the headline's passes alternating between them); < 2 = skip")
-    ap.add_argument("--grouped-steps", type=int, default=5,
+    ap.add_argument("--grouped-steps", type=int, default=None,
                     help="steps of the grouped check (per-proof verdicts from one weighted check per group); 0 = skip")
     ap.add_argument("--group", type=int, default=32, help="proofs per group of the grouped check (a power of two)")
-    ap.add_argument("--other-curves-steps", type=int, default=3,
+    ap.add_argument("--other-curves-steps", type=int, default=None,
                     help="steps per extra leg on the other two instantiations of the same kernels (edwards25519 -- the curve "
                          "under Ristretto255, which BASELINE.json's configs[1] names -- and secp256k1); 0 = skip")
-    ap.add_argument("--hard-steps", type=int, default=4,
+    ap.add_argument("--hard-steps", type=int, default=None,
                     help="steps of the 'hard distribution' leg (random generators, random full-width challenges; SURVEY 8d); 0 = skip")
-    ap.add_argument("--c3-steps", type=int, default=5, help="steps of the C3 leg (4096 x (64,1)) of a c2 run; 0 = skip")
-    ap.add_argument("--latency-steps", type=int, default=5, help="steps per small-batch latency point (B = 1, 16, 256); 0 = skip")
-    ap.add_argument("--prove-steps", type=int, default=2, help="steps of the device-resident batched prover leg; 0 = skip")
-    ap.add_argument("--serialized-steps", type=int, default=3,
+    ap.add_argument("--c3-steps", type=int, default=None, help="steps of the C3 leg (4096 x (64,1)) of a c2 run; 0 = skip")
+    ap.add_argument("--latency-steps", type=int, default=None, help="steps per small-batch latency point (B = 1, 16, 256); 0 = skip")
+    ap.add_argument("--prove-steps", type=int, default=None, help="steps of the device-resident batched prover leg; 0 = skip")
+    ap.add_argument("--serialized-steps", type=int, default=None,
                     help="steps of the serialized-input leg (containers + compressed commitments resident in HBM); 0 = skip")
-    ap.add_argument("--sustained-steps", type=int, default=0,
+    ap.add_argument("--sustained-steps", type=int, default=None,
                     help="extra back-to-back steps of the headline pass after the timed region (a 200-step run is kept in profiles/)")
-    ap.add_argument("--production-steps", type=int, default=3,
+    ap.add_argument("--production-steps", type=int, default=None,
                     help="steps of the production-path leg (hashed generators + transcript + serialized input); 0 = skip")
-    ap.add_argument("--single-call-reps", type=int, default=5,
+    ap.add_argument("--single-call-reps", type=int, default=None,
                     help="calls per point of the single_call leg (bpp_range_prove / bpp_range_verify, host pointers); 0 = skip")
-    ap.add_argument("--msm-steps", type=int, default=5,
+    ap.add_argument("--msm-steps", type=int, default=None,
                     help="steps per point of the `msm` leg (device-resident general MulVec, N = 2^16 .. 2^22 on the three curves); 0 = skip")
     ap.add_argument("--msm-log2n", type=int, nargs="+", default=[16, 18, 20, 22])
-    ap.add_argument("--tampered", type=int, default=64, help="tampered proofs of the untimed verdict check after the timed region")
+    ap.add_argument("--tampered", type=int, default=None, help="tampered proofs of the untimed verdict check after the timed region")
     ap.add_argument("--dry-run", action="store_true", help="launcher/collective rehearsal without a GPU (see dry_run)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    for k, v in FULL_DEFAULTS.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v if args.full else 0)
+        elif not args.full:
+            ap.error("--%s belongs to a check or side leg beyond the headline: add --full" % k.replace("_", "-"))
 
     # ---- launcher mode: must come before anything imports torch or touches the GPU ---------------------
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -427,11 +457,15 @@ def main():
     d_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     d_fail = torch.zeros(1, dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream().cuda_stream
+    # --dump-outputs: the pass also hands back its MulVec scalars (bpp_verifier_run's d_out_scalars), written there
+    # instead of into the workspace -- the same kernels and the same work
+    d_osc = torch.empty((Bsz, bv.msm_len, 4), dtype=torch.int64, device=dev) if args.dump_outputs else None
 
     comm_ev = []   # (before, after) events around the exchange step of every timed step (world > 1)
 
     def step(_i=0):
-        bv.run_device(d_pts.data_ptr(), d_sc.data_ptr(), Bsz, d_ok.data_ptr(), d_ws.data_ptr(), wsb, stream)
+        bv.run_device(d_pts.data_ptr(), d_sc.data_ptr(), Bsz, d_ok.data_ptr(), d_ws.data_ptr(), wsb, stream,
+                      d_out_scalars=d_osc.data_ptr() if d_osc is not None else 0)
         if dist is not None:
             # the one exchange step of the path: batch verdict = sum of per-proof failures over all ranks
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -443,6 +477,7 @@ def main():
 
     for _ in range(args.warmup):
         step()
+    d_ok.fill_(7)          # the verdicts read below are the timed steps' own, not the warm-up's
     torch.cuda.synchronize()
     bv.set_profiling(True)
     comm_ev.clear()
@@ -450,13 +485,29 @@ def main():
     stage_ms, passes, bpp_ = bv.profile()
     bv.set_profiling(False)
     comm_ms = (sum(e0.elapsed_time(e1) for e0, e1 in comm_ev) / len(comm_ev)) if comm_ev else None
+    ok = d_ok.cpu().numpy()
+    if args.dump_outputs:
+        # what a caller of the timed path receives from its last step: the verdict word of every proof (0 = Ok) and the
+        # MulVec scalars of a seeded sample of the proofs, each 256-bit scalar as eight 32-bit words (exact in float64)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = "" if rank == 0 else "_rank%d" % rank
+        out_v = ok.astype(np.float32)
+        if out_v.size > DUMP_VERDICTS:
+            out_v = out_v[np.sort(np.random.RandomState(0).choice(out_v.size, DUMP_VERDICTS, replace=False))]
+        np.save(os.path.join(args.dump_outputs, "verdicts%s.npy" % sfx), out_v)
+        S = max(1, min(256, Bsz, DUMP_SCALAR_BYTES // (bv.msm_len * 64)))
+        pick = np.sort(np.random.RandomState(1).choice(Bsz, S, replace=False))
+        words = d_osc[torch.from_numpy(pick).to(dev)].cpu().numpy().view(np.uint32)      # (S, msm_len, 8), little-endian
+        np.save(os.path.join(args.dump_outputs, "mulvec_scalars%s.npy" % sfx), words.astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "mulvec_scalars_proofs%s.npy" % sfx), pick.astype(np.float64))
+        d_osc = None
+        torch.cuda.empty_cache()
     # sustained: the same step many times back to back (clock drift / thermal check of the short timed region)
     sustained = None
     if args.sustained_steps > 0:
         sdt_ = timed(step, args.sustained_steps, torch, dist, coll_dev)
         sustained = {"steps": args.sustained_steps, "seconds": sdt_, "value": world * Bsz * args.sustained_steps / sdt_,
                      "ms_per_step": sdt_ / args.sustained_steps * 1e3}
-    ok = d_ok.cpu().numpy()
     assert int(ok.sum()) == 0, "a valid proof failed to verify"
     if dist is not None:
         assert int(d_fail.item()) == 0

@@ -44,13 +44,12 @@ def test_product_does_not_import_the_oracle():
                     os.path.join(dirpath, f)
 
 
-def test_host_field_arithmetic_matches_bigints():
+def test_host_field_arithmetic_matches_bigints(tmp_path):
     """csrc/field.hpp compiled for the host (g++) against Python big integers."""
     import random
     import subprocess
-    import tempfile
     import pyref as P
-    exe = os.path.join(tempfile.gettempdir(), "bpp_field_host_test")
+    exe = str(tmp_path / "bpp_field_host_test")
     subprocess.check_call(["g++", "-O2", "-std=c++17"] + SANITIZE + ["-o", exe, os.path.join(ROOT, "tests", "host", "field_host_test.cpp")])
     mods = {"blsfp": P.BLS12_381["p"], "blsfr": P.BLS12_381["r"], "secpfp": P.SECP256K1["p"], "secpfr": P.SECP256K1["r"],
             "edfp": P.ED25519["p"], "edfr": P.ED25519["r"]}
@@ -80,13 +79,12 @@ def test_host_field_arithmetic_matches_bigints():
     assert [int(o, 16) for o in out] == exp
 
 
-def test_generated_constants_are_in_sync():
+def test_generated_constants_are_in_sync(tmp_path):
     """csrc/constants_gen.h is what tools/gen_constants.py generates from the field moduli (Montgomery constants,
     p^-1 mod 2^30, number of divstep batches, curve constants)."""
     import subprocess
     import sys
-    import tempfile
-    out = os.path.join(tempfile.gettempdir(), "bpp_constants_check.h")
+    out = str(tmp_path / "bpp_constants_check.h")
     subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "gen_constants.py"), out], stdout=subprocess.DEVNULL)
     with open(out) as f, open(os.path.join(ROOT, "bulletproofsplus_amd", "csrc", "constants_gen.h")) as g:
         assert f.read() == g.read()

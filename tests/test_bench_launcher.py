@@ -51,3 +51,13 @@ def test_under_torch_distributed_run():
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "2"]
     line = _json_line(subprocess.check_output(cmd, env=_env(), timeout=300, stderr=subprocess.DEVNULL))
     assert line["n_gpus"] == 2 and line["ranks_seen"] == 2
+
+
+def test_side_leg_options_need_full():
+    """A plain run times the headline only: an option of a check or side leg without --full is refused, not ignored."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--hard-steps", "2"], env=_env(),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr, r.stderr
+    line = _json_line(subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--full",
+                                               "--hard-steps", "2"], env=_env(), timeout=300))
+    assert line["n_gpus"] == 1 and line["ranks_seen"] == 1

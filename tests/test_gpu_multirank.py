@@ -36,7 +36,7 @@ def test_bench_spawns_two_ranks_c5_shape():
         pytest.skip("needs a GPU")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update({"BPP_BENCH_BACKEND": "gloo", "BPP_BENCH_DEVICE": "0"})
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "c5", "--batch", "512", "--window", "10",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--config", "c5", "--batch", "512", "--window", "10",
            "--steps", "2", "--warmup", "1", "--combined-steps", "2", "--hard-steps", "0", "--other-curves-steps", "0",
            "--prove-steps", "1", "--tampered", "9"]
     out = subprocess.check_output(cmd, env=env, timeout=900)
@@ -60,7 +60,7 @@ def test_rccl_initialises_and_runs_the_bench_collectives():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "BPP_BENCH_BACKEND")}
     env.update({"BPP_BENCH_FORCE_DIST": "1", "RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1", "MASTER_ADDR": "127.0.0.1",
                 "MASTER_PORT": str(_free_port())})
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c5", "--batch", "512", "--window", "10",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "c5", "--batch", "512", "--window", "10",
            "--steps", "2", "--warmup", "1", "--combined-steps", "2", "--hard-steps", "0", "--other-curves-steps", "0",
            "--prove-steps", "0", "--serialized-steps", "0", "--latency-steps", "0", "--cpu-seconds", "0", "--tampered", "5"]
     out = subprocess.check_output(cmd, env=env, timeout=900)

@@ -6,7 +6,6 @@ intermediate bound asserted (tests/host/lazy_host_test.cpp), and the GLV scalar 
 import os
 import random
 import subprocess
-import tempfile
 
 import pyref as P
 
@@ -18,24 +17,24 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g"] if os.environ.get("BPP_HOST_SANITIZE") else []
 
 
-def _build(name, opt="-O1"):
-    exe = os.path.join(tempfile.gettempdir(), "bpp_" + name + ("_san" if SANITIZE else ""))
+def _build(name, tmp_path, opt="-O1"):
+    exe = str(tmp_path / ("bpp_" + name + ("_san" if SANITIZE else "")))
     subprocess.check_call(["g++", opt, "-std=c++17"] + SANITIZE + ["-o", exe, os.path.join(ROOT, "tests", "host", name + ".cpp")])
     return exe
 
 
-def test_lazy_mixed_addition_bounds_and_values():
-    out = subprocess.check_output([_build("lazy_host_test")]).decode()
+def test_lazy_mixed_addition_bounds_and_values(tmp_path):
+    out = subprocess.check_output([_build("lazy_host_test", tmp_path)]).decode()
     assert "ok bls12_381" in out and "ok secp256k1" in out
 
 
-def test_edwards_lazy_mixed_addition():
-    out = subprocess.check_output([_build("ed_lazy_host_test")]).decode()
+def test_edwards_lazy_mixed_addition(tmp_path):
+    out = subprocess.check_output([_build("ed_lazy_host_test", tmp_path)]).decode()
     assert "ok ed25519" in out
 
 
-def test_glv_split_matches_integers():
-    exe = _build("glv_host_test", "-O2")
+def test_glv_split_matches_integers(tmp_path):
+    exe = _build("glv_host_test", tmp_path, "-O2")
     r = P.BLS12_381["r"]
     z2 = 0xd201000000010000 ** 2
     rng = random.Random(11)
@@ -53,10 +52,10 @@ def test_glv_split_matches_integers():
             assert k1 < (1 << 128) and k2 < (1 << 128)
 
 
-def test_glv_split_secp256k1_signed():
+def test_glv_split_secp256k1_signed(tmp_path):
     """k == (+-k1) + (+-k2) lambda mod n with both magnitudes below 2^128 -- random scalars and the edges (0, 1, n - 1,
     lambda, n - lambda, the middle of the range, values that make either half negative)"""
-    exe = _build("glv_host_test", "-O2")
+    exe = _build("glv_host_test", tmp_path, "-O2")
     n = P.SECP256K1["r"]
     lam = 0x5363ad4cc05c30e0a5261c028812645a122e22ea20816678df02967c1b23bd72
     assert (lam * lam + lam + 1) % n == 0

@@ -19,8 +19,8 @@ SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "
 
 
 @pytest.fixture(scope="module")
-def harness():
-    exe = os.path.join(tempfile.gettempdir(), "bpp_transcript_host_test")
+def harness(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("host") / "bpp_transcript_host_test")
     subprocess.check_call(["g++", "-O2", "-std=c++17"] + SANITIZE + ["-o", exe, os.path.join(ROOT, "tests", "host", "transcript_host_test.cpp")])
     return exe
 

@@ -8,7 +8,7 @@ OUT=$(readlink -f "$1"); PART=${2:-all}
 mkdir -p "$OUT"
 ROOT=$(pwd)
 cd /tmp && export TMPDIR=/tmp
-OFF="--c3-steps 0 --prove-steps 0 --serialized-steps 0 --hard-steps 0 --other-curves-steps 0 --production-steps 0 --single-call-reps 0 --msm-steps 0 --latency-steps 0 --combined-steps 0 --grouped-steps 0 --pipeline-streams 0 --cpu-seconds 0"
+OFF="--full --c3-steps 0 --prove-steps 0 --serialized-steps 0 --hard-steps 0 --other-curves-steps 0 --production-steps 0 --single-call-reps 0 --msm-steps 0 --latency-steps 0 --combined-steps 0 --grouped-steps 0 --pipeline-streams 0 --cpu-seconds 0"
 prof() {  # name, bench args...
     local name=$1; shift
     timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$name" -o k -- python3 "$ROOT/bench.py" "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" || return 1
