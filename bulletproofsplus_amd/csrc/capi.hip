@@ -235,6 +235,9 @@ static VerifyCacheEntry* engine_for_key(bpp_ctx* ctx, const uint64_t* gh, const 
     if (!hit->v) {   // the key came back: build its tables (an invalid generator or no memory: stay with the table-free path)
         bpp_verifier* v = nullptr;
         if (bpp_verifier_create(ctx, gh, G, H, n, m, VCACHE_WINDOW, &v)) return nullptr;
+        // the literal call takes wire points of unknown origin: on BLS12-381 a point outside G1 must not reach the
+        // endomorphism evaluation, which is not the full-curve sum there (include/bpp_amd.h, bpp_verifier_set_subgroup_check)
+        v->check_subgroup = ctx->curve == BPP_BLS12_381_G1;
         const size_t wsb = bpp_verifier_workspace_bytes(v, 1);
         if (hit->pts.alloc(v->s.NV * pw * 8) != hipSuccess || hit->sc.alloc(96) != hipSuccess ||
             hit->ok.alloc(4) != hipSuccess || hit->ws.alloc(wsb) != hipSuccess) {
@@ -270,6 +273,11 @@ extern "C" int bpp_range_verify(bpp_ctx* ctx, const uint64_t* gh, const uint64_t
     if (rc) return rc;
     uint32_t verdict = 1;
     HIPCHK(hipMemcpy(&verdict, hit->ok.p, 4, hipMemcpyDeviceToHost));
+    // BLS12-381: an accept of the cached pass is exact (its points passed the membership test); a reject may be a curve
+    // point outside G1 whose full-curve contribution cancels, so the table-free full-curve path decides it, as it decides
+    // every call of the reference.  secp256k1 (cofactor 1) and edwards25519 (the same E[4] identity test as the naive
+    // path) need no second opinion.
+    if (verdict && ctx->curve == BPP_BLS12_381_G1) return naive();
     return verdict ? BPP_VERIFICATION_ERROR : BPP_OK;
 }
 

@@ -77,11 +77,13 @@ inline int dispatch(int curve, F&& f) {
 
 inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
-// scalar (4 x u64 = 8 words) reduced mod r on the host: PrimeFieldElem values are always < r
+// scalar (4 x u64 = 8 words) reduced mod r on the host: PrimeFieldElem values are always < r.  A 256-bit value holds up
+// to floor(2^256 / r) multiples of r: 1 on secp256k1, 2 on BLS12-381, 15 on edwards25519 (r ~ 2^252) -- hence 16
+// rounds, as k_pip_points does on the device
 template <class C>
 void reduce_scalar_words(uint32_t* w) {
     using P = typename C::Fr;
-    for (int iter = 0; iter < 4; iter++) {
+    for (int iter = 0; iter < 16; iter++) {
         if (words_lt_mod<P>(w)) return;
         uint64_t borrow = 0;
         for (int i = 0; i < 8; i++) {

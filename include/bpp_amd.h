@@ -151,7 +151,11 @@ int bpp_wip_fold_round(bpp_ctx *ctx, uint64_t *a, uint64_t *b, uint64_t *G, uint
  * verifier with narrow window tables for it (c = 8: milliseconds to build, < 1 GB at n m = 1024) and that and later
  * calls run the batch verifier's pass at count = 1.  A cached entry is found by hash and confirmed by comparing the
  * key bytes; at most four keys, least recently used out; bpp_set_verify_cache(ctx, 0) switches the mechanism off and
- * frees it.  Verdicts do not depend on which path ran (tests/test_gpu_round3.py). */
+ * frees it.  Points outside the prime-order group are judged by the full-curve sum, as the reference does: on BLS12-381
+ * the cached verifier runs with the subgroup check on (bpp_verifier_set_subgroup_check), and a reject of the cached pass
+ * is decided again by the table-free full-curve MulVec -- so a curve point outside G1 whose contribution cancels is
+ * accepted, one whose contribution does not is rejected.  Verdicts do not depend on which path ran
+ * (tests/test_gpu_verdict_parity.py). */
 int bpp_set_verify_cache(bpp_ctx *ctx, int on);
 int bpp_range_verify(bpp_ctx *ctx, const uint64_t *gh, const uint64_t *G, const uint64_t *H, size_t n,
                      size_t m, const uint64_t *proof_points, size_t k, const uint64_t *proof_scalars,
