@@ -20,6 +20,7 @@ beyond (de)serialisation.
 from __future__ import annotations
 
 import ctypes
+import os
 
 import numpy as np
 
@@ -458,6 +459,22 @@ class RangeProof:
             raise VerificationError("VerificationError")
 
 
+STAGES = ("from_wire", "verify_scalars", "fixed_msm", "var_msm", "finalize")
+
+
+def _weight_key_arg(weight_key, d_weights):
+    """The weighted checks' key argument: None when the weights come from d_weights, else 32 bytes (weight_key None = drawn
+    here from os.urandom, fresh per call)."""
+    if d_weights:
+        return None
+    if weight_key is None:
+        weight_key = os.urandom(32)
+    key = bytes(weight_key)
+    if len(key) != 32:
+        raise ValueError("weight_key must be 32 bytes")
+    return key
+
+
 class BatchVerifier:
     """Device-resident batch verification of independent proofs for one (pk, n, m).
 
@@ -556,15 +573,10 @@ class BatchVerifier:
         """verify_serialized_device with the grouped check behind the decoder (include/bpp_amd.h): the same status words at the
         grouped check's price when (nearly) every proof is valid.  weight_key: 32 secret bytes, None = os.urandom(32).
         Synchronises the stream.  -> (groups that failed, proofs re-verified exactly)"""
-        if weight_key is None:
-            import os
-            weight_key = os.urandom(32)
-        key = bytes(weight_key)
-        if len(key) != 32:
-            raise ValueError("weight_key must be 32 bytes")
         stats = (ctypes.c_uint64 * 2)()
         check(_lib.lib().bpp_range_verify_batch_serialized_grouped_device(
-            self.handle, d_proofs, d_commitments, count, (1 if transcript else 0) | (2 if uncompressed else 0), key,
+            self.handle, d_proofs, d_commitments, count, (1 if transcript else 0) | (2 if uncompressed else 0),
+            _weight_key_arg(weight_key, 0),
             ctypes.c_uint64(index_base), group, d_ok, stats, d_workspace, workspace_bytes, stream or None),
             "bpp_range_verify_batch_serialized_grouped_device")
         return int(stats[0]), int(stats[1])
@@ -574,6 +586,147 @@ class BatchVerifier:
         check(_lib.lib().bpp_verifier_run(self.handle, d_points, d_scalars, count, d_challenges or None, d_ok,
                                           d_workspace, workspace_bytes, d_out_scalars or None, d_out_result or None,
                                           stream or None), "bpp_verifier_run")
+
+    def graph_capture(self, d_points: int, d_scalars: int, count: int, d_ok: int, d_workspace: int, workspace_bytes: int,
+                      d_challenges: int = 0) -> PassGraph:
+        h = ctypes.c_void_p()
+        check(_lib.lib().bpp_verifier_graph_capture(self.handle, d_points, d_scalars, count, d_challenges or None, d_ok,
+                                                    d_workspace, workspace_bytes, ctypes.byref(h)),
+              "bpp_verifier_graph_capture")
+        return PassGraph(h)
+
+    def set_subgroup_check(self, on: bool):
+        """wire points outside the prime-order subgroup count as invalid points (include/bpp_amd.h); off by default"""
+        check(_lib.lib().bpp_verifier_set_subgroup_check(self.handle, 1 if on else 0), "bpp_verifier_set_subgroup_check")
+
+    def set_profiling(self, on: bool):
+        check(_lib.lib().bpp_verifier_set_profiling(self.handle, 1 if on else 0), "bpp_verifier_set_profiling")
+
+    def profile(self):
+        """-> ({stage: mean ms}, passes, blocks_per_proof of k_fixed_msm), HIP events on the launch stream"""
+        ms = (ctypes.c_float * 5)()
+        passes = ctypes.c_size_t()
+        bpp_ = ctypes.c_uint()
+        check(_lib.lib().bpp_verifier_profile(self.handle, ms, ctypes.byref(passes), ctypes.byref(bpp_)),
+              "bpp_verifier_profile")
+        return {k: float(ms[i]) for i, k in enumerate(STAGES)}, passes.value, bpp_.value
+
+    def partial_bytes(self) -> int:
+        return _lib.lib().bpp_verifier_partial_bytes(self.handle)
+
+    def combined_workspace_bytes(self, count: int) -> int:
+        return _lib.lib().bpp_verifier_combined_workspace_bytes(self.handle, count)
+
+    def run_combined_device(self, d_points: int, d_scalars: int, count: int, weight_key, index_base: int,
+                            d_out_partial: int, d_ok: int, d_workspace: int, workspace_bytes: int, stream: int = 0,
+                            d_challenges: int = 0, d_weights: int = 0):
+        """Combined batch check (NOT the reference's per-proof semantics, see include/bpp_amd.h): one weighted
+        sum of the batch's verification MulVecs.  d_ok[0] == 0 iff it is the identity.
+        weight_key: 32 secret bytes (None = drawn here from os.urandom, fresh per call) expanded on the device by a
+        SHA-256 PRF over the global proof index index_base + p; or d_weights: count x 16 bytes on the device."""
+        check(_lib.lib().bpp_verifier_run_combined(self.handle, d_points, d_scalars, count, d_challenges or None,
+                                                   _weight_key_arg(weight_key, d_weights), ctypes.c_uint64(index_base),
+                                                   d_weights or None, d_out_partial, d_ok, d_workspace, workspace_bytes,
+                                                   stream or None),
+              "bpp_verifier_run_combined")
+
+    def grouped_workspace_bytes(self, count: int, group: int = 32) -> int:
+        return _lib.lib().bpp_verifier_grouped_workspace_bytes(self.handle, count, group)
+
+    def run_grouped_device(self, d_points: int, d_scalars: int, count: int, weight_key, index_base: int,
+                           d_out_verdicts: int, d_workspace: int, workspace_bytes: int, group: int = 32,
+                           stream: int = 0, d_challenges: int = 0, d_weights: int = 0):
+        """Per-proof verdicts (the vector run_device writes) from one weighted check per group of `group` neighbouring proofs
+        and an exact pass over the proofs of the groups that fail (include/bpp_amd.h "grouped check"; an engine mode, not a
+        reference path).  weight_key / d_weights as for run_combined_device.  Synchronises the stream.
+        Returns (groups that failed, proofs re-verified exactly)."""
+        stats = (ctypes.c_uint64 * 2)()
+        check(_lib.lib().bpp_verifier_run_grouped(self.handle, d_points, d_scalars, count, d_challenges or None,
+                                                  _weight_key_arg(weight_key, d_weights), ctypes.c_uint64(index_base),
+                                                  d_weights or None, group, d_out_verdicts, stats, d_workspace,
+                                                  workspace_bytes, stream or None),
+              "bpp_verifier_run_grouped")
+        return int(stats[0]), int(stats[1])
+
+    def grouped_begin_device(self, d_points: int, d_scalars: int, count: int, weight_key, index_base: int,
+                             d_out_verdicts: int, d_workspace: int, workspace_bytes: int, group: int = 32, stream: int = 0,
+                             d_challenges: int = 0, d_weights: int = 0):
+        """First half of run_grouped_device: enqueues the weighted checks of the groups and returns (nothing synchronises)."""
+        check(_lib.lib().bpp_verifier_grouped_begin(self.handle, d_points, d_scalars, count, d_challenges or None,
+                                                    _weight_key_arg(weight_key, d_weights), ctypes.c_uint64(index_base),
+                                                    d_weights or None, group, d_out_verdicts, d_workspace, workspace_bytes,
+                                                    stream or None), "bpp_verifier_grouped_begin")
+
+    def grouped_finish_device(self, d_points: int, d_scalars: int, count: int, d_out_verdicts: int, d_workspace: int,
+                              workspace_bytes: int, group: int = 32, stream: int = 0, d_challenges: int = 0):
+        """Second half: same buffers, count, group and stream as the begin it completes; synchronises the stream.
+        -> (groups that failed, proofs re-verified exactly)"""
+        stats = (ctypes.c_uint64 * 2)()
+        check(_lib.lib().bpp_verifier_grouped_finish(self.handle, d_points, d_scalars, count, d_challenges or None, group,
+                                                     d_out_verdicts, stats, d_workspace, workspace_bytes, stream or None),
+              "bpp_verifier_grouped_finish")
+        return int(stats[0]), int(stats[1])
+
+    def derive_challenges_device(self, d_points: int, count: int, d_challenges: int, stream: int = 0):
+        """Fiat-Shamir challenges [y, z, e, e_1..e_k] of every proof record of a resident batch (csrc/transcript.hpp),
+        in the layout run_device takes as d_challenges.  The reference has no transcript: parity unpinned."""
+        check(_lib.lib().bpp_verifier_derive_challenges(self.handle, d_points, count, d_challenges, stream or None),
+              "bpp_verifier_derive_challenges")
+
+    def sum_partials_device(self, d_partials: int, n: int, d_ok: int, stream: int = 0):
+        check(_lib.lib().bpp_verifier_sum_partials(self.handle, d_partials, n, d_ok, stream or None),
+              "bpp_verifier_sum_partials")
+
+    def prove_batch(self, values, gammas, transcript: bool = False, blind_key: bytes = None, index_base: int = 0):
+        """RangeProof::prove + RangeProver::commit for `count` provers sharing this engine's (pk, n, m).
+        transcript=True: challenges from the Fiat-Shamir transcript (csrc/transcript.hpp) instead of the reference's
+        constants -- not a reference code path, parity unpinned.  blind_key (32 secret bytes, transcript mode only): the
+        blinding values come from this key (include/bpp_amd.h "Blinding"); None = the reference's literals, which hide nothing.
+        values: (count, m) ints < 2^64 ; gammas: (count, m) scalars (ints or (count, m, 4) uint64).
+        Returns (points (count, 3+2k, PW), scalars (count, 3, 4), V (count, m, PW)) in wire format --
+        bit-identical to RangeProof.prove / RangeProver.commit one by one."""
+        vals = np.ascontiguousarray(np.asarray(values, dtype=np.uint64).reshape(-1, self.m))
+        count = vals.shape[0]
+        if isinstance(gammas, np.ndarray) and gammas.dtype == np.uint64 and gammas.ndim == 3:
+            gm = np.ascontiguousarray(gammas)
+        else:
+            gm = np.zeros((count, self.m, 4), dtype=np.uint64)
+            for i, row in enumerate(gammas):
+                for j, g in enumerate(row):
+                    gm[i, j] = scalar_to_wire(g)
+        PW = self.arith.PW
+        pts = np.zeros((count, 3 + 2 * self.k, PW), dtype=np.uint64)
+        sc = np.zeros((count, 3, 4), dtype=np.uint64)
+        V = np.zeros((count, self.m, PW), dtype=np.uint64)
+        if blind_key is not None and (not transcript or len(blind_key) != 32):
+            raise ValueError("blind_key: 32 bytes, transcript mode only")
+        if transcript:
+            check(_lib.lib().bpp_range_prove_batch_fs(self.handle, _ptr(vals), _ptr(gm), count, blind_key, index_base,
+                                                      _ptr(pts), _ptr(sc), _ptr(V)), "bpp_range_prove_batch_fs")
+        else:
+            check(_lib.lib().bpp_range_prove_batch(self.handle, _ptr(vals), _ptr(gm), count, _ptr(pts), _ptr(sc), _ptr(V)),
+                  "bpp_range_prove_batch")
+        return pts, sc, V
+
+    def prover_workspace_bytes(self, count: int) -> int:
+        return _lib.lib().bpp_prover_workspace_bytes(self.handle, count)
+
+    def prove_batch_device(self, d_values: int, d_gammas: int, count: int, d_out_points: int, d_out_scalars: int,
+                           d_out_V: int, d_workspace: int, workspace_bytes: int, stream: int = 0,
+                           transcript: bool = False, d_out_challenges: int = 0, blind_key: bytes = None,
+                           index_base: int = 0, d_blinding: int = 0):
+        """prove_batch with every buffer in HBM (raw device pointers), asynchronous on `stream`.  Transcript mode: blinding
+        from blind_key (32 bytes) / d_blinding (count x (5 + 2k) scalars on the device), else the reference's literals."""
+        if transcript:
+            check(_lib.lib().bpp_range_prove_batch_fs_device(self.handle, d_values, d_gammas, count, blind_key, index_base,
+                                                             d_blinding or None, d_out_points,
+                                                             d_out_scalars, d_out_V or None, d_out_challenges or None,
+                                                             d_workspace, workspace_bytes, stream or None),
+                  "bpp_range_prove_batch_fs_device")
+            return
+        check(_lib.lib().bpp_range_prove_batch_device(self.handle, d_values, d_gammas, count, d_out_points, d_out_scalars,
+                                                      d_out_V or None, d_workspace, workspace_bytes, stream or None),
+              "bpp_range_prove_batch_device")
 
 
 class PassGraph:
@@ -596,206 +749,6 @@ class PassGraph:
             self.close()
         except Exception:
             pass
-
-
-def _verifier_graph_capture(self, d_points: int, d_scalars: int, count: int, d_ok: int, d_workspace: int, workspace_bytes: int,
-                            d_challenges: int = 0) -> PassGraph:
-    h = ctypes.c_void_p()
-    check(_lib.lib().bpp_verifier_graph_capture(self.handle, d_points, d_scalars, count, d_challenges or None, d_ok, d_workspace,
-                                                workspace_bytes, ctypes.byref(h)), "bpp_verifier_graph_capture")
-    return PassGraph(h)
-
-
-STAGES = ("from_wire", "verify_scalars", "fixed_msm", "var_msm", "finalize")
-
-
-def _verifier_set_profiling(self, on: bool):
-    check(_lib.lib().bpp_verifier_set_profiling(self.handle, 1 if on else 0), "bpp_verifier_set_profiling")
-
-
-def _verifier_profile(self):
-    """-> ({stage: mean ms}, passes, blocks_per_proof of k_fixed_msm), HIP events on the launch stream"""
-    ms = (ctypes.c_float * 5)()
-    passes = ctypes.c_size_t()
-    bpp_ = ctypes.c_uint()
-    check(_lib.lib().bpp_verifier_profile(self.handle, ms, ctypes.byref(passes), ctypes.byref(bpp_)),
-          "bpp_verifier_profile")
-    return {k: float(ms[i]) for i, k in enumerate(STAGES)}, passes.value, bpp_.value
-
-
-def _verifier_partial_bytes(self) -> int:
-    return _lib.lib().bpp_verifier_partial_bytes(self.handle)
-
-
-def _verifier_combined_workspace_bytes(self, count: int) -> int:
-    return _lib.lib().bpp_verifier_combined_workspace_bytes(self.handle, count)
-
-
-def _verifier_run_combined_device(self, d_points: int, d_scalars: int, count: int, weight_key, index_base: int,
-                                  d_out_partial: int, d_ok: int, d_workspace: int, workspace_bytes: int, stream: int = 0,
-                                  d_challenges: int = 0, d_weights: int = 0):
-    """Combined batch check (NOT the reference's per-proof semantics, see include/bpp_amd.h): one weighted
-    sum of the batch's verification MulVecs.  d_ok[0] == 0 iff it is the identity.
-    weight_key: 32 secret bytes (None = drawn here from os.urandom, fresh per call) expanded on the device by a
-    SHA-256 PRF over the global proof index index_base + p; or d_weights: count x 16 bytes on the device."""
-    if d_weights:
-        key = None
-    else:
-        if weight_key is None:
-            import os
-            weight_key = os.urandom(32)
-        key = bytes(weight_key)
-        if len(key) != 32:
-            raise ValueError("weight_key must be 32 bytes")
-    check(_lib.lib().bpp_verifier_run_combined(self.handle, d_points, d_scalars, count, d_challenges or None, key,
-                                               ctypes.c_uint64(index_base), d_weights or None, d_out_partial, d_ok,
-                                               d_workspace, workspace_bytes, stream or None),
-          "bpp_verifier_run_combined")
-
-
-def _verifier_grouped_workspace_bytes(self, count: int, group: int = 32) -> int:
-    return _lib.lib().bpp_verifier_grouped_workspace_bytes(self.handle, count, group)
-
-
-def _verifier_run_grouped_device(self, d_points: int, d_scalars: int, count: int, weight_key, index_base: int,
-                                 d_out_verdicts: int, d_workspace: int, workspace_bytes: int, group: int = 32,
-                                 stream: int = 0, d_challenges: int = 0, d_weights: int = 0):
-    """Per-proof verdicts (the vector run_device writes) from one weighted check per group of `group` neighbouring proofs
-    and an exact pass over the proofs of the groups that fail (include/bpp_amd.h "grouped check"; an engine mode, not a
-    reference path).  weight_key / d_weights as for run_combined_device.  Synchronises the stream.
-    Returns (groups that failed, proofs re-verified exactly)."""
-    if d_weights:
-        key = None
-    else:
-        if weight_key is None:
-            import os
-            weight_key = os.urandom(32)
-        key = bytes(weight_key)
-        if len(key) != 32:
-            raise ValueError("weight_key must be 32 bytes")
-    stats = (ctypes.c_uint64 * 2)()
-    check(_lib.lib().bpp_verifier_run_grouped(self.handle, d_points, d_scalars, count, d_challenges or None, key,
-                                              ctypes.c_uint64(index_base), d_weights or None, group, d_out_verdicts, stats,
-                                              d_workspace, workspace_bytes, stream or None),
-          "bpp_verifier_run_grouped")
-    return int(stats[0]), int(stats[1])
-
-
-def _verifier_grouped_begin_device(self, d_points: int, d_scalars: int, count: int, weight_key, index_base: int,
-                                   d_out_verdicts: int, d_workspace: int, workspace_bytes: int, group: int = 32, stream: int = 0,
-                                   d_challenges: int = 0, d_weights: int = 0):
-    """First half of run_grouped_device: enqueues the weighted checks of the groups and returns (nothing synchronises)."""
-    key = None
-    if not d_weights:
-        if weight_key is None:
-            import os
-            weight_key = os.urandom(32)
-        key = bytes(weight_key)
-        if len(key) != 32:
-            raise ValueError("weight_key must be 32 bytes")
-    check(_lib.lib().bpp_verifier_grouped_begin(self.handle, d_points, d_scalars, count, d_challenges or None, key,
-                                                ctypes.c_uint64(index_base), d_weights or None, group, d_out_verdicts,
-                                                d_workspace, workspace_bytes, stream or None), "bpp_verifier_grouped_begin")
-
-
-def _verifier_grouped_finish_device(self, d_points: int, d_scalars: int, count: int, d_out_verdicts: int, d_workspace: int,
-                                    workspace_bytes: int, group: int = 32, stream: int = 0, d_challenges: int = 0):
-    """Second half: same buffers, count, group and stream as the begin it completes; synchronises the stream.
-    -> (groups that failed, proofs re-verified exactly)"""
-    stats = (ctypes.c_uint64 * 2)()
-    check(_lib.lib().bpp_verifier_grouped_finish(self.handle, d_points, d_scalars, count, d_challenges or None, group,
-                                                 d_out_verdicts, stats, d_workspace, workspace_bytes, stream or None),
-          "bpp_verifier_grouped_finish")
-    return int(stats[0]), int(stats[1])
-
-
-def _verifier_derive_challenges_device(self, d_points: int, count: int, d_challenges: int, stream: int = 0):
-    """Fiat-Shamir challenges [y, z, e, e_1..e_k] of every proof record of a resident batch (csrc/transcript.hpp),
-    in the layout run_device takes as d_challenges.  The reference has no transcript: parity unpinned."""
-    check(_lib.lib().bpp_verifier_derive_challenges(self.handle, d_points, count, d_challenges, stream or None),
-          "bpp_verifier_derive_challenges")
-
-
-def _verifier_sum_partials_device(self, d_partials: int, n: int, d_ok: int, stream: int = 0):
-    check(_lib.lib().bpp_verifier_sum_partials(self.handle, d_partials, n, d_ok, stream or None),
-          "bpp_verifier_sum_partials")
-
-
-def _engine_prove_batch(self, values, gammas, transcript: bool = False, blind_key: bytes = None, index_base: int = 0):
-    """RangeProof::prove + RangeProver::commit for `count` provers sharing this engine's (pk, n, m).
-    transcript=True: challenges from the Fiat-Shamir transcript (csrc/transcript.hpp) instead of the reference's
-    constants -- not a reference code path, parity unpinned.  blind_key (32 secret bytes, transcript mode only): the
-    blinding values come from this key (include/bpp_amd.h "Blinding"); None = the reference's literals, which hide nothing.
-    values: (count, m) ints < 2^64 ; gammas: (count, m) scalars (ints or (count, m, 4) uint64).
-    Returns (points (count, 3+2k, PW), scalars (count, 3, 4), V (count, m, PW)) in wire format --
-    bit-identical to RangeProof.prove / RangeProver.commit one by one."""
-    vals = np.ascontiguousarray(np.asarray(values, dtype=np.uint64).reshape(-1, self.m))
-    count = vals.shape[0]
-    if isinstance(gammas, np.ndarray) and gammas.dtype == np.uint64 and gammas.ndim == 3:
-        gm = np.ascontiguousarray(gammas)
-    else:
-        gm = np.zeros((count, self.m, 4), dtype=np.uint64)
-        for i, row in enumerate(gammas):
-            for j, g in enumerate(row):
-                gm[i, j] = scalar_to_wire(g)
-    PW = self.arith.PW
-    pts = np.zeros((count, 3 + 2 * self.k, PW), dtype=np.uint64)
-    sc = np.zeros((count, 3, 4), dtype=np.uint64)
-    V = np.zeros((count, self.m, PW), dtype=np.uint64)
-    if blind_key is not None and (not transcript or len(blind_key) != 32):
-        raise ValueError("blind_key: 32 bytes, transcript mode only")
-    if transcript:
-        check(_lib.lib().bpp_range_prove_batch_fs(self.handle, _ptr(vals), _ptr(gm), count, blind_key, index_base, _ptr(pts),
-                                                  _ptr(sc), _ptr(V)), "bpp_range_prove_batch_fs")
-    else:
-        check(_lib.lib().bpp_range_prove_batch(self.handle, _ptr(vals), _ptr(gm), count, _ptr(pts), _ptr(sc), _ptr(V)),
-              "bpp_range_prove_batch")
-    return pts, sc, V
-
-
-def _engine_prover_workspace_bytes(self, count: int) -> int:
-    return _lib.lib().bpp_prover_workspace_bytes(self.handle, count)
-
-
-def _engine_prove_batch_device(self, d_values: int, d_gammas: int, count: int, d_out_points: int, d_out_scalars: int,
-                               d_out_V: int, d_workspace: int, workspace_bytes: int, stream: int = 0,
-                               transcript: bool = False, d_out_challenges: int = 0, blind_key: bytes = None,
-                               index_base: int = 0, d_blinding: int = 0):
-    """prove_batch with every buffer in HBM (raw device pointers), asynchronous on `stream`.  Transcript mode: blinding
-    from blind_key (32 bytes) / d_blinding (count x (5 + 2k) scalars on the device), else the reference's literals."""
-    if transcript:
-        check(_lib.lib().bpp_range_prove_batch_fs_device(self.handle, d_values, d_gammas, count, blind_key, index_base,
-                                                         d_blinding or None, d_out_points,
-                                                         d_out_scalars, d_out_V or None, d_out_challenges or None,
-                                                         d_workspace, workspace_bytes, stream or None),
-              "bpp_range_prove_batch_fs_device")
-        return
-    check(_lib.lib().bpp_range_prove_batch_device(self.handle, d_values, d_gammas, count, d_out_points, d_out_scalars,
-                                                  d_out_V or None, d_workspace, workspace_bytes, stream or None),
-          "bpp_range_prove_batch_device")
-
-
-BatchVerifier.prove_batch = _engine_prove_batch
-BatchVerifier.prover_workspace_bytes = _engine_prover_workspace_bytes
-BatchVerifier.prove_batch_device = _engine_prove_batch_device
-BatchVerifier.partial_bytes = _verifier_partial_bytes
-BatchVerifier.combined_workspace_bytes = _verifier_combined_workspace_bytes
-BatchVerifier.run_combined_device = _verifier_run_combined_device
-BatchVerifier.grouped_workspace_bytes = _verifier_grouped_workspace_bytes
-BatchVerifier.run_grouped_device = _verifier_run_grouped_device
-BatchVerifier.grouped_begin_device = _verifier_grouped_begin_device
-BatchVerifier.grouped_finish_device = _verifier_grouped_finish_device
-BatchVerifier.derive_challenges_device = _verifier_derive_challenges_device
-BatchVerifier.sum_partials_device = _verifier_sum_partials_device
-def _verifier_set_subgroup_check(self, on: bool):
-    """wire points outside the prime-order subgroup count as invalid points (include/bpp_amd.h); off by default"""
-    check(_lib.lib().bpp_verifier_set_subgroup_check(self.handle, 1 if on else 0), "bpp_verifier_set_subgroup_check")
-
-
-BatchVerifier.set_subgroup_check = _verifier_set_subgroup_check
-BatchVerifier.graph_capture = _verifier_graph_capture
-BatchVerifier.set_profiling = _verifier_set_profiling
-BatchVerifier.profile = _verifier_profile
 
 
 def proof_record(proof: RangeProof, commitment_vec) -> np.ndarray:

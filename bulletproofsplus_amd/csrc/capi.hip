@@ -8,6 +8,59 @@
 
 using namespace bpp;
 
+namespace {
+// The entry shim: the calls of a context -- or of a verifier, through its copy v->ctx -- run on its device (a verifier's
+// launches must go to the device that holds its tables), then f(curve tag) on the curve's implementation.
+template <class F>
+int on_ctx(const bpp_ctx& ctx, F&& f) {
+    HIPCHK(hipSetDevice(ctx.device));
+    return dispatch(ctx.curve, f);
+}
+// the size getters: f(curve tag), or 0 for a null handle
+template <class F>
+size_t size_for(const bpp_ctx* ctx, F&& f) {
+    size_t r = 0;
+    if (ctx)
+        dispatch(ctx->curve, [&](auto cv) -> int {
+            r = f(cv);
+            return 0;
+        });
+    return r;
+}
+template <class F>
+size_t size_for(const bpp_verifier* v, F&& f) {
+    return size_for(v ? &v->ctx : nullptr, f);
+}
+// mean milliseconds per stage over the first `passes` passes of an event ring: pass p's stage t runs from
+// ev[p * per_pass + t * step] to the event after it
+int stage_means(const hipEvent_t* ev, size_t passes, size_t per_pass, int stages, int step, float* out_ms) {
+    for (int t = 0; t < stages; t++) out_ms[t] = 0.f;
+    for (size_t p = 0; p < passes; p++)
+        for (int t = 0; t < stages; t++) {
+            const hipEvent_t* e = ev + p * per_pass + t * step;
+            HIPCHK(hipEventSynchronize(e[1]));
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, e[0], e[1]));
+            out_ms[t] += ms;
+        }
+    for (int t = 0; t < stages; t++) out_ms[t] = passes ? out_ms[t] / (float)passes : 0.f;
+    return BPP_OK;
+}
+// canonical (< group order) 32-byte little-endian scalar?
+bool scalar_is_canonical(int curve, const uint8_t* b) {
+    bool lt = false;
+    dispatch(curve, [&](auto cv) -> int {
+        using Fr = typename decltype(cv)::Fr;
+        uint32_t w[8];
+        for (int i = 0; i < 8; i++)
+            w[i] = (uint32_t)b[4 * i] | ((uint32_t)b[4 * i + 1] << 8) | ((uint32_t)b[4 * i + 2] << 16) | ((uint32_t)b[4 * i + 3] << 24);
+        lt = words_lt_mod<Fr>(w);
+        return 0;
+    });
+    return lt;
+}
+}  // namespace
+
 extern "C" const char* bpp_last_error(void) { return g_err.c_str(); }
 
 extern "C" int bpp_init(int curve_id, int device, bpp_ctx** out_ctx) {
@@ -84,8 +137,7 @@ extern "C" int bpp_point_words(int curve_id) {
 extern "C" int bpp_msm_batch(bpp_ctx* ctx, const uint64_t* scalars, const uint64_t* points, const uint32_t* lens,
                              size_t count, uint64_t* out) {
     if (!ctx || !out || (count && !lens)) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    return dispatch(ctx->curve, [&](auto cv) -> int {
+    return on_ctx(*ctx, [&](auto cv) -> int {
         return MsmImpl<decltype(cv)>::msm_batch(scalars, points, lens, count, out);
     });
 }
@@ -99,28 +151,20 @@ extern "C" int bpp_msm(bpp_ctx* ctx, const uint64_t* scalars, const uint64_t* po
 extern "C" int bpp_msm_pippenger(bpp_ctx* ctx, const uint64_t* scalars, const uint64_t* points, size_t n,
                                  int window_bits, uint64_t* out) {
     if (!ctx || !out || (n && (!scalars || !points))) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    return dispatch(ctx->curve, [&](auto cv) -> int {
+    return on_ctx(*ctx, [&](auto cv) -> int {
         return MsmImpl<decltype(cv)>::msm_pippenger(scalars, points, n, window_bits, out);
     });
 }
 
 extern "C" size_t bpp_msm_workspace_bytes(bpp_ctx* ctx, size_t n, int window_bits) {
-    if (!ctx) return 0;
-    size_t r = 0;
-    dispatch(ctx->curve, [&](auto cv) -> int {
-        r = MsmImpl<decltype(cv)>::msm_workspace_bytes(n, window_bits);
-        return 0;
-    });
-    return r;
+    return size_for(ctx, [&](auto cv) { return MsmImpl<decltype(cv)>::msm_workspace_bytes(n, window_bits); });
 }
 
 extern "C" int bpp_msm_device(bpp_ctx* ctx, const uint64_t* d_scalars, const uint64_t* d_points, size_t n, int window_bits,
                               uint64_t* d_out, uint32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream) {
     if (!ctx || !d_out || !d_workspace || (n && (!d_scalars || !d_points))) return fail(BPP_E_ARG, "null argument");
     if (window_bits && (window_bits < 2 || window_bits > 16)) return fail(BPP_E_ARG, "window_bits must be in [2, 16]");
-    HIPCHK(hipSetDevice(ctx->device));
-    return dispatch(ctx->curve, [&](auto cv) -> int {
+    return on_ctx(*ctx, [&](auto cv) -> int {
         return MsmImpl<decltype(cv)>::msm_device(reinterpret_cast<const uint32_t*>(d_scalars),
                                                  reinterpret_cast<const uint32_t*>(d_points), n, window_bits,
                                                  reinterpret_cast<uint32_t*>(d_out), d_status, d_workspace, workspace_bytes,
@@ -144,17 +188,8 @@ extern "C" int bpp_msm_profile(bpp_ctx* ctx, float* out_stage_ms, size_t* out_pa
     if (!ctx || !out_stage_ms) return fail(BPP_E_ARG, "null argument");
     HIPCHK(hipSetDevice(ctx->device));
     const size_t np = std::min<size_t>(ctx->msm_passes, BPP_MSM_SLOTS);
-    for (int t = 0; t < PIP_STAGES; t++) out_stage_ms[t] = 0.f;
-    for (size_t p = 0; p < np; p++) {
-        hipEvent_t* ev = ctx->msm_events.data() + p * (PIP_STAGES + 1);
-        for (int t = 0; t < PIP_STAGES; t++) {
-            HIPCHK(hipEventSynchronize(ev[t + 1]));
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, ev[t], ev[t + 1]));
-            out_stage_ms[t] += ms;
-        }
-    }
-    for (int t = 0; t < PIP_STAGES; t++) out_stage_ms[t] = np ? out_stage_ms[t] / (float)np : 0.f;
+    int rc = stage_means(ctx->msm_events.data(), np, PIP_STAGES + 1, PIP_STAGES, 1, out_stage_ms);
+    if (rc) return rc;
     if (out_passes) *out_passes = np;
     if (out_shape) std::memcpy(out_shape, ctx->msm_shape, sizeof ctx->msm_shape);
     return BPP_OK;
@@ -163,16 +198,14 @@ extern "C" int bpp_msm_profile(bpp_ctx* ctx, float* out_stage_ms, size_t* out_pa
 extern "C" int bpp_scalar_mul_batch(bpp_ctx* ctx, const uint64_t* scalars, const uint64_t* points, size_t n,
                                     uint64_t* out) {
     if (!ctx || !out || (n && (!scalars || !points))) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    return dispatch(ctx->curve, [&](auto cv) -> int {
+    return on_ctx(*ctx, [&](auto cv) -> int {
         return MsmImpl<decltype(cv)>::scalar_mul_batch(scalars, points, n, out);
     });
 }
 
 extern "C" int bpp_pk_new(bpp_ctx* ctx, size_t length, uint64_t* out_gh, uint64_t* out_G, uint64_t* out_H) {
     if (!ctx || !out_gh || (length && (!out_G || !out_H))) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    return dispatch(ctx->curve, [&](auto cv) -> int {
+    return on_ctx(*ctx, [&](auto cv) -> int {
         return MsmImpl<decltype(cv)>::pk_new(length, out_gh, out_G, out_H);
     });
 }
@@ -181,16 +214,14 @@ extern "C" int bpp_pk_hashed(bpp_ctx* ctx, const uint8_t* label, size_t label_le
                              uint64_t* out_G, uint64_t* out_H) {
     if (!ctx || !out_gh || (label_len && !label) || (length && (!out_G || !out_H))) return fail(BPP_E_ARG, "null argument");
     if (length > (1u << 24)) return fail(BPP_E_ARG, "length too large");
-    HIPCHK(hipSetDevice(ctx->device));
-    return dispatch(ctx->curve, [&](auto cv) -> int {
+    return on_ctx(*ctx, [&](auto cv) -> int {
         return MsmImpl<decltype(cv)>::pk_hashed(label, label_len, length, out_gh, out_G, out_H);
     });
 }
 
 extern "C" int bpp_commit(bpp_ctx* ctx, const uint64_t* gh, uint64_t v, const uint64_t* gamma, uint64_t* out) {
     if (!ctx || !gh || !gamma || !out) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    return dispatch(ctx->curve, [&](auto cv) -> int { return MsmImpl<decltype(cv)>::commit(gh, v, gamma, out); });
+    return on_ctx(*ctx, [&](auto cv) -> int { return MsmImpl<decltype(cv)>::commit(gh, v, gamma, out); });
 }
 
 // The cached engine of a public key, or null when the call has to take the table-free path: first sight of the key (it
@@ -323,8 +354,7 @@ extern "C" int bpp_range_prove(bpp_ctx* ctx, const uint64_t* gh, const uint64_t*
 extern "C" int bpp_wip_fold_round(bpp_ctx* ctx, uint64_t* a, uint64_t* b, uint64_t* G, uint64_t* H, size_t len,
                                   const uint64_t* y_nhat, const uint64_t* e) {
     if (!ctx || !a || !b || !G || !H || !y_nhat || !e) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    return dispatch(ctx->curve, [&](auto cv) -> int {
+    return on_ctx(*ctx, [&](auto cv) -> int {
         return ProveImpl<decltype(cv)>::wip_fold_round(a, b, G, H, len, y_nhat, e);
     });
 }
@@ -333,21 +363,14 @@ extern "C" int bpp_wip_fold_round(bpp_ctx* ctx, uint64_t* a, uint64_t* b, uint64
 extern "C" int bpp_verifier_create(bpp_ctx* ctx, const uint64_t* gh, const uint64_t* G, const uint64_t* H, size_t n,
                                    size_t m, int window_bits, bpp_verifier** out) {
     if (!ctx || !gh || !G || !H || !out) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    return dispatch(ctx->curve, [&](auto cv) -> int {
+    return on_ctx(*ctx, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::create(*ctx, gh, G, H, n, m, window_bits, out);
     });
 }
 extern "C" void bpp_verifier_destroy(bpp_verifier* v) { delete v; }
 
 extern "C" size_t bpp_verifier_workspace_bytes(const bpp_verifier* v, size_t count) {
-    if (!v) return 0;
-    size_t r = 0;
-    dispatch(v->ctx.curve, [&](auto cv) -> int {
-        r = VerifyImpl<decltype(cv)>::ws_layout(v->s, count).total;
-        return 0;
-    });
-    return r;
+    return size_for(v, [&](auto cv) { return VerifyImpl<decltype(cv)>::ws_layout(v->s, count).total; });
 }
 extern "C" size_t bpp_verifier_msm_len(const bpp_verifier* v) { return v ? v->s.N : 0; }
 extern "C" size_t bpp_verifier_table_bytes(const bpp_verifier* v) { return v ? v->table_bytes : 0; }
@@ -360,8 +383,7 @@ extern "C" int bpp_verifier_run(bpp_verifier* v, const uint64_t* d_points, const
     if (!v || !d_points || !d_scalars || !d_ok || !d_workspace) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
     if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
-    HIPCHK(hipSetDevice(v->ctx.device));   // the launches must go to the device that holds this verifier's tables
-    return dispatch(v->ctx.curve, [&](auto cv) -> int {
+    return on_ctx(v->ctx, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::run(v, d_points, d_scalars, count, d_challenges, d_ok, d_workspace,
                                              workspace_bytes, d_out_scalars, d_out_result,
                                              static_cast<hipStream_t>(stream));
@@ -431,8 +453,7 @@ extern "C" int bpp_range_prove_batch(bpp_verifier* engine, const uint64_t* v, co
                                      uint64_t* out_points, uint64_t* out_scalars, uint64_t* out_V) {
     if (!engine || !v || !gamma || !out_points || !out_scalars) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
-    HIPCHK(hipSetDevice(engine->ctx.device));
-    return dispatch(engine->ctx.curve, [&](auto cv) -> int {
+    return on_ctx(engine->ctx, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::prove_batch(engine, v, gamma, count, out_points, out_scalars, out_V, false);
     });
 }
@@ -442,44 +463,27 @@ extern "C" int bpp_range_prove_batch_fs(bpp_verifier* engine, const uint64_t* v,
                                         uint64_t* out_scalars, uint64_t* out_V) {
     if (!engine || !v || !gamma || !out_points || !out_scalars) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
-    HIPCHK(hipSetDevice(engine->ctx.device));
-    return dispatch(engine->ctx.curve, [&](auto cv) -> int {
+    return on_ctx(engine->ctx, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::prove_batch(engine, v, gamma, count, out_points, out_scalars, out_V, true, blind_key,
                                                      index_base);
     });
 }
 
 extern "C" size_t bpp_prover_workspace_bytes(const bpp_verifier* engine, size_t count) {
-    if (!engine) return 0;
-    size_t r = 0;
-    dispatch(engine->ctx.curve, [&](auto cv) -> int {
-        r = VerifyImpl<decltype(cv)>::prove_layout(engine->s, count).total;
-        return 0;
-    });
-    return r;
-}
-
-static int prove_batch_device_common(bpp_verifier* engine, const uint64_t* d_v, const uint64_t* d_gamma, size_t count,
-                                     uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_V, bool fs,
-                                     uint64_t* d_out_challenges, void* d_workspace, size_t workspace_bytes, void* stream,
-                                     const uint8_t* blind_key = nullptr, uint64_t index_base = 0,
-                                     const uint64_t* d_blinding = nullptr) {
-    if (!engine || !d_v || !d_gamma || !d_out_points || !d_out_scalars || !d_workspace)
-        return fail(BPP_E_ARG, "null argument");
-    if (count == 0) return BPP_OK;
-    HIPCHK(hipSetDevice(engine->ctx.device));
-    return dispatch(engine->ctx.curve, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::prove_batch_device(engine, d_v, d_gamma, count, d_out_points, d_out_scalars,
-                                                            d_out_V, fs, d_out_challenges, d_workspace, workspace_bytes,
-                                                            static_cast<hipStream_t>(stream), blind_key, index_base, d_blinding);
-    });
+    return size_for(engine, [&](auto cv) { return VerifyImpl<decltype(cv)>::prove_layout(engine->s, count).total; });
 }
 
 extern "C" int bpp_range_prove_batch_device(bpp_verifier* engine, const uint64_t* d_v, const uint64_t* d_gamma,
                                             size_t count, uint64_t* d_out_points, uint64_t* d_out_scalars,
                                             uint64_t* d_out_V, void* d_workspace, size_t workspace_bytes, void* stream) {
-    return prove_batch_device_common(engine, d_v, d_gamma, count, d_out_points, d_out_scalars, d_out_V, false, nullptr,
-                                     d_workspace, workspace_bytes, stream);
+    if (!engine || !d_v || !d_gamma || !d_out_points || !d_out_scalars || !d_workspace)
+        return fail(BPP_E_ARG, "null argument");
+    if (count == 0) return BPP_OK;
+    return on_ctx(engine->ctx, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::prove_batch_device(engine, d_v, d_gamma, count, d_out_points, d_out_scalars,
+                                                            d_out_V, false, nullptr, d_workspace, workspace_bytes,
+                                                            static_cast<hipStream_t>(stream));
+    });
 }
 
 extern "C" int bpp_range_prove_batch_fs_device(bpp_verifier* engine, const uint64_t* d_v, const uint64_t* d_gamma,
@@ -487,28 +491,23 @@ extern "C" int bpp_range_prove_batch_fs_device(bpp_verifier* engine, const uint6
                                                const uint64_t* d_blinding, uint64_t* d_out_points, uint64_t* d_out_scalars,
                                                uint64_t* d_out_V, uint64_t* d_out_challenges, void* d_workspace,
                                                size_t workspace_bytes, void* stream) {
-    return prove_batch_device_common(engine, d_v, d_gamma, count, d_out_points, d_out_scalars, d_out_V, true,
-                                     d_out_challenges, d_workspace, workspace_bytes, stream, blind_key, index_base, d_blinding);
+    if (!engine || !d_v || !d_gamma || !d_out_points || !d_out_scalars || !d_workspace)
+        return fail(BPP_E_ARG, "null argument");
+    if (count == 0) return BPP_OK;
+    return on_ctx(engine->ctx, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::prove_batch_device(engine, d_v, d_gamma, count, d_out_points, d_out_scalars,
+                                                            d_out_V, true, d_out_challenges, d_workspace, workspace_bytes,
+                                                            static_cast<hipStream_t>(stream), blind_key, index_base,
+                                                            d_blinding);
+    });
 }
 
 // ---- combined batch check ------------------------------------------------------------------------------
 extern "C" size_t bpp_verifier_partial_bytes(const bpp_verifier* v) {
-    if (!v) return 0;
-    size_t r = 0;
-    dispatch(v->ctx.curve, [&](auto cv) -> int {
-        r = (size_t)partial_words<decltype(cv)>() * 4;
-        return 0;
-    });
-    return r;
+    return size_for(v, [&](auto cv) { return (size_t)partial_words<decltype(cv)>() * 4; });
 }
 extern "C" size_t bpp_verifier_combined_workspace_bytes(const bpp_verifier* v, size_t count) {
-    if (!v) return 0;
-    size_t r = 0;
-    dispatch(v->ctx.curve, [&](auto cv) -> int {
-        r = VerifyImpl<decltype(cv)>::comb_layout(v->s, count).total;
-        return 0;
-    });
-    return r;
+    return size_for(v, [&](auto cv) { return VerifyImpl<decltype(cv)>::comb_layout(v->s, count).total; });
 }
 extern "C" int bpp_verifier_run_combined(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars,
                                          size_t count, const uint64_t* d_challenges, const uint8_t* weight_key,
@@ -517,8 +516,7 @@ extern "C" int bpp_verifier_run_combined(bpp_verifier* v, const uint64_t* d_poin
     if (!v || !d_points || !d_scalars || !d_out_partial || !d_ok || !d_workspace) return fail(BPP_E_ARG, "null argument");
     if (!weight_key && !d_weights) return fail(BPP_E_ARG, "the combined check needs a weight key or a weight buffer");
     if (count == 0) return fail(BPP_E_ARG, "empty batch");
-    HIPCHK(hipSetDevice(v->ctx.device));
-    return dispatch(v->ctx.curve, [&](auto cv) -> int {
+    return on_ctx(v->ctx, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::run_combined(v, d_points, d_scalars, count, d_challenges, weight_key, index_base,
                                                       d_weights, static_cast<uint32_t*>(d_out_partial), d_ok, d_workspace,
                                                       workspace_bytes, static_cast<hipStream_t>(stream));
@@ -526,13 +524,8 @@ extern "C" int bpp_verifier_run_combined(bpp_verifier* v, const uint64_t* d_poin
 }
 // ---- grouped check: per-proof verdicts, one weighted check per group, exact pass over the failing groups ------
 extern "C" size_t bpp_verifier_grouped_workspace_bytes(const bpp_verifier* v, size_t count, uint32_t group) {
-    if (!v || group < 2 || (group & (group - 1))) return 0;
-    size_t r = 0;
-    dispatch(v->ctx.curve, [&](auto cv) -> int {
-        r = VerifyImpl<decltype(cv)>::group_layout(v->s, count, group).total;
-        return 0;
-    });
-    return r;
+    if (group < 2 || (group & (group - 1))) return 0;
+    return size_for(v, [&](auto cv) { return VerifyImpl<decltype(cv)>::group_layout(v->s, count, group).total; });
 }
 extern "C" int bpp_verifier_run_grouped(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
                                         const uint64_t* d_challenges, const uint8_t* weight_key, uint64_t index_base,
@@ -541,8 +534,7 @@ extern "C" int bpp_verifier_run_grouped(bpp_verifier* v, const uint64_t* d_point
     if (!v || !d_out_verdicts || !d_workspace || (count && (!d_points || !d_scalars)))
         return fail(BPP_E_ARG, "null argument");
     if (!weight_key && !d_weights) return fail(BPP_E_ARG, "the grouped check needs a weight key or a weight buffer");
-    HIPCHK(hipSetDevice(v->ctx.device));
-    return dispatch(v->ctx.curve, [&](auto cv) -> int {
+    return on_ctx(v->ctx, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::run_grouped(v, d_points, d_scalars, count, d_challenges, weight_key, index_base,
                                                      d_weights, group, d_out_verdicts, stats, d_workspace, workspace_bytes,
                                                      static_cast<hipStream_t>(stream));
@@ -556,8 +548,7 @@ extern "C" int bpp_verifier_grouped_begin(bpp_verifier* v, const uint64_t* d_poi
     if (!v || !d_out_verdicts || !d_workspace || (count && (!d_points || !d_scalars)))
         return fail(BPP_E_ARG, "null argument");
     if (!weight_key && !d_weights) return fail(BPP_E_ARG, "the grouped check needs a weight key or a weight buffer");
-    HIPCHK(hipSetDevice(v->ctx.device));
-    return dispatch(v->ctx.curve, [&](auto cv) -> int {
+    return on_ctx(v->ctx, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::grouped_begin(v, d_points, d_scalars, count, d_challenges, weight_key, index_base,
                                                        d_weights, group, d_out_verdicts, d_workspace, workspace_bytes,
                                                        static_cast<hipStream_t>(stream));
@@ -568,8 +559,7 @@ extern "C" int bpp_verifier_grouped_finish(bpp_verifier* v, const uint64_t* d_po
                                            uint64_t* stats, void* d_workspace, size_t workspace_bytes, void* stream) {
     if (!v || !d_out_verdicts || !d_workspace || (count && (!d_points || !d_scalars)))
         return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(v->ctx.device));
-    return dispatch(v->ctx.curve, [&](auto cv) -> int {
+    return on_ctx(v->ctx, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::grouped_finish(v, d_points, d_scalars, count, d_challenges, group, d_out_verdicts, stats,
                                                         d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
     });
@@ -577,8 +567,7 @@ extern "C" int bpp_verifier_grouped_finish(bpp_verifier* v, const uint64_t* d_po
 extern "C" int bpp_verifier_sum_partials(bpp_verifier* v, const void* d_partials, size_t n, uint32_t* d_ok,
                                          void* stream) {
     if (!v || !d_partials || !d_ok) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(v->ctx.device));
-    return dispatch(v->ctx.curve, [&](auto cv) -> int {
+    return on_ctx(v->ctx, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::sum_partials(static_cast<const uint32_t*>(d_partials), n, d_ok,
                                                       static_cast<hipStream_t>(stream));
     });
@@ -588,8 +577,7 @@ extern "C" int bpp_verifier_derive_challenges(bpp_verifier* v, const uint64_t* d
                                               uint64_t* d_challenges, void* stream) {
     if (!v || !d_points || !d_challenges) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
-    HIPCHK(hipSetDevice(v->ctx.device));
-    return dispatch(v->ctx.curve, [&](auto cv) -> int {
+    return on_ctx(v->ctx, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::derive_challenges(v, d_points, count, d_challenges,
                                                            static_cast<hipStream_t>(stream));
     });
@@ -618,17 +606,8 @@ extern "C" int bpp_verifier_profile(bpp_verifier* v, float* out_stage_ms, size_t
     if (!v || !out_stage_ms) return fail(BPP_E_ARG, "null argument");
     HIPCHK(hipSetDevice(v->ctx.device));
     const size_t np = std::min<size_t>(v->passes_recorded, BPP_PROFILE_SLOTS);
-    for (int t = 0; t < BPP_NUM_STAGES; t++) out_stage_ms[t] = 0.f;
-    for (size_t p = 0; p < np; p++) {
-        hipEvent_t* ev = v->events.data() + p * (BPP_NUM_STAGES * 2);
-        for (int t = 0; t < BPP_NUM_STAGES; t++) {
-            HIPCHK(hipEventSynchronize(ev[2 * t + 1]));
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, ev[2 * t], ev[2 * t + 1]));
-            out_stage_ms[t] += ms;
-        }
-    }
-    for (int t = 0; t < BPP_NUM_STAGES; t++) out_stage_ms[t] = np ? out_stage_ms[t] / (float)np : 0.f;
+    int rc = stage_means(v->events.data(), np, BPP_NUM_STAGES * 2, BPP_NUM_STAGES, 2, out_stage_ms);
+    if (rc) return rc;
     if (out_passes) *out_passes = np;
     if (out_blocks_per_proof) *out_blocks_per_proof = v->last_blocks_per_proof;
     return BPP_OK;
@@ -667,22 +646,18 @@ extern "C" size_t bpp_point_compressed_bytes(int curve_id) {
 
 extern "C" int bpp_points_compress(bpp_ctx* ctx, const uint64_t* points, size_t n, uint8_t* out) {
     if (!ctx || (n && (!points || !out))) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    return dispatch(ctx->curve, [&](auto cv) -> int { return CodecImpl<decltype(cv)>::compress(points, n, out); });
+    return on_ctx(*ctx, [&](auto cv) -> int { return CodecImpl<decltype(cv)>::compress(points, n, out); });
 }
 
 extern "C" int bpp_points_decompress(bpp_ctx* ctx, const uint8_t* in, size_t n, uint64_t* out_points, uint32_t* out_ok) {
     if (!ctx || (n && (!in || !out_points || !out_ok))) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    return dispatch(ctx->curve,
-                    [&](auto cv) -> int { return CodecImpl<decltype(cv)>::decompress(in, n, out_points, out_ok); });
+    return on_ctx(*ctx, [&](auto cv) -> int { return CodecImpl<decltype(cv)>::decompress(in, n, out_points, out_ok); });
 }
 
 extern "C" int bpp_points_decompress_device(bpp_ctx* ctx, const void* d_in, size_t n, uint64_t* d_points, uint32_t* d_ok,
                                             int check_subgroup, void* stream) {
     if (!ctx || (n && (!d_in || !d_points || !d_ok))) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    return dispatch(ctx->curve, [&](auto cv) -> int {
+    return on_ctx(*ctx, [&](auto cv) -> int {
         return CodecImpl<decltype(cv)>::decompress_device(static_cast<const uint8_t*>(d_in), n, d_points, d_ok,
                                                           static_cast<hipStream_t>(stream), check_subgroup != 0);
     });
@@ -720,22 +695,10 @@ extern "C" int bpp_range_verify_batch_compressed(bpp_verifier* v, const uint8_t*
     for (size_t i = 0; i < npts; i++)
         if (bad[i]) out_ok[i / v->s.NV] = BPP_FORMAT_ERROR;   // a malformed encoding / a point outside the group: ProofError::FormatError
     // ... and so does a non-canonical scalar (r', s' or delta' >= the group order): a serialized proof has one encoding
-    dispatch(v->ctx.curve, [&](auto cv) -> int {
-        using Fr = typename decltype(cv)::Fr;
-        for (size_t i = 0; i < count * 3; i++) {
-            const uint64_t* x = scalars + i * 4;
-            bool lt = false;
-            for (int t = 3; t >= 0; t--) {
-                const uint64_t mw = ((uint64_t)Fr::MODW[2 * t + 1] << 32) | Fr::MODW[2 * t];
-                if (x[t] != mw) {
-                    lt = x[t] < mw;
-                    break;
-                }
-            }
-            if (!lt) out_ok[i / 3] = BPP_FORMAT_ERROR;
-        }
-        return BPP_OK;
-    });
+    // (little-endian host: the u64 limbs are the bytes)
+    for (size_t i = 0; i < count * 3; i++)
+        if (!scalar_is_canonical(v->ctx.curve, reinterpret_cast<const uint8_t*>(scalars + i * 4)))
+            out_ok[i / 3] = BPP_FORMAT_ERROR;
     return BPP_OK;
 }
 
@@ -746,19 +709,6 @@ inline uint32_t log2_exact(size_t x) {
     uint32_t k = 0;
     while (((size_t)1 << k) < x) k++;
     return k;
-}
-// canonical (< group order) 32-byte little-endian scalar?
-inline bool scalar_is_canonical(int curve, const uint8_t* b) {
-    bool lt = false;
-    dispatch(curve, [&](auto cv) -> int {
-        using Fr = typename decltype(cv)::Fr;
-        uint32_t w[8];
-        for (int i = 0; i < 8; i++)
-            w[i] = (uint32_t)b[4 * i] | ((uint32_t)b[4 * i + 1] << 8) | ((uint32_t)b[4 * i + 2] << 16) | ((uint32_t)b[4 * i + 3] << 24);
-        lt = words_lt_mod<Fr>(w);
-        return 0;
-    });
-    return lt;
 }
 }  // namespace
 
@@ -894,13 +844,7 @@ extern "C" int bpp_proofs_decode(bpp_ctx* ctx, size_t n, size_t m, const uint8_t
 }
 
 extern "C" size_t bpp_verifier_serialized_workspace_bytes(const bpp_verifier* v, size_t count) {
-    if (!v) return 0;
-    size_t r = 0;
-    dispatch(v->ctx.curve, [&](auto cv) -> int {
-        r = VerifyImpl<decltype(cv)>::ser_layout(v->s, count).total;
-        return 0;
-    });
-    return r;
+    return size_for(v, [&](auto cv) { return VerifyImpl<decltype(cv)>::ser_layout(v->s, count).total; });
 }
 
 extern "C" int bpp_range_verify_batch_serialized_device(bpp_verifier* v, const void* d_proofs, const void* d_commitments,
@@ -912,8 +856,7 @@ extern "C" int bpp_range_verify_batch_serialized_device(bpp_verifier* v, const v
     const uint32_t version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
     if (count == 0) return BPP_OK;
     if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
-    HIPCHK(hipSetDevice(v->ctx.device));
-    return dispatch(v->ctx.curve, [&](auto cv) -> int {
+    return on_ctx(v->ctx, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::run_serialized(v, static_cast<const uint8_t*>(d_proofs),
                                                         static_cast<const uint8_t*>(d_commitments), count, transcript != 0,
                                                         d_ok, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream),
@@ -923,13 +866,8 @@ extern "C" int bpp_range_verify_batch_serialized_device(bpp_verifier* v, const v
 
 // the same with the grouped check behind the decoder (per-proof statuses; synchronises the stream)
 extern "C" size_t bpp_verifier_serialized_grouped_workspace_bytes(const bpp_verifier* v, size_t count, uint32_t group) {
-    if (!v || group < 2 || (group & (group - 1))) return 0;
-    size_t r = 0;
-    dispatch(v->ctx.curve, [&](auto cv) -> int {
-        r = VerifyImpl<decltype(cv)>::ser_layout(v->s, count, group).total;
-        return 0;
-    });
-    return r;
+    if (group < 2 || (group & (group - 1))) return 0;
+    return size_for(v, [&](auto cv) { return VerifyImpl<decltype(cv)>::ser_layout(v->s, count, group).total; });
 }
 extern "C" int bpp_range_verify_batch_serialized_grouped_device(bpp_verifier* v, const void* d_proofs, const void* d_commitments,
                                                                 size_t count, int flags, const uint8_t* weight_key,
@@ -943,8 +881,7 @@ extern "C" int bpp_range_verify_batch_serialized_grouped_device(bpp_verifier* v,
     if (stats) stats[0] = stats[1] = 0;
     if (count == 0) return BPP_OK;
     if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
-    HIPCHK(hipSetDevice(v->ctx.device));
-    return dispatch(v->ctx.curve, [&](auto cv) -> int {
+    return on_ctx(v->ctx, [&](auto cv) -> int {
         using Impl = VerifyImpl<decltype(cv)>;
         const typename Impl::GroupedArgs ga{weight_key, index_base, nullptr, group, stats};
         return Impl::run_serialized(v, static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), count,
@@ -984,8 +921,7 @@ extern "C" int bpp_range_verify_batch_serialized(bpp_verifier* v, const uint8_t*
 extern "C" int bpp_debug_field_op(bpp_ctx* ctx, int field, int op, const uint32_t* a, const uint32_t* b, size_t n,
                                   uint32_t* out) {
     if (!ctx || !a || !b || !out) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    return dispatch(ctx->curve, [&](auto cv) -> int {
+    return on_ctx(*ctx, [&](auto cv) -> int {
         return MsmImpl<decltype(cv)>::debug_field_op(field, op, a, b, n, out);
     });
 }
@@ -993,8 +929,7 @@ extern "C" int bpp_debug_field_op(bpp_ctx* ctx, int field, int op, const uint32_
 extern "C" int bpp_debug_point_op(bpp_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, size_t n,
                                   uint64_t* out) {
     if (!ctx || !a || !b || !out) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    return dispatch(ctx->curve, [&](auto cv) -> int {
+    return on_ctx(*ctx, [&](auto cv) -> int {
         return MsmImpl<decltype(cv)>::debug_point_op(op, a, b, n, out);
     });
 }

@@ -77,6 +77,25 @@ inline int dispatch(int curve, F&& f) {
 
 inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
+// Lays a workspace out buffer by buffer: take(bytes) returns the next buffer's offset and reserves `bytes` rounded up to
+// 256; `total` is the size of everything taken so far.
+struct WsCarver {
+    size_t total = 0;
+    size_t take(size_t bytes) {
+        const size_t o = total;
+        total += (bytes + 255) & ~(size_t)255;
+        return o;
+    }
+};
+
+// a 32-byte key (WeightKey, BlindKey) as 8 little-endian words; null: zeros
+inline void load_key_words(const uint8_t* key, uint32_t w[8]) {
+    for (int i = 0; i < 8; i++)
+        w[i] = key ? (uint32_t)key[4 * i] | ((uint32_t)key[4 * i + 1] << 8) | ((uint32_t)key[4 * i + 2] << 16) |
+                         ((uint32_t)key[4 * i + 3] << 24)
+                   : 0u;
+}
+
 // scalar (4 x u64 = 8 words) reduced mod r on the host: PrimeFieldElem values are always < r.  A 256-bit value holds up
 // to floor(2^256 / r) multiples of r: 1 on secp256k1, 2 on BLS12-381, 15 on edwards25519 (r ~ 2^252) -- hence 16
 // rounds, as k_pip_points does on the device

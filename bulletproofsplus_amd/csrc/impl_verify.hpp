@@ -84,36 +84,22 @@ struct VerifyImpl {
     static constexpr int PW = WW / 2;
 
     static WsLayout ws_layout(const VerifyShape& s, size_t count) {
-        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
         WsLayout w;
-        size_t o = 0;
-        w.pts = o;
-        o += al(count * s.NV * 2 * N * 4);
-        w.bad = o;
-        o += al(count * 4);
-        w.scalars = o;
-        o += al(count * (size_t)s.N * 32);
-        w.prep = o;
-        o += al(count * vs_prep_bytes<C>(s));                      // per-proof constants of the verifier-scalars kernels
-        w.fthread = o;
-        o += al(count * blocks_per_proof(s, count) * FIXED_BLOCK * JW * 4);                // one partial per thread
-        w.fpart = o;
-        o += al(count * blocks_per_proof(s, count) * (FIXED_BLOCK / FOLD_GROUP) * JW * 4);  // folded 8 to 1
-        w.fpart2 = o;
-        o += al(count * blocks_per_proof(s, count) * (FIXED_BLOCK / FOLD_GROUP / FOLD_GROUP2) * JW * 4);  // then 4 to 1
-        w.fpart3 = o;
-        o += al(count * (FIXED_BLOCK / FOLD_GROUP / FOLD_GROUP2) * JW * 4);   // then the blocks of a proof: 4 per proof
-        w.vpart = o;
-        o += al(count * JW * 4);                                   // one jacobian per proof
-        w.vdig = o;
-        o += al(count * s.NV * VAR_DIGIT_STRIDE);                  // digit bytes per proof point (65, or 2 x 33)
-        w.vwsum = o;
-        o += al(count * var_wsums_max<C>() * JW * 4);                 // window sums
-        w.vtbl = o;
-        o += al(count * s.NV * VAR_MULTIPLES * 2 * N * 4);         // 1P..8P of every proof point, affine
-        w.vscr = o;
-        o += al(count * s.NV * 2 * (VAR_MULTIPLES - 1) * N * 4);   // Z's and their prefix products while normalising
-        w.total = o;
+        WsCarver o;
+        w.pts = o.take(count * s.NV * 2 * N * 4);
+        w.bad = o.take(count * 4);
+        w.scalars = o.take(count * (size_t)s.N * 32);
+        w.prep = o.take(count * vs_prep_bytes<C>(s));                     // per-proof constants of the verifier-scalars kernels
+        w.fthread = o.take(count * blocks_per_proof(s, count) * FIXED_BLOCK * JW * 4);                // one partial per thread
+        w.fpart = o.take(count * blocks_per_proof(s, count) * (FIXED_BLOCK / FOLD_GROUP) * JW * 4);  // folded 8 to 1
+        w.fpart2 = o.take(count * blocks_per_proof(s, count) * (FIXED_BLOCK / FOLD_GROUP / FOLD_GROUP2) * JW * 4);  // then 4 to 1
+        w.fpart3 = o.take(count * (FIXED_BLOCK / FOLD_GROUP / FOLD_GROUP2) * JW * 4);   // then the blocks of a proof: 4 per proof
+        w.vpart = o.take(count * JW * 4);                                  // one jacobian per proof
+        w.vdig = o.take(count * s.NV * VAR_DIGIT_STRIDE);                 // digit bytes per proof point (65, or 2 x 33)
+        w.vwsum = o.take(count * var_wsums_max<C>() * JW * 4);            // window sums
+        w.vtbl = o.take(count * s.NV * VAR_MULTIPLES * 2 * N * 4);        // 1P..8P of every proof point, affine
+        w.vscr = o.take(count * s.NV * 2 * (VAR_MULTIPLES - 1) * N * 4);  // Z's and their prefix products while normalising
+        w.total = o.total;
         return w;
     }
 
@@ -152,6 +138,25 @@ struct VerifyImpl {
         lock.unlock();
         return BPP_OK;
     }
+    // stage timing: ev (null when the pass is not profiled) holds ev[2 * stage] / ev[2 * stage + 1]
+    static hipError_t mark(hipEvent_t* ev, int idx, hipStream_t st) { return ev ? hipEventRecord(ev[idx], st) : hipSuccess; }
+    // The head of every pass (run, run_combined, grouped_begin): zero the invalid-point flags, the proof points from the
+    // wire, their tables forked onto the side stream (the caller joins them before k_var_windows), the verifier scalars
+    // into w_sc.  L: the pass's layout (WsLayout, CombLayout or GroupLayout), whose pts, bad, prep, vtbl and vscr it uses.
+    template <class Layout>
+    static int begin_pass(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
+                          const uint64_t* d_challenges, uint8_t* ws, const Layout& L, uint32_t* w_sc,
+                          std::unique_lock<std::mutex>& aux_lock, hipStream_t st, hipEvent_t* ev);
+    // The weighted checks' middle (run_combined, grouped_begin): the weights, then -- after fixed_sums(w_wt), which enqueues
+    // the caller's fixed-generator sums -- the weighted proof-point scalars, their digits and, once the tables have joined,
+    // `per` window sums per proof (k_var_windows with `split`).  L: CombLayout or GroupLayout.
+    template <class Layout, class FixedSums>
+    static int weighted_windows(bpp_verifier* v, uint8_t* ws, const Layout& L, size_t count, const uint8_t* weight_key,
+                                uint64_t index_base, const uint64_t* d_weights, uint32_t per, uint32_t split,
+                                std::unique_lock<std::mutex>& aux_lock, hipStream_t st, FixedSums&& fixed_sums);
+    // one level of k_comb_window_fold: the window sums (`per` each) of every `step` neighbouring proofs of `nrem` added
+    // into one; returns how many sums per window are left
+    static size_t fold_windows(const uint32_t* in, size_t nrem, uint32_t step, uint32_t* out, uint32_t per, hipStream_t st);
     static int finish(bpp_verifier* v, uint8_t* ws, const WsLayout& L, size_t count, const uint32_t* w_sc,
                       const uint32_t* w_vw, const uint32_t* w_bad, uint32_t* d_ok, uint32_t* d_out_result, uint32_t tree,
                       bool lone, hipStream_t st, hipEvent_t* ev);
@@ -166,20 +171,14 @@ struct VerifyImpl {
     };
     // group != 0: the verification behind the decoder is the grouped check (run_grouped) with groups of that size
     static SerLayout ser_layout(const VerifyShape& s, size_t count, uint32_t group = 0) {
-        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
         SerLayout w;
-        size_t o = 0;
-        w.records = o;
-        o += al(count * s.NV * WW * 4);
-        w.scalars = o;
-        o += al(count * 96);
-        w.status = o;
-        o += al(count * 4);
-        w.challenges = o;
-        o += al(count * (size_t)(3 + s.k) * 32);
-        w.run = o;
-        o += group ? group_layout(s, count, group).total : ws_layout(s, count).total;
-        w.total = o;
+        WsCarver o;
+        w.records = o.take(count * s.NV * WW * 4);
+        w.scalars = o.take(count * 96);
+        w.status = o.take(count * 4);
+        w.challenges = o.take(count * (size_t)(3 + s.k) * 32);
+        w.run = o.take(group ? group_layout(s, count, group).total : ws_layout(s, count).total);
+        w.total = o.total;
         return w;
     }
     // the grouped check's arguments when it stands behind the decoder (run_serialized)
@@ -204,38 +203,24 @@ struct VerifyImpl {
     };
     static constexpr uint32_t COMB_FOLD_GROUP = 4;    // proofs whose window sums one lane of k_comb_window_fold adds
     static CombLayout comb_layout(const VerifyShape& s, size_t count) {
-        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
         CombLayout w;
         const size_t items = count * s.NV;
         w.fixed_blocks = blocks_per_proof(s, 1);
-        size_t o = 0;
-        w.pts = o;
-        o += al(items * 2 * N * 4);
-        w.bad = o;
-        o += al(count * 4);
-        w.scalars = o;
-        o += al(count * (size_t)s.N * 32);
-        w.prep = o;
-        o += al(count * vs_prep_bytes<C>(s));
-        w.weights = o;
-        o += al(count * 32);
-        w.comb_sc = o;
-        o += al((size_t)s.N * 32);
-        w.fpart = o;
-        o += al((size_t)(w.fixed_blocks + 1) * JW * 4);            // fixed-generator block sums + the Horner result
-        w.var_sc = o;
-        o += al(items * 32);
-        w.vdig = o;
-        o += al(items * VAR_DIGIT_STRIDE);
-        w.vtbl = o;
-        o += al(items * VAR_MULTIPLES * 2 * N * 4);
-        w.vscr = o;
-        o += al(items * 2 * (VAR_MULTIPLES - 1) * N * 4);
-        w.vwsum = o;
-        o += al(count * var_wsums<C>() * JW * 4);
-        w.vfold = o;
-        o += al((size_t)cdiv(count, COMB_FOLD_GROUP) * var_wsums<C>() * JW * 4);
-        w.total = o;
+        WsCarver o;
+        w.pts = o.take(items * 2 * N * 4);
+        w.bad = o.take(count * 4);
+        w.scalars = o.take(count * (size_t)s.N * 32);
+        w.prep = o.take(count * vs_prep_bytes<C>(s));
+        w.weights = o.take(count * 32);
+        w.comb_sc = o.take((size_t)s.N * 32);
+        w.fpart = o.take((size_t)(w.fixed_blocks + 1) * JW * 4);   // fixed-generator block sums + the Horner result
+        w.var_sc = o.take(items * 32);
+        w.vdig = o.take(items * VAR_DIGIT_STRIDE);
+        w.vtbl = o.take(items * VAR_MULTIPLES * 2 * N * 4);
+        w.vscr = o.take(items * 2 * (VAR_MULTIPLES - 1) * N * 4);
+        w.vwsum = o.take(count * var_wsums<C>() * JW * 4);
+        w.vfold = o.take((size_t)cdiv(count, COMB_FOLD_GROUP) * var_wsums<C>() * JW * 4);
+        w.total = o.total;
         return w;
     }
 
@@ -255,59 +240,37 @@ struct VerifyImpl {
     };
     static constexpr size_t GROUP_EXACT_SLICE = 2048;   // proofs of failing groups re-verified per exact pass
     static GroupLayout group_layout(const VerifyShape& s, size_t count, uint32_t group) {
-        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
         GroupLayout w;
         const size_t items = count * s.NV;
         w.groups = cdiv(count, group);
         w.slice = std::min<size_t>(std::max<size_t>(count, 1), GROUP_EXACT_SLICE);
-        size_t o = 0;
-        w.pts = o;
-        o += al(items * 2 * N * 4);
-        w.bad = o;
-        o += al(count * 4);
-        w.scalars = o;
-        o += al(count * (size_t)s.N * 32);
-        w.prep = o;
-        o += al(count * vs_prep_bytes<C>(s));
-        w.weights = o;
-        o += al(count * 32);
-        w.var_sc = o;
-        o += al(items * 32);
-        w.vdig = o;
-        o += al(items * VAR_DIGIT_STRIDE);
-        w.vtbl = o;
-        o += al(items * VAR_MULTIPLES * 2 * N * 4);
-        w.vscr = o;
-        o += al(items * 2 * (VAR_MULTIPLES - 1) * N * 4);
-        w.vwsum = o;
-        o += al(count * var_wsums<C>() * JW * 4);
-        w.vfold = o;
-        o += al((size_t)cdiv(count, 2) * var_wsums<C>() * JW * 4);
-        w.grows = o;
-        o += al(w.groups * (size_t)s.N * 32);
-        w.gbad = o;
-        o += al(w.groups * 4);
-        w.gok = o;
-        o += al(w.groups * 4);
-        w.tail = o;
-        o += ws_layout(s, w.groups).total;
-        w.list = o;
-        o += al(w.slice * 4);
-        w.x_pts = o;
-        o += al(w.slice * s.NV * WW * 4);
-        w.x_sc = o;
-        o += al(w.slice * 96);
-        w.x_ch = o;
-        o += al(w.slice * (size_t)(3 + s.k) * 32);
-        w.x_ok = o;
-        o += al(w.slice * 4);
-        w.x_run = o;
+        WsCarver o;
+        w.pts = o.take(items * 2 * N * 4);
+        w.bad = o.take(count * 4);
+        w.scalars = o.take(count * (size_t)s.N * 32);
+        w.prep = o.take(count * vs_prep_bytes<C>(s));
+        w.weights = o.take(count * 32);
+        w.var_sc = o.take(items * 32);
+        w.vdig = o.take(items * VAR_DIGIT_STRIDE);
+        w.vtbl = o.take(items * VAR_MULTIPLES * 2 * N * 4);
+        w.vscr = o.take(items * 2 * (VAR_MULTIPLES - 1) * N * 4);
+        w.vwsum = o.take(count * var_wsums<C>() * JW * 4);
+        w.vfold = o.take((size_t)cdiv(count, 2) * var_wsums<C>() * JW * 4);
+        w.grows = o.take(w.groups * (size_t)s.N * 32);
+        w.gbad = o.take(w.groups * 4);
+        w.gok = o.take(w.groups * 4);
+        w.tail = o.take(ws_layout(s, w.groups).total);
+        w.list = o.take(w.slice * 4);
+        w.x_pts = o.take(w.slice * s.NV * WW * 4);
+        w.x_sc = o.take(w.slice * 96);
+        w.x_ch = o.take(w.slice * (size_t)(3 + s.k) * 32);
+        w.x_ok = o.take(w.slice * 4);
         // the exact pass runs over however many proofs the failing groups hold, and a SMALLER batch can need a LARGER
         // workspace (more blocks per proof, blocks_per_proof): room for the worst count up to the slice
         size_t xrun = 0;
         for (size_t c = 1; c <= w.slice; c++) xrun = std::max(xrun, ws_layout(s, c).total);
-        o += xrun;
-        w.total = o;
+        w.x_run = o.take(xrun);
+        w.total = o.total;
         return w;
     }
     // d_out_verdicts: count words, 0 = Ok / 1 = VerificationError, as bpp_verifier_run writes them.  h_stats (host, may be
@@ -341,43 +304,28 @@ struct VerifyImpl {
         return std::min(chunk_max, std::max<size_t>(count, 1));
     }
     static ProveLayout prove_layout(const VerifyShape& s, size_t count) {
-        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
         ProveLayout w;
         const uint32_t nvp = pb_num_vps(s.k, s.m);
         w.chunk = prove_chunk(s, count);
         const size_t nv_total = w.chunk * nvp;
         w.per = blocks_per_proof(s, nv_total);
         const size_t vec = w.chunk * (size_t)s.mn * 32;
-        size_t o = 0;
-        w.a = o;
-        o += al(vec);
-        w.b = o;
-        o += al(vec);
-        w.cG = o;
-        o += al(vec);
-        w.cH = o;
-        o += al(vec);
-        w.pwy = o;
-        o += al(vec);
-        w.con = o;
-        o += al(w.chunk * (size_t)pb_consts_elems(s.k) * 32);
-        w.vps = o;
-        o += al(nv_total * (size_t)s.N * 32);
-        w.part = o;
-        o += al(nv_total * w.per * FIXED_BLOCK * JW * 4);                                  // one partial per thread
-        w.part1 = o;
-        o += al(nv_total * w.per * (FIXED_BLOCK / FOLD_GROUP) * JW * 4);                   // folded 8 to 1
-        w.part2 = o;
-        o += al(nv_total * w.per * (FIXED_BLOCK / FOLD_GROUP / FOLD_GROUP2) * JW * 4);     // then 4 to 1
-        w.vout = o;
-        o += al(w.chunk * (size_t)s.m * WW * 4);   // the commitments of a chunk when the caller does not want them
-        w.trst = o;
-        o += al(w.chunk * 32);                      // transcript states (Fiat-Shamir mode)
-        w.ch = o;
-        o += al(w.chunk * (size_t)(3 + s.k) * 32);  // ... and the challenge blocks when the caller does not want them
-        w.blind = o;
-        o += al(w.chunk * (size_t)pb_blind_elems(s.k) * 32);   // blinding scalars expanded from the caller's key
-        w.total = o;
+        WsCarver o;
+        w.a = o.take(vec);
+        w.b = o.take(vec);
+        w.cG = o.take(vec);
+        w.cH = o.take(vec);
+        w.pwy = o.take(vec);
+        w.con = o.take(w.chunk * (size_t)pb_consts_elems(s.k) * 32);
+        w.vps = o.take(nv_total * (size_t)s.N * 32);
+        w.part = o.take(nv_total * w.per * FIXED_BLOCK * JW * 4);                                // one partial per thread
+        w.part1 = o.take(nv_total * w.per * (FIXED_BLOCK / FOLD_GROUP) * JW * 4);                // folded 8 to 1
+        w.part2 = o.take(nv_total * w.per * (FIXED_BLOCK / FOLD_GROUP / FOLD_GROUP2) * JW * 4);  // then 4 to 1
+        w.vout = o.take(w.chunk * (size_t)s.m * WW * 4);     // the commitments of a chunk when the caller does not want them
+        w.trst = o.take(w.chunk * 32);                        // transcript states (Fiat-Shamir mode)
+        w.ch = o.take(w.chunk * (size_t)(3 + s.k) * 32);    // ... and the challenge blocks when the caller does not want them
+        w.blind = o.take(w.chunk * (size_t)pb_blind_elems(s.k) * 32);   // blinding scalars expanded from the caller's key
+        w.total = o.total;
         return w;
     }
     // d_values: count x m u64 ; d_gammas: count x m scalars ; d_out_points: count x (3 + 2k) wire points ;
@@ -463,6 +411,72 @@ int VerifyImpl<C>::create(const bpp_ctx& ctx, const uint64_t* gh, const uint64_t
 }
 
 template <class C>
+template <class Layout>
+int VerifyImpl<C>::begin_pass(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
+                              const uint64_t* d_challenges, uint8_t* ws, const Layout& L, uint32_t* w_sc,
+                              std::unique_lock<std::mutex>& aux_lock, hipStream_t st, hipEvent_t* ev) {
+    const VerifyShape& s = v->s;
+    uint32_t* w_pts = reinterpret_cast<uint32_t*>(ws + L.pts);
+    uint32_t* w_bad = reinterpret_cast<uint32_t*>(ws + L.bad);
+    const size_t npts = count * s.NV;
+    HIPCHK(zero_words_async(w_bad, count * 4, st));
+    HIPCHK(mark(ev, 2 * BPP_STAGE_FROM_WIRE, st));
+    hipLaunchKernelGGL(k_points_from_wire<C>, dim3(cdiv(npts, 128)), dim3(128), 0, st,
+                       reinterpret_cast<const uint32_t*>(d_points), w_pts, w_bad, npts, s.NV, v->check_subgroup ? 1u : 0u);
+    HIPCHK(mark(ev, 2 * BPP_STAGE_FROM_WIRE + 1, st));
+    // The tables of the proof points need the points only, not the scalars -- a chain of seven additions and an inversion
+    // that nothing else waits for yet -- so they are built on a side stream beside the scalar kernels and join before the
+    // window sums.  For a lone batch both are latency bound; for a large one k_vs_prepare is (one lane per proof: 128 waves
+    // for 8 192 proofs, 0.2 ms with the chip nearly empty) and the tables fill what it leaves.
+    int rc = fork_tables(v, st, w_pts, reinterpret_cast<uint32_t*>(ws + L.vtbl), reinterpret_cast<uint32_t*>(ws + L.vscr),
+                         npts, aux_lock);
+    if (rc) return rc;
+    const uint32_t* ch = d_challenges ? reinterpret_cast<const uint32_t*>(d_challenges) : v->challenges.u32();
+    const uint32_t ch_stride = d_challenges ? (3 + s.k) * 8 : 0;
+    HIPCHK(mark(ev, 2 * BPP_STAGE_SCALARS, st));
+    rc = launch_verify_scalars<C>(s, reinterpret_cast<const uint32_t*>(d_scalars), ch, ch_stride, w_sc, count,
+                                  reinterpret_cast<uint32_t*>(ws + L.prep), st);
+    if (rc) return rc;
+    HIPCHK(mark(ev, 2 * BPP_STAGE_SCALARS + 1, st));
+    return BPP_OK;
+}
+
+template <class C>
+template <class Layout, class FixedSums>
+int VerifyImpl<C>::weighted_windows(bpp_verifier* v, uint8_t* ws, const Layout& L, size_t count, const uint8_t* weight_key,
+                                    uint64_t index_base, const uint64_t* d_weights, uint32_t per, uint32_t split,
+                                    std::unique_lock<std::mutex>& aux_lock, hipStream_t st, FixedSums&& fixed_sums) {
+    const VerifyShape& s = v->s;
+    auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    uint32_t *w_sc = W(L.scalars), *w_wt = W(L.weights), *w_vs = W(L.var_sc);
+    uint8_t* w_vd = ws + L.vdig;
+    const size_t items = count * s.NV;
+    WeightKey wk;
+    load_key_words(d_weights ? nullptr : weight_key, wk.w);
+    hipLaunchKernelGGL(k_comb_weights<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, wk, index_base,
+                       reinterpret_cast<const uint32_t*>(d_weights), w_wt, count);
+    fixed_sums(w_wt);
+    // proof-carried points: weighted scalars -> per-proof Straus window sums (the caller sums them across proofs)
+    hipLaunchKernelGGL(k_comb_var_scalars<C>, dim3(cdiv(items, 256)), dim3(256), 0, st, s, w_sc, w_wt, w_vs, items);
+    hipLaunchKernelGGL(k_var_digits<C>, dim3(cdiv(items, 256)), dim3(256), 0, st, s, w_vs, w_vd, items, 1u);
+    int rc = join_tables(v, st, aux_lock);
+    if (rc) return rc;
+    const size_t vlanes = count * per;
+    hipLaunchKernelGGL(k_var_windows<C>, dim3(cdiv(vlanes, VAR_BLOCK)), dim3(VAR_BLOCK), 0, st, s, w_vd, W(L.vtbl),
+                       W(L.vwsum), vlanes, split, 1u);
+    return BPP_OK;
+}
+
+template <class C>
+size_t VerifyImpl<C>::fold_windows(const uint32_t* in, size_t nrem, uint32_t step, uint32_t* out, uint32_t per,
+                                   hipStream_t st) {
+    const size_t outn = cdiv(nrem, step);
+    hipLaunchKernelGGL(k_comb_window_fold<C>, dim3(cdiv(outn * per, 64)), dim3(64), 0, st, in, nrem, step, out, outn * per,
+                       per);
+    return outn;
+}
+
+template <class C>
 int VerifyImpl<C>::run(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
                const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace, size_t workspace_bytes,
                uint64_t* d_out_scalars, uint64_t* d_out_result, hipStream_t st) {
@@ -470,47 +484,21 @@ int VerifyImpl<C>::run(bpp_verifier* v, const uint64_t* d_points, const uint64_t
     const WsLayout L = ws_layout(s, count);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-    uint32_t* w_pts = reinterpret_cast<uint32_t*>(ws + L.pts);
     uint32_t* w_bad = reinterpret_cast<uint32_t*>(ws + L.bad);
     uint32_t* w_sc = d_out_scalars ? reinterpret_cast<uint32_t*>(d_out_scalars)
                                    : reinterpret_cast<uint32_t*>(ws + L.scalars);
     uint32_t* w_vt = reinterpret_cast<uint32_t*>(ws + L.vtbl);
     const unsigned bpp_ = blocks_per_proof(s, count);
     const size_t npts = count * s.NV;
-    hipEvent_t* ev = nullptr;   // ev[2 * stage], ev[2 * stage + 1]
+    hipEvent_t* ev = nullptr;
     if (v->profiling) {
         ev = v->events.data() + (v->passes_recorded % BPP_PROFILE_SLOTS) * (BPP_NUM_STAGES * 2);
         v->passes_recorded++;
     }
-    auto mark = [&](int idx, hipStream_t s_) { return ev ? hipEventRecord(ev[idx], s_) : hipSuccess; };
     v->last_blocks_per_proof = bpp_;
-    HIPCHK(zero_words_async(w_bad, count * 4, st));
-    HIPCHK(mark(2 * BPP_STAGE_FROM_WIRE, st));
-    hipLaunchKernelGGL(k_points_from_wire<C>, dim3(cdiv(npts, 128)), dim3(128), 0, st,
-                       reinterpret_cast<const uint32_t*>(d_points), w_pts, w_bad, npts, s.NV, v->check_subgroup ? 1u : 0u);
-    HIPCHK(mark(2 * BPP_STAGE_FROM_WIRE + 1, st));
-    // The tables of the proof points need the points only, not the scalars -- a chain of seven additions and an inversion
-    // that nothing else waits for yet -- so they are built on a side stream beside the scalar kernels and join before the
-    // window sums.  For a lone batch both are latency bound; for a large one k_vs_prepare is (one lane per proof: 128 waves
-    // for 8 192 proofs, 0.2 ms with the chip nearly empty) and the tables fill what it leaves.
-#ifndef BPP_SIDE_TABLES_ALWAYS
-#define BPP_SIDE_TABLES_ALWAYS 1
-#endif
-    const bool side_tables = BPP_SIDE_TABLES_ALWAYS || (count * blocks_per_proof(s, count) <= 1024 && count <= HORNER_TREE_MAX);
     std::unique_lock<std::mutex> aux_lock;
-    if (side_tables) {
-        int rc_f = fork_tables(v, st, w_pts, w_vt, reinterpret_cast<uint32_t*>(ws + L.vscr), npts, aux_lock);
-        if (rc_f) return rc_f;
-    }
-    const uint32_t* ch = d_challenges ? reinterpret_cast<const uint32_t*>(d_challenges) : v->challenges.u32();
-    const uint32_t ch_stride = d_challenges ? (3 + s.k) * 8 : 0;
-    HIPCHK(mark(2 * BPP_STAGE_SCALARS, st));
-    {
-        int rc_vs = launch_verify_scalars<C>(s, reinterpret_cast<const uint32_t*>(d_scalars), ch, ch_stride, w_sc, count,
-                                             reinterpret_cast<uint32_t*>(ws + L.prep), st);
-        if (rc_vs) return rc_vs;
-    }
-    HIPCHK(mark(2 * BPP_STAGE_SCALARS + 1, st));
+    int rc = begin_pass(v, d_points, d_scalars, count, d_challenges, ws, L, w_sc, aux_lock, st, ev);
+    if (rc) return rc;
     // proof-point MSM: digits, per-point tables, window sums (all arithmetic bound, so they simply run in
     // sequence); its latency-bound Horner stage rides in the first blocks of the fixed-generator launch
     uint8_t* w_vd = ws + L.vdig;
@@ -527,17 +515,13 @@ int VerifyImpl<C>::run(bpp_verifier* v, const uint64_t* d_points, const uint64_t
     const bool lone = tree == 1 && count * bpp_ <= 1024;
     const uint32_t vgroups = lone ? VAR_GROUPS : 1u;
     const size_t vlanes = count * (tree == 1 ? var_wsums<C>() * vgroups : var_windows<C>());
-    HIPCHK(mark(2 * BPP_STAGE_VAR_MSM, st));
+    HIPCHK(mark(ev, 2 * BPP_STAGE_VAR_MSM, st));
     hipLaunchKernelGGL(k_var_digits<C>, dim3(cdiv(npts, 256)), dim3(256), 0, st, s, w_sc, w_vd, npts, 0u);
-    if (side_tables) {
-        int rc_j = join_tables(v, st, aux_lock);
-        if (rc_j) return rc_j;
-    } else
-        hipLaunchKernelGGL(k_var_tables<C>, dim3(cdiv(npts, VAR_BLOCK)), dim3(VAR_BLOCK), 0, st, w_pts, w_vt,
-                           reinterpret_cast<uint32_t*>(ws + L.vscr), npts);
+    rc = join_tables(v, st, aux_lock);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_var_windows<C>, dim3(cdiv(vlanes, VAR_BLOCK)), dim3(VAR_BLOCK), 0, st, s, w_vd, w_vt, w_vw,
                        vlanes, tree == 1 ? 1u : 0u, vgroups);
-    HIPCHK(mark(2 * BPP_STAGE_VAR_MSM + 1, st));
+    HIPCHK(mark(ev, 2 * BPP_STAGE_VAR_MSM + 1, st));
     return finish(v, ws, L, count, w_sc, w_vw, w_bad, d_ok, reinterpret_cast<uint32_t*>(d_out_result), tree, lone, st, ev);
 }
 
@@ -551,14 +535,13 @@ int VerifyImpl<C>::finish(bpp_verifier* v, uint8_t* ws, const WsLayout& L, size_
     const unsigned bpp_ = blocks_per_proof(s, count);
     uint32_t* w_fp = reinterpret_cast<uint32_t*>(ws + L.fpart);
     uint32_t* w_vp = reinterpret_cast<uint32_t*>(ws + L.vpart);
-    auto mark = [&](int idx, hipStream_t s_) { return ev ? hipEventRecord(ev[idx], s_) : hipSuccess; };
-    HIPCHK(mark(2 * BPP_STAGE_FIXED_MSM, st));
+    HIPCHK(mark(ev, 2 * BPP_STAGE_FIXED_MSM, st));
     const unsigned hb = tree == 1 ? (unsigned)count : cdiv(count, tree == 2 ? FIXED_BLOCK / 8 : FIXED_BLOCK);
     uint32_t* w_ft = reinterpret_cast<uint32_t*>(ws + L.fthread);
     launch_fixed_msm<C, 0>((unsigned)(hb + count * bpp_), st, s, w_sc, v->table.u32(), w_ft, bpp_, hb, w_vw, w_vp, count,
                            lone ? 3u : tree, VpSel{1u, 0u, 1u, 0u});
-    HIPCHK(mark(2 * BPP_STAGE_FIXED_MSM + 1, st));
-    HIPCHK(mark(2 * BPP_STAGE_FINALIZE, st));
+    HIPCHK(mark(ev, 2 * BPP_STAGE_FIXED_MSM + 1, st));
+    HIPCHK(mark(ev, 2 * BPP_STAGE_FINALIZE, st));
     // 128 per-thread partials per block -> 16 -> 4 (-> 4 per proof), every lane of the fold kernels busy;
     // k_finalize adds the rest
     const unsigned folded = bpp_ * (FIXED_BLOCK / FOLD_GROUP);
@@ -571,7 +554,7 @@ int VerifyImpl<C>::finish(bpp_verifier* v, uint8_t* ws, const WsLayout& L, size_
                                count * folded);
         hipLaunchKernelGGL(k_finalize_tree<C>, dim3((unsigned)count), dim3(64), 0, st, lone ? w_ft : w_fp,
                            lone ? bpp_ : folded, w_vp, w_bad, d_ok, d_out_result, count);
-        HIPCHK(mark(2 * BPP_STAGE_FINALIZE + 1, st));
+        HIPCHK(mark(ev, 2 * BPP_STAGE_FINALIZE + 1, st));
         HIPCHK(hipGetLastError());
         return BPP_OK;
     }
@@ -590,7 +573,7 @@ int VerifyImpl<C>::finish(bpp_verifier* v, uint8_t* ws, const WsLayout& L, size_
     }
     hipLaunchKernelGGL(k_finalize<C>, dim3(cdiv(count, 64)), dim3(64), 0, st, w_last, last, w_vp, 1u, w_bad, d_ok,
                        d_out_result, count);
-    HIPCHK(mark(2 * BPP_STAGE_FINALIZE + 1, st));
+    HIPCHK(mark(ev, 2 * BPP_STAGE_FINALIZE + 1, st));
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
@@ -651,62 +634,24 @@ int VerifyImpl<C>::run_combined(bpp_verifier* v, const uint64_t* d_points, const
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     if (count * s.NV >= ((size_t)1 << 30)) return fail(BPP_E_ARG, "count too large");
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-    uint32_t* w_pts = reinterpret_cast<uint32_t*>(ws + L.pts);
     uint32_t* w_bad = reinterpret_cast<uint32_t*>(ws + L.bad);
     uint32_t* w_sc = reinterpret_cast<uint32_t*>(ws + L.scalars);
-    uint32_t* w_wt = reinterpret_cast<uint32_t*>(ws + L.weights);
     uint32_t* w_cs = reinterpret_cast<uint32_t*>(ws + L.comb_sc);
     uint32_t* w_fp = reinterpret_cast<uint32_t*>(ws + L.fpart);
-    uint32_t* w_vs = reinterpret_cast<uint32_t*>(ws + L.var_sc);
-    uint8_t* w_vd = ws + L.vdig;
-    uint32_t* w_vt = reinterpret_cast<uint32_t*>(ws + L.vtbl);
-    uint32_t* w_vscr = reinterpret_cast<uint32_t*>(ws + L.vscr);
-    uint32_t* w_vw = reinterpret_cast<uint32_t*>(ws + L.vwsum);
-    uint32_t* w_vf = reinterpret_cast<uint32_t*>(ws + L.vfold);
-    const size_t items = count * s.NV;
-    HIPCHK(zero_words_async(w_bad, count * 4, st));
     HIPCHK(zero_words_async(w_cs, (size_t)s.N * 32, st));
-    hipLaunchKernelGGL(k_points_from_wire<C>, dim3(cdiv(items, 128)), dim3(128), 0, st,
-                       reinterpret_cast<const uint32_t*>(d_points), w_pts, w_bad, items, s.NV, v->check_subgroup ? 1u : 0u);
     std::unique_lock<std::mutex> aux_lock;
-    {
-        int rc_f = fork_tables(v, st, w_pts, w_vt, w_vscr, items, aux_lock);
-        if (rc_f) return rc_f;
-    }
-    const uint32_t* ch = d_challenges ? reinterpret_cast<const uint32_t*>(d_challenges) : v->challenges.u32();
-    const uint32_t ch_stride = d_challenges ? (3 + s.k) * 8 : 0;
-    {
-        int rc_vs = launch_verify_scalars<C>(s, reinterpret_cast<const uint32_t*>(d_scalars), ch, ch_stride, w_sc, count,
-                                             reinterpret_cast<uint32_t*>(ws + L.prep), st);
-        if (rc_vs) return rc_vs;
-    }
-    WeightKey wk;
-    for (int i = 0; i < 8; i++)
-        wk.w[i] = d_weights ? 0u
-                            : (uint32_t)weight_key[4 * i] | ((uint32_t)weight_key[4 * i + 1] << 8) |
-                                  ((uint32_t)weight_key[4 * i + 2] << 16) | ((uint32_t)weight_key[4 * i + 3] << 24);
-    hipLaunchKernelGGL(k_comb_weights<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, wk, index_base,
-                       reinterpret_cast<const uint32_t*>(d_weights), w_wt, count);
-    hipLaunchKernelGGL(k_comb_fixed<C>, dim3(s.NF), dim3(256), 0, st, s, w_sc, w_wt, count, w_cs);
-    // proof-carried points: weighted scalars -> per-proof Straus window sums -> summed across proofs per window
-    hipLaunchKernelGGL(k_comb_var_scalars<C>, dim3(cdiv(items, 256)), dim3(256), 0, st, s, w_sc, w_wt, w_vs, items);
-    hipLaunchKernelGGL(k_var_digits<C>, dim3(cdiv(items, 256)), dim3(256), 0, st, s, w_vs, w_vd, items, 1u);
-    {
-        int rc_j = join_tables(v, st, aux_lock);
-        if (rc_j) return rc_j;
-    }
-    const size_t vlanes = count * var_wsums<C>();
-    hipLaunchKernelGGL(k_var_windows<C>, dim3(cdiv(vlanes, VAR_BLOCK)), dim3(VAR_BLOCK), 0, st, s, w_vd, w_vt, w_vw,
-                       vlanes, 1u, 1u);
-    uint32_t* cur = w_vw;
-    uint32_t* nxt = w_vf;
-    for (size_t nrem = count; nrem > 1;) {
-        const size_t groups = cdiv(nrem, COMB_FOLD_GROUP);
-        hipLaunchKernelGGL(k_comb_window_fold<C>, dim3(cdiv(groups * var_wsums<C>(), 64)), dim3(64), 0, st, cur, nrem,
-                           COMB_FOLD_GROUP, nxt, groups * var_wsums<C>(), var_wsums<C>());
-        std::swap(cur, nxt);
-        nrem = groups;
-    }
+    int rc = begin_pass(v, d_points, d_scalars, count, d_challenges, ws, L, w_sc, aux_lock, st, nullptr);
+    if (rc) return rc;
+    rc = weighted_windows(v, ws, L, count, weight_key, index_base, d_weights, var_wsums<C>(), 1u, aux_lock, st,
+                          [&](const uint32_t* w_wt) {
+                              hipLaunchKernelGGL(k_comb_fixed<C>, dim3(s.NF), dim3(256), 0, st, s, w_sc, w_wt, count, w_cs);
+                          });
+    if (rc) return rc;
+    // the proofs' window sums, summed across proofs per window: 4 to 1 per level
+    uint32_t* cur = reinterpret_cast<uint32_t*>(ws + L.vwsum);
+    uint32_t* nxt = reinterpret_cast<uint32_t*>(ws + L.vfold);
+    for (size_t nrem = count; nrem > 1; std::swap(cur, nxt))
+        nrem = fold_windows(cur, nrem, COMB_FOLD_GROUP, nxt, var_wsums<C>(), st);
     // the collapsed fixed-generator MulVec (one "virtual proof") with the Horner lane over the 65 sums in its
     // leading block; the Horner result lands behind the block sums
     launch_fixed_msm<C, 1>(1 + L.fixed_blocks, st, s, w_cs, v->table.u32(), w_fp, L.fixed_blocks, 1u, cur,
@@ -744,64 +689,31 @@ int VerifyImpl<C>::grouped_begin(bpp_verifier* v, const uint64_t* d_points, cons
     if (count == 0) return BPP_OK;
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
-    uint32_t *w_pts = W(L.pts), *w_bad = W(L.bad), *w_sc = W(L.scalars), *w_wt = W(L.weights), *w_vs = W(L.var_sc);
-    uint32_t *w_vt = W(L.vtbl), *w_vw = W(L.vwsum), *w_vf = W(L.vfold), *w_rows = W(L.grows), *w_gbad = W(L.gbad);
-    uint32_t* w_gok = W(L.gok);
-    uint8_t* w_vd = ws + L.vdig;
-    const size_t items = count * s.NV, G = L.groups;
-    HIPCHK(zero_words_async(w_bad, count * 4, st));
-    hipLaunchKernelGGL(k_points_from_wire<C>, dim3(cdiv(items, 128)), dim3(128), 0, st,
-                       reinterpret_cast<const uint32_t*>(d_points), w_pts, w_bad, items, s.NV, v->check_subgroup ? 1u : 0u);
+    uint32_t *w_bad = W(L.bad), *w_sc = W(L.scalars), *w_rows = W(L.grows), *w_gbad = W(L.gbad), *w_gok = W(L.gok);
+    const size_t G = L.groups;
     std::unique_lock<std::mutex> aux_lock;
-    {
-        int rc_f = fork_tables(v, st, w_pts, w_vt, W(L.vscr), items, aux_lock);
-        if (rc_f) return rc_f;
-    }
-    const uint32_t* ch = d_challenges ? reinterpret_cast<const uint32_t*>(d_challenges) : v->challenges.u32();
-    const uint32_t ch_stride = d_challenges ? (3 + s.k) * 8 : 0;
-    {
-        int rc_vs = launch_verify_scalars<C>(s, reinterpret_cast<const uint32_t*>(d_scalars), ch, ch_stride, w_sc, count,
-                                             W(L.prep), st);
-        if (rc_vs) return rc_vs;
-    }
-    WeightKey wk;
-    for (int i = 0; i < 8; i++)
-        wk.w[i] = d_weights ? 0u
-                            : (uint32_t)weight_key[4 * i] | ((uint32_t)weight_key[4 * i + 1] << 8) |
-                                  ((uint32_t)weight_key[4 * i + 2] << 16) | ((uint32_t)weight_key[4 * i + 3] << 24);
-    hipLaunchKernelGGL(k_comb_weights<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, wk, index_base,
-                       reinterpret_cast<const uint32_t*>(d_weights), w_wt, count);
-    hipLaunchKernelGGL(k_comb_fixed_grouped<C>, dim3((unsigned)(G * cdiv(s.NF, 64))), dim3(64), 0, st, s, w_sc, w_wt, count,
-                       group, w_rows);
-    hipLaunchKernelGGL(k_comb_group_bad, dim3(cdiv(G, 256)), dim3(256), 0, st, w_bad, count, group, w_gbad, G);
+    int rc = begin_pass(v, d_points, d_scalars, count, d_challenges, ws, L, w_sc, aux_lock, st, nullptr);
+    if (rc) return rc;
     const uint32_t tree = horner_form(s, G);
     const uint32_t per = tree == 1 ? var_wsums<C>() : var_windows<C>();   // window sums per proof, in the layout the Horner form reads
-    hipLaunchKernelGGL(k_comb_var_scalars<C>, dim3(cdiv(items, 256)), dim3(256), 0, st, s, w_sc, w_wt, w_vs, items);
-    hipLaunchKernelGGL(k_var_digits<C>, dim3(cdiv(items, 256)), dim3(256), 0, st, s, w_vs, w_vd, items, 1u);
-    {
-        int rc_j = join_tables(v, st, aux_lock);
-        if (rc_j) return rc_j;
-    }
-    const size_t vlanes = count * per;
-    hipLaunchKernelGGL(k_var_windows<C>, dim3(cdiv(vlanes, VAR_BLOCK)), dim3(VAR_BLOCK), 0, st, s, w_vd, w_vt, w_vw,
-                       vlanes, tree == 1 ? 1u : 0u, 1u);
-    uint32_t* cur = w_vw;
-    uint32_t* nxt = w_vf;
+    rc = weighted_windows(v, ws, L, count, weight_key, index_base, d_weights, per, tree == 1 ? 1u : 0u, aux_lock, st,
+                          [&](const uint32_t* w_wt) {
+                              hipLaunchKernelGGL(k_comb_fixed_grouped<C>, dim3((unsigned)(G * cdiv(s.NF, 64))), dim3(64), 0,
+                                                 st, s, w_sc, w_wt, count, group, w_rows);
+                              hipLaunchKernelGGL(k_comb_group_bad, dim3(cdiv(G, 256)), dim3(256), 0, st, w_bad, count, group,
+                                                 w_gbad, G);
+                          });
+    if (rc) return rc;
+    uint32_t* cur = W(L.vwsum);
+    uint32_t* nxt = W(L.vfold);
     size_t nrem = count;
-    for (uint32_t left = group; left > 1;) {   // the proofs of a group are neighbours: 4 (at last 2) to 1 per level
+    for (uint32_t left = group; left > 1; std::swap(cur, nxt)) {   // the proofs of a group are neighbours: 4 (at last 2) to 1 per level
         const uint32_t step = left >= 4 ? 4u : 2u;
-        const size_t outn = cdiv(nrem, step);
-        hipLaunchKernelGGL(k_comb_window_fold<C>, dim3(cdiv(outn * per, 64)), dim3(64), 0, st, cur, nrem, step, nxt, outn * per,
-                           per);
-        std::swap(cur, nxt);
-        nrem = outn;
+        nrem = fold_windows(cur, nrem, step, nxt, per, st);
         left /= step;
     }
-    {
-        const WsLayout T = ws_layout(s, G);
-        int rc = finish(v, ws + L.tail, T, G, w_rows, cur, w_gbad, w_gok, nullptr, tree, false, st, nullptr);
-        if (rc) return rc;
-    }
+    rc = finish(v, ws + L.tail, ws_layout(s, G), G, w_rows, cur, w_gbad, w_gok, nullptr, tree, false, st, nullptr);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_comb_group_spread, dim3(cdiv(count, 256)), dim3(256), 0, st, w_gok, group, d_out_verdicts, count);
     HIPCHK(hipGetLastError());
     return BPP_OK;
@@ -868,10 +780,7 @@ int VerifyImpl<C>::prove_batch_device(bpp_verifier* v, const uint64_t* d_values,
     const uint32_t k = s.k, m = s.m;
     const uint32_t nvp = pb_num_vps(k, m);
     BlindKey bk;
-    for (int i = 0; i < 8; i++)
-        bk.w[i] = blind_key ? (uint32_t)blind_key[4 * i] | ((uint32_t)blind_key[4 * i + 1] << 8) |
-                                  ((uint32_t)blind_key[4 * i + 2] << 16) | ((uint32_t)blind_key[4 * i + 3] << 24)
-                            : 0u;
+    load_key_words(blind_key, bk.w);
     const ProveLayout L = prove_layout(s, count);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     ProverConsts pc;

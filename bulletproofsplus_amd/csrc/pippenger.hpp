@@ -47,6 +47,7 @@
 #pragma once
 #include <algorithm>
 
+#include "host_util.hpp"
 #include "kernels.hpp"
 
 namespace bpp {
@@ -848,50 +849,30 @@ template <class C>
 inline PipWorkspace pip_workspace(const PipShape& s) {
     constexpr int N = C::Fp::N;
     constexpr int JW = jac_words<C>();
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     PipWorkspace w;
-    size_t o = 0;
-    w.points = o;
-    o += al(((size_t)s.items + 1) * 2 * N * 4);
-    w.split = o;
-    o += al((size_t)s.n * PIP_SPLIT_WORDS * 4);
-    w.rec_item = o;
-    o += al((size_t)s.W * s.items * 4);
-    w.rec_low = o;
-    o += al((size_t)s.W * s.items * 2);
-    w.sorted = o;
-    o += al((size_t)s.W * s.istride * 4 + 64);
+    WsCarver o;
+    w.points = o.take(((size_t)s.items + 1) * 2 * N * 4);
+    w.split = o.take((size_t)s.n * PIP_SPLIT_WORDS * 4);
+    w.rec_item = o.take((size_t)s.W * s.items * 4);
+    w.rec_low = o.take((size_t)s.W * s.items * 2);
+    w.sorted = o.take((size_t)s.W * s.istride * 4 + 64);
     const size_t ncb = pip_ncoarse_total(s);
-    w.ccount = o;
-    o += al(ncb * 4);
-    w.cstart = o;
-    o += al(ncb * 4);
-    w.ccursor = o;
-    o += al(ncb * 4);
-    w.counts = o;
-    o += al((size_t)s.nbuckets * 4);
-    w.offsets = o;
-    o += al((size_t)s.nbuckets * 4);
-    w.segbase = o;
-    o += al((size_t)s.nbuckets * 4);
-    w.chunk_first = o;
-    o += al((size_t)s.W * s.cpw * 4);
-    w.wtotal = o;
-    o += al((size_t)s.W * 4);
-    w.segs = o;
-    o += al((size_t)s.W * s.capseg * seg_words<C>() * 4);
-    w.buckets = o;
-    o += al((size_t)s.nbuckets * JW * 4);
-    w.tiles = o;
-    o += al((size_t)s.ntiles * 2 * JW * 4);
-    w.wsums = o;
-    o += al((size_t)s.W * JW * 4);
-    w.hlist = o;
-    o += al((size_t)s.nbuckets * 4);
-    w.hcount = o;
-    w.bad = o + 4;   // private status word, right behind the heavy-bucket counter
-    o += al(8);
-    w.total = o;
+    w.ccount = o.take(ncb * 4);
+    w.cstart = o.take(ncb * 4);
+    w.ccursor = o.take(ncb * 4);
+    w.counts = o.take((size_t)s.nbuckets * 4);
+    w.offsets = o.take((size_t)s.nbuckets * 4);
+    w.segbase = o.take((size_t)s.nbuckets * 4);
+    w.chunk_first = o.take((size_t)s.W * s.cpw * 4);
+    w.wtotal = o.take((size_t)s.W * 4);
+    w.segs = o.take((size_t)s.W * s.capseg * seg_words<C>() * 4);
+    w.buckets = o.take((size_t)s.nbuckets * JW * 4);
+    w.tiles = o.take((size_t)s.ntiles * 2 * JW * 4);
+    w.wsums = o.take((size_t)s.W * JW * 4);
+    w.hlist = o.take((size_t)s.nbuckets * 4);
+    w.hcount = o.take(8);
+    w.bad = w.hcount + 4;   // private status word, right behind the heavy-bucket counter
+    w.total = o.total;
     return w;
 }
 
