@@ -295,6 +295,46 @@ impl BatchVerifier {
         assert!(rc == 0, "bpp_range_verify_batch: {}", rc);
         ok.iter().map(|&v| if v == 0 { Ok(()) } else { Err(ProofError::VerificationError) }).collect()
     }
+    /// A batch of mixed aggregation sizes against this verifier's tables (include/bpp_amd.h: bpp_range_verify_batch_mixed):
+    /// proof i with m_i = its commitments' count, a power of two <= m.  Each `Result` is
+    /// RangeProof::verify(proof_i, PublicKey::new(n m_i), n, V_i) -- the verdict against the PREFIX key of the proof's own
+    /// shape.  A proof whose L_vec / R_vec lengths are not log2(n m_i), or whose m_i the verifier does not take, is
+    /// Err(VerificationError) without reaching the engine.
+    pub fn verify_batch_mixed(&self, batch: &[(&RangeProof, &[Point])]) -> Vec<Result<(), ProofError>> {
+        let logn = self.k - self.m.trailing_zeros() as usize;
+        let mut out: Vec<Result<(), ProofError>> = vec![Err(ProofError::VerificationError); batch.len()];
+        let (mut pts, mut scs, mut ms, mut at) = (Vec::<Point>::new(), Vec::<PrimeFieldElem>::new(), Vec::<u32>::new(), Vec::new());
+        for (i, (proof, commitment_vec)) in batch.iter().enumerate() {
+            let mi = commitment_vec.len();
+            if mi == 0 || !mi.is_power_of_two() || mi > self.m {
+                continue;
+            }
+            let ki = logn + mi.trailing_zeros() as usize;
+            if proof.proof.L_vec.len() != ki || proof.proof.R_vec.len() != ki {
+                continue;   // wip.rs:335-337
+            }
+            pts.extend_from_slice(&[proof.A, proof.proof.A, proof.proof.B]);
+            pts.extend_from_slice(&proof.proof.L_vec);
+            pts.extend_from_slice(&proof.proof.R_vec);
+            pts.extend_from_slice(commitment_vec);
+            scs.extend_from_slice(&[proof.proof.r_prime, proof.proof.s_prime, proof.proof.d_prime]);
+            ms.push(mi as u32);
+            at.push(i);
+        }
+        if ms.is_empty() {
+            return out;
+        }
+        let (pw, sw) = (flat_points(&pts), flat_scalars(&scs));
+        let mut ok = vec![0u32; ms.len()];
+        let rc = unsafe {
+            ffi::bpp_range_verify_batch_mixed(self.handle, pw.as_ptr(), sw.as_ptr(), ms.as_ptr(), ms.len(), ok.as_mut_ptr())
+        };
+        assert!(rc == 0, "bpp_range_verify_batch_mixed: {}", rc);
+        for (j, &i) in at.iter().enumerate() {
+            out[i] = if ok[j] == 0 { Ok(()) } else { Err(ProofError::VerificationError) };
+        }
+        out
+    }
 }
 impl Drop for BatchVerifier {
     fn drop(&mut self) {

@@ -42,6 +42,8 @@ EXPORTS = [
     "bpp_range_verify_batch_serialized", "bpp_verifier_serialized_workspace_bytes",
     "bpp_range_verify_batch_serialized_device",
     "bpp_verifier_serialized_grouped_workspace_bytes", "bpp_range_verify_batch_serialized_grouped_device",
+    "bpp_verifier_mixed_workspace_bytes", "bpp_verifier_run_mixed", "bpp_verifier_derive_challenges_mixed",
+    "bpp_range_verify_batch_mixed",
 ]
 
 
@@ -147,6 +149,11 @@ def lib():
         L.bpp_verifier_serialized_grouped_workspace_bytes.restype = sz
         L.bpp_range_verify_batch_serialized_grouped_device.argtypes = [vp, vp, vp, sz, i32, ctypes.c_char_p, u64, ctypes.c_uint32,
                                                                        vp, vp, vp, sz, vp]
+        L.bpp_verifier_mixed_workspace_bytes.argtypes = [vp, vp, sz]
+        L.bpp_verifier_mixed_workspace_bytes.restype = sz
+        L.bpp_verifier_run_mixed.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, vp]
+        L.bpp_verifier_derive_challenges_mixed.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
+        L.bpp_range_verify_batch_mixed.argtypes = [vp, vp, vp, vp, sz, vp]
         L.bpp_debug_field_op.argtypes = [vp, i32, i32, vp, vp, sz, vp]
         L.bpp_debug_point_op.argtypes = [vp, i32, vp, vp, sz, vp]
         _lib = L

@@ -673,6 +673,67 @@ class BatchVerifier:
         check(_lib.lib().bpp_verifier_derive_challenges(self.handle, d_points, count, d_challenges, stream or None),
               "bpp_verifier_derive_challenges")
 
+    # ---- mixed batches: proof i of shape (n, ms[i]), ms[i] a power of two <= m (include/bpp_amd.h) ----
+    def _ms(self, ms) -> np.ndarray:
+        return np.ascontiguousarray(ms, dtype=np.uint32).reshape(-1)
+
+    def mixed_points(self, m_i: int) -> int:
+        """wire points of a proof record of shape (n, m_i): 3 + 2 log2(n m_i) + m_i"""
+        return 3 + 2 * ((self.n * m_i).bit_length() - 1) + m_i
+
+    def mixed_workspace_bytes(self, ms) -> int:
+        """bytes of device workspace run_mixed_device / derive_challenges_mixed_device need (0: an m_i is not taken)"""
+        m = self._ms(ms)
+        return _lib.lib().bpp_verifier_mixed_workspace_bytes(self.handle, _ptr(m), len(m))
+
+    def run_mixed_device(self, d_points: int, d_scalars: int, ms, d_ok: int, d_workspace: int, workspace_bytes: int,
+                         stream: int = 0, d_challenges: int = 0, d_out_result: int = 0):
+        """RangeProof::verify(proof_i, PublicKey::new(n ms[i]), n, V_i) for every proof of a resident batch: the verdict
+        against the prefix key of the proof's own shape.  d_points: the packed records (mixed_points(ms[i]) wire points
+        each, caller order); ms: host list.  Blocks while it uploads the per-proof index, the rest is on `stream`."""
+        m = self._ms(ms)
+        check(_lib.lib().bpp_verifier_run_mixed(self.handle, d_points, d_scalars, _ptr(m), len(m), d_challenges or None,
+                                                d_ok, d_workspace, workspace_bytes, d_out_result or None, stream or None),
+              "bpp_verifier_run_mixed")
+
+    def derive_challenges_mixed_device(self, d_points: int, ms, d_challenges: int, d_workspace: int,
+                                       workspace_bytes: int, stream: int = 0):
+        """Fiat-Shamir challenges of a mixed batch, 3 + log2(n ms[i]) scalars per proof packed in caller order (the
+        layout run_mixed_device takes); each transcript starts from the prefix key of the proof's own shape"""
+        m = self._ms(ms)
+        check(_lib.lib().bpp_verifier_derive_challenges_mixed(self.handle, d_points, _ptr(m), len(m), d_challenges,
+                                                              d_workspace, workspace_bytes, stream or None),
+              "bpp_verifier_derive_challenges_mixed")
+
+    def verify_wire_mixed(self, records, scalars, ms) -> np.ndarray:
+        """records: a list of per-proof (mixed_points(ms[i]), PW) arrays or one packed array; scalars (count, 3, 4);
+        ms: m_i per proof -> ok (count,) u32 (bpp_range_verify_batch_mixed)"""
+        m = self._ms(ms)
+        count = len(m)
+        # an m_i the verifier does not take is reported by the library (BPP_E_ARG naming the proof)
+        taken = all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m)
+        need = sum(self.mixed_points(int(x)) for x in m) if taken else None
+        if isinstance(records, (list, tuple)):
+            if len(records) != count:
+                raise RuntimeError("verify_wire_mixed: one record per entry of ms")
+            for i, (r, x) in enumerate(zip(records, m)):
+                if taken and np.asarray(r).reshape(-1, self.arith.PW).shape[0] != self.mixed_points(int(x)):
+                    raise RuntimeError("verify_wire_mixed: record %d does not hold %d points" % (i, self.mixed_points(int(x))))
+            pts = (np.concatenate([np.asarray(r, dtype=np.uint64).reshape(-1, self.arith.PW) for r in records])
+                   if count else np.zeros((0, self.arith.PW), dtype=np.uint64))
+        else:
+            pts = np.asarray(records, dtype=np.uint64).reshape(-1, self.arith.PW)
+        pts = np.ascontiguousarray(pts)
+        if need is not None and pts.shape[0] != need:
+            raise RuntimeError("verify_wire_mixed: %d wire points, the shapes in ms need %d" % (pts.shape[0], need))
+        sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 3, 4)
+        if sc.shape[0] != count:
+            raise RuntimeError("verify_wire_mixed: one scalar triple per proof record")
+        ok = np.zeros(count, dtype=np.uint32)
+        check(_lib.lib().bpp_range_verify_batch_mixed(self.handle, _ptr(pts), _ptr(sc), _ptr(m), count, _ptr(ok)),
+              "bpp_range_verify_batch_mixed")
+        return ok
+
     def sum_partials_device(self, d_partials: int, n: int, d_ok: int, stream: int = 0):
         check(_lib.lib().bpp_verifier_sum_partials(self.handle, d_partials, n, d_ok, stream or None),
               "bpp_verifier_sum_partials")

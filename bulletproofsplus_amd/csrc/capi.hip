@@ -634,6 +634,68 @@ extern "C" int bpp_range_verify_batch(bpp_verifier* v, const uint64_t* points, c
     return BPP_OK;
 }
 
+// ---- mixed batches: proof i of shape (n, m_i) against the verifier's (n, m) tables (mixed.hpp) ------------------
+extern "C" size_t bpp_verifier_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
+    if (count && !m_of) return 0;
+    return size_for(v, [&](auto cv) { return VerifyImpl<decltype(cv)>::mixed_workspace_bytes(v, m_of, count); });
+}
+
+extern "C" int bpp_verifier_run_mixed(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars,
+                                      const uint32_t* m_of, size_t count, const uint64_t* d_challenges, uint32_t* d_ok,
+                                      void* d_workspace, size_t workspace_bytes, uint64_t* d_out_result, void* stream) {
+    if (!v) return fail(BPP_E_ARG, "null argument");
+    if (count == 0) return BPP_OK;
+    if (!d_points || !d_scalars || !m_of || !d_ok || !d_workspace) return fail(BPP_E_ARG, "null argument");
+    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    return on_ctx(v->ctx, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::run_mixed(v, d_points, d_scalars, m_of, count, d_challenges, d_ok, d_workspace,
+                                                   workspace_bytes, d_out_result, static_cast<hipStream_t>(stream));
+    });
+}
+
+extern "C" int bpp_verifier_derive_challenges_mixed(bpp_verifier* v, const uint64_t* d_points, const uint32_t* m_of,
+                                                    size_t count, uint64_t* d_challenges, void* d_workspace,
+                                                    size_t workspace_bytes, void* stream) {
+    if (!v) return fail(BPP_E_ARG, "null argument");
+    if (count == 0) return BPP_OK;
+    if (!d_points || !m_of || !d_challenges || !d_workspace) return fail(BPP_E_ARG, "null argument");
+    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    return on_ctx(v->ctx, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::derive_challenges_mixed(v, d_points, m_of, count, d_challenges, d_workspace,
+                                                                 workspace_bytes, static_cast<hipStream_t>(stream));
+    });
+}
+
+extern "C" int bpp_range_verify_batch_mixed(bpp_verifier* v, const uint64_t* points, const uint64_t* scalars,
+                                            const uint32_t* m_of, size_t count, uint32_t* out_ok) {
+    if (!v) return fail(BPP_E_ARG, "null argument");
+    if (count == 0) return BPP_OK;
+    if (!points || !scalars || !m_of || !out_ok) return fail(BPP_E_ARG, "null argument");
+    const size_t wsb = bpp_verifier_mixed_workspace_bytes(v, m_of, count);
+    if (!wsb) {   // an m_i the verifier does not take: the plan names the proof
+        MixedPlan p;
+        const int rc = mixed_plan(v->s, m_of, count, false, p);
+        return rc ? rc : fail(BPP_E_ARG, "mixed batch rejected");
+    }
+    HIPCHK(hipSetDevice(v->ctx.device));
+    const size_t pw = (size_t)bpp_point_words(v->ctx.curve) * 8;
+    size_t npts = 0;
+    const uint32_t logn = v->s.k - (uint32_t)__builtin_ctz(v->s.m);
+    for (size_t i = 0; i < count; i++) npts += 3 + 2 * (logn + (uint32_t)__builtin_ctz(m_of[i])) + m_of[i];
+    DevBuf dp, ds, dok, dws;
+    HIPCHK(dp.alloc(npts * pw));
+    HIPCHK(ds.alloc(count * 3 * 32));
+    HIPCHK(dok.alloc(count * 4));
+    HIPCHK(dws.alloc(wsb));
+    HIPCHK(hipMemcpy(dp.p, points, npts * pw, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ds.p, scalars, count * 3 * 32, hipMemcpyHostToDevice));
+    int rc = bpp_verifier_run_mixed(v, static_cast<const uint64_t*>(dp.p), static_cast<const uint64_t*>(ds.p), m_of, count,
+                                    nullptr, dok.u32(), dws.p, wsb, nullptr, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(out_ok, dok.p, count * 4, hipMemcpyDeviceToHost));
+    return BPP_OK;
+}
+
 // ---- compressed point encodings (codec.hpp) ---------------------------------------------------------------
 extern "C" size_t bpp_point_compressed_bytes(int curve_id) {
     switch (curve_id) {

@@ -228,6 +228,7 @@ inline int make_shape(size_t n, size_t m, int c, const uint32_t* fr_modw, int fr
     const uint64_t per_f = (uint64_t)(s.W - 1) * s.half + s.top;
     if (per_f >> 32) return fail(BPP_E_ARG, "window table too large");
     s.per_f = (uint32_t)per_f;
+    s.hgap = 0;
     return BPP_OK;
 }
 
@@ -235,11 +236,13 @@ inline int make_shape(size_t n, size_t m, int c, const uint32_t* fr_modw, int fr
 template <class C>
 inline int launch_verify_scalars(const VerifyShape& s, const uint32_t* d_proof_scalars, const uint32_t* d_challenges,
                                  uint32_t ch_stride, uint32_t* d_out, size_t count, uint32_t* d_prep, hipStream_t st) {
-    static bool lds_opted_in = false;   // above the default dynamic-LDS limit: opt in once (160 KB per CU on gfx950)
-    if (vs_lds_bytes<C>(s) > 64 * 1024 && !lds_opted_in) {
+    // above the default dynamic-LDS limit: opt in (160 KB per CU on gfx950) to the largest shape seen so far -- the
+    // passes of a mixed batch (bpp_verifier_run_mixed) run the smaller shapes first
+    static size_t lds_opted_in = 64 * 1024;
+    if (vs_lds_bytes<C>(s) > lds_opted_in) {
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vs_expand<C>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)vs_lds_bytes<C>(s)));
-        lds_opted_in = true;
+        lds_opted_in = vs_lds_bytes<C>(s);
     }
     hipLaunchKernelGGL(k_vs_prepare<C>, dim3(cdiv(count, 64)), dim3(64), 0, st, s, d_proof_scalars, d_challenges, ch_stride,
                        d_prep, d_out, count);

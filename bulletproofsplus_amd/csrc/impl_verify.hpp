@@ -7,6 +7,7 @@
 #include "combined.hpp"
 #include "fixed_launch.hpp"
 #include "host_util.hpp"
+#include "mixed.hpp"
 #include "pippenger.hpp"
 #include "prover_batch.hpp"
 
@@ -15,12 +16,24 @@ enum { BPP_STAGE_FROM_WIRE = 0, BPP_STAGE_SCALARS, BPP_STAGE_FIXED_MSM, BPP_STAG
        BPP_NUM_STAGES };
 constexpr int BPP_PROFILE_SLOTS = 64;  // passes remembered by the event ring
 
+namespace bpp {
+// the shape of one pass: the verifier's own (n, m), or a prefix view (n, m') of its tables (mixed.hpp)
+struct PassShape {
+    VerifyShape s;                // hgap = n (m - m') for a view
+    const uint32_t* challenges;   // the shape's default challenges (device)
+    TranscriptState tr0;          // transcript state after the domain, curve, (n, m') and the digest of the prefix key
+};
+}  // namespace bpp
+
 struct bpp_verifier {
     bpp_ctx ctx;
     bpp::VerifyShape s;
     bpp::DevBuf table;       // window tables
     bpp::DevBuf challenges;  // default challenges
     bpp::TranscriptState tr0;   // transcript state after the domain, curve, (n, m) and generator digest
+    // the prefix views (n, m') of the tables, m' = 1, 2, 4, .. < m (index log2 m'), and their default challenges
+    std::vector<bpp::PassShape> views;
+    bpp::DevBuf view_challenges;
     size_t table_bytes = 0;
     // bpp_verifier_set_subgroup_check: wire points outside the prime-order subgroup count as invalid points (off by
     // default: the in-memory API takes points that are in the group by construction, as the reference's mcl values are)
@@ -106,9 +119,23 @@ struct VerifyImpl {
     static int create(const bpp_ctx& ctx, const uint64_t* gh, const uint64_t* G, const uint64_t* H, size_t n, size_t m,
                       int window_bits, bpp_verifier** out);
 
-    static int run(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
+    // the verifier's own shape, as a pass takes it
+    static PassShape own(const bpp_verifier* v) { return PassShape{v->s, v->challenges.u32(), v->tr0}; }
+    // the shape of class c (m' = 2^c) of a mixed batch: a prefix view, or the verifier's own shape
+    static PassShape class_shape(const bpp_verifier* v, uint32_t c) {
+        return c < v->views.size() ? v->views[c] : own(v);
+    }
+
+    // one pass over `count` proofs of shape ps (run(v, ...): the verifier's own)
+    static int run(bpp_verifier* v, const PassShape& ps, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
                    const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace, size_t workspace_bytes,
                    uint64_t* d_out_scalars, uint64_t* d_out_result, hipStream_t st);
+    static int run(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
+                   const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace, size_t workspace_bytes,
+                   uint64_t* d_out_scalars, uint64_t* d_out_result, hipStream_t st) {
+        return run(v, own(v), d_points, d_scalars, count, d_challenges, d_ok, d_workspace, workspace_bytes, d_out_scalars,
+                   d_out_result, st);
+    }
 
     // form of the Horner stage for a pass over `count` proofs (k_fixed_msm's horner_tree: 0, 1 or 2)
     static uint32_t horner_form(const VerifyShape& s, size_t count) {
@@ -144,8 +171,8 @@ struct VerifyImpl {
     // wire, their tables forked onto the side stream (the caller joins them before k_var_windows), the verifier scalars
     // into w_sc.  L: the pass's layout (WsLayout, CombLayout or GroupLayout), whose pts, bad, prep, vtbl and vscr it uses.
     template <class Layout>
-    static int begin_pass(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
-                          const uint64_t* d_challenges, uint8_t* ws, const Layout& L, uint32_t* w_sc,
+    static int begin_pass(bpp_verifier* v, const PassShape& ps, const uint64_t* d_points, const uint64_t* d_scalars,
+                          size_t count, const uint64_t* d_challenges, uint8_t* ws, const Layout& L, uint32_t* w_sc,
                           std::unique_lock<std::mutex>& aux_lock, hipStream_t st, hipEvent_t* ev);
     // The weighted checks' middle (run_combined, grouped_begin): the weights, then -- after fixed_sums(w_wt), which enqueues
     // the caller's fixed-generator sums -- the weighted proof-point scalars, their digits and, once the tables have joined,
@@ -157,12 +184,57 @@ struct VerifyImpl {
     // one level of k_comb_window_fold: the window sums (`per` each) of every `step` neighbouring proofs of `nrem` added
     // into one; returns how many sums per window are left
     static size_t fold_windows(const uint32_t* in, size_t nrem, uint32_t step, uint32_t* out, uint32_t per, hipStream_t st);
-    static int finish(bpp_verifier* v, uint8_t* ws, const WsLayout& L, size_t count, const uint32_t* w_sc,
-                      const uint32_t* w_vw, const uint32_t* w_bad, uint32_t* d_ok, uint32_t* d_out_result, uint32_t tree,
-                      bool lone, hipStream_t st, hipEvent_t* ev);
+    static int finish(bpp_verifier* v, const VerifyShape& s, uint8_t* ws, const WsLayout& L, size_t count,
+                      const uint32_t* w_sc, const uint32_t* w_vw, const uint32_t* w_bad, uint32_t* d_ok,
+                      uint32_t* d_out_result, uint32_t tree, bool lone, hipStream_t st, hipEvent_t* ev);
 
+    static int derive_challenges(bpp_verifier* v, const PassShape& ps, const uint64_t* d_points, size_t count,
+                                 uint64_t* d_challenges, hipStream_t st);
     static int derive_challenges(bpp_verifier* v, const uint64_t* d_points, size_t count, uint64_t* d_challenges,
-                                 hipStream_t st);
+                                 hipStream_t st) {
+        return derive_challenges(v, own(v), d_points, count, d_challenges, st);
+    }
+
+    // ---- mixed batches (mixed.hpp): proof i of shape (n, m_i), m_i a power of two <= m ---------------------------
+    // workspace = per-proof index | gathered records | scalars | challenges | verdicts | result points | one class
+    // pass's workspace (the classes run one after the other on the caller's stream and share it)
+    struct MixedLayout {
+        size_t idx, pts, scalars, challenges, ok, result, run, total;
+    };
+    static MixedLayout mixed_layout(const bpp_verifier* v, const MixedPlan& p, size_t count) {
+        MixedLayout w;
+        WsCarver o;
+        w.idx = o.take(count * MX_WORDS * 4);
+        w.pts = o.take(p.points * WW * 4);
+        w.scalars = o.take(count * 96);
+        w.challenges = o.take(p.chals * 32);
+        w.ok = o.take(count * 4);
+        w.result = o.take(count * WW * 4);
+        size_t run = 0;
+        for (uint32_t c = 0; c < MIXED_CLASSES; c++)
+            if (p.count[c]) run = std::max(run, ws_layout(class_shape(v, c).s, p.count[c]).total);
+        w.run = o.take(run);
+        w.total = o.total;
+        return w;
+    }
+    // 0 for an m_of the verifier does not take
+    static size_t mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
+        MixedPlan p;
+        if (mixed_plan(v->s, m_of, count, false, p)) return 0;
+        return mixed_layout(v, p, count).total;
+    }
+    // d_challenges: NULL or 3 + k_i scalars per proof, packed in caller order; d_ok, d_out_result (may be NULL) in caller
+    // order.  Uploads the per-proof index (blocking the host until the copy has read it), the rest is enqueued on st.
+    static int run_mixed(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, const uint32_t* m_of,
+                         size_t count, const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace,
+                         size_t workspace_bytes, uint64_t* d_out_result, hipStream_t st);
+    // d_challenges: 3 + k_i scalars per proof, packed in caller order (the layout run_mixed takes)
+    static int derive_challenges_mixed(bpp_verifier* v, const uint64_t* d_points, const uint32_t* m_of, size_t count,
+                                       uint64_t* d_challenges, void* d_workspace, size_t workspace_bytes, hipStream_t st);
+    // the shared head of both: plan, workspace check, index upload, gather (d_scalars null: points only)
+    static int mixed_gather(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, const uint32_t* m_of,
+                            size_t count, const uint64_t* d_challenges, void* d_workspace, size_t workspace_bytes,
+                            hipStream_t st, MixedPlan& p, MixedLayout& L);
 
     // ---- RangeProof::verify over SERIALIZED proofs resident in HBM (codec.hpp: the container) ---------------
     // workspace = decoded records | scalars | decoder status | challenges (transcript mode) | run()'s workspace
@@ -400,6 +472,35 @@ int VerifyImpl<C>::create(const bpp_ctx& ctx, const uint64_t* gh, const uint64_t
     default_challenges(s, ch);
     e = v->challenges.alloc(ch.size() * 4);
     if (e == hipSuccess) e = hipMemcpy(v->challenges.p, ch.data(), ch.size() * 4, hipMemcpyHostToDevice);
+    // the prefix views (n, m') of the same tables, m' < m (bpp_verifier_run_mixed): the prover of shape (n, m') hashes
+    // its own key [g, h, G_0..G_{nm'-1}, H_0..H_{nm'-1}] and m' into the transcript, and its default challenges are
+    // those of its shape
+    std::vector<uint32_t> vch;
+    std::vector<size_t> voff;
+    for (uint32_t mp = 1; mp < s.m; mp <<= 1) {
+        PassShape ps{};
+        rc = make_shape(n, mp, window_bits, C::Fr::MODW, C::Fr::BITS, ps.s);
+        if (rc) {
+            delete v;
+            return rc;
+        }
+        ps.s.hgap = s.n * (s.m - mp);
+        std::vector<uint64_t> prefix((size_t)ps.s.NF * PW);
+        std::memcpy(prefix.data(), fixed.data(), (size_t)(2 + ps.s.mn) * PW * 8);
+        std::memcpy(prefix.data() + (size_t)(2 + ps.s.mn) * PW, fixed.data() + (size_t)(2 + s.mn) * PW,
+                    (size_t)ps.s.mn * PW * 8);
+        tr_initial_state<C>(ps.s.n, ps.s.m, reinterpret_cast<const uint32_t*>(prefix.data()), ps.s.NF, ps.tr0.st);
+        std::vector<uint32_t> c1;
+        default_challenges(ps.s, c1);
+        voff.push_back(vch.size());
+        vch.insert(vch.end(), c1.begin(), c1.end());
+        v->views.push_back(ps);
+    }
+    if (e == hipSuccess && !vch.empty()) {
+        e = v->view_challenges.alloc(vch.size() * 4);
+        if (e == hipSuccess) e = hipMemcpy(v->view_challenges.p, vch.data(), vch.size() * 4, hipMemcpyHostToDevice);
+        for (size_t i = 0; i < v->views.size(); i++) v->views[i].challenges = v->view_challenges.u32() + voff[i];
+    }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) {
@@ -412,10 +513,10 @@ int VerifyImpl<C>::create(const bpp_ctx& ctx, const uint64_t* gh, const uint64_t
 
 template <class C>
 template <class Layout>
-int VerifyImpl<C>::begin_pass(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
-                              const uint64_t* d_challenges, uint8_t* ws, const Layout& L, uint32_t* w_sc,
+int VerifyImpl<C>::begin_pass(bpp_verifier* v, const PassShape& ps, const uint64_t* d_points, const uint64_t* d_scalars,
+                              size_t count, const uint64_t* d_challenges, uint8_t* ws, const Layout& L, uint32_t* w_sc,
                               std::unique_lock<std::mutex>& aux_lock, hipStream_t st, hipEvent_t* ev) {
-    const VerifyShape& s = v->s;
+    const VerifyShape& s = ps.s;
     uint32_t* w_pts = reinterpret_cast<uint32_t*>(ws + L.pts);
     uint32_t* w_bad = reinterpret_cast<uint32_t*>(ws + L.bad);
     const size_t npts = count * s.NV;
@@ -431,7 +532,7 @@ int VerifyImpl<C>::begin_pass(bpp_verifier* v, const uint64_t* d_points, const u
     int rc = fork_tables(v, st, w_pts, reinterpret_cast<uint32_t*>(ws + L.vtbl), reinterpret_cast<uint32_t*>(ws + L.vscr),
                          npts, aux_lock);
     if (rc) return rc;
-    const uint32_t* ch = d_challenges ? reinterpret_cast<const uint32_t*>(d_challenges) : v->challenges.u32();
+    const uint32_t* ch = d_challenges ? reinterpret_cast<const uint32_t*>(d_challenges) : ps.challenges;
     const uint32_t ch_stride = d_challenges ? (3 + s.k) * 8 : 0;
     HIPCHK(mark(ev, 2 * BPP_STAGE_SCALARS, st));
     rc = launch_verify_scalars<C>(s, reinterpret_cast<const uint32_t*>(d_scalars), ch, ch_stride, w_sc, count,
@@ -477,10 +578,10 @@ size_t VerifyImpl<C>::fold_windows(const uint32_t* in, size_t nrem, uint32_t ste
 }
 
 template <class C>
-int VerifyImpl<C>::run(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
-               const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace, size_t workspace_bytes,
-               uint64_t* d_out_scalars, uint64_t* d_out_result, hipStream_t st) {
-    const VerifyShape& s = v->s;
+int VerifyImpl<C>::run(bpp_verifier* v, const PassShape& ps, const uint64_t* d_points, const uint64_t* d_scalars,
+                       size_t count, const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace,
+                       size_t workspace_bytes, uint64_t* d_out_scalars, uint64_t* d_out_result, hipStream_t st) {
+    const VerifyShape& s = ps.s;
     const WsLayout L = ws_layout(s, count);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
@@ -497,7 +598,7 @@ int VerifyImpl<C>::run(bpp_verifier* v, const uint64_t* d_points, const uint64_t
     }
     v->last_blocks_per_proof = bpp_;
     std::unique_lock<std::mutex> aux_lock;
-    int rc = begin_pass(v, d_points, d_scalars, count, d_challenges, ws, L, w_sc, aux_lock, st, ev);
+    int rc = begin_pass(v, ps, d_points, d_scalars, count, d_challenges, ws, L, w_sc, aux_lock, st, ev);
     if (rc) return rc;
     // proof-point MSM: digits, per-point tables, window sums (all arithmetic bound, so they simply run in
     // sequence); its latency-bound Horner stage rides in the first blocks of the fixed-generator launch
@@ -522,16 +623,16 @@ int VerifyImpl<C>::run(bpp_verifier* v, const uint64_t* d_points, const uint64_t
     hipLaunchKernelGGL(k_var_windows<C>, dim3(cdiv(vlanes, VAR_BLOCK)), dim3(VAR_BLOCK), 0, st, s, w_vd, w_vt, w_vw,
                        vlanes, tree == 1 ? 1u : 0u, vgroups);
     HIPCHK(mark(ev, 2 * BPP_STAGE_VAR_MSM + 1, st));
-    return finish(v, ws, L, count, w_sc, w_vw, w_bad, d_ok, reinterpret_cast<uint32_t*>(d_out_result), tree, lone, st, ev);
+    return finish(v, s, ws, L, count, w_sc, w_vw, w_bad, d_ok, reinterpret_cast<uint32_t*>(d_out_result), tree, lone, st,
+                  ev);
 }
 
 // The rest of a pass, from the scalars [count][N] and the proof points' window sums: the fixed-generator MulVec with the
 // Horner stage in its leading blocks, the folds of its partials, the verdicts.  ws / L: a workspace laid out for `count`.
 template <class C>
-int VerifyImpl<C>::finish(bpp_verifier* v, uint8_t* ws, const WsLayout& L, size_t count, const uint32_t* w_sc,
-                          const uint32_t* w_vw, const uint32_t* w_bad, uint32_t* d_ok, uint32_t* d_out_result, uint32_t tree,
-                          bool lone, hipStream_t st, hipEvent_t* ev) {
-    const VerifyShape& s = v->s;
+int VerifyImpl<C>::finish(bpp_verifier* v, const VerifyShape& s, uint8_t* ws, const WsLayout& L, size_t count,
+                          const uint32_t* w_sc, const uint32_t* w_vw, const uint32_t* w_bad, uint32_t* d_ok,
+                          uint32_t* d_out_result, uint32_t tree, bool lone, hipStream_t st, hipEvent_t* ev) {
     const unsigned bpp_ = blocks_per_proof(s, count);
     uint32_t* w_fp = reinterpret_cast<uint32_t*>(ws + L.fpart);
     uint32_t* w_vp = reinterpret_cast<uint32_t*>(ws + L.vpart);
@@ -616,10 +717,81 @@ int VerifyImpl<C>::run_serialized(bpp_verifier* v, const uint8_t* d_proofs, cons
 }
 
 template <class C>
-int VerifyImpl<C>::derive_challenges(bpp_verifier* v, const uint64_t* d_points, size_t count, uint64_t* d_challenges,
-                             hipStream_t st) {
-    hipLaunchKernelGGL(k_transcript_challenges<C>, dim3(cdiv(count, 64)), dim3(64), 0, st, v->s, v->tr0,
+int VerifyImpl<C>::derive_challenges(bpp_verifier* v, const PassShape& ps, const uint64_t* d_points, size_t count,
+                                     uint64_t* d_challenges, hipStream_t st) {
+    (void)v;
+    hipLaunchKernelGGL(k_transcript_challenges<C>, dim3(cdiv(count, 64)), dim3(64), 0, st, ps.s, ps.tr0,
                        reinterpret_cast<const uint32_t*>(d_points), reinterpret_cast<uint32_t*>(d_challenges), count);
+    HIPCHK(hipGetLastError());
+    return BPP_OK;
+}
+
+template <class C>
+int VerifyImpl<C>::mixed_gather(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, const uint32_t* m_of,
+                                size_t count, const uint64_t* d_challenges, void* d_workspace, size_t workspace_bytes,
+                                hipStream_t st, MixedPlan& p, MixedLayout& L) {
+    int rc = mixed_plan(v->s, m_of, count, true, p);
+    if (rc) return rc;
+    L = mixed_layout(v, p, count);
+    if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
+    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+    // pageable source: the copy has read it when the call returns
+    HIPCHK(hipMemcpyAsync(ws + L.idx, p.idx.data(), p.idx.size() * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_mixed_gather<C>, dim3((unsigned)count), dim3(MIXED_BLOCK), 0, st,
+                       reinterpret_cast<const uint32_t*>(ws + L.idx), count, d_points, d_scalars, d_challenges,
+                       reinterpret_cast<uint64_t*>(ws + L.pts), reinterpret_cast<uint64_t*>(ws + L.scalars),
+                       reinterpret_cast<uint64_t*>(ws + L.challenges));
+    HIPCHK(hipGetLastError());
+    return BPP_OK;
+}
+
+// Gather, then today's pass over each class's contiguous region with the class's view (Horner form, lone batch and
+// blocks per proof follow the class's own count), then the verdicts and result points back into caller order.
+template <class C>
+int VerifyImpl<C>::run_mixed(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, const uint32_t* m_of,
+                             size_t count, const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace,
+                             size_t workspace_bytes, uint64_t* d_out_result, hipStream_t st) {
+    MixedPlan p;
+    MixedLayout L;
+    int rc = mixed_gather(v, d_points, d_scalars, m_of, count, d_challenges, d_workspace, workspace_bytes, st, p, L);
+    if (rc) return rc;
+    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+    auto U64 = [&](size_t off) { return reinterpret_cast<uint64_t*>(ws + off); };
+    uint32_t* w_ok = reinterpret_cast<uint32_t*>(ws + L.ok);
+    for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
+        if (!p.count[c]) continue;
+        const PassShape ps = class_shape(v, c);
+        rc = run(v, ps, U64(L.pts) + p.pt[c] * PW, U64(L.scalars) + p.first[c] * 12, p.count[c],
+                 d_challenges ? U64(L.challenges) + p.chal[c] * 4 : nullptr, w_ok + p.first[c], ws + L.run,
+                 workspace_bytes - L.run, nullptr, d_out_result ? U64(L.result) + p.first[c] * PW : nullptr, st);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_mixed_scatter<C>, dim3(cdiv(count, 4)), dim3(256), 0, st,
+                       reinterpret_cast<const uint32_t*>(ws + L.idx), count, w_ok, d_out_result ? U64(L.result) : nullptr,
+                       nullptr, d_ok, d_out_result, nullptr);
+    HIPCHK(hipGetLastError());
+    return BPP_OK;
+}
+
+template <class C>
+int VerifyImpl<C>::derive_challenges_mixed(bpp_verifier* v, const uint64_t* d_points, const uint32_t* m_of, size_t count,
+                                           uint64_t* d_challenges, void* d_workspace, size_t workspace_bytes,
+                                           hipStream_t st) {
+    MixedPlan p;
+    MixedLayout L;
+    int rc = mixed_gather(v, d_points, nullptr, m_of, count, nullptr, d_workspace, workspace_bytes, st, p, L);
+    if (rc) return rc;
+    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+    auto U64 = [&](size_t off) { return reinterpret_cast<uint64_t*>(ws + off); };
+    for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
+        if (!p.count[c]) continue;
+        rc = derive_challenges(v, class_shape(v, c), U64(L.pts) + p.pt[c] * PW, p.count[c], U64(L.challenges) + p.chal[c] * 4,
+                               st);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_mixed_scatter<C>, dim3(cdiv(count, 4)), dim3(256), 0, st,
+                       reinterpret_cast<const uint32_t*>(ws + L.idx), count, nullptr, nullptr, U64(L.challenges), nullptr,
+                       nullptr, d_challenges);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
@@ -640,7 +812,7 @@ int VerifyImpl<C>::run_combined(bpp_verifier* v, const uint64_t* d_points, const
     uint32_t* w_fp = reinterpret_cast<uint32_t*>(ws + L.fpart);
     HIPCHK(zero_words_async(w_cs, (size_t)s.N * 32, st));
     std::unique_lock<std::mutex> aux_lock;
-    int rc = begin_pass(v, d_points, d_scalars, count, d_challenges, ws, L, w_sc, aux_lock, st, nullptr);
+    int rc = begin_pass(v, own(v), d_points, d_scalars, count, d_challenges, ws, L, w_sc, aux_lock, st, nullptr);
     if (rc) return rc;
     rc = weighted_windows(v, ws, L, count, weight_key, index_base, d_weights, var_wsums<C>(), 1u, aux_lock, st,
                           [&](const uint32_t* w_wt) {
@@ -692,7 +864,7 @@ int VerifyImpl<C>::grouped_begin(bpp_verifier* v, const uint64_t* d_points, cons
     uint32_t *w_bad = W(L.bad), *w_sc = W(L.scalars), *w_rows = W(L.grows), *w_gbad = W(L.gbad), *w_gok = W(L.gok);
     const size_t G = L.groups;
     std::unique_lock<std::mutex> aux_lock;
-    int rc = begin_pass(v, d_points, d_scalars, count, d_challenges, ws, L, w_sc, aux_lock, st, nullptr);
+    int rc = begin_pass(v, own(v), d_points, d_scalars, count, d_challenges, ws, L, w_sc, aux_lock, st, nullptr);
     if (rc) return rc;
     const uint32_t tree = horner_form(s, G);
     const uint32_t per = tree == 1 ? var_wsums<C>() : var_windows<C>();   // window sums per proof, in the layout the Horner form reads
@@ -712,7 +884,7 @@ int VerifyImpl<C>::grouped_begin(bpp_verifier* v, const uint64_t* d_points, cons
         nrem = fold_windows(cur, nrem, step, nxt, per, st);
         left /= step;
     }
-    rc = finish(v, ws + L.tail, ws_layout(s, G), G, w_rows, cur, w_gbad, w_gok, nullptr, tree, false, st, nullptr);
+    rc = finish(v, s, ws + L.tail, ws_layout(s, G), G, w_rows, cur, w_gbad, w_gok, nullptr, tree, false, st, nullptr);
     if (rc) return rc;
     hipLaunchKernelGGL(k_comb_group_spread, dim3(cdiv(count, 256)), dim3(256), 0, st, w_gok, group, d_out_verdicts, count);
     HIPCHK(hipGetLastError());

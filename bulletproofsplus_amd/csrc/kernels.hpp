@@ -363,7 +363,14 @@ struct VerifyShape {
     uint32_t top;              // entries of the top window (its digit is unsigned: 0..top)
     uint32_t per_f;            // table entries per generator: (W-1) * half + top
     uint32_t bias[10];         // sum_{j < W-1} half * 2^(c j) as 32-bit words (signed-digit recoding bias)
+    uint32_t hgap;             // table H block - this shape's H block: mn_table - mn (a prefix view of a larger table), else 0
 };
+
+// table slot of fixed generator f of shape s: a prefix view (n, m') of an (n, m) table finds g, h and G_0.. where they
+// are, and its H_i hgap = n (m - m') generators further on
+__host__ __device__ __forceinline__ uint32_t table_generator(const VerifyShape& s, uint32_t f) {
+    return f + (f >= 2 + s.mn ? s.hgap : 0u);
+}
 
 // index of fixed generator f (0 = g, 1 = h, 2.. = G_i, 2+mn.. = H_i) in the MulVec
 __host__ __device__ __forceinline__ uint32_t fixed_term_index(const VerifyShape& s, uint32_t f) {
@@ -1165,7 +1172,7 @@ __global__ void __launch_bounds__(FIXED_BLOCK, fixed_waves<C>()) k_fixed_msm(Ver
             if (x < NFc && dg != 0) {
                 const uint32_t f = gen_of(x);
                 const uint32_t mag = dg < 0 ? (uint32_t)(-dg) : (uint32_t)dg;
-                src = table + ((size_t)f * s.per_f + (size_t)ji * s.half + (mag - 1)) * 2 * N;
+                src = table + ((size_t)table_generator(s, f) * s.per_f + (size_t)ji * s.half + (mag - 1)) * 2 * N;
                 valid = 1;
                 neg = (dg < 0 ? 1u : 0u) ^ (f >= neg_from ? 1u : 0u);
             }
@@ -1193,7 +1200,7 @@ __global__ void __launch_bounds__(FIXED_BLOCK, fixed_waves<C>()) k_fixed_msm(Ver
                 const int32_t dg = jx + 1 < s.W ? (int32_t)(we[0] & mask) - (int32_t)s.half : (int32_t)we[0];
                 if (dg != 0) {
                     const uint32_t mag = dg < 0 ? (uint32_t)(-dg) : (uint32_t)dg;
-                    src = table + ((size_t)f * s.per_f + (size_t)jx * s.half + (mag - 1)) * 2 * N;
+                    src = table + ((size_t)table_generator(s, f) * s.per_f + (size_t)jx * s.half + (mag - 1)) * 2 * N;
                     valid = 1;
                     neg = (dg < 0 ? 1u : 0u) ^ (f >= neg_from ? 1u : 0u);
                 }

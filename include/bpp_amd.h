@@ -203,6 +203,44 @@ int bpp_verifier_run(bpp_verifier *v, const uint64_t *d_points, const uint64_t *
                      const uint64_t *d_challenges, uint32_t *d_ok, void *d_workspace,
                      size_t workspace_bytes, uint64_t *d_out_scalars, uint64_t *d_out_result,
                      void *stream);
+/* ---- mixed batches: proofs of several aggregation sizes against ONE verifier's tables ----
+ * A verifier created for (n, m) -- its "capacity" -- also verifies batches in which proof i has m_i commitments, m_i a
+ * power of two <= m.  Proof i's verdict is RangeProof::verify(proof_i, PublicKey::new(n m_i), n, V_i)
+ * (src/range/mod.rs:57-78, :189-238, :405-510): the verdict against the PREFIX key of the proof's own shape, i.e. the
+ * first n m_i generators of the verifier's G and H vectors with its g and h (PublicKey::new(L) is a prefix of every
+ * longer key, src/publickey.rs:21-48; so is bpp_pk_hashed(label, .), which derives each generator from its index).  No
+ * table memory beyond the verifier's own is used: the tables of (n, m) hold every generator a shape (n, m_i) needs.
+ *   m_of        : HOST array of count values m_i (the caller has parsed the proofs)
+ *   d_points    : proof i's record [A, wip.A, wip.B, L.., R.., V_0..V_{m_i-1}] (3 + 2 k_i + m_i wire points,
+ *                 k_i = log2(n m_i)) at wire point sum_{j<i} (3 + 2 k_j + m_j): packed, in caller order
+ *   d_scalars   : count x 3 scalars [r', s', delta']
+ *   d_challenges: NULL (the reference's literals for each proof's own shape) or 3 + k_i scalars [y, z, e, e_1..e_k]
+ *                 per proof, packed in caller order
+ *   d_ok        : count x uint32_t in caller order, 0 = Ok(()) / 1 = Err(VerificationError)
+ *   d_out_result: NULL or count x wire point, the MulVec result of each proof, in caller order
+ *   d_workspace : bpp_verifier_mixed_workspace_bytes(v, m_of, count) bytes (0 when an m_i is not taken)
+ * An m_i that is zero, not a power of two or larger than m, a workspace that is too small or a NULL pointer returns
+ * BPP_E_ARG, with the offending proof's index in bpp_last_error(), and enqueues nothing; count = 0 is BPP_OK.
+ * The call BLOCKS the host while it uploads the per-proof index array (32 bytes per proof, a pageable copy on `stream`,
+ * which first waits for the work already queued there); everything else is enqueued asynchronously on `stream`: the
+ * gather of the records into one region per m_i (k_mixed_gather), one pass of bpp_verifier_run per m_i present over its
+ * region, the verdicts back into caller order (k_mixed_scatter).  bpp_verifier_set_subgroup_check applies as it does to
+ * bpp_verifier_run.  Several host threads may use one verifier at once, each call with a workspace and buffers of its
+ * own, as for bpp_verifier_run. */
+size_t bpp_verifier_mixed_workspace_bytes(const bpp_verifier *v, const uint32_t *m_of, size_t count);
+int bpp_verifier_run_mixed(bpp_verifier *v, const uint64_t *d_points, const uint64_t *d_scalars, const uint32_t *m_of,
+                           size_t count, const uint64_t *d_challenges, uint32_t *d_ok, void *d_workspace,
+                           size_t workspace_bytes, uint64_t *d_out_result, void *stream);
+/* Fiat-Shamir challenges of a mixed batch (see bpp_verifier_derive_challenges): proof i's transcript starts from the
+ * prefix key of its own shape (n, m_i), as its prover's does.  d_challenges: 3 + k_i scalars per proof, packed in caller
+ * order -- the layout bpp_verifier_run_mixed takes.  Arguments, errors and blocking as for bpp_verifier_run_mixed. */
+int bpp_verifier_derive_challenges_mixed(bpp_verifier *v, const uint64_t *d_points, const uint32_t *m_of, size_t count,
+                                         uint64_t *d_challenges, void *d_workspace, size_t workspace_bytes, void *stream);
+/* bpp_verifier_run_mixed on HOST buffers (points, scalars, m_of laid out as above), the reference's literal challenges;
+ * synchronous.  out_ok: count x uint32_t. */
+int bpp_range_verify_batch_mixed(bpp_verifier *v, const uint64_t *points, const uint64_t *scalars, const uint32_t *m_of,
+                                 size_t count, uint32_t *out_ok);
+
 /* The same pass captured ONCE into a HIP graph and replayed: a small batch is a chain of a dozen launches and a stream
  * fork/join that a replay submits in one call.  bpp_verifier_graph_capture runs the pass once eagerly (argument checks;
  * what a pass creates lazily must exist before a capture), captures it on a stream of its own and instantiates the graph;

@@ -1,0 +1,159 @@
+#!/usr/bin/env python3
+"""A block of range proofs with mixed aggregation sizes, verified by ONE verifier (bpp_verifier_run_mixed) against the
+same proofs verified class by class on dedicated verifiers (bpp_verifier_run).
+
+The block: BLS12-381, n = 64, capacity m = 16, window 16; 8 192 distinct proofs made on the device by the batched
+prover, m_i distributed 4096 / 2048 / 1024 / 512 / 512 over m_i = 1 / 2 / 4 / 8 / 16, shuffled, a handful with a flipped
+s'.  Prints one JSON object: both times (device events, after warm-up) with their spread, their ratio, verifies/s of the
+mixed block, the table bytes of the one verifier against the sum of the dedicated ones, and whether the verdict vectors
+are identical.
+usage: python tools/mixed_bench.py [--reps 20] [--warmup 3] [--window 16] [--out profiles/mixed_bench.json]
+       [--mixed-only]   (no dedicated verifiers: the run to put under rocprofv3 --kernel-trace --stats)"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+
+N = 64
+CAP = 16
+MIX = {1: 4096, 2: 2048, 4: 1024, 8: 512, 16: 512}
+
+
+def stats(ms):
+    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms),
+            "stdev_ms": statistics.stdev(ms) if len(ms) > 1 else 0.0, "reps": len(ms)}
+
+
+def timed(torch, fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--window", type=int, default=16)
+    ap.add_argument("--tamper", type=int, default=8, help="proofs with a flipped s'")
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--mixed-only", action="store_true")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    import bulletproofsplus_amd as B
+    dev = torch.device("cuda:0")
+    stream = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
+    rng = np.random.default_rng(args.seed)
+    a = B.Arith("bls12_381")
+    pk = B.PublicKey.new(a, N * CAP)
+    t0 = time.time()
+    cap = B.BatchVerifier(pk, N, CAP, window_bits=args.window)
+    build_s = {"capacity": time.time() - t0}
+    # engines that make (and, for the comparison, verify) each class's proofs: the dedicated (64, m') verifiers
+    ded = {}
+    for m in MIX:
+        if m == CAP:
+            ded[m] = cap
+        elif not args.mixed_only:
+            t0 = time.time()
+            ded[m] = B.BatchVerifier(B.PublicKey.new(a, N * m), N, m, window_bits=args.window)
+            build_s[str(m)] = time.time() - t0
+        else:
+            ded[m] = B.BatchVerifier(B.PublicKey.new(a, N * m), N, m, window_bits=8)   # a prover only
+    recs, scs = {}, {}
+    for m, cnt in MIX.items():
+        # values below 2^31 (RangeProver::commit takes v as i32); every proof distinct
+        vals = rng.integers(0, 1 << 31, size=(cnt, m), dtype=np.uint64)
+        gams = rng.integers(1, 1 << 62, size=(cnt, m, 4), dtype=np.uint64)
+        gams[:, :, 1:] = 0
+        pts, sc, V = ded[m].prove_batch(vals, gams)
+        recs[m] = np.concatenate([pts, V], axis=1)
+        scs[m] = sc
+    if args.mixed_only:
+        for m in MIX:
+            if m != CAP:
+                ded[m].close()
+    # the block in caller order: shuffled, a handful tampered
+    order = [(m, i) for m, cnt in MIX.items() for i in range(cnt)]
+    perm = rng.permutation(len(order))
+    order = [order[p] for p in perm]
+    for t in rng.choice(len(order), size=args.tamper, replace=False):
+        m, i = order[t]
+        scs[m][i, 1, 0] ^= 1
+    count = len(order)
+    ms = [m for m, _ in order]
+    PW = a.PW
+    packed = np.ascontiguousarray(np.concatenate([recs[m][i] for m, i in order]))
+    d_pts = torch.from_numpy(packed.view(np.int64)).to(dev)
+    d_sc = torch.from_numpy(np.ascontiguousarray(np.stack([scs[m][i] for m, i in order])).view(np.int64)).to(dev)
+    d_ok = torch.full((count,), 7, dtype=torch.int32, device=dev)
+    wsb = cap.mixed_workspace_bytes(ms)
+    d_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+
+    def mixed():
+        cap.run_mixed_device(d_pts.data_ptr(), d_sc.data_ptr(), ms, d_ok.data_ptr(), d_ws.data_ptr(), wsb, stream())
+
+    t_mixed = timed(torch, mixed, args.reps, args.warmup)
+    ok_mixed = d_ok.cpu().numpy().astype(np.uint32)
+    res = {"shape": {"curve": "bls12_381", "n": N, "capacity_m": CAP, "window": args.window, "count": count,
+                     "mix": {str(m): c for m, c in MIX.items()}, "tampered": args.tamper},
+           "mixed": stats(t_mixed), "mixed_verifies_per_s": count / (statistics.median(t_mixed) / 1e3),
+           "mixed_rejects": int(ok_mixed.sum()), "table_bytes_one": int(cap.table_bytes),
+           "mixed_workspace_bytes": int(wsb), "build_s": build_s}
+    if not args.mixed_only:
+        # the same proofs, class by class on the dedicated verifiers (class-contiguous buffers prepared up front)
+        pos = {m: [j for j, (mm, _) in enumerate(order) if mm == m] for m in MIX}
+        bufs = {}
+        for m in MIX:
+            cnt = len(pos[m])
+            r = np.ascontiguousarray(np.stack([recs[m][order[j][1]] for j in pos[m]]))
+            s = np.ascontiguousarray(np.stack([scs[m][order[j][1]] for j in pos[m]]))
+            w = ded[m].workspace_bytes(cnt)
+            bufs[m] = (torch.from_numpy(r.view(np.int64)).to(dev), torch.from_numpy(s.view(np.int64)).to(dev),
+                       torch.full((cnt,), 7, dtype=torch.int32, device=dev), torch.empty(w, dtype=torch.uint8, device=dev),
+                       w, cnt)
+
+        def dedicated():
+            for m in MIX:
+                p, s, o, w, wb, cnt = bufs[m]
+                ded[m].run_device(p.data_ptr(), s.data_ptr(), cnt, o.data_ptr(), w.data_ptr(), wb, stream())
+
+        t_ded = timed(torch, dedicated, args.reps, args.warmup)
+        ok_ded = np.zeros(count, dtype=np.uint32)
+        per_class = {}
+        for m in MIX:
+            ok_ded[pos[m]] = bufs[m][2].cpu().numpy().astype(np.uint32)
+            p, s, o, w, wb, cnt = bufs[m]
+            one = timed(torch, lambda: ded[m].run_device(p.data_ptr(), s.data_ptr(), cnt, o.data_ptr(), w.data_ptr(), wb,
+                                                         stream()), max(5, args.reps // 2), 1)
+            per_class[str(m)] = statistics.median(one)
+        res.update({"dedicated": stats(t_ded), "dedicated_per_class_median_ms": per_class,
+                    "ratio_mixed_over_dedicated": statistics.median(t_mixed) / statistics.median(t_ded),
+                    "table_bytes_dedicated_sum": int(sum(ded[m].table_bytes for m in MIX)),
+                    "verdicts_identical": bool(np.array_equal(ok_mixed, ok_ded))})
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
