@@ -9,21 +9,40 @@
 using namespace bpp;
 
 namespace {
-// The entry shim: the calls of a context -- or of a verifier, through its copy v->ctx -- run on its device (a verifier's
-// launches must go to the device that holds its tables), then f(curve tag) on the curve's implementation.
+// The entry shims.  Every entry point past its argument checks runs here: under guarded (abi_guard.hpp), so nothing
+// unwinds across the C ABI, with the caller count `c` bounded before anything is read, laid out, allocated or launched.
+// on_device runs f() on a device; on_ctx runs the calls of a context -- or of a verifier, through its copy v->ctx -- on
+// its device (a verifier's launches must go to the device that holds its tables) as f(curve tag) on the curve's
+// implementation.
 template <class F>
-int on_ctx(const bpp_ctx& ctx, F&& f) {
-    HIPCHK(hipSetDevice(ctx.device));
-    return dispatch(ctx.curve, f);
+int on_device(int device, Count c, F&& f) noexcept {
+    return guarded(c, [&]() -> int {
+        HIPCHK(hipSetDevice(device));
+        return f();
+    });
 }
-// the size getters: f(curve tag), or 0 for a null handle
 template <class F>
-size_t size_for(const bpp_ctx* ctx, F&& f) {
+int on_device(int device, F&& f) noexcept {
+    return on_device(device, Count{0, ""}, f);
+}
+template <class F>
+int on_ctx(const bpp_ctx& ctx, Count c, F&& f) noexcept {
+    return on_device(ctx.device, c, [&] { return dispatch(ctx.curve, f); });
+}
+template <class F>
+int on_ctx(const bpp_ctx& ctx, F&& f) noexcept {
+    return on_ctx(ctx, Count{0, ""}, f);
+}
+// the size getters: f(curve tag), or 0 for a null handle or an exception
+template <class F>
+size_t size_for(const bpp_ctx* ctx, F&& f) noexcept {
     size_t r = 0;
     if (ctx)
-        dispatch(ctx->curve, [&](auto cv) -> int {
-            r = f(cv);
-            return 0;
+        (void)guarded([&] {
+            return dispatch(ctx->curve, [&](auto cv) -> int {
+                r = f(cv);
+                return 0;
+            });
         });
     return r;
 }
@@ -59,20 +78,40 @@ bool scalar_is_canonical(int curve, const uint8_t* b) {
     });
     return lt;
 }
+// The host-pointer verify calls: two host inputs copied to device buffers, the verdicts of `count` proofs and a workspace
+// of wsb bytes allocated, run(d_in0, d_in1, d_ok, d_ws) for the device path, then the verdicts copied to out_ok.
+template <class F>
+int verify_staged(const void* in0, size_t bytes0, const void* in1, size_t bytes1, size_t count, size_t wsb, uint32_t* out_ok,
+                  F&& run) {
+    DevBuf d0, d1, dok, dws;
+    HIPCHK(d0.alloc(bytes0));
+    HIPCHK(d1.alloc(bytes1));
+    HIPCHK(dok.alloc(count * 4));
+    HIPCHK(dws.alloc(wsb));
+    HIPCHK(hipMemcpy(d0.p, in0, bytes0, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d1.p, in1, bytes1, hipMemcpyHostToDevice));
+    const int rc = run(d0.p, d1.p, dok.u32(), dws.p);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(out_ok, dok.p, count * 4, hipMemcpyDeviceToHost));
+    return BPP_OK;
+}
 }  // namespace
 
-extern "C" const char* bpp_last_error(void) { return g_err.c_str(); }
+extern "C" const char* bpp_last_error(void) { return last_error(); }
 
 extern "C" int bpp_init(int curve_id, int device, bpp_ctx** out_ctx) {
     if (!out_ctx) return fail(BPP_E_ARG, "null out_ctx");
     if (curve_id != BPP_BLS12_381_G1 && curve_id != BPP_SECP256K1 && curve_id != BPP_ED25519)
         return fail(BPP_E_ARG, "unknown curve id");
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(BPP_E_HIP, "no such HIP device");
-    HIPCHK(hipSetDevice(device));
-    *out_ctx = new bpp_ctx{curve_id, device};
-    return BPP_OK;
+    return guarded([&]() -> int {
+        int ndev = 0;
+        HIPCHK(hipGetDeviceCount(&ndev));
+        if (device < 0 || device >= ndev) return fail(BPP_E_HIP, "no such HIP device");
+        return on_device(device, [&] {
+            *out_ctx = new bpp_ctx{curve_id, device};
+            return BPP_OK;
+        });
+    });
 }
 // ---- the literal single-call API, second call onwards: a small-table verifier per public key -------------------
 // RangeProof::verify (src/range/mod.rs:57-78) takes the public key with every call and the reference pays the whole
@@ -87,20 +126,14 @@ constexpr int VCACHE_WINDOW = 8;
 struct VerifyCacheEntry {
     uint64_t hash = 0;
     size_t n = 0, m = 0;
-    std::vector<uint64_t> key;   // gh | G | H as handed in
-    bpp_verifier* v = nullptr;   // null: seen once, tables not built yet
-    DevBuf pts, sc, ok, ws;      // count = 1 buffers of the pass
+    std::vector<uint64_t> key;              // gh | G | H as handed in
+    std::unique_ptr<bpp_verifier> v;        // null: seen once, tables not built yet
+    DevBuf pts, sc, ok, ws;                 // count = 1 buffers of the pass
     uint64_t stamp = 0;
 };
 struct VerifyCache {
-    std::vector<VerifyCacheEntry*> e;
+    std::vector<std::unique_ptr<VerifyCacheEntry>> e;
     uint64_t clock = 0;
-    ~VerifyCache() {
-        for (VerifyCacheEntry* x : e) {
-            delete x->v;
-            delete x;
-        }
-    }
 };
 inline uint64_t key_hash(int curve, size_t n, size_t m, const uint64_t* gh, const uint64_t* G, const uint64_t* H, size_t pw) {
     uint64_t h = 0x9E3779B97F4A7C15ull ^ ((uint64_t)curve << 48) ^ ((uint64_t)n << 24) ^ (uint64_t)m;
@@ -137,15 +170,16 @@ extern "C" int bpp_point_words(int curve_id) {
 extern "C" int bpp_msm_batch(bpp_ctx* ctx, const uint64_t* scalars, const uint64_t* points, const uint32_t* lens,
                              size_t count, uint64_t* out) {
     if (!ctx || !out || (count && !lens)) return fail(BPP_E_ARG, "null argument");
-    return on_ctx(*ctx, [&](auto cv) -> int {
+    return on_ctx(*ctx, {count, "count"}, [&](auto cv) -> int {
         return MsmImpl<decltype(cv)>::msm_batch(scalars, points, lens, count, out);
     });
 }
 
 extern "C" int bpp_msm(bpp_ctx* ctx, const uint64_t* scalars, const uint64_t* points, size_t n, uint64_t* out) {
-    if (n > 0xffffffffull) return fail(BPP_E_ARG, "n too large");
-    const uint32_t len = (uint32_t)n;
-    return bpp_msm_batch(ctx, scalars, points, &len, 1, out);
+    return guarded({n, "n"}, [&] {
+        const uint32_t len = (uint32_t)n;
+        return bpp_msm_batch(ctx, scalars, points, &len, 1, out);
+    });
 }
 
 extern "C" int bpp_msm_pippenger(bpp_ctx* ctx, const uint64_t* scalars, const uint64_t* points, size_t n,
@@ -174,38 +208,40 @@ extern "C" int bpp_msm_device(bpp_ctx* ctx, const uint64_t* d_scalars, const uin
 
 extern "C" int bpp_msm_set_profiling(bpp_ctx* ctx, int on) {
     if (!ctx) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    if (on && ctx->msm_events.empty()) {
-        ctx->msm_events.resize(BPP_MSM_SLOTS * (PIP_STAGES + 1));
-        for (hipEvent_t& e : ctx->msm_events) HIPCHK(hipEventCreate(&e));
-    }
-    ctx->msm_profiling = on != 0;
-    ctx->msm_passes = 0;
-    return BPP_OK;
+    return on_device(ctx->device, [&]() -> int {
+        if (on && ctx->msm_events.empty()) {
+            ctx->msm_events.resize(BPP_MSM_SLOTS * (PIP_STAGES + 1));
+            for (hipEvent_t& e : ctx->msm_events) HIPCHK(hipEventCreate(&e));
+        }
+        ctx->msm_profiling = on != 0;
+        ctx->msm_passes = 0;
+        return BPP_OK;
+    });
 }
 
 extern "C" int bpp_msm_profile(bpp_ctx* ctx, float* out_stage_ms, size_t* out_passes, uint32_t* out_shape) {
     if (!ctx || !out_stage_ms) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t np = std::min<size_t>(ctx->msm_passes, BPP_MSM_SLOTS);
-    int rc = stage_means(ctx->msm_events.data(), np, PIP_STAGES + 1, PIP_STAGES, 1, out_stage_ms);
-    if (rc) return rc;
-    if (out_passes) *out_passes = np;
-    if (out_shape) std::memcpy(out_shape, ctx->msm_shape, sizeof ctx->msm_shape);
-    return BPP_OK;
+    return on_device(ctx->device, [&]() -> int {
+        const size_t np = std::min<size_t>(ctx->msm_passes, BPP_MSM_SLOTS);
+        int rc = stage_means(ctx->msm_events.data(), np, PIP_STAGES + 1, PIP_STAGES, 1, out_stage_ms);
+        if (rc) return rc;
+        if (out_passes) *out_passes = np;
+        if (out_shape) std::memcpy(out_shape, ctx->msm_shape, sizeof ctx->msm_shape);
+        return BPP_OK;
+    });
 }
 
 extern "C" int bpp_scalar_mul_batch(bpp_ctx* ctx, const uint64_t* scalars, const uint64_t* points, size_t n,
                                     uint64_t* out) {
     if (!ctx || !out || (n && (!scalars || !points))) return fail(BPP_E_ARG, "null argument");
-    return on_ctx(*ctx, [&](auto cv) -> int {
+    return on_ctx(*ctx, {n, "n"}, [&](auto cv) -> int {
         return MsmImpl<decltype(cv)>::scalar_mul_batch(scalars, points, n, out);
     });
 }
 
 extern "C" int bpp_pk_new(bpp_ctx* ctx, size_t length, uint64_t* out_gh, uint64_t* out_G, uint64_t* out_H) {
     if (!ctx || !out_gh || (length && (!out_G || !out_H))) return fail(BPP_E_ARG, "null argument");
-    return on_ctx(*ctx, [&](auto cv) -> int {
+    return on_ctx(*ctx, {length, "length"}, [&](auto cv) -> int {
         return MsmImpl<decltype(cv)>::pk_new(length, out_gh, out_G, out_H);
     });
 }
@@ -236,21 +272,13 @@ static VerifyCacheEntry* engine_for_key(bpp_ctx* ctx, const uint64_t* gh, const 
     const uint64_t h = key_hash(ctx->curve, n, m, gh, G, H, pw);
     const size_t kw = (2 + 2 * mn) * pw;
     VerifyCacheEntry* hit = nullptr;
-    for (VerifyCacheEntry* x : vc.e)
+    for (const auto& x : vc.e)
         if (x->hash == h && x->n == n && x->m == m && std::memcmp(x->key.data(), gh, 2 * pw * 8) == 0 &&
             std::memcmp(x->key.data() + 2 * pw, G, mn * pw * 8) == 0 &&
             std::memcmp(x->key.data() + (2 + mn) * pw, H, mn * pw * 8) == 0)
-            hit = x;
+            hit = x.get();
     if (!hit) {   // first sight of this key: remember it
-        if (vc.e.size() >= VCACHE_MAX) {
-            size_t old = 0;
-            for (size_t i = 1; i < vc.e.size(); i++)
-                if (vc.e[i]->stamp < vc.e[old]->stamp) old = i;
-            delete vc.e[old]->v;
-            delete vc.e[old];
-            vc.e.erase(vc.e.begin() + old);
-        }
-        VerifyCacheEntry* x = new VerifyCacheEntry();
+        auto x = std::make_unique<VerifyCacheEntry>();
         x->hash = h;
         x->n = n;
         x->m = m;
@@ -259,7 +287,9 @@ static VerifyCacheEntry* engine_for_key(bpp_ctx* ctx, const uint64_t* gh, const 
         std::memcpy(x->key.data() + 2 * pw, G, mn * pw * 8);
         std::memcpy(x->key.data() + (2 + mn) * pw, H, mn * pw * 8);
         x->stamp = ++vc.clock;
-        vc.e.push_back(x);
+        if (vc.e.size() >= VCACHE_MAX)
+            vc.e.erase(std::min_element(vc.e.begin(), vc.e.end(), [](const auto& a, const auto& b) { return a->stamp < b->stamp; }));
+        vc.e.push_back(std::move(x));
         return nullptr;
     }
     hit->stamp = ++vc.clock;
@@ -270,12 +300,11 @@ static VerifyCacheEntry* engine_for_key(bpp_ctx* ctx, const uint64_t* gh, const 
         // endomorphism evaluation, which is not the full-curve sum there (include/bpp_amd.h, bpp_verifier_set_subgroup_check)
         v->check_subgroup = ctx->curve == BPP_BLS12_381_G1;
         const size_t wsb = bpp_verifier_workspace_bytes(v, 1);
+        std::unique_ptr<bpp_verifier> owned(v);
         if (hit->pts.alloc(v->s.NV * pw * 8) != hipSuccess || hit->sc.alloc(96) != hipSuccess ||
-            hit->ok.alloc(4) != hipSuccess || hit->ws.alloc(wsb) != hipSuccess) {
-            delete v;
+            hit->ok.alloc(4) != hipSuccess || hit->ws.alloc(wsb) != hipSuccess)
             return nullptr;
-        }
-        hit->v = v;
+        hit->v = std::move(owned);
     }
     return hit;
 }
@@ -284,42 +313,41 @@ extern "C" int bpp_range_verify(bpp_ctx* ctx, const uint64_t* gh, const uint64_t
                                 size_t m, const uint64_t* proof_points, size_t k, const uint64_t* proof_scalars,
                                 const uint64_t* V) {
     if (!ctx || !gh || !G || !H || !proof_points || !proof_scalars || !V) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    auto naive = [&]() -> int {
-        return dispatch(ctx->curve, [&](auto cv) -> int {
-            return MsmImpl<decltype(cv)>::range_verify_single(gh, G, H, n, m, proof_points, k, proof_scalars, V);
-        });
-    };
-    VerifyCacheEntry* hit = engine_for_key(ctx, gh, G, H, n, m);
-    if (!hit) return naive();
-    const size_t pw = (size_t)bpp_point_words(ctx->curve);
-    bpp_verifier* v = hit->v;
-    if (k != v->s.k) return BPP_VERIFICATION_ERROR;   // wip.rs:335-337
-    // record [A, wip.A, wip.B, L.., R.., V..]
-    HIPCHK(hipMemcpyAsync(hit->pts.p, proof_points, (3 + 2 * k) * pw * 8, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(static_cast<uint8_t*>(hit->pts.p) + (3 + 2 * k) * pw * 8, V, m * pw * 8, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(hipMemcpyAsync(hit->sc.p, proof_scalars, 96, hipMemcpyHostToDevice, nullptr));
-    int rc = bpp_verifier_run(v, static_cast<const uint64_t*>(hit->pts.p), static_cast<const uint64_t*>(hit->sc.p), 1, nullptr,
-                              hit->ok.u32(), hit->ws.p, hit->ws.bytes, nullptr, nullptr, nullptr);
-    if (rc) return rc;
-    uint32_t verdict = 1;
-    HIPCHK(hipMemcpy(&verdict, hit->ok.p, 4, hipMemcpyDeviceToHost));
-    // BLS12-381: an accept of the cached pass is exact (its points passed the membership test); a reject may be a curve
-    // point outside G1 whose full-curve contribution cancels, so the table-free full-curve path decides it, as it decides
-    // every call of the reference.  secp256k1 (cofactor 1) and edwards25519 (the same E[4] identity test as the naive
-    // path) need no second opinion.
-    if (verdict && ctx->curve == BPP_BLS12_381_G1) return naive();
-    return verdict ? BPP_VERIFICATION_ERROR : BPP_OK;
+    return on_ctx(*ctx, [&](auto cv) -> int {
+        auto naive = [&] { return MsmImpl<decltype(cv)>::range_verify_single(gh, G, H, n, m, proof_points, k, proof_scalars, V); };
+        VerifyCacheEntry* hit = engine_for_key(ctx, gh, G, H, n, m);
+        if (!hit) return naive();
+        const size_t pw = (size_t)bpp_point_words(ctx->curve);
+        bpp_verifier* v = hit->v.get();
+        if (k != v->s.k) return BPP_VERIFICATION_ERROR;   // wip.rs:335-337
+        // record [A, wip.A, wip.B, L.., R.., V..]
+        HIPCHK(hipMemcpyAsync(hit->pts.p, proof_points, (3 + 2 * k) * pw * 8, hipMemcpyHostToDevice, nullptr));
+        HIPCHK(hipMemcpyAsync(static_cast<uint8_t*>(hit->pts.p) + (3 + 2 * k) * pw * 8, V, m * pw * 8, hipMemcpyHostToDevice, nullptr));
+        HIPCHK(hipMemcpyAsync(hit->sc.p, proof_scalars, 96, hipMemcpyHostToDevice, nullptr));
+        int rc = bpp_verifier_run(v, static_cast<const uint64_t*>(hit->pts.p), static_cast<const uint64_t*>(hit->sc.p), 1, nullptr,
+                                  hit->ok.u32(), hit->ws.p, hit->ws.bytes, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+        uint32_t verdict = 1;
+        HIPCHK(hipMemcpy(&verdict, hit->ok.p, 4, hipMemcpyDeviceToHost));
+        // BLS12-381: an accept of the cached pass is exact (its points passed the membership test); a reject may be a curve
+        // point outside G1 whose full-curve contribution cancels, so the table-free full-curve path decides it, as it
+        // decides every call of the reference.  secp256k1 (cofactor 1) and edwards25519 (the same E[4] identity test as
+        // the naive path) need no second opinion.
+        if (verdict && ctx->curve == BPP_BLS12_381_G1) return naive();
+        return verdict ? BPP_VERIFICATION_ERROR : BPP_OK;
+    });
 }
 
 extern "C" int bpp_set_verify_cache(bpp_ctx* ctx, int on) {
     if (!ctx) return fail(BPP_E_ARG, "null argument");
-    ctx->verify_cache_off = on == 0;
-    if (!on) {
-        delete static_cast<VerifyCache*>(ctx->verify_cache);
-        ctx->verify_cache = nullptr;
-    }
-    return BPP_OK;
+    return guarded([&] {
+        ctx->verify_cache_off = on == 0;
+        if (!on) {
+            delete static_cast<VerifyCache*>(ctx->verify_cache);
+            ctx->verify_cache = nullptr;
+        }
+        return BPP_OK;
+    });
 }
 
 extern "C" int bpp_range_prove(bpp_ctx* ctx, const uint64_t* gh, const uint64_t* G, const uint64_t* H, size_t n,
@@ -327,26 +355,26 @@ extern "C" int bpp_range_prove(bpp_ctx* ctx, const uint64_t* gh, const uint64_t*
                                uint64_t* out_points, uint64_t* out_scalars) {
     if (!ctx || !gh || !G || !H || !v || !gamma || !V || !out_points || !out_scalars)
         return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    // a key that has been seen before proves through its cached engine: the batched prover at count = 1 (every L, R, A, B
-    // one MulVec over the window tables, bit-identical output) instead of folding the generator vectors round by round
-    if (VerifyCacheEntry* hit = engine_for_key(ctx, gh, G, H, n, m)) {
-        // the batched prover forms the commitments from (v, gamma) itself; the reference's prove reads them from the
-        // prover object (range/mod.rs:330-343) -- if the caller's V are not those, only the fold-based path reproduces it
-        const size_t pw = (size_t)bpp_point_words(ctx->curve);
-        std::vector<uint64_t> myV(m * pw), pts((3 + 2 * hit->v->s.k) * pw), sc(12);
-        int rc = dispatch(ctx->curve, [&](auto cv) -> int {
-            return VerifyImpl<decltype(cv)>::prove_batch(hit->v, v, gamma, 1, pts.data(), sc.data(), myV.data(), false);
-        });
-        if (rc == BPP_OK && std::memcmp(myV.data(), V, m * pw * 8) == 0) {
-            std::memcpy(out_points, pts.data(), pts.size() * 8);
-            std::memcpy(out_scalars, sc.data(), 96);
-            return BPP_OK;
+    return on_ctx(*ctx, {m, "m"}, [&](auto cv) -> int {
+        // a key that has been seen before proves through its cached engine: the batched prover at count = 1 (every L, R,
+        // A, B one MulVec over the window tables, bit-identical output) instead of folding the generator vectors round by
+        // round
+        if (VerifyCacheEntry* hit = engine_for_key(ctx, gh, G, H, n, m)) {
+            // the batched prover forms the commitments from (v, gamma) itself; the reference's prove reads them from the
+            // prover object (range/mod.rs:330-343) -- if the caller's V are not those, only the fold-based path
+            // reproduces it
+            const size_t pw = (size_t)bpp_point_words(ctx->curve);
+            std::vector<uint64_t> myV(m * pw), pts((3 + 2 * hit->v->s.k) * pw), sc(12);
+            const int rc = VerifyImpl<decltype(cv)>::prove_batch(hit->v.get(), v, gamma, 1, pts.data(), sc.data(), myV.data(),
+                                                                 false);
+            if (rc == BPP_OK && std::memcmp(myV.data(), V, m * pw * 8) == 0) {
+                std::memcpy(out_points, pts.data(), pts.size() * 8);
+                std::memcpy(out_scalars, sc.data(), 96);
+                return BPP_OK;
+            }
         }
-    }
-    return dispatch(ctx->curve, [&](auto cv) -> int {
         std::string err;
-        int rc = ProveImpl<decltype(cv)>::range_prove(gh, G, H, n, m, v, gamma, V, out_points, out_scalars, err);
+        const int rc = ProveImpl<decltype(cv)>::range_prove(gh, G, H, n, m, v, gamma, V, out_points, out_scalars, err);
         return rc ? fail(rc, err) : BPP_OK;
     });
 }
@@ -354,7 +382,7 @@ extern "C" int bpp_range_prove(bpp_ctx* ctx, const uint64_t* gh, const uint64_t*
 extern "C" int bpp_wip_fold_round(bpp_ctx* ctx, uint64_t* a, uint64_t* b, uint64_t* G, uint64_t* H, size_t len,
                                   const uint64_t* y_nhat, const uint64_t* e) {
     if (!ctx || !a || !b || !G || !H || !y_nhat || !e) return fail(BPP_E_ARG, "null argument");
-    return on_ctx(*ctx, [&](auto cv) -> int {
+    return on_ctx(*ctx, {len, "len"}, [&](auto cv) -> int {
         return ProveImpl<decltype(cv)>::wip_fold_round(a, b, G, H, len, y_nhat, e);
     });
 }
@@ -395,65 +423,60 @@ struct bpp_graph {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     int device = 0;
+    ~bpp_graph() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+    }
 };
-extern "C" void bpp_graph_destroy(bpp_graph* g) {
-    if (!g) return;
-    if (g->exec) (void)hipGraphExecDestroy(g->exec);
-    if (g->graph) (void)hipGraphDestroy(g->graph);
-    delete g;
-}
+extern "C" void bpp_graph_destroy(bpp_graph* g) { delete g; }
 extern "C" int bpp_verifier_graph_capture(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
                                           const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace,
                                           size_t workspace_bytes, bpp_graph** out) {
     if (!v || !d_points || !d_scalars || !d_ok || !d_workspace || !out) return fail(BPP_E_ARG, "null argument");
     if (count == 0 || count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count out of range");
     if (v->profiling) return fail(BPP_E_ARG, "switch the stage profiling off before capturing a pass");
-    HIPCHK(hipSetDevice(v->ctx.device));
-    hipStream_t cs = nullptr;
-    HIPCHK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-    auto pass = [&]() {
-        return dispatch(v->ctx.curve, [&](auto cv) -> int {
+    return on_ctx(v->ctx, [&](auto cv) -> int {
+        hipStream_t cs = nullptr;
+        HIPCHK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+        const std::unique_ptr<std::remove_pointer_t<hipStream_t>, decltype(&hipStreamDestroy)> own_cs(cs, hipStreamDestroy);
+        auto pass = [&] {
             return VerifyImpl<decltype(cv)>::run(v, d_points, d_scalars, count, d_challenges, d_ok, d_workspace, workspace_bytes,
                                                  nullptr, nullptr, cs);
-        });
-    };
-    // one eager pass first: it checks the arguments and creates what a pass creates lazily (the side stream and its events
-    // of a lone batch), which must not happen inside a capture
-    int rc = pass();
-    hipError_t e = rc ? hipSuccess : hipStreamSynchronize(cs);
-    if (rc || e != hipSuccess) {
-        (void)hipStreamDestroy(cs);
-        return rc ? rc : fail(BPP_E_HIP, std::string("eager pass before the capture failed: ") + hipGetErrorString(e));
-    }
-    bpp_graph* g = new bpp_graph();
-    g->device = v->ctx.device;
-    e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-    if (e == hipSuccess) {
-        rc = pass();
-        const hipError_t e2 = hipStreamEndCapture(cs, &g->graph);   // always ends the capture, also after a failed pass
-        if (!rc) e = e2;
-    }
-    if (!rc && e == hipSuccess) e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
-    (void)hipStreamDestroy(cs);
-    if (rc || e != hipSuccess) {
-        bpp_graph_destroy(g);
-        return rc ? rc : fail(BPP_E_HIP, std::string("graph capture failed: ") + hipGetErrorString(e));
-    }
-    *out = g;
-    return BPP_OK;
+        };
+        // one eager pass first: it checks the arguments and creates what a pass creates lazily (the side stream and its
+        // events of a lone batch), which must not happen inside a capture
+        int rc = pass();
+        if (rc) return rc;
+        hipError_t e = hipStreamSynchronize(cs);
+        if (e != hipSuccess) return fail(BPP_E_HIP, "eager pass before the capture failed: ", hipGetErrorString(e));
+        auto g = std::make_unique<bpp_graph>();
+        g->device = v->ctx.device;
+        e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+        if (e == hipSuccess) {
+            rc = guarded(pass);   // a pass that throws fails like one that returns an error
+            const hipError_t e2 = hipStreamEndCapture(cs, &g->graph);   // always ends the capture, also after a failed pass
+            if (rc) return rc;
+            e = e2;
+        }
+        if (e == hipSuccess) e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
+        if (e != hipSuccess) return fail(BPP_E_HIP, "graph capture failed: ", hipGetErrorString(e));
+        *out = g.release();
+        return BPP_OK;
+    });
 }
 extern "C" int bpp_graph_launch(bpp_graph* g, void* stream) {
     if (!g || !g->exec) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(g->device));
-    HIPCHK(hipGraphLaunch(g->exec, static_cast<hipStream_t>(stream)));
-    return BPP_OK;
+    return on_device(g->device, [&]() -> int {
+        HIPCHK(hipGraphLaunch(g->exec, static_cast<hipStream_t>(stream)));
+        return BPP_OK;
+    });
 }
 
 extern "C" int bpp_range_prove_batch(bpp_verifier* engine, const uint64_t* v, const uint64_t* gamma, size_t count,
                                      uint64_t* out_points, uint64_t* out_scalars, uint64_t* out_V) {
     if (!engine || !v || !gamma || !out_points || !out_scalars) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
-    return on_ctx(engine->ctx, [&](auto cv) -> int {
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::prove_batch(engine, v, gamma, count, out_points, out_scalars, out_V, false);
     });
 }
@@ -463,7 +486,7 @@ extern "C" int bpp_range_prove_batch_fs(bpp_verifier* engine, const uint64_t* v,
                                         uint64_t* out_scalars, uint64_t* out_V) {
     if (!engine || !v || !gamma || !out_points || !out_scalars) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
-    return on_ctx(engine->ctx, [&](auto cv) -> int {
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::prove_batch(engine, v, gamma, count, out_points, out_scalars, out_V, true, blind_key,
                                                      index_base);
     });
@@ -479,7 +502,7 @@ extern "C" int bpp_range_prove_batch_device(bpp_verifier* engine, const uint64_t
     if (!engine || !d_v || !d_gamma || !d_out_points || !d_out_scalars || !d_workspace)
         return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
-    return on_ctx(engine->ctx, [&](auto cv) -> int {
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::prove_batch_device(engine, d_v, d_gamma, count, d_out_points, d_out_scalars,
                                                             d_out_V, false, nullptr, d_workspace, workspace_bytes,
                                                             static_cast<hipStream_t>(stream));
@@ -494,7 +517,7 @@ extern "C" int bpp_range_prove_batch_fs_device(bpp_verifier* engine, const uint6
     if (!engine || !d_v || !d_gamma || !d_out_points || !d_out_scalars || !d_workspace)
         return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
-    return on_ctx(engine->ctx, [&](auto cv) -> int {
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::prove_batch_device(engine, d_v, d_gamma, count, d_out_points, d_out_scalars,
                                                             d_out_V, true, d_out_challenges, d_workspace, workspace_bytes,
                                                             static_cast<hipStream_t>(stream), blind_key, index_base,
@@ -516,7 +539,7 @@ extern "C" int bpp_verifier_run_combined(bpp_verifier* v, const uint64_t* d_poin
     if (!v || !d_points || !d_scalars || !d_out_partial || !d_ok || !d_workspace) return fail(BPP_E_ARG, "null argument");
     if (!weight_key && !d_weights) return fail(BPP_E_ARG, "the combined check needs a weight key or a weight buffer");
     if (count == 0) return fail(BPP_E_ARG, "empty batch");
-    return on_ctx(v->ctx, [&](auto cv) -> int {
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::run_combined(v, d_points, d_scalars, count, d_challenges, weight_key, index_base,
                                                       d_weights, static_cast<uint32_t*>(d_out_partial), d_ok, d_workspace,
                                                       workspace_bytes, static_cast<hipStream_t>(stream));
@@ -534,7 +557,7 @@ extern "C" int bpp_verifier_run_grouped(bpp_verifier* v, const uint64_t* d_point
     if (!v || !d_out_verdicts || !d_workspace || (count && (!d_points || !d_scalars)))
         return fail(BPP_E_ARG, "null argument");
     if (!weight_key && !d_weights) return fail(BPP_E_ARG, "the grouped check needs a weight key or a weight buffer");
-    return on_ctx(v->ctx, [&](auto cv) -> int {
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::run_grouped(v, d_points, d_scalars, count, d_challenges, weight_key, index_base,
                                                      d_weights, group, d_out_verdicts, stats, d_workspace, workspace_bytes,
                                                      static_cast<hipStream_t>(stream));
@@ -548,7 +571,7 @@ extern "C" int bpp_verifier_grouped_begin(bpp_verifier* v, const uint64_t* d_poi
     if (!v || !d_out_verdicts || !d_workspace || (count && (!d_points || !d_scalars)))
         return fail(BPP_E_ARG, "null argument");
     if (!weight_key && !d_weights) return fail(BPP_E_ARG, "the grouped check needs a weight key or a weight buffer");
-    return on_ctx(v->ctx, [&](auto cv) -> int {
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::grouped_begin(v, d_points, d_scalars, count, d_challenges, weight_key, index_base,
                                                        d_weights, group, d_out_verdicts, d_workspace, workspace_bytes,
                                                        static_cast<hipStream_t>(stream));
@@ -559,7 +582,7 @@ extern "C" int bpp_verifier_grouped_finish(bpp_verifier* v, const uint64_t* d_po
                                            uint64_t* stats, void* d_workspace, size_t workspace_bytes, void* stream) {
     if (!v || !d_out_verdicts || !d_workspace || (count && (!d_points || !d_scalars)))
         return fail(BPP_E_ARG, "null argument");
-    return on_ctx(v->ctx, [&](auto cv) -> int {
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::grouped_finish(v, d_points, d_scalars, count, d_challenges, group, d_out_verdicts, stats,
                                                         d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
     });
@@ -567,7 +590,7 @@ extern "C" int bpp_verifier_grouped_finish(bpp_verifier* v, const uint64_t* d_po
 extern "C" int bpp_verifier_sum_partials(bpp_verifier* v, const void* d_partials, size_t n, uint32_t* d_ok,
                                          void* stream) {
     if (!v || !d_partials || !d_ok) return fail(BPP_E_ARG, "null argument");
-    return on_ctx(v->ctx, [&](auto cv) -> int {
+    return on_ctx(v->ctx, {n, "n"}, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::sum_partials(static_cast<const uint32_t*>(d_partials), n, d_ok,
                                                       static_cast<hipStream_t>(stream));
     });
@@ -577,7 +600,7 @@ extern "C" int bpp_verifier_derive_challenges(bpp_verifier* v, const uint64_t* d
                                               uint64_t* d_challenges, void* stream) {
     if (!v || !d_points || !d_challenges) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
-    return on_ctx(v->ctx, [&](auto cv) -> int {
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::derive_challenges(v, d_points, count, d_challenges,
                                                            static_cast<hipStream_t>(stream));
     });
@@ -591,47 +614,42 @@ extern "C" int bpp_verifier_set_subgroup_check(bpp_verifier* v, int on) {
 
 extern "C" int bpp_verifier_set_profiling(bpp_verifier* v, int on) {
     if (!v) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(v->ctx.device));
-    if (on && v->events.empty()) {
-        v->events.resize((size_t)BPP_PROFILE_SLOTS * BPP_NUM_STAGES * 2);
-        for (hipEvent_t& e : v->events) HIPCHK(hipEventCreate(&e));
-    }
-    v->profiling = on != 0;
-    v->passes_recorded = 0;
-    return BPP_OK;
+    return on_device(v->ctx.device, [&]() -> int {
+        if (on && v->events.empty()) {
+            v->events.resize((size_t)BPP_PROFILE_SLOTS * BPP_NUM_STAGES * 2);
+            for (hipEvent_t& e : v->events) HIPCHK(hipEventCreate(&e));
+        }
+        v->profiling = on != 0;
+        v->passes_recorded = 0;
+        return BPP_OK;
+    });
 }
 
 extern "C" int bpp_verifier_profile(bpp_verifier* v, float* out_stage_ms, size_t* out_passes,
                                     unsigned* out_blocks_per_proof) {
     if (!v || !out_stage_ms) return fail(BPP_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(v->ctx.device));
-    const size_t np = std::min<size_t>(v->passes_recorded, BPP_PROFILE_SLOTS);
-    int rc = stage_means(v->events.data(), np, BPP_NUM_STAGES * 2, BPP_NUM_STAGES, 2, out_stage_ms);
-    if (rc) return rc;
-    if (out_passes) *out_passes = np;
-    if (out_blocks_per_proof) *out_blocks_per_proof = v->last_blocks_per_proof;
-    return BPP_OK;
+    return on_device(v->ctx.device, [&]() -> int {
+        const size_t np = std::min<size_t>(v->passes_recorded, BPP_PROFILE_SLOTS);
+        int rc = stage_means(v->events.data(), np, BPP_NUM_STAGES * 2, BPP_NUM_STAGES, 2, out_stage_ms);
+        if (rc) return rc;
+        if (out_passes) *out_passes = np;
+        if (out_blocks_per_proof) *out_blocks_per_proof = v->last_blocks_per_proof;
+        return BPP_OK;
+    });
 }
 
 extern "C" int bpp_range_verify_batch(bpp_verifier* v, const uint64_t* points, const uint64_t* scalars, size_t count,
                                       uint32_t* out_ok) {
     if (!v || !points || !scalars || !out_ok) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
-    HIPCHK(hipSetDevice(v->ctx.device));
-    const size_t pw = (size_t)bpp_point_words(v->ctx.curve) * 8;
-    DevBuf dp, ds, dok, dws;
-    HIPCHK(dp.alloc(count * v->s.NV * pw));
-    HIPCHK(ds.alloc(count * 3 * 32));
-    HIPCHK(dok.alloc(count * 4));
-    const size_t wsb = bpp_verifier_workspace_bytes(v, count);
-    HIPCHK(dws.alloc(wsb));
-    HIPCHK(hipMemcpy(dp.p, points, count * v->s.NV * pw, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ds.p, scalars, count * 3 * 32, hipMemcpyHostToDevice));
-    int rc = bpp_verifier_run(v, static_cast<const uint64_t*>(dp.p), static_cast<const uint64_t*>(ds.p), count, nullptr,
-                              dok.u32(), dws.p, wsb, nullptr, nullptr, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(out_ok, dok.p, count * 4, hipMemcpyDeviceToHost));
-    return BPP_OK;
+    return on_device(v->ctx.device, {count, "count"}, [&] {
+        const size_t pw = (size_t)bpp_point_words(v->ctx.curve) * 8, wsb = bpp_verifier_workspace_bytes(v, count);
+        return verify_staged(points, count * v->s.NV * pw, scalars, count * 3 * 32, count, wsb, out_ok,
+                             [&](void* dp, void* ds, uint32_t* dok, void* dws) {
+                                 return bpp_verifier_run(v, static_cast<const uint64_t*>(dp), static_cast<const uint64_t*>(ds),
+                                                         count, nullptr, dok, dws, wsb, nullptr, nullptr, nullptr);
+                             });
+    });
 }
 
 // ---- mixed batches: proof i of shape (n, m_i) against the verifier's (n, m) tables (mixed.hpp) ------------------
@@ -671,29 +689,24 @@ extern "C" int bpp_range_verify_batch_mixed(bpp_verifier* v, const uint64_t* poi
     if (!v) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
     if (!points || !scalars || !m_of || !out_ok) return fail(BPP_E_ARG, "null argument");
-    const size_t wsb = bpp_verifier_mixed_workspace_bytes(v, m_of, count);
-    if (!wsb) {   // an m_i the verifier does not take: the plan names the proof
-        MixedPlan p;
-        const int rc = mixed_plan(v->s, m_of, count, false, p);
-        return rc ? rc : fail(BPP_E_ARG, "mixed batch rejected");
-    }
-    HIPCHK(hipSetDevice(v->ctx.device));
-    const size_t pw = (size_t)bpp_point_words(v->ctx.curve) * 8;
-    size_t npts = 0;
-    const uint32_t logn = v->s.k - (uint32_t)__builtin_ctz(v->s.m);
-    for (size_t i = 0; i < count; i++) npts += 3 + 2 * (logn + (uint32_t)__builtin_ctz(m_of[i])) + m_of[i];
-    DevBuf dp, ds, dok, dws;
-    HIPCHK(dp.alloc(npts * pw));
-    HIPCHK(ds.alloc(count * 3 * 32));
-    HIPCHK(dok.alloc(count * 4));
-    HIPCHK(dws.alloc(wsb));
-    HIPCHK(hipMemcpy(dp.p, points, npts * pw, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ds.p, scalars, count * 3 * 32, hipMemcpyHostToDevice));
-    int rc = bpp_verifier_run_mixed(v, static_cast<const uint64_t*>(dp.p), static_cast<const uint64_t*>(ds.p), m_of, count,
-                                    nullptr, dok.u32(), dws.p, wsb, nullptr, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(out_ok, dok.p, count * 4, hipMemcpyDeviceToHost));
-    return BPP_OK;
+    return on_device(v->ctx.device, {count, "count"}, [&]() -> int {
+        const size_t wsb = bpp_verifier_mixed_workspace_bytes(v, m_of, count);
+        if (!wsb) {   // an m_i the verifier does not take: the plan names the proof
+            MixedPlan p;
+            const int rc = mixed_plan(v->s, m_of, count, false, p);
+            return rc ? rc : fail(BPP_E_ARG, "mixed batch rejected");
+        }
+        const size_t pw = (size_t)bpp_point_words(v->ctx.curve) * 8;
+        size_t npts = 0;
+        const uint32_t logn = v->s.k - (uint32_t)__builtin_ctz(v->s.m);
+        for (size_t i = 0; i < count; i++) npts += 3 + 2 * (logn + (uint32_t)__builtin_ctz(m_of[i])) + m_of[i];
+        return verify_staged(points, npts * pw, scalars, count * 3 * 32, count, wsb, out_ok,
+                             [&](void* dp, void* ds, uint32_t* dok, void* dws) {
+                                 return bpp_verifier_run_mixed(v, static_cast<const uint64_t*>(dp),
+                                                               static_cast<const uint64_t*>(ds), m_of, count, nullptr, dok,
+                                                               dws, wsb, nullptr, nullptr);
+                             });
+    });
 }
 
 // ---- compressed point encodings (codec.hpp) ---------------------------------------------------------------
@@ -708,18 +721,18 @@ extern "C" size_t bpp_point_compressed_bytes(int curve_id) {
 
 extern "C" int bpp_points_compress(bpp_ctx* ctx, const uint64_t* points, size_t n, uint8_t* out) {
     if (!ctx || (n && (!points || !out))) return fail(BPP_E_ARG, "null argument");
-    return on_ctx(*ctx, [&](auto cv) -> int { return CodecImpl<decltype(cv)>::compress(points, n, out); });
+    return on_ctx(*ctx, {n, "n"}, [&](auto cv) -> int { return CodecImpl<decltype(cv)>::compress(points, n, out); });
 }
 
 extern "C" int bpp_points_decompress(bpp_ctx* ctx, const uint8_t* in, size_t n, uint64_t* out_points, uint32_t* out_ok) {
     if (!ctx || (n && (!in || !out_points || !out_ok))) return fail(BPP_E_ARG, "null argument");
-    return on_ctx(*ctx, [&](auto cv) -> int { return CodecImpl<decltype(cv)>::decompress(in, n, out_points, out_ok); });
+    return on_ctx(*ctx, {n, "n"}, [&](auto cv) -> int { return CodecImpl<decltype(cv)>::decompress(in, n, out_points, out_ok); });
 }
 
 extern "C" int bpp_points_decompress_device(bpp_ctx* ctx, const void* d_in, size_t n, uint64_t* d_points, uint32_t* d_ok,
                                             int check_subgroup, void* stream) {
     if (!ctx || (n && (!d_in || !d_points || !d_ok))) return fail(BPP_E_ARG, "null argument");
-    return on_ctx(*ctx, [&](auto cv) -> int {
+    return on_ctx(*ctx, {n, "n"}, [&](auto cv) -> int {
         return CodecImpl<decltype(cv)>::decompress_device(static_cast<const uint8_t*>(d_in), n, d_points, d_ok,
                                                           static_cast<hipStream_t>(stream), check_subgroup != 0);
     });
@@ -729,39 +742,37 @@ extern "C" int bpp_range_verify_batch_compressed(bpp_verifier* v, const uint8_t*
                                                  size_t count, uint32_t* out_ok) {
     if (!v || !records || !scalars || !out_ok) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
-    HIPCHK(hipSetDevice(v->ctx.device));
     const size_t cb = bpp_point_compressed_bytes(v->ctx.curve);
     if (cb == 0) return fail(BPP_E_ARG, "compressed encoding is not offered for this curve");
-    const size_t pw = (size_t)bpp_point_words(v->ctx.curve) * 8;
-    const size_t npts = count * v->s.NV;
-    DevBuf db, dp, dk, ds, dok, dws;
-    HIPCHK(db.alloc(npts * cb));
-    HIPCHK(dp.alloc(npts * pw));
-    HIPCHK(dk.alloc(npts * 4));
-    HIPCHK(ds.alloc(count * 3 * 32));
-    HIPCHK(dok.alloc(count * 4));
-    const size_t wsb = bpp_verifier_workspace_bytes(v, count);
-    HIPCHK(dws.alloc(wsb));
-    HIPCHK(hipMemcpy(db.p, records, npts * cb, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ds.p, scalars, count * 3 * 32, hipMemcpyHostToDevice));
-    // the one wire entry point for points of unknown origin besides the container: reject what is outside the prime-order
-    // group too (the verifier's GLV evaluation equals s * P only there, include/bpp_amd.h)
-    int rc = bpp_points_decompress_device(&v->ctx, db.p, npts, static_cast<uint64_t*>(dp.p), dk.u32(), 1, nullptr);
-    if (rc) return rc;
-    rc = bpp_verifier_run(v, static_cast<const uint64_t*>(dp.p), static_cast<const uint64_t*>(ds.p), count, nullptr,
-                          dok.u32(), dws.p, wsb, nullptr, nullptr, nullptr);
-    if (rc) return rc;
-    std::vector<uint32_t> bad(npts);
-    HIPCHK(hipMemcpy(out_ok, dok.p, count * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(bad.data(), dk.p, npts * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < npts; i++)
-        if (bad[i]) out_ok[i / v->s.NV] = BPP_FORMAT_ERROR;   // a malformed encoding / a point outside the group: ProofError::FormatError
-    // ... and so does a non-canonical scalar (r', s' or delta' >= the group order): a serialized proof has one encoding
-    // (little-endian host: the u64 limbs are the bytes)
-    for (size_t i = 0; i < count * 3; i++)
-        if (!scalar_is_canonical(v->ctx.curve, reinterpret_cast<const uint8_t*>(scalars + i * 4)))
-            out_ok[i / 3] = BPP_FORMAT_ERROR;
-    return BPP_OK;
+    return on_device(v->ctx.device, {count, "count"}, [&]() -> int {
+        const size_t pw = (size_t)bpp_point_words(v->ctx.curve) * 8, wsb = bpp_verifier_workspace_bytes(v, count);
+        const size_t npts = count * v->s.NV;
+        std::vector<uint32_t> bad(npts);
+        const int rc = verify_staged(records, npts * cb, scalars, count * 3 * 32, count, wsb, out_ok,
+                                     [&](void* db, void* ds, uint32_t* dok, void* dws) -> int {
+            DevBuf dp, dk;
+            HIPCHK(dp.alloc(npts * pw));
+            HIPCHK(dk.alloc(npts * 4));
+            // the one wire entry point for points of unknown origin besides the container: reject what is outside the
+            // prime-order group too (the verifier's GLV evaluation equals s * P only there, include/bpp_amd.h)
+            int rc = bpp_points_decompress_device(&v->ctx, db, npts, static_cast<uint64_t*>(dp.p), dk.u32(), 1, nullptr);
+            if (rc) return rc;
+            rc = bpp_verifier_run(v, static_cast<const uint64_t*>(dp.p), static_cast<const uint64_t*>(ds), count, nullptr, dok,
+                                  dws, wsb, nullptr, nullptr, nullptr);
+            if (rc) return rc;
+            HIPCHK(hipMemcpy(bad.data(), dk.p, npts * 4, hipMemcpyDeviceToHost));
+            return BPP_OK;
+        });
+        if (rc) return rc;
+        for (size_t i = 0; i < npts; i++)
+            if (bad[i]) out_ok[i / v->s.NV] = BPP_FORMAT_ERROR;   // a malformed encoding / a point outside the group: ProofError::FormatError
+        // ... and so does a non-canonical scalar (r', s' or delta' >= the group order): a serialized proof has one encoding
+        // (little-endian host: the u64 limbs are the bytes)
+        for (size_t i = 0; i < count * 3; i++)
+            if (!scalar_is_canonical(v->ctx.curve, reinterpret_cast<const uint8_t*>(scalars + i * 4)))
+                out_ok[i / 3] = BPP_FORMAT_ERROR;
+        return BPP_OK;
+    });
 }
 
 // ---- serialized proofs (the container; see include/bpp_amd.h) -----------------------------------------------------
@@ -815,8 +826,10 @@ static void points_to_uncompressed(int curve, const uint64_t* points, size_t n, 
 extern "C" int bpp_points_uncompressed(bpp_ctx* ctx, const uint64_t* points, size_t n, uint8_t* out) {
     if (!ctx || (n && (!points || !out))) return fail(BPP_E_ARG, "null argument");
     if (bpp_point_uncompressed_bytes(ctx->curve) == 0) return fail(BPP_E_ARG, "no uncompressed form for this curve");
-    points_to_uncompressed(ctx->curve, points, n, out);
-    return BPP_OK;
+    return guarded({n, "n"}, [&] {
+        points_to_uncompressed(ctx->curve, points, n, out);
+        return BPP_OK;
+    });
 }
 
 extern "C" int bpp_proofs_encode_version(bpp_ctx* ctx, size_t n, size_t m, int version, const uint64_t* points,
@@ -825,24 +838,26 @@ extern "C" int bpp_proofs_encode_version(bpp_ctx* ctx, size_t n, size_t m, int v
     const size_t pb = bpp_proof_bytes_version(ctx->curve, n, m, version);
     if (pb == 0 || n > 255 || m > 255) return fail(BPP_E_ARG, "n*m must be a power of two (n, m <= 255); version 1 or 2");
     if (count == 0) return BPP_OK;
-    const size_t cb = container_point_size(ctx->curve, version);
-    const uint32_t k = log2_exact(n * m);
-    const size_t npp = 3 + 2 * (size_t)k;
-    std::vector<uint8_t> comp(count * npp * cb);
-    if (version == 2) {
-        points_to_uncompressed(ctx->curve, points, count * npp, comp.data());
-    } else {
-        int rc = bpp_points_compress(ctx, points, count * npp, comp.data());
-        if (rc) return rc;
-    }
-    for (size_t p = 0; p < count; p++) {
-        uint8_t* o = out + p * pb;
-        const uint8_t hdr[BPP_HDR] = {'B', 'P', 'P', '+', (uint8_t)version, (uint8_t)ctx->curve, (uint8_t)n, (uint8_t)m, (uint8_t)k, 0, 0, 0};
-        std::memcpy(o, hdr, BPP_HDR);
-        std::memcpy(o + BPP_HDR, comp.data() + p * npp * cb, npp * cb);
-        std::memcpy(o + BPP_HDR + npp * cb, scalars + p * 12, 96);   // little-endian host: the u64 limbs are the bytes
-    }
-    return BPP_OK;
+    return guarded({count, "count"}, [&] {
+        const size_t cb = container_point_size(ctx->curve, version);
+        const uint32_t k = log2_exact(n * m);
+        const size_t npp = 3 + 2 * (size_t)k;
+        std::vector<uint8_t> comp(count * npp * cb);
+        if (version == 2) {
+            points_to_uncompressed(ctx->curve, points, count * npp, comp.data());
+        } else {
+            int rc = bpp_points_compress(ctx, points, count * npp, comp.data());
+            if (rc) return rc;
+        }
+        for (size_t p = 0; p < count; p++) {
+            uint8_t* o = out + p * pb;
+            const uint8_t hdr[BPP_HDR] = {'B', 'P', 'P', '+', (uint8_t)version, (uint8_t)ctx->curve, (uint8_t)n, (uint8_t)m, (uint8_t)k, 0, 0, 0};
+            std::memcpy(o, hdr, BPP_HDR);
+            std::memcpy(o + BPP_HDR, comp.data() + p * npp * cb, npp * cb);
+            std::memcpy(o + BPP_HDR + npp * cb, scalars + p * 12, 96);   // little-endian host: the u64 limbs are the bytes
+        }
+        return BPP_OK;
+    });
 }
 
 extern "C" int bpp_proofs_encode(bpp_ctx* ctx, size_t n, size_t m, const uint64_t* points, const uint64_t* scalars,
@@ -850,59 +865,48 @@ extern "C" int bpp_proofs_encode(bpp_ctx* ctx, size_t n, size_t m, const uint64_
     return bpp_proofs_encode_version(ctx, n, m, 1, points, scalars, count, out);
 }
 
-// decode to device buffers: d_points count x (3 + 2k) wire points, status[p] = 0 / BPP_FORMAT_ERROR (host vector)
-static int proofs_decode_common(bpp_ctx* ctx, size_t n, size_t m, const uint8_t* in, size_t count, DevBuf& d_points,
-                                std::vector<uint64_t>& scalars, std::vector<uint32_t>& status) {
-    const size_t pb = bpp_proof_bytes(ctx->curve, n, m);
-    if (pb == 0 || n > 255 || m > 255) return fail(BPP_E_ARG, "n*m must be a power of two (n, m <= 255)");
-    const size_t cb = bpp_point_compressed_bytes(ctx->curve);
-    const uint32_t k = log2_exact(n * m);
-    const size_t npp = 3 + 2 * (size_t)k;
-    const size_t pw = (size_t)bpp_point_words(ctx->curve) * 8;
-    status.assign(count, 0);
-    scalars.assign(count * 12, 0);
-    std::vector<uint8_t> comp(count * npp * cb);
-    for (size_t p = 0; p < count; p++) {
-        const uint8_t* s = in + p * pb;
-        const uint8_t hdr[BPP_HDR] = {'B', 'P', 'P', '+', 1, (uint8_t)ctx->curve, (uint8_t)n, (uint8_t)m, (uint8_t)k, 0, 0, 0};
-        if (std::memcmp(s, hdr, BPP_HDR) != 0) status[p] = BPP_FORMAT_ERROR;   // magic, version, curve, shape, reserved
-        std::memcpy(comp.data() + p * npp * cb, s + BPP_HDR, npp * cb);
-        const uint8_t* sc = s + BPP_HDR + npp * cb;
-        for (int t = 0; t < 3; t++)
-            if (!scalar_is_canonical(ctx->curve, sc + 32 * t)) status[p] = BPP_FORMAT_ERROR;   // one encoding per scalar
-        std::memcpy(scalars.data() + p * 12, sc, 96);
-    }
-    DevBuf db, dk;
-    HIPCHK(db.alloc(count * npp * cb));
-    HIPCHK(dk.alloc(count * npp * 4));
-    HIPCHK(d_points.alloc(count * npp * pw));
-    HIPCHK(hipMemcpy(db.p, comp.data(), comp.size(), hipMemcpyHostToDevice));
-    int rc = dispatch(ctx->curve, [&](auto cv) -> int {
-        return CodecImpl<decltype(cv)>::decompress_device(static_cast<const uint8_t*>(db.p), count * npp,
-                                                          static_cast<uint64_t*>(d_points.p), dk.u32(), nullptr, true);
-    });
-    if (rc) return rc;
-    std::vector<uint32_t> bad(count * npp);
-    HIPCHK(hipMemcpy(bad.data(), dk.p, bad.size() * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < bad.size(); i++)
-        if (bad[i]) status[i / npp] = BPP_FORMAT_ERROR;   // malformed encoding or a point outside the prime-order group
-    return BPP_OK;
-}
-
 extern "C" int bpp_proofs_decode(bpp_ctx* ctx, size_t n, size_t m, const uint8_t* in, size_t count, uint64_t* out_points,
                                  uint64_t* out_scalars, uint32_t* out_status) {
     if (!ctx || (count && (!in || !out_points || !out_scalars || !out_status))) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    DevBuf dp;
-    std::vector<uint64_t> sc;
-    std::vector<uint32_t> st;
-    int rc = proofs_decode_common(ctx, n, m, in, count, dp, sc, st);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(out_points, dp.p, dp.bytes, hipMemcpyDeviceToHost));
-    std::memcpy(out_scalars, sc.data(), sc.size() * 8);
-    std::memcpy(out_status, st.data(), st.size() * 4);
-    return BPP_OK;
+    const size_t pb = bpp_proof_bytes(ctx->curve, n, m);
+    if (pb == 0 || n > 255 || m > 255) return fail(BPP_E_ARG, "n*m must be a power of two (n, m <= 255)");
+    return on_ctx(*ctx, {count, "count"}, [&](auto cv) -> int {
+        const size_t cb = bpp_point_compressed_bytes(ctx->curve);
+        const uint32_t k = log2_exact(n * m);
+        const size_t npp = 3 + 2 * (size_t)k;
+        const size_t pw = (size_t)bpp_point_words(ctx->curve) * 8;
+        // status[p] = 0 / BPP_FORMAT_ERROR; the caller's buffers are written once everything has succeeded
+        std::vector<uint32_t> status(count, 0);
+        std::vector<uint64_t> scalars(count * 12, 0);
+        std::vector<uint8_t> comp(count * npp * cb);
+        for (size_t p = 0; p < count; p++) {
+            const uint8_t* s = in + p * pb;
+            const uint8_t hdr[BPP_HDR] = {'B', 'P', 'P', '+', 1, (uint8_t)ctx->curve, (uint8_t)n, (uint8_t)m, (uint8_t)k, 0, 0, 0};
+            if (std::memcmp(s, hdr, BPP_HDR) != 0) status[p] = BPP_FORMAT_ERROR;   // magic, version, curve, shape, reserved
+            std::memcpy(comp.data() + p * npp * cb, s + BPP_HDR, npp * cb);
+            const uint8_t* sc = s + BPP_HDR + npp * cb;
+            for (int t = 0; t < 3; t++)
+                if (!scalar_is_canonical(ctx->curve, sc + 32 * t)) status[p] = BPP_FORMAT_ERROR;   // one encoding per scalar
+            std::memcpy(scalars.data() + p * 12, sc, 96);
+        }
+        DevBuf db, dk, dp;
+        HIPCHK(db.alloc(count * npp * cb));
+        HIPCHK(dk.alloc(count * npp * 4));
+        HIPCHK(dp.alloc(count * npp * pw));
+        HIPCHK(hipMemcpy(db.p, comp.data(), comp.size(), hipMemcpyHostToDevice));
+        const int rc = CodecImpl<decltype(cv)>::decompress_device(static_cast<const uint8_t*>(db.p), count * npp,
+                                                                  static_cast<uint64_t*>(dp.p), dk.u32(), nullptr, true);
+        if (rc) return rc;
+        std::vector<uint32_t> bad(count * npp);
+        HIPCHK(hipMemcpy(bad.data(), dk.p, bad.size() * 4, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < bad.size(); i++)
+            if (bad[i]) status[i / npp] = BPP_FORMAT_ERROR;   // malformed encoding or a point outside the prime-order group
+        HIPCHK(hipMemcpy(out_points, dp.p, dp.bytes, hipMemcpyDeviceToHost));
+        std::memcpy(out_scalars, scalars.data(), scalars.size() * 8);
+        std::memcpy(out_status, status.data(), status.size() * 4);
+        return BPP_OK;
+    });
 }
 
 extern "C" size_t bpp_verifier_serialized_workspace_bytes(const bpp_verifier* v, size_t count) {
@@ -957,24 +961,19 @@ extern "C" int bpp_range_verify_batch_serialized(bpp_verifier* v, const uint8_t*
                                                  size_t count, int flags, uint32_t* out_ok) {
     if (!v || !proofs || !commitments || !out_ok) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
-    HIPCHK(hipSetDevice(v->ctx.device));
     const VerifyShape& s = v->s;
     const int version = (flags & BPP_SER_UNCOMPRESSED) ? 2 : 1;
     const size_t pb = bpp_proof_bytes_version(v->ctx.curve, s.n, s.m, version);
     const size_t cb = container_point_size(v->ctx.curve, version);
     if (pb == 0 || s.n > 255 || s.m > 255) return fail(BPP_E_ARG, "n*m must be a power of two (n, m <= 255)");
-    DevBuf dpr, dcm, dok, dws;
-    const size_t wsb = bpp_verifier_serialized_workspace_bytes(v, count);
-    HIPCHK(dpr.alloc(count * pb));
-    HIPCHK(dcm.alloc(count * s.m * cb));
-    HIPCHK(dok.alloc(count * 4));
-    HIPCHK(dws.alloc(wsb));
-    HIPCHK(hipMemcpy(dpr.p, proofs, count * pb, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dcm.p, commitments, count * s.m * cb, hipMemcpyHostToDevice));
-    int rc = bpp_range_verify_batch_serialized_device(v, dpr.p, dcm.p, count, flags, dok.u32(), dws.p, wsb, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(out_ok, dok.p, count * 4, hipMemcpyDeviceToHost));
-    return BPP_OK;
+    return on_device(v->ctx.device, {count, "count"}, [&] {
+        const size_t wsb = bpp_verifier_serialized_workspace_bytes(v, count);
+        return verify_staged(proofs, count * pb, commitments, count * s.m * cb, count, wsb, out_ok,
+                             [&](void* dpr, void* dcm, uint32_t* dok, void* dws) {
+                                 return bpp_range_verify_batch_serialized_device(v, dpr, dcm, count, flags, dok, dws, wsb,
+                                                                                 nullptr);
+                             });
+    });
 }
 
 // ---- device-side unit-test hooks (tests/ check the device field / group primitives against a CPU checker) --
@@ -983,7 +982,7 @@ extern "C" int bpp_range_verify_batch_serialized(bpp_verifier* v, const uint8_t*
 extern "C" int bpp_debug_field_op(bpp_ctx* ctx, int field, int op, const uint32_t* a, const uint32_t* b, size_t n,
                                   uint32_t* out) {
     if (!ctx || !a || !b || !out) return fail(BPP_E_ARG, "null argument");
-    return on_ctx(*ctx, [&](auto cv) -> int {
+    return on_ctx(*ctx, {n, "n"}, [&](auto cv) -> int {
         return MsmImpl<decltype(cv)>::debug_field_op(field, op, a, b, n, out);
     });
 }
@@ -991,7 +990,7 @@ extern "C" int bpp_debug_field_op(bpp_ctx* ctx, int field, int op, const uint32_
 extern "C" int bpp_debug_point_op(bpp_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, size_t n,
                                   uint64_t* out) {
     if (!ctx || !a || !b || !out) return fail(BPP_E_ARG, "null argument");
-    return on_ctx(*ctx, [&](auto cv) -> int {
+    return on_ctx(*ctx, {n, "n"}, [&](auto cv) -> int {
         return MsmImpl<decltype(cv)>::debug_point_op(op, a, b, n, out);
     });
 }

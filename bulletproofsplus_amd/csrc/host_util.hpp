@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/bpp_amd.h"
+#include "abi_guard.hpp"
 #include "kernels.hpp"
 
 struct bpp_ctx {
@@ -33,17 +34,11 @@ constexpr size_t BPP_MSM_SLOTS = 16;
 // to inline it: without this attribute capi.hip compiled every kernel of every curve a second time (8 minutes, 12 MB).
 #define BPP_NOINL __attribute__((noinline))
 
-// ---- error handling ------------------------------------------------------------------------------------
-inline thread_local std::string g_err;
-inline int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
+// ---- error handling (g_err, fail: abi_guard.hpp) -------------------------------------------------------
 #define HIPCHK(expr)                                                                            \
     do {                                                                                        \
         hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return fail(BPP_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));          \
+        if (e_ != hipSuccess) return fail(BPP_E_HIP, #expr ": ", hipGetErrorString(e_));        \
     } while (0)
 
 
@@ -58,7 +53,9 @@ struct DevBuf {
     ~DevBuf() {
         if (p) (void)hipFree(p);
     }
-    hipError_t alloc(size_t n) {
+    hipError_t alloc(size_t n) {   // (re)allocates: a buffer held from an earlier call is freed first
+        if (p) (void)hipFree(p);
+        p = nullptr;
         bytes = n;
         return hipMalloc(&p, n ? n : 16);
     }

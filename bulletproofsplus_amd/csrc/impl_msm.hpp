@@ -207,6 +207,7 @@ int MsmImpl<C>::msm_batch(const uint64_t* scalars, const uint64_t* points, const
     for (size_t c = 0; c < count; c++) off[c + 1] = off[c] + lens[c];
     const size_t total = off[count];
     if (total && (!scalars || !points)) return fail(BPP_E_ARG, "null scalars/points");
+    if (total >> 32) return fail(BPP_E_ARG, "sum of lens too large");
     if (count == 1 && total >= PIPPENGER_MIN_N) return msm_pippenger(scalars, points, total, 0, out);
     DevBuf dsc, dpt;
     int rc = upload_scalars<C>(scalars, total, dsc, nullptr);

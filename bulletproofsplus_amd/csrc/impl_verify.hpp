@@ -1,6 +1,7 @@
 // impl_verify.hpp -- the batch verifier (bpp_verifier_*): window tables in HBM + one pass of the hot path
 // over a device-resident batch.  One instantiation per curve (tu_verify_*.hip).
 #pragma once
+#include <memory>
 #include <mutex>
 
 #include "codec.hpp"
@@ -441,26 +442,20 @@ int VerifyImpl<C>::create(const bpp_ctx& ctx, const uint64_t* gh, const uint64_t
     DevBuf dfixed;
     rc = upload_points<C>(fixed.data(), s.NF, dfixed, nullptr);
     if (rc) return rc;
-    bpp_verifier* v = new bpp_verifier();
+    auto v = std::make_unique<bpp_verifier>();
     v->ctx = ctx;
     v->s = s;
     const size_t entries = (size_t)s.NF * s.per_f;
     v->table_bytes = entries * 2 * N * 4;
     hipError_t e = v->table.alloc(v->table_bytes);
-    if (e != hipSuccess) {
-        delete v;
-        return fail(BPP_E_NOMEM, std::string("window table allocation failed: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(BPP_E_NOMEM, "window table allocation failed: ", hipGetErrorString(e));
     hipLaunchKernelGGL(k_tbl_bases<C>, dim3(cdiv(s.NF, 64)), dim3(64), 0, nullptr, s, dfixed.u32(), v->table.u32());
     // fill in slabs of generators: one thread per run of TBL_RUN entries, 2 * TBL_RUN field elements of scratch each
     const uint32_t runs_f = tbl_runs_per_generator(s);
     const uint32_t slab = (uint32_t)std::max<size_t>(1, ((size_t)1 << 21) / runs_f);
     DevBuf tbl_scratch;
     e = tbl_scratch.alloc((size_t)std::min<uint32_t>(slab, s.NF) * runs_f * 2 * TBL_RUN * N * 4);
-    if (e != hipSuccess) {
-        delete v;
-        return fail(BPP_E_NOMEM, std::string("table scratch allocation failed: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(BPP_E_NOMEM, "table scratch allocation failed: ", hipGetErrorString(e));
     for (uint32_t f0 = 0; f0 < s.NF; f0 += slab) {
         const uint32_t f1 = std::min<uint32_t>(s.NF, f0 + slab);
         const size_t total = (size_t)(f1 - f0) * runs_f;
@@ -480,10 +475,7 @@ int VerifyImpl<C>::create(const bpp_ctx& ctx, const uint64_t* gh, const uint64_t
     for (uint32_t mp = 1; mp < s.m; mp <<= 1) {
         PassShape ps{};
         rc = make_shape(n, mp, window_bits, C::Fr::MODW, C::Fr::BITS, ps.s);
-        if (rc) {
-            delete v;
-            return rc;
-        }
+        if (rc) return rc;
         ps.s.hgap = s.n * (s.m - mp);
         std::vector<uint64_t> prefix((size_t)ps.s.NF * PW);
         std::memcpy(prefix.data(), fixed.data(), (size_t)(2 + ps.s.mn) * PW * 8);
@@ -503,11 +495,8 @@ int VerifyImpl<C>::create(const bpp_ctx& ctx, const uint64_t* gh, const uint64_t
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) {
-        delete v;
-        return fail(BPP_E_HIP, std::string("table build failed: ") + hipGetErrorString(e));
-    }
-    *out = v;
+    if (e != hipSuccess) return fail(BPP_E_HIP, "table build failed: ", hipGetErrorString(e));
+    *out = v.release();
     return BPP_OK;
 }
 

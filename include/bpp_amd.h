@@ -14,7 +14,8 @@
  *     (reference src/errors.rs:14-50; the only variant the path constructs, range/mod.rs:508,
  *     weighted_inner_product_proof.rs:326,336), negative = usage / runtime error (BPP_E_*), where the
  *     reference would panic (mulvec.rs:23-25, range/mod.rs:90-91,252-253, wip.rs:60-67).
- *     Nothing unwinds, nothing is printed.
+ *     Nothing unwinds, nothing is printed.  A failed host allocation returns BPP_E_NOMEM; a count of 2^32 or
+ *     more (proofs, points, scalars, generators) returns BPP_E_ARG.
  *   - scalar: 4 x uint64_t little-endian limbs, canonical (non-Montgomery) value; values >= r are
  *     reduced mod r on entry.
  *   - point : (2*L + 1) x uint64_t = affine x (L limbs LE) | y (L limbs LE) | infinity flag (0/1),
@@ -45,7 +46,7 @@ extern "C" {
 #define BPP_VERIFICATION_ERROR 1
 #define BPP_FORMAT_ERROR 2  /* ProofError::FormatError (src/errors.rs:20): per-proof status of the serialized-proof path */
 #define BPP_E_ARG (-1)      /* bad argument (null pointer, unknown curve, n*m not a power of two...) */
-#define BPP_E_HIP (-2)      /* HIP runtime error; bpp_last_error() has the text */
+#define BPP_E_HIP (-2)      /* HIP runtime error or another runtime failure inside the library; bpp_last_error() has the text */
 #define BPP_E_LENGTH (-3)   /* "mulvec: lengths of scalars and points must match" and friends */
 #define BPP_E_POINT (-4)    /* a point is not on the curve / coordinate >= p */
 #define BPP_E_NOMEM (-5)

@@ -267,6 +267,29 @@ def test_length_mismatches_raise():
     rec = B.proof_record(proof, pr.commitment_vec)
     with pytest.raises(RuntimeError):
         bv.verify_wire(np.stack([rec, rec]), proof.scalars_wire()[None])
+    # a count of 2^32 or more with small real buffers: a usage error naming the count, returned before any buffer is
+    # read, any memory is allocated or anything is launched
+    import ctypes
+    from bulletproofsplus_amd import _lib
+    L = _lib.lib()
+    buf = np.zeros(4096, dtype=np.uint64)
+    b = buf.ctypes.data_as(ctypes.c_void_p)
+    for big in (1 << 32, 1 << 62):
+        for call, what in ((lambda: L.bpp_pk_new(a.handle, big, b, b, b), "length"),
+                           (lambda: L.bpp_proofs_encode_version(a.handle, 8, 2, 1, b, b, big, b), "count"),
+                           (lambda: L.bpp_proofs_decode(a.handle, 8, 2, b, big, b, b, b), "count"),
+                           (lambda: L.bpp_points_compress(a.handle, b, big, b), "n"),
+                           (lambda: L.bpp_scalar_mul_batch(a.handle, b, b, big, b), "n"),
+                           (lambda: L.bpp_range_verify_batch(bv.handle, b, b, big, b), "count")):
+            rc = call()
+            assert rc == -1, (what, big, rc)   # BPP_E_ARG
+            assert L.bpp_last_error().decode() == what + " too large", (what, big)
+    # ... and the context and the verifier still give the oracle's answers
+    opk = O.PublicKey(1, 16)
+    pk2 = B.PublicKey.new(a, 16)
+    assert np.array_equal(pk2.G_vec, opk.G) and np.array_equal(pk2.H_vec, opk.H)
+    opts, osc, oV = O.range_prove(opk, 8, [200, 5], [3, 7])
+    assert bv.verify_wire(rec[None], proof.scalars_wire()[None]).tolist() == [O.range_verify(opk, 8, 2, opts, osc, oV)] == [0]
     bv.close()
 
 
