@@ -335,6 +335,73 @@ impl BatchVerifier {
         }
         out
     }
+    /// A block of SERIALIZED proofs of mixed aggregation sizes (include/bpp_amd.h: bpp_range_verify_batch_serialized_mixed):
+    /// `proofs` holds the version 1 containers back to back, container i of bpp_proof_bytes(curve, n, ms[i]) bytes, and
+    /// `commitments` ms[i] compressed points per proof, both in the order of `ms`.  Each `Result` is
+    /// RangeProof::verify(proof_i, PublicKey::new(n ms[i]), n, V_i), or Err(FormatError) for a container, an encoding or a
+    /// scalar the decoder rejects.  `ms = None`: the stream is framed first (`proofs_scan`).  Err(FormatError) for the whole
+    /// call when the stream cannot be framed, an ms[i] is not taken by this verifier, or the buffers' lengths are not those
+    /// `ms` implies: nothing then reaches the engine.
+    pub fn verify_serialized_mixed(&self, proofs: &[u8], commitments: &[u8], ms: Option<&[u32]>, transcript: bool)
+                                   -> Result<Vec<Result<(), ProofError>>, ProofError> {
+        let n = 1usize << (self.k - self.m.trailing_zeros() as usize);
+        let scanned;
+        let ms: &[u32] = match ms {
+            Some(ms) => ms,
+            None => {
+                scanned = proofs_scan(n, proofs)?;
+                &scanned
+            }
+        };
+        let cb = unsafe { ffi::bpp_point_compressed_bytes(ffi::BPP_BLS12_381_G1) };
+        let (mut pbytes, mut cbytes) = (0usize, 0usize);
+        for &mi in ms {
+            let mi = mi as usize;
+            if mi == 0 || !mi.is_power_of_two() || mi > self.m {
+                return Err(ProofError::FormatError);
+            }
+            pbytes += unsafe { ffi::bpp_proof_bytes(ffi::BPP_BLS12_381_G1, n, mi) };
+            cbytes += mi * cb;
+        }
+        if pbytes != proofs.len() || cbytes != commitments.len() {
+            return Err(ProofError::FormatError);
+        }
+        if ms.is_empty() {
+            return Ok(Vec::new());
+        }
+        let mut ok = vec![0u32; ms.len()];
+        let flags = if transcript { ffi::BPP_SER_TRANSCRIPT } else { 0 };
+        let rc = unsafe {
+            ffi::bpp_range_verify_batch_serialized_mixed(self.handle, proofs.as_ptr(), commitments.as_ptr(), ms.as_ptr(), ms.len(),
+                                                         flags, ok.as_mut_ptr())
+        };
+        assert!(rc == 0, "bpp_range_verify_batch_serialized_mixed: {}", rc);
+        Ok(ok.iter().map(|&v| match v {
+            0 => Ok(()),
+            2 => Err(ProofError::FormatError),
+            _ => Err(ProofError::VerificationError),
+        }).collect())
+    }
+}
+
+/// m_i of every container of a bare stream of version 1 containers for n-bit values (include/bpp_amd.h: bpp_proofs_scan; host
+/// code, no device).  Err(FormatError) when the stream cannot be framed.
+pub fn proofs_scan(n: usize, proofs: &[u8]) -> Result<Vec<u32>, ProofError> {
+    // the shortest container (m = 1) bounds the count
+    let shortest = unsafe { ffi::bpp_proof_bytes(ffi::BPP_BLS12_381_G1, n, 1) };
+    if shortest == 0 {
+        return Err(ProofError::FormatError);
+    }
+    let mut ms = vec![0u32; proofs.len() / shortest];
+    let mut count = 0usize;
+    let rc = unsafe {
+        ffi::bpp_proofs_scan(ffi::BPP_BLS12_381_G1, n, 1, proofs.as_ptr(), proofs.len(), ms.as_mut_ptr(), ms.len(), &mut count)
+    };
+    if rc != 0 {
+        return Err(ProofError::FormatError);
+    }
+    ms.truncate(count);
+    Ok(ms)
 }
 impl Drop for BatchVerifier {
     fn drop(&mut self) {

@@ -44,6 +44,8 @@ EXPORTS = [
     "bpp_verifier_serialized_grouped_workspace_bytes", "bpp_range_verify_batch_serialized_grouped_device",
     "bpp_verifier_mixed_workspace_bytes", "bpp_verifier_run_mixed", "bpp_verifier_derive_challenges_mixed",
     "bpp_range_verify_batch_mixed",
+    "bpp_verifier_serialized_mixed_workspace_bytes", "bpp_range_verify_batch_serialized_mixed_device",
+    "bpp_range_verify_batch_serialized_mixed", "bpp_proofs_scan",
 ]
 
 
@@ -154,6 +156,11 @@ def lib():
         L.bpp_verifier_run_mixed.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, sz, vp, vp]
         L.bpp_verifier_derive_challenges_mixed.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
         L.bpp_range_verify_batch_mixed.argtypes = [vp, vp, vp, vp, sz, vp]
+        L.bpp_verifier_serialized_mixed_workspace_bytes.argtypes = [vp, vp, sz]
+        L.bpp_verifier_serialized_mixed_workspace_bytes.restype = sz
+        L.bpp_range_verify_batch_serialized_mixed_device.argtypes = [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp]
+        L.bpp_range_verify_batch_serialized_mixed.argtypes = [vp, vp, vp, vp, sz, i32, vp]
+        L.bpp_proofs_scan.argtypes = [i32, sz, i32, vp, sz, vp, sz, vp]
         L.bpp_debug_field_op.argtypes = [vp, i32, i32, vp, vp, sz, vp]
         L.bpp_debug_point_op.argtypes = [vp, i32, vp, vp, sz, vp]
         _lib = L

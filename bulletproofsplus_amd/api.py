@@ -283,6 +283,23 @@ def decode_proofs(arith: Arith, n: int, m: int, data):
     return pts, sc, st
 
 
+def proofs_scan(arith, n: int, data, version: int = 1) -> np.ndarray:
+    """Frames a bare byte stream of concatenated containers (bpp_proofs_scan; host code, no device): -> m_i per container,
+    (count,) u32.  arith: an Arith, a curve name or a curve id.  Raises BppError, naming the container and its byte
+    offset, when the stream cannot be framed."""
+    curve = getattr(arith, "curve", arith)
+    if isinstance(curve, str):
+        curve = CURVE_IDS[curve]
+    raw = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else \
+        np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    shortest = _lib.lib().bpp_proof_bytes_version(curve, n, 1, version)   # bounds the count
+    ms = np.zeros(len(raw) // shortest if shortest else 0, dtype=np.uint32)
+    count = ctypes.c_size_t(0)
+    check(_lib.lib().bpp_proofs_scan(curve, n, version, _ptr(raw) if len(raw) else None, len(raw),
+                                     _ptr(ms) if len(ms) else None, len(ms), ctypes.byref(count)), "bpp_proofs_scan")
+    return ms[:count.value]
+
+
 class FormatError(ProofError):
     """ProofError::FormatError (reference src/errors.rs:20): a serialized proof that does not parse"""
 
@@ -732,6 +749,51 @@ class BatchVerifier:
         ok = np.zeros(count, dtype=np.uint32)
         check(_lib.lib().bpp_range_verify_batch_mixed(self.handle, _ptr(pts), _ptr(sc), _ptr(m), count, _ptr(ok)),
               "bpp_range_verify_batch_mixed")
+        return ok
+
+    # ---- serialized proofs of mixed aggregation sizes: bytes in, one status per proof out (include/bpp_amd.h) ----
+    def serialized_mixed_workspace_bytes(self, ms) -> int:
+        """bytes of device workspace verify_serialized_mixed_device needs (0: an m_i is not taken)"""
+        m = self._ms(ms)
+        return _lib.lib().bpp_verifier_serialized_mixed_workspace_bytes(self.handle, _ptr(m), len(m))
+
+    def verify_serialized_mixed_device(self, d_proofs: int, d_commitments: int, ms, d_ok: int, d_workspace: int,
+                                       workspace_bytes: int, stream: int = 0, transcript: bool = False,
+                                       uncompressed: bool = False):
+        """verify_serialized_device for a resident block of containers of mixed aggregation sizes: container i of
+        proof_bytes(arith, n, ms[i]) bytes, packed back to back in caller order, and ms[i] encoded commitments per proof,
+        packed likewise; ms: host list.  d_ok[i] = 0 / 1 / 2, the verdict against the prefix key of the proof's own shape.
+        Blocks while it uploads the per-proof index, the rest is on `stream`."""
+        m = self._ms(ms)
+        check(_lib.lib().bpp_range_verify_batch_serialized_mixed_device(
+            self.handle, d_proofs, d_commitments, _ptr(m), len(m), (1 if transcript else 0) | (2 if uncompressed else 0),
+            d_ok, d_workspace, workspace_bytes, stream or None), "bpp_range_verify_batch_serialized_mixed_device")
+
+    def verify_serialized_mixed(self, proofs, commitments, ms=None, transcript: bool = False,
+                                uncompressed: bool = False) -> np.ndarray:
+        """proofs: the containers back to back (bytes or u8 array), commitments: ms[i] encoded points per proof back to
+        back; ms: m_i per proof, or None to frame the stream first (proofs_scan; BppError when it cannot be framed)
+        -> status (count,) u32: 0 Ok / 1 VerificationError / 2 FormatError"""
+        def flat(x):
+            return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
+        raw, cm = flat(proofs), flat(commitments)
+        version = 2 if uncompressed else 1
+        m = proofs_scan(self.arith, self.n, raw, version) if ms is None else self._ms(ms)
+        count = len(m)
+        # an m_i the verifier does not take is reported by the library (BPP_E_ARG naming the proof)
+        if all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m):
+            pb = uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)
+            need = sum(proof_bytes(self.arith, self.n, int(x), version) for x in m)
+            if len(raw) != need:
+                raise RuntimeError("verify_serialized_mixed: %d bytes of proofs, the shapes in ms need %d" % (len(raw), need))
+            if len(cm) != int(m.sum()) * pb:
+                raise RuntimeError("verify_serialized_mixed: ms[i] commitments per proof")
+        ok = np.zeros(count, dtype=np.uint32)
+        check(_lib.lib().bpp_range_verify_batch_serialized_mixed(
+            self.handle, _ptr(raw) if len(raw) else None, _ptr(cm) if len(cm) else None, _ptr(m) if count else None, count,
+            (1 if transcript else 0) | (2 if uncompressed else 0), _ptr(ok) if count else None),
+            "bpp_range_verify_batch_serialized_mixed")
         return ok
 
     def sum_partials_device(self, d_partials: int, n: int, d_ok: int, stream: int = 0):

@@ -2,6 +2,7 @@
 // checks, curve dispatch, then the per-curve implementations (impl_*.hpp, compiled in tu_*.hip).
 // No CPU fallback: every entry point launches HIP kernels on the context's device.
 #include "codec.hpp"
+#include "container_scan.hpp"
 #include "impl_msm.hpp"
 #include "impl_prove.hpp"
 #include "impl_verify.hpp"
@@ -972,6 +973,75 @@ extern "C" int bpp_range_verify_batch_serialized(bpp_verifier* v, const uint8_t*
                              [&](void* dpr, void* dcm, uint32_t* dok, void* dws) {
                                  return bpp_range_verify_batch_serialized_device(v, dpr, dcm, count, flags, dok, dws, wsb,
                                                                                  nullptr);
+                             });
+    });
+}
+
+// ---- serialized proofs of mixed aggregation sizes (mixed.hpp; the framing of a bare stream: container_scan.hpp) ----
+extern "C" int bpp_proofs_scan(int curve_id, size_t n, int version, const uint8_t* proofs, size_t proofs_bytes,
+                               uint32_t* m_of, size_t max_count, size_t* out_count) {
+    if (!out_count || (proofs_bytes && !proofs) || (max_count && !m_of)) return fail(BPP_E_ARG, "null argument");
+    *out_count = 0;
+    return guarded({max_count, "max_count"}, [&]() -> int {
+        const ScanResult r = container_scan(curve_id, n, version, proofs, proofs_bytes, m_of, max_count);
+        *out_count = r.count;
+        if (r.status == SCAN_OK) return BPP_OK;
+        if (r.status == SCAN_BAD_ARG) return fail(BPP_E_ARG, "bpp_proofs_scan: ", scan_status_text(r.status));
+        return fail(r.status == SCAN_TOO_MANY ? BPP_E_ARG : BPP_E_LENGTH,
+                    "container " + std::to_string(r.count) + " at byte " + std::to_string(r.offset) + ": " +
+                        scan_status_text(r.status));
+    });
+}
+
+extern "C" size_t bpp_verifier_serialized_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
+    if ((count && !m_of) || count > 0x7fffffffu / 64) return 0;
+    return size_for(v, [&](auto cv) { return VerifyImpl<decltype(cv)>::ser_mixed_workspace_bytes(v, m_of, count); });
+}
+
+extern "C" int bpp_range_verify_batch_serialized_mixed_device(bpp_verifier* v, const void* d_proofs, const void* d_commitments,
+                                                              const uint32_t* m_of, size_t count, int flags, uint32_t* d_ok,
+                                                              void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!v) return fail(BPP_E_ARG, "null argument");
+    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED)) return fail(BPP_E_ARG, "unknown flag");
+    if (count == 0) return BPP_OK;
+    if (!d_proofs || !d_commitments || !m_of || !d_ok || !d_workspace) return fail(BPP_E_ARG, "null argument");
+    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    const int transcript = flags & BPP_SER_TRANSCRIPT;
+    const uint32_t version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::run_serialized_mixed(v, static_cast<const uint8_t*>(d_proofs),
+                                                              static_cast<const uint8_t*>(d_commitments), m_of, count,
+                                                              transcript != 0, d_ok, d_workspace, workspace_bytes,
+                                                              static_cast<hipStream_t>(stream), version);
+    });
+}
+
+// host buffers in, host verdicts out: the device path above between two copies
+extern "C" int bpp_range_verify_batch_serialized_mixed(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments,
+                                                       const uint32_t* m_of, size_t count, int flags, uint32_t* out_ok) {
+    if (!v) return fail(BPP_E_ARG, "null argument");
+    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED)) return fail(BPP_E_ARG, "unknown flag");
+    if (count == 0) return BPP_OK;
+    if (!proofs || !commitments || !m_of || !out_ok) return fail(BPP_E_ARG, "null argument");
+    const int version = (flags & BPP_SER_UNCOMPRESSED) ? 2 : 1;
+    const size_t cb = container_point_size(v->ctx.curve, version);
+    if (cb == 0) return fail(BPP_E_ARG, "container version 2 (uncompressed points) is not offered for this curve");
+    return on_device(v->ctx.device, {count, "count"}, [&]() -> int {
+        const size_t wsb = bpp_verifier_serialized_mixed_workspace_bytes(v, m_of, count);
+        if (!wsb) {   // an m_i the verifier does not take: the plan names the proof
+            MixedPlan p;
+            const int rc = mixed_plan_serialized(v->s, m_of, count, cb, false, p);
+            return rc ? rc : fail(BPP_E_ARG, "serialized mixed batch rejected");
+        }
+        size_t pbytes = 0, cbytes = 0;
+        for (size_t i = 0; i < count; i++) {
+            pbytes += bpp_proof_bytes_version(v->ctx.curve, v->s.n, m_of[i], version);
+            cbytes += m_of[i] * cb;
+        }
+        return verify_staged(proofs, pbytes, commitments, cbytes, count, wsb, out_ok,
+                             [&](void* dpr, void* dcm, uint32_t* dok, void* dws) {
+                                 return bpp_range_verify_batch_serialized_mixed_device(v, dpr, dcm, m_of, count, flags, dok,
+                                                                                       dws, wsb, nullptr);
                              });
     });
 }

@@ -299,13 +299,42 @@ __host__ __device__ constexpr size_t container_bytes(uint32_t k, uint32_t versio
 // of the container and the m commitments, decompressed WITH the subgroup check straight into the layout
 // bpp_verifier_run reads.  The lane of a proof's first point also checks the header and the canonicity of r', s',
 // delta' and copies them out.  status[p] (zeroed by the caller) becomes non-zero when anything of proof p is rejected.
+// One lane of the container decoder (k_container_decode; k_container_decode_mixed in mixed.hpp): point t of a proof of
+// shape (n, m, k) whose container starts at rec and whose encoding is at src, decoded into the record slot w; the lane of
+// the proof's first point also checks the header and the canonicity of r', s', delta' and copies them to sc_out (24 words).
+// false: something of the proof is rejected.
+template <class C>
+__device__ __forceinline__ bool container_decode_lane(const uint8_t* __restrict__ rec, const uint8_t* __restrict__ src,
+                                                      uint32_t t, uint32_t n, uint32_t m, uint32_t k, uint32_t version,
+                                                      uint32_t* __restrict__ w, uint32_t* __restrict__ sc_out) {
+    const int CB = container_point_bytes<C>(version);   // version 2: uncompressed points (and commitments)
+    const uint32_t npp = 3 + 2 * k;
+    // the G1 membership test is a kernel of its own (k_records_subgroup below): two chains of 64 doublings beside the
+    // square root's window table in one kernel cost 256 VGPRs and scratch
+    bool good = version == 2 ? point_uncompressed_read<C>(src, w) : point_decompress<C, false>(src, w);
+    if (t == 0) {
+        const uint8_t hdr[CONTAINER_HDR] = {'B', 'P', 'P', '+', (uint8_t)version, (uint8_t)C::ID, (uint8_t)n, (uint8_t)m, (uint8_t)k, 0, 0, 0};
+        for (uint32_t b = 0; b < CONTAINER_HDR; b++) good = good && rec[b] == hdr[b];
+        const uint8_t* sc = rec + CONTAINER_HDR + (size_t)npp * CB;
+        for (int e = 0; e < 3; e++) {
+            uint32_t v[8];
+            for (int q = 0; q < 8; q++)
+                v[q] = (uint32_t)sc[32 * e + 4 * q] | ((uint32_t)sc[32 * e + 4 * q + 1] << 8) |
+                       ((uint32_t)sc[32 * e + 4 * q + 2] << 16) | ((uint32_t)sc[32 * e + 4 * q + 3] << 24);
+            good = good && words_lt_mod<typename C::Fr>(v);   // one encoding per scalar
+            for (int q = 0; q < 8; q++) sc_out[e * 8 + q] = v[q];
+        }
+    }
+    return good;
+}
+
 template <class C>
 __global__ void __launch_bounds__(64, 2) k_container_decode(VerifyShape s, const uint8_t* __restrict__ proofs,
                                                          const uint8_t* __restrict__ commitments,
                                                          uint32_t* __restrict__ records, uint32_t* __restrict__ scalars,
                                                          uint32_t* __restrict__ status, size_t count, uint32_t version) {
     constexpr int N = C::Fp::N;
-    const int CB = container_point_bytes<C>(version);   // version 2: uncompressed points (and commitments)
+    const int CB = container_point_bytes<C>(version);
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count * s.NV) return;
     const size_t p = i / s.NV;
@@ -313,24 +342,23 @@ __global__ void __launch_bounds__(64, 2) k_container_decode(VerifyShape s, const
     const uint32_t npp = 3 + 2 * s.k;
     const uint8_t* rec = proofs + p * container_bytes<C>(s.k, version);
     const uint8_t* src = t < npp ? rec + CONTAINER_HDR + (size_t)t * CB : commitments + (p * s.m + (t - npp)) * CB;
-    // the G1 membership test is a kernel of its own (k_records_subgroup below): two chains of 64 doublings beside the
-    // square root's window table in one kernel cost 256 VGPRs and scratch
-    bool good = version == 2 ? point_uncompressed_read<C>(src, records + i * (2 * N + 2))
-                             : point_decompress<C, false>(src, records + i * (2 * N + 2));
-    if (t == 0) {
-        const uint8_t hdr[CONTAINER_HDR] = {'B', 'P', 'P', '+', (uint8_t)version, (uint8_t)C::ID, (uint8_t)s.n, (uint8_t)s.m, (uint8_t)s.k, 0, 0, 0};
-        for (uint32_t b = 0; b < CONTAINER_HDR; b++) good = good && rec[b] == hdr[b];
-        const uint8_t* sc = rec + CONTAINER_HDR + (size_t)npp * CB;
-        for (int e = 0; e < 3; e++) {
-            uint32_t w[8];
-            for (int q = 0; q < 8; q++)
-                w[q] = (uint32_t)sc[32 * e + 4 * q] | ((uint32_t)sc[32 * e + 4 * q + 1] << 8) |
-                       ((uint32_t)sc[32 * e + 4 * q + 2] << 16) | ((uint32_t)sc[32 * e + 4 * q + 3] << 24);
-            good = good && words_lt_mod<typename C::Fr>(w);   // one encoding per scalar
-            for (int q = 0; q < 8; q++) scalars[(p * 3 + e) * 8 + q] = w[q];
-        }
-    }
-    if (!good) atomicOr(status + p, 1u);
+    if (!container_decode_lane<C>(rec, src, t, s.n, s.m, s.k, version, records + i * (2 * N + 2), scalars + p * 24))
+        atomicOr(status + p, 1u);
+}
+
+// One lane of the membership test: the decoded record point at w outside the prime-order subgroup => true, and the point
+// is replaced by infinity
+template <class C>
+__device__ __forceinline__ bool record_leaves_subgroup(uint32_t* __restrict__ w) {
+    using P = typename C::Fp;
+    constexpr int N = P::N;
+    if (w[2 * N] | w[2 * N + 1]) return false;   // infinity
+    Aff<C> a;
+    a.x = fe_from_canonical<P>(w);
+    a.y = fe_from_canonical<P>(w + N);
+    if (aff_in_prime_subgroup(a)) return false;
+    for (int t = 0; t < 2 * N + 2; t++) w[t] = t == 2 * N ? 1u : 0u;
+    return true;
 }
 
 // One lane per decoded record point: outside the prime-order subgroup (BLS12-381 G1: csrc/ec.hpp aff_in_prime_subgroup) =>
@@ -338,18 +366,10 @@ __global__ void __launch_bounds__(64, 2) k_container_decode(VerifyShape s, const
 template <class C>
 __global__ void __launch_bounds__(64, 2) k_records_subgroup(uint32_t* __restrict__ records, uint32_t* __restrict__ status,
                                                             uint32_t per_proof, size_t npoints) {
-    using P = typename C::Fp;
-    constexpr int N = P::N;
+    constexpr int N = C::Fp::N;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= npoints) return;
-    uint32_t* w = records + i * (2 * N + 2);
-    if (w[2 * N] | w[2 * N + 1]) return;   // infinity
-    Aff<C> a;
-    a.x = fe_from_canonical<P>(w);
-    a.y = fe_from_canonical<P>(w + N);
-    if (aff_in_prime_subgroup(a)) return;
-    for (int t = 0; t < 2 * N + 2; t++) w[t] = t == 2 * N ? 1u : 0u;
-    atomicOr(status + i / per_proof, 1u);
+    if (record_leaves_subgroup<C>(records + i * (2 * N + 2))) atomicOr(status + i / per_proof, 1u);
 }
 
 // ok[p] = BPP_FORMAT_ERROR where the decoder rejected proof p: ProofError::FormatError takes precedence over the

@@ -269,6 +269,42 @@ struct VerifyImpl {
                               bool transcript, uint32_t* d_ok, void* d_workspace, size_t workspace_bytes, hipStream_t st,
                               uint32_t version = 1, const GroupedArgs* grouped = nullptr);
 
+    // ---- ... of MIXED aggregation sizes: the decoder writes each record into its class region (mixed.hpp) -------
+    // workspace = per-proof index (by gathered position) | class regions of decoded records | scalars | decoder status |
+    // challenges (transcript mode) | verdicts -- the last four by gathered position -- | one class pass's workspace
+    struct SerMixedLayout {
+        size_t idx, records, scalars, status, challenges, ok, run, total;
+    };
+    static SerMixedLayout ser_mixed_layout(const bpp_verifier* v, const MixedPlan& p, size_t count) {
+        SerMixedLayout w;
+        WsCarver o;
+        w.idx = o.take(count * SX_WORDS * 4);
+        w.records = o.take(p.points * WW * 4);
+        w.scalars = o.take(count * 96);
+        w.status = o.take(count * 4);
+        w.challenges = o.take(p.chals * 32);
+        w.ok = o.take(count * 4);
+        size_t run = 0;
+        for (uint32_t c = 0; c < MIXED_CLASSES; c++)
+            if (p.count[c]) run = std::max(run, ws_layout(class_shape(v, c).s, p.count[c]).total);
+        w.run = o.take(run);
+        w.total = o.total;
+        return w;
+    }
+    // 0 for an m_of the verifier does not take (the larger point encoding sizes the byte-offset check)
+    static size_t ser_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
+        MixedPlan p;
+        const size_t pb = uncompressed_bytes<C>() ? uncompressed_bytes<C>() : compressed_bytes<C>();
+        if (v->s.n > 255 || v->s.m > 255 || mixed_plan_serialized(v->s, m_of, count, pb, false, p)) return 0;
+        return ser_mixed_layout(v, p, count).total;
+    }
+    // d_proofs: the containers packed back to back in caller order, container i of container_bytes(k_i, version) bytes;
+    // d_commitments: m_i encoded points per proof, packed in caller order; m_of: host; d_ok: caller order, 0 / 1 / 2.
+    // Uploads the per-proof index (blocking the host until the copy has read it), the rest is enqueued on st.
+    static int run_serialized_mixed(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments,
+                                    const uint32_t* m_of, size_t count, bool transcript, uint32_t* d_ok, void* d_workspace,
+                                    size_t workspace_bytes, hipStream_t st, uint32_t version);
+
     // ---- combined batch check (combined.hpp) ------------------------------------------------------------
     struct CombLayout {
         size_t pts, bad, scalars, prep, weights, comb_sc, fpart, var_sc, vdig, vtbl, vscr, vwsum, vfold, total;
@@ -781,6 +817,55 @@ int VerifyImpl<C>::derive_challenges_mixed(bpp_verifier* v, const uint64_t* d_po
     hipLaunchKernelGGL(k_mixed_scatter<C>, dim3(cdiv(count, 4)), dim3(256), 0, st,
                        reinterpret_cast<const uint32_t*>(ws + L.idx), count, nullptr, nullptr, U64(L.challenges), nullptr,
                        nullptr, d_challenges);
+    HIPCHK(hipGetLastError());
+    return BPP_OK;
+}
+
+// Decode into the class regions, membership test, then per class present the challenges (transcript mode) and today's
+// pass with the class's view; decoder status and verdicts go back to caller order in one kernel.  A container whose
+// header names another shape than m_of[i] fails the header compare of ITS class: a FormatError of that proof only.
+template <class C>
+int VerifyImpl<C>::run_serialized_mixed(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments,
+                                        const uint32_t* m_of, size_t count, bool transcript, uint32_t* d_ok,
+                                        void* d_workspace, size_t workspace_bytes, hipStream_t st, uint32_t version) {
+    if (v->s.n > 255 || v->s.m > 255) return fail(BPP_E_ARG, "the container holds n, m <= 255");
+    if (version != 1 && !(version == 2 && uncompressed_bytes<C>() != 0))
+        return fail(BPP_E_ARG, "container version 2 (uncompressed points) is not offered for this curve");
+    MixedPlan p;
+    int rc = mixed_plan_serialized(v->s, m_of, count, (size_t)container_point_bytes<C>(version), true, p);
+    if (rc) return rc;
+    const SerMixedLayout L = ser_mixed_layout(v, p, count);
+    if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
+    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+    auto U64 = [&](size_t off) { return reinterpret_cast<uint64_t*>(ws + off); };
+    uint32_t* w_idx = reinterpret_cast<uint32_t*>(ws + L.idx);
+    uint32_t* w_rec = reinterpret_cast<uint32_t*>(ws + L.records);
+    uint32_t* w_sc = reinterpret_cast<uint32_t*>(ws + L.scalars);
+    uint32_t* w_st = reinterpret_cast<uint32_t*>(ws + L.status);
+    uint32_t* w_ok = reinterpret_cast<uint32_t*>(ws + L.ok);
+    // pageable source: the copy has read it when the call returns
+    HIPCHK(hipMemcpyAsync(w_idx, p.sidx.data(), p.sidx.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(zero_words_async(w_st, count * 4, st));
+    const unsigned waves = (unsigned)(p.lanes / SER_WAVE);
+    hipLaunchKernelGGL(k_container_decode_mixed<C>, dim3(waves), dim3(SER_WAVE), 0, st, p.classes, w_idx, d_proofs,
+                       d_commitments, w_rec, w_sc, w_st, version);
+    if constexpr (C::ID == 0)   // cofactor > 1: membership of the prime-order subgroup
+        hipLaunchKernelGGL(k_records_subgroup_mixed<C>, dim3(waves), dim3(SER_WAVE), 0, st, p.classes, w_rec, w_st);
+    HIPCHK(hipGetLastError());
+    for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
+        if (!p.count[c]) continue;
+        const PassShape ps = class_shape(v, c);
+        const uint64_t* recs = U64(L.records) + p.pt[c] * PW;
+        uint64_t* ch = transcript ? U64(L.challenges) + p.chal[c] * 4 : nullptr;
+        if (transcript) {
+            rc = derive_challenges(v, ps, recs, p.count[c], ch, st);
+            if (rc) return rc;
+        }
+        rc = run(v, ps, recs, U64(L.scalars) + p.first[c] * 12, p.count[c], ch, w_ok + p.first[c], ws + L.run,
+                 workspace_bytes - L.run, nullptr, nullptr, st);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_mixed_status_scatter<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, w_idx, w_st, w_ok, d_ok, count);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }

@@ -4,9 +4,12 @@
 // serves (n, m_i): g, h and G_0.. sit where they sit, its H_i n (m - m_i) generators further on (VerifyShape::hgap).
 // The pass gathers the caller-order records into one contiguous region per class (m_i), runs today's pass over each
 // region with the class's view, and scatters the verdicts back into caller order.
+// Serialized form (bpp_range_verify_batch_serialized_mixed_device): the container decoder is the producer of the
+// records, so it writes them straight into the class regions (k_container_decode_mixed) and nothing is gathered.
 #pragma once
 #include <vector>
 
+#include "codec.hpp"
 #include "host_util.hpp"
 
 namespace bpp {
@@ -64,6 +67,99 @@ __global__ void __launch_bounds__(256) k_mixed_scatter(const uint32_t* __restric
     }
 }
 
+// ---- serialized mixed batches: the decoder writes the class regions ------------------------------------------------
+// one entry per proof, by GATHERED position (built on the host, SX_WORDS 32-bit words): the byte offsets of its container
+// and of its commitments in the caller's packed buffers, and its caller position
+enum { SX_PROOF = 0, SX_COMM, SX_CALLER, SX_WORDS = 4 };
+
+// The class regions as the decode kernels see them, passed by value.  One lane per record point in gathered order; each
+// class's lane range is padded to a multiple of the wave size, so a wave (= a block of these kernels) never straddles
+// two classes and the class lookup below is wave-uniform.
+struct SerClasses {
+    uint32_t lane_end[MIXED_CLASSES];   // end of class c's padded lane range (cumulative, multiples of 64)
+    uint32_t lanes[MIXED_CLASSES];      // lanes of the range in use: proofs of the class x NV(c)
+    uint32_t first[MIXED_CLASSES];      // first gathered position of the class
+    uint32_t pt[MIXED_CLASSES];         // first gathered record point of the class
+    uint32_t n, logn;
+};
+constexpr uint32_t SER_WAVE = 64;
+
+// a lane of the serialized mixed kernels: its class's shape (n, m, k, NV), the proof's gathered position, the point's
+// index in the record and among the gathered points; `live` false for a padding lane
+struct SerLane {
+    uint32_t m, k, NV, pos, t, point;
+    bool live;
+};
+// base: the wave's first lane (wave-uniform, so the comparisons and selects below are scalar work)
+__device__ __forceinline__ SerLane ser_lane(const SerClasses& g, uint32_t base, uint32_t lane_in_wave) {
+    uint32_t c = 0;
+#pragma unroll
+    for (int j = 0; j < MIXED_CLASSES - 1; j++) c += base >= g.lane_end[j] ? 1u : 0u;   // empty classes are skipped
+    uint32_t start = 0, lanes = 0, first = 0, pt = 0;
+#pragma unroll
+    for (int j = 0; j < MIXED_CLASSES; j++)
+        if ((uint32_t)j == c) {
+            start = j ? g.lane_end[j - 1] : 0u;
+            lanes = g.lanes[j];
+            first = g.first[j];
+            pt = g.pt[j];
+        }
+    SerLane L;
+    L.m = 1u << c;
+    L.k = g.logn + c;
+    L.NV = 3 + 2 * L.k + L.m;
+    const uint32_t j = base - start + lane_in_wave;
+    L.live = j < lanes;
+    const uint32_t r = j / L.NV;
+    L.pos = first + r;
+    L.t = j - r * L.NV;
+    L.point = pt + j;
+    return L;
+}
+
+// k_container_decode over a mixed batch: one lane per record point of all classes in gathered order.  The containers are
+// read where the caller packed them (idx: SX_PROOF / SX_COMM, lengths implied by m_of on the host, never by the bytes)
+// and decoded straight into the class regions; status words by gathered position.
+template <class C>
+__global__ void __launch_bounds__(64, 2) k_container_decode_mixed(SerClasses g, const uint32_t* __restrict__ idx,
+                                                                  const uint8_t* __restrict__ proofs,
+                                                                  const uint8_t* __restrict__ commitments,
+                                                                  uint32_t* __restrict__ records, uint32_t* __restrict__ scalars,
+                                                                  uint32_t* __restrict__ status, uint32_t version) {
+    constexpr int N = C::Fp::N;
+    const SerLane L = ser_lane(g, blockIdx.x * SER_WAVE, threadIdx.x);
+    if (!L.live) return;
+    const int CB = container_point_bytes<C>(version);
+    const uint32_t* e = idx + (size_t)L.pos * SX_WORDS;
+    const uint32_t npp = 3 + 2 * L.k;
+    const uint8_t* rec = proofs + e[SX_PROOF];
+    const uint8_t* src = L.t < npp ? rec + CONTAINER_HDR + (size_t)L.t * CB : commitments + e[SX_COMM] + (size_t)(L.t - npp) * CB;
+    if (!container_decode_lane<C>(rec, src, L.t, g.n, L.m, L.k, version, records + (size_t)L.point * (2 * N + 2),
+                                  scalars + (size_t)L.pos * 24))
+        atomicOr(status + L.pos, 1u);
+}
+
+// k_records_subgroup over the class regions (same lanes as k_container_decode_mixed): one launch for all classes
+template <class C>
+__global__ void __launch_bounds__(64, 2) k_records_subgroup_mixed(SerClasses g, uint32_t* __restrict__ records,
+                                                                  uint32_t* __restrict__ status) {
+    constexpr int N = C::Fp::N;
+    const SerLane L = ser_lane(g, blockIdx.x * SER_WAVE, threadIdx.x);
+    if (!L.live) return;
+    if (record_leaves_subgroup<C>(records + (size_t)L.point * (2 * N + 2))) atomicOr(status + L.pos, 1u);
+}
+
+// k_container_status and the scatter in one: out_ok[caller position] = FormatError where the decoder rejected the proof,
+// else the pass's verdict
+template <class C>
+__global__ void __launch_bounds__(256) k_mixed_status_scatter(const uint32_t* __restrict__ idx, const uint32_t* __restrict__ status,
+                                                              const uint32_t* __restrict__ ok, uint32_t* __restrict__ out_ok,
+                                                              size_t count) {
+    const size_t pos = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos >= count) return;
+    out_ok[idx[pos * SX_WORDS + SX_CALLER]] = status[pos] ? (uint32_t)BPP_FORMAT_ERROR : ok[pos];
+}
+
 // The classes of a mixed batch.  Class c holds the proofs with m_i = 2^c, gathered in caller order behind the classes
 // below it.  idx (when wanted): the per-proof entries k_mixed_gather / k_mixed_scatter read.
 struct MixedPlan {
@@ -71,6 +167,11 @@ struct MixedPlan {
     size_t pt[MIXED_CLASSES] = {}, chal[MIXED_CLASSES] = {};       // its first gathered wire point / challenge
     size_t points = 0, chals = 0;                                   // totals
     std::vector<uint32_t> idx;
+    // serialized form (mixed_plan_serialized): the packed input's sizes, the per-proof entries by gathered position
+    // (SX_*), the lane ranges of the decode kernels
+    size_t proof_bytes = 0, comm_bytes = 0, lanes = 0;
+    std::vector<uint32_t> sidx;
+    SerClasses classes = {};
 };
 
 // cap: the verifier's shape.  BPP_E_ARG (with the index of the first offending proof) for an m_i that is zero, not a power
@@ -117,6 +218,61 @@ inline int mixed_plan(const VerifyShape& cap, const uint32_t* m_of, size_t count
         e[MX_NCH] = (uint32_t)nch(c);
         src_pt += nv(c);
         src_ch += nch(c);
+    }
+    return BPP_OK;
+}
+
+// mixed_plan for containers packed back to back in caller order (container i of hdr + (3 + 2 k_i) pb + 96 bytes, then
+// m_i encoded commitments of pb bytes each in a buffer of their own).  pb: bytes of an encoded point.  BPP_E_ARG also
+// for a batch whose byte offsets do not fit the 32-bit index.
+inline int mixed_plan_serialized(const VerifyShape& cap, const uint32_t* m_of, size_t count, size_t pb, bool want_idx,
+                                 MixedPlan& p) {
+    int rc = mixed_plan(cap, m_of, count, false, p);
+    if (rc) return rc;
+    uint32_t logm = 0;
+    while ((1u << logm) < cap.m) logm++;
+    const uint32_t logn = cap.k - logm;
+    auto nv = [&](uint32_t c) -> size_t { return 3 + 2 * (logn + c) + ((size_t)1 << c); };
+    auto cbytes = [&](uint32_t c) -> size_t { return CONTAINER_HDR + (size_t)(3 + 2 * (logn + c)) * pb + 96; };
+    SerClasses& g = p.classes;
+    g.n = cap.n;
+    g.logn = logn;
+    size_t lanes = 0;
+    for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
+        p.proof_bytes += p.count[c] * cbytes(c);
+        p.comm_bytes += (p.count[c] << c) * pb;
+        const size_t used = p.count[c] * nv(c);   // < 2^28 in all (mixed_plan)
+        lanes += (used + SER_WAVE - 1) / SER_WAVE * SER_WAVE;
+        g.lane_end[c] = (uint32_t)lanes;
+        g.lanes[c] = (uint32_t)used;
+        g.first[c] = (uint32_t)p.first[c];
+        g.pt[c] = (uint32_t)p.pt[c];
+    }
+    p.lanes = lanes;
+    if ((p.proof_bytes | p.comm_bytes) >> 32) {   // name the first proof that ends beyond 4 GiB
+        size_t i = 0;
+        for (size_t pr = 0, cm = 0; i < count; i++) {
+            const uint32_t c = (uint32_t)__builtin_ctz(m_of[i]);
+            pr += cbytes(c);
+            cm += ((size_t)1 << c) * pb;
+            if ((pr | cm) >> 32) break;
+        }
+        return fail(BPP_E_ARG, "batch too large: the bytes of m_of[" + std::to_string(i) + "] lie beyond the 32-bit index");
+    }
+    if (!want_idx) return BPP_OK;
+    p.sidx.assign(count * SX_WORDS, 0u);
+    size_t next[MIXED_CLASSES];
+    for (uint32_t c = 0; c < MIXED_CLASSES; c++) next[c] = p.first[c];
+    size_t src_pr = 0, src_cm = 0;
+    for (size_t i = 0; i < count; i++) {
+        uint32_t c = 0;
+        while ((1u << c) < m_of[i]) c++;
+        uint32_t* e = p.sidx.data() + next[c]++ * SX_WORDS;
+        e[SX_PROOF] = (uint32_t)src_pr;
+        e[SX_COMM] = (uint32_t)src_cm;
+        e[SX_CALLER] = (uint32_t)i;
+        src_pr += cbytes(c);
+        src_cm += ((size_t)1 << c) * pb;
     }
     return BPP_OK;
 }

@@ -473,6 +473,49 @@ int bpp_range_verify_batch_serialized_grouped_device(bpp_verifier *v, const void
                                                      uint32_t group, uint32_t *d_ok, uint64_t *stats, void *d_workspace,
                                                      size_t workspace_bytes, void *stream);
 
+/* ---- serialized proofs of MIXED aggregation sizes: a block of bytes off the wire against ONE verifier's tables ----
+ * bpp_range_verify_batch_serialized_device for a batch in which proof i carries m_i commitments, m_i a power of two <=
+ * the verifier's m (see "mixed batches" above).  d_ok[i], in caller order, is 0 Ok / 1 VerificationError / 2 FormatError,
+ * the verdict being RangeProof::verify(proof_i, PublicKey::new(n m_i), n, V_i): the prefix key of the proof's own shape,
+ * exactly as bpp_verifier_run_mixed defines it; FormatError takes precedence as on the single-shape path.
+ *   d_proofs      : the containers packed back to back in caller order, container i of
+ *                   bpp_proof_bytes_version(curve, n, m_of[i], version) bytes
+ *   d_commitments : m_of[i] encoded commitments per proof, packed in caller order
+ *   m_of          : HOST array of count values m_i (the framing layer knows each length; bpp_proofs_scan recovers them
+ *                   from a bare stream)
+ *   flags         : BPP_SER_TRANSCRIPT, BPP_SER_UNCOMPRESSED as above (version 2 is refused for ristretto255)
+ *   d_workspace   : bpp_verifier_serialized_mixed_workspace_bytes(v, m_of, count) bytes (0 when an m_i is not taken)
+ * A container whose header disagrees with m_of[i] (m, k, n, curve, version, magic, reserved bytes) is a FormatError OF
+ * THAT PROOF ONLY: every length comes from m_of, never from the bytes, so its neighbours are read where they are.
+ * An m_i that is zero, not a power of two or larger than m, a workspace that is too small or a NULL pointer returns
+ * BPP_E_ARG, with the offending proof's index in bpp_last_error(), enqueues nothing and leaves d_ok untouched; so does a
+ * batch of 4 GiB or more of containers or of commitments (the per-proof index holds 32-bit byte offsets); count = 0 is
+ * BPP_OK.
+ * The call BLOCKS the host while it uploads the per-proof index array (16 bytes per proof, a pageable copy on `stream`,
+ * which first waits for the work already queued there); everything else is enqueued asynchronously on `stream`: one
+ * decode of every container straight into one region of records per m_i (k_container_decode_mixed; no record is copied a
+ * second time), the subgroup test, per m_i present the challenges (BPP_SER_TRANSCRIPT) and one pass of bpp_verifier_run
+ * over its region, the statuses back into caller order.  bpp_verifier_set_subgroup_check applies as it does to
+ * bpp_range_verify_batch_serialized_device.  Several host threads may use one verifier at once, each call with a
+ * workspace and buffers of its own. */
+size_t bpp_verifier_serialized_mixed_workspace_bytes(const bpp_verifier *v, const uint32_t *m_of, size_t count);
+int bpp_range_verify_batch_serialized_mixed_device(bpp_verifier *v, const void *d_proofs, const void *d_commitments,
+                                                   const uint32_t *m_of, size_t count, int flags, uint32_t *d_ok,
+                                                   void *d_workspace, size_t workspace_bytes, void *stream);
+/* the same on HOST buffers (proofs, commitments, m_of laid out as above); synchronous.  out_ok: count x uint32_t. */
+int bpp_range_verify_batch_serialized_mixed(bpp_verifier *v, const uint8_t *proofs, const uint8_t *commitments,
+                                            const uint32_t *m_of, size_t count, int flags, uint32_t *out_ok);
+/* Frames a bare byte stream of concatenated containers (host memory; no device, no context): m_of[i] = the m of container
+ * i, whose length its header implies (n, m, k, version).  BPP_OK with *out_count containers when the stream is consumed
+ * exactly (an empty stream: 0).  Otherwise a negative code, *out_count = the containers before the offending one, and
+ * "container <index> at byte <offset>: <why>" in bpp_last_error(): BPP_E_LENGTH for a header that cannot be walked (bad
+ * magic, a version, curve or n other than asked for, m not a power of two, k != log2(n m), a truncated tail), BPP_E_ARG
+ * when there are more than max_count containers or for a curve / version / n (a power of two <= 255) that has no
+ * container.  It validates only what it needs to find the next container and never reads beyond proofs_bytes; the
+ * reserved bytes, the encodings and the scalars stay the decoder's business. */
+int bpp_proofs_scan(int curve_id, size_t n, int version, const uint8_t *proofs, size_t proofs_bytes, uint32_t *m_of,
+                    size_t max_count, size_t *out_count);
+
 /* name of the kernel that dominates bpp_verifier_run (for profilers) and its launch geometry */
 const char *bpp_verifier_dominant_kernel(void);
 

@@ -8,7 +8,13 @@ s'.  Prints one JSON object: both times (device events, after warm-up) with thei
 mixed block, the table bytes of the one verifier against the sum of the dedicated ones, and whether the verdict vectors
 are identical.
 usage: python tools/mixed_bench.py [--reps 20] [--warmup 3] [--window 16] [--out profiles/mixed_bench.json]
-       [--mixed-only]   (no dedicated verifiers: the run to put under rocprofv3 --kernel-trace --stats)"""
+       [--mixed-only]   (no dedicated verifiers: the run to put under rocprofv3 --kernel-trace --stats)
+       [--serialized]   the same block as BYTES: proofs made under the transcript, encoded as containers, and verified by
+                        bpp_range_verify_batch_serialized_mixed_device (one call) against five
+                        bpp_range_verify_batch_serialized_device calls on the dedicated verifiers, the two ALTERNATED
+                        repetition by repetition; also, timed by the wall clock, the host-side detour the one call
+                        replaces (decode per class, re-pack wire records, derive_challenges_mixed + run_mixed).
+                        Write it with --out profiles/mixed_serialized_bench.json"""
 import argparse
 import json
 import os
@@ -54,6 +60,8 @@ def main():
     ap.add_argument("--tamper", type=int, default=8, help="proofs with a flipped s'")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--mixed-only", action="store_true")
+    ap.add_argument("--serialized", action="store_true")
+    ap.add_argument("--detour-reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -83,7 +91,7 @@ def main():
         vals = rng.integers(0, 1 << 31, size=(cnt, m), dtype=np.uint64)
         gams = rng.integers(1, 1 << 62, size=(cnt, m, 4), dtype=np.uint64)
         gams[:, :, 1:] = 0
-        pts, sc, V = ded[m].prove_batch(vals, gams)
+        pts, sc, V = ded[m].prove_batch(vals, gams, transcript=args.serialized)
         recs[m] = np.concatenate([pts, V], axis=1)
         scs[m] = sc
     if args.mixed_only:
@@ -100,6 +108,8 @@ def main():
     count = len(order)
     ms = [m for m, _ in order]
     PW = a.PW
+    if args.serialized:
+        return serialized(args, torch, B, a, cap, ded, recs, scs, order, ms, build_s)
     packed = np.ascontiguousarray(np.concatenate([recs[m][i] for m, i in order]))
     d_pts = torch.from_numpy(packed.view(np.int64)).to(dev)
     d_sc = torch.from_numpy(np.ascontiguousarray(np.stack([scs[m][i] for m, i in order])).view(np.int64)).to(dev)
@@ -148,6 +158,120 @@ def main():
                     "ratio_mixed_over_dedicated": statistics.median(t_mixed) / statistics.median(t_ded),
                     "table_bytes_dedicated_sum": int(sum(ded[m].table_bytes for m in MIX)),
                     "verdicts_identical": bool(np.array_equal(ok_mixed, ok_ded))})
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+def serialized(args, torch, B, a, cap, ded, recs, scs, order, ms, build_s):
+    """the --serialized leg: the block as containers in HBM, transcript on"""
+    dev = torch.device("cuda:0")
+    stream = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
+    count = len(order)
+    blobs, comms = {}, {}
+    for m in MIX:
+        k = (N * m).bit_length() - 1
+        blobs[m] = B.encode_proofs(a, N, m, recs[m][:, :3 + 2 * k], scs[m])
+        comms[m] = B.compress_points(a, recs[m][:, 3 + 2 * k:].reshape(-1, a.PW)).reshape(len(recs[m]), -1)
+    raw = np.concatenate([blobs[m][i] for m, i in order])
+    cm = np.concatenate([comms[m][i] for m, i in order])
+    assert B.proofs_scan(a, N, raw).tolist() == ms
+    d_raw, d_cm = torch.from_numpy(raw).to(dev), torch.from_numpy(cm).to(dev)
+    d_ok = torch.full((count,), 7, dtype=torch.int32, device=dev)
+    wsb = cap.serialized_mixed_workspace_bytes(ms)
+    d_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+
+    def one_call():
+        cap.verify_serialized_mixed_device(d_raw.data_ptr(), d_cm.data_ptr(), ms, d_ok.data_ptr(), d_ws.data_ptr(), wsb,
+                                           stream(), transcript=True)
+
+    res = {"shape": {"curve": "bls12_381", "n": N, "capacity_m": CAP, "window": args.window, "count": count,
+                     "mix": {str(m): c for m, c in MIX.items()}, "tampered": args.tamper, "transcript": True,
+                     "container_bytes": int(len(raw)), "commitment_bytes": int(len(cm))},
+           "table_bytes_one": int(cap.table_bytes), "serialized_mixed_workspace_bytes": int(wsb), "build_s": build_s}
+    if args.mixed_only:
+        t_one = timed(torch, one_call, args.reps, args.warmup)
+        res.update({"serialized_mixed": stats(t_one), "rejects": int((d_ok.cpu().numpy() != 0).sum())})
+        return finish(args, res)
+    pos = {m: [j for j, (mm, _) in enumerate(order) if mm == m] for m in MIX}
+    bufs = {}
+    for m in MIX:
+        idx = [order[j][1] for j in pos[m]]
+        cnt = len(idx)
+        w = ded[m].serialized_workspace_bytes(cnt)
+        bufs[m] = (torch.from_numpy(np.ascontiguousarray(blobs[m][idx])).to(dev),
+                   torch.from_numpy(np.ascontiguousarray(comms[m][idx])).to(dev),
+                   torch.full((cnt,), 7, dtype=torch.int32, device=dev), torch.empty(w, dtype=torch.uint8, device=dev), w, cnt)
+
+    def five_calls():
+        for m in MIX:
+            p, c, o, w, wb, cnt = bufs[m]
+            ded[m].verify_serialized_device(p.data_ptr(), c.data_ptr(), cnt, o.data_ptr(), w.data_ptr(), wb, stream(),
+                                            transcript=True)
+
+    # alternated on one box: one repetition of each, in turn
+    for _ in range(args.warmup):
+        one_call()
+        five_calls()
+    torch.cuda.synchronize()
+    t_one, t_five = [], []
+    for _ in range(args.reps):
+        t_one += timed(torch, one_call, 1, 0)
+        t_five += timed(torch, five_calls, 1, 0)
+    ok_one = d_ok.cpu().numpy().astype(np.uint32)
+    ok_five = np.zeros(count, dtype=np.uint32)
+    for m in MIX:
+        ok_five[pos[m]] = bufs[m][2].cpu().numpy().astype(np.uint32)
+    res.update({"serialized_mixed": stats(t_one), "dedicated_serialized": stats(t_five),
+                "ratio_mixed_over_dedicated": statistics.median(t_one) / statistics.median(t_five),
+                "serialized_mixed_verifies_per_s": count / (statistics.median(t_one) / 1e3),
+                "rejects": int((ok_one != 0).sum()), "format_errors": int((ok_one == 2).sum()),
+                "table_bytes_dedicated_sum": int(sum(ded[m].table_bytes for m in MIX)),
+                "status_vectors_identical": bool(np.array_equal(ok_one, ok_five))})
+    # the "before": what a user of this library did with such a block -- decode each class on its own, re-pack the wire
+    # records in caller order, then the unserialized mixed call under the transcript.  Host work: timed by the wall clock.
+    if args.detour_reps:
+        nch = [3 + (N * m).bit_length() - 1 for m in ms]
+        w2 = cap.mixed_workspace_bytes(ms)
+        d_ws2 = torch.empty(w2, dtype=torch.uint8, device=dev)
+        d_ch = torch.zeros(sum(nch) * 4, dtype=torch.int64, device=dev)
+        d_ok2 = torch.full((count,), 7, dtype=torch.int32, device=dev)
+        lens = [len(blobs[m][0]) for m in ms]
+        starts = np.concatenate([[0], np.cumsum(lens)])
+        clens = [len(comms[m][0]) for m in ms]
+        cstarts = np.concatenate([[0], np.cumsum(clens)])
+        t_detour = []
+        for _ in range(args.detour_reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            status = np.zeros(count, dtype=np.uint32)
+            rec_of, sc_of = [None] * count, [None] * count
+            for m in MIX:
+                sel = pos[m]
+                pb = np.stack([raw[starts[j]:starts[j + 1]] for j in sel])
+                pts, sc, st = B.decode_proofs(a, N, m, pb)
+                V, vok = B.decompress_points(a, np.stack([cm[cstarts[j]:cstarts[j + 1]] for j in sel]).reshape(-1, comms[m].shape[1] // m))
+                V = V.reshape(len(sel), m, a.PW)
+                st = st | (2 * (vok.reshape(len(sel), m).max(axis=1) != 0)).astype(np.uint32)
+                for t, j in enumerate(sel):
+                    rec_of[j] = np.concatenate([pts[t], V[t]])
+                    sc_of[j] = sc[t]
+                    status[j] = st[t]
+            d_pts = torch.from_numpy(np.ascontiguousarray(np.concatenate(rec_of)).view(np.int64)).to(dev)
+            d_sc = torch.from_numpy(np.ascontiguousarray(np.stack(sc_of)).view(np.int64)).to(dev)
+            cap.derive_challenges_mixed_device(d_pts.data_ptr(), ms, d_ch.data_ptr(), d_ws2.data_ptr(), w2, stream())
+            cap.run_mixed_device(d_pts.data_ptr(), d_sc.data_ptr(), ms, d_ok2.data_ptr(), d_ws2.data_ptr(), w2, stream(),
+                                 d_challenges=d_ch.data_ptr())
+            ok2 = d_ok2.cpu().numpy().astype(np.uint32)
+            ok2[status != 0] = 2
+            t_detour.append((time.perf_counter() - t0) * 1e3)
+        res.update({"host_detour_wall": stats(t_detour), "host_detour_statuses_identical": bool(np.array_equal(ok2, ok_one))})
+    return finish(args, res)
+
+
+def finish(args, res):
     print(json.dumps(res))
     if args.out:
         with open(args.out, "w") as f:
