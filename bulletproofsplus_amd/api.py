@@ -300,6 +300,22 @@ def proofs_scan(arith, n: int, data, version: int = 1) -> np.ndarray:
     return ms[:count.value]
 
 
+def mixed_groups(ms, group: int) -> np.ndarray:
+    """The partition of the grouped check over a mixed batch (bpp_verifier_run_grouped_mixed; pure host code): the group
+    number of every proof, in caller order.  The batch is gathered by aggregation size -- the proofs with ms[i] = 1 in caller
+    order, then those with 2, 4, ... -- and group g holds the gathered positions [g * group, (g + 1) * group): a group may
+    hold proofs of several sizes and the last one may be short.  `stats` of the call = (groups holding at least one proof the
+    exact check rejects, the sizes of those groups)."""
+    m = np.ascontiguousarray(ms, dtype=np.uint32).reshape(-1)
+    if group < 2 or group & (group - 1):
+        raise ValueError("group must be a power of two, at least 2")
+    if len(m) and (m.min() == 0 or np.any(m & (m - 1))):
+        raise ValueError("every ms[i] must be a power of two")
+    pos = np.empty(len(m), dtype=np.int64)
+    pos[np.argsort(m, kind="stable")] = np.arange(len(m))   # gathered position of caller i
+    return pos // group
+
+
 class FormatError(ProofError):
     """ProofError::FormatError (reference src/errors.rs:20): a serialized proof that does not parse"""
 
@@ -795,6 +811,47 @@ class BatchVerifier:
             (1 if transcript else 0) | (2 if uncompressed else 0), _ptr(ok) if count else None),
             "bpp_range_verify_batch_serialized_mixed")
         return ok
+
+    # ---- the grouped check over mixed batches (include/bpp_amd.h; the partition: mixed_groups) ----
+    def grouped_mixed_workspace_bytes(self, ms, group: int = 32) -> int:
+        """bytes of device workspace run_grouped_mixed_device needs (0: an m_i or the group is not taken)"""
+        m = self._ms(ms)
+        return _lib.lib().bpp_verifier_grouped_mixed_workspace_bytes(self.handle, _ptr(m), len(m), group)
+
+    def run_grouped_mixed_device(self, d_points: int, d_scalars: int, ms, weight_key, index_base: int, d_out_verdicts: int,
+                                 d_workspace: int, workspace_bytes: int, group: int = 32, stream: int = 0,
+                                 d_challenges: int = 0, d_weights: int = 0):
+        """run_mixed_device's verdict vector through the grouped check: one weighted check per group of `group` neighbours of
+        the batch gathered by aggregation size (mixed_groups(ms, group) is the partition), an exact pass over the proofs of
+        the groups that fail.  Input as for run_mixed_device; weight_key / d_weights (caller order) as for
+        run_grouped_device.  Synchronises the stream.  -> (groups that failed, proofs re-verified exactly)"""
+        m = self._ms(ms)
+        stats = (ctypes.c_uint64 * 2)()
+        check(_lib.lib().bpp_verifier_run_grouped_mixed(self.handle, d_points, d_scalars, _ptr(m), len(m), d_challenges or None,
+                                                        _weight_key_arg(weight_key, d_weights), ctypes.c_uint64(index_base),
+                                                        d_weights or None, group, d_out_verdicts, stats, d_workspace,
+                                                        workspace_bytes, stream or None),
+              "bpp_verifier_run_grouped_mixed")
+        return int(stats[0]), int(stats[1])
+
+    def serialized_grouped_mixed_workspace_bytes(self, ms, group: int = 32) -> int:
+        """bytes of device workspace verify_serialized_grouped_mixed_device needs (0: an m_i or the group is not taken)"""
+        m = self._ms(ms)
+        return _lib.lib().bpp_verifier_serialized_grouped_mixed_workspace_bytes(self.handle, _ptr(m), len(m), group)
+
+    def verify_serialized_grouped_mixed_device(self, d_proofs: int, d_commitments: int, ms, d_ok: int, d_workspace: int,
+                                               workspace_bytes: int, weight_key: bytes = None, index_base: int = 0,
+                                               group: int = 32, stream: int = 0, transcript: bool = False,
+                                               uncompressed: bool = False):
+        """verify_serialized_mixed_device's status vector with the grouped check behind the decoder.  weight_key: 32 secret
+        bytes, None = os.urandom(32).  Synchronises the stream.  -> (groups that failed, proofs re-verified exactly)"""
+        m = self._ms(ms)
+        stats = (ctypes.c_uint64 * 2)()
+        check(_lib.lib().bpp_range_verify_batch_serialized_grouped_mixed_device(
+            self.handle, d_proofs, d_commitments, _ptr(m), len(m), (1 if transcript else 0) | (2 if uncompressed else 0),
+            _weight_key_arg(weight_key, 0), ctypes.c_uint64(index_base), group, d_ok, stats, d_workspace, workspace_bytes,
+            stream or None), "bpp_range_verify_batch_serialized_grouped_mixed_device")
+        return int(stats[0]), int(stats[1])
 
     def sum_partials_device(self, d_partials: int, n: int, d_ok: int, stream: int = 0):
         check(_lib.lib().bpp_verifier_sum_partials(self.handle, d_partials, n, d_ok, stream or None),

@@ -1046,6 +1046,60 @@ extern "C" int bpp_range_verify_batch_serialized_mixed(bpp_verifier* v, const ui
     });
 }
 
+// ---- the grouped check over mixed batches, wire records and bytes (impl_verify.hpp "grouped check over a MIXED batch") ----
+extern "C" size_t bpp_verifier_grouped_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count,
+                                                             uint32_t group) {
+    if ((count && !m_of) || count > 0x7fffffffu / 64) return 0;
+    return size_for(v, [&](auto cv) { return VerifyImpl<decltype(cv)>::grouped_mixed_workspace_bytes(v, m_of, count, group); });
+}
+
+extern "C" int bpp_verifier_run_grouped_mixed(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars,
+                                              const uint32_t* m_of, size_t count, const uint64_t* d_challenges,
+                                              const uint8_t* weight_key, uint64_t index_base, const uint64_t* d_weights,
+                                              uint32_t group, uint32_t* d_out_verdicts, uint64_t* stats, void* d_workspace,
+                                              size_t workspace_bytes, void* stream) {
+    if (!v) return fail(BPP_E_ARG, "null argument");
+    if (stats) stats[0] = stats[1] = 0;
+    if (count == 0) return BPP_OK;
+    if (!d_points || !d_scalars || !m_of || !d_out_verdicts || !d_workspace) return fail(BPP_E_ARG, "null argument");
+    if (!weight_key && !d_weights) return fail(BPP_E_ARG, "the grouped check needs a weight key or a weight buffer");
+    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::run_grouped_mixed(v, d_points, d_scalars, m_of, count, d_challenges, weight_key,
+                                                           index_base, d_weights, group, d_out_verdicts, stats, d_workspace,
+                                                           workspace_bytes, static_cast<hipStream_t>(stream));
+    });
+}
+
+extern "C" size_t bpp_verifier_serialized_grouped_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of,
+                                                                        size_t count, uint32_t group) {
+    if ((count && !m_of) || count > 0x7fffffffu / 64) return 0;
+    return size_for(v, [&](auto cv) {
+        return VerifyImpl<decltype(cv)>::ser_grouped_mixed_workspace_bytes(v, m_of, count, group);
+    });
+}
+
+extern "C" int bpp_range_verify_batch_serialized_grouped_mixed_device(bpp_verifier* v, const void* d_proofs,
+                                                                      const void* d_commitments, const uint32_t* m_of,
+                                                                      size_t count, int flags, const uint8_t* weight_key,
+                                                                      uint64_t index_base, uint32_t group, uint32_t* d_ok,
+                                                                      uint64_t* stats, void* d_workspace,
+                                                                      size_t workspace_bytes, void* stream) {
+    if (!v) return fail(BPP_E_ARG, "null argument");
+    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED)) return fail(BPP_E_ARG, "unknown flag");
+    if (stats) stats[0] = stats[1] = 0;
+    if (count == 0) return BPP_OK;
+    if (!d_proofs || !d_commitments || !m_of || !d_ok || !d_workspace || !weight_key) return fail(BPP_E_ARG, "null argument");
+    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    const int transcript = flags & BPP_SER_TRANSCRIPT;
+    const uint32_t version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::run_serialized_grouped_mixed(
+            v, static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), m_of, count, transcript != 0,
+            weight_key, index_base, group, d_ok, stats, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream), version);
+    });
+}
+
 // ---- device-side unit-test hooks (tests/ check the device field / group primitives against a CPU checker) --
 // field: 0 = base field, 1 = scalar field; op: 0 mul, 1 add, 2 sub, 3 inv, 4 sqr, 5 neg
 // a, b, out: n elements of N 32-bit words (N = 12 for BLS12-381 Fp, else 8), host pointers

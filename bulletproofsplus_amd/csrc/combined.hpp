@@ -40,23 +40,19 @@ struct WeightKey {
     uint32_t w[8];   // the 32 key bytes as little-endian words
 };
 template <class C>
-__global__ void __launch_bounds__(256) k_comb_weights(WeightKey key, uint64_t index_base,
-                                                      const uint32_t* __restrict__ raw, uint32_t* __restrict__ weights,
-                                                      size_t count) {
+__device__ __forceinline__ void comb_weight(const WeightKey& key, uint64_t idx, const uint32_t* __restrict__ raw,
+                                            uint32_t* __restrict__ out) {
     using P = typename C::Fr;
-    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= count) return;
     uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (raw) {
 #pragma unroll
-        for (int i = 0; i < 4; i++) w[i] = raw[p * 4 + i];
+        for (int i = 0; i < 4; i++) w[i] = raw[i];
     } else {
         Sha256 s;
         sha256_init(s);
 #pragma unroll
         for (int i = 0; i < 8; i++) sha256_word_le(s, key.w[i]);
         sha256_word_le(s, 0x77707062u);   // "bppw"
-        const uint64_t idx = index_base + p;
         sha256_word_le(s, (uint32_t)idx);
         sha256_word_le(s, (uint32_t)(idx >> 32));
         uint32_t dg[8];
@@ -71,7 +67,31 @@ __global__ void __launch_bounds__(256) k_comb_weights(WeightKey key, uint64_t in
     Fe<P> x = fe_from_canonical<P>(w);
     uint32_t o[8];
     fe_store(x, o);
-    st_words<8>(weights + p * 8, o);
+    st_words<8>(out, o);
+}
+template <class C>
+__global__ void __launch_bounds__(256) k_comb_weights(WeightKey key, uint64_t index_base,
+                                                      const uint32_t* __restrict__ raw, uint32_t* __restrict__ weights,
+                                                      size_t count) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= count) return;
+    comb_weight<C>(key, index_base + p, raw ? raw + p * 4 : nullptr, weights + p * 8);
+}
+// the same for a mixed batch (bpp_verifier_run_grouped_mixed): the weight belongs to the CALLER's numbering (the PRF's
+// index, the row of `raw`), and is stored by GATHERED position.  One lane per entry of the per-proof index `map`, `stride`
+// words each: from_word = the entry's word holding the caller position (the lane itself when >= stride), to_word = the
+// word holding the gathered position (likewise).  mixed.hpp: (MX_WORDS, MX_WORDS, MX_POS) / (SX_WORDS, SX_CALLER, SX_WORDS)
+template <class C>
+__global__ void __launch_bounds__(256) k_comb_weights_mixed(WeightKey key, uint64_t index_base,
+                                                            const uint32_t* __restrict__ raw,
+                                                            const uint32_t* __restrict__ map, uint32_t stride,
+                                                            uint32_t from_word, uint32_t to_word,
+                                                            uint32_t* __restrict__ weights, size_t count) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= count) return;
+    const size_t caller = from_word < stride ? map[p * stride + from_word] : p;
+    const size_t pos = to_word < stride ? map[p * stride + to_word] : p;
+    comb_weight<C>(key, index_base + caller, raw ? raw + caller * 4 : nullptr, weights + pos * 8);
 }
 
 // out[item] = canonical(w_p * s[p][var_term_index(v)]),  item = p * NV + v
@@ -177,6 +197,74 @@ __global__ void __launch_bounds__(64) k_comb_fixed_grouped(VerifyShape s, const 
     uint32_t w[8];
     fe_to_canonical(acc, w);
     st_words<8>(rows + (g * s.N + idx) * 8, w);
+}
+
+// ---- ... over a MIXED batch (mixed.hpp): groups of neighbours in GATHERED order, whatever the classes of their proofs ----
+// A view's generators ARE generators of the capacity table (table_generator), so a group's fixed-generator scalars collapse
+// into one row in the CAPACITY shape's numbering and the group runs as one virtual proof of the capacity shape.
+// The classes as the row kernel sees them, passed by value (the pattern of SerClasses): where each class's gathered range
+// ends and where its scalars [proofs of the class][N_c] begin, in scalars
+struct GroupClasses {
+    uint32_t end[8];    // first gathered position behind class c (cumulative; an empty class repeats its predecessor's)
+    uint64_t sc[8];     // first scalar of class c
+    uint32_t logn;      // log2 n: class c has k = logn + c
+};
+
+// rows[g][fixed_term_index(cap, f)] = canonical(sum_{p in group g} w_p * s[p][fixed_term_index(view_p, f_view)]) for every
+// capacity generator f, zero where no proof of the group has the term: one lane per (g, f), f fastest.  g, hence p, its class
+// and its weight are wave-uniform; a wave reads 64 neighbouring scalars of one proof at a time.  Capacity generator f is
+// generator f of the view (n, m') below 2 + n m' (g, h, G_i), generator f - hgap inside the view's H block
+// [2 + mn_cap, 2 + mn_cap + n m'), and no generator of the view otherwise.
+template <class C>
+__global__ void __launch_bounds__(64) k_comb_fixed_grouped_mixed(VerifyShape cap, GroupClasses gc,
+                                                                 const uint32_t* __restrict__ scalars,
+                                                                 const uint32_t* __restrict__ weights, size_t count,
+                                                                 uint32_t group, uint32_t* __restrict__ rows) {
+    using P = typename C::Fr;
+    using F = Fe<P>;
+    const uint32_t bpg = (cap.NF + 63) / 64;
+    const size_t g = blockIdx.x / bpg;
+    const uint32_t f = (blockIdx.x % bpg) * 64 + threadIdx.x;
+    if (f >= cap.NF) return;
+    F acc = F::zero();
+    for (uint32_t t = 0; t < group; t++) {
+        const size_t p = g * group + t;
+        if (p >= count) break;
+        uint32_t c = 0;
+#pragma unroll
+        for (int j = 0; j < 7; j++) c += p >= gc.end[j] ? 1u : 0u;
+        uint32_t first = 0;
+        uint64_t base = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++)
+            if ((uint32_t)j == c) {
+                first = j ? gc.end[j - 1] : 0u;
+                base = gc.sc[j];
+            }
+        const uint32_t mv = 1u << c, mnv = cap.n << c, kv = gc.logn + c;
+        const uint32_t Nv = 2 * mnv + 2 * kv + mv + 5;          // the view's MulVec length
+        uint32_t fv = f;                                         // the view's generator
+        if (f >= 2 + mnv) {
+            if (f < 2 + cap.mn || f >= 2 + cap.mn + mnv) continue;   // G_i or H_i beyond the view's key
+            fv = f - (cap.mn - mnv);
+        }
+        const uint32_t idx = fv < 2 ? 3 + fv : 5 + 2 * kv + (fv - 2);   // fixed_term_index of the view
+        uint32_t w[8];
+        ld_words<8>(scalars + (base + (p - first) * (size_t)Nv + idx) * 8, w);
+        const F x = fe_from_canonical<P>(w);
+        ld_words<8>(weights + p * 8, w);
+        acc = fe_add(acc, fe_mul(x, fe_load<P>(w)));
+    }
+    uint32_t w[8];
+    fe_to_canonical(acc, w);
+    st_words<8>(rows + (g * cap.N + fixed_term_index(cap, f)) * 8, w);
+}
+
+// bad[p] |= more[p] (the decoder's status of a serialized mixed batch: a rejected container fails its group)
+static __global__ void __launch_bounds__(256) k_comb_or_words(uint32_t* __restrict__ bad, const uint32_t* __restrict__ more,
+                                                              size_t count) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < count && more[p]) bad[p] = 1u;
 }
 
 // gbad[g] = any proof of group g carried an invalid point

@@ -179,9 +179,15 @@ struct VerifyImpl {
     // the caller's fixed-generator sums -- the weighted proof-point scalars, their digits and, once the tables have joined,
     // `per` window sums per proof (k_var_windows with `split`).  L: CombLayout or GroupLayout.
     template <class Layout, class FixedSums>
-    static int weighted_windows(bpp_verifier* v, uint8_t* ws, const Layout& L, size_t count, const uint8_t* weight_key,
-                                uint64_t index_base, const uint64_t* d_weights, uint32_t per, uint32_t split,
-                                std::unique_lock<std::mutex>& aux_lock, hipStream_t st, FixedSums&& fixed_sums);
+    static int weighted_windows(bpp_verifier* v, const PassShape& ps, uint8_t* ws, const Layout& L, size_t count,
+                                const uint8_t* weight_key, uint64_t index_base, const uint64_t* d_weights, uint32_t per,
+                                uint32_t split, std::unique_lock<std::mutex>& aux_lock, hipStream_t st,
+                                FixedSums&& fixed_sums);
+    // its second half alone, for a pass whose weights exist already (run_grouped_mixed writes them once for all classes):
+    // L's scalars, weights, var_sc, vdig, vtbl and vwsum
+    template <class Layout>
+    static int weighted_middle(bpp_verifier* v, const PassShape& ps, uint8_t* ws, const Layout& L, size_t count, uint32_t per,
+                               uint32_t split, std::unique_lock<std::mutex>& aux_lock, hipStream_t st);
     // one level of k_comb_window_fold: the window sums (`per` each) of every `step` neighbouring proofs of `nrem` added
     // into one; returns how many sums per window are left
     static size_t fold_windows(const uint32_t* in, size_t nrem, uint32_t step, uint32_t* out, uint32_t per, hipStream_t st);
@@ -399,6 +405,115 @@ struct VerifyImpl {
                               const uint64_t* d_challenges, uint32_t group, uint32_t* d_out_verdicts, uint64_t* h_stats,
                               void* d_workspace, size_t workspace_bytes, hipStream_t st);
 
+    // ---- grouped check over a MIXED batch (combined.hpp, mixed.hpp) -------------------------------------------
+    // The PARTITION: groups are runs of `group` neighbours in GATHERED order (classes ascending, caller order within a
+    // class): group g holds the gathered positions [g group, min(count, (g + 1) group)).  A group may straddle a class
+    // boundary and the last one may be short; the partition is fixed by (m_of, group) before any weight is drawn, which
+    // is all the soundness argument of the grouped check asks of it.  Each group is ONE virtual proof of the CAPACITY shape
+    // (k_comb_fixed_grouped_mixed), so the back end (finish) runs once whatever the mix -- and costs G capacity rows
+    // whatever the mix: a group of small proofs pays a full capacity row.
+    // workspace = front (the wire form's index, gathered records, scalar triples and challenges; the serialized form's
+    // index, class regions, triples, decoder status and challenges) | the core: verdicts, weights and invalid-point flags
+    // by gathered position, the scalars of every class, the front end's per-class buffers (shared by the classes, which
+    // run one after the other), the window sums by gathered position and their folds, per group the rows, flags, verdicts
+    // and the back end's workspace, and the exact second pass's slice buffers
+    struct GroupMixedLayout {
+        size_t idx, pts, sc3, status, challenges,                                       // the front
+            ok, weights, bad, scalars, cpts, prep, var_sc, vdig, vtbl, vscr, vwsum, vfold,   // per proof
+            grows, gbad, gok, tail,                                                     // per group
+            list, x_pts, x_sc, x_ch, x_ok, x_run,                                       // the exact second pass
+            total;
+        size_t sc_of[MIXED_CLASSES];   // class c's scalars [count_c][N_c], from `scalars`, in bytes
+        size_t groups, slice;
+    };
+    // the offsets begin_pass and weighted_middle take, for one class of the batch
+    struct ClassFront {
+        size_t pts, bad, prep, vtbl, vscr, scalars, weights, var_sc, vdig, vwsum;
+    };
+    static GroupMixedLayout group_mixed_layout(const bpp_verifier* v, const MixedPlan& p, size_t count, uint32_t group,
+                                               bool serialized) {
+        GroupMixedLayout w{};
+        w.groups = cdiv(count, group);
+        w.slice = std::min<size_t>(std::max<size_t>(count, 1), GROUP_EXACT_SLICE);
+        WsCarver o;
+        w.idx = o.take(count * (serialized ? (size_t)SX_WORDS : (size_t)MX_WORDS) * 4);
+        w.pts = o.take(p.points * WW * 4);
+        w.sc3 = o.take(count * 96);
+        w.status = o.take(serialized ? count * 4 : 0);
+        w.challenges = o.take(p.chals * 32);
+        w.ok = o.take(count * 4);
+        w.weights = o.take(count * 32);
+        w.bad = o.take(count * 4);
+        size_t scalars = 0, items = 0, prep = 0, xrun = 0, nv_max = 0, k_max = 0;
+        for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
+            w.sc_of[c] = scalars;
+            if (!p.count[c]) continue;
+            const VerifyShape& s = class_shape(v, c).s;
+            scalars += p.count[c] * (size_t)s.N * 32;
+            items = std::max(items, p.count[c] * s.NV);
+            prep = std::max(prep, p.count[c] * vs_prep_bytes<C>(s));
+            nv_max = std::max<size_t>(nv_max, s.NV);
+            k_max = std::max<size_t>(k_max, s.k);
+            // the exact pass of a class runs over however many of its proofs the failing groups hold, and a SMALLER batch
+            // can need a LARGER workspace (group_layout): room for the worst count up to the slice
+            for (size_t n = 1; n <= std::min(w.slice, p.count[c]); n++) xrun = std::max(xrun, ws_layout(s, n).total);
+        }
+        w.scalars = o.take(scalars);
+        for (uint32_t c = 0; c < MIXED_CLASSES; c++) w.sc_of[c] += w.scalars;
+        w.cpts = o.take(items * 2 * N * 4);
+        w.prep = o.take(prep);
+        w.var_sc = o.take(items * 32);
+        w.vdig = o.take(items * VAR_DIGIT_STRIDE);
+        w.vtbl = o.take(items * VAR_MULTIPLES * 2 * N * 4);
+        w.vscr = o.take(items * 2 * (VAR_MULTIPLES - 1) * N * 4);
+        w.vwsum = o.take(count * var_wsums<C>() * JW * 4);
+        w.vfold = o.take((size_t)cdiv(count, 2) * var_wsums<C>() * JW * 4);
+        w.grows = o.take(w.groups * (size_t)v->s.N * 32);
+        w.gbad = o.take(w.groups * 4);
+        w.gok = o.take(w.groups * 4);
+        w.tail = o.take(ws_layout(v->s, w.groups).total);
+        w.list = o.take(w.slice * 4);
+        w.x_pts = o.take(w.slice * nv_max * WW * 4);
+        w.x_sc = o.take(w.slice * 96);
+        w.x_ch = o.take(w.slice * (3 + k_max) * 32);
+        w.x_ok = o.take(w.slice * 4);
+        w.x_run = o.take(xrun);
+        w.total = o.total;
+        return w;
+    }
+    static bool group_ok(uint32_t group) { return group >= 2 && !(group & (group - 1)); }
+    // 0 for an m_of or a group the verifier does not take
+    static size_t grouped_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, uint32_t group) {
+        MixedPlan p;
+        if (!group_ok(group) || mixed_plan(v->s, m_of, count, false, p)) return 0;
+        return group_mixed_layout(v, p, count, group, false).total;
+    }
+    static size_t ser_grouped_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, uint32_t group) {
+        MixedPlan p;
+        const size_t pb = uncompressed_bytes<C>() ? uncompressed_bytes<C>() : compressed_bytes<C>();
+        if (!group_ok(group) || v->s.n > 255 || v->s.m > 255 || mixed_plan_serialized(v->s, m_of, count, pb, false, p))
+            return 0;
+        return group_mixed_layout(v, p, count, group, true).total;
+    }
+    // Input layout, m_of rules and errors: run_mixed's.  Weights (proof i of the CALLER's order gets PRF(key, index_base + i)
+    // or d_weights[i]), group, h_stats, verdict words and the stream synchronisation: run_grouped's.
+    static int run_grouped_mixed(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, const uint32_t* m_of,
+                                 size_t count, const uint64_t* d_challenges, const uint8_t* weight_key, uint64_t index_base,
+                                 const uint64_t* d_weights, uint32_t group, uint32_t* d_out_verdicts, uint64_t* h_stats,
+                                 void* d_workspace, size_t workspace_bytes, hipStream_t st);
+    // ... behind the decoder: run_serialized_mixed's front, d_ok 0 / 1 / 2 in caller order; a container the decoder rejects
+    // keeps FormatError and fails its group
+    static int run_serialized_grouped_mixed(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments,
+                                            const uint32_t* m_of, size_t count, bool transcript, const uint8_t* weight_key,
+                                            uint64_t index_base, uint32_t group, uint32_t* d_ok, uint64_t* h_stats,
+                                            void* d_workspace, size_t workspace_bytes, hipStream_t st, uint32_t version);
+    // the core of both, from the plan and the gathered regions in the workspace (L.pts, L.sc3, L.challenges when
+    // with_challenges, L.weights by gathered position, L.status when with_status): both passes; the verdicts are left in
+    // L.ok by GATHERED position for the caller's scatter.  Synchronises `st`.
+    static int grouped_mixed_core(bpp_verifier* v, const MixedPlan& p, size_t count, uint32_t group, bool with_challenges,
+                                  bool with_status, uint64_t* h_stats, uint8_t* ws, const GroupMixedLayout& L,
+                                  size_t workspace_bytes, hipStream_t st);
+
     // ---- batched prover (prover_batch.hpp) -------------------------------------------------------------
     // Device-resident form: values, gammas, outputs and workspace are device buffers, nothing touches the host
     // and nothing synchronises.  The batch is processed in chunks that reuse one workspace.
@@ -569,19 +684,28 @@ int VerifyImpl<C>::begin_pass(bpp_verifier* v, const PassShape& ps, const uint64
 
 template <class C>
 template <class Layout, class FixedSums>
-int VerifyImpl<C>::weighted_windows(bpp_verifier* v, uint8_t* ws, const Layout& L, size_t count, const uint8_t* weight_key,
-                                    uint64_t index_base, const uint64_t* d_weights, uint32_t per, uint32_t split,
-                                    std::unique_lock<std::mutex>& aux_lock, hipStream_t st, FixedSums&& fixed_sums) {
-    const VerifyShape& s = v->s;
-    auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
-    uint32_t *w_sc = W(L.scalars), *w_wt = W(L.weights), *w_vs = W(L.var_sc);
-    uint8_t* w_vd = ws + L.vdig;
-    const size_t items = count * s.NV;
+int VerifyImpl<C>::weighted_windows(bpp_verifier* v, const PassShape& ps, uint8_t* ws, const Layout& L, size_t count,
+                                    const uint8_t* weight_key, uint64_t index_base, const uint64_t* d_weights, uint32_t per,
+                                    uint32_t split, std::unique_lock<std::mutex>& aux_lock, hipStream_t st,
+                                    FixedSums&& fixed_sums) {
+    uint32_t* w_wt = reinterpret_cast<uint32_t*>(ws + L.weights);
     WeightKey wk;
     load_key_words(d_weights ? nullptr : weight_key, wk.w);
     hipLaunchKernelGGL(k_comb_weights<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, wk, index_base,
                        reinterpret_cast<const uint32_t*>(d_weights), w_wt, count);
     fixed_sums(w_wt);
+    return weighted_middle(v, ps, ws, L, count, per, split, aux_lock, st);
+}
+
+template <class C>
+template <class Layout>
+int VerifyImpl<C>::weighted_middle(bpp_verifier* v, const PassShape& ps, uint8_t* ws, const Layout& L, size_t count,
+                                   uint32_t per, uint32_t split, std::unique_lock<std::mutex>& aux_lock, hipStream_t st) {
+    const VerifyShape& s = ps.s;
+    auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    uint32_t *w_sc = W(L.scalars), *w_wt = W(L.weights), *w_vs = W(L.var_sc);
+    uint8_t* w_vd = ws + L.vdig;
+    const size_t items = count * s.NV;
     // proof-carried points: weighted scalars -> per-proof Straus window sums (the caller sums them across proofs)
     hipLaunchKernelGGL(k_comb_var_scalars<C>, dim3(cdiv(items, 256)), dim3(256), 0, st, s, w_sc, w_wt, w_vs, items);
     hipLaunchKernelGGL(k_var_digits<C>, dim3(cdiv(items, 256)), dim3(256), 0, st, s, w_vs, w_vd, items, 1u);
@@ -888,7 +1012,7 @@ int VerifyImpl<C>::run_combined(bpp_verifier* v, const uint64_t* d_points, const
     std::unique_lock<std::mutex> aux_lock;
     int rc = begin_pass(v, own(v), d_points, d_scalars, count, d_challenges, ws, L, w_sc, aux_lock, st, nullptr);
     if (rc) return rc;
-    rc = weighted_windows(v, ws, L, count, weight_key, index_base, d_weights, var_wsums<C>(), 1u, aux_lock, st,
+    rc = weighted_windows(v, own(v), ws, L, count, weight_key, index_base, d_weights, var_wsums<C>(), 1u, aux_lock, st,
                           [&](const uint32_t* w_wt) {
                               hipLaunchKernelGGL(k_comb_fixed<C>, dim3(s.NF), dim3(256), 0, st, s, w_sc, w_wt, count, w_cs);
                           });
@@ -942,7 +1066,7 @@ int VerifyImpl<C>::grouped_begin(bpp_verifier* v, const uint64_t* d_points, cons
     if (rc) return rc;
     const uint32_t tree = horner_form(s, G);
     const uint32_t per = tree == 1 ? var_wsums<C>() : var_windows<C>();   // window sums per proof, in the layout the Horner form reads
-    rc = weighted_windows(v, ws, L, count, weight_key, index_base, d_weights, per, tree == 1 ? 1u : 0u, aux_lock, st,
+    rc = weighted_windows(v, own(v), ws, L, count, weight_key, index_base, d_weights, per, tree == 1 ? 1u : 0u, aux_lock, st,
                           [&](const uint32_t* w_wt) {
                               hipLaunchKernelGGL(k_comb_fixed_grouped<C>, dim3((unsigned)(G * cdiv(s.NF, 64))), dim3(64), 0,
                                                  st, s, w_sc, w_wt, count, group, w_rows);
@@ -1014,6 +1138,196 @@ int VerifyImpl<C>::grouped_finish(bpp_verifier* v, const uint64_t* d_points, con
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));   // `list` slices are staged from pageable memory
     }
+    return BPP_OK;
+}
+
+// Pass 1: per class present, today's front end over the class's region with the class's view -- the proof points from the
+// wire, their tables, the verifier scalars, the weighted proof-point scalars and their window sums, `per` per proof into ONE
+// array by gathered position; then one row per group in the capacity shape's numbering, the groups' window sums, and the back
+// end once over G virtual proofs of the capacity shape.  Pass 2: the proofs of the failing groups, class by class (a class's
+// gathered range is contiguous), exactly, from the gathered regions.
+template <class C>
+int VerifyImpl<C>::grouped_mixed_core(bpp_verifier* v, const MixedPlan& p, size_t count, uint32_t group, bool with_challenges,
+                                      bool with_status, uint64_t* h_stats, uint8_t* ws, const GroupMixedLayout& L,
+                                      size_t workspace_bytes, hipStream_t st) {
+    const VerifyShape& cap = v->s;
+    auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    auto U64 = [&](size_t off) { return reinterpret_cast<uint64_t*>(ws + off); };
+    uint32_t *w_bad = W(L.bad), *w_rows = W(L.grows), *w_gbad = W(L.gbad), *w_gok = W(L.gok), *w_ok = W(L.ok);
+    const size_t G = L.groups;
+    const uint32_t tree = horner_form(cap, G);
+    const uint32_t per = tree == 1 ? var_wsums<C>() : var_windows<C>();   // window sums per proof, as the Horner form of G reads them
+    GroupClasses gc{};
+    uint32_t logm = 0;
+    while ((1u << logm) < cap.m) logm++;
+    gc.logn = cap.k - logm;
+    for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
+        gc.end[c] = (uint32_t)(p.first[c] + p.count[c]);
+        gc.sc[c] = (L.sc_of[c] - L.scalars) / 32;
+        if (!p.count[c]) continue;
+        const PassShape ps = class_shape(v, c);
+        ClassFront F;
+        F.pts = L.cpts, F.prep = L.prep, F.vtbl = L.vtbl, F.vscr = L.vscr, F.var_sc = L.var_sc, F.vdig = L.vdig;
+        F.bad = L.bad + p.first[c] * 4;
+        F.scalars = L.sc_of[c];
+        F.weights = L.weights + p.first[c] * 32;
+        F.vwsum = L.vwsum + p.first[c] * (size_t)per * JW * 4;
+        std::unique_lock<std::mutex> aux_lock;
+        int rc = begin_pass(v, ps, U64(L.pts) + p.pt[c] * PW, U64(L.sc3) + p.first[c] * 12, p.count[c],
+                            with_challenges ? U64(L.challenges) + p.chal[c] * 4 : nullptr, ws, F, W(F.scalars), aux_lock, st,
+                            nullptr);
+        if (rc) return rc;
+        rc = weighted_middle(v, ps, ws, F, p.count[c], per, tree == 1 ? 1u : 0u, aux_lock, st);
+        if (rc) return rc;
+    }
+    if (with_status)
+        hipLaunchKernelGGL(k_comb_or_words, dim3(cdiv(count, 256)), dim3(256), 0, st, w_bad, W(L.status), count);
+    hipLaunchKernelGGL(k_comb_fixed_grouped_mixed<C>, dim3((unsigned)(G * cdiv(cap.NF, 64))), dim3(64), 0, st, cap, gc,
+                       W(L.scalars), W(L.weights), count, group, w_rows);
+    hipLaunchKernelGGL(k_comb_group_bad, dim3(cdiv(G, 256)), dim3(256), 0, st, w_bad, count, group, w_gbad, G);
+    uint32_t* cur = W(L.vwsum);
+    uint32_t* nxt = W(L.vfold);
+    size_t nrem = count;
+    for (uint32_t left = group; left > 1; std::swap(cur, nxt)) {   // as grouped_begin: 4 (at last 2) to 1 per level
+        const uint32_t step = left >= 4 ? 4u : 2u;
+        nrem = fold_windows(cur, nrem, step, nxt, per, st);
+        left /= step;
+    }
+    int rc = finish(v, cap, ws + L.tail, ws_layout(cap, G), G, w_rows, cur, w_gbad, w_gok, nullptr, tree, false, st, nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_comb_group_spread, dim3(cdiv(count, 256)), dim3(256), 0, st, w_gok, group, w_ok, count);
+    HIPCHK(hipGetLastError());
+    // pass 2
+    std::vector<uint32_t> gok(G);
+    HIPCHK(hipMemcpyAsync(gok.data(), w_gok, G * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<uint32_t> redo[MIXED_CLASSES];   // per class, the failing groups' proofs as positions within the class
+    size_t failed = 0, redone = 0;
+    for (size_t g = 0; g < G; g++) {
+        if (!gok[g]) continue;
+        failed++;
+        for (size_t pos = g * group; pos < std::min(count, (g + 1) * (size_t)group); pos++) {
+            uint32_t c = 0;
+            while (pos >= p.first[c] + p.count[c]) c++;
+            redo[c].push_back((uint32_t)(pos - p.first[c]));
+            redone++;
+        }
+    }
+    if (h_stats) {
+        h_stats[0] = failed;
+        h_stats[1] = redone;
+    }
+    for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
+        const std::vector<uint32_t>& list = redo[c];
+        if (list.empty()) continue;
+        const PassShape ps = class_shape(v, c);
+        const uint32_t row_pts = ps.s.NV * WW, row_sc = 24, row_ch = (3 + ps.s.k) * 8;
+        for (size_t lo = 0; lo < list.size(); lo += L.slice) {
+            const size_t cnt = std::min(L.slice, list.size() - lo);
+            HIPCHK(hipMemcpyAsync(W(L.list), list.data() + lo, cnt * 4, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_comb_gather_rows, dim3((unsigned)cnt), dim3(256), 0, st,
+                               reinterpret_cast<const uint32_t*>(U64(L.pts) + p.pt[c] * PW), W(L.list), row_pts, W(L.x_pts));
+            hipLaunchKernelGGL(k_comb_gather_rows, dim3((unsigned)cnt), dim3(64), 0, st,
+                               reinterpret_cast<const uint32_t*>(U64(L.sc3) + p.first[c] * 12), W(L.list), row_sc, W(L.x_sc));
+            if (with_challenges)
+                hipLaunchKernelGGL(k_comb_gather_rows, dim3((unsigned)cnt), dim3(64), 0, st,
+                                   reinterpret_cast<const uint32_t*>(U64(L.challenges) + p.chal[c] * 4), W(L.list), row_ch,
+                                   W(L.x_ch));
+            rc = run(v, ps, U64(L.x_pts), U64(L.x_sc), cnt, with_challenges ? U64(L.x_ch) : nullptr, W(L.x_ok), ws + L.x_run,
+                     workspace_bytes - L.x_run, nullptr, nullptr, st);
+            if (rc) return rc;
+            hipLaunchKernelGGL(k_comb_scatter_words, dim3(cdiv(cnt, 256)), dim3(256), 0, st, W(L.x_ok), W(L.list),
+                               w_ok + p.first[c], cnt);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(st));   // `list` slices are staged from pageable memory
+        }
+    }
+    return BPP_OK;
+}
+
+template <class C>
+int VerifyImpl<C>::run_grouped_mixed(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars,
+                                     const uint32_t* m_of, size_t count, const uint64_t* d_challenges,
+                                     const uint8_t* weight_key, uint64_t index_base, const uint64_t* d_weights, uint32_t group,
+                                     uint32_t* d_out_verdicts, uint64_t* h_stats, void* d_workspace, size_t workspace_bytes,
+                                     hipStream_t st) {
+    MixedPlan p;
+    int rc = mixed_plan(v->s, m_of, count, true, p);
+    if (rc) return rc;
+    if (!group_ok(group)) return fail(BPP_E_ARG, "group must be a power of two, at least 2");
+    const GroupMixedLayout L = group_mixed_layout(v, p, count, group, false);
+    if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
+    if (h_stats) h_stats[0] = h_stats[1] = 0;
+    if (count == 0) return BPP_OK;
+    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+    uint32_t* w_idx = reinterpret_cast<uint32_t*>(ws + L.idx);
+    // pageable source: the copy has read it when the call returns
+    HIPCHK(hipMemcpyAsync(w_idx, p.idx.data(), p.idx.size() * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_mixed_gather<C>, dim3((unsigned)count), dim3(MIXED_BLOCK), 0, st, w_idx, count, d_points, d_scalars,
+                       d_challenges, reinterpret_cast<uint64_t*>(ws + L.pts), reinterpret_cast<uint64_t*>(ws + L.sc3),
+                       reinterpret_cast<uint64_t*>(ws + L.challenges));
+    // one lane per caller position: its weight, stored at its gathered position
+    WeightKey wk;
+    load_key_words(d_weights ? nullptr : weight_key, wk.w);
+    hipLaunchKernelGGL(k_comb_weights_mixed<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, wk, index_base,
+                       reinterpret_cast<const uint32_t*>(d_weights), w_idx, (uint32_t)MX_WORDS, (uint32_t)MX_WORDS,
+                       (uint32_t)MX_POS, reinterpret_cast<uint32_t*>(ws + L.weights), count);
+    HIPCHK(hipGetLastError());
+    rc = grouped_mixed_core(v, p, count, group, d_challenges != nullptr, false, h_stats, ws, L, workspace_bytes, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_mixed_scatter<C>, dim3(cdiv(count, 4)), dim3(256), 0, st, w_idx, count,
+                       reinterpret_cast<const uint32_t*>(ws + L.ok), nullptr, nullptr, d_out_verdicts, nullptr, nullptr);
+    HIPCHK(hipGetLastError());
+    return BPP_OK;
+}
+
+template <class C>
+int VerifyImpl<C>::run_serialized_grouped_mixed(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments,
+                                                const uint32_t* m_of, size_t count, bool transcript,
+                                                const uint8_t* weight_key, uint64_t index_base, uint32_t group, uint32_t* d_ok,
+                                                uint64_t* h_stats, void* d_workspace, size_t workspace_bytes, hipStream_t st,
+                                                uint32_t version) {
+    if (v->s.n > 255 || v->s.m > 255) return fail(BPP_E_ARG, "the container holds n, m <= 255");
+    if (version != 1 && !(version == 2 && uncompressed_bytes<C>() != 0))
+        return fail(BPP_E_ARG, "container version 2 (uncompressed points) is not offered for this curve");
+    MixedPlan p;
+    int rc = mixed_plan_serialized(v->s, m_of, count, (size_t)container_point_bytes<C>(version), true, p);
+    if (rc) return rc;
+    if (!group_ok(group)) return fail(BPP_E_ARG, "group must be a power of two, at least 2");
+    const GroupMixedLayout L = group_mixed_layout(v, p, count, group, true);
+    if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
+    if (h_stats) h_stats[0] = h_stats[1] = 0;
+    if (count == 0) return BPP_OK;
+    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+    auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    auto U64 = [&](size_t off) { return reinterpret_cast<uint64_t*>(ws + off); };
+    uint32_t *w_idx = W(L.idx), *w_st = W(L.status);
+    // pageable source: the copy has read it when the call returns
+    HIPCHK(hipMemcpyAsync(w_idx, p.sidx.data(), p.sidx.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(zero_words_async(w_st, count * 4, st));
+    const unsigned waves = (unsigned)(p.lanes / SER_WAVE);
+    hipLaunchKernelGGL(k_container_decode_mixed<C>, dim3(waves), dim3(SER_WAVE), 0, st, p.classes, w_idx, d_proofs,
+                       d_commitments, W(L.pts), W(L.sc3), w_st, version);
+    if constexpr (C::ID == 0)   // cofactor > 1: membership of the prime-order subgroup
+        hipLaunchKernelGGL(k_records_subgroup_mixed<C>, dim3(waves), dim3(SER_WAVE), 0, st, p.classes, W(L.pts), w_st);
+    // one lane per gathered position: the weight of its caller position
+    WeightKey wk;
+    load_key_words(weight_key, wk.w);
+    hipLaunchKernelGGL(k_comb_weights_mixed<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, wk, index_base,
+                       (const uint32_t*)nullptr, w_idx, (uint32_t)SX_WORDS, (uint32_t)SX_CALLER, (uint32_t)SX_WORDS,
+                       W(L.weights), count);
+    HIPCHK(hipGetLastError());
+    if (transcript)
+        for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
+            if (!p.count[c]) continue;
+            rc = derive_challenges(v, class_shape(v, c), U64(L.pts) + p.pt[c] * PW, p.count[c],
+                                   U64(L.challenges) + p.chal[c] * 4, st);
+            if (rc) return rc;
+        }
+    rc = grouped_mixed_core(v, p, count, group, transcript, true, h_stats, ws, L, workspace_bytes, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_mixed_status_scatter<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, w_idx, w_st, W(L.ok), d_ok, count);
+    HIPCHK(hipGetLastError());
     return BPP_OK;
 }
 

@@ -505,6 +505,40 @@ int bpp_range_verify_batch_serialized_mixed_device(bpp_verifier *v, const void *
 /* the same on HOST buffers (proofs, commitments, m_of laid out as above); synchronous.  out_ok: count x uint32_t. */
 int bpp_range_verify_batch_serialized_mixed(bpp_verifier *v, const uint8_t *proofs, const uint8_t *commitments,
                                             const uint32_t *m_of, size_t count, int flags, uint32_t *out_ok);
+/* ---- the grouped check over MIXED batches: wire records (bpp_verifier_run_mixed's input) and bytes off the wire ----
+ * bpp_verifier_run_grouped's verdicts for a batch in which proof i has m_of[i] commitments: the vector bpp_verifier_run_mixed
+ * writes (each proof against the prefix key of its own shape), at the grouped check's price when (nearly) every proof is
+ * valid, from ONE verifier's tables.  Input layout, m_of rules and blocking as for bpp_verifier_run_mixed; weights
+ * (weight_key / index_base / d_weights), group, stats, the verdict words, the soundness conditions and the stream
+ * synchronisation as for bpp_verifier_run_grouped.
+ * THE PARTITION.  The batch is gathered by aggregation size: all proofs with m_i = 1 in caller order, then those with
+ * m_i = 2, 4, ...  Group g holds the gathered positions [g * group, min(count, (g + 1) * group)): a group may hold proofs of
+ * two or more sizes and the last one may be short.  The partition depends on (m_of, group) only, so it is fixed before a
+ * weight is drawn; stats = [groups that failed, proofs re-verified exactly] follows from it and the exact verdicts.
+ * THE WEIGHTS belong to the caller's numbering: proof i (caller order) is weighted with PRF(weight_key, index_base + i), or
+ * with d_weights[i] (count x 16 bytes, caller order).
+ * Each group is one virtual proof of the verifier's CAPACITY shape (the generators of a smaller shape are generators of the
+ * capacity tables), so the last stages run once for the whole batch; a group costs one capacity-sized fixed-generator
+ * MulVec whatever the sizes of its proofs.
+ * Errors: BPP_E_ARG for an m_of[i] that is not taken (the text names i), a group that is not a power of two >= 2, a
+ * workspace that is too small, a NULL pointer; nothing is enqueued or written then.  count = 0 is BPP_OK, stats = {0, 0}.
+ * The workspace-size calls return 0 for an m_of or a group that is not taken. */
+size_t bpp_verifier_grouped_mixed_workspace_bytes(const bpp_verifier *v, const uint32_t *m_of, size_t count, uint32_t group);
+int bpp_verifier_run_grouped_mixed(bpp_verifier *v, const uint64_t *d_points, const uint64_t *d_scalars, const uint32_t *m_of,
+                                   size_t count, const uint64_t *d_challenges, const uint8_t *weight_key, uint64_t index_base,
+                                   const uint64_t *d_weights, uint32_t group, uint32_t *d_out_verdicts, uint64_t *stats,
+                                   void *d_workspace, size_t workspace_bytes, void *stream);
+/* ... behind the decoder: bpp_range_verify_batch_serialized_mixed_device's status vector (0 / 1 / 2 in caller order; both
+ * container versions, BPP_SER_TRANSCRIPT) through the grouped check above.  weight_key is required.  A container the decoder
+ * rejects keeps FormatError whatever its group did, changes no other proof's status, and counts its group as failed. */
+size_t bpp_verifier_serialized_grouped_mixed_workspace_bytes(const bpp_verifier *v, const uint32_t *m_of, size_t count,
+                                                             uint32_t group);
+int bpp_range_verify_batch_serialized_grouped_mixed_device(bpp_verifier *v, const void *d_proofs, const void *d_commitments,
+                                                           const uint32_t *m_of, size_t count, int flags,
+                                                           const uint8_t *weight_key, uint64_t index_base, uint32_t group,
+                                                           uint32_t *d_ok, uint64_t *stats, void *d_workspace,
+                                                           size_t workspace_bytes, void *stream);
+
 /* Frames a bare byte stream of concatenated containers (host memory; no device, no context): m_of[i] = the m of container
  * i, whose length its header implies (n, m, k, version).  BPP_OK with *out_count containers when the stream is consumed
  * exactly (an empty stream: 0).  Otherwise a negative code, *out_count = the containers before the offending one, and

@@ -14,7 +14,16 @@ usage: python tools/mixed_bench.py [--reps 20] [--warmup 3] [--window 16] [--out
                         bpp_range_verify_batch_serialized_device calls on the dedicated verifiers, the two ALTERNATED
                         repetition by repetition; also, timed by the wall clock, the host-side detour the one call
                         replaces (decode per class, re-pack wire records, derive_challenges_mixed + run_mixed).
-                        Write it with --out profiles/mixed_serialized_bench.json"""
+                        Write it with --out profiles/mixed_serialized_bench.json
+       [--grouped]      the GROUPED check over the same block (bpp_verifier_run_grouped_mixed; with --serialized
+                        bpp_range_verify_batch_serialized_grouped_mixed_device), subgroup check on.  Four legs, alternated
+                        repetition by repetition, the verdict / status vectors compared after each:
+                          A  the new call on the all-valid block
+                          B  the exact mixed call on the same buffers
+                          C  five grouped calls on the dedicated verifiers, the proofs pre-sorted by class
+                          A' the new call on the block with --tamper proofs flipped
+                        Write it with --out profiles/mixed_grouped_bench.json / mixed_grouped_serialized_bench.json;
+                        with --mixed-only: leg A alone (the run to put under rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
 import os
@@ -61,6 +70,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--mixed-only", action="store_true")
     ap.add_argument("--serialized", action="store_true")
+    ap.add_argument("--grouped", action="store_true")
+    ap.add_argument("--group", type=int, default=32)
     ap.add_argument("--detour-reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -102,12 +113,14 @@ def main():
     order = [(m, i) for m, cnt in MIX.items() for i in range(cnt)]
     perm = rng.permutation(len(order))
     order = [order[p] for p in perm]
-    for t in rng.choice(len(order), size=args.tamper, replace=False):
-        m, i = order[t]
-        scs[m][i, 1, 0] ^= 1
+    victims = [int(t) for t in rng.choice(len(order), size=args.tamper, replace=False)]
     count = len(order)
     ms = [m for m, _ in order]
-    PW = a.PW
+    if args.grouped:
+        return grouped(args, torch, B, a, cap, ded, recs, scs, order, ms, victims, build_s)
+    for t in victims:
+        m, i = order[t]
+        scs[m][i, 1, 0] ^= 1
     if args.serialized:
         return serialized(args, torch, B, a, cap, ded, recs, scs, order, ms, build_s)
     packed = np.ascontiguousarray(np.concatenate([recs[m][i] for m, i in order]))
@@ -268,6 +281,135 @@ def serialized(args, torch, B, a, cap, ded, recs, scs, order, ms, build_s):
             ok2[status != 0] = 2
             t_detour.append((time.perf_counter() - t0) * 1e3)
         res.update({"host_detour_wall": stats(t_detour), "host_detour_statuses_identical": bool(np.array_equal(ok2, ok_one))})
+    return finish(args, res)
+
+
+def grouped(args, torch, B, a, cap, ded, recs, scs, order, ms, victims, build_s):
+    """the --grouped legs (wire records, or with --serialized containers under the transcript)"""
+    dev = torch.device("cuda:0")
+    stream = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
+    count, group, ser = len(order), args.group, args.serialized
+    key = os.urandom(32)
+    # the condition the header states for the weighted checks: prime-order points.  Wire records: the subgroup check of the
+    # pass, on for every leg; containers: the decoder's own membership test provides it
+    for v in ([cap] if args.mixed_only else set(ded.values())):
+        v.set_subgroup_check(not ser)
+    gof = B.mixed_groups(ms, group)
+    want_bad = np.zeros(count, dtype=np.uint32)
+    want_bad[victims] = 1
+    hit = sorted(set(gof[victims].tolist()))
+    want_stats = (len(hit), int(sum(int((gof == h).sum()) for h in hit)))
+
+    def tampered(m):
+        sc = scs[m].copy()
+        for t in victims:
+            if order[t][0] == m:
+                sc[order[t][1], 1, 0] ^= 1
+        return sc
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    if ser:
+        blobs, blobs_bad, comms = {}, {}, {}
+        for m in MIX:
+            k = (N * m).bit_length() - 1
+            blobs[m] = B.encode_proofs(a, N, m, recs[m][:, :3 + 2 * k], scs[m])
+            blobs_bad[m] = B.encode_proofs(a, N, m, recs[m][:, :3 + 2 * k], tampered(m))
+            comms[m] = B.compress_points(a, recs[m][:, 3 + 2 * k:].reshape(-1, a.PW)).reshape(len(recs[m]), -1)
+        d_in = up(np.concatenate([blobs[m][i] for m, i in order]))
+        d_in_bad = up(np.concatenate([blobs_bad[m][i] for m, i in order]))
+        d_aux = up(np.concatenate([comms[m][i] for m, i in order]))
+        wsb = cap.serialized_grouped_mixed_workspace_bytes(ms, group)
+        wsb_exact = cap.serialized_mixed_workspace_bytes(ms)
+    else:
+        d_in = up(np.concatenate([recs[m][i] for m, i in order]).view(np.int64))
+        d_aux = up(np.stack([scs[m][i] for m, i in order]).view(np.int64))
+        bad = {m: tampered(m) for m in MIX}
+        d_aux_bad = up(np.stack([bad[m][i] for m, i in order]).view(np.int64))
+        wsb = cap.grouped_mixed_workspace_bytes(ms, group)
+        wsb_exact = cap.mixed_workspace_bytes(ms)
+    d_ws = torch.empty(max(wsb, wsb_exact), dtype=torch.uint8, device=dev)
+    d_ok = {leg: torch.full((count,), 7, dtype=torch.int32, device=dev) for leg in ("A", "B", "A_tampered")}
+    got_stats = {}
+
+    def leg_a(which="A"):
+        if ser:
+            got_stats[which] = cap.verify_serialized_grouped_mixed_device(
+                (d_in if which == "A" else d_in_bad).data_ptr(), d_aux.data_ptr(), ms, d_ok[which].data_ptr(), d_ws.data_ptr(), wsb,
+                key, 0, group, stream(), transcript=True)
+        else:
+            got_stats[which] = cap.run_grouped_mixed_device(
+                d_in.data_ptr(), (d_aux if which == "A" else d_aux_bad).data_ptr(), ms, key, 0, d_ok[which].data_ptr(),
+                d_ws.data_ptr(), wsb, group=group, stream=stream())
+
+    def leg_b():
+        if ser:
+            cap.verify_serialized_mixed_device(d_in.data_ptr(), d_aux.data_ptr(), ms, d_ok["B"].data_ptr(), d_ws.data_ptr(),
+                                               wsb_exact, stream(), transcript=True)
+        else:
+            cap.run_mixed_device(d_in.data_ptr(), d_aux.data_ptr(), ms, d_ok["B"].data_ptr(), d_ws.data_ptr(), wsb_exact, stream())
+
+    res = {"shape": {"curve": "bls12_381", "n": N, "capacity_m": CAP, "window": args.window, "count": count,
+                     "mix": {str(m): c for m, c in MIX.items()}, "tampered": args.tamper, "group": group,
+                     "groups": int(gof.max()) + 1, "serialized": ser, "transcript": ser, "subgroup_check": not ser},
+           "device": torch.cuda.get_device_name(0), "table_bytes_one": int(cap.table_bytes),
+           "grouped_mixed_workspace_bytes": int(wsb), "exact_mixed_workspace_bytes": int(wsb_exact), "build_s": build_s}
+    if args.mixed_only:
+        t_a = timed(torch, leg_a, args.reps, args.warmup)
+        res.update({"A_grouped_mixed_valid": stats(t_a), "A_stats": got_stats["A"],
+                    "A_all_valid": not bool(d_ok["A"].cpu().numpy().any())})
+        return finish(args, res)
+    # leg C: the block sorted by class on the host beforehand, one grouped call per dedicated verifier
+    pos = {m: [j for j, (mm, _) in enumerate(order) if mm == m] for m in MIX}
+    bufs = {}
+    for m in MIX:
+        idx = [order[j][1] for j in pos[m]]
+        cnt = len(idx)
+        if ser:
+            w = ded[m].serialized_grouped_workspace_bytes(cnt, group)
+            first, second = up(blobs[m][idx]), up(comms[m][idx])
+        else:
+            w = ded[m].grouped_workspace_bytes(cnt, group)
+            first, second = up(recs[m][idx].view(np.int64)), up(scs[m][idx].view(np.int64))
+        bufs[m] = (first, second, torch.full((cnt,), 7, dtype=torch.int32, device=dev),
+                   torch.empty(w, dtype=torch.uint8, device=dev), w, cnt)
+
+    def leg_c():
+        for m in MIX:
+            p, s, o, w, wb, cnt = bufs[m]
+            if ser:
+                ded[m].verify_serialized_grouped_device(p.data_ptr(), s.data_ptr(), cnt, o.data_ptr(), w.data_ptr(), wb, key, 0,
+                                                        group, stream(), transcript=True)
+            else:
+                ded[m].run_grouped_device(p.data_ptr(), s.data_ptr(), cnt, key, 0, o.data_ptr(), w.data_ptr(), wb, group=group,
+                                          stream=stream())
+
+    legs = (("A", leg_a), ("B", leg_b), ("C", leg_c), ("A_tampered", lambda: leg_a("A_tampered")))
+    for _ in range(args.warmup):
+        for _, fn in legs:
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in legs}
+    same = {name: True for name, _ in legs}
+    for _ in range(args.reps):      # alternated on one box: one repetition of each leg, in turn, its vector checked after it
+        for name, fn in legs:
+            times[name] += timed(torch, fn, 1, 0)
+            if name == "C":
+                vec = np.zeros(count, dtype=np.uint32)
+                for m in MIX:
+                    vec[pos[m]] = bufs[m][2].cpu().numpy().astype(np.uint32)
+            else:
+                vec = d_ok[name].cpu().numpy().astype(np.uint32)
+            same[name] &= bool(np.array_equal(vec, want_bad if name == "A_tampered" else np.zeros(count, dtype=np.uint32)))
+            if name in got_stats:
+                same[name] &= tuple(got_stats[name]) == (want_stats if name == "A_tampered" else (0, 0))
+    med = {name: statistics.median(t) for name, t in times.items()}
+    res.update({"A_grouped_mixed_valid": stats(times["A"]), "B_exact_mixed_valid": stats(times["B"]),
+                "C_five_grouped_dedicated_valid": stats(times["C"]), "A_grouped_mixed_tampered": stats(times["A_tampered"]),
+                "vectors_and_stats_as_expected": same, "A_tampered_stats": list(got_stats["A_tampered"]),
+                "A_tampered_stats_predicted": list(want_stats),
+                "ratio_A_over_B": med["A"] / med["B"], "ratio_A_over_C": med["A"] / med["C"],
+                "ranges_A_B_disjoint": max(times["A"]) < min(times["B"]),
+                "A_verifies_per_s": count / (med["A"] / 1e3), "A_tampered_verifies_per_s": count / (med["A_tampered"] / 1e3),
+                "table_bytes_dedicated_sum": int(sum(ded[m].table_bytes for m in MIX))})
     return finish(args, res)
 
 
