@@ -48,6 +48,9 @@ EXPORTS = [
     "bpp_range_verify_batch_serialized_mixed", "bpp_proofs_scan",
     "bpp_verifier_grouped_mixed_workspace_bytes", "bpp_verifier_run_grouped_mixed",
     "bpp_verifier_serialized_grouped_mixed_workspace_bytes", "bpp_range_verify_batch_serialized_grouped_mixed_device",
+    "bpp_prover_mixed_workspace_bytes", "bpp_range_prove_batch_mixed_device",
+    "bpp_prover_serialized_mixed_workspace_bytes", "bpp_range_prove_batch_serialized_mixed_device",
+    "bpp_range_prove_batch_mixed", "bpp_range_prove_batch_serialized_mixed",
 ]
 
 
@@ -170,6 +173,15 @@ def lib():
         L.bpp_verifier_serialized_grouped_mixed_workspace_bytes.restype = sz
         L.bpp_range_verify_batch_serialized_grouped_mixed_device.argtypes = [vp, vp, vp, vp, sz, i32, ctypes.c_char_p, u64,
                                                                              ctypes.c_uint32, vp, vp, vp, sz, vp]
+        L.bpp_prover_mixed_workspace_bytes.argtypes = [vp, vp, sz]
+        L.bpp_prover_mixed_workspace_bytes.restype = sz
+        L.bpp_range_prove_batch_mixed_device.argtypes = [vp, vp, vp, vp, sz, i32, ctypes.c_char_p, u64, vp, vp, vp, vp, vp, sz, vp]
+        L.bpp_prover_serialized_mixed_workspace_bytes.argtypes = [vp, vp, sz]
+        L.bpp_prover_serialized_mixed_workspace_bytes.restype = sz
+        L.bpp_range_prove_batch_serialized_mixed_device.argtypes = [vp, vp, vp, vp, sz, i32, ctypes.c_char_p, u64, vp, vp, vp,
+                                                                    vp, sz, vp]
+        L.bpp_range_prove_batch_mixed.argtypes = [vp, vp, vp, vp, sz, i32, ctypes.c_char_p, u64, vp, vp, vp]
+        L.bpp_range_prove_batch_serialized_mixed.argtypes = [vp, vp, vp, vp, sz, i32, ctypes.c_char_p, u64, vp, vp]
         L.bpp_proofs_scan.argtypes = [i32, sz, i32, vp, sz, vp, sz, vp]
         L.bpp_debug_field_op.argtypes = [vp, i32, i32, vp, vp, sz, vp]
         L.bpp_debug_point_op.argtypes = [vp, i32, vp, vp, sz, vp]

@@ -909,6 +909,100 @@ class BatchVerifier:
               "bpp_range_prove_batch_device")
 
 
+    # ---- proving blocks of mixed aggregation sizes: proof i has ms[i] values (include/bpp_amd.h) ----
+    def prover_mixed_workspace_bytes(self, ms, serialized: bool = False) -> int:
+        """bytes of device workspace prove_mixed_device (serialized: prove_serialized_mixed_device) needs (0: an m_i is
+        not taken)"""
+        m = self._ms(ms)
+        f = _lib.lib().bpp_prover_serialized_mixed_workspace_bytes if serialized else _lib.lib().bpp_prover_mixed_workspace_bytes
+        return f(self.handle, _ptr(m) if len(m) else None, len(m))
+
+    def prove_mixed_device(self, d_values: int, d_gammas: int, ms, d_out_points: int, d_out_scalars: int, d_workspace: int,
+                           workspace_bytes: int, stream: int = 0, transcript: bool = False, d_out_challenges: int = 0,
+                           blind_key: bytes = None, index_base: int = 0, d_blinding: int = 0):
+        """RangeProof::prove for a resident block in which proof i has ms[i] values (packed in caller order, as the gammas),
+        each against the prefix key PublicKey::new(n ms[i]).  d_out_points receives the packed records [A, wip.A, wip.B,
+        L.., R.., V..] run_mixed_device reads, d_out_scalars (count, 3) scalars, d_out_challenges the packed challenge
+        blocks.  Proof i's blinding index is index_base + i.  Blocks while it uploads the per-proof index."""
+        m = self._ms(ms)
+        check(_lib.lib().bpp_range_prove_batch_mixed_device(
+            self.handle, d_values, d_gammas, _ptr(m) if len(m) else None, len(m), 1 if transcript else 0, blind_key,
+            ctypes.c_uint64(index_base), d_blinding or None, d_out_points, d_out_scalars, d_out_challenges or None, d_workspace,
+            workspace_bytes, stream or None), "bpp_range_prove_batch_mixed_device")
+
+    def prove_serialized_mixed_device(self, d_values: int, d_gammas: int, ms, d_out_proofs: int, d_out_commitments: int,
+                                      d_workspace: int, workspace_bytes: int, stream: int = 0, transcript: bool = False,
+                                      uncompressed: bool = False, blind_key: bytes = None, index_base: int = 0,
+                                      d_blinding: int = 0):
+        """prove_mixed_device with the proofs written as containers packed back to back in caller order and ms[i] encoded
+        commitments per proof: the two inputs of verify_serialized_mixed_device"""
+        m = self._ms(ms)
+        check(_lib.lib().bpp_range_prove_batch_serialized_mixed_device(
+            self.handle, d_values, d_gammas, _ptr(m) if len(m) else None, len(m),
+            (1 if transcript else 0) | (2 if uncompressed else 0), blind_key, ctypes.c_uint64(index_base), d_blinding or None,
+            d_out_proofs, d_out_commitments, d_workspace, workspace_bytes, stream or None),
+            "bpp_range_prove_batch_serialized_mixed_device")
+
+    def _mixed_inputs(self, values, gammas):
+        """values, gammas: one sequence per proof -> (packed values, packed gammas (sum m_i, 4), ms)"""
+        ms = np.array([len(v) for v in values], dtype=np.uint32)
+        if len(gammas) != len(values) or any(len(g) != len(v) for g, v in zip(gammas, values)):
+            raise RuntimeError("one gamma per value")
+        vals = np.array([int(x) for v in values for x in v], dtype=np.uint64)
+        gm = np.zeros((len(vals), 4), dtype=np.uint64)
+        j = 0
+        for row in gammas:
+            for g in row:
+                gm[j] = np.asarray(g, dtype=np.uint64) if isinstance(g, np.ndarray) else scalar_to_wire(g)
+                j += 1
+        return vals, gm, ms
+
+    def prove_batch_mixed(self, values, gammas, transcript: bool = False, blind_key: bytes = None, index_base: int = 0,
+                          challenges: bool = False):
+        """values[i], gammas[i]: the m_i values and gammas of proof i (m_i a power of two <= m).  -> (records, scalars):
+        records[i] the (mixed_points(m_i), PW) wire record [A, wip.A, wip.B, L.., R.., V..] of proof i, bit for bit what
+        a dedicated (n, m_i) engine of the same key proves; scalars (count, 3, 4).  challenges=True: also the list of
+        per-proof challenge blocks (3 + k_i, 4)."""
+        if blind_key is not None and (not transcript or len(blind_key) != 32):
+            raise ValueError("blind_key: 32 bytes, transcript mode only")
+        vals, gm, ms = self._mixed_inputs(values, gammas)
+        count, PW = len(ms), self.arith.PW
+        taken = all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in ms)
+        npts = [self.mixed_points(int(x)) if taken else 0 for x in ms]
+        nch = [3 + (self.n * int(x)).bit_length() - 1 if taken else 0 for x in ms]
+        pts = np.zeros((max(sum(npts), 1), PW), dtype=np.uint64)
+        sc = np.zeros((count, 3, 4), dtype=np.uint64)
+        ch = np.zeros((max(sum(nch), 1), 4), dtype=np.uint64)
+        check(_lib.lib().bpp_range_prove_batch_mixed(
+            self.handle, _ptr(vals) if len(vals) else None, _ptr(gm) if len(vals) else None, _ptr(ms) if count else None, count,
+            1 if transcript else 0, blind_key, ctypes.c_uint64(index_base), _ptr(pts), _ptr(sc) if count else None,
+            _ptr(ch) if challenges else None), "bpp_range_prove_batch_mixed")
+        po, co = np.concatenate([[0], np.cumsum(npts)]).astype(int), np.concatenate([[0], np.cumsum(nch)]).astype(int)
+        recs = [pts[po[i]:po[i + 1]] for i in range(count)]
+        if challenges:
+            return recs, sc, [ch[co[i]:co[i + 1]] for i in range(count)]
+        return recs, sc
+
+    def prove_serialized_mixed(self, values, gammas, transcript: bool = False, blind_key: bytes = None, index_base: int = 0,
+                               uncompressed: bool = False):
+        """prove_batch_mixed as bytes -> (proofs, commitments, ms): the containers back to back in caller order, ms[i]
+        encoded commitments per proof back to back -- what verify_serialized_mixed takes, and a stream proofs_scan frames"""
+        if blind_key is not None and (not transcript or len(blind_key) != 32):
+            raise ValueError("blind_key: 32 bytes, transcript mode only")
+        vals, gm, ms = self._mixed_inputs(values, gammas)
+        count, version = len(ms), 2 if uncompressed else 1
+        taken = all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in ms)
+        pb = uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)
+        nbytes = sum(proof_bytes(self.arith, self.n, int(x), version) for x in ms) if taken and pb else 0
+        raw = np.zeros(max(nbytes, 1), dtype=np.uint8)
+        cm = np.zeros(max(int(ms.sum()) * pb, 1), dtype=np.uint8)
+        check(_lib.lib().bpp_range_prove_batch_serialized_mixed(
+            self.handle, _ptr(vals) if len(vals) else None, _ptr(gm) if len(vals) else None, _ptr(ms) if count else None, count,
+            (1 if transcript else 0) | (2 if uncompressed else 0), blind_key, ctypes.c_uint64(index_base), _ptr(raw), _ptr(cm)),
+            "bpp_range_prove_batch_serialized_mixed")
+        return raw[:nbytes].tobytes(), cm[:int(ms.sum()) * pb].tobytes(), ms
+
+
 class PassGraph:
     """One pass of the batch verifier captured into a HIP graph (bpp_verifier_graph_capture): launch() replays it over the
     buffers it was captured with.  Keep the verifier alive while its graphs are."""

@@ -87,16 +87,12 @@ BPP_HD bool words_gt_half(const uint32_t* w) {
     return false;
 }
 
-// one thread per point: wire (canonical x | y | inf) -> compressed bytes
+// wire point at w (canonical x | y | inf) -> its compressed bytes at o: the one encoder (k_points_compress,
+// k_container_encode_mixed in mixed.hpp).  Byte stores: o carries no alignment (a secp256k1 point is 33 bytes).
 template <class C>
-__global__ void __launch_bounds__(128) k_points_compress(const uint32_t* __restrict__ wire, uint8_t* __restrict__ out, size_t n) {
+__device__ __forceinline__ void point_compress(const uint32_t* __restrict__ w, uint8_t* __restrict__ o) {
     using P = typename C::Fp;
     constexpr int N = P::N;
-    constexpr int CB = compressed_bytes<C>();
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t* w = wire + i * (2 * N + 2);
-    uint8_t* o = out + i * CB;
     const bool inf = (w[2 * N] | w[2 * N + 1]) != 0;
     if constexpr (C::ID == 2) {
         Aff<C> a = aff_inf<C>();
@@ -126,6 +122,34 @@ __global__ void __launch_bounds__(128) k_points_compress(const uint32_t* __restr
             }
         }
     }
+}
+
+// wire point at w -> its uncompressed bytes at o (container version 2; the device form of the byte order
+// bpp_points_uncompressed writes on the host): BLS12-381 G1 x | y big-endian, infinity 0x40 00 .. 00; secp256k1
+// 0x04 | x | y, infinity 65 zero bytes.  Not offered for ristretto255 (nothing is written).
+template <class C>
+__device__ __forceinline__ void point_uncompressed_write(const uint32_t* __restrict__ w, uint8_t* __restrict__ o) {
+    constexpr int N = C::Fp::N;
+    if constexpr (C::ID != 2) {
+        constexpr int FB = N * 4;                       // bytes per coordinate
+        constexpr int OFF = C::ID == 0 ? 0 : 1;         // SEC1 prefix byte
+        const bool inf = (w[2 * N] | w[2 * N + 1]) != 0;
+        if (OFF) o[0] = inf ? 0 : 0x04;
+        for (int b = 0; b < FB; b++) {
+            const int k = FB - 1 - b;
+            o[OFF + b] = inf ? 0 : (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+            o[OFF + FB + b] = inf ? 0 : (uint8_t)(w[N + (k >> 2)] >> (8 * (k & 3)));
+        }
+        if (C::ID == 0 && inf) o[0] = 0x40;
+    }
+}
+
+// one thread per point: wire (canonical x | y | inf) -> compressed bytes
+template <class C>
+__global__ void __launch_bounds__(128) k_points_compress(const uint32_t* __restrict__ wire, uint8_t* __restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    point_compress<C>(wire + i * (2 * C::Fp::N + 2), out + i * compressed_bytes<C>());
 }
 
 // compressed bytes -> wire point at w (2N + 2 words).  false: malformed (bad flags, x >= p, x not on the curve, not a

@@ -6,11 +6,15 @@
 // region with the class's view, and scatters the verdicts back into caller order.
 // Serialized form (bpp_range_verify_batch_serialized_mixed_device): the container decoder is the producer of the
 // records, so it writes them straight into the class regions (k_container_decode_mixed) and nothing is gathered.
+// Producing side (bpp_range_prove_batch_mixed_device, bpp_range_prove_batch_serialized_mixed_device): the same classes, each
+// proved with its view; the prover writes every record once, through the per-proof index (prove_plan), into the caller-order
+// packed block -- or into the class regions, from which k_container_encode_mixed writes the containers.
 #pragma once
 #include <vector>
 
 #include "codec.hpp"
 #include "host_util.hpp"
+#include "prover_batch.hpp"
 
 namespace bpp {
 
@@ -139,6 +143,43 @@ __global__ void __launch_bounds__(64, 2) k_container_decode_mixed(SerClasses g, 
         atomicOr(status + L.pos, 1u);
 }
 
+// The decoder's mirror (bpp_range_prove_batch_serialized_mixed_device): one lane per record point of all classes in gathered
+// order encodes its point out of the class regions -- lane t < 3 + 2k into container SX_PROOF at CONTAINER_HDR + t CB, the
+// others as commitment t - (3 + 2k) at SX_COMM -- and the lane of a proof's first point writes the 12-byte header and the
+// three scalars (scalars: by CALLER position, as k_pb_final leaves them for a mixed block).  Byte stores throughout: a
+// container starts wherever the ones before it end (a secp256k1 point is 33 bytes), and a lane's bytes are its own.
+template <class C>
+__global__ void __launch_bounds__(64, 2) k_container_encode_mixed(SerClasses g, const uint32_t* __restrict__ idx,
+                                                                  const uint32_t* __restrict__ records,
+                                                                  const uint32_t* __restrict__ scalars,
+                                                                  uint8_t* __restrict__ proofs, uint8_t* __restrict__ commitments,
+                                                                  uint32_t version) {
+    constexpr int N = C::Fp::N;
+    const SerLane L = ser_lane(g, blockIdx.x * SER_WAVE, threadIdx.x);
+    if (!L.live) return;
+    const int CB = container_point_bytes<C>(version);
+    const uint32_t* e = idx + (size_t)L.pos * SX_WORDS;
+    const uint32_t npp = 3 + 2 * L.k;
+    uint8_t* rec = proofs + e[SX_PROOF];
+    uint8_t* dst = L.t < npp ? rec + CONTAINER_HDR + (size_t)L.t * CB : commitments + e[SX_COMM] + (size_t)(L.t - npp) * CB;
+    const uint32_t* w = records + (size_t)L.point * (2 * N + 2);
+    if (version == 2) point_uncompressed_write<C>(w, dst);
+    else point_compress<C>(w, dst);
+    if (L.t == 0) {
+        const uint8_t hdr[CONTAINER_HDR] = {'B', 'P', 'P', '+', (uint8_t)version, (uint8_t)C::ID, (uint8_t)g.n, (uint8_t)L.m, (uint8_t)L.k, 0, 0, 0};
+        for (uint32_t b = 0; b < CONTAINER_HDR; b++) rec[b] = hdr[b];
+        uint8_t* sc = rec + CONTAINER_HDR + (size_t)npp * CB;
+        const uint32_t* sw = scalars + (size_t)e[SX_CALLER] * 24;
+        for (int q = 0; q < 24; q++) {
+            const uint32_t v = sw[q];
+            sc[4 * q] = (uint8_t)v;
+            sc[4 * q + 1] = (uint8_t)(v >> 8);
+            sc[4 * q + 2] = (uint8_t)(v >> 16);
+            sc[4 * q + 3] = (uint8_t)(v >> 24);
+        }
+    }
+}
+
 // k_records_subgroup over the class regions (same lanes as k_container_decode_mixed): one launch for all classes
 template <class C>
 __global__ void __launch_bounds__(64, 2) k_records_subgroup_mixed(SerClasses g, uint32_t* __restrict__ records,
@@ -172,6 +213,8 @@ struct MixedPlan {
     size_t proof_bytes = 0, comm_bytes = 0, lanes = 0;
     std::vector<uint32_t> sidx;
     SerClasses classes = {};
+    // producing side (prove_plan): the prover's per-proof entries by gathered position (PX_*, prover_batch.hpp)
+    std::vector<uint32_t> px;
 };
 
 // cap: the verifier's shape.  BPP_E_ARG (with the index of the first offending proof) for an m_i that is zero, not a power
@@ -273,6 +316,39 @@ inline int mixed_plan_serialized(const VerifyShape& cap, const uint32_t* m_of, s
         e[SX_CALLER] = (uint32_t)i;
         src_pr += cbytes(c);
         src_cm += ((size_t)1 << c) * pb;
+    }
+    return BPP_OK;
+}
+
+// The plan of a block to PROVE: mixed_plan / mixed_plan_serialized (pb != 0: the containers' point size) and the prover's
+// index px by gathered position.  PX_REC: wire form -- the proof's record in the caller-order packed block (what
+// bpp_verifier_run_mixed reads as d_points); serialized form -- its record in the class regions.
+inline int prove_plan(const VerifyShape& cap, const uint32_t* m_of, size_t count, size_t pb, bool want_idx, MixedPlan& p) {
+    int rc = pb ? mixed_plan_serialized(cap, m_of, count, pb, want_idx, p) : mixed_plan(cap, m_of, count, false, p);
+    if (rc || !want_idx) return rc;
+    uint32_t logm = 0;
+    while ((1u << logm) < cap.m) logm++;
+    const uint32_t logn = cap.k - logm;
+    p.px.assign(count * PX_WORDS, 0u);
+    size_t next[MIXED_CLASSES];
+    for (uint32_t c = 0; c < MIXED_CLASSES; c++) next[c] = p.first[c];
+    size_t src_pt = 0, src_val = 0, src_bl = 0, src_ch = 0;
+    for (size_t i = 0; i < count; i++) {
+        uint32_t c = 0;
+        while ((1u << c) < m_of[i]) c++;
+        const uint32_t k = logn + c;
+        const size_t nv = 3 + 2 * (size_t)k + ((size_t)1 << c);
+        const size_t pos = next[c]++;
+        uint32_t* e = p.px.data() + pos * PX_WORDS;
+        e[PX_REC] = (uint32_t)(pb ? p.pt[c] + (pos - p.first[c]) * nv : src_pt);
+        e[PX_CALLER] = (uint32_t)i;
+        e[PX_VAL] = (uint32_t)src_val;
+        e[PX_BLIND] = (uint32_t)src_bl;
+        e[PX_CH] = (uint32_t)src_ch;
+        src_pt += nv;
+        src_val += (size_t)1 << c;
+        src_bl += pb_blind_elems(k);
+        src_ch += 3 + k;
     }
     return BPP_OK;
 }

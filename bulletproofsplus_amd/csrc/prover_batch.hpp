@@ -31,6 +31,24 @@ struct ProverConsts {
     uint32_t r, s, delta, eta; // wip.rs:175-178
 };
 
+// A block of MIXED aggregation sizes (bpp_range_prove_batch_mixed_device; mixed.hpp prove_plan): the proofs of one class
+// (n, m_i) are proved together, in gathered order, and every kernel below that touches caller-owned memory takes `px`,
+// one entry of PX_WORDS 32-bit words per proof of the launch: where the proof's record goes (a wire-point index into
+// out_points; the record is then the packed [A, wip.A, wip.B, L.., R.., V_0..V_{m-1}]), its position in the caller's
+// numbering (blinding index, scalar triple), and where its values, blinding scalars and challenge block sit in the
+// caller's packed buffers.  px == nullptr: the single-shape layouts (proof p at fixed strides), as before.
+enum { PX_REC = 0, PX_CALLER, PX_VAL, PX_BLIND, PX_CH, PX_WORDS = 8 };
+// the record [A, wip.A, wip.B, L.., R..] of proof p and its commitments
+template <int WW, class T>
+__device__ __forceinline__ T* pb_record(T* out_points, const uint32_t* __restrict__ px, size_t p, uint32_t k) {
+    return out_points + (px ? (size_t)px[p * PX_WORDS + PX_REC] : p * (3 + 2 * k)) * WW;
+}
+template <int WW, class T>
+__device__ __forceinline__ T* pb_commitments(T* out_points, T* out_V, const uint32_t* __restrict__ px, size_t p, uint32_t k,
+                                             uint32_t m) {
+    return px ? out_points + ((size_t)px[p * PX_WORDS + PX_REC] + 3 + 2 * k) * WW : out_V + p * m * WW;
+}
+
 // The reference's blinding values are literals, so its proofs hide nothing (with alpha, r, s, delta, eta, d_L, d_R known,
 // r', s', delta' give away the folded a, b and a linear combination of the gammas).  A caller that wants hiding proofs
 // supplies them per proof -- `blind`: [count][5 + 2k] canonical scalars [alpha, r, s, delta, eta, d_L[0..k), d_R[0..k)] --
@@ -47,17 +65,19 @@ __device__ __forceinline__ Fe<P> pb_blind(uint32_t literal, const uint32_t* __re
 }
 // blind[p][slot] = (c0 + 2^256 c1) mod r,  c_h = SHA-256(key[32] || "bppb" || (index_base + p) as u64 LE || slot as u32 LE
 // || h as u32 LE) read as little-endian 256-bit integers; zero is replaced by one.  One lane per (proof, slot).
+// px != null (a mixed block): p is the proof's position in the CALLER's numbering, whatever its gathered position.
 struct BlindKey {
     uint32_t w[8];   // the 32 key bytes as little-endian words
 };
 template <class C>
 __global__ void __launch_bounds__(64) k_pb_blind(BlindKey key, uint64_t index_base, uint32_t k,
-                                                 uint32_t* __restrict__ blind, size_t count) {
+                                                 uint32_t* __restrict__ blind, size_t count,
+                                                 const uint32_t* __restrict__ px) {
     using P = typename C::Fr;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t ne = pb_blind_elems(k);
     if (i >= count * ne) return;
-    const uint64_t idx = index_base + i / ne;
+    const uint64_t idx = index_base + (px ? (size_t)px[i / ne * PX_WORDS + PX_CALLER] : i / ne);
     const uint32_t slot = (uint32_t)(i % ne);
     uint32_t c[16];
     for (uint32_t h = 0; h < 2; h++) {
@@ -379,7 +399,8 @@ __global__ void __launch_bounds__(256) k_pb_final(VerifyShape s, ProverConsts pc
                                                   const uint32_t* __restrict__ st_cG,
                                                   const uint32_t* __restrict__ st_cH,
                                                   const uint32_t* __restrict__ st_consts,
-                                                  uint32_t* __restrict__ vps, uint32_t* __restrict__ out_scalars) {
+                                                  uint32_t* __restrict__ vps, uint32_t* __restrict__ out_scalars,
+                                                  const uint32_t* __restrict__ px) {
     using P = typename C::Fr;
     using F = Fe<P>;
     const uint32_t tid = threadIdx.x;
@@ -409,7 +430,7 @@ __global__ void __launch_bounds__(256) k_pb_final(VerifyShape s, ProverConsts pc
         }
         if (phase == PB_PRE) return;
         const F ef = pb_ld<P>(consts + 4 * 8);
-        uint32_t* o = out_scalars + p * 24;
+        uint32_t* o = out_scalars + (px ? (size_t)px[p * PX_WORDS + PX_CALLER] : p) * 24;   // a mixed block: caller order
         pb_st_canon<P>(o, fe_add(r, fe_mul(a0, ef)));
         pb_st_canon<P>(o + 8, fe_add(sc, fe_mul(b0, ef)));
         pb_st_canon<P>(o + 16, fe_add(fe_add(eta, fe_mul(delta, ef)), fe_mul(fe_mul(alpha, ef), ef)));
@@ -418,11 +439,12 @@ __global__ void __launch_bounds__(256) k_pb_final(VerifyShape s, ProverConsts pc
 
 // One lane per virtual proof of the launch (sel.cnt per real proof, starting at virtual proof sel.first): sums its
 // `per` jacobian partials, converts to affine, writes the wire point at its place in the proof record:
-// out_points[p][3+2k] = [A, wip.A, wip.B, L.., R..] and out_V[p][m].
+// out_points[p][3+2k] = [A, wip.A, wip.B, L.., R..] and out_V[p][m] -- or, px != null, the packed record at PX_REC.
 template <class C>
 __global__ void __launch_bounds__(64) k_pb_collect(VerifyShape s, VpSel sel, const uint32_t* __restrict__ partials,
                                                    uint32_t per, uint32_t* __restrict__ out_points,
-                                                   uint32_t* __restrict__ out_V, size_t nvp_total) {
+                                                   uint32_t* __restrict__ out_V, size_t nvp_total,
+                                                   const uint32_t* __restrict__ px) {
     constexpr int N = C::Fp::N;
     constexpr int JW = jac_words<C>();
     constexpr int WW = 2 * N + 2;
@@ -436,15 +458,16 @@ __global__ void __launch_bounds__(64) k_pb_collect(VerifyShape s, VpSel sel, con
     aff_to_wire(jac_to_aff(acc), w);
     uint32_t* dst;
     const uint32_t k = s.k;
-    if (v == 0) dst = out_points + (p * (3 + 2 * k) + 0) * WW;
-    else if (v == 2 * k + 1) dst = out_points + (p * (3 + 2 * k) + 1) * WW;
-    else if (v == 2 * k + 2) dst = out_points + (p * (3 + 2 * k) + 2) * WW;
+    uint32_t* rec = pb_record<WW>(out_points, px, p, k);
+    if (v == 0) dst = rec;
+    else if (v == 2 * k + 1) dst = rec + 1 * WW;
+    else if (v == 2 * k + 2) dst = rec + 2 * WW;
     else if (v <= 2 * k) {
         const uint32_t t = (v - 1) >> 1;
         const bool isR = ((v - 1) & 1u) != 0;
-        dst = out_points + (p * (3 + 2 * k) + 3 + (isR ? k : 0) + t) * WW;
+        dst = rec + (size_t)(3 + (isR ? k : 0) + t) * WW;
     } else {
-        dst = out_V + (p * s.m + (v - (2 * k + 3))) * WW;
+        dst = pb_commitments<WW>(out_points, out_V, px, p, k, s.m) + (size_t)(v - (2 * k + 3)) * WW;
     }
 #pragma unroll
     for (int t = 0; t < WW; t++) dst[t] = w[t];
@@ -458,15 +481,16 @@ __global__ void __launch_bounds__(64) k_pb_collect(VerifyShape s, VpSel sel, con
 template <class C>
 __global__ void __launch_bounds__(64) k_pb_fs_yz(VerifyShape s, TranscriptState st0, const uint32_t* __restrict__ out_points,
                                                  const uint32_t* __restrict__ out_V, uint32_t* __restrict__ tr_st,
-                                                 uint32_t* __restrict__ ch, size_t count) {
+                                                 uint32_t* __restrict__ ch, size_t count, const uint32_t* __restrict__ px) {
     using P = typename C::Fr;
     constexpr uint32_t WW = 2 * C::Fp::N + 2;
     const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= count) return;
     Transcript t;
     for (int i = 0; i < 8; i++) t.st[i] = st0.st[i];
-    for (uint32_t j = 0; j < s.m; j++) tr_append_point<C>(t, tr_tag('V'), out_V + (p * s.m + j) * WW);
-    tr_append_point<C>(t, tr_tag('A'), out_points + p * (size_t)(3 + 2 * s.k) * WW);
+    const uint32_t* V = pb_commitments<WW>(out_points, out_V, px, p, s.k, s.m);
+    for (uint32_t j = 0; j < s.m; j++) tr_append_point<C>(t, tr_tag('V'), V + (size_t)j * WW);
+    tr_append_point<C>(t, tr_tag('A'), pb_record<WW>(out_points, px, p, s.k));
     uint32_t w[8];
     uint32_t* c = ch + p * (size_t)(3 + s.k) * 8;
     fe_to_canonical(tr_challenge<P>(t, tr_tag('y')), w);
@@ -483,7 +507,8 @@ __global__ void __launch_bounds__(64) k_pb_fs_yz(VerifyShape s, TranscriptState 
 template <class C>
 __global__ void __launch_bounds__(64) k_pb_fs_round(VerifyShape s, uint32_t t, const uint32_t* __restrict__ out_points,
                                                     uint32_t* __restrict__ tr_st, uint32_t* __restrict__ ch,
-                                                    uint32_t* __restrict__ st_consts, size_t count) {
+                                                    uint32_t* __restrict__ st_consts, size_t count,
+                                                    const uint32_t* __restrict__ px) {
     using P = typename C::Fr;
     constexpr uint32_t WW = 2 * C::Fp::N + 2;
     const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -491,7 +516,7 @@ __global__ void __launch_bounds__(64) k_pb_fs_round(VerifyShape s, uint32_t t, c
     const uint32_t k = s.k;
     Transcript tr;
     for (int i = 0; i < 8; i++) tr.st[i] = tr_st[p * 8 + i];
-    const uint32_t* rec = out_points + p * (size_t)(3 + 2 * k) * WW;
+    const uint32_t* rec = pb_record<WW>(out_points, px, p, k);
     tr_append_point<C>(tr, tr_tag('L'), rec + (size_t)(3 + t) * WW);
     tr_append_point<C>(tr, tr_tag('R'), rec + (size_t)(3 + k + t) * WW);
     const Fe<P> e = tr_challenge<P>(tr, tr_tag('e'));
@@ -508,7 +533,8 @@ __global__ void __launch_bounds__(64) k_pb_fs_round(VerifyShape s, uint32_t t, c
 template <class C>
 __global__ void __launch_bounds__(64) k_pb_fs_final(VerifyShape s, const uint32_t* __restrict__ out_points,
                                                     uint32_t* __restrict__ tr_st, uint32_t* __restrict__ ch,
-                                                    uint32_t* __restrict__ st_consts, size_t count) {
+                                                    uint32_t* __restrict__ st_consts, size_t count,
+                                                    const uint32_t* __restrict__ px) {
     using P = typename C::Fr;
     constexpr uint32_t WW = 2 * C::Fp::N + 2;
     const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -516,7 +542,7 @@ __global__ void __launch_bounds__(64) k_pb_fs_final(VerifyShape s, const uint32_
     const uint32_t k = s.k;
     Transcript tr;
     for (int i = 0; i < 8; i++) tr.st[i] = tr_st[p * 8 + i];
-    const uint32_t* rec = out_points + p * (size_t)(3 + 2 * k) * WW;
+    const uint32_t* rec = pb_record<WW>(out_points, px, p, k);
     tr_append_point<C>(tr, tr_tag('w', 'A'), rec + (size_t)1 * WW);
     tr_append_point<C>(tr, tr_tag('w', 'B'), rec + (size_t)2 * WW);
     const Fe<P> e = tr_challenge<P>(tr, tr_tag('e'));
@@ -524,6 +550,39 @@ __global__ void __launch_bounds__(64) k_pb_fs_final(VerifyShape s, const uint32_
     fe_to_canonical(e, w);
     for (int i = 0; i < 8; i++) ch[(p * (3 + k) + 2) * 8 + i] = w[i];
     pb_st<P>(st_consts + p * (size_t)pb_consts_elems(k) * 8 + 4 * 8, e);
+}
+
+// ---- a mixed block: the inputs of one class's chunk out of the caller's packed buffers ---------------------------------
+// One wave per proof (px entry p): its m values and m gammas (40 m bytes) and, blinding != null, its 5 + 2k blinding scalars,
+// copied as 64-bit words to the fixed strides the kernels above read.
+template <class C>
+__global__ void __launch_bounds__(64) k_pb_gather_mixed(const uint32_t* __restrict__ px, uint32_t m, uint32_t k,
+                                                        const uint64_t* __restrict__ values, const uint64_t* __restrict__ gammas,
+                                                        const uint64_t* __restrict__ blinding, uint64_t* __restrict__ out_values,
+                                                        uint64_t* __restrict__ out_gammas, uint64_t* __restrict__ out_blind) {
+    const size_t p = blockIdx.x;
+    const uint32_t* e = px + p * PX_WORDS;
+    const uint32_t lane = threadIdx.x;
+    const size_t v0 = e[PX_VAL];
+    for (uint32_t w = lane; w < m; w += 64) out_values[p * m + w] = values[v0 + w];
+    for (uint32_t w = lane; w < 4 * m; w += 64) out_gammas[p * 4 * m + w] = gammas[v0 * 4 + w];
+    if (blinding) {
+        const uint32_t nb = pb_blind_elems(k) * 4;
+        const size_t b0 = (size_t)e[PX_BLIND] * 4;
+        for (uint32_t w = lane; w < nb; w += 64) out_blind[p * nb + w] = blinding[b0 + w];
+    }
+}
+
+// One wave per proof: its 3 + k challenges from the chunk's block (64-bit words `stride` apart; 0: one block shared by
+// all, the literal challenges) to the caller's packed buffer (PX_CH)
+template <class C>
+__global__ void __launch_bounds__(64) k_pb_challenges_out(const uint32_t* __restrict__ px, uint32_t k,
+                                                          const uint64_t* __restrict__ ch, uint32_t stride,
+                                                          uint64_t* __restrict__ out_ch) {
+    const size_t p = blockIdx.x;
+    const uint32_t nw = (3 + k) * 4;
+    const size_t c0 = (size_t)px[p * PX_WORDS + PX_CH] * 4;
+    for (uint32_t w = threadIdx.x; w < nw; w += 64) out_ch[c0 + w] = ch[p * stride + w];
 }
 
 }  // namespace bpp

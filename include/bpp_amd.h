@@ -539,6 +539,58 @@ int bpp_range_verify_batch_serialized_grouped_mixed_device(bpp_verifier *v, cons
                                                            uint32_t *d_ok, uint64_t *stats, void *d_workspace,
                                                            size_t workspace_bytes, void *stream);
 
+/* ---- PROVING blocks of mixed aggregation sizes with one engine: the producing side of the mixed verify calls ----
+ * One engine created for capacity (n, m) proves a block in which proof i has m_of[i] values, m_of[i] a power of two <= m
+ * (the rules and error texts of bpp_verifier_run_mixed).  Proof i is, bit for bit, RangeProof::prove (reference
+ * src/range/mod.rs:31-55, :80-187, :240-403; src/weighted_inner_product_proof.rs:36-227; commitments
+ * src/range/prover.rs:28-42) for PublicKey::new(n m_i), the prefix key of its own shape: what bpp_range_prove_batch* gives
+ * on a dedicated (n, m_i) engine of the same key.  The output is written once, straight into the layout the mixed verifier
+ * reads.
+ *   d_v, d_gamma     : sum m_i uint64_t / sum m_i scalars, packed in caller order (device)
+ *   m_of             : HOST array of count values m_i
+ *   flags            : 0: the reference's literal challenges and blinding.  BPP_SER_TRANSCRIPT: Fiat-Shamir, as
+ *                      bpp_range_prove_batch_fs_device, with blinding from blind_key (32 bytes, host), or from d_blinding
+ *                      (5 + 2 k_i scalars per proof, packed in caller order, device), or -- both NULL -- the literals.
+ *                      Blinding without BPP_SER_TRANSCRIPT is BPP_E_ARG.
+ *   index_base       : the blinding index belongs to the CALLER's numbering: proof i uses index_base + i whatever its
+ *                      place inside the engine (the rule bpp_verifier_run_grouped_mixed states for its weights)
+ *   d_out_points     : proof i's record [A, wip.A, wip.B, L.., R.., V_0..V_{m_i-1}] at wire point
+ *                      sum_{j<i} (3 + 2 k_j + m_j): exactly bpp_verifier_run_mixed's d_points
+ *   d_out_scalars    : count x 3 scalars [r', s', delta'], caller order
+ *   d_out_challenges : NULL, or the packed 3 + k_i blocks [y, z, e, e_1..e_k]: bpp_verifier_run_mixed's d_challenges
+ *   d_workspace      : bpp_prover_mixed_workspace_bytes(engine, m_of, count) bytes (0 when an m_i is not taken)
+ * Errors: BPP_E_ARG for an m_of[i] that is not taken (the text names i), a NULL pointer, a workspace that is too small,
+ * blind_key and d_blinding both given, an unknown flag; nothing is enqueued and no output is written then.  count = 0 is
+ * BPP_OK.  The call BLOCKS the host only while it uploads the per-proof index (a pageable copy on `stream`); everything else
+ * is enqueued asynchronously on `stream`: per m_i present a gather of its values and gammas and bpp_range_prove_batch*'s
+ * kernels over the prefix view of the tables, the records written through the index (k_pb_collect). */
+size_t bpp_prover_mixed_workspace_bytes(const bpp_verifier *engine, const uint32_t *m_of, size_t count);
+int bpp_range_prove_batch_mixed_device(bpp_verifier *engine, const uint64_t *d_v, const uint64_t *d_gamma, const uint32_t *m_of,
+                                       size_t count, int flags, const uint8_t *blind_key, uint64_t index_base,
+                                       const uint64_t *d_blinding, uint64_t *d_out_points, uint64_t *d_out_scalars,
+                                       uint64_t *d_out_challenges, void *d_workspace, size_t workspace_bytes, void *stream);
+/* The same proofs as BYTES (reference: as above; the container has no reference counterpart, see "serialized proofs"):
+ * container i of bpp_proof_bytes_version(curve, n, m_of[i], version) bytes, packed back to back in caller order in
+ * d_out_proofs, and m_of[i] encoded commitments per proof packed in d_out_commitments -- the input of
+ * bpp_range_verify_batch_serialized_mixed_device, and a stream bpp_proofs_scan frames.  flags also takes
+ * BPP_SER_UNCOMPRESSED (container version 2, commitments uncompressed; BPP_E_ARG on ristretto255).  The 4 GiB limits of
+ * the 32-bit byte index apply as on the verify side.  The records are proved into workspace regions per m_i and one kernel
+ * (k_container_encode_mixed) writes every byte of the two output buffers.  Errors and blocking as above. */
+size_t bpp_prover_serialized_mixed_workspace_bytes(const bpp_verifier *engine, const uint32_t *m_of, size_t count);
+int bpp_range_prove_batch_serialized_mixed_device(bpp_verifier *engine, const uint64_t *d_v, const uint64_t *d_gamma,
+                                                  const uint32_t *m_of, size_t count, int flags, const uint8_t *blind_key,
+                                                  uint64_t index_base, const uint64_t *d_blinding, void *d_out_proofs,
+                                                  void *d_out_commitments, void *d_workspace, size_t workspace_bytes,
+                                                  void *stream);
+/* Both on HOST buffers (RangeProof::prove per proof, src/range/mod.rs:31-55), synchronous; layouts as above, blinding from
+ * blind_key or the literals.  out_challenges may be NULL. */
+int bpp_range_prove_batch_mixed(bpp_verifier *engine, const uint64_t *v, const uint64_t *gamma, const uint32_t *m_of,
+                                size_t count, int flags, const uint8_t *blind_key, uint64_t index_base, uint64_t *out_points,
+                                uint64_t *out_scalars, uint64_t *out_challenges);
+int bpp_range_prove_batch_serialized_mixed(bpp_verifier *engine, const uint64_t *v, const uint64_t *gamma, const uint32_t *m_of,
+                                           size_t count, int flags, const uint8_t *blind_key, uint64_t index_base,
+                                           uint8_t *out_proofs, uint8_t *out_commitments);
+
 /* Frames a bare byte stream of concatenated containers (host memory; no device, no context): m_of[i] = the m of container
  * i, whose length its header implies (n, m, k, version).  BPP_OK with *out_count containers when the stream is consumed
  * exactly (an empty stream: 0).  Otherwise a negative code, *out_count = the containers before the offending one, and

@@ -23,7 +23,15 @@ usage: python tools/mixed_bench.py [--reps 20] [--warmup 3] [--window 16] [--out
                           C  five grouped calls on the dedicated verifiers, the proofs pre-sorted by class
                           A' the new call on the block with --tamper proofs flipped
                         Write it with --out profiles/mixed_grouped_bench.json / mixed_grouped_serialized_bench.json;
-                        with --mixed-only: leg A alone (the run to put under rocprofv3 --kernel-trace --stats)"""
+                        with --mixed-only: leg A alone (the run to put under rocprofv3 --kernel-trace --stats)
+       [--prove]        PROVING the same block of values, under the transcript (literal blinding), as containers in HBM.
+                        Three legs, alternated repetition by repetition:
+                          A  one bpp_range_prove_batch_serialized_mixed_device call on the capacity engine
+                          B  five bpp_range_prove_batch_fs_device calls on dedicated engines, the inputs pre-sorted by class
+                          C  (wall clock) what a caller did after B to get the same bytes: D2H, bpp_proofs_encode_version
+                             and bpp_points_compress per class, the interleave into caller order
+                        A's bytes are compared with C's after every repetition.  Write it with
+                        --out profiles/mixed_prove_bench.json; with --mixed-only: leg A alone, one engine, no comparison"""
 import argparse
 import json
 import os
@@ -71,6 +79,7 @@ def main():
     ap.add_argument("--mixed-only", action="store_true")
     ap.add_argument("--serialized", action="store_true")
     ap.add_argument("--grouped", action="store_true")
+    ap.add_argument("--prove", action="store_true")
     ap.add_argument("--group", type=int, default=32)
     ap.add_argument("--detour-reps", type=int, default=3)
     ap.add_argument("--out", default=None)
@@ -85,6 +94,8 @@ def main():
     t0 = time.time()
     cap = B.BatchVerifier(pk, N, CAP, window_bits=args.window)
     build_s = {"capacity": time.time() - t0}
+    if args.prove:
+        return prove(args, torch, B, a, cap, rng, build_s)
     # engines that make (and, for the comparison, verify) each class's proofs: the dedicated (64, m') verifiers
     ded = {}
     for m in MIX:
@@ -409,6 +420,112 @@ def grouped(args, torch, B, a, cap, ded, recs, scs, order, ms, victims, build_s)
                 "ratio_A_over_B": med["A"] / med["B"], "ratio_A_over_C": med["A"] / med["C"],
                 "ranges_A_B_disjoint": max(times["A"]) < min(times["B"]),
                 "A_verifies_per_s": count / (med["A"] / 1e3), "A_tampered_verifies_per_s": count / (med["A_tampered"] / 1e3),
+                "table_bytes_dedicated_sum": int(sum(ded[m].table_bytes for m in MIX))})
+    return finish(args, res)
+
+
+def prove(args, torch, B, a, cap, rng, build_s):
+    """the --prove legs: the block's values in HBM in, containers and commitments in HBM out"""
+    dev = torch.device("cuda:0")
+    stream = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    order = [(m, i) for m, cnt in MIX.items() for i in range(cnt)]
+    order = [order[p] for p in rng.permutation(len(order))]
+    count, ms = len(order), [m for m, _ in order]
+    vals = {m: rng.integers(0, 1 << 31, size=(cnt, m), dtype=np.uint64) for m, cnt in MIX.items()}
+    gams = {m: np.zeros((cnt, m, 4), dtype=np.uint64) for m, cnt in MIX.items()}
+    for m in MIX:
+        gams[m][:, :, 0] = rng.integers(1, 1 << 62, size=gams[m].shape[:2], dtype=np.uint64)
+    d_v = up(np.concatenate([vals[m][i] for m, i in order]).view(np.int64))
+    d_g = up(np.concatenate([gams[m][i] for m, i in order]).view(np.int64))
+    pbytes = sum(B.proof_bytes(a, N, m) for m in ms)
+    cbytes = sum(ms) * B.compressed_bytes(a)
+    d_raw = torch.zeros(pbytes, dtype=torch.uint8, device=dev)
+    d_cm = torch.zeros(cbytes, dtype=torch.uint8, device=dev)
+    wsb = cap.prover_mixed_workspace_bytes(ms, serialized=True)
+    d_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+
+    def leg_a():
+        cap.prove_serialized_mixed_device(d_v.data_ptr(), d_g.data_ptr(), ms, d_raw.data_ptr(), d_cm.data_ptr(), d_ws.data_ptr(),
+                                          wsb, stream(), transcript=True)
+
+    res = {"shape": {"curve": "bls12_381", "n": N, "capacity_m": CAP, "window": args.window, "count": count,
+                     "mix": {str(m): c for m, c in MIX.items()}, "transcript": True, "blinding": "literals",
+                     "container_bytes": int(pbytes), "commitment_bytes": int(cbytes)},
+           "device": torch.cuda.get_device_name(0), "table_bytes_one": int(cap.table_bytes),
+           "prover_serialized_mixed_workspace_bytes": int(wsb), "build_s": build_s}
+    if args.mixed_only:
+        t_a = timed(torch, leg_a, args.reps, args.warmup)
+        res.update({"A_one_call": stats(t_a), "A_proofs_per_s": count / (statistics.median(t_a) / 1e3)})
+        return finish(args, res)
+    ded = {}
+    for m in MIX:
+        if m == CAP:
+            ded[m] = cap
+            continue
+        t0 = time.time()
+        ded[m] = B.BatchVerifier(B.PublicKey.new(a, N * m), N, m, window_bits=args.window)
+        build_s[str(m)] = time.time() - t0
+    pos = {m: [j for j, (mm, _) in enumerate(order) if mm == m] for m in MIX}
+    bufs = {}
+    for m in MIX:
+        idx = [order[j][1] for j in pos[m]]
+        cnt, k = len(idx), (N * m).bit_length() - 1
+        w = ded[m].prover_workspace_bytes(cnt)
+        bufs[m] = (up(vals[m][idx].view(np.int64)), up(gams[m][idx].view(np.int64)),
+                   torch.zeros((cnt, 3 + 2 * k, a.PW), dtype=torch.int64, device=dev),
+                   torch.zeros((cnt, 3, 4), dtype=torch.int64, device=dev), torch.zeros((cnt, m, a.PW), dtype=torch.int64, device=dev),
+                   torch.empty(w, dtype=torch.uint8, device=dev), w, cnt)
+
+    def leg_b():
+        for m in MIX:
+            v, g, p, s, V, w, wb, cnt = bufs[m]
+            ded[m].prove_batch_device(v.data_ptr(), g.data_ptr(), cnt, p.data_ptr(), s.data_ptr(), V.data_ptr(), w.data_ptr(), wb,
+                                      stream(), transcript=True)
+
+    lens = np.array([B.proof_bytes(a, N, m) for m in ms])
+    starts = np.concatenate([[0], np.cumsum(lens)])
+    cstarts = np.concatenate([[0], np.cumsum(np.array(ms) * B.compressed_bytes(a))])
+
+    def leg_c():
+        """-> (container bytes, commitment bytes) in caller order, through the host"""
+        raw = np.empty(pbytes, dtype=np.uint8)
+        cm = np.empty(cbytes, dtype=np.uint8)
+        for m in MIX:
+            v, g, p, s, V, w, wb, cnt = bufs[m]
+            blobs = B.encode_proofs(a, N, m, p.cpu().numpy().view(np.uint64), s.cpu().numpy().view(np.uint64))
+            comm = B.compress_points(a, V.cpu().numpy().view(np.uint64).reshape(-1, a.PW)).reshape(cnt, -1)
+            sel = np.array(pos[m])
+            raw[(starts[sel][:, None] + np.arange(blobs.shape[1])[None, :]).reshape(-1)] = blobs.reshape(-1)
+            cm[(cstarts[sel][:, None] + np.arange(comm.shape[1])[None, :]).reshape(-1)] = comm.reshape(-1)
+        return raw, cm
+
+    for _ in range(args.warmup):
+        leg_a()
+        leg_b()
+    torch.cuda.synchronize()
+    t_a, t_b, t_c, same = [], [], [], True
+    for _ in range(args.reps):
+        t_a += timed(torch, leg_a, 1, 0)
+        t_b += timed(torch, leg_b, 1, 0)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        raw, cm = leg_c()
+        t_c.append((time.perf_counter() - t0) * 1e3)
+        same &= bool(np.array_equal(d_raw.cpu().numpy(), raw) and np.array_equal(d_cm.cpu().numpy(), cm))
+    # the block verifies where it lies
+    d_ok = torch.full((count,), 7, dtype=torch.int32, device=dev)
+    w2 = cap.serialized_mixed_workspace_bytes(ms)
+    d_ws2 = torch.empty(w2, dtype=torch.uint8, device=dev)
+    cap.verify_serialized_mixed_device(d_raw.data_ptr(), d_cm.data_ptr(), ms, d_ok.data_ptr(), d_ws2.data_ptr(), w2, stream(),
+                                       transcript=True)
+    med = {"A": statistics.median(t_a), "B": statistics.median(t_b), "C": statistics.median(t_c)}
+    res.update({"A_one_call": stats(t_a), "B_five_dedicated_calls": stats(t_b), "C_host_encode_wall": stats(t_c),
+                "A_bytes_equal_C_every_rep": same, "A_block_verifies": not bool(d_ok.cpu().numpy().any()),
+                "A_minus_B_median_ms": med["A"] - med["B"], "B_spread_ms": max(t_b) - min(t_b),
+                "A_within_B_spread": med["A"] - med["B"] <= max(t_b) - min(t_b),
+                "ratio_A_over_B": med["A"] / med["B"], "ratio_A_over_B_plus_C": med["A"] / (med["B"] + med["C"]),
+                "A_proofs_per_s": count / (med["A"] / 1e3),
                 "table_bytes_dedicated_sum": int(sum(ded[m].table_bytes for m in MIX))})
     return finish(args, res)
 
