@@ -507,6 +507,82 @@ BPP_HD void glv_split(const uint32_t* k, uint32_t* k1, uint32_t* k2) {
     }
 }
 
+// The BALANCED form of that split, for the fixed-generator window tables (kernels.hpp k_fixed_msm): both halves signed and
+// one bit shorter, k = (+-k1) + (+-k2) z^2 (mod r) with k1 <= z^2 / 2 and k2 <= floor(z^2 / 2) + 1 (< 2^126.43).
+//   k > (r - 1) / 2: split r - k and flip both signs, so the quotient is at most (r - 1) / (2 z^2) < z^2 / 2;
+//   k1 > z^2 / 2:    k1 <- z^2 - k1 with its sign flipped, and k2 <- k2 + 1.
+// k: 8 canonical words (< r).  A zero half may carry either sign.  tests/host/fixed_glv_host_test.cpp checks it against
+// Python integers.
+template <class C>
+BPP_HD void glv_split_balanced(const uint32_t* k, uint32_t* k1, uint32_t* k2, bool& neg1, bool& neg2) {
+    using K = typename C::K;
+    using P = typename C::Fr;
+    bool above = false;   // k > (r - 1) / 2 ?
+    for (int t = 7; t >= 0; t--) {
+        if (k[t] != P::HALFW[t]) {
+            above = k[t] > P::HALFW[t];
+            break;
+        }
+    }
+    uint32_t kk[8];
+    {
+        uint32_t borrow = 0;
+#pragma unroll
+        for (int t = 0; t < 8; t++) {
+            const uint64_t d = (uint64_t)P::MODW[t] - k[t] - borrow;
+            kk[t] = above ? (uint32_t)d : k[t];
+            borrow = (uint32_t)(d >> 63);
+        }
+    }
+    glv_split<C>(kk, k1, k2);
+    // z^2 is even: k1 > z^2 / 2  <=>  2 k1 > z^2
+    bool big = (k1[3] >> 31) != 0;
+    if (!big) {
+        for (int t = 3; t >= 0; t--) {
+            const uint32_t d = (k1[t] << 1) | (t > 0 ? k1[t - 1] >> 31 : 0u);
+            if (d != K::ZSQW[t]) {
+                big = d > K::ZSQW[t];
+                break;
+            }
+        }
+    }
+    uint32_t borrow = 0, carry = big ? 1u : 0u;
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const uint64_t d = (uint64_t)K::ZSQW[t] - k1[t] - borrow;
+        borrow = (uint32_t)(d >> 63);
+        if (big) k1[t] = (uint32_t)d;
+        const uint64_t x = (uint64_t)k2[t] + carry;
+        k2[t] = (uint32_t)x;
+        carry = (uint32_t)(x >> 32);
+    }
+    neg1 = above != big;
+    neg2 = above;
+}
+
+// The endomorphism image [z^2] P = (beta x, -y) of an XYZZ accumulator, WITHOUT the sign: X <- beta X.  The caller of the
+// fixed-generator sums folds the sign into the additions that built the accumulator (psi(-S) = (beta X, Y)).  Infinity
+// (ZZ = 0) stays infinity; X may carry the lazy bound of xyzz_madd_lazy (< 6p) and comes out < 1.07p.
+template <class C>
+BPP_HD void xyzz_mul_x_beta(Xyzz<C>& p) {
+    Fe<typename C::Fp> beta;
+#pragma unroll
+    for (int i = 0; i < C::Fp::NL; i++) beta.l[i] = C::K::BETA[i];
+    p.X = fe_mul(p.X, beta);
+}
+
+// ... and of one affine table entry, kept canonical (x < p) as xyzz_madd_lazy wants its entries; infinity (x = y = 0)
+// stays infinity
+template <class C>
+BPP_HD void aff_mul_x_beta(Aff<C>& q) {
+    if (q.is_inf()) return;
+    Fe<typename C::Fp> beta;
+#pragma unroll
+    for (int i = 0; i < C::Fp::NL; i++) beta.l[i] = C::K::BETA[i];
+    q.x = fe_mul(q.x, beta);
+    fe_cond_sub_p(q.x);
+}
+
 // Which curves split scalars with an endomorphism: BLS12-381 G1 ([z^2] P = (beta x, -y), above) and secp256k1
 // ([lambda] P = (beta x, y)); the Edwards instantiation has none.
 template <class C>

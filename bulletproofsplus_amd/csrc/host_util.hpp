@@ -176,7 +176,10 @@ inline void store_generator(uint32_t* affm_words) {
 inline bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
 
 // fr_modw: the scalar-field modulus as 8 little-endian 32-bit words, fr_bits its bit length.
-inline int make_shape(size_t n, size_t m, int c, const uint32_t* fr_modw, int fr_bits, VerifyShape& s) {
+// glv_half_max (4 words, or null): the table serves the two halves of the curve's endomorphism split, each at most this
+// large -- the layout of fixed_glv.hpp instead of uniform windows over the whole scalar (make_verify_shape below).
+inline int make_shape(size_t n, size_t m, int c, const uint32_t* fr_modw, int fr_bits, VerifyShape& s,
+                      const uint32_t* glv_half_max = nullptr) {
     const size_t mn = n * m;
     if (n == 0 || m == 0 || !is_pow2(mn)) return fail(BPP_E_ARG, "n*m must be a power of two");
     if (n > VS_MAXN || m > VS_MAXM) return fail(BPP_E_ARG, "n or m exceeds the supported maximum (64)");
@@ -192,10 +195,31 @@ inline int make_shape(size_t n, size_t m, int c, const uint32_t* fr_modw, int fr
     s.NF = (uint32_t)(2 * mn + 2);
     s.NV = (uint32_t)(3 + 2 * k + m);
     s.c = (uint32_t)c;
+    s.hgap = 0;
+    s.glv = 0;
+    for (int j = 0; j < VS_MAXW; j++) {
+        s.wc[j] = 0;
+        s.went[j] = 0;
+    }
     // W - 1 signed windows below bit c (W-1) < fr_bits, then one unsigned top window for the rest of the value
     s.W = (uint32_t)((fr_bits - 1) / c + 1);
     s.half = 1u << (c - 1);
     for (int t = 0; t < 10; t++) s.bias[t] = 0;
+    if (glv_half_max) {
+        static_assert(VS_MAXW == GLV_MAXW, "VerifyShape carries a GlvLayout's windows");
+        GlvLayout L;
+        if (!glv_layout(c, fr_bits, glv_half_max, L)) return fail(BPP_E_ARG, "window_bits too small or too large for this scalar field");
+        s.glv = 1;
+        s.W = L.W;
+        s.top = L.top;
+        s.per_f = L.per_f;
+        for (uint32_t j = 0; j < L.W; j++) {
+            s.wc[j] = L.wc[j];
+            s.went[j] = L.went[j];
+        }
+        for (int t = 0; t < GLV_HALF_WORDS; t++) s.bias[t] = L.bias[t];
+        return BPP_OK;
+    }
     for (uint32_t j = 0; j + 1 < s.W; j++) {
         const uint32_t bit = s.c * j + (s.c - 1);
         s.bias[bit >> 5] |= 1u << (bit & 31);
@@ -225,8 +249,19 @@ inline int make_shape(size_t n, size_t m, int c, const uint32_t* fr_modw, int fr
     const uint64_t per_f = (uint64_t)(s.W - 1) * s.half + s.top;
     if (per_f >> 32) return fail(BPP_E_ARG, "window table too large");
     s.per_f = (uint32_t)per_f;
-    s.hgap = 0;
     return BPP_OK;
+}
+
+// the shape of a verifier on curve C
+template <class C>
+inline int make_verify_shape(size_t n, size_t m, int c, VerifyShape& s) {
+    if constexpr (fixed_glv<C>()) {
+        uint32_t hmax[4];
+        glv_half_max<C>(hmax);
+        return make_shape(n, m, c, C::Fr::MODW, C::Fr::BITS, s, hmax);
+    } else {
+        return make_shape(n, m, c, C::Fr::MODW, C::Fr::BITS, s);
+    }
 }
 
 // the two verifier-scalars kernels (kernels.hpp): d_prep holds count * vs_prep_bytes<C>(s) bytes

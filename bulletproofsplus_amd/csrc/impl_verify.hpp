@@ -140,7 +140,7 @@ struct VerifyImpl {
 
     // form of the Horner stage for a pass over `count` proofs (k_fixed_msm's horner_tree: 0, 1 or 2)
     static uint32_t horner_form(const VerifyShape& s, size_t count) {
-        const bool small_job = (double)count * ((double)s.NF * s.W / 7.0e9 + 9.2e-8) < 2.0e-3;
+        const bool small_job = (double)count * ((double)s.NF * fixed_adds_per_generator(s) / 7.0e9 + 9.2e-8) < 2.0e-3;
         return count <= HORNER_TREE_MAX ? 1u : (small_job ? 2u : 0u);
     }
     // The proof points' tables (k_var_tables) need the points but not the scalars: fork_tables builds them on the verifier's
@@ -655,7 +655,7 @@ template <class C>
 int VerifyImpl<C>::create(const bpp_ctx& ctx, const uint64_t* gh, const uint64_t* G, const uint64_t* H, size_t n, size_t m,
                   int window_bits, bpp_verifier** out) {
     VerifyShape s;
-    int rc = make_shape(n, m, window_bits, C::Fr::MODW, C::Fr::BITS, s);
+    int rc = make_verify_shape<C>(n, m, window_bits, s);
     if (rc) return rc;
     std::vector<uint64_t> fixed((size_t)s.NF * PW);
     std::memcpy(fixed.data(), gh, 2 * PW * 8);
@@ -664,6 +664,18 @@ int VerifyImpl<C>::create(const bpp_ctx& ctx, const uint64_t* gh, const uint64_t
     DevBuf dfixed;
     rc = upload_points<C>(fixed.data(), s.NF, dfixed, nullptr);
     if (rc) return rc;
+    if constexpr (fixed_glv<C>()) {
+        // the shared table evaluates [z^2] F as (beta x, -y): true in the prime-order subgroup only, and from_points-style
+        // callers may hand over any curve point
+        DevBuf bad;
+        uint32_t hbad = 0;
+        HIPCHK(bad.alloc(4));
+        HIPCHK(zero_words_async(bad.p, 4, nullptr));
+        hipLaunchKernelGGL(k_affm_subgroup<C>, dim3(cdiv(s.NF, 64)), dim3(64), 0, nullptr, dfixed.u32(), bad.u32(), (size_t)s.NF);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(&hbad, bad.p, 4, hipMemcpyDeviceToHost));
+        if (hbad) return fail(BPP_E_ARG, "a fixed generator lies outside the prime-order subgroup");
+    }
     auto v = std::make_unique<bpp_verifier>();
     v->ctx = ctx;
     v->s = s;
@@ -696,7 +708,7 @@ int VerifyImpl<C>::create(const bpp_ctx& ctx, const uint64_t* gh, const uint64_t
     std::vector<size_t> voff;
     for (uint32_t mp = 1; mp < s.m; mp <<= 1) {
         PassShape ps{};
-        rc = make_shape(n, mp, window_bits, C::Fr::MODW, C::Fr::BITS, ps.s);
+        rc = make_verify_shape<C>(n, mp, window_bits, ps.s);
         if (rc) return rc;
         ps.s.hgap = s.n * (s.m - mp);
         std::vector<uint64_t> prefix((size_t)ps.s.NF * PW);

@@ -9,6 +9,8 @@
 //                      d = 1..half (signed digits, half = 2^(c-1)), the top window W-1 holds d = 1..top (its digit
 //                      is the unsigned remainder of the scalar, so no window is spent on a recoding carry);
 //                      per_f = (W-1) half + top; F = [g, h, G_0.., H_0..] the verifier's fixed generators.
+//                      BLS12-381 (fixed_glv<C>()): one table for both 127-bit halves of the endomorphism split, windows of
+//                      mixed widths: entry[f * per_f + went[j] + (d - 1)] = d * 2^(off_j) * F_f   (fixed_glv.hpp)
 //
 // Kernel inventory (each names the reference call site it serves; paths relative to /root/reference/src):
 //   k_points_from_wire   wire -> affm (+ on-curve check)
@@ -28,6 +30,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ec.hpp"
+#include "fixed_glv.hpp"
 #include "ed25519.hpp"
 #include "ristretto.hpp"
 #include "transcript.hpp"
@@ -355,6 +358,7 @@ __global__ void __launch_bounds__(64) k_jac_reduce(const uint32_t* __restrict__ 
 
 // ---- verifier scalars --------------------------------------------------------------------------------
 
+#define VS_MAXW 64   // windows per half of a split scalar (window_bits 2 on a 255-bit field: 128 / 2)
 struct VerifyShape {
     uint32_t n, m, mn, k;      // bits per value, values, n*m, log2(mn)
     uint32_t N;                // MulVec length 2mn + 2k + m + 5
@@ -364,7 +368,31 @@ struct VerifyShape {
     uint32_t per_f;            // table entries per generator: (W-1) * half + top
     uint32_t bias[10];         // sum_{j < W-1} half * 2^(c j) as 32-bit words (signed-digit recoding bias)
     uint32_t hgap;             // table H block - this shape's H block: mn_table - mn (a prefix view of a larger table), else 0
+    // Curves whose tables serve both halves of the endomorphism split (fixed_glv<C>(), below): W counts the windows of ONE
+    // half, W - 1 signed ones of mixed widths wc[j] whose entries start at went[j], then the unsigned top window at
+    // went[W - 1]; c is the window_bits the layout was derived from and half is unused (host_util.hpp make_shape).
+    uint32_t glv;
+    uint8_t wc[VS_MAXW];
+    uint32_t went[VS_MAXW];
 };
+
+// Fixed-generator sums through the curve's endomorphism (BLS12-381 G1): a scalar is split into two signed halves of 127
+// bits (ec.hpp glv_split_balanced), ONE table T[j][d] = d 2^(off_j) F serves both, and because psi = [z^2] is a group
+// homomorphism it is applied once to a lane's accumulator -- after the lane has summed all its k2-half entries -- instead of
+// once per gathered entry.  Half the windows per half, one more window bit for the same memory: 14 additions per generator
+// instead of 15 at window_bits 17.  Holds only on G1: the verifier refuses generators outside it (impl_verify.hpp create).
+template <class C>
+constexpr bool fixed_glv() {
+    return C::ID == 0;
+}
+// mixed additions per fixed generator
+__host__ __device__ __forceinline__ uint32_t fixed_adds_per_generator(const VerifyShape& s) {
+    return s.glv ? 2 * s.W : s.W;
+}
+// entries of window j of the shared table, and where they start within a generator's per_f entries
+__host__ __device__ __forceinline__ uint32_t glv_window_entries(const VerifyShape& s, uint32_t j) {
+    return j + 1 < s.W ? 1u << (s.wc[j] - 1) : s.top;
+}
 
 // table slot of fixed generator f of shape s: a prefix view (n, m') of an (n, m) table finds g, h and G_0.. where they
 // are, and its H_i hgap = n (m - m') generators further on
@@ -790,7 +818,21 @@ __device__ __forceinline__ void affine_chain(Jac<C> J, const uint32_t* __restric
     }
 }
 
-// thread f: base_{f,j} = 2^(c j) * F_f for every window j, written as entry d = 1
+// one lane per affm point: bad[0] |= 1 for a point outside the prime-order subgroup (ec.hpp aff_in_prime_subgroup).  The
+// shared table of fixed_glv<C>() curves relies on [z^2] P = (beta x, -y), which holds only there.
+template <class C>
+__global__ void __launch_bounds__(64) k_affm_subgroup(const uint32_t* __restrict__ affm, uint32_t* __restrict__ bad, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (!aff_in_prime_subgroup<C>(aff_ldg<C>(affm + i * 2 * C::Fp::N))) atomicOr(bad, 1u);
+}
+
+// first entry (d = 1) of window j within a generator's per_f entries
+__host__ __device__ __forceinline__ size_t tbl_window_start(const VerifyShape& s, uint32_t j) {
+    return s.glv ? (size_t)s.went[j] : (size_t)j * s.half;
+}
+// thread f: base_{f,j} = 2^(off_j) * F_f for every window j (off_j = c j, or the sum of the widths below j), written as
+// entry d = 1
 template <class C>
 __global__ void __launch_bounds__(64) k_tbl_bases(VerifyShape s, const uint32_t* __restrict__ fixed_pts, uint32_t* __restrict__ table) {
     constexpr int N = C::Fp::N;
@@ -799,10 +841,11 @@ __global__ void __launch_bounds__(64) k_tbl_bases(VerifyShape s, const uint32_t*
     if (f >= s.NF) return;
     Aff<C> p = aff_ldg<C>(fixed_pts + (size_t)f * 2 * N);
     for (uint32_t j = 0; j < s.W; j++) {
-        aff_stg<C>(table + ((size_t)f * s.per_f + (size_t)j * s.half) * 2 * N, p);
+        aff_stg<C>(table + ((size_t)f * s.per_f + tbl_window_start(s, j)) * 2 * N, p);
         if (j + 1 < s.W) {
             Jac<C> q = jac_from_aff(p);
-            for (uint32_t t = 0; t < s.c; t++) q = jac_dbl(q);
+            const uint32_t cj = s.glv ? s.wc[j] : s.c;
+            for (uint32_t t = 0; t < cj; t++) q = jac_dbl(q);
             p = jac_to_aff(q);
         }
     }
@@ -812,6 +855,11 @@ __global__ void __launch_bounds__(64) k_tbl_bases(VerifyShape s, const uint32_t*
 // (d0 + 1) * base, ... by affine_chain.  scratch: [thread][2 * TBL_RUN] field elements.
 constexpr uint32_t TBL_RUN = 32;
 __host__ __device__ __forceinline__ uint32_t tbl_runs_per_generator(const VerifyShape& s) {
+    if (s.glv) {   // windows of mixed widths: each has its own number of runs
+        uint32_t runs = 0;
+        for (uint32_t j = 0; j < s.W; j++) runs += (glv_window_entries(s, j) + TBL_RUN - 1) / TBL_RUN;
+        return runs;
+    }
     return (s.W - 1) * ((s.half + TBL_RUN - 1) / TBL_RUN) + (s.top + TBL_RUN - 1) / TBL_RUN;
 }
 template <class C>
@@ -824,12 +872,23 @@ __global__ void __launch_bounds__(64, BPP_VAR_TABLES_WAVES) k_tbl_fill(VerifySha
     if (idx >= (size_t)(f_end - f_begin) * runs_f) return;
     const uint32_t f = f_begin + (uint32_t)(idx / runs_f);
     const uint32_t rem = (uint32_t)(idx % runs_f);
-    const uint32_t j = min(rem / runs_low, s.W - 1);   // the top window has its own number of runs
-    const uint32_t r = rem - j * runs_low;
-    const uint32_t cnt = j + 1 < s.W ? s.half : s.top;
+    uint32_t j = min(rem / runs_low, s.W - 1);   // the top window has its own number of runs
+    uint32_t r = rem - j * runs_low;
+    uint32_t cnt = j + 1 < s.W ? s.half : s.top;
+    if (s.glv) {
+        j = 0;
+        r = rem;
+        for (;;) {
+            cnt = glv_window_entries(s, j);
+            const uint32_t runs_j = (cnt + TBL_RUN - 1) / TBL_RUN;
+            if (r < runs_j) break;   // rem < runs_f: ends at the top window at the latest
+            r -= runs_j;
+            j++;
+        }
+    }
     const uint32_t d0 = r * TBL_RUN + 1;
     const uint32_t n = min(TBL_RUN, cnt - (d0 - 1));
-    uint32_t* win = table + ((size_t)f * s.per_f + (size_t)j * s.half) * 2 * N;
+    uint32_t* win = table + ((size_t)f * s.per_f + tbl_window_start(s, j)) * 2 * N;
     const Aff<C> base = aff_ldg<C>(win);   // entry d = 1, written by k_tbl_bases
     Jac<C> J;
     if (d0 == 1) {
@@ -1055,6 +1114,8 @@ __global__ void __launch_bounds__(FIXED_BLOCK, fixed_waves<C>()) k_fixed_msm(Ver
     constexpr int JW = jac_words<C>();
     constexpr int CH = 2 * N / 4;                              // 16-byte pieces of a table entry
     constexpr int WAVE_WORDS = (FIXED_RING * CH + 2) * 256;    // LDS words of one wave's ring + scalar buffer
+    constexpr bool GLV = fixed_glv<C>();                       // two phases over the shared table (see fixed_glv<C>())
+    constexpr int NWD = GLV ? GLV_HALF_WORDS : 10;             // words of a biased scalar (GLV: of one half)
     extern __shared__ __align__(16) uint32_t lds[];
     if (blockIdx.x < horner_blocks) {   // block-uniform: the Horner stage of the proof-point MSM
         if (horner_tree == 2) {   // mid-size batches: eight lanes per proof, blockDim.x / 8 proofs per block
@@ -1127,8 +1188,16 @@ __global__ void __launch_bounds__(FIXED_BLOCK, fixed_waves<C>()) k_fixed_msm(Ver
     const bool spread = NFc >= stride;
     const uint32_t G = spread ? NFc / stride : (first < NFc ? 1u : 0u);
     const uint32_t T = G * s.W;                                    // whole-generator steps, the same for every lane
-    const uint32_t LW = spread ? (NFc - G * stride) * s.W : 0u;    // left-over (generator, window) entries of the proof
+    constexpr uint32_t PH = GLV ? 2u : 1u;
+    const uint32_t LWH = spread ? (NFc - G * stride) * s.W : 0u;   // left-over (generator, window) entries of the proof
+    const uint32_t LW = PH * LWH;                                  // (GLV: of its k2 halves, then of its k1 halves)
     const uint32_t TT = T + (LW + stride - 1) / stride;            // + extra steps
+    // GLV: the T whole-generator steps run once per PHASE.  Phase 0 sums the k2 halves NEGATED, then the accumulator's X is
+    // multiplied by beta -- psi(-S) = (beta X, Y), i.e. [z^2] of the k2 sum -- and phase 1 adds the k1 halves over the same
+    // windows of half the scalar's length.  The scalar of a generator travels through sbuf once per phase.  The left-over
+    // entries of BOTH halves follow phase 1 in one set of extra steps (two sets would cost a proof of 130 generators a
+    // whole step more than the unsplit schedule): there a k2 entry meets psi on its own, x <- beta x, one multiplication.
+    const uint32_t NQ = PH * G;                                    // scalars a lane takes, phase after phase
     Xyzz<C> acc = xyzz_inf<C>();  // the running sum only ever receives affine points: 8M + 2S per addition
 
     auto dma_scalar = [&](uint32_t g) {
@@ -1138,27 +1207,87 @@ __global__ void __launch_bounds__(FIXED_BLOCK, fixed_waves<C>()) k_fixed_msm(Ver
         glds16(src, sbuf_addr);
         glds16(src + 4, sbuf_addr + 1024);
     };
-    uint32_t w[10];
+    uint32_t w[NWD];
+    uint32_t hneg = 0;   // GLV: the half in w stands for its negative (phase 0: the sign of psi folded in)
+    uint32_t pi = 0;     // GLV: phase of the issue side -- block-uniform
+    // GLV: half `which` (0: k2, 1: k1) of scalar v, biased, and the sign its entries take (k2: that of psi folded in)
+    auto take_half = [&](const uint32_t* v, uint32_t which, uint32_t* out, uint32_t& negate) {
+        if constexpr (GLV) {
+            uint32_t k1[4], k2[4];
+            bool n1, n2;
+            glv_split_balanced<C>(v, k1, k2, n1, n2);
+            glv_biased(which ? k1 : k2, s.bias, out);
+            negate = which ? (n1 ? 1u : 0u) : (n2 ? 0u : 1u);
+        }
+    };
     auto take_scalar = [&]() {   // sbuf -> w = scalar + bias K (K = sum_{j < W-1} half * 2^(c j))
         const uint4* q = reinterpret_cast<const uint4*>(sbuf);
         const uint4 lo = q[lane], hi = q[64 + lane];
         const uint32_t v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-        uint32_t carry = 0;
+        if constexpr (GLV) {
+            take_half(v, pi, w, hneg);
+        } else {
+            uint32_t carry = 0;
 #pragma unroll
-        for (int t = 0; t < 10; t++) {
-            uint64_t x = (uint64_t)(t < 8 ? v[t] : 0u) + s.bias[t] + carry;
-            w[t] = (uint32_t)x;
-            carry = (uint32_t)(x >> 32);
+            for (int t = 0; t < 10; t++) {
+                uint64_t x = (uint64_t)(t < 8 ? v[t] : 0u) + s.bias[t] + carry;
+                w[t] = (uint32_t)x;
+                carry = (uint32_t)(x >> 32);
+            }
         }
     };
     // issue side: runs FIXED_RING steps ahead of the additions
-    uint32_t ti = 0, gi = 0, ji = 0;   // step, generator iteration, window -- block-uniform
+    uint32_t ti = 0, gi = 0, ji = 0;   // step (GLV: of the phase), generator iteration, window -- block-uniform
     uint32_t vbits = 0, nbits = 0;     // per ring slot: this lane has an entry there / it must be negated
+    uint32_t bbits = 0;                // GLV: ... / it is a left-over entry of a k2 half (x <- beta x)
     auto issue = [&]() {
-        const uint32_t slot = ti % FIXED_RING;
+        const uint32_t slot = (GLV ? pi * T + ti : ti) % FIXED_RING;
         const uint32_t* src = table;   // dummy line for lanes without an entry
-        uint32_t valid = 0, neg = 0;
-        if (ti < T) {
+        uint32_t valid = 0, neg = 0, viabeta = 0;
+        if constexpr (GLV) {
+            if (ti < T) {
+                const uint32_t qi = pi * G + gi;
+                if (ji == 0 && qi > 0) {
+                    take_scalar();
+                    if (qi + 1 < NQ) dma_scalar(gi + 1 < G ? gi + 1 : 0u);
+                }
+                const uint32_t x = f0 + gi * stride;
+                const int32_t dg = glv_next_digit(w, s.wc[ji]);   // width 0: the top window
+                if (x < NFc && dg != 0) {
+                    const uint32_t f = gen_of(x);
+                    const uint32_t mag = dg < 0 ? (uint32_t)(-dg) : (uint32_t)dg;
+                    src = table + ((size_t)table_generator(s, f) * s.per_f + s.went[ji] + (mag - 1)) * 2 * N;
+                    valid = 1;
+                    neg = (dg < 0 ? 1u : 0u) ^ hneg ^ (f >= neg_from ? 1u : 0u);
+                }
+            } else if (pi == 1 && ti < TT) {
+                const uint32_t x = (ti - T) * stride + f0;   // this lane's left-over entry, if any
+                if (x < LW) {
+                    const uint32_t which = x >= LWH ? 1u : 0u, xh = x - which * LWH;
+                    const uint32_t l = xh / s.W, jx = xh - l * s.W;
+                    const uint32_t f = gen_of(G * stride + l);
+                    uint32_t v[8], we[GLV_HALF_WORDS], hn;
+                    ld_words<8>(sc + (size_t)fixed_term_index(s, f) * 8, v);   // an ordinary load: once per block
+                    take_half(v, which, we, hn);
+                    viabeta = 1u - which;
+                    int32_t dg = 0;
+                    uint32_t eo = 0;
+                    for (uint32_t r = 0; r < s.W; r++) {   // r is the same in every lane: the widths stay scalar loads
+                        const int32_t d = glv_next_digit(we, s.wc[r]);
+                        if (r == jx) {
+                            dg = d;
+                            eo = s.went[r];
+                        }
+                    }
+                    if (dg != 0) {
+                        const uint32_t mag = dg < 0 ? (uint32_t)(-dg) : (uint32_t)dg;
+                        src = table + ((size_t)table_generator(s, f) * s.per_f + eo + (mag - 1)) * 2 * N;
+                        valid = 1;
+                        neg = (dg < 0 ? 1u : 0u) ^ hn ^ (f >= neg_from ? 1u : 0u);
+                    }
+                }
+            }
+        } else if (ti < T) {
             if (ji == 0 && gi > 0) {
                 take_scalar();
                 if (gi + 1 < G) dma_scalar(gi + 1);
@@ -1211,21 +1340,34 @@ __global__ void __launch_bounds__(FIXED_BLOCK, fixed_waves<C>()) k_fixed_msm(Ver
         for (int k = 0; k < CH; k++) glds16(src + 4 * k, ring_addr + (slot * CH + k) * 1024);
         vbits = (vbits & ~(1u << slot)) | (valid << slot);
         nbits = (nbits & ~(1u << slot)) | (neg << slot);
+        if constexpr (GLV) bbits = (bbits & ~(1u << slot)) | (viabeta << slot);
         ti++;
         if (++ji == s.W) {
             ji = 0;
             gi++;
+        }
+        if constexpr (GLV) {
+            if (ti == T && pi == 0) {   // the same generators again for the other half
+                pi = 1;
+                ti = 0;
+                gi = 0;
+                ji = 0;
+            }
         }
     };
     if (G) {
         dma_scalar(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         take_scalar();
-        if (G > 1) dma_scalar(1);
+        if (NQ > 1) dma_scalar(G > 1 ? 1u : 0u);
     }
     for (int d = 0; d < FIXED_RING; d++) issue();
-    for (uint32_t t = 0; t < TT; t++) {
-        const uint32_t slot = t % FIXED_RING;
+    for (uint32_t ph = 0; ph < PH; ph++)
+    for (uint32_t t = 0; t < (ph + 1 < PH ? T : TT); t++) {
+        if constexpr (GLV) {
+            if (ph == 1 && t == 0) xyzz_mul_x_beta(acc);   // [z^2] (sum of the k2 halves); infinity stays infinity
+        }
+        const uint32_t slot = (GLV ? ph * T + t : t) % FIXED_RING;
         // everything but the newest FIXED_RING - 1 steps' DMAs has landed: step t's entry is in LDS
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"((FIXED_RING - 1) * CH) : "memory");
         uint32_t raw[2 * N];
@@ -1239,7 +1381,10 @@ __global__ void __launch_bounds__(FIXED_BLOCK, fixed_waves<C>()) k_fixed_msm(Ver
             raw[4 * k + 3] = v.w;
         }
         const bool valid = (vbits >> slot) & 1u, neg = (nbits >> slot) & 1u;
-        const Aff<C> cur = aff_load<C>(raw);
+        Aff<C> cur = aff_load<C>(raw);
+        if constexpr (GLV) {
+            if (ph == 1 && t >= T && ((bbits >> slot) & 1u)) aff_mul_x_beta(cur);   // before issue() rewrites the slot's bits
+        }
         issue();   // step t + FIXED_RING goes into the slot just read
         if (valid) xyzz_madd_lazy(acc, cur, neg);
     }

@@ -173,7 +173,8 @@ int bpp_range_verify(bpp_ctx *ctx, const uint64_t *gh, const uint64_t *G, const 
  * RangeProof::verify would return for that proof.
  * window_bits in [2, 20] trades HBM for arithmetic: a b-bit scalar costs floor((b-1)/c) + 1 table additions per
  * generator and the tables hold about (2mn + 2) x b/c x 2^(c-1) affine points (n=64, m=16 on BLS12-381:
- * 12.7 GB at c = 13, 103 GB at c = 16, 204 GB at c = 17).  BPP_E_NOMEM (-5) if they do not fit. */
+ * 7.0 GB at c = 13, 49.5 GB at c = 16, 215 GB at c = 17: BLS12-381 keeps one table for both halves of the endomorphism
+ * split and returns BPP_E_ARG for a generator outside the prime-order subgroup).  BPP_E_NOMEM (-5) if they do not fit. */
 int bpp_verifier_create(bpp_ctx *ctx, const uint64_t *gh, const uint64_t *G, const uint64_t *H, size_t n,
                         size_t m, int window_bits, bpp_verifier **out);
 void bpp_verifier_destroy(bpp_verifier *v);
