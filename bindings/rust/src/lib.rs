@@ -197,6 +197,90 @@ pub struct WeightedInnerProductProof {
     pub d_prime: PrimeFieldElem,
 }
 
+impl WeightedInnerProductProof {
+    /// reference src/weighted_inner_product_proof.rs:36-227, on the engine's WIP seam (include/bpp_amd.h:
+    /// bpp_wip_prove_batch).  `power_of_y_vec` must be [y, y^2, .., y^len]; as the reference's verify (:252, :276) the engine
+    /// reads its first entry and rebuilds the rest.  `commitment` is dead in the reference (:57, :137-142) and is ignored.
+    /// `engine`: a BatchVerifier of this key with n m = len, or None for a small one created for the call.
+    pub fn prove(pk: &PublicKey, a_vec: &[PrimeFieldElem], b_vec: &[PrimeFieldElem], power_of_y_vec: &[PrimeFieldElem],
+                 gamma: &PrimeFieldElem, commitment: &Point, engine: Option<&BatchVerifier>) -> WeightedInnerProductProof {
+        let _ = commitment;
+        let len = pk.G_vec.len();
+        assert_eq!(pk.H_vec.len(), len);                        // wip.rs:60-67
+        assert_eq!(a_vec.len(), len);
+        assert_eq!(b_vec.len(), len);
+        assert_eq!(power_of_y_vec.len(), len);
+        assert!(len.is_power_of_two());
+        let k = len.trailing_zeros() as usize;
+        let own;
+        let eng = match engine {
+            Some(e) => e,
+            None => {
+                own = BatchVerifier::new(pk, len.min(64), len / len.min(64), 4);
+                &own
+            }
+        };
+        assert_eq!(1usize << eng.k, len);
+        let (a, b) = (flat_scalars(a_vec), flat_scalars(b_vec));
+        let mut pts = vec![0u64; (3 + 2 * k) * PW];
+        let mut sc = vec![0u64; 12];
+        let rc = unsafe {
+            ffi::bpp_wip_prove_batch(eng.handle, a.as_ptr(), b.as_ptr(), power_of_y_vec[0].0.as_ptr(), gamma.0.as_ptr(), 1, 0, 0,
+                                     std::ptr::null(), std::ptr::null(), 0, std::ptr::null(), pts.as_mut_ptr(),
+                                     sc.as_mut_ptr(), std::ptr::null_mut())
+        };
+        assert!(rc == 0, "bpp_wip_prove_batch failed: {}", rc);
+        let p = unflat_points(&pts);
+        let s = |i: usize| PrimeFieldElem([sc[4 * i], sc[4 * i + 1], sc[4 * i + 2], sc[4 * i + 3]]);
+        WeightedInnerProductProof { A: p[1], B: p[2], L_vec: p[3..3 + k].to_vec(), R_vec: p[3 + k..3 + 2 * k].to_vec(),
+                                    r_prime: s(0), s_prime: s(1), d_prime: s(2) }
+    }
+    /// reference src/weighted_inner_product_proof.rs:238-328; the four `*_exp` arguments are its *_exp_of_commitment
+    /// (:238-247).  A length that does not fit is Err(VerificationError), as :335-337, before anything reaches the engine.
+    #[allow(clippy::too_many_arguments)]
+    pub fn verify(&self, pk: &PublicKey, power_of_y_vec: &[PrimeFieldElem], G_exp: &[PrimeFieldElem], H_exp: &[PrimeFieldElem],
+                  g_exp: &PrimeFieldElem, V_exp: &[PrimeFieldElem], A_prime: &Point, V: &[Point],
+                  engine: Option<&BatchVerifier>) -> Result<(), ProofError> {
+        let len = pk.G_vec.len();
+        let k = self.L_vec.len();
+        if k >= 32 || len != 1usize << k || self.R_vec.len() != k || pk.H_vec.len() != len || G_exp.len() != len
+            || H_exp.len() != len || power_of_y_vec.len() != len || V_exp.len() != V.len() || V.len() > 64 {
+            return Err(ProofError::VerificationError);
+        }
+        let own;
+        let eng = match engine {
+            Some(e) => e,
+            None => {
+                own = BatchVerifier::new(pk, len.min(64), len / len.min(64), 4);
+                &own
+            }
+        };
+        if 1usize << eng.k != len {
+            return Err(ProofError::VerificationError);
+        }
+        let mut pts = vec![*A_prime, self.A, self.B];
+        pts.extend_from_slice(&self.L_vec);
+        pts.extend_from_slice(&self.R_vec);
+        pts.extend_from_slice(V);
+        let pw = flat_points(&pts);
+        let sc = flat_scalars(&[self.r_prime, self.s_prime, self.d_prime]);
+        let mut stm = Vec::with_capacity(2 * len + 1 + V.len());
+        stm.extend_from_slice(G_exp);
+        stm.extend_from_slice(H_exp);
+        stm.push(*g_exp);
+        stm.extend_from_slice(V_exp);
+        let stm = flat_scalars(&stm);
+        let mut ok = [1u32; 1];
+        let rc = unsafe {
+            ffi::bpp_wip_verify_batch(eng.handle, pw.as_ptr(), sc.as_ptr(), power_of_y_vec[0].0.as_ptr(), stm.as_ptr(), V.len(), 1,
+                                      0, std::ptr::null(), std::ptr::null(), ok.as_mut_ptr(), std::ptr::null_mut(),
+                                      std::ptr::null_mut())
+        };
+        assert!(rc == 0, "bpp_wip_verify_batch failed: {}", rc);
+        if ok[0] == 0 { Ok(()) } else { Err(ProofError::VerificationError) }
+    }
+}
+
 /// reference src/range/mod.rs:25-28
 pub struct RangeProof {
     pub A: Point,

@@ -51,6 +51,8 @@ EXPORTS = [
     "bpp_prover_mixed_workspace_bytes", "bpp_range_prove_batch_mixed_device",
     "bpp_prover_serialized_mixed_workspace_bytes", "bpp_range_prove_batch_serialized_mixed_device",
     "bpp_range_prove_batch_mixed", "bpp_range_prove_batch_serialized_mixed",
+    "bpp_wip_prover_workspace_bytes", "bpp_wip_prove_batch_device", "bpp_wip_verifier_workspace_bytes",
+    "bpp_wip_verify_batch_device", "bpp_wip_prove_batch", "bpp_wip_verify_batch",
 ]
 
 
@@ -183,6 +185,15 @@ def lib():
         L.bpp_range_prove_batch_mixed.argtypes = [vp, vp, vp, vp, sz, i32, ctypes.c_char_p, u64, vp, vp, vp]
         L.bpp_range_prove_batch_serialized_mixed.argtypes = [vp, vp, vp, vp, sz, i32, ctypes.c_char_p, u64, vp, vp]
         L.bpp_proofs_scan.argtypes = [i32, sz, i32, vp, sz, vp, sz, vp]
+        L.bpp_wip_prover_workspace_bytes.argtypes = [vp, sz]
+        L.bpp_wip_prover_workspace_bytes.restype = sz
+        L.bpp_wip_prove_batch_device.argtypes = [vp, vp, vp, vp, vp, sz, sz, i32, vp, ctypes.c_char_p, u64, vp, vp, vp, vp, vp,
+                                                 sz, vp]
+        L.bpp_wip_verifier_workspace_bytes.argtypes = [vp, sz, sz]
+        L.bpp_wip_verifier_workspace_bytes.restype = sz
+        L.bpp_wip_verify_batch_device.argtypes = [vp, vp, vp, vp, vp, sz, sz, i32, vp, vp, vp, vp, sz, vp, vp, vp]
+        L.bpp_wip_prove_batch.argtypes = [vp, vp, vp, vp, vp, sz, sz, i32, vp, ctypes.c_char_p, u64, vp, vp, vp, vp]
+        L.bpp_wip_verify_batch.argtypes = [vp, vp, vp, vp, vp, sz, sz, i32, vp, vp, vp, vp, vp]
         L.bpp_debug_field_op.argtypes = [vp, i32, i32, vp, vp, sz, vp]
         L.bpp_debug_point_op.argtypes = [vp, i32, vp, vp, sz, vp]
         _lib = L

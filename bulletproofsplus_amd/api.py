@@ -418,12 +418,93 @@ class RangeVerifier:
         self.commitment_vec = [np.ascontiguousarray(c, dtype=np.uint64) for c in commitment_vec]
 
 
+# the scalar-field orders r (group orders of the three instantiations)
+FR_ORDER = {
+    BLS12_381_G1: 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001,
+    _lib.SECP256K1: 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141,
+    _lib.ED25519: (1 << 252) + 27742317777372353535851937790883648493,
+}
+
+
+def _scalar_int(x) -> int:
+    return wire_to_int(x) if isinstance(x, np.ndarray) else int(x)
+
+
+def _wip_y(arith, power_of_y_vec, length: int) -> int:
+    """the y of a power_of_y_vec = [y, y^2, .., y^len] (exp_iter_type2), ValueError for anything else: the reference's
+    verify reads only the first entry (wip.rs:252) and rebuilds the rest, which is what the engine does"""
+    r = FR_ORDER[arith.curve]
+    pw = [_scalar_int(x) % r for x in power_of_y_vec]
+    if len(pw) != length:
+        raise ValueError("power_of_y_vec must hold one power per generator")
+    y, cur = pw[0], 1
+    for x in pw:
+        cur = cur * y % r
+        if x != cur:
+            raise ValueError("power_of_y_vec must be [y, y^2, .., y^len]")
+    return y
+
+
 class WeightedInnerProductProof:
-    """Field holder, reference weighted_inner_product_proof.rs:25-33."""
+    """reference weighted_inner_product_proof.rs:25-33, with prove (:36-227) and verify (:238-328) on the engine's WIP
+    seam (include/bpp_amd.h, bpp_wip_prove_batch / bpp_wip_verify_batch)."""
 
     def __init__(self, L_vec, R_vec, A, B, r_prime, s_prime, d_prime):
         self.L_vec, self.R_vec, self.A, self.B = L_vec, R_vec, A, B
         self.r_prime, self.s_prime, self.d_prime = r_prime, s_prime, d_prime
+
+    @staticmethod
+    def _engine(pk, engine):
+        length = len(pk.G_vec)
+        if engine is None:   # a small engine of its own: only n m = len counts (n <= 64)
+            n = min(length, 64)
+            return BatchVerifier(pk, n, length // n, window_bits=4), True
+        if engine.n * engine.m != length:
+            raise AssertionError("the engine's key must hold len generators")
+        return engine, False
+
+    @classmethod
+    def prove(cls, pk, a_vec, b_vec, power_of_y_vec, gamma, commitment=None, engine=None) -> "WeightedInnerProductProof":
+        """WeightedInnerProductProof::prove with the reference's argument list (`commitment` is dead there, wip.rs:57, and
+        is ignored here); the reference's literal challenges and blinding"""
+        length = len(pk.G_vec)
+        if len(pk.H_vec) != length or len(a_vec) != length or len(b_vec) != length or length & (length - 1) or not length:
+            raise AssertionError("a_vec, b_vec and the key must have the same power-of-two length")   # wip.rs:60-67
+        y = _wip_y(pk.arith, power_of_y_vec, length)
+        eng, own = cls._engine(pk, engine)
+        try:
+            pts, sc, _ = eng.wip_prove_batch([a_vec], [b_vec], [y], [gamma])
+        finally:
+            if own:
+                eng.close()
+        k = eng.k
+        p = pts[0]
+        return cls(p[3:3 + k], p[3 + k:3 + 2 * k], p[1], p[2], sc[0, 0], sc[0, 1], sc[0, 2])
+
+    def verify(self, pk, power_of_y_vec, G_exp, H_exp, g_exp, V_exp, A_prime, V, engine=None) -> None:
+        """WeightedInnerProductProof::verify with the reference's argument list (the four *_exp_of_commitment arguments,
+        wip.rs:238-247).  Returns None for Ok(()); raises VerificationError."""
+        length = len(pk.G_vec)
+        if (1 << len(self.L_vec)) != length or len(self.R_vec) != len(self.L_vec):
+            raise VerificationError("VerificationError")                                              # wip.rs:335-337
+        if len(G_exp) != length or len(H_exp) != length or len(V_exp) != len(V):
+            raise AssertionError("statement exponents must match the key and V")                      # mulvec.rs:23-25
+        y = _wip_y(pk.arith, power_of_y_vec, length)
+        eng, own = self._engine(pk, engine)
+        try:
+            PW = pk.arith.PW
+            rec = np.concatenate([np.asarray(A_prime, dtype=np.uint64).reshape(1, PW), np.stack([self.A, self.B]),
+                                  np.asarray(self.L_vec, dtype=np.uint64).reshape(-1, PW),
+                                  np.asarray(self.R_vec, dtype=np.uint64).reshape(-1, PW),
+                                  np.asarray(V, dtype=np.uint64).reshape(-1, PW)]).astype(np.uint64)
+            sc = np.stack([scalar_to_wire(self.r_prime), scalar_to_wire(self.s_prime), scalar_to_wire(self.d_prime)])
+            stm = list(G_exp) + list(H_exp) + [g_exp] + list(V_exp)
+            ok = eng.wip_verify_batch(rec[None], sc[None], [y], [stm], nv=len(V))
+        finally:
+            if own:
+                eng.close()
+        if int(ok[0]) != 0:
+            raise VerificationError("VerificationError")
 
 
 class RangeProof:
@@ -908,6 +989,98 @@ class BatchVerifier:
                                                       d_out_V or None, d_workspace, workspace_bytes, stream or None),
               "bpp_range_prove_batch_device")
 
+    # ---- the WIP seam: WeightedInnerProductProof::{prove, verify} for any statement over this engine's key ----
+    def wip_prover_workspace_bytes(self, count: int) -> int:
+        return _lib.lib().bpp_wip_prover_workspace_bytes(self.handle, count)
+
+    def wip_verifier_workspace_bytes(self, count: int, nv: int) -> int:
+        return _lib.lib().bpp_wip_verifier_workspace_bytes(self.handle, count, nv)
+
+    def wip_points_per_proof(self, nv: int) -> int:
+        """wire points of a seam record [A', wip.A, wip.B, L.., R.., V_0..V_{nv-1}]"""
+        return 3 + 2 * self.k + nv
+
+    def wip_prove_device(self, d_a: int, d_b: int, d_y: int, d_gamma: int, count: int, nv: int, d_out_points: int,
+                         d_out_scalars: int, d_workspace: int, workspace_bytes: int, stream: int = 0, transcript: bool = False,
+                         d_transcript: int = 0, blind_key: bytes = None, index_base: int = 0, d_blinding: int = 0,
+                         d_out_challenges: int = 0):
+        """bpp_wip_prove_batch_device (include/bpp_amd.h): every buffer in HBM (raw device pointers), asynchronous on
+        `stream`.  Writes points 1 .. 2+2k of each record of 3 + 2k + nv wire points."""
+        check(_lib.lib().bpp_wip_prove_batch_device(self.handle, d_a, d_b, d_y, d_gamma, count, nv, 1 if transcript else 0,
+                                                    d_transcript or None, blind_key, index_base, d_blinding or None,
+                                                    d_out_points, d_out_scalars, d_out_challenges or None, d_workspace,
+                                                    workspace_bytes, stream or None), "bpp_wip_prove_batch_device")
+
+    def wip_verify_device(self, d_points: int, d_scalars: int, d_y: int, d_statement: int, nv: int, count: int, d_ok: int,
+                          d_workspace: int, workspace_bytes: int, stream: int = 0, transcript: bool = False,
+                          d_transcript: int = 0, d_challenges: int = 0, d_out_scalars: int = 0, d_out_result: int = 0):
+        """bpp_wip_verify_batch_device (include/bpp_amd.h): every buffer in HBM, asynchronous on `stream`"""
+        check(_lib.lib().bpp_wip_verify_batch_device(self.handle, d_points, d_scalars, d_y, d_statement, nv, count,
+                                                     1 if transcript else 0, d_transcript or None, d_challenges or None, d_ok,
+                                                     d_workspace, workspace_bytes, d_out_scalars or None,
+                                                     d_out_result or None, stream or None), "bpp_wip_verify_batch_device")
+
+    @staticmethod
+    def _wip_rows(rows, width: int) -> np.ndarray:
+        if isinstance(rows, np.ndarray) and rows.dtype == np.uint64:
+            return np.ascontiguousarray(rows).reshape(-1, width, 4)
+        out = np.zeros((len(rows), width, 4), dtype=np.uint64)
+        for i, row in enumerate(rows):
+            if len(row) != width:
+                raise ValueError("expected %d scalars per proof" % width)
+            out[i] = scalars_to_wire(list(row))
+        return out
+
+    def wip_prove_batch(self, a, b, y, gamma, nv: int = 0, points=None, transcript=None, blind_key: bytes = None,
+                        index_base: int = 0, blinding=None):
+        """WeightedInnerProductProof::prove for `count` statements over this engine's key (host arrays, synchronous).
+        a, b: (count, len) scalars; y, gamma: (count,) scalars.  points: None, or the (count, 3+2k+nv, PW) records to
+        write into (point 0 and the last nv are the caller's and come back untouched).  transcript: None (the reference's
+        literal challenges) or (count, 32) uint8 running transcript states.  blinding: None or (count, 5+2k) scalars.
+        -> (points, scalars (count, 3, 4), challenges (count, 1+k, 4) [e, e_1..e_k])"""
+        mn = self.n * self.m
+        av, bv = self._wip_rows(a, mn), self._wip_rows(b, mn)
+        count = av.shape[0]
+        yv, gv = scalars_to_wire(y).reshape(count, 4), scalars_to_wire(gamma).reshape(count, 4)
+        PW = self.arith.PW
+        npts = self.wip_points_per_proof(nv)
+        pts = (np.zeros((count, npts, PW), dtype=np.uint64) if points is None
+               else np.ascontiguousarray(points, dtype=np.uint64).reshape(count, npts, PW).copy())
+        tr = None if transcript is None else np.ascontiguousarray(transcript, dtype=np.uint8).reshape(count, 32)
+        bl = None if blinding is None else self._wip_rows(blinding, 5 + 2 * self.k)
+        sc = np.zeros((count, 3, 4), dtype=np.uint64)
+        ch = np.zeros((count, 1 + self.k, 4), dtype=np.uint64)
+        check(_lib.lib().bpp_wip_prove_batch(self.handle, _ptr(av), _ptr(bv), _ptr(yv), _ptr(gv), count, nv,
+                                             0 if tr is None else 1, _ptr(tr), blind_key, index_base, _ptr(bl), _ptr(pts),
+                                             _ptr(sc), _ptr(ch)), "bpp_wip_prove_batch")
+        return pts, sc, ch
+
+    def wip_verify_batch(self, points, scalars, y, statement, nv: int, transcript=None, challenges=None,
+                         want_scalars: bool = False, want_result: bool = False):
+        """WeightedInnerProductProof::verify for `count` proofs (host arrays, synchronous).  points: (count, 3+2k+nv, PW)
+        records [A', wip.A, wip.B, L.., R.., V..]; scalars: (count, 3, 4); y: (count,); statement: (count, 2 len + 1 + nv)
+        scalars [Gc, Hc, gc, Vc].  challenges: None or (count, 1+k) scalars [e, e_1..e_k].  -> ok (count,) u32, and with
+        want_scalars / want_result also the MulVec scalars (count, N, 4) / the sums (count, PW)"""
+        mn = self.n * self.m
+        PW = self.arith.PW
+        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, self.wip_points_per_proof(nv), PW)
+        count = pts.shape[0]
+        sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(count, 3, 4)
+        yv = scalars_to_wire(y).reshape(count, 4)
+        stm = self._wip_rows(statement, 2 * mn + 1 + nv)
+        if stm.shape[0] != count:
+            raise RuntimeError("wip_verify_batch: one statement per proof record")
+        tr = None if transcript is None else np.ascontiguousarray(transcript, dtype=np.uint8).reshape(count, 32)
+        ch = None if challenges is None else self._wip_rows(challenges, 1 + self.k)
+        ok = np.zeros(count, dtype=np.uint32)
+        osc = np.zeros((count, 2 * mn + 2 * self.k + 5 + nv, 4), dtype=np.uint64) if want_scalars else None
+        ores = np.zeros((count, PW), dtype=np.uint64) if want_result else None
+        check(_lib.lib().bpp_wip_verify_batch(self.handle, _ptr(pts), _ptr(sc), _ptr(yv), _ptr(stm), nv, count,
+                                              0 if tr is None else 1, _ptr(tr), _ptr(ch), _ptr(ok), _ptr(osc), _ptr(ores)),
+              "bpp_wip_verify_batch")
+        if want_scalars or want_result:
+            return ok, osc, ores
+        return ok
 
     # ---- proving blocks of mixed aggregation sizes: proof i has ms[i] values (include/bpp_amd.h) ----
     def prover_mixed_workspace_bytes(self, ms, serialized: bool = False) -> int:

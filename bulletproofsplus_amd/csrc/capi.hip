@@ -6,6 +6,7 @@
 #include "impl_msm.hpp"
 #include "impl_prove.hpp"
 #include "impl_verify.hpp"
+#include "impl_wip.hpp"
 
 using namespace bpp;
 
@@ -523,6 +524,93 @@ extern "C" int bpp_range_prove_batch_fs_device(bpp_verifier* engine, const uint6
                                                             d_out_V, true, d_out_challenges, d_workspace, workspace_bytes,
                                                             static_cast<hipStream_t>(stream), blind_key, index_base,
                                                             d_blinding);
+    });
+}
+
+// ---- the WIP seam (impl_wip.hpp) -------------------------------------------------------------------------
+// the argument checks the four entries share; 0: go on
+static int wip_args(size_t nv, int flags, bool have_transcript) {
+    if (nv > VS_MAXM) return fail(BPP_E_ARG, "nv exceeds the supported maximum (64)");
+    if (flags & ~BPP_SER_TRANSCRIPT) return fail(BPP_E_ARG, "unknown flag");
+    if ((flags & BPP_SER_TRANSCRIPT) && !have_transcript) return fail(BPP_E_ARG, "BPP_SER_TRANSCRIPT needs the transcript states");
+    return BPP_OK;
+}
+static int wip_blinding_args(int flags, const uint8_t* blind_key, const uint64_t* blinding) {
+    if (blind_key && blinding) return fail(BPP_E_ARG, "give blind_key or d_blinding, not both");
+    if ((blind_key || blinding) && !(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
+    return BPP_OK;
+}
+extern "C" size_t bpp_wip_prover_workspace_bytes(const bpp_verifier* engine, size_t count) {
+    if (count >> 32) return 0;
+    return size_for(engine, [&](auto cv) { return WipImpl<decltype(cv)>::prove_ws(engine, count).total; });
+}
+extern "C" size_t bpp_wip_verifier_workspace_bytes(const bpp_verifier* v, size_t count, size_t nv) {
+    if (nv > VS_MAXM || count > 0x7fffffffu / 64) return 0;
+    return size_for(v, [&](auto cv) { return WipImpl<decltype(cv)>::verify_ws(v, count, nv).total; });
+}
+extern "C" int bpp_wip_prove_batch_device(bpp_verifier* engine, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_y,
+                                          const uint64_t* d_gamma, size_t count, size_t nv, int flags, const void* d_transcript,
+                                          const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_blinding,
+                                          uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_challenges,
+                                          void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!engine || !d_a || !d_b || !d_y || !d_gamma || !d_out_points || !d_out_scalars || !d_workspace)
+        return fail(BPP_E_ARG, "null argument");
+    int rc = wip_args(nv, flags, d_transcript != nullptr);
+    if (!rc) rc = wip_blinding_args(flags, blind_key, d_blinding);
+    if (rc) return rc;
+    if (count == 0) return BPP_OK;
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
+        return WipImpl<decltype(cv)>::prove_device(engine, d_a, d_b, d_y, d_gamma, count, nv, (flags & BPP_SER_TRANSCRIPT) != 0,
+                                                   d_transcript, blind_key, index_base, d_blinding, d_out_points, d_out_scalars,
+                                                   d_out_challenges, d_workspace, workspace_bytes,
+                                                   static_cast<hipStream_t>(stream));
+    });
+}
+extern "C" int bpp_wip_verify_batch_device(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars,
+                                           const uint64_t* d_y, const uint64_t* d_statement, size_t nv, size_t count, int flags,
+                                           const void* d_transcript, const uint64_t* d_challenges, uint32_t* d_ok,
+                                           void* d_workspace, size_t workspace_bytes, uint64_t* d_out_scalars,
+                                           uint64_t* d_out_result, void* stream) {
+    if (!v || !d_points || !d_scalars || !d_y || !d_statement || !d_ok || !d_workspace) return fail(BPP_E_ARG, "null argument");
+    const int rc = wip_args(nv, flags, d_transcript || d_challenges);   // explicit challenges need no transcript
+    if (rc) return rc;
+    if (count == 0) return BPP_OK;
+    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    return on_ctx(v->ctx, [&](auto cv) -> int {
+        return WipImpl<decltype(cv)>::verify_device(v, d_points, d_scalars, d_y, d_statement, nv, count,
+                                                    (flags & BPP_SER_TRANSCRIPT) != 0, d_transcript, d_challenges, d_ok,
+                                                    d_workspace, workspace_bytes, d_out_scalars, d_out_result,
+                                                    static_cast<hipStream_t>(stream));
+    });
+}
+extern "C" int bpp_wip_prove_batch(bpp_verifier* engine, const uint64_t* a, const uint64_t* b, const uint64_t* y,
+                                   const uint64_t* gamma, size_t count, size_t nv, int flags, const void* transcript,
+                                   const uint8_t* blind_key, uint64_t index_base, const uint64_t* blinding, uint64_t* points,
+                                   uint64_t* out_scalars, uint64_t* out_challenges) {
+    if (!engine || !a || !b || !y || !gamma || !points || !out_scalars) return fail(BPP_E_ARG, "null argument");
+    int rc = wip_args(nv, flags, transcript != nullptr);
+    if (!rc) rc = wip_blinding_args(flags, blind_key, blinding);
+    if (rc) return rc;
+    if (count == 0) return BPP_OK;
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
+        return WipImpl<decltype(cv)>::prove_host(engine, a, b, y, gamma, count, nv, (flags & BPP_SER_TRANSCRIPT) != 0,
+                                                 (flags & BPP_SER_TRANSCRIPT) ? transcript : nullptr, blind_key, index_base,
+                                                 blinding, points, out_scalars, out_challenges);
+    });
+}
+extern "C" int bpp_wip_verify_batch(bpp_verifier* v, const uint64_t* points, const uint64_t* scalars, const uint64_t* y,
+                                    const uint64_t* statement, size_t nv, size_t count, int flags, const void* transcript,
+                                    const uint64_t* challenges, uint32_t* out_ok, uint64_t* out_scalars,
+                                    uint64_t* out_result) {
+    if (!v || !points || !scalars || !y || !statement || !out_ok) return fail(BPP_E_ARG, "null argument");
+    const int rc = wip_args(nv, flags, transcript || challenges);
+    if (rc) return rc;
+    if (count == 0) return BPP_OK;
+    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    return on_ctx(v->ctx, [&](auto cv) -> int {
+        const bool fs = (flags & BPP_SER_TRANSCRIPT) != 0 && !challenges;
+        return WipImpl<decltype(cv)>::verify_host(v, points, scalars, y, statement, nv, count, fs, fs ? transcript : nullptr,
+                                                  challenges, out_ok, out_scalars, out_result);
     });
 }
 

@@ -197,6 +197,7 @@ inline int make_shape(size_t n, size_t m, int c, const uint32_t* fr_modw, int fr
     s.c = (uint32_t)c;
     s.hgap = 0;
     s.glv = 0;
+    s.head_wip = m == 1 ? 1u : 0u;
     for (int j = 0; j < VS_MAXW; j++) {
         s.wc[j] = 0;
         s.went[j] = 0;

@@ -1,6 +1,7 @@
 // impl_verify.hpp -- the batch verifier (bpp_verifier_*): window tables in HBM + one pass of the hot path
 // over a device-resident batch.  One instantiation per curve (tu_verify_*.hip).
 #pragma once
+#include <functional>
 #include <memory>
 #include <mutex>
 
@@ -138,6 +139,14 @@ struct VerifyImpl {
                    d_out_result, st);
     }
 
+    // run() with the scalar stage left to the caller: scalars(w_sc, w_prep, w_bad, st) enqueues on st whatever writes the
+    // [count][s.N] MulVec scalars into w_sc (w_prep: ws_layout's per-proof scratch; w_bad: the invalid-proof flags, zeroed
+    // and already marked by the wire points).  run() passes the range statement's kernels, the WIP seam (impl_wip.hpp) its own.
+    using ScalarStage = std::function<int(uint32_t* w_sc, uint32_t* w_prep, uint32_t* w_bad, hipStream_t st)>;
+    static int run_stage(bpp_verifier* v, const VerifyShape& s, const uint64_t* d_points, size_t count,
+                         const ScalarStage& scalars, uint32_t* d_ok, void* d_workspace, size_t workspace_bytes,
+                         uint64_t* d_out_scalars, uint64_t* d_out_result, hipStream_t st);
+
     // form of the Horner stage for a pass over `count` proofs (k_fixed_msm's horner_tree: 0, 1 or 2)
     static uint32_t horner_form(const VerifyShape& s, size_t count) {
         const bool small_job = (double)count * ((double)s.NF * fixed_adds_per_generator(s) / 7.0e9 + 9.2e-8) < 2.0e-3;
@@ -175,6 +184,10 @@ struct VerifyImpl {
     static int begin_pass(bpp_verifier* v, const PassShape& ps, const uint64_t* d_points, const uint64_t* d_scalars,
                           size_t count, const uint64_t* d_challenges, uint8_t* ws, const Layout& L, uint32_t* w_sc,
                           std::unique_lock<std::mutex>& aux_lock, hipStream_t st, hipEvent_t* ev);
+    // ... up to the fork of the tables: everything that needs the points only
+    template <class Layout>
+    static int begin_points(bpp_verifier* v, const VerifyShape& s, const uint64_t* d_points, size_t count, uint8_t* ws,
+                            const Layout& L, std::unique_lock<std::mutex>& aux_lock, hipStream_t st, hipEvent_t* ev);
     // The weighted checks' middle (run_combined, grouped_begin): the weights, then -- after fixed_sums(w_wt), which enqueues
     // the caller's fixed-generator sums -- the weighted proof-point scalars, their digits and, once the tables have joined,
     // `per` window sums per proof (k_var_windows with `split`).  L: CombLayout or GroupLayout.
@@ -736,10 +749,8 @@ int VerifyImpl<C>::create(const bpp_ctx& ctx, const uint64_t* gh, const uint64_t
 
 template <class C>
 template <class Layout>
-int VerifyImpl<C>::begin_pass(bpp_verifier* v, const PassShape& ps, const uint64_t* d_points, const uint64_t* d_scalars,
-                              size_t count, const uint64_t* d_challenges, uint8_t* ws, const Layout& L, uint32_t* w_sc,
-                              std::unique_lock<std::mutex>& aux_lock, hipStream_t st, hipEvent_t* ev) {
-    const VerifyShape& s = ps.s;
+int VerifyImpl<C>::begin_points(bpp_verifier* v, const VerifyShape& s, const uint64_t* d_points, size_t count, uint8_t* ws,
+                                const Layout& L, std::unique_lock<std::mutex>& aux_lock, hipStream_t st, hipEvent_t* ev) {
     uint32_t* w_pts = reinterpret_cast<uint32_t*>(ws + L.pts);
     uint32_t* w_bad = reinterpret_cast<uint32_t*>(ws + L.bad);
     const size_t npts = count * s.NV;
@@ -752,8 +763,17 @@ int VerifyImpl<C>::begin_pass(bpp_verifier* v, const PassShape& ps, const uint64
     // that nothing else waits for yet -- so they are built on a side stream beside the scalar kernels and join before the
     // window sums.  For a lone batch both are latency bound; for a large one k_vs_prepare is (one lane per proof: 128 waves
     // for 8 192 proofs, 0.2 ms with the chip nearly empty) and the tables fill what it leaves.
-    int rc = fork_tables(v, st, w_pts, reinterpret_cast<uint32_t*>(ws + L.vtbl), reinterpret_cast<uint32_t*>(ws + L.vscr),
-                         npts, aux_lock);
+    return fork_tables(v, st, w_pts, reinterpret_cast<uint32_t*>(ws + L.vtbl), reinterpret_cast<uint32_t*>(ws + L.vscr), npts,
+                       aux_lock);
+}
+
+template <class C>
+template <class Layout>
+int VerifyImpl<C>::begin_pass(bpp_verifier* v, const PassShape& ps, const uint64_t* d_points, const uint64_t* d_scalars,
+                              size_t count, const uint64_t* d_challenges, uint8_t* ws, const Layout& L, uint32_t* w_sc,
+                              std::unique_lock<std::mutex>& aux_lock, hipStream_t st, hipEvent_t* ev) {
+    const VerifyShape& s = ps.s;
+    int rc = begin_points(v, s, d_points, count, ws, L, aux_lock, st, ev);
     if (rc) return rc;
     const uint32_t* ch = d_challenges ? reinterpret_cast<const uint32_t*>(d_challenges) : ps.challenges;
     const uint32_t ch_stride = d_challenges ? (3 + s.k) * 8 : 0;
@@ -814,6 +834,20 @@ int VerifyImpl<C>::run(bpp_verifier* v, const PassShape& ps, const uint64_t* d_p
                        size_t count, const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace,
                        size_t workspace_bytes, uint64_t* d_out_scalars, uint64_t* d_out_result, hipStream_t st) {
     const VerifyShape& s = ps.s;
+    const uint32_t* ch = d_challenges ? reinterpret_cast<const uint32_t*>(d_challenges) : ps.challenges;
+    const uint32_t ch_stride = d_challenges ? (3 + s.k) * 8 : 0;
+    return run_stage(v, s, d_points, count,
+                     [&](uint32_t* w_sc, uint32_t* w_prep, uint32_t*, hipStream_t st_) {
+                         return launch_verify_scalars<C>(s, reinterpret_cast<const uint32_t*>(d_scalars), ch, ch_stride, w_sc,
+                                                         count, w_prep, st_);
+                     },
+                     d_ok, d_workspace, workspace_bytes, d_out_scalars, d_out_result, st);
+}
+
+template <class C>
+int VerifyImpl<C>::run_stage(bpp_verifier* v, const VerifyShape& s, const uint64_t* d_points, size_t count,
+                             const ScalarStage& scalars, uint32_t* d_ok, void* d_workspace, size_t workspace_bytes,
+                             uint64_t* d_out_scalars, uint64_t* d_out_result, hipStream_t st) {
     const WsLayout L = ws_layout(s, count);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
@@ -830,8 +864,12 @@ int VerifyImpl<C>::run(bpp_verifier* v, const PassShape& ps, const uint64_t* d_p
     }
     v->last_blocks_per_proof = bpp_;
     std::unique_lock<std::mutex> aux_lock;
-    int rc = begin_pass(v, ps, d_points, d_scalars, count, d_challenges, ws, L, w_sc, aux_lock, st, ev);
+    int rc = begin_points(v, s, d_points, count, ws, L, aux_lock, st, ev);
     if (rc) return rc;
+    HIPCHK(mark(ev, 2 * BPP_STAGE_SCALARS, st));
+    rc = scalars(w_sc, reinterpret_cast<uint32_t*>(ws + L.prep), w_bad, st);
+    if (rc) return rc;
+    HIPCHK(mark(ev, 2 * BPP_STAGE_SCALARS + 1, st));
     // proof-point MSM: digits, per-point tables, window sums (all arithmetic bound, so they simply run in
     // sequence); its latency-bound Horner stage rides in the first blocks of the fixed-generator launch
     uint8_t* w_vd = ws + L.vdig;

@@ -1,0 +1,294 @@
+// impl_wip.hpp -- host side of the WIP seam (wip_seam.hpp): bpp_wip_prove_batch_device / bpp_wip_verify_batch_device and
+// their host-buffer forms, on an engine's tables.  One instantiation per curve (tu_wip_*.hip).
+//
+// The verifier is VerifyImpl::run_stage -- the pass prologue, layout carver, proof-point MSM, fixed-generator MulVec and
+// verdicts of bpp_verifier_run -- with the seam's two scalar kernels as its scalar stage and a pass shape of its own
+// (wip_verify_shape).  The prover runs the range prover's round / final / MulVec / collect kernels behind k_wip_init.
+#pragma once
+#include "impl_verify.hpp"
+#include "wip_seam.hpp"
+
+namespace bpp {
+
+constexpr uint32_t WIP_E_ROUND = 7, WIP_E_FINAL = 99;   // wip.rs:131 / :353, :211 / :369
+
+template <class C>
+struct WipImpl {
+    using V = VerifyImpl<C>;
+    static constexpr int WW = V::WW;
+    static constexpr int JW = V::JW;
+
+    // The pass shape of the seam's verifier on engine v: mn = len, m = nv statement points, NV = 3 + 2k + nv,
+    // N = 2 len + 2k + 5 + nv, head in the order of wip.rs:309-311.  It drives k_fixed_msm, k_var_* and k_finalize* as the
+    // engine's own shape does (same tables, same generators).
+    static VerifyShape verify_shape(const bpp_verifier* v, size_t nv) {
+        VerifyShape s = v->s;
+        s.m = (uint32_t)nv;
+        s.NV = 3 + 2 * s.k + (uint32_t)nv;
+        s.N = 2 * s.mn + 2 * s.k + 5 + (uint32_t)nv;
+        s.head_wip = 1;
+        return s;
+    }
+    // ... and of its prover: no commitments, so 2k + 3 virtual-proof slots of 2 len + 2k + 5 scalars (slot 0 unused)
+    static VerifyShape prove_shape(const bpp_verifier* v) { return verify_shape(v, 0); }
+
+    // ---- prover: workspace = the range prover's layout for the seam's shape | the chunk's px entries -----------------
+    struct ProveWs {
+        typename V::ProveLayout run;
+        size_t px, total;
+    };
+    static ProveWs prove_ws(const bpp_verifier* v, size_t count) {
+        ProveWs w;
+        w.run = V::prove_layout(prove_shape(v), count);
+        WsCarver o;
+        o.take(w.run.total);
+        w.px = o.take(w.run.chunk * (size_t)PX_WORDS * 4);
+        w.total = o.total;
+        return w;
+    }
+    static int prove_device(bpp_verifier* v, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_y,
+                            const uint64_t* d_gamma, size_t count, size_t nv, bool fs, const void* d_transcript,
+                            const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_blinding, uint64_t* d_out_points,
+                            uint64_t* d_out_scalars, uint64_t* d_out_challenges, void* d_workspace, size_t workspace_bytes,
+                            hipStream_t st);
+    static int prove_host(bpp_verifier* v, const uint64_t* a, const uint64_t* b, const uint64_t* y, const uint64_t* gamma,
+                          size_t count, size_t nv, bool fs, const void* transcript, const uint8_t* blind_key,
+                          uint64_t index_base, const uint64_t* blinding, uint64_t* points, uint64_t* out_scalars,
+                          uint64_t* out_challenges);
+
+    // ---- verifier: workspace = challenges derived from the transcript | the pass's workspace (ws_layout) ---------------
+    struct VerifyWs {
+        size_t ch, run, total;
+    };
+    static VerifyWs verify_ws(const bpp_verifier* v, size_t count, size_t nv) {
+        const VerifyShape s = verify_shape(v, nv);
+        VerifyWs w;
+        WsCarver o;
+        w.ch = o.take(count * (size_t)(1 + s.k) * 32);
+        w.run = o.take(V::ws_layout(s, count).total);
+        w.total = o.total;
+        return w;
+    }
+    static int verify_device(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, const uint64_t* d_y,
+                             const uint64_t* d_statement, size_t nv, size_t count, bool fs, const void* d_transcript,
+                             const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace, size_t workspace_bytes,
+                             uint64_t* d_out_scalars, uint64_t* d_out_result, hipStream_t st);
+    static int verify_host(bpp_verifier* v, const uint64_t* points, const uint64_t* scalars, const uint64_t* y,
+                           const uint64_t* statement, size_t nv, size_t count, bool fs, const void* transcript,
+                           const uint64_t* challenges, uint32_t* out_ok, uint64_t* out_scalars, uint64_t* out_result);
+};
+
+#ifdef BPP_IMPL_DEFINITIONS
+template <class C>
+int WipImpl<C>::prove_device(bpp_verifier* v, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_y,
+                             const uint64_t* d_gamma, size_t count, size_t nv, bool fs, const void* d_transcript,
+                             const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_blinding,
+                             uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_challenges, void* d_workspace,
+                             size_t workspace_bytes, hipStream_t st) {
+    const VerifyShape s = prove_shape(v);
+    const uint32_t k = s.k;
+    const uint32_t nvp = pb_num_vps(k, s.m);            // 2k + 3
+    const uint32_t rec_stride = 3 + 2 * k + (uint32_t)nv;
+    if ((count * rec_stride) >> 32) return fail(BPP_E_ARG, "count too large");
+    const ProveWs Lw = prove_ws(v, count);
+    if (workspace_bytes < Lw.total) return fail(BPP_E_ARG, "workspace too small");
+    const typename V::ProveLayout& L = Lw.run;
+    BlindKey bk;
+    load_key_words(blind_key, bk.w);
+    ProverConsts pc;
+    pc.alpha = 0;   // the range statement's; not read by the kernels of the seam
+    pc.d_L = 4;     // wip.rs:94
+    pc.d_R = 5;     // wip.rs:95
+    pc.r = 33;      // wip.rs:175-178
+    pc.s = 44;
+    pc.delta = 88;
+    pc.eta = 123;
+    const WipLiterals lit{WIP_E_ROUND, WIP_E_FINAL};
+    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+    auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    uint32_t* o_pts = reinterpret_cast<uint32_t*>(d_out_points);
+    uint32_t* o_sc = reinterpret_cast<uint32_t*>(d_out_scalars);
+    uint32_t* px = W(Lw.px);
+    for (size_t base = 0; base < count; base += L.chunk) {
+        const size_t cnt = std::min(L.chunk, count - base);
+        const unsigned lanes = cdiv(cnt, 64);
+        hipLaunchKernelGGL(k_wip_px, dim3(cdiv(cnt, 256)), dim3(256), 0, st, px, base, rec_stride, cnt);
+        const uint32_t* blind = nullptr;
+        if (d_blinding) {
+            blind = reinterpret_cast<const uint32_t*>(d_blinding) + base * (size_t)pb_blind_elems(k) * 8;
+        } else if (blind_key) {
+            hipLaunchKernelGGL(k_pb_blind<C>, dim3(cdiv(cnt * pb_blind_elems(k), 64)), dim3(64), 0, st, bk, index_base, k,
+                               W(L.blind), cnt, px);
+            blind = W(L.blind);
+        }
+        // one MulVec launch over `sel` of every proof's virtual proofs, then their wire points into the records
+        auto msm = [&](VpSel sel) {
+            const size_t n = cnt * sel.cnt;
+            const unsigned per = std::min(L.per, blocks_per_proof(s, n));
+            launch_fixed_msm<C, 2>((unsigned)(n * per), st, s, W(L.vps), v->table.u32(), W(L.part), per, 0u,
+                                   (const uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)0, 0u, sel);
+            const size_t f1 = n * per * (FIXED_BLOCK / FOLD_GROUP), f2 = f1 / FOLD_GROUP2;
+            hipLaunchKernelGGL(k_partials_fold<C>, dim3(cdiv(f1, 64)), dim3(64), 0, st, W(L.part), FOLD_GROUP, W(L.part1), f1);
+            hipLaunchKernelGGL(k_partials_fold<C>, dim3(cdiv(f2, 64)), dim3(64), 0, st, W(L.part1), FOLD_GROUP2, W(L.part2), f2);
+            hipLaunchKernelGGL(k_pb_collect<C>, dim3(cdiv(n, 64)), dim3(64), 0, st, s, sel, W(L.part2),
+                               per * (FIXED_BLOCK / FOLD_GROUP / FOLD_GROUP2), o_pts, (uint32_t*)nullptr, n, px);
+        };
+        hipLaunchKernelGGL(k_wip_init<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, lit, fs ? 1u : 0u,
+                           reinterpret_cast<const uint32_t*>(d_a) + base * (size_t)s.mn * 8,
+                           reinterpret_cast<const uint32_t*>(d_b) + base * (size_t)s.mn * 8,
+                           reinterpret_cast<const uint32_t*>(d_y) + base * 8,
+                           reinterpret_cast<const uint32_t*>(d_gamma) + base * 8, W(L.a), W(L.b), W(L.cG), W(L.cH), W(L.pwy),
+                           W(L.con), W(L.vps));
+        uint32_t* o_ch = d_out_challenges ? reinterpret_cast<uint32_t*>(d_out_challenges) + base * (size_t)(1 + k) * 8 : nullptr;
+        if (!fs) {
+            for (uint32_t t = 0; t < k; t++)
+                hipLaunchKernelGGL(k_pb_round<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, t, (uint32_t)PB_ALL, W(L.a),
+                                   W(L.b), W(L.cG), W(L.cH), W(L.pwy), W(L.con), W(L.vps));
+            hipLaunchKernelGGL(k_pb_final<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, (uint32_t)PB_ALL, W(L.a), W(L.b),
+                               W(L.cG), W(L.cH), W(L.con), W(L.vps), o_sc, px);
+            msm(VpSel{nvp, 1u, 2 * k + 2, 1u});   // L_t, R_t, wip.A, wip.B: the virtual proofs that exist
+            if (o_ch)
+                hipLaunchKernelGGL(k_wip_challenges_out<C>, dim3((unsigned)cnt), dim3(64), 0, st, k, lit, (const uint32_t*)nullptr,
+                                   o_ch);
+            continue;
+        }
+        hipLaunchKernelGGL(k_wip_fs_start<C>, dim3(lanes), dim3(64), 0, st, s, static_cast<const uint8_t*>(d_transcript) + base * 32,
+                           W(L.trst), cnt);
+        for (uint32_t t = 0; t < k; t++) {
+            hipLaunchKernelGGL(k_pb_round<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, t, (uint32_t)PB_PRE, W(L.a), W(L.b),
+                               W(L.cG), W(L.cH), W(L.pwy), W(L.con), W(L.vps));
+            msm(VpSel{nvp, 1 + 2 * t, 2u, 1u});   // L_t, R_t
+            hipLaunchKernelGGL(k_pb_fs_round<C>, dim3(lanes), dim3(64), 0, st, s, t, o_pts, W(L.trst), W(L.ch), W(L.con), cnt, px);
+            hipLaunchKernelGGL(k_pb_round<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, t, (uint32_t)PB_POST, W(L.a),
+                               W(L.b), W(L.cG), W(L.cH), W(L.pwy), W(L.con), W(L.vps));
+        }
+        hipLaunchKernelGGL(k_pb_final<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, (uint32_t)PB_PRE, W(L.a), W(L.b),
+                           W(L.cG), W(L.cH), W(L.con), W(L.vps), o_sc, px);
+        msm(VpSel{nvp, 2 * k + 1, 2u, 1u});       // wip.A, wip.B
+        hipLaunchKernelGGL(k_pb_fs_final<C>, dim3(lanes), dim3(64), 0, st, s, o_pts, W(L.trst), W(L.ch), W(L.con), cnt, px);
+        hipLaunchKernelGGL(k_pb_final<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, (uint32_t)PB_POST, W(L.a), W(L.b),
+                           W(L.cG), W(L.cH), W(L.con), W(L.vps), o_sc, px);
+        if (o_ch)
+            hipLaunchKernelGGL(k_wip_challenges_out<C>, dim3((unsigned)cnt), dim3(64), 0, st, k, lit, W(L.ch), o_ch);
+    }
+    HIPCHK(hipGetLastError());
+    return BPP_OK;
+}
+
+template <class C>
+int WipImpl<C>::verify_device(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, const uint64_t* d_y,
+                              const uint64_t* d_statement, size_t nv, size_t count, bool fs, const void* d_transcript,
+                              const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace, size_t workspace_bytes,
+                              uint64_t* d_out_scalars, uint64_t* d_out_result, hipStream_t st) {
+    const VerifyShape s = verify_shape(v, nv);
+    const VerifyWs L = verify_ws(v, count, nv);
+    if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
+    if (wvs_lds_bytes<C>(s) > 64 * 1024) return fail(BPP_E_ARG, "n*m too large for the seam's scalar kernels");
+    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+    const uint32_t* ch = reinterpret_cast<const uint32_t*>(d_challenges);   // the caller's own transcript comes first
+    if (!ch && fs) {
+        uint32_t* w_ch = reinterpret_cast<uint32_t*>(ws + L.ch);
+        hipLaunchKernelGGL(k_wip_transcript_challenges<C>, dim3(cdiv(count, 64)), dim3(64), 0, st, s,
+                           static_cast<const uint8_t*>(d_transcript), reinterpret_cast<const uint32_t*>(d_points), w_ch, count);
+        ch = w_ch;
+    }
+    const WipLiterals lit{WIP_E_ROUND, WIP_E_FINAL};
+    return V::run_stage(
+        v, s, d_points, count,
+        [&](uint32_t* w_sc, uint32_t* w_prep, uint32_t* w_bad, hipStream_t st_) -> int {
+            hipLaunchKernelGGL(k_wvs_prepare<C>, dim3(cdiv(count, 64)), dim3(64), 0, st_, s, lit,
+                               reinterpret_cast<const uint32_t*>(d_scalars), reinterpret_cast<const uint32_t*>(d_y),
+                               reinterpret_cast<const uint32_t*>(d_statement), ch, w_prep, w_sc, w_bad, count);
+            hipLaunchKernelGGL(k_wvs_expand<C>, dim3(cdiv(count, VS_PB)), dim3(VS_BLOCK), wvs_lds_bytes<C>(s), st_, s, w_prep,
+                               reinterpret_cast<const uint32_t*>(d_statement), w_sc, count);
+            HIPCHK(hipGetLastError());
+            return BPP_OK;
+        },
+        d_ok, ws + L.run, workspace_bytes - L.run, d_out_scalars, d_out_result, st);
+}
+
+// a host buffer of n bytes on the device (null: nothing)
+inline int wip_upload(const void* h, size_t n, DevBuf& d, hipStream_t st) {
+    if (!h) return BPP_OK;
+    HIPCHK(d.alloc(n));
+    if (n) HIPCHK(hipMemcpyAsync(d.p, h, n, hipMemcpyHostToDevice, st));
+    return BPP_OK;
+}
+
+template <class C>
+int WipImpl<C>::prove_host(bpp_verifier* v, const uint64_t* a, const uint64_t* b, const uint64_t* y, const uint64_t* gamma,
+                           size_t count, size_t nv, bool fs, const void* transcript, const uint8_t* blind_key,
+                           uint64_t index_base, const uint64_t* blinding, uint64_t* points, uint64_t* out_scalars,
+                           uint64_t* out_challenges) {
+    const VerifyShape s = prove_shape(v);
+    const uint32_t k = s.k;
+    hipStream_t st = nullptr;
+    const size_t pts_bytes = count * (size_t)(3 + 2 * k + nv) * WW * 4;
+    DevBuf da, db, dy, dg, dtr, dbl, dpts, dsc, dch, dws;
+    int rc;
+    if ((rc = wip_upload(a, count * (size_t)s.mn * 32, da, st))) return rc;
+    if ((rc = wip_upload(b, count * (size_t)s.mn * 32, db, st))) return rc;
+    if ((rc = wip_upload(y, count * 32, dy, st))) return rc;
+    if ((rc = wip_upload(gamma, count * 32, dg, st))) return rc;
+    if ((rc = wip_upload(transcript, count * 32, dtr, st))) return rc;
+    if ((rc = wip_upload(blinding, count * (size_t)pb_blind_elems(k) * 32, dbl, st))) return rc;
+    if ((rc = wip_upload(points, pts_bytes, dpts, st))) return rc;   // point 0 and the last nv of a record are the caller's
+    HIPCHK(dsc.alloc(count * 96));
+    if (out_challenges) HIPCHK(dch.alloc(count * (size_t)(1 + k) * 32));
+    const size_t wsb = prove_ws(v, count).total;
+    HIPCHK(dws.alloc(wsb));
+    rc = prove_device(v, static_cast<const uint64_t*>(da.p), static_cast<const uint64_t*>(db.p),
+                      static_cast<const uint64_t*>(dy.p), static_cast<const uint64_t*>(dg.p), count, nv, fs, dtr.p, blind_key,
+                      index_base, static_cast<const uint64_t*>(dbl.p), static_cast<uint64_t*>(dpts.p),
+                      static_cast<uint64_t*>(dsc.p), static_cast<uint64_t*>(dch.p), dws.p, wsb, st);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    HIPCHK(hipMemcpyAsync(points, dpts.p, pts_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out_scalars, dsc.p, count * 96, hipMemcpyDeviceToHost, st));
+    if (out_challenges) HIPCHK(hipMemcpyAsync(out_challenges, dch.p, count * (size_t)(1 + k) * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return BPP_OK;
+}
+
+template <class C>
+int WipImpl<C>::verify_host(bpp_verifier* v, const uint64_t* points, const uint64_t* scalars, const uint64_t* y,
+                            const uint64_t* statement, size_t nv, size_t count, bool fs, const void* transcript,
+                            const uint64_t* challenges, uint32_t* out_ok, uint64_t* out_scalars, uint64_t* out_result) {
+    const VerifyShape s = verify_shape(v, nv);
+    hipStream_t st = nullptr;
+    DevBuf dp, dsc, dy, dstm, dtr, dch, dok, dos, dres, dws;
+    int rc;
+    if ((rc = wip_upload(points, count * (size_t)s.NV * WW * 4, dp, st))) return rc;
+    if ((rc = wip_upload(scalars, count * 96, dsc, st))) return rc;
+    if ((rc = wip_upload(y, count * 32, dy, st))) return rc;
+    if ((rc = wip_upload(statement, count * (size_t)wip_statement_elems(s) * 32, dstm, st))) return rc;
+    if ((rc = wip_upload(transcript, count * 32, dtr, st))) return rc;
+    if ((rc = wip_upload(challenges, count * (size_t)(1 + s.k) * 32, dch, st))) return rc;
+    HIPCHK(dok.alloc(count * 4));
+    if (out_scalars) HIPCHK(dos.alloc(count * (size_t)s.N * 32));
+    if (out_result) HIPCHK(dres.alloc(count * (size_t)WW * 4));
+    const size_t wsb = verify_ws(v, count, nv).total;
+    HIPCHK(dws.alloc(wsb));
+    rc = verify_device(v, static_cast<const uint64_t*>(dp.p), static_cast<const uint64_t*>(dsc.p),
+                       static_cast<const uint64_t*>(dy.p), static_cast<const uint64_t*>(dstm.p), nv, count, fs, dtr.p,
+                       static_cast<const uint64_t*>(dch.p), static_cast<uint32_t*>(dok.p), dws.p, wsb,
+                       static_cast<uint64_t*>(dos.p), static_cast<uint64_t*>(dres.p), st);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    HIPCHK(hipMemcpyAsync(out_ok, dok.p, count * 4, hipMemcpyDeviceToHost, st));
+    if (out_scalars) HIPCHK(hipMemcpyAsync(out_scalars, dos.p, count * (size_t)s.N * 32, hipMemcpyDeviceToHost, st));
+    if (out_result) HIPCHK(hipMemcpyAsync(out_result, dres.p, count * (size_t)WW * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return BPP_OK;
+}
+#endif  // BPP_IMPL_DEFINITIONS
+
+extern template struct WipImpl<Bls12381>;
+extern template struct WipImpl<Secp256k1>;
+extern template struct WipImpl<Ed25519>;
+
+}  // namespace bpp

@@ -374,6 +374,10 @@ struct VerifyShape {
     uint32_t glv;
     uint8_t wc[VS_MAXW];
     uint32_t went[VS_MAXW];
+    // order of the three head points of the MulVec (var_term_index): 1 = [wip.B, wip.A, A'] as WeightedInnerProductProof::
+    // verify assembles it (wip.rs:309-311) -- the m == 1 range statement and every pass of the WIP seam (wip_seam.hpp) --,
+    // 0 = [A, wip.A, wip.B] (range/mod.rs:492-494, m > 1)
+    uint32_t head_wip;
 };
 
 // Fixed-generator sums through the curve's endomorphism (BLS12-381 G1): a scalar is split into two signed halves of 127
@@ -406,9 +410,9 @@ __host__ __device__ __forceinline__ uint32_t fixed_term_index(const VerifyShape&
 }
 // index, in the MulVec, of proof-dependent point v of a proof record [A, wip.A, wip.B, L.., R.., V..].
 // The head of the MulVec is [A, wip.A, wip.B] for m > 1 (range/mod.rs:492-494) but [wip.B, wip.A, A]
-// for m == 1 (wip.rs:309-311).
+// for m == 1 (wip.rs:309-311): VerifyShape::head_wip.
 __host__ __device__ __forceinline__ uint32_t var_term_index(const VerifyShape& s, uint32_t v) {
-    if (v < 3) return s.m == 1 ? 2 - v : v;
+    if (v < 3) return s.head_wip ? 2 - v : v;
     if (v < 3 + 2 * s.k) return 5 + (v - 3);
     return 5 + 2 * s.k + 2 * s.mn + (v - 3 - 2 * s.k);
 }

@@ -592,6 +592,70 @@ int bpp_range_prove_batch_serialized_mixed(bpp_verifier *engine, const uint64_t 
                                            size_t count, int flags, const uint8_t *blind_key, uint64_t index_base,
                                            uint8_t *out_proofs, uint8_t *out_commitments);
 
+/* ---- the weighted inner product argument as a seam of its own: WeightedInnerProductProof::{prove, verify} ----
+ * Reference: src/weighted_inner_product_proof.rs:36-227 (prove), :238-328 (verify), :330-382 (verification_scalars).
+ * An engine created for (n, m) proves and verifies the WIP relation over its key for ANY statement that ends in one; only
+ * len = n m counts, k = log2(len):
+ *     P = sum a_i G_i + sum b_i H_i + (sum a_i b_i y^(i+1)) g + gamma h
+ * power_of_y_vec is [y, y^2, .., y^len] (exp_iter_type2(y, len)): the reference's verify reads only its first entry and
+ * rebuilds the rest (:252, :276) and both callers of its prove pass exactly this vector, so the seam takes the one scalar y
+ * per proof.  prove's `commitment` argument is dead in the reference (:57, :137-142) and is not taken.
+ *
+ * The record of a proof is the one bpp_verifier_run reads: [A', wip.A, wip.B, L_0.., R_0.., V_0..V_{nv-1}], 3 + 2k + nv wire
+ * points, 0 <= nv <= 64 (nv need not be a power of two).  The PROVER writes points 1 .. 2 + 2k of every record and leaves
+ * point 0 and the last nv alone: the caller, who knows A' and V, fills them, and the prover's output is the verifier's input.
+ *   d_a, d_b         : count x len scalars          d_y, d_gamma : count scalars (scalars >= r are reduced)
+ *   d_out_scalars    : count x 3 scalars [r', s', delta']
+ *   flags            : 0: the reference's literals (e_t = 7, e = 99; d_L, d_R = 4, 5; r, s, delta, eta = 33, 44, 88, 123).
+ *                      BPP_SER_TRANSCRIPT: the argument continues a transcript the CALLER owns: d_transcript holds 32 bytes
+ *                      per proof, the running SHA-256 state of csrc/transcript.hpp after the caller absorbed its statement
+ *                      and drew y.  The engine appends dsep "wipp v1\0" and n = len (u64), per round L_t, R_t and draws e_t,
+ *                      then wA, wB and draws e.  d_transcript is ignored without the flag.
+ *   blinding         : d_blinding, count x (5 + 2k) scalars [unused, r, s, delta, eta, d_L[0..k), d_R[0..k)] (slot 0 is
+ *                      ignored), or blind_key (32 bytes, host) expanded with index_base + i as bpp_range_prove_batch_fs_device
+ *                      does, or -- both NULL -- the literals.  Blinding without BPP_SER_TRANSCRIPT, or both sources, is
+ *                      BPP_E_ARG.
+ *   d_out_challenges : NULL, or count x (1 + k) scalars [e, e_1..e_k] as drawn
+ * y = 0 (mod r) has no inverse: the prover's output for that proof is unspecified (its neighbours are not disturbed).
+ *
+ * The VERIFIER takes the statement as the four *_exp_of_commitment arguments of :238-247,
+ *   d_statement      : count x (2 len + 1 + nv) scalars [Gc (len), Hc (len), gc, Vc (nv)]
+ * and checks the MulVec of :298-320 in the reference's order,
+ *   scalars [1, e, e^2, g_exp, h_exp, e_j^2 e^2 (k), e_j^-2 e^2 (k), G_exp (len), H_exp (len), V_exp (nv)]
+ *   points  [B, A, A', g, h, L.., R.., G_vec, H_vec, V..]
+ *   G_exp[i] = -s[i] y^-(i+1) r' e y + Gc[i] e^2        H_exp[i] = -s[len-1-i] s' e + Hc[i] e^2
+ *   g_exp = -r' y s' + gc e^2        h_exp = -delta'        V_exp[j] = Vc[j] e^2        (s[i]: :372-380)
+ * d_ok[i] = 0 iff the sum is the identity (ristretto255: the engine's class test); a proof with y = 0 gets 1.
+ *   d_challenges     : NULL, or count x (1 + k) scalars [e, e_1..e_k] for a caller with a transcript of its own; it takes
+ *                      precedence over flags.  Otherwise BPP_SER_TRANSCRIPT derives them from d_transcript and the record.
+ *   d_out_scalars    : NULL, or count x N scalars, N = 2 len + 2k + 5 + nv, in MulVec order; d_out_result: NULL, or the sum
+ *                      per proof -- both as for bpp_verifier_run, as is bpp_verifier_set_subgroup_check.
+ * Both device calls only enqueue on `stream` (no host synchronisation, no host-side upload).  Errors: BPP_E_ARG for a NULL
+ * required pointer, nv > 64, a workspace that is too small, BPP_SER_TRANSCRIPT without d_transcript, the blinding rules, an
+ * unknown flag; nothing is enqueued or written then.  count = 0 is BPP_OK.  The size calls return 0 for arguments that are
+ * not taken.  Kernels: k_wip_init, k_wvs_prepare / k_wvs_expand, k_wip_transcript_challenges (csrc/wip_seam.hpp); everything
+ * else is the range passes' own. */
+size_t bpp_wip_prover_workspace_bytes(const bpp_verifier *engine, size_t count);
+int bpp_wip_prove_batch_device(bpp_verifier *engine, const uint64_t *d_a, const uint64_t *d_b, const uint64_t *d_y,
+                               const uint64_t *d_gamma, size_t count, size_t nv, int flags, const void *d_transcript,
+                               const uint8_t *blind_key, uint64_t index_base, const uint64_t *d_blinding,
+                               uint64_t *d_out_points, uint64_t *d_out_scalars, uint64_t *d_out_challenges, void *d_workspace,
+                               size_t workspace_bytes, void *stream);
+size_t bpp_wip_verifier_workspace_bytes(const bpp_verifier *v, size_t count, size_t nv);
+int bpp_wip_verify_batch_device(bpp_verifier *v, const uint64_t *d_points, const uint64_t *d_scalars, const uint64_t *d_y,
+                                const uint64_t *d_statement, size_t nv, size_t count, int flags, const void *d_transcript,
+                                const uint64_t *d_challenges, uint32_t *d_ok, void *d_workspace, size_t workspace_bytes,
+                                uint64_t *d_out_scalars, uint64_t *d_out_result, void *stream);
+/* Both on HOST buffers, synchronous.  `points` of the prover is read AND written: count x (3 + 2k + nv) wire points whose
+ * point 0 and last nv come back as they went in.  blinding, out_challenges, out_scalars (verify), out_result may be NULL. */
+int bpp_wip_prove_batch(bpp_verifier *engine, const uint64_t *a, const uint64_t *b, const uint64_t *y, const uint64_t *gamma,
+                        size_t count, size_t nv, int flags, const void *transcript, const uint8_t *blind_key,
+                        uint64_t index_base, const uint64_t *blinding, uint64_t *points, uint64_t *out_scalars,
+                        uint64_t *out_challenges);
+int bpp_wip_verify_batch(bpp_verifier *v, const uint64_t *points, const uint64_t *scalars, const uint64_t *y,
+                         const uint64_t *statement, size_t nv, size_t count, int flags, const void *transcript,
+                         const uint64_t *challenges, uint32_t *out_ok, uint64_t *out_scalars, uint64_t *out_result);
+
 /* Frames a bare byte stream of concatenated containers (host memory; no device, no context): m_of[i] = the m of container
  * i, whose length its header implies (n, m, k, version).  BPP_OK with *out_count containers when the stream is consumed
  * exactly (an empty stream: 0).  Otherwise a negative code, *out_count = the containers before the offending one, and

@@ -10,7 +10,7 @@
 //   bpp::PublicKey{g,h,G_vec,H_vec}            publickey.rs:13-52
 //   bpp::RangeProver{v_vec,gamma_vec,commitment_vec}   range/prover.rs:13-42
 //   bpp::RangeVerifier{commitment_vec}.allocate()       README.md:47-48 (no code in the reference)
-//   bpp::WeightedInnerProductProof             weighted_inner_product_proof.rs:25-33
+//   bpp::WeightedInnerProductProof::prove / verify      weighted_inner_product_proof.rs:25-33, :36-227, :238-328
 //   bpp::RangeProof{A, proof}::prove / verify  range/mod.rs:25-78
 //   bpp::ProofError::VerificationError         errors.rs:14-50
 //
@@ -170,10 +170,102 @@ struct RangeVerifier {
     void allocate(const std::vector<Point>& commitments) { commitment_vec = commitments; }
 };
 
+// WeightedInnerProductProof with prove (weighted_inner_product_proof.rs:36-227) and verify (:238-328) on the engine's WIP
+// seam (bpp_amd.h, bpp_wip_prove_batch / bpp_wip_verify_batch).  power_of_y_vec must be [y, y^2, .., y^len]: as the
+// reference's verify (:252, :276) only its first entry is read, the engine rebuilds the rest.  engine: an engine created
+// for this key (bpp_verifier_create, n m = len); null: a small one (window_bits 4) is created for the call.
 struct WeightedInnerProductProof {
     std::vector<Point> L_vec, R_vec;
     Point A, B;
     PrimeFieldElem r_prime, s_prime, d_prime;
+
+    // `commitment` is dead in the reference (:57, :137-142) and is ignored
+    static WeightedInnerProductProof prove(const PublicKey& pk, const std::vector<PrimeFieldElem>& a_vec,
+                                           const std::vector<PrimeFieldElem>& b_vec,
+                                           const std::vector<PrimeFieldElem>& power_of_y_vec, const PrimeFieldElem& gamma,
+                                           const Point& commitment, bpp_verifier* engine = nullptr) {
+        (void)commitment;
+        const size_t len = pk.G_vec.size(), pw = Arith::point_words();
+        if (pk.H_vec.size() != len || a_vec.size() != len || b_vec.size() != len || power_of_y_vec.size() != len ||
+            len == 0 || (len & (len - 1)))
+            throw std::logic_error("assertion failed: vectors of one power-of-two length");              // :60-67
+        size_t k = 0;
+        while (((size_t)1 << k) < len) k++;
+        Engine eng(pk, engine);
+        std::vector<uint64_t> a = flat(a_vec), b = flat(b_vec), pts((3 + 2 * k) * pw), sc(12);
+        if (bpp_wip_prove_batch(eng.e, a.data(), b.data(), power_of_y_vec[0].e.data(), gamma.e.data(), 1, 0, 0, nullptr,
+                                nullptr, 0, nullptr, pts.data(), sc.data(), nullptr) != BPP_OK)
+            throw std::runtime_error(std::string("bpp_wip_prove_batch: ") + bpp_last_error());
+        WeightedInnerProductProof p;
+        p.A = Point(pts.data() + pw);
+        p.B = Point(pts.data() + 2 * pw);
+        for (size_t i = 0; i < k; i++) {
+            p.L_vec.emplace_back(pts.data() + (3 + i) * pw);
+            p.R_vec.emplace_back(pts.data() + (3 + k + i) * pw);
+        }
+        p.r_prime = PrimeFieldElem::from_limbs(sc.data());
+        p.s_prime = PrimeFieldElem::from_limbs(sc.data() + 4);
+        p.d_prime = PrimeFieldElem::from_limbs(sc.data() + 8);
+        return p;
+    }
+
+    // Ok(()) -> std::nullopt ; Err(ProofError::VerificationError) -> the error; the four *_exp arguments are the
+    // *_exp_of_commitment of :238-247
+    std::optional<ProofError> verify(const PublicKey& pk, const std::vector<PrimeFieldElem>& power_of_y_vec,
+                                     const std::vector<PrimeFieldElem>& G_exp, const std::vector<PrimeFieldElem>& H_exp,
+                                     const PrimeFieldElem& g_exp, const std::vector<PrimeFieldElem>& V_exp,
+                                     const Point& A_prime, const std::vector<Point>& V, bpp_verifier* engine = nullptr) const {
+        const size_t len = pk.G_vec.size(), k = L_vec.size();
+        if (len != ((size_t)1 << k) || R_vec.size() != k) return ProofError::VerificationError;            // :335-337
+        if (G_exp.size() != len || H_exp.size() != len || V_exp.size() != V.size() || power_of_y_vec.size() != len)
+            throw std::logic_error("mulvec: lengths of scalars and points must match");                    // mulvec.rs:23-25
+        Engine eng(pk, engine);
+        std::vector<uint64_t> pts(A_prime.w);
+        pts.insert(pts.end(), A.w.begin(), A.w.end());
+        pts.insert(pts.end(), B.w.begin(), B.w.end());
+        for (auto& p : L_vec) pts.insert(pts.end(), p.w.begin(), p.w.end());
+        for (auto& p : R_vec) pts.insert(pts.end(), p.w.begin(), p.w.end());
+        for (auto& p : V) pts.insert(pts.end(), p.w.begin(), p.w.end());
+        std::vector<uint64_t> stm = flat(G_exp), h = flat(H_exp), vc = flat(V_exp);
+        stm.insert(stm.end(), h.begin(), h.end());
+        stm.insert(stm.end(), g_exp.e.begin(), g_exp.e.end());
+        stm.insert(stm.end(), vc.begin(), vc.end());
+        uint64_t sc[12];
+        std::memcpy(sc, r_prime.e.data(), 32);
+        std::memcpy(sc + 4, s_prime.e.data(), 32);
+        std::memcpy(sc + 8, d_prime.e.data(), 32);
+        uint32_t ok = 1;
+        if (bpp_wip_verify_batch(eng.e, pts.data(), sc, power_of_y_vec[0].e.data(), stm.data(), V.size(), 1, 0, nullptr,
+                                 nullptr, &ok, nullptr, nullptr) != BPP_OK)
+            throw std::runtime_error(std::string("bpp_wip_verify_batch: ") + bpp_last_error());
+        if (ok == 0) return std::nullopt;
+        return ProofError::VerificationError;
+    }
+
+  private:
+    static std::vector<uint64_t> flat(const std::vector<PrimeFieldElem>& v) {
+        std::vector<uint64_t> o;
+        for (auto& x : v) o.insert(o.end(), x.e.begin(), x.e.end());
+        return o;
+    }
+    // the caller's engine, or one of its own for the length of the key (only n m = len counts; n <= 64)
+    struct Engine {
+        bpp_verifier* e;
+        bool own;
+        Engine(const PublicKey& pk, bpp_verifier* given) : e(given), own(false) {
+            if (e) return;
+            const size_t len = pk.G_vec.size(), n = len < 64 ? len : 64;
+            auto gh = pk.gh_wire(), G = PublicKey::flat(pk.G_vec), H = PublicKey::flat(pk.H_vec);
+            if (bpp_verifier_create(Arith::ctx(), gh.data(), G.data(), H.data(), n, len / n, 4, &e) != BPP_OK)
+                throw std::runtime_error(std::string("bpp_verifier_create: ") + bpp_last_error());
+            own = true;
+        }
+        Engine(const Engine&) = delete;
+        Engine& operator=(const Engine&) = delete;
+        ~Engine() {
+            if (own) bpp_verifier_destroy(e);
+        }
+    };
 };
 
 struct RangeProof {
