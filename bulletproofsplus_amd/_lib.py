@@ -196,6 +196,10 @@ def lib():
         L.bpp_wip_verify_batch.argtypes = [vp, vp, vp, vp, vp, sz, sz, i32, vp, vp, vp, vp, vp]
         L.bpp_debug_field_op.argtypes = [vp, i32, i32, vp, vp, sz, vp]
         L.bpp_debug_point_op.argtypes = [vp, i32, vp, vp, sz, vp]
+        # the raw-image hooks of csrc/tu_debug.hip (like the two above: not declared in include/bpp_amd.h)
+        L.bpp_debug_field_raw_op.argtypes = [vp, i32, i32, vp, vp, vp, vp, sz, vp]
+        L.bpp_debug_madd_lazy_raw.argtypes = [vp, vp, vp, vp, sz, vp]
+        L.bpp_debug_glv_op.argtypes = [vp, i32, i32, vp, sz, vp, vp]
         _lib = L
     return _lib
 

@@ -1334,6 +1334,8 @@ extern "C" int bpp_range_prove_batch_serialized_mixed(bpp_verifier* engine, cons
 }
 
 // ---- device-side unit-test hooks (tests/ check the device field / group primitives against a CPU checker) --
+// (their raw-image siblings bpp_debug_field_raw_op, bpp_debug_madd_lazy_raw and bpp_debug_glv_op live in tu_debug.hip,
+// a translation unit of their own)
 // field: 0 = base field, 1 = scalar field; op: 0 mul, 1 add, 2 sub, 3 inv, 4 sqr, 5 neg
 // a, b, out: n elements of N 32-bit words (N = 12 for BLS12-381 Fp, else 8), host pointers
 extern "C" int bpp_debug_field_op(bpp_ctx* ctx, int field, int op, const uint32_t* a, const uint32_t* b, size_t n,

@@ -16,9 +16,12 @@
 // Why 30-bit limbs: the only wide multiplier on gfx950 is v_mad_u64_u32 (32x32+64 -> 64).  It has a
 // carry-OUT but no carry-IN, and on gfx90a+/gfx950 a VALU carry written to VCC/SGPR needs two wait
 // states before a VALU instruction may read it, so a saturated 32-bit-limb schedule costs >= 3 issue
-// slots per limb product.  With 30-bit limbs a 64-bit column accumulator absorbs all NL <= 13
-// products of a column (13 * 2^60 < 2^64) with no carry handling at all: one v_mad_u64_u32 per limb
-// product, plus one shift + one mask per column.  No MFMA: there is no carry chain in the matrix pipe.
+// slots per limb product.  With 30-bit limbs a 64-bit column accumulator absorbs up to 15 limb products
+// and a carry (15 (2^30 - 1)^2 + 2^36 < 2^64) with no carry handling at all: one v_mad_u64_u32 per limb
+// product, plus one shift + one mask per column.  A column of ONE product of two elements has at most
+// NL <= 13 of them; the two-product form fe_mul_add has up to 2 NL = 26 and therefore runs its middle columns
+// in two accumulators (fe_fused_column, which asserts the count of every accumulator at compile time).
+// No MFMA: there is no carry chain in the matrix pipe.
 #pragma once
 #include <stdint.h>
 #include <type_traits>
@@ -362,13 +365,15 @@ __device__ __forceinline__ void chain_barrier_ops(uint64_t& accB, uint64_t& accA
         BPP_PIN_CASES(BPP_L13(x))
     }
 }
+// the two-product form: its second plain-product chain accC rides in the same statement
 template <int NL, int CNT>
-__device__ __forceinline__ void chain_barrier_ops(uint64_t& accB, uint64_t& accA, uint32_t* m, uint32_t* x, uint32_t* y) {
+__device__ __forceinline__ void chain_barrier_ops(uint64_t& accB, uint64_t& accA, uint64_t& accC, uint32_t* m, uint32_t* x,
+                                                  uint32_t* y) {
     static_assert((NL == 9 || NL == 13) && CNT >= 0 && CNT <= 13, "limb counts of the fields in use");
     if constexpr (NL == 9) {
-        BPP_PIN_CASES(BPP_L9(x), BPP_L9(y))
+        BPP_PIN_CASES("+v"(accC), BPP_L9(x), BPP_L9(y))
     } else {
-        BPP_PIN_CASES(BPP_L13(x), BPP_L13(y))
+        BPP_PIN_CASES("+v"(accC), BPP_L13(x), BPP_L13(y))
     }
 }
 #else
@@ -379,7 +384,7 @@ BPP_HD void chain_barrier_m(uint64_t&, uint32_t*) {}
 template <int NL, int CNT>
 BPP_HD void chain_barrier_ops(uint64_t&, uint64_t&, uint32_t*, uint32_t*) {}
 template <int NL, int CNT>
-BPP_HD void chain_barrier_ops(uint64_t&, uint64_t&, uint32_t*, uint32_t*, uint32_t*) {}
+BPP_HD void chain_barrier_ops(uint64_t&, uint64_t&, uint64_t&, uint32_t*, uint32_t*, uint32_t*) {}
 #endif
 
 // Montgomery reduction of a 2*NL-limb product T (limbs < 2^31): returns T * R^-1 mod p.
@@ -432,16 +437,26 @@ BPP_HD void fe_mul_wide(const Fe<P>& a, const Fe<P>& b, uint32_t* T) {
 
 // ---- fused product + Montgomery reduction ------------------------------------------------------------------
 // fe_mul / fe_sqr / fe_mul_add run the product and its reduction in ONE pass over the 2 NL columns.  Column k
-// receives na(k) = min(k, 2NL-2-k) + 1 plain products (W times that for the two-product form) and nm(k) =
-// (k < NL ? k + 1 : 2NL-1-k) products m_i p_j of the reduction.  Where W na + nm <= 15 -- the outer columns --
-// they all fit one 64-bit accumulator (15 * 2^60 + carry < 2^64), so the column needs no intermediate limb
-// T[k] at all: no mask, no second shift, no re-entry of T[k] into the reduction chain.  Only the middle
-// columns (k = 7..17 of 26 for the 13-limb field, k = 7..9 of 18 for the 9-limb fields) would overflow; there
-// the plain products run in a second accumulator whose limb enters the reduction chain as T * 1 (one
-// multiply-add).  Per 13-limb product: 338 + 11 v_mad_u64_u32, 37 masks, 37 64-bit shifts, 13 v_mul_lo_u32,
-// against 338 v_mad + 60 v_lshl_add_u64 + 48 shifts + 51 masks + 25 v_mov + 13 v_mul_lo of the two-pass form
-// as the compiler scheduled it.
-//   col(k, acc): adds the plain products of column k (k <= 2NL-2) to acc.
+// receives na(k) = min(k, 2NL-2-k) + 1 plain products per product of two elements (W na(k) for the W-product form)
+// and nm(k) = (k < NL ? k + 1 : 2NL-1-k) products m_i p_j of the reduction.  A 64-bit accumulator holds 15 products
+// of normalised limbs and the carries of all three chains, each < 2^34 (15 (2^30 - 1)^2 + 2^36 < 2^64), whatever the
+// limbs are, and no more.  So:
+//   * FUSED columns, W na + nm <= 15 -- the outer ones: everything goes into the reduction chain accB, and the
+//     column needs no intermediate limb T[k] at all: no mask, no second shift, no re-entry of T[k] into the chain.
+//   * SPLIT columns, W na + nm > 15 but W na <= 15 (k = 7..17 of 26 for one 13-limb product, k = 7..9 of 18 for one
+//     9-limb product; k = 5, 6 and 18, 19 resp. k = 5, 6 and 10, 11 of the two-product form): the plain products run in
+//     a second accumulator accA, a chain of its own, whose limb enters the reduction chain as T * 1.
+//   * DUAL columns, W na > 15 -- only the two-product form has them (na >= 8: k = 7..17 for 13 limbs, k = 7..9 for 9):
+//     the products of a b run in accA and those of c d in a third chain accC, at most NL <= 13 each; the sum of the
+//     two limbs (< 2^31) enters the reduction chain as one T * 1.  Until this was done the 26 products of a middle
+//     column shared accA and overflowed it for large limbs (BLS12-381 Fp, a = b = c = d = 2^360 - 1); the 9-limb
+//     fields happened to fit only because their top limb is short, which nothing here relies on any more.
+// The static_asserts of fe_fused_column hold every accumulator of every instantiation to these counts.
+// Per 13-limb product: 338 + 11 v_mad_u64_u32, 37 masks, 37 64-bit shifts, 13 v_mul_lo_u32, against 338 v_mad +
+// 60 v_lshl_add_u64 + 48 shifts + 51 masks + 25 v_mov + 13 v_mul_lo of the two-pass form as the compiler scheduled
+// it.  The dual columns add 11 masks, 11 shifts and 11 32-bit adds to the 13-limb fe_mul_add (3 each for 9 limbs).
+//   col(k, acc, part): adds the plain products of column k (k <= 2NL-2) to acc; part (an integral_constant) is -1 for
+//   all of them, 0 / 1 for those of the first / second product alone (dual columns).
 // acc += a * b, and acc += a * k for a limb k of the modulus.
 // Tried and not kept (-DBPP_ASM_MAD): every multiply-add as inline asm pins the chain order completely (no
 // reassociation, no 64-bit merge adds) but the compiler pads almost every asm statement with an s_nop (it must assume
@@ -474,25 +489,48 @@ BPP_HD void fe_mad_k(uint64_t& acc, uint32_t a, uint32_t k) {
     acc += (uint64_t)a * k;
 }
 
+// shape of column k: plain products per product of two elements, reduction products, and how the column is run
+constexpr int fused_na(int NL, int k) { return k <= 2 * NL - 2 ? (k < 2 * NL - 2 - k ? k : 2 * NL - 2 - k) + 1 : 0; }
+constexpr int fused_nm(int NL, int k) { return k < NL ? k + 1 : 2 * NL - 1 - k; }
+constexpr int COL_FUSED = 0, COL_SPLIT = 1, COL_DUAL = 2, ACC_MAX_PRODUCTS = 15;
+constexpr int fused_kind(int NL, int W, int k) {
+    return W * fused_na(NL, k) + fused_nm(NL, k) <= ACC_MAX_PRODUCTS ? COL_FUSED
+           : W * fused_na(NL, k) <= ACC_MAX_PRODUCTS                 ? COL_SPLIT
+                                                                     : COL_DUAL;
+}
+
 template <class P, int W, int K, class ColFn, class PinFn>
-BPP_HD void fe_fused_column(ColFn& col, PinFn& pin, uint64_t& accA, uint64_t& accB, uint32_t* m, Fe<P>& r, uint32_t one) {
+BPP_HD void fe_fused_column(ColFn& col, PinFn& pin, uint64_t& accA, uint64_t& accB, uint64_t& accC, uint32_t* m, Fe<P>& r,
+                            uint32_t one) {
     constexpr int NL = P::NL;
-    constexpr int na = K <= 2 * NL - 2 ? (K < 2 * NL - 2 - K ? K : 2 * NL - 2 - K) + 1 : 0;
-    constexpr int nm = K < NL ? K + 1 : 2 * NL - 1 - K;
-    constexpr bool fused = W * na + nm <= 15;
-    // the column before this one: was it split?  (its plain-product chain then holds a carry for this column)
-    constexpr int nap = K >= 1 ? ((K - 1) < 2 * NL - 2 - (K - 1) ? (K - 1) : 2 * NL - 2 - (K - 1)) + 1 : 0;
-    constexpr int nmp = K >= 1 ? ((K - 1) < NL ? K : 2 * NL - K) : 0;
-    constexpr bool prev_split = K >= 1 && !(W * nap + nmp <= 15);
-    if constexpr (!fused) {
-        if constexpr (!prev_split) accA = 0;
-        col(K, accA);
+    constexpr int na = fused_na(NL, K), nm = fused_nm(NL, K);
+    constexpr int kind = fused_kind(NL, W, K);
+    // the column before this one: a split or dual one left the carries of its plain-product chains for this column
+    constexpr int prev = K >= 1 ? fused_kind(NL, W, K - 1) : COL_FUSED;
+    // products (of two normalised limbs, or a 31-bit limb sum times one) per accumulator; each also takes <= 3 carries
+    static_assert(kind != COL_FUSED || W * na + nm <= ACC_MAX_PRODUCTS, "reduction chain of a fused column");
+    static_assert(kind != COL_SPLIT || (W * na <= ACC_MAX_PRODUCTS && nm + 1 <= ACC_MAX_PRODUCTS), "split column");
+    static_assert(kind != COL_DUAL || (W == 2 && na <= ACC_MAX_PRODUCTS && nm + 1 <= ACC_MAX_PRODUCTS), "dual column");
+    if constexpr (kind == COL_DUAL) {
+        if constexpr (prev == COL_FUSED) accA = 0;
+        if constexpr (prev != COL_DUAL) accC = 0;
+        col(K, accA, std::integral_constant<int, 0>{});
+        col(K, accC, std::integral_constant<int, 1>{});
+        const uint32_t T = ((uint32_t)accA & LIMB_MASK) + ((uint32_t)accC & LIMB_MASK);   // < 2^31
+        accA >>= LIMB_BITS;
+        accC >>= LIMB_BITS;
+        fe_mad(accB, T, one);
+    } else if constexpr (kind == COL_SPLIT) {
+        if constexpr (prev == COL_FUSED) accA = 0;
+        if constexpr (prev == COL_DUAL) accA += accC;
+        col(K, accA, std::integral_constant<int, -1>{});
         const uint32_t T = (uint32_t)accA & LIMB_MASK;
         accA >>= LIMB_BITS;
         fe_mad(accB, T, one);
     } else {
-        if constexpr (prev_split) accB += accA;
-        if constexpr (na > 0) col(K, accB);
+        if constexpr (prev != COL_FUSED) accB += accA;
+        if constexpr (prev == COL_DUAL) accB += accC;
+        if constexpr (na > 0) col(K, accB, std::integral_constant<int, -1>{});
     }
     if constexpr (K < NL) {
 #pragma unroll
@@ -509,8 +547,8 @@ BPP_HD void fe_fused_column(ColFn& col, PinFn& pin, uint64_t& accA, uint64_t& ac
         // the multipliers column K + 1 reads: m[lo .. hi)
         constexpr int lo = K + 1 < NL ? 0 : K + 1 - NL + 1;
         constexpr int hi = K + 1 < NL ? K + 1 : NL;
-        pin(accB, accA, m + lo, std::integral_constant<int, (hi > lo ? hi - lo : 0)>{});
-        fe_fused_column<P, W, K + 1>(col, pin, accA, accB, m, r, one);
+        pin(accB, accA, accC, m + lo, std::integral_constant<int, (hi > lo ? hi - lo : 0)>{});
+        fe_fused_column<P, W, K + 1>(col, pin, accA, accB, accC, m, r, one);
     }
 }
 
@@ -518,8 +556,9 @@ template <class P, int W, class ColFn, class PinFn>
 BPP_HD Fe<P> fe_fused_reduce(ColFn&& col, PinFn&& pin) {
     uint32_t m[P::NL];
     Fe<P> r;
-    uint64_t accB = 0, accA = 0;   // reduction chain (and the fused columns); plain-product chain of the middle columns
-    fe_fused_column<P, W, 0>(col, pin, accA, accB, m, r, opaque_one());
+    // reduction chain (and the fused columns); plain-product chain of the split columns; second one of the dual columns
+    uint64_t accB = 0, accA = 0, accC = 0;
+    fe_fused_column<P, W, 0>(col, pin, accA, accB, accC, m, r, opaque_one());
     // (T + m p) / R < T / R + p: far below 2p for every caller (T < HEADROOM / 8 p^2)  =>  accB == 0 here
     return r;
 }
@@ -534,11 +573,13 @@ BPP_HD Fe<P> fe_mul_io(Fe<P>& a, const Fe<P>& b) {
     constexpr int NL = P::NL;
     uint32_t* x = a.l;
     return fe_fused_reduce<P, 1>(
-        [&](int k, uint64_t& acc) {
+        [&](int k, uint64_t& acc, auto) {
 #pragma unroll
             for (int i = (k < NL ? 0 : k - NL + 1); i <= (k < NL ? k : NL - 1); i++) fe_mad(acc, x[i], b.l[k - i]);
         },
-        [&](uint64_t& accB, uint64_t& accA, uint32_t* mm, auto cnt) { chain_barrier_ops<NL, decltype(cnt)::value>(accB, accA, mm, x); });
+        [&](uint64_t& accB, uint64_t& accA, uint64_t&, uint32_t* mm, auto cnt) {
+            chain_barrier_ops<NL, decltype(cnt)::value>(accB, accA, mm, x);
+        });
 }
 template <class P>
 BPP_HD Fe<P> fe_mul(const Fe<P>& a, const Fe<P>& b) {
@@ -558,15 +599,16 @@ BPP_HD Fe<P> fe_mul_add(const Fe<P>& a, const Fe<P>& b, const Fe<P>& c, const Fe
         y[i] = c.l[i];
     }
     return fe_fused_reduce<P, 2>(
-        [&](int k, uint64_t& acc) {
+        [&](int k, uint64_t& acc, auto part) {
+            constexpr int sel = decltype(part)::value;
 #pragma unroll
             for (int i = (k < NL ? 0 : k - NL + 1); i <= (k < NL ? k : NL - 1); i++) {
-                fe_mad(acc, x[i], b.l[k - i]);
-                fe_mad(acc, y[i], d.l[k - i]);
+                if constexpr (sel != 1) fe_mad(acc, x[i], b.l[k - i]);
+                if constexpr (sel != 0) fe_mad(acc, y[i], d.l[k - i]);
             }
         },
-        [&](uint64_t& accB, uint64_t& accA, uint32_t* mm, auto cnt) {
-            chain_barrier_ops<NL, decltype(cnt)::value>(accB, accA, mm, x, y);
+        [&](uint64_t& accB, uint64_t& accA, uint64_t& accC, uint32_t* mm, auto cnt) {
+            chain_barrier_ops<NL, decltype(cnt)::value>(accB, accA, accC, mm, x, y);
         });
 }
 
@@ -581,13 +623,15 @@ BPP_HD Fe<P> fe_sqr_io(Fe<P>& a) {
 #pragma unroll
     for (int i = 0; i < NL; i++) a2[i] = a.l[i] << 1;
     return fe_fused_reduce<P, 1>(
-        [&](int k, uint64_t& acc) {
+        [&](int k, uint64_t& acc, auto) {
             // pairs i < j, i + j = k
 #pragma unroll
             for (int i = (k < NL ? 0 : k - NL + 1); 2 * i < k; i++) fe_mad(acc, x[i], a2[k - i]);
             if ((k & 1) == 0) fe_mad(acc, x[k / 2], x[k / 2]);
         },
-        [&](uint64_t& accB, uint64_t& accA, uint32_t* mm, auto cnt) { chain_barrier_ops<NL, decltype(cnt)::value>(accB, accA, mm, x); });
+        [&](uint64_t& accB, uint64_t& accA, uint64_t&, uint32_t* mm, auto cnt) {
+            chain_barrier_ops<NL, decltype(cnt)::value>(accB, accA, mm, x);
+        });
 }
 template <class P>
 BPP_HD Fe<P> fe_sqr(const Fe<P>& a) {

@@ -1,0 +1,216 @@
+// tu_debug.hip -- device-side unit-test hooks on RAW register images: the field operations at limbs the test chooses
+// (field_raw_ops.hpp), the lazy mixed addition on a raw accumulator, and the scalar splits / digit recoding as the
+// device compiles them.  A translation unit of its own: none of this is compiled into the units of the hot kernels.
+// Like bpp_debug_field_op / bpp_debug_point_op (capi.hip) the entries are not part of include/bpp_amd.h.
+// Every pointer is a host pointer.
+#include "host_util.hpp"
+
+#include "field_raw_ops.hpp"
+#include "fixed_glv.hpp"
+
+namespace bpp {
+
+template <class P, int G>
+__global__ void __launch_bounds__(64) k_dbg_field_raw(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c,
+                                                       const uint32_t* d, uint32_t* out, uint32_t* bad, size_t n) {
+    constexpr int NL = P::NL, OW = raw_out_words(NL);
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t wa[NL], wb[NL], wc[NL], wd[NL], wr[OW];
+    for (int t = 0; t < NL; t++) {
+        wa[t] = a[i * NL + t];
+        wb[t] = b[i * NL + t];
+        wc[t] = c[i * NL + t];
+        wd[t] = d[i * NL + t];
+    }
+    if (!fe_raw_op<P, G>(op, wa, wb, wc, wd, wr)) *bad = 1u;
+    for (int t = 0; t < OW; t++) out[i * OW + t] = wr[t];
+}
+
+// acc: 4 raw elements (X | Y | ZZ | ZZZ, on edwards25519 X | Y | Z | T); q: 2 raw elements, canonical (x, y < p)
+template <class C>
+__global__ void __launch_bounds__(64) k_dbg_madd_lazy_raw(const uint32_t* acc, const uint32_t* q, const uint32_t* neg,
+                                                           uint32_t* out, size_t n) {
+    using P = typename C::Fp;
+    constexpr int NL = P::NL;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Fe<P> e[4];
+    for (int t = 0; t < 4; t++) e[t] = raw_limbs<P>(acc + (i * 4 + t) * NL);
+    Aff<C> pt;
+    pt.x = raw_limbs<P>(q + (i * 2) * NL);
+    pt.y = raw_limbs<P>(q + (i * 2 + 1) * NL);
+    Xyzz<C> p;
+    if constexpr (C::ID == 2) {
+        p.e.X = e[0], p.e.Y = e[1], p.e.Z = e[2], p.e.T = e[3];
+    } else {
+        p.X = e[0], p.Y = e[1], p.ZZ = e[2], p.ZZZ = e[3];
+    }
+    xyzz_madd_lazy(p, pt, neg[i] != 0);
+    if constexpr (C::ID == 2) {
+        e[0] = p.e.X, e[1] = p.e.Y, e[2] = p.e.Z, e[3] = p.e.T;
+    } else {
+        e[0] = p.X, e[1] = p.Y, e[2] = p.ZZ, e[3] = p.ZZZ;
+    }
+    for (int t = 0; t < 4; t++) raw_put(e[t], out + (i * 4 + t) * NL);
+}
+
+constexpr int GLV_SPLIT_OUT = 10;   // k1[4] | k2[4] | neg1 | neg2
+
+// op 0 glv_split, 1 glv_split_balanced, 2 glv_split_signed: k = 8 canonical words per scalar
+template <class C>
+__global__ void __launch_bounds__(64) k_dbg_glv_split(int op, const uint32_t* k, uint32_t* out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t kk[8], k1[4], k2[4];
+    for (int t = 0; t < 8; t++) kk[t] = k[i * 8 + t];
+    bool n1 = false, n2 = false;
+    if constexpr (C::ID == 0) {
+        if (op == 0) glv_split<C>(kk, k1, k2);
+        else if (op == 1) glv_split_balanced<C>(kk, k1, k2, n1, n2);
+        else glv_split_signed<C>(kk, k1, k2, n1, n2);
+    } else {
+        glv_split_signed<C>(kk, k1, k2, n1, n2);
+    }
+    for (int t = 0; t < 4; t++) {
+        out[i * GLV_SPLIT_OUT + t] = k1[t];
+        out[i * GLV_SPLIT_OUT + 4 + t] = k2[t];
+    }
+    out[i * GLV_SPLIT_OUT + 8] = n1 ? 1u : 0u;
+    out[i * GLV_SPLIT_OUT + 9] = n2 ? 1u : 0u;
+}
+
+// op 3: halves of 4 words -> the L.W digits of glv_biased / glv_next_digit, GLV_MAXW words per half
+__global__ void __launch_bounds__(64) k_dbg_glv_recode(GlvLayout L, const uint32_t* h, uint32_t* out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t half[4], v[GLV_HALF_WORDS];
+    for (int t = 0; t < 4; t++) half[t] = h[i * 4 + t];
+    glv_biased(half, L.bias, v);
+    for (uint32_t j = 0; j < (uint32_t)GLV_MAXW; j++) out[i * GLV_MAXW + j] = j < L.W ? (uint32_t)glv_next_digit(v, L.wc[j]) : 0u;
+}
+
+template <class F>
+static int on_ctx_device(const bpp_ctx* ctx, size_t n, F&& f) noexcept {
+    return guarded(Count{n, "n"}, [&]() -> int {
+        HIPCHK(hipSetDevice(ctx->device));
+        return dispatch(ctx->curve, f);
+    });
+}
+
+static int upload(DevBuf& d, const void* src, size_t bytes) {
+    HIPCHK(d.alloc(bytes));
+    if (bytes) HIPCHK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+    return BPP_OK;
+}
+
+template <class P>
+static int field_raw_op(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, size_t n, uint32_t* out) {
+    const size_t in_bytes = n * P::NL * 4, out_bytes = n * raw_out_words(P::NL) * 4;
+    DevBuf da, db, dc, dd, dout, dbad;
+    if (int rc = upload(da, a, in_bytes)) return rc;
+    if (int rc = upload(db, b, in_bytes)) return rc;
+    if (int rc = upload(dc, c, in_bytes)) return rc;
+    if (int rc = upload(dd, d, in_bytes)) return rc;
+    HIPCHK(dout.alloc(out_bytes));
+    HIPCHK(dbad.alloc(4));
+    HIPCHK(hipMemset(dbad.p, 0, 4));
+    if (n) {
+        const dim3 grid(cdiv(n, 64)), block(64);
+        switch (raw_op_group(op)) {
+            case 0: hipLaunchKernelGGL((k_dbg_field_raw<P, 0>), grid, block, 0, nullptr, op, da.u32(), db.u32(), dc.u32(), dd.u32(), dout.u32(), dbad.u32(), n); break;
+            case 1: hipLaunchKernelGGL((k_dbg_field_raw<P, 1>), grid, block, 0, nullptr, op, da.u32(), db.u32(), dc.u32(), dd.u32(), dout.u32(), dbad.u32(), n); break;
+            case 2: hipLaunchKernelGGL((k_dbg_field_raw<P, 2>), grid, block, 0, nullptr, op, da.u32(), db.u32(), dc.u32(), dd.u32(), dout.u32(), dbad.u32(), n); break;
+            default: return fail(BPP_E_ARG, "unknown raw field op");
+        }
+        HIPCHK(hipGetLastError());
+    }
+    uint32_t bad = 0;
+    HIPCHK(hipMemcpy(&bad, dbad.p, 4, hipMemcpyDeviceToHost));
+    if (bad) return fail(BPP_E_ARG, "unknown raw field op");
+    if (out_bytes) HIPCHK(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+    return BPP_OK;
+}
+
+}  // namespace bpp
+
+using namespace bpp;
+
+// field: 0 = base field, 1 = scalar field; op: a RawOp of field_raw_ops.hpp.  a, b, c, d: n operands of NL words each
+// (30-bit limbs, taken as given; every operation reads only the operands it has, but all four must be readable);
+// out: n results of 2 NL words.
+extern "C" int bpp_debug_field_raw_op(bpp_ctx* ctx, int field, int op, const uint32_t* a, const uint32_t* b, const uint32_t* c,
+                                      const uint32_t* d, size_t n, uint32_t* out) {
+    if (!ctx || !a || !b || !c || !d || !out) return fail(BPP_E_ARG, "null argument");
+    if (raw_op_group(op) < 0) return fail(BPP_E_ARG, "unknown raw field op");
+    return on_ctx_device(ctx, n, [&](auto cv) -> int {
+        using C = decltype(cv);
+        if (field == 0) return field_raw_op<typename C::Fp>(op, a, b, c, d, n, out);
+        return field_raw_op<typename C::Fr>(op, a, b, c, d, n, out);
+    });
+}
+
+// xyzz_madd_lazy(acc, q, neg) on n raw accumulators: acc 4 NL words each (X | Y | ZZ | ZZZ; edwards25519: X | Y | Z | T),
+// q 2 NL words each (Montgomery form, canonical), neg one word each; out: the accumulators afterwards, 4 NL words each.
+extern "C" int bpp_debug_madd_lazy_raw(bpp_ctx* ctx, const uint32_t* acc, const uint32_t* q, const uint32_t* neg, size_t n,
+                                       uint32_t* out) {
+    if (!ctx || !acc || !q || !neg || !out) return fail(BPP_E_ARG, "null argument");
+    return on_ctx_device(ctx, n, [&](auto cv) -> int {
+        using C = decltype(cv);
+        constexpr int NL = C::Fp::NL;
+        DevBuf dacc, dq, dneg, dout;
+        if (int rc = upload(dacc, acc, n * 4 * NL * 4)) return rc;
+        if (int rc = upload(dq, q, n * 2 * NL * 4)) return rc;
+        if (int rc = upload(dneg, neg, n * 4)) return rc;
+        HIPCHK(dout.alloc(n * 4 * NL * 4));
+        if (n) {
+            hipLaunchKernelGGL(k_dbg_madd_lazy_raw<C>, dim3(cdiv(n, 64)), dim3(64), 0, nullptr, dacc.u32(), dq.u32(), dneg.u32(),
+                               dout.u32(), n);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpy(out, dout.p, n * 4 * NL * 4, hipMemcpyDeviceToHost));
+        }
+        return BPP_OK;
+    });
+}
+
+// The scalar splits and the digit recoding of the fixed-generator tables, from a kernel.
+//   op 0 glv_split, 1 glv_split_balanced (BLS12-381), 2 glv_split_signed (BLS12-381, secp256k1): in = n scalars of 8
+//     canonical words; out = 10 words each: k1[4] | k2[4] | neg1 | neg2.
+//   op 3 glv_biased + glv_next_digit for the layout of window_bits (BLS12-381): in = n halves of 4 words; out = 64 words
+//     each, the W digits (two's complement) then zeros; out_layout (may be null) = W | top | per_f | 64 window widths.
+extern "C" int bpp_debug_glv_op(bpp_ctx* ctx, int op, int window_bits, const uint32_t* in, size_t n, uint32_t* out,
+                                uint32_t* out_layout) {
+    if (!ctx || !in || !out) return fail(BPP_E_ARG, "null argument");
+    if (op < 0 || op > 3) return fail(BPP_E_ARG, "unknown glv op");
+    if (op == 3 && (window_bits < 2 || window_bits > 20)) return fail(BPP_E_ARG, "window_bits must be in [2, 20]");
+    return on_ctx_device(ctx, n, [&](auto cv) -> int {
+        using C = decltype(cv);
+        if constexpr (!curve_has_glv<C>()) {
+            return fail(BPP_E_ARG, "this curve has no scalar split");
+        } else {
+            if (op != 2 && C::ID != 0) return fail(BPP_E_ARG, "BLS12-381 only");
+            const size_t in_words = op == 3 ? 4 : 8, out_words = op == 3 ? (size_t)GLV_MAXW : (size_t)GLV_SPLIT_OUT;
+            DevBuf din, dout;
+            if (int rc = upload(din, in, n * in_words * 4)) return rc;
+            HIPCHK(dout.alloc(n * out_words * 4));
+            if (op == 3) {
+                if constexpr (C::ID == 0) {
+                    uint32_t hmax[4];
+                    glv_half_max<C>(hmax);
+                    GlvLayout L;
+                    if (!glv_layout(window_bits, C::Fr::BITS, hmax, L)) return fail(BPP_E_ARG, "no layout at this window_bits");
+                    if (out_layout) {
+                        out_layout[0] = L.W, out_layout[1] = L.top, out_layout[2] = L.per_f;
+                        for (int j = 0; j < GLV_MAXW; j++) out_layout[3 + j] = L.wc[j];
+                    }
+                    if (n) hipLaunchKernelGGL(k_dbg_glv_recode, dim3(cdiv(n, 64)), dim3(64), 0, nullptr, L, din.u32(), dout.u32(), n);
+                }
+            } else if (n) {
+                hipLaunchKernelGGL(k_dbg_glv_split<C>, dim3(cdiv(n, 64)), dim3(64), 0, nullptr, op, din.u32(), dout.u32(), n);
+            }
+            HIPCHK(hipGetLastError());
+            if (n) HIPCHK(hipMemcpy(out, dout.p, n * out_words * 4, hipMemcpyDeviceToHost));
+            return BPP_OK;
+        }
+    });
+}

@@ -9,15 +9,11 @@ import subprocess
 
 import pytest
 
-import pyref as P
+from glv_cases import HALF_MAX, R, Z2, edges as _edges, recode_halves
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g"] if os.environ.get("BPP_HOST_SANITIZE") else []
 
-Z = 0xd201000000010000
-Z2 = Z * Z
-R = P.BLS12_381["r"]
-HALF_MAX = Z2 // 2 + 1          # the stated bound on both magnitudes
 assert R == Z2 * Z2 - Z2 + 1 and HALF_MAX < 2 ** 126.43
 
 
@@ -35,20 +31,6 @@ def _run(exe, args, chunk=2000):
     for off in range(0, len(items), chunk):
         lines += subprocess.check_output([exe] + head + items[off:off + chunk]).decode().splitlines()
     return lines
-
-
-def _edges():
-    """the scalars of the issue's list: 0, 1, r-1, the middle of the range, around z^2 and z^2/2, multiples of z^2, and the
-    scalars that give the largest k1 and the largest k2"""
-    ks = [0, 1, 2, R - 1, R - 2, (R - 1) // 2, (R + 1) // 2, (R - 1) // 2 - 1, (R + 1) // 2 + 1,
-          Z2 - 1, Z2, Z2 + 1, Z2 // 2, Z2 // 2 + 1, Z2 // 2 - 1, R - Z2, R - Z2 // 2, R - Z2 // 2 - 1]
-    ks += [j * Z2 for j in (2, 3, 5, Z2 // 2 - 1, Z2 // 2, (R - 1) // (2 * Z2))]
-    ks += [R - j * Z2 for j in (1, 2, 3, 7)]
-    q_max = ((R - 1) // 2) // Z2                      # largest quotient of a scalar in the lower half of the range
-    ks += [q_max * Z2 + d for d in (0, 1, Z2 // 2, Z2 // 2 + 1, ((R - 1) // 2) % Z2)]   # largest k2 (k1 folds upwards)
-    ks += [j * Z2 + Z2 // 2 for j in (0, 1, 12345)]   # largest k1
-    ks += [R - k for k in ks[-8:] if k]
-    return [k % R for k in ks]
 
 
 def test_balanced_split_matches_integers(exe):
@@ -82,7 +64,7 @@ def _layout(exe, c):
     return W, top, per_f, wins, int(out[1 + W], 16)
 
 
-@pytest.mark.parametrize("c", [10, 13, 16, 17])
+@pytest.mark.parametrize("c", [10, 13, 16, 17])   # glv_cases.RECODE_WINDOW_BITS
 def test_layout_and_recoding(exe, c):
     W, top, per_f, wins, bias = _layout(exe, c)
     assert W == ((255 - 1) // c + 1) // 2
@@ -98,10 +80,7 @@ def test_layout_and_recoding(exe, c):
         assert per_f * 2050 * 96 < 220e9             # the table at (64, 16)
     if c == 16:
         assert (widths, top, per_f) == ([16] * 7, 22051, 251427)
-    rng = random.Random(22 + c)
-    hs = [0, 1, 2, HALF_MAX, HALF_MAX - 1, Z2 // 2, Z2 // 4] + [1 << o for o in offs] + [(1 << o) - 1 for o in offs[1:]]
-    hs += [(1 << (o + w - 1)) for w, o, _ in wins[:-1]] + [(1 << (o + w - 1)) - 1 for w, o, _ in wins[:-1]]
-    hs += [rng.randrange(HALF_MAX + 1) for _ in range(5000)]
+    hs = recode_halves(c, wins)
     out = _run(exe, (["recode", str(c)], ["%032x" % h for h in hs]))
     assert len(out) == len(hs)
     for h, line in zip(hs, out):

@@ -4,10 +4,10 @@ intermediate bound asserted (tests/host/lazy_host_test.cpp), and the GLV scalar 
 (tests/host/glv_host_test.cpp) against Python integers."""
 
 import os
-import random
 import subprocess
 
 import pyref as P
+from glv_cases import SECP_LAMBDA, bls_split_scalars, secp_split_scalars
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -37,12 +37,8 @@ def test_glv_split_matches_integers(tmp_path):
     exe = _build("glv_host_test", tmp_path, "-O2")
     r = P.BLS12_381["r"]
     z2 = 0xd201000000010000 ** 2
-    rng = random.Random(11)
-    ks = [0, 1, z2 - 1, z2, z2 + 1, 2 * z2 - 1, 2 * z2, r - 1, r - 2, (r // z2) * z2, (r // z2) * z2 - 1, (1 << 128) - 1, 1 << 128,
-          (1 << 255) - 1 if (1 << 255) - 1 < r else r - 3]
-    ks += [rng.randrange(r) for _ in range(3000)]
-    ks += [rng.randrange(1 << 128) * z2 + d for d in (0, 1, z2 - 1) for _ in range(200) if True]
-    ks = [k for k in ks if k < r]
+    ks = bls_split_scalars()
+    assert len(ks) > 3000 and all(k < r for k in ks)
     for off in range(0, len(ks), 500):
         chunk = ks[off:off + 500]
         out = subprocess.check_output([exe] + ["%064x" % k for k in chunk]).decode().split("\n")
@@ -57,14 +53,10 @@ def test_glv_split_secp256k1_signed(tmp_path):
     lambda, n - lambda, the middle of the range, values that make either half negative)"""
     exe = _build("glv_host_test", tmp_path, "-O2")
     n = P.SECP256K1["r"]
-    lam = 0x5363ad4cc05c30e0a5261c028812645a122e22ea20816678df02967c1b23bd72
+    lam = SECP_LAMBDA
     assert (lam * lam + lam + 1) % n == 0
-    rng = random.Random(12)
-    ks = [0, 1, 2, n - 1, n - 2, lam, n - lam, lam + 1, lam - 1, (n - 1) // 2, (n + 1) // 2, (1 << 128) - 1, 1 << 128, (1 << 255),
-          (1 << 256) - 1 - ((1 << 256) - n) - 5]
-    ks += [rng.randrange(n) for _ in range(4000)]
-    ks += [(a + b * lam) % n for a in (1, -1, (1 << 127) - 1, -(1 << 127) + 1) for b in (1, -1, (1 << 127) - 1, -(1 << 127) + 1)]
-    ks = [k % n for k in ks]
+    ks = secp_split_scalars()
+    assert len(ks) > 4000 and all(k < n for k in ks)
     seen_neg = [0, 0]
     for off in range(0, len(ks), 500):
         chunk = ks[off:off + 500]
