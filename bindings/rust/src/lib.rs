@@ -468,6 +468,182 @@ impl BatchVerifier {
     }
 }
 
+/// The cuts of a batch over `world` shards (include/bpp_amd.h: bpp_shard_cuts): shard r takes proofs
+/// [cuts[r], cuts[r + 1]).  `ms = None`: a uniform batch of `count` proofs; else proof i costs ms[i] (and `count` must be
+/// ms.len()).  Host code, no device.
+pub fn shard_cuts(ms: Option<&[u32]>, count: usize, world: usize) -> Result<Vec<usize>, ProofError> {
+    if world == 0 || world > 16 || ms.map_or(false, |m| m.len() != count) {
+        return Err(ProofError::FormatError);
+    }
+    let mut cuts = vec![0usize; world + 1];
+    let rc = unsafe { ffi::bpp_shard_cuts(ms.map_or(std::ptr::null(), |m| m.as_ptr()), count, world, cuts.as_mut_ptr()) };
+    if rc != 0 {
+        return Err(ProofError::FormatError);
+    }
+    Ok(cuts)
+}
+
+/// How `VerifierPool::verify_serialized_mixed` checks a block.
+pub enum PoolMode<'a> {
+    /// every shard runs the exact per-proof pass over its slice
+    Exact,
+    /// every shard runs the grouped check over its slice: 32 secret bytes from the OS CSPRNG, the GLOBAL index of the
+    /// block's first proof, and the group size (a power of two >= 2)
+    Grouped { weight_key: &'a [u8; 32], index_base: u64, group: u32 },
+}
+
+/// ONE batch sharded over several devices of a node in this process (include/bpp_amd.h "verifier pool"): per entry of
+/// `devices` a context and a verifier of capacity (n, m) on that device; a verify call cuts the batch (shard_cuts), runs
+/// the shards' passes on one host thread each and returns the verdicts in caller order.  An ordinal may repeat: the
+/// shards then share a device.  One host thread at a time (hence `&mut self`).
+pub struct VerifierPool {
+    handle: *mut std::os::raw::c_void,
+    n: usize,
+    m: usize,
+    k: usize,
+}
+impl VerifierPool {
+    pub fn new(pk: &PublicKey, n: usize, m: usize, window_bits: i32, devices: &[i32]) -> VerifierPool {
+        assert!(pk.G_vec.len() == n * m && pk.H_vec.len() == n * m, "public key of length n*m");
+        assert!(!devices.is_empty() && devices.len() <= 16, "1 to 16 devices");
+        let gh = flat_points(&[pk.g, pk.h]);
+        let (gv, hv) = (flat_points(&pk.G_vec), flat_points(&pk.H_vec));
+        let dev: Vec<c_int> = devices.iter().map(|&d| d as c_int).collect();
+        let mut h: *mut std::os::raw::c_void = std::ptr::null_mut();
+        let rc = unsafe {
+            ffi::bpp_pool_create(ffi::BPP_BLS12_381_G1, dev.as_ptr(), dev.len(), gh.as_ptr(), gv.as_ptr(), hv.as_ptr(), n, m,
+                                 window_bits as c_int, &mut h)
+        };
+        assert!(rc == 0 && !h.is_null(), "bpp_pool_create: {}", rc);
+        VerifierPool { handle: h, n, m, k: (n * m).trailing_zeros() as usize }
+    }
+    pub fn size(&self) -> usize {
+        unsafe { ffi::bpp_pool_size(self.handle) }
+    }
+    /// `BatchVerifier::verify_batch_mixed` over the pool (bpp_pool_verify_mixed): each `Result` is
+    /// RangeProof::verify(proof_i, PublicKey::new(n m_i), n, V_i).  A proof whose shape the pool does not take is
+    /// Err(VerificationError) without reaching the engine.
+    pub fn verify_batch_mixed(&mut self, batch: &[(&RangeProof, &[Point])]) -> Vec<Result<(), ProofError>> {
+        let logn = self.k - self.m.trailing_zeros() as usize;
+        let mut out: Vec<Result<(), ProofError>> = vec![Err(ProofError::VerificationError); batch.len()];
+        let (mut pts, mut scs, mut ms, mut at) = (Vec::<Point>::new(), Vec::<PrimeFieldElem>::new(), Vec::<u32>::new(), Vec::new());
+        for (i, (proof, commitment_vec)) in batch.iter().enumerate() {
+            let mi = commitment_vec.len();
+            if mi == 0 || !mi.is_power_of_two() || mi > self.m {
+                continue;
+            }
+            let ki = logn + mi.trailing_zeros() as usize;
+            if proof.proof.L_vec.len() != ki || proof.proof.R_vec.len() != ki {
+                continue;   // wip.rs:335-337
+            }
+            pts.extend_from_slice(&[proof.A, proof.proof.A, proof.proof.B]);
+            pts.extend_from_slice(&proof.proof.L_vec);
+            pts.extend_from_slice(&proof.proof.R_vec);
+            pts.extend_from_slice(commitment_vec);
+            scs.extend_from_slice(&[proof.proof.r_prime, proof.proof.s_prime, proof.proof.d_prime]);
+            ms.push(mi as u32);
+            at.push(i);
+        }
+        if ms.is_empty() {
+            return out;
+        }
+        let (pw, sw) = (flat_points(&pts), flat_scalars(&scs));
+        let mut ok = vec![0u32; ms.len()];
+        let rc = unsafe {
+            ffi::bpp_pool_verify_mixed(self.handle, pw.as_ptr(), sw.as_ptr(), ms.as_ptr(), ms.len(), ok.as_mut_ptr())
+        };
+        assert!(rc == 0, "bpp_pool_verify_mixed: {}", rc);
+        for (j, &i) in at.iter().enumerate() {
+            out[i] = if ok[j] == 0 { Ok(()) } else { Err(ProofError::VerificationError) };
+        }
+        out
+    }
+    /// `BatchVerifier::verify_serialized_mixed` over the pool (bpp_pool_verify_serialized_mixed): a block of version 1
+    /// containers and their compressed commitments, `ms = None` framing the stream first.  Err(FormatError) for the whole
+    /// call when the stream cannot be framed, an ms[i] is not taken, the buffers' lengths are not those `ms` implies or
+    /// the group is not a power of two >= 2: nothing then reaches the engine.  With PoolMode::Grouped the second value is
+    /// [groups that failed, proofs re-verified exactly] summed over the shards (it depends on the cut; the statuses do not).
+    pub fn verify_serialized_mixed(&mut self, proofs: &[u8], commitments: &[u8], ms: Option<&[u32]>, transcript: bool,
+                                   mode: PoolMode) -> Result<(Vec<Result<(), ProofError>>, [u64; 2]), ProofError> {
+        let scanned;
+        let ms: &[u32] = match ms {
+            Some(ms) => ms,
+            None => {
+                scanned = proofs_scan(self.n, proofs)?;
+                &scanned
+            }
+        };
+        let cb = unsafe { ffi::bpp_point_compressed_bytes(ffi::BPP_BLS12_381_G1) };
+        let (mut pbytes, mut cbytes) = (0usize, 0usize);
+        for &mi in ms {
+            let mi = mi as usize;
+            if mi == 0 || !mi.is_power_of_two() || mi > self.m {
+                return Err(ProofError::FormatError);
+            }
+            pbytes += unsafe { ffi::bpp_proof_bytes(ffi::BPP_BLS12_381_G1, self.n, mi) };
+            cbytes += mi * cb;
+        }
+        if pbytes != proofs.len() || cbytes != commitments.len() {
+            return Err(ProofError::FormatError);
+        }
+        let (mode_id, key, index_base, group) = match mode {
+            PoolMode::Exact => (ffi::BPP_POOL_EXACT, std::ptr::null(), 0u64, 0u32),
+            PoolMode::Grouped { weight_key, index_base, group } => {
+                if group < 2 || !group.is_power_of_two() {
+                    return Err(ProofError::FormatError);
+                }
+                (ffi::BPP_POOL_GROUPED, weight_key.as_ptr(), index_base, group)
+            }
+        };
+        let mut stats = [0u64; 2];
+        if ms.is_empty() {
+            return Ok((Vec::new(), stats));
+        }
+        let mut ok = vec![0u32; ms.len()];
+        let flags = if transcript { ffi::BPP_SER_TRANSCRIPT } else { 0 };
+        let rc = unsafe {
+            ffi::bpp_pool_verify_serialized_mixed(self.handle, proofs.as_ptr(), commitments.as_ptr(), ms.as_ptr(), ms.len(), flags,
+                                                  mode_id, key, index_base, group, ok.as_mut_ptr(), stats.as_mut_ptr())
+        };
+        assert!(rc == 0, "bpp_pool_verify_serialized_mixed: {}", rc);
+        Ok((ok.iter().map(|&v| match v {
+            0 => Ok(()),
+            2 => Err(ProofError::FormatError),
+            _ => Err(ProofError::VerificationError),
+        }).collect(), stats))
+    }
+    /// The combined check of a uniform batch at the capacity shape (bpp_pool_verify_combined): every shard's weighted sum
+    /// and ONE reduce on shard 0's device.  Ok(()) iff the batch passes; on Err the caller asks `verify_batch_mixed` which
+    /// proofs failed.  `weight_key`: 32 secret bytes from the OS CSPRNG; `index_base`: the global index of the first proof.
+    pub fn verify_combined(&mut self, batch: &[(&RangeProof, &[Point])], weight_key: &[u8; 32], index_base: u64)
+                           -> Result<(), ProofError> {
+        let mut pts: Vec<Point> = Vec::with_capacity(batch.len() * (3 + 2 * self.k + self.m));
+        let mut scs: Vec<PrimeFieldElem> = Vec::with_capacity(batch.len() * 3);
+        for (proof, commitment_vec) in batch {
+            if proof.proof.L_vec.len() != self.k || proof.proof.R_vec.len() != self.k || commitment_vec.len() != self.m {
+                return Err(ProofError::VerificationError);   // a proof of another shape fails the batch
+            }
+            pts.extend_from_slice(&[proof.A, proof.proof.A, proof.proof.B]);
+            pts.extend_from_slice(&proof.proof.L_vec);
+            pts.extend_from_slice(&proof.proof.R_vec);
+            pts.extend_from_slice(commitment_vec);
+            scs.extend_from_slice(&[proof.proof.r_prime, proof.proof.s_prime, proof.proof.d_prime]);
+        }
+        let (pw, sw) = (flat_points(&pts), flat_scalars(&scs));
+        let mut ok = 1u32;
+        let rc = unsafe {
+            ffi::bpp_pool_verify_combined(self.handle, pw.as_ptr(), sw.as_ptr(), batch.len(), weight_key.as_ptr(), index_base, &mut ok)
+        };
+        assert!(rc == 0, "bpp_pool_verify_combined: {}", rc);
+        if ok == 0 { Ok(()) } else { Err(ProofError::VerificationError) }
+    }
+}
+impl Drop for VerifierPool {
+    fn drop(&mut self) {
+        unsafe { ffi::bpp_pool_destroy(self.handle) }
+    }
+}
+
 /// m_i of every container of a bare stream of version 1 containers for n-bit values (include/bpp_amd.h: bpp_proofs_scan; host
 /// code, no device).  Err(FormatError) when the stream cannot be framed.
 pub fn proofs_scan(n: usize, proofs: &[u8]) -> Result<Vec<u32>, ProofError> {

@@ -53,6 +53,8 @@ EXPORTS = [
     "bpp_range_prove_batch_mixed", "bpp_range_prove_batch_serialized_mixed",
     "bpp_wip_prover_workspace_bytes", "bpp_wip_prove_batch_device", "bpp_wip_verifier_workspace_bytes",
     "bpp_wip_verify_batch_device", "bpp_wip_prove_batch", "bpp_wip_verify_batch",
+    "bpp_shard_cuts", "bpp_pool_create", "bpp_pool_destroy", "bpp_pool_size", "bpp_pool_device", "bpp_pool_verifier",
+    "bpp_pool_verify_mixed", "bpp_pool_verify_serialized_mixed", "bpp_pool_verify_combined",
 ]
 
 
@@ -194,6 +196,18 @@ def lib():
         L.bpp_wip_verify_batch_device.argtypes = [vp, vp, vp, vp, vp, sz, sz, i32, vp, vp, vp, vp, sz, vp, vp, vp]
         L.bpp_wip_prove_batch.argtypes = [vp, vp, vp, vp, vp, sz, sz, i32, vp, ctypes.c_char_p, u64, vp, vp, vp, vp]
         L.bpp_wip_verify_batch.argtypes = [vp, vp, vp, vp, vp, sz, sz, i32, vp, vp, vp, vp, vp]
+        L.bpp_shard_cuts.argtypes = [vp, sz, sz, vp]
+        L.bpp_pool_create.argtypes = [i32, vp, sz, vp, vp, vp, sz, sz, i32, ctypes.POINTER(vp)]
+        L.bpp_pool_destroy.argtypes = [vp]
+        L.bpp_pool_destroy.restype = None
+        L.bpp_pool_size.argtypes = [vp]
+        L.bpp_pool_size.restype = sz
+        L.bpp_pool_device.argtypes = [vp, sz]
+        L.bpp_pool_verifier.argtypes = [vp, sz, ctypes.POINTER(vp)]
+        L.bpp_pool_verify_mixed.argtypes = [vp, vp, vp, vp, sz, vp]
+        L.bpp_pool_verify_serialized_mixed.argtypes = [vp, vp, vp, vp, sz, i32, i32, ctypes.c_char_p, u64, ctypes.c_uint32,
+                                                       vp, vp]
+        L.bpp_pool_verify_combined.argtypes = [vp, vp, vp, sz, ctypes.c_char_p, u64, vp]
         L.bpp_debug_field_op.argtypes = [vp, i32, i32, vp, vp, sz, vp]
         L.bpp_debug_point_op.argtypes = [vp, i32, vp, vp, sz, vp]
         # the raw-image hooks of csrc/tu_debug.hip (like the two above: not declared in include/bpp_amd.h)

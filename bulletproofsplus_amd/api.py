@@ -612,10 +612,21 @@ class BatchVerifier:
         self.k = mn.bit_length() - 1
         self.points_per_proof = 3 + 2 * self.k + m
 
+    @classmethod
+    def _borrowed(cls, arith: Arith, handle, n: int, m: int, owner) -> "BatchVerifier":
+        """a verifier that belongs to `owner` (a VerifierPool's shard): close() leaves it alone"""
+        v = cls.__new__(cls)
+        v.arith, v.n, v.m, v.handle, v._owner = arith, n, m, handle, owner
+        v.msm_len = _lib.lib().bpp_verifier_msm_len(handle)
+        v.table_bytes = _lib.lib().bpp_verifier_table_bytes(handle)
+        v.k = (n * m).bit_length() - 1
+        v.points_per_proof = 3 + 2 * v.k + m
+        return v
+
     def close(self):
-        if self.handle:
+        if self.handle and getattr(self, "_owner", None) is None:
             _lib.lib().bpp_verifier_destroy(self.handle)
-            self.handle = None
+        self.handle = None
 
     def __del__(self):
         try:
@@ -1174,6 +1185,141 @@ class BatchVerifier:
             (1 if transcript else 0) | (2 if uncompressed else 0), blind_key, ctypes.c_uint64(index_base), _ptr(raw), _ptr(cm)),
             "bpp_range_prove_batch_serialized_mixed")
         return raw[:nbytes].tobytes(), cm[:int(ms.sum()) * pb].tobytes(), ms
+
+
+def shard_cuts(ms, count: int, world: int) -> np.ndarray:
+    """bpp_shard_cuts: the world + 1 cuts of a batch of `count` proofs over `world` shards, shard r taking proofs
+    [cuts[r], cuts[r + 1]).  ms None: a uniform batch (sharding.shard_bounds); else proof i costs ms[i] and every shard
+    costs less than sum(ms) / world + max(ms)."""
+    m = None if ms is None else np.ascontiguousarray(ms, dtype=np.uint32).reshape(-1)
+    if m is not None and len(m) != count:
+        raise ValueError("shard_cuts: one cost per proof")
+    cuts = np.zeros(world + 1 if 0 < world <= 16 else 17, dtype=np.uintp)
+    check(_lib.lib().bpp_shard_cuts(_ptr(m) if m is not None and count else None, count, world, _ptr(cuts)), "bpp_shard_cuts")
+    return cuts.astype(np.int64)
+
+
+class VerifierPool:
+    """One batch sharded over several devices in ONE process (include/bpp_amd.h "verifier pool"): per entry of `devices`
+    a context and a verifier of capacity (n, m) on that device, the batch cut by shard_cuts, the shards' passes run on a
+    host thread each, verdicts in caller order.  An ordinal may repeat -- devices=(0, 0) exercises two shards on a one-GPU
+    machine.  One host thread at a time."""
+
+    def __init__(self, pk: PublicKey, n: int, m: int, window_bits: int = 13, devices=(0,)):
+        self.arith = pk.arith
+        self.n, self.m = n, m
+        if len(pk.G_vec) != n * m or len(pk.H_vec) != n * m:
+            raise AssertionError("pk must hold n*m generators")       # range/mod.rs:90-91,252-253 assert_eq
+        self.handle = None
+        dev = np.ascontiguousarray(list(devices), dtype=np.int32)
+        h = ctypes.c_void_p()
+        G = np.ascontiguousarray(pk.G_vec)
+        H = np.ascontiguousarray(pk.H_vec)
+        check(_lib.lib().bpp_pool_create(pk.arith.curve, _ptr(dev) if len(dev) else None, len(dev), _ptr(pk.gh), _ptr(G),
+                                         _ptr(H), n, m, window_bits, ctypes.byref(h)), "bpp_pool_create")
+        self.handle = h
+        self.size = _lib.lib().bpp_pool_size(h)
+        self.devices = [_lib.lib().bpp_pool_device(h, r) for r in range(self.size)]
+
+    def close(self):
+        if self.handle:
+            _lib.lib().bpp_pool_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def verifier(self, r: int) -> BatchVerifier:
+        """shard r's verifier, borrowed: valid while the pool lives (the _device calls, set_subgroup_check)"""
+        h = ctypes.c_void_p()
+        check(_lib.lib().bpp_pool_verifier(self.handle, r, ctypes.byref(h)), "bpp_pool_verifier")
+        return BatchVerifier._borrowed(self.arith, h, self.n, self.m, self)
+
+    def cuts(self, ms, count: int = None) -> np.ndarray:
+        """the cuts a verify call of this pool makes for a batch with aggregation sizes ms (None: uniform, `count` proofs)"""
+        return shard_cuts(ms, len(ms) if ms is not None else count, self.size)
+
+    def _one(self) -> BatchVerifier:
+        v = BatchVerifier.__new__(BatchVerifier)   # the shape helpers of a verifier, no handle
+        v.arith, v.n, v.m, v.handle, v._owner = self.arith, self.n, self.m, None, self
+        return v
+
+    def verify_wire_mixed(self, records, scalars, ms=None) -> np.ndarray:
+        """BatchVerifier.verify_wire_mixed over the pool (bpp_pool_verify_mixed).  ms None: a uniform batch at the
+        capacity shape, records (count, 3 + 2k + m, PW)."""
+        if isinstance(records, (list, tuple)):
+            pts = (np.concatenate([np.asarray(r, dtype=np.uint64).reshape(-1, self.arith.PW) for r in records])
+                   if len(records) else np.zeros((0, self.arith.PW), dtype=np.uint64))
+        else:
+            pts = np.asarray(records, dtype=np.uint64).reshape(-1, self.arith.PW)
+        pts = np.ascontiguousarray(pts)
+        sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 3, 4)
+        count = sc.shape[0]
+        one = self._one()
+        if ms is None:
+            m = None
+            need = count * one.mixed_points(self.m)
+        else:
+            m = one._ms(ms)
+            if len(m) != count:
+                raise RuntimeError("verify_wire_mixed: one scalar triple per entry of ms")
+            # an m_i the pool does not take is reported by the library (BPP_E_ARG naming the proof)
+            taken = all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m)
+            need = sum(one.mixed_points(int(x)) for x in m) if taken else None
+        if need is not None and pts.shape[0] != need:
+            raise RuntimeError("verify_wire_mixed: %d wire points, the shapes need %d" % (pts.shape[0], need))
+        ok = np.zeros(count, dtype=np.uint32)
+        check(_lib.lib().bpp_pool_verify_mixed(self.handle, _ptr(pts), _ptr(sc), _ptr(m) if m is not None else None, count,
+                                               _ptr(ok)), "bpp_pool_verify_mixed")
+        return ok
+
+    def verify_serialized_mixed(self, proofs, commitments, ms=None, transcript: bool = False, uncompressed: bool = False,
+                                grouped: bool = False, weight_key: bytes = None, index_base: int = 0, group: int = 32,
+                                return_stats: bool = False):
+        """BatchVerifier.verify_serialized_mixed over the pool (bpp_pool_verify_serialized_mixed): status (count,) u32,
+        0 Ok / 1 VerificationError / 2 FormatError.  grouped: every shard runs the grouped check over its slice, proof i
+        weighted by PRF(weight_key, index_base + i) whatever the cut (weight_key None = os.urandom(32)); with
+        return_stats -> (status, (groups that failed, proofs re-verified exactly)), summed over the shards -- the stats
+        depend on the cut, the statuses do not."""
+        def flat(x):
+            return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
+        raw, cm = flat(proofs), flat(commitments)
+        version = 2 if uncompressed else 1
+        m = proofs_scan(self.arith, self.n, raw, version) if ms is None else np.ascontiguousarray(ms, dtype=np.uint32).reshape(-1)
+        count = len(m)
+        if all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m):
+            pb = uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)
+            need = sum(proof_bytes(self.arith, self.n, int(x), version) for x in m)
+            if len(raw) != need:
+                raise RuntimeError("verify_serialized_mixed: %d bytes of proofs, the shapes in ms need %d" % (len(raw), need))
+            if len(cm) != int(m.sum()) * pb:
+                raise RuntimeError("verify_serialized_mixed: ms[i] commitments per proof")
+        ok = np.zeros(count, dtype=np.uint32)
+        stats = (ctypes.c_uint64 * 2)()
+        check(_lib.lib().bpp_pool_verify_serialized_mixed(
+            self.handle, _ptr(raw) if len(raw) else None, _ptr(cm) if len(cm) else None, _ptr(m) if count else None, count,
+            (1 if transcript else 0) | (2 if uncompressed else 0), 1 if grouped else 0,
+            _weight_key_arg(weight_key, 0) if grouped else None, ctypes.c_uint64(index_base), group if grouped else 0,
+            _ptr(ok) if count else None, stats), "bpp_pool_verify_serialized_mixed")
+        return (ok, (int(stats[0]), int(stats[1]))) if return_stats else ok
+
+    def verify_combined(self, points, scalars, weight_key: bytes = None, index_base: int = 0) -> int:
+        """The combined check of a uniform batch at the capacity shape over the pool (bpp_pool_verify_combined): every
+        shard's weighted sum, one reduce on shard 0's device.  -> 0 iff the batch passes (an empty batch does)."""
+        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 3 + 2 * ((self.n * self.m).bit_length() - 1) + self.m,
+                                                                      self.arith.PW)
+        sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 3, 4)
+        if sc.shape[0] != pts.shape[0]:
+            raise RuntimeError("verify_combined: one scalar triple per proof record")
+        ok = np.ones(1, dtype=np.uint32)
+        check(_lib.lib().bpp_pool_verify_combined(self.handle, _ptr(pts) if len(pts) else None, _ptr(sc) if len(sc) else None,
+                                                  pts.shape[0], _weight_key_arg(weight_key, 0), ctypes.c_uint64(index_base),
+                                                  _ptr(ok)), "bpp_pool_verify_combined")
+        return int(ok[0])
 
 
 class PassGraph:

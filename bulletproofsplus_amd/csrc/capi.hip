@@ -1333,6 +1333,109 @@ extern "C" int bpp_range_prove_batch_serialized_mixed(bpp_verifier* engine, cons
     });
 }
 
+// ---- the verifier pool: one batch sharded over the devices of a node (shard.hpp, pool.hpp; see include/bpp_amd.h) ----
+#include "pool.hpp"
+
+extern "C" int bpp_shard_cuts(const uint32_t* m_of, size_t count, size_t world, size_t* out_cuts) {
+    return guarded([&] { return shard_cuts(m_of, count, world, out_cuts); });
+}
+
+extern "C" int bpp_pool_create(int curve_id, const int* devices, size_t n_dev, const uint64_t* gh, const uint64_t* G,
+                               const uint64_t* H, size_t n, size_t m, int window_bits, void** out) {
+    if (!out) return fail(BPP_E_ARG, "null out");
+    *out = nullptr;
+    if (!devices || !gh || !G || !H) return fail(BPP_E_ARG, "null argument");
+    if (n_dev == 0 || n_dev > POOL_MAX_SHARDS) return fail(BPP_E_ARG, "n_dev must be in [1, 16]");
+    return guarded([&] {
+        bpp_pool* pool = nullptr;
+        const int rc = pool_create(curve_id, devices, n_dev, gh, G, H, n, m, window_bits, &pool);
+        *out = pool;
+        return rc;
+    });
+}
+extern "C" void bpp_pool_destroy(void* pool) {
+    (void)guarded([&] {
+        pool_release(static_cast<bpp_pool*>(pool));
+        return BPP_OK;
+    });
+}
+extern "C" size_t bpp_pool_size(const void* pool) {
+    size_t r = 0;
+    if (pool)
+        (void)guarded([&] {
+            r = static_cast<const bpp_pool*>(pool)->shards.size();
+            return BPP_OK;
+        });
+    return r;
+}
+extern "C" int bpp_pool_device(const void* pool, size_t shard) {
+    int d = -1;
+    if (pool)
+        (void)guarded([&] {
+            const bpp_pool* p = static_cast<const bpp_pool*>(pool);
+            if (shard < p->shards.size()) d = p->shards[shard].device;
+            return BPP_OK;
+        });
+    return d;
+}
+extern "C" int bpp_pool_verifier(void* pool, size_t shard, bpp_verifier** out) {
+    if (!out) return fail(BPP_E_ARG, "null out");
+    *out = nullptr;
+    if (!pool) return fail(BPP_E_ARG, "null pool");
+    return guarded([&] {
+        bpp_pool* p = static_cast<bpp_pool*>(pool);
+        if (shard >= p->shards.size()) return fail(BPP_E_ARG, "no such shard");
+        *out = p->shards[shard].v;
+        return BPP_OK;
+    });
+}
+
+extern "C" int bpp_pool_verify_mixed(void* pool, const uint64_t* points, const uint64_t* scalars, const uint32_t* m_of,
+                                     size_t count, uint32_t* out_ok) {
+    if (!pool) return fail(BPP_E_ARG, "null pool");
+    if (count == 0) return BPP_OK;
+    if (!points || !scalars || !out_ok) return fail(BPP_E_ARG, "null argument");
+    return guarded({count, "count"}, [&] {
+        return pool_verify_mixed(static_cast<bpp_pool*>(pool), points, scalars, m_of, count, out_ok);
+    });
+}
+
+extern "C" int bpp_pool_verify_serialized_mixed(void* pool, const uint8_t* proofs, const uint8_t* commitments,
+                                                const uint32_t* m_of, size_t count, int flags, int mode,
+                                                const uint8_t* weight_key, uint64_t index_base, uint32_t group,
+                                                uint32_t* out_ok, uint64_t* stats) {
+    if (!pool) return fail(BPP_E_ARG, "null pool");
+    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED)) return fail(BPP_E_ARG, "unknown flag");
+    if (mode != BPP_POOL_EXACT && mode != BPP_POOL_GROUPED) return fail(BPP_E_ARG, "unknown mode");
+    if (mode == BPP_POOL_GROUPED) {
+        if (!weight_key) return fail(BPP_E_ARG, "null weight_key: the grouped check needs a weight key");
+        if (group < 2 || (group & (group - 1))) return fail(BPP_E_ARG, "group must be a power of two >= 2");
+    }
+    if (count == 0) {
+        if (mode == BPP_POOL_GROUPED && stats) stats[0] = stats[1] = 0;
+        return BPP_OK;
+    }
+    if (!proofs || !commitments || !m_of || !out_ok) return fail(BPP_E_ARG, "null argument");
+    return guarded({count, "count"}, [&] {
+        return pool_verify_serialized_mixed(static_cast<bpp_pool*>(pool), proofs, commitments, m_of, count, flags, mode,
+                                            weight_key, index_base, group, out_ok, stats);
+    });
+}
+
+extern "C" int bpp_pool_verify_combined(void* pool, const uint64_t* points, const uint64_t* scalars, size_t count,
+                                        const uint8_t* weight_key, uint64_t index_base, uint32_t* out_ok) {
+    if (!pool || !out_ok) return fail(BPP_E_ARG, "null argument");
+    if (!weight_key) return fail(BPP_E_ARG, "null weight_key: the combined check needs a weight key");
+    if (count == 0) {
+        *out_ok = 0;
+        return BPP_OK;
+    }
+    if (!points || !scalars) return fail(BPP_E_ARG, "null argument");
+    return guarded({count, "count"}, [&] {
+        return pool_verify_combined(static_cast<bpp_pool*>(pool), points, scalars, count, weight_key, index_base, out_ok);
+    });
+}
+
 // ---- device-side unit-test hooks (tests/ check the device field / group primitives against a CPU checker) --
 // (their raw-image siblings bpp_debug_field_raw_op, bpp_debug_madd_lazy_raw and bpp_debug_glv_op live in tu_debug.hip,
 // a translation unit of their own)

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -270,12 +271,22 @@ template <class C>
 inline int launch_verify_scalars(const VerifyShape& s, const uint32_t* d_proof_scalars, const uint32_t* d_challenges,
                                  uint32_t ch_stride, uint32_t* d_out, size_t count, uint32_t* d_prep, hipStream_t st) {
     // above the default dynamic-LDS limit: opt in (160 KB per CU on gfx950) to the largest shape seen so far -- the
-    // passes of a mixed batch (bpp_verifier_run_mixed) run the smaller shapes first
-    static size_t lds_opted_in = 64 * 1024;
-    if (vs_lds_bytes<C>(s) > lds_opted_in) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vs_expand<C>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)vs_lds_bytes<C>(s)));
-        lds_opted_in = vs_lds_bytes<C>(s);
+    // passes of a mixed batch (bpp_verifier_run_mixed) run the smaller shapes first.  The record is kept per device (the
+    // attribute belongs to the kernel's code object on the current device) and under a lock: a verifier serves several
+    // host threads, and a pool (pool.hpp) runs one thread per device.
+    if (vs_lds_bytes<C>(s) > 64 * 1024) {
+        constexpr int MAX_DEV = 64;
+        static std::mutex mu;
+        static size_t lds_opted_in[MAX_DEV] = {};   // 0: the default limit
+        int dev = -1;
+        HIPCHK(hipGetDevice(&dev));
+        const std::lock_guard<std::mutex> lock(mu);
+        const bool known = dev >= 0 && dev < MAX_DEV;   // an ordinal beyond the record opts in every time
+        if (!known || vs_lds_bytes<C>(s) > lds_opted_in[dev]) {
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vs_expand<C>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)vs_lds_bytes<C>(s)));
+            if (known) lds_opted_in[dev] = vs_lds_bytes<C>(s);
+        }
     }
     hipLaunchKernelGGL(k_vs_prepare<C>, dim3(cdiv(count, 64)), dim3(64), 0, st, s, d_proof_scalars, d_challenges, ch_stride,
                        d_prep, d_out, count);

@@ -667,6 +667,77 @@ int bpp_wip_verify_batch(bpp_verifier *v, const uint64_t *points, const uint64_t
 int bpp_proofs_scan(int curve_id, size_t n, int version, const uint8_t *proofs, size_t proofs_bytes, uint32_t *m_of,
                     size_t max_count, size_t *out_count);
 
+/* ---- verifier pool: ONE batch sharded over the devices of a node, behind the C ABI ----------------------------------
+ * Proofs are independent units (reference src/range/mod.rs:503-509: each proof ends in its own check), so a batch is cut
+ * into contiguous slices, one per shard, every shard runs the existing device pass over its slice on its own device and
+ * host thread, and the verdicts come back in caller order.  The only data that cross devices are the verdict words and,
+ * for the combined check, one partial of bpp_verifier_partial_bytes() bytes per shard ("a single reduce for the final
+ * multiscalar check").  No kernel is added: the hot path is the passes above, run concurrently.
+ *
+ * THE CUT.  bpp_shard_cuts writes world + 1 cuts; shard r takes proofs [cuts[r], cuts[r + 1]): contiguous, in caller
+ * order, possibly empty.  cuts[0] = 0, cuts[world] = count.
+ *   m_of == NULL (uniform batch): base, rem = divmod(count, world), cuts[r] = r base + min(r, rem).
+ *   otherwise proof i costs m_of[i] (n is fixed and a pass costs ~ n m_i): cuts[r], 0 < r < world, is the smallest i with
+ *   world * sum_{j<i} m_of[j] >= r * sum_all m_of[j], in 64-bit arithmetic.  The cuts are monotone and every shard costs
+ *   less than total / world + max m.
+ * BPP_E_ARG: world = 0 or > 16, out_cuts NULL, count >= 2^32, an m_of[i] = 0 (the text names i).  Pure host code.
+ *
+ * THE POOL.  The handle is an opaque pointer, passed as void * like the streams of this header.  bpp_pool_create takes
+ * 1 <= n_dev <= 16 ordinals and builds, concurrently, per shard r one context and one verifier of capacity (n, m) on
+ * devices[r] (arguments as for bpp_init / bpp_verifier_create), with a non-blocking stream of its own.  An ordinal may
+ * appear more than once: the shards then share that device -- the way to exercise a pool on a one-GPU machine.  On any
+ * failure everything built is destroyed, *out stays NULL, and the code and text of the LOWEST failing shard are returned,
+ * the text prefixed "shard r (device d): " (BPP_E_NOMEM for tables that do not fit, BPP_E_HIP for "no such HIP device").
+ * Each shard owns its device input, verdict and workspace buffers; they grow on demand and are reused across calls.
+ * bpp_pool_device: the ordinal of a shard, -1 if out of range.  bpp_pool_verifier: *out = the shard's verifier, BORROWED
+ * (it dies with the pool), for callers who hold device buffers and use the _device entries, or who set
+ * bpp_verifier_set_subgroup_check on each shard before a call; BPP_E_ARG and *out = NULL if out of range.
+ * A pool is used by ONE host thread at a time; the borrowed verifiers follow their own rules above.  Worker threads are
+ * started per call and joined before it returns.
+ *
+ * THE VERIFY CALLS take host pointers, are synchronous and give verdicts in caller order.
+ *   bpp_pool_verify_mixed: layout and semantics of bpp_range_verify_batch_mixed (packed records, the reference's literal
+ *     challenges); m_of == NULL: every proof has the capacity m.  out_ok is, word for word, what the single-verifier call
+ *     writes for the whole batch.
+ *   bpp_pool_verify_serialized_mixed: layout, flags and statuses 0 / 1 / 2 of bpp_range_verify_batch_serialized_mixed;
+ *     m_of is required (bpp_proofs_scan recovers it from a bare stream).
+ *       mode = BPP_POOL_EXACT  : each shard runs bpp_range_verify_batch_serialized_mixed_device over its slice;
+ *                                weight_key, group and stats are ignored and may be NULL / 0.
+ *       mode = BPP_POOL_GROUPED: each shard runs bpp_range_verify_batch_serialized_grouped_mixed_device with
+ *                                index_base + cuts[r], so proof i of the caller's numbering is weighted by
+ *                                PRF(weight_key, index_base + i) whatever the cut.  weight_key (32 bytes) is required,
+ *                                group is a power of two >= 2.  Groups are formed INSIDE a shard, and stats = [groups
+ *                                that failed, proofs re-verified exactly] is the sum over the shards: stats therefore
+ *                                DEPEND ON THE CUT (on the number of shards); the statuses do not.
+ *     The 4 GiB limits on container and commitment bytes apply per shard.
+ *   bpp_pool_verify_combined: the combined check of a uniform batch at the capacity shape, literal challenges.  Shard r
+ *     runs bpp_verifier_run_combined with index_base + cuts[r]; the partials of the non-empty shards are copied to shard
+ *     0's device (a peer copy; no peer access needs enabling) and summed there by bpp_verifier_sum_partials.
+ *     *out_ok (one word) = 0 iff the sum is the identity and no shard saw an invalid point; count = 0 gives 0.
+ *     weight_key (32 bytes) is required.
+ * Errors.  Argument errors are found before any thread starts and return BPP_E_ARG: a NULL pool or required pointer,
+ * count >= 2^32, an m_of[i] that is zero, not a power of two or above the capacity (the text names the CALLER's index i),
+ * an unknown flag or mode, a missing key, a bad group.  A runtime failure in a shard returns the code of the lowest
+ * failing shard with the prefixed text.  In both cases out_ok and stats are not written: the shards write into the pool's
+ * own host buffer, which is copied out only when every shard returned BPP_OK.  count = 0 is BPP_OK.  After a HIP
+ * failure (BPP_E_HIP) the pool is usable only for bpp_pool_destroy. */
+#define BPP_POOL_EXACT 0
+#define BPP_POOL_GROUPED 1
+int bpp_shard_cuts(const uint32_t *m_of, size_t count, size_t world, size_t *out_cuts);
+int bpp_pool_create(int curve_id, const int *devices, size_t n_dev, const uint64_t *gh, const uint64_t *G, const uint64_t *H,
+                    size_t n, size_t m, int window_bits, void **out);
+void bpp_pool_destroy(void *pool);
+size_t bpp_pool_size(const void *pool);
+int bpp_pool_device(const void *pool, size_t shard);
+int bpp_pool_verifier(void *pool, size_t shard, bpp_verifier **out);
+int bpp_pool_verify_mixed(void *pool, const uint64_t *points, const uint64_t *scalars, const uint32_t *m_of, size_t count,
+                          uint32_t *out_ok);
+int bpp_pool_verify_serialized_mixed(void *pool, const uint8_t *proofs, const uint8_t *commitments, const uint32_t *m_of,
+                                     size_t count, int flags, int mode, const uint8_t *weight_key, uint64_t index_base,
+                                     uint32_t group, uint32_t *out_ok, uint64_t *stats);
+int bpp_pool_verify_combined(void *pool, const uint64_t *points, const uint64_t *scalars, size_t count,
+                             const uint8_t *weight_key, uint64_t index_base, uint32_t *out_ok);
+
 /* name of the kernel that dominates bpp_verifier_run (for profilers) and its launch geometry */
 const char *bpp_verifier_dominant_kernel(void);
 
