@@ -88,3 +88,20 @@ def run_grouped_device(torch, bv, records, scalars, group, seed=12345, index_bas
                                            d_challenges=d_ch.data_ptr() if d_ch is not None else 0)
     torch.cuda.synchronize()
     return d_ok.cpu().numpy().astype(np.uint32)[:count], failed, redone
+
+
+def msm_device_tensors(torch, B, a, d_scalars, d_points, c=0):
+    """bpp_msm_device on int64 tensors that are already on the device: scalars (n, 4), wire points (n, PW), n >= 1
+    -> (wire point numpy, status word, the call's shape as msm_profile reports it)"""
+    dev = d_scalars.device
+    n = d_scalars.shape[0]
+    assert d_points.shape == (n, a.PW) and d_scalars.is_contiguous() and d_points.is_contiguous()
+    d_out = torch.full((a.PW,), -1, dtype=torch.int64, device=dev)
+    d_st = torch.full((1,), 7, dtype=torch.int32, device=dev)
+    wsb = B.msm_workspace_bytes(a, n, c)
+    assert wsb > 0
+    d_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    B.msm_device(a, d_scalars.data_ptr(), d_points.data_ptr(), n, d_out.data_ptr(), d_ws.data_ptr(), wsb, window_bits=c,
+                 d_status=d_st.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return d_out.cpu().numpy().view(np.uint64), int(d_st.item()), B.msm_profile(a)[2]
