@@ -171,6 +171,18 @@ impl RangeProver {
         self.gamma_vec.push(gamma);
         self.commitment_vec.push(pk.commitment(v, &gamma)); // keeps the `v as i32` truncation of prover.rs:37
     }
+    /// `commit` for a whole 64-bit amount: V = v g + gamma h without the `v as i32` of prover.rs:37 (a two-term MulVec) --
+    /// the commitment a proof made under BPP_PROVE_AMOUNT64 verifies against
+    pub fn commit_amount(&mut self, pk: &PublicKey, v: u64, gamma: PrimeFieldElem) {
+        let sc = flat_scalars(&[PrimeFieldElem([v, 0, 0, 0]), gamma]);
+        let pts = flat_points(&[pk.g, pk.h]);
+        let mut out = [0u64; PW];
+        let rc = unsafe { ffi::bpp_msm(ctx(), sc.as_ptr(), pts.as_ptr(), 2, out.as_mut_ptr()) };
+        assert!(rc == 0, "bpp_msm failed: {}", rc);
+        self.v_vec.push(v);
+        self.gamma_vec.push(gamma);
+        self.commitment_vec.push(Point(out));
+    }
 }
 
 /// README.md:47-55 (the reference's code has no such type; `verify` takes the slice, src/range/mod.rs:57-62)
@@ -378,6 +390,58 @@ impl BatchVerifier {
         let rc = unsafe { ffi::bpp_range_verify_batch(self.handle, pw.as_ptr(), sw.as_ptr(), batch.len(), ok.as_mut_ptr()) };
         assert!(rc == 0, "bpp_range_verify_batch: {}", rc);
         ok.iter().map(|&v| if v == 0 { Ok(()) } else { Err(ProofError::VerificationError) }).collect()
+    }
+    /// RangeProof::prove for a block in which proof i has values[i].len() = m_i values (a power of two <= m), each against the
+    /// prefix key PublicKey::new(n m_i) (include/bpp_amd.h: bpp_range_prove_batch_mixed, literal challenges and blinding).
+    /// Returns each proof with its commitments.  amount64 = false: the commitments are RangeProver::commit's, with the
+    /// `v as i32` of src/range/prover.rs:37; true (BPP_PROVE_AMOUNT64): V = v g + gamma h over the whole u64, so an amount of
+    /// 2^31 or more proves and verifies.
+    pub fn prove_batch_mixed(&self, values: &[Vec<u64>], gammas: &[Vec<PrimeFieldElem>], amount64: bool) -> Vec<(RangeProof, Vec<Point>)> {
+        assert!(values.len() == gammas.len(), "one gamma list per proof");
+        let logn = self.k - self.m.trailing_zeros() as usize;
+        let (mut vs, mut gs, mut ms, mut npts) = (Vec::<u64>::new(), Vec::<PrimeFieldElem>::new(), Vec::<u32>::new(), 0usize);
+        for (v, g) in values.iter().zip(gammas) {
+            assert!(v.len() == g.len() && v.len().is_power_of_two() && v.len() <= self.m, "m_i: a power of two <= m, one gamma per value");
+            vs.extend_from_slice(v);
+            gs.extend_from_slice(g);
+            ms.push(v.len() as u32);
+            npts += 3 + 2 * (logn + v.len().trailing_zeros() as usize) + v.len();
+        }
+        let gw = flat_scalars(&gs);
+        let mut pts = vec![0u64; npts * PW];
+        let mut sc = vec![0u64; values.len() * 12];
+        let flags = if amount64 { ffi::BPP_PROVE_AMOUNT64 } else { 0 };
+        let rc = unsafe {
+            ffi::bpp_range_prove_batch_mixed(self.handle, vs.as_ptr(), gw.as_ptr(), ms.as_ptr(), values.len(), flags, std::ptr::null(), 0,
+                                             pts.as_mut_ptr(), sc.as_mut_ptr(), std::ptr::null_mut())
+        };
+        assert!(rc == 0, "bpp_range_prove_batch_mixed: {}", rc);
+        let all = unflat_points(&pts);
+        let (mut out, mut at) = (Vec::with_capacity(values.len()), 0usize);
+        for (i, v) in values.iter().enumerate() {
+            let k = logn + v.len().trailing_zeros() as usize;
+            let p = &all[at..at + 3 + 2 * k + v.len()];
+            let s = |j: usize| PrimeFieldElem([sc[12 * i + 4 * j], sc[12 * i + 4 * j + 1], sc[12 * i + 4 * j + 2], sc[12 * i + 4 * j + 3]]);
+            out.push((RangeProof {
+                A: p[0],
+                proof: WeightedInnerProductProof { A: p[1], B: p[2], L_vec: p[3..3 + k].to_vec(), R_vec: p[3 + k..3 + 2 * k].to_vec(),
+                                                   r_prime: s(0), s_prime: s(1), d_prime: s(2) },
+            }, p[3 + 2 * k..].to_vec()));
+            at += p.len();
+        }
+        out
+    }
+    /// RangeProver::commit (src/range/prover.rs:28-42) for a block of values over this engine's g and h, through its
+    /// window tables (include/bpp_amd.h: bpp_commit_batch).  amount64 = false keeps the `v as i32` of prover.rs:37, so each
+    /// point equals PublicKey::commitment; true (BPP_PROVE_AMOUNT64) commits the whole u64.
+    pub fn commit_batch(&self, values: &[u64], gammas: &[PrimeFieldElem], amount64: bool) -> Vec<Point> {
+        assert!(values.len() == gammas.len(), "one gamma per value");
+        let gw = flat_scalars(gammas);
+        let mut out = vec![0u64; values.len() * PW];
+        let flags = if amount64 { ffi::BPP_PROVE_AMOUNT64 } else { 0 };
+        let rc = unsafe { ffi::bpp_commit_batch(self.handle, values.as_ptr(), gw.as_ptr(), values.len(), flags, out.as_mut_ptr()) };
+        assert!(rc == 0, "bpp_commit_batch: {}", rc);
+        unflat_points(&out)
     }
     /// A batch of mixed aggregation sizes against this verifier's tables (include/bpp_amd.h: bpp_range_verify_batch_mixed):
     /// proof i with m_i = its commitments' count, a power of two <= m.  Each `Result` is

@@ -28,6 +28,9 @@ from . import _lib
 from ._lib import BLS12_381_G1, SECP256K1, ED25519, CURVE_IDS, BppError, check  # noqa: F401
 
 
+AMOUNT64 = 0x100   # BPP_PROVE_AMOUNT64 (include/bpp_amd.h): commitments over the whole 64-bit amount
+
+
 class ProofError(Exception):
     """reference src/errors.rs:14-50"""
 
@@ -393,10 +396,17 @@ class RangeProver:
     def new(cls):
         return cls()
 
-    def commit(self, pk: PublicKey, v: int, gamma):
+    def commit(self, pk: PublicKey, v: int, gamma, amount64: bool = False):
+        """range/prover.rs:28-42.  amount64=False keeps the `v as i32` of prover.rs:37; amount64=True commits the whole
+        64-bit amount, v g + gamma h (a two-term MulVec), what a proof of an amount of 2^31 or more verifies against."""
         g = scalar_to_wire(gamma)
-        out = np.zeros(pk.arith.PW, dtype=np.uint64)
-        check(_lib.lib().bpp_commit(pk.arith.handle, _ptr(pk.gh), ctypes.c_uint64(v), _ptr(g), _ptr(out)), "bpp_commit")
+        if amount64:
+            if not 0 <= int(v) < 1 << 64:
+                raise ValueError("amount64: 0 <= v < 2^64")
+            out = pk.commitment(int(v), g)
+        else:
+            out = np.zeros(pk.arith.PW, dtype=np.uint64)
+            check(_lib.lib().bpp_commit(pk.arith.handle, _ptr(pk.gh), ctypes.c_uint64(v), _ptr(g), _ptr(out)), "bpp_commit")
         self.v_vec.append(int(v))
         self.gamma_vec.append(g)
         self.commitment_vec.append(out)
@@ -949,16 +959,32 @@ class BatchVerifier:
         check(_lib.lib().bpp_verifier_sum_partials(self.handle, d_partials, n, d_ok, stream or None),
               "bpp_verifier_sum_partials")
 
-    def prove_batch(self, values, gammas, transcript: bool = False, blind_key: bytes = None, index_base: int = 0):
+    def prove_batch(self, values, gammas, transcript: bool = False, blind_key: bytes = None, index_base: int = 0,
+                    amount64: bool = False):
         """RangeProof::prove + RangeProver::commit for `count` provers sharing this engine's (pk, n, m).
         transcript=True: challenges from the Fiat-Shamir transcript (csrc/transcript.hpp) instead of the reference's
         constants -- not a reference code path, parity unpinned.  blind_key (32 secret bytes, transcript mode only): the
         blinding values come from this key (include/bpp_amd.h "Blinding"); None = the reference's literals, which hide nothing.
         values: (count, m) ints < 2^64 ; gammas: (count, m) scalars (ints or (count, m, 4) uint64).
         Returns (points (count, 3+2k, PW), scalars (count, 3, 4), V (count, m, PW)) in wire format --
-        bit-identical to RangeProof.prove / RangeProver.commit one by one."""
+        bit-identical to RangeProof.prove / RangeProver.commit one by one.
+        amount64=True (BPP_PROVE_AMOUNT64): the commitments are v g + gamma h with the whole 64-bit v instead of the
+        `v as i32` of range/prover.rs:37; routed through the mixed call with every m_i = m."""
         vals = np.ascontiguousarray(np.asarray(values, dtype=np.uint64).reshape(-1, self.m))
         count = vals.shape[0]
+        if amount64:
+            if isinstance(gammas, np.ndarray) and gammas.dtype == np.uint64 and gammas.ndim == 3:
+                grows = [[gammas[i, j] for j in range(self.m)] for i in range(count)]
+            else:
+                grows = [list(row) for row in gammas]
+            recs, sc = self.prove_batch_mixed([[int(x) for x in row] for row in vals], grows, transcript=transcript,
+                                              blind_key=blind_key, index_base=index_base, amount64=True)
+            PW, nrec = self.arith.PW, 3 + 2 * self.k
+            pts = np.zeros((count, nrec, PW), dtype=np.uint64)
+            V = np.zeros((count, self.m, PW), dtype=np.uint64)
+            for i, r in enumerate(recs):
+                pts[i], V[i] = r[:nrec], r[nrec:]
+            return pts, sc, V
         if isinstance(gammas, np.ndarray) and gammas.dtype == np.uint64 and gammas.ndim == 3:
             gm = np.ascontiguousarray(gammas)
         else:
@@ -1093,6 +1119,31 @@ class BatchVerifier:
             return ok, osc, ores
         return ok
 
+    # ---- commitments for a block of amounts through the engine's tables (include/bpp_amd.h) ----
+    def commit_batch_device(self, d_values: int, d_gammas: int, count: int, d_out_V: int, stream: int = 0,
+                            amount64: bool = False):
+        """RangeProver::commit (range/prover.rs:28-42) for `count` resident values and gammas over this engine's g and h:
+        d_out_V receives count wire points.  amount64=False keeps the `v as i32` of prover.rs:37.  Only enqueues."""
+        check(_lib.lib().bpp_commit_batch_device(self.handle, d_values, d_gammas, count, AMOUNT64 if amount64 else 0, d_out_V,
+                                                 stream or None), "bpp_commit_batch_device")
+
+    def commit_batch(self, values, gammas, amount64: bool = False) -> np.ndarray:
+        """values: count ints < 2^64; gammas: count scalars (ints or (count, 4) uint64) -> (count, PW) wire points,
+        s g + gamma h with s = new(v as i32) (range/prover.rs:37; equal to RangeProver.commit one by one) or, amount64=True,
+        the whole value"""
+        vals = np.ascontiguousarray(np.asarray([int(x) for x in values], dtype=np.uint64))
+        count = len(vals)
+        if isinstance(gammas, np.ndarray) and gammas.dtype == np.uint64 and gammas.ndim == 2:
+            gm = np.ascontiguousarray(gammas)
+        else:
+            gm = scalars_to_wire(gammas) if count else np.zeros((0, 4), dtype=np.uint64)
+        if len(gm) != count:
+            raise RuntimeError("one gamma per value")
+        out = np.zeros((count, self.arith.PW), dtype=np.uint64)
+        check(_lib.lib().bpp_commit_batch(self.handle, _ptr(vals) if count else None, _ptr(gm) if count else None, count,
+                                          AMOUNT64 if amount64 else 0, _ptr(out) if count else None), "bpp_commit_batch")
+        return out
+
     # ---- proving blocks of mixed aggregation sizes: proof i has ms[i] values (include/bpp_amd.h) ----
     def prover_mixed_workspace_bytes(self, ms, serialized: bool = False) -> int:
         """bytes of device workspace prove_mixed_device (serialized: prove_serialized_mixed_device) needs (0: an m_i is
@@ -1103,27 +1154,30 @@ class BatchVerifier:
 
     def prove_mixed_device(self, d_values: int, d_gammas: int, ms, d_out_points: int, d_out_scalars: int, d_workspace: int,
                            workspace_bytes: int, stream: int = 0, transcript: bool = False, d_out_challenges: int = 0,
-                           blind_key: bytes = None, index_base: int = 0, d_blinding: int = 0):
+                           blind_key: bytes = None, index_base: int = 0, d_blinding: int = 0, amount64: bool = False):
         """RangeProof::prove for a resident block in which proof i has ms[i] values (packed in caller order, as the gammas),
         each against the prefix key PublicKey::new(n ms[i]).  d_out_points receives the packed records [A, wip.A, wip.B,
         L.., R.., V..] run_mixed_device reads, d_out_scalars (count, 3) scalars, d_out_challenges the packed challenge
-        blocks.  Proof i's blinding index is index_base + i.  Blocks while it uploads the per-proof index."""
+        blocks.  Proof i's blinding index is index_base + i.  Blocks while it uploads the per-proof index.
+        amount64=True (BPP_PROVE_AMOUNT64): commitments over the whole 64-bit values, not `v as i32` (range/prover.rs:37)."""
         m = self._ms(ms)
         check(_lib.lib().bpp_range_prove_batch_mixed_device(
-            self.handle, d_values, d_gammas, _ptr(m) if len(m) else None, len(m), 1 if transcript else 0, blind_key,
+            self.handle, d_values, d_gammas, _ptr(m) if len(m) else None, len(m),
+            (1 if transcript else 0) | (AMOUNT64 if amount64 else 0), blind_key,
             ctypes.c_uint64(index_base), d_blinding or None, d_out_points, d_out_scalars, d_out_challenges or None, d_workspace,
             workspace_bytes, stream or None), "bpp_range_prove_batch_mixed_device")
 
     def prove_serialized_mixed_device(self, d_values: int, d_gammas: int, ms, d_out_proofs: int, d_out_commitments: int,
                                       d_workspace: int, workspace_bytes: int, stream: int = 0, transcript: bool = False,
                                       uncompressed: bool = False, blind_key: bytes = None, index_base: int = 0,
-                                      d_blinding: int = 0):
+                                      d_blinding: int = 0, amount64: bool = False):
         """prove_mixed_device with the proofs written as containers packed back to back in caller order and ms[i] encoded
         commitments per proof: the two inputs of verify_serialized_mixed_device"""
         m = self._ms(ms)
         check(_lib.lib().bpp_range_prove_batch_serialized_mixed_device(
             self.handle, d_values, d_gammas, _ptr(m) if len(m) else None, len(m),
-            (1 if transcript else 0) | (2 if uncompressed else 0), blind_key, ctypes.c_uint64(index_base), d_blinding or None,
+            (1 if transcript else 0) | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0), blind_key,
+            ctypes.c_uint64(index_base), d_blinding or None,
             d_out_proofs, d_out_commitments, d_workspace, workspace_bytes, stream or None),
             "bpp_range_prove_batch_serialized_mixed_device")
 
@@ -1142,11 +1196,12 @@ class BatchVerifier:
         return vals, gm, ms
 
     def prove_batch_mixed(self, values, gammas, transcript: bool = False, blind_key: bytes = None, index_base: int = 0,
-                          challenges: bool = False):
+                          challenges: bool = False, amount64: bool = False):
         """values[i], gammas[i]: the m_i values and gammas of proof i (m_i a power of two <= m).  -> (records, scalars):
         records[i] the (mixed_points(m_i), PW) wire record [A, wip.A, wip.B, L.., R.., V..] of proof i, bit for bit what
         a dedicated (n, m_i) engine of the same key proves; scalars (count, 3, 4).  challenges=True: also the list of
-        per-proof challenge blocks (3 + k_i, 4)."""
+        per-proof challenge blocks (3 + k_i, 4).  amount64=True (BPP_PROVE_AMOUNT64): each V is v g + gamma h over the whole
+        64-bit value instead of the `v as i32` of range/prover.rs:37, so amounts of 2^31 and more prove and verify."""
         if blind_key is not None and (not transcript or len(blind_key) != 32):
             raise ValueError("blind_key: 32 bytes, transcript mode only")
         vals, gm, ms = self._mixed_inputs(values, gammas)
@@ -1159,7 +1214,8 @@ class BatchVerifier:
         ch = np.zeros((max(sum(nch), 1), 4), dtype=np.uint64)
         check(_lib.lib().bpp_range_prove_batch_mixed(
             self.handle, _ptr(vals) if len(vals) else None, _ptr(gm) if len(vals) else None, _ptr(ms) if count else None, count,
-            1 if transcript else 0, blind_key, ctypes.c_uint64(index_base), _ptr(pts), _ptr(sc) if count else None,
+            (1 if transcript else 0) | (AMOUNT64 if amount64 else 0), blind_key, ctypes.c_uint64(index_base), _ptr(pts),
+            _ptr(sc) if count else None,
             _ptr(ch) if challenges else None), "bpp_range_prove_batch_mixed")
         po, co = np.concatenate([[0], np.cumsum(npts)]).astype(int), np.concatenate([[0], np.cumsum(nch)]).astype(int)
         recs = [pts[po[i]:po[i + 1]] for i in range(count)]
@@ -1168,7 +1224,7 @@ class BatchVerifier:
         return recs, sc
 
     def prove_serialized_mixed(self, values, gammas, transcript: bool = False, blind_key: bytes = None, index_base: int = 0,
-                               uncompressed: bool = False):
+                               uncompressed: bool = False, amount64: bool = False):
         """prove_batch_mixed as bytes -> (proofs, commitments, ms): the containers back to back in caller order, ms[i]
         encoded commitments per proof back to back -- what verify_serialized_mixed takes, and a stream proofs_scan frames"""
         if blind_key is not None and (not transcript or len(blind_key) != 32):
@@ -1182,7 +1238,8 @@ class BatchVerifier:
         cm = np.zeros(max(int(ms.sum()) * pb, 1), dtype=np.uint8)
         check(_lib.lib().bpp_range_prove_batch_serialized_mixed(
             self.handle, _ptr(vals) if len(vals) else None, _ptr(gm) if len(vals) else None, _ptr(ms) if count else None, count,
-            (1 if transcript else 0) | (2 if uncompressed else 0), blind_key, ctypes.c_uint64(index_base), _ptr(raw), _ptr(cm)),
+            (1 if transcript else 0) | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0), blind_key,
+            ctypes.c_uint64(index_base), _ptr(raw), _ptr(cm)),
             "bpp_range_prove_batch_serialized_mixed")
         return raw[:nbytes].tobytes(), cm[:int(ms.sum()) * pb].tobytes(), ms
 

@@ -2,6 +2,7 @@
 // checks, curve dispatch, then the per-curve implementations (impl_*.hpp, compiled in tu_*.hip).
 // No CPU fallback: every entry point launches HIP kernels on the context's device.
 #include "codec.hpp"
+#include "commit.hpp"
 #include "container_scan.hpp"
 #include "impl_msm.hpp"
 #include "impl_prove.hpp"
@@ -367,12 +368,18 @@ extern "C" int bpp_range_prove(bpp_ctx* ctx, const uint64_t* gh, const uint64_t*
             // reproduces it
             const size_t pw = (size_t)bpp_point_words(ctx->curve);
             std::vector<uint64_t> myV(m * pw), pts((3 + 2 * hit->v->s.k) * pw), sc(12);
-            const int rc = VerifyImpl<decltype(cv)>::prove_batch(hit->v.get(), v, gamma, 1, pts.data(), sc.data(), myV.data(),
-                                                                 false);
-            if (rc == BPP_OK && std::memcmp(myV.data(), V, m * pw * 8) == 0) {
-                std::memcpy(out_points, pts.data(), pts.size() * 8);
-                std::memcpy(out_scalars, sc.data(), 96);
-                return BPP_OK;
+            // ... first with the reference's own commitments, new(v as i32) g + gamma h (range/prover.rs:37), then with the
+            // untruncated ones a caller with an amount of 2^31 or more has to bring (BPP_PROVE_AMOUNT64): in literal mode the
+            // proof is a function of (v, gamma, V), so whichever form matches the caller's V is the fold-based path's output
+            for (int amount64 = 0; amount64 < 2; amount64++) {
+                const int rc = VerifyImpl<decltype(cv)>::prove_batch(hit->v.get(), v, gamma, 1, pts.data(), sc.data(), myV.data(),
+                                                                     false, nullptr, 0, amount64 != 0);
+                if (rc == BPP_OK && std::memcmp(myV.data(), V, m * pw * 8) == 0) {
+                    std::memcpy(out_points, pts.data(), pts.size() * 8);
+                    std::memcpy(out_scalars, sc.data(), 96);
+                    return BPP_OK;
+                }
+                if (rc != BPP_OK) break;
             }
         }
         std::string err;
@@ -1200,7 +1207,7 @@ extern "C" int bpp_range_prove_batch_mixed_device(bpp_verifier* engine, const ui
                                                   uint64_t* d_out_scalars, uint64_t* d_out_challenges, void* d_workspace,
                                                   size_t workspace_bytes, void* stream) {
     if (!engine) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~BPP_SER_TRANSCRIPT) return fail(BPP_E_ARG, "unknown flag");
+    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_PROVE_AMOUNT64)) return fail(BPP_E_ARG, "unknown flag");
     if (count == 0) return BPP_OK;
     if (!d_v || !d_gamma || !m_of || !d_out_points || !d_out_scalars || !d_workspace) return fail(BPP_E_ARG, "null argument");
     if (blind_key && d_blinding) return fail(BPP_E_ARG, "blind_key and d_blinding are both given");
@@ -1209,7 +1216,8 @@ extern "C" int bpp_range_prove_batch_mixed_device(bpp_verifier* engine, const ui
     return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
         return VerifyImpl<decltype(cv)>::prove_mixed(engine, d_v, d_gamma, m_of, count, (flags & BPP_SER_TRANSCRIPT) != 0, blind_key,
                                                      index_base, d_blinding, d_out_points, d_out_scalars, d_out_challenges,
-                                                     d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+                                                     d_workspace, workspace_bytes, static_cast<hipStream_t>(stream),
+                                                     (flags & BPP_PROVE_AMOUNT64) != 0);
     });
 }
 
@@ -1225,7 +1233,7 @@ extern "C" int bpp_range_prove_batch_serialized_mixed_device(bpp_verifier* engin
                                                              void* d_out_commitments, void* d_workspace, size_t workspace_bytes,
                                                              void* stream) {
     if (!engine) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED)) return fail(BPP_E_ARG, "unknown flag");
+    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED | BPP_PROVE_AMOUNT64)) return fail(BPP_E_ARG, "unknown flag");
     if (count == 0) return BPP_OK;
     if (!d_v || !d_gamma || !m_of || !d_out_proofs || !d_out_commitments || !d_workspace) return fail(BPP_E_ARG, "null argument");
     if (blind_key && d_blinding) return fail(BPP_E_ARG, "blind_key and d_blinding are both given");
@@ -1236,7 +1244,7 @@ extern "C" int bpp_range_prove_batch_serialized_mixed_device(bpp_verifier* engin
         return VerifyImpl<decltype(cv)>::prove_serialized_mixed(
             engine, d_v, d_gamma, m_of, count, (flags & BPP_SER_TRANSCRIPT) != 0, blind_key, index_base, d_blinding,
             static_cast<uint8_t*>(d_out_proofs), static_cast<uint8_t*>(d_out_commitments), d_workspace, workspace_bytes,
-            static_cast<hipStream_t>(stream), version);
+            static_cast<hipStream_t>(stream), version, (flags & BPP_PROVE_AMOUNT64) != 0);
     });
 }
 
@@ -1269,7 +1277,7 @@ extern "C" int bpp_range_prove_batch_mixed(bpp_verifier* engine, const uint64_t*
                                            size_t count, int flags, const uint8_t* blind_key, uint64_t index_base,
                                            uint64_t* out_points, uint64_t* out_scalars, uint64_t* out_challenges) {
     if (!engine) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~BPP_SER_TRANSCRIPT) return fail(BPP_E_ARG, "unknown flag");
+    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_PROVE_AMOUNT64)) return fail(BPP_E_ARG, "unknown flag");
     if (count == 0) return BPP_OK;
     if (!v || !gamma || !m_of || !out_points || !out_scalars) return fail(BPP_E_ARG, "null argument");
     return on_device(engine->ctx.device, {count, "count"}, [&]() -> int {
@@ -1306,7 +1314,7 @@ extern "C" int bpp_range_prove_batch_serialized_mixed(bpp_verifier* engine, cons
                                                       const uint32_t* m_of, size_t count, int flags, const uint8_t* blind_key,
                                                       uint64_t index_base, uint8_t* out_proofs, uint8_t* out_commitments) {
     if (!engine) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED)) return fail(BPP_E_ARG, "unknown flag");
+    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED | BPP_PROVE_AMOUNT64)) return fail(BPP_E_ARG, "unknown flag");
     if (count == 0) return BPP_OK;
     if (!v || !gamma || !m_of || !out_proofs || !out_commitments) return fail(BPP_E_ARG, "null argument");
     const int version = (flags & BPP_SER_UNCOMPRESSED) ? 2 : 1;
@@ -1330,6 +1338,31 @@ extern "C" int bpp_range_prove_batch_serialized_mixed(bpp_verifier* engine, cons
                                                                                            blind_key, index_base, nullptr, d0, d1,
                                                                                            dws, wsb, nullptr);
                                   });
+    });
+}
+
+// ---- commitments for a block of amounts through the engine's tables (commit.hpp; RangeProver::commit, range/prover.rs:28-42;
+// flags = 0 keeps the `v as i32` of range/prover.rs:37, BPP_PROVE_AMOUNT64 commits the whole u64) ----------------------------
+extern "C" int bpp_commit_batch_device(bpp_verifier* engine, const uint64_t* d_v, const uint64_t* d_gamma, size_t count, int flags,
+                                       uint64_t* d_out_V, void* stream) {
+    if (!engine) return fail(BPP_E_ARG, "null argument");
+    if (flags & ~BPP_PROVE_AMOUNT64) return fail(BPP_E_ARG, "unknown flag");
+    if (count == 0) return BPP_OK;
+    if (!d_v || !d_gamma || !d_out_V) return fail(BPP_E_ARG, "null argument");
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
+        return CommitImpl<decltype(cv)>::commit_batch_device(engine, d_v, d_gamma, count, (flags & BPP_PROVE_AMOUNT64) != 0, d_out_V,
+                                                             static_cast<hipStream_t>(stream));
+    });
+}
+
+extern "C" int bpp_commit_batch(bpp_verifier* engine, const uint64_t* v, const uint64_t* gamma, size_t count, int flags,
+                                uint64_t* out_V) {
+    if (!engine) return fail(BPP_E_ARG, "null argument");
+    if (flags & ~BPP_PROVE_AMOUNT64) return fail(BPP_E_ARG, "unknown flag");
+    if (count == 0) return BPP_OK;
+    if (!v || !gamma || !out_V) return fail(BPP_E_ARG, "null argument");
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
+        return CommitImpl<decltype(cv)>::commit_batch(engine, v, gamma, count, (flags & BPP_PROVE_AMOUNT64) != 0, out_V);
     });
 }
 

@@ -1,0 +1,102 @@
+// commit_walk.hpp -- one commitment s g + gamma h as a walk over the window-table rows of generators 0 (g) and 1 (h) of an
+// engine (kernels.hpp "window table"): RangeProver::commit, reference src/range/prover.rs:28-42, with the `v as i32` of
+// prover.rs:37 or, in amount mode (BPP_PROVE_AMOUNT64), the whole u64.  Plain C++ beside ec.hpp and fixed_glv.hpp, so the
+// host test (tests/host/commit_walk_host_test.cpp) compiles the very code k_commit_batch (commit.hpp) runs.
+//
+// The digits are those k_fixed_msm takes from the same tables: uniform layouts add the bias, cut signed digits of c bits
+// and keep what is left as the unsigned top digit; BLS12-381 splits each scalar with the endomorphism (glv_split_balanced),
+// sums both k2 halves negated, multiplies the accumulator's X by beta once and adds both k1 halves.  A non-zero digit is
+// one table entry and one lazy mixed addition; a zero digit is nothing, so a 64-bit amount costs at most
+// ceil(65 / c) additions on g whatever the scalar field's width.  xyzz_madd_lazy is complete (P + P, P - P): with the
+// reference's test key h = 2 g both occur.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "ed25519.hpp"
+#include "fixed_glv.hpp"
+
+namespace bpp {
+
+// the table serves the two halves of the endomorphism split (kernels.hpp fixed_glv<C>())
+template <class C>
+constexpr bool commit_walk_glv() {
+    return C::ID == 0;
+}
+
+// canonical words of the scalar on g: the amount itself, or PrimeFieldElem::new(v as i32) (negative: r - |v|)
+template <class C>
+BPP_HD void commit_amount_scalar(uint64_t v, bool amount64, uint32_t out[8]) {
+    using P = typename C::Fr;
+#pragma unroll
+    for (int t = 0; t < 8; t++) out[t] = 0;
+    if (amount64) {
+        out[0] = (uint32_t)v;
+        out[1] = (uint32_t)(v >> 32);
+        return;
+    }
+    const int32_t vi = (int32_t)(uint32_t)v;
+    if (vi >= 0)
+        out[0] = (uint32_t)vi;
+    else
+        fe_to_canonical(fe_from_i32<P>(vi), out);
+}
+
+// S: the window layout (VerifyShape, or the host test's restatement): c, W, half, per_f, bias[], and for the split
+// tables wc[], went[].  kv, kg: canonical scalars (< r) on g and h.  load_entry(e) -> Aff<C>: entry e of the table
+// (generator f's row starts at f * per_f).  add(acc, entry, neg): acc += neg ? -entry : entry.
+template <class C, class S, class Load, class Add>
+BPP_HD Xyzz<C> commit_walk(const S& s, const uint32_t kv[8], const uint32_t kg[8], Load&& load_entry, Add&& add) {
+    Xyzz<C> acc = xyzz_inf<C>();
+    if constexpr (commit_walk_glv<C>()) {
+        // the four halves stay in registers: they are chosen by selects on the (wave-uniform) step, never indexed
+        uint32_t k1v[4], k2v[4], k1g[4], k2g[4];
+        bool n1v, n2v, n1g, n2g;
+        glv_split_balanced<C>(kv, k1v, k2v, n1v, n2v);
+        glv_split_balanced<C>(kg, k1g, k2g, n1g, n2g);
+#pragma unroll 1
+        for (uint32_t step = 0; step < 4; step++) {   // k2 of v, k2 of gamma, then k1 of v, k1 of gamma
+            const bool phase = step >= 2;
+            const uint32_t f = step & 1u;
+            if (step == 2) xyzz_mul_x_beta(acc);   // [z^2] of the k2 sum, summed negated: psi(-S) = (beta X, Y)
+            uint32_t h[4];
+#pragma unroll
+            for (int t = 0; t < 4; t++) h[t] = phase ? (f ? k1g[t] : k1v[t]) : (f ? k2g[t] : k2v[t]);
+            const bool hneg = phase ? (f ? n1g : n1v) : !(f ? n2g : n2v);
+            uint32_t w[GLV_HALF_WORDS];
+            glv_biased(h, s.bias, w);
+            for (uint32_t j = 0; j < s.W; j++) {
+                const int32_t dg = glv_next_digit(w, s.wc[j]);   // width 0: the top window
+                if (dg == 0) continue;
+                const uint32_t mag = dg < 0 ? (uint32_t)(-dg) : (uint32_t)dg;
+                add(acc, load_entry((size_t)f * s.per_f + s.went[j] + (mag - 1)), (dg < 0) != hneg);
+            }
+        }
+    } else {
+        const uint32_t mask = (1u << s.c) - 1u;
+        for (uint32_t f = 0; f < 2; f++) {
+            const uint32_t* k = f ? kg : kv;
+            uint32_t w[10];
+            uint32_t carry = 0;
+#pragma unroll
+            for (int t = 0; t < 10; t++) {
+                const uint64_t x = (uint64_t)(t < 8 ? k[t] : 0u) + s.bias[t] + carry;
+                w[t] = (uint32_t)x;
+                carry = (uint32_t)(x >> 32);
+            }
+            for (uint32_t j = 0; j < s.W; j++) {
+                // windows below the top: signed digit; top window: what is left of the value, unsigned (<= top)
+                const int32_t dg = j + 1 < s.W ? (int32_t)(w[0] & mask) - (int32_t)s.half : (int32_t)w[0];
+#pragma unroll
+                for (int t = 0; t < 9; t++) w[t] = (w[t] >> s.c) | (w[t + 1] << (32 - s.c));
+                w[9] >>= s.c;
+                if (dg == 0) continue;
+                const uint32_t mag = dg < 0 ? (uint32_t)(-dg) : (uint32_t)dg;
+                add(acc, load_entry((size_t)f * s.per_f + (size_t)j * s.half + (mag - 1)), dg < 0);
+            }
+        }
+    }
+    return acc;
+}
+
+}  // namespace bpp

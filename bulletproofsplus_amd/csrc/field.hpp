@@ -733,6 +733,17 @@ BPP_HD Fe<P> fe_from_i32(int32_t n) {
     return fe_neg(fe_from_u32<P>((uint32_t)(-(int64_t)n)));
 }
 
+// a whole 64-bit amount, no truncation (every modulus here exceeds 2^64)
+template <class P>
+BPP_HD Fe<P> fe_from_u64(uint64_t x) {
+    static_assert(3 * LIMB_BITS >= 64 && P::NL >= 3, "a 64-bit value spans three limbs");
+    Fe<P> t = Fe<P>::zero();
+    t.l[0] = (uint32_t)x & LIMB_MASK;
+    t.l[1] = (uint32_t)(x >> LIMB_BITS) & LIMB_MASK;
+    t.l[2] = (uint32_t)(x >> (2 * LIMB_BITS));
+    return fe_mul(t, Fe<P>::r2());
+}
+
 // a^(p-2) by square-and-multiply over the bits of p-2 (a = 0 -> 0): ~1.5 BITS Montgomery products.  Kept
 // as the independent cross-check of fe_inv (tests/host/field_host_test.cpp, tools/ubench.hip).
 template <class P>

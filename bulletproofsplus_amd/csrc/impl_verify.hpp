@@ -589,14 +589,15 @@ struct VerifyImpl {
                                   size_t count, uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_V, bool fs,
                                   uint64_t* d_out_challenges, void* d_workspace, size_t workspace_bytes, hipStream_t st,
                                   const uint8_t* blind_key = nullptr, uint64_t index_base = 0,
-                                  const uint64_t* d_blinding = nullptr, const uint32_t* px = nullptr);
+                                  const uint64_t* d_blinding = nullptr, const uint32_t* px = nullptr, bool amount64 = false);
     static int prove_batch_device(bpp_verifier* v, const uint64_t* d_values, const uint64_t* d_gammas, size_t count,
                                   uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_V, bool fs,
                                   uint64_t* d_out_challenges, void* d_workspace, size_t workspace_bytes, hipStream_t st,
                                   const uint8_t* blind_key = nullptr, uint64_t index_base = 0,
-                                  const uint64_t* d_blinding = nullptr) {
+                                  const uint64_t* d_blinding = nullptr, bool amount64 = false) {
         return prove_batch_device(v, own(v), d_values, d_gammas, count, d_out_points, d_out_scalars, d_out_V, fs,
-                                  d_out_challenges, d_workspace, workspace_bytes, st, blind_key, index_base, d_blinding);
+                                  d_out_challenges, d_workspace, workspace_bytes, st, blind_key, index_base, d_blinding, nullptr,
+                                  amount64);
     }
 
     // ---- ... of a block of MIXED aggregation sizes (mixed.hpp prove_plan): proof i has m_of[i] values ---------------
@@ -638,23 +639,25 @@ struct VerifyImpl {
     static int prove_mixed(bpp_verifier* v, const uint64_t* d_values, const uint64_t* d_gammas, const uint32_t* m_of,
                            size_t count, bool fs, const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_blinding,
                            uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_challenges, void* d_workspace,
-                           size_t workspace_bytes, hipStream_t st);
+                           size_t workspace_bytes, hipStream_t st, bool amount64 = false);
     // ... as containers packed back to back in caller order (container i of container_bytes(k_i, version) bytes) and
     // m_i encoded commitments per proof in a buffer of their own: run_serialized_mixed's input
     static int prove_serialized_mixed(bpp_verifier* v, const uint64_t* d_values, const uint64_t* d_gammas, const uint32_t* m_of,
                                       size_t count, bool fs, const uint8_t* blind_key, uint64_t index_base,
                                       const uint64_t* d_blinding, uint8_t* d_out_proofs, uint8_t* d_out_commitments,
-                                      void* d_workspace, size_t workspace_bytes, hipStream_t st, uint32_t version);
+                                      void* d_workspace, size_t workspace_bytes, hipStream_t st, uint32_t version,
+                                      bool amount64 = false);
     // the shared body: plan p (with its indices) and layout L in hand, every class present proved with its view
     static int prove_mixed_classes(bpp_verifier* v, const MixedPlan& p, const ProveMixedLayout& L, const uint64_t* d_values,
                                    const uint64_t* d_gammas, bool fs, const uint8_t* blind_key, uint64_t index_base,
                                    const uint64_t* d_blinding, uint64_t* d_out_points, uint64_t* d_out_scalars,
-                                   uint64_t* d_out_challenges, uint8_t* ws, size_t workspace_bytes, hipStream_t st);
+                                   uint64_t* d_out_challenges, uint8_t* ws, size_t workspace_bytes, hipStream_t st,
+                                   bool amount64 = false);
 
     // host buffers in, host buffers out
     static int prove_batch(bpp_verifier* v, const uint64_t* values, const uint64_t* gammas, size_t count,
                            uint64_t* out_points, uint64_t* out_scalars, uint64_t* out_V, bool fs,
-                           const uint8_t* blind_key = nullptr, uint64_t index_base = 0);
+                           const uint8_t* blind_key = nullptr, uint64_t index_base = 0, bool amount64 = false);
 
     // d_partials: n partials as bpp_verifier_run_combined wrote them (jacobian + validity word each)
     static int sum_partials(const uint32_t* d_partials, size_t n, uint32_t* d_ok, hipStream_t st);
@@ -1457,7 +1460,7 @@ int VerifyImpl<C>::prove_batch_device(bpp_verifier* v, const PassShape& ps, cons
                               const uint64_t* d_gammas, size_t count, uint64_t* d_out_points, uint64_t* d_out_scalars,
                               uint64_t* d_out_V, bool fs, uint64_t* d_out_challenges, void* d_workspace,
                               size_t workspace_bytes, hipStream_t st, const uint8_t* blind_key, uint64_t index_base,
-                              const uint64_t* d_blinding, const uint32_t* px) {
+                              const uint64_t* d_blinding, const uint32_t* px, bool amount64) {
     const VerifyShape& s = ps.s;
     const uint32_t k = s.k, m = s.m;
     const uint32_t nvp = pb_num_vps(k, m);
@@ -1473,6 +1476,7 @@ int VerifyImpl<C>::prove_batch_device(bpp_verifier* v, const PassShape& ps, cons
     pc.s = 44;
     pc.delta = 88;
     pc.eta = 123;
+    pc.amount64 = amount64 ? 1u : 0u;   // the commitments' scalar on g: the u64, not `v as i32` (range/prover.rs:37)
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
     for (size_t base = 0; base < count; base += L.chunk) {
@@ -1565,7 +1569,8 @@ template <class C>
 int VerifyImpl<C>::prove_mixed_classes(bpp_verifier* v, const MixedPlan& p, const ProveMixedLayout& L, const uint64_t* d_values,
                                        const uint64_t* d_gammas, bool fs, const uint8_t* blind_key, uint64_t index_base,
                                        const uint64_t* d_blinding, uint64_t* d_out_points, uint64_t* d_out_scalars,
-                                       uint64_t* d_out_challenges, uint8_t* ws, size_t workspace_bytes, hipStream_t st) {
+                                       uint64_t* d_out_challenges, uint8_t* ws, size_t workspace_bytes, hipStream_t st,
+                                       bool amount64) {
     const size_t count = p.px.size() / PX_WORDS;
     uint32_t* w_idx = reinterpret_cast<uint32_t*>(ws + L.idx);
     // pageable source: the copies have read it when the call returns
@@ -1576,7 +1581,7 @@ int VerifyImpl<C>::prove_mixed_classes(bpp_verifier* v, const MixedPlan& p, cons
         if (!p.count[c]) continue;
         const int rc = prove_batch_device(v, class_shape(v, c), d_values, d_gammas, p.count[c], d_out_points, d_out_scalars,
                                           nullptr, fs, d_out_challenges, ws + L.run, workspace_bytes - L.run, st, blind_key,
-                                          index_base, d_blinding, w_idx + p.first[c] * PX_WORDS);
+                                          index_base, d_blinding, w_idx + p.first[c] * PX_WORDS, amount64);
         if (rc) return rc;
     }
     return BPP_OK;
@@ -1586,14 +1591,14 @@ template <class C>
 int VerifyImpl<C>::prove_mixed(bpp_verifier* v, const uint64_t* d_values, const uint64_t* d_gammas, const uint32_t* m_of,
                                size_t count, bool fs, const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_blinding,
                                uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_challenges, void* d_workspace,
-                               size_t workspace_bytes, hipStream_t st) {
+                               size_t workspace_bytes, hipStream_t st, bool amount64) {
     MixedPlan p;
     int rc = prove_plan(v->s, m_of, count, 0, true, p);
     if (rc) return rc;
     const ProveMixedLayout L = prove_mixed_layout(v, p, count, false);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     return prove_mixed_classes(v, p, L, d_values, d_gammas, fs, blind_key, index_base, d_blinding, d_out_points, d_out_scalars,
-                               d_out_challenges, static_cast<uint8_t*>(d_workspace), workspace_bytes, st);
+                               d_out_challenges, static_cast<uint8_t*>(d_workspace), workspace_bytes, st, amount64);
 }
 
 // The classes are proved into the class regions of the workspace (the layout the mixed decoder writes); the encoder is the
@@ -1603,7 +1608,7 @@ int VerifyImpl<C>::prove_serialized_mixed(bpp_verifier* v, const uint64_t* d_val
                                           const uint32_t* m_of, size_t count, bool fs, const uint8_t* blind_key,
                                           uint64_t index_base, const uint64_t* d_blinding, uint8_t* d_out_proofs,
                                           uint8_t* d_out_commitments, void* d_workspace, size_t workspace_bytes, hipStream_t st,
-                                          uint32_t version) {
+                                          uint32_t version, bool amount64) {
     if (v->s.n > 255 || v->s.m > 255) return fail(BPP_E_ARG, "the container holds n, m <= 255");
     if (version != 1 && !(version == 2 && uncompressed_bytes<C>() != 0))
         return fail(BPP_E_ARG, "container version 2 (uncompressed points) is not offered for this curve");
@@ -1615,7 +1620,7 @@ int VerifyImpl<C>::prove_serialized_mixed(bpp_verifier* v, const uint64_t* d_val
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     rc = prove_mixed_classes(v, p, L, d_values, d_gammas, fs, blind_key, index_base, d_blinding,
                              reinterpret_cast<uint64_t*>(ws + L.records), reinterpret_cast<uint64_t*>(ws + L.scalars), nullptr, ws,
-                             workspace_bytes, st);
+                             workspace_bytes, st, amount64);
     if (rc) return rc;
     hipLaunchKernelGGL(k_container_encode_mixed<C>, dim3((unsigned)(p.lanes / SER_WAVE)), dim3(SER_WAVE), 0, st, p.classes,
                        reinterpret_cast<const uint32_t*>(ws + L.idx) + count * PX_WORDS,
@@ -1628,7 +1633,7 @@ int VerifyImpl<C>::prove_serialized_mixed(bpp_verifier* v, const uint64_t* d_val
 template <class C>
 int VerifyImpl<C>::prove_batch(bpp_verifier* v, const uint64_t* values, const uint64_t* gammas, size_t count,
                        uint64_t* out_points, uint64_t* out_scalars, uint64_t* out_V, bool fs, const uint8_t* blind_key,
-                       uint64_t index_base) {
+                       uint64_t index_base, bool amount64) {
     const VerifyShape& s = v->s;
     const uint32_t k = s.k, m = s.m;
     hipStream_t st = nullptr;
@@ -1644,7 +1649,8 @@ int VerifyImpl<C>::prove_batch(bpp_verifier* v, const uint64_t* values, const ui
     HIPCHK(d_ws.alloc(L.total));
     rc = prove_batch_device(v, static_cast<const uint64_t*>(d_val.p), static_cast<const uint64_t*>(d_gam.p), count,
                             static_cast<uint64_t*>(d_pts.p), static_cast<uint64_t*>(d_sc.p),
-                            static_cast<uint64_t*>(d_V.p), fs, nullptr, d_ws.p, L.total, st, blind_key, index_base, nullptr);
+                            static_cast<uint64_t*>(d_V.p), fs, nullptr, d_ws.p, L.total, st, blind_key, index_base, nullptr,
+                            amount64);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(out_points, d_pts.p, count * (size_t)(3 + 2 * k) * WW * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(out_scalars, d_sc.p, count * 96, hipMemcpyDeviceToHost, st));

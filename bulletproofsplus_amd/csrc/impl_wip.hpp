@@ -103,6 +103,7 @@ int WipImpl<C>::prove_device(bpp_verifier* v, const uint64_t* d_a, const uint64_
     pc.s = 44;
     pc.delta = 88;
     pc.eta = 123;
+    pc.amount64 = 0;   // the range statement's; the seam forms no commitment
     const WipLiterals lit{WIP_E_ROUND, WIP_E_FINAL};
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };

@@ -29,6 +29,9 @@ struct ProverConsts {
     uint32_t alpha;            // range/mod.rs:94 (7, m == 1) / :256 (33, m > 1)
     uint32_t d_L, d_R;         // wip.rs:94-95
     uint32_t r, s, delta, eta; // wip.rs:175-178
+    // BPP_PROVE_AMOUNT64: the scalar on g of a commitment is the whole u64 instead of the reference's `v as i32`
+    // (range/prover.rs:37); read by the commitment branch of k_pb_init alone
+    uint32_t amount64;
 };
 
 // A block of MIXED aggregation sizes (bpp_range_prove_batch_mixed_device; mixed.hpp prove_plan): the proofs of one class
@@ -187,13 +190,14 @@ __global__ void __launch_bounds__(256) k_pb_init(VerifyShape s, ProverConsts pc,
         if (tid == 0) {
             pb_st_canon<P>(vp0 + (size_t)fixed_term_index(s, 1) * 8, pb_blind<P>(pc.alpha, blind, p, k, PB_BL_ALPHA));
             for (uint32_t j = 0; j < m; j++) {
-                // commitment V_j = new(v as i32) g + gamma h            (range/prover.rs:34-40)
+                // commitment V_j = new(v as i32) g + gamma h            (range/prover.rs:34-40); pc.amount64: v g + gamma h
                 uint32_t w[8];
                 ld_words<8>(gammas + (p * m + j) * 8, w);
                 const F g = fe_from_canonical<P>(w);
                 uint32_t* vpV = vp0 + (size_t)(2 * k + 3 + j) * s.N * 8;
-                const int32_t vi = (int32_t)(uint32_t)values[p * m + j];
-                pb_st_canon<P>(vpV + (size_t)fixed_term_index(s, 0) * 8, fe_from_i32<P>(vi));
+                const uint64_t vj = values[p * m + j];
+                pb_st_canon<P>(vpV + (size_t)fixed_term_index(s, 0) * 8,
+                               pc.amount64 ? fe_from_u64<P>(vj) : fe_from_i32<P>((int32_t)(uint32_t)vj));
                 pb_st_canon<P>(vpV + (size_t)fixed_term_index(s, 1) * 8, g);
             }
         }

@@ -125,12 +125,18 @@ int bpp_pk_hashed(bpp_ctx *ctx, const uint8_t *label, size_t label_len, size_t l
 /* RangeProver::commit / PublicKey::commitment (src/range/prover.rs:28-42, src/publickey.rs:50-52):
  * out = g * new(v as i32) + h * gamma.  The `v as i32` truncation of prover.rs:37 is kept. */
 int bpp_commit(bpp_ctx *ctx, const uint64_t *gh, uint64_t v, const uint64_t *gamma, uint64_t *out);
+/* (bpp_commit_batch / bpp_commit_batch_device, below the mixed prove calls: `count` commitments over an engine's g and h
+ * through its window tables, with or without the truncation.) */
 
 /* RangeProof::prove (src/range/mod.rs:31-55 -> prove_single :80-187 / prove_multiple :240-403, and
  * WeightedInnerProductProof::prove, src/weighted_inner_product_proof.rs:36-227).
  * pk = (gh, G, H) with n*m generators each; v[m], gamma[m] (scalars), V[m] commitments.
  * out_points : 3 + 2k points  [A, wip.A, wip.B, L_0..L_{k-1}, R_0..R_{k-1}],  k = log2(n*m)
- * out_scalars: 3 scalars      [r', s', delta'] */
+ * out_scalars: 3 scalars      [r', s', delta']
+ * The proof is a function of (v, gamma, V): V is read, not formed.  A key that has been seen before proves through its
+ * cached engine when V is what the batched prover forms from (v, gamma) -- the reference's new(v as i32) g + gamma h
+ * (src/range/prover.rs:37) or, tried second, the untruncated v g + gamma h a caller brings for an amount of 2^31 or more
+ * (BPP_PROVE_AMOUNT64 below) -- and through the fold-based prover for any other V; the output is the same either way. */
 int bpp_range_prove(bpp_ctx *ctx, const uint64_t *gh, const uint64_t *G, const uint64_t *H, size_t n,
                     size_t m, const uint64_t *v, const uint64_t *gamma, const uint64_t *V,
                     uint64_t *out_points, uint64_t *out_scalars);
@@ -553,6 +559,13 @@ int bpp_range_verify_batch_serialized_grouped_mixed_device(bpp_verifier *v, cons
  *                      bpp_range_prove_batch_fs_device, with blinding from blind_key (32 bytes, host), or from d_blinding
  *                      (5 + 2 k_i scalars per proof, packed in caller order, device), or -- both NULL -- the literals.
  *                      Blinding without BPP_SER_TRANSCRIPT is BPP_E_ARG.
+ *                      BPP_PROVE_AMOUNT64 (0x100, defined below; alone or with the above): full 64-bit amounts.
+ *                      The reference forms a commitment as new(v as i32) g + gamma h (src/range/prover.rs:37) while the witness bits come from
+ *                      the whole u64, so its proof of an amount of 2^31 or more does not verify; with this flag the scalar
+ *                      on g is the uint64_t itself (below r on every curve).  Nothing else changes -- bits of a_L,
+ *                      challenges, blinding, layout -- and for v < 2^31 the output is bit-identical with and without it.
+ *                      With n < 64 and v >= 2^n the call succeeds and the proof does not verify, as out of range
+ *                      values behave without the flag.
  *   index_base       : the blinding index belongs to the CALLER's numbering: proof i uses index_base + i whatever its
  *                      place inside the engine (the rule bpp_verifier_run_grouped_mixed states for its weights)
  *   d_out_points     : proof i's record [A, wip.A, wip.B, L.., R.., V_0..V_{m_i-1}] at wire point
@@ -565,6 +578,7 @@ int bpp_range_verify_batch_serialized_grouped_mixed_device(bpp_verifier *v, cons
  * BPP_OK.  The call BLOCKS the host only while it uploads the per-proof index (a pageable copy on `stream`); everything else
  * is enqueued asynchronously on `stream`: per m_i present a gather of its values and gammas and bpp_range_prove_batch*'s
  * kernels over the prefix view of the tables, the records written through the index (k_pb_collect). */
+#define BPP_PROVE_AMOUNT64 0x100
 size_t bpp_prover_mixed_workspace_bytes(const bpp_verifier *engine, const uint32_t *m_of, size_t count);
 int bpp_range_prove_batch_mixed_device(bpp_verifier *engine, const uint64_t *d_v, const uint64_t *d_gamma, const uint32_t *m_of,
                                        size_t count, int flags, const uint8_t *blind_key, uint64_t index_base,
@@ -574,7 +588,8 @@ int bpp_range_prove_batch_mixed_device(bpp_verifier *engine, const uint64_t *d_v
  * container i of bpp_proof_bytes_version(curve, n, m_of[i], version) bytes, packed back to back in caller order in
  * d_out_proofs, and m_of[i] encoded commitments per proof packed in d_out_commitments -- the input of
  * bpp_range_verify_batch_serialized_mixed_device, and a stream bpp_proofs_scan frames.  flags also takes
- * BPP_SER_UNCOMPRESSED (container version 2, commitments uncompressed; BPP_E_ARG on ristretto255).  The 4 GiB limits of
+ * BPP_SER_UNCOMPRESSED (container version 2, commitments uncompressed; BPP_E_ARG on ristretto255) and BPP_PROVE_AMOUNT64
+ * (the untruncated commitment scalar in place of src/range/prover.rs:37's `v as i32`, as above).  The 4 GiB limits of
  * the 32-bit byte index apply as on the verify side.  The records are proved into workspace regions per m_i and one kernel
  * (k_container_encode_mixed) writes every byte of the two output buffers.  Errors and blocking as above. */
 size_t bpp_prover_serialized_mixed_workspace_bytes(const bpp_verifier *engine, const uint32_t *m_of, size_t count);
@@ -584,13 +599,32 @@ int bpp_range_prove_batch_serialized_mixed_device(bpp_verifier *engine, const ui
                                                   void *d_out_commitments, void *d_workspace, size_t workspace_bytes,
                                                   void *stream);
 /* Both on HOST buffers (RangeProof::prove per proof, src/range/mod.rs:31-55), synchronous; layouts as above, blinding from
- * blind_key or the literals.  out_challenges may be NULL. */
+ * blind_key or the literals.  out_challenges may be NULL.  flags as above, BPP_PROVE_AMOUNT64 (src/range/prover.rs:37
+ * without its truncation) included. */
 int bpp_range_prove_batch_mixed(bpp_verifier *engine, const uint64_t *v, const uint64_t *gamma, const uint32_t *m_of,
                                 size_t count, int flags, const uint8_t *blind_key, uint64_t index_base, uint64_t *out_points,
                                 uint64_t *out_scalars, uint64_t *out_challenges);
 int bpp_range_prove_batch_serialized_mixed(bpp_verifier *engine, const uint64_t *v, const uint64_t *gamma, const uint32_t *m_of,
                                            size_t count, int flags, const uint8_t *blind_key, uint64_t index_base,
                                            uint8_t *out_proofs, uint8_t *out_commitments);
+
+/* ---- commitments for a block of amounts through the engine's tables ----
+ * RangeProver::commit (reference src/range/prover.rs:28-42) for `count` values over the engine's g and h:
+ *     out_V[i] = s_i g + gamma_i h,   s_i = new(v_i as i32) with flags = 0 (the truncation of src/range/prover.rs:37, so
+ *     each point equals bpp_commit's), s_i = v_i, the whole uint64_t, with BPP_PROVE_AMOUNT64.
+ * One lane per commitment walks the window-table rows of g and h (k_commit_batch, csrc/commit.hpp): a table gather and a
+ * mixed addition per non-zero digit, no doubling; a 64-bit amount has at most ceil(65 / window_bits) non-zero digits.
+ *   d_v, d_gamma : count uint64_t / count scalars (device); gamma is read as bpp_range_prove_batch_mixed_device reads it
+ *                  (canonical, < r)
+ *   d_out_V      : count wire points in caller order, in the form the prover writes its commitments (the same image of
+ *                  the point at infinity; on ristretto255 the same representative)
+ * The device call only enqueues on `stream`: no workspace, no host synchronisation.  The host call copies around it and
+ * reduces gamma mod r first, as the host prove calls do.  BPP_E_ARG for a NULL pointer or any other flag bit, nothing
+ * written; count = 0 is BPP_OK. */
+int bpp_commit_batch_device(bpp_verifier *engine, const uint64_t *d_v, const uint64_t *d_gamma, size_t count, int flags,
+                            uint64_t *d_out_V, void *stream);
+int bpp_commit_batch(bpp_verifier *engine, const uint64_t *v, const uint64_t *gamma, size_t count, int flags,
+                     uint64_t *out_V);
 
 /* ---- the weighted inner product argument as a seam of its own: WeightedInnerProductProof::{prove, verify} ----
  * Reference: src/weighted_inner_product_proof.rs:36-227 (prove), :238-328 (verify), :330-382 (verification_scalars).

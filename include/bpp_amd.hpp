@@ -151,16 +151,39 @@ struct RangeProver {
     std::vector<uint64_t> v_vec;
     std::vector<PrimeFieldElem> gamma_vec;
     std::vector<Point> commitment_vec;
-    void commit(const PublicKey& pk, uint64_t v, const PrimeFieldElem& gamma) {   // range/prover.rs:28-42
+    // range/prover.rs:28-42.  amount64 = false keeps the `v as i32` of prover.rs:37; true commits the whole 64-bit amount,
+    // V = v g + gamma h (a two-term MulVec): the commitment a proof made under BPP_PROVE_AMOUNT64 verifies against
+    void commit(const PublicKey& pk, uint64_t v, const PrimeFieldElem& gamma, bool amount64 = false) {
         Point out;
-        auto gh = pk.gh_wire();
-        if (bpp_commit(Arith::ctx(), gh.data(), v, gamma.e.data(), out.w.data()) != BPP_OK)
-            throw std::runtime_error(std::string("bpp_commit: ") + bpp_last_error());
+        if (amount64) {
+            PrimeFieldElem s;
+            s.e[0] = v;
+            out = pk.commitment(s, gamma);
+        } else {
+            auto gh = pk.gh_wire();
+            if (bpp_commit(Arith::ctx(), gh.data(), v, gamma.e.data(), out.w.data()) != BPP_OK)
+                throw std::runtime_error(std::string("bpp_commit: ") + bpp_last_error());
+        }
         v_vec.push_back(v);
         gamma_vec.push_back(gamma);
         commitment_vec.push_back(out);
     }
 };
+
+// RangeProver::commit (range/prover.rs:28-42) for a block of values over an engine's g and h, through its window tables
+// (bpp_commit_batch): amount64 = false keeps the `v as i32` of prover.rs:37, true (BPP_PROVE_AMOUNT64) commits the whole u64
+inline std::vector<Point> commit_batch(bpp_verifier* engine, const std::vector<uint64_t>& values,
+                                       const std::vector<PrimeFieldElem>& gammas, bool amount64 = false) {
+    if (values.size() != gammas.size()) throw std::logic_error("commit_batch: one gamma per value");
+    const size_t pw = Arith::point_words();
+    std::vector<uint64_t> gw, out(values.size() * pw + 1);
+    for (auto& g : gammas) gw.insert(gw.end(), g.e.begin(), g.e.end());
+    if (bpp_commit_batch(engine, values.data(), gw.data(), values.size(), amount64 ? BPP_PROVE_AMOUNT64 : 0, out.data()) != BPP_OK)
+        throw std::runtime_error(std::string("bpp_commit_batch: ") + bpp_last_error());
+    std::vector<Point> V;
+    for (size_t i = 0; i < values.size(); i++) V.emplace_back(out.data() + i * pw);
+    return V;
+}
 
 // Verifier-side holder of the commitments.  It exists only in the reference's (stale) README
 // (README.md:47-55: RangeVerifier::new(), allocate(&prover.commitment_vec), proof.verify(.., &verifier));
@@ -324,5 +347,58 @@ struct RangeProof {
         return verify(pk, n, verifier.commitment_vec);
     }
 };
+
+// RangeProof::prove (range/mod.rs:31-55) for a block in which proof i has values[i].size() = m_i values (a power of two <= the
+// engine's m), each against the prefix key PublicKey::new(n m_i) (bpp_range_prove_batch_mixed, literal challenges and
+// blinding): each proof with its commitments.  amount64 = false: RangeProver::commit's commitments, with the `v as i32` of
+// range/prover.rs:37; true (BPP_PROVE_AMOUNT64): V = v g + gamma h over the whole u64, so an amount of 2^31 or more proves
+// and verifies.  n: the engine's bits per value.
+inline std::vector<std::pair<RangeProof, std::vector<Point>>> prove_batch_mixed(
+    bpp_verifier* engine, size_t n, const std::vector<std::vector<uint64_t>>& values,
+    const std::vector<std::vector<PrimeFieldElem>>& gammas, bool amount64 = false) {
+    if (values.size() != gammas.size()) throw std::logic_error("prove_batch_mixed: one gamma list per proof");
+    const size_t pw = Arith::point_words();
+    auto log2of = [](size_t x) {
+        size_t k = 0;
+        while (((size_t)1 << k) < x) k++;
+        return k;
+    };
+    std::vector<uint64_t> vs, gw;
+    std::vector<uint32_t> ms;
+    size_t npts = 0;
+    for (size_t i = 0; i < values.size(); i++) {
+        if (values[i].size() != gammas[i].size()) throw std::logic_error("prove_batch_mixed: one gamma per value");
+        vs.insert(vs.end(), values[i].begin(), values[i].end());
+        for (auto& g : gammas[i]) gw.insert(gw.end(), g.e.begin(), g.e.end());
+        ms.push_back((uint32_t)values[i].size());
+        npts += 3 + 2 * log2of(n * values[i].size()) + values[i].size();
+    }
+    std::vector<uint64_t> pts(npts * pw + 1), sc(values.size() * 12 + 1);
+    if (bpp_range_prove_batch_mixed(engine, vs.data(), gw.data(), ms.data(), values.size(), amount64 ? BPP_PROVE_AMOUNT64 : 0,
+                                    nullptr, 0, pts.data(), sc.data(), nullptr) != BPP_OK)
+        throw std::runtime_error(std::string("bpp_range_prove_batch_mixed: ") + bpp_last_error());
+    std::vector<std::pair<RangeProof, std::vector<Point>>> out;
+    size_t at = 0;
+    for (size_t i = 0; i < values.size(); i++) {
+        const size_t k = log2of(n * values[i].size());
+        const uint64_t* p = pts.data() + at * pw;
+        RangeProof rp;
+        rp.A = Point(p);
+        rp.proof.A = Point(p + pw);
+        rp.proof.B = Point(p + 2 * pw);
+        for (size_t t = 0; t < k; t++) {
+            rp.proof.L_vec.emplace_back(p + (3 + t) * pw);
+            rp.proof.R_vec.emplace_back(p + (3 + k + t) * pw);
+        }
+        rp.proof.r_prime = PrimeFieldElem::from_limbs(sc.data() + 12 * i);
+        rp.proof.s_prime = PrimeFieldElem::from_limbs(sc.data() + 12 * i + 4);
+        rp.proof.d_prime = PrimeFieldElem::from_limbs(sc.data() + 12 * i + 8);
+        std::vector<Point> V;
+        for (size_t j = 0; j < values[i].size(); j++) V.emplace_back(p + (3 + 2 * k + j) * pw);
+        out.emplace_back(std::move(rp), std::move(V));
+        at += 3 + 2 * k + values[i].size();
+    }
+    return out;
+}
 
 }  // namespace bpp
