@@ -1120,7 +1120,7 @@ extern "C" int bpp_range_verify_batch_serialized_mixed(bpp_verifier* v, const ui
     if (!proofs || !commitments || !m_of || !out_ok) return fail(BPP_E_ARG, "null argument");
     const int version = (flags & BPP_SER_UNCOMPRESSED) ? 2 : 1;
     const size_t cb = container_point_size(v->ctx.curve, version);
-    if (cb == 0) return fail(BPP_E_ARG, "container version 2 (uncompressed points) is not offered for this curve");
+    if (int rc = container_version_ok(cb)) return rc;
     return on_device(v->ctx.device, {count, "count"}, [&]() -> int {
         const size_t wsb = bpp_verifier_serialized_mixed_workspace_bytes(v, m_of, count);
         if (!wsb) {   // an m_i the verifier does not take: the plan names the proof
@@ -1319,7 +1319,7 @@ extern "C" int bpp_range_prove_batch_serialized_mixed(bpp_verifier* engine, cons
     if (!v || !gamma || !m_of || !out_proofs || !out_commitments) return fail(BPP_E_ARG, "null argument");
     const int version = (flags & BPP_SER_UNCOMPRESSED) ? 2 : 1;
     const size_t cb = container_point_size(engine->ctx.curve, version);
-    if (cb == 0) return fail(BPP_E_ARG, "container version 2 (uncompressed points) is not offered for this curve");
+    if (int rc = container_version_ok(cb)) return rc;
     return on_device(engine->ctx.device, {count, "count"}, [&]() -> int {
         const size_t wsb = bpp_prover_serialized_mixed_workspace_bytes(engine, m_of, count);
         if (!wsb) {   // an m_i the engine does not take: the plan names the proof

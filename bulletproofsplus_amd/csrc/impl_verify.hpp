@@ -139,6 +139,14 @@ struct VerifyImpl {
                    d_out_result, st);
     }
 
+    // the range statement's scalar stage (run, begin_pass); d_challenges null: the shape's default ones for every proof
+    static int range_scalars(const PassShape& ps, const uint64_t* d_scalars, const uint64_t* d_challenges, uint32_t* w_sc,
+                             size_t count, uint32_t* w_prep, hipStream_t st) {
+        const uint32_t* ch = d_challenges ? reinterpret_cast<const uint32_t*>(d_challenges) : ps.challenges;
+        const uint32_t ch_stride = d_challenges ? (3 + ps.s.k) * 8 : 0;
+        return launch_verify_scalars<C>(ps.s, reinterpret_cast<const uint32_t*>(d_scalars), ch, ch_stride, w_sc, count, w_prep, st);
+    }
+
     // run() with the scalar stage left to the caller: scalars(w_sc, w_prep, w_bad, st) enqueues on st whatever writes the
     // [count][s.N] MulVec scalars into w_sc (w_prep: ws_layout's per-proof scratch; w_bad: the invalid-proof flags, zeroed
     // and already marked by the wire points).  run() passes the range statement's kernels, the WIP seam (impl_wip.hpp) its own.
@@ -216,24 +224,67 @@ struct VerifyImpl {
     }
 
     // ---- mixed batches (mixed.hpp): proof i of shape (n, m_i), m_i a power of two <= m ---------------------------
-    // workspace = per-proof index | gathered records | scalars | challenges | verdicts | result points | one class
-    // pass's workspace (the classes run one after the other on the caller's stream and share it)
+    // the front of every mixed workspace: per-proof index | class regions of records (gathered, or decoded) | scalar triples |
+    // decoder status (serialized form only) | challenges | verdicts -- all but the first two by gathered position
+    struct MixedFront {
+        size_t idx, pts, sc3, status, challenges, ok;
+    };
+    static MixedFront carve_front(WsCarver& o, const MixedPlan& p, size_t count, bool serialized) {
+        MixedFront f;
+        f.idx = o.take(count * (serialized ? (size_t)SX_WORDS : (size_t)MX_WORDS) * 4);
+        f.pts = o.take(p.points * WW * 4);
+        f.sc3 = o.take(count * 96);
+        f.status = o.take(serialized ? count * 4 : 0);
+        f.challenges = o.take(p.chals * 32);
+        f.ok = o.take(count * 4);
+        return f;
+    }
+    // wire form: the index upload (blocks until the copy has read it), the gather (d_scalars, d_challenges may be null)
+    static int gather_front(const MixedPlan& p, const MixedFront& front, size_t count, const uint64_t* d_points,
+                            const uint64_t* d_scalars, const uint64_t* d_challenges, uint8_t* ws, hipStream_t st);
+    // serialized form: the index upload, then the decoder and the membership test write records, triples and status
+    static int decode_front(const MixedPlan& p, const MixedFront& front, size_t count, const uint8_t* d_proofs,
+                            const uint8_t* d_commitments, uint32_t version, uint8_t* ws, hipStream_t st);
+    // one class present in a mixed batch: its shape, its gathered range and its regions of a front
+    struct ClassView {
+        uint32_t c;
+        PassShape ps;
+        size_t first, count;
+        uint64_t *pts, *sc3, *challenges;
+    };
+    // f(view) for every class present, in ascending order, until one returns an error
+    template <class F>
+    static int for_each_class(const bpp_verifier* v, const MixedPlan& p, const MixedFront& front, uint8_t* ws, F&& f) {
+        auto U64 = [&](size_t off) { return reinterpret_cast<uint64_t*>(ws + off); };
+        for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
+            if (!p.count[c]) continue;
+            const int rc = f(ClassView{c, class_shape(v, c), p.first[c], p.count[c], U64(front.pts) + p.pt[c] * PW,
+                                       U64(front.sc3) + p.first[c] * 12, U64(front.challenges) + p.chal[c] * 4});
+            if (rc) return rc;
+        }
+        return BPP_OK;
+    }
+    // the classes run one after the other on the caller's stream and share one workspace: the largest size_fn(shape, count)
+    template <class F>
+    static size_t class_run_max(const bpp_verifier* v, const MixedPlan& p, F&& size_fn) {
+        size_t run = 0;
+        for (uint32_t c = 0; c < MIXED_CLASSES; c++)
+            if (p.count[c]) run = std::max<size_t>(run, size_fn(class_shape(v, c).s, p.count[c]));
+        return run;
+    }
+    static size_t pass_bytes(const VerifyShape& s, size_t count) { return ws_layout(s, count).total; }
+
+    // workspace = front | result points | one class pass's workspace
     struct MixedLayout {
-        size_t idx, pts, scalars, challenges, ok, result, run, total;
+        MixedFront f;
+        size_t result, run, total;
     };
     static MixedLayout mixed_layout(const bpp_verifier* v, const MixedPlan& p, size_t count) {
         MixedLayout w;
         WsCarver o;
-        w.idx = o.take(count * MX_WORDS * 4);
-        w.pts = o.take(p.points * WW * 4);
-        w.scalars = o.take(count * 96);
-        w.challenges = o.take(p.chals * 32);
-        w.ok = o.take(count * 4);
+        w.f = carve_front(o, p, count, false);
         w.result = o.take(count * WW * 4);
-        size_t run = 0;
-        for (uint32_t c = 0; c < MIXED_CLASSES; c++)
-            if (p.count[c]) run = std::max(run, ws_layout(class_shape(v, c).s, p.count[c]).total);
-        w.run = o.take(run);
+        w.run = o.take(class_run_max(v, p, pass_bytes));
         w.total = o.total;
         return w;
     }
@@ -251,12 +302,14 @@ struct VerifyImpl {
     // d_challenges: 3 + k_i scalars per proof, packed in caller order (the layout run_mixed takes)
     static int derive_challenges_mixed(bpp_verifier* v, const uint64_t* d_points, const uint32_t* m_of, size_t count,
                                        uint64_t* d_challenges, void* d_workspace, size_t workspace_bytes, hipStream_t st);
-    // the shared head of both: plan, workspace check, index upload, gather (d_scalars null: points only)
-    static int mixed_gather(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, const uint32_t* m_of,
-                            size_t count, const uint64_t* d_challenges, void* d_workspace, size_t workspace_bytes,
-                            hipStream_t st, MixedPlan& p, MixedLayout& L);
 
     // ---- RangeProof::verify over SERIALIZED proofs resident in HBM (codec.hpp: the container) ---------------
+    // what every serialized entry point asks of engine and container version (the size getters: of the engine alone)
+    static bool container_shape_ok(const bpp_verifier* v) { return v->s.n <= 255 && v->s.m <= 255; }
+    static int container_args_ok(const bpp_verifier* v, uint32_t version) {
+        if (!container_shape_ok(v)) return fail(BPP_E_ARG, "the container holds n, m <= 255");
+        return container_version_ok(version == 1 || version == 2 ? (size_t)container_point_bytes<C>(version) : 0);
+    }
     // workspace = decoded records | scalars | decoder status | challenges (transcript mode) | run()'s workspace
     struct SerLayout {
         size_t records, scalars, status, challenges, run, total;
@@ -289,32 +342,23 @@ struct VerifyImpl {
                               uint32_t version = 1, const GroupedArgs* grouped = nullptr);
 
     // ---- ... of MIXED aggregation sizes: the decoder writes each record into its class region (mixed.hpp) -------
-    // workspace = per-proof index (by gathered position) | class regions of decoded records | scalars | decoder status |
-    // challenges (transcript mode) | verdicts -- the last four by gathered position -- | one class pass's workspace
+    // workspace = front (the challenges in transcript mode) | one class pass's workspace
     struct SerMixedLayout {
-        size_t idx, records, scalars, status, challenges, ok, run, total;
+        MixedFront f;
+        size_t run, total;
     };
     static SerMixedLayout ser_mixed_layout(const bpp_verifier* v, const MixedPlan& p, size_t count) {
         SerMixedLayout w;
         WsCarver o;
-        w.idx = o.take(count * SX_WORDS * 4);
-        w.records = o.take(p.points * WW * 4);
-        w.scalars = o.take(count * 96);
-        w.status = o.take(count * 4);
-        w.challenges = o.take(p.chals * 32);
-        w.ok = o.take(count * 4);
-        size_t run = 0;
-        for (uint32_t c = 0; c < MIXED_CLASSES; c++)
-            if (p.count[c]) run = std::max(run, ws_layout(class_shape(v, c).s, p.count[c]).total);
-        w.run = o.take(run);
+        w.f = carve_front(o, p, count, true);
+        w.run = o.take(class_run_max(v, p, pass_bytes));
         w.total = o.total;
         return w;
     }
     // 0 for an m_of the verifier does not take (the larger point encoding sizes the byte-offset check)
     static size_t ser_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
         MixedPlan p;
-        const size_t pb = uncompressed_bytes<C>() ? uncompressed_bytes<C>() : compressed_bytes<C>();
-        if (v->s.n > 255 || v->s.m > 255 || mixed_plan_serialized(v->s, m_of, count, pb, false, p)) return 0;
+        if (!container_shape_ok(v) || mixed_plan_serialized(v->s, m_of, count, max_point_bytes<C>(), false, p)) return 0;
         return ser_mixed_layout(v, p, count).total;
     }
     // d_proofs: the containers packed back to back in caller order, container i of container_bytes(k_i, version) bytes;
@@ -359,19 +403,47 @@ struct VerifyImpl {
                             size_t workspace_bytes, hipStream_t st);
 
     // ---- grouped check (combined.hpp): per-proof verdicts from one weighted check per GROUP of proofs ------
-    struct GroupLayout {
-        size_t pts, bad, scalars, prep, weights, var_sc, vdig, vtbl, vscr, vwsum, vfold,   // per proof, as the combined check's
-            grows, gbad, gok, tail,                                                         // per group
-            list, x_pts, x_sc, x_ch, x_ok, x_run,                                           // the exact second pass
-            total;
+    // the back of every grouped workspace, behind the proofs' window sums: their folds | per group the rows, invalid-point
+    // flags, verdicts and the back end's workspace | the exact second pass's slice buffers
+    struct GroupBack {
+        size_t vfold, grows, gbad, gok, tail, list, x_pts, x_sc, x_ch, x_ok, x_run;
         size_t groups, slice;
     };
     static constexpr size_t GROUP_EXACT_SLICE = 2048;   // proofs of failing groups re-verified per exact pass
+    static size_t exact_slice(size_t count) { return std::min<size_t>(std::max<size_t>(count, 1), GROUP_EXACT_SLICE); }
+    // The exact pass runs over however many proofs the failing groups hold, and a SMALLER batch can need a LARGER
+    // workspace (more blocks per proof, blocks_per_proof): room for the worst count up to the slice, of `count` proofs of s
+    static size_t exact_run_max(const VerifyShape& s, size_t count) {
+        size_t xrun = 0;
+        for (size_t c = 1; c <= exact_slice(count); c++) xrun = std::max(xrun, ws_layout(s, c).total);
+        return xrun;
+    }
+    // cap: the shape of the groups' rows; nv_max, k_max, xrun: the exact pass's longest record, challenge block, workspace
+    static GroupBack carve_back(WsCarver& o, const VerifyShape& cap, size_t count, uint32_t group, size_t nv_max, size_t k_max,
+                                size_t xrun) {
+        GroupBack w;
+        w.groups = cdiv(count, group);
+        w.slice = exact_slice(count);
+        w.vfold = o.take((size_t)cdiv(count, 2) * var_wsums<C>() * JW * 4);
+        w.grows = o.take(w.groups * (size_t)cap.N * 32);
+        w.gbad = o.take(w.groups * 4);
+        w.gok = o.take(w.groups * 4);
+        w.tail = o.take(ws_layout(cap, w.groups).total);
+        w.list = o.take(w.slice * 4);
+        w.x_pts = o.take(w.slice * nv_max * WW * 4);
+        w.x_sc = o.take(w.slice * 96);
+        w.x_ch = o.take(w.slice * (3 + k_max) * 32);
+        w.x_ok = o.take(w.slice * 4);
+        w.x_run = o.take(xrun);
+        return w;
+    }
+    struct GroupLayout {
+        size_t pts, bad, scalars, prep, weights, var_sc, vdig, vtbl, vscr, vwsum, total;   // per proof, as the combined check's
+        GroupBack b;
+    };
     static GroupLayout group_layout(const VerifyShape& s, size_t count, uint32_t group) {
         GroupLayout w;
         const size_t items = count * s.NV;
-        w.groups = cdiv(count, group);
-        w.slice = std::min<size_t>(std::max<size_t>(count, 1), GROUP_EXACT_SLICE);
         WsCarver o;
         w.pts = o.take(items * 2 * N * 4);
         w.bad = o.take(count * 4);
@@ -383,23 +455,13 @@ struct VerifyImpl {
         w.vtbl = o.take(items * VAR_MULTIPLES * 2 * N * 4);
         w.vscr = o.take(items * 2 * (VAR_MULTIPLES - 1) * N * 4);
         w.vwsum = o.take(count * var_wsums<C>() * JW * 4);
-        w.vfold = o.take((size_t)cdiv(count, 2) * var_wsums<C>() * JW * 4);
-        w.grows = o.take(w.groups * (size_t)s.N * 32);
-        w.gbad = o.take(w.groups * 4);
-        w.gok = o.take(w.groups * 4);
-        w.tail = o.take(ws_layout(s, w.groups).total);
-        w.list = o.take(w.slice * 4);
-        w.x_pts = o.take(w.slice * s.NV * WW * 4);
-        w.x_sc = o.take(w.slice * 96);
-        w.x_ch = o.take(w.slice * (size_t)(3 + s.k) * 32);
-        w.x_ok = o.take(w.slice * 4);
-        // the exact pass runs over however many proofs the failing groups hold, and a SMALLER batch can need a LARGER
-        // workspace (more blocks per proof, blocks_per_proof): room for the worst count up to the slice
-        size_t xrun = 0;
-        for (size_t c = 1; c <= w.slice; c++) xrun = std::max(xrun, ws_layout(s, c).total);
-        w.x_run = o.take(xrun);
+        w.b = carve_back(o, s, count, group, s.NV, s.k, exact_run_max(s, count));
         w.total = o.total;
         return w;
+    }
+    static bool group_ok(uint32_t group) { return group >= 2 && !(group & (group - 1)); }
+    static int check_group(uint32_t group) {
+        return group_ok(group) ? BPP_OK : fail(BPP_E_ARG, "group must be a power of two, at least 2");
     }
     // d_out_verdicts: count words, 0 = Ok / 1 = VerificationError, as bpp_verifier_run writes them.  h_stats (host, may be
     // null): [groups that failed their weighted check, proofs re-verified by the exact pass].  Synchronises `st`.
@@ -417,6 +479,36 @@ struct VerifyImpl {
     static int grouped_finish(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
                               const uint64_t* d_challenges, uint32_t group, uint32_t* d_out_verdicts, uint64_t* h_stats,
                               void* d_workspace, size_t workspace_bytes, hipStream_t st);
+    // the grouped back end (only enqueues), behind the writers of the rows B.grows and flags B.gbad: the window sums at
+    // `vwsum` (`per` per proof) folded to one set per group, the batch verifier's last stages over G virtual proofs of shape
+    // cap in Horner form `tree`, each group's verdict spread over its proofs into out_verdicts
+    static int group_back_end(bpp_verifier* v, const VerifyShape& cap, uint8_t* ws, const GroupBack& B, size_t vwsum,
+                              uint32_t per, uint32_t tree, size_t count, uint32_t group, uint32_t* out_verdicts,
+                              hipStream_t st);
+    // the groups' verdicts back on the host (synchronises `st`) -> list: the positions of the failing groups' proofs,
+    // ascending; h_stats (may be null): [failing groups, their proofs]
+    static int failing_groups(const uint32_t* d_gok, size_t G, uint32_t group, size_t count, uint64_t* h_stats,
+                              std::vector<uint32_t>& list, hipStream_t st) {
+        std::vector<uint32_t> gok(G);
+        HIPCHK(hipMemcpyAsync(gok.data(), d_gok, G * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        size_t failed = 0;
+        for (size_t g = 0; g < G; g++)
+            if (gok[g]) {
+                failed++;
+                for (size_t p = g * group; p < std::min(count, (g + 1) * (size_t)group); p++) list.push_back((uint32_t)p);
+            }
+        if (h_stats) {
+            h_stats[0] = failed;
+            h_stats[1] = list.size();
+        }
+        return BPP_OK;
+    }
+    // the exact second pass: the proofs (of shape ps) `list` names in src_pts, src_sc and src_ch (null: the shape's default
+    // challenges) through run() a slice at a time, verdict i to out_verdicts[list[i]].  Synchronises `st` after every slice.
+    static int exact_pass(bpp_verifier* v, const PassShape& ps, const uint64_t* src_pts, const uint64_t* src_sc,
+                          const uint64_t* src_ch, const std::vector<uint32_t>& list, uint32_t* out_verdicts, uint8_t* ws,
+                          const GroupBack& B, size_t workspace_bytes, hipStream_t st);
 
     // ---- grouped check over a MIXED batch (combined.hpp, mixed.hpp) -------------------------------------------
     // The PARTITION: groups are runs of `group` neighbours in GATHERED order (classes ascending, caller order within a
@@ -425,19 +517,14 @@ struct VerifyImpl {
     // is all the soundness argument of the grouped check asks of it.  Each group is ONE virtual proof of the CAPACITY shape
     // (k_comb_fixed_grouped_mixed), so the back end (finish) runs once whatever the mix -- and costs G capacity rows
     // whatever the mix: a group of small proofs pays a full capacity row.
-    // workspace = front (the wire form's index, gathered records, scalar triples and challenges; the serialized form's
-    // index, class regions, triples, decoder status and challenges) | the core: verdicts, weights and invalid-point flags
-    // by gathered position, the scalars of every class, the front end's per-class buffers (shared by the classes, which
-    // run one after the other), the window sums by gathered position and their folds, per group the rows, flags, verdicts
-    // and the back end's workspace, and the exact second pass's slice buffers
+    // workspace = front (MixedFront, wire or serialized form) | weights and invalid-point flags by gathered position, the
+    // scalars of every class, the front end's per-class buffers (shared by the classes, which run one after the other),
+    // the window sums by gathered position | back (GroupBack)
     struct GroupMixedLayout {
-        size_t idx, pts, sc3, status, challenges,                                       // the front
-            ok, weights, bad, scalars, cpts, prep, var_sc, vdig, vtbl, vscr, vwsum, vfold,   // per proof
-            grows, gbad, gok, tail,                                                     // per group
-            list, x_pts, x_sc, x_ch, x_ok, x_run,                                       // the exact second pass
-            total;
+        MixedFront f;
+        size_t weights, bad, scalars, cpts, prep, var_sc, vdig, vtbl, vscr, vwsum, total;   // per proof
         size_t sc_of[MIXED_CLASSES];   // class c's scalars [count_c][N_c], from `scalars`, in bytes
-        size_t groups, slice;
+        GroupBack b;
     };
     // the offsets begin_pass and weighted_middle take, for one class of the batch
     struct ClassFront {
@@ -446,15 +533,8 @@ struct VerifyImpl {
     static GroupMixedLayout group_mixed_layout(const bpp_verifier* v, const MixedPlan& p, size_t count, uint32_t group,
                                                bool serialized) {
         GroupMixedLayout w{};
-        w.groups = cdiv(count, group);
-        w.slice = std::min<size_t>(std::max<size_t>(count, 1), GROUP_EXACT_SLICE);
         WsCarver o;
-        w.idx = o.take(count * (serialized ? (size_t)SX_WORDS : (size_t)MX_WORDS) * 4);
-        w.pts = o.take(p.points * WW * 4);
-        w.sc3 = o.take(count * 96);
-        w.status = o.take(serialized ? count * 4 : 0);
-        w.challenges = o.take(p.chals * 32);
-        w.ok = o.take(count * 4);
+        w.f = carve_front(o, p, count, serialized);
         w.weights = o.take(count * 32);
         w.bad = o.take(count * 4);
         size_t scalars = 0, items = 0, prep = 0, xrun = 0, nv_max = 0, k_max = 0;
@@ -467,9 +547,7 @@ struct VerifyImpl {
             prep = std::max(prep, p.count[c] * vs_prep_bytes<C>(s));
             nv_max = std::max<size_t>(nv_max, s.NV);
             k_max = std::max<size_t>(k_max, s.k);
-            // the exact pass of a class runs over however many of its proofs the failing groups hold, and a SMALLER batch
-            // can need a LARGER workspace (group_layout): room for the worst count up to the slice
-            for (size_t n = 1; n <= std::min(w.slice, p.count[c]); n++) xrun = std::max(xrun, ws_layout(s, n).total);
+            xrun = std::max(xrun, exact_run_max(s, p.count[c]));   // a class's exact pass runs over its own proofs
         }
         w.scalars = o.take(scalars);
         for (uint32_t c = 0; c < MIXED_CLASSES; c++) w.sc_of[c] += w.scalars;
@@ -480,21 +558,10 @@ struct VerifyImpl {
         w.vtbl = o.take(items * VAR_MULTIPLES * 2 * N * 4);
         w.vscr = o.take(items * 2 * (VAR_MULTIPLES - 1) * N * 4);
         w.vwsum = o.take(count * var_wsums<C>() * JW * 4);
-        w.vfold = o.take((size_t)cdiv(count, 2) * var_wsums<C>() * JW * 4);
-        w.grows = o.take(w.groups * (size_t)v->s.N * 32);
-        w.gbad = o.take(w.groups * 4);
-        w.gok = o.take(w.groups * 4);
-        w.tail = o.take(ws_layout(v->s, w.groups).total);
-        w.list = o.take(w.slice * 4);
-        w.x_pts = o.take(w.slice * nv_max * WW * 4);
-        w.x_sc = o.take(w.slice * 96);
-        w.x_ch = o.take(w.slice * (3 + k_max) * 32);
-        w.x_ok = o.take(w.slice * 4);
-        w.x_run = o.take(xrun);
+        w.b = carve_back(o, v->s, count, group, nv_max, k_max, xrun);
         w.total = o.total;
         return w;
     }
-    static bool group_ok(uint32_t group) { return group >= 2 && !(group & (group - 1)); }
     // 0 for an m_of or a group the verifier does not take
     static size_t grouped_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, uint32_t group) {
         MixedPlan p;
@@ -503,8 +570,8 @@ struct VerifyImpl {
     }
     static size_t ser_grouped_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, uint32_t group) {
         MixedPlan p;
-        const size_t pb = uncompressed_bytes<C>() ? uncompressed_bytes<C>() : compressed_bytes<C>();
-        if (!group_ok(group) || v->s.n > 255 || v->s.m > 255 || mixed_plan_serialized(v->s, m_of, count, pb, false, p))
+        if (!group_ok(group) || !container_shape_ok(v) ||
+            mixed_plan_serialized(v->s, m_of, count, max_point_bytes<C>(), false, p))
             return 0;
         return group_mixed_layout(v, p, count, group, true).total;
     }
@@ -520,9 +587,9 @@ struct VerifyImpl {
                                             const uint32_t* m_of, size_t count, bool transcript, const uint8_t* weight_key,
                                             uint64_t index_base, uint32_t group, uint32_t* d_ok, uint64_t* h_stats,
                                             void* d_workspace, size_t workspace_bytes, hipStream_t st, uint32_t version);
-    // the core of both, from the plan and the gathered regions in the workspace (L.pts, L.sc3, L.challenges when
-    // with_challenges, L.weights by gathered position, L.status when with_status): both passes; the verdicts are left in
-    // L.ok by GATHERED position for the caller's scatter.  Synchronises `st`.
+    // the core of both, from the plan and the front L.f in the workspace (its challenges when with_challenges, its status
+    // when with_status) and L.weights by gathered position: both passes; the verdicts are left in L.f.ok by GATHERED
+    // position for the caller's scatter.  Synchronises `st`.
     static int grouped_mixed_core(bpp_verifier* v, const MixedPlan& p, size_t count, uint32_t group, bool with_challenges,
                                   bool with_status, uint64_t* h_stats, uint8_t* ws, const GroupMixedLayout& L,
                                   size_t workspace_bytes, hipStream_t st);
@@ -612,10 +679,7 @@ struct VerifyImpl {
         w.idx = o.take(count * (size_t)(PX_WORDS + SX_WORDS) * 4);
         w.records = o.take(serialized ? p.points * WW * 4 : 0);
         w.scalars = o.take(serialized ? count * 96 : 0);
-        size_t run = 0;
-        for (uint32_t c = 0; c < MIXED_CLASSES; c++)
-            if (p.count[c]) run = std::max(run, prove_layout(class_shape(v, c).s, p.count[c], true).total);
-        w.run = o.take(run);
+        w.run = o.take(class_run_max(v, p, [](const VerifyShape& s, size_t n) { return prove_layout(s, n, true).total; }));
         w.total = o.total;
         return w;
     }
@@ -627,8 +691,7 @@ struct VerifyImpl {
     }
     static size_t prove_ser_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
         MixedPlan p;
-        const size_t pb = uncompressed_bytes<C>() ? uncompressed_bytes<C>() : compressed_bytes<C>();
-        if (v->s.n > 255 || v->s.m > 255 || prove_plan(v->s, m_of, count, pb, false, p)) return 0;
+        if (!container_shape_ok(v) || prove_plan(v->s, m_of, count, max_point_bytes<C>(), false, p)) return 0;
         return prove_mixed_layout(v, p, count, true).total;
     }
     // d_values: sum m_i u64, d_gammas: sum m_i scalars, d_blinding (may be null): 5 + 2 k_i scalars per proof, all packed
@@ -775,14 +838,10 @@ template <class Layout>
 int VerifyImpl<C>::begin_pass(bpp_verifier* v, const PassShape& ps, const uint64_t* d_points, const uint64_t* d_scalars,
                               size_t count, const uint64_t* d_challenges, uint8_t* ws, const Layout& L, uint32_t* w_sc,
                               std::unique_lock<std::mutex>& aux_lock, hipStream_t st, hipEvent_t* ev) {
-    const VerifyShape& s = ps.s;
-    int rc = begin_points(v, s, d_points, count, ws, L, aux_lock, st, ev);
+    int rc = begin_points(v, ps.s, d_points, count, ws, L, aux_lock, st, ev);
     if (rc) return rc;
-    const uint32_t* ch = d_challenges ? reinterpret_cast<const uint32_t*>(d_challenges) : ps.challenges;
-    const uint32_t ch_stride = d_challenges ? (3 + s.k) * 8 : 0;
     HIPCHK(mark(ev, 2 * BPP_STAGE_SCALARS, st));
-    rc = launch_verify_scalars<C>(s, reinterpret_cast<const uint32_t*>(d_scalars), ch, ch_stride, w_sc, count,
-                                  reinterpret_cast<uint32_t*>(ws + L.prep), st);
+    rc = range_scalars(ps, d_scalars, d_challenges, w_sc, count, reinterpret_cast<uint32_t*>(ws + L.prep), st);
     if (rc) return rc;
     HIPCHK(mark(ev, 2 * BPP_STAGE_SCALARS + 1, st));
     return BPP_OK;
@@ -836,13 +895,9 @@ template <class C>
 int VerifyImpl<C>::run(bpp_verifier* v, const PassShape& ps, const uint64_t* d_points, const uint64_t* d_scalars,
                        size_t count, const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace,
                        size_t workspace_bytes, uint64_t* d_out_scalars, uint64_t* d_out_result, hipStream_t st) {
-    const VerifyShape& s = ps.s;
-    const uint32_t* ch = d_challenges ? reinterpret_cast<const uint32_t*>(d_challenges) : ps.challenges;
-    const uint32_t ch_stride = d_challenges ? (3 + s.k) * 8 : 0;
-    return run_stage(v, s, d_points, count,
+    return run_stage(v, ps.s, d_points, count,
                      [&](uint32_t* w_sc, uint32_t* w_prep, uint32_t*, hipStream_t st_) {
-                         return launch_verify_scalars<C>(s, reinterpret_cast<const uint32_t*>(d_scalars), ch, ch_stride, w_sc,
-                                                         count, w_prep, st_);
+                         return range_scalars(ps, d_scalars, d_challenges, w_sc, count, w_prep, st_);
                      },
                      d_ok, d_workspace, workspace_bytes, d_out_scalars, d_out_result, st);
 }
@@ -877,12 +932,11 @@ int VerifyImpl<C>::run_stage(bpp_verifier* v, const VerifyShape& s, const uint64
     // sequence); its latency-bound Horner stage rides in the first blocks of the fixed-generator launch
     uint8_t* w_vd = ws + L.vdig;
     uint32_t* w_vw = reinterpret_cast<uint32_t*>(ws + L.vwsum);
-    // Horner stage: one lane per proof, or -- while the waves are there to spare -- one wave per proof (tree); the tree
-    // reads the window sums split by scalar half (k_var_windows)
-    // (mode 1, window sums split by scalar half); in between, eight lanes per proof (mode 2) while the launch would
-    // otherwise wait for the one-lane chains: the chain is ~2 ms, the eight-lane form costs ~0.09 us of chip time per
-    // proof on top of the fixed-generator work (~7 G mixed additions/s) -- measured on (64,1): better at 4 096 proofs,
-    // worse at 8 192
+    // Horner stage (horner_form): one lane per proof (mode 0), or -- while the waves are there to spare -- one wave per
+    // proof (the tree, mode 1), which reads the window sums split by scalar half (k_var_windows); in between, eight lanes
+    // per proof (mode 2) while the launch would otherwise wait for the one-lane chains: the chain is ~2 ms, the eight-lane
+    // form costs ~0.09 us of chip time per proof on top of the fixed-generator work (~7 G mixed additions/s) -- measured
+    // on (64,1): better at 4 096 proofs, worse at 8 192
     const uint32_t tree = horner_form(s, count);
     // a launch whose blocks are all resident at once (<= 1024): only latency counts -- its blocks also sum their own
     // partials (mode 3 of k_fixed_msm) and the points of a proof are dealt to VAR_GROUPS lanes per window
@@ -957,9 +1011,7 @@ int VerifyImpl<C>::run_serialized(bpp_verifier* v, const uint8_t* d_proofs, cons
                                   bool transcript, uint32_t* d_ok, void* d_workspace, size_t workspace_bytes,
                                   hipStream_t st, uint32_t version, const GroupedArgs* grouped) {
     const VerifyShape& s = v->s;
-    if (s.n > 255 || s.m > 255) return fail(BPP_E_ARG, "the container holds n, m <= 255");
-    if (version != 1 && !(version == 2 && uncompressed_bytes<C>() != 0))
-        return fail(BPP_E_ARG, "container version 2 (uncompressed points) is not offered for this curve");
+    if (int rc = container_args_ok(v, version)) return rc;
     const SerLayout L = ser_layout(s, count, grouped ? grouped->group : 0u);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
@@ -1000,20 +1052,31 @@ int VerifyImpl<C>::derive_challenges(bpp_verifier* v, const PassShape& ps, const
 }
 
 template <class C>
-int VerifyImpl<C>::mixed_gather(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, const uint32_t* m_of,
-                                size_t count, const uint64_t* d_challenges, void* d_workspace, size_t workspace_bytes,
-                                hipStream_t st, MixedPlan& p, MixedLayout& L) {
-    int rc = mixed_plan(v->s, m_of, count, true, p);
-    if (rc) return rc;
-    L = mixed_layout(v, p, count);
-    if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
-    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+int VerifyImpl<C>::gather_front(const MixedPlan& p, const MixedFront& front, size_t count, const uint64_t* d_points,
+                                const uint64_t* d_scalars, const uint64_t* d_challenges, uint8_t* ws, hipStream_t st) {
+    auto U64 = [&](size_t off) { return reinterpret_cast<uint64_t*>(ws + off); };
+    uint32_t* w_idx = reinterpret_cast<uint32_t*>(ws + front.idx);
     // pageable source: the copy has read it when the call returns
-    HIPCHK(hipMemcpyAsync(ws + L.idx, p.idx.data(), p.idx.size() * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_mixed_gather<C>, dim3((unsigned)count), dim3(MIXED_BLOCK), 0, st,
-                       reinterpret_cast<const uint32_t*>(ws + L.idx), count, d_points, d_scalars, d_challenges,
-                       reinterpret_cast<uint64_t*>(ws + L.pts), reinterpret_cast<uint64_t*>(ws + L.scalars),
-                       reinterpret_cast<uint64_t*>(ws + L.challenges));
+    HIPCHK(hipMemcpyAsync(w_idx, p.idx.data(), p.idx.size() * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_mixed_gather<C>, dim3((unsigned)count), dim3(MIXED_BLOCK), 0, st, w_idx, count, d_points, d_scalars,
+                       d_challenges, U64(front.pts), U64(front.sc3), U64(front.challenges));
+    HIPCHK(hipGetLastError());
+    return BPP_OK;
+}
+
+template <class C>
+int VerifyImpl<C>::decode_front(const MixedPlan& p, const MixedFront& front, size_t count, const uint8_t* d_proofs,
+                                const uint8_t* d_commitments, uint32_t version, uint8_t* ws, hipStream_t st) {
+    auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    uint32_t *w_idx = W(front.idx), *w_rec = W(front.pts), *w_st = W(front.status);
+    // pageable source: the copy has read it when the call returns
+    HIPCHK(hipMemcpyAsync(w_idx, p.sidx.data(), p.sidx.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(zero_words_async(w_st, count * 4, st));
+    const unsigned waves = (unsigned)(p.lanes / SER_WAVE);
+    hipLaunchKernelGGL(k_container_decode_mixed<C>, dim3(waves), dim3(SER_WAVE), 0, st, p.classes, w_idx, d_proofs,
+                       d_commitments, w_rec, W(front.sc3), w_st, version);
+    if constexpr (C::ID == 0)   // cofactor > 1: membership of the prime-order subgroup
+        hipLaunchKernelGGL(k_records_subgroup_mixed<C>, dim3(waves), dim3(SER_WAVE), 0, st, p.classes, w_rec, w_st);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
@@ -1025,23 +1088,23 @@ int VerifyImpl<C>::run_mixed(bpp_verifier* v, const uint64_t* d_points, const ui
                              size_t count, const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace,
                              size_t workspace_bytes, uint64_t* d_out_result, hipStream_t st) {
     MixedPlan p;
-    MixedLayout L;
-    int rc = mixed_gather(v, d_points, d_scalars, m_of, count, d_challenges, d_workspace, workspace_bytes, st, p, L);
+    int rc = mixed_plan(v->s, m_of, count, true, p);
     if (rc) return rc;
+    const MixedLayout L = mixed_layout(v, p, count);
+    if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-    auto U64 = [&](size_t off) { return reinterpret_cast<uint64_t*>(ws + off); };
-    uint32_t* w_ok = reinterpret_cast<uint32_t*>(ws + L.ok);
-    for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
-        if (!p.count[c]) continue;
-        const PassShape ps = class_shape(v, c);
-        rc = run(v, ps, U64(L.pts) + p.pt[c] * PW, U64(L.scalars) + p.first[c] * 12, p.count[c],
-                 d_challenges ? U64(L.challenges) + p.chal[c] * 4 : nullptr, w_ok + p.first[c], ws + L.run,
-                 workspace_bytes - L.run, nullptr, d_out_result ? U64(L.result) + p.first[c] * PW : nullptr, st);
-        if (rc) return rc;
-    }
+    rc = gather_front(p, L.f, count, d_points, d_scalars, d_challenges, ws, st);
+    if (rc) return rc;
+    uint32_t* w_ok = reinterpret_cast<uint32_t*>(ws + L.f.ok);
+    uint64_t* w_res = d_out_result ? reinterpret_cast<uint64_t*>(ws + L.result) : nullptr;
+    rc = for_each_class(v, p, L.f, ws, [&](const ClassView& cv) {
+        return run(v, cv.ps, cv.pts, cv.sc3, cv.count, d_challenges ? cv.challenges : nullptr, w_ok + cv.first, ws + L.run,
+                   workspace_bytes - L.run, nullptr, w_res ? w_res + cv.first * PW : nullptr, st);
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(k_mixed_scatter<C>, dim3(cdiv(count, 4)), dim3(256), 0, st,
-                       reinterpret_cast<const uint32_t*>(ws + L.idx), count, w_ok, d_out_result ? U64(L.result) : nullptr,
-                       nullptr, d_ok, d_out_result, nullptr);
+                       reinterpret_cast<const uint32_t*>(ws + L.f.idx), count, w_ok, w_res, nullptr, d_ok, d_out_result,
+                       nullptr);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
@@ -1051,20 +1114,20 @@ int VerifyImpl<C>::derive_challenges_mixed(bpp_verifier* v, const uint64_t* d_po
                                            uint64_t* d_challenges, void* d_workspace, size_t workspace_bytes,
                                            hipStream_t st) {
     MixedPlan p;
-    MixedLayout L;
-    int rc = mixed_gather(v, d_points, nullptr, m_of, count, nullptr, d_workspace, workspace_bytes, st, p, L);
+    int rc = mixed_plan(v->s, m_of, count, true, p);
     if (rc) return rc;
+    const MixedLayout L = mixed_layout(v, p, count);
+    if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-    auto U64 = [&](size_t off) { return reinterpret_cast<uint64_t*>(ws + off); };
-    for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
-        if (!p.count[c]) continue;
-        rc = derive_challenges(v, class_shape(v, c), U64(L.pts) + p.pt[c] * PW, p.count[c], U64(L.challenges) + p.chal[c] * 4,
-                               st);
-        if (rc) return rc;
-    }
+    rc = gather_front(p, L.f, count, d_points, nullptr, nullptr, ws, st);   // the points only
+    if (rc) return rc;
+    rc = for_each_class(v, p, L.f, ws, [&](const ClassView& cv) {
+        return derive_challenges(v, cv.ps, cv.pts, cv.count, cv.challenges, st);
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(k_mixed_scatter<C>, dim3(cdiv(count, 4)), dim3(256), 0, st,
-                       reinterpret_cast<const uint32_t*>(ws + L.idx), count, nullptr, nullptr, U64(L.challenges), nullptr,
-                       nullptr, d_challenges);
+                       reinterpret_cast<const uint32_t*>(ws + L.f.idx), count, nullptr, nullptr,
+                       reinterpret_cast<uint64_t*>(ws + L.f.challenges), nullptr, nullptr, d_challenges);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
@@ -1076,44 +1139,27 @@ template <class C>
 int VerifyImpl<C>::run_serialized_mixed(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments,
                                         const uint32_t* m_of, size_t count, bool transcript, uint32_t* d_ok,
                                         void* d_workspace, size_t workspace_bytes, hipStream_t st, uint32_t version) {
-    if (v->s.n > 255 || v->s.m > 255) return fail(BPP_E_ARG, "the container holds n, m <= 255");
-    if (version != 1 && !(version == 2 && uncompressed_bytes<C>() != 0))
-        return fail(BPP_E_ARG, "container version 2 (uncompressed points) is not offered for this curve");
+    if (int rc = container_args_ok(v, version)) return rc;
     MixedPlan p;
     int rc = mixed_plan_serialized(v->s, m_of, count, (size_t)container_point_bytes<C>(version), true, p);
     if (rc) return rc;
     const SerMixedLayout L = ser_mixed_layout(v, p, count);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-    auto U64 = [&](size_t off) { return reinterpret_cast<uint64_t*>(ws + off); };
-    uint32_t* w_idx = reinterpret_cast<uint32_t*>(ws + L.idx);
-    uint32_t* w_rec = reinterpret_cast<uint32_t*>(ws + L.records);
-    uint32_t* w_sc = reinterpret_cast<uint32_t*>(ws + L.scalars);
-    uint32_t* w_st = reinterpret_cast<uint32_t*>(ws + L.status);
-    uint32_t* w_ok = reinterpret_cast<uint32_t*>(ws + L.ok);
-    // pageable source: the copy has read it when the call returns
-    HIPCHK(hipMemcpyAsync(w_idx, p.sidx.data(), p.sidx.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(zero_words_async(w_st, count * 4, st));
-    const unsigned waves = (unsigned)(p.lanes / SER_WAVE);
-    hipLaunchKernelGGL(k_container_decode_mixed<C>, dim3(waves), dim3(SER_WAVE), 0, st, p.classes, w_idx, d_proofs,
-                       d_commitments, w_rec, w_sc, w_st, version);
-    if constexpr (C::ID == 0)   // cofactor > 1: membership of the prime-order subgroup
-        hipLaunchKernelGGL(k_records_subgroup_mixed<C>, dim3(waves), dim3(SER_WAVE), 0, st, p.classes, w_rec, w_st);
-    HIPCHK(hipGetLastError());
-    for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
-        if (!p.count[c]) continue;
-        const PassShape ps = class_shape(v, c);
-        const uint64_t* recs = U64(L.records) + p.pt[c] * PW;
-        uint64_t* ch = transcript ? U64(L.challenges) + p.chal[c] * 4 : nullptr;
+    auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    rc = decode_front(p, L.f, count, d_proofs, d_commitments, version, ws, st);
+    if (rc) return rc;
+    rc = for_each_class(v, p, L.f, ws, [&](const ClassView& cv) {
         if (transcript) {
-            rc = derive_challenges(v, ps, recs, p.count[c], ch, st);
-            if (rc) return rc;
+            const int rc1 = derive_challenges(v, cv.ps, cv.pts, cv.count, cv.challenges, st);
+            if (rc1) return rc1;
         }
-        rc = run(v, ps, recs, U64(L.scalars) + p.first[c] * 12, p.count[c], ch, w_ok + p.first[c], ws + L.run,
-                 workspace_bytes - L.run, nullptr, nullptr, st);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(k_mixed_status_scatter<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, w_idx, w_st, w_ok, d_ok, count);
+        return run(v, cv.ps, cv.pts, cv.sc3, cv.count, transcript ? cv.challenges : nullptr, W(L.f.ok) + cv.first, ws + L.run,
+                   workspace_bytes - L.run, nullptr, nullptr, st);
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_mixed_status_scatter<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, W(L.f.idx), W(L.f.status), W(L.f.ok),
+                       d_ok, count);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
@@ -1169,6 +1215,54 @@ int VerifyImpl<C>::run_grouped(bpp_verifier* v, const uint64_t* d_points, const 
                           workspace_bytes, st);
 }
 
+template <class C>
+int VerifyImpl<C>::group_back_end(bpp_verifier* v, const VerifyShape& cap, uint8_t* ws, const GroupBack& B, size_t vwsum,
+                                  uint32_t per, uint32_t tree, size_t count, uint32_t group, uint32_t* out_verdicts,
+                                  hipStream_t st) {
+    auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    uint32_t* cur = W(vwsum);
+    uint32_t* nxt = W(B.vfold);
+    size_t nrem = count;
+    for (uint32_t left = group; left > 1; std::swap(cur, nxt)) {   // the proofs of a group are neighbours: 4 (at last 2) to 1 per level
+        const uint32_t step = left >= 4 ? 4u : 2u;
+        nrem = fold_windows(cur, nrem, step, nxt, per, st);
+        left /= step;
+    }
+    int rc = finish(v, cap, ws + B.tail, ws_layout(cap, B.groups), B.groups, W(B.grows), cur, W(B.gbad), W(B.gok), nullptr, tree,
+                    false, st, nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_comb_group_spread, dim3(cdiv(count, 256)), dim3(256), 0, st, W(B.gok), group, out_verdicts, count);
+    HIPCHK(hipGetLastError());
+    return BPP_OK;
+}
+
+template <class C>
+int VerifyImpl<C>::exact_pass(bpp_verifier* v, const PassShape& ps, const uint64_t* src_pts, const uint64_t* src_sc,
+                              const uint64_t* src_ch, const std::vector<uint32_t>& list, uint32_t* out_verdicts, uint8_t* ws,
+                              const GroupBack& B, size_t workspace_bytes, hipStream_t st) {
+    auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    auto U64 = [&](size_t off) { return reinterpret_cast<const uint64_t*>(ws + off); };
+    const uint32_t row_pts = ps.s.NV * WW, row_sc = 24, row_ch = (3 + ps.s.k) * 8;
+    for (size_t lo = 0; lo < list.size(); lo += B.slice) {
+        const size_t cnt = std::min(B.slice, list.size() - lo);
+        HIPCHK(hipMemcpyAsync(W(B.list), list.data() + lo, cnt * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_comb_gather_rows, dim3((unsigned)cnt), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(src_pts),
+                           W(B.list), row_pts, W(B.x_pts));
+        hipLaunchKernelGGL(k_comb_gather_rows, dim3((unsigned)cnt), dim3(64), 0, st, reinterpret_cast<const uint32_t*>(src_sc),
+                           W(B.list), row_sc, W(B.x_sc));
+        if (src_ch)
+            hipLaunchKernelGGL(k_comb_gather_rows, dim3((unsigned)cnt), dim3(64), 0, st,
+                               reinterpret_cast<const uint32_t*>(src_ch), W(B.list), row_ch, W(B.x_ch));
+        int rc = run(v, ps, U64(B.x_pts), U64(B.x_sc), cnt, src_ch ? U64(B.x_ch) : nullptr, W(B.x_ok), ws + B.x_run,
+                     workspace_bytes - B.x_run, nullptr, nullptr, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_comb_scatter_words, dim3(cdiv(cnt, 256)), dim3(256), 0, st, W(B.x_ok), W(B.list), out_verdicts, cnt);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));   // `list` slices are staged from pageable memory
+    }
+    return BPP_OK;
+}
+
 // pass 1 (only enqueues): one weighted check per group, through the batch verifier's own last stages at count = G
 template <class C>
 int VerifyImpl<C>::grouped_begin(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
@@ -1176,15 +1270,15 @@ int VerifyImpl<C>::grouped_begin(bpp_verifier* v, const uint64_t* d_points, cons
                                  const uint64_t* d_weights, uint32_t group, uint32_t* d_out_verdicts, void* d_workspace,
                                  size_t workspace_bytes, hipStream_t st) {
     const VerifyShape& s = v->s;
-    if (group < 2 || (group & (group - 1))) return fail(BPP_E_ARG, "group must be a power of two, at least 2");
+    if (int rc = check_group(group)) return rc;
     const GroupLayout L = group_layout(s, count, group);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     if (count * s.NV >= ((size_t)1 << 30)) return fail(BPP_E_ARG, "count too large");
     if (count == 0) return BPP_OK;
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
-    uint32_t *w_bad = W(L.bad), *w_sc = W(L.scalars), *w_rows = W(L.grows), *w_gbad = W(L.gbad), *w_gok = W(L.gok);
-    const size_t G = L.groups;
+    uint32_t *w_bad = W(L.bad), *w_sc = W(L.scalars), *w_rows = W(L.b.grows), *w_gbad = W(L.b.gbad);
+    const size_t G = L.b.groups;
     std::unique_lock<std::mutex> aux_lock;
     int rc = begin_pass(v, own(v), d_points, d_scalars, count, d_challenges, ws, L, w_sc, aux_lock, st, nullptr);
     if (rc) return rc;
@@ -1198,19 +1292,7 @@ int VerifyImpl<C>::grouped_begin(bpp_verifier* v, const uint64_t* d_points, cons
                                                  w_gbad, G);
                           });
     if (rc) return rc;
-    uint32_t* cur = W(L.vwsum);
-    uint32_t* nxt = W(L.vfold);
-    size_t nrem = count;
-    for (uint32_t left = group; left > 1; std::swap(cur, nxt)) {   // the proofs of a group are neighbours: 4 (at last 2) to 1 per level
-        const uint32_t step = left >= 4 ? 4u : 2u;
-        nrem = fold_windows(cur, nrem, step, nxt, per, st);
-        left /= step;
-    }
-    rc = finish(v, s, ws + L.tail, ws_layout(s, G), G, w_rows, cur, w_gbad, w_gok, nullptr, tree, false, st, nullptr);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_comb_group_spread, dim3(cdiv(count, 256)), dim3(256), 0, st, w_gok, group, d_out_verdicts, count);
-    HIPCHK(hipGetLastError());
-    return BPP_OK;
+    return group_back_end(v, s, ws, L.b, L.vwsum, per, tree, count, group, d_out_verdicts, st);
 }
 
 // the groups' verdicts come back to the host (synchronises `st`); pass 2: the proofs of the groups that failed, exactly,
@@ -1219,66 +1301,31 @@ template <class C>
 int VerifyImpl<C>::grouped_finish(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
                                   const uint64_t* d_challenges, uint32_t group, uint32_t* d_out_verdicts, uint64_t* h_stats,
                                   void* d_workspace, size_t workspace_bytes, hipStream_t st) {
-    const VerifyShape& s = v->s;
-    if (group < 2 || (group & (group - 1))) return fail(BPP_E_ARG, "group must be a power of two, at least 2");
-    const GroupLayout L = group_layout(s, count, group);
+    if (int rc = check_group(group)) return rc;
+    const GroupLayout L = group_layout(v->s, count, group);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     if (h_stats) h_stats[0] = h_stats[1] = 0;
     if (count == 0) return BPP_OK;
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-    auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
-    const size_t G = L.groups;
-    std::vector<uint32_t> gok(G);
-    HIPCHK(hipMemcpyAsync(gok.data(), W(L.gok), G * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
     std::vector<uint32_t> list;
-    size_t failed = 0;
-    for (size_t g = 0; g < G; g++)
-        if (gok[g]) {
-            failed++;
-            for (size_t p = g * group; p < std::min(count, (g + 1) * (size_t)group); p++) list.push_back((uint32_t)p);
-        }
-    if (h_stats) {
-        h_stats[0] = failed;
-        h_stats[1] = list.size();
-    }
-    const uint32_t row_pts = s.NV * WW, row_sc = 24, row_ch = (3 + s.k) * 8;
-    for (size_t lo = 0; lo < list.size(); lo += L.slice) {
-        const size_t cnt = std::min(L.slice, list.size() - lo);
-        HIPCHK(hipMemcpyAsync(W(L.list), list.data() + lo, cnt * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_comb_gather_rows, dim3((unsigned)cnt), dim3(256), 0, st,
-                           reinterpret_cast<const uint32_t*>(d_points), W(L.list), row_pts, W(L.x_pts));
-        hipLaunchKernelGGL(k_comb_gather_rows, dim3((unsigned)cnt), dim3(64), 0, st,
-                           reinterpret_cast<const uint32_t*>(d_scalars), W(L.list), row_sc, W(L.x_sc));
-        if (d_challenges)
-            hipLaunchKernelGGL(k_comb_gather_rows, dim3((unsigned)cnt), dim3(64), 0, st,
-                               reinterpret_cast<const uint32_t*>(d_challenges), W(L.list), row_ch, W(L.x_ch));
-        int rc = run(v, reinterpret_cast<const uint64_t*>(ws + L.x_pts), reinterpret_cast<const uint64_t*>(ws + L.x_sc), cnt,
-                     d_challenges ? reinterpret_cast<const uint64_t*>(ws + L.x_ch) : nullptr, W(L.x_ok), ws + L.x_run,
-                     workspace_bytes - L.x_run, nullptr, nullptr, st);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_comb_scatter_words, dim3(cdiv(cnt, 256)), dim3(256), 0, st, W(L.x_ok), W(L.list), d_out_verdicts,
-                           cnt);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(st));   // `list` slices are staged from pageable memory
-    }
-    return BPP_OK;
+    int rc = failing_groups(reinterpret_cast<const uint32_t*>(ws + L.b.gok), L.b.groups, group, count, h_stats, list, st);
+    if (rc) return rc;
+    return exact_pass(v, own(v), d_points, d_scalars, d_challenges, list, d_out_verdicts, ws, L.b, workspace_bytes, st);
 }
 
 // Pass 1: per class present, today's front end over the class's region with the class's view -- the proof points from the
 // wire, their tables, the verifier scalars, the weighted proof-point scalars and their window sums, `per` per proof into ONE
-// array by gathered position; then one row per group in the capacity shape's numbering, the groups' window sums, and the back
-// end once over G virtual proofs of the capacity shape.  Pass 2: the proofs of the failing groups, class by class (a class's
-// gathered range is contiguous), exactly, from the gathered regions.
+// array by gathered position; then one row per group in the capacity shape's numbering, and the back end once over G virtual
+// proofs of the capacity shape.  Pass 2: the proofs of the failing groups, class by class (a class's gathered range is
+// contiguous), exactly, from the class regions.
 template <class C>
 int VerifyImpl<C>::grouped_mixed_core(bpp_verifier* v, const MixedPlan& p, size_t count, uint32_t group, bool with_challenges,
                                       bool with_status, uint64_t* h_stats, uint8_t* ws, const GroupMixedLayout& L,
                                       size_t workspace_bytes, hipStream_t st) {
     const VerifyShape& cap = v->s;
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
-    auto U64 = [&](size_t off) { return reinterpret_cast<uint64_t*>(ws + off); };
-    uint32_t *w_bad = W(L.bad), *w_rows = W(L.grows), *w_gbad = W(L.gbad), *w_gok = W(L.gok), *w_ok = W(L.ok);
-    const size_t G = L.groups;
+    uint32_t *w_bad = W(L.bad), *w_ok = W(L.f.ok);
+    const size_t G = L.b.groups;
     const uint32_t tree = horner_form(cap, G);
     const uint32_t per = tree == 1 ? var_wsums<C>() : var_windows<C>();   // window sums per proof, as the Horner form of G reads them
     GroupClasses gc{};
@@ -1288,85 +1335,41 @@ int VerifyImpl<C>::grouped_mixed_core(bpp_verifier* v, const MixedPlan& p, size_
     for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
         gc.end[c] = (uint32_t)(p.first[c] + p.count[c]);
         gc.sc[c] = (L.sc_of[c] - L.scalars) / 32;
-        if (!p.count[c]) continue;
-        const PassShape ps = class_shape(v, c);
+    }
+    int rc = for_each_class(v, p, L.f, ws, [&](const ClassView& cv) {
         ClassFront F;
         F.pts = L.cpts, F.prep = L.prep, F.vtbl = L.vtbl, F.vscr = L.vscr, F.var_sc = L.var_sc, F.vdig = L.vdig;
-        F.bad = L.bad + p.first[c] * 4;
-        F.scalars = L.sc_of[c];
-        F.weights = L.weights + p.first[c] * 32;
-        F.vwsum = L.vwsum + p.first[c] * (size_t)per * JW * 4;
+        F.bad = L.bad + cv.first * 4;
+        F.scalars = L.sc_of[cv.c];
+        F.weights = L.weights + cv.first * 32;
+        F.vwsum = L.vwsum + cv.first * (size_t)per * JW * 4;
         std::unique_lock<std::mutex> aux_lock;
-        int rc = begin_pass(v, ps, U64(L.pts) + p.pt[c] * PW, U64(L.sc3) + p.first[c] * 12, p.count[c],
-                            with_challenges ? U64(L.challenges) + p.chal[c] * 4 : nullptr, ws, F, W(F.scalars), aux_lock, st,
-                            nullptr);
-        if (rc) return rc;
-        rc = weighted_middle(v, ps, ws, F, p.count[c], per, tree == 1 ? 1u : 0u, aux_lock, st);
-        if (rc) return rc;
-    }
-    if (with_status)
-        hipLaunchKernelGGL(k_comb_or_words, dim3(cdiv(count, 256)), dim3(256), 0, st, w_bad, W(L.status), count);
-    hipLaunchKernelGGL(k_comb_fixed_grouped_mixed<C>, dim3((unsigned)(G * cdiv(cap.NF, 64))), dim3(64), 0, st, cap, gc,
-                       W(L.scalars), W(L.weights), count, group, w_rows);
-    hipLaunchKernelGGL(k_comb_group_bad, dim3(cdiv(G, 256)), dim3(256), 0, st, w_bad, count, group, w_gbad, G);
-    uint32_t* cur = W(L.vwsum);
-    uint32_t* nxt = W(L.vfold);
-    size_t nrem = count;
-    for (uint32_t left = group; left > 1; std::swap(cur, nxt)) {   // as grouped_begin: 4 (at last 2) to 1 per level
-        const uint32_t step = left >= 4 ? 4u : 2u;
-        nrem = fold_windows(cur, nrem, step, nxt, per, st);
-        left /= step;
-    }
-    int rc = finish(v, cap, ws + L.tail, ws_layout(cap, G), G, w_rows, cur, w_gbad, w_gok, nullptr, tree, false, st, nullptr);
+        const int rc1 = begin_pass(v, cv.ps, cv.pts, cv.sc3, cv.count, with_challenges ? cv.challenges : nullptr, ws, F,
+                                   W(F.scalars), aux_lock, st, nullptr);
+        if (rc1) return rc1;
+        return weighted_middle(v, cv.ps, ws, F, cv.count, per, tree == 1 ? 1u : 0u, aux_lock, st);
+    });
     if (rc) return rc;
-    hipLaunchKernelGGL(k_comb_group_spread, dim3(cdiv(count, 256)), dim3(256), 0, st, w_gok, group, w_ok, count);
-    HIPCHK(hipGetLastError());
-    // pass 2
-    std::vector<uint32_t> gok(G);
-    HIPCHK(hipMemcpyAsync(gok.data(), w_gok, G * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    std::vector<uint32_t> redo[MIXED_CLASSES];   // per class, the failing groups' proofs as positions within the class
-    size_t failed = 0, redone = 0;
-    for (size_t g = 0; g < G; g++) {
-        if (!gok[g]) continue;
-        failed++;
-        for (size_t pos = g * group; pos < std::min(count, (g + 1) * (size_t)group); pos++) {
-            uint32_t c = 0;
-            while (pos >= p.first[c] + p.count[c]) c++;
-            redo[c].push_back((uint32_t)(pos - p.first[c]));
-            redone++;
-        }
+    if (with_status)
+        hipLaunchKernelGGL(k_comb_or_words, dim3(cdiv(count, 256)), dim3(256), 0, st, w_bad, W(L.f.status), count);
+    hipLaunchKernelGGL(k_comb_fixed_grouped_mixed<C>, dim3((unsigned)(G * cdiv(cap.NF, 64))), dim3(64), 0, st, cap, gc,
+                       W(L.scalars), W(L.weights), count, group, W(L.b.grows));
+    hipLaunchKernelGGL(k_comb_group_bad, dim3(cdiv(G, 256)), dim3(256), 0, st, w_bad, count, group, W(L.b.gbad), G);
+    rc = group_back_end(v, cap, ws, L.b, L.vwsum, per, tree, count, group, w_ok, st);
+    if (rc) return rc;
+    // pass 2: the failing positions, split into per class lists of positions within the class
+    std::vector<uint32_t> list, redo[MIXED_CLASSES];
+    rc = failing_groups(W(L.b.gok), G, group, count, h_stats, list, st);
+    if (rc) return rc;
+    uint32_t c = 0;
+    for (uint32_t pos : list) {
+        while (pos >= p.first[c] + p.count[c]) c++;
+        redo[c].push_back((uint32_t)(pos - p.first[c]));
     }
-    if (h_stats) {
-        h_stats[0] = failed;
-        h_stats[1] = redone;
-    }
-    for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
-        const std::vector<uint32_t>& list = redo[c];
-        if (list.empty()) continue;
-        const PassShape ps = class_shape(v, c);
-        const uint32_t row_pts = ps.s.NV * WW, row_sc = 24, row_ch = (3 + ps.s.k) * 8;
-        for (size_t lo = 0; lo < list.size(); lo += L.slice) {
-            const size_t cnt = std::min(L.slice, list.size() - lo);
-            HIPCHK(hipMemcpyAsync(W(L.list), list.data() + lo, cnt * 4, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_comb_gather_rows, dim3((unsigned)cnt), dim3(256), 0, st,
-                               reinterpret_cast<const uint32_t*>(U64(L.pts) + p.pt[c] * PW), W(L.list), row_pts, W(L.x_pts));
-            hipLaunchKernelGGL(k_comb_gather_rows, dim3((unsigned)cnt), dim3(64), 0, st,
-                               reinterpret_cast<const uint32_t*>(U64(L.sc3) + p.first[c] * 12), W(L.list), row_sc, W(L.x_sc));
-            if (with_challenges)
-                hipLaunchKernelGGL(k_comb_gather_rows, dim3((unsigned)cnt), dim3(64), 0, st,
-                                   reinterpret_cast<const uint32_t*>(U64(L.challenges) + p.chal[c] * 4), W(L.list), row_ch,
-                                   W(L.x_ch));
-            rc = run(v, ps, U64(L.x_pts), U64(L.x_sc), cnt, with_challenges ? U64(L.x_ch) : nullptr, W(L.x_ok), ws + L.x_run,
-                     workspace_bytes - L.x_run, nullptr, nullptr, st);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_comb_scatter_words, dim3(cdiv(cnt, 256)), dim3(256), 0, st, W(L.x_ok), W(L.list),
-                               w_ok + p.first[c], cnt);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(st));   // `list` slices are staged from pageable memory
-        }
-    }
-    return BPP_OK;
+    return for_each_class(v, p, L.f, ws, [&](const ClassView& cv) {
+        return exact_pass(v, cv.ps, cv.pts, cv.sc3, with_challenges ? cv.challenges : nullptr, redo[cv.c], w_ok + cv.first, ws,
+                          L.b, workspace_bytes, st);
+    });
 }
 
 template <class C>
@@ -1378,18 +1381,16 @@ int VerifyImpl<C>::run_grouped_mixed(bpp_verifier* v, const uint64_t* d_points, 
     MixedPlan p;
     int rc = mixed_plan(v->s, m_of, count, true, p);
     if (rc) return rc;
-    if (!group_ok(group)) return fail(BPP_E_ARG, "group must be a power of two, at least 2");
+    rc = check_group(group);
+    if (rc) return rc;
     const GroupMixedLayout L = group_mixed_layout(v, p, count, group, false);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     if (h_stats) h_stats[0] = h_stats[1] = 0;
     if (count == 0) return BPP_OK;
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-    uint32_t* w_idx = reinterpret_cast<uint32_t*>(ws + L.idx);
-    // pageable source: the copy has read it when the call returns
-    HIPCHK(hipMemcpyAsync(w_idx, p.idx.data(), p.idx.size() * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_mixed_gather<C>, dim3((unsigned)count), dim3(MIXED_BLOCK), 0, st, w_idx, count, d_points, d_scalars,
-                       d_challenges, reinterpret_cast<uint64_t*>(ws + L.pts), reinterpret_cast<uint64_t*>(ws + L.sc3),
-                       reinterpret_cast<uint64_t*>(ws + L.challenges));
+    uint32_t* w_idx = reinterpret_cast<uint32_t*>(ws + L.f.idx);
+    rc = gather_front(p, L.f, count, d_points, d_scalars, d_challenges, ws, st);
+    if (rc) return rc;
     // one lane per caller position: its weight, stored at its gathered position
     WeightKey wk;
     load_key_words(d_weights ? nullptr : weight_key, wk.w);
@@ -1400,7 +1401,7 @@ int VerifyImpl<C>::run_grouped_mixed(bpp_verifier* v, const uint64_t* d_points, 
     rc = grouped_mixed_core(v, p, count, group, d_challenges != nullptr, false, h_stats, ws, L, workspace_bytes, st);
     if (rc) return rc;
     hipLaunchKernelGGL(k_mixed_scatter<C>, dim3(cdiv(count, 4)), dim3(256), 0, st, w_idx, count,
-                       reinterpret_cast<const uint32_t*>(ws + L.ok), nullptr, nullptr, d_out_verdicts, nullptr, nullptr);
+                       reinterpret_cast<const uint32_t*>(ws + L.f.ok), nullptr, nullptr, d_out_verdicts, nullptr, nullptr);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
@@ -1411,46 +1412,37 @@ int VerifyImpl<C>::run_serialized_grouped_mixed(bpp_verifier* v, const uint8_t* 
                                                 const uint8_t* weight_key, uint64_t index_base, uint32_t group, uint32_t* d_ok,
                                                 uint64_t* h_stats, void* d_workspace, size_t workspace_bytes, hipStream_t st,
                                                 uint32_t version) {
-    if (v->s.n > 255 || v->s.m > 255) return fail(BPP_E_ARG, "the container holds n, m <= 255");
-    if (version != 1 && !(version == 2 && uncompressed_bytes<C>() != 0))
-        return fail(BPP_E_ARG, "container version 2 (uncompressed points) is not offered for this curve");
+    if (int rc = container_args_ok(v, version)) return rc;
     MixedPlan p;
     int rc = mixed_plan_serialized(v->s, m_of, count, (size_t)container_point_bytes<C>(version), true, p);
     if (rc) return rc;
-    if (!group_ok(group)) return fail(BPP_E_ARG, "group must be a power of two, at least 2");
+    rc = check_group(group);
+    if (rc) return rc;
     const GroupMixedLayout L = group_mixed_layout(v, p, count, group, true);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     if (h_stats) h_stats[0] = h_stats[1] = 0;
     if (count == 0) return BPP_OK;
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
-    auto U64 = [&](size_t off) { return reinterpret_cast<uint64_t*>(ws + off); };
-    uint32_t *w_idx = W(L.idx), *w_st = W(L.status);
-    // pageable source: the copy has read it when the call returns
-    HIPCHK(hipMemcpyAsync(w_idx, p.sidx.data(), p.sidx.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(zero_words_async(w_st, count * 4, st));
-    const unsigned waves = (unsigned)(p.lanes / SER_WAVE);
-    hipLaunchKernelGGL(k_container_decode_mixed<C>, dim3(waves), dim3(SER_WAVE), 0, st, p.classes, w_idx, d_proofs,
-                       d_commitments, W(L.pts), W(L.sc3), w_st, version);
-    if constexpr (C::ID == 0)   // cofactor > 1: membership of the prime-order subgroup
-        hipLaunchKernelGGL(k_records_subgroup_mixed<C>, dim3(waves), dim3(SER_WAVE), 0, st, p.classes, W(L.pts), w_st);
+    rc = decode_front(p, L.f, count, d_proofs, d_commitments, version, ws, st);
+    if (rc) return rc;
     // one lane per gathered position: the weight of its caller position
     WeightKey wk;
     load_key_words(weight_key, wk.w);
     hipLaunchKernelGGL(k_comb_weights_mixed<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, wk, index_base,
-                       (const uint32_t*)nullptr, w_idx, (uint32_t)SX_WORDS, (uint32_t)SX_CALLER, (uint32_t)SX_WORDS,
+                       (const uint32_t*)nullptr, W(L.f.idx), (uint32_t)SX_WORDS, (uint32_t)SX_CALLER, (uint32_t)SX_WORDS,
                        W(L.weights), count);
     HIPCHK(hipGetLastError());
-    if (transcript)
-        for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
-            if (!p.count[c]) continue;
-            rc = derive_challenges(v, class_shape(v, c), U64(L.pts) + p.pt[c] * PW, p.count[c],
-                                   U64(L.challenges) + p.chal[c] * 4, st);
-            if (rc) return rc;
-        }
+    if (transcript) {
+        rc = for_each_class(v, p, L.f, ws, [&](const ClassView& cv) {
+            return derive_challenges(v, cv.ps, cv.pts, cv.count, cv.challenges, st);
+        });
+        if (rc) return rc;
+    }
     rc = grouped_mixed_core(v, p, count, group, transcript, true, h_stats, ws, L, workspace_bytes, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_mixed_status_scatter<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, w_idx, w_st, W(L.ok), d_ok, count);
+    hipLaunchKernelGGL(k_mixed_status_scatter<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, W(L.f.idx), W(L.f.status), W(L.f.ok),
+                       d_ok, count);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
@@ -1609,9 +1601,7 @@ int VerifyImpl<C>::prove_serialized_mixed(bpp_verifier* v, const uint64_t* d_val
                                           uint64_t index_base, const uint64_t* d_blinding, uint8_t* d_out_proofs,
                                           uint8_t* d_out_commitments, void* d_workspace, size_t workspace_bytes, hipStream_t st,
                                           uint32_t version, bool amount64) {
-    if (v->s.n > 255 || v->s.m > 255) return fail(BPP_E_ARG, "the container holds n, m <= 255");
-    if (version != 1 && !(version == 2 && uncompressed_bytes<C>() != 0))
-        return fail(BPP_E_ARG, "container version 2 (uncompressed points) is not offered for this curve");
+    if (int rc = container_args_ok(v, version)) return rc;
     MixedPlan p;
     int rc = prove_plan(v->s, m_of, count, (size_t)container_point_bytes<C>(version), true, p);
     if (rc) return rc;

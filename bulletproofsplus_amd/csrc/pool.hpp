@@ -158,7 +158,7 @@ inline int pool_verify_serialized_mixed(bpp_pool* pool, const uint8_t* proofs, c
                                         uint32_t group, uint32_t* out_ok, uint64_t* stats) {
     const int curve = pool->shards[0].ctx->curve, version = (flags & BPP_SER_UNCOMPRESSED) ? 2 : 1;
     const size_t cb = container_point_size(curve, version);
-    if (cb == 0) return fail(BPP_E_ARG, "container version 2 (uncompressed points) is not offered for this curve");
+    if (int rc = container_version_ok(cb)) return rc;
     int rc = pool_check_m_of(pool, m_of, count);
     if (rc) return rc;
     const size_t world = pool->shards.size(), n = pool->shards[0].v->s.n;

@@ -267,6 +267,48 @@ def test_grouped_mixed_every_horner_form_and_exact_slices():
     bv.close()
 
 
+def test_grouped_mixed_exact_slices_with_caller_challenges():
+    """The exact pass's SECOND slice of one class with the caller's challenges present: the slice's challenge blocks are
+    gathered with the class's own row length (3 + k_i scalars).  Device-proved transcript proofs of two classes, tiled; more
+    tampered proofs in class 1 than one slice (2 048) and a few in class 2."""
+    torch = need_gpu()
+    import bulletproofsplus_amd as B
+    cname, cap_m, count, group, nbad = "bls12_381", 2, 6000, 2, 2500
+    opk = O.PublicKey(O.CURVE_IDS[cname], N * cap_m)
+    bv = B.BatchVerifier(B.PublicKey.from_points(B.Arith(cname), opk.gh, opk.G, opk.H), N, cap_m, window_bits=5)
+    bv.set_subgroup_check(True)
+    sizes = [1, 2] * 5
+    brecs, bsc = bv.prove_batch_mixed([[(200 + 31 * t + j) % 256 for j in range(m)] for t, m in enumerate(sizes)],
+                                      [[3 + t + j for j in range(m)] for t, m in enumerate(sizes)], transcript=True)
+    base = {m: [t for t in range(len(sizes)) if sizes[t] == m] for m in (1, 2)}
+    rng = np.random.RandomState(11)
+    ms = [1 if x < 0.67 else 2 for x in rng.rand(count)]
+    pick = [base[m][i] for m, i in zip(ms, rng.randint(0, 5, size=count))]
+    recs = [brecs[t] for t in pick]
+    scs = np.stack([bsc[t] for t in pick])
+    victims = sorted(rng.choice([i for i in range(count) if ms[i] == 1], size=nbad - 200, replace=False).tolist() +
+                     rng.choice([i for i in range(count) if ms[i] == 2], size=200, replace=False).tolist())
+    for v in victims:
+        scs[v, 2, 0] ^= np.uint64(2)
+    d_pts, _, _ = _upload(torch, bv, recs, scs)
+    nch = [3 + (N * m).bit_length() - 1 for m in ms]
+    d_ch = torch.zeros(sum(nch) * 4, dtype=torch.int64, device=torch.device("cuda:0"))
+    wsb = bv.mixed_workspace_bytes(ms)
+    d_ws = torch.empty(wsb, dtype=torch.uint8, device=torch.device("cuda:0"))
+    bv.derive_challenges_mixed_device(d_pts.data_ptr(), ms, d_ch.data_ptr(), d_ws.data_ptr(), wsb,
+                                      torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    off = np.concatenate([[0], np.cumsum(nch)]).astype(int)
+    flat = d_ch.cpu().numpy().view(np.uint64).reshape(-1, 4)
+    ch = [flat[off[i]:off[i + 1]] for i in range(count)]
+    exact = _both(torch, bv, recs, scs, ms, group, "challenges, two slices", seed=count, challenges=ch)
+    assert int(exact.sum()) == nbad and all(exact[v] == 1 for v in victims)
+    g = B.mixed_groups(ms, group)
+    hit = set(g[exact != 0].tolist())
+    assert sum(1 for i in range(count) if ms[i] == 1 and g[i] in hit) > 2048
+    bv.close()
+
+
 # ---- 5. transcript ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("cname", ("bls12_381", "secp256k1"))
 def test_grouped_mixed_transcript(cname):
