@@ -530,6 +530,80 @@ impl BatchVerifier {
             _ => Err(ProofError::VerificationError),
         }).collect())
     }
+    /// Mask recovery from wire data (include/bpp_amd.h: bpp_range_recover_masks_mixed): Gamma_i = gamma_0 + z^2 gamma_1 + ..
+    /// of proof i from its scalar triple, its challenge block (`challenges`: 3 + k_i scalars per proof in the order of `ms`,
+    /// or None for the reference's literals) and the blinding key it was made under; `index` names the blinding index of
+    /// each proof (None: index_base + i).  For ms[i] = 1 Gamma_i is the output's mask.  NOT a verification; key and index
+    /// together are a view key.  Err(FormatError) when an ms[i] is not taken or a length is not what `ms` implies: nothing
+    /// then reaches the engine.
+    pub fn recover_masks(&self, scalars: &[[PrimeFieldElem; 3]], ms: &[u32], challenges: Option<&[PrimeFieldElem]>,
+                         blind_key: &[u8; 32], index_base: u64, index: Option<&[u64]>) -> Result<Vec<PrimeFieldElem>, ProofError> {
+        let logn = self.k - self.m.trailing_zeros() as usize;
+        let mut nch = 0usize;
+        for &mi in ms {
+            let mi = mi as usize;
+            if mi == 0 || !mi.is_power_of_two() || mi > self.m {
+                return Err(ProofError::FormatError);
+            }
+            nch += 3 + logn + mi.trailing_zeros() as usize;
+        }
+        if scalars.len() != ms.len() || challenges.map_or(false, |c| c.len() != nch) || index.map_or(false, |x| x.len() != ms.len()) {
+            return Err(ProofError::FormatError);
+        }
+        if ms.is_empty() {
+            return Ok(Vec::new());
+        }
+        let flat: Vec<PrimeFieldElem> = scalars.iter().flat_map(|t| t.iter().cloned()).collect();
+        let sw = flat_scalars(&flat);
+        let cw = challenges.map(flat_scalars);
+        let mut out = vec![0u64; ms.len() * 4];
+        let rc = unsafe {
+            ffi::bpp_range_recover_masks_mixed(self.handle, sw.as_ptr(), ms.as_ptr(), ms.len(),
+                                               cw.as_ref().map_or(std::ptr::null(), |c| c.as_ptr()), blind_key.as_ptr(), index_base,
+                                               index.map_or(std::ptr::null(), |x| x.as_ptr()), std::ptr::null(), out.as_mut_ptr())
+        };
+        assert!(rc == 0, "bpp_range_recover_masks_mixed: {}", rc);
+        Ok(out.chunks(4).map(|c| PrimeFieldElem([c[0], c[1], c[2], c[3]])).collect())
+    }
+    /// Scans a block of serialized proofs (the input of `verify_serialized_mixed`, made under the transcript) for the outputs
+    /// of a blinding key (include/bpp_amd.h: bpp_range_scan_serialized_mixed).  `amounts`: one candidate amount per proof,
+    /// read for ms[i] = 1 (None: nothing is confirmed); amount64: the proofs commit whole u64 amounts (BPP_PROVE_AMOUNT64).
+    /// Per proof (status, Gamma): 0 -- the output opens to (amount, Gamma), it is the key's and Gamma its mask; 1 -- it does
+    /// not (Gamma zero); 2 -- FormatError (Gamma zero); 3 (BPP_SCAN_UNCONFIRMED) -- no amount, or ms[i] > 1.  A scan is NOT a
+    /// verification: scan what has been verified.  Err(FormatError) as for `verify_serialized_mixed`.
+    pub fn scan_serialized_mixed(&self, proofs: &[u8], commitments: &[u8], ms: &[u32], amount64: bool, blind_key: &[u8; 32],
+                                 index_base: u64, index: Option<&[u64]>, amounts: Option<&[u64]>)
+                                 -> Result<Vec<(u32, PrimeFieldElem)>, ProofError> {
+        let n = 1usize << (self.k - self.m.trailing_zeros() as usize);
+        let cb = unsafe { ffi::bpp_point_compressed_bytes(ffi::BPP_BLS12_381_G1) };
+        let (mut pbytes, mut cbytes) = (0usize, 0usize);
+        for &mi in ms {
+            let mi = mi as usize;
+            if mi == 0 || !mi.is_power_of_two() || mi > self.m {
+                return Err(ProofError::FormatError);
+            }
+            pbytes += unsafe { ffi::bpp_proof_bytes(ffi::BPP_BLS12_381_G1, n, mi) };
+            cbytes += mi * cb;
+        }
+        if pbytes != proofs.len() || cbytes != commitments.len() || index.map_or(false, |x| x.len() != ms.len())
+            || amounts.map_or(false, |x| x.len() != ms.len()) {
+            return Err(ProofError::FormatError);
+        }
+        if ms.is_empty() {
+            return Ok(Vec::new());
+        }
+        let flags = ffi::BPP_SER_TRANSCRIPT | if amount64 { ffi::BPP_PROVE_AMOUNT64 } else { 0 };
+        let mut masks = vec![0u64; ms.len() * 4];
+        let mut status = vec![0u32; ms.len()];
+        let rc = unsafe {
+            ffi::bpp_range_scan_serialized_mixed(self.handle, proofs.as_ptr(), commitments.as_ptr(), ms.as_ptr(), ms.len(), flags,
+                                                 blind_key.as_ptr(), index_base, index.map_or(std::ptr::null(), |x| x.as_ptr()),
+                                                 std::ptr::null(), amounts.map_or(std::ptr::null(), |x| x.as_ptr()),
+                                                 masks.as_mut_ptr(), status.as_mut_ptr())
+        };
+        assert!(rc == 0, "bpp_range_scan_serialized_mixed: {}", rc);
+        Ok(status.iter().zip(masks.chunks(4)).map(|(&s, c)| (s, PrimeFieldElem([c[0], c[1], c[2], c[3]]))).collect())
+    }
 }
 
 /// The cuts of a batch over `world` shards (include/bpp_amd.h: bpp_shard_cuts): shard r takes proofs

@@ -29,6 +29,7 @@ from ._lib import BLS12_381_G1, SECP256K1, ED25519, CURVE_IDS, BppError, check  
 
 
 AMOUNT64 = 0x100   # BPP_PROVE_AMOUNT64 (include/bpp_amd.h): commitments over the whole 64-bit amount
+SCAN_UNCONFIRMED = 3   # BPP_SCAN_UNCONFIRMED: a scanned proof with no candidate amount, or of more than one output
 
 
 class ProofError(Exception):
@@ -1242,6 +1243,124 @@ class BatchVerifier:
             ctypes.c_uint64(index_base), _ptr(raw), _ptr(cm)),
             "bpp_range_prove_batch_serialized_mixed")
         return raw[:nbytes].tobytes(), cm[:int(ms.sum()) * pb].tobytes(), ms
+
+    # ---- mask recovery and scanning: the receiver's side (include/bpp_amd.h "mask recovery") ----
+    def _blinding_args(self, blind_key, index, blinding, count: int, ms):
+        """host-side blinding arguments of the recovery calls -> (key, index array or None, blinding array or None)"""
+        if blind_key is not None and len(blind_key) != 32:
+            raise ValueError("blind_key: 32 bytes")
+        idx = bl = None
+        if index is not None:
+            idx = np.ascontiguousarray(np.asarray([int(x) for x in index], dtype=np.uint64))
+            if len(idx) != count:
+                raise RuntimeError("one index per proof")
+        if blinding is not None:
+            if isinstance(blinding, np.ndarray) and blinding.dtype == np.uint64:
+                bl = np.ascontiguousarray(blinding).reshape(-1, 4)
+            else:
+                bl = scalars_to_wire([int(x) for row in blinding for x in row])
+            if all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in ms):
+                need = sum(5 + 2 * ((self.n * int(x)).bit_length() - 1) for x in ms)
+                if len(bl) != need:
+                    raise RuntimeError("blinding: 5 + 2 k_i scalars per proof (%d in all), got %d" % (need, len(bl)))
+        return blind_key, idx, bl
+
+    def recover_workspace_bytes(self, ms, serialized: bool = False) -> int:
+        """bytes of device workspace recover_masks_device (serialized: scan_serialized_mixed_device) needs (0: an m_i is
+        not taken)"""
+        m = self._ms(ms)
+        f = _lib.lib().bpp_scan_serialized_mixed_workspace_bytes if serialized else _lib.lib().bpp_recover_mixed_workspace_bytes
+        return f(self.handle, _ptr(m) if len(m) else None, len(m))
+
+    def recover_masks_device(self, d_scalars: int, ms, d_out_masks: int, d_workspace: int, workspace_bytes: int,
+                             stream: int = 0, d_challenges: int = 0, blind_key: bytes = None, index_base: int = 0,
+                             d_index: int = 0, d_blinding: int = 0):
+        """Gamma_i = gamma_0 + z^2 gamma_1 + .. of every proof of a resident mixed batch, from its scalar triple, its
+        challenge block (d_challenges: the packed blocks derive_challenges_mixed_device writes; 0: the literals) and its
+        blinding: blind_key with index d_index[i] or index_base + i, or d_blinding, or the literals.  For ms[i] = 1
+        Gamma_i is the output's mask.  Not a verification.  d_out_masks: (count, 4) u64 in caller order."""
+        m = self._ms(ms)
+        check(_lib.lib().bpp_range_recover_masks_mixed_device(
+            self.handle, d_scalars, _ptr(m) if len(m) else None, len(m), d_challenges or None, blind_key,
+            ctypes.c_uint64(index_base), d_index or None, d_blinding or None, d_out_masks, d_workspace, workspace_bytes,
+            stream or None), "bpp_range_recover_masks_mixed_device")
+
+    def recover_masks(self, scalars, ms, challenges=None, blind_key: bytes = None, index_base: int = 0, index=None,
+                      blinding=None) -> list:
+        """scalars (count, 3, 4); ms: m_i per proof; challenges: None (the literals) or the per-proof blocks (a list of
+        (3 + k_i, 4) arrays or one packed array); index: None or one blinding index per proof; blinding: None or per proof
+        its 5 + 2 k_i scalars -> [Gamma_i] as ints (bpp_range_recover_masks_mixed)"""
+        m = self._ms(ms)
+        count = len(m)
+        sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 3, 4)
+        if sc.shape[0] != count:
+            raise RuntimeError("recover_masks: one scalar triple per proof")
+        key, idx, bl = self._blinding_args(blind_key, index, blinding, count, m)
+        ch = None
+        if challenges is not None:
+            ch = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.uint64).reshape(-1, 4) for c in challenges])
+                                      if isinstance(challenges, (list, tuple)) else
+                                      np.asarray(challenges, dtype=np.uint64).reshape(-1, 4))
+            if all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m):
+                need = sum(3 + (self.n * int(x)).bit_length() - 1 for x in m)
+                if len(ch) != need:
+                    raise RuntimeError("recover_masks: 3 + k_i challenges per proof (%d in all), got %d" % (need, len(ch)))
+        out = np.zeros((count, 4), dtype=np.uint64)
+        check(_lib.lib().bpp_range_recover_masks_mixed(
+            self.handle, _ptr(sc) if count else None, _ptr(m) if count else None, count, _ptr(ch) if ch is not None else None,
+            key, ctypes.c_uint64(index_base), _ptr(idx) if idx is not None else None, _ptr(bl) if bl is not None else None,
+            _ptr(out) if count else None), "bpp_range_recover_masks_mixed")
+        return [wire_to_int(x) for x in out]
+
+    def scan_serialized_mixed_device(self, d_proofs: int, d_commitments: int, ms, d_out_masks: int, d_status: int,
+                                     d_workspace: int, workspace_bytes: int, stream: int = 0, transcript: bool = False,
+                                     uncompressed: bool = False, amount64: bool = False, blind_key: bytes = None,
+                                     index_base: int = 0, d_index: int = 0, d_blinding: int = 0, d_amounts: int = 0):
+        """Scans a resident block of containers (verify_serialized_mixed_device's input) for the outputs of a key: decoder,
+        challenges, Gamma_i, and for ms[i] = 1 with a candidate amount d_amounts[i] the test V_0 == v g + Gamma h.
+        d_status[i]: 0 the output is the key's and d_out_masks[i] its mask / 1 it is not (mask zero) / 2 FormatError (mask
+        zero) / 3 unconfirmed -- no amount, or ms[i] > 1 (Gamma as computed).  A scan is not a verification."""
+        m = self._ms(ms)
+        check(_lib.lib().bpp_range_scan_serialized_mixed_device(
+            self.handle, d_proofs, d_commitments, _ptr(m) if len(m) else None, len(m),
+            (1 if transcript else 0) | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0), blind_key,
+            ctypes.c_uint64(index_base), d_index or None, d_blinding or None, d_amounts or None, d_out_masks, d_status,
+            d_workspace, workspace_bytes, stream or None), "bpp_range_scan_serialized_mixed_device")
+
+    def scan_serialized_mixed(self, proofs, commitments, ms=None, transcript: bool = False, uncompressed: bool = False,
+                              amount64: bool = False, blind_key: bytes = None, index_base: int = 0, index=None,
+                              blinding=None, amounts=None):
+        """proofs, commitments, ms: as verify_serialized_mixed; amounts: None or one candidate amount per proof (read for
+        ms[i] = 1) -> (status (count,) u32, [Gamma_i] as ints); see scan_serialized_mixed_device for the status words"""
+        def flat(x):
+            return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
+        raw, cm = flat(proofs), flat(commitments)
+        version = 2 if uncompressed else 1
+        m = proofs_scan(self.arith, self.n, raw, version) if ms is None else self._ms(ms)
+        count = len(m)
+        if all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m):
+            pb = uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)
+            need = sum(proof_bytes(self.arith, self.n, int(x), version) for x in m)
+            if len(raw) != need:
+                raise RuntimeError("scan_serialized_mixed: %d bytes of proofs, the shapes in ms need %d" % (len(raw), need))
+            if len(cm) != int(m.sum()) * pb:
+                raise RuntimeError("scan_serialized_mixed: ms[i] commitments per proof")
+        key, idx, bl = self._blinding_args(blind_key, index, blinding, count, m)
+        am = None
+        if amounts is not None:
+            am = np.ascontiguousarray(np.asarray([int(x) for x in amounts], dtype=np.uint64))
+            if len(am) != count:
+                raise RuntimeError("scan_serialized_mixed: one candidate amount per proof")
+        masks = np.zeros((count, 4), dtype=np.uint64)
+        status = np.zeros(count, dtype=np.uint32)
+        check(_lib.lib().bpp_range_scan_serialized_mixed(
+            self.handle, _ptr(raw) if len(raw) else None, _ptr(cm) if len(cm) else None, _ptr(m) if count else None, count,
+            (1 if transcript else 0) | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0), key,
+            ctypes.c_uint64(index_base), _ptr(idx) if idx is not None else None, _ptr(bl) if bl is not None else None,
+            _ptr(am) if am is not None else None, _ptr(masks) if count else None, _ptr(status) if count else None),
+            "bpp_range_scan_serialized_mixed")
+        return status, [wire_to_int(x) for x in masks]
 
 
 def shard_cuts(ms, count: int, world: int) -> np.ndarray:

@@ -8,6 +8,7 @@
 #include "impl_prove.hpp"
 #include "impl_verify.hpp"
 #include "impl_wip.hpp"
+#include "recover.hpp"
 
 using namespace bpp;
 
@@ -1363,6 +1364,110 @@ extern "C" int bpp_commit_batch(bpp_verifier* engine, const uint64_t* v, const u
     if (!v || !gamma || !out_V) return fail(BPP_E_ARG, "null argument");
     return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
         return CommitImpl<decltype(cv)>::commit_batch(engine, v, gamma, count, (flags & BPP_PROVE_AMOUNT64) != 0, out_V);
+    });
+}
+
+// ---- mask recovery and scanning (recover.hpp; the quantities inverted: range/mod.rs:159-172, wip.rs:94-95,175-227) ----
+namespace {
+// What the recovery and scan calls can answer before the engine handle is read: an m_i no engine takes (zero, or not a
+// power of two; one above the engine's m is the plan's to name), the blinding rules, a workspace of no bytes.
+// Runs under the guard itself (the error text is built on the heap).
+int recover_args(const uint32_t* m_of, size_t count, const uint8_t* blind_key, const void* index, const void* blinding) noexcept {
+    return guarded([&]() -> int {
+        if (blind_key && blinding) return fail(BPP_E_ARG, "blind_key and d_blinding are both given");
+        if (index && !blind_key) return fail(BPP_E_ARG, "d_index is the index of a blind_key: it needs one");
+        if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+        for (size_t i = 0; i < count; i++)
+            if (m_of[i] == 0 || (m_of[i] & (m_of[i] - 1)))
+                return fail(BPP_E_ARG, "m_of[" + std::to_string(i) + "] = " + std::to_string(m_of[i]) + ": not a power of two");
+        return BPP_OK;
+    });
+}
+bool m_of_wellformed(const uint32_t* m_of, size_t count) noexcept {
+    for (size_t i = 0; i < count; i++)
+        if (m_of[i] == 0 || (m_of[i] & (m_of[i] - 1))) return false;
+    return true;
+}
+constexpr int SCAN_FLAGS = BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED | BPP_PROVE_AMOUNT64;
+}  // namespace
+
+extern "C" size_t bpp_recover_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
+    if ((count && !m_of) || count > 0x7fffffffu / 64 || !m_of_wellformed(m_of, count)) return 0;
+    return size_for(v, [&](auto cv) { return RecoverImpl<decltype(cv)>::recover_workspace_bytes(v, m_of, count); });
+}
+
+extern "C" int bpp_range_recover_masks_mixed_device(bpp_verifier* v, const uint64_t* d_scalars, const uint32_t* m_of, size_t count,
+                                                    const uint64_t* d_challenges, const uint8_t* blind_key, uint64_t index_base,
+                                                    const uint64_t* d_index, const uint64_t* d_blinding, uint64_t* d_out_masks,
+                                                    void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!v) return fail(BPP_E_ARG, "null argument");
+    if (count == 0) return BPP_OK;
+    if (!d_scalars || !m_of || !d_out_masks || !d_workspace) return fail(BPP_E_ARG, "null argument");
+    if (int rc = recover_args(m_of, count, blind_key, d_index, d_blinding)) return rc;
+    if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        using R = RecoverImpl<decltype(cv)>;
+        return R::recover_masks_mixed(v, d_scalars, m_of, count, d_challenges,
+                                      typename R::Blinding{blind_key, index_base, d_index, d_blinding}, d_out_masks, d_workspace,
+                                      workspace_bytes, static_cast<hipStream_t>(stream));
+    });
+}
+
+// host buffers in, host masks out: the device path above between copies
+extern "C" int bpp_range_recover_masks_mixed(bpp_verifier* v, const uint64_t* scalars, const uint32_t* m_of, size_t count,
+                                             const uint64_t* challenges, const uint8_t* blind_key, uint64_t index_base,
+                                             const uint64_t* index, const uint64_t* blinding, uint64_t* out_masks) {
+    if (!v) return fail(BPP_E_ARG, "null argument");
+    if (count == 0) return BPP_OK;
+    if (!scalars || !m_of || !out_masks) return fail(BPP_E_ARG, "null argument");
+    if (int rc = recover_args(m_of, count, blind_key, index, blinding)) return rc;
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return RecoverImpl<decltype(cv)>::recover_masks_mixed_host(v, scalars, m_of, count, challenges, blind_key, index_base,
+                                                                   index, blinding, out_masks);
+    });
+}
+
+extern "C" size_t bpp_scan_serialized_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
+    if ((count && !m_of) || count > 0x7fffffffu / 64 || !m_of_wellformed(m_of, count)) return 0;
+    return size_for(v, [&](auto cv) { return RecoverImpl<decltype(cv)>::scan_workspace_bytes(v, m_of, count); });
+}
+
+extern "C" int bpp_range_scan_serialized_mixed_device(bpp_verifier* v, const void* d_proofs, const void* d_commitments,
+                                                      const uint32_t* m_of, size_t count, int flags, const uint8_t* blind_key,
+                                                      uint64_t index_base, const uint64_t* d_index, const uint64_t* d_blinding,
+                                                      const uint64_t* d_amounts, uint64_t* d_out_masks, uint32_t* d_status,
+                                                      void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!v) return fail(BPP_E_ARG, "null argument");
+    if (flags & ~SCAN_FLAGS) return fail(BPP_E_ARG, "unknown flag");
+    if (count == 0) return BPP_OK;
+    if (!d_proofs || !d_commitments || !m_of || !d_out_masks || !d_status || !d_workspace) return fail(BPP_E_ARG, "null argument");
+    if (int rc = recover_args(m_of, count, blind_key, d_index, d_blinding)) return rc;
+    if ((blind_key || d_blinding) && !(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
+    if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        using R = RecoverImpl<decltype(cv)>;
+        return R::scan_serialized_mixed(v, static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), m_of,
+                                        count, (flags & BPP_SER_TRANSCRIPT) != 0, (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u,
+                                        (flags & BPP_PROVE_AMOUNT64) != 0,
+                                        typename R::Blinding{blind_key, index_base, d_index, d_blinding}, d_amounts, d_out_masks,
+                                        d_status, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    });
+}
+
+// host buffers in, host masks and statuses out: the device path above between copies
+extern "C" int bpp_range_scan_serialized_mixed(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments,
+                                               const uint32_t* m_of, size_t count, int flags, const uint8_t* blind_key,
+                                               uint64_t index_base, const uint64_t* index, const uint64_t* blinding,
+                                               const uint64_t* amounts, uint64_t* out_masks, uint32_t* out_status) {
+    if (!v) return fail(BPP_E_ARG, "null argument");
+    if (flags & ~SCAN_FLAGS) return fail(BPP_E_ARG, "unknown flag");
+    if (count == 0) return BPP_OK;
+    if (!proofs || !commitments || !m_of || !out_masks || !out_status) return fail(BPP_E_ARG, "null argument");
+    if (int rc = recover_args(m_of, count, blind_key, index, blinding)) return rc;
+    if ((blind_key || blinding) && !(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return RecoverImpl<decltype(cv)>::scan_serialized_mixed_host(v, proofs, commitments, m_of, count, flags, blind_key,
+                                                                     index_base, index, blinding, amounts, out_masks, out_status);
     });
 }
 

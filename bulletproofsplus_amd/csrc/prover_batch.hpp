@@ -20,6 +20,7 @@
 // consts[...]; virtual-proof scalar arrays vps[(2k+3+m)][N][8] in the verifier's MulVec layout
 // (fixed_term_index), canonical.
 #pragma once
+#include "blind_layout.hpp"
 #include "kernels.hpp"
 
 namespace bpp {
@@ -56,8 +57,7 @@ __device__ __forceinline__ T* pb_commitments(T* out_points, T* out_V, const uint
 // r', s', delta' give away the folded a, b and a linear combination of the gammas).  A caller that wants hiding proofs
 // supplies them per proof -- `blind`: [count][5 + 2k] canonical scalars [alpha, r, s, delta, eta, d_L[0..k), d_R[0..k)] --
 // either as a buffer of its own or expanded from a 32-byte secret key by k_pb_blind.  blind == nullptr: the literals.
-__host__ __device__ inline uint32_t pb_blind_elems(uint32_t k) { return 5 + 2 * k; }
-enum { PB_BL_ALPHA = 0, PB_BL_R = 1, PB_BL_S = 2, PB_BL_DELTA = 3, PB_BL_ETA = 4, PB_BL_DL = 5 };
+// (pb_blind_elems and the slot numbers PB_BL_*: blind_layout.hpp, shared with the recovery of the masks)
 template <class P>
 __device__ __forceinline__ Fe<P> pb_blind(uint32_t literal, const uint32_t* __restrict__ blind, size_t p, uint32_t k,
                                           uint32_t slot) {
@@ -68,6 +68,7 @@ __device__ __forceinline__ Fe<P> pb_blind(uint32_t literal, const uint32_t* __re
 }
 // blind[p][slot] = (c0 + 2^256 c1) mod r,  c_h = SHA-256(key[32] || "bppb" || (index_base + p) as u64 LE || slot as u32 LE
 // || h as u32 LE) read as little-endian 256-bit integers; zero is replaced by one.  One lane per (proof, slot).
+// (recover_terms.hpp blind_slot computes the same slot in registers alone, for the kernel that reads proofs back.)
 // px != null (a mixed block): p is the proof's position in the CALLER's numbering, whatever its gathered position.
 struct BlindKey {
     uint32_t w[8];   // the 32 key bytes as little-endian words

@@ -626,6 +626,76 @@ int bpp_commit_batch_device(bpp_verifier *engine, const uint64_t *d_v, const uin
 int bpp_commit_batch(bpp_verifier *engine, const uint64_t *v, const uint64_t *gamma, size_t count, int flags,
                      uint64_t *out_V);
 
+/* ---- mask recovery ("rewind") and scanning: the receiver's side of a proof ----
+ * "Blinding" above states as a warning that whoever knows alpha, delta, eta, d_L, d_R reads a linear combination of the
+ * gammas off delta'.  For the holder of the blinding key that is the feature: the key derives exactly those scalars from
+ * (blind_key, index, slot), so the mask of an output comes back out of its proof.  The quantities inverted are the
+ * prover's own (reference src/range/mod.rs:159-172: alpha_hat = alpha + y^(nm+1) gamma, the m > 1 form at :366-376;
+ * src/weighted_inner_product_proof.rs:94-95,175-227: d_L, d_R enter alpha in every round, delta' = eta + delta e +
+ * alpha e^2).  With [y, z, e, e_1..e_k] the challenge block of a proof of shape (n, m), k = log2(n m):
+ *     alpha_k = (delta' - eta - delta e) e^-2
+ *     S       = (alpha_k - sum_t (e_t^2 d_L[t] + e_t^-2 d_R[t]) - alpha) y^-(nm+1)
+ *     Gamma   = gamma_0 + z^2 gamma_1 + .. + z^(2(m-1)) gamma_{m-1}  =  S for m = 1, S z^-2 for m > 1
+ * so for a single output Gamma IS its mask gamma.  A zero challenge leaves an inversion undefined: Gamma is then written
+ * as zero (and a scan treats the proof as unconfirmed).
+ * A SCAN IS NOT A VERIFICATION.  Nothing here checks a proof: Gamma of an invalid proof is a number like any other, and
+ * status 0 below says that V_0 opens to (v, Gamma), not that the proof is sound.  Scan what has been verified.
+ * blind_key TOGETHER WITH THE INDEX IS A VIEW KEY for every proof made with it: whoever holds both reads the mask of
+ * every single-output proof the key blinded (and Gamma of the aggregated ones).  Hand it out as such, to wallets and
+ * auditors, and to nobody else.  THE INDEX RULE HOLDS: a key never meets an index twice, on the proving side; the recovery
+ * must name the index each proof was MADE with, in the caller's numbering -- d_index[i] when given, else index_base + i.  A
+ * scanner does not see proofs in the order they were made: d_index carries that order.
+ * The blinding source is one of: blind_key (32 bytes, host) with the index rule above; d_blinding (device), the prover's
+ * layout, 5 + 2 k_i canonical scalars per proof packed in caller order; both NULL, the reference's literals (whose proofs
+ * hide nothing).  m_of follows "mixed batches" above (HOST array, m_i a power of two <= the engine's m).
+ * A proof is sixteen lanes of k_recover_masks (csrc/recover.hpp), one per term; every shape bpp_verifier_create admits has
+ * at most 14 terms (k <= 12), and a k above 14 would be BPP_E_ARG.
+ *
+ * RECOVERY FROM WIRE DATA reads the scalar triples and the challenge blocks only, no points:
+ *   d_scalars     : count x 3 scalars [r', s', delta'] in caller order (bpp_verifier_run_mixed's)
+ *   d_challenges  : the packed 3 + k_i blocks (bpp_verifier_derive_challenges_mixed's output), or NULL: the literals of
+ *                   each proof's own shape
+ *   d_out_masks   : count x 4 words, canonical Gamma_i in caller order
+ *   d_workspace   : bpp_recover_mixed_workspace_bytes(v, m_of, count) bytes (0 when an m_i is not taken)
+ * SCANNING FROM BYTES takes bpp_range_verify_batch_serialized_mixed_device's input (d_proofs, d_commitments, m_of) and
+ * runs its decoder, membership test and -- BPP_SER_TRANSCRIPT -- challenges, then the recovery instead of the verifier's
+ * pass, and for single outputs the confirmation V_0 == v g + Gamma h through the engine's window tables
+ * (k_recover_confirm, the lane of k_commit_batch).
+ *   flags         : BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED | BPP_PROVE_AMOUNT64 (the scalar on g is the whole uint64_t,
+ *                   as the proofs were made; without it new(v as i32), src/range/prover.rs:37)
+ *   d_amounts     : count x uint64_t, one candidate amount per proof in caller order, read for m_i = 1 only; may be NULL
+ *   d_out_masks   : count x 4 words ; d_status : count words, caller order:
+ *                     0                     m_i = 1, amount given, V_0 == v g + Gamma h: the output belongs to the key and
+ *                                           Gamma is its mask
+ *                     1                     m_i = 1, amount given, the equation fails (another key, another amount); mask zero
+ *                     2                     the decoder's FormatError, exactly as in the verify calls; mask zero
+ *                     BPP_SCAN_UNCONFIRMED  no amount given, or m_i > 1: Gamma is written as computed
+ *   d_workspace   : bpp_scan_serialized_mixed_workspace_bytes(v, m_of, count) bytes (0 when an m_i is not taken)
+ * Errors: BPP_E_ARG for a NULL required pointer, a workspace that is too small, an m_of[i] that is not taken (the text
+ * names i), blind_key and d_blinding both given, d_index without blind_key, blinding without BPP_SER_TRANSCRIPT on the
+ * scan calls (as the prove calls rule), an unknown flag; nothing is enqueued and nothing is written then.  count = 0 is
+ * BPP_OK.  Both device calls BLOCK the host only while they upload the per-proof index; the rest is enqueued on `stream`.
+ * The host-buffer twins take every buffer (index, blinding, amounts included) from the host and are synchronous. */
+#define BPP_SCAN_UNCONFIRMED 3
+size_t bpp_recover_mixed_workspace_bytes(const bpp_verifier *v, const uint32_t *m_of, size_t count);
+int bpp_range_recover_masks_mixed_device(bpp_verifier *v, const uint64_t *d_scalars, const uint32_t *m_of, size_t count,
+                                         const uint64_t *d_challenges, const uint8_t *blind_key, uint64_t index_base,
+                                         const uint64_t *d_index, const uint64_t *d_blinding, uint64_t *d_out_masks,
+                                         void *d_workspace, size_t workspace_bytes, void *stream);
+int bpp_range_recover_masks_mixed(bpp_verifier *v, const uint64_t *scalars, const uint32_t *m_of, size_t count,
+                                  const uint64_t *challenges, const uint8_t *blind_key, uint64_t index_base,
+                                  const uint64_t *index, const uint64_t *blinding, uint64_t *out_masks);
+size_t bpp_scan_serialized_mixed_workspace_bytes(const bpp_verifier *v, const uint32_t *m_of, size_t count);
+int bpp_range_scan_serialized_mixed_device(bpp_verifier *v, const void *d_proofs, const void *d_commitments,
+                                           const uint32_t *m_of, size_t count, int flags, const uint8_t *blind_key,
+                                           uint64_t index_base, const uint64_t *d_index, const uint64_t *d_blinding,
+                                           const uint64_t *d_amounts, uint64_t *d_out_masks, uint32_t *d_status,
+                                           void *d_workspace, size_t workspace_bytes, void *stream);
+int bpp_range_scan_serialized_mixed(bpp_verifier *v, const uint8_t *proofs, const uint8_t *commitments, const uint32_t *m_of,
+                                    size_t count, int flags, const uint8_t *blind_key, uint64_t index_base,
+                                    const uint64_t *index, const uint64_t *blinding, const uint64_t *amounts,
+                                    uint64_t *out_masks, uint32_t *out_status);
+
 /* ---- the weighted inner product argument as a seam of its own: WeightedInnerProductProof::{prove, verify} ----
  * Reference: src/weighted_inner_product_proof.rs:36-227 (prove), :238-328 (verify), :330-382 (verification_scalars).
  * An engine created for (n, m) proves and verifies the WIP relation over its key for ANY statement that ends in one; only

@@ -185,6 +185,59 @@ inline std::vector<Point> commit_batch(bpp_verifier* engine, const std::vector<u
     return V;
 }
 
+// Mask recovery from wire data (bpp_range_recover_masks_mixed): Gamma_i = gamma_0 + z^2 gamma_1 + .. of proof i from its
+// scalar triple [r', s', delta'], its challenge block (`challenges`: the 3 + k_i scalars of every proof back to back, or empty
+// for the reference's literals) and the blinding key it was made under; `index` names each proof's blinding index (empty:
+// index_base + i).  For ms[i] = 1 Gamma_i is the output's mask.  NOT a verification; key and index together are a view key.
+inline std::vector<PrimeFieldElem> recover_masks(bpp_verifier* engine, const std::vector<PrimeFieldElem>& scalars,
+                                                 const std::vector<uint32_t>& ms, const std::vector<PrimeFieldElem>& challenges,
+                                                 const std::array<uint8_t, 32>& blind_key, uint64_t index_base = 0,
+                                                 const std::vector<uint64_t>& index = {}) {
+    if (scalars.size() != 3 * ms.size()) throw std::logic_error("recover_masks: three scalars per proof");
+    if (!index.empty() && index.size() != ms.size()) throw std::logic_error("recover_masks: one index per proof");
+    std::vector<uint64_t> sw, cw, out(ms.size() * 4 + 1);
+    for (auto& s : scalars) sw.insert(sw.end(), s.e.begin(), s.e.end());
+    for (auto& c : challenges) cw.insert(cw.end(), c.e.begin(), c.e.end());
+    if (bpp_range_recover_masks_mixed(engine, sw.data(), ms.data(), ms.size(), cw.empty() ? nullptr : cw.data(), blind_key.data(),
+                                      index_base, index.empty() ? nullptr : index.data(), nullptr, out.data()) != BPP_OK)
+        throw std::runtime_error(std::string("bpp_range_recover_masks_mixed: ") + bpp_last_error());
+    std::vector<PrimeFieldElem> masks(ms.size());
+    for (size_t i = 0; i < ms.size(); i++)
+        for (int t = 0; t < 4; t++) masks[i].e[t] = out[i * 4 + t];
+    return masks;
+}
+
+// Scanning a block of serialized proofs made under the transcript for the outputs of a blinding key
+// (bpp_range_scan_serialized_mixed): proofs, commitments and ms as bpp_range_verify_batch_serialized_mixed takes them;
+// `amounts` one candidate amount per proof, read for ms[i] = 1 (empty: nothing is confirmed); amount64: the proofs commit
+// whole u64 amounts.  status[i]: 0 the output opens to (amount, Gamma) -- it is the key's, Gamma its mask; 1 it does not (Gamma
+// zero); 2 FormatError (Gamma zero); BPP_SCAN_UNCONFIRMED no amount or ms[i] > 1.  A scan is NOT a verification.
+struct ScanResult {
+    std::vector<uint32_t> status;
+    std::vector<PrimeFieldElem> masks;
+};
+inline ScanResult scan_serialized_mixed(bpp_verifier* engine, const std::vector<uint8_t>& proofs,
+                                        const std::vector<uint8_t>& commitments, const std::vector<uint32_t>& ms,
+                                        const std::array<uint8_t, 32>& blind_key, uint64_t index_base = 0,
+                                        const std::vector<uint64_t>& index = {}, const std::vector<uint64_t>& amounts = {},
+                                        bool amount64 = false, bool uncompressed = false) {
+    if (!index.empty() && index.size() != ms.size()) throw std::logic_error("scan_serialized_mixed: one index per proof");
+    if (!amounts.empty() && amounts.size() != ms.size()) throw std::logic_error("scan_serialized_mixed: one amount per proof");
+    ScanResult r;
+    r.status.assign(ms.size() + 1, 0);
+    std::vector<uint64_t> out(ms.size() * 4 + 1);
+    const int flags = BPP_SER_TRANSCRIPT | (uncompressed ? BPP_SER_UNCOMPRESSED : 0) | (amount64 ? BPP_PROVE_AMOUNT64 : 0);
+    if (bpp_range_scan_serialized_mixed(engine, proofs.data(), commitments.data(), ms.data(), ms.size(), flags, blind_key.data(),
+                                        index_base, index.empty() ? nullptr : index.data(), nullptr,
+                                        amounts.empty() ? nullptr : amounts.data(), out.data(), r.status.data()) != BPP_OK)
+        throw std::runtime_error(std::string("bpp_range_scan_serialized_mixed: ") + bpp_last_error());
+    r.status.resize(ms.size());
+    r.masks.resize(ms.size());
+    for (size_t i = 0; i < ms.size(); i++)
+        for (int t = 0; t < 4; t++) r.masks[i].e[t] = out[i * 4 + t];
+    return r;
+}
+
 // Verifier-side holder of the commitments.  It exists only in the reference's (stale) README
 // (README.md:47-55: RangeVerifier::new(), allocate(&prover.commitment_vec), proof.verify(.., &verifier));
 // the reference's code takes the commitment slice directly (range/mod.rs:57-62).  Both forms are offered.

@@ -1,0 +1,201 @@
+#!/usr/bin/env python3
+"""What a scan costs beside a verification of the same block.  One process, BLS12-381, a (64, 16) engine; every
+GPU step runs under an alarm of its own (a SLOW step ends the run there, with what was measured so far written out).  The
+alarm is raised only when the interpreter has control again, so run the whole tool under `timeout -k 10 <seconds>` as well.
+
+  scan     bpp_range_scan_serialized_mixed_device and bpp_range_verify_batch_serialized_mixed_device on the same block of
+           containers, alternated repetition by repetition: medians, ranges, the ratio scan / verify.  Two blocks, both made
+           by the device prover under the transcript with a blind key: `mixed`, the 8 192-proof block of DESIGN 4f (4 096 x
+           m = 1, 2 048 x 2, 1 024 x 4, 512 x 8, 512 x 16, shuffled), and `wallet`, 2^16 containers with m = 1 and a
+           candidate amount each.
+  recover  bpp_range_recover_masks_mixed_device alone (triples and challenge blocks resident) at 2^12 and 2^16 single-output
+           proofs: masks per second.
+usage: timeout -k 10 1100 python tools/recover_bench.py [--reps 20] [--warmup 3] [--window 13] [--scale 1.0] [--legs sr]
+       [--blocks mixed,wallet] [--out profiles/recover_bench.json]"""
+import argparse
+import json
+import os
+import signal
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+for p in (ROOT, os.path.join(ROOT, "oracle")):
+    sys.path.insert(0, p)
+
+N, CAP = 64, 16
+KEY = bytes(range(1, 33))
+BASE = 1 << 40
+
+
+class StepTimeout(Exception):
+    pass
+
+
+def step(seconds, fn):
+    """fn() under an alarm of its own"""
+    def on_alarm(signum, frame):
+        raise StepTimeout()
+    old = signal.signal(signal.SIGALRM, on_alarm)
+    signal.alarm(int(seconds))
+    try:
+        return fn()
+    finally:
+        signal.alarm(0)
+        signal.signal(signal.SIGALRM, old)
+
+
+def stats(ms):
+    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms),
+            "stdev_ms": statistics.stdev(ms) if len(ms) > 1 else 0.0, "reps": len(ms)}
+
+
+def alternate(torch, fns, reps, warmup):
+    for _ in range(warmup):
+        for f in fns:
+            f()
+    torch.cuda.synchronize()
+    out = [[] for _ in fns]
+    for _ in range(reps):
+        for i, f in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            e1.synchronize()
+            out[i].append(e0.elapsed_time(e1))
+    return out
+
+
+def block_shapes(name, scale):
+    rng = np.random.default_rng(7)
+    if name == "mixed":
+        counts = {1: 4096, 2: 2048, 4: 1024, 8: 512, 16: 512}
+        ms = np.concatenate([np.full(max(1, int(c * scale)), m) for m, c in counts.items()])
+        return ms[rng.permutation(len(ms))].astype(np.uint32)
+    return np.ones(max(1, int((1 << 16) * scale)), dtype=np.uint32)
+
+
+def make_block(torch, B, a, bv, ms):
+    """the block as containers, by the device prover -> (d_proofs, d_commitments, d_amounts)"""
+    rng = np.random.default_rng(11)
+    nval = int(ms.sum())
+    vals = rng.integers(0, 1 << 31, size=nval, dtype=np.uint64)
+    gams = np.zeros((nval, 4), dtype=np.uint64)
+    gams[:, :3] = rng.integers(0, 1 << 62, size=(nval, 3), dtype=np.uint64)
+    dev = torch.device("cuda:0")
+    d_v = torch.from_numpy(vals.view(np.int64)).to(dev)
+    d_g = torch.from_numpy(gams.view(np.int64)).to(dev)
+    pb = B.compressed_bytes(a)
+    nbytes = sum(int((ms == m).sum()) * B.proof_bytes(a, N, int(m)) for m in np.unique(ms))
+    d_p = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    d_c = torch.zeros(nval * pb, dtype=torch.uint8, device=dev)
+    wsb = bv.prover_mixed_workspace_bytes(ms, serialized=True)
+    d_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    bv.prove_serialized_mixed_device(d_v.data_ptr(), d_g.data_ptr(), ms, d_p.data_ptr(), d_c.data_ptr(), d_ws.data_ptr(), wsb,
+                                     torch.cuda.current_stream().cuda_stream, transcript=True, blind_key=KEY, index_base=BASE)
+    torch.cuda.synchronize()
+    del d_ws
+    first = np.concatenate([[0], np.cumsum(ms)[:-1]]).astype(int)   # the candidate amount of a proof: its first value
+    d_a = torch.from_numpy(vals[first].view(np.int64)).to(dev)
+    return d_p, d_c, d_a
+
+
+def scan_leg(torch, B, a, bv, name, args, out):
+    ms = block_shapes(name, args.scale)
+    count = len(ms)
+    d_p, d_c, d_a = step(600, lambda: make_block(torch, B, a, bv, ms))
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    vsb, ssb = bv.serialized_mixed_workspace_bytes(ms), bv.recover_workspace_bytes(ms, serialized=True)
+    d_vws = torch.empty(vsb, dtype=torch.uint8, device=dev)
+    d_sws = torch.empty(ssb, dtype=torch.uint8, device=dev)
+    d_ok = torch.full((count,), 7, dtype=torch.int32, device=dev)
+    d_st = torch.full((count,), 7, dtype=torch.int32, device=dev)
+    d_m = torch.zeros((count, 4), dtype=torch.int64, device=dev)
+
+    def verify():
+        bv.verify_serialized_mixed_device(d_p.data_ptr(), d_c.data_ptr(), ms, d_ok.data_ptr(), d_vws.data_ptr(), vsb, st,
+                                          transcript=True)
+
+    def scan():
+        bv.scan_serialized_mixed_device(d_p.data_ptr(), d_c.data_ptr(), ms, d_m.data_ptr(), d_st.data_ptr(), d_sws.data_ptr(),
+                                        ssb, st, transcript=True, blind_key=KEY, index_base=BASE, d_amounts=d_a.data_ptr())
+
+    t_scan, t_ver = step(600, lambda: alternate(torch, [scan, verify], args.reps, args.warmup))
+    status = d_st.cpu().numpy()
+    want = np.where(ms == 1, 0, 3)
+    res = {"count": count, "classes": {int(m): int((ms == m).sum()) for m in np.unique(ms)}, "scan": stats(t_scan),
+           "verify": stats(t_ver), "ratio_scan_over_verify": statistics.median(t_scan) / statistics.median(t_ver),
+           "scans_per_s": count / (statistics.median(t_scan) * 1e-3), "verdicts_all_ok": bool((d_ok.cpu().numpy() == 0).all()),
+           "status_as_expected": bool((status == want).all()), "scan_workspace_bytes": ssb, "verify_workspace_bytes": vsb}
+    out["scan"][name] = res
+    print(name, json.dumps(res), flush=True)
+
+
+def recover_leg(torch, B, a, bv, log2n, args, out):
+    """the recover-only wire call: triples and challenges of 2^log2n single-output proofs, resident"""
+    count = max(1, int((1 << log2n) * args.scale))
+    ms = np.ones(count, dtype=np.uint32)
+    rng = np.random.default_rng(13)
+    dev = torch.device("cuda:0")
+    k = (N).bit_length() - 1
+    sc = np.zeros((count, 3, 4), dtype=np.uint64)
+    sc[:, :, :3] = rng.integers(0, 1 << 62, size=(count, 3, 3), dtype=np.uint64)
+    ch = np.zeros((count, 3 + k, 4), dtype=np.uint64)
+    ch[:, :, :3] = rng.integers(1, 1 << 62, size=(count, 3 + k, 3), dtype=np.uint64)
+    d_sc = torch.from_numpy(sc.view(np.int64)).to(dev)
+    d_ch = torch.from_numpy(ch.view(np.int64)).to(dev)
+    d_m = torch.zeros((count, 4), dtype=torch.int64, device=dev)
+    wsb = bv.recover_workspace_bytes(ms)
+    d_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    st = torch.cuda.current_stream().cuda_stream
+
+    def run():
+        bv.recover_masks_device(d_sc.data_ptr(), ms, d_m.data_ptr(), d_ws.data_ptr(), wsb, st, d_challenges=d_ch.data_ptr(),
+                                blind_key=KEY, index_base=BASE)
+
+    (t,) = step(300, lambda: alternate(torch, [run], args.reps, args.warmup))
+    res = dict(stats(t), count=count, masks_per_s=count / (statistics.median(t) * 1e-3))
+    out["recover"]["2^%d" % log2n] = res
+    print("recover 2^%d" % log2n, json.dumps(res), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--window", type=int, default=13)
+    ap.add_argument("--scale", type=float, default=1.0)
+    ap.add_argument("--legs", default="sr")
+    ap.add_argument("--blocks", default="mixed,wallet")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "recover_bench.json"))
+    args = ap.parse_args()
+    import torch
+    import bulletproofsplus_amd as B
+    a = B.Arith("bls12_381")
+    bv = step(300, lambda: B.BatchVerifier(B.PublicKey.new(a, N * CAP), N, CAP, window_bits=args.window))
+    out = {"curve": "bls12_381", "n": N, "capacity_m": CAP, "window_bits": args.window, "reps": args.reps, "warmup": args.warmup,
+           "scale": args.scale, "device": torch.cuda.get_device_name(0), "scan": {}, "recover": {}, "complete": False}
+    try:
+        if "s" in args.legs:
+            for name in args.blocks.split(","):
+                scan_leg(torch, B, a, bv, name, args, out)
+        if "r" in args.legs:
+            for log2n in (12, 16):
+                recover_leg(torch, B, a, bv, log2n, args, out)
+        out["complete"] = True
+    except StepTimeout:
+        out["stopped"] = "a step ran into its time limit"
+    finally:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1, sort_keys=True)
+            f.write("\n")
+    print(json.dumps({"complete": out["complete"], "out": args.out}))
+
+
+if __name__ == "__main__":
+    main()
