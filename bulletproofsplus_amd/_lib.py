@@ -228,6 +228,10 @@ def lib():
         L.bpp_debug_field_raw_op.argtypes = [vp, i32, i32, vp, vp, vp, vp, sz, vp]
         L.bpp_debug_madd_lazy_raw.argtypes = [vp, vp, vp, vp, sz, vp]
         L.bpp_debug_glv_op.argtypes = [vp, i32, i32, vp, sz, vp, vp]
+        # ... and the verifier's back end on chosen MulVec scalars (device buffers, as bpp_verifier_run takes them)
+        L.bpp_debug_verifier_mulvec_workspace_bytes.argtypes = [vp, sz, ctypes.c_uint32]
+        L.bpp_debug_verifier_mulvec_workspace_bytes.restype = sz
+        L.bpp_debug_verifier_mulvec.argtypes = [vp, ctypes.c_uint32, vp, vp, sz, vp, vp, sz, vp, vp, vp]
         _lib = L
     return _lib
 

@@ -45,6 +45,7 @@ struct bpp_verifier {
     std::vector<hipEvent_t> events;  // BPP_PROFILE_SLOTS x BPP_NUM_STAGES x 2
     size_t passes_recorded = 0;
     unsigned last_blocks_per_proof = 0;
+    unsigned last_horner_form = 0;   // of the last run_stage, as k_fixed_msm took it: 0, 1, 2, or 3 (the lone form of 1)
     // side stream of the lone-batch path (run(): the proof-point tables are built beside the verifier scalars), created
     // on first use
     hipStream_t aux = nullptr;
@@ -942,6 +943,7 @@ int VerifyImpl<C>::run_stage(bpp_verifier* v, const VerifyShape& s, const uint64
     // partials (mode 3 of k_fixed_msm) and the points of a proof are dealt to VAR_GROUPS lanes per window
     const bool lone = tree == 1 && count * bpp_ <= 1024;
     const uint32_t vgroups = lone ? VAR_GROUPS : 1u;
+    v->last_horner_form = lone ? 3u : tree;
     const size_t vlanes = count * (tree == 1 ? var_wsums<C>() * vgroups : var_windows<C>());
     HIPCHK(mark(ev, 2 * BPP_STAGE_VAR_MSM, st));
     hipLaunchKernelGGL(k_var_digits<C>, dim3(cdiv(npts, 256)), dim3(256), 0, st, s, w_sc, w_vd, npts, 0u);

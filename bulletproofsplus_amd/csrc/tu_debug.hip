@@ -2,11 +2,13 @@
 // (field_raw_ops.hpp), the lazy mixed addition on a raw accumulator, and the scalar splits / digit recoding as the
 // device compiles them.  A translation unit of its own: none of this is compiled into the units of the hot kernels.
 // Like bpp_debug_field_op / bpp_debug_point_op (capi.hip) the entries are not part of include/bpp_amd.h.
-// Every pointer is a host pointer.
+// Every pointer is a host pointer -- except in bpp_debug_verifier_mulvec, the verifier's back end (VerifyImpl::run_stage) on
+// MulVec scalars the test chooses, which takes device buffers as bpp_verifier_run does and adds no kernel.
 #include "host_util.hpp"
 
 #include "field_raw_ops.hpp"
 #include "fixed_glv.hpp"
+#include "impl_verify.hpp"   // declarations only (no BPP_IMPL_DEFINITIONS): the kernels live in tu_verify_*.hip
 
 namespace bpp {
 
@@ -212,5 +214,69 @@ extern "C" int bpp_debug_glv_op(bpp_ctx* ctx, int op, int window_bits, const uin
             if (n) HIPCHK(hipMemcpy(out, dout.p, n * out_words * 4, hipMemcpyDeviceToHost));
             return BPP_OK;
         }
+    });
+}
+
+// m_view -> the class whose shape VerifyImpl::class_shape returns (beyond every view: the verifier's own shape)
+static bool debug_view_shape(const bpp_verifier* v, uint32_t m_view, uint32_t& cls) {
+    if (m_view == 0) {
+        cls = (uint32_t)MIXED_CLASSES;
+        return true;
+    }
+    if ((m_view & (m_view - 1)) || m_view >= v->s.m) return false;
+    for (cls = 0; (1u << cls) < m_view; cls++) {}
+    return true;
+}
+
+// The verifier's back end -- everything of a pass behind the scalar stage: k_var_digits, k_var_tables, k_var_windows,
+// k_fixed_msm with its Horner stage, the folds, k_finalize(_tree) -- on MulVec scalars the caller chooses.
+//   m_view: 0 = the verifier's own shape; a power of two below m = the prefix view (n, m_view) of its tables, as the
+//     passes of a mixed batch use it.  N and NV below are that shape's.
+//   d_points [count][NV][PW] wire records as bpp_verifier_run takes them; d_scalars [count][N][4]: the MulVec's scalars,
+//     canonical (< r), in MulVec order (head, g, h, L.., R.., G.., H.., V..); d_ok, d_workspace, d_out_result [count][PW]
+//     (may be null), stream: as bpp_verifier_run's.  All device buffers.
+//   out_geometry (host, may be null): [Horner form as launched: 0, 1, 2, or 3 = lone; blocks per proof]
+extern "C" size_t bpp_debug_verifier_mulvec_workspace_bytes(const bpp_verifier* v, size_t count, uint32_t m_view) {
+    uint32_t cls = 0;
+    if (!v || count > 0x7fffffffu / 64 || !debug_view_shape(v, m_view, cls)) return 0;
+    size_t r = 0;
+    (void)guarded([&] {
+        return dispatch(v->ctx.curve, [&](auto cv) -> int {
+            using V = VerifyImpl<decltype(cv)>;
+            r = V::ws_layout(V::class_shape(v, cls).s, count).total;
+            return 0;
+        });
+    });
+    return r;
+}
+extern "C" int bpp_debug_verifier_mulvec(bpp_verifier* v, uint32_t m_view, const uint64_t* d_points, const uint64_t* d_scalars,
+                                         size_t count, uint32_t* d_ok, void* d_workspace, size_t workspace_bytes,
+                                         uint64_t* d_out_result, uint32_t* out_geometry, void* stream) {
+    if (!v || !d_points || !d_scalars || !d_ok || !d_workspace) return fail(BPP_E_ARG, "null argument");
+    if (count == 0) return BPP_OK;
+    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");   // before the handle is read
+    uint32_t cls = 0;
+    if (!debug_view_shape(v, m_view, cls)) return fail(BPP_E_ARG, "m_view must be 0 or a power of two below m");
+    return guarded(Count{count, "count"}, [&]() -> int {
+        HIPCHK(hipSetDevice(v->ctx.device));
+        return dispatch(v->ctx.curve, [&](auto cv) -> int {
+            using V = VerifyImpl<decltype(cv)>;
+            const VerifyShape s = V::class_shape(v, cls).s;
+            if (workspace_bytes < V::ws_layout(s, count).total) return fail(BPP_E_ARG, "workspace too small");
+            const size_t sc_bytes = count * (size_t)s.N * 32;
+            const int rc = V::run_stage(
+                v, s, d_points, count,
+                [&](uint32_t* w_sc, uint32_t*, uint32_t*, hipStream_t st) -> int {
+                    HIPCHK(hipMemcpyAsync(w_sc, d_scalars, sc_bytes, hipMemcpyDeviceToDevice, st));
+                    return BPP_OK;
+                },
+                d_ok, d_workspace, workspace_bytes, nullptr, d_out_result, static_cast<hipStream_t>(stream));
+            if (rc == BPP_OK && out_geometry) {
+                out_geometry[0] = v->last_horner_form;
+                out_geometry[1] = v->last_blocks_per_proof;
+            }
+            return rc;
+        });
     });
 }
