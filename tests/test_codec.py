@@ -3,7 +3,12 @@
 PARITY UNPINNED by the reference -- it has no serialization at all (only the commented-out size() functions,
 range/mod.rs:512-517 and wip.rs:384-397).  What pins the format: the public standard encodings of the two
 generators (ZCash / IETF BLS12-381 G1, SEC1 secp256k1), checked against the big-integer restatement in
-oracle/pyref.py on the CPU; the device kernels are then checked against that restatement."""
+oracle/pyref.py on the CPU; the device kernels are then checked against that restatement.
+
+Random points and a few malformed strings live here.  The edges -- x at the modulus and at the limb and word boundaries,
+every flag value, y at the boundary of the BLS12-381 sign comparison, the launch geometry and guard words of the device
+entry -- are the corpora of tests/codec_cases.py, checked in tests/test_codec_cases_cpu.py and
+tests/test_gpu_codec_cases.py."""
 
 import numpy as np
 import pytest

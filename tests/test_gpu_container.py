@@ -1,6 +1,10 @@
 """-m gpu: serialized proofs (the container), ristretto255 and the G1 subgroup check on the device against their
 restatements in oracle/pyref.py.  No reference counterpart (no serialization, no Ristretto in the reference): parity
-unpinned; pinned by the standard generator encodings and the restatements."""
+unpinned; pinned by the standard generator encodings and the restatements.
+
+The codec and hashed-generator tests here are spot checks (a handful of points, one label).  Branch-by-branch coverage of
+rist_decode / rist_encode, of the rejections and of k_hash_to_group (two blocks, counters past 0, padding boundaries, the
+prefix property) is in tests/test_gpu_codec_cases.py over the corpora of tests/codec_cases.py."""
 
 import hashlib
 
