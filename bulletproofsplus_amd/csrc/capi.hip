@@ -6,6 +6,7 @@
 #include "container_scan.hpp"
 #include "impl_msm.hpp"
 #include "impl_prove.hpp"
+#include "impl_prove_batch.hpp"
 #include "impl_verify.hpp"
 #include "impl_wip.hpp"
 #include "recover.hpp"
@@ -373,7 +374,7 @@ extern "C" int bpp_range_prove(bpp_ctx* ctx, const uint64_t* gh, const uint64_t*
             // untruncated ones a caller with an amount of 2^31 or more has to bring (BPP_PROVE_AMOUNT64): in literal mode the
             // proof is a function of (v, gamma, V), so whichever form matches the caller's V is the fold-based path's output
             for (int amount64 = 0; amount64 < 2; amount64++) {
-                const int rc = VerifyImpl<decltype(cv)>::prove_batch(hit->v.get(), v, gamma, 1, pts.data(), sc.data(), myV.data(),
+                const int rc = ProveBatchImpl<decltype(cv)>::prove_batch(hit->v.get(), v, gamma, 1, pts.data(), sc.data(), myV.data(),
                                                                      false, nullptr, 0, amount64 != 0);
                 if (rc == BPP_OK && std::memcmp(myV.data(), V, m * pw * 8) == 0) {
                     std::memcpy(out_points, pts.data(), pts.size() * 8);
@@ -487,7 +488,7 @@ extern "C" int bpp_range_prove_batch(bpp_verifier* engine, const uint64_t* v, co
     if (!engine || !v || !gamma || !out_points || !out_scalars) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
     return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::prove_batch(engine, v, gamma, count, out_points, out_scalars, out_V, false);
+        return ProveBatchImpl<decltype(cv)>::prove_batch(engine, v, gamma, count, out_points, out_scalars, out_V, false);
     });
 }
 
@@ -497,13 +498,13 @@ extern "C" int bpp_range_prove_batch_fs(bpp_verifier* engine, const uint64_t* v,
     if (!engine || !v || !gamma || !out_points || !out_scalars) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
     return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::prove_batch(engine, v, gamma, count, out_points, out_scalars, out_V, true, blind_key,
+        return ProveBatchImpl<decltype(cv)>::prove_batch(engine, v, gamma, count, out_points, out_scalars, out_V, true, blind_key,
                                                      index_base);
     });
 }
 
 extern "C" size_t bpp_prover_workspace_bytes(const bpp_verifier* engine, size_t count) {
-    return size_for(engine, [&](auto cv) { return VerifyImpl<decltype(cv)>::prove_layout(engine->s, count).total; });
+    return size_for(engine, [&](auto cv) { return ProveBatchImpl<decltype(cv)>::prove_layout(engine->s, count).total; });
 }
 
 extern "C" int bpp_range_prove_batch_device(bpp_verifier* engine, const uint64_t* d_v, const uint64_t* d_gamma,
@@ -513,7 +514,7 @@ extern "C" int bpp_range_prove_batch_device(bpp_verifier* engine, const uint64_t
         return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
     return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::prove_batch_device(engine, d_v, d_gamma, count, d_out_points, d_out_scalars,
+        return ProveBatchImpl<decltype(cv)>::prove_batch_device(engine, d_v, d_gamma, count, d_out_points, d_out_scalars,
                                                             d_out_V, false, nullptr, d_workspace, workspace_bytes,
                                                             static_cast<hipStream_t>(stream));
     });
@@ -528,7 +529,7 @@ extern "C" int bpp_range_prove_batch_fs_device(bpp_verifier* engine, const uint6
         return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
     return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::prove_batch_device(engine, d_v, d_gamma, count, d_out_points, d_out_scalars,
+        return ProveBatchImpl<decltype(cv)>::prove_batch_device(engine, d_v, d_gamma, count, d_out_points, d_out_scalars,
                                                             d_out_V, true, d_out_challenges, d_workspace, workspace_bytes,
                                                             static_cast<hipStream_t>(stream), blind_key, index_base,
                                                             d_blinding);
@@ -1196,10 +1197,10 @@ extern "C" int bpp_range_verify_batch_serialized_grouped_mixed_device(bpp_verifi
     });
 }
 
-// ---- proving blocks of mixed aggregation sizes (impl_verify.hpp prove_mixed / prove_serialized_mixed) -----------------
+// ---- proving blocks of mixed aggregation sizes (impl_prove_batch.hpp prove_mixed / prove_serialized_mixed) -----------
 extern "C" size_t bpp_prover_mixed_workspace_bytes(const bpp_verifier* engine, const uint32_t* m_of, size_t count) {
     if ((count && !m_of) || count > 0x7fffffffu / 64) return 0;
-    return size_for(engine, [&](auto cv) { return VerifyImpl<decltype(cv)>::prove_mixed_workspace_bytes(engine, m_of, count); });
+    return size_for(engine, [&](auto cv) { return ProveBatchImpl<decltype(cv)>::prove_mixed_workspace_bytes(engine, m_of, count); });
 }
 
 extern "C" int bpp_range_prove_batch_mixed_device(bpp_verifier* engine, const uint64_t* d_v, const uint64_t* d_gamma,
@@ -1215,7 +1216,7 @@ extern "C" int bpp_range_prove_batch_mixed_device(bpp_verifier* engine, const ui
     if ((blind_key || d_blinding) && !(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
     if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
     return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::prove_mixed(engine, d_v, d_gamma, m_of, count, (flags & BPP_SER_TRANSCRIPT) != 0, blind_key,
+        return ProveBatchImpl<decltype(cv)>::prove_mixed(engine, d_v, d_gamma, m_of, count, (flags & BPP_SER_TRANSCRIPT) != 0, blind_key,
                                                      index_base, d_blinding, d_out_points, d_out_scalars, d_out_challenges,
                                                      d_workspace, workspace_bytes, static_cast<hipStream_t>(stream),
                                                      (flags & BPP_PROVE_AMOUNT64) != 0);
@@ -1224,7 +1225,7 @@ extern "C" int bpp_range_prove_batch_mixed_device(bpp_verifier* engine, const ui
 
 extern "C" size_t bpp_prover_serialized_mixed_workspace_bytes(const bpp_verifier* engine, const uint32_t* m_of, size_t count) {
     if ((count && !m_of) || count > 0x7fffffffu / 64) return 0;
-    return size_for(engine, [&](auto cv) { return VerifyImpl<decltype(cv)>::prove_ser_mixed_workspace_bytes(engine, m_of, count); });
+    return size_for(engine, [&](auto cv) { return ProveBatchImpl<decltype(cv)>::prove_ser_mixed_workspace_bytes(engine, m_of, count); });
 }
 
 extern "C" int bpp_range_prove_batch_serialized_mixed_device(bpp_verifier* engine, const uint64_t* d_v, const uint64_t* d_gamma,
@@ -1242,38 +1243,14 @@ extern "C" int bpp_range_prove_batch_serialized_mixed_device(bpp_verifier* engin
     if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
     const uint32_t version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
     return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::prove_serialized_mixed(
+        return ProveBatchImpl<decltype(cv)>::prove_serialized_mixed(
             engine, d_v, d_gamma, m_of, count, (flags & BPP_SER_TRANSCRIPT) != 0, blind_key, index_base, d_blinding,
             static_cast<uint8_t*>(d_out_proofs), static_cast<uint8_t*>(d_out_commitments), d_workspace, workspace_bytes,
             static_cast<hipStream_t>(stream), version, (flags & BPP_PROVE_AMOUNT64) != 0);
     });
 }
 
-namespace {
-// The host-pointer mixed prove calls: values and gammas of a block copied to the device, a workspace of wsb bytes and two
-// outputs of bytes0 / bytes1 allocated, run(d_v, d_gamma, d_out0, d_out1, d_ws), then the outputs copied to the host.
-template <class F>
-int prove_mixed_staged(const bpp_verifier* engine, const uint64_t* v, const uint64_t* gamma, const uint32_t* m_of, size_t count,
-                       size_t wsb, void* out0, size_t bytes0, void* out1, size_t bytes1, F&& run) {
-    size_t nval = 0;
-    for (size_t i = 0; i < count; i++) nval += m_of[i];
-    DevBuf dv, dg, d0, d1, dws;
-    HIPCHK(dv.alloc(nval * 8));
-    HIPCHK(hipMemcpy(dv.p, v, nval * 8, hipMemcpyHostToDevice));
-    int rc = dispatch(engine->ctx.curve, [&](auto cv) -> int { return upload_scalars<decltype(cv)>(gamma, nval, dg, nullptr); });
-    if (rc) return rc;
-    HIPCHK(d0.alloc(bytes0));
-    HIPCHK(d1.alloc(bytes1));
-    HIPCHK(dws.alloc(wsb));
-    rc = run(static_cast<const uint64_t*>(dv.p), static_cast<const uint64_t*>(dg.p), d0.p, d1.p, dws.p);
-    if (rc) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out0, d0.p, bytes0, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out1, d1.p, bytes1, hipMemcpyDeviceToHost));
-    return BPP_OK;
-}
-}  // namespace
-
+// host buffers in, host buffers out: the device paths above between copies
 extern "C" int bpp_range_prove_batch_mixed(bpp_verifier* engine, const uint64_t* v, const uint64_t* gamma, const uint32_t* m_of,
                                            size_t count, int flags, const uint8_t* blind_key, uint64_t index_base,
                                            uint64_t* out_points, uint64_t* out_scalars, uint64_t* out_challenges) {
@@ -1281,33 +1258,9 @@ extern "C" int bpp_range_prove_batch_mixed(bpp_verifier* engine, const uint64_t*
     if (flags & ~(BPP_SER_TRANSCRIPT | BPP_PROVE_AMOUNT64)) return fail(BPP_E_ARG, "unknown flag");
     if (count == 0) return BPP_OK;
     if (!v || !gamma || !m_of || !out_points || !out_scalars) return fail(BPP_E_ARG, "null argument");
-    return on_device(engine->ctx.device, {count, "count"}, [&]() -> int {
-        const size_t wsb = bpp_prover_mixed_workspace_bytes(engine, m_of, count);
-        if (!wsb) {   // an m_i the engine does not take: the plan names the proof
-            MixedPlan p;
-            const int rc = mixed_plan(engine->s, m_of, count, false, p);
-            return rc ? rc : fail(BPP_E_ARG, "mixed block rejected");
-        }
-        const size_t pw = (size_t)bpp_point_words(engine->ctx.curve) * 8;
-        size_t npts = 0, nch = 0;
-        const uint32_t logn = engine->s.k - (uint32_t)__builtin_ctz(engine->s.m);
-        for (size_t i = 0; i < count; i++) {
-            const uint32_t k = logn + (uint32_t)__builtin_ctz(m_of[i]);
-            npts += 3 + 2 * k + m_of[i];
-            nch += 3 + k;
-        }
-        DevBuf dch;
-        if (out_challenges) HIPCHK(dch.alloc(nch * 32));
-        const int rc = prove_mixed_staged(engine, v, gamma, m_of, count, wsb, out_points, npts * pw, out_scalars, count * 96,
-                                          [&](const uint64_t* dv, const uint64_t* dg, void* d0, void* d1, void* dws) {
-                                              return bpp_range_prove_batch_mixed_device(
-                                                  engine, dv, dg, m_of, count, flags, blind_key, index_base, nullptr,
-                                                  static_cast<uint64_t*>(d0), static_cast<uint64_t*>(d1),
-                                                  static_cast<uint64_t*>(dch.p), dws, wsb, nullptr);
-                                          });
-        if (rc) return rc;
-        if (out_challenges) HIPCHK(hipMemcpy(out_challenges, dch.p, nch * 32, hipMemcpyDeviceToHost));
-        return BPP_OK;
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
+        return ProveBatchImpl<decltype(cv)>::prove_mixed_host(engine, v, gamma, m_of, count, flags, blind_key, index_base,
+                                                              out_points, out_scalars, out_challenges);
     });
 }
 
@@ -1318,27 +1271,11 @@ extern "C" int bpp_range_prove_batch_serialized_mixed(bpp_verifier* engine, cons
     if (flags & ~(BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED | BPP_PROVE_AMOUNT64)) return fail(BPP_E_ARG, "unknown flag");
     if (count == 0) return BPP_OK;
     if (!v || !gamma || !m_of || !out_proofs || !out_commitments) return fail(BPP_E_ARG, "null argument");
-    const int version = (flags & BPP_SER_UNCOMPRESSED) ? 2 : 1;
-    const size_t cb = container_point_size(engine->ctx.curve, version);
+    const size_t cb = container_point_size(engine->ctx.curve, (flags & BPP_SER_UNCOMPRESSED) ? 2 : 1);
     if (int rc = container_version_ok(cb)) return rc;
-    return on_device(engine->ctx.device, {count, "count"}, [&]() -> int {
-        const size_t wsb = bpp_prover_serialized_mixed_workspace_bytes(engine, m_of, count);
-        if (!wsb) {   // an m_i the engine does not take: the plan names the proof
-            MixedPlan p;
-            const int rc = mixed_plan_serialized(engine->s, m_of, count, cb, false, p);
-            return rc ? rc : fail(BPP_E_ARG, "serialized mixed block rejected");
-        }
-        size_t pbytes = 0, cbytes = 0;
-        for (size_t i = 0; i < count; i++) {
-            pbytes += bpp_proof_bytes_version(engine->ctx.curve, engine->s.n, m_of[i], version);
-            cbytes += m_of[i] * cb;
-        }
-        return prove_mixed_staged(engine, v, gamma, m_of, count, wsb, out_proofs, pbytes, out_commitments, cbytes,
-                                  [&](const uint64_t* dv, const uint64_t* dg, void* d0, void* d1, void* dws) {
-                                      return bpp_range_prove_batch_serialized_mixed_device(engine, dv, dg, m_of, count, flags,
-                                                                                           blind_key, index_base, nullptr, d0, d1,
-                                                                                           dws, wsb, nullptr);
-                                  });
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
+        return ProveBatchImpl<decltype(cv)>::prove_serialized_mixed_host(engine, v, gamma, m_of, count, flags, blind_key,
+                                                                         index_base, out_proofs, out_commitments);
     });
 }
 

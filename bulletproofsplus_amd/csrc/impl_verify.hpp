@@ -1,5 +1,7 @@
 // impl_verify.hpp -- the batch verifier (bpp_verifier_*): window tables in HBM + one pass of the hot path
-// over a device-resident batch.  One instantiation per curve (tu_verify_*.hip).
+// over a device-resident batch, in its exact, mixed, serialized, combined and grouped forms.  One instantiation per curve
+// (tu_verify_*.hip).  The engine's prover lives in impl_prove_batch.hpp and calls own, class_shape, class_run_max and the
+// container checks of this struct.
 #pragma once
 #include <functional>
 #include <memory>
@@ -11,7 +13,6 @@
 #include "host_util.hpp"
 #include "mixed.hpp"
 #include "pippenger.hpp"
-#include "prover_batch.hpp"
 
 // stages of one pass, in launch order (bpp_verifier_profile reports one duration per stage)
 enum { BPP_STAGE_FROM_WIRE = 0, BPP_STAGE_SCALARS, BPP_STAGE_FIXED_MSM, BPP_STAGE_VAR_MSM, BPP_STAGE_FINALIZE,
@@ -594,134 +595,6 @@ struct VerifyImpl {
     static int grouped_mixed_core(bpp_verifier* v, const MixedPlan& p, size_t count, uint32_t group, bool with_challenges,
                                   bool with_status, uint64_t* h_stats, uint8_t* ws, const GroupMixedLayout& L,
                                   size_t workspace_bytes, hipStream_t st);
-
-    // ---- batched prover (prover_batch.hpp) -------------------------------------------------------------
-    // Device-resident form: values, gammas, outputs and workspace are device buffers, nothing touches the host
-    // and nothing synchronises.  The batch is processed in chunks that reuse one workspace.
-    struct ProveLayout {
-        size_t a, b, cG, cH, pwy, con, vps, part, part1, part2, vout, trst, ch, blind, vals, gams, total;
-        size_t chunk;
-        unsigned per;
-    };
-    static size_t prove_chunk(const VerifyShape& s, size_t count) {
-        const uint32_t nvp = pb_num_vps(s.k, s.m);
-        const size_t chunk_max = std::max<size_t>(1, std::min<size_t>(2048, ((size_t)12 << 30) / ((size_t)nvp * s.N * 32)));
-        return std::min(chunk_max, std::max<size_t>(count, 1));
-    }
-    // mixed: one class of a mixed block -- a chunk's values and gammas are gathered out of the caller's packed buffers
-    static ProveLayout prove_layout(const VerifyShape& s, size_t count, bool mixed = false) {
-        ProveLayout w;
-        const uint32_t nvp = pb_num_vps(s.k, s.m);
-        w.chunk = prove_chunk(s, count);
-        const size_t nv_total = w.chunk * nvp;
-        w.per = blocks_per_proof(s, nv_total);
-        const size_t vec = w.chunk * (size_t)s.mn * 32;
-        WsCarver o;
-        w.a = o.take(vec);
-        w.b = o.take(vec);
-        w.cG = o.take(vec);
-        w.cH = o.take(vec);
-        w.pwy = o.take(vec);
-        w.con = o.take(w.chunk * (size_t)pb_consts_elems(s.k) * 32);
-        w.vps = o.take(nv_total * (size_t)s.N * 32);
-        w.part = o.take(nv_total * w.per * FIXED_BLOCK * JW * 4);                                // one partial per thread
-        w.part1 = o.take(nv_total * w.per * (FIXED_BLOCK / FOLD_GROUP) * JW * 4);                // folded 8 to 1
-        w.part2 = o.take(nv_total * w.per * (FIXED_BLOCK / FOLD_GROUP / FOLD_GROUP2) * JW * 4);  // then 4 to 1
-        w.vout = o.take(w.chunk * (size_t)s.m * WW * 4);     // the commitments of a chunk when the caller does not want them
-        w.trst = o.take(w.chunk * 32);                        // transcript states (Fiat-Shamir mode)
-        w.ch = o.take(w.chunk * (size_t)(3 + s.k) * 32);    // ... and the challenge blocks when the caller does not want them
-        w.blind = o.take(w.chunk * (size_t)pb_blind_elems(s.k) * 32);   // blinding scalars expanded from the caller's key
-        w.vals = w.gams = 0;
-        if (mixed) {
-            w.vals = o.take(w.chunk * (size_t)s.m * 8);
-            w.gams = o.take(w.chunk * (size_t)s.m * 32);
-        }
-        w.total = o.total;
-        return w;
-    }
-    // d_values: count x m u64 ; d_gammas: count x m scalars ; d_out_points: count x (3 + 2k) wire points ;
-    // d_out_scalars: count x 3 scalars ; d_out_V: count x m wire points (may be null).
-    // fs = false: the reference's constant challenges, every MulVec of the batch in ONE k_fixed_msm launch.
-    // fs = true : challenges from the transcript (transcript.hpp): A and the commitments first, then y, z; each round's
-    //             L_t, R_t before e_t; wip.A, wip.B before e -- 3 + k smaller launches and the hashing steps between
-    //             them.  d_out_challenges (count x (3 + k) scalars, may be null) receives [y, z, e, e_1..e_k].
-    // Blinding (alpha, r, s, delta, eta, d_L[t], d_R[t] per proof): d_blinding (count x (5 + 2k) canonical scalars), or
-    // blind_key (32 bytes, host) expanded on the device with the global proof index index_base + p (k_pb_blind), or --
-    // both null -- the reference's literals (range/mod.rs:94,256; wip.rs:94-95,175-178), whose proofs hide nothing.
-    // ps: the shape proved -- the engine's own, or a prefix view (n, m') of its tables: the proofs of PublicKey::new(n m').
-    // px (one class of a mixed block, ps its view; prover_batch.hpp PX_*): `count` entries by gathered position.  The
-    // values, gammas, blinding scalars and challenge blocks are then the caller's PACKED buffers, read and written through
-    // the entries; each record, commitments behind it, goes to wire point PX_REC of d_out_points (d_out_V is not used);
-    // scalar triples and blinding indices follow PX_CALLER.
-    static int prove_batch_device(bpp_verifier* v, const PassShape& ps, const uint64_t* d_values, const uint64_t* d_gammas,
-                                  size_t count, uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_V, bool fs,
-                                  uint64_t* d_out_challenges, void* d_workspace, size_t workspace_bytes, hipStream_t st,
-                                  const uint8_t* blind_key = nullptr, uint64_t index_base = 0,
-                                  const uint64_t* d_blinding = nullptr, const uint32_t* px = nullptr, bool amount64 = false);
-    static int prove_batch_device(bpp_verifier* v, const uint64_t* d_values, const uint64_t* d_gammas, size_t count,
-                                  uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_V, bool fs,
-                                  uint64_t* d_out_challenges, void* d_workspace, size_t workspace_bytes, hipStream_t st,
-                                  const uint8_t* blind_key = nullptr, uint64_t index_base = 0,
-                                  const uint64_t* d_blinding = nullptr, bool amount64 = false) {
-        return prove_batch_device(v, own(v), d_values, d_gammas, count, d_out_points, d_out_scalars, d_out_V, fs,
-                                  d_out_challenges, d_workspace, workspace_bytes, st, blind_key, index_base, d_blinding, nullptr,
-                                  amount64);
-    }
-
-    // ---- ... of a block of MIXED aggregation sizes (mixed.hpp prove_plan): proof i has m_of[i] values ---------------
-    // workspace = the per-proof indices (PX_* | SX_*, by gathered position) | serialized form: the class regions of wire
-    // records and the scalar triples | one class's prove_layout (the classes run one after the other on st and share it)
-    struct ProveMixedLayout {
-        size_t idx, records, scalars, run, total;
-    };
-    static ProveMixedLayout prove_mixed_layout(const bpp_verifier* v, const MixedPlan& p, size_t count, bool serialized) {
-        ProveMixedLayout w;
-        WsCarver o;
-        w.idx = o.take(count * (size_t)(PX_WORDS + SX_WORDS) * 4);
-        w.records = o.take(serialized ? p.points * WW * 4 : 0);
-        w.scalars = o.take(serialized ? count * 96 : 0);
-        w.run = o.take(class_run_max(v, p, [](const VerifyShape& s, size_t n) { return prove_layout(s, n, true).total; }));
-        w.total = o.total;
-        return w;
-    }
-    // 0 for an m_of the engine does not take
-    static size_t prove_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
-        MixedPlan p;
-        if (prove_plan(v->s, m_of, count, 0, false, p)) return 0;
-        return prove_mixed_layout(v, p, count, false).total;
-    }
-    static size_t prove_ser_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
-        MixedPlan p;
-        if (!container_shape_ok(v) || prove_plan(v->s, m_of, count, max_point_bytes<C>(), false, p)) return 0;
-        return prove_mixed_layout(v, p, count, true).total;
-    }
-    // d_values: sum m_i u64, d_gammas: sum m_i scalars, d_blinding (may be null): 5 + 2 k_i scalars per proof, all packed
-    // in caller order; m_of: host.  d_out_points: record i [A, wip.A, wip.B, L.., R.., V_0..] at wire point
-    // sum_{j<i} (3 + 2 k_j + m_j) -- run_mixed's d_points; d_out_scalars: count x 3; d_out_challenges (may be null): the
-    // packed 3 + k_i blocks.  Proof i's blinding index is index_base + i.  Uploads the per-proof index (blocking the host
-    // until the copy has read it), the rest is enqueued on st.
-    static int prove_mixed(bpp_verifier* v, const uint64_t* d_values, const uint64_t* d_gammas, const uint32_t* m_of,
-                           size_t count, bool fs, const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_blinding,
-                           uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_challenges, void* d_workspace,
-                           size_t workspace_bytes, hipStream_t st, bool amount64 = false);
-    // ... as containers packed back to back in caller order (container i of container_bytes(k_i, version) bytes) and
-    // m_i encoded commitments per proof in a buffer of their own: run_serialized_mixed's input
-    static int prove_serialized_mixed(bpp_verifier* v, const uint64_t* d_values, const uint64_t* d_gammas, const uint32_t* m_of,
-                                      size_t count, bool fs, const uint8_t* blind_key, uint64_t index_base,
-                                      const uint64_t* d_blinding, uint8_t* d_out_proofs, uint8_t* d_out_commitments,
-                                      void* d_workspace, size_t workspace_bytes, hipStream_t st, uint32_t version,
-                                      bool amount64 = false);
-    // the shared body: plan p (with its indices) and layout L in hand, every class present proved with its view
-    static int prove_mixed_classes(bpp_verifier* v, const MixedPlan& p, const ProveMixedLayout& L, const uint64_t* d_values,
-                                   const uint64_t* d_gammas, bool fs, const uint8_t* blind_key, uint64_t index_base,
-                                   const uint64_t* d_blinding, uint64_t* d_out_points, uint64_t* d_out_scalars,
-                                   uint64_t* d_out_challenges, uint8_t* ws, size_t workspace_bytes, hipStream_t st,
-                                   bool amount64 = false);
-
-    // host buffers in, host buffers out
-    static int prove_batch(bpp_verifier* v, const uint64_t* values, const uint64_t* gammas, size_t count,
-                           uint64_t* out_points, uint64_t* out_scalars, uint64_t* out_V, bool fs,
-                           const uint8_t* blind_key = nullptr, uint64_t index_base = 0, bool amount64 = false);
 
     // d_partials: n partials as bpp_verifier_run_combined wrote them (jacobian + validity word each)
     static int sum_partials(const uint32_t* d_partials, size_t n, uint32_t* d_ok, hipStream_t st);
@@ -1446,208 +1319,6 @@ int VerifyImpl<C>::run_serialized_grouped_mixed(bpp_verifier* v, const uint8_t* 
     hipLaunchKernelGGL(k_mixed_status_scatter<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, W(L.f.idx), W(L.f.status), W(L.f.ok),
                        d_ok, count);
     HIPCHK(hipGetLastError());
-    return BPP_OK;
-}
-
-template <class C>
-int VerifyImpl<C>::prove_batch_device(bpp_verifier* v, const PassShape& ps, const uint64_t* d_values,
-                              const uint64_t* d_gammas, size_t count, uint64_t* d_out_points, uint64_t* d_out_scalars,
-                              uint64_t* d_out_V, bool fs, uint64_t* d_out_challenges, void* d_workspace,
-                              size_t workspace_bytes, hipStream_t st, const uint8_t* blind_key, uint64_t index_base,
-                              const uint64_t* d_blinding, const uint32_t* px, bool amount64) {
-    const VerifyShape& s = ps.s;
-    const uint32_t k = s.k, m = s.m;
-    const uint32_t nvp = pb_num_vps(k, m);
-    BlindKey bk;
-    load_key_words(blind_key, bk.w);
-    const ProveLayout L = prove_layout(s, count, px != nullptr);
-    if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
-    ProverConsts pc;
-    pc.alpha = m == 1 ? 7 : 33;   // range/mod.rs:94 / :256
-    pc.d_L = 4;                   // wip.rs:94
-    pc.d_R = 5;                   // wip.rs:95
-    pc.r = 33;                    // wip.rs:175
-    pc.s = 44;
-    pc.delta = 88;
-    pc.eta = 123;
-    pc.amount64 = amount64 ? 1u : 0u;   // the commitments' scalar on g: the u64, not `v as i32` (range/prover.rs:37)
-    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-    auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
-    for (size_t base = 0; base < count; base += L.chunk) {
-        const size_t cnt = std::min(L.chunk, count - base);
-        const uint32_t* cpx = px ? px + base * PX_WORDS : nullptr;   // this chunk's entries of a mixed block
-        uint32_t* o_pts = reinterpret_cast<uint32_t*>(d_out_points) + (px ? 0 : base * (size_t)(3 + 2 * k) * WW);
-        uint32_t* o_sc = reinterpret_cast<uint32_t*>(d_out_scalars) + (px ? 0 : base * 24);
-        uint32_t* o_V = d_out_V && !px ? reinterpret_cast<uint32_t*>(d_out_V) + base * (size_t)m * WW : W(L.vout);
-        const uint64_t* vals = d_values + base * m;
-        const uint32_t* gams = reinterpret_cast<const uint32_t*>(d_gammas) + base * (size_t)m * 8;
-        const uint32_t* blind = nullptr;   // this chunk's blinding scalars
-        if (px) {   // the chunk's inputs out of the caller's packed buffers
-            hipLaunchKernelGGL(k_pb_gather_mixed<C>, dim3((unsigned)cnt), dim3(64), 0, st, cpx, m, k, d_values, d_gammas,
-                               d_blinding, reinterpret_cast<uint64_t*>(ws + L.vals), reinterpret_cast<uint64_t*>(ws + L.gams),
-                               reinterpret_cast<uint64_t*>(ws + L.blind));
-            vals = reinterpret_cast<const uint64_t*>(ws + L.vals);
-            gams = W(L.gams);
-        }
-        if (d_blinding) {
-            blind = px ? W(L.blind) : reinterpret_cast<const uint32_t*>(d_blinding) + base * (size_t)pb_blind_elems(k) * 8;
-        } else if (blind_key) {
-            hipLaunchKernelGGL(k_pb_blind<C>, dim3(cdiv(cnt * pb_blind_elems(k), 64)), dim3(64), 0, st, bk,
-                               px ? index_base : index_base + base, k, W(L.blind), cnt, cpx);
-            blind = W(L.blind);
-        }
-        // one MulVec launch over `sel` of every proof's virtual proofs, then their wire points into the records
-        auto msm = [&](VpSel sel) {
-            const size_t nv = cnt * sel.cnt;
-            // never more blocks per virtual proof than the workspace was sized for
-            const unsigned per = std::min(L.per, blocks_per_proof(s, nv));
-            launch_fixed_msm<C, 2>((unsigned)(nv * per), st, s, W(L.vps), v->table.u32(), W(L.part), per, 0u,
-                                   (const uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)0, 0u, sel);
-            // per-thread partials -> 16 -> 4 per block with every lane busy (as the verifier does); k_pb_collect adds
-            // the 4 * per that are left of each MulVec
-            const size_t f1 = nv * per * (FIXED_BLOCK / FOLD_GROUP), f2 = f1 / FOLD_GROUP2;
-            hipLaunchKernelGGL(k_partials_fold<C>, dim3(cdiv(f1, 64)), dim3(64), 0, st, W(L.part), FOLD_GROUP, W(L.part1), f1);
-            hipLaunchKernelGGL(k_partials_fold<C>, dim3(cdiv(f2, 64)), dim3(64), 0, st, W(L.part1), FOLD_GROUP2, W(L.part2), f2);
-            hipLaunchKernelGGL(k_pb_collect<C>, dim3(cdiv(nv, 64)), dim3(64), 0, st, s, sel, W(L.part2),
-                               per * (FIXED_BLOCK / FOLD_GROUP / FOLD_GROUP2), o_pts, o_V, nv, cpx);
-        };
-        if (!fs) {
-            hipLaunchKernelGGL(k_pb_init<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, (uint32_t)PB_ALL, 0u, vals, gams,
-                               ps.challenges, 0u, W(L.a), W(L.b), W(L.cG), W(L.cH), W(L.pwy), W(L.con), W(L.vps));
-            for (uint32_t t = 0; t < k; t++)
-                hipLaunchKernelGGL(k_pb_round<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, t, (uint32_t)PB_ALL, W(L.a),
-                                   W(L.b), W(L.cG), W(L.cH), W(L.pwy), W(L.con), W(L.vps));
-            hipLaunchKernelGGL(k_pb_final<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, (uint32_t)PB_ALL, W(L.a), W(L.b),
-                               W(L.cG), W(L.cH), W(L.con), W(L.vps), o_sc, cpx);
-            msm(VpSel{nvp, 0u, nvp, 1u});
-            if (px && d_out_challenges)   // a mixed block: the class's literal challenges, one copy per proof
-                hipLaunchKernelGGL(k_pb_challenges_out<C>, dim3((unsigned)cnt), dim3(64), 0, st, cpx, k,
-                                   reinterpret_cast<const uint64_t*>(ps.challenges), 0u, d_out_challenges);
-            continue;
-        }
-        uint32_t* o_ch = d_out_challenges && !px ? reinterpret_cast<uint32_t*>(d_out_challenges) + base * (size_t)(3 + k) * 8
-                                                 : W(L.ch);
-        const uint32_t chs = (3 + k) * 8;
-        const unsigned lanes = cdiv(cnt, 64);
-        hipLaunchKernelGGL(k_pb_init<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, (uint32_t)PB_PRE, 1u, vals, gams, o_ch,
-                           chs, W(L.a), W(L.b), W(L.cG), W(L.cH), W(L.pwy), W(L.con), W(L.vps));
-        msm(VpSel{nvp, 0u, 1u, 1u});              // A
-        msm(VpSel{nvp, 2 * k + 3, m, 1u});        // V_0 .. V_{m-1}
-        hipLaunchKernelGGL(k_pb_fs_yz<C>, dim3(lanes), dim3(64), 0, st, s, ps.tr0, o_pts, o_V, W(L.trst), o_ch, cnt, cpx);
-        hipLaunchKernelGGL(k_pb_init<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, (uint32_t)PB_POST, 1u, vals, gams, o_ch,
-                           chs, W(L.a), W(L.b), W(L.cG), W(L.cH), W(L.pwy), W(L.con), W(L.vps));
-        for (uint32_t t = 0; t < k; t++) {
-            hipLaunchKernelGGL(k_pb_round<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, t, (uint32_t)PB_PRE, W(L.a), W(L.b),
-                               W(L.cG), W(L.cH), W(L.pwy), W(L.con), W(L.vps));
-            msm(VpSel{nvp, 1 + 2 * t, 2u, 1u});   // L_t, R_t
-            hipLaunchKernelGGL(k_pb_fs_round<C>, dim3(lanes), dim3(64), 0, st, s, t, o_pts, W(L.trst), o_ch, W(L.con), cnt, cpx);
-            hipLaunchKernelGGL(k_pb_round<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, t, (uint32_t)PB_POST, W(L.a),
-                               W(L.b), W(L.cG), W(L.cH), W(L.pwy), W(L.con), W(L.vps));
-        }
-        hipLaunchKernelGGL(k_pb_final<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, (uint32_t)PB_PRE, W(L.a), W(L.b),
-                           W(L.cG), W(L.cH), W(L.con), W(L.vps), o_sc, cpx);
-        msm(VpSel{nvp, 2 * k + 1, 2u, 1u});       // wip.A, wip.B
-        hipLaunchKernelGGL(k_pb_fs_final<C>, dim3(lanes), dim3(64), 0, st, s, o_pts, W(L.trst), o_ch, W(L.con), cnt, cpx);
-        hipLaunchKernelGGL(k_pb_final<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, (uint32_t)PB_POST, W(L.a), W(L.b),
-                           W(L.cG), W(L.cH), W(L.con), W(L.vps), o_sc, cpx);
-        if (px && d_out_challenges)   // the chunk's challenge blocks to their places in the caller's packed buffer
-            hipLaunchKernelGGL(k_pb_challenges_out<C>, dim3((unsigned)cnt), dim3(64), 0, st, cpx, k,
-                               reinterpret_cast<const uint64_t*>(o_ch), (3 + k) * 4, d_out_challenges);
-    }
-    HIPCHK(hipGetLastError());
-    return BPP_OK;
-}
-
-// Every class present, one after the other on st, with its view and its slice of the index; the classes share L.run.
-template <class C>
-int VerifyImpl<C>::prove_mixed_classes(bpp_verifier* v, const MixedPlan& p, const ProveMixedLayout& L, const uint64_t* d_values,
-                                       const uint64_t* d_gammas, bool fs, const uint8_t* blind_key, uint64_t index_base,
-                                       const uint64_t* d_blinding, uint64_t* d_out_points, uint64_t* d_out_scalars,
-                                       uint64_t* d_out_challenges, uint8_t* ws, size_t workspace_bytes, hipStream_t st,
-                                       bool amount64) {
-    const size_t count = p.px.size() / PX_WORDS;
-    uint32_t* w_idx = reinterpret_cast<uint32_t*>(ws + L.idx);
-    // pageable source: the copies have read it when the call returns
-    HIPCHK(hipMemcpyAsync(w_idx, p.px.data(), p.px.size() * 4, hipMemcpyHostToDevice, st));
-    if (!p.sidx.empty())
-        HIPCHK(hipMemcpyAsync(w_idx + count * PX_WORDS, p.sidx.data(), p.sidx.size() * 4, hipMemcpyHostToDevice, st));
-    for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
-        if (!p.count[c]) continue;
-        const int rc = prove_batch_device(v, class_shape(v, c), d_values, d_gammas, p.count[c], d_out_points, d_out_scalars,
-                                          nullptr, fs, d_out_challenges, ws + L.run, workspace_bytes - L.run, st, blind_key,
-                                          index_base, d_blinding, w_idx + p.first[c] * PX_WORDS, amount64);
-        if (rc) return rc;
-    }
-    return BPP_OK;
-}
-
-template <class C>
-int VerifyImpl<C>::prove_mixed(bpp_verifier* v, const uint64_t* d_values, const uint64_t* d_gammas, const uint32_t* m_of,
-                               size_t count, bool fs, const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_blinding,
-                               uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_challenges, void* d_workspace,
-                               size_t workspace_bytes, hipStream_t st, bool amount64) {
-    MixedPlan p;
-    int rc = prove_plan(v->s, m_of, count, 0, true, p);
-    if (rc) return rc;
-    const ProveMixedLayout L = prove_mixed_layout(v, p, count, false);
-    if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
-    return prove_mixed_classes(v, p, L, d_values, d_gammas, fs, blind_key, index_base, d_blinding, d_out_points, d_out_scalars,
-                               d_out_challenges, static_cast<uint8_t*>(d_workspace), workspace_bytes, st, amount64);
-}
-
-// The classes are proved into the class regions of the workspace (the layout the mixed decoder writes); the encoder is the
-// only kernel that touches the caller's byte buffers.
-template <class C>
-int VerifyImpl<C>::prove_serialized_mixed(bpp_verifier* v, const uint64_t* d_values, const uint64_t* d_gammas,
-                                          const uint32_t* m_of, size_t count, bool fs, const uint8_t* blind_key,
-                                          uint64_t index_base, const uint64_t* d_blinding, uint8_t* d_out_proofs,
-                                          uint8_t* d_out_commitments, void* d_workspace, size_t workspace_bytes, hipStream_t st,
-                                          uint32_t version, bool amount64) {
-    if (int rc = container_args_ok(v, version)) return rc;
-    MixedPlan p;
-    int rc = prove_plan(v->s, m_of, count, (size_t)container_point_bytes<C>(version), true, p);
-    if (rc) return rc;
-    const ProveMixedLayout L = prove_mixed_layout(v, p, count, true);
-    if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
-    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-    rc = prove_mixed_classes(v, p, L, d_values, d_gammas, fs, blind_key, index_base, d_blinding,
-                             reinterpret_cast<uint64_t*>(ws + L.records), reinterpret_cast<uint64_t*>(ws + L.scalars), nullptr, ws,
-                             workspace_bytes, st, amount64);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_container_encode_mixed<C>, dim3((unsigned)(p.lanes / SER_WAVE)), dim3(SER_WAVE), 0, st, p.classes,
-                       reinterpret_cast<const uint32_t*>(ws + L.idx) + count * PX_WORDS,
-                       reinterpret_cast<const uint32_t*>(ws + L.records), reinterpret_cast<const uint32_t*>(ws + L.scalars),
-                       d_out_proofs, d_out_commitments, version);
-    HIPCHK(hipGetLastError());
-    return BPP_OK;
-}
-
-template <class C>
-int VerifyImpl<C>::prove_batch(bpp_verifier* v, const uint64_t* values, const uint64_t* gammas, size_t count,
-                       uint64_t* out_points, uint64_t* out_scalars, uint64_t* out_V, bool fs, const uint8_t* blind_key,
-                       uint64_t index_base, bool amount64) {
-    const VerifyShape& s = v->s;
-    const uint32_t k = s.k, m = s.m;
-    hipStream_t st = nullptr;
-    const ProveLayout L = prove_layout(s, count);
-    DevBuf d_val, d_gam, d_pts, d_V, d_sc, d_ws;
-    HIPCHK(d_val.alloc(count * m * 8));
-    HIPCHK(hipMemcpyAsync(d_val.p, values, count * m * 8, hipMemcpyHostToDevice, st));
-    int rc = upload_scalars<C>(gammas, count * m, d_gam, st);
-    if (rc) return rc;
-    HIPCHK(d_pts.alloc(count * (size_t)(3 + 2 * k) * WW * 4));
-    HIPCHK(d_V.alloc(count * (size_t)m * WW * 4));
-    HIPCHK(d_sc.alloc(count * 3 * 32));
-    HIPCHK(d_ws.alloc(L.total));
-    rc = prove_batch_device(v, static_cast<const uint64_t*>(d_val.p), static_cast<const uint64_t*>(d_gam.p), count,
-                            static_cast<uint64_t*>(d_pts.p), static_cast<uint64_t*>(d_sc.p),
-                            static_cast<uint64_t*>(d_V.p), fs, nullptr, d_ws.p, L.total, st, blind_key, index_base, nullptr,
-                            amount64);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out_points, d_pts.p, count * (size_t)(3 + 2 * k) * WW * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out_scalars, d_sc.p, count * 96, hipMemcpyDeviceToHost, st));
-    if (out_V) HIPCHK(hipMemcpyAsync(out_V, d_V.p, count * (size_t)m * WW * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
     return BPP_OK;
 }
 

@@ -3,9 +3,11 @@
 //
 // The verifier is VerifyImpl::run_stage -- the pass prologue, layout carver, proof-point MSM, fixed-generator MulVec and
 // verdicts of bpp_verifier_run -- with the seam's two scalar kernels as its scalar stage and a pass shape of its own
-// (wip_verify_shape).  The prover runs the range prover's round / final / MulVec / collect kernels behind k_wip_init.
+// (wip_verify_shape).  The prover is k_wip_px, the blinding, k_wip_init (k_wip_fs_start) and k_wip_challenges_out around
+// ProveBatchImpl::argument (impl_prove_batch.hpp), the schedule it shares with the range prover: the kernels of
+// prover_batch.hpp are launched from there, this unit compiles k_wip_* and k_wvs_* alone.
 #pragma once
-#include "impl_verify.hpp"
+#include "impl_prove_batch.hpp"
 #include "wip_seam.hpp"
 
 namespace bpp {
@@ -15,6 +17,7 @@ constexpr uint32_t WIP_E_ROUND = 7, WIP_E_FINAL = 99;   // wip.rs:131 / :353, :2
 template <class C>
 struct WipImpl {
     using V = VerifyImpl<C>;
+    using PB = ProveBatchImpl<C>;
     static constexpr int WW = V::WW;
     static constexpr int JW = V::JW;
 
@@ -34,12 +37,12 @@ struct WipImpl {
 
     // ---- prover: workspace = the range prover's layout for the seam's shape | the chunk's px entries -----------------
     struct ProveWs {
-        typename V::ProveLayout run;
+        typename PB::ProveLayout run;
         size_t px, total;
     };
     static ProveWs prove_ws(const bpp_verifier* v, size_t count) {
         ProveWs w;
-        w.run = V::prove_layout(prove_shape(v), count);
+        w.run = PB::prove_layout(prove_shape(v), count);
         WsCarver o;
         o.take(w.run.total);
         w.px = o.take(w.run.chunk * (size_t)PX_WORDS * 4);
@@ -92,85 +95,35 @@ int WipImpl<C>::prove_device(bpp_verifier* v, const uint64_t* d_a, const uint64_
     if ((count * rec_stride) >> 32) return fail(BPP_E_ARG, "count too large");
     const ProveWs Lw = prove_ws(v, count);
     if (workspace_bytes < Lw.total) return fail(BPP_E_ARG, "workspace too small");
-    const typename V::ProveLayout& L = Lw.run;
-    BlindKey bk;
-    load_key_words(blind_key, bk.w);
-    ProverConsts pc;
-    pc.alpha = 0;   // the range statement's; not read by the kernels of the seam
-    pc.d_L = 4;     // wip.rs:94
-    pc.d_R = 5;     // wip.rs:95
-    pc.r = 33;      // wip.rs:175-178
-    pc.s = 44;
-    pc.delta = 88;
-    pc.eta = 123;
-    pc.amount64 = 0;   // the range statement's; the seam forms no commitment
+    const typename PB::ProveLayout& L = Lw.run;
+    const ProverConsts pc = PB::literals();   // alpha and amount64 are the range statement's: not read, no commitment formed
     const WipLiterals lit{WIP_E_ROUND, WIP_E_FINAL};
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
-    uint32_t* o_pts = reinterpret_cast<uint32_t*>(d_out_points);
-    uint32_t* o_sc = reinterpret_cast<uint32_t*>(d_out_scalars);
     uint32_t* px = W(Lw.px);
     for (size_t base = 0; base < count; base += L.chunk) {
         const size_t cnt = std::min(L.chunk, count - base);
-        const unsigned lanes = cdiv(cnt, 64);
         hipLaunchKernelGGL(k_wip_px, dim3(cdiv(cnt, 256)), dim3(256), 0, st, px, base, rec_stride, cnt);
-        const uint32_t* blind = nullptr;
-        if (d_blinding) {
-            blind = reinterpret_cast<const uint32_t*>(d_blinding) + base * (size_t)pb_blind_elems(k) * 8;
-        } else if (blind_key) {
-            hipLaunchKernelGGL(k_pb_blind<C>, dim3(cdiv(cnt * pb_blind_elems(k), 64)), dim3(64), 0, st, bk, index_base, k,
-                               W(L.blind), cnt, px);
-            blind = W(L.blind);
-        }
-        // one MulVec launch over `sel` of every proof's virtual proofs, then their wire points into the records
-        auto msm = [&](VpSel sel) {
-            const size_t n = cnt * sel.cnt;
-            const unsigned per = std::min(L.per, blocks_per_proof(s, n));
-            launch_fixed_msm<C, 2>((unsigned)(n * per), st, s, W(L.vps), v->table.u32(), W(L.part), per, 0u,
-                                   (const uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)0, 0u, sel);
-            const size_t f1 = n * per * (FIXED_BLOCK / FOLD_GROUP), f2 = f1 / FOLD_GROUP2;
-            hipLaunchKernelGGL(k_partials_fold<C>, dim3(cdiv(f1, 64)), dim3(64), 0, st, W(L.part), FOLD_GROUP, W(L.part1), f1);
-            hipLaunchKernelGGL(k_partials_fold<C>, dim3(cdiv(f2, 64)), dim3(64), 0, st, W(L.part1), FOLD_GROUP2, W(L.part2), f2);
-            hipLaunchKernelGGL(k_pb_collect<C>, dim3(cdiv(n, 64)), dim3(64), 0, st, s, sel, W(L.part2),
-                               per * (FIXED_BLOCK / FOLD_GROUP / FOLD_GROUP2), o_pts, (uint32_t*)nullptr, n, px);
-        };
+        const uint32_t* slice =
+            d_blinding ? reinterpret_cast<const uint32_t*>(d_blinding) + base * (size_t)pb_blind_elems(k) * 8 : nullptr;
+        const uint32_t* blind = PB::chunk_blinding(slice, blind_key, index_base, k, cnt, px, W(L.blind), st);
         hipLaunchKernelGGL(k_wip_init<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, lit, fs ? 1u : 0u,
                            reinterpret_cast<const uint32_t*>(d_a) + base * (size_t)s.mn * 8,
                            reinterpret_cast<const uint32_t*>(d_b) + base * (size_t)s.mn * 8,
                            reinterpret_cast<const uint32_t*>(d_y) + base * 8,
                            reinterpret_cast<const uint32_t*>(d_gamma) + base * 8, W(L.a), W(L.b), W(L.cG), W(L.cH), W(L.pwy),
                            W(L.con), W(L.vps));
-        uint32_t* o_ch = d_out_challenges ? reinterpret_cast<uint32_t*>(d_out_challenges) + base * (size_t)(1 + k) * 8 : nullptr;
-        if (!fs) {
-            for (uint32_t t = 0; t < k; t++)
-                hipLaunchKernelGGL(k_pb_round<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, t, (uint32_t)PB_ALL, W(L.a),
-                                   W(L.b), W(L.cG), W(L.cH), W(L.pwy), W(L.con), W(L.vps));
-            hipLaunchKernelGGL(k_pb_final<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, (uint32_t)PB_ALL, W(L.a), W(L.b),
-                               W(L.cG), W(L.cH), W(L.con), W(L.vps), o_sc, px);
-            msm(VpSel{nvp, 1u, 2 * k + 2, 1u});   // L_t, R_t, wip.A, wip.B: the virtual proofs that exist
-            if (o_ch)
-                hipLaunchKernelGGL(k_wip_challenges_out<C>, dim3((unsigned)cnt), dim3(64), 0, st, k, lit, (const uint32_t*)nullptr,
-                                   o_ch);
-            continue;
-        }
-        hipLaunchKernelGGL(k_wip_fs_start<C>, dim3(lanes), dim3(64), 0, st, s, static_cast<const uint8_t*>(d_transcript) + base * 32,
-                           W(L.trst), cnt);
-        for (uint32_t t = 0; t < k; t++) {
-            hipLaunchKernelGGL(k_pb_round<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, t, (uint32_t)PB_PRE, W(L.a), W(L.b),
-                               W(L.cG), W(L.cH), W(L.pwy), W(L.con), W(L.vps));
-            msm(VpSel{nvp, 1 + 2 * t, 2u, 1u});   // L_t, R_t
-            hipLaunchKernelGGL(k_pb_fs_round<C>, dim3(lanes), dim3(64), 0, st, s, t, o_pts, W(L.trst), W(L.ch), W(L.con), cnt, px);
-            hipLaunchKernelGGL(k_pb_round<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, t, (uint32_t)PB_POST, W(L.a),
-                               W(L.b), W(L.cG), W(L.cH), W(L.pwy), W(L.con), W(L.vps));
-        }
-        hipLaunchKernelGGL(k_pb_final<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, (uint32_t)PB_PRE, W(L.a), W(L.b),
-                           W(L.cG), W(L.cH), W(L.con), W(L.vps), o_sc, px);
-        msm(VpSel{nvp, 2 * k + 1, 2u, 1u});       // wip.A, wip.B
-        hipLaunchKernelGGL(k_pb_fs_final<C>, dim3(lanes), dim3(64), 0, st, s, o_pts, W(L.trst), W(L.ch), W(L.con), cnt, px);
-        hipLaunchKernelGGL(k_pb_final<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, (uint32_t)PB_POST, W(L.a), W(L.b),
-                           W(L.cG), W(L.cH), W(L.con), W(L.vps), o_sc, px);
-        if (o_ch)
-            hipLaunchKernelGGL(k_wip_challenges_out<C>, dim3((unsigned)cnt), dim3(64), 0, st, k, lit, W(L.ch), o_ch);
+        if (fs)
+            hipLaunchKernelGGL(k_wip_fs_start<C>, dim3(cdiv(cnt, 64)), dim3(64), 0, st, s,
+                               static_cast<const uint8_t*>(d_transcript) + base * 32, W(L.trst), cnt);
+        // the challenges are hashed into the workspace's 3 + k blocks; the caller's are [e, e_1..e_k]
+        PB::argument(typename PB::Chunk{s, pc, L, ws, cnt, blind, px, reinterpret_cast<uint32_t*>(d_out_points), nullptr,
+                                        reinterpret_cast<uint32_t*>(d_out_scalars), W(L.ch), st, v->table.u32()},
+                     fs, VpSel{nvp, 1u, 2 * k + 2, 1u});   // literal mode: L_t, R_t, wip.A, wip.B, the virtual proofs that exist
+        if (d_out_challenges)
+            hipLaunchKernelGGL(k_wip_challenges_out<C>, dim3((unsigned)cnt), dim3(64), 0, st, k, lit,
+                               fs ? W(L.ch) : (const uint32_t*)nullptr,
+                               reinterpret_cast<uint32_t*>(d_out_challenges) + base * (size_t)(1 + k) * 8);
     }
     HIPCHK(hipGetLastError());
     return BPP_OK;

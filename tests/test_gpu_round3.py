@@ -2,6 +2,7 @@
   * blinding supplied by the caller to the transcript-mode prover (include/bpp_amd.h "Blinding") == the C oracle's
     transcript-mode prover with the same blinding values, bit for bit; the reference's literals
     (src/range/mod.rs:94,256; src/weighted_inner_product_proof.rs:94-95,175-178) stay the default of the parity calls
+    (and the same over 2 050 proofs, more than one chunk of the prover's workspace: the chunk loop, host and device form)
   * points outside BLS12-381's G1: what the raw wire call does with R_0 + T (T of order 3), pinned; the opt-in subgroup
     check (bpp_verifier_set_subgroup_check) rejects it, like the reference's full-curve sum
     (src/bls12_381/building_block/point/point.rs:69-85 = mcl G1::mul) would
@@ -69,6 +70,69 @@ def test_blinded_transcript_prover_matches_oracle(cname, cid, n, vals, gams):
     ch = d_ch.cpu().numpy().view(np.uint64)
     ok, _, _ = run_verifier_device(torch, bv, recs, scs, want_scalars=False, want_result=False, challenges=ch)
     assert ok.tolist() == [0, 0, 0]
+    bv.close()
+
+
+def test_transcript_prover_across_a_chunk_boundary():
+    """2050 proofs, more than one chunk of the prover's workspace, under the transcript with a key: the proofs next to the
+    boundary against the oracle, one call against two, the device form with a blinding buffer against the host form"""
+    torch = need_gpu()
+    import bulletproofsplus_amd as B
+    cname, cid, n, m = "bls12_381", 0, 4, 2
+    a = B.Arith.init(cname)
+    r = P.CURVES[cname]["r"]
+    opk = O.PublicKey(cid, n * m)
+    bv = B.BatchVerifier(B.PublicKey.from_points(a, opk.gh, opk.G, opk.H), n, m, window_bits=5)
+    k, PW = bv.k, a.PW
+    # The prover works through a batch in chunks of min(2048, 12 GB / (virtual proofs x MulVec length x 32 B)) proofs.  Here a
+    # proof has 2k + 3 + m = 11 virtual proofs of 2 n m + 2k + 5 + m = 29 scalars, 10 kB: the memory bound is six orders of
+    # magnitude away and a chunk is 2048 proofs.
+    chunk, count, base = 2048, 2050, 1000
+    key = bytes(range(100, 132))
+    rng = np.random.default_rng(2050)
+    vals = rng.integers(0, 1 << n, size=(count, m), dtype=np.uint64)
+    gints = [[int(x) for x in row] for row in rng.integers(1, 1 << 62, size=(count, m))]
+    gams = np.zeros((count, m, 4), dtype=np.uint64)
+    gams[:, :, 0] = np.asarray(gints, dtype=np.uint64)
+    pts, scs, V = bv.prove_batch(vals, gams, transcript=True, blind_key=key, index_base=base)
+    O.set_transcript(True)
+    try:
+        for i in (0, chunk - 1, chunk, count - 1):
+            O.set_blinding(O.blinding_from_key(key, base + i, k, r))
+            opts, osc, oV = O.range_prove(opk, n, [int(x) for x in vals[i]], gints[i])
+            assert np.array_equal(pts[i], opts) and np.array_equal(scs[i], osc) and np.array_equal(V[i], oV), i
+    finally:
+        O.set_blinding(None)
+        O.set_transcript(False)
+    lo = bv.prove_batch(vals[:chunk], gams[:chunk], transcript=True, blind_key=key, index_base=base)
+    hi = bv.prove_batch(vals[chunk:], gams[chunk:], transcript=True, blind_key=key, index_base=base + chunk)
+    for whole, x, y in zip((pts, scs, V), lo, hi):
+        assert np.array_equal(whole, np.concatenate([x, y]))
+    # the device form: the key's expansions as a blinding buffer, the challenges written out
+    dev = torch.device("cuda:0")
+    bl = b"".join(x.to_bytes(32, "little") for i in range(count) for x in O.blinding_from_key(key, base + i, k, r))
+    d_bl = torch.from_numpy(np.frombuffer(bl, dtype=np.int64).copy()).to(dev)
+    d_v = torch.from_numpy(np.ascontiguousarray(vals).view(np.int64)).to(dev)
+    d_g = torch.from_numpy(np.ascontiguousarray(gams).view(np.int64)).to(dev)
+    d_p = torch.zeros((count, 3 + 2 * k, PW), dtype=torch.int64, device=dev)
+    d_s = torch.zeros((count, 3, 4), dtype=torch.int64, device=dev)
+    d_V = torch.zeros((count, m, PW), dtype=torch.int64, device=dev)
+    d_c = torch.zeros((count, 3 + k, 4), dtype=torch.int64, device=dev)
+    wsb = bv.prover_workspace_bytes(count)
+    d_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    bv.prove_batch_device(d_v.data_ptr(), d_g.data_ptr(), count, d_p.data_ptr(), d_s.data_ptr(), d_V.data_ptr(), d_ws.data_ptr(),
+                          wsb, torch.cuda.current_stream().cuda_stream, transcript=True, d_out_challenges=d_c.data_ptr(),
+                          d_blinding=d_bl.data_ptr())
+    torch.cuda.synchronize()
+    assert np.array_equal(d_p.cpu().numpy().view(np.uint64), pts)
+    assert np.array_equal(d_s.cpu().numpy().view(np.uint64), scs)
+    assert np.array_equal(d_V.cpu().numpy().view(np.uint64), V)
+    recs = np.ascontiguousarray(np.concatenate([pts, V], axis=1))
+    d_recs = torch.from_numpy(recs.view(np.int64)).to(dev)
+    d_ch = torch.zeros((count, 3 + k, 4), dtype=torch.int64, device=dev)
+    bv.derive_challenges_device(d_recs.data_ptr(), count, d_ch.data_ptr())
+    torch.cuda.synchronize()
+    assert np.array_equal(d_c.cpu().numpy(), d_ch.cpu().numpy())
     bv.close()
 
 

@@ -2,8 +2,8 @@
 (bpp_wip_prove_batch_device, bpp_wip_verify_batch_device and their host forms; include/bpp_amd.h).
 
 The prover is pinned bit for bit against pyref's restatement of wip.rs:36-227 (literal mode, under a caller-owned
-transcript, with blinding) and against the engine's own range prover; the verifier against bpp_verifier_run on range
-statements (m = 1: scalars and result identical; m > 1: verdicts), against pyref's verify_mulvec scalar list and the
+transcript, with blinding, and across a chunk of the prover's workspace) and against the engine's own range prover; the
+verifier against bpp_verifier_run on range statements (m = 1: scalars and result identical; m > 1: verdicts), against pyref's verify_mulvec scalar list and the
 oracle's MulVec of it on a sweep of geometries, and for the subgroup check, the usage errors and y = 0."""
 
 import hashlib
@@ -54,18 +54,25 @@ def _dev(torch, x):
     return torch.from_numpy(x.view(np.uint8).reshape(-1)).to(torch.device("cuda:0"))
 
 
+def _rows_wire(rows):
+    """scalars (a list, or a list of rows) in wire form; an array is taken to be in wire form already"""
+    if isinstance(rows, np.ndarray):
+        return rows
+    rows = list(rows)
+    return O.scalars_to_wire([x for row in rows for x in row] if rows and isinstance(rows[0], (list, tuple)) else rows)
+
+
 def _prove_device(torch, cx, a, b, y, gamma, nv, transcript=None, blind_key=None, index_base=0, blinding=None):
     """bpp_wip_prove_batch_device into sentinel-filled buffers -> (records (count, 3+2k+nv, PW), scalars, challenges)"""
     bv, count = cx.bv, len(a)
     npts = bv.wip_points_per_proof(nv)
-    d_a = _dev(torch, O.scalars_to_wire([x for row in a for x in row]))
-    d_b = _dev(torch, O.scalars_to_wire([x for row in b for x in row]))
-    d_y, d_g = _dev(torch, O.scalars_to_wire(list(y))), _dev(torch, O.scalars_to_wire(list(gamma)))
+    d_a, d_b = _dev(torch, _rows_wire(a)), _dev(torch, _rows_wire(b))
+    d_y, d_g = _dev(torch, _rows_wire(y)), _dev(torch, _rows_wire(gamma))
     d_p = torch.full((count * npts * cx.PW * 8,), SENT, dtype=torch.uint8, device="cuda:0")
     d_s = torch.full((count * 96,), SENT, dtype=torch.uint8, device="cuda:0")
     d_c = torch.full((count * (1 + cx.k) * 32,), SENT, dtype=torch.uint8, device="cuda:0")
     d_t = _dev(torch, np.frombuffer(b"".join(transcript), dtype=np.uint8).copy()) if transcript is not None else None
-    d_bl = _dev(torch, O.scalars_to_wire([x for row in blinding for x in row])) if blinding is not None else None
+    d_bl = _dev(torch, _rows_wire(blinding)) if blinding is not None else None
     wsb = bv.wip_prover_workspace_bytes(count)
     assert wsb > 0
     d_ws = torch.empty(wsb, dtype=torch.uint8, device="cuda:0")
@@ -237,6 +244,72 @@ def test_blinding_from_a_key_and_from_a_buffer():
     assert not np.array_equal(recs[0], recs[1]) and not np.array_equal(scs[0], scs[1])
     ok, _, _ = _verify_device(torch, cx, np.stack(recs), np.stack(scs), [c.y] * 2, [c.statement()] * 2, 1, transcript=st * 2)
     assert ok.tolist() == [0, 0]
+
+
+# ---- 4b. more proofs than one chunk of the prover's workspace ------------------------------------------------------------
+def _bulk_wire(xs):
+    """O.scalars_to_wire for thousands of scalars < 2^256"""
+    return np.frombuffer(b"".join(x.to_bytes(32, "little") for x in xs), dtype=np.uint64).reshape(-1, 4).copy()
+
+
+def test_seam_across_a_chunk_boundary():
+    """one call over 2050 proofs == the calls [0:2048] and [2048:2050], in literal mode, under the transcript with a key and
+    with a blinding buffer; the proofs next to the boundary against pyref; the key's expansion against the oracle's"""
+    torch = need_gpu()
+    cx = Ctx("secp256k1", 8, 1, 5)
+    k, r, ln, nv = cx.k, cx.r, cx.length, 1
+    # The prover works through a batch in chunks of min(2048, 12 GB / (virtual proofs x MulVec length x 32 B)) proofs.  Here a
+    # proof has 2k + 3 = 9 virtual proofs of 2 len + 2k + 5 = 27 scalars, 7.8 kB: the memory bound is six orders of
+    # magnitude away and a chunk is 2048 proofs.
+    chunk, count, base = 2048, 2050, 1000
+    rng = random.Random(20480)
+    a = [[rng.randrange(r) for _ in range(ln)] for _ in range(count)]
+    b = [[rng.randrange(r) for _ in range(ln)] for _ in range(count)]
+    y = [rng.randrange(1, r) for _ in range(count)]
+    gamma = [rng.randrange(r) for _ in range(count)]
+    wa = _bulk_wire([x for row in a for x in row]).reshape(count, ln, 4)
+    wb = _bulk_wire([x for row in b for x in row]).reshape(count, ln, 4)
+    wy, wg = _bulk_wire(y), _bulk_wire(gamma)
+    states = [hashlib.sha256(b"chunk boundary %d" % i).digest() for i in range(count)]
+    key = bytes(range(50, 82))
+    # d_L[t], d_R[t] the same in every round: what pyref's class attributes express
+    const_bl = []
+    for _ in range(count):
+        s7 = [rng.randrange(1, r) for _ in range(7)]
+        const_bl.append(s7[:5] + [s7[5]] * k + [s7[6]] * k)
+    w_const = _bulk_wire([x for row in const_bl for x in row]).reshape(count, 5 + 2 * k, 4)
+    w_key = _bulk_wire([x for i in range(count) for x in O.blinding_from_key(key, base + i, k, r)]).reshape(count, 5 + 2 * k, 4)
+
+    def run(lo, hi, **kw):
+        return _prove_device(torch, cx, wa[lo:hi], wb[lo:hi], wy[lo:hi], wg[lo:hi], nv, **kw)
+
+    modes = {
+        "literal": lambda lo, hi: run(lo, hi),
+        "key": lambda lo, hi: run(lo, hi, transcript=states[lo:hi], blind_key=key, index_base=base + lo),
+        "buffer": lambda lo, hi: run(lo, hi, transcript=states[lo:hi], blinding=w_const[lo:hi]),
+    }
+    sent = np.frombuffer(bytes([SENT]) * 8, dtype=np.uint64)[0]
+    near = (0, chunk - 1, chunk, count - 1)
+    cases = {i: W.WipCase(cx.pk, a[i], b[i], y[i], gamma[i], None, None, None, None, [], None) for i in near}
+    for name, f in modes.items():
+        rec, sc, ch = f(0, count)
+        parts = [f(0, chunk), f(chunk, count)]          # the second call in key mode: index_base = 3048
+        assert np.array_equal(rec[:, 1:3 + 2 * k], np.concatenate([p[0][:, 1:3 + 2 * k] for p in parts])), name
+        assert np.array_equal(sc, np.concatenate([p[1] for p in parts])), name
+        assert np.array_equal(ch, np.concatenate([p[2] for p in parts])), name
+        assert (rec[:, 0] == sent).all() and (rec[:, 3 + 2 * k:] == sent).all(), name      # A' and V are the caller's
+        if name == "key":       # the oracle's expansion of the key, handed over as a buffer
+            kr, ks, kc = run(0, count, transcript=states, blinding=w_key)
+            assert np.array_equal(rec, kr) and np.array_equal(sc, ks) and np.array_equal(ch, kc)
+            continue
+        for i in near:
+            if name == "literal":
+                pf, es = cases[i].prove(), [99] + [7] * k
+            else:
+                pf, es = _with_blinding(const_bl[i], k, lambda: _pyref_fs_prove(cx, cases[i], states[i]))
+            assert np.array_equal(rec[i, 1:3 + 2 * k], cx.wire([pf.A, pf.B] + list(pf.L_vec) + list(pf.R_vec))), (name, i)
+            assert O.wire_to_scalars(sc[i]) == [pf.r_prime, pf.s_prime, pf.d_prime], (name, i)
+            assert O.wire_to_scalars(ch[i]) == es, (name, i)
 
 
 # ---- 5. the verifier equals the range pass, m = 1 --------------------------------------------------------------------
