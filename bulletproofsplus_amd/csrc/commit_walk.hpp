@@ -3,9 +3,9 @@
 // prover.rs:37 or, in amount mode (BPP_PROVE_AMOUNT64), the whole u64.  Plain C++ beside ec.hpp and fixed_glv.hpp, so the
 // host test (tests/host/commit_walk_host_test.cpp) compiles the very code k_commit_batch (commit.hpp) runs.
 //
-// The digits are those k_fixed_msm takes from the same tables: uniform layouts add the bias, cut signed digits of c bits
-// and keep what is left as the unsigned top digit; BLS12-381 splits each scalar with the endomorphism (glv_split_balanced),
-// sums both k2 halves negated, multiplies the accumulator's X by beta once and adds both k1 halves.  A non-zero digit is
+// The digits are those k_fixed_msm takes from the same tables (fixed_glv.hpp win_biased / win_next_digit), of the whole
+// scalar or, on BLS12-381, of the halves of its endomorphism split (glv_split_balanced): there the walk sums both k2
+// halves negated, multiplies the accumulator's X by beta once and adds both k1 halves.  A non-zero digit is
 // one table entry and one lazy mixed addition; a zero digit is nothing, so a 64-bit amount costs at most
 // ceil(65 / c) additions on g whatever the scalar field's width.  xyzz_madd_lazy is complete (P + P, P - P): with the
 // reference's test key h = 2 g both occur.
@@ -42,13 +42,26 @@ BPP_HD void commit_amount_scalar(uint64_t v, bool amount64, uint32_t out[8]) {
         fe_to_canonical(fe_from_i32<P>(vi), out);
 }
 
-// S: the window layout (VerifyShape, or the host test's restatement): c, W, half, per_f, bias[], and for the split
-// tables wc[], went[].  kv, kg: canonical scalars (< r) on g and h.  load_entry(e) -> Aff<C>: entry e of the table
-// (generator f's row starts at f * per_f).  add(acc, entry, neg): acc += neg ? -entry : entry.
+// S: the window layout (VerifyShape, or a WinLayout): W, per_f, bias[], wc[], went[].  kv, kg: canonical scalars (< r) on g
+// and h.  load_entry(e) -> Aff<C>: entry e of the table (generator f's row starts at f * per_f).  add(acc, entry, neg):
+// acc += neg ? -entry : entry.
 template <class C, class S, class Load, class Add>
 BPP_HD Xyzz<C> commit_walk(const S& s, const uint32_t kv[8], const uint32_t kg[8], Load&& load_entry, Add&& add) {
+    constexpr bool GLV = commit_walk_glv<C>();
+    constexpr int NW = GLV ? GLV_HALF_WORDS : WIN_FULL_WORDS;
     Xyzz<C> acc = xyzz_inf<C>();
-    if constexpr (commit_walk_glv<C>()) {
+    // the digit loop: the value k (a scalar, or a half that stands for its negative if hneg) over generator f's row
+    auto walk = [&](const uint32_t* k, uint32_t f, bool hneg) {
+        uint32_t w[NW];
+        win_biased<NW>(k, s.bias, w);
+        for (uint32_t j = 0; j < s.W; j++) {
+            const int32_t dg = win_next_digit(w, win_width(s, j));   // width 0: the top window
+            if (dg == 0) continue;
+            const uint32_t mag = dg < 0 ? (uint32_t)(-dg) : (uint32_t)dg;
+            add(acc, load_entry((size_t)f * s.per_f + s.went[j] + (mag - 1)), (dg < 0) != hneg);
+        }
+    };
+    if constexpr (GLV) {
         // the four halves stay in registers: they are chosen by selects on the (wave-uniform) step, never indexed
         uint32_t k1v[4], k2v[4], k1g[4], k2g[4];
         bool n1v, n2v, n1g, n2g;
@@ -62,38 +75,15 @@ BPP_HD Xyzz<C> commit_walk(const S& s, const uint32_t kv[8], const uint32_t kg[8
             uint32_t h[4];
 #pragma unroll
             for (int t = 0; t < 4; t++) h[t] = phase ? (f ? k1g[t] : k1v[t]) : (f ? k2g[t] : k2v[t]);
-            const bool hneg = phase ? (f ? n1g : n1v) : !(f ? n2g : n2v);
-            uint32_t w[GLV_HALF_WORDS];
-            glv_biased(h, s.bias, w);
-            for (uint32_t j = 0; j < s.W; j++) {
-                const int32_t dg = glv_next_digit(w, s.wc[j]);   // width 0: the top window
-                if (dg == 0) continue;
-                const uint32_t mag = dg < 0 ? (uint32_t)(-dg) : (uint32_t)dg;
-                add(acc, load_entry((size_t)f * s.per_f + s.went[j] + (mag - 1)), (dg < 0) != hneg);
-            }
+            walk(h, f, phase ? (f ? n1g : n1v) : !(f ? n2g : n2v));
         }
     } else {
-        const uint32_t mask = (1u << s.c) - 1u;
+#pragma unroll 1
         for (uint32_t f = 0; f < 2; f++) {
-            const uint32_t* k = f ? kg : kv;
-            uint32_t w[10];
-            uint32_t carry = 0;
+            uint32_t k[8];   // chosen by selects, as the halves are: an indexed scalar would go to scratch
 #pragma unroll
-            for (int t = 0; t < 10; t++) {
-                const uint64_t x = (uint64_t)(t < 8 ? k[t] : 0u) + s.bias[t] + carry;
-                w[t] = (uint32_t)x;
-                carry = (uint32_t)(x >> 32);
-            }
-            for (uint32_t j = 0; j < s.W; j++) {
-                // windows below the top: signed digit; top window: what is left of the value, unsigned (<= top)
-                const int32_t dg = j + 1 < s.W ? (int32_t)(w[0] & mask) - (int32_t)s.half : (int32_t)w[0];
-#pragma unroll
-                for (int t = 0; t < 9; t++) w[t] = (w[t] >> s.c) | (w[t + 1] << (32 - s.c));
-                w[9] >>= s.c;
-                if (dg == 0) continue;
-                const uint32_t mag = dg < 0 ? (uint32_t)(-dg) : (uint32_t)dg;
-                add(acc, load_entry((size_t)f * s.per_f + (size_t)j * s.half + (mag - 1)), dg < 0);
-            }
+            for (int t = 0; t < 8; t++) k[t] = f ? kg[t] : kv[t];
+            walk(k, f, false);
         }
     }
     return acc;

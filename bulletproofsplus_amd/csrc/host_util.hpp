@@ -178,7 +178,7 @@ inline bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
 
 // fr_modw: the scalar-field modulus as 8 little-endian 32-bit words, fr_bits its bit length.
 // glv_half_max (4 words, or null): the table serves the two halves of the curve's endomorphism split, each at most this
-// large -- the layout of fixed_glv.hpp instead of uniform windows over the whole scalar (make_verify_shape below).
+// large -- the mixed-width layout of fixed_glv.hpp instead of the uniform one (make_verify_shape below).
 inline int make_shape(size_t n, size_t m, int c, const uint32_t* fr_modw, int fr_bits, VerifyShape& s,
                       const uint32_t* glv_half_max = nullptr) {
     const size_t mn = n * m;
@@ -188,6 +188,13 @@ inline int make_shape(size_t n, size_t m, int c, const uint32_t* fr_modw, int fr
     while (((size_t)1 << k) < mn) k++;
     if (k > VS_MAXK) return fail(BPP_E_ARG, "n*m too large");
     if (c < 2 || c > 20) return fail(BPP_E_ARG, "window_bits must be in [2, 20]");
+    static_assert(VS_MAXW == GLV_MAXW, "VerifyShape carries a WinLayout's windows");
+    WinLayout L;
+    if (glv_half_max) {
+        if (!glv_layout(c, fr_bits, glv_half_max, L)) return fail(BPP_E_ARG, "window_bits too small or too large for this scalar field");
+    } else if (const char* why = win_layout_uniform(c, fr_modw, fr_bits, L)) {
+        return fail(BPP_E_ARG, why);
+    }
     s.n = (uint32_t)n;
     s.m = (uint32_t)m;
     s.mn = (uint32_t)mn;
@@ -196,61 +203,17 @@ inline int make_shape(size_t n, size_t m, int c, const uint32_t* fr_modw, int fr
     s.NF = (uint32_t)(2 * mn + 2);
     s.NV = (uint32_t)(3 + 2 * k + m);
     s.c = (uint32_t)c;
+    s.W = L.W;
+    s.top = L.top;
+    s.per_f = L.per_f;
+    for (int t = 0; t < WIN_FULL_WORDS; t++) s.bias[t] = L.bias[t];
     s.hgap = 0;
-    s.glv = 0;
-    s.head_wip = m == 1 ? 1u : 0u;
+    s.glv = glv_half_max ? 1u : 0u;
     for (int j = 0; j < VS_MAXW; j++) {
-        s.wc[j] = 0;
-        s.went[j] = 0;
+        s.wc[j] = L.wc[j];
+        s.went[j] = L.went[j];
     }
-    // W - 1 signed windows below bit c (W-1) < fr_bits, then one unsigned top window for the rest of the value
-    s.W = (uint32_t)((fr_bits - 1) / c + 1);
-    s.half = 1u << (c - 1);
-    for (int t = 0; t < 10; t++) s.bias[t] = 0;
-    if (glv_half_max) {
-        static_assert(VS_MAXW == GLV_MAXW, "VerifyShape carries a GlvLayout's windows");
-        GlvLayout L;
-        if (!glv_layout(c, fr_bits, glv_half_max, L)) return fail(BPP_E_ARG, "window_bits too small or too large for this scalar field");
-        s.glv = 1;
-        s.W = L.W;
-        s.top = L.top;
-        s.per_f = L.per_f;
-        for (uint32_t j = 0; j < L.W; j++) {
-            s.wc[j] = L.wc[j];
-            s.went[j] = L.went[j];
-        }
-        for (int t = 0; t < GLV_HALF_WORDS; t++) s.bias[t] = L.bias[t];
-        return BPP_OK;
-    }
-    for (uint32_t j = 0; j + 1 < s.W; j++) {
-        const uint32_t bit = s.c * j + (s.c - 1);
-        s.bias[bit >> 5] |= 1u << (bit & 31);
-    }
-    // largest top digit: (r - 1 + bias) >> c (W - 1)
-    uint32_t v[10];
-    uint32_t carry = 0;
-    for (int t = 0; t < 10; t++) {
-        uint64_t x = (uint64_t)(t < 8 ? fr_modw[t] : 0u) + s.bias[t] + carry;
-        v[t] = (uint32_t)x;
-        carry = (uint32_t)(x >> 32);
-    }
-    uint32_t borrow = 1;   // - 1
-    for (int t = 0; t < 10 && borrow; t++) {
-        borrow = v[t] == 0 ? 1u : 0u;
-        v[t] -= 1u;
-    }
-    const uint32_t sh = s.c * (s.W - 1);
-    uint64_t top = 0;
-    for (int t = 9; t >= 0; t--) {
-        const int lo = 32 * t - (int)sh;   // bit position of word t after the shift
-        if (lo >= 32 && v[t]) return fail(BPP_E_ARG, "window_bits too small for this scalar field");
-        if (lo > -32 && lo < 32) top |= lo >= 0 ? (uint64_t)v[t] << lo : (uint64_t)(v[t] >> (-lo));
-    }
-    if (top == 0 || top >= ((uint64_t)1 << 31)) return fail(BPP_E_ARG, "window_bits too small for this scalar field");
-    s.top = (uint32_t)top;
-    const uint64_t per_f = (uint64_t)(s.W - 1) * s.half + s.top;
-    if (per_f >> 32) return fail(BPP_E_ARG, "window table too large");
-    s.per_f = (uint32_t)per_f;
+    s.head_wip = m == 1 ? 1u : 0u;
     return BPP_OK;
 }
 

@@ -5,12 +5,12 @@
 //   "affm" points    : Montgomery x | y                 (2N words)     -- pk, proof points, tables
 //   jacobian partials: Montgomery X | Y | Z             (3N words)
 //   scalars          : canonical, 8 words (4 x u64)
-//   window table     : entry[f * per_f + j * half + (d - 1)] = d * 2^(c j) * F_f   (affm); windows 0..W-2 hold
-//                      d = 1..half (signed digits, half = 2^(c-1)), the top window W-1 holds d = 1..top (its digit
-//                      is the unsigned remainder of the scalar, so no window is spent on a recoding carry);
-//                      per_f = (W-1) half + top; F = [g, h, G_0.., H_0..] the verifier's fixed generators.
-//                      BLS12-381 (fixed_glv<C>()): one table for both 127-bit halves of the endomorphism split, windows of
-//                      mixed widths: entry[f * per_f + went[j] + (d - 1)] = d * 2^(off_j) * F_f   (fixed_glv.hpp)
+//   window table     : entry[f * per_f + went[j] + (d - 1)] = d * 2^(off_j) * F_f   (affm); window j < W-1 is wc[j] bits
+//                      wide and holds d = 1..2^(wc[j]-1) (signed digits), the top window W-1 holds d = 1..top (its digit
+//                      is the unsigned remainder of the value, so no window is spent on a recoding carry); F = [g, h,
+//                      G_0.., H_0..] the verifier's fixed generators.  The layout and its digit recoding are
+//                      fixed_glv.hpp's: equal widths over the whole scalar, or (BLS12-381, fixed_glv<C>()) mixed
+//                      widths over the two 127-bit halves of the endomorphism split, which share one table.
 //
 // Kernel inventory (each names the reference call site it serves; paths relative to /root/reference/src):
 //   k_points_from_wire   wire -> affm (+ on-curve check)
@@ -358,21 +358,20 @@ __global__ void __launch_bounds__(64) k_jac_reduce(const uint32_t* __restrict__ 
 
 // ---- verifier scalars --------------------------------------------------------------------------------
 
-#define VS_MAXW 64   // windows per half of a split scalar (window_bits 2 on a 255-bit field: 128 / 2)
+#define VS_MAXW 128   // windows of a table (fixed_glv.hpp GLV_MAXW: window_bits 2 on an unsplit 256-bit scalar)
 struct VerifyShape {
     uint32_t n, m, mn, k;      // bits per value, values, n*m, log2(mn)
     uint32_t N;                // MulVec length 2mn + 2k + m + 5
     uint32_t NF, NV;           // fixed terms 2mn + 2, proof-dependent terms 3 + 2k + m
-    uint32_t c, W, half;       // window bits, windows, 2^(c-1)
+    // the windows of the fixed-generator tables (a WinLayout of fixed_glv.hpp, filled by host_util.hpp make_shape): W - 1
+    // signed windows of wc[j] bits whose entries start at went[j], then the unsigned top window (wc 0) at went[W - 1]
+    uint32_t c, W;             // the window_bits the layout was derived from, windows
     uint32_t top;              // entries of the top window (its digit is unsigned: 0..top)
-    uint32_t per_f;            // table entries per generator: (W-1) * half + top
-    uint32_t bias[10];         // sum_{j < W-1} half * 2^(c j) as 32-bit words (signed-digit recoding bias)
+    uint32_t per_f;            // table entries per generator
+    uint32_t bias[10];         // signed-digit recoding bias, as 32-bit words
     uint32_t hgap;             // table H block - this shape's H block: mn_table - mn (a prefix view of a larger table), else 0
-    // Curves whose tables serve both halves of the endomorphism split (fixed_glv<C>(), below): W counts the windows of ONE
-    // half, W - 1 signed ones of mixed widths wc[j] whose entries start at went[j], then the unsigned top window at
-    // went[W - 1]; c is the window_bits the layout was derived from and half is unused (host_util.hpp make_shape).
-    uint32_t glv;
-    uint8_t wc[VS_MAXW];
+    uint32_t glv;              // the table serves both halves of the endomorphism split (fixed_glv<C>(), below): W counts ONE half's windows
+    alignas(4) uint8_t wc[VS_MAXW];   // read with win_width (fixed_glv.hpp)
     uint32_t went[VS_MAXW];
     // order of the three head points of the MulVec (var_term_index): 1 = [wip.B, wip.A, A'] as WeightedInnerProductProof::
     // verify assembles it (wip.rs:309-311) -- the m == 1 range statement and every pass of the WIP seam (wip_seam.hpp) --,
@@ -392,10 +391,6 @@ constexpr bool fixed_glv() {
 // mixed additions per fixed generator
 __host__ __device__ __forceinline__ uint32_t fixed_adds_per_generator(const VerifyShape& s) {
     return s.glv ? 2 * s.W : s.W;
-}
-// entries of window j of the shared table, and where they start within a generator's per_f entries
-__host__ __device__ __forceinline__ uint32_t glv_window_entries(const VerifyShape& s, uint32_t j) {
-    return j + 1 < s.W ? 1u << (s.wc[j] - 1) : s.top;
 }
 
 // table slot of fixed generator f of shape s: a prefix view (n, m') of an (n, m) table finds g, h and G_0.. where they
@@ -831,12 +826,7 @@ __global__ void __launch_bounds__(64) k_affm_subgroup(const uint32_t* __restrict
     if (!aff_in_prime_subgroup<C>(aff_ldg<C>(affm + i * 2 * C::Fp::N))) atomicOr(bad, 1u);
 }
 
-// first entry (d = 1) of window j within a generator's per_f entries
-__host__ __device__ __forceinline__ size_t tbl_window_start(const VerifyShape& s, uint32_t j) {
-    return s.glv ? (size_t)s.went[j] : (size_t)j * s.half;
-}
-// thread f: base_{f,j} = 2^(off_j) * F_f for every window j (off_j = c j, or the sum of the widths below j), written as
-// entry d = 1
+// thread f: base_{f,j} = 2^(off_j) * F_f for every window j (off_j = the sum of the widths below j), written as entry d = 1
 template <class C>
 __global__ void __launch_bounds__(64) k_tbl_bases(VerifyShape s, const uint32_t* __restrict__ fixed_pts, uint32_t* __restrict__ table) {
     constexpr int N = C::Fp::N;
@@ -845,10 +835,10 @@ __global__ void __launch_bounds__(64) k_tbl_bases(VerifyShape s, const uint32_t*
     if (f >= s.NF) return;
     Aff<C> p = aff_ldg<C>(fixed_pts + (size_t)f * 2 * N);
     for (uint32_t j = 0; j < s.W; j++) {
-        aff_stg<C>(table + ((size_t)f * s.per_f + tbl_window_start(s, j)) * 2 * N, p);
+        aff_stg<C>(table + ((size_t)f * s.per_f + s.went[j]) * 2 * N, p);
         if (j + 1 < s.W) {
             Jac<C> q = jac_from_aff(p);
-            const uint32_t cj = s.glv ? s.wc[j] : s.c;
+            const uint32_t cj = win_width(s, j);
             for (uint32_t t = 0; t < cj; t++) q = jac_dbl(q);
             p = jac_to_aff(q);
         }
@@ -859,40 +849,29 @@ __global__ void __launch_bounds__(64) k_tbl_bases(VerifyShape s, const uint32_t*
 // (d0 + 1) * base, ... by affine_chain.  scratch: [thread][2 * TBL_RUN] field elements.
 constexpr uint32_t TBL_RUN = 32;
 __host__ __device__ __forceinline__ uint32_t tbl_runs_per_generator(const VerifyShape& s) {
-    if (s.glv) {   // windows of mixed widths: each has its own number of runs
-        uint32_t runs = 0;
-        for (uint32_t j = 0; j < s.W; j++) runs += (glv_window_entries(s, j) + TBL_RUN - 1) / TBL_RUN;
-        return runs;
-    }
-    return (s.W - 1) * ((s.half + TBL_RUN - 1) / TBL_RUN) + (s.top + TBL_RUN - 1) / TBL_RUN;
+    uint32_t runs = 0;   // every window has its own number of runs
+    for (uint32_t j = 0; j < s.W; j++) runs += (win_entries(s, j) + TBL_RUN - 1) / TBL_RUN;
+    return runs;
 }
 template <class C>
 __global__ void __launch_bounds__(64, BPP_VAR_TABLES_WAVES) k_tbl_fill(VerifyShape s, uint32_t* __restrict__ table, uint32_t* __restrict__ scratch,
                                                     uint32_t f_begin, uint32_t f_end) {
     constexpr int N = C::Fp::N;
-    const uint32_t runs_low = (s.half + TBL_RUN - 1) / TBL_RUN;
     const uint32_t runs_f = tbl_runs_per_generator(s);
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)(f_end - f_begin) * runs_f) return;
     const uint32_t f = f_begin + (uint32_t)(idx / runs_f);
-    const uint32_t rem = (uint32_t)(idx % runs_f);
-    uint32_t j = min(rem / runs_low, s.W - 1);   // the top window has its own number of runs
-    uint32_t r = rem - j * runs_low;
-    uint32_t cnt = j + 1 < s.W ? s.half : s.top;
-    if (s.glv) {
-        j = 0;
-        r = rem;
-        for (;;) {
-            cnt = glv_window_entries(s, j);
-            const uint32_t runs_j = (cnt + TBL_RUN - 1) / TBL_RUN;
-            if (r < runs_j) break;   // rem < runs_f: ends at the top window at the latest
-            r -= runs_j;
-            j++;
-        }
+    uint32_t j = 0, r = (uint32_t)(idx % runs_f), cnt;   // run r of window j, which has cnt entries
+    for (;;) {
+        cnt = win_entries(s, j);
+        const uint32_t runs_j = (cnt + TBL_RUN - 1) / TBL_RUN;
+        if (r < runs_j) break;   // r < runs_f: ends at the top window at the latest
+        r -= runs_j;
+        j++;
     }
     const uint32_t d0 = r * TBL_RUN + 1;
     const uint32_t n = min(TBL_RUN, cnt - (d0 - 1));
-    uint32_t* win = table + ((size_t)f * s.per_f + tbl_window_start(s, j)) * 2 * N;
+    uint32_t* win = table + ((size_t)f * s.per_f + s.went[j]) * 2 * N;
     const Aff<C> base = aff_ldg<C>(win);   // entry d = 1, written by k_tbl_bases
     Jac<C> J;
     if (d0 == 1) {
@@ -1082,7 +1061,7 @@ struct VpSel {
 };
 
 // Fixed-generator part: for proof b, sum_f scalar_f * F_f through the window tables.
-// scalar + bias -> W windows -> signed digits in [-half, half) (top window: unsigned) -> one table gather and
+// scalar + bias -> W windows -> signed digits (top window: unsigned; fixed_glv.hpp) -> one table gather and
 // one mixed addition per (generator, window).  No doublings, no buckets, no scatter: the 288 GB of HBM pay for
 // that.  partials: ROLE 0, 2: [count][per][blockDim.x] jacobians (one per thread, summed by k_partials_fold);
 // ROLE 1: [count][per] (block sums: the combined check's single MulVec, whose handful of blocks is summed by one
@@ -1119,7 +1098,7 @@ __global__ void __launch_bounds__(FIXED_BLOCK, fixed_waves<C>()) k_fixed_msm(Ver
     constexpr int CH = 2 * N / 4;                              // 16-byte pieces of a table entry
     constexpr int WAVE_WORDS = (FIXED_RING * CH + 2) * 256;    // LDS words of one wave's ring + scalar buffer
     constexpr bool GLV = fixed_glv<C>();                       // two phases over the shared table (see fixed_glv<C>())
-    constexpr int NWD = GLV ? GLV_HALF_WORDS : 10;             // words of a biased scalar (GLV: of one half)
+    constexpr int NWD = GLV ? GLV_HALF_WORDS : WIN_FULL_WORDS; // words of a biased scalar (GLV: of one half)
     extern __shared__ __align__(16) uint32_t lds[];
     if (blockIdx.x < horner_blocks) {   // block-uniform: the Horner stage of the proof-point MSM
         if (horner_tree == 2) {   // mid-size batches: eight lanes per proof, blockDim.x / 8 proofs per block
@@ -1153,7 +1132,6 @@ __global__ void __launch_bounds__(FIXED_BLOCK, fixed_waves<C>()) k_fixed_msm(Ver
     const size_t b = bid / per;
     const uint32_t part = bid % per;
     const uint32_t* sc = scalars + ((b / sel.cnt) * sel.nvp + sel.first + b % sel.cnt) * (size_t)s.N * 8;
-    const uint32_t mask = (1u << s.c) - 1u;
     const uint32_t stride = per * blockDim.x;
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t* ring = lds + (threadIdx.x >> 6) * WAVE_WORDS;    // [slot][piece][lane][4 words]
@@ -1214,30 +1192,36 @@ __global__ void __launch_bounds__(FIXED_BLOCK, fixed_waves<C>()) k_fixed_msm(Ver
     uint32_t w[NWD];
     uint32_t hneg = 0;   // GLV: the half in w stands for its negative (phase 0: the sign of psi folded in)
     uint32_t pi = 0;     // GLV: phase of the issue side -- block-uniform
-    // GLV: half `which` (0: k2, 1: k1) of scalar v, biased, and the sign its entries take (k2: that of psi folded in)
-    auto take_half = [&](const uint32_t* v, uint32_t which, uint32_t* out, uint32_t& negate) {
+    // scalar v, biased: the whole of it, or (GLV) its half `which` (0: k2, 1: k1) and the sign that half's entries take
+    // (k2: that of psi folded in)
+    auto take = [&](const uint32_t* v, uint32_t which, uint32_t* out, uint32_t& negate) {
         if constexpr (GLV) {
             uint32_t k1[4], k2[4];
             bool n1, n2;
             glv_split_balanced<C>(v, k1, k2, n1, n2);
-            glv_biased(which ? k1 : k2, s.bias, out);
+            win_biased<NWD>(which ? k1 : k2, s.bias, out);
             negate = which ? (n1 ? 1u : 0u) : (n2 ? 0u : 1u);
+        } else {
+            win_biased<NWD>(v, s.bias, out);
+            negate = 0;
         }
     };
-    auto take_scalar = [&]() {   // sbuf -> w = scalar + bias K (K = sum_{j < W-1} half * 2^(c j))
+    auto take_scalar = [&]() {   // sbuf -> w
         const uint4* q = reinterpret_cast<const uint4*>(sbuf);
         const uint4 lo = q[lane], hi = q[64 + lane];
         const uint32_t v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        take(v, pi, w, hneg);
+    };
+    // window j: its width (0: the top window) and first entry.  The uniform layout's follow from c (fixed_glv.hpp
+    // win_layout_uniform), which stays in a register; read from s.wc / s.went they cost two scalar loads a step and
+    // secp256k1 0.5 % of its headline
+    auto window = [&](uint32_t j, uint32_t& cj, uint32_t& e0) {
         if constexpr (GLV) {
-            take_half(v, pi, w, hneg);
+            cj = win_width(s, j);
+            e0 = s.went[j];
         } else {
-            uint32_t carry = 0;
-#pragma unroll
-            for (int t = 0; t < 10; t++) {
-                uint64_t x = (uint64_t)(t < 8 ? v[t] : 0u) + s.bias[t] + carry;
-                w[t] = (uint32_t)x;
-                carry = (uint32_t)(x >> 32);
-            }
+            cj = j + 1 < s.W ? s.c : 0u;
+            e0 = j << (s.c - 1);
         }
     };
     // issue side: runs FIXED_RING steps ahead of the additions
@@ -1248,95 +1232,46 @@ __global__ void __launch_bounds__(FIXED_BLOCK, fixed_waves<C>()) k_fixed_msm(Ver
         const uint32_t slot = (GLV ? pi * T + ti : ti) % FIXED_RING;
         const uint32_t* src = table;   // dummy line for lanes without an entry
         uint32_t valid = 0, neg = 0, viabeta = 0;
-        if constexpr (GLV) {
-            if (ti < T) {
-                const uint32_t qi = pi * G + gi;
-                if (ji == 0 && qi > 0) {
-                    take_scalar();
-                    if (qi + 1 < NQ) dma_scalar(gi + 1 < G ? gi + 1 : 0u);
-                }
-                const uint32_t x = f0 + gi * stride;
-                const int32_t dg = glv_next_digit(w, s.wc[ji]);   // width 0: the top window
-                if (x < NFc && dg != 0) {
-                    const uint32_t f = gen_of(x);
-                    const uint32_t mag = dg < 0 ? (uint32_t)(-dg) : (uint32_t)dg;
-                    src = table + ((size_t)table_generator(s, f) * s.per_f + s.went[ji] + (mag - 1)) * 2 * N;
-                    valid = 1;
-                    neg = (dg < 0 ? 1u : 0u) ^ hneg ^ (f >= neg_from ? 1u : 0u);
-                }
-            } else if (pi == 1 && ti < TT) {
-                const uint32_t x = (ti - T) * stride + f0;   // this lane's left-over entry, if any
-                if (x < LW) {
-                    const uint32_t which = x >= LWH ? 1u : 0u, xh = x - which * LWH;
-                    const uint32_t l = xh / s.W, jx = xh - l * s.W;
-                    const uint32_t f = gen_of(G * stride + l);
-                    uint32_t v[8], we[GLV_HALF_WORDS], hn;
-                    ld_words<8>(sc + (size_t)fixed_term_index(s, f) * 8, v);   // an ordinary load: once per block
-                    take_half(v, which, we, hn);
-                    viabeta = 1u - which;
-                    int32_t dg = 0;
-                    uint32_t eo = 0;
-                    for (uint32_t r = 0; r < s.W; r++) {   // r is the same in every lane: the widths stay scalar loads
-                        const int32_t d = glv_next_digit(we, s.wc[r]);
-                        if (r == jx) {
-                            dg = d;
-                            eo = s.went[r];
-                        }
-                    }
-                    if (dg != 0) {
-                        const uint32_t mag = dg < 0 ? (uint32_t)(-dg) : (uint32_t)dg;
-                        src = table + ((size_t)table_generator(s, f) * s.per_f + eo + (mag - 1)) * 2 * N;
-                        valid = 1;
-                        neg = (dg < 0 ? 1u : 0u) ^ hn ^ (f >= neg_from ? 1u : 0u);
-                    }
-                }
-            }
-        } else if (ti < T) {
-            if (ji == 0 && gi > 0) {
+        // non-zero digit dg of generator f in the window whose entries start at e0; hn: the value's own sign
+        auto entry = [&](int32_t dg, uint32_t f, uint32_t e0, uint32_t hn) {
+            const uint32_t mag = dg < 0 ? (uint32_t)(-dg) : (uint32_t)dg;
+            src = table + ((size_t)table_generator(s, f) * s.per_f + e0 + (mag - 1)) * 2 * N;
+            valid = 1;
+            neg = (dg < 0 ? 1u : 0u) ^ hn ^ (f >= neg_from ? 1u : 0u);
+        };
+        if (ti < T) {
+            const uint32_t qi = pi * G + gi;
+            if (ji == 0 && qi > 0) {
                 take_scalar();
-                if (gi + 1 < G) dma_scalar(gi + 1);
+                if (qi + 1 < NQ) dma_scalar(gi + 1 < G ? gi + 1 : 0u);
             }
             const uint32_t x = f0 + gi * stride;
-            // windows below the top: signed digit; top window: what is left of the value, unsigned (<= top)
-            const int32_t dg = ji + 1 < s.W ? (int32_t)(w[0] & mask) - (int32_t)s.half : (int32_t)w[0];
-#pragma unroll
-            for (int t = 0; t < 9; t++) w[t] = (w[t] >> s.c) | (w[t + 1] << (32 - s.c));
-            w[9] >>= s.c;
-            if (x < NFc && dg != 0) {
-                const uint32_t f = gen_of(x);
-                const uint32_t mag = dg < 0 ? (uint32_t)(-dg) : (uint32_t)dg;
-                src = table + ((size_t)table_generator(s, f) * s.per_f + (size_t)ji * s.half + (mag - 1)) * 2 * N;
-                valid = 1;
-                neg = (dg < 0 ? 1u : 0u) ^ (f >= neg_from ? 1u : 0u);
-            }
-        } else if (ti < TT) {
+            uint32_t cj, e0;
+            window(ji, cj, e0);
+            const int32_t dg = win_next_digit(w, cj);
+            if (x < NFc && dg != 0) entry(dg, gen_of(x), e0, hneg);
+        } else if (pi + 1 == PH && ti < TT) {
             const uint32_t x = (ti - T) * stride + f0;   // this lane's left-over entry, if any
             if (x < LW) {
-                const uint32_t l = x / s.W, jx = x - l * s.W;
+                const uint32_t which = x >= LWH ? 1u : 0u, xh = x - which * LWH;   // (GLV: the k2 halves come first)
+                const uint32_t l = xh / s.W, jx = xh - l * s.W;
                 const uint32_t f = gen_of(G * stride + l);
-                uint32_t we[10];
-                ld_words<8>(sc + (size_t)fixed_term_index(s, f) * 8, we);   // an ordinary load: once per block
-                we[8] = 0;
-                we[9] = 0;
-                uint32_t carry = 0;
-#pragma unroll
-                for (int t = 0; t < 10; t++) {
-                    uint64_t v = (uint64_t)we[t] + s.bias[t] + carry;
-                    we[t] = (uint32_t)v;
-                    carry = (uint32_t)(v >> 32);
+                uint32_t v[8], we[NWD], hn;
+                ld_words<8>(sc + (size_t)fixed_term_index(s, f) * 8, v);   // an ordinary load: once per block
+                take(v, which, we, hn);
+                if constexpr (GLV) viabeta = 1u - which;
+                int32_t dg = 0;
+                uint32_t e0 = 0;
+                for (uint32_t r = 0; r < s.W; r++) {   // r is the same in every lane: the widths stay scalar loads
+                    uint32_t cr, er;
+                    window(r, cr, er);
+                    const int32_t d = win_next_digit(we, cr);
+                    if (r == jx) {
+                        dg = d;
+                        e0 = er;
+                    }
                 }
-                for (uint32_t r = 0; r < jx; r++) {
-#pragma unroll
-                    for (int t = 0; t < 9; t++) we[t] = (we[t] >> s.c) | (we[t + 1] << (32 - s.c));
-                    we[9] >>= s.c;
-                }
-                const int32_t dg = jx + 1 < s.W ? (int32_t)(we[0] & mask) - (int32_t)s.half : (int32_t)we[0];
-                if (dg != 0) {
-                    const uint32_t mag = dg < 0 ? (uint32_t)(-dg) : (uint32_t)dg;
-                    src = table + ((size_t)table_generator(s, f) * s.per_f + (size_t)jx * s.half + (mag - 1)) * 2 * N;
-                    valid = 1;
-                    neg = (dg < 0 ? 1u : 0u) ^ (f >= neg_from ? 1u : 0u);
-                }
+                if (dg != 0) entry(dg, f, e0, hn);
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the slot's previous entry has been read out

@@ -82,14 +82,18 @@ __global__ void __launch_bounds__(64) k_dbg_glv_split(int op, const uint32_t* k,
     out[i * GLV_SPLIT_OUT + 9] = n2 ? 1u : 0u;
 }
 
-// op 3: halves of 4 words -> the L.W digits of glv_biased / glv_next_digit, GLV_MAXW words per half
-__global__ void __launch_bounds__(64) k_dbg_glv_recode(GlvLayout L, const uint32_t* h, uint32_t* out, size_t n) {
+// op 3: values of NK words (4: a half, NW = 5; 8: a whole scalar, NW = 10) -> the L.W digits of win_biased /
+// win_next_digit, ROW words per value
+constexpr int GLV_RECODE_ROW = 64;   // the split layout's rows: a half never has more windows
+template <int NW, int ROW>
+__global__ void __launch_bounds__(64) k_dbg_win_recode(WinLayout L, const uint32_t* k, uint32_t* out, size_t n) {
+    constexpr int NK = NW == GLV_HALF_WORDS ? 4 : 8;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    uint32_t half[4], v[GLV_HALF_WORDS];
-    for (int t = 0; t < 4; t++) half[t] = h[i * 4 + t];
-    glv_biased(half, L.bias, v);
-    for (uint32_t j = 0; j < (uint32_t)GLV_MAXW; j++) out[i * GLV_MAXW + j] = j < L.W ? (uint32_t)glv_next_digit(v, L.wc[j]) : 0u;
+    uint32_t kk[NK], v[NW];
+    for (int t = 0; t < NK; t++) kk[t] = k[i * NK + t];
+    win_biased<NW>(kk, L.bias, v);
+    for (uint32_t j = 0; j < (uint32_t)ROW; j++) out[i * ROW + j] = j < L.W ? (uint32_t)win_next_digit(v, win_width(L, j)) : 0u;
 }
 
 template <class F>
@@ -178,8 +182,10 @@ extern "C" int bpp_debug_madd_lazy_raw(bpp_ctx* ctx, const uint32_t* acc, const 
 // The scalar splits and the digit recoding of the fixed-generator tables, from a kernel.
 //   op 0 glv_split, 1 glv_split_balanced (BLS12-381), 2 glv_split_signed (BLS12-381, secp256k1): in = n scalars of 8
 //     canonical words; out = 10 words each: k1[4] | k2[4] | neg1 | neg2.
-//   op 3 glv_biased + glv_next_digit for the layout of window_bits (BLS12-381): in = n halves of 4 words; out = 64 words
-//     each, the W digits (two's complement) then zeros; out_layout (may be null) = W | top | per_f | 64 window widths.
+//   op 3 win_biased + win_next_digit for the layout of window_bits (every curve; fixed_glv.hpp).  BLS12-381: in = n
+//     halves of 4 words, ROW = 64; secp256k1, edwards25519: in = n scalars of 8 canonical words, ROW = 128 (VS_MAXW).
+//     out = ROW words each, the W digits (two's complement) then zeros; out_layout (may be null) = W | top | per_f | ROW
+//     window widths.
 extern "C" int bpp_debug_glv_op(bpp_ctx* ctx, int op, int window_bits, const uint32_t* in, size_t n, uint32_t* out,
                                 uint32_t* out_layout) {
     if (!ctx || !in || !out) return fail(BPP_E_ARG, "null argument");
@@ -187,31 +193,44 @@ extern "C" int bpp_debug_glv_op(bpp_ctx* ctx, int op, int window_bits, const uin
     if (op == 3 && (window_bits < 2 || window_bits > 20)) return fail(BPP_E_ARG, "window_bits must be in [2, 20]");
     return on_ctx_device(ctx, n, [&](auto cv) -> int {
         using C = decltype(cv);
-        if constexpr (!curve_has_glv<C>()) {
+        if (op == 3) {
+            constexpr bool GLV = fixed_glv<C>();
+            constexpr int NW = GLV ? GLV_HALF_WORDS : WIN_FULL_WORDS, ROW = GLV ? GLV_RECODE_ROW : VS_MAXW;
+            WinLayout L;
+            bool have;
+            if constexpr (GLV) {
+                uint32_t hmax[4];
+                glv_half_max<C>(hmax);
+                have = glv_layout(window_bits, C::Fr::BITS, hmax, L);
+            } else {
+                have = !win_layout_uniform(window_bits, C::Fr::MODW, C::Fr::BITS, L);
+            }
+            if (!have || L.W > (uint32_t)ROW) return fail(BPP_E_ARG, "no layout at this window_bits");
+            if (out_layout) {
+                out_layout[0] = L.W, out_layout[1] = L.top, out_layout[2] = L.per_f;
+                for (int j = 0; j < ROW; j++) out_layout[3 + j] = L.wc[j];
+            }
+            DevBuf din, dout;
+            if (int rc = upload(din, in, n * (GLV ? 4 : 8) * 4)) return rc;
+            HIPCHK(dout.alloc(n * ROW * 4));
+            if (n) {
+                hipLaunchKernelGGL((k_dbg_win_recode<NW, ROW>), dim3(cdiv(n, 64)), dim3(64), 0, nullptr, L, din.u32(), dout.u32(), n);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpy(out, dout.p, n * ROW * 4, hipMemcpyDeviceToHost));
+            }
+            return BPP_OK;
+        } else if constexpr (!curve_has_glv<C>()) {
             return fail(BPP_E_ARG, "this curve has no scalar split");
         } else {
             if (op != 2 && C::ID != 0) return fail(BPP_E_ARG, "BLS12-381 only");
-            const size_t in_words = op == 3 ? 4 : 8, out_words = op == 3 ? (size_t)GLV_MAXW : (size_t)GLV_SPLIT_OUT;
             DevBuf din, dout;
-            if (int rc = upload(din, in, n * in_words * 4)) return rc;
-            HIPCHK(dout.alloc(n * out_words * 4));
-            if (op == 3) {
-                if constexpr (C::ID == 0) {
-                    uint32_t hmax[4];
-                    glv_half_max<C>(hmax);
-                    GlvLayout L;
-                    if (!glv_layout(window_bits, C::Fr::BITS, hmax, L)) return fail(BPP_E_ARG, "no layout at this window_bits");
-                    if (out_layout) {
-                        out_layout[0] = L.W, out_layout[1] = L.top, out_layout[2] = L.per_f;
-                        for (int j = 0; j < GLV_MAXW; j++) out_layout[3 + j] = L.wc[j];
-                    }
-                    if (n) hipLaunchKernelGGL(k_dbg_glv_recode, dim3(cdiv(n, 64)), dim3(64), 0, nullptr, L, din.u32(), dout.u32(), n);
-                }
-            } else if (n) {
+            if (int rc = upload(din, in, n * 8 * 4)) return rc;
+            HIPCHK(dout.alloc(n * GLV_SPLIT_OUT * 4));
+            if (n) {
                 hipLaunchKernelGGL(k_dbg_glv_split<C>, dim3(cdiv(n, 64)), dim3(64), 0, nullptr, op, din.u32(), dout.u32(), n);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpy(out, dout.p, n * GLV_SPLIT_OUT * 4, hipMemcpyDeviceToHost));
             }
-            HIPCHK(hipGetLastError());
-            if (n) HIPCHK(hipMemcpy(out, dout.p, n * out_words * 4, hipMemcpyDeviceToHost));
             return BPP_OK;
         }
     });

@@ -25,49 +25,25 @@ static bool parse_words(const char* h, int nwords, uint32_t* out) {
     return true;
 }
 
-// the window layout of a verifier's tables, restated (csrc/host_util.hpp make_shape)
-struct Shape {
-    uint32_t c = 0, W = 0, half = 0, top = 0, per_f = 0;
-    uint32_t bias[10] = {};
-    uint8_t wc[GLV_MAXW] = {};
-    uint32_t went[GLV_MAXW] = {};
-    uint32_t off[GLV_MAXW] = {};   // bit offset of window j
-};
-
+// The window layout of a verifier's tables (csrc/host_util.hpp make_shape: the constructors of csrc/fixed_glv.hpp).  The
+// uniform layout's W, top and per_f are computed here once more, independently, and the constructor is held to them.
 template <class C>
-static bool make_shape(int c, Shape& s) {
+static bool make_shape(int c, WinLayout& s) {
     using Fr = typename C::Fr;
-    s.c = (uint32_t)c;
     if constexpr (commit_walk_glv<C>()) {
         uint32_t hmax[4];
         glv_half_max<C>(hmax);
-        GlvLayout L;
-        if (!glv_layout(c, Fr::BITS, hmax, L)) return false;
-        s.W = L.W;
-        s.top = L.top;
-        s.per_f = L.per_f;
-        for (uint32_t j = 0; j < L.W; j++) {
-            s.wc[j] = L.wc[j];
-            s.went[j] = L.went[j];
-            s.off[j] = L.off[j];
-        }
-        for (int t = 0; t < GLV_HALF_WORDS; t++) s.bias[t] = L.bias[t];
-        return true;
+        return glv_layout(c, Fr::BITS, hmax, s);
     } else {
-        s.W = (uint32_t)((Fr::BITS - 1) / c + 1);
-        s.half = 1u << (c - 1);
-        if (s.W > (uint32_t)GLV_MAXW) return false;
-        uint32_t v[10], carry = 0;   // r - 1 + bias: the top digit is what is left of it above bit c (W - 1)
-        for (uint32_t j = 0; j + 1 < s.W; j++) {
-            const uint32_t bit = s.c * j + (s.c - 1);
-            s.bias[bit >> 5] |= 1u << (bit & 31);
-        }
-        for (uint32_t j = 0; j < s.W; j++) {
-            s.off[j] = s.c * j;
-            s.went[j] = j * s.half;
+        const uint32_t W = (uint32_t)((Fr::BITS - 1) / c + 1), half = 1u << (c - 1);
+        if (W > (uint32_t)GLV_MAXW) return false;
+        uint32_t bias[10] = {}, v[10], carry = 0;   // r - 1 + bias: the top digit is what is left of it above bit c (W - 1)
+        for (uint32_t j = 0; j + 1 < W; j++) {
+            const uint32_t bit = (uint32_t)c * j + ((uint32_t)c - 1);
+            bias[bit >> 5] |= 1u << (bit & 31);
         }
         for (int t = 0; t < 10; t++) {
-            const uint64_t x = (uint64_t)(t < 8 ? Fr::MODW[t] : 0u) + s.bias[t] + carry;
+            const uint64_t x = (uint64_t)(t < 8 ? Fr::MODW[t] : 0u) + bias[t] + carry;
             v[t] = (uint32_t)x;
             carry = (uint32_t)(x >> 32);
         }
@@ -76,16 +52,29 @@ static bool make_shape(int c, Shape& s) {
             borrow = v[t] == 0 ? 1u : 0u;
             v[t] -= 1u;
         }
-        const uint32_t sh = s.c * (s.W - 1);
+        const uint32_t sh = (uint32_t)c * (W - 1);
         uint64_t top = 0;
+        bool fits = true;
         for (int t = 9; t >= 0; t--) {
             const int l = 32 * t - (int)sh;
-            if (l >= 32 && v[t]) return false;
+            if (l >= 32 && v[t]) fits = false;
             if (l > -32 && l < 32) top |= l >= 0 ? (uint64_t)v[t] << l : (uint64_t)(v[t] >> (-l));
         }
-        if (top == 0 || top >> 31) return false;
-        s.top = (uint32_t)top;
-        s.per_f = (s.W - 1) * s.half + s.top;
+        fits = fits && top != 0 && !(top >> 31);
+        if (win_layout_uniform(c, Fr::MODW, Fr::BITS, s)) {
+            if (fits) {
+                fprintf(stderr, "the uniform constructor refuses window_bits %d\n", c);
+                exit(1);
+            }
+            return false;
+        }
+        bool same = fits && s.W == W && s.top == (uint32_t)top && s.per_f == (W - 1) * half + (uint32_t)top && !memcmp(s.bias, bias, sizeof bias);
+        for (uint32_t j = 0; j < W && same; j++)
+            same = s.wc[j] == (j + 1 < W ? c : 0) && s.off[j] == c * j && s.went[j] == j * half;
+        if (!same) {
+            fprintf(stderr, "the uniform constructor's layout at window_bits %d differs from the restated one\n", c);
+            exit(1);
+        }
         return true;
     }
 }
@@ -100,11 +89,11 @@ static Aff<C> canon(const Aff<C>& a) {
 
 template <class C>
 struct Table {
-    Shape s;
+    WinLayout s;
     Aff<C> F[2];                               // g, h
     std::vector<Aff<C>> base[2];               // 2^(off_j) F_f
     std::unordered_map<size_t, Aff<C>> memo;   // entries built so far
-    explicit Table(const Shape& sh) : s(sh) {
+    explicit Table(const WinLayout& sh) : s(sh) {
         F[0] = aff_generator<C>();
         F[1] = canon(jac_to_aff(aff_dbl(F[0])));
         for (int f = 0; f < 2; f++) {
@@ -127,7 +116,7 @@ struct Table {
         uint32_t j = s.W - 1;
         while (j > 0 && s.went[j] > idx) j--;
         const uint32_t d = idx - s.went[j] + 1;
-        const uint32_t cnt = j + 1 < s.W ? (commit_walk_glv<C>() ? 1u << (s.wc[j] - 1) : s.half) : s.top;
+        const uint32_t cnt = win_entries(s, j);
         if (d > cnt) {
             fprintf(stderr, "entry %zu is past window %u\n", e, j);
             exit(1);
@@ -140,7 +129,7 @@ struct Table {
 
 template <class C>
 static int run(int c, bool amount64, const std::vector<uint64_t>& vs, const std::vector<std::vector<uint32_t>>& gs) {
-    Shape s;
+    WinLayout s;
     if (!make_shape<C>(c, s)) return 2;
     Table<C> T(s);
     long additions = 0, doublings = 0, cancellations = 0, sums = 0;

@@ -1,9 +1,12 @@
-// Host-side checks of the fixed-generator GLV path (csrc/ec.hpp glv_split_balanced / xyzz_mul_x_beta, csrc/fixed_glv.hpp),
-// compiled with g++; the kernels (k_fixed_msm, k_tbl_bases / k_tbl_fill) and the verifier's constructor run the same code.
-// tests/test_fixed_glv_cpu.py drives it and compares with Python integers.
+// Host-side checks of the fixed-generator tables' windows (csrc/fixed_glv.hpp) and of the GLV path over them (csrc/ec.hpp
+// glv_split_balanced / xyzz_mul_x_beta), compiled with g++; the kernels (k_fixed_msm, k_tbl_bases / k_tbl_fill) and the
+// verifier's constructor run the same code.  tests/test_fixed_glv_cpu.py drives it and compares with Python integers.
+// <c> is window_bits: alone the mixed-width layout of BLS12-381's halves, as <c>@secp256k1 or <c>@ed25519 the uniform
+// layout of that curve's whole scalars.
 //   split  <k>...        per scalar (64 hex digits): "s1 k1 s2 k2" (signs as 0 / 1, magnitudes as 32 hex digits)
-//   layout <c>           "W top per_f" then one line per window: "width offset first_entry", then the bias (40 hex digits)
-//   recode <c> <h>...    per half (32 hex digits): its W digits, lowest window first
+//   layout <c>           "W top per_f" then one line per window: "width offset first_entry", then the bias (40 hex digits;
+//                        uniform: 80)
+//   recode <c> <h>...    per half (32 hex digits; uniform: per scalar, 64 hex digits): its W digits, lowest window first
 //   group  <c> <k>...    the two-phase sum over a host-built table of the BLS12-381 generator F against double-and-add:
 //                        every scalar alone (k F), and every pair of neighbours in ONE accumulator, as two generators that
 //                        happen to be the same point ((k_i + k_{i+1}) F: the pairs reach P + P and P - P); and every scalar
@@ -14,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include "../../bulletproofsplus_amd/csrc/ed25519.hpp"
 #include "../../bulletproofsplus_amd/csrc/fixed_glv.hpp"
 using namespace bpp;
 using C = Bls12381;
@@ -29,10 +33,27 @@ static bool parse_words(const char* h, int nwords, uint32_t* out) {
     return true;
 }
 
-static bool layout_of(int c, GlvLayout& L) {
-    uint32_t hmax[4];
-    glv_half_max<C>(hmax);
-    return glv_layout(c, C::Fr::BITS, hmax, L);
+// carg: "<c>" or "<c>@<curve>"; NW: the words of a biased value under the layout
+static bool layout_of(const char* carg, WinLayout& L, int& NW) {
+    const int c = atoi(carg);
+    const char* at = strchr(carg, '@');
+    NW = at ? WIN_FULL_WORDS : GLV_HALF_WORDS;
+    if (!at) {
+        uint32_t hmax[4];
+        glv_half_max<C>(hmax);
+        return glv_layout(c, C::Fr::BITS, hmax, L);
+    }
+    if (c < 2 || c > 20) return false;   // csrc/host_util.hpp make_shape
+    if (!strcmp(at, "@secp256k1")) return !win_layout_uniform(c, Secp256k1::Fr::MODW, Secp256k1::Fr::BITS, L);
+    if (!strcmp(at, "@ed25519")) return !win_layout_uniform(c, Ed25519::Fr::MODW, Ed25519::Fr::BITS, L);
+    return false;
+}
+
+template <int NW>
+static void print_digits(const WinLayout& L, const uint32_t* k) {
+    uint32_t v[NW];
+    win_biased<NW>(k, L.bias, v);
+    for (uint32_t j = 0; j < L.W; j++) printf("%d%c", win_next_digit(v, win_width(L, j)), j + 1 < L.W ? ' ' : '\n');
 }
 
 static Aff<C> canon(const Aff<C>& a) {
@@ -79,14 +100,15 @@ static bool same_affine(const Jac<C>& a, const Jac<C>& b) {
     return x.x == y.x && x.y == y.y;
 }
 
-static int group(int c, int argc, char** argv) {
-    GlvLayout L;
-    if (!layout_of(c, L) || L.per_f > 4096) return 2;
+static int group(const char* carg, int argc, char** argv) {
+    WinLayout L;
+    int NW;
+    if (!layout_of(carg, L, NW) || NW != GLV_HALF_WORDS || L.per_f > 4096) return 2;
     const Aff<C> F = aff_generator<C>();
     std::vector<Aff<C>> table(L.per_f);
     Jac<C> base = jac_from_aff(F);
     for (uint32_t j = 0; j < L.W; j++) {   // T[j][d] = d 2^(off_j) F
-        const uint32_t cnt = j + 1 < L.W ? 1u << (L.wc[j] - 1) : L.top;
+        const uint32_t cnt = win_entries(L, j);
         const Aff<C> b = canon(jac_to_aff(base));
         Jac<C> run = base;
         for (uint32_t d = 1; d <= cnt; d++) {
@@ -148,22 +170,25 @@ int main(int argc, char** argv) {
         return 0;
     }
     if (argc < 3) return 2;
-    const int c = atoi(argv[2]);
-    if (!strcmp(mode, "group")) return group(c, argc - 3, argv + 3);
-    GlvLayout L;
-    if (!layout_of(c, L)) return 3;
+    if (!strcmp(mode, "group")) return group(argv[2], argc - 3, argv + 3);
+    WinLayout L;
+    int NW;
+    if (!layout_of(argv[2], L, NW)) return 3;
     if (!strcmp(mode, "layout")) {
         printf("%u %u %u\n", L.W, L.top, L.per_f);
         for (uint32_t j = 0; j < L.W; j++) printf("%u %u %u\n", (unsigned)L.wc[j], (unsigned)L.off[j], L.went[j]);
-        printf("%08x%08x%08x%08x%08x\n", L.bias[4], L.bias[3], L.bias[2], L.bias[1], L.bias[0]);
+        for (int t = NW - 1; t >= 0; t--) printf("%08x", L.bias[t]);
+        printf("\n");
         return 0;
     }
     if (!strcmp(mode, "recode")) {
         for (int a = 3; a < argc; a++) {
-            uint32_t h[4], v[GLV_HALF_WORDS];
-            if (!parse_words(argv[a], 4, h)) return 2;
-            glv_biased(h, L.bias, v);
-            for (uint32_t j = 0; j < L.W; j++) printf("%d%c", glv_next_digit(v, L.wc[j]), j + 1 < L.W ? ' ' : '\n');
+            uint32_t k[8];
+            if (!parse_words(argv[a], NW == GLV_HALF_WORDS ? 4 : 8, k)) return 2;
+            if (NW == GLV_HALF_WORDS)
+                print_digits<GLV_HALF_WORDS>(L, k);
+            else
+                print_digits<WIN_FULL_WORDS>(L, k);
         }
         return 0;
     }

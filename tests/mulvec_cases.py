@@ -90,7 +90,7 @@ def recode_mixed(h, widths, offs, bias):
 
 
 def recode_uniform(k, c, W):
-    """the digits of a scalar under the unsplit layout (csrc/host_util.hpp make_shape, k_fixed_msm): W - 1 signed windows
+    """the digits of a scalar under the unsplit layout (csrc/fixed_glv.hpp win_layout_uniform, k_fixed_msm): W - 1 signed windows
     of c bits, then what is left"""
     half = 1 << (c - 1)
     v = k + sum(half << (c * j) for j in range(W - 1))
@@ -473,8 +473,8 @@ GPU_CASES = [
     # NF = 258: three blocks per proof and no spreading; two blocks (G = 1 and 2 left-over generators); one block (G = 2 and
     # 2 left-over) -- the last two in the one-lane-per-proof form
     ("bls12_381", 16, 8, 4, 3, 0, 3, 3), ("secp256k1", 16, 8, 4, 3, 0, 3, 3),
-    ("bls12_381", 16, 8, 4, 1100, 0, 0, 2), ("secp256k1", 16, 8, 4, 1100, 0, 0, 2),
-    ("bls12_381", 16, 8, 4, 2100, 0, 0, 1), ("secp256k1", 16, 8, 4, 2100, 0, 0, 1),
+    ("bls12_381", 16, 8, 4, 1100, 0, 0, 2), ("secp256k1", 16, 8, 4, 1100, 0, 0, 2), ("ed25519", 16, 8, 4, 1100, 0, 0, 2),
+    ("bls12_381", 16, 8, 4, 2100, 0, 0, 1), ("secp256k1", 16, 8, 4, 2100, 0, 0, 1), ("ed25519", 16, 8, 4, 2100, 0, 0, 1),
     # eight lanes per proof; 257 and 300 leave a last block with one and with twelve proofs
     ("bls12_381", 8, 2, 5, 257, 0, 2, 1), ("bls12_381", 8, 2, 5, 300, 0, 2, 1),
     ("ed25519", 8, 2, 5, 257, 0, 2, 1), ("ed25519", 8, 2, 5, 300, 0, 2, 1),

@@ -1,7 +1,7 @@
-"""CPU: the fixed-generator GLV path (csrc/ec.hpp glv_split_balanced, csrc/fixed_glv.hpp) as a host build (g++) of the
-headers the kernels compile, against Python integers and against plain double-and-add
-(tests/host/fixed_glv_host_test.cpp): the balanced split, the window layouts and their digit recoding, and the two-phase
-sum with the endomorphism applied once to the accumulator."""
+"""CPU: the windows of the fixed-generator tables (csrc/fixed_glv.hpp) and the GLV path over them (csrc/ec.hpp
+glv_split_balanced) as a host build (g++) of the headers the kernels compile, against Python integers and against plain
+double-and-add (tests/host/fixed_glv_host_test.cpp): the balanced split, the window layouts of all three curves and their
+digit recoding, and the two-phase sum with the endomorphism applied once to the accumulator."""
 
 import os
 import random
@@ -9,6 +9,7 @@ import subprocess
 
 import pytest
 
+import mulvec_cases as M
 from glv_cases import HALF_MAX, R, Z2, edges as _edges, recode_halves
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -89,6 +90,34 @@ def test_layout_and_recoding(exe, c):
         assert sum(dj << o for dj, o in zip(d, offs)) == h, hex(h)
         assert all(-(1 << (w - 1)) <= dj < (1 << (w - 1)) for dj, w in zip(d, widths)), hex(h)
         assert 0 <= d[-1] <= top, hex(h)
+
+
+@pytest.mark.parametrize("c", [2, 3, 4, 13, 16])   # 2 and 3: more than 64 windows
+@pytest.mark.parametrize("curve", ["secp256k1", "ed25519"])
+def test_uniform_layout_and_recoding(exe, curve, c):
+    """win_layout_uniform against mulvec_cases' restatement, and win_biased<10> / win_next_digit<10> on whole scalars"""
+    sh = M.Shape(curve, 2, 2, c)
+    r, half = sh.r, 1 << (c - 1)
+    W, top, per_f, wins, bias = _layout(exe, "%d@%s" % (c, curve))
+    assert W == sh.W == (r.bit_length() - 1) // c + 1 and (W > 64) == (c < 4)
+    assert wins == [(c if j + 1 < W else 0, c * j, j * half) for j in range(W)]
+    assert bias == sum(half << (c * j) for j in range(W - 1))
+    assert top == sh.top == (r - 1 + bias) >> (c * (W - 1))
+    assert per_f == (W - 1) * half + top
+    offs = [c * j for j in range(W)]
+    rng = random.Random(29 + c)
+    ks = [k for k, _ in M.digit_scalars(curve, c)] + [0, 1, r - 1] + [rng.randrange(r) for _ in range(5000)]
+    out = _run(exe, (["recode", "%d@%s" % (c, curve)], ["%064x" % k for k in ks]), chunk=1000)
+    assert len(out) == len(ks)
+    tops = set()
+    for k, line in zip(ks, out):
+        d = [int(x) for x in line.split()]
+        assert d == M.recode_uniform(k, c, W), hex(k)
+        assert sum(dj << o for dj, o in zip(d, offs)) == k, hex(k)
+        assert all(-half <= dj < half for dj in d[:-1]), hex(k)
+        assert 0 <= d[-1] <= top, hex(k)
+        tops.add(d[-1])
+    assert top in tops   # r - 1 reaches it
 
 
 def test_table_bytes_fall_with_window_bits(exe):

@@ -2,8 +2,8 @@
   * xyzz_madd_lazy on raw accumulator images in every representation its invariant allows (tests/madd_cases.py, which
     test_field_raw_cpu.py runs on the host build), against pyref's group law.
   * the scalar splits (csrc/ec.hpp glv_split, glv_split_balanced, glv_split_signed) and the digit recoding of the
-    fixed-generator tables (csrc/fixed_glv.hpp glv_biased, glv_next_digit) on the edge lists the host builds are checked
-    on (tests/glv_cases.py), against Python integers."""
+    fixed-generator tables (csrc/fixed_glv.hpp win_biased, win_next_digit) on the edge lists the host builds are
+    checked on (tests/glv_cases.py; uniform layouts: tests/mulvec_cases.py digit_scalars), against Python integers."""
 
 import random
 
@@ -124,3 +124,46 @@ def test_recoding_on_device(c):
         assert sum(dj << o for dj, o in zip(d, offs)) == h, hex(h)
         assert all(-(1 << (w - 1)) <= dj < (1 << (w - 1)) for dj, w in zip(d, widths)), hex(h)
         assert 0 <= d[-1] <= top, hex(h)
+
+
+UNIFORM_ROW = 128   # csrc/kernels.hpp VS_MAXW: the hook's row on the curves whose tables take whole scalars
+
+
+@pytest.mark.parametrize("c", [3, 4, 16])
+@pytest.mark.parametrize("curve", ["secp256k1", "ed25519"])
+def test_recoding_on_device_uniform(curve, c):
+    """the uniform layout (csrc/fixed_glv.hpp win_layout_uniform) and the recoding of whole scalars as the device
+    compiles them: the identities of test_fixed_glv_cpu.py test_uniform_layout_and_recoding"""
+    need_gpu()
+    import bulletproofsplus_amd as B
+    from bulletproofsplus_amd import _lib
+    import mulvec_cases as M
+    a = B.Arith.init(curve)
+    sh = M.Shape(curve, 2, 2, c)
+    r, W = sh.r, sh.W
+
+    def recode(ks):
+        k = _words(ks, 8)
+        out = np.full((max(len(ks), 1), UNIFORM_ROW), 0x7FFFFFFF, dtype=np.uint32)
+        lay = np.zeros(3 + UNIFORM_ROW, dtype=np.uint32)
+        assert _lib.lib().bpp_debug_glv_op(a.handle, 3, c, k.ctypes.data, len(ks), out.ctypes.data, lay.ctypes.data) == 0
+        return out.view(np.int32), lay
+
+    _, lay = recode([])
+    assert (int(lay[0]), int(lay[1])) == (W, sh.top)
+    assert int(lay[2]) == (W - 1) * sh.half + sh.top
+    assert [int(w) for w in lay[3:]] == [c] * (W - 1) + [0] * (UNIFORM_ROW - W + 1)
+    offs = [c * j for j in range(W)]
+    rng = random.Random(31 + c)
+    ks = [k for k, _ in M.digit_scalars(curve, c)] + [0, 1, r - 1] + [rng.randrange(r) for _ in range(2000)]
+    out, _ = recode(ks)
+    assert not out[:, W:].any()
+    tops = set()
+    for k, row in zip(ks, out):
+        d = [int(x) for x in row[:W]]
+        assert d == M.recode_uniform(k, c, W), hex(k)
+        assert sum(dj << o for dj, o in zip(d, offs)) == k, hex(k)
+        assert all(-sh.half <= dj < sh.half for dj in d[:-1]), hex(k)
+        assert 0 <= d[-1] <= sh.top, hex(k)
+        tops.add(d[-1])
+    assert sh.top in tops   # r - 1 reaches it

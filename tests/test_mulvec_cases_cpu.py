@@ -255,10 +255,11 @@ def test_gpu_cases_name_every_geometry_class():
         assert n * (mv or m) <= 256 and (mv == 0 or (mv < m and mv & (mv - 1) == 0))
     assert forms[3] == {"bls12_381", "secp256k1", "ed25519"}
     assert forms[1] == {"bls12_381", "ed25519"} == forms[2]
-    assert forms[0] == {"bls12_381", "secp256k1"}
+    assert forms[0] == {"bls12_381", "secp256k1", "ed25519"}
     assert all(count % 128 for _, _, _, _, count, _, form, _ in M.GPU_CASES if form == 0)
     nf258 = {(cname, blocks) for cname, n, m, c, count, mv, form, blocks in M.GPU_CASES if 2 * n * m + 2 == 258}
-    assert nf258 == {(cn, bl) for cn in ("bls12_381", "secp256k1") for bl in (1, 2, 3)}
+    # edwards25519 too reaches the left-over steps (two and one block: 2 left-over generators)
+    assert nf258 == {(cn, bl) for cn in ("bls12_381", "secp256k1") for bl in (1, 2, 3)} | {("ed25519", 1), ("ed25519", 2)}
     # BLS12-381 at NF = 258, W = 32, two blocks: 2 left-over generators x 2 halves x 32 windows = 128 entries over 256 lanes
     assert M.Shape("bls12_381", 16, 8, 4).W == 32
     parities = {M.Shape("bls12_381", n, m, c).W % 2 for cn, n, m, c, *_ in M.GPU_CASES if cn == "bls12_381"}
