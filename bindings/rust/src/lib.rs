@@ -604,6 +604,55 @@ impl BatchVerifier {
         assert!(rc == 0, "bpp_range_scan_serialized_mixed: {}", rc);
         Ok(status.iter().zip(masks.chunks(4)).map(|(&s, c)| (s, PrimeFieldElem([c[0], c[1], c[2], c[3]]))).collect())
     }
+    /// `scan_serialized_mixed` under MANY keys in one call (include/bpp_amd.h: bpp_range_scan_serialized_mixed_keys): the
+    /// decode, the membership test, the challenges and the inversions run once, the key-dependent part per (key, proof)
+    /// pair.  The blinding index of proof i (index[i], or index_base + i) is shared by all keys; `amounts` is key-major,
+    /// keys.len() x ms.len() (None: nothing is confirmed).  Result: one row per key of (status, Gamma) per proof, the
+    /// status words of `scan_serialized_mixed`.  Every key is a view key; a scan is NOT a verification.
+    pub fn scan_serialized_mixed_keys(&self, proofs: &[u8], commitments: &[u8], ms: &[u32], amount64: bool, keys: &[[u8; 32]],
+                                      index_base: u64, index: Option<&[u64]>, amounts: Option<&[u64]>)
+                                      -> Result<Vec<Vec<(u32, PrimeFieldElem)>>, ProofError> {
+        let n = 1usize << (self.k - self.m.trailing_zeros() as usize);
+        let cb = unsafe { ffi::bpp_point_compressed_bytes(ffi::BPP_BLS12_381_G1) };
+        let (mut pbytes, mut cbytes) = (0usize, 0usize);
+        for &mi in ms {
+            let mi = mi as usize;
+            if mi == 0 || !mi.is_power_of_two() || mi > self.m {
+                return Err(ProofError::FormatError);
+            }
+            pbytes += unsafe { ffi::bpp_proof_bytes(ffi::BPP_BLS12_381_G1, n, mi) };
+            cbytes += mi * cb;
+        }
+        let pairs = match keys.len().checked_mul(ms.len()) {
+            Some(p) if p <= (0x7fff_ffff / 64) => p,
+            _ => return Err(ProofError::FormatError),
+        };
+        if pbytes != proofs.len() || cbytes != commitments.len() || index.map_or(false, |x| x.len() != ms.len())
+            || amounts.map_or(false, |x| x.len() != pairs) {
+            return Err(ProofError::FormatError);
+        }
+        if pairs == 0 {
+            return Ok(vec![Vec::new(); keys.len()]);
+        }
+        let flags = ffi::BPP_SER_TRANSCRIPT | if amount64 { ffi::BPP_PROVE_AMOUNT64 } else { 0 };
+        let mut packed: Vec<u8> = keys.iter().flat_map(|k| k.iter().copied()).collect();
+        let mut masks = vec![0u64; pairs * 4];
+        let mut status = vec![0u32; pairs];
+        let rc = unsafe {
+            ffi::bpp_range_scan_serialized_mixed_keys(self.handle, proofs.as_ptr(), commitments.as_ptr(), ms.as_ptr(), ms.len(),
+                                                      flags, packed.as_ptr(), keys.len(), index_base,
+                                                      index.map_or(std::ptr::null(), |x| x.as_ptr()),
+                                                      amounts.map_or(std::ptr::null(), |x| x.as_ptr()), masks.as_mut_ptr(),
+                                                      status.as_mut_ptr())
+        };
+        for b in packed.iter_mut() {
+            unsafe { std::ptr::write_volatile(b, 0) };   // the packed copy of the keys made here
+        }
+        assert!(rc == 0, "bpp_range_scan_serialized_mixed_keys: {}", rc);
+        Ok(status.chunks(ms.len()).zip(masks.chunks(4 * ms.len()))
+            .map(|(st, mk)| st.iter().zip(mk.chunks(4)).map(|(&s, c)| (s, PrimeFieldElem([c[0], c[1], c[2], c[3]]))).collect())
+            .collect())
+    }
 }
 
 /// The cuts of a batch over `world` shards (include/bpp_amd.h: bpp_shard_cuts): shard r takes proofs

@@ -1362,6 +1362,76 @@ class BatchVerifier:
             "bpp_range_scan_serialized_mixed")
         return status, [wire_to_int(x) for x in masks]
 
+    def scan_keys_workspace_bytes(self, ms, n_keys: int) -> int:
+        """bytes of device workspace scan_serialized_mixed_keys_device needs (0: an m_i is not taken, or n_keys x count is
+        over the bound)"""
+        m = self._ms(ms)
+        return _lib.lib().bpp_scan_serialized_mixed_keys_workspace_bytes(self.handle, _ptr(m) if len(m) else None, len(m), n_keys)
+
+    def scan_serialized_mixed_keys_device(self, d_proofs: int, d_commitments: int, ms, d_keys: int, n_keys: int,
+                                          d_out_masks: int, d_status: int, d_workspace: int, workspace_bytes: int,
+                                          stream: int = 0, transcript: bool = True, uncompressed: bool = False,
+                                          amount64: bool = False, index_base: int = 0, d_index: int = 0, d_amounts: int = 0):
+        """scan_serialized_mixed_device for n_keys view keys in one call: decoder, membership test, challenges and the
+        inversions once, the key-dependent part per (key, proof) pair.  d_keys: n_keys x 32 bytes; the blinding index of
+        proof i (d_index[i] or index_base + i) is shared by all keys; d_amounts (n_keys, count) u64, d_out_masks
+        (n_keys, count, 4) u64 and d_status (n_keys, count) u32 are key-major.  The status words are the single-key call's.
+        Every key is a view key; a scan is not a verification."""
+        m = self._ms(ms)
+        check(_lib.lib().bpp_range_scan_serialized_mixed_keys_device(
+            self.handle, d_proofs, d_commitments, _ptr(m) if len(m) else None, len(m),
+            (1 if transcript else 0) | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0), d_keys or None, n_keys,
+            ctypes.c_uint64(index_base), d_index or None, d_amounts or None, d_out_masks, d_status, d_workspace,
+            workspace_bytes, stream or None), "bpp_range_scan_serialized_mixed_keys_device")
+
+    def scan_serialized_mixed_keys(self, proofs, commitments, ms=None, keys=(), transcript: bool = True,
+                                   uncompressed: bool = False, amount64: bool = False, index_base: int = 0, index=None,
+                                   amounts=None):
+        """proofs, commitments, ms: as scan_serialized_mixed; keys: a list of 32-byte strings; index: None or one blinding
+        index per proof, shared by all keys; amounts: None or K x count candidate amounts (amounts[j][i]: proof i under key
+        j) -> (status (K, count) u32, masks: K lists of count ints) (bpp_range_scan_serialized_mixed_keys)"""
+        def flat(x):
+            return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
+        raw, cm = flat(proofs), flat(commitments)
+        version = 2 if uncompressed else 1
+        m = proofs_scan(self.arith, self.n, raw, version) if ms is None else self._ms(ms)
+        count = len(m)
+        keys = [bytes(k) for k in keys]
+        if any(len(k) != 32 for k in keys):
+            raise RuntimeError("scan_serialized_mixed_keys: every key is 32 bytes")
+        nk = len(keys)
+        if all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m):
+            pb = uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)
+            need = sum(proof_bytes(self.arith, self.n, int(x), version) for x in m)
+            if len(raw) != need:
+                raise RuntimeError("scan_serialized_mixed_keys: %d bytes of proofs, the shapes in ms need %d" % (len(raw), need))
+            if len(cm) != int(m.sum()) * pb:
+                raise RuntimeError("scan_serialized_mixed_keys: ms[i] commitments per proof")
+        idx = None
+        if index is not None:
+            idx = np.ascontiguousarray(np.asarray([int(x) for x in index], dtype=np.uint64))
+            if len(idx) != count:
+                raise RuntimeError("scan_serialized_mixed_keys: one blinding index per proof")
+        am = None
+        if amounts is not None:
+            am = np.ascontiguousarray(np.asarray([[int(x) for x in row] for row in amounts], dtype=np.uint64).reshape(-1))
+            if len(am) != nk * count:
+                raise RuntimeError("scan_serialized_mixed_keys: K x count candidate amounts")
+        kb = np.frombuffer(b"".join(keys), dtype=np.uint8).copy() if nk else None
+        masks = np.zeros((nk, count, 4), dtype=np.uint64)
+        status = np.zeros((nk, count), dtype=np.uint32)
+        some = nk > 0 and count > 0
+        check(_lib.lib().bpp_range_scan_serialized_mixed_keys(
+            self.handle, _ptr(raw) if len(raw) else None, _ptr(cm) if len(cm) else None, _ptr(m) if count else None, count,
+            (1 if transcript else 0) | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0),
+            _ptr(kb) if kb is not None else None, nk, ctypes.c_uint64(index_base), _ptr(idx) if idx is not None else None,
+            _ptr(am) if am is not None and some else None, _ptr(masks) if some else None, _ptr(status) if some else None),
+            "bpp_range_scan_serialized_mixed_keys")
+        if kb is not None:
+            kb[:] = 0   # the packed copy of the keys made here
+        return status, [[wire_to_int(x) for x in row] for row in masks]
+
 
 def shard_cuts(ms, count: int, world: int) -> np.ndarray:
     """bpp_shard_cuts: the world + 1 cuts of a batch of `count` proofs over `world` shards, shard r taking proofs

@@ -10,6 +10,7 @@
 #include "impl_verify.hpp"
 #include "impl_wip.hpp"
 #include "recover.hpp"
+#include "recover_keys.hpp"
 
 using namespace bpp;
 
@@ -1405,6 +1406,70 @@ extern "C" int bpp_range_scan_serialized_mixed(bpp_verifier* v, const uint8_t* p
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
         return RecoverImpl<decltype(cv)>::scan_serialized_mixed_host(v, proofs, commitments, m_of, count, flags, blind_key,
                                                                      index_base, index, blinding, amounts, out_masks, out_status);
+    });
+}
+
+// ---- scanning under many keys (recover_keys.hpp): the front and the inversions once, n_keys x count pairs ----
+namespace {
+// n_keys x count within the bound the other entries put on count alone, without forming a product that can wrap
+bool pairs_bounded(size_t n_keys, size_t count) noexcept {
+    const size_t bound = 0x7fffffffu / 64;
+    return n_keys <= bound && count <= bound && (n_keys == 0 || count <= bound / n_keys);
+}
+// what the many-key scan can answer before the engine handle is read (runs under the guard itself)
+int scan_keys_args(const uint32_t* m_of, size_t count, size_t n_keys, int flags) noexcept {
+    return guarded([&]() -> int {
+        if (!pairs_bounded(n_keys, count)) return fail(BPP_E_ARG, "n_keys x count too large for one launch");
+        for (size_t i = 0; i < count; i++)
+            if (m_of[i] == 0 || (m_of[i] & (m_of[i] - 1)))
+                return fail(BPP_E_ARG, "m_of[" + std::to_string(i) + "] = " + std::to_string(m_of[i]) + ": not a power of two");
+        if (!(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
+        return BPP_OK;
+    });
+}
+}  // namespace
+
+extern "C" size_t bpp_scan_serialized_mixed_keys_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count,
+                                                                 size_t n_keys) {
+    if ((count && !m_of) || !pairs_bounded(n_keys, count) || !m_of_wellformed(m_of, count)) return 0;
+    return size_for(v, [&](auto cv) { return RecoverKeysImpl<decltype(cv)>::workspace_bytes(v, m_of, count); });
+}
+
+extern "C" int bpp_range_scan_serialized_mixed_keys_device(bpp_verifier* v, const void* d_proofs, const void* d_commitments,
+                                                           const uint32_t* m_of, size_t count, int flags, const uint8_t* d_keys,
+                                                           size_t n_keys, uint64_t index_base, const uint64_t* d_index,
+                                                           const uint64_t* d_amounts, uint64_t* d_out_masks, uint32_t* d_status,
+                                                           void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (!v) return fail(BPP_E_ARG, "null argument");
+    if (flags & ~SCAN_FLAGS) return fail(BPP_E_ARG, "unknown flag");
+    if (count == 0 || n_keys == 0) return BPP_OK;
+    if (!d_proofs || !d_commitments || !m_of || !d_keys || !d_out_masks || !d_status || !d_workspace)
+        return fail(BPP_E_ARG, "null argument");
+    if (reinterpret_cast<uintptr_t>(d_keys) & 3) return fail(BPP_E_ARG, "d_keys must be 4-byte aligned");
+    if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
+    if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return RecoverKeysImpl<decltype(cv)>::scan(v, static_cast<const uint8_t*>(d_proofs),
+                                                   static_cast<const uint8_t*>(d_commitments), m_of, count,
+                                                   (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u, (flags & BPP_PROVE_AMOUNT64) != 0,
+                                                   d_keys, n_keys, index_base, d_index, d_amounts, d_out_masks, d_status,
+                                                   d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    });
+}
+
+// host buffers in (keys, index and amounts included), host masks and statuses out: the device path above between copies
+extern "C" int bpp_range_scan_serialized_mixed_keys(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments,
+                                                    const uint32_t* m_of, size_t count, int flags, const uint8_t* keys,
+                                                    size_t n_keys, uint64_t index_base, const uint64_t* index,
+                                                    const uint64_t* amounts, uint64_t* out_masks, uint32_t* out_status) {
+    if (!v) return fail(BPP_E_ARG, "null argument");
+    if (flags & ~SCAN_FLAGS) return fail(BPP_E_ARG, "unknown flag");
+    if (count == 0 || n_keys == 0) return BPP_OK;
+    if (!proofs || !commitments || !m_of || !keys || !out_masks || !out_status) return fail(BPP_E_ARG, "null argument");
+    if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return RecoverKeysImpl<decltype(cv)>::scan_host(v, proofs, commitments, m_of, count, flags, keys, n_keys, index_base,
+                                                        index, amounts, out_masks, out_status);
     });
 }
 

@@ -1,0 +1,326 @@
+// recover_keys.hpp -- scanning a block of containers under MANY blinding keys in one call
+// (bpp_range_scan_serialized_mixed_keys*): the front of the single-key scan (recover.hpp) once, the inversions once per
+// proof, and per (key, proof) pair only what depends on the key.  recover_coeffs.hpp has the arithmetic.  One
+// instantiation per curve (tu_recover_keys_*.hip).
+//
+// k_recover_coeffs: k_recover_masks's mapping -- a proof is RECOVER_GROUP = 16 lanes, lane t inverts for term t (t < k:
+// e_t^2; t = k: e^2 y^(nm+1) [z^2]) -- but what is written is the proof's 2k + 4 coefficients, by gathered position, and
+// a flag for a zero challenge.  Nothing of a key is involved: the coefficients are public and live in the workspace, as
+// the field's own limbs (Montgomery form, COEFF_WORDS words each) so that a pair lane multiplies what it loads.
+// k_scan_keys: a pair is SCAN_GROUP = 8 lanes, eight pairs per wave; lane s expands live slots s, s + 8, s + 16 (alpha,
+// delta, eta, d_L, d_R: 2k + 3 of them; r and s have coefficient zero and are never hashed), multiplies each by its
+// coefficient, the group sums by a 3-step butterfly of wave_shfl and lane 0 adds A0 and stores Gamma and the status at
+// [key][caller position].  The key's words come from the caller's buffer into registers; no LDS, no scratch, no atomics:
+// nothing derived from a key but Gamma reaches memory.  Pairs are numbered proof-major (pair = position * n_keys + key),
+// so the groups of a wave read one proof's coefficients.
+// k_scan_keys_confirm: one lane per (key, single-output proof) pair with a candidate amount: k_recover_confirm's walk,
+// compared with the decoded V_0 projectively (walk_equals_wire): no inversion in Fp.
+#pragma once
+#include "recover.hpp"
+#include "recover_coeffs.hpp"
+
+namespace bpp {
+
+constexpr unsigned SCAN_GROUP = 8;   // lanes per (key, proof) pair
+constexpr unsigned SCAN_BLOCK = 64;
+// a coefficient in memory: the NL limbs of the scalar field, padded to whole 16-byte granules
+template <class P>
+constexpr int coeff_words() {
+    return (P::NL + 3) & ~3;
+}
+
+template <class P>
+__device__ __forceinline__ Fe<P> coeff_ldg(const uint32_t* __restrict__ p) {
+    uint32_t w[coeff_words<P>()];
+    ld_words<coeff_words<P>()>(p, w);
+    Fe<P> r;
+#pragma unroll
+    for (int i = 0; i < P::NL; i++) r.l[i] = w[i];
+    return r;
+}
+template <class P>
+__device__ __forceinline__ void coeff_stg(uint32_t* __restrict__ p, const Fe<P>& a) {
+    uint32_t w[coeff_words<P>()];
+#pragma unroll
+    for (int i = 0; i < coeff_words<P>(); i++) w[i] = i < P::NL ? a.l[i] : 0u;
+    st_words<coeff_words<P>()>(p, w);
+}
+
+// One class: `count` proofs of shape (n, m), k = log2(n m); triples and challenge blocks (3 + k scalars per proof) by
+// launch position.  coeffs: count x coeff_elems(k) x COEFF_WORDS; bad[i] = 1 after a zero challenge, else 0.
+template <class C>
+__global__ void __launch_bounds__(RECOVER_BLOCK) k_recover_coeffs(uint32_t k, uint32_t m, const uint32_t* __restrict__ triples,
+                                                                  const uint32_t* __restrict__ ch, uint32_t* __restrict__ coeffs,
+                                                                  uint32_t* __restrict__ bad_out, size_t count) {
+    using P = typename C::Fr;
+    using F = Fe<P>;
+    constexpr int CW = coeff_words<P>();
+    const uint32_t lane = threadIdx.x & 63u, t = lane & (RECOVER_GROUP - 1);
+    const size_t g = ((size_t)blockIdx.x * RECOVER_BLOCK + threadIdx.x) / RECOVER_GROUP;
+    const bool live = g < count;
+    const size_t p = live ? g : count - 1;   // an idle group of the last wave repeats the last proof and stores nothing
+    const uint32_t* pch = ch + p * (size_t)(3 + k) * 8;
+    F e = F::zero(), e2 = F::zero(), den = F::zero();
+    bool ok;
+    const F x = coeff_term_x<P>(k, m, t, pch, e, e2, den, ok);
+    const F xinv = fe_inv(x);
+    F D = F::one(), head[4];
+    if (t == k) {
+        uint32_t w[8];
+        ld_words<8>(triples + p * 24 + 16, w);
+        coeff_head(fe_from_canonical<P>(w), e, e2, den, xinv, D, head);
+    }
+    D = wave_shfl(D, (int)((lane & ~(RECOVER_GROUP - 1)) + k));
+    uint32_t bad = ok ? 0u : 1u;
+#pragma unroll 1
+    for (int d = RECOVER_GROUP >> 1; d >= 1; d >>= 1) bad |= (uint32_t)__shfl((int)bad, (int)(lane ^ d), 64);
+    if (!live) return;
+    uint32_t* o = coeffs + p * (size_t)coeff_elems(k) * CW;
+    if (t < k) {
+        F cL, cR;
+        coeff_round(D, x, xinv, cL, cR);
+        coeff_stg<P>(o + (size_t)(4 + t) * CW, cL);
+        coeff_stg<P>(o + (size_t)(4 + k + t) * CW, cR);
+    } else if (t == k) {
+#pragma unroll
+        for (int h = 0; h < 4; h++) coeff_stg<P>(o + (size_t)h * CW, head[h]);
+        bad_out[p] = bad;
+    }
+}
+
+// one launch of the pair kernels: `count` proofs of one class (rx: their entries, by launch position) under n_keys keys
+struct ScanKeysJob {
+    uint32_t k;
+    uint32_t n_keys;
+    const uint32_t* keys;        // the CALLER's buffer: n_keys x 8 little-endian words
+    uint64_t index_base;
+    const uint64_t* index;       // by caller position, or null: index_base + caller position
+    const uint32_t* rx;
+    const uint32_t* coeffs;
+    const uint32_t* bad;
+    const uint32_t* status;      // the decoder's, by launch position
+    uint32_t* out_masks;         // n_keys x total x 8 words, [key][caller position]
+    uint32_t* out_status;        // n_keys x total
+    size_t count, total;         // proofs of this class, proofs of the call
+};
+
+template <class C>
+__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_keys(ScanKeysJob j) {
+    using P = typename C::Fr;
+    using F = Fe<P>;
+    constexpr int CW = coeff_words<P>();
+    const uint32_t lane = threadIdx.x & 63u, s = lane & (SCAN_GROUP - 1);
+    const size_t q = ((size_t)blockIdx.x * SCAN_BLOCK + threadIdx.x) / SCAN_GROUP;
+    if (q >= j.count * j.n_keys) return;   // a whole group: the exchanges below stay inside a group
+    const size_t p = q / j.n_keys;
+    const uint32_t key_no = (uint32_t)(q - p * j.n_keys);
+    const size_t caller = j.rx[p * RX_WORDS + RX_CALLER];
+    const size_t at = (size_t)key_no * j.total + caller;
+    const bool rejected = j.status[p] != 0;
+    if (rejected || j.bad[p]) {   // before the key is read: the decoder's FormatError for every key; Gamma undefined
+        if (s == 0) {
+            const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            st_words<8>(j.out_masks + at * 8, z);
+            j.out_status[at] = rejected ? (uint32_t)BPP_FORMAT_ERROR : (uint32_t)BPP_SCAN_UNCONFIRMED;
+        }
+        return;
+    }
+    uint32_t key[8];
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = j.keys[(size_t)key_no * 8 + w];
+    const uint64_t idx = j.index ? j.index[caller] : j.index_base + caller;
+    const uint32_t nl = coeff_live_slots(j.k);
+    const uint32_t* cf = j.coeffs + p * (size_t)coeff_elems(j.k) * CW;
+    F sum = F::zero();
+#pragma unroll 1
+    for (uint32_t l0 = 0; l0 < nl; l0 += SCAN_GROUP) {
+        const uint32_t l = l0 + s;
+        const bool mine = l < nl;
+        const uint32_t lc = mine ? l : 0u;   // an idle lane of the last stride runs the group's instruction stream on slot 0
+        const F share = coeff_slot_share<P>(key, idx, coeff_live_slot(lc), coeff_ldg<P>(cf + (size_t)(1 + lc) * CW));
+        sum = fe_add(sum, mine ? share : F::zero());
+    }
+#pragma unroll 1
+    for (int d = SCAN_GROUP >> 1; d >= 1; d >>= 1) sum = fe_add(sum, wave_shfl(sum, (int)(lane ^ d)));
+    if (s == 0) {
+        uint32_t o[8];
+        fe_to_canonical(fe_add(sum, coeff_ldg<P>(cf)), o);
+        st_words<8>(j.out_masks + at * 8, o);
+        j.out_status[at] = (uint32_t)BPP_SCAN_UNCONFIRMED;
+    }
+}
+
+// One lane per (key, proof) pair of the single-output class (launch position = gathered position: the class comes
+// first), numbered as k_scan_keys numbers them: status 0 when V_0 of the proof's decoded record is
+// amounts[key][caller] g + Gamma h with the Gamma k_scan_keys left at [key][caller], else status 1 and Gamma zeroed.  A
+// lane whose container the decoder rejected or whose coefficients are undefined returns before its first load of either.
+template <class C>
+__global__ void __launch_bounds__(COMMIT_BLOCK) k_scan_keys_confirm(VerifyShape s, const uint32_t* __restrict__ table,
+                                                                    ScanKeysJob j, const uint64_t* __restrict__ amounts,
+                                                                    uint32_t amount64, const uint32_t* __restrict__ records,
+                                                                    uint32_t nv, uint32_t v0) {
+    constexpr int N = C::Fp::N;
+    constexpr int WW = 2 * N + 2;
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= j.count * j.n_keys) return;
+    const size_t p = q / j.n_keys;
+    if (j.status[p] || j.bad[p]) return;
+    const size_t at = (q - p * j.n_keys) * j.total + j.rx[p * RX_WORDS + RX_CALLER];
+    uint32_t kv[8], kg[8];
+    commit_amount_scalar<C>(amounts[at], amount64 != 0, kv);
+    ld_words<8>(j.out_masks + at * 8, kg);   // canonical: k_scan_keys wrote it
+    const Xyzz<C> acc = commit_walk<C>(
+        s, kv, kg, [&](size_t e) { return aff_ldg<C>(table + e * (size_t)(2 * N)); },
+        [](Xyzz<C>& a, const Aff<C>& pt, bool neg) { xyzz_madd_lazy(a, pt, neg); });
+    const bool same = walk_equals_wire<C>(acc, records + ((size_t)p * nv + v0) * WW);
+    j.out_status[at] = same ? 0u : 1u;
+    if (!same) {
+        const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        st_words<8>(j.out_masks + at * 8, z);
+    }
+}
+
+template <class C>
+struct RecoverKeysImpl {
+    using V = VerifyImpl<C>;
+    using R = RecoverImpl<C>;
+    static constexpr int CW = coeff_words<typename C::Fr>();
+
+    // workspace = front (MixedFront, serialized form) | coefficients, class after class by gathered position | the
+    // zero-challenge flags by gathered position.  Its size does not depend on the number of keys.
+    struct Layout {
+        typename V::MixedFront f;
+        size_t coeffs, coeff_of[MIXED_CLASSES], bad, total;
+    };
+    static Layout layout(const bpp_verifier* v, const MixedPlan& p, size_t count) {
+        Layout w;
+        WsCarver o;
+        w.f = V::carve_front(o, p, count, true);
+        size_t elems = 0;
+        for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
+            w.coeff_of[c] = elems;
+            if (p.count[c]) elems += p.count[c] * coeff_elems(V::class_shape(v, c).s.k);
+        }
+        w.coeffs = o.take(elems * CW * 4);
+        w.bad = o.take(count * 4);
+        w.total = o.total;
+        return w;
+    }
+    static size_t workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count);
+    // d_keys: n_keys x 32 bytes (device, 4-byte aligned); d_index: count x u64 or null; d_amounts: n_keys x count or null;
+    // d_out_masks: n_keys x count x 4 words; d_status: n_keys x count words
+    static int scan(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments, const uint32_t* m_of, size_t count,
+                    uint32_t version, bool amount64, const uint8_t* d_keys, size_t n_keys, uint64_t index_base,
+                    const uint64_t* d_index, const uint64_t* d_amounts, uint64_t* d_out_masks, uint32_t* d_status,
+                    void* d_workspace, size_t workspace_bytes, hipStream_t st);
+    static int scan_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, const uint32_t* m_of, size_t count,
+                         int flags, const uint8_t* keys, size_t n_keys, uint64_t index_base, const uint64_t* index,
+                         const uint64_t* amounts, uint64_t* out_masks, uint32_t* out_status);
+};
+
+#ifdef BPP_IMPL_DEFINITIONS
+template <class C>
+size_t RecoverKeysImpl<C>::workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
+    MixedPlan p;
+    if (!V::container_shape_ok(v) || mixed_plan_serialized(v->s, m_of, count, max_point_bytes<C>(), false, p)) return 0;
+    return layout(v, p, count).total;
+}
+
+template <class C>
+int RecoverKeysImpl<C>::scan(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments, const uint32_t* m_of,
+                             size_t count, uint32_t version, bool amount64, const uint8_t* d_keys, size_t n_keys,
+                             uint64_t index_base, const uint64_t* d_index, const uint64_t* d_amounts, uint64_t* d_out_masks,
+                             uint32_t* d_status, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
+    if (int rc = V::container_args_ok(v, version)) return rc;
+    MixedPlan p;
+    int rc = mixed_plan_serialized(v->s, m_of, count, (size_t)container_point_bytes<C>(version), true, p);
+    if (rc) return rc;
+    const Layout L = layout(v, p, count);
+    if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
+    if ((rc = R::check_classes(v, p))) return rc;
+    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+    auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    rc = V::decode_front(p, L.f, count, d_proofs, d_commitments, version, ws, st);
+    if (rc) return rc;
+    return V::for_each_class(v, p, L.f, ws, [&](const typename V::ClassView& cv) {
+        const int rc1 = V::derive_challenges(v, cv.ps, cv.pts, cv.count, cv.challenges, st);
+        if (rc1) return rc1;
+        const uint32_t k = cv.ps.s.k;
+        uint32_t* coeffs = W(L.coeffs) + L.coeff_of[cv.c] * CW;
+        hipLaunchKernelGGL(k_recover_coeffs<C>, dim3(cdiv(cv.count * RECOVER_GROUP, RECOVER_BLOCK)), dim3(RECOVER_BLOCK), 0, st, k,
+                           cv.ps.s.m, reinterpret_cast<const uint32_t*>(cv.sc3), reinterpret_cast<const uint32_t*>(cv.challenges),
+                           coeffs, W(L.bad) + cv.first, cv.count);
+        HIPCHK(hipGetLastError());
+        ScanKeysJob j;
+        j.k = k;
+        j.n_keys = (uint32_t)n_keys;
+        j.keys = reinterpret_cast<const uint32_t*>(d_keys);
+        j.index_base = index_base;
+        j.index = d_index;
+        j.rx = W(L.f.idx) + cv.first * RX_WORDS;
+        j.coeffs = coeffs;
+        j.bad = W(L.bad) + cv.first;
+        j.status = W(L.f.status) + cv.first;
+        j.out_masks = reinterpret_cast<uint32_t*>(d_out_masks);
+        j.out_status = d_status;
+        j.count = cv.count;
+        j.total = count;
+        const size_t pairs = cv.count * n_keys;
+        hipLaunchKernelGGL(k_scan_keys<C>, dim3(cdiv(pairs * SCAN_GROUP, SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, st, j);
+        HIPCHK(hipGetLastError());
+        if (cv.c != 0 || !d_amounts) return BPP_OK;
+        // the single-output class comes first in gathered order: launch position = gathered position
+        hipLaunchKernelGGL(k_scan_keys_confirm<C>, dim3(cdiv(pairs, COMMIT_BLOCK)), dim3(COMMIT_BLOCK), 0, st, v->s,
+                           v->table.u32(), j, d_amounts, amount64 ? 1u : 0u, reinterpret_cast<const uint32_t*>(cv.pts),
+                           cv.ps.s.NV, 3 + 2 * k);
+        HIPCHK(hipGetLastError());
+        return BPP_OK;
+    });
+}
+
+// the host twin's copy of the keys: overwritten before it is freed, on every way out
+struct KeyUpload {
+    DevBuf d;
+    ~KeyUpload() {
+        if (d.p) (void)hipMemset(d.p, 0, d.bytes);
+    }
+};
+
+template <class C>
+int RecoverKeysImpl<C>::scan_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, const uint32_t* m_of,
+                                  size_t count, int flags, const uint8_t* keys, size_t n_keys, uint64_t index_base,
+                                  const uint64_t* index, const uint64_t* amounts, uint64_t* out_masks, uint32_t* out_status) {
+    const uint32_t version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
+    if (int rc = V::container_args_ok(v, version)) return rc;
+    MixedPlan p;
+    int rc = mixed_plan_serialized(v->s, m_of, count, (size_t)container_point_bytes<C>(version), false, p);
+    if (rc) return rc;
+    const size_t pairs = n_keys * count;
+    KeyUpload dk;
+    DevBuf dpr, dcm, dix, dam, dout, dst, dws;
+    const void *p_pr, *p_cm, *p_ix, *p_am, *p_k;
+    if ((rc = upload_optional(proofs, p.proof_bytes, dpr, p_pr))) return rc;
+    if ((rc = upload_optional(commitments, p.comm_bytes, dcm, p_cm))) return rc;
+    if ((rc = upload_optional(index, count * 8, dix, p_ix))) return rc;
+    if ((rc = upload_optional(amounts, pairs * 8, dam, p_am))) return rc;
+    if ((rc = upload_optional(keys, n_keys * 32, dk.d, p_k))) return rc;
+    const size_t wsb = layout(v, p, count).total;
+    HIPCHK(dout.alloc(pairs * 32));
+    HIPCHK(dst.alloc(pairs * 4));
+    HIPCHK(dws.alloc(wsb));
+    rc = scan(v, static_cast<const uint8_t*>(p_pr), static_cast<const uint8_t*>(p_cm), m_of, count, version,
+              (flags & BPP_PROVE_AMOUNT64) != 0, static_cast<const uint8_t*>(p_k), n_keys, index_base,
+              static_cast<const uint64_t*>(p_ix), static_cast<const uint64_t*>(p_am), static_cast<uint64_t*>(dout.p), dst.u32(),
+              dws.p, wsb, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(out_masks, dout.p, pairs * 32, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_status, dst.p, pairs * 4, hipMemcpyDeviceToHost));
+    return BPP_OK;
+}
+#endif  // BPP_IMPL_DEFINITIONS
+
+extern template struct RecoverKeysImpl<Bls12381>;
+extern template struct RecoverKeysImpl<Secp256k1>;
+extern template struct RecoverKeysImpl<Ed25519>;
+
+}  // namespace bpp

@@ -696,6 +696,47 @@ int bpp_range_scan_serialized_mixed(bpp_verifier *v, const uint8_t *proofs, cons
                                     const uint64_t *index, const uint64_t *blinding, const uint64_t *amounts,
                                     uint64_t *out_masks, uint32_t *out_status);
 
+/* ---- scanning a block under MANY keys: bpp_range_scan_serialized_mixed* for n_keys view keys in one call ----
+ * A wallet server, an exchange or an auditor tests every block against all the keys it holds.  Most of a scan does not
+ * depend on the key -- the container decode, the membership test, the challenges, the k + 1 inversions per proof -- so
+ * this call does that once and spends per (key, proof) pair only the 2k + 3 slot expansions and as many products: Gamma
+ * is affine in the blinding slots, Gamma = A0 + sum_s c_s slot_s(key, index) with public coefficients (c_alpha = -D,
+ * c_delta = -D e^-1, c_eta = -D e^-2, c_dL[t] = -D e_t^2, c_dR[t] = -D e_t^-2, c_r = c_s = 0, A0 = D e^-2 delta',
+ * D = (y^(nm+1) [z^2])^-1; csrc/recover_coeffs.hpp).  Every pair gets exactly the status and mask
+ * bpp_range_scan_serialized_mixed gives for that key.
+ * EVERY KEY HERE TOGETHER WITH THE INDEX IS A VIEW KEY, as stated above for blind_key: whoever holds both reads the mask
+ * of every single-output proof the key blinded.  A SCAN IS NOT A VERIFICATION.  The device call reads the keys from the
+ * caller's buffer into registers and copies them nowhere: nothing derived from a key but Gamma reaches memory.  The host
+ * twin uploads the keys into a buffer of its own and overwrites that buffer before freeing it, on every return path.
+ *   d_proofs, d_commitments, m_of, count : as bpp_range_scan_serialized_mixed_device takes them
+ *   flags         : BPP_SER_TRANSCRIPT (REQUIRED: keys are the only blinding source here) | BPP_SER_UNCOMPRESSED |
+ *                   BPP_PROVE_AMOUNT64, each meaning what it means there
+ *   d_keys        : n_keys x 32 bytes (device, 4-byte aligned), key j at d_keys + 32 j
+ *   index_base, d_index : the blinding index of proof i, SHARED BY ALL KEYS: d_index[i] (count x uint64_t, device) when
+ *                   given, else index_base + i
+ *   d_amounts     : KEY-MAJOR n_keys x count uint64_t, d_amounts[j * count + i] the candidate amount of proof i under key
+ *                   j, read for m_i = 1 only; may be NULL
+ *   d_out_masks   : KEY-MAJOR n_keys x count x 4 words; d_status : KEY-MAJOR n_keys x count words -- pair (j, i) at
+ *                   j * count + i, 36 bytes of output per pair; the status words are those of the single-key call (2, the
+ *                   decoder's FormatError, under every key)
+ *   d_workspace   : bpp_scan_serialized_mixed_keys_workspace_bytes(v, m_of, count, n_keys) bytes (0 when an m_i is not
+ *                   taken or n_keys x count is over the bound)
+ * Errors: BPP_E_ARG for a NULL required pointer, a d_keys that is not 4-byte aligned, flags without BPP_SER_TRANSCRIPT, an
+ * unknown flag, an m_of[i] that is not taken (the text names i), n_keys x count above 0x7fffffff / 64 (checked without
+ * overflow), a workspace that is too small; nothing is enqueued and nothing is written then.  n_keys = 0 or count = 0 is
+ * BPP_OK.  The device call BLOCKS the host only while it uploads the per-proof index; the host twin is synchronous. */
+size_t bpp_scan_serialized_mixed_keys_workspace_bytes(const bpp_verifier *v, const uint32_t *m_of, size_t count,
+                                                      size_t n_keys);
+int bpp_range_scan_serialized_mixed_keys_device(bpp_verifier *v, const void *d_proofs, const void *d_commitments,
+                                                const uint32_t *m_of, size_t count, int flags, const uint8_t *d_keys,
+                                                size_t n_keys, uint64_t index_base, const uint64_t *d_index,
+                                                const uint64_t *d_amounts, uint64_t *d_out_masks, uint32_t *d_status,
+                                                void *d_workspace, size_t workspace_bytes, void *stream);
+int bpp_range_scan_serialized_mixed_keys(bpp_verifier *v, const uint8_t *proofs, const uint8_t *commitments,
+                                         const uint32_t *m_of, size_t count, int flags, const uint8_t *keys, size_t n_keys,
+                                         uint64_t index_base, const uint64_t *index, const uint64_t *amounts,
+                                         uint64_t *out_masks, uint32_t *out_status);
+
 /* ---- the weighted inner product argument as a seam of its own: WeightedInnerProductProof::{prove, verify} ----
  * Reference: src/weighted_inner_product_proof.rs:36-227 (prove), :238-328 (verify), :330-382 (verification_scalars).
  * An engine created for (n, m) proves and verifies the WIP relation over its key for ANY statement that ends in one; only

@@ -238,6 +238,39 @@ inline ScanResult scan_serialized_mixed(bpp_verifier* engine, const std::vector<
     return r;
 }
 
+// The same scan under MANY keys in one call (bpp_range_scan_serialized_mixed_keys): the decode, the membership test, the
+// challenges and the inversions run once, the key-dependent part per (key, proof) pair.  The blinding index of proof i
+// (index[i], or index_base + i) is shared by all keys; `amounts` is key-major, keys.size() x ms.size() (empty: nothing is
+// confirmed).  Result: key-major, pair (j, i) at j * ms.size() + i, the status words of scan_serialized_mixed.  Every key
+// is a view key; a scan is NOT a verification.
+inline ScanResult scan_serialized_mixed_keys(bpp_verifier* engine, const std::vector<uint8_t>& proofs,
+                                             const std::vector<uint8_t>& commitments, const std::vector<uint32_t>& ms,
+                                             const std::vector<std::array<uint8_t, 32>>& keys, uint64_t index_base = 0,
+                                             const std::vector<uint64_t>& index = {}, const std::vector<uint64_t>& amounts = {},
+                                             bool amount64 = false, bool uncompressed = false) {
+    const size_t pairs = keys.size() * ms.size();
+    if (!index.empty() && index.size() != ms.size()) throw std::logic_error("scan_serialized_mixed_keys: one index per proof");
+    if (!amounts.empty() && amounts.size() != pairs) throw std::logic_error("scan_serialized_mixed_keys: K x count amounts");
+    ScanResult r;
+    r.status.assign(pairs + 1, 0);
+    std::vector<uint64_t> out(pairs * 4 + 1);
+    std::vector<uint8_t> packed(keys.size() * 32 + 1);
+    for (size_t j = 0; j < keys.size(); j++)
+        for (size_t t = 0; t < 32; t++) packed[j * 32 + t] = keys[j][t];
+    const int flags = BPP_SER_TRANSCRIPT | (uncompressed ? BPP_SER_UNCOMPRESSED : 0) | (amount64 ? BPP_PROVE_AMOUNT64 : 0);
+    const int rc = bpp_range_scan_serialized_mixed_keys(engine, proofs.data(), commitments.data(), ms.data(), ms.size(), flags,
+                                                        packed.data(), keys.size(), index_base,
+                                                        index.empty() ? nullptr : index.data(),
+                                                        amounts.empty() ? nullptr : amounts.data(), out.data(), r.status.data());
+    for (volatile uint8_t& b : packed) b = 0;   // the packed copy of the keys made here
+    if (rc != BPP_OK) throw std::runtime_error(std::string("bpp_range_scan_serialized_mixed_keys: ") + bpp_last_error());
+    r.status.resize(pairs);
+    r.masks.resize(pairs);
+    for (size_t i = 0; i < pairs; i++)
+        for (int t = 0; t < 4; t++) r.masks[i].e[t] = out[i * 4 + t];
+    return r;
+}
+
 // Verifier-side holder of the commitments.  It exists only in the reference's (stale) README
 // (README.md:47-55: RangeVerifier::new(), allocate(&prover.commitment_vec), proof.verify(.., &verifier));
 // the reference's code takes the commitment slice directly (range/mod.rs:57-62).  Both forms are offered.

@@ -10,9 +10,16 @@ alarm is raised only when the interpreter has control again, so run the whole to
            candidate amount each.
   recover  bpp_range_recover_masks_mixed_device alone (triples and challenge blocks resident) at 2^12 and 2^16 single-output
            proofs: masks per second.
+  keys     (--keys K[,K..]; --legs k) bpp_range_scan_serialized_mixed_keys_device under K keys against K calls of
+           bpp_range_scan_serialized_mixed_device, one per key, on the `wallet` block: same process, alternated repetition
+           by repetition; both medians, their ratio with the spread of the per-repetition ratios.  --side many|single runs
+           one side alone (the run to put under rocprofv3 --kernel-trace --stats); --kernel-stats SIDE=CSV[,SIDE=CSV] folds
+           such runs' k_kernel_stats.csv into an existing --out file as the per-kernel split (no GPU needed).
 usage: timeout -k 10 1100 python tools/recover_bench.py [--reps 20] [--warmup 3] [--window 13] [--scale 1.0] [--legs sr]
-       [--blocks mixed,wallet] [--out profiles/recover_bench.json]"""
+       [--blocks mixed,wallet] [--keys 1,4,16,64] [--side both] [--out profiles/recover_bench.json]"""
 import argparse
+import csv
+import hashlib
 import json
 import os
 import signal
@@ -163,8 +170,81 @@ def recover_leg(torch, B, a, bv, log2n, args, out):
     print("recover 2^%d" % log2n, json.dumps(res), flush=True)
 
 
+def keys_leg(torch, B, a, bv, ks, args, out):
+    """the K-key scan against K single-key scans of the wallet block; key 0 made the block, the others own nothing"""
+    ms = block_shapes("wallet", args.scale)
+    count = len(ms)
+    d_p, d_c, d_a = step(600, lambda: make_block(torch, B, a, bv, ms))
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    ssb = bv.recover_workspace_bytes(ms, serialized=True)
+    d_sws = torch.empty(ssb, dtype=torch.uint8, device=dev)
+    d_st1 = torch.full((count,), 7, dtype=torch.int32, device=dev)
+    d_m1 = torch.zeros((count, 4), dtype=torch.int64, device=dev)
+    out["keys"] = {"block": "wallet", "count": count, "side": args.side, "by_keys": {}}
+    for K in ks:
+        keys = [KEY] + [hashlib.sha256(b"recover_bench key %d" % j).digest() for j in range(1, K)]
+        d_keys = torch.from_numpy(np.frombuffer(b"".join(keys), dtype=np.uint8).copy()).to(dev)
+        d_am = d_a.repeat(K)
+        ksb = bv.scan_keys_workspace_bytes(ms, K)
+        d_kws = torch.empty(ksb, dtype=torch.uint8, device=dev)
+        d_stK = torch.full((K, count), 7, dtype=torch.int32, device=dev)
+        d_mK = torch.zeros((K, count, 4), dtype=torch.int64, device=dev)
+
+        def many():
+            bv.scan_serialized_mixed_keys_device(d_p.data_ptr(), d_c.data_ptr(), ms, d_keys.data_ptr(), K, d_mK.data_ptr(),
+                                                 d_stK.data_ptr(), d_kws.data_ptr(), ksb, st, index_base=BASE,
+                                                 d_amounts=d_am.data_ptr())
+
+        def single():
+            for key in keys:
+                bv.scan_serialized_mixed_device(d_p.data_ptr(), d_c.data_ptr(), ms, d_m1.data_ptr(), d_st1.data_ptr(),
+                                                d_sws.data_ptr(), ssb, st, transcript=True, blind_key=key, index_base=BASE,
+                                                d_amounts=d_a.data_ptr())
+
+        fns = {"both": [many, single], "many": [many], "single": [single]}[args.side]
+        ts = step(900, lambda: alternate(torch, fns, args.reps, args.warmup))
+        res = {"pairs": K * count, "keys_workspace_bytes": ksb, "single_workspace_bytes": ssb}
+        if args.side in ("both", "many"):
+            status = d_stK.cpu().numpy()
+            res["many"] = stats(ts[0])
+            res["pairs_per_s"] = K * count / (statistics.median(ts[0]) * 1e-3)
+            res["status_as_expected"] = bool((status[0] == 0).all() and (status[1:] == 1).all())
+        if args.side in ("both", "single"):
+            res["single_x_K"] = stats(ts[-1])
+        if args.side == "both":
+            per_rep = [m / s for m, s in zip(ts[0], ts[1])]
+            res["ratio_many_over_single"] = statistics.median(ts[0]) / statistics.median(ts[1])
+            res["ratio_per_rep"] = {"median": statistics.median(per_rep), "min": min(per_rep), "max": max(per_rep)}
+        out["keys"]["by_keys"][str(K)] = res
+        print("keys %d" % K, json.dumps(res), flush=True)
+        del d_keys, d_am, d_kws, d_stK, d_mK
+
+
+def merge_kernel_stats(args):
+    """folds rocprofv3 k_kernel_stats.csv files (one per side) into the JSON at --out: no GPU"""
+    with open(args.out) as f:
+        out = json.load(f)
+    split = {}
+    for item in args.kernel_stats.split(","):
+        side, path = item.split("=", 1)
+        with open(path, newline="") as f:
+            rows = list(csv.DictReader(f))
+        split[side] = [{"kernel": r["Name"].split("(")[0], "calls": int(r["Calls"]), "total_ms": float(r["TotalDurationNs"]) * 1e-6,
+                        "average_us": float(r["AverageNs"]) * 1e-3, "percent": float(r["Percentage"])} for r in rows
+                       if float(r["Percentage"]) >= 0.1]
+    out.setdefault("keys", {})["kernel_split"] = split
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps({"merged": sorted(split), "out": args.out}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--keys", default="")
+    ap.add_argument("--side", default="both", choices=("both", "many", "single"))
+    ap.add_argument("--kernel-stats", default="")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--window", type=int, default=13)
@@ -173,6 +253,10 @@ def main():
     ap.add_argument("--blocks", default="mixed,wallet")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "recover_bench.json"))
     args = ap.parse_args()
+    if args.kernel_stats:
+        return merge_kernel_stats(args)
+    if args.keys and "k" not in args.legs:
+        args.legs = "k"   # --keys alone: the many-key leg alone
     import torch
     import bulletproofsplus_amd as B
     a = B.Arith("bls12_381")
@@ -186,6 +270,8 @@ def main():
         if "r" in args.legs:
             for log2n in (12, 16):
                 recover_leg(torch, B, a, bv, log2n, args, out)
+        if "k" in args.legs:
+            keys_leg(torch, B, a, bv, [int(x) for x in (args.keys or "1,4,16,64").split(",")], args, out)
         out["complete"] = True
     except StepTimeout:
         out["stopped"] = "a step ran into its time limit"
