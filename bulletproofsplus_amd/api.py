@@ -29,6 +29,7 @@ from ._lib import BLS12_381_G1, SECP256K1, ED25519, CURVE_IDS, BppError, check  
 
 
 AMOUNT64 = 0x100   # BPP_PROVE_AMOUNT64 (include/bpp_amd.h): commitments over the whole 64-bit amount
+AMOUNTS_SEALED = 0x200   # BPP_FIND_AMOUNTS_SEALED: verify_find's amounts are one sealed amount per proof
 SCAN_UNCONFIRMED = 3   # BPP_SCAN_UNCONFIRMED: a scanned proof with no candidate amount, or of more than one output
 
 
@@ -1431,6 +1432,112 @@ class BatchVerifier:
         if kb is not None:
             kb[:] = 0   # the packed copy of the keys made here
         return status, [[wire_to_int(x) for x in row] for row in masks]
+
+    # ---- sealed amounts; verifying a block and listing the outputs of many keys (include/bpp_amd.h) ----
+    def seal_amounts_device(self, blind_key: bytes, d_in: int, count: int, d_out: int, stream: int = 0, index_base: int = 0,
+                            d_index: int = 0):
+        """d_out[i] = d_in[i] XOR pad(blind_key, d_index[i] or index_base + i) over count resident u64: seals amounts, and
+        opens sealed ones (bpp_amounts_seal_device).  d_in and d_out may be the same buffer."""
+        check(_lib.lib().bpp_amounts_seal_device(self.arith.handle, blind_key, ctypes.c_uint64(index_base), d_index or None,
+                                                 d_in or None, count, d_out or None, stream or None), "bpp_amounts_seal_device")
+
+    def seal_amounts(self, blind_key: bytes, amounts, index_base: int = 0, index=None) -> np.ndarray:
+        """amounts: ints below 2^64; index: None or one blinding index per amount -> (count,) u64, amount XOR pad; applied
+        to sealed amounts it opens them (bpp_amounts_seal)"""
+        am = np.ascontiguousarray(np.asarray([int(x) for x in amounts], dtype=np.uint64))
+        idx = None
+        if index is not None:
+            idx = np.ascontiguousarray(np.asarray([int(x) for x in index], dtype=np.uint64))
+            if len(idx) != len(am):
+                raise RuntimeError("seal_amounts: one blinding index per amount")
+        out = np.zeros(len(am), dtype=np.uint64)
+        check(_lib.lib().bpp_amounts_seal(self.arith.handle, blind_key, ctypes.c_uint64(index_base),
+                                          _ptr(idx) if idx is not None else None, _ptr(am) if len(am) else None, len(am),
+                                          _ptr(out) if len(am) else None), "bpp_amounts_seal")
+        return out
+
+    def verify_find_workspace_bytes(self, ms, n_keys: int) -> int:
+        """bytes of device workspace verify_find_serialized_mixed_keys_device needs (0: an m_i is not taken, or
+        n_keys x count is over the bound); grows with n_keys"""
+        m = self._ms(ms)
+        return _lib.lib().bpp_verify_find_serialized_mixed_keys_workspace_bytes(self.handle, _ptr(m) if len(m) else None, len(m),
+                                                                                n_keys)
+
+    def verify_find_serialized_mixed_keys_device(self, d_proofs: int, d_commitments: int, ms, d_keys: int, n_keys: int,
+                                                 d_amounts: int, d_ok: int, d_hits: int, max_hits: int, d_n_hits: int,
+                                                 d_workspace: int, workspace_bytes: int, stream: int = 0,
+                                                 uncompressed: bool = False, amount64: bool = False, sealed: bool = False,
+                                                 index_base: int = 0, d_index: int = 0):
+        """Verifies a resident block (d_ok: verify_serialized_mixed_device's words under the transcript) and lists the
+        single outputs that belong to the n_keys view keys at d_keys, the front run once.  d_amounts: sealed -- count u64
+        sealed amounts shared by all keys; else (n_keys, count) u64 candidates, key-major.  d_hits: max_hits records of 12
+        u32 [key number, position, amount lo, hi, mask as 8 words] in ascending (key number, position); d_n_hits: one u32,
+        the hits found -- above max_hits, only the first max_hits are written.  A hit is a VERIFIED single output whose
+        commitment opens to the amount and the mask recovered under that key."""
+        m = self._ms(ms)
+        check(_lib.lib().bpp_range_verify_find_serialized_mixed_keys_device(
+            self.handle, d_proofs, d_commitments, _ptr(m) if len(m) else None, len(m),
+            1 | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0) | (AMOUNTS_SEALED if sealed else 0), d_keys or None,
+            n_keys, ctypes.c_uint64(index_base), d_index or None, d_amounts or None, d_ok or None, d_hits or None, max_hits,
+            d_n_hits or None, d_workspace, workspace_bytes, stream or None), "bpp_range_verify_find_serialized_mixed_keys_device")
+
+    def verify_find_serialized_mixed_keys(self, proofs, commitments, ms=None, keys=(), amounts=(), sealed: bool = False,
+                                          uncompressed: bool = False, amount64: bool = False, index_base: int = 0, index=None,
+                                          max_hits: int = None):
+        """proofs, commitments, ms, keys, index: as scan_serialized_mixed_keys; amounts: sealed -- one sealed amount per
+        proof; else K x count candidates (amounts[j][i]: proof i under key j); max_hits: None for room for every pair
+        -> (ok (count,) u32, hits, found): ok as verify_serialized_mixed under the transcript; hits the list of
+        (key_no, position, amount, mask) in ascending (key_no, position), at most max_hits of them; found the number of
+        hits there are (bpp_range_verify_find_serialized_mixed_keys).  With no keys the block is verified all the same
+        and no hit is listed."""
+        def flat(x):
+            return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
+        raw, cm = flat(proofs), flat(commitments)
+        version = 2 if uncompressed else 1
+        m = proofs_scan(self.arith, self.n, raw, version) if ms is None else self._ms(ms)
+        count = len(m)
+        keys = [bytes(k) for k in keys]
+        if any(len(k) != 32 for k in keys):
+            raise RuntimeError("verify_find_serialized_mixed_keys: every key is 32 bytes")
+        nk = len(keys)
+        if all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m):
+            pb = uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)
+            need = sum(proof_bytes(self.arith, self.n, int(x), version) for x in m)
+            if len(raw) != need:
+                raise RuntimeError("verify_find_serialized_mixed_keys: %d bytes of proofs, the shapes in ms need %d" % (len(raw), need))
+            if len(cm) != int(m.sum()) * pb:
+                raise RuntimeError("verify_find_serialized_mixed_keys: ms[i] commitments per proof")
+        idx = None
+        if index is not None:
+            idx = np.ascontiguousarray(np.asarray([int(x) for x in index], dtype=np.uint64))
+            if len(idx) != count:
+                raise RuntimeError("verify_find_serialized_mixed_keys: one blinding index per proof")
+        if sealed:
+            am = np.ascontiguousarray(np.asarray([int(x) for x in amounts], dtype=np.uint64).reshape(-1))
+            if len(am) != count:
+                raise RuntimeError("verify_find_serialized_mixed_keys: one sealed amount per proof")
+        else:
+            am = np.ascontiguousarray(np.asarray([[int(x) for x in row] for row in amounts], dtype=np.uint64).reshape(-1))
+            if len(am) != nk * count:
+                raise RuntimeError("verify_find_serialized_mixed_keys: K x count candidate amounts")
+        cap = nk * count if max_hits is None else int(max_hits)
+        kb = np.frombuffer(b"".join(keys), dtype=np.uint8).copy() if nk else None
+        ok = np.zeros(count, dtype=np.uint32)
+        rec = np.zeros((cap, 12), dtype=np.uint32)
+        found = np.zeros(1, dtype=np.uint32)
+        some = nk > 0 and count > 0
+        check(_lib.lib().bpp_range_verify_find_serialized_mixed_keys(
+            self.handle, _ptr(raw) if len(raw) else None, _ptr(cm) if len(cm) else None, _ptr(m) if count else None, count,
+            1 | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0) | (AMOUNTS_SEALED if sealed else 0),
+            _ptr(kb) if kb is not None else None, nk, ctypes.c_uint64(index_base), _ptr(idx) if idx is not None else None,
+            _ptr(am) if some else None, _ptr(ok) if count else None, _ptr(rec) if cap else None, cap, _ptr(found)),
+            "bpp_range_verify_find_serialized_mixed_keys")
+        if kb is not None:
+            kb[:] = 0   # the packed copy of the keys made here
+        n = int(found[0])
+        hits = [(int(r[0]), int(r[1]), int(r[2]) | int(r[3]) << 32, wire_to_int(np.ascontiguousarray(r[4:]).view(np.uint64))) for r in rec[:min(n, cap)]]
+        return ok, hits, n
 
 
 def shard_cuts(ms, count: int, world: int) -> np.ndarray:

@@ -10,6 +10,7 @@
 #include "impl_verify.hpp"
 #include "impl_wip.hpp"
 #include "recover.hpp"
+#include "find.hpp"
 #include "recover_keys.hpp"
 
 using namespace bpp;
@@ -1470,6 +1471,89 @@ extern "C" int bpp_range_scan_serialized_mixed_keys(bpp_verifier* v, const uint8
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
         return RecoverKeysImpl<decltype(cv)>::scan_host(v, proofs, commitments, m_of, count, flags, keys, n_keys, index_base,
                                                         index, amounts, out_masks, out_status);
+    });
+}
+
+// ---- sealed amounts, and verifying a block while listing the outputs of many keys (find.hpp) ----
+extern "C" int bpp_amounts_seal_device(bpp_ctx* ctx, const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_index,
+                                       const uint64_t* d_in, size_t count, uint64_t* d_out, void* stream) {
+    if (!ctx || !blind_key) return fail(BPP_E_ARG, "null argument");
+    if (count == 0) return BPP_OK;
+    if (!d_in || !d_out) return fail(BPP_E_ARG, "null argument");
+    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    return on_ctx(*ctx, {count, "count"}, [&](auto cv) -> int {
+        return FindImpl<decltype(cv)>::seal(blind_key, index_base, d_index, d_in, count, d_out, static_cast<hipStream_t>(stream));
+    });
+}
+
+extern "C" int bpp_amounts_seal(bpp_ctx* ctx, const uint8_t* blind_key, uint64_t index_base, const uint64_t* index,
+                                const uint64_t* in, size_t count, uint64_t* out) {
+    if (!ctx || !blind_key) return fail(BPP_E_ARG, "null argument");
+    if (count == 0) return BPP_OK;
+    if (!in || !out) return fail(BPP_E_ARG, "null argument");
+    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    return on_ctx(*ctx, {count, "count"}, [&](auto cv) -> int {
+        return FindImpl<decltype(cv)>::seal_host(blind_key, index_base, index, in, count, out);
+    });
+}
+
+namespace {
+constexpr int FIND_FLAGS = SCAN_FLAGS | BPP_FIND_AMOUNTS_SEALED;
+}
+
+extern "C" size_t bpp_verify_find_serialized_mixed_keys_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count,
+                                                                        size_t n_keys) {
+    if ((count && !m_of) || !pairs_bounded(n_keys, count) || !m_of_wellformed(m_of, count)) return 0;
+    return size_for(v, [&](auto cv) { return FindImpl<decltype(cv)>::workspace_bytes(v, m_of, count, n_keys); });
+}
+
+extern "C" int bpp_range_verify_find_serialized_mixed_keys_device(bpp_verifier* v, const void* d_proofs, const void* d_commitments,
+                                                                  const uint32_t* m_of, size_t count, int flags,
+                                                                  const uint8_t* d_keys, size_t n_keys, uint64_t index_base,
+                                                                  const uint64_t* d_index, const uint64_t* d_amounts,
+                                                                  uint32_t* d_ok, uint32_t* d_hits, size_t max_hits,
+                                                                  uint32_t* d_n_hits, void* d_workspace, size_t workspace_bytes,
+                                                                  void* stream) {
+    if (!v || !d_n_hits) return fail(BPP_E_ARG, "null argument");
+    if (flags & ~FIND_FLAGS) return fail(BPP_E_ARG, "unknown flag");
+    if (count == 0)   // no proof: no verdict, no hit
+        return on_device(v->ctx.device, [&]() -> int {
+            HIPCHK(zero_words_async(d_n_hits, 4, static_cast<hipStream_t>(stream)));
+            return BPP_OK;
+        });
+    // without keys the block is verified all the same: the call IS a verification, and d_ok is never left unwritten
+    if (!d_proofs || !d_commitments || !m_of || !d_ok || !d_workspace) return fail(BPP_E_ARG, "null argument");
+    if (n_keys && (!d_keys || !d_amounts || (!d_hits && max_hits))) return fail(BPP_E_ARG, "null argument");
+    if (n_keys && (reinterpret_cast<uintptr_t>(d_keys) & 3)) return fail(BPP_E_ARG, "d_keys must be 4-byte aligned");
+    if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
+    if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return FindImpl<decltype(cv)>::find(v, static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments),
+                                            m_of, count, (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u,
+                                            (flags & BPP_PROVE_AMOUNT64) != 0, (flags & BPP_FIND_AMOUNTS_SEALED) != 0, d_keys,
+                                            n_keys, index_base, d_index, d_amounts, d_ok, d_hits, max_hits, d_n_hits, d_workspace,
+                                            workspace_bytes, static_cast<hipStream_t>(stream));
+    });
+}
+
+// host buffers in (keys, index and amounts included), host verdicts and hit records out: the device path above between copies
+extern "C" int bpp_range_verify_find_serialized_mixed_keys(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments,
+                                                           const uint32_t* m_of, size_t count, int flags, const uint8_t* keys,
+                                                           size_t n_keys, uint64_t index_base, const uint64_t* index,
+                                                           const uint64_t* amounts, uint32_t* out_ok, uint32_t* out_hits,
+                                                           size_t max_hits, uint32_t* out_n_hits) {
+    if (!v || !out_n_hits) return fail(BPP_E_ARG, "null argument");
+    if (flags & ~FIND_FLAGS) return fail(BPP_E_ARG, "unknown flag");
+    if (count == 0) {   // no proof: no verdict, no hit
+        *out_n_hits = 0;
+        return BPP_OK;
+    }
+    if (!proofs || !commitments || !m_of || !out_ok) return fail(BPP_E_ARG, "null argument");
+    if (n_keys && (!keys || !amounts || (!out_hits && max_hits))) return fail(BPP_E_ARG, "null argument");
+    if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return FindImpl<decltype(cv)>::find_host(v, proofs, commitments, m_of, count, flags, keys, n_keys, index_base, index,
+                                                 amounts, out_ok, out_hits, max_hits, out_n_hits);
     });
 }
 

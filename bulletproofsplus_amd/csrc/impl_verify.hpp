@@ -247,6 +247,8 @@ struct VerifyImpl {
     // serialized form: the index upload, then the decoder and the membership test write records, triples and status
     static int decode_front(const MixedPlan& p, const MixedFront& front, size_t count, const uint8_t* d_proofs,
                             const uint8_t* d_commitments, uint32_t version, uint8_t* ws, hipStream_t st);
+    // serialized form, the way back: d_ok[caller position] = FormatError where the decoder rejected the proof, else front.ok
+    static int scatter_verdicts(const MixedFront& front, uint8_t* ws, uint32_t* d_ok, size_t count, hipStream_t st);
     // one class present in a mixed batch: its shape, its gathered range and its regions of a front
     struct ClassView {
         uint32_t c;
@@ -956,6 +958,15 @@ int VerifyImpl<C>::decode_front(const MixedPlan& p, const MixedFront& front, siz
     return BPP_OK;
 }
 
+template <class C>
+int VerifyImpl<C>::scatter_verdicts(const MixedFront& front, uint8_t* ws, uint32_t* d_ok, size_t count, hipStream_t st) {
+    auto W = [&](size_t off) { return reinterpret_cast<const uint32_t*>(ws + off); };
+    hipLaunchKernelGGL(k_mixed_status_scatter<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, W(front.idx), W(front.status),
+                       W(front.ok), d_ok, count);
+    HIPCHK(hipGetLastError());
+    return BPP_OK;
+}
+
 // Gather, then today's pass over each class's contiguous region with the class's view (Horner form, lone batch and
 // blocks per proof follow the class's own count), then the verdicts and result points back into caller order.
 template <class C>
@@ -1033,10 +1044,7 @@ int VerifyImpl<C>::run_serialized_mixed(bpp_verifier* v, const uint8_t* d_proofs
                    workspace_bytes - L.run, nullptr, nullptr, st);
     });
     if (rc) return rc;
-    hipLaunchKernelGGL(k_mixed_status_scatter<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, W(L.f.idx), W(L.f.status), W(L.f.ok),
-                       d_ok, count);
-    HIPCHK(hipGetLastError());
-    return BPP_OK;
+    return scatter_verdicts(L.f, ws, d_ok, count, st);
 }
 
 template <class C>
@@ -1316,10 +1324,7 @@ int VerifyImpl<C>::run_serialized_grouped_mixed(bpp_verifier* v, const uint8_t* 
     }
     rc = grouped_mixed_core(v, p, count, group, transcript, true, h_stats, ws, L, workspace_bytes, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_mixed_status_scatter<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, W(L.f.idx), W(L.f.status), W(L.f.ok),
-                       d_ok, count);
-    HIPCHK(hipGetLastError());
-    return BPP_OK;
+    return scatter_verdicts(L.f, ws, d_ok, count, st);
 }
 
 template <class C>

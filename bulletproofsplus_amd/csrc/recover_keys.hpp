@@ -207,6 +207,11 @@ struct RecoverKeysImpl {
         return w;
     }
     static size_t workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count);
+    // One class of a call: k_recover_coeffs over its proofs, then k_scan_keys over its (key, proof) pairs.  j arrives with
+    // the call's part filled in (keys, index, outputs, total) and leaves with the class's (k, rx, coeffs, bad, status,
+    // count), for the confirmation that follows.  w_idx, w_status, w_bad: the call's, from gathered position 0.
+    static int scan_class(const typename V::ClassView& cv, const uint32_t* w_idx, const uint32_t* w_status, uint32_t* w_bad,
+                          uint32_t* coeffs, ScanKeysJob& j, hipStream_t st);
     // d_keys: n_keys x 32 bytes (device, 4-byte aligned); d_index: count x u64 or null; d_amounts: n_keys x count or null;
     // d_out_masks: n_keys x count x 4 words; d_status: n_keys x count words
     static int scan(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments, const uint32_t* m_of, size_t count,
@@ -242,40 +247,44 @@ int RecoverKeysImpl<C>::scan(bpp_verifier* v, const uint8_t* d_proofs, const uin
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
     rc = V::decode_front(p, L.f, count, d_proofs, d_commitments, version, ws, st);
     if (rc) return rc;
+    ScanKeysJob j;
+    j.n_keys = (uint32_t)n_keys;
+    j.keys = reinterpret_cast<const uint32_t*>(d_keys);
+    j.index_base = index_base;
+    j.index = d_index;
+    j.out_masks = reinterpret_cast<uint32_t*>(d_out_masks);
+    j.out_status = d_status;
+    j.total = count;
     return V::for_each_class(v, p, L.f, ws, [&](const typename V::ClassView& cv) {
-        const int rc1 = V::derive_challenges(v, cv.ps, cv.pts, cv.count, cv.challenges, st);
+        int rc1 = V::derive_challenges(v, cv.ps, cv.pts, cv.count, cv.challenges, st);
         if (rc1) return rc1;
-        const uint32_t k = cv.ps.s.k;
-        uint32_t* coeffs = W(L.coeffs) + L.coeff_of[cv.c] * CW;
-        hipLaunchKernelGGL(k_recover_coeffs<C>, dim3(cdiv(cv.count * RECOVER_GROUP, RECOVER_BLOCK)), dim3(RECOVER_BLOCK), 0, st, k,
-                           cv.ps.s.m, reinterpret_cast<const uint32_t*>(cv.sc3), reinterpret_cast<const uint32_t*>(cv.challenges),
-                           coeffs, W(L.bad) + cv.first, cv.count);
-        HIPCHK(hipGetLastError());
-        ScanKeysJob j;
-        j.k = k;
-        j.n_keys = (uint32_t)n_keys;
-        j.keys = reinterpret_cast<const uint32_t*>(d_keys);
-        j.index_base = index_base;
-        j.index = d_index;
-        j.rx = W(L.f.idx) + cv.first * RX_WORDS;
-        j.coeffs = coeffs;
-        j.bad = W(L.bad) + cv.first;
-        j.status = W(L.f.status) + cv.first;
-        j.out_masks = reinterpret_cast<uint32_t*>(d_out_masks);
-        j.out_status = d_status;
-        j.count = cv.count;
-        j.total = count;
-        const size_t pairs = cv.count * n_keys;
-        hipLaunchKernelGGL(k_scan_keys<C>, dim3(cdiv(pairs * SCAN_GROUP, SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, st, j);
-        HIPCHK(hipGetLastError());
+        if ((rc1 = scan_class(cv, W(L.f.idx), W(L.f.status), W(L.bad), W(L.coeffs) + L.coeff_of[cv.c] * CW, j, st))) return rc1;
         if (cv.c != 0 || !d_amounts) return BPP_OK;
         // the single-output class comes first in gathered order: launch position = gathered position
-        hipLaunchKernelGGL(k_scan_keys_confirm<C>, dim3(cdiv(pairs, COMMIT_BLOCK)), dim3(COMMIT_BLOCK), 0, st, v->s,
+        hipLaunchKernelGGL(k_scan_keys_confirm<C>, dim3(cdiv(cv.count * n_keys, COMMIT_BLOCK)), dim3(COMMIT_BLOCK), 0, st, v->s,
                            v->table.u32(), j, d_amounts, amount64 ? 1u : 0u, reinterpret_cast<const uint32_t*>(cv.pts),
-                           cv.ps.s.NV, 3 + 2 * k);
+                           cv.ps.s.NV, 3 + 2 * cv.ps.s.k);
         HIPCHK(hipGetLastError());
         return BPP_OK;
     });
+}
+
+template <class C>
+int RecoverKeysImpl<C>::scan_class(const typename V::ClassView& cv, const uint32_t* w_idx, const uint32_t* w_status,
+                                   uint32_t* w_bad, uint32_t* coeffs, ScanKeysJob& j, hipStream_t st) {
+    j.k = cv.ps.s.k;
+    j.rx = w_idx + cv.first * RX_WORDS;
+    j.coeffs = coeffs;
+    j.bad = w_bad + cv.first;
+    j.status = w_status + cv.first;
+    j.count = cv.count;
+    hipLaunchKernelGGL(k_recover_coeffs<C>, dim3(cdiv(cv.count * RECOVER_GROUP, RECOVER_BLOCK)), dim3(RECOVER_BLOCK), 0, st, j.k,
+                       cv.ps.s.m, reinterpret_cast<const uint32_t*>(cv.sc3), reinterpret_cast<const uint32_t*>(cv.challenges),
+                       coeffs, w_bad + cv.first, cv.count);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_scan_keys<C>, dim3(cdiv(cv.count * j.n_keys * SCAN_GROUP, SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, st, j);
+    HIPCHK(hipGetLastError());
+    return BPP_OK;
 }
 
 // the host twin's copy of the keys: overwritten before it is freed, on every way out

@@ -1,0 +1,6 @@
+// explicit instantiation: FindImpl<Bls12381> (k_amounts_seal, k_find_confirm, k_find_count, k_find_offsets, k_find_emit are compiled in this translation unit only)
+#define BPP_IMPL_DEFINITIONS 1
+#include "find.hpp"
+namespace bpp {
+template struct FindImpl<Bls12381>;
+}

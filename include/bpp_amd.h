@@ -737,6 +737,85 @@ int bpp_range_scan_serialized_mixed_keys(bpp_verifier *v, const uint8_t *proofs,
                                          uint64_t index_base, const uint64_t *index, const uint64_t *amounts,
                                          uint64_t *out_masks, uint32_t *out_status);
 
+/* ---- sealed amounts: the 8-byte ciphertext of its amount that an output carries ----
+ * A scanner has no candidate amount per (key, proof) pair; a real output carries ONE ciphertext of its amount and every
+ * view key tries its own pad on it:
+ *     pad(key, idx) = the first 8 bytes, read as a little-endian uint64_t, of
+ *                     SHA-256(key || "bppa" || idx as u64 LE || 0 as u32 || 0 as u32)
+ *     sealed        = amount XOR pad(key, idx)
+ * the 52-byte block of the blinding slots under the tag "bppa" in place of "bppb": domain-separated from every scalar
+ * that enters a proof (csrc/find_terms.hpp).  Sealing and opening are the same operation.  idx is the blinding index of
+ * the output's proof and THE INDEX RULE ABOVE HOLDS UNCHANGED: output i has index d_index[i] when given, else
+ * index_base + i, and a key never meets an index twice.  The pad hides an amount from whoever lacks the key; it does not
+ * authenticate it -- what ties an opened amount to an output is the confirmation V_0 == v g + Gamma h of the call below.
+ *   blind_key : 32 bytes (HOST); it travels to the kernel by value and is stored nowhere
+ *   d_in, d_out : count x uint64_t (device); may be the same buffer
+ * Errors: BPP_E_ARG for a NULL ctx, blind_key, d_in or d_out and a count above 0x7fffffff / 64; count = 0 is BPP_OK.
+ * Asynchronous on `stream`; the host twin takes host buffers and is synchronous. */
+int bpp_amounts_seal_device(bpp_ctx *ctx, const uint8_t *blind_key, uint64_t index_base, const uint64_t *d_index,
+                            const uint64_t *d_in, size_t count, uint64_t *d_out, void *stream);
+int bpp_amounts_seal(bpp_ctx *ctx, const uint8_t *blind_key, uint64_t index_base, const uint64_t *index, const uint64_t *in,
+                     size_t count, uint64_t *out);
+
+/* ---- VERIFY a block and LIST the outputs of many view keys in one call ----
+ * What a scanning service wants of a block: one verdict per proof and the short list of outputs that belong to its keys.
+ * With the calls above that is bpp_range_verify_batch_serialized_mixed_device, then
+ * bpp_range_scan_serialized_mixed_keys_device on what passed, then a walk over 36 bytes per (key, proof) pair.  This call
+ * runs their common front (index upload, container decode, membership test, challenges) ONCE, then today's exact pass
+ * per class, then for the single outputs the many-key scan's pair kernels, the confirmation and a compaction.
+ * THIS CALL IS A VERIFICATION OF THE BLOCK: d_ok[i] is exactly the word bpp_range_verify_batch_serialized_mixed_device
+ * writes for the same bytes and flags -- 0 Ok / 1 VerificationError / 2 FormatError -- for every proof, aggregated ones
+ * included.  A HIT is a pair (key j, proof i) with
+ *     m_i = 1,  d_ok[i] == 0,  no zero challenge (the coefficients of Gamma are defined),  V_0 == v g + Gamma h
+ * where Gamma is the mask recovered under key j and v the candidate amount of the pair.  A HIT IMPLIES A VERIFIED PROOF:
+ * a proof that opens under its owner's key but fails verification (a tampered r', say) is status 0 in the scan calls and
+ * is NOT a hit here.  Aggregated proofs (m_i > 1) are verified and never listed.
+ * EVERY KEY HERE TOGETHER WITH THE INDEX IS A VIEW KEY, as stated above.  The device call reads the keys from the
+ * caller's buffer into registers and copies them nowhere: nothing derived from a key but Gamma, and for a hit its
+ * amount, reaches memory, and no Gamma of a pair that is not a hit is left in the workspace when the call's kernels
+ * have run.  The host twin uploads the keys into a buffer of its own and overwrites that buffer before freeing it, on
+ * every return path.
+ *   d_proofs, d_commitments, m_of, count, d_keys, n_keys, index_base, d_index :
+ *                   as bpp_range_scan_serialized_mixed_keys_device takes them
+ *   flags         : BPP_SER_TRANSCRIPT (REQUIRED) | BPP_SER_UNCOMPRESSED | BPP_PROVE_AMOUNT64, each meaning what it means
+ *                   there, | BPP_FIND_AMOUNTS_SEALED
+ *   d_amounts     : REQUIRED (nothing could be confirmed without it).  With BPP_FIND_AMOUNTS_SEALED: count x uint64_t
+ *                   sealed amounts in caller order, SHARED BY ALL KEYS -- the candidate of pair (j, i) is
+ *                   d_amounts[i] XOR pad(key_j, index_i), formed in registers.  Without it: the KEY-MAJOR
+ *                   n_keys x count array of the many-key scan.  Read for m_i = 1 only.
+ *   d_ok          : count words, caller order, as above
+ *   d_hits        : max_hits records of 12 words: [key number j, caller position i, amount lo, amount hi, Gamma as 8
+ *                   canonical words], IN ASCENDING (key number, caller position) ORDER, the same from run to run
+ *   d_n_hits      : one word: the number of hits FOUND.  When it exceeds max_hits only the first max_hits records in that
+ *                   order are written; nothing beyond min(n_hits, max_hits) records is touched, and the caller sees the
+ *                   overflow from the count.  d_hits may be NULL when max_hits = 0.
+ *   d_workspace   : bpp_verify_find_serialized_mixed_keys_workspace_bytes(v, m_of, count, n_keys) bytes (0 when an m_i is
+ *                   not taken or n_keys x count is over the bound); it grows with n_keys: 44 bytes per pair
+ * Nothing else is written: no dense status matrix, no dense mask matrix.
+ * Errors: BPP_E_ARG for a NULL required pointer (d_ok and d_n_hits among them; with n_keys > 0 also d_keys, d_amounts, and
+ * d_hits when max_hits > 0), a
+ * d_keys that is not 4-byte aligned, flags without BPP_SER_TRANSCRIPT, an unknown flag, an m_of[i] that is not taken (the
+ * text names i), n_keys x count above 0x7fffffff / 64 (checked without overflow), a workspace that is too small; nothing
+ * is enqueued and nothing is written then.  count = 0 is BPP_OK with d_n_hits[0] = 0 and nothing else written.
+ * n_keys = 0 is BPP_OK with d_n_hits[0] = 0 too, AND THE BLOCK IS VERIFIED ALL THE SAME: d_ok is written as above (the
+ * pass needs no key; d_keys, d_amounts and d_hits are not read and may be NULL), so d_ok never comes back unwritten from
+ * a successful call with count > 0.  The device call BLOCKS the host only while it uploads the per-proof index; the host
+ * twin is synchronous and writes min(n_hits, max_hits) records. */
+#define BPP_FIND_AMOUNTS_SEALED 0x200
+size_t bpp_verify_find_serialized_mixed_keys_workspace_bytes(const bpp_verifier *v, const uint32_t *m_of, size_t count,
+                                                             size_t n_keys);
+int bpp_range_verify_find_serialized_mixed_keys_device(bpp_verifier *v, const void *d_proofs, const void *d_commitments,
+                                                       const uint32_t *m_of, size_t count, int flags, const uint8_t *d_keys,
+                                                       size_t n_keys, uint64_t index_base, const uint64_t *d_index,
+                                                       const uint64_t *d_amounts, uint32_t *d_ok, uint32_t *d_hits,
+                                                       size_t max_hits, uint32_t *d_n_hits, void *d_workspace,
+                                                       size_t workspace_bytes, void *stream);
+int bpp_range_verify_find_serialized_mixed_keys(bpp_verifier *v, const uint8_t *proofs, const uint8_t *commitments,
+                                                const uint32_t *m_of, size_t count, int flags, const uint8_t *keys,
+                                                size_t n_keys, uint64_t index_base, const uint64_t *index,
+                                                const uint64_t *amounts, uint32_t *out_ok, uint32_t *out_hits, size_t max_hits,
+                                                uint32_t *out_n_hits);
+
 /* ---- the weighted inner product argument as a seam of its own: WeightedInnerProductProof::{prove, verify} ----
  * Reference: src/weighted_inner_product_proof.rs:36-227 (prove), :238-328 (verify), :330-382 (verification_scalars).
  * An engine created for (n, m) proves and verifies the WIP relation over its key for ANY statement that ends in one; only

@@ -18,6 +18,7 @@
 // Result-like `std::optional<ProofError>` (nullopt = Ok(())).  Every operation runs HIP kernels through
 // libbpp_amd.so; nothing here computes on the CPU beyond (de)serialisation.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -268,6 +269,76 @@ inline ScanResult scan_serialized_mixed_keys(bpp_verifier* engine, const std::ve
     r.masks.resize(pairs);
     for (size_t i = 0; i < pairs; i++)
         for (int t = 0; t < 4; t++) r.masks[i].e[t] = out[i * 4 + t];
+    return r;
+}
+
+// amount XOR pad(blind_key, index) per amount (bpp_amounts_seal): seals amounts, and opens sealed ones.  The index of amount
+// i is index[i], or index_base + i: the blinding index of the output's proof.
+inline std::vector<uint64_t> seal_amounts(bpp_ctx* ctx, const std::array<uint8_t, 32>& blind_key,
+                                          const std::vector<uint64_t>& amounts, uint64_t index_base = 0,
+                                          const std::vector<uint64_t>& index = {}) {
+    if (!index.empty() && index.size() != amounts.size()) throw std::logic_error("seal_amounts: one index per amount");
+    std::vector<uint64_t> out(amounts.size() + 1);
+    if (bpp_amounts_seal(ctx, blind_key.data(), index_base, index.empty() ? nullptr : index.data(), amounts.data(), amounts.size(),
+                         out.data()) != BPP_OK)
+        throw std::runtime_error(std::string("bpp_amounts_seal: ") + bpp_last_error());
+    out.resize(amounts.size());
+    return out;
+}
+
+// Verifying a block AND listing the single outputs that belong to `keys` in one call, the common front of
+// bpp_range_verify_batch_serialized_mixed and scan_serialized_mixed_keys run once
+// (bpp_range_verify_find_serialized_mixed_keys).  `amounts`: sealed -- one sealed amount per proof, shared by all keys; else
+// key-major, keys.size() x ms.size() candidates.  ok[i]: the verdict of proof i under the transcript, 0 / 1 / 2.  hits: in
+// ascending (key number, position), at most max_hits of them; found: how many there are.  A hit is a VERIFIED single output
+// whose commitment opens to the amount and the mask recovered under that key.  Every key is a view key.  With no keys the
+// block is verified all the same (ok is the library's in every case, never a default).
+struct FindHit {
+    uint32_t key_no, position;
+    uint64_t amount;
+    PrimeFieldElem mask;
+};
+struct FindResult {
+    std::vector<uint32_t> ok;
+    std::vector<FindHit> hits;
+    size_t found;
+};
+inline FindResult verify_find_serialized_mixed_keys(bpp_verifier* engine, const std::vector<uint8_t>& proofs,
+                                                    const std::vector<uint8_t>& commitments, const std::vector<uint32_t>& ms,
+                                                    const std::vector<std::array<uint8_t, 32>>& keys,
+                                                    const std::vector<uint64_t>& amounts, bool sealed, size_t max_hits,
+                                                    uint64_t index_base = 0, const std::vector<uint64_t>& index = {},
+                                                    bool amount64 = false, bool uncompressed = false) {
+    const size_t pairs = keys.size() * ms.size();
+    if (!index.empty() && index.size() != ms.size()) throw std::logic_error("verify_find_serialized_mixed_keys: one index per proof");
+    if (amounts.size() != (sealed ? ms.size() : pairs))
+        throw std::logic_error("verify_find_serialized_mixed_keys: one sealed amount per proof, or K x count amounts");
+    const size_t cap = std::min(max_hits, pairs);
+    FindResult r;
+    r.ok.assign(ms.size() + 1, 0);
+    std::vector<uint32_t> rec(cap * 12 + 1);
+    std::vector<uint8_t> packed(keys.size() * 32 + 1);
+    for (size_t j = 0; j < keys.size(); j++)
+        for (size_t t = 0; t < 32; t++) packed[j * 32 + t] = keys[j][t];
+    const int flags = BPP_SER_TRANSCRIPT | (uncompressed ? BPP_SER_UNCOMPRESSED : 0) | (amount64 ? BPP_PROVE_AMOUNT64 : 0) |
+                      (sealed ? BPP_FIND_AMOUNTS_SEALED : 0);
+    uint32_t found = 0;
+    const int rc = bpp_range_verify_find_serialized_mixed_keys(engine, proofs.data(), commitments.data(), ms.data(), ms.size(),
+                                                               flags, packed.data(), keys.size(), index_base,
+                                                               index.empty() ? nullptr : index.data(), amounts.data(),
+                                                               r.ok.data(), rec.data(), cap, &found);
+    for (volatile uint8_t& b : packed) b = 0;   // the packed copy of the keys made here
+    if (rc != BPP_OK) throw std::runtime_error(std::string("bpp_range_verify_find_serialized_mixed_keys: ") + bpp_last_error());
+    r.ok.resize(ms.size());
+    r.found = found;
+    r.hits.resize(std::min<size_t>(found, cap));
+    for (size_t h = 0; h < r.hits.size(); h++) {
+        const uint32_t* w = rec.data() + h * 12;
+        r.hits[h].key_no = w[0];
+        r.hits[h].position = w[1];
+        r.hits[h].amount = (uint64_t)w[2] | (uint64_t)w[3] << 32;
+        for (int t = 0; t < 4; t++) r.hits[h].mask.e[t] = (uint64_t)w[4 + 2 * t] | (uint64_t)w[5 + 2 * t] << 32;
+    }
     return r;
 }
 

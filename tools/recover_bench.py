@@ -15,8 +15,15 @@ alarm is raised only when the interpreter has control again, so run the whole to
            by repetition; both medians, their ratio with the spread of the per-repetition ratios.  --side many|single runs
            one side alone (the run to put under rocprofv3 --kernel-trace --stats); --kernel-stats SIDE=CSV[,SIDE=CSV] folds
            such runs' k_kernel_stats.csv into an existing --out file as the per-kernel split (no GPU needed).
+  find     (--find --keys K[,K..]) bpp_range_verify_find_serialized_mixed_keys_device with sealed amounts plus the copy of
+           d_ok, d_n_hits and the hit records to the host, against what a caller does today -- verify_serialized_mixed_device,
+           scan_serialized_mixed_keys_device, the copy of the verdicts and of the dense pair matrix -- on the `wallet` block,
+           alternated repetition by repetition.  The verdicts and the hit list are checked: a wrong one ends the
+           run with an error and the file says complete: false.  --side fused|today
+           runs one side alone; --kernel-stats fused=CSV,today=CSV folds their per-kernel split in.  The leg's result is
+           merged into an existing --out file under "find"; the other legs' results there stay.
 usage: timeout -k 10 1100 python tools/recover_bench.py [--reps 20] [--warmup 3] [--window 13] [--scale 1.0] [--legs sr]
-       [--blocks mixed,wallet] [--keys 1,4,16,64] [--side both] [--out profiles/recover_bench.json]"""
+       [--blocks mixed,wallet] [--keys 1,4,16,64] [--find] [--side both] [--out profiles/recover_bench.json]"""
 import argparse
 import csv
 import hashlib
@@ -221,6 +228,91 @@ def keys_leg(torch, B, a, bv, ks, args, out):
         del d_keys, d_am, d_kws, d_stK, d_mK
 
 
+def find_leg(torch, B, a, bv, ks, args, out):
+    """the fused verify-and-find call against verify + K-key scan + the copy of the pair matrix; key 0 made the block"""
+    ms = block_shapes("wallet", args.scale)
+    count = len(ms)
+    d_p, d_c, d_a = step(600, lambda: make_block(torch, B, a, bv, ms))
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    d_sealed = torch.zeros_like(d_a)
+    bv.seal_amounts_device(KEY, d_a.data_ptr(), count, d_sealed.data_ptr(), st, index_base=BASE)
+    vsb = bv.serialized_mixed_workspace_bytes(ms)
+    d_vws = torch.empty(vsb, dtype=torch.uint8, device=dev)
+    d_ok_f = torch.full((count,), 7, dtype=torch.int32, device=dev)
+    d_ok_t = torch.full((count,), 7, dtype=torch.int32, device=dev)
+    h_ok_f = torch.empty((count,), dtype=torch.int32, pin_memory=True)
+    h_ok_t = torch.empty((count,), dtype=torch.int32, pin_memory=True)
+    max_hits = count   # room for every output of one key
+    d_hits = torch.zeros((max_hits, 12), dtype=torch.int32, device=dev)
+    h_hits = torch.empty((max_hits, 12), dtype=torch.int32, pin_memory=True)
+    d_n = torch.zeros((1,), dtype=torch.int32, device=dev)
+    out["find"] = {"block": "wallet", "count": count, "side": args.side, "max_hits": max_hits, "by_keys": {}}
+    for K in ks:
+        keys = [KEY] + [hashlib.sha256(b"recover_bench key %d" % j).digest() for j in range(1, K)]
+        d_keys = torch.from_numpy(np.frombuffer(b"".join(keys), dtype=np.uint8).copy()).to(dev)
+        d_am = d_a.repeat(K)
+        fsb, ksb = bv.verify_find_workspace_bytes(ms, K), bv.scan_keys_workspace_bytes(ms, K)
+        d_fws = torch.empty(fsb, dtype=torch.uint8, device=dev)
+        d_kws = torch.empty(ksb, dtype=torch.uint8, device=dev)
+        d_stK = torch.full((K, count), 7, dtype=torch.int32, device=dev)
+        d_mK = torch.zeros((K, count, 4), dtype=torch.int64, device=dev)
+        h_stK = torch.empty((K, count), dtype=torch.int32, pin_memory=True)
+        h_mK = torch.empty((K, count, 4), dtype=torch.int64, pin_memory=True)
+        got = {}
+
+        def fused():
+            bv.verify_find_serialized_mixed_keys_device(d_p.data_ptr(), d_c.data_ptr(), ms, d_keys.data_ptr(), K,
+                                                        d_sealed.data_ptr(), d_ok_f.data_ptr(), d_hits.data_ptr(), max_hits,
+                                                        d_n.data_ptr(), d_fws.data_ptr(), fsb, st, sealed=True, index_base=BASE)
+            h_ok_f.copy_(d_ok_f, non_blocking=True)
+            got["n"] = int(d_n.cpu()[0])   # the count first, then as many records
+            w = min(got["n"], max_hits)
+            h_hits[:w].copy_(d_hits[:w], non_blocking=True)
+
+        def today():
+            bv.verify_serialized_mixed_device(d_p.data_ptr(), d_c.data_ptr(), ms, d_ok_t.data_ptr(), d_vws.data_ptr(), vsb, st,
+                                              transcript=True)
+            bv.scan_serialized_mixed_keys_device(d_p.data_ptr(), d_c.data_ptr(), ms, d_keys.data_ptr(), K, d_mK.data_ptr(),
+                                                 d_stK.data_ptr(), d_kws.data_ptr(), ksb, st, index_base=BASE,
+                                                 d_amounts=d_am.data_ptr())
+            h_ok_t.copy_(d_ok_t, non_blocking=True)
+            h_stK.copy_(d_stK, non_blocking=True)
+            h_mK.copy_(d_mK, non_blocking=True)
+
+        fns = {"both": [fused, today], "fused": [fused], "today": [today]}[args.side]
+        ts = step(900, lambda: alternate(torch, fns, args.reps, args.warmup))
+        torch.cuda.synchronize()
+        res = {"pairs": K * count, "find_workspace_bytes": fsb, "today_workspace_bytes": vsb + ksb,
+               "today_copy_bytes": K * count * 36 + count * 4}
+        if args.side in ("both", "fused"):
+            hits = h_hits.numpy().view(np.uint32)
+            amounts = hits[:, 2].astype(np.uint64) | hits[:, 3].astype(np.uint64) << np.uint64(32)
+            res["fused"] = stats(ts[0])
+            res["hits_found"] = got["n"]
+            res["fused_copy_bytes"] = count * 4 + 4 + min(got["n"], max_hits) * 48
+            res["verdicts_all_ok"] = bool((h_ok_f.numpy() == 0).all())
+            res["hits_as_expected"] = bool(got["n"] == count and (hits[:, 0] == 0).all() and
+                                           (hits[:, 1] == np.arange(count)).all() and
+                                           (amounts == d_a.cpu().numpy().view(np.uint64)).all())
+        if args.side in ("both", "today"):
+            res["today"] = stats(ts[-1])
+            status = h_stK.numpy()
+            res["status_as_expected"] = bool((status[0] == 0).all() and (status[1:] == 1).all() and (h_ok_t.numpy() == 0).all())
+        if args.side == "both":
+            res["masks_agree"] = bool((h_hits.numpy()[:, 4:].view(np.uint64).reshape(count, 4) ==
+                                       h_mK.numpy()[0].view(np.uint64)).all())
+            per_rep = [f / t for f, t in zip(ts[0], ts[1])]
+            res["ratio_fused_over_today"] = statistics.median(ts[0]) / statistics.median(ts[1])
+            res["ratio_per_rep"] = {"median": statistics.median(per_rep), "min": min(per_rep), "max": max(per_rep)}
+        out["find"]["by_keys"][str(K)] = res
+        print("find %d" % K, json.dumps(res), flush=True)
+        wrong = [c for c in ("verdicts_all_ok", "hits_as_expected", "status_as_expected", "masks_agree") if res.get(c) is False]
+        if wrong:   # a run that computed something else is no measurement: recorded as incomplete, non-zero exit
+            raise RuntimeError("find leg, K = %d: %s" % (K, ", ".join(wrong)))
+        del d_keys, d_am, d_fws, d_kws, d_stK, d_mK, h_stK, h_mK
+
+
 def merge_kernel_stats(args):
     """folds rocprofv3 k_kernel_stats.csv files (one per side) into the JSON at --out: no GPU"""
     with open(args.out) as f:
@@ -233,7 +325,8 @@ def merge_kernel_stats(args):
         split[side] = [{"kernel": r["Name"].split("(")[0], "calls": int(r["Calls"]), "total_ms": float(r["TotalDurationNs"]) * 1e-6,
                         "average_us": float(r["AverageNs"]) * 1e-3, "percent": float(r["Percentage"])} for r in rows
                        if float(r["Percentage"]) >= 0.1]
-    out.setdefault("keys", {})["kernel_split"] = split
+    leg = "find" if set(split) <= {"fused", "today"} else "keys"
+    out.setdefault(leg, {})["kernel_split"] = split
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
         f.write("\n")
@@ -243,7 +336,8 @@ def merge_kernel_stats(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--keys", default="")
-    ap.add_argument("--side", default="both", choices=("both", "many", "single"))
+    ap.add_argument("--find", action="store_true")
+    ap.add_argument("--side", default="both", choices=("both", "many", "single", "fused", "today"))
     ap.add_argument("--kernel-stats", default="")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -255,7 +349,9 @@ def main():
     args = ap.parse_args()
     if args.kernel_stats:
         return merge_kernel_stats(args)
-    if args.keys and "k" not in args.legs:
+    if args.find:
+        args.legs = "f"   # --find: that leg alone, at --keys
+    elif args.keys and "k" not in args.legs:
         args.legs = "k"   # --keys alone: the many-key leg alone
     import torch
     import bulletproofsplus_amd as B
@@ -272,15 +368,24 @@ def main():
                 recover_leg(torch, B, a, bv, log2n, args, out)
         if "k" in args.legs:
             keys_leg(torch, B, a, bv, [int(x) for x in (args.keys or "1,4,16,64").split(",")], args, out)
+        if "f" in args.legs:
+            find_leg(torch, B, a, bv, [int(x) for x in (args.keys or "1,16,64").split(",")], args, out)
         out["complete"] = True
     except StepTimeout:
         out["stopped"] = "a step ran into its time limit"
     finally:
+        complete = out["complete"]
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        if args.find and os.path.exists(args.out):   # beside what the other legs recorded there
+            with open(args.out) as f:
+                kept = json.load(f)
+            kept["find"] = dict(out.get("find", {}), reps=args.reps, warmup=args.warmup, window_bits=args.window,
+                                scale=args.scale, device=out["device"], complete=out["complete"])
+            out = kept
         with open(args.out, "w") as f:
             json.dump(out, f, indent=1, sort_keys=True)
             f.write("\n")
-    print(json.dumps({"complete": out["complete"], "out": args.out}))
+    print(json.dumps({"complete": complete, "out": args.out}))
 
 
 if __name__ == "__main__":
