@@ -248,6 +248,8 @@ def lib():
         L.bpp_debug_verifier_mulvec_workspace_bytes.argtypes = [vp, sz, ctypes.c_uint32]
         L.bpp_debug_verifier_mulvec_workspace_bytes.restype = sz
         L.bpp_debug_verifier_mulvec.argtypes = [vp, ctypes.c_uint32, vp, vp, sz, vp, vp, sz, vp, vp, vp]
+        # ... and its scalar stage on chosen proof scalars and challenges (host buffers, synchronous)
+        L.bpp_debug_verifier_scalars.argtypes = [vp, ctypes.c_uint32, vp, vp, sz, vp]
         _lib = L
     return _lib
 

@@ -3,7 +3,8 @@
 // device compiles them.  A translation unit of its own: none of this is compiled into the units of the hot kernels.
 // Like bpp_debug_field_op / bpp_debug_point_op (capi.hip) the entries are not part of include/bpp_amd.h.
 // Every pointer is a host pointer -- except in bpp_debug_verifier_mulvec, the verifier's back end (VerifyImpl::run_stage) on
-// MulVec scalars the test chooses, which takes device buffers as bpp_verifier_run does and adds no kernel.
+// MulVec scalars the test chooses, which takes device buffers as bpp_verifier_run does and adds no kernel.  Its front half,
+// the scalar stage (launch_verify_scalars) on challenges the test chooses, is bpp_debug_verifier_scalars: host pointers again.
 #include "host_util.hpp"
 
 #include "field_raw_ops.hpp"
@@ -245,6 +246,44 @@ static bool debug_view_shape(const bpp_verifier* v, uint32_t m_view, uint32_t& c
     if ((m_view & (m_view - 1)) || m_view >= v->s.m) return false;
     for (cls = 0; (1u << cls) < m_view; cls++) {}
     return true;
+}
+
+// The verifier's scalar stage -- k_vs_prepare and k_vs_expand through launch_verify_scalars, the function every pass calls
+// (with its dynamic-LDS opt-in) -- on proof scalars and challenges the caller chooses.  Host pointers, synchronous.
+//   m_view: as for bpp_debug_verifier_mulvec below; N and k are that shape's.
+//   scalars3 [count][3][4]: r', s', delta' ; challenges [count][3 + k][4]: y, z, e, e_1..e_k per proof (any 256-bit words:
+//     the kernels reduce them), or null: the shape's literals for every proof ; out [count][N][4]: the MulVec's scalars.
+extern "C" int bpp_debug_verifier_scalars(bpp_verifier* v, uint32_t m_view, const uint64_t* scalars3, const uint64_t* challenges,
+                                          size_t count, uint64_t* out) {
+    if (!v || !scalars3 || !out) return fail(BPP_E_ARG, "null argument");
+    uint32_t cls = 0;
+    if (!debug_view_shape(v, m_view, cls)) return fail(BPP_E_ARG, "m_view must be 0 or a power of two below m");
+    if (count == 0) return BPP_OK;
+    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    return guarded(Count{count, "count"}, [&]() -> int {
+        HIPCHK(hipSetDevice(v->ctx.device));
+        return dispatch(v->ctx.curve, [&](auto cv) -> int {
+            using C = decltype(cv);
+            const VerifyShape s = VerifyImpl<C>::class_shape(v, cls).s;
+            const size_t ch_words = (size_t)(3 + s.k) * 8, out_bytes = count * (size_t)s.N * 32;
+            DevBuf dps, dch, dprep, dout;
+            if (int rc = upload(dps, scalars3, count * 96)) return rc;
+            if (challenges) {
+                if (int rc = upload(dch, challenges, count * ch_words * 4)) return rc;
+            } else {
+                std::vector<uint32_t> lit;
+                default_challenges(s, lit);
+                if (int rc = upload(dch, lit.data(), lit.size() * 4)) return rc;
+            }
+            HIPCHK(dprep.alloc(count * vs_prep_bytes<C>(s)));
+            HIPCHK(dout.alloc(out_bytes));
+            if (int rc = launch_verify_scalars<C>(s, dps.u32(), dch.u32(), challenges ? (uint32_t)ch_words : 0u, dout.u32(), count,
+                                                  dprep.u32(), nullptr))
+                return rc;
+            HIPCHK(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+            return BPP_OK;
+        });
+    });
 }
 
 // The verifier's back end -- everything of a pass behind the scalar stage: k_var_digits, k_var_tables, k_var_windows,

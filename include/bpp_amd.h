@@ -193,7 +193,10 @@ size_t bpp_verifier_table_bytes(const bpp_verifier *v);
 
 /* One pass of the hot path over a resident batch, asynchronous on `stream` (a hipStream_t; NULL =
  * default stream).  d_challenges is NULL (the reference's hard-coded "transcript") or
- * count x (3 + k) scalars [y, z, e, e_1..e_k] per proof.
+ * count x (3 + k) scalars [y, z, e, e_1..e_k] per proof.  Any 256-bit words are taken: a value >= r stands for its
+ * residue mod r.  For a challenge that is 0 mod r the inverse the scalars call for (y^-1, e^-1 for m > 1, e_t^-1) is
+ * taken as 0 -- no honest transcript yields one; the proof is judged by the scalars that follow from that -- and the
+ * other proofs of the batch are unaffected.
  * Optional debug / parity outputs (NULL to skip):
  *   d_out_scalars: count x N scalars -- the MulVec scalars in the reference's MulVec order
  *                  (range/mod.rs:481-490 for m > 1, wip.rs:298-307 for m == 1)
@@ -852,6 +855,8 @@ int bpp_range_verify_find_serialized_mixed_keys(bpp_verifier *v, const uint8_t *
  * d_ok[i] = 0 iff the sum is the identity (ristretto255: the engine's class test); a proof with y = 0 gets 1.
  *   d_challenges     : NULL, or count x (1 + k) scalars [e, e_1..e_k] for a caller with a transcript of its own; it takes
  *                      precedence over flags.  Otherwise BPP_SER_TRANSCRIPT derives them from d_transcript and the record.
+ *                      Values >= r are taken as their residue mod r (so are d_y, d_scalars and d_statement); for an e_t
+ *                      that is 0 mod r the inverse e_t^-1 is taken as 0, and the other proofs of the batch are unaffected.
  *   d_out_scalars    : NULL, or count x N scalars, N = 2 len + 2k + 5 + nv, in MulVec order; d_out_result: NULL, or the sum
  *                      per proof -- both as for bpp_verifier_run, as is bpp_verifier_set_subgroup_check.
  * Both device calls only enqueue on `stream` (no host synchronisation, no host-side upload).  Errors: BPP_E_ARG for a NULL

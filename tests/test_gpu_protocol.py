@@ -179,7 +179,9 @@ def test_batch_verifier_reference_sizes(golden, case_idx, c):
     assert ok.tolist() == [0, 1, 1, 0]
     _, exp_sc, _ = O.range_verify(opk, n, m, pts, sc, V, want_scalars=True, skip_msm=True)
     assert np.array_equal(got_sc[0], exp_sc) and np.array_equal(got_sc[3], exp_sc)
-    assert got_sc.shape[1] == 2 * n * m + 2 * (pts.shape[0] - 3) // 2 * 1 + m + 5 or True
+    k = (pts.shape[0] - 3) // 2
+    assert n * m == 1 << k
+    assert got_sc.shape[1] == 2 * n * m + 2 * k + m + 5
     assert bv.msm_len == exp_sc.shape[0]
     assert a.is_zero(got_res[0]) and a.is_zero(got_res[3])
     assert not a.is_zero(got_res[1]) and not a.is_zero(got_res[2])
