@@ -731,6 +731,80 @@ impl BatchVerifier {
             .collect();
         Ok((ok, hits, found as usize))
     }
+    /// view_tag(blind_key, index) per output (include/bpp_amd.h: bpp_view_tags): the byte a SENDER attaches to an output
+    /// next to its sealed amount.  The index of output i is index[i], or index_base + i.  The tag authenticates nothing.
+    pub fn view_tags(&self, blind_key: &[u8; 32], index_base: u64, index: Option<&[u64]>, count: usize)
+                     -> Result<Vec<u8>, ProofError> {
+        if index.map_or(false, |x| x.len() != count) || count > 0x7fff_ffff / 64 {
+            return Err(ProofError::FormatError);
+        }
+        let mut out = vec![0u8; count];
+        if count == 0 {
+            return Ok(out);
+        }
+        let rc = unsafe {
+            ffi::bpp_view_tags(ctx(), blind_key.as_ptr(), index_base, index.map_or(std::ptr::null(), |x| x.as_ptr()), count,
+                               out.as_mut_ptr())
+        };
+        assert!(rc == 0, "bpp_view_tags: {}", rc);
+        Ok(out)
+    }
+    /// `verify_find_serialized_mixed_keys` with the outputs' view tags (include/bpp_amd.h:
+    /// bpp_range_verify_find_tagged_serialized_mixed_keys): `tags` holds one byte per proof, shared by all keys; a pair
+    /// whose tag does not match its key is ruled out after one hash.  Result: the untagged call's three, and the number of
+    /// pairs that passed the tag test.
+    pub fn verify_find_tagged_serialized_mixed_keys(&self, proofs: &[u8], commitments: &[u8], ms: &[u32], amount64: bool,
+                                                    sealed: bool, keys: &[[u8; 32]], index_base: u64, index: Option<&[u64]>,
+                                                    amounts: &[u64], tags: &[u8], max_hits: usize)
+                                                    -> Result<(Vec<u32>, Vec<(u32, u32, u64, PrimeFieldElem)>, usize, usize), ProofError> {
+        let n = 1usize << (self.k - self.m.trailing_zeros() as usize);
+        let cb = unsafe { ffi::bpp_point_compressed_bytes(ffi::BPP_BLS12_381_G1) };
+        let (mut pbytes, mut cbytes) = (0usize, 0usize);
+        for &mi in ms {
+            let mi = mi as usize;
+            if mi == 0 || !mi.is_power_of_two() || mi > self.m {
+                return Err(ProofError::FormatError);
+            }
+            pbytes += unsafe { ffi::bpp_proof_bytes(ffi::BPP_BLS12_381_G1, n, mi) };
+            cbytes += mi * cb;
+        }
+        let pairs = match keys.len().checked_mul(ms.len()) {
+            Some(p) if p <= (0x7fff_ffff / 64) => p,
+            _ => return Err(ProofError::FormatError),
+        };
+        if pbytes != proofs.len() || cbytes != commitments.len() || index.map_or(false, |x| x.len() != ms.len())
+            || amounts.len() != if sealed { ms.len() } else { pairs } || tags.len() != ms.len() {
+            return Err(ProofError::FormatError);
+        }
+        if ms.is_empty() {
+            return Ok((Vec::new(), Vec::new(), 0, 0));
+        }
+        let flags = ffi::BPP_SER_TRANSCRIPT | if amount64 { ffi::BPP_PROVE_AMOUNT64 } else { 0 }
+            | if sealed { ffi::BPP_FIND_AMOUNTS_SEALED } else { 0 };
+        let cap = max_hits.min(pairs);
+        let mut packed: Vec<u8> = keys.iter().flat_map(|k| k.iter().copied()).collect();
+        let mut ok = vec![0u32; ms.len()];
+        let mut rec = vec![0u32; cap * 12];
+        let (mut found, mut candidates) = (0u32, 0u32);
+        let rc = unsafe {
+            ffi::bpp_range_verify_find_tagged_serialized_mixed_keys(self.handle, proofs.as_ptr(), commitments.as_ptr(), ms.as_ptr(),
+                                                                    ms.len(), flags, packed.as_ptr(), keys.len(), index_base,
+                                                                    index.map_or(std::ptr::null(), |x| x.as_ptr()), amounts.as_ptr(),
+                                                                    ok.as_mut_ptr(), if cap > 0 { rec.as_mut_ptr() } else { std::ptr::null_mut() },
+                                                                    cap, &mut found, tags.as_ptr(), &mut candidates)
+        };
+        for b in packed.iter_mut() {
+            unsafe { std::ptr::write_volatile(b, 0) };   // the packed copy of the keys made here
+        }
+        assert!(rc == 0, "bpp_range_verify_find_tagged_serialized_mixed_keys: {}", rc);
+        let hits = rec.chunks(12).take((found as usize).min(cap))
+            .map(|h| {
+                let w = |t: usize| h[4 + 2 * t] as u64 | (h[5 + 2 * t] as u64) << 32;
+                (h[0], h[1], h[2] as u64 | (h[3] as u64) << 32, PrimeFieldElem([w(0), w(1), w(2), w(3)]))
+            })
+            .collect();
+        Ok((ok, hits, found as usize, candidates as usize))
+    }
 }
 
 /// The cuts of a batch over `world` shards (include/bpp_amd.h: bpp_shard_cuts): shard r takes proofs

@@ -1456,6 +1456,34 @@ class BatchVerifier:
                                           _ptr(out) if len(am) else None), "bpp_amounts_seal")
         return out
 
+    def view_tags_device(self, blind_key: bytes, count: int, d_out: int, stream: int = 0, index_base: int = 0, d_index: int = 0):
+        """d_out[i] = view_tag(blind_key, d_index[i] or index_base + i) over count resident bytes: the byte a sender
+        attaches to an output next to its sealed amount (bpp_view_tags_device)"""
+        check(_lib.lib().bpp_view_tags_device(self.arith.handle, blind_key, ctypes.c_uint64(index_base), d_index or None, count,
+                                              d_out or None, stream or None), "bpp_view_tags_device")
+
+    def view_tags(self, blind_key: bytes, count: int = None, index_base: int = 0, index=None) -> np.ndarray:
+        """count outputs from index_base, or one blinding index per output -> (count,) u8, the first byte of
+        SHA-256(key || "bppt" || index || 0 || 0) (bpp_view_tags).  The tag authenticates nothing."""
+        idx = None
+        if index is not None:
+            idx = np.ascontiguousarray(np.asarray([int(x) for x in index], dtype=np.uint64))
+            if count is not None and len(idx) != count:
+                raise RuntimeError("view_tags: one blinding index per output")
+            count = len(idx)
+        count = int(count or 0)
+        out = np.zeros(count, dtype=np.uint8)
+        check(_lib.lib().bpp_view_tags(self.arith.handle, blind_key, ctypes.c_uint64(index_base),
+                                       _ptr(idx) if idx is not None and count else None, count, _ptr(out) if count else None),
+              "bpp_view_tags")
+        return out
+
+    def verify_find_tagged_workspace_bytes(self, ms, n_keys: int) -> int:
+        """bytes of device workspace verify_find_serialized_mixed_keys_device needs when d_tags is given (0 where
+        verify_find_workspace_bytes gives 0): room for every pair being a candidate"""
+        m = self._ms(ms)
+        return _lib.lib().bpp_verify_find_tagged_workspace_bytes(self.handle, _ptr(m) if len(m) else None, len(m), n_keys)
+
     def verify_find_workspace_bytes(self, ms, n_keys: int) -> int:
         """bytes of device workspace verify_find_serialized_mixed_keys_device needs (0: an m_i is not taken, or
         n_keys x count is over the bound); grows with n_keys"""
@@ -1467,14 +1495,25 @@ class BatchVerifier:
                                                  d_amounts: int, d_ok: int, d_hits: int, max_hits: int, d_n_hits: int,
                                                  d_workspace: int, workspace_bytes: int, stream: int = 0,
                                                  uncompressed: bool = False, amount64: bool = False, sealed: bool = False,
-                                                 index_base: int = 0, d_index: int = 0):
+                                                 index_base: int = 0, d_index: int = 0, d_tags: int = 0, d_n_candidates: int = 0):
         """Verifies a resident block (d_ok: verify_serialized_mixed_device's words under the transcript) and lists the
         single outputs that belong to the n_keys view keys at d_keys, the front run once.  d_amounts: sealed -- count u64
         sealed amounts shared by all keys; else (n_keys, count) u64 candidates, key-major.  d_hits: max_hits records of 12
         u32 [key number, position, amount lo, hi, mask as 8 words] in ascending (key number, position); d_n_hits: one u32,
         the hits found -- above max_hits, only the first max_hits are written.  A hit is a VERIFIED single output whose
-        commitment opens to the amount and the mask recovered under that key."""
+        commitment opens to the amount and the mask recovered under that key.  d_tags (None or 0: the untagged entry):
+        count resident view-tag bytes, shared by all keys -- the tagged entry, which rules a pair out after one hash when
+        its tag does not match, takes verify_find_tagged_workspace_bytes of workspace and writes the number of pairs that
+        passed the tag test to d_n_candidates (one u32) when that is given."""
         m = self._ms(ms)
+        if d_tags:
+            check(_lib.lib().bpp_range_verify_find_tagged_serialized_mixed_keys_device(
+                self.handle, d_proofs, d_commitments, _ptr(m) if len(m) else None, len(m),
+                1 | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0) | (AMOUNTS_SEALED if sealed else 0), d_keys or None,
+                n_keys, ctypes.c_uint64(index_base), d_index or None, d_amounts or None, d_ok or None, d_hits or None, max_hits,
+                d_n_hits or None, d_tags, d_n_candidates or None, d_workspace, workspace_bytes, stream or None),
+                "bpp_range_verify_find_tagged_serialized_mixed_keys_device")
+            return
         check(_lib.lib().bpp_range_verify_find_serialized_mixed_keys_device(
             self.handle, d_proofs, d_commitments, _ptr(m) if len(m) else None, len(m),
             1 | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0) | (AMOUNTS_SEALED if sealed else 0), d_keys or None,
@@ -1483,13 +1522,15 @@ class BatchVerifier:
 
     def verify_find_serialized_mixed_keys(self, proofs, commitments, ms=None, keys=(), amounts=(), sealed: bool = False,
                                           uncompressed: bool = False, amount64: bool = False, index_base: int = 0, index=None,
-                                          max_hits: int = None):
+                                          max_hits: int = None, tags=None):
         """proofs, commitments, ms, keys, index: as scan_serialized_mixed_keys; amounts: sealed -- one sealed amount per
         proof; else K x count candidates (amounts[j][i]: proof i under key j); max_hits: None for room for every pair
         -> (ok (count,) u32, hits, found): ok as verify_serialized_mixed under the transcript; hits the list of
         (key_no, position, amount, mask) in ascending (key_no, position), at most max_hits of them; found the number of
         hits there are (bpp_range_verify_find_serialized_mixed_keys).  With no keys the block is verified all the same
-        and no hit is listed."""
+        and no hit is listed.  tags (None or 0: the untagged entry): one view-tag byte per proof, shared by all keys -- a pair
+        whose tag does not match its key is ruled out after one hash, and the result is (ok, hits, found, candidates) with
+        candidates the number of pairs that passed the tag test (bpp_range_verify_find_tagged_serialized_mixed_keys)."""
         def flat(x):
             return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else \
                 np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
@@ -1521,23 +1562,38 @@ class BatchVerifier:
             am = np.ascontiguousarray(np.asarray([[int(x) for x in row] for row in amounts], dtype=np.uint64).reshape(-1))
             if len(am) != nk * count:
                 raise RuntimeError("verify_find_serialized_mixed_keys: K x count candidate amounts")
+        tg = None
+        if tags is not None and not (isinstance(tags, int) and tags == 0):
+            tg = flat(tags) if isinstance(tags, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(np.asarray([int(x) for x in tags], dtype=np.uint8).reshape(-1))
+            if len(tg) != count:
+                raise RuntimeError("verify_find_serialized_mixed_keys: one view tag per proof")
         cap = nk * count if max_hits is None else int(max_hits)
         kb = np.frombuffer(b"".join(keys), dtype=np.uint8).copy() if nk else None
         ok = np.zeros(count, dtype=np.uint32)
         rec = np.zeros((cap, 12), dtype=np.uint32)
         found = np.zeros(1, dtype=np.uint32)
+        cands = np.zeros(1, dtype=np.uint32)
         some = nk > 0 and count > 0
-        check(_lib.lib().bpp_range_verify_find_serialized_mixed_keys(
-            self.handle, _ptr(raw) if len(raw) else None, _ptr(cm) if len(cm) else None, _ptr(m) if count else None, count,
-            1 | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0) | (AMOUNTS_SEALED if sealed else 0),
-            _ptr(kb) if kb is not None else None, nk, ctypes.c_uint64(index_base), _ptr(idx) if idx is not None else None,
-            _ptr(am) if some else None, _ptr(ok) if count else None, _ptr(rec) if cap else None, cap, _ptr(found)),
-            "bpp_range_verify_find_serialized_mixed_keys")
+        if tg is not None:
+            check(_lib.lib().bpp_range_verify_find_tagged_serialized_mixed_keys(
+                self.handle, _ptr(raw) if len(raw) else None, _ptr(cm) if len(cm) else None, _ptr(m) if count else None, count,
+                1 | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0) | (AMOUNTS_SEALED if sealed else 0),
+                _ptr(kb) if kb is not None else None, nk, ctypes.c_uint64(index_base), _ptr(idx) if idx is not None else None,
+                _ptr(am) if some else None, _ptr(ok) if count else None, _ptr(rec) if cap else None, cap, _ptr(found),
+                _ptr(tg) if some else None, _ptr(cands)), "bpp_range_verify_find_tagged_serialized_mixed_keys")
+        else:
+            check(_lib.lib().bpp_range_verify_find_serialized_mixed_keys(
+                self.handle, _ptr(raw) if len(raw) else None, _ptr(cm) if len(cm) else None, _ptr(m) if count else None, count,
+                1 | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0) | (AMOUNTS_SEALED if sealed else 0),
+                _ptr(kb) if kb is not None else None, nk, ctypes.c_uint64(index_base), _ptr(idx) if idx is not None else None,
+                _ptr(am) if some else None, _ptr(ok) if count else None, _ptr(rec) if cap else None, cap, _ptr(found)),
+                "bpp_range_verify_find_serialized_mixed_keys")
         if kb is not None:
             kb[:] = 0   # the packed copy of the keys made here
         n = int(found[0])
         hits = [(int(r[0]), int(r[1]), int(r[2]) | int(r[3]) << 32, wire_to_int(np.ascontiguousarray(r[4:]).view(np.uint64))) for r in rec[:min(n, cap)]]
-        return ok, hits, n
+        return (ok, hits, n) if tg is None else (ok, hits, n, int(cands[0]))
 
 
 def shard_cuts(ms, count: int, world: int) -> np.ndarray:

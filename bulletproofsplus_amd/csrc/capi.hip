@@ -11,6 +11,7 @@
 #include "impl_wip.hpp"
 #include "recover.hpp"
 #include "find.hpp"
+#include "find_tags.hpp"
 #include "recover_keys.hpp"
 
 using namespace bpp;
@@ -1554,6 +1555,83 @@ extern "C" int bpp_range_verify_find_serialized_mixed_keys(bpp_verifier* v, cons
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
         return FindImpl<decltype(cv)>::find_host(v, proofs, commitments, m_of, count, flags, keys, n_keys, index_base, index,
                                                  amounts, out_ok, out_hits, max_hits, out_n_hits);
+    });
+}
+
+// ---- view tags, and the verify-and-find call that tests them first (find_tags.hpp) ----
+extern "C" int bpp_view_tags_device(bpp_ctx* ctx, const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_index,
+                                    size_t count, uint8_t* d_out, void* stream) {
+    if (!ctx || !blind_key) return fail(BPP_E_ARG, "null argument");
+    if (count == 0) return BPP_OK;
+    if (!d_out) return fail(BPP_E_ARG, "null argument");
+    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    return on_ctx(*ctx, {count, "count"}, [&](auto cv) -> int {
+        return FindTagsImpl<decltype(cv)>::tags(blind_key, index_base, d_index, count, d_out, static_cast<hipStream_t>(stream));
+    });
+}
+
+extern "C" int bpp_view_tags(bpp_ctx* ctx, const uint8_t* blind_key, uint64_t index_base, const uint64_t* index, size_t count,
+                             uint8_t* out) {
+    if (!ctx || !blind_key) return fail(BPP_E_ARG, "null argument");
+    if (count == 0) return BPP_OK;
+    if (!out) return fail(BPP_E_ARG, "null argument");
+    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    return on_ctx(*ctx, {count, "count"}, [&](auto cv) -> int {
+        return FindTagsImpl<decltype(cv)>::tags_host(blind_key, index_base, index, count, out);
+    });
+}
+
+extern "C" size_t bpp_verify_find_tagged_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys) {
+    if ((count && !m_of) || !pairs_bounded(n_keys, count) || !m_of_wellformed(m_of, count)) return 0;
+    return size_for(v, [&](auto cv) { return FindTagsImpl<decltype(cv)>::workspace_bytes(v, m_of, count, n_keys); });
+}
+
+extern "C" int bpp_range_verify_find_tagged_serialized_mixed_keys_device(
+    bpp_verifier* v, const void* d_proofs, const void* d_commitments, const uint32_t* m_of, size_t count, int flags,
+    const uint8_t* d_keys, size_t n_keys, uint64_t index_base, const uint64_t* d_index, const uint64_t* d_amounts, uint32_t* d_ok,
+    uint32_t* d_hits, size_t max_hits, uint32_t* d_n_hits, const uint8_t* d_tags, uint32_t* d_n_candidates, void* d_workspace,
+    size_t workspace_bytes, void* stream) {
+    if (!v || !d_n_hits) return fail(BPP_E_ARG, "null argument");
+    if (flags & ~FIND_FLAGS) return fail(BPP_E_ARG, "unknown flag");
+    if (count == 0)   // no proof: no verdict, no candidate, no hit
+        return on_device(v->ctx.device, [&]() -> int {
+            HIPCHK(zero_words_async(d_n_hits, 4, static_cast<hipStream_t>(stream)));
+            if (d_n_candidates) HIPCHK(zero_words_async(d_n_candidates, 4, static_cast<hipStream_t>(stream)));
+            return BPP_OK;
+        });
+    // without keys the block is verified all the same, as in the untagged call
+    if (!d_proofs || !d_commitments || !m_of || !d_ok || !d_workspace) return fail(BPP_E_ARG, "null argument");
+    if (n_keys && (!d_keys || !d_amounts || !d_tags || (!d_hits && max_hits))) return fail(BPP_E_ARG, "null argument");
+    if (n_keys && (reinterpret_cast<uintptr_t>(d_keys) & 3)) return fail(BPP_E_ARG, "d_keys must be 4-byte aligned");
+    if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
+    if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return FindTagsImpl<decltype(cv)>::find(
+            v, static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), m_of, count,
+            (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u, (flags & BPP_PROVE_AMOUNT64) != 0, (flags & BPP_FIND_AMOUNTS_SEALED) != 0,
+            d_keys, n_keys, index_base, d_index, d_amounts, d_ok, d_hits, max_hits, d_n_hits, d_tags, d_n_candidates, d_workspace,
+            workspace_bytes, static_cast<hipStream_t>(stream));
+    });
+}
+
+// host buffers in (keys, index, amounts and tags included), host verdicts, hit records and counts out
+extern "C" int bpp_range_verify_find_tagged_serialized_mixed_keys(
+    bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, const uint32_t* m_of, size_t count, int flags,
+    const uint8_t* keys, size_t n_keys, uint64_t index_base, const uint64_t* index, const uint64_t* amounts, uint32_t* out_ok,
+    uint32_t* out_hits, size_t max_hits, uint32_t* out_n_hits, const uint8_t* tags, uint32_t* out_n_candidates) {
+    if (!v || !out_n_hits) return fail(BPP_E_ARG, "null argument");
+    if (flags & ~FIND_FLAGS) return fail(BPP_E_ARG, "unknown flag");
+    if (count == 0) {   // no proof: no verdict, no candidate, no hit
+        *out_n_hits = 0;
+        if (out_n_candidates) *out_n_candidates = 0;
+        return BPP_OK;
+    }
+    if (!proofs || !commitments || !m_of || !out_ok) return fail(BPP_E_ARG, "null argument");
+    if (n_keys && (!keys || !amounts || !tags || (!out_hits && max_hits))) return fail(BPP_E_ARG, "null argument");
+    if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return FindTagsImpl<decltype(cv)>::find_host(v, proofs, commitments, m_of, count, flags, keys, n_keys, index_base, index,
+                                                     amounts, out_ok, out_hits, max_hits, out_n_hits, tags, out_n_candidates);
     });
 }
 

@@ -1,11 +1,17 @@
 // find_terms.hpp -- the arithmetic of the fused verify-and-find call (find.hpp) that is not the curve's: the pad that
 // seals an output's amount, and the index arithmetic of the hit list's compaction.  Plain C++ beside recover_terms.hpp, so
-// the host test (tests/host/find_host_test.cpp) compiles the very code k_amounts_seal, k_find_confirm and the compaction
-// kernels run.
+// the host tests (tests/host/find_host_test.cpp, tests/host/view_tag_host_test.cpp) compile the very code k_amounts_seal,
+// k_find_confirm, the compaction kernels and the tag kernels of find_tags.hpp run.
 //
 // A sealed amount is amount XOR pad(key, idx): an output carries ONE 8-byte ciphertext of its amount and every view key
 // tries its own pad on it.  The pad is domain-separated from every blinding slot by its tag ("bppa" against blind_half's
 // "bppb"), so it is no function of any scalar that enters a proof.  Sealing and opening are the same operation.
+//
+// A view tag is ONE byte of the same block under a third tag ("bppt"): the sender attaches view_tag(key, idx) to the output,
+// and the tagged call (find_tags.hpp) computes it first -- one compression per (key, output) pair -- and expands slots and
+// walks tables only where it matches: 255 of 256 foreign pairs stop there.  The tag hides nothing that a one-byte PRF
+// output does not, and it authenticates nothing: a wrong tag hides an output from its owner's scan exactly as a wrong sealed
+// amount does.  Also here: how the tag test's lanes and the candidate list are numbered.
 #pragma once
 #include "recover_terms.hpp"
 
@@ -29,6 +35,24 @@ BPP_HD uint64_t amount_pad(const uint32_t* key, uint64_t idx) {
     return (uint64_t)bswap32(dg[0]) | (uint64_t)bswap32(dg[1]) << 32;
 }
 
+// the first byte of SHA-256(key || "bppt" || idx as u64 LE || 0 as u32 || 0 as u32): amount_pad's block under the third tag,
+// in registers alone
+BPP_HD uint8_t view_tag(const uint32_t* key, uint64_t idx) {
+    uint32_t w[16], dg[8];
+#pragma unroll
+    for (int t = 0; t < 8; t++) w[t] = bswap32(key[t]);
+    w[8] = 0x62707074u;   // "bppt", as the block's big-endian word
+    w[9] = bswap32((uint32_t)idx);
+    w[10] = bswap32((uint32_t)(idx >> 32));
+    w[11] = 0;
+    w[12] = 0;
+    w[13] = 0x80000000u;
+    w[14] = 0;
+    w[15] = 52 * 8;
+    sha256_one_block(w, dg);
+    return (uint8_t)(dg[0] >> 24);
+}
+
 // ---- the compaction of the hit flags into the ordered hit list --------------------------------------------------------
 // The flags of a call lie key-major, pair (j, i) at j * count + i: ascending position IS ascending (key number, caller
 // position).  A tile is FIND_TILE consecutive positions, read by one 64-lane block in FIND_ROUNDS rounds of 64; lane l of
@@ -49,5 +73,22 @@ BPP_HD uint32_t find_ballot_count(uint64_t ballot) { return (uint32_t)__builtin_
 BPP_HD uint32_t find_lane_rank(uint64_t ballot, uint32_t lane) {
     return find_ballot_count(ballot & (((uint64_t)1 << lane) - 1));
 }
+
+
+// ---- the tag test's lanes and the candidate list ------------------------------------------------------------------------
+// The pairs of the tag test lie key-major over the LAUNCH positions of the single-output class, pair (j, p) at
+// j * count + p, and each key's row is cut into tiles of FIND_TILE positions of its own (the last one short), so a tile
+// never straddles two keys: its key is uniform over the block that reads it.  Tile t belongs to key t / per_key and starts
+// at launch position (t % per_key) * FIND_TILE; lane l of round r holds launch position tag_launch_position(t, per_key, r, l),
+// a pair when that is below count.  What a tile leaves in memory is its FIND_ROUNDS ballots (one BIT per pair) and its
+// count; a candidate's place in the list is find's: the counts of the tiles before, the ballots of the rounds before, the
+// lanes below.  Tiles ascend with (key, position), so the list is in ascending key-major pair number tag_pair(j, p, count).
+BPP_HD size_t tag_tiles_per_key(size_t count) { return find_tiles(count); }
+BPP_HD size_t tag_tiles(size_t n_keys, size_t count) { return n_keys * tag_tiles_per_key(count); }
+BPP_HD size_t tag_tile_key(size_t tile, size_t per_key) { return tile / per_key; }
+BPP_HD size_t tag_launch_position(size_t tile, size_t per_key, uint32_t round, uint32_t lane) {
+    return find_position(tile % per_key, round, lane);
+}
+BPP_HD size_t tag_pair(size_t key_no, size_t position, size_t count) { return key_no * count + position; }
 
 }  // namespace bpp

@@ -819,6 +819,61 @@ int bpp_range_verify_find_serialized_mixed_keys(bpp_verifier *v, const uint8_t *
                                                 const uint64_t *amounts, uint32_t *out_ok, uint32_t *out_hits, size_t max_hits,
                                                 uint32_t *out_n_hits);
 
+/* ---- view tags: the one byte an output carries so that a scanner can rule out foreign keys cheaply ----
+ * The find call above pays 2k + 3 slot expansions, as many products in Fr and a table walk for EVERY (key, output) pair,
+ * and a service with hundreds of keys owns almost none of a block's outputs.  A tagged output carries one byte more:
+ *     view_tag(key, idx) = the first byte of SHA-256(key || "bppt" || idx as u64 LE || 0 as u32 || 0 as u32)
+ * the 52-byte block of the sealed amount's pad under a third domain tag (csrc/find_terms.hpp).  THE SENDER MAKES THE TAG,
+ * under the recipient's key, next to the sealed amount; the scanner computes it first -- ONE compression per pair -- and
+ * does the expensive work only where it matches: 255 of 256 foreign pairs stop there.  idx is the blinding index of the
+ * output's proof and THE INDEX RULE ABOVE HOLDS UNCHANGED: d_index[i] when given, else index_base + i.
+ * The tag hides nothing that a one-byte PRF output does not, and IT DOES NOT AUTHENTICATE ANYTHING: a wrong tag hides an
+ * output from its owner's scan exactly as a wrong sealed amount does, and a matching tag proves nothing -- what ties an
+ * output to a key is still the confirmation V_0 == v g + Gamma h.
+ *   blind_key : 32 bytes (HOST); it travels to the kernel by value and is stored nowhere
+ *   d_out     : count bytes (device)
+ * Errors: BPP_E_ARG for a NULL ctx, blind_key or d_out and a count above 0x7fffffff / 64; count = 0 is BPP_OK.
+ * Asynchronous on `stream`; the host twin takes host buffers and is synchronous. */
+int bpp_view_tags_device(bpp_ctx *ctx, const uint8_t *blind_key, uint64_t index_base, const uint64_t *d_index, size_t count,
+                         uint8_t *d_out, void *stream);
+int bpp_view_tags(bpp_ctx *ctx, const uint8_t *blind_key, uint64_t index_base, const uint64_t *index, size_t count,
+                  uint8_t *out);
+
+/* ---- VERIFY a block and LIST the outputs of many view keys, TESTING THE VIEW TAGS FIRST ----
+ * bpp_range_verify_find_serialized_mixed_keys_device with two more arguments; every other argument, every flag and every
+ * rule stated there holds here, and that call is unchanged.  d_ok IS EXACTLY THE UNTAGGED CALL'S.  A CANDIDATE is a pair
+ * (key j, proof i) with
+ *     m_i = 1,  d_ok[i] == 0,  the decoder's status 0,  no zero challenge,  view_tag(key_j, index_i) == d_tags[i]
+ * and A HIT IS A CANDIDATE THAT IS A HIT OF THE UNTAGGED CALL: the tag can only remove pairs.  Records, their order
+ * (ascending key number, then caller position), max_hits and d_n_hits are as there.  The tag is independent of how
+ * amounts are offered (sealed or key-major).
+ *   d_tags         : count bytes, caller order, SHARED BY ALL KEYS, read for m_i = 1 only; REQUIRED when n_keys > 0
+ *   d_n_candidates : one word, may be NULL: the pairs that passed the tag test (hits and chance matches of foreign keys)
+ *   d_workspace    : bpp_verify_find_tagged_workspace_bytes(v, m_of, count, n_keys) bytes, a function of those alone with
+ *                    room for every pair being a candidate; 0 where the untagged size function gives 0
+ * Per pair the call computes one compression and moves one bit; slots are expanded and tables walked for candidates only.
+ * The key rule, extended by one sentence: nothing derived from a key reaches memory but the candidate bit (the match of a
+ * public byte), the hit bit, Gamma of a candidate (zeroed on a miss) and a hit's amount.
+ * Errors: those of the untagged call, and BPP_E_ARG for a NULL d_tags with n_keys > 0; nothing is enqueued and nothing is
+ * written then.  count = 0 is BPP_OK with d_n_hits[0] = 0, and d_n_candidates[0] = 0 when given; n_keys = 0 and a block of
+ * nothing but aggregated proofs likewise, THE BLOCK VERIFIED ALL THE SAME (d_keys, d_amounts, d_tags, d_hits may be NULL).
+ * The device call BLOCKS the host only while it uploads the per-proof index: the candidate count never travels to the
+ * host.  The host twin is synchronous. */
+size_t bpp_verify_find_tagged_workspace_bytes(const bpp_verifier *v, const uint32_t *m_of, size_t count, size_t n_keys);
+int bpp_range_verify_find_tagged_serialized_mixed_keys_device(bpp_verifier *v, const void *d_proofs, const void *d_commitments,
+                                                              const uint32_t *m_of, size_t count, int flags,
+                                                              const uint8_t *d_keys, size_t n_keys, uint64_t index_base,
+                                                              const uint64_t *d_index, const uint64_t *d_amounts, uint32_t *d_ok,
+                                                              uint32_t *d_hits, size_t max_hits, uint32_t *d_n_hits,
+                                                              const uint8_t *d_tags, uint32_t *d_n_candidates, void *d_workspace,
+                                                              size_t workspace_bytes, void *stream);
+int bpp_range_verify_find_tagged_serialized_mixed_keys(bpp_verifier *v, const uint8_t *proofs, const uint8_t *commitments,
+                                                       const uint32_t *m_of, size_t count, int flags, const uint8_t *keys,
+                                                       size_t n_keys, uint64_t index_base, const uint64_t *index,
+                                                       const uint64_t *amounts, uint32_t *out_ok, uint32_t *out_hits,
+                                                       size_t max_hits, uint32_t *out_n_hits, const uint8_t *tags,
+                                                       uint32_t *out_n_candidates);
+
 /* ---- the weighted inner product argument as a seam of its own: WeightedInnerProductProof::{prove, verify} ----
  * Reference: src/weighted_inner_product_proof.rs:36-227 (prove), :238-328 (verify), :330-382 (verification_scalars).
  * An engine created for (n, m) proves and verifies the WIP relation over its key for ANY statement that ends in one; only

@@ -342,6 +342,67 @@ inline FindResult verify_find_serialized_mixed_keys(bpp_verifier* engine, const 
     return r;
 }
 
+// view_tag(blind_key, index) per output (bpp_view_tags): the byte a SENDER attaches to an output next to its sealed amount.
+// The index of output i is index[i], or index_base + i.  The tag authenticates nothing.
+inline std::vector<uint8_t> view_tags(bpp_ctx* ctx, const std::array<uint8_t, 32>& blind_key, size_t count, uint64_t index_base = 0,
+                                      const std::vector<uint64_t>& index = {}) {
+    if (!index.empty() && index.size() != count) throw std::logic_error("view_tags: one index per output");
+    std::vector<uint8_t> out(count + 1);
+    if (bpp_view_tags(ctx, blind_key.data(), index_base, index.empty() ? nullptr : index.data(), count, out.data()) != BPP_OK)
+        throw std::runtime_error(std::string("bpp_view_tags: ") + bpp_last_error());
+    out.resize(count);
+    return out;
+}
+
+// verify_find_serialized_mixed_keys with the outputs' view tags (bpp_range_verify_find_tagged_serialized_mixed_keys): `tags`
+// holds one byte per proof, shared by all keys; a pair whose tag does not match its key is ruled out after one hash.  ok
+// is the untagged call's; the hits are its hits among the candidates; candidates: the pairs that passed the tag test.
+struct FindTaggedResult {
+    std::vector<uint32_t> ok;
+    std::vector<FindHit> hits;
+    size_t found, candidates;
+};
+inline FindTaggedResult verify_find_tagged_serialized_mixed_keys(
+    bpp_verifier* engine, const std::vector<uint8_t>& proofs, const std::vector<uint8_t>& commitments,
+    const std::vector<uint32_t>& ms, const std::vector<std::array<uint8_t, 32>>& keys, const std::vector<uint64_t>& amounts,
+    bool sealed, const std::vector<uint8_t>& tags, size_t max_hits, uint64_t index_base = 0,
+    const std::vector<uint64_t>& index = {}, bool amount64 = false, bool uncompressed = false) {
+    const size_t pairs = keys.size() * ms.size();
+    if (!index.empty() && index.size() != ms.size())
+        throw std::logic_error("verify_find_tagged_serialized_mixed_keys: one index per proof");
+    if (amounts.size() != (sealed ? ms.size() : pairs))
+        throw std::logic_error("verify_find_tagged_serialized_mixed_keys: one sealed amount per proof, or K x count amounts");
+    if (tags.size() != ms.size()) throw std::logic_error("verify_find_tagged_serialized_mixed_keys: one tag per proof");
+    const size_t cap = std::min(max_hits, pairs);
+    FindTaggedResult r;
+    r.ok.assign(ms.size() + 1, 0);
+    std::vector<uint32_t> rec(cap * 12 + 1);
+    std::vector<uint8_t> packed(keys.size() * 32 + 1);
+    for (size_t j = 0; j < keys.size(); j++)
+        for (size_t t = 0; t < 32; t++) packed[j * 32 + t] = keys[j][t];
+    const int flags = BPP_SER_TRANSCRIPT | (uncompressed ? BPP_SER_UNCOMPRESSED : 0) | (amount64 ? BPP_PROVE_AMOUNT64 : 0) |
+                      (sealed ? BPP_FIND_AMOUNTS_SEALED : 0);
+    uint32_t found = 0, candidates = 0;
+    const int rc = bpp_range_verify_find_tagged_serialized_mixed_keys(
+        engine, proofs.data(), commitments.data(), ms.data(), ms.size(), flags, packed.data(), keys.size(), index_base,
+        index.empty() ? nullptr : index.data(), amounts.data(), r.ok.data(), rec.data(), cap, &found, tags.data(), &candidates);
+    for (volatile uint8_t& b : packed) b = 0;   // the packed copy of the keys made here
+    if (rc != BPP_OK)
+        throw std::runtime_error(std::string("bpp_range_verify_find_tagged_serialized_mixed_keys: ") + bpp_last_error());
+    r.ok.resize(ms.size());
+    r.found = found;
+    r.candidates = candidates;
+    r.hits.resize(std::min<size_t>(found, cap));
+    for (size_t h = 0; h < r.hits.size(); h++) {
+        const uint32_t* w = rec.data() + h * 12;
+        r.hits[h].key_no = w[0];
+        r.hits[h].position = w[1];
+        r.hits[h].amount = (uint64_t)w[2] | (uint64_t)w[3] << 32;
+        for (int t = 0; t < 4; t++) r.hits[h].mask.e[t] = (uint64_t)w[4 + 2 * t] | (uint64_t)w[5 + 2 * t] << 32;
+    }
+    return r;
+}
+
 // Verifier-side holder of the commitments.  It exists only in the reference's (stale) README
 // (README.md:47-55: RangeVerifier::new(), allocate(&prover.commitment_vec), proof.verify(.., &verifier));
 // the reference's code takes the commitment slice directly (range/mod.rs:57-62).  Both forms are offered.

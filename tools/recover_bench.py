@@ -22,8 +22,13 @@ alarm is raised only when the interpreter has control again, so run the whole to
            run with an error and the file says complete: false.  --side fused|today
            runs one side alone; --kernel-stats fused=CSV,today=CSV folds their per-kernel split in.  The leg's result is
            merged into an existing --out file under "find"; the other legs' results there stay.
+  tags     (--find --tags --keys K[,K..]) bpp_range_verify_find_tagged_serialized_mixed_keys_device against the untagged find
+           call ON THE SAME BUILD and against the call with no keys (the front and the pass alone), each with its copies to
+           the host, on the `wallet` block with the owner's view tags, alternated repetition by repetition:
+           medians, spreads, tagged / untagged with the per-repetition spread, and n_candidates / pairs.  Verdicts, hits and
+           the candidate count (against hashlib) are checked.  Merged into --out under "find_tags".
 usage: timeout -k 10 1100 python tools/recover_bench.py [--reps 20] [--warmup 3] [--window 13] [--scale 1.0] [--legs sr]
-       [--blocks mixed,wallet] [--keys 1,4,16,64] [--find] [--side both] [--out profiles/recover_bench.json]"""
+       [--blocks mixed,wallet] [--keys 1,4,16,64] [--find] [--tags] [--side both] [--out profiles/recover_bench.json]"""
 import argparse
 import csv
 import hashlib
@@ -31,6 +36,7 @@ import json
 import os
 import signal
 import statistics
+import struct
 import sys
 
 import numpy as np
@@ -313,6 +319,97 @@ def find_leg(torch, B, a, bv, ks, args, out):
         del d_keys, d_am, d_fws, d_kws, d_stK, d_mK, h_stK, h_mK
 
 
+def view_tag(key, idx):
+    """the first byte of SHA-256(key || "bppt" || idx as u64 LE || 0 || 0), by hashlib"""
+    return hashlib.sha256(key + b"bppt" + struct.pack("<QII", idx, 0, 0)).digest()[0]
+
+
+def tags_leg(torch, B, a, bv, ks, args, out):
+    """the tagged find call against the untagged one and against the call without keys; key 0 made the block and its tags"""
+    ms = block_shapes("wallet", args.scale)
+    count = len(ms)
+    d_p, d_c, d_a = step(600, lambda: make_block(torch, B, a, bv, ms))
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    d_sealed = torch.zeros_like(d_a)
+    bv.seal_amounts_device(KEY, d_a.data_ptr(), count, d_sealed.data_ptr(), st, index_base=BASE)
+    d_tags = torch.zeros((count,), dtype=torch.uint8, device=dev)
+    bv.view_tags_device(KEY, count, d_tags.data_ptr(), st, index_base=BASE)
+    torch.cuda.synchronize()
+    tags = d_tags.cpu().numpy()
+    probe = list(range(0, count, max(1, count // 64)))
+    tags_are_hashlib = all(int(tags[i]) == view_tag(KEY, BASE + i) for i in probe)
+    d_ok = torch.full((count,), 7, dtype=torch.int32, device=dev)
+    h_ok = torch.empty((count,), dtype=torch.int32, pin_memory=True)
+    max_hits = count
+    d_hits = torch.zeros((max_hits, 12), dtype=torch.int32, device=dev)
+    h_hits = torch.empty((max_hits, 12), dtype=torch.int32, pin_memory=True)
+    d_n = torch.zeros((2,), dtype=torch.int32, device=dev)   # hits, candidates
+    out["find_tags"] = {"block": "wallet", "count": count, "max_hits": max_hits, "tags_are_hashlib": tags_are_hashlib, "by_keys": {}}
+    want_amounts = d_a.cpu().numpy().view(np.uint64)
+    for K in ks:
+        keys = [KEY] + [hashlib.sha256(b"recover_bench key %d" % j).digest() for j in range(1, K)]
+        d_keys = torch.from_numpy(np.frombuffer(b"".join(keys), dtype=np.uint8).copy()).to(dev)
+        tsb, fsb = bv.verify_find_tagged_workspace_bytes(ms, K), bv.verify_find_workspace_bytes(ms, K)
+        d_ws = torch.empty(tsb, dtype=torch.uint8, device=dev)
+        got = {}
+
+        def find(name, nk, wsb, tagged):
+            def run():
+                d_n.zero_()
+                bv.verify_find_serialized_mixed_keys_device(d_p.data_ptr(), d_c.data_ptr(), ms, d_keys.data_ptr() if nk else 0, nk,
+                                                            d_sealed.data_ptr() if nk else 0, d_ok.data_ptr(),
+                                                            d_hits.data_ptr() if nk else 0, max_hits, d_n.data_ptr(),
+                                                            d_ws.data_ptr(), wsb, st, sealed=True, index_base=BASE,
+                                                            d_tags=d_tags.data_ptr() if tagged else 0,
+                                                            d_n_candidates=d_n.data_ptr() + 4 if tagged else 0)
+                h_ok.copy_(d_ok, non_blocking=True)
+                got[name] = d_n.cpu().numpy().tolist()   # the counts first, then as many records
+                w = min(got[name][0], max_hits)
+                h_hits[:w].copy_(d_hits[:w], non_blocking=True)
+            return run
+
+        def check(name):
+            torch.cuda.synchronize()
+            hits = h_hits.numpy().view(np.uint32)
+            amounts = hits[:, 2].astype(np.uint64) | hits[:, 3].astype(np.uint64) << np.uint64(32)
+            return bool((h_ok.numpy() == 0).all() and got[name][0] == count and (hits[:, 0] == 0).all() and
+                        (hits[:, 1] == np.arange(count)).all() and (amounts == want_amounts).all())
+
+        tagged, untagged = find("tagged", K, tsb, True), find("untagged", K, fsb, False)
+        no_keys = find("no_keys", 0, bv.verify_find_workspace_bytes(ms, 0), False)
+        res = {"pairs": K * count, "tagged_workspace_bytes": tsb, "untagged_workspace_bytes": fsb}
+        # each side once alone, so that what is checked is that side's answer
+        for name, f in (("untagged", untagged), ("tagged", tagged)):
+            h_hits.zero_()
+            step(300, f)
+            res[name + "_hits_as_expected"] = check(name)
+        chance = sum(1 for j in range(1, K) for i in probe if view_tag(keys[j], BASE + i) == int(tags[i]))
+        res["n_candidates"] = got["tagged"][1]
+        res["candidates_over_pairs"] = got["tagged"][1] / (K * count)
+        res["chance_matches_in_probe"] = {"found": chance, "probed_pairs": (K - 1) * len(probe)}
+        res["candidates_as_expected"] = bool(count <= got["tagged"][1] <= count + max(64, 2 * (K - 1) * count // 256))
+        ts = step(900, lambda: alternate(torch, [tagged, untagged, no_keys], args.reps, args.warmup))
+        torch.cuda.synchronize()
+        res["tagged"], res["untagged"], res["no_keys"] = stats(ts[0]), stats(ts[1]), stats(ts[2])
+        per_rep = [t / u for t, u in zip(ts[0], ts[1])]
+        res["ratio_tagged_over_untagged"] = statistics.median(ts[0]) / statistics.median(ts[1])
+        res["ratio_per_rep"] = {"median": statistics.median(per_rep), "min": min(per_rep), "max": max(per_rep)}
+        res["ratio_tagged_over_no_keys"] = statistics.median(ts[0]) / statistics.median(ts[2])
+        res["grows_with_keys_ms"] = {"tagged": statistics.median(ts[0]) - statistics.median(ts[2]),
+                                     "untagged": statistics.median(ts[1]) - statistics.median(ts[2])}
+        # the acceptance of DESIGN 4l: faster than the untagged call by more than that leg's run-to-run spread
+        res["faster_by_more_than_untagged_spread"] = bool(statistics.median(ts[1]) - statistics.median(ts[0]) >
+                                                          max(ts[1]) - min(ts[1]))
+        out["find_tags"]["by_keys"][str(K)] = res
+        print("tags %d" % K, json.dumps(res), flush=True)
+        wrong = [c for c in ("untagged_hits_as_expected", "tagged_hits_as_expected", "candidates_as_expected")
+                 if res.get(c) is False] + ([] if tags_are_hashlib else ["tags_are_hashlib"])
+        if wrong:   # a run that computed something else is no measurement
+            raise RuntimeError("tags leg, K = %d: %s" % (K, ", ".join(wrong)))
+        del d_keys, d_ws
+
+
 def merge_kernel_stats(args):
     """folds rocprofv3 k_kernel_stats.csv files (one per side) into the JSON at --out: no GPU"""
     with open(args.out) as f:
@@ -337,6 +434,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--keys", default="")
     ap.add_argument("--find", action="store_true")
+    ap.add_argument("--tags", action="store_true")
     ap.add_argument("--side", default="both", choices=("both", "many", "single", "fused", "today"))
     ap.add_argument("--kernel-stats", default="")
     ap.add_argument("--reps", type=int, default=20)
@@ -350,7 +448,7 @@ def main():
     if args.kernel_stats:
         return merge_kernel_stats(args)
     if args.find:
-        args.legs = "f"   # --find: that leg alone, at --keys
+        args.legs = "t" if args.tags else "f"   # --find: that leg alone, at --keys; with --tags the tagged call's
     elif args.keys and "k" not in args.legs:
         args.legs = "k"   # --keys alone: the many-key leg alone
     import torch
@@ -370,6 +468,8 @@ def main():
             keys_leg(torch, B, a, bv, [int(x) for x in (args.keys or "1,4,16,64").split(",")], args, out)
         if "f" in args.legs:
             find_leg(torch, B, a, bv, [int(x) for x in (args.keys or "1,16,64").split(",")], args, out)
+        if "t" in args.legs:
+            tags_leg(torch, B, a, bv, [int(x) for x in (args.keys or "1,16,64,256").split(",")], args, out)
         out["complete"] = True
     except StepTimeout:
         out["stopped"] = "a step ran into its time limit"
@@ -379,8 +479,9 @@ def main():
         if args.find and os.path.exists(args.out):   # beside what the other legs recorded there
             with open(args.out) as f:
                 kept = json.load(f)
-            kept["find"] = dict(out.get("find", {}), reps=args.reps, warmup=args.warmup, window_bits=args.window,
-                                scale=args.scale, device=out["device"], complete=out["complete"])
+            leg = "find_tags" if args.tags else "find"
+            kept[leg] = dict(out.get(leg, {}), reps=args.reps, warmup=args.warmup, window_bits=args.window,
+                             scale=args.scale, device=out["device"], complete=out["complete"])
             out = kept
         with open(args.out, "w") as f:
             json.dump(out, f, indent=1, sort_keys=True)
