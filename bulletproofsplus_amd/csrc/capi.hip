@@ -11,7 +11,6 @@
 #include "impl_wip.hpp"
 #include "recover.hpp"
 #include "find.hpp"
-#include "find_tags.hpp"
 #include "recover_keys.hpp"
 
 using namespace bpp;
@@ -1475,13 +1474,59 @@ extern "C" int bpp_range_scan_serialized_mixed_keys(bpp_verifier* v, const uint8
     });
 }
 
-// ---- sealed amounts, and verifying a block while listing the outputs of many keys (find.hpp) ----
-extern "C" int bpp_amounts_seal_device(bpp_ctx* ctx, const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_index,
-                                       const uint64_t* d_in, size_t count, uint64_t* d_out, void* stream) {
+// ---- sealed amounts, view tags, and verifying a block while listing the outputs of many keys, with tags or without
+// (find.hpp) ----
+namespace {
+constexpr int FIND_FLAGS = SCAN_FLAGS | BPP_FIND_AMOUNTS_SEALED;
+
+// The checks of the four entries that expand one key over `count` outputs (seal and tag, device and host); count = 0 passes
+// them and is answered by the entry.  buffers: whether every buffer that a count above zero reads or writes, the optional
+// index aside, is there.
+int key_stream_args(const bpp_ctx* ctx, const uint8_t* blind_key, size_t count, bool buffers) noexcept {
     if (!ctx || !blind_key) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
-    if (!d_in || !d_out) return fail(BPP_E_ARG, "null argument");
+    if (!buffers) return fail(BPP_E_ARG, "null argument");
     if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    return BPP_OK;
+}
+
+// no proof: no verdict, no candidate, no hit -- the counts a find entry answers with, on the device or on the host
+int find_nothing(const bpp_verifier* v, const FindArgs& a, bool device, hipStream_t st) noexcept {
+    if (!device) {
+        *a.n_hits = 0;
+        if (a.n_candidates) *a.n_candidates = 0;
+        return BPP_OK;
+    }
+    return on_device(v->ctx.device, [&]() -> int {
+        HIPCHK(zero_words_async(a.n_hits, 4, st));
+        if (a.n_candidates) HIPCHK(zero_words_async(a.n_candidates, 4, st));
+        return BPP_OK;
+    });
+}
+
+// The checks of the four find entries, tagged and untagged, that come before scan_keys_args; count = 0 passes them and is
+// answered by find_nothing.  a holds the entry's pointers, the device's (device: with a workspace) or the host's, and leaves
+// with what the flags say.  Without keys the block is verified all the same: the call IS a verification, and ok is never
+// left unwritten.
+int find_args(const bpp_verifier* v, int flags, FindArgs& a, bool device, const void* d_workspace) noexcept {
+    if (!v || !a.n_hits) return fail(BPP_E_ARG, "null argument");
+    if (flags & ~FIND_FLAGS) return fail(BPP_E_ARG, "unknown flag");
+    a.version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
+    a.amount64 = (flags & BPP_PROVE_AMOUNT64) != 0;
+    a.sealed = (flags & BPP_FIND_AMOUNTS_SEALED) != 0;
+    if (a.count == 0) return BPP_OK;
+    if (!a.proofs || !a.commitments || !a.m_of || !a.ok || (device && !d_workspace)) return fail(BPP_E_ARG, "null argument");
+    if (a.n_keys && (!a.keys || !a.amounts || (a.tagged && !a.tags) || (!a.hits && a.max_hits)))
+        return fail(BPP_E_ARG, "null argument");
+    if (device && a.n_keys && (reinterpret_cast<uintptr_t>(a.keys) & 3)) return fail(BPP_E_ARG, "d_keys must be 4-byte aligned");
+    return BPP_OK;
+}
+}  // namespace
+
+extern "C" int bpp_amounts_seal_device(bpp_ctx* ctx, const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_index,
+                                       const uint64_t* d_in, size_t count, uint64_t* d_out, void* stream) {
+    if (int rc = key_stream_args(ctx, blind_key, count, d_in && d_out)) return rc;
+    if (count == 0) return BPP_OK;
     return on_ctx(*ctx, {count, "count"}, [&](auto cv) -> int {
         return FindImpl<decltype(cv)>::seal(blind_key, index_base, d_index, d_in, count, d_out, static_cast<hipStream_t>(stream));
     });
@@ -1489,23 +1534,40 @@ extern "C" int bpp_amounts_seal_device(bpp_ctx* ctx, const uint8_t* blind_key, u
 
 extern "C" int bpp_amounts_seal(bpp_ctx* ctx, const uint8_t* blind_key, uint64_t index_base, const uint64_t* index,
                                 const uint64_t* in, size_t count, uint64_t* out) {
-    if (!ctx || !blind_key) return fail(BPP_E_ARG, "null argument");
+    if (int rc = key_stream_args(ctx, blind_key, count, in && out)) return rc;
     if (count == 0) return BPP_OK;
-    if (!in || !out) return fail(BPP_E_ARG, "null argument");
-    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
     return on_ctx(*ctx, {count, "count"}, [&](auto cv) -> int {
         return FindImpl<decltype(cv)>::seal_host(blind_key, index_base, index, in, count, out);
     });
 }
 
-namespace {
-constexpr int FIND_FLAGS = SCAN_FLAGS | BPP_FIND_AMOUNTS_SEALED;
+extern "C" int bpp_view_tags_device(bpp_ctx* ctx, const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_index,
+                                    size_t count, uint8_t* d_out, void* stream) {
+    if (int rc = key_stream_args(ctx, blind_key, count, d_out != nullptr)) return rc;
+    if (count == 0) return BPP_OK;
+    return on_ctx(*ctx, {count, "count"}, [&](auto cv) -> int {
+        return FindImpl<decltype(cv)>::tags(blind_key, index_base, d_index, count, d_out, static_cast<hipStream_t>(stream));
+    });
+}
+
+extern "C" int bpp_view_tags(bpp_ctx* ctx, const uint8_t* blind_key, uint64_t index_base, const uint64_t* index, size_t count,
+                             uint8_t* out) {
+    if (int rc = key_stream_args(ctx, blind_key, count, out != nullptr)) return rc;
+    if (count == 0) return BPP_OK;
+    return on_ctx(*ctx, {count, "count"}, [&](auto cv) -> int {
+        return FindImpl<decltype(cv)>::tags_host(blind_key, index_base, index, count, out);
+    });
 }
 
 extern "C" size_t bpp_verify_find_serialized_mixed_keys_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count,
                                                                         size_t n_keys) {
     if ((count && !m_of) || !pairs_bounded(n_keys, count) || !m_of_wellformed(m_of, count)) return 0;
-    return size_for(v, [&](auto cv) { return FindImpl<decltype(cv)>::workspace_bytes(v, m_of, count, n_keys); });
+    return size_for(v, [&](auto cv) { return FindImpl<decltype(cv)>::workspace_bytes(v, m_of, count, n_keys, false); });
+}
+
+extern "C" size_t bpp_verify_find_tagged_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys) {
+    if ((count && !m_of) || !pairs_bounded(n_keys, count) || !m_of_wellformed(m_of, count)) return 0;
+    return size_for(v, [&](auto cv) { return FindImpl<decltype(cv)>::workspace_bytes(v, m_of, count, n_keys, true); });
 }
 
 extern "C" int bpp_range_verify_find_serialized_mixed_keys_device(bpp_verifier* v, const void* d_proofs, const void* d_commitments,
@@ -1515,25 +1577,14 @@ extern "C" int bpp_range_verify_find_serialized_mixed_keys_device(bpp_verifier* 
                                                                   uint32_t* d_ok, uint32_t* d_hits, size_t max_hits,
                                                                   uint32_t* d_n_hits, void* d_workspace, size_t workspace_bytes,
                                                                   void* stream) {
-    if (!v || !d_n_hits) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~FIND_FLAGS) return fail(BPP_E_ARG, "unknown flag");
-    if (count == 0)   // no proof: no verdict, no hit
-        return on_device(v->ctx.device, [&]() -> int {
-            HIPCHK(zero_words_async(d_n_hits, 4, static_cast<hipStream_t>(stream)));
-            return BPP_OK;
-        });
-    // without keys the block is verified all the same: the call IS a verification, and d_ok is never left unwritten
-    if (!d_proofs || !d_commitments || !m_of || !d_ok || !d_workspace) return fail(BPP_E_ARG, "null argument");
-    if (n_keys && (!d_keys || !d_amounts || (!d_hits && max_hits))) return fail(BPP_E_ARG, "null argument");
-    if (n_keys && (reinterpret_cast<uintptr_t>(d_keys) & 3)) return fail(BPP_E_ARG, "d_keys must be 4-byte aligned");
+    FindArgs a{static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), m_of, count, d_keys, n_keys,
+               index_base, d_index, d_amounts, d_ok, d_hits, max_hits, d_n_hits, false, nullptr, nullptr};
+    if (int rc = find_args(v, flags, a, true, d_workspace)) return rc;
+    if (count == 0) return find_nothing(v, a, true, static_cast<hipStream_t>(stream));
     if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
     if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return FindImpl<decltype(cv)>::find(v, static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments),
-                                            m_of, count, (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u,
-                                            (flags & BPP_PROVE_AMOUNT64) != 0, (flags & BPP_FIND_AMOUNTS_SEALED) != 0, d_keys,
-                                            n_keys, index_base, d_index, d_amounts, d_ok, d_hits, max_hits, d_n_hits, d_workspace,
-                                            workspace_bytes, static_cast<hipStream_t>(stream));
+        return FindImpl<decltype(cv)>::find(v, a, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
     });
 }
 
@@ -1543,47 +1594,12 @@ extern "C" int bpp_range_verify_find_serialized_mixed_keys(bpp_verifier* v, cons
                                                            size_t n_keys, uint64_t index_base, const uint64_t* index,
                                                            const uint64_t* amounts, uint32_t* out_ok, uint32_t* out_hits,
                                                            size_t max_hits, uint32_t* out_n_hits) {
-    if (!v || !out_n_hits) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~FIND_FLAGS) return fail(BPP_E_ARG, "unknown flag");
-    if (count == 0) {   // no proof: no verdict, no hit
-        *out_n_hits = 0;
-        return BPP_OK;
-    }
-    if (!proofs || !commitments || !m_of || !out_ok) return fail(BPP_E_ARG, "null argument");
-    if (n_keys && (!keys || !amounts || (!out_hits && max_hits))) return fail(BPP_E_ARG, "null argument");
+    FindArgs a{proofs, commitments, m_of,     count,    keys,       n_keys, index_base, index,
+               amounts, out_ok,     out_hits, max_hits, out_n_hits, false,  nullptr,    nullptr};
+    if (int rc = find_args(v, flags, a, false, nullptr)) return rc;
+    if (count == 0) return find_nothing(v, a, false, nullptr);
     if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return FindImpl<decltype(cv)>::find_host(v, proofs, commitments, m_of, count, flags, keys, n_keys, index_base, index,
-                                                 amounts, out_ok, out_hits, max_hits, out_n_hits);
-    });
-}
-
-// ---- view tags, and the verify-and-find call that tests them first (find_tags.hpp) ----
-extern "C" int bpp_view_tags_device(bpp_ctx* ctx, const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_index,
-                                    size_t count, uint8_t* d_out, void* stream) {
-    if (!ctx || !blind_key) return fail(BPP_E_ARG, "null argument");
-    if (count == 0) return BPP_OK;
-    if (!d_out) return fail(BPP_E_ARG, "null argument");
-    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
-    return on_ctx(*ctx, {count, "count"}, [&](auto cv) -> int {
-        return FindTagsImpl<decltype(cv)>::tags(blind_key, index_base, d_index, count, d_out, static_cast<hipStream_t>(stream));
-    });
-}
-
-extern "C" int bpp_view_tags(bpp_ctx* ctx, const uint8_t* blind_key, uint64_t index_base, const uint64_t* index, size_t count,
-                             uint8_t* out) {
-    if (!ctx || !blind_key) return fail(BPP_E_ARG, "null argument");
-    if (count == 0) return BPP_OK;
-    if (!out) return fail(BPP_E_ARG, "null argument");
-    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
-    return on_ctx(*ctx, {count, "count"}, [&](auto cv) -> int {
-        return FindTagsImpl<decltype(cv)>::tags_host(blind_key, index_base, index, count, out);
-    });
-}
-
-extern "C" size_t bpp_verify_find_tagged_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys) {
-    if ((count && !m_of) || !pairs_bounded(n_keys, count) || !m_of_wellformed(m_of, count)) return 0;
-    return size_for(v, [&](auto cv) { return FindTagsImpl<decltype(cv)>::workspace_bytes(v, m_of, count, n_keys); });
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int { return FindImpl<decltype(cv)>::find_host(v, a); });
 }
 
 extern "C" int bpp_range_verify_find_tagged_serialized_mixed_keys_device(
@@ -1591,26 +1607,14 @@ extern "C" int bpp_range_verify_find_tagged_serialized_mixed_keys_device(
     const uint8_t* d_keys, size_t n_keys, uint64_t index_base, const uint64_t* d_index, const uint64_t* d_amounts, uint32_t* d_ok,
     uint32_t* d_hits, size_t max_hits, uint32_t* d_n_hits, const uint8_t* d_tags, uint32_t* d_n_candidates, void* d_workspace,
     size_t workspace_bytes, void* stream) {
-    if (!v || !d_n_hits) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~FIND_FLAGS) return fail(BPP_E_ARG, "unknown flag");
-    if (count == 0)   // no proof: no verdict, no candidate, no hit
-        return on_device(v->ctx.device, [&]() -> int {
-            HIPCHK(zero_words_async(d_n_hits, 4, static_cast<hipStream_t>(stream)));
-            if (d_n_candidates) HIPCHK(zero_words_async(d_n_candidates, 4, static_cast<hipStream_t>(stream)));
-            return BPP_OK;
-        });
-    // without keys the block is verified all the same, as in the untagged call
-    if (!d_proofs || !d_commitments || !m_of || !d_ok || !d_workspace) return fail(BPP_E_ARG, "null argument");
-    if (n_keys && (!d_keys || !d_amounts || !d_tags || (!d_hits && max_hits))) return fail(BPP_E_ARG, "null argument");
-    if (n_keys && (reinterpret_cast<uintptr_t>(d_keys) & 3)) return fail(BPP_E_ARG, "d_keys must be 4-byte aligned");
+    FindArgs a{static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), m_of, count, d_keys, n_keys,
+               index_base, d_index, d_amounts, d_ok, d_hits, max_hits, d_n_hits, true, d_tags, d_n_candidates};
+    if (int rc = find_args(v, flags, a, true, d_workspace)) return rc;
+    if (count == 0) return find_nothing(v, a, true, static_cast<hipStream_t>(stream));
     if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
     if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return FindTagsImpl<decltype(cv)>::find(
-            v, static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), m_of, count,
-            (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u, (flags & BPP_PROVE_AMOUNT64) != 0, (flags & BPP_FIND_AMOUNTS_SEALED) != 0,
-            d_keys, n_keys, index_base, d_index, d_amounts, d_ok, d_hits, max_hits, d_n_hits, d_tags, d_n_candidates, d_workspace,
-            workspace_bytes, static_cast<hipStream_t>(stream));
+        return FindImpl<decltype(cv)>::find(v, a, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
     });
 }
 
@@ -1619,20 +1623,12 @@ extern "C" int bpp_range_verify_find_tagged_serialized_mixed_keys(
     bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, const uint32_t* m_of, size_t count, int flags,
     const uint8_t* keys, size_t n_keys, uint64_t index_base, const uint64_t* index, const uint64_t* amounts, uint32_t* out_ok,
     uint32_t* out_hits, size_t max_hits, uint32_t* out_n_hits, const uint8_t* tags, uint32_t* out_n_candidates) {
-    if (!v || !out_n_hits) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~FIND_FLAGS) return fail(BPP_E_ARG, "unknown flag");
-    if (count == 0) {   // no proof: no verdict, no candidate, no hit
-        *out_n_hits = 0;
-        if (out_n_candidates) *out_n_candidates = 0;
-        return BPP_OK;
-    }
-    if (!proofs || !commitments || !m_of || !out_ok) return fail(BPP_E_ARG, "null argument");
-    if (n_keys && (!keys || !amounts || !tags || (!out_hits && max_hits))) return fail(BPP_E_ARG, "null argument");
+    FindArgs a{proofs, commitments, m_of,     count,    keys,       n_keys, index_base, index,
+               amounts, out_ok,     out_hits, max_hits, out_n_hits, true,   tags,       out_n_candidates};
+    if (int rc = find_args(v, flags, a, false, nullptr)) return rc;
+    if (count == 0) return find_nothing(v, a, false, nullptr);
     if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return FindTagsImpl<decltype(cv)>::find_host(v, proofs, commitments, m_of, count, flags, keys, n_keys, index_base, index,
-                                                     amounts, out_ok, out_hits, max_hits, out_n_hits, tags, out_n_candidates);
-    });
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int { return FindImpl<decltype(cv)>::find_host(v, a); });
 }
 
 // ---- the verifier pool: one batch sharded over the devices of a node (shard.hpp, pool.hpp; see include/bpp_amd.h) ----

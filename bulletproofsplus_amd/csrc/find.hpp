@@ -1,33 +1,60 @@
 // find.hpp -- verifying a block of containers AND listing the outputs of many view keys in one call
-// (bpp_range_verify_find_serialized_mixed_keys*), and sealing amounts (bpp_amounts_seal*).  What a scanning service does
-// with a block today is two calls that share a front -- bpp_range_verify_batch_serialized_mixed_device, then
-// bpp_range_scan_serialized_mixed_keys_device -- and a walk over the scan's dense pair matrix; here the front (index
-// upload, decode, membership test, challenges) runs once, the verdict gates the confirmation, and the answer is the
-// verdicts and a short ordered list of hits.  One instantiation per curve (tu_find_*.hip); find_terms.hpp has the pad
-// and the compaction's index arithmetic.
+// (bpp_range_verify_find_serialized_mixed_keys*), the same call with one-byte view tags
+// (bpp_range_verify_find_tagged_serialized_mixed_keys*), sealing amounts (bpp_amounts_seal*) and making the tags
+// (bpp_view_tags*).  What a scanning service does with a block otherwise is two calls that share a front --
+// bpp_range_verify_batch_serialized_mixed_device, then bpp_range_scan_serialized_mixed_keys_device -- and a walk over the
+// scan's dense pair matrix; here the front (index upload, decode, membership test, challenges) runs once, the verdict gates
+// the confirmation, and the answer is the verdicts and a short ordered list of hits.  The untagged call pays 2k + 3 slot
+// expansions, as many products in Fr and a table walk for EVERY (key, single output) pair; in the tagged call a pair first
+// pays one SHA-256 compression -- view_tag(key, idx) against the byte the output carries -- and only the pairs that match,
+// the CANDIDATES, go on.  Verdicts, hit records, their order and the max_hits rule are the same in both.  One engine
+// (FindImpl::find, "tagged" a flag of its arguments), one instantiation per curve (tu_find_*.hip); find_terms.hpp has the
+// pad, the tag and the index arithmetic; what a pair's lanes compute (its Gamma, its confirmation) is recover_keys.hpp's.
 //
-// Schedule, all on the caller's stream: decode_front; per class present derive_challenges and today's exact pass
-// (VerifyImpl::run) into front.ok; for the single-output class RecoverKeysImpl::scan_class (k_recover_coeffs, k_scan_keys,
-// unchanged) with Gamma and the pair word pointed at the pair region of the workspace, then k_find_confirm;
-// k_mixed_status_scatter writes d_ok; k_find_count, k_find_offsets, k_find_emit make the hit list.
+// Schedule, all on the caller's stream, no host synchronisation beyond the front's index upload: decode_front; the pair
+// words zeroed where a kernel below will not write them (untagged: those of aggregated proofs, so only when there are any;
+// tagged: every non-candidate's, so always); per class present derive_challenges and today's exact pass (VerifyImpl::run)
+// into front.ok; for the single-output class RecoverKeysImpl's bind_class and launch_coeffs (k_recover_coeffs) with Gamma
+// and the pair word pointed at the pair region of the workspace, then the class step below; k_mixed_status_scatter writes
+// d_ok; k_find_count, k_find_offsets, k_find_emit make the hit list.
+// The class step, untagged: k_scan_keys, then
 // k_find_confirm: one lane per (key, single-output proof) pair, numbered as k_scan_keys numbers them.  A lane whose proof
 // the pass did not accept, the decoder rejected or whose coefficients are undefined clears its pair (no hit, Gamma zero)
-// before it reads a key or a Gamma.  Otherwise the candidate amount -- sealed mode: the key's words into registers, the
-// pad by amount_pad, amount = sealed XOR pad; else a load from the key-major array -- then k_scan_keys_confirm's walk and
-// projective comparison.  A hit keeps its Gamma and stores its amount; a miss has its Gamma zeroed.  No LDS, no scratch:
-// nothing derived from a key but Gamma, and for a hit its amount, reaches memory, and when the kernel ends no Gamma of a
-// pair that is not a hit is left in the workspace.
+// before it reads a key or a Gamma.  Otherwise the candidate amount (find_pair_amount) -- sealed mode: the key's words into
+// registers, the pad by amount_pad, amount = sealed XOR pad; else a load from the key-major array -- then pair_confirms.  A
+// hit keeps its Gamma and stores its amount; a miss has its Gamma zeroed.
+// The class step, tagged:
+// k_find_tags: one 64-lane block per tile of FIND_TILE launch positions OF ONE KEY (find_terms.hpp), a lane per pair and
+// round.  A lane whose proof the pass did not accept, the decoder rejected or whose coefficients are undefined is no
+// candidate before it reads a key.  The others read the tile's key (uniform over the block: scalar loads), the index and
+// the tag byte of their caller position, and compress once.  The tile leaves its FIND_ROUNDS ballots and its count: ONE
+// BIT per pair instead of a flag word.
+// k_find_offsets scans the tile counts and leaves the candidate count in a workspace word.
+// k_find_list: the lanes of k_find_tags again, from the ballots: candidate number h of the call, in ascending key-major
+// pair number, to list[h].  No atomics; the same list from run to run.
+// k_find_scan_list: k_scan_keys's eight lanes per pair (pair_gamma), over the list: group g takes candidates g,
+// g + groups, .. below the count it READS FROM THE WORKSPACE; the grid is sized from n_keys x count alone, so the host never
+// learns the count.  Gamma goes to the pair's place in the key-major region.
+// k_find_confirm_list: k_find_confirm's lane, one per POSSIBLE pair (the stride over the list is one step: lanes at or
+// beyond the count end at once): candidate amount, pair_confirms; a hit sets its pair word and stores its amount, a miss has
+// its Gamma zeroed.
 // The compaction: the pair words lie key-major ([key][caller position]), so ascending position is ascending (key number,
 // caller position).  k_find_count: one 64-lane block per tile of FIND_TILE positions, a ballot per round, the tile's
 // count.  k_find_offsets: one wave scans the tile counts in place (exclusive) and writes the total to d_n_hits.
 // k_find_emit: the lanes of k_find_count again; a hit's place is its tile's offset, the ballots of the rounds before and
 // the lanes below it -- no atomics, and an order that does not depend on scheduling.  Records at or beyond max_hits are
 // not written.
+// The key rule: no LDS, no scratch in any kernel here.  Nothing derived from a key reaches memory but the candidate bit
+// (the match of a PUBLIC byte), the hit bit, Gamma of a pair that was scanned (zeroed on a miss: when the call ends no
+// Gamma of a pair that is not a hit is left in the workspace) and a hit's amount.  The Gamma and amount words of
+// non-candidates are never written.
 #pragma once
 #include "recover_keys.hpp"
 #include "find_terms.hpp"
 
 namespace bpp {
+
+constexpr unsigned FIND_LIST_BLOCKS = 8192;   // most blocks k_find_scan_list is launched with: 32 waves for each of 256 CUs
 
 // one lane per output: out[i] = in[i] XOR pad(key, index of i); in and out may be one buffer.  The key travels by value
 // (RecoverSource's reason).
@@ -42,7 +69,19 @@ __global__ void __launch_bounds__(FIND_BLOCK) k_amounts_seal(BlindKey key, uint6
     out[i] = in[i] ^ amount_pad(kw, index ? index[i] : index_base + i);
 }
 
-// what k_find_confirm takes beside the pair job of k_scan_keys (whose out_status is the pair word: 1 for a hit, else 0)
+// one lane per output: out[i] = view_tag(key, index of i).  The key travels by value (k_amounts_seal's reason).
+template <class C>
+__global__ void __launch_bounds__(FIND_BLOCK) k_view_tags(BlindKey key, uint64_t index_base, const uint64_t* __restrict__ index,
+                                                          uint8_t* __restrict__ out, size_t count) {
+    const size_t i = (size_t)blockIdx.x * FIND_BLOCK + threadIdx.x;
+    if (i >= count) return;
+    uint32_t kw[8];
+#pragma unroll
+    for (int w = 0; w < 8; w++) kw[w] = key.w[w];
+    out[i] = view_tag(kw, index ? index[i] : index_base + i);
+}
+
+// what the confirmation kernels take beside the pair job of k_scan_keys (whose out_status is the pair word: 1 for a hit, else 0)
 struct FindJob {
     const uint32_t* ok;        // the pass's verdicts, by launch position
     const uint64_t* amounts;   // sealed: count x u64 by caller position; else n_keys x total, key-major
@@ -50,12 +89,20 @@ struct FindJob {
     uint64_t* hit_amounts;     // n_keys x total, key-major; written for hits only
 };
 
+// the candidate amount of the pair at place `at` ([key_no][caller]): sealed -- the key's words into registers, the output's
+// one ciphertext XOR the key's pad -- else a load from the key-major array
+__device__ __forceinline__ uint64_t find_pair_amount(const ScanKeysJob& j, const FindJob& f, size_t key_no, size_t caller,
+                                                     size_t at) {
+    if (!f.sealed) return f.amounts[at];
+    uint32_t key[8];
+    const uint64_t idx = pair_key_index(j, key_no, caller, key);
+    return f.amounts[caller] ^ amount_pad(key, idx);
+}
+
 template <class C>
 __global__ void __launch_bounds__(FIND_BLOCK) k_find_confirm(VerifyShape s, const uint32_t* __restrict__ table, ScanKeysJob j,
                                                              FindJob f, const uint32_t* __restrict__ records, uint32_t nv,
                                                              uint32_t v0) {
-    constexpr int N = C::Fp::N;
-    constexpr int WW = 2 * N + 2;
     const size_t q = (size_t)blockIdx.x * FIND_BLOCK + threadIdx.x;
     if (q >= j.count * j.n_keys) return;
     const size_t p = q / j.n_keys;
@@ -68,22 +115,8 @@ __global__ void __launch_bounds__(FIND_BLOCK) k_find_confirm(VerifyShape s, cons
         j.out_status[at] = 0u;
         return;
     }
-    uint64_t amount;
-    if (f.sealed) {
-        uint32_t key[8];
-#pragma unroll
-        for (int w = 0; w < 8; w++) key[w] = j.keys[(size_t)key_no * 8 + w];
-        amount = f.amounts[caller] ^ amount_pad(key, j.index ? j.index[caller] : j.index_base + caller);
-    } else {
-        amount = f.amounts[at];
-    }
-    uint32_t kv[8], kg[8];
-    commit_amount_scalar<C>(amount, f.amount64 != 0, kv);
-    ld_words<8>(j.out_masks + at * 8, kg);   // canonical: k_scan_keys wrote it
-    const Xyzz<C> acc = commit_walk<C>(
-        s, kv, kg, [&](size_t e) { return aff_ldg<C>(table + e * (size_t)(2 * N)); },
-        [](Xyzz<C>& a, const Aff<C>& pt, bool neg) { xyzz_madd_lazy(a, pt, neg); });
-    const bool same = walk_equals_wire<C>(acc, records + ((size_t)p * nv + v0) * WW);
+    const uint64_t amount = find_pair_amount(j, f, key_no, caller, at);
+    const bool same = pair_confirms<C>(s, table, j, amount, f.amount64, at, p, records, nv, v0);   // Gamma: k_scan_keys's
     j.out_status[at] = same ? 1u : 0u;
     if (same)
         f.hit_amounts[at] = amount;
@@ -157,6 +190,122 @@ __global__ void __launch_bounds__(FIND_BLOCK) k_find_emit(const uint32_t* __rest
     }
 }
 
+// what the tagged call keeps beside the untagged call's regions
+struct TagJob {
+    const uint8_t* tags;    // by caller position
+    const uint32_t* ok;     // the pass's verdicts, by launch position
+    size_t per_key;         // tiles per key
+    uint64_t* ballots;      // tiles x FIND_ROUNDS
+    uint32_t* tile_count;   // tiles: counts, then their exclusive scan
+    uint32_t* list;         // the candidates' pair numbers (key * count + launch position), ascending
+    uint32_t* n_cand;       // one word
+};
+
+// tile blockIdx.x of the tag test; j as k_scan_keys takes it (count: the proofs of the single-output class)
+template <class C>
+__global__ void __launch_bounds__(FIND_BLOCK) k_find_tags(ScanKeysJob j, TagJob t) {
+    const uint32_t lane = threadIdx.x;
+    const size_t tile = blockIdx.x;
+    const size_t key_no = tag_tile_key(tile, t.per_key);
+    uint32_t n = 0;
+#pragma unroll 1
+    for (uint32_t r = 0; r < FIND_ROUNDS; r++) {
+        const size_t p = tag_launch_position(tile, t.per_key, r, lane);
+        bool cand = false;
+        if (p < j.count && !(t.ok[p] | j.status[p] | j.bad[p])) {   // a verified proof with a defined Gamma: only then a key is read
+            const size_t caller = j.rx[p * RX_WORDS + RX_CALLER];
+            uint32_t key[8];
+            const uint64_t idx = pair_key_index(j, key_no, caller, key);
+            cand = view_tag(key, idx) == t.tags[caller];
+        }
+        const uint64_t ballot = __ballot(cand);
+        if (lane == 0) t.ballots[tile * FIND_ROUNDS + r] = ballot;
+        n += find_ballot_count(ballot);
+    }
+    if (lane == 0) t.tile_count[tile] = n;
+}
+
+// the candidates of tile blockIdx.x to their places in the list; block 0 hands the count to the caller
+template <class C>
+__global__ void __launch_bounds__(FIND_BLOCK) k_find_list(TagJob t, size_t count, uint32_t* __restrict__ n_candidates) {
+    const uint32_t lane = threadIdx.x;
+    const size_t tile = blockIdx.x;
+    const size_t key_no = tag_tile_key(tile, t.per_key);
+    size_t before = t.tile_count[tile];
+#pragma unroll 1
+    for (uint32_t r = 0; r < FIND_ROUNDS; r++) {
+        const uint64_t ballot = t.ballots[tile * FIND_ROUNDS + r];
+        if (ballot >> lane & 1)
+            t.list[before + find_lane_rank(ballot, lane)] =
+                (uint32_t)tag_pair(key_no, tag_launch_position(tile, t.per_key, r, lane), count);
+        before += find_ballot_count(ballot);
+    }
+    if (tile == 0 && lane == 0 && n_candidates) n_candidates[0] = t.n_cand[0];
+}
+
+// k_scan_keys over the candidates: Gamma = A0 + sum c_s slot_s to [key][caller position]; the pair word is not touched
+template <class C>
+__global__ void __launch_bounds__(SCAN_BLOCK) k_find_scan_list(ScanKeysJob j, const uint32_t* __restrict__ list,
+                                                               const uint32_t* __restrict__ n_cand) {
+    const size_t groups = (size_t)gridDim.x * (SCAN_BLOCK / SCAN_GROUP);
+    const size_t n = n_cand[0];
+#pragma unroll 1
+    for (size_t c = ((size_t)blockIdx.x * SCAN_BLOCK + threadIdx.x) / SCAN_GROUP; c < n; c += groups) {   // a whole group
+        const size_t q = list[c];
+        const size_t key_no = q / j.count, p = q - key_no * j.count;
+        const size_t caller = j.rx[p * RX_WORDS + RX_CALLER];
+        pair_gamma<C>(j, key_no, p, caller, key_no * j.total + caller);
+    }
+}
+
+// k_find_confirm over the candidates, one lane each.  A candidate is a verified proof with a defined Gamma already.
+template <class C>
+__global__ void __launch_bounds__(FIND_BLOCK) k_find_confirm_list(VerifyShape s, const uint32_t* __restrict__ table, ScanKeysJob j,
+                                                                  FindJob f, const uint32_t* __restrict__ records, uint32_t nv,
+                                                                  uint32_t v0, const uint32_t* __restrict__ list,
+                                                                  const uint32_t* __restrict__ n_cand) {
+    // one lane per POSSIBLE pair, so the stride over the list is a single step: the grid comes from n_keys x count alone and
+    // a lane at or beyond the count read here ends at once.  (A loop around this body keeps the shape's scalars live
+    // across the walk and costs SGPR spill slots -- a private segment -- on two of the three curves.)
+    const size_t c = (size_t)blockIdx.x * FIND_BLOCK + threadIdx.x;
+    if (c >= n_cand[0]) return;
+    const size_t q = list[c];
+    const size_t key_no = q / j.count, p = q - key_no * j.count;
+    const size_t caller = j.rx[p * RX_WORDS + RX_CALLER];
+    const size_t at = key_no * j.total + caller;
+    const uint64_t amount = find_pair_amount(j, f, key_no, caller, at);
+    if (pair_confirms<C>(s, table, j, amount, f.amount64, at, p, records, nv, v0)) {   // Gamma: k_find_scan_list's
+        j.out_status[at] = 1u;
+        f.hit_amounts[at] = amount;
+    } else {
+        const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        st_words<8>(j.out_masks + at * 8, z);
+    }
+}
+
+// What a find call takes, tagged or not, in the C ABI's order.  For FindImpl::find the pointers are the device's (keys
+// 4-byte aligned), for find_host the host's.  n_keys = 0: the block is verified all the same (keys, amounts, tags unread),
+// no hit.
+struct FindArgs {
+    const uint8_t *proofs, *commitments;
+    const uint32_t* m_of;   // host, always
+    size_t count;
+    const uint8_t* keys;   // n_keys x 32 bytes
+    size_t n_keys;
+    uint64_t index_base;
+    const uint64_t* index;     // count x u64 or null
+    const uint64_t* amounts;   // count x u64 (sealed) or n_keys x count
+    uint32_t* ok;              // count words
+    uint32_t* hits;            // max_hits x FIND_HIT_WORDS words
+    size_t max_hits;
+    uint32_t* n_hits;          // one word
+    bool tagged;               // the tagged call: tags is read and n_candidates, where given, answered
+    const uint8_t* tags;       // count bytes by caller position
+    uint32_t* n_candidates;    // one word or null
+    uint32_t version = 1;      // what the call's flags say
+    bool amount64 = false, sealed = false;
+};
+
 template <class C>
 struct FindImpl {
     using V = VerifyImpl<C>;
@@ -165,13 +314,16 @@ struct FindImpl {
 
     // workspace = front (MixedFront, serialized form) | one class pass's workspace | the single-output class's coefficients
     // and zero-challenge flags | the pair region, key-major over ALL caller positions (k_scan_keys addresses it so): Gamma,
-    // the pair word, the amounts of hits | the tile counts.  Its size depends on the number of keys.
+    // the pair word, the amounts of hits | the tile counts; tagged calls only: | the tag test's ballots and tile counts | the
+    // candidate list, with room for every pair | the candidate count.  A function of (m_of, count, n_keys, tagged) alone.
     struct Layout {
         typename V::MixedFront f;
-        size_t run, run_bytes, coeffs, bad, masks, hit, hit_amounts, tiles, total;
+        size_t run, run_bytes, coeffs, bad, masks, hit, hit_amounts, tiles;
+        size_t ballots, tag_tiles, list, n_cand;   // tagged only
+        size_t total;
     };
-    static Layout layout(const bpp_verifier* v, const MixedPlan& p, size_t count, size_t n_keys) {
-        Layout w;
+    static Layout layout(const bpp_verifier* v, const MixedPlan& p, size_t count, size_t n_keys, bool tagged) {
+        Layout w = {};
         WsCarver o;
         const size_t pairs = n_keys * count;
         w.f = V::carve_front(o, p, count, true);
@@ -183,63 +335,58 @@ struct FindImpl {
         w.hit = o.take(pairs * 4);
         w.hit_amounts = o.take(pairs * 8);
         w.tiles = o.take(find_tiles(pairs) * 4);
+        if (tagged) {
+            const size_t tiles = tag_tiles(n_keys, p.count[0]);
+            w.ballots = o.take(tiles * FIND_ROUNDS * 8);
+            w.tag_tiles = o.take(tiles * 4);
+            w.list = o.take(n_keys * p.count[0] * 4);
+            w.n_cand = o.take(4);
+        }
         w.total = o.total;
         return w;
     }
-    static size_t workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys);
-    // d_keys: n_keys x 32 bytes (device, 4-byte aligned); d_index: count x u64 or null; d_amounts: count x u64 (sealed) or
-    // n_keys x count; d_ok: count words; d_hits: max_hits x FIND_HIT_WORDS words; d_n_hits: one word.  n_keys = 0: the
-    // block is verified all the same (d_keys, d_amounts unread), no hit
-    static int find(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments, const uint32_t* m_of, size_t count,
-                    uint32_t version, bool amount64, bool sealed, const uint8_t* d_keys, size_t n_keys, uint64_t index_base,
-                    const uint64_t* d_index, const uint64_t* d_amounts, uint32_t* d_ok, uint32_t* d_hits, size_t max_hits,
-                    uint32_t* d_n_hits, void* d_workspace, size_t workspace_bytes, hipStream_t st);
-    static int find_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, const uint32_t* m_of, size_t count,
-                         int flags, const uint8_t* keys, size_t n_keys, uint64_t index_base, const uint64_t* index,
-                         const uint64_t* amounts, uint32_t* out_ok, uint32_t* out_hits, size_t max_hits, uint32_t* out_n_hits);
+    static size_t workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys, bool tagged);
+    static int find(bpp_verifier* v, const FindArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st);
+    static int find_host(bpp_verifier* v, const FindArgs& a);
     // blind_key: 32 bytes (host); d_index: count x u64 or null; d_in, d_out: count x u64 (may be the same buffer)
     static int seal(const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_index, const uint64_t* d_in, size_t count,
                     uint64_t* d_out, hipStream_t st);
     static int seal_host(const uint8_t* blind_key, uint64_t index_base, const uint64_t* index, const uint64_t* in, size_t count,
                          uint64_t* out);
+    // blind_key: 32 bytes (host); d_index: count x u64 or null; d_out: count bytes
+    static int tags(const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_index, size_t count, uint8_t* d_out,
+                    hipStream_t st);
+    static int tags_host(const uint8_t* blind_key, uint64_t index_base, const uint64_t* index, size_t count, uint8_t* out);
 };
 
 #ifdef BPP_IMPL_DEFINITIONS
 template <class C>
-size_t FindImpl<C>::workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys) {
+size_t FindImpl<C>::workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys, bool tagged) {
     MixedPlan p;
     if (!V::container_shape_ok(v) || mixed_plan_serialized(v->s, m_of, count, max_point_bytes<C>(), false, p)) return 0;
-    return layout(v, p, count, n_keys).total;
+    return layout(v, p, count, n_keys, tagged).total;
 }
 
 template <class C>
-int FindImpl<C>::find(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments, const uint32_t* m_of, size_t count,
-                      uint32_t version, bool amount64, bool sealed, const uint8_t* d_keys, size_t n_keys, uint64_t index_base,
-                      const uint64_t* d_index, const uint64_t* d_amounts, uint32_t* d_ok, uint32_t* d_hits, size_t max_hits,
-                      uint32_t* d_n_hits, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
-    if (int rc = V::container_args_ok(v, version)) return rc;
+int FindImpl<C>::find(bpp_verifier* v, const FindArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
+    if (int rc = V::container_args_ok(v, a.version)) return rc;
+    const size_t count = a.count, n_keys = a.n_keys;
     MixedPlan p;
-    int rc = mixed_plan_serialized(v->s, m_of, count, (size_t)container_point_bytes<C>(version), true, p);
+    int rc = mixed_plan_serialized(v->s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), true, p);
     if (rc) return rc;
-    const Layout L = layout(v, p, count, n_keys);
+    const Layout L = layout(v, p, count, n_keys, a.tagged);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     const bool scan = n_keys != 0 && p.count[0] != 0;   // only single outputs are scanned: the other classes need not fit a lane group
     if (scan && V::class_shape(v, 0).s.k + 2 > RECOVER_GROUP) return fail(BPP_E_ARG, "mask recovery takes shapes with log2(n m) <= 14");
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
     const size_t pairs = n_keys * count;
-    rc = V::decode_front(p, L.f, count, d_proofs, d_commitments, version, ws, st);
+    rc = V::decode_front(p, L.f, count, a.proofs, a.commitments, a.version, ws, st);
     if (rc) return rc;
-    // the pair words of aggregated proofs: no kernel below writes them (nor their Gamma and amount words, which nothing reads)
-    if (scan && p.count[0] != count) HIPCHK(zero_words_async(W(L.hit), pairs * 4, st));
-    ScanKeysJob j;
-    j.n_keys = (uint32_t)n_keys;
-    j.keys = reinterpret_cast<const uint32_t*>(d_keys);
-    j.index_base = index_base;
-    j.index = d_index;
-    j.out_masks = W(L.masks);
-    j.out_status = W(L.hit);
-    j.total = count;
+    // the pair words no kernel below writes (nor their Gamma and amount words, which nothing reads): untagged, those of
+    // aggregated proofs; tagged, those of every pair that is no candidate
+    if (scan && (a.tagged || p.count[0] != count)) HIPCHK(zero_words_async(W(L.hit), pairs * 4, st));
+    ScanKeysJob j = K::call_job(a.keys, n_keys, a.index_base, a.index, W(L.masks), W(L.hit), count);
     rc = V::for_each_class(v, p, L.f, ws, [&](const typename V::ClassView& cv) {
         int rc1 = V::derive_challenges(v, cv.ps, cv.pts, cv.count, cv.challenges, st);
         if (rc1) return rc1;
@@ -247,66 +394,91 @@ int FindImpl<C>::find(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d
                      nullptr, st);
         if (rc1 || cv.c != 0 || !scan) return rc1;
         // the single-output class comes first in gathered order: launch position = gathered position
-        if ((rc1 = K::scan_class(cv, W(L.f.idx), W(L.f.status), W(L.bad), W(L.coeffs), j, st))) return rc1;
-        const FindJob f{W(L.f.ok), d_amounts, sealed ? 1u : 0u, amount64 ? 1u : 0u, reinterpret_cast<uint64_t*>(ws + L.hit_amounts)};
-        hipLaunchKernelGGL(k_find_confirm<C>, dim3(cdiv(cv.count * n_keys, FIND_BLOCK)), dim3(FIND_BLOCK), 0, st, v->s,
-                           v->table.u32(), j, f, reinterpret_cast<const uint32_t*>(cv.pts), cv.ps.s.NV, 3 + 2 * cv.ps.s.k);
+        K::bind_class(cv, W(L.f.idx), W(L.f.status), W(L.bad), W(L.coeffs), j);
+        if ((rc1 = K::launch_coeffs(cv, W(L.coeffs), W(L.bad), st))) return rc1;
+        const FindJob f{W(L.f.ok) + cv.first, a.amounts, a.sealed ? 1u : 0u, a.amount64 ? 1u : 0u, reinterpret_cast<uint64_t*>(ws + L.hit_amounts)};
+        const uint32_t* records = reinterpret_cast<const uint32_t*>(cv.pts);
+        const uint32_t nv = cv.ps.s.NV, v0 = 3 + 2 * cv.ps.s.k;
+        const size_t pairs0 = n_keys * cv.count;
+        if (!a.tagged) {
+            if ((rc1 = K::launch_scan_keys(j, st))) return rc1;
+            hipLaunchKernelGGL(k_find_confirm<C>, dim3(cdiv(pairs0, FIND_BLOCK)), dim3(FIND_BLOCK), 0, st, v->s, v->table.u32(), j,
+                               f, records, nv, v0);
+            HIPCHK(hipGetLastError());
+            return BPP_OK;
+        }
+        const TagJob t{a.tags, f.ok, tag_tiles_per_key(cv.count), reinterpret_cast<uint64_t*>(ws + L.ballots), W(L.tag_tiles),
+                       W(L.list), W(L.n_cand)};
+        const size_t tiles = tag_tiles(n_keys, cv.count);
+        hipLaunchKernelGGL(k_find_tags<C>, dim3((unsigned)tiles), dim3(FIND_BLOCK), 0, st, j, t);
+        hipLaunchKernelGGL(k_find_offsets<C>, dim3(1), dim3(FIND_BLOCK), 0, st, t.tile_count, tiles, t.n_cand);
+        hipLaunchKernelGGL(k_find_list<C>, dim3((unsigned)tiles), dim3(FIND_BLOCK), 0, st, t, cv.count, a.n_candidates);
+        HIPCHK(hipGetLastError());
+        // the list kernels: grids sized for every pair a candidate, capped; they read the count on the device
+        const size_t scan_blocks = std::min<size_t>(cdiv(pairs0 * SCAN_GROUP, SCAN_BLOCK), FIND_LIST_BLOCKS);
+        hipLaunchKernelGGL(k_find_scan_list<C>, dim3((unsigned)scan_blocks), dim3(SCAN_BLOCK), 0, st, j, t.list, t.n_cand);
+        hipLaunchKernelGGL(k_find_confirm_list<C>, dim3(cdiv(pairs0, FIND_BLOCK)), dim3(FIND_BLOCK), 0, st, v->s, v->table.u32(),
+                           j, f, records, nv, v0, t.list, t.n_cand);
         HIPCHK(hipGetLastError());
         return BPP_OK;
     });
     if (rc) return rc;
-    if ((rc = V::scatter_verdicts(L.f, ws, d_ok, count, st))) return rc;
-    if (!scan) {   // no key, or nothing but aggregated proofs: verified, and no pair to list
-        HIPCHK(zero_words_async(d_n_hits, 4, st));
+    if ((rc = V::scatter_verdicts(L.f, ws, a.ok, count, st))) return rc;
+    if (!scan) {   // no key, or nothing but aggregated proofs: verified, and no pair to test or list
+        HIPCHK(zero_words_async(a.n_hits, 4, st));
+        if (a.tagged && a.n_candidates) HIPCHK(zero_words_async(a.n_candidates, 4, st));
         return BPP_OK;
     }
     const unsigned tiles = (unsigned)find_tiles(pairs);
     hipLaunchKernelGGL(k_find_count<C>, dim3(tiles), dim3(FIND_BLOCK), 0, st, W(L.hit), pairs, W(L.tiles));
-    hipLaunchKernelGGL(k_find_offsets<C>, dim3(1), dim3(FIND_BLOCK), 0, st, W(L.tiles), (size_t)tiles, d_n_hits);
+    hipLaunchKernelGGL(k_find_offsets<C>, dim3(1), dim3(FIND_BLOCK), 0, st, W(L.tiles), (size_t)tiles, a.n_hits);
     hipLaunchKernelGGL(k_find_emit<C>, dim3(tiles), dim3(FIND_BLOCK), 0, st, W(L.hit),
-                       reinterpret_cast<const uint64_t*>(ws + L.hit_amounts), W(L.masks), pairs, count, W(L.tiles), max_hits,
-                       d_hits);
+                       reinterpret_cast<const uint64_t*>(ws + L.hit_amounts), W(L.masks), pairs, count, W(L.tiles), a.max_hits,
+                       a.hits);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
 
+// host buffers in, host verdicts, hit records and counts out: find between copies
 template <class C>
-int FindImpl<C>::find_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, const uint32_t* m_of, size_t count,
-                           int flags, const uint8_t* keys, size_t n_keys, uint64_t index_base, const uint64_t* index,
-                           const uint64_t* amounts, uint32_t* out_ok, uint32_t* out_hits, size_t max_hits,
-                           uint32_t* out_n_hits) {
-    const uint32_t version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
-    const bool sealed = (flags & BPP_FIND_AMOUNTS_SEALED) != 0;
-    if (int rc = V::container_args_ok(v, version)) return rc;
+int FindImpl<C>::find_host(bpp_verifier* v, const FindArgs& a) {
+    if (int rc = V::container_args_ok(v, a.version)) return rc;
     MixedPlan p;
-    int rc = mixed_plan_serialized(v->s, m_of, count, (size_t)container_point_bytes<C>(version), false, p);
+    int rc = mixed_plan_serialized(v->s, a.m_of, a.count, (size_t)container_point_bytes<C>(a.version), false, p);
     if (rc) return rc;
-    // no more records than there are pairs can come back
-    const size_t cap = std::min(max_hits, n_keys * count);
+    const size_t pairs = a.n_keys * a.count;
     KeyUpload dk;
-    DevBuf dpr, dcm, dix, dam, dok, dhits, dn, dws;
-    const void *p_pr, *p_cm, *p_ix, *p_am, *p_k;
-    if ((rc = upload_optional(proofs, p.proof_bytes, dpr, p_pr))) return rc;
-    if ((rc = upload_optional(commitments, p.comm_bytes, dcm, p_cm))) return rc;
-    if ((rc = upload_optional(index, count * 8, dix, p_ix))) return rc;
-    if ((rc = upload_optional(amounts, (sealed ? count : n_keys * count) * 8, dam, p_am))) return rc;
-    if ((rc = upload_optional(keys, n_keys * 32, dk.d, p_k))) return rc;
-    const size_t wsb = layout(v, p, count, n_keys).total;
-    HIPCHK(dok.alloc(count * 4));
-    HIPCHK(dhits.alloc(cap * FIND_HIT_WORDS * 4));
-    HIPCHK(dn.alloc(4));
+    BlockUpload up;
+    DevBuf dtg, dok, dhits, dn, dws;
+    const void *p_k, *p_tg = nullptr;
+    if ((rc = up.upload(p, a.proofs, a.commitments, a.index, a.count, a.amounts, a.sealed ? a.count : pairs))) return rc;
+    if (a.tagged && (rc = upload_optional(a.tags, a.count, dtg, p_tg))) return rc;
+    if ((rc = upload_optional(a.keys, a.n_keys * 32, dk.d, p_k))) return rc;
+    const size_t wsb = layout(v, p, a.count, a.n_keys, a.tagged).total;
+    FindArgs d = a;
+    d.proofs = up.proofs;
+    d.commitments = up.commitments;
+    d.index = up.index;
+    d.amounts = up.amounts;
+    d.keys = static_cast<const uint8_t*>(p_k);
+    d.tags = static_cast<const uint8_t*>(p_tg);
+    d.max_hits = std::min(a.max_hits, pairs);   // no more records than there are pairs can come back
+    HIPCHK(dok.alloc(a.count * 4));
+    HIPCHK(dhits.alloc(d.max_hits * FIND_HIT_WORDS * 4));
+    HIPCHK(dn.alloc(8));   // the hits found, the candidates
     HIPCHK(dws.alloc(wsb));
-    rc = find(v, static_cast<const uint8_t*>(p_pr), static_cast<const uint8_t*>(p_cm), m_of, count, version,
-              (flags & BPP_PROVE_AMOUNT64) != 0, sealed, static_cast<const uint8_t*>(p_k), n_keys, index_base,
-              static_cast<const uint64_t*>(p_ix), static_cast<const uint64_t*>(p_am), dok.u32(), dhits.u32(), cap, dn.u32(), dws.p,
-              wsb, nullptr);
-    if (rc) return rc;
-    uint32_t found = 0;
-    HIPCHK(hipMemcpy(&found, dn.p, 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_ok, dok.p, count * 4, hipMemcpyDeviceToHost));
-    const size_t written = std::min<size_t>(found, cap);
-    if (written) HIPCHK(hipMemcpy(out_hits, dhits.p, written * FIND_HIT_WORDS * 4, hipMemcpyDeviceToHost));
-    *out_n_hits = found;
+    d.ok = dok.u32();
+    d.hits = dhits.u32();
+    d.n_hits = dn.u32();
+    d.n_candidates = dn.u32() + 1;
+    if ((rc = find(v, d, dws.p, wsb, nullptr))) return rc;
+    uint32_t found[2] = {0, 0};
+    HIPCHK(hipMemcpy(found, dn.p, a.tagged ? 8 : 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(a.ok, dok.p, a.count * 4, hipMemcpyDeviceToHost));
+    const size_t written = std::min<size_t>(found[0], d.max_hits);
+    if (written) HIPCHK(hipMemcpy(a.hits, dhits.p, written * FIND_HIT_WORDS * 4, hipMemcpyDeviceToHost));
+    *a.n_hits = found[0];
+    if (a.tagged && a.n_candidates) *a.n_candidates = found[1];
     return BPP_OK;
 }
 
@@ -333,6 +505,29 @@ int FindImpl<C>::seal_host(const uint8_t* blind_key, uint64_t index_base, const 
                       static_cast<uint64_t*>(dio.p), nullptr))
         return rc;
     HIPCHK(hipMemcpy(out, dio.p, count * 8, hipMemcpyDeviceToHost));
+    return BPP_OK;
+}
+
+template <class C>
+int FindImpl<C>::tags(const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_index, size_t count, uint8_t* d_out,
+                          hipStream_t st) {
+    BlindKey key;
+    load_key_words(blind_key, key.w);
+    hipLaunchKernelGGL(k_view_tags<C>, dim3(cdiv(count, FIND_BLOCK)), dim3(FIND_BLOCK), 0, st, key, index_base, d_index, d_out,
+                       count);
+    HIPCHK(hipGetLastError());
+    return BPP_OK;
+}
+
+template <class C>
+int FindImpl<C>::tags_host(const uint8_t* blind_key, uint64_t index_base, const uint64_t* index, size_t count, uint8_t* out) {
+    DevBuf dix, dout;
+    const void* p_ix;
+    if (int rc = upload_optional(index, count * 8, dix, p_ix)) return rc;
+    HIPCHK(dout.alloc(count));
+    if (int rc = tags(blind_key, index_base, static_cast<const uint64_t*>(p_ix), count, static_cast<uint8_t*>(dout.p), nullptr))
+        return rc;
+    HIPCHK(hipMemcpy(out, dout.p, count, hipMemcpyDeviceToHost));
     return BPP_OK;
 }
 #endif  // BPP_IMPL_DEFINITIONS

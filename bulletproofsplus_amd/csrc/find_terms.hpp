@@ -1,14 +1,14 @@
 // find_terms.hpp -- the arithmetic of the fused verify-and-find call (find.hpp) that is not the curve's: the pad that
 // seals an output's amount, and the index arithmetic of the hit list's compaction.  Plain C++ beside recover_terms.hpp, so
 // the host tests (tests/host/find_host_test.cpp, tests/host/view_tag_host_test.cpp) compile the very code k_amounts_seal,
-// k_find_confirm, the compaction kernels and the tag kernels of find_tags.hpp run.
+// the confirmation kernels, the compaction kernels and the tag kernels of find.hpp run.
 //
 // A sealed amount is amount XOR pad(key, idx): an output carries ONE 8-byte ciphertext of its amount and every view key
 // tries its own pad on it.  The pad is domain-separated from every blinding slot by its tag ("bppa" against blind_half's
 // "bppb"), so it is no function of any scalar that enters a proof.  Sealing and opening are the same operation.
 //
 // A view tag is ONE byte of the same block under a third tag ("bppt"): the sender attaches view_tag(key, idx) to the output,
-// and the tagged call (find_tags.hpp) computes it first -- one compression per (key, output) pair -- and expands slots and
+// and the tagged call (find.hpp) computes it first -- one compression per (key, output) pair -- and expands slots and
 // walks tables only where it matches: 255 of 256 foreign pairs stop there.  The tag hides nothing that a one-byte PRF
 // output does not, and it authenticates nothing: a wrong tag hides an output from its owner's scan exactly as a wrong sealed
 // amount does.  Also here: how the tag test's lanes and the candidate list are numbered.
@@ -18,38 +18,18 @@
 namespace bpp {
 
 // the first 8 bytes, as a little-endian u64, of SHA-256(key || "bppa" || idx as u64 LE || 0 as u32 || 0 as u32): blind_half's
-// 52-byte block under the other tag, in registers alone
+// 52-byte block (key_block_digest) under the other tag, in registers alone
 BPP_HD uint64_t amount_pad(const uint32_t* key, uint64_t idx) {
-    uint32_t w[16], dg[8];
-#pragma unroll
-    for (int t = 0; t < 8; t++) w[t] = bswap32(key[t]);
-    w[8] = 0x62707061u;   // "bppa", as the block's big-endian word
-    w[9] = bswap32((uint32_t)idx);
-    w[10] = bswap32((uint32_t)(idx >> 32));
-    w[11] = 0;
-    w[12] = 0;
-    w[13] = 0x80000000u;
-    w[14] = 0;
-    w[15] = 52 * 8;
-    sha256_one_block(w, dg);
+    uint32_t dg[8];
+    key_block_digest(key, 0x62707061u, idx, 0, 0, dg);   // "bppa", as the block's big-endian word
     return (uint64_t)bswap32(dg[0]) | (uint64_t)bswap32(dg[1]) << 32;
 }
 
-// the first byte of SHA-256(key || "bppt" || idx as u64 LE || 0 as u32 || 0 as u32): amount_pad's block under the third tag,
-// in registers alone
+// the first byte of SHA-256(key || "bppt" || idx as u64 LE || 0 as u32 || 0 as u32): the same block under the third tag, in
+// registers alone
 BPP_HD uint8_t view_tag(const uint32_t* key, uint64_t idx) {
-    uint32_t w[16], dg[8];
-#pragma unroll
-    for (int t = 0; t < 8; t++) w[t] = bswap32(key[t]);
-    w[8] = 0x62707074u;   // "bppt", as the block's big-endian word
-    w[9] = bswap32((uint32_t)idx);
-    w[10] = bswap32((uint32_t)(idx >> 32));
-    w[11] = 0;
-    w[12] = 0;
-    w[13] = 0x80000000u;
-    w[14] = 0;
-    w[15] = 52 * 8;
-    sha256_one_block(w, dg);
+    uint32_t dg[8];
+    key_block_digest(key, 0x62707074u, idx, 0, 0, dg);   // "bppt", as the block's big-endian word
     return (uint8_t)(dg[0] >> 24);
 }
 

@@ -327,6 +327,27 @@ static inline int upload_optional(const void* src, size_t bytes, DevBuf& d, cons
     return BPP_OK;
 }
 
+// what every host twin of a scan uploads of its block: proofs, commitments, index and amounts (n_amounts of them)
+struct BlockUpload {
+    DevBuf dpr, dcm, dix, dam;
+    const uint8_t *proofs = nullptr, *commitments = nullptr;
+    const uint64_t *index = nullptr, *amounts = nullptr;
+    int upload(const MixedPlan& p, const uint8_t* h_proofs, const uint8_t* h_commitments, const uint64_t* h_index, size_t count,
+               const uint64_t* h_amounts, size_t n_amounts) {
+        const void *pr, *cm, *ix, *am;
+        int rc;
+        if ((rc = upload_optional(h_proofs, p.proof_bytes, dpr, pr))) return rc;
+        if ((rc = upload_optional(h_commitments, p.comm_bytes, dcm, cm))) return rc;
+        if ((rc = upload_optional(h_index, count * 8, dix, ix))) return rc;
+        if ((rc = upload_optional(h_amounts, n_amounts * 8, dam, am))) return rc;
+        proofs = static_cast<const uint8_t*>(pr);
+        commitments = static_cast<const uint8_t*>(cm);
+        index = static_cast<const uint64_t*>(ix);
+        amounts = static_cast<const uint64_t*>(am);
+        return BPP_OK;
+    }
+};
+
 template <class C>
 int RecoverImpl<C>::recover_masks_mixed_host(bpp_verifier* v, const uint64_t* scalars, const uint32_t* m_of, size_t count,
                                              const uint64_t* challenges, const uint8_t* blind_key, uint64_t index_base,
@@ -429,21 +450,19 @@ int RecoverImpl<C>::scan_serialized_mixed_host(bpp_verifier* v, const uint8_t* p
     const uint32_t logn = v->s.k - (uint32_t)__builtin_ctz(v->s.m);
     size_t nbl = 0;
     for (size_t i = 0; i < count; i++) nbl += pb_blind_elems(logn + (uint32_t)__builtin_ctz(m_of[i]));
-    DevBuf dpr, dcm, dix, dbl, dam, dout, dst, dws;
-    const void *p_pr, *p_cm, *p_ix, *p_bl, *p_am;
-    if ((rc = upload_optional(proofs, p.proof_bytes, dpr, p_pr))) return rc;
-    if ((rc = upload_optional(commitments, p.comm_bytes, dcm, p_cm))) return rc;
-    if ((rc = upload_optional(index, count * 8, dix, p_ix))) return rc;
+    BlockUpload up;
+    DevBuf dbl, dout, dst, dws;
+    const void* p_bl;
+    if ((rc = up.upload(p, proofs, commitments, index, count, amounts, count))) return rc;
     if ((rc = upload_optional(blinding, nbl * 32, dbl, p_bl))) return rc;
-    if ((rc = upload_optional(amounts, count * 8, dam, p_am))) return rc;
     const size_t wsb = scan_layout(p, count).total;
     HIPCHK(dout.alloc(count * 32));
     HIPCHK(dst.alloc(count * 4));
     HIPCHK(dws.alloc(wsb));
-    const Blinding b{blind_key, index_base, static_cast<const uint64_t*>(p_ix), static_cast<const uint64_t*>(p_bl)};
-    rc = scan_serialized_mixed(v, static_cast<const uint8_t*>(p_pr), static_cast<const uint8_t*>(p_cm), m_of, count,
-                               (flags & BPP_SER_TRANSCRIPT) != 0, version, (flags & BPP_PROVE_AMOUNT64) != 0, b,
-                               static_cast<const uint64_t*>(p_am), static_cast<uint64_t*>(dout.p), dst.u32(), dws.p, wsb, nullptr);
+    const Blinding b{blind_key, index_base, up.index, static_cast<const uint64_t*>(p_bl)};
+    rc = scan_serialized_mixed(v, up.proofs, up.commitments, m_of, count, (flags & BPP_SER_TRANSCRIPT) != 0, version,
+                               (flags & BPP_PROVE_AMOUNT64) != 0, b, up.amounts, static_cast<uint64_t*>(dout.p), dst.u32(), dws.p,
+                               wsb, nullptr);
     if (rc) return rc;
     HIPCHK(hipMemcpy(out_masks, dout.p, count * 32, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out_status, dst.p, count * 4, hipMemcpyDeviceToHost));

@@ -15,6 +15,9 @@
 // so the groups of a wave read one proof's coefficients.
 // k_scan_keys_confirm: one lane per (key, single-output proof) pair with a candidate amount: k_recover_confirm's walk,
 // compared with the decoded V_0 projectively (walk_equals_wire): no inversion in Fp.
+// What a pair's lanes compute is written once, as force-inlined device functions -- pair_key_index, pair_gamma,
+// pair_confirms -- which the find kernels (find.hpp) call too; a kernel keeps its numbering, its early exits and its stores.
+// Force-inlined because the key is a local array: handed to a function that is not inlined it would go through memory.
 #pragma once
 #include "recover.hpp"
 #include "recover_coeffs.hpp"
@@ -104,31 +107,24 @@ struct ScanKeysJob {
     size_t count, total;         // proofs of this class, proofs of the call
 };
 
+// key number key_no's words from the caller's buffer into registers; returns the blinding index of caller position `caller`
+__device__ __forceinline__ uint64_t pair_key_index(const ScanKeysJob& j, size_t key_no, size_t caller, uint32_t key[8]) {
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = j.keys[key_no * 8 + w];
+    return j.index ? j.index[caller] : j.index_base + caller;
+}
+
+// Gamma = A0 + sum c_s slot_s of the pair (key key_no, launch position p, caller position `caller`), by the pair's whole
+// group of SCAN_GROUP lanes: a strided sum over the live slots, the butterfly, and from lane s == 0 the canonical words to
+// the pair's place `at` of j.out_masks
 template <class C>
-__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_keys(ScanKeysJob j) {
+__device__ __forceinline__ void pair_gamma(const ScanKeysJob& j, size_t key_no, size_t p, size_t caller, size_t at) {
     using P = typename C::Fr;
     using F = Fe<P>;
     constexpr int CW = coeff_words<P>();
     const uint32_t lane = threadIdx.x & 63u, s = lane & (SCAN_GROUP - 1);
-    const size_t q = ((size_t)blockIdx.x * SCAN_BLOCK + threadIdx.x) / SCAN_GROUP;
-    if (q >= j.count * j.n_keys) return;   // a whole group: the exchanges below stay inside a group
-    const size_t p = q / j.n_keys;
-    const uint32_t key_no = (uint32_t)(q - p * j.n_keys);
-    const size_t caller = j.rx[p * RX_WORDS + RX_CALLER];
-    const size_t at = (size_t)key_no * j.total + caller;
-    const bool rejected = j.status[p] != 0;
-    if (rejected || j.bad[p]) {   // before the key is read: the decoder's FormatError for every key; Gamma undefined
-        if (s == 0) {
-            const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            st_words<8>(j.out_masks + at * 8, z);
-            j.out_status[at] = rejected ? (uint32_t)BPP_FORMAT_ERROR : (uint32_t)BPP_SCAN_UNCONFIRMED;
-        }
-        return;
-    }
     uint32_t key[8];
-#pragma unroll
-    for (int w = 0; w < 8; w++) key[w] = j.keys[(size_t)key_no * 8 + w];
-    const uint64_t idx = j.index ? j.index[caller] : j.index_base + caller;
+    const uint64_t idx = pair_key_index(j, key_no, caller, key);
     const uint32_t nl = coeff_live_slots(j.k);
     const uint32_t* cf = j.coeffs + p * (size_t)coeff_elems(j.k) * CW;
     F sum = F::zero();
@@ -146,8 +142,46 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan_keys(ScanKeysJob j) {
         uint32_t o[8];
         fe_to_canonical(fe_add(sum, coeff_ldg<P>(cf)), o);
         st_words<8>(j.out_masks + at * 8, o);
-        j.out_status[at] = (uint32_t)BPP_SCAN_UNCONFIRMED;
     }
+}
+
+// whether V_0 of the record of launch position p is amount g + Gamma h, with the canonical Gamma a scan kernel left at
+// pair place `at`: k_recover_confirm's walk, compared projectively
+template <class C>
+__device__ __forceinline__ bool pair_confirms(const VerifyShape& s, const uint32_t* __restrict__ table, const ScanKeysJob& j,
+                                              uint64_t amount, uint32_t amount64, size_t at, size_t p,
+                                              const uint32_t* __restrict__ records, uint32_t nv, uint32_t v0) {
+    constexpr int N = C::Fp::N;
+    constexpr int WW = 2 * N + 2;
+    uint32_t kv[8], kg[8];
+    commit_amount_scalar<C>(amount, amount64 != 0, kv);
+    ld_words<8>(j.out_masks + at * 8, kg);
+    const Xyzz<C> acc = commit_walk<C>(
+        s, kv, kg, [&](size_t e) { return aff_ldg<C>(table + e * (size_t)(2 * N)); },
+        [](Xyzz<C>& a, const Aff<C>& pt, bool neg) { xyzz_madd_lazy(a, pt, neg); });
+    return walk_equals_wire<C>(acc, records + ((size_t)p * nv + v0) * WW);
+}
+
+template <class C>
+__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_keys(ScanKeysJob j) {
+    const uint32_t s = threadIdx.x & (SCAN_GROUP - 1);
+    const size_t q = ((size_t)blockIdx.x * SCAN_BLOCK + threadIdx.x) / SCAN_GROUP;
+    if (q >= j.count * j.n_keys) return;   // a whole group: the exchanges of pair_gamma stay inside a group
+    const size_t p = q / j.n_keys;
+    const uint32_t key_no = (uint32_t)(q - p * j.n_keys);
+    const size_t caller = j.rx[p * RX_WORDS + RX_CALLER];
+    const size_t at = (size_t)key_no * j.total + caller;
+    const bool rejected = j.status[p] != 0;
+    if (rejected || j.bad[p]) {   // before the key is read: the decoder's FormatError for every key; Gamma undefined
+        if (s == 0) {
+            const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            st_words<8>(j.out_masks + at * 8, z);
+            j.out_status[at] = rejected ? (uint32_t)BPP_FORMAT_ERROR : (uint32_t)BPP_SCAN_UNCONFIRMED;
+        }
+        return;
+    }
+    pair_gamma<C>(j, key_no, p, caller, at);
+    if (s == 0) j.out_status[at] = (uint32_t)BPP_SCAN_UNCONFIRMED;
 }
 
 // One lane per (key, proof) pair of the single-output class (launch position = gathered position: the class comes
@@ -159,20 +193,12 @@ __global__ void __launch_bounds__(COMMIT_BLOCK) k_scan_keys_confirm(VerifyShape 
                                                                     ScanKeysJob j, const uint64_t* __restrict__ amounts,
                                                                     uint32_t amount64, const uint32_t* __restrict__ records,
                                                                     uint32_t nv, uint32_t v0) {
-    constexpr int N = C::Fp::N;
-    constexpr int WW = 2 * N + 2;
     const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= j.count * j.n_keys) return;
     const size_t p = q / j.n_keys;
     if (j.status[p] || j.bad[p]) return;
     const size_t at = (q - p * j.n_keys) * j.total + j.rx[p * RX_WORDS + RX_CALLER];
-    uint32_t kv[8], kg[8];
-    commit_amount_scalar<C>(amounts[at], amount64 != 0, kv);
-    ld_words<8>(j.out_masks + at * 8, kg);   // canonical: k_scan_keys wrote it
-    const Xyzz<C> acc = commit_walk<C>(
-        s, kv, kg, [&](size_t e) { return aff_ldg<C>(table + e * (size_t)(2 * N)); },
-        [](Xyzz<C>& a, const Aff<C>& pt, bool neg) { xyzz_madd_lazy(a, pt, neg); });
-    const bool same = walk_equals_wire<C>(acc, records + ((size_t)p * nv + v0) * WW);
+    const bool same = pair_confirms<C>(s, table, j, amounts[at], amount64, at, p, records, nv, v0);
     j.out_status[at] = same ? 0u : 1u;
     if (!same) {
         const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -207,11 +233,17 @@ struct RecoverKeysImpl {
         return w;
     }
     static size_t workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count);
-    // One class of a call: k_recover_coeffs over its proofs, then k_scan_keys over its (key, proof) pairs.  j arrives with
-    // the call's part filled in (keys, index, outputs, total) and leaves with the class's (k, rx, coeffs, bad, status,
-    // count), for the confirmation that follows.  w_idx, w_status, w_bad: the call's, from gathered position 0.
-    static int scan_class(const typename V::ClassView& cv, const uint32_t* w_idx, const uint32_t* w_status, uint32_t* w_bad,
-                          uint32_t* coeffs, ScanKeysJob& j, hipStream_t st);
+    // the call's part of the pair job: the keys, the index, where Gamma and the pair word go ([key][caller position]), total
+    static ScanKeysJob call_job(const uint8_t* d_keys, size_t n_keys, uint64_t index_base, const uint64_t* d_index,
+                                uint32_t* out_masks, uint32_t* out_status, size_t total);
+    // One class of a call, in three steps (the find call, find.hpp, takes them apart).  bind_class: the class's part of j
+    // (k, rx, coeffs, bad, status, count), which the confirmation that follows reads too; w_idx, w_status, w_bad: the call's,
+    // from gathered position 0; coeffs: the class's.  launch_coeffs: k_recover_coeffs over its proofs, into the coeffs and
+    // bad that j was bound to.  launch_scan_keys: k_scan_keys over its (key, proof) pairs.
+    static void bind_class(const typename V::ClassView& cv, const uint32_t* w_idx, const uint32_t* w_status, const uint32_t* w_bad,
+                           const uint32_t* coeffs, ScanKeysJob& j);
+    static int launch_coeffs(const typename V::ClassView& cv, uint32_t* coeffs, uint32_t* w_bad, hipStream_t st);
+    static int launch_scan_keys(const ScanKeysJob& j, hipStream_t st);
     // d_keys: n_keys x 32 bytes (device, 4-byte aligned); d_index: count x u64 or null; d_amounts: n_keys x count or null;
     // d_out_masks: n_keys x count x 4 words; d_status: n_keys x count words
     static int scan(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments, const uint32_t* m_of, size_t count,
@@ -247,18 +279,14 @@ int RecoverKeysImpl<C>::scan(bpp_verifier* v, const uint8_t* d_proofs, const uin
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
     rc = V::decode_front(p, L.f, count, d_proofs, d_commitments, version, ws, st);
     if (rc) return rc;
-    ScanKeysJob j;
-    j.n_keys = (uint32_t)n_keys;
-    j.keys = reinterpret_cast<const uint32_t*>(d_keys);
-    j.index_base = index_base;
-    j.index = d_index;
-    j.out_masks = reinterpret_cast<uint32_t*>(d_out_masks);
-    j.out_status = d_status;
-    j.total = count;
+    ScanKeysJob j = call_job(d_keys, n_keys, index_base, d_index, reinterpret_cast<uint32_t*>(d_out_masks), d_status, count);
     return V::for_each_class(v, p, L.f, ws, [&](const typename V::ClassView& cv) {
         int rc1 = V::derive_challenges(v, cv.ps, cv.pts, cv.count, cv.challenges, st);
         if (rc1) return rc1;
-        if ((rc1 = scan_class(cv, W(L.f.idx), W(L.f.status), W(L.bad), W(L.coeffs) + L.coeff_of[cv.c] * CW, j, st))) return rc1;
+        uint32_t* coeffs = W(L.coeffs) + L.coeff_of[cv.c] * CW;
+        bind_class(cv, W(L.f.idx), W(L.f.status), W(L.bad), coeffs, j);
+        if ((rc1 = launch_coeffs(cv, coeffs, W(L.bad), st))) return rc1;
+        if ((rc1 = launch_scan_keys(j, st))) return rc1;
         if (cv.c != 0 || !d_amounts) return BPP_OK;
         // the single-output class comes first in gathered order: launch position = gathered position
         hipLaunchKernelGGL(k_scan_keys_confirm<C>, dim3(cdiv(cv.count * n_keys, COMMIT_BLOCK)), dim3(COMMIT_BLOCK), 0, st, v->s,
@@ -270,19 +298,42 @@ int RecoverKeysImpl<C>::scan(bpp_verifier* v, const uint8_t* d_proofs, const uin
 }
 
 template <class C>
-int RecoverKeysImpl<C>::scan_class(const typename V::ClassView& cv, const uint32_t* w_idx, const uint32_t* w_status,
-                                   uint32_t* w_bad, uint32_t* coeffs, ScanKeysJob& j, hipStream_t st) {
+ScanKeysJob RecoverKeysImpl<C>::call_job(const uint8_t* d_keys, size_t n_keys, uint64_t index_base, const uint64_t* d_index,
+                                         uint32_t* out_masks, uint32_t* out_status, size_t total) {
+    ScanKeysJob j = {};
+    j.n_keys = (uint32_t)n_keys;
+    j.keys = reinterpret_cast<const uint32_t*>(d_keys);
+    j.index_base = index_base;
+    j.index = d_index;
+    j.out_masks = out_masks;
+    j.out_status = out_status;
+    j.total = total;
+    return j;
+}
+
+template <class C>
+void RecoverKeysImpl<C>::bind_class(const typename V::ClassView& cv, const uint32_t* w_idx, const uint32_t* w_status,
+                                    const uint32_t* w_bad, const uint32_t* coeffs, ScanKeysJob& j) {
     j.k = cv.ps.s.k;
     j.rx = w_idx + cv.first * RX_WORDS;
     j.coeffs = coeffs;
     j.bad = w_bad + cv.first;
     j.status = w_status + cv.first;
     j.count = cv.count;
-    hipLaunchKernelGGL(k_recover_coeffs<C>, dim3(cdiv(cv.count * RECOVER_GROUP, RECOVER_BLOCK)), dim3(RECOVER_BLOCK), 0, st, j.k,
-                       cv.ps.s.m, reinterpret_cast<const uint32_t*>(cv.sc3), reinterpret_cast<const uint32_t*>(cv.challenges),
-                       coeffs, w_bad + cv.first, cv.count);
+}
+
+template <class C>
+int RecoverKeysImpl<C>::launch_coeffs(const typename V::ClassView& cv, uint32_t* coeffs, uint32_t* w_bad, hipStream_t st) {
+    hipLaunchKernelGGL(k_recover_coeffs<C>, dim3(cdiv(cv.count * RECOVER_GROUP, RECOVER_BLOCK)), dim3(RECOVER_BLOCK), 0, st,
+                       cv.ps.s.k, cv.ps.s.m, reinterpret_cast<const uint32_t*>(cv.sc3),
+                       reinterpret_cast<const uint32_t*>(cv.challenges), coeffs, w_bad + cv.first, cv.count);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_scan_keys<C>, dim3(cdiv(cv.count * j.n_keys * SCAN_GROUP, SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, st, j);
+    return BPP_OK;
+}
+
+template <class C>
+int RecoverKeysImpl<C>::launch_scan_keys(const ScanKeysJob& j, hipStream_t st) {
+    hipLaunchKernelGGL(k_scan_keys<C>, dim3(cdiv(j.count * j.n_keys * SCAN_GROUP, SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, st, j);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
@@ -306,20 +357,17 @@ int RecoverKeysImpl<C>::scan_host(bpp_verifier* v, const uint8_t* proofs, const 
     if (rc) return rc;
     const size_t pairs = n_keys * count;
     KeyUpload dk;
-    DevBuf dpr, dcm, dix, dam, dout, dst, dws;
-    const void *p_pr, *p_cm, *p_ix, *p_am, *p_k;
-    if ((rc = upload_optional(proofs, p.proof_bytes, dpr, p_pr))) return rc;
-    if ((rc = upload_optional(commitments, p.comm_bytes, dcm, p_cm))) return rc;
-    if ((rc = upload_optional(index, count * 8, dix, p_ix))) return rc;
-    if ((rc = upload_optional(amounts, pairs * 8, dam, p_am))) return rc;
+    BlockUpload up;
+    DevBuf dout, dst, dws;
+    const void* p_k;
+    if ((rc = up.upload(p, proofs, commitments, index, count, amounts, pairs))) return rc;
     if ((rc = upload_optional(keys, n_keys * 32, dk.d, p_k))) return rc;
     const size_t wsb = layout(v, p, count).total;
     HIPCHK(dout.alloc(pairs * 32));
     HIPCHK(dst.alloc(pairs * 4));
     HIPCHK(dws.alloc(wsb));
-    rc = scan(v, static_cast<const uint8_t*>(p_pr), static_cast<const uint8_t*>(p_cm), m_of, count, version,
-              (flags & BPP_PROVE_AMOUNT64) != 0, static_cast<const uint8_t*>(p_k), n_keys, index_base,
-              static_cast<const uint64_t*>(p_ix), static_cast<const uint64_t*>(p_am), static_cast<uint64_t*>(dout.p), dst.u32(),
+    rc = scan(v, up.proofs, up.commitments, m_of, count, version, (flags & BPP_PROVE_AMOUNT64) != 0,
+              static_cast<const uint8_t*>(p_k), n_keys, index_base, up.index, up.amounts, static_cast<uint64_t*>(dout.p), dst.u32(),
               dws.p, wsb, nullptr);
     if (rc) return rc;
     HIPCHK(hipMemcpy(out_masks, dout.p, pairs * 32, hipMemcpyDeviceToHost));

@@ -61,13 +61,14 @@ BPP_HD void sha256_one_block(uint32_t w[16], uint32_t out[8]) {
 }
 BPP_HD uint32_t bswap32(uint32_t x) { return (x >> 24) | ((x >> 8) & 0xff00u) | ((x << 8) & 0xff0000u) | (x << 24); }
 
-// c_h = SHA-256(key || "bppb" || idx as u64 LE || slot as u32 LE || h as u32 LE) as 8 little-endian words of a 256-bit
-// integer: 52 bytes, one block
-BPP_HD void blind_half(const uint32_t* key, uint64_t idx, uint32_t slot, uint32_t h, uint32_t c[8]) {
-    uint32_t w[16], dg[8];
+// SHA-256(key || tag || idx as u64 LE || slot as u32 LE || h as u32 LE): the 52-byte block, one compression, that every
+// value derived from a blinding key starts from -- a blinding slot here, the amount pad and the view tag in find_terms.hpp.
+// key: 8 little-endian words; tag: the block's big-endian word, the domain separator; dg: the digest's big-endian words.
+BPP_HD void key_block_digest(const uint32_t* key, uint32_t tag, uint64_t idx, uint32_t slot, uint32_t h, uint32_t dg[8]) {
+    uint32_t w[16];
 #pragma unroll
     for (int t = 0; t < 8; t++) w[t] = bswap32(key[t]);
-    w[8] = bswap32(0x62707062u);   // "bppb"
+    w[8] = tag;
     w[9] = bswap32((uint32_t)idx);
     w[10] = bswap32((uint32_t)(idx >> 32));
     w[11] = bswap32(slot);
@@ -76,6 +77,12 @@ BPP_HD void blind_half(const uint32_t* key, uint64_t idx, uint32_t slot, uint32_
     w[14] = 0;
     w[15] = 52 * 8;
     sha256_one_block(w, dg);
+}
+
+// c_h = the digest of the block under "bppb", as 8 little-endian words of a 256-bit integer
+BPP_HD void blind_half(const uint32_t* key, uint64_t idx, uint32_t slot, uint32_t h, uint32_t c[8]) {
+    uint32_t dg[8];
+    key_block_digest(key, bswap32(0x62707062u), idx, slot, h, dg);   // "bppb"
 #pragma unroll
     for (int t = 0; t < 8; t++) c[t] = bswap32(dg[t]);
 }

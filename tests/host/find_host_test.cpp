@@ -1,6 +1,7 @@
 // Host-side harness for csrc/find_terms.hpp (compiled with g++, no GPU needed): the pad of a sealed amount and the index
-// arithmetic of the hit list's compaction, by the code k_amounts_seal, k_find_confirm, k_find_count and k_find_emit
-// (csrc/find.hpp) run.
+// arithmetic of the hit list's compaction, by the code k_amounts_seal, the two confirmation kernels (find_pair_amount),
+// k_find_count and k_find_emit (csrc/find.hpp) run -- amount_pad is key_block_digest (csrc/recover_terms.hpp), the one builder
+// of the 52-byte block, under the pad's word.
 //   find_host_test pad <file>
 // file: one line per pad, "<64 hex key bytes> <index, decimal>"; prints the pad as 16 hex digits per line.
 //   find_host_test seal <file>

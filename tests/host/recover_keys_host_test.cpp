@@ -1,6 +1,7 @@
 // Host-side harness for csrc/recover_coeffs.hpp (compiled with g++, no GPU needed): the key-independent coefficients of
-// mask recovery and the projective comparison of the many-key scan, by the code k_recover_coeffs, k_scan_keys and
-// k_scan_keys_confirm (csrc/recover_keys.hpp) run.
+// mask recovery and the projective comparison of the many-key scan, by the code k_recover_coeffs, pair_gamma
+// (k_scan_keys; k_find_scan_list of csrc/find.hpp) and pair_confirms (k_scan_keys_confirm and the find call's two confirmation
+// kernels) of csrc/recover_keys.hpp run.
 //   recover_keys_host_test <file>
 // file: one proof per line, fields separated by blanks, scalars as 64 hex digits (big-endian integers):
 //   <curve 0|1|2> <k> <m> <index> <n_keys> <64 hex key bytes>.. <r'> <s'> <delta'> <y> <z> <e> <e_1..e_k>

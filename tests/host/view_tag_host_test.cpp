@@ -1,5 +1,6 @@
 // Host-side harness for the view tag and the candidate list's index arithmetic of csrc/find_terms.hpp (compiled with g++,
-// no GPU needed): the code k_view_tags, k_find_tags and k_find_list (csrc/find_tags.hpp) run.
+// no GPU needed): the code k_view_tags, k_find_tags and k_find_list (csrc/find.hpp) run -- view_tag is key_block_digest
+// (csrc/recover_terms.hpp), the one builder of the 52-byte block, under the tag's word.
 //   view_tag_host_test tag <file>
 // file: one line per tag, "<64 hex key bytes> <index, decimal>"; prints the tag as 2 hex digits per line.
 //   view_tag_host_test list <n_keys> <count> <file>

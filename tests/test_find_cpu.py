@@ -1,5 +1,5 @@
 """CPU: the pad of a sealed amount and the compaction's index arithmetic (csrc/find_terms.hpp) through their host build
-(tests/host/find_host_test.cpp: the code k_amounts_seal, k_find_confirm, k_find_count and k_find_emit run).
+(tests/host/find_host_test.cpp: the code k_amounts_seal, the two confirmation kernels, k_find_count and k_find_emit run).
 
 The pad is held against hashlib (find_cases.pad), the hit list against a prefix sum (find_cases.compact).
 BPP_HOST_SANITIZE=1 builds the program under ASan + UBSan (a stand-alone binary, like the other host tests)."""

@@ -234,8 +234,9 @@ def _grid(cname):
     return bv, b"".join(pr), b"".join(cs), index, [v[0] for v in vals], keys, owner, hits
 
 
-def _find_device(torch, bv, raw, cm, ms, keys, amounts, index, max_hits, sealed):
-    """the device entry with guard words behind the records -> (ok, all words of d_hits, n_hits)"""
+def _find_device(torch, bv, raw, cm, ms, keys, amounts, index, max_hits, sealed, fill=None):
+    """the device entry with guard words behind the records, its workspace as the allocator hands it out or, with `fill`,
+    every byte of it set to that value -> (ok, all words of d_hits, n_hits)"""
     count, nk = len(ms), len(keys)
     dev = torch.device("cuda:0")
     d_p = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
@@ -249,6 +250,8 @@ def _find_device(torch, bv, raw, cm, ms, keys, amounts, index, max_hits, sealed)
     wsb = bv.verify_find_workspace_bytes(ms, nk)
     assert wsb > 0
     d_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    if fill is not None:
+        d_ws.fill_(fill)
     bv.verify_find_serialized_mixed_keys_device(d_p.data_ptr(), d_c.data_ptr(), ms, d_k.data_ptr(), nk, d_a.data_ptr(),
                                                 d_ok.data_ptr(), d_hits.data_ptr(), max_hits, d_n.data_ptr(), d_ws.data_ptr(),
                                                 wsb, torch.cuda.current_stream().cuda_stream, sealed=sealed,
@@ -299,6 +302,37 @@ def test_order_boundaries_and_overflow(cname):
                                                           index=index)
     assert ok.tolist() == plain and got == [(22 + j, i, am, g) for j, i, am, g in hits] and found == n_hits
     bv.close()
+
+
+def _dirty_cases(blk):
+    """the block of test 1 whole, and its single outputs alone (no pair word is left to zero then) -> [(positions, ms, raw,
+    cm, index, hits by their new positions, the two amount modes as (sealed, amounts))]"""
+    out = []
+    for pick in (list(range(len(MS))), [i for i, m in enumerate(MS) if m == 1]):
+        inv = {i: at for at, i in enumerate(pick)}
+        hits = [(j, inv[i], am, g) for j, i, am, g in blk["hits"]]
+        assert hits == sorted(hits) and len(hits) == len(blk["hits"])
+        modes = ((False, [[blk["amounts"][i] for i in pick]] * len(KEYS)), (True, [blk["sealed"][i] for i in pick]))
+        out.append((pick, [MS[i] for i in pick], b"".join(blk["pr"][i] for i in pick), b"".join(blk["cs"][i] for i in pick),
+                    [BASE + i for i in pick], hits, modes))
+    return out
+
+
+@pytest.mark.parametrize("cname", CURVES)
+def test_workspace_full_of_ones(cname):
+    """the device entry over a workspace whose every byte is 0xFF (a fresh allocation is usually zero, and would hide a pair
+    word that nothing wrote): the block of test 1 under three keys, max_hits above the hit count, key-major and sealed --
+    verdicts, records and n_hits are the fixtures', the words behind the records keep their guard value.  Then the
+    block's single outputs alone: every pair word is a kernel's to write, and the call zeroes none."""
+    torch = need_gpu()
+    blk = _block(cname, False, 1)
+    whole, singles = _dirty_cases(blk)
+    assert len(whole[0]) == 8 and 1 < len(singles[0]) < 8 and set(singles[1]) == {1}
+    for pick, ms, raw, cm, index, want, modes in (whole, singles):
+        for sl, am in modes:
+            ok, words, found = _find_device(torch, blk["bv"], raw, cm, ms, KEYS, am, index, len(want) + 3, sl, fill=0xff)
+            assert ok == [blk["verdict"][i] for i in pick] and found == len(want) > 0
+            assert words[:found].tolist() == _records(want) and (words[found:] == GUARD).all()
 
 
 @pytest.mark.parametrize("cname", CURVES)

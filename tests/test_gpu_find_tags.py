@@ -1,5 +1,5 @@
 """-m gpu: view tags, and the verify-and-find call that tests them first (bpp_view_tags*,
-bpp_range_verify_find_tagged_serialized_mixed_keys*; csrc/find_tags.hpp).
+bpp_range_verify_find_tagged_serialized_mixed_keys*; csrc/find.hpp).
 
 Expected values never come from the library.  The tag of an output is hashlib's (tag_cases.tag), made under the key of
 whoever made the proof.  The verdicts, the owners and the hit lists are those of tests/test_gpu_find.py, whose blocks are
@@ -191,8 +191,9 @@ def test_the_tag_decides(cname):
 
 
 # ---- 4. order and boundaries ------------------------------------------------------------------------------------------
-def _find_device(torch, bv, raw, cm, ms, keys, amounts, index, tags, max_hits, sealed):
-    """the device entry with tags and guard words behind the records -> (ok, all words of d_hits, n_hits, n_candidates)"""
+def _find_device(torch, bv, raw, cm, ms, keys, amounts, index, tags, max_hits, sealed, fill=None):
+    """the device entry with tags and guard words behind the records, its workspace as the allocator hands it out or, with
+    `fill`, every byte of it set to that value -> (ok, all words of d_hits, n_hits, n_candidates)"""
     count, nk = len(ms), len(keys)
     dev = torch.device("cuda:0")
     d_p = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
@@ -207,6 +208,8 @@ def _find_device(torch, bv, raw, cm, ms, keys, amounts, index, tags, max_hits, s
     wsb = bv.verify_find_tagged_workspace_bytes(ms, nk)
     assert wsb >= bv.verify_find_workspace_bytes(ms, nk) > 0
     d_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    if fill is not None:
+        d_ws.fill_(fill)
     bv.verify_find_serialized_mixed_keys_device(d_p.data_ptr(), d_c.data_ptr(), ms, d_k.data_ptr(), nk, d_a.data_ptr(),
                                                 d_ok.data_ptr(), d_hits.data_ptr(), max_hits, d_n.data_ptr(), d_ws.data_ptr(),
                                                 wsb, torch.cuda.current_stream().cuda_stream, sealed=sealed,
@@ -215,6 +218,25 @@ def _find_device(torch, bv, raw, cm, ms, keys, amounts, index, tags, max_hits, s
     n = d_n.cpu().numpy().view(np.uint32).tolist()
     assert n[1] == n[3] == GUARD
     return (d_ok.cpu().numpy().view(np.uint32).tolist(), d_hits.cpu().numpy().view(np.uint32).reshape(-1, 12), n[0], n[2])
+
+
+@pytest.mark.parametrize("cname", CURVES)
+def test_workspace_full_of_ones(cname):
+    """test_gpu_find's test of the same name through the tagged device entry: over a workspace of 0xFF bytes every pair
+    that is no candidate must read as no hit, so the call has to zero the pair words whatever the block holds -- the whole
+    block of test 1, then its single outputs alone.  Verdicts, records, n_hits and n_candidates (the hashlib count) are the
+    fixtures'."""
+    torch = need_gpu()
+    blk = TF._block(cname, False, 1)
+    tags = _maker_tags()
+    cands, hits = _tagged_hits(blk, KEYS, tags)
+    assert hits == blk["hits"] and 0 < len(hits) < len(cands) < len(KEYS) * len(MS)
+    for pick, ms, raw, cm, index, want, modes in TF._dirty_cases(blk):
+        for sl, am in modes:
+            ok, words, found, n_cand = _find_device(torch, blk["bv"], raw, cm, ms, KEYS, am, index, [tags[i] for i in pick],
+                                                    len(want) + 3, sl, fill=0xff)
+            assert ok == [blk["verdict"][i] for i in pick] and found == len(want) and n_cand == len(cands)
+            assert words[:found].tolist() == TF._records(want) and (words[found:] == GUARD).all()
 
 
 def _grid_tags(keys_in_set, all_keys, owner, index, need_foreign):

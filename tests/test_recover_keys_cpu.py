@@ -1,6 +1,6 @@
 """CPU: the key-independent coefficients of mask recovery and the projective comparison of the many-key scan
 (csrc/recover_coeffs.hpp) through their host build (tests/host/recover_keys_host_test.cpp: the code k_recover_coeffs,
-k_scan_keys and k_scan_keys_confirm run).
+k_scan_keys and k_scan_keys_confirm run, through pair_gamma and pair_confirms, which the find kernels call too).
 
 Gamma = A0 + sum_s c_s slot_s(key, index) is held against recover_mask's output (the single-key code) AND against the
 big-integer value recover_cases.recover_bigint on oracle.blinding_from_key(key, index, k, r) -- for the owning key also
