@@ -261,6 +261,8 @@ def lib():
         L.bpp_debug_verifier_mulvec.argtypes = [vp, ctypes.c_uint32, vp, vp, sz, vp, vp, sz, vp, vp, vp]
         # ... and its scalar stage on chosen proof scalars and challenges (host buffers, synchronous)
         L.bpp_debug_verifier_scalars.argtypes = [vp, ctypes.c_uint32, vp, vp, sz, vp]
+        # ... and the many-key scan's two kernels on chosen proof scalars and challenges (host buffers, synchronous)
+        L.bpp_debug_scan_keys.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, sz, sz, vp, sz, u64, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 

@@ -7,10 +7,11 @@
 // e_t^2; t = k: e^2 y^(nm+1) [z^2]) -- but what is written is the proof's 2k + 4 coefficients, by gathered position, and
 // a flag for a zero challenge.  Nothing of a key is involved: the coefficients are public and live in the workspace, as
 // the field's own limbs (Montgomery form, COEFF_WORDS words each) so that a pair lane multiplies what it loads.
-// k_scan_keys: a pair is SCAN_GROUP = 8 lanes, eight pairs per wave; lane s expands live slots s, s + 8, s + 16 (alpha,
-// delta, eta, d_L, d_R: 2k + 3 of them; r and s have coefficient zero and are never hashed), multiplies each by its
-// coefficient, the group sums by a 3-step butterfly of wave_shfl and lane 0 adds A0 and stores Gamma and the status at
-// [key][caller position].  The key's words come from the caller's buffer into registers; no LDS, no scratch, no atomics:
+// k_scan_keys: a pair is SCAN_GROUP = 8 lanes, eight pairs per wave; lane s expands live slots s, s + 8, s + 16 and, for
+// k >= 11 (25 live slots at k = 11, 27 at k = 12), s + 24 in a fourth stride (alpha, delta, eta, d_L, d_R: 2k + 3 of
+// them; r and s have coefficient zero and are never hashed), multiplies each by its coefficient, the group sums by a
+// 3-step butterfly of wave_shfl and lane 0 adds A0 and stores Gamma and the status at [key][caller position].
+// The key's words come from the caller's buffer into registers; no LDS, no scratch, no atomics:
 // nothing derived from a key but Gamma reaches memory.  Pairs are numbered proof-major (pair = position * n_keys + key),
 // so the groups of a wave read one proof's coefficients.
 // k_scan_keys_confirm: one lane per (key, single-output proof) pair with a candidate amount: k_recover_confirm's walk,
@@ -255,6 +256,15 @@ struct RecoverKeysImpl {
                          const uint64_t* amounts, uint64_t* out_masks, uint32_t* out_status);
 };
 
+// a host twin's copy of the keys (scan_host, find_host, the debug hook of tu_debug.hip): overwritten before it is freed, on
+// every way out
+struct KeyUpload {
+    DevBuf d;
+    ~KeyUpload() {
+        if (d.p) (void)hipMemset(d.p, 0, d.bytes);
+    }
+};
+
 #ifdef BPP_IMPL_DEFINITIONS
 template <class C>
 size_t RecoverKeysImpl<C>::workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
@@ -337,14 +347,6 @@ int RecoverKeysImpl<C>::launch_scan_keys(const ScanKeysJob& j, hipStream_t st) {
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
-
-// the host twin's copy of the keys: overwritten before it is freed, on every way out
-struct KeyUpload {
-    DevBuf d;
-    ~KeyUpload() {
-        if (d.p) (void)hipMemset(d.p, 0, d.bytes);
-    }
-};
 
 template <class C>
 int RecoverKeysImpl<C>::scan_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, const uint32_t* m_of,

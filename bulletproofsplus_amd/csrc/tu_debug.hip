@@ -5,11 +5,14 @@
 // Every pointer is a host pointer -- except in bpp_debug_verifier_mulvec, the verifier's back end (VerifyImpl::run_stage) on
 // MulVec scalars the test chooses, which takes device buffers as bpp_verifier_run does and adds no kernel.  Its front half,
 // the scalar stage (launch_verify_scalars) on challenges the test chooses, is bpp_debug_verifier_scalars: host pointers again.
+// bpp_debug_scan_keys is that hook's counterpart for the many-key scan (recover_keys.hpp): a class of chosen proofs through
+// k_recover_coeffs and k_scan_keys, host pointers, no kernel of its own.
 #include "host_util.hpp"
 
 #include "field_raw_ops.hpp"
 #include "fixed_glv.hpp"
 #include "impl_verify.hpp"   // declarations only (no BPP_IMPL_DEFINITIONS): the kernels live in tu_verify_*.hip
+#include "recover_keys.hpp"  // likewise: k_recover_coeffs and k_scan_keys live in tu_recover_keys_*.hip
 
 namespace bpp {
 
@@ -335,6 +338,95 @@ extern "C" int bpp_debug_verifier_mulvec(bpp_verifier* v, uint32_t m_view, const
                 out_geometry[1] = v->last_blocks_per_proof;
             }
             return rc;
+        });
+    });
+}
+
+// The many-key scan behind its decoder and its transcript -- k_recover_coeffs and k_scan_keys through
+// RecoverKeysImpl::call_job, bind_class, launch_coeffs and launch_scan_keys, the functions the scan and the find call run a
+// class with -- on proof scalars and challenges the caller chooses.  Host pointers, synchronous, no kernel of its own.
+//   m_view: as for bpp_debug_verifier_mulvec above; k and m are that shape's.
+//   scalars3 [count][3][4]: r', s', delta' ; challenges [count][3 + k][4]: y, z, e, e_1..e_k per launch position, canonical
+//   status_in [count]: the decoder's word per launch position (null: zeros) ; caller [count]: the caller position of each
+//     launch position, each below total (null: the identity) ; total >= count: the caller positions of the call
+//   keys [n_keys][32] ; index_base, index [total] (or null): the blinding index of a caller position
+//   out_coeffs [count][2k + 4][4]: [A0, c_alpha, c_delta, c_eta, c_dL.., c_dR..], canonical ; out_bad [count]
+//   out_masks [n_keys][total][4], out_status [n_keys][total]: uploaded as the caller filled them, then downloaded, so a place
+//     no launch position names comes back as it went in.  n_keys = 0: the coefficients alone.
+extern "C" int bpp_debug_scan_keys(bpp_verifier* v, uint32_t m_view, const uint64_t* scalars3, const uint64_t* challenges,
+                                   const uint32_t* status_in, const uint32_t* caller, size_t count, size_t total,
+                                   const uint8_t* keys, size_t n_keys, uint64_t index_base, const uint64_t* index,
+                                   uint64_t* out_coeffs, uint32_t* out_bad, uint64_t* out_masks, uint32_t* out_status) {
+    if (!v || !scalars3 || !challenges || !out_coeffs || !out_bad) return fail(BPP_E_ARG, "null argument");
+    if (n_keys && (!keys || !out_masks || !out_status)) return fail(BPP_E_ARG, "null argument");
+    uint32_t cls = 0;
+    if (!debug_view_shape(v, m_view, cls)) return fail(BPP_E_ARG, "m_view must be 0 or a power of two below m");
+    if (count == 0) return BPP_OK;   // before any launch -- and before total and caller are looked at: there is nothing to place
+    if (total < count) return fail(BPP_E_ARG, "total must be at least count");
+    // n_keys x total (>= n_keys x count) within the bound the scan's entry puts on its pairs, without a product that can wrap
+    const size_t bound = 0x7fffffffu / 64;
+    if (n_keys > bound || total > bound || (n_keys && total > bound / n_keys))
+        return fail(BPP_E_ARG, "n_keys x count too large for one launch");
+    if (caller)
+        for (size_t i = 0; i < count; i++)
+            if (caller[i] >= total) return fail(BPP_E_ARG, "caller position beyond total");
+    return guarded(Count{total, "total"}, [&]() -> int {
+        HIPCHK(hipSetDevice(v->ctx.device));
+        return dispatch(v->ctx.curve, [&](auto cv) -> int {
+            using C = decltype(cv);
+            using P = typename C::Fr;
+            using K = RecoverKeysImpl<C>;
+            typename VerifyImpl<C>::ClassView view;
+            view.c = cls;
+            view.ps = VerifyImpl<C>::class_shape(v, cls);
+            const uint32_t k = view.ps.s.k;
+            // not reachable today (make_shape: n, m <= 64, so k <= 12): kept beside check_classes of recover.hpp, which
+            // says the same of the public entries
+            if (k + 2 > RECOVER_GROUP) return fail(BPP_E_ARG, "mask recovery takes shapes with log2(n m) <= 14");
+            const size_t ne = coeff_elems(k), pairs = n_keys * total;
+            std::vector<uint32_t> rx(count * RX_WORDS, 0u);
+            for (size_t i = 0; i < count; i++) rx[i * RX_WORDS + RX_CALLER] = caller ? caller[i] : (uint32_t)i;
+            const std::vector<uint32_t> zeros(count, 0u);
+            DevBuf dsc, dch, drx, dst, dix, dco, dbad, dom, dos;
+            KeyUpload dk;
+            if (int rc = upload(dsc, scalars3, count * 96)) return rc;
+            if (int rc = upload(dch, challenges, count * (size_t)(3 + k) * 32)) return rc;
+            if (int rc = upload(drx, rx.data(), rx.size() * 4)) return rc;
+            if (int rc = upload(dst, status_in ? status_in : zeros.data(), count * 4)) return rc;
+            if (index)
+                if (int rc = upload(dix, index, total * 8)) return rc;
+            HIPCHK(dco.alloc(count * ne * K::CW * 4));
+            HIPCHK(dbad.alloc(count * 4));
+            view.first = 0;
+            view.count = count;
+            view.pts = nullptr;
+            view.sc3 = static_cast<uint64_t*>(dsc.p);
+            view.challenges = static_cast<uint64_t*>(dch.p);
+            if (n_keys) {
+                if (int rc = upload(dk.d, keys, n_keys * 32)) return rc;
+                if (int rc = upload(dom, out_masks, pairs * 32)) return rc;
+                if (int rc = upload(dos, out_status, pairs * 4)) return rc;
+            }
+            ScanKeysJob j = K::call_job(static_cast<const uint8_t*>(dk.d.p), n_keys, index_base,
+                                        static_cast<const uint64_t*>(dix.p), dom.u32(), dos.u32(), total);
+            K::bind_class(view, drx.u32(), dst.u32(), dbad.u32(), dco.u32(), j);
+            if (int rc = K::launch_coeffs(view, dco.u32(), dbad.u32(), nullptr)) return rc;
+            if (n_keys)
+                if (int rc = K::launch_scan_keys(j, nullptr)) return rc;
+            std::vector<uint32_t> co(count * ne * K::CW);
+            HIPCHK(hipMemcpy(co.data(), dco.p, co.size() * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(out_bad, dbad.p, count * 4, hipMemcpyDeviceToHost));
+            if (n_keys) {
+                HIPCHK(hipMemcpy(out_masks, dom.p, pairs * 32, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(out_status, dos.p, pairs * 4, hipMemcpyDeviceToHost));
+            }
+            uint32_t* oc = reinterpret_cast<uint32_t*>(out_coeffs);
+            for (size_t i = 0; i < count * ne; i++) {
+                Fe<P> f;
+                for (int t = 0; t < P::NL; t++) f.l[t] = co[i * K::CW + t];
+                fe_to_canonical(f, oc + i * 8);
+            }
+            return BPP_OK;
         });
     });
 }

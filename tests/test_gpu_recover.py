@@ -125,10 +125,13 @@ def _made(cname):
 
 
 def _recover_device(torch, bv, ms, triples, d_ch=None, **kw):
-    """-> [Gamma_i] through bpp_range_recover_masks_mixed_device; kw: blind_key, index_base, index (ints), blinding (ints)"""
+    """-> [Gamma_i] through bpp_range_recover_masks_mixed_device; kw: blind_key, index_base, index (ints), blinding (ints).
+    d_out_masks sits between two guards of 64 bytes, which must come back as they went in."""
     count = len(ms)
+    guard = 64
     d_sc = _dev(torch, O.scalars_to_wire([x for t in triples for x in t]))
-    d_out = torch.full((count * 32,), 0x5a, dtype=torch.uint8, device="cuda:0")
+    d_all = torch.full((count * 32 + 2 * guard,), 0x5a, dtype=torch.uint8, device="cuda:0")
+    d_out = d_all[guard:guard + count * 32]
     wsb = bv.recover_workspace_bytes(ms)
     assert wsb > 0
     d_ws = torch.empty(wsb, dtype=torch.uint8, device="cuda:0")
@@ -139,7 +142,9 @@ def _recover_device(torch, bv, ms, triples, d_ch=None, **kw):
                             index_base=kw.get("index_base", 0), d_index=d_ix.data_ptr() if d_ix is not None else 0,
                             d_blinding=d_bl.data_ptr() if d_bl is not None else 0)
     torch.cuda.synchronize()
-    return [int(x) for x in O.wire_to_scalars(d_out.cpu().numpy().view(np.uint64).reshape(count, 4))]
+    got = d_all.cpu().numpy()
+    assert (got[:guard] == 0x5a).all() and (got[guard + count * 32:] == 0x5a).all(), "a store outside d_out_masks"
+    return [int(x) for x in O.wire_to_scalars(got[guard:guard + count * 32].copy().view(np.uint64).reshape(count, 4))]
 
 
 def _derive(torch, bv, ms, recs):

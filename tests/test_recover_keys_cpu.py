@@ -16,6 +16,7 @@ import subprocess
 import pytest
 
 import recover_cases as RC
+import recover_rows as RR
 from test_host_arith_cpu import _build
 
 CID = {"bls12_381": 0, "secp256k1": 1, "ed25519": 2}
@@ -98,12 +99,8 @@ def test_edwards_scalar_field(harness, tmp_path):
         index = 9 + k
         blind = RC.O.blinding_from_key(KEYS[0], index, k, r)
         gammas = [rng.randrange(r) for _ in range(m)]
-        y, z, e, et = ch[0], ch[1], ch[2], ch[3:]
-        s = sum(pow(z, 2 * (j + 1) if m > 1 else 0, r) * g for j, g in enumerate(gammas))
-        alpha = blind[0] + pow(y, n * m + 1, r) * s
-        for t in range(k):
-            alpha += et[t] ** 2 * blind[5 + t] + pow(et[t], r - 3, r) * blind[5 + k + t]
-        dprime = (blind[4] + blind[3] * e + alpha * e * e) % r
+        z = ch[1]
+        dprime = RR.delta_prime(r, n, m, ch, blind, gammas)   # forward, in the prover's direction
         p = {"n": n, "m": m, "triple": [1, 2, dprime], "ch": ch}
         lines.append(_line(cname, p, index, KEYS))
         w = [_bigint(cname, p, key, index) for key in KEYS]
