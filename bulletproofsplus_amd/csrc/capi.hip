@@ -1,5 +1,6 @@
 // capi.hip -- the extern "C" boundary of libbpp_amd.so (declared in include/bpp_amd.h).  Thin: argument
-// checks, curve dispatch, then the per-curve implementations (impl_*.hpp, compiled in tu_*.hip).
+// checks, the entry shim, curve dispatch, then the per-curve implementations (impl_*.hpp, compiled in tu_*.hip) and the
+// literal single-call API (literal.hpp).  No buffer is staged here: the host forms live in the *Impl<C> structs as *_host.
 // No CPU fallback: every entry point launches HIP kernels on the context's device.
 #include "codec.hpp"
 #include "commit.hpp"
@@ -9,6 +10,7 @@
 #include "impl_prove_batch.hpp"
 #include "impl_verify.hpp"
 #include "impl_wip.hpp"
+#include "literal.hpp"
 #include "recover.hpp"
 #include "find.hpp"
 #include "recover_keys.hpp"
@@ -72,36 +74,6 @@ int stage_means(const hipEvent_t* ev, size_t passes, size_t per_pass, int stages
     for (int t = 0; t < stages; t++) out_ms[t] = passes ? out_ms[t] / (float)passes : 0.f;
     return BPP_OK;
 }
-// canonical (< group order) 32-byte little-endian scalar?
-bool scalar_is_canonical(int curve, const uint8_t* b) {
-    bool lt = false;
-    dispatch(curve, [&](auto cv) -> int {
-        using Fr = typename decltype(cv)::Fr;
-        uint32_t w[8];
-        for (int i = 0; i < 8; i++)
-            w[i] = (uint32_t)b[4 * i] | ((uint32_t)b[4 * i + 1] << 8) | ((uint32_t)b[4 * i + 2] << 16) | ((uint32_t)b[4 * i + 3] << 24);
-        lt = words_lt_mod<Fr>(w);
-        return 0;
-    });
-    return lt;
-}
-// The host-pointer verify calls: two host inputs copied to device buffers, the verdicts of `count` proofs and a workspace
-// of wsb bytes allocated, run(d_in0, d_in1, d_ok, d_ws) for the device path, then the verdicts copied to out_ok.
-template <class F>
-int verify_staged(const void* in0, size_t bytes0, const void* in1, size_t bytes1, size_t count, size_t wsb, uint32_t* out_ok,
-                  F&& run) {
-    DevBuf d0, d1, dok, dws;
-    HIPCHK(d0.alloc(bytes0));
-    HIPCHK(d1.alloc(bytes1));
-    HIPCHK(dok.alloc(count * 4));
-    HIPCHK(dws.alloc(wsb));
-    HIPCHK(hipMemcpy(d0.p, in0, bytes0, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d1.p, in1, bytes1, hipMemcpyHostToDevice));
-    const int rc = run(d0.p, d1.p, dok.u32(), dws.p);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(out_ok, dok.p, count * 4, hipMemcpyDeviceToHost));
-    return BPP_OK;
-}
 }  // namespace
 
 extern "C" const char* bpp_last_error(void) { return last_error(); }
@@ -120,48 +92,10 @@ extern "C" int bpp_init(int curve_id, int device, bpp_ctx** out_ctx) {
         });
     });
 }
-// ---- the literal single-call API, second call onwards: a small-table verifier per public key -------------------
-// RangeProof::verify (src/range/mod.rs:57-78) takes the public key with every call and the reference pays the whole
-// naive MulVec each time.  bpp_range_verify does the same on the FIRST call with a key (the data-parallel naive MulVec,
-// no setup); a key that comes back gets a verifier with narrow window tables (c = 8: built in milliseconds, < 1 GB at
-// n m = 1024) that later calls with the same key run through -- the batch verifier's pass at count = 1.  Entries are
-// found by a 64-bit hash of (curve, n, m, g, h, G, H) and CONFIRMED by comparing the key bytes, so a hash collision can
-// never make a proof verify against another key's generators.  At most VCACHE_MAX verifiers, least recently used out.
-namespace {
-constexpr size_t VCACHE_MAX = 4;
-constexpr int VCACHE_WINDOW = 8;
-struct VerifyCacheEntry {
-    uint64_t hash = 0;
-    size_t n = 0, m = 0;
-    std::vector<uint64_t> key;              // gh | G | H as handed in
-    std::unique_ptr<bpp_verifier> v;        // null: seen once, tables not built yet
-    DevBuf pts, sc, ok, ws;                 // count = 1 buffers of the pass
-    uint64_t stamp = 0;
-};
-struct VerifyCache {
-    std::vector<std::unique_ptr<VerifyCacheEntry>> e;
-    uint64_t clock = 0;
-};
-inline uint64_t key_hash(int curve, size_t n, size_t m, const uint64_t* gh, const uint64_t* G, const uint64_t* H, size_t pw) {
-    uint64_t h = 0x9E3779B97F4A7C15ull ^ ((uint64_t)curve << 48) ^ ((uint64_t)n << 24) ^ (uint64_t)m;
-    auto mix = [&](const uint64_t* p, size_t words) {
-        for (size_t i = 0; i < words; i++) {
-            h ^= p[i];
-            h *= 0xff51afd7ed558ccdull;
-            h ^= h >> 29;
-        }
-    };
-    mix(gh, 2 * pw);
-    mix(G, n * m * pw);
-    mix(H, n * m * pw);
-    return h;
-}
-}  // namespace
-
 extern "C" void bpp_destroy(bpp_ctx* ctx) {
     if (!ctx) return;
     for (hipEvent_t e : ctx->msm_events) (void)hipEventDestroy(e);
-    delete static_cast<VerifyCache*>(ctx->verify_cache);
+    verify_cache_release(ctx);
     delete ctx;
 }
 
@@ -267,81 +201,12 @@ extern "C" int bpp_commit(bpp_ctx* ctx, const uint64_t* gh, uint64_t v, const ui
     return on_ctx(*ctx, [&](auto cv) -> int { return MsmImpl<decltype(cv)>::commit(gh, v, gamma, out); });
 }
 
-// The cached engine of a public key, or null when the call has to take the table-free path: first sight of the key (it
-// is remembered), a shape the engine does not take, the cache switched off, or no memory for the tables.
-static VerifyCacheEntry* engine_for_key(bpp_ctx* ctx, const uint64_t* gh, const uint64_t* G, const uint64_t* H, size_t n,
-                                        size_t m) {
-    const size_t mn = n * m;
-    if (n == 0 || m == 0 || n > VS_MAXN || m > VS_MAXM || (mn & (mn - 1)) || ctx->verify_cache_off) return nullptr;
-    const size_t pw = (size_t)bpp_point_words(ctx->curve);
-    if (!ctx->verify_cache) ctx->verify_cache = new VerifyCache();
-    VerifyCache& vc = *static_cast<VerifyCache*>(ctx->verify_cache);
-    const uint64_t h = key_hash(ctx->curve, n, m, gh, G, H, pw);
-    const size_t kw = (2 + 2 * mn) * pw;
-    VerifyCacheEntry* hit = nullptr;
-    for (const auto& x : vc.e)
-        if (x->hash == h && x->n == n && x->m == m && std::memcmp(x->key.data(), gh, 2 * pw * 8) == 0 &&
-            std::memcmp(x->key.data() + 2 * pw, G, mn * pw * 8) == 0 &&
-            std::memcmp(x->key.data() + (2 + mn) * pw, H, mn * pw * 8) == 0)
-            hit = x.get();
-    if (!hit) {   // first sight of this key: remember it
-        auto x = std::make_unique<VerifyCacheEntry>();
-        x->hash = h;
-        x->n = n;
-        x->m = m;
-        x->key.resize(kw);
-        std::memcpy(x->key.data(), gh, 2 * pw * 8);
-        std::memcpy(x->key.data() + 2 * pw, G, mn * pw * 8);
-        std::memcpy(x->key.data() + (2 + mn) * pw, H, mn * pw * 8);
-        x->stamp = ++vc.clock;
-        if (vc.e.size() >= VCACHE_MAX)
-            vc.e.erase(std::min_element(vc.e.begin(), vc.e.end(), [](const auto& a, const auto& b) { return a->stamp < b->stamp; }));
-        vc.e.push_back(std::move(x));
-        return nullptr;
-    }
-    hit->stamp = ++vc.clock;
-    if (!hit->v) {   // the key came back: build its tables (an invalid generator or no memory: stay with the table-free path)
-        bpp_verifier* v = nullptr;
-        if (bpp_verifier_create(ctx, gh, G, H, n, m, VCACHE_WINDOW, &v)) return nullptr;
-        // the literal call takes wire points of unknown origin: on BLS12-381 a point outside G1 must not reach the
-        // endomorphism evaluation, which is not the full-curve sum there (include/bpp_amd.h, bpp_verifier_set_subgroup_check)
-        v->check_subgroup = ctx->curve == BPP_BLS12_381_G1;
-        const size_t wsb = bpp_verifier_workspace_bytes(v, 1);
-        std::unique_ptr<bpp_verifier> owned(v);
-        if (hit->pts.alloc(v->s.NV * pw * 8) != hipSuccess || hit->sc.alloc(96) != hipSuccess ||
-            hit->ok.alloc(4) != hipSuccess || hit->ws.alloc(wsb) != hipSuccess)
-            return nullptr;
-        hit->v = std::move(owned);
-    }
-    return hit;
-}
-
 extern "C" int bpp_range_verify(bpp_ctx* ctx, const uint64_t* gh, const uint64_t* G, const uint64_t* H, size_t n,
                                 size_t m, const uint64_t* proof_points, size_t k, const uint64_t* proof_scalars,
                                 const uint64_t* V) {
     if (!ctx || !gh || !G || !H || !proof_points || !proof_scalars || !V) return fail(BPP_E_ARG, "null argument");
     return on_ctx(*ctx, [&](auto cv) -> int {
-        auto naive = [&] { return MsmImpl<decltype(cv)>::range_verify_single(gh, G, H, n, m, proof_points, k, proof_scalars, V); };
-        VerifyCacheEntry* hit = engine_for_key(ctx, gh, G, H, n, m);
-        if (!hit) return naive();
-        const size_t pw = (size_t)bpp_point_words(ctx->curve);
-        bpp_verifier* v = hit->v.get();
-        if (k != v->s.k) return BPP_VERIFICATION_ERROR;   // wip.rs:335-337
-        // record [A, wip.A, wip.B, L.., R.., V..]
-        HIPCHK(hipMemcpyAsync(hit->pts.p, proof_points, (3 + 2 * k) * pw * 8, hipMemcpyHostToDevice, nullptr));
-        HIPCHK(hipMemcpyAsync(static_cast<uint8_t*>(hit->pts.p) + (3 + 2 * k) * pw * 8, V, m * pw * 8, hipMemcpyHostToDevice, nullptr));
-        HIPCHK(hipMemcpyAsync(hit->sc.p, proof_scalars, 96, hipMemcpyHostToDevice, nullptr));
-        int rc = bpp_verifier_run(v, static_cast<const uint64_t*>(hit->pts.p), static_cast<const uint64_t*>(hit->sc.p), 1, nullptr,
-                                  hit->ok.u32(), hit->ws.p, hit->ws.bytes, nullptr, nullptr, nullptr);
-        if (rc) return rc;
-        uint32_t verdict = 1;
-        HIPCHK(hipMemcpy(&verdict, hit->ok.p, 4, hipMemcpyDeviceToHost));
-        // BLS12-381: an accept of the cached pass is exact (its points passed the membership test); a reject may be a curve
-        // point outside G1 whose full-curve contribution cancels, so the table-free full-curve path decides it, as it
-        // decides every call of the reference.  secp256k1 (cofactor 1) and edwards25519 (the same E[4] identity test as
-        // the naive path) need no second opinion.
-        if (verdict && ctx->curve == BPP_BLS12_381_G1) return naive();
-        return verdict ? BPP_VERIFICATION_ERROR : BPP_OK;
+        return literal_verify<decltype(cv)>(ctx, gh, G, H, n, m, proof_points, k, proof_scalars, V);
     });
 }
 
@@ -349,10 +214,7 @@ extern "C" int bpp_set_verify_cache(bpp_ctx* ctx, int on) {
     if (!ctx) return fail(BPP_E_ARG, "null argument");
     return guarded([&] {
         ctx->verify_cache_off = on == 0;
-        if (!on) {
-            delete static_cast<VerifyCache*>(ctx->verify_cache);
-            ctx->verify_cache = nullptr;
-        }
+        if (!on) verify_cache_release(ctx);
         return BPP_OK;
     });
 }
@@ -363,32 +225,7 @@ extern "C" int bpp_range_prove(bpp_ctx* ctx, const uint64_t* gh, const uint64_t*
     if (!ctx || !gh || !G || !H || !v || !gamma || !V || !out_points || !out_scalars)
         return fail(BPP_E_ARG, "null argument");
     return on_ctx(*ctx, {m, "m"}, [&](auto cv) -> int {
-        // a key that has been seen before proves through its cached engine: the batched prover at count = 1 (every L, R,
-        // A, B one MulVec over the window tables, bit-identical output) instead of folding the generator vectors round by
-        // round
-        if (VerifyCacheEntry* hit = engine_for_key(ctx, gh, G, H, n, m)) {
-            // the batched prover forms the commitments from (v, gamma) itself; the reference's prove reads them from the
-            // prover object (range/mod.rs:330-343) -- if the caller's V are not those, only the fold-based path
-            // reproduces it
-            const size_t pw = (size_t)bpp_point_words(ctx->curve);
-            std::vector<uint64_t> myV(m * pw), pts((3 + 2 * hit->v->s.k) * pw), sc(12);
-            // ... first with the reference's own commitments, new(v as i32) g + gamma h (range/prover.rs:37), then with the
-            // untruncated ones a caller with an amount of 2^31 or more has to bring (BPP_PROVE_AMOUNT64): in literal mode the
-            // proof is a function of (v, gamma, V), so whichever form matches the caller's V is the fold-based path's output
-            for (int amount64 = 0; amount64 < 2; amount64++) {
-                const int rc = ProveBatchImpl<decltype(cv)>::prove_batch(hit->v.get(), v, gamma, 1, pts.data(), sc.data(), myV.data(),
-                                                                     false, nullptr, 0, amount64 != 0);
-                if (rc == BPP_OK && std::memcmp(myV.data(), V, m * pw * 8) == 0) {
-                    std::memcpy(out_points, pts.data(), pts.size() * 8);
-                    std::memcpy(out_scalars, sc.data(), 96);
-                    return BPP_OK;
-                }
-                if (rc != BPP_OK) break;
-            }
-        }
-        std::string err;
-        const int rc = ProveImpl<decltype(cv)>::range_prove(gh, G, H, n, m, v, gamma, V, out_points, out_scalars, err);
-        return rc ? fail(rc, err) : BPP_OK;
+        return literal_prove<decltype(cv)>(ctx, gh, G, H, n, m, v, gamma, V, out_points, out_scalars);
     });
 }
 
@@ -742,13 +579,8 @@ extern "C" int bpp_range_verify_batch(bpp_verifier* v, const uint64_t* points, c
                                       uint32_t* out_ok) {
     if (!v || !points || !scalars || !out_ok) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
-    return on_device(v->ctx.device, {count, "count"}, [&] {
-        const size_t pw = (size_t)bpp_point_words(v->ctx.curve) * 8, wsb = bpp_verifier_workspace_bytes(v, count);
-        return verify_staged(points, count * v->s.NV * pw, scalars, count * 3 * 32, count, wsb, out_ok,
-                             [&](void* dp, void* ds, uint32_t* dok, void* dws) {
-                                 return bpp_verifier_run(v, static_cast<const uint64_t*>(dp), static_cast<const uint64_t*>(ds),
-                                                         count, nullptr, dok, dws, wsb, nullptr, nullptr, nullptr);
-                             });
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::verify_batch_host(v, points, scalars, count, out_ok);
     });
 }
 
@@ -789,23 +621,8 @@ extern "C" int bpp_range_verify_batch_mixed(bpp_verifier* v, const uint64_t* poi
     if (!v) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
     if (!points || !scalars || !m_of || !out_ok) return fail(BPP_E_ARG, "null argument");
-    return on_device(v->ctx.device, {count, "count"}, [&]() -> int {
-        const size_t wsb = bpp_verifier_mixed_workspace_bytes(v, m_of, count);
-        if (!wsb) {   // an m_i the verifier does not take: the plan names the proof
-            MixedPlan p;
-            const int rc = mixed_plan(v->s, m_of, count, false, p);
-            return rc ? rc : fail(BPP_E_ARG, "mixed batch rejected");
-        }
-        const size_t pw = (size_t)bpp_point_words(v->ctx.curve) * 8;
-        size_t npts = 0;
-        const uint32_t logn = v->s.k - (uint32_t)__builtin_ctz(v->s.m);
-        for (size_t i = 0; i < count; i++) npts += 3 + 2 * (logn + (uint32_t)__builtin_ctz(m_of[i])) + m_of[i];
-        return verify_staged(points, npts * pw, scalars, count * 3 * 32, count, wsb, out_ok,
-                             [&](void* dp, void* ds, uint32_t* dok, void* dws) {
-                                 return bpp_verifier_run_mixed(v, static_cast<const uint64_t*>(dp),
-                                                               static_cast<const uint64_t*>(ds), m_of, count, nullptr, dok,
-                                                               dws, wsb, nullptr, nullptr);
-                             });
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::verify_batch_mixed_host(v, points, scalars, m_of, count, out_ok);
     });
 }
 
@@ -844,47 +661,12 @@ extern "C" int bpp_range_verify_batch_compressed(bpp_verifier* v, const uint8_t*
     if (count == 0) return BPP_OK;
     const size_t cb = bpp_point_compressed_bytes(v->ctx.curve);
     if (cb == 0) return fail(BPP_E_ARG, "compressed encoding is not offered for this curve");
-    return on_device(v->ctx.device, {count, "count"}, [&]() -> int {
-        const size_t pw = (size_t)bpp_point_words(v->ctx.curve) * 8, wsb = bpp_verifier_workspace_bytes(v, count);
-        const size_t npts = count * v->s.NV;
-        std::vector<uint32_t> bad(npts);
-        const int rc = verify_staged(records, npts * cb, scalars, count * 3 * 32, count, wsb, out_ok,
-                                     [&](void* db, void* ds, uint32_t* dok, void* dws) -> int {
-            DevBuf dp, dk;
-            HIPCHK(dp.alloc(npts * pw));
-            HIPCHK(dk.alloc(npts * 4));
-            // the one wire entry point for points of unknown origin besides the container: reject what is outside the
-            // prime-order group too (the verifier's GLV evaluation equals s * P only there, include/bpp_amd.h)
-            int rc = bpp_points_decompress_device(&v->ctx, db, npts, static_cast<uint64_t*>(dp.p), dk.u32(), 1, nullptr);
-            if (rc) return rc;
-            rc = bpp_verifier_run(v, static_cast<const uint64_t*>(dp.p), static_cast<const uint64_t*>(ds), count, nullptr, dok,
-                                  dws, wsb, nullptr, nullptr, nullptr);
-            if (rc) return rc;
-            HIPCHK(hipMemcpy(bad.data(), dk.p, npts * 4, hipMemcpyDeviceToHost));
-            return BPP_OK;
-        });
-        if (rc) return rc;
-        for (size_t i = 0; i < npts; i++)
-            if (bad[i]) out_ok[i / v->s.NV] = BPP_FORMAT_ERROR;   // a malformed encoding / a point outside the group: ProofError::FormatError
-        // ... and so does a non-canonical scalar (r', s' or delta' >= the group order): a serialized proof has one encoding
-        // (little-endian host: the u64 limbs are the bytes)
-        for (size_t i = 0; i < count * 3; i++)
-            if (!scalar_is_canonical(v->ctx.curve, reinterpret_cast<const uint8_t*>(scalars + i * 4)))
-                out_ok[i / 3] = BPP_FORMAT_ERROR;
-        return BPP_OK;
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::verify_batch_compressed_host(v, records, scalars, count, out_ok);
     });
 }
 
 // ---- serialized proofs (the container; see include/bpp_amd.h) -----------------------------------------------------
-namespace {
-constexpr size_t BPP_HDR = 12;   // "BPP+" | version | curve | n | m | k | 3 reserved zero bytes
-inline uint32_t log2_exact(size_t x) {
-    uint32_t k = 0;
-    while (((size_t)1 << k) < x) k++;
-    return k;
-}
-}  // namespace
-
 extern "C" size_t bpp_point_uncompressed_bytes(int curve_id) {
     switch (curve_id) {
         case BPP_BLS12_381_G1: return 96;
@@ -899,30 +681,10 @@ extern "C" size_t bpp_proof_bytes_version(int curve_id, size_t n, size_t m, int 
     const size_t cb = container_point_size(curve_id, version);
     const size_t mn = n * m;
     if (cb == 0 || mn == 0 || (mn & (mn - 1))) return 0;
-    return BPP_HDR + (3 + 2 * (size_t)log2_exact(mn)) * cb + 96;
+    return CONTAINER_HDR + (3 + 2 * (size_t)log2_exact(mn)) * cb + 96;
 }
 extern "C" size_t bpp_proof_bytes(int curve_id, size_t n, size_t m) { return bpp_proof_bytes_version(curve_id, n, m, 1); }
 
-// wire points -> uncompressed bytes (host: a change of byte order)
-static void points_to_uncompressed(int curve, const uint64_t* points, size_t n, uint8_t* out) {
-    const size_t pw = (size_t)bpp_point_words(curve), L = (pw - 1) / 2, ub = bpp_point_uncompressed_bytes(curve);
-    const size_t off = curve == BPP_SECP256K1 ? 1 : 0, fb = L * 8;
-    for (size_t i = 0; i < n; i++) {
-        const uint64_t* w = points + i * pw;
-        uint8_t* o = out + i * ub;
-        std::memset(o, 0, ub);
-        if (w[2 * L]) {
-            if (curve == BPP_BLS12_381_G1) o[0] = 0x40;
-            continue;
-        }
-        if (curve == BPP_SECP256K1) o[0] = 0x04;
-        for (size_t b = 0; b < fb; b++) {
-            const size_t k = fb - 1 - b;
-            o[off + b] = (uint8_t)(w[k >> 3] >> (8 * (k & 7)));
-            o[off + fb + b] = (uint8_t)(w[L + (k >> 3)] >> (8 * (k & 7)));
-        }
-    }
-}
 extern "C" int bpp_points_uncompressed(bpp_ctx* ctx, const uint64_t* points, size_t n, uint8_t* out) {
     if (!ctx || (n && (!points || !out))) return fail(BPP_E_ARG, "null argument");
     if (bpp_point_uncompressed_bytes(ctx->curve) == 0) return fail(BPP_E_ARG, "no uncompressed form for this curve");
@@ -938,25 +700,8 @@ extern "C" int bpp_proofs_encode_version(bpp_ctx* ctx, size_t n, size_t m, int v
     const size_t pb = bpp_proof_bytes_version(ctx->curve, n, m, version);
     if (pb == 0 || n > 255 || m > 255) return fail(BPP_E_ARG, "n*m must be a power of two (n, m <= 255); version 1 or 2");
     if (count == 0) return BPP_OK;
-    return guarded({count, "count"}, [&] {
-        const size_t cb = container_point_size(ctx->curve, version);
-        const uint32_t k = log2_exact(n * m);
-        const size_t npp = 3 + 2 * (size_t)k;
-        std::vector<uint8_t> comp(count * npp * cb);
-        if (version == 2) {
-            points_to_uncompressed(ctx->curve, points, count * npp, comp.data());
-        } else {
-            int rc = bpp_points_compress(ctx, points, count * npp, comp.data());
-            if (rc) return rc;
-        }
-        for (size_t p = 0; p < count; p++) {
-            uint8_t* o = out + p * pb;
-            const uint8_t hdr[BPP_HDR] = {'B', 'P', 'P', '+', (uint8_t)version, (uint8_t)ctx->curve, (uint8_t)n, (uint8_t)m, (uint8_t)k, 0, 0, 0};
-            std::memcpy(o, hdr, BPP_HDR);
-            std::memcpy(o + BPP_HDR, comp.data() + p * npp * cb, npp * cb);
-            std::memcpy(o + BPP_HDR + npp * cb, scalars + p * 12, 96);   // little-endian host: the u64 limbs are the bytes
-        }
-        return BPP_OK;
+    return on_ctx(*ctx, {count, "count"}, [&](auto cv) -> int {
+        return CodecImpl<decltype(cv)>::encode_host(n, m, version, points, scalars, count, out);
     });
 }
 
@@ -972,40 +717,7 @@ extern "C" int bpp_proofs_decode(bpp_ctx* ctx, size_t n, size_t m, const uint8_t
     const size_t pb = bpp_proof_bytes(ctx->curve, n, m);
     if (pb == 0 || n > 255 || m > 255) return fail(BPP_E_ARG, "n*m must be a power of two (n, m <= 255)");
     return on_ctx(*ctx, {count, "count"}, [&](auto cv) -> int {
-        const size_t cb = bpp_point_compressed_bytes(ctx->curve);
-        const uint32_t k = log2_exact(n * m);
-        const size_t npp = 3 + 2 * (size_t)k;
-        const size_t pw = (size_t)bpp_point_words(ctx->curve) * 8;
-        // status[p] = 0 / BPP_FORMAT_ERROR; the caller's buffers are written once everything has succeeded
-        std::vector<uint32_t> status(count, 0);
-        std::vector<uint64_t> scalars(count * 12, 0);
-        std::vector<uint8_t> comp(count * npp * cb);
-        for (size_t p = 0; p < count; p++) {
-            const uint8_t* s = in + p * pb;
-            const uint8_t hdr[BPP_HDR] = {'B', 'P', 'P', '+', 1, (uint8_t)ctx->curve, (uint8_t)n, (uint8_t)m, (uint8_t)k, 0, 0, 0};
-            if (std::memcmp(s, hdr, BPP_HDR) != 0) status[p] = BPP_FORMAT_ERROR;   // magic, version, curve, shape, reserved
-            std::memcpy(comp.data() + p * npp * cb, s + BPP_HDR, npp * cb);
-            const uint8_t* sc = s + BPP_HDR + npp * cb;
-            for (int t = 0; t < 3; t++)
-                if (!scalar_is_canonical(ctx->curve, sc + 32 * t)) status[p] = BPP_FORMAT_ERROR;   // one encoding per scalar
-            std::memcpy(scalars.data() + p * 12, sc, 96);
-        }
-        DevBuf db, dk, dp;
-        HIPCHK(db.alloc(count * npp * cb));
-        HIPCHK(dk.alloc(count * npp * 4));
-        HIPCHK(dp.alloc(count * npp * pw));
-        HIPCHK(hipMemcpy(db.p, comp.data(), comp.size(), hipMemcpyHostToDevice));
-        const int rc = CodecImpl<decltype(cv)>::decompress_device(static_cast<const uint8_t*>(db.p), count * npp,
-                                                                  static_cast<uint64_t*>(dp.p), dk.u32(), nullptr, true);
-        if (rc) return rc;
-        std::vector<uint32_t> bad(count * npp);
-        HIPCHK(hipMemcpy(bad.data(), dk.p, bad.size() * 4, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < bad.size(); i++)
-            if (bad[i]) status[i / npp] = BPP_FORMAT_ERROR;   // malformed encoding or a point outside the prime-order group
-        HIPCHK(hipMemcpy(out_points, dp.p, dp.bytes, hipMemcpyDeviceToHost));
-        std::memcpy(out_scalars, scalars.data(), scalars.size() * 8);
-        std::memcpy(out_status, status.data(), status.size() * 4);
-        return BPP_OK;
+        return CodecImpl<decltype(cv)>::decode_host(n, m, in, count, out_points, out_scalars, out_status);
     });
 }
 
@@ -1062,17 +774,10 @@ extern "C" int bpp_range_verify_batch_serialized(bpp_verifier* v, const uint8_t*
     if (!v || !proofs || !commitments || !out_ok) return fail(BPP_E_ARG, "null argument");
     if (count == 0) return BPP_OK;
     const VerifyShape& s = v->s;
-    const int version = (flags & BPP_SER_UNCOMPRESSED) ? 2 : 1;
-    const size_t pb = bpp_proof_bytes_version(v->ctx.curve, s.n, s.m, version);
-    const size_t cb = container_point_size(v->ctx.curve, version);
-    if (pb == 0 || s.n > 255 || s.m > 255) return fail(BPP_E_ARG, "n*m must be a power of two (n, m <= 255)");
-    return on_device(v->ctx.device, {count, "count"}, [&] {
-        const size_t wsb = bpp_verifier_serialized_workspace_bytes(v, count);
-        return verify_staged(proofs, count * pb, commitments, count * s.m * cb, count, wsb, out_ok,
-                             [&](void* dpr, void* dcm, uint32_t* dok, void* dws) {
-                                 return bpp_range_verify_batch_serialized_device(v, dpr, dcm, count, flags, dok, dws, wsb,
-                                                                                 nullptr);
-                             });
+    if (bpp_proof_bytes_version(v->ctx.curve, s.n, s.m, (flags & BPP_SER_UNCOMPRESSED) ? 2 : 1) == 0 || s.n > 255 || s.m > 255)
+        return fail(BPP_E_ARG, "n*m must be a power of two (n, m <= 255)");
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::verify_batch_serialized_host(v, proofs, commitments, count, flags, out_ok);
     });
 }
 
@@ -1125,23 +830,8 @@ extern "C" int bpp_range_verify_batch_serialized_mixed(bpp_verifier* v, const ui
     const int version = (flags & BPP_SER_UNCOMPRESSED) ? 2 : 1;
     const size_t cb = container_point_size(v->ctx.curve, version);
     if (int rc = container_version_ok(cb)) return rc;
-    return on_device(v->ctx.device, {count, "count"}, [&]() -> int {
-        const size_t wsb = bpp_verifier_serialized_mixed_workspace_bytes(v, m_of, count);
-        if (!wsb) {   // an m_i the verifier does not take: the plan names the proof
-            MixedPlan p;
-            const int rc = mixed_plan_serialized(v->s, m_of, count, cb, false, p);
-            return rc ? rc : fail(BPP_E_ARG, "serialized mixed batch rejected");
-        }
-        size_t pbytes = 0, cbytes = 0;
-        for (size_t i = 0; i < count; i++) {
-            pbytes += bpp_proof_bytes_version(v->ctx.curve, v->s.n, m_of[i], version);
-            cbytes += m_of[i] * cb;
-        }
-        return verify_staged(proofs, pbytes, commitments, cbytes, count, wsb, out_ok,
-                             [&](void* dpr, void* dcm, uint32_t* dok, void* dws) {
-                                 return bpp_range_verify_batch_serialized_mixed_device(v, dpr, dcm, m_of, count, flags, dok,
-                                                                                       dws, wsb, nullptr);
-                             });
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::verify_batch_serialized_mixed_host(v, proofs, commitments, m_of, count, flags, out_ok);
     });
 }
 
@@ -1731,26 +1421,5 @@ extern "C" int bpp_pool_verify_combined(void* pool, const uint64_t* points, cons
     if (!points || !scalars) return fail(BPP_E_ARG, "null argument");
     return guarded({count, "count"}, [&] {
         return pool_verify_combined(static_cast<bpp_pool*>(pool), points, scalars, count, weight_key, index_base, out_ok);
-    });
-}
-
-// ---- device-side unit-test hooks (tests/ check the device field / group primitives against a CPU checker) --
-// (their raw-image siblings bpp_debug_field_raw_op, bpp_debug_madd_lazy_raw and bpp_debug_glv_op live in tu_debug.hip,
-// a translation unit of their own)
-// field: 0 = base field, 1 = scalar field; op: 0 mul, 1 add, 2 sub, 3 inv, 4 sqr, 5 neg
-// a, b, out: n elements of N 32-bit words (N = 12 for BLS12-381 Fp, else 8), host pointers
-extern "C" int bpp_debug_field_op(bpp_ctx* ctx, int field, int op, const uint32_t* a, const uint32_t* b, size_t n,
-                                  uint32_t* out) {
-    if (!ctx || !a || !b || !out) return fail(BPP_E_ARG, "null argument");
-    return on_ctx(*ctx, {n, "n"}, [&](auto cv) -> int {
-        return MsmImpl<decltype(cv)>::debug_field_op(field, op, a, b, n, out);
-    });
-}
-// op: 0 add, 1 madd, 2 dbl(a), 3 madd(2a, b), 4 add(2a, 2b), 5 xyzz: inf + a + b + a; wire points, host pointers
-extern "C" int bpp_debug_point_op(bpp_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, size_t n,
-                                  uint64_t* out) {
-    if (!ctx || !a || !b || !out) return fail(BPP_E_ARG, "null argument");
-    return on_ctx(*ctx, {n, "n"}, [&](auto cv) -> int {
-        return MsmImpl<decltype(cv)>::debug_point_op(op, a, b, n, out);
     });
 }

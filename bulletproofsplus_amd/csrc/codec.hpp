@@ -414,6 +414,27 @@ __global__ void __launch_bounds__(256) k_container_status(const uint32_t* __rest
     if (p < count && status[p]) ok[p] = BPP_FORMAT_ERROR;
 }
 
+// wire points -> uncompressed bytes (host: a change of byte order)
+inline void points_to_uncompressed(int curve, const uint64_t* points, size_t n, uint8_t* out) {
+    const size_t pw = (size_t)bpp_point_words(curve), L = (pw - 1) / 2, ub = bpp_point_uncompressed_bytes(curve);
+    const size_t off = curve == BPP_SECP256K1 ? 1 : 0, fb = L * 8;
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t* w = points + i * pw;
+        uint8_t* o = out + i * ub;
+        std::memset(o, 0, ub);
+        if (w[2 * L]) {
+            if (curve == BPP_BLS12_381_G1) o[0] = 0x40;
+            continue;
+        }
+        if (curve == BPP_SECP256K1) o[0] = 0x04;
+        for (size_t b = 0; b < fb; b++) {
+            const size_t k = fb - 1 - b;
+            o[off + b] = (uint8_t)(w[k >> 3] >> (8 * (k & 7)));
+            o[off + fb + b] = (uint8_t)(w[L + (k >> 3)] >> (8 * (k & 7)));
+        }
+    }
+}
+
 template <class C>
 struct CodecImpl {
     static constexpr int N = C::Fp::N;
@@ -426,6 +447,14 @@ struct CodecImpl {
                                  bool check_subgroup = false);
 
     static int decompress(const uint8_t* in, size_t n, uint64_t* out_points, uint32_t* out_ok);
+
+    // the container (include/bpp_amd.h "serialized proofs") from and to host buffers: bpp_proofs_encode_version and
+    // bpp_proofs_decode past their argument checks
+    static int encode_host(size_t n, size_t m, int version, const uint64_t* points, const uint64_t* scalars, size_t count,
+                           uint8_t* out);
+    // out_status[p] = 0 / BPP_FORMAT_ERROR; the caller's buffers are written once everything has succeeded
+    static int decode_host(size_t n, size_t m, const uint8_t* in, size_t count, uint64_t* out_points, uint64_t* out_scalars,
+                           uint32_t* out_status);
 };
 
 // ---- definitions: compiled only by the translation unit that instantiates the struct (tu_*.hip defines
@@ -440,13 +469,11 @@ int CodecImpl<C>::compress(const uint64_t* points, size_t n, uint8_t* out) {
         if (n == 0) return BPP_OK;
         constexpr int CB = compressed_bytes<C>();
         DevBuf dw, db;
-        HIPCHK(dw.alloc(n * WW * 4));
+        HIPCHK(dw.upload(points, n * WW * 4));
         HIPCHK(db.alloc(n * CB));
-        HIPCHK(hipMemcpy(dw.p, points, n * WW * 4, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_points_compress<C>, dim3(cdiv(n, 128)), dim3(128), 0, nullptr, dw.u32(),
-                           static_cast<uint8_t*>(db.p), n);
+        hipLaunchKernelGGL(k_points_compress<C>, dim3(cdiv(n, 128)), dim3(128), 0, nullptr, dw.u32(), db.u8(), n);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy(out, db.p, n * CB, hipMemcpyDeviceToHost));
+        HIPCHK(db.download(out, n * CB));
         return BPP_OK;
     }
 }
@@ -473,16 +500,67 @@ int CodecImpl<C>::decompress(const uint8_t* in, size_t n, uint64_t* out_points, 
         if (n == 0) return BPP_OK;
         constexpr int CB = compressed_bytes<C>();
         DevBuf dw, db, dk;
+        HIPCHK(db.upload(in, n * CB));
         HIPCHK(dw.alloc(n * WW * 4));
-        HIPCHK(db.alloc(n * CB));
         HIPCHK(dk.alloc(n * 4));
-        HIPCHK(hipMemcpy(db.p, in, n * CB, hipMemcpyHostToDevice));
-        int rc = decompress_device(static_cast<const uint8_t*>(db.p), n, static_cast<uint64_t*>(dw.p), dk.u32(), nullptr);
-        if (rc) return rc;
-        HIPCHK(hipMemcpy(out_points, dw.p, n * WW * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(out_ok, dk.p, n * 4, hipMemcpyDeviceToHost));
+        BPP_TRY(decompress_device(db.u8(), n, dw.u64(), dk.u32(), nullptr));
+        HIPCHK(dw.download(out_points, n * WW * 4));
+        HIPCHK(dk.download(out_ok, n * 4));
         return BPP_OK;
     }
+}
+
+template <class C>
+int CodecImpl<C>::encode_host(size_t n, size_t m, int version, const uint64_t* points, const uint64_t* scalars, size_t count,
+                              uint8_t* out) {
+    const size_t cb = (size_t)container_point_bytes<C>((uint32_t)version);
+    const uint32_t k = log2_exact(n * m);
+    const size_t npp = 3 + 2 * (size_t)k, pb = container_bytes<C>(k, (uint32_t)version);
+    std::vector<uint8_t> comp(count * npp * cb);
+    if (version == 2) points_to_uncompressed(C::ID, points, count * npp, comp.data());
+    else BPP_TRY(compress(points, count * npp, comp.data()));
+    for (size_t p = 0; p < count; p++) {
+        uint8_t* o = out + p * pb;
+        const uint8_t hdr[CONTAINER_HDR] = {'B', 'P', 'P', '+', (uint8_t)version, (uint8_t)C::ID, (uint8_t)n, (uint8_t)m, (uint8_t)k, 0, 0, 0};
+        std::memcpy(o, hdr, CONTAINER_HDR);
+        std::memcpy(o + CONTAINER_HDR, comp.data() + p * npp * cb, npp * cb);
+        std::memcpy(o + CONTAINER_HDR + npp * cb, scalars + p * 12, 96);   // little-endian host: the u64 limbs are the bytes
+    }
+    return BPP_OK;
+}
+
+template <class C>
+int CodecImpl<C>::decode_host(size_t n, size_t m, const uint8_t* in, size_t count, uint64_t* out_points, uint64_t* out_scalars,
+                              uint32_t* out_status) {
+    constexpr size_t cb = compressed_bytes<C>();
+    const uint32_t k = log2_exact(n * m);
+    const size_t npp = 3 + 2 * (size_t)k, pb = container_bytes<C>(k);
+    std::vector<uint32_t> status(count, 0);
+    std::vector<uint64_t> scalars(count * 12, 0);
+    std::vector<uint8_t> comp(count * npp * cb);
+    for (size_t p = 0; p < count; p++) {
+        const uint8_t* s = in + p * pb;
+        const uint8_t hdr[CONTAINER_HDR] = {'B', 'P', 'P', '+', 1, (uint8_t)C::ID, (uint8_t)n, (uint8_t)m, (uint8_t)k, 0, 0, 0};
+        if (std::memcmp(s, hdr, CONTAINER_HDR) != 0) status[p] = BPP_FORMAT_ERROR;   // magic, version, curve, shape, reserved
+        std::memcpy(comp.data() + p * npp * cb, s + CONTAINER_HDR, npp * cb);
+        const uint8_t* sc = s + CONTAINER_HDR + npp * cb;
+        for (int t = 0; t < 3; t++)
+            if (!scalar_is_canonical<C>(sc + 32 * t)) status[p] = BPP_FORMAT_ERROR;   // one encoding per scalar
+        std::memcpy(scalars.data() + p * 12, sc, 96);
+    }
+    DevBuf db, dk, dp;
+    HIPCHK(db.upload(comp.data(), comp.size()));
+    HIPCHK(dk.alloc(count * npp * 4));
+    HIPCHK(dp.alloc(count * npp * WW * 4));
+    BPP_TRY(decompress_device(db.u8(), count * npp, dp.u64(), dk.u32(), nullptr, true));
+    std::vector<uint32_t> bad(count * npp);
+    HIPCHK(dk.download(bad.data(), bad.size() * 4));
+    for (size_t i = 0; i < bad.size(); i++)
+        if (bad[i]) status[i / npp] = BPP_FORMAT_ERROR;   // malformed encoding or a point outside the prime-order group
+    HIPCHK(dp.download(out_points, dp.bytes));
+    std::memcpy(out_scalars, scalars.data(), scalars.size() * 8);
+    std::memcpy(out_status, status.data(), status.size() * 4);
+    return BPP_OK;
 }
 
 #endif  // BPP_IMPL_DEFINITIONS

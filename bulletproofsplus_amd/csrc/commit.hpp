@@ -71,18 +71,13 @@ int CommitImpl<C>::commit_batch_device(bpp_verifier* v, const uint64_t* d_values
 template <class C>
 int CommitImpl<C>::commit_batch(bpp_verifier* v, const uint64_t* values, const uint64_t* gammas, size_t count, bool amount64,
                                 uint64_t* out_V) {
-    hipStream_t st = nullptr;
+    // (blocking copies where asynchronous ones on the null stream and a synchronise stood: the same transfers)
     DevBuf d_val, d_gam, d_V;
-    HIPCHK(d_val.alloc(count * 8));
-    HIPCHK(hipMemcpyAsync(d_val.p, values, count * 8, hipMemcpyHostToDevice, st));
-    int rc = upload_scalars<C>(gammas, count, d_gam, st);
-    if (rc) return rc;
+    HIPCHK(d_val.upload(values, count * 8));
+    BPP_TRY(upload_scalars<C>(gammas, count, d_gam, nullptr));
     HIPCHK(d_V.alloc(count * (size_t)WW * 4));
-    rc = commit_batch_device(v, static_cast<const uint64_t*>(d_val.p), static_cast<const uint64_t*>(d_gam.p), count, amount64,
-                             static_cast<uint64_t*>(d_V.p), st);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out_V, d_V.p, count * (size_t)WW * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    BPP_TRY(commit_batch_device(v, d_val.u64(), d_gam.u64(), count, amount64, d_V.u64(), nullptr));
+    HIPCHK(d_V.download(out_V, count * (size_t)WW * 4));
     return BPP_OK;
 }
 #endif  // BPP_IMPL_DEFINITIONS

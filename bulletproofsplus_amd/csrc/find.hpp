@@ -447,21 +447,20 @@ int FindImpl<C>::find_host(bpp_verifier* v, const FindArgs& a) {
     int rc = mixed_plan_serialized(v->s, a.m_of, a.count, (size_t)container_point_bytes<C>(a.version), false, p);
     if (rc) return rc;
     const size_t pairs = a.n_keys * a.count;
-    KeyUpload dk;
+    DevBuf dk(true);   // the keys: wiped before they are freed, on every way out
     BlockUpload up;
     DevBuf dtg, dok, dhits, dn, dws;
-    const void *p_k, *p_tg = nullptr;
-    if ((rc = up.upload(p, a.proofs, a.commitments, a.index, a.count, a.amounts, a.sealed ? a.count : pairs))) return rc;
-    if (a.tagged && (rc = upload_optional(a.tags, a.count, dtg, p_tg))) return rc;
-    if ((rc = upload_optional(a.keys, a.n_keys * 32, dk.d, p_k))) return rc;
+    BPP_TRY(up.upload(p, a.proofs, a.commitments, a.index, a.count, a.amounts, a.sealed ? a.count : pairs));
+    if (a.tagged) HIPCHK(dtg.upload(a.tags, a.count));
+    HIPCHK(dk.upload(a.keys, a.n_keys * 32));
     const size_t wsb = layout(v, p, a.count, a.n_keys, a.tagged).total;
     FindArgs d = a;
-    d.proofs = up.proofs;
-    d.commitments = up.commitments;
-    d.index = up.index;
-    d.amounts = up.amounts;
-    d.keys = static_cast<const uint8_t*>(p_k);
-    d.tags = static_cast<const uint8_t*>(p_tg);
+    d.proofs = up.proofs.u8();
+    d.commitments = up.commitments.u8();
+    d.index = up.index.u64();
+    d.amounts = up.amounts.u64();
+    d.keys = dk.u8();
+    d.tags = dtg.u8();
     d.max_hits = std::min(a.max_hits, pairs);   // no more records than there are pairs can come back
     HIPCHK(dok.alloc(a.count * 4));
     HIPCHK(dhits.alloc(d.max_hits * FIND_HIT_WORDS * 4));
@@ -471,12 +470,11 @@ int FindImpl<C>::find_host(bpp_verifier* v, const FindArgs& a) {
     d.hits = dhits.u32();
     d.n_hits = dn.u32();
     d.n_candidates = dn.u32() + 1;
-    if ((rc = find(v, d, dws.p, wsb, nullptr))) return rc;
+    BPP_TRY(find(v, d, dws.p, wsb, nullptr));
     uint32_t found[2] = {0, 0};
-    HIPCHK(hipMemcpy(found, dn.p, a.tagged ? 8 : 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(a.ok, dok.p, a.count * 4, hipMemcpyDeviceToHost));
-    const size_t written = std::min<size_t>(found[0], d.max_hits);
-    if (written) HIPCHK(hipMemcpy(a.hits, dhits.p, written * FIND_HIT_WORDS * 4, hipMemcpyDeviceToHost));
+    HIPCHK(dn.download(found, a.tagged ? 8 : 4));
+    HIPCHK(dok.download(a.ok, a.count * 4));
+    HIPCHK(dhits.download(a.hits, std::min<size_t>(found[0], d.max_hits) * FIND_HIT_WORDS * 4));
     *a.n_hits = found[0];
     if (a.tagged && a.n_candidates) *a.n_candidates = found[1];
     return BPP_OK;
@@ -497,14 +495,10 @@ template <class C>
 int FindImpl<C>::seal_host(const uint8_t* blind_key, uint64_t index_base, const uint64_t* index, const uint64_t* in, size_t count,
                            uint64_t* out) {
     DevBuf dix, dio;
-    const void* p_ix;
-    if (int rc = upload_optional(index, count * 8, dix, p_ix)) return rc;
-    HIPCHK(dio.alloc(count * 8));
-    HIPCHK(hipMemcpy(dio.p, in, count * 8, hipMemcpyHostToDevice));
-    if (int rc = seal(blind_key, index_base, static_cast<const uint64_t*>(p_ix), static_cast<const uint64_t*>(dio.p), count,
-                      static_cast<uint64_t*>(dio.p), nullptr))
-        return rc;
-    HIPCHK(hipMemcpy(out, dio.p, count * 8, hipMemcpyDeviceToHost));
+    HIPCHK(dix.upload(index, count * 8));
+    HIPCHK(dio.upload(in, count * 8));
+    BPP_TRY(seal(blind_key, index_base, dix.u64(), dio.u64(), count, dio.u64(), nullptr));
+    HIPCHK(dio.download(out, count * 8));
     return BPP_OK;
 }
 
@@ -522,12 +516,10 @@ int FindImpl<C>::tags(const uint8_t* blind_key, uint64_t index_base, const uint6
 template <class C>
 int FindImpl<C>::tags_host(const uint8_t* blind_key, uint64_t index_base, const uint64_t* index, size_t count, uint8_t* out) {
     DevBuf dix, dout;
-    const void* p_ix;
-    if (int rc = upload_optional(index, count * 8, dix, p_ix)) return rc;
+    HIPCHK(dix.upload(index, count * 8));
     HIPCHK(dout.alloc(count));
-    if (int rc = tags(blind_key, index_base, static_cast<const uint64_t*>(p_ix), count, static_cast<uint8_t*>(dout.p), nullptr))
-        return rc;
-    HIPCHK(hipMemcpy(out, dout.p, count, hipMemcpyDeviceToHost));
+    BPP_TRY(tags(blind_key, index_base, dix.u64(), count, dout.u8(), nullptr));
+    HIPCHK(dout.download(out, count));
     return BPP_OK;
 }
 #endif  // BPP_IMPL_DEFINITIONS

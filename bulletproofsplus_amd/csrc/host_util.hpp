@@ -1,5 +1,5 @@
-// host_util.hpp -- host-side helpers shared by capi.hip and prover.hpp (device buffers, error state,
-// curve dispatch, scalar canonicalisation, the MulVec launcher).
+// host_util.hpp -- host-side helpers shared by capi.hip and the impl_*.hpp units (device buffers: staging.hpp, error
+// state, curve dispatch, scalar canonicalisation, the MulVec launcher).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,7 +23,7 @@ struct bpp_ctx {
     size_t msm_passes = 0;
     std::vector<hipEvent_t> msm_events;
     uint32_t msm_shape[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // of the last bpp_msm_device call: n, items, W, q, nwide, nbuckets, L, c
-    // the small-table verifiers bpp_range_verify keeps per public key (capi.hip, struct VerifyCache); owned by the
+    // the small-table verifiers bpp_range_verify keeps per public key (literal.hpp, struct VerifyCache); owned by the
     // context that bpp_init returned -- the copies inside verifiers never touch it
     void* verify_cache = nullptr;
     bool verify_cache_off = false;
@@ -35,33 +35,9 @@ constexpr size_t BPP_MSM_SLOTS = 16;
 // to inline it: without this attribute capi.hip compiled every kernel of every curve a second time (8 minutes, 12 MB).
 #define BPP_NOINL __attribute__((noinline))
 
-// ---- error handling (g_err, fail: abi_guard.hpp) -------------------------------------------------------
-#define HIPCHK(expr)                                                                            \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return fail(BPP_E_HIP, #expr ": ", hipGetErrorString(e_));        \
-    } while (0)
-
+#include "staging.hpp"   // HIPCHK, DevBuf: the staging vocabulary of the host forms
 
 namespace bpp {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) {   // (re)allocates: a buffer held from an earlier call is freed first
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = n;
-        return hipMalloc(&p, n ? n : 16);
-    }
-    uint32_t* u32() const { return static_cast<uint32_t*>(p); }
-};
 
 template <class F>
 inline int dispatch(int curve, F&& f) {
@@ -92,6 +68,20 @@ inline void load_key_words(const uint8_t* key, uint32_t w[8]) {
         w[i] = key ? (uint32_t)key[4 * i] | ((uint32_t)key[4 * i + 1] << 8) | ((uint32_t)key[4 * i + 2] << 16) |
                          ((uint32_t)key[4 * i + 3] << 24)
                    : 0u;
+}
+
+// canonical (< group order) 32-byte little-endian scalar?
+template <class C>
+inline bool scalar_is_canonical(const uint8_t* b) {
+    uint32_t w[8];
+    load_key_words(b, w);
+    return words_lt_mod<typename C::Fr>(w);
+}
+
+inline uint32_t log2_exact(size_t x) {
+    uint32_t k = 0;
+    while (((size_t)1 << k) < x) k++;
+    return k;
 }
 
 // scalar (4 x u64 = 8 words) reduced mod r on the host: PrimeFieldElem values are always < r.  A 256-bit value holds up

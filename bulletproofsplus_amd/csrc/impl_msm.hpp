@@ -1,67 +1,12 @@
 // impl_msm.hpp -- host orchestration of the MulVec / scalar-multiplication kernels, one instantiation per
 // curve (tu_msm_*.hip).  Serves bpp_msm, bpp_msm_batch, bpp_scalar_mul_batch, bpp_pk_new, bpp_commit,
-// bpp_range_verify (single proof, no tables) and the device unit-test hooks.
+// bpp_range_verify (single proof, no tables).
 #pragma once
 #include "hash_to_group.hpp"
 #include "host_util.hpp"
 #include "pippenger.hpp"
 
 namespace bpp {
-
-template <class P>
-__global__ void __launch_bounds__(64) k_dbg_field(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t wa[P::N], wb[P::N], wr[P::N];
-    for (int t = 0; t < P::N; t++) {
-        wa[t] = a[i * P::N + t];
-        wb[t] = b[i * P::N + t];
-    }
-    Fe<P> x = fe_from_canonical<P>(wa), y = fe_from_canonical<P>(wb), r;
-    switch (op) {
-        case 0: r = fe_mul(x, y); break;
-        case 1: r = fe_add(x, y); break;
-        case 2: r = fe_sub(x, y); break;
-        case 3: r = fe_inv(x); break;
-        case 4: r = fe_sqr(x); break;
-        default: r = fe_neg(x); break;
-    }
-    fe_to_canonical(r, wr);
-    for (int t = 0; t < P::N; t++) out[i * P::N + t] = wr[t];
-}
-
-template <class C>
-__global__ void __launch_bounds__(64) k_dbg_point(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n) {
-    constexpr int WW = 2 * C::Fp::N + 2;
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t wa[WW], wb[WW], wr[WW];
-    for (int t = 0; t < WW; t++) {
-        wa[t] = a[i * WW + t];
-        wb[t] = b[i * WW + t];
-    }
-    Aff<C> p, q;
-    aff_from_wire<C>(wa, p);
-    aff_from_wire<C>(wb, q);
-    Jac<C> r;
-    switch (op) {
-        case 0: r = jac_add(jac_from_aff(p), jac_from_aff(q)); break;
-        case 1: r = jac_madd(jac_from_aff(p), q); break;
-        case 2: r = jac_dbl(jac_from_aff(p)); break;
-        case 3: r = jac_madd(jac_dbl(jac_from_aff(p)), q); break;  // non-trivial Z
-        case 4: r = jac_add(jac_dbl(jac_from_aff(p)), jac_dbl(jac_from_aff(q))); break;
-        default: {  // XYZZ accumulator: inf + p + q + p
-            Xyzz<C> acc = xyzz_inf<C>();
-            acc = xyzz_madd(acc, p);
-            acc = xyzz_madd(acc, q);
-            acc = xyzz_madd(acc, p);
-            r = xyzz_to_jac(acc);
-            break;
-        }
-    }
-    aff_to_wire(jac_to_aff(r), wr);
-    for (int t = 0; t < WW; t++) out[i * WW + t] = wr[t];
-}
 
 template <class C>
 struct MsmImpl {
@@ -104,11 +49,6 @@ struct MsmImpl {
     static int range_verify_single(const uint64_t* gh, const uint64_t* G, const uint64_t* H, size_t n, size_t m,
                                    const uint64_t* proof_points, size_t k, const uint64_t* proof_scalars,
                                    const uint64_t* V);
-
-    // field: 0 = base field, 1 = scalar field
-    static int debug_field_op(int field, int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out);
-
-    static int debug_point_op(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out);
 };
 
 // ---- definitions: compiled only by the translation unit that instantiates the struct (tu_*.hip defines
@@ -184,18 +124,15 @@ int MsmImpl<C>::msm_pippenger(const uint64_t* scalars, const uint64_t* points, s
     const size_t wsb = msm_workspace_bytes(n, window_bits);
     if (wsb == 0) return fail(BPP_E_ARG, "n too large");
     DevBuf dsc, dpt, ws, dout, dst;
-    HIPCHK(dsc.alloc(n * 32));
-    HIPCHK(dpt.alloc(n * WW * 4));
+    HIPCHK(dsc.upload(scalars, n * 32));
+    HIPCHK(dpt.upload(points, n * WW * 4));
     HIPCHK(ws.alloc(wsb));
     HIPCHK(dout.alloc(WW * 4));
     HIPCHK(dst.alloc(4));
-    HIPCHK(hipMemcpy(dsc.p, scalars, n * 32, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dpt.p, points, n * WW * 4, hipMemcpyHostToDevice));
-    int rc = msm_device(dsc.u32(), dpt.u32(), n, window_bits, dout.u32(), dst.u32(), ws.p, wsb, nullptr);
-    if (rc) return rc;
+    BPP_TRY(msm_device(dsc.u32(), dpt.u32(), n, window_bits, dout.u32(), dst.u32(), ws.p, wsb, nullptr));
     uint32_t bad = 0;
-    HIPCHK(hipMemcpy(out, dout.p, WW * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&bad, dst.p, 4, hipMemcpyDeviceToHost));
+    HIPCHK(dout.download(out, WW * 4));
+    HIPCHK(dst.download(&bad, 4));
     if (bad) return fail(BPP_E_POINT, "point not on curve / coordinate out of range");
     return BPP_OK;
 }
@@ -232,7 +169,7 @@ int MsmImpl<C>::scalar_mul_batch(const uint64_t* scalars, const uint64_t* points
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_points_to_wire<C>, dim3(cdiv(n, 64)), dim3(64), 0, nullptr, dres.u32(), dw.u32(), n);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(out, dw.p, n * WW * 4, hipMemcpyDeviceToHost));
+    HIPCHK(dw.download(out, n * WW * 4));
     return BPP_OK;
 }
 
@@ -252,12 +189,10 @@ int MsmImpl<C>::pk_new(size_t length, uint64_t* out_gh, uint64_t* out_G, uint64_
     Aff<C> gen = aff_generator<C>();
     aff_store(gen, g);
     DevBuf dsc, dg, dres, dw;
-    HIPCHK(dsc.alloc(total * 32));
-    HIPCHK(dg.alloc(sizeof g));
+    HIPCHK(dsc.upload(sc.data(), total * 32));
+    HIPCHK(dg.upload(g, sizeof g));
     HIPCHK(dres.alloc(total * 2 * N * 4));
     HIPCHK(dw.alloc(total * WW * 4));
-    HIPCHK(hipMemcpy(dsc.p, sc.data(), total * 32, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dg.p, g, sizeof g, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_scalar_mul<C>, dim3(cdiv(total, 64)), dim3(64), 0, nullptr, dsc.u32(), dg.u32(),
                        (size_t)0, dres.u32(), total);
     HIPCHK(hipGetLastError());
@@ -265,7 +200,7 @@ int MsmImpl<C>::pk_new(size_t length, uint64_t* out_gh, uint64_t* out_G, uint64_
                        total);
     HIPCHK(hipGetLastError());
     std::vector<uint32_t> hw(total * WW);
-    HIPCHK(hipMemcpy(hw.data(), dw.p, hw.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(dw.download(hw.data(), hw.size() * 4));
     const size_t pb = WW * 4;
     std::memcpy(out_gh, hw.data(), 2 * pb);
     if (length) {
@@ -286,7 +221,7 @@ int MsmImpl<C>::pk_hashed(const uint8_t* label, size_t label_len, size_t length,
     hipLaunchKernelGGL(k_hash_to_group<C>, dim3(cdiv(total, 64)), dim3(64), 0, nullptr, seed, (uint32_t)length, dw.u32());
     HIPCHK(hipGetLastError());
     std::vector<uint32_t> hw(total * WW);
-    HIPCHK(hipMemcpy(hw.data(), dw.p, hw.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(dw.download(hw.data(), hw.size() * 4));
     uint32_t gw[WW];
     aff_to_wire(aff_generator<C>(), gw);
     const size_t pb = WW * 4;
@@ -345,8 +280,7 @@ int MsmImpl<C>::range_verify_single(const uint64_t* gh, const uint64_t* G, const
     if (rc) return rc;
     std::vector<uint32_t> ch;
     default_challenges(s, ch);
-    HIPCHK(dch.alloc(ch.size() * 4));
-    HIPCHK(hipMemcpy(dch.p, ch.data(), ch.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(dch.upload(ch.data(), ch.size() * 4));
     HIPCHK(dsc.alloc((size_t)s.N * 32));
     DevBuf dprep;
     HIPCHK(dprep.alloc(vs_prep_bytes<C>(s)));
@@ -368,43 +302,6 @@ int MsmImpl<C>::range_verify_single(const uint64_t* gh, const uint64_t* G, const
         identity = identity || x0 || y0;
     }
     return identity ? BPP_OK : BPP_VERIFICATION_ERROR;
-}
-
-template <class C>
-int MsmImpl<C>::debug_field_op(int field, int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out) {
-    auto run = [&](auto pv) -> int {
-        using P = decltype(pv);
-        DevBuf da, db, dout;
-        const size_t bytes = n * P::N * 4;
-        HIPCHK(da.alloc(bytes));
-        HIPCHK(db.alloc(bytes));
-        HIPCHK(dout.alloc(bytes));
-        HIPCHK(hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_dbg_field<P>, dim3(cdiv(n, 64)), dim3(64), 0, nullptr, op, da.u32(), db.u32(),
-                           dout.u32(), n);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
-        return BPP_OK;
-    };
-    if (field == 0) return run(typename C::Fp{});
-    return run(typename C::Fr{});
-}
-
-template <class C>
-int MsmImpl<C>::debug_point_op(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {
-    DevBuf da, db, dout;
-    const size_t bytes = n * WW * 4;
-    HIPCHK(da.alloc(bytes));
-    HIPCHK(db.alloc(bytes));
-    HIPCHK(dout.alloc(bytes));
-    HIPCHK(hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_dbg_point<C>, dim3(cdiv(n, 64)), dim3(64), 0, nullptr, op, da.u32(), db.u32(), dout.u32(),
-                       n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
-    return BPP_OK;
 }
 
 #endif  // BPP_IMPL_DEFINITIONS

@@ -176,27 +176,11 @@ struct ProveBatchImpl {
     static int prove_serialized_mixed_host(bpp_verifier* v, const uint64_t* values, const uint64_t* gammas, const uint32_t* m_of,
                                            size_t count, int flags, const uint8_t* blind_key, uint64_t index_base,
                                            uint8_t* out_proofs, uint8_t* out_commitments);
-    // Values and gammas of the block p copied to the device, a workspace of wsb bytes and two outputs of bytes0 / bytes1
-    // allocated, run(d_v, d_gamma, d_out0, d_out1, d_ws), then the outputs copied to the host.
-    template <class F>
-    static int prove_mixed_staged(const MixedPlan& p, const uint64_t* values, const uint64_t* gammas, size_t wsb, void* out0,
-                                  size_t bytes0, void* out1, size_t bytes1, F&& run) {
+    // the amounts (and gammas) of the block p
+    static size_t plan_values(const MixedPlan& p) {
         size_t nval = 0;
         for (uint32_t c = 0; c < MIXED_CLASSES; c++) nval += p.count[c] << c;
-        DevBuf dv, dg, d0, d1, dws;
-        HIPCHK(dv.alloc(nval * 8));
-        HIPCHK(hipMemcpy(dv.p, values, nval * 8, hipMemcpyHostToDevice));
-        int rc = upload_scalars<C>(gammas, nval, dg, nullptr);
-        if (rc) return rc;
-        HIPCHK(d0.alloc(bytes0));
-        HIPCHK(d1.alloc(bytes1));
-        HIPCHK(dws.alloc(wsb));
-        rc = run(static_cast<const uint64_t*>(dv.p), static_cast<const uint64_t*>(dg.p), d0.p, d1.p, dws.p);
-        if (rc) return rc;
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(out0, d0.p, bytes0, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(out1, d1.p, bytes1, hipMemcpyDeviceToHost));
-        return BPP_OK;
+        return nval;
     }
 };
 
@@ -390,28 +374,24 @@ template <class C>
 int ProveBatchImpl<C>::prove_batch(bpp_verifier* v, const uint64_t* values, const uint64_t* gammas, size_t count,
                                    uint64_t* out_points, uint64_t* out_scalars, uint64_t* out_V, bool fs,
                                    const uint8_t* blind_key, uint64_t index_base, bool amount64) {
+    // (blocking copies through DevBuf where asynchronous ones on the null stream and a synchronise stood: the same
+    // transfers from and to pageable host memory, in the same order around the device form's launches)
     const VerifyShape& s = v->s;
     const uint32_t k = s.k, m = s.m;
-    hipStream_t st = nullptr;
     const ProveLayout L = prove_layout(s, count);
+    const size_t pts_bytes = count * (size_t)(3 + 2 * k) * WW * 4, V_bytes = count * (size_t)m * WW * 4;
     DevBuf d_val, d_gam, d_pts, d_V, d_sc, d_ws;
-    HIPCHK(d_val.alloc(count * m * 8));
-    HIPCHK(hipMemcpyAsync(d_val.p, values, count * m * 8, hipMemcpyHostToDevice, st));
-    int rc = upload_scalars<C>(gammas, count * m, d_gam, st);
-    if (rc) return rc;
-    HIPCHK(d_pts.alloc(count * (size_t)(3 + 2 * k) * WW * 4));
-    HIPCHK(d_V.alloc(count * (size_t)m * WW * 4));
+    HIPCHK(d_val.upload(values, count * m * 8));
+    BPP_TRY(upload_scalars<C>(gammas, count * m, d_gam, nullptr));
+    HIPCHK(d_pts.alloc(pts_bytes));
+    HIPCHK(d_V.alloc(V_bytes));
     HIPCHK(d_sc.alloc(count * 3 * 32));
     HIPCHK(d_ws.alloc(L.total));
-    rc = prove_batch_device(v, static_cast<const uint64_t*>(d_val.p), static_cast<const uint64_t*>(d_gam.p), count,
-                            static_cast<uint64_t*>(d_pts.p), static_cast<uint64_t*>(d_sc.p),
-                            static_cast<uint64_t*>(d_V.p), fs, nullptr, d_ws.p, L.total, st, blind_key, index_base, nullptr,
-                            amount64);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out_points, d_pts.p, count * (size_t)(3 + 2 * k) * WW * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out_scalars, d_sc.p, count * 96, hipMemcpyDeviceToHost, st));
-    if (out_V) HIPCHK(hipMemcpyAsync(out_V, d_V.p, count * (size_t)m * WW * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    BPP_TRY(prove_batch_device(v, d_val.u64(), d_gam.u64(), count, d_pts.u64(), d_sc.u64(), d_V.u64(), fs, nullptr, d_ws.p,
+                               L.total, nullptr, blind_key, index_base, nullptr, amount64));
+    HIPCHK(d_pts.download(out_points, pts_bytes));
+    HIPCHK(d_sc.download(out_scalars, count * 96));
+    if (out_V) HIPCHK(d_V.download(out_V, V_bytes));
     return BPP_OK;
 }
 
@@ -426,18 +406,20 @@ int ProveBatchImpl<C>::prove_mixed_host(bpp_verifier* v, const uint64_t* values,
     if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "mixed block rejected");
     const bool fs = (flags & BPP_SER_TRANSCRIPT) != 0;
     if (blind_key && !fs) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
-    const size_t wsb = prove_mixed_layout(v, p, count, false).total;
-    DevBuf dch;
+    const size_t wsb = prove_mixed_layout(v, p, count, false).total, nval = plan_values(p);
+    DevBuf dv, dg, dpts, dsc, dch, dws;
+    HIPCHK(dv.upload(values, nval * 8));
+    BPP_TRY(upload_scalars<C>(gammas, nval, dg, nullptr));
+    HIPCHK(dpts.alloc(p.points * WW * 4));
+    HIPCHK(dsc.alloc(count * 96));
     if (out_challenges) HIPCHK(dch.alloc(p.chals * 32));
-    const int rc = prove_mixed_staged(
-        p, values, gammas, wsb, out_points, p.points * WW * 4, out_scalars, count * 96,
-        [&](const uint64_t* dv, const uint64_t* dg, void* d0, void* d1, void* dws) {
-            return prove_mixed(v, dv, dg, m_of, count, fs, blind_key, index_base, nullptr, static_cast<uint64_t*>(d0),
-                               static_cast<uint64_t*>(d1), static_cast<uint64_t*>(dch.p), dws, wsb, nullptr,
-                               (flags & BPP_PROVE_AMOUNT64) != 0);
-        });
-    if (rc) return rc;
-    if (out_challenges) HIPCHK(hipMemcpy(out_challenges, dch.p, p.chals * 32, hipMemcpyDeviceToHost));
+    HIPCHK(dws.alloc(wsb));
+    BPP_TRY(prove_mixed(v, dv.u64(), dg.u64(), m_of, count, fs, blind_key, index_base, nullptr, dpts.u64(), dsc.u64(), dch.u64(),
+                        dws.p, wsb, nullptr, (flags & BPP_PROVE_AMOUNT64) != 0));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dpts.download(out_points, p.points * WW * 4));
+    HIPCHK(dsc.download(out_scalars, count * 96));
+    if (out_challenges) HIPCHK(dch.download(out_challenges, p.chals * 32));
     return BPP_OK;
 }
 
@@ -452,13 +434,19 @@ int ProveBatchImpl<C>::prove_serialized_mixed_host(bpp_verifier* v, const uint64
         return fail(BPP_E_ARG, "serialized mixed block rejected");
     const bool fs = (flags & BPP_SER_TRANSCRIPT) != 0;
     if (blind_key && !fs) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
-    const size_t wsb = prove_mixed_layout(v, p, count, true).total;
-    return prove_mixed_staged(p, values, gammas, wsb, out_proofs, p.proof_bytes, out_commitments, p.comm_bytes,
-                              [&](const uint64_t* dv, const uint64_t* dg, void* d0, void* d1, void* dws) {
-                                  return prove_serialized_mixed(v, dv, dg, m_of, count, fs, blind_key, index_base, nullptr,
-                                                                static_cast<uint8_t*>(d0), static_cast<uint8_t*>(d1), dws, wsb,
-                                                                nullptr, version, (flags & BPP_PROVE_AMOUNT64) != 0);
-                              });
+    const size_t wsb = prove_mixed_layout(v, p, count, true).total, nval = plan_values(p);
+    DevBuf dv, dg, dpr, dcm, dws;
+    HIPCHK(dv.upload(values, nval * 8));
+    BPP_TRY(upload_scalars<C>(gammas, nval, dg, nullptr));
+    HIPCHK(dpr.alloc(p.proof_bytes));
+    HIPCHK(dcm.alloc(p.comm_bytes));
+    HIPCHK(dws.alloc(wsb));
+    BPP_TRY(prove_serialized_mixed(v, dv.u64(), dg.u64(), m_of, count, fs, blind_key, index_base, nullptr, dpr.u8(), dcm.u8(),
+                                   dws.p, wsb, nullptr, version, (flags & BPP_PROVE_AMOUNT64) != 0));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(dpr.download(out_proofs, p.proof_bytes));
+    HIPCHK(dcm.download(out_commitments, p.comm_bytes));
+    return BPP_OK;
 }
 #endif  // BPP_IMPL_DEFINITIONS
 

@@ -598,6 +598,22 @@ struct VerifyImpl {
                                   bool with_status, uint64_t* h_stats, uint8_t* ws, const GroupMixedLayout& L,
                                   size_t workspace_bytes, hipStream_t st);
 
+    // ---- host buffers in, host verdicts out (staging.hpp) ------------------------------------------------------------
+    // bpp_range_verify_batch, _mixed, _compressed, _serialized and _serialized_mixed past their argument checks: each is
+    // its device ENTRY (bpp_verifier_run, .._run_mixed, bpp_range_verify_batch_serialized[_mixed]_device) between copies,
+    // so the entry's own argument rules (count per launch, flags) hold here without a second copy of them
+    static int verify_batch_host(bpp_verifier* v, const uint64_t* points, const uint64_t* scalars, size_t count, uint32_t* out_ok);
+    static int verify_batch_mixed_host(bpp_verifier* v, const uint64_t* points, const uint64_t* scalars, const uint32_t* m_of,
+                                       size_t count, uint32_t* out_ok);
+    // records: NV compressed points per proof; a malformed encoding, a point outside the group or a non-canonical scalar
+    // makes the proof's verdict BPP_FORMAT_ERROR
+    static int verify_batch_compressed_host(bpp_verifier* v, const uint8_t* records, const uint64_t* scalars, size_t count,
+                                            uint32_t* out_ok);
+    static int verify_batch_serialized_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, size_t count,
+                                            int flags, uint32_t* out_ok);
+    static int verify_batch_serialized_mixed_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments,
+                                                  const uint32_t* m_of, size_t count, int flags, uint32_t* out_ok);
+
     // d_partials: n partials as bpp_verifier_run_combined wrote them (jacobian + validity word each)
     static int sum_partials(const uint32_t* d_partials, size_t n, uint32_t* d_ok, hipStream_t st);
 };
@@ -1332,6 +1348,103 @@ int VerifyImpl<C>::sum_partials(const uint32_t* d_partials, size_t n, uint32_t* 
     hipLaunchKernelGGL(k_comb_sum_partials<C>, dim3(1), dim3(64), 0, st, d_partials, (uint32_t)n,
                        (uint32_t)partial_words<C>(), 1u, d_ok, (uint32_t*)nullptr);
     HIPCHK(hipGetLastError());
+    return BPP_OK;
+}
+
+template <class C>
+int VerifyImpl<C>::verify_batch_host(bpp_verifier* v, const uint64_t* points, const uint64_t* scalars, size_t count,
+                                     uint32_t* out_ok) {
+    const size_t wsb = ws_layout(v->s, count).total;
+    DevBuf dp, ds, dok, dws;
+    HIPCHK(dp.upload(points, count * v->s.NV * WW * 4));
+    HIPCHK(ds.upload(scalars, count * 96));
+    HIPCHK(dok.alloc(count * 4));
+    HIPCHK(dws.alloc(wsb));
+    BPP_TRY(bpp_verifier_run(v, dp.u64(), ds.u64(), count, nullptr, dok.u32(), dws.p, wsb, nullptr, nullptr, nullptr));
+    HIPCHK(dok.download(out_ok, count * 4));
+    return BPP_OK;
+}
+
+template <class C>
+int VerifyImpl<C>::verify_batch_mixed_host(bpp_verifier* v, const uint64_t* points, const uint64_t* scalars, const uint32_t* m_of,
+                                           size_t count, uint32_t* out_ok) {
+    const size_t wsb = mixed_workspace_bytes(v, m_of, count);
+    if (!wsb) {   // an m_i the verifier does not take: the plan names the proof
+        MixedPlan p;
+        const int rc = mixed_plan(v->s, m_of, count, false, p);
+        return rc ? rc : fail(BPP_E_ARG, "mixed batch rejected");
+    }
+    size_t npts = 0;
+    const uint32_t logn = v->s.k - (uint32_t)__builtin_ctz(v->s.m);
+    for (size_t i = 0; i < count; i++) npts += 3 + 2 * (logn + (uint32_t)__builtin_ctz(m_of[i])) + m_of[i];
+    DevBuf dp, ds, dok, dws;
+    HIPCHK(dp.upload(points, npts * WW * 4));
+    HIPCHK(ds.upload(scalars, count * 96));
+    HIPCHK(dok.alloc(count * 4));
+    HIPCHK(dws.alloc(wsb));
+    BPP_TRY(bpp_verifier_run_mixed(v, dp.u64(), ds.u64(), m_of, count, nullptr, dok.u32(), dws.p, wsb, nullptr, nullptr));
+    HIPCHK(dok.download(out_ok, count * 4));
+    return BPP_OK;
+}
+
+template <class C>
+int VerifyImpl<C>::verify_batch_compressed_host(bpp_verifier* v, const uint8_t* records, const uint64_t* scalars, size_t count,
+                                                uint32_t* out_ok) {
+    const size_t wsb = ws_layout(v->s, count).total, npts = count * v->s.NV;
+    std::vector<uint32_t> bad(npts);
+    DevBuf db, ds, dp, dk, dok, dws;
+    HIPCHK(db.upload(records, npts * compressed_bytes<C>()));
+    HIPCHK(ds.upload(scalars, count * 96));
+    HIPCHK(dok.alloc(count * 4));
+    HIPCHK(dws.alloc(wsb));
+    HIPCHK(dp.alloc(npts * WW * 4));
+    HIPCHK(dk.alloc(npts * 4));
+    // the one wire entry point for points of unknown origin besides the container: reject what is outside the
+    // prime-order group too (the verifier's GLV evaluation equals s * P only there, include/bpp_amd.h)
+    BPP_TRY(bpp_points_decompress_device(&v->ctx, db.p, npts, dp.u64(), dk.u32(), 1, nullptr));
+    BPP_TRY(bpp_verifier_run(v, dp.u64(), ds.u64(), count, nullptr, dok.u32(), dws.p, wsb, nullptr, nullptr, nullptr));
+    HIPCHK(dk.download(bad.data(), npts * 4));
+    HIPCHK(dok.download(out_ok, count * 4));
+    for (size_t i = 0; i < npts; i++)
+        if (bad[i]) out_ok[i / v->s.NV] = BPP_FORMAT_ERROR;   // a malformed encoding / a point outside the group: ProofError::FormatError
+    // ... and so does a non-canonical scalar (r', s' or delta' >= the group order): a serialized proof has one encoding
+    // (little-endian host: the u64 limbs are the bytes)
+    for (size_t i = 0; i < count * 3; i++)
+        if (!scalar_is_canonical<C>(reinterpret_cast<const uint8_t*>(scalars + i * 4))) out_ok[i / 3] = BPP_FORMAT_ERROR;
+    return BPP_OK;
+}
+
+template <class C>
+int VerifyImpl<C>::verify_batch_serialized_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, size_t count,
+                                                int flags, uint32_t* out_ok) {
+    const uint32_t version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
+    const size_t pb = container_bytes<C>(v->s.k, version), cb = (size_t)container_point_bytes<C>(version);
+    const size_t wsb = ser_layout(v->s, count).total;
+    DevBuf dpr, dcm, dok, dws;
+    HIPCHK(dpr.upload(proofs, count * pb));
+    HIPCHK(dcm.upload(commitments, count * v->s.m * cb));
+    HIPCHK(dok.alloc(count * 4));
+    HIPCHK(dws.alloc(wsb));
+    BPP_TRY(bpp_range_verify_batch_serialized_device(v, dpr.p, dcm.p, count, flags, dok.u32(), dws.p, wsb, nullptr));
+    HIPCHK(dok.download(out_ok, count * 4));
+    return BPP_OK;
+}
+
+template <class C>
+int VerifyImpl<C>::verify_batch_serialized_mixed_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments,
+                                                      const uint32_t* m_of, size_t count, int flags, uint32_t* out_ok) {
+    const size_t cb = (size_t)container_point_bytes<C>((flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u);
+    const size_t wsb = bpp_verifier_serialized_mixed_workspace_bytes(v, m_of, count);
+    MixedPlan p;
+    const int rc = mixed_plan_serialized(v->s, m_of, count, cb, false, p);   // its byte totals size the uploads
+    if (rc || !wsb) return rc ? rc : fail(BPP_E_ARG, "serialized mixed batch rejected");   // an m_i the verifier does not take
+    DevBuf dpr, dcm, dok, dws;
+    HIPCHK(dpr.upload(proofs, p.proof_bytes));
+    HIPCHK(dcm.upload(commitments, p.comm_bytes));
+    HIPCHK(dok.alloc(count * 4));
+    HIPCHK(dws.alloc(wsb));
+    BPP_TRY(bpp_range_verify_batch_serialized_mixed_device(v, dpr.p, dcm.p, m_of, count, flags, dok.u32(), dws.p, wsb, nullptr));
+    HIPCHK(dok.download(out_ok, count * 4));
     return BPP_OK;
 }
 

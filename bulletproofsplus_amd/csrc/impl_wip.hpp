@@ -161,14 +161,10 @@ int WipImpl<C>::verify_device(bpp_verifier* v, const uint64_t* d_points, const u
         d_ok, ws + L.run, workspace_bytes - L.run, d_out_scalars, d_out_result, st);
 }
 
-// a host buffer of n bytes on the device (null: nothing)
-inline int wip_upload(const void* h, size_t n, DevBuf& d, hipStream_t st) {
-    if (!h) return BPP_OK;
-    HIPCHK(d.alloc(n));
-    if (n) HIPCHK(hipMemcpyAsync(d.p, h, n, hipMemcpyHostToDevice, st));
-    return BPP_OK;
-}
-
+// The two host forms stage through DevBuf (staging.hpp): blocking copies, where they used to enqueue asynchronous ones on
+// the null stream and synchronise -- from and to pageable host memory that is the same transfer, and the device entries'
+// launches on the null stream are ordered between the copies as before.  A failed entry returns at once: the buffers'
+// hipFree waits for whatever was enqueued.
 template <class C>
 int WipImpl<C>::prove_host(bpp_verifier* v, const uint64_t* a, const uint64_t* b, const uint64_t* y, const uint64_t* gamma,
                            size_t count, size_t nv, bool fs, const void* transcript, const uint8_t* blind_key,
@@ -176,33 +172,24 @@ int WipImpl<C>::prove_host(bpp_verifier* v, const uint64_t* a, const uint64_t* b
                            uint64_t* out_challenges) {
     const VerifyShape s = prove_shape(v);
     const uint32_t k = s.k;
-    hipStream_t st = nullptr;
-    const size_t pts_bytes = count * (size_t)(3 + 2 * k + nv) * WW * 4;
+    const size_t pts_bytes = count * (size_t)(3 + 2 * k + nv) * WW * 4, ch_bytes = count * (size_t)(1 + k) * 32;
     DevBuf da, db, dy, dg, dtr, dbl, dpts, dsc, dch, dws;
-    int rc;
-    if ((rc = wip_upload(a, count * (size_t)s.mn * 32, da, st))) return rc;
-    if ((rc = wip_upload(b, count * (size_t)s.mn * 32, db, st))) return rc;
-    if ((rc = wip_upload(y, count * 32, dy, st))) return rc;
-    if ((rc = wip_upload(gamma, count * 32, dg, st))) return rc;
-    if ((rc = wip_upload(transcript, count * 32, dtr, st))) return rc;
-    if ((rc = wip_upload(blinding, count * (size_t)pb_blind_elems(k) * 32, dbl, st))) return rc;
-    if ((rc = wip_upload(points, pts_bytes, dpts, st))) return rc;   // point 0 and the last nv of a record are the caller's
+    HIPCHK(da.upload(a, count * (size_t)s.mn * 32));
+    HIPCHK(db.upload(b, count * (size_t)s.mn * 32));
+    HIPCHK(dy.upload(y, count * 32));
+    HIPCHK(dg.upload(gamma, count * 32));
+    HIPCHK(dtr.upload(transcript, count * 32));
+    HIPCHK(dbl.upload(blinding, count * (size_t)pb_blind_elems(k) * 32));
+    HIPCHK(dpts.upload(points, pts_bytes));   // point 0 and the last nv of a record are the caller's
     HIPCHK(dsc.alloc(count * 96));
-    if (out_challenges) HIPCHK(dch.alloc(count * (size_t)(1 + k) * 32));
+    if (out_challenges) HIPCHK(dch.alloc(ch_bytes));
     const size_t wsb = prove_ws(v, count).total;
     HIPCHK(dws.alloc(wsb));
-    rc = prove_device(v, static_cast<const uint64_t*>(da.p), static_cast<const uint64_t*>(db.p),
-                      static_cast<const uint64_t*>(dy.p), static_cast<const uint64_t*>(dg.p), count, nv, fs, dtr.p, blind_key,
-                      index_base, static_cast<const uint64_t*>(dbl.p), static_cast<uint64_t*>(dpts.p),
-                      static_cast<uint64_t*>(dsc.p), static_cast<uint64_t*>(dch.p), dws.p, wsb, st);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    HIPCHK(hipMemcpyAsync(points, dpts.p, pts_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out_scalars, dsc.p, count * 96, hipMemcpyDeviceToHost, st));
-    if (out_challenges) HIPCHK(hipMemcpyAsync(out_challenges, dch.p, count * (size_t)(1 + k) * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    BPP_TRY(prove_device(v, da.u64(), db.u64(), dy.u64(), dg.u64(), count, nv, fs, dtr.p, blind_key, index_base, dbl.u64(),
+                         dpts.u64(), dsc.u64(), dch.u64(), dws.p, wsb, nullptr));
+    HIPCHK(dpts.download(points, pts_bytes));
+    HIPCHK(dsc.download(out_scalars, count * 96));
+    if (out_challenges) HIPCHK(dch.download(out_challenges, ch_bytes));
     return BPP_OK;
 }
 
@@ -211,32 +198,23 @@ int WipImpl<C>::verify_host(bpp_verifier* v, const uint64_t* points, const uint6
                             const uint64_t* statement, size_t nv, size_t count, bool fs, const void* transcript,
                             const uint64_t* challenges, uint32_t* out_ok, uint64_t* out_scalars, uint64_t* out_result) {
     const VerifyShape s = verify_shape(v, nv);
-    hipStream_t st = nullptr;
     DevBuf dp, dsc, dy, dstm, dtr, dch, dok, dos, dres, dws;
-    int rc;
-    if ((rc = wip_upload(points, count * (size_t)s.NV * WW * 4, dp, st))) return rc;
-    if ((rc = wip_upload(scalars, count * 96, dsc, st))) return rc;
-    if ((rc = wip_upload(y, count * 32, dy, st))) return rc;
-    if ((rc = wip_upload(statement, count * (size_t)wip_statement_elems(s) * 32, dstm, st))) return rc;
-    if ((rc = wip_upload(transcript, count * 32, dtr, st))) return rc;
-    if ((rc = wip_upload(challenges, count * (size_t)(1 + s.k) * 32, dch, st))) return rc;
+    HIPCHK(dp.upload(points, count * (size_t)s.NV * WW * 4));
+    HIPCHK(dsc.upload(scalars, count * 96));
+    HIPCHK(dy.upload(y, count * 32));
+    HIPCHK(dstm.upload(statement, count * (size_t)wip_statement_elems(s) * 32));
+    HIPCHK(dtr.upload(transcript, count * 32));
+    HIPCHK(dch.upload(challenges, count * (size_t)(1 + s.k) * 32));
     HIPCHK(dok.alloc(count * 4));
     if (out_scalars) HIPCHK(dos.alloc(count * (size_t)s.N * 32));
     if (out_result) HIPCHK(dres.alloc(count * (size_t)WW * 4));
     const size_t wsb = verify_ws(v, count, nv).total;
     HIPCHK(dws.alloc(wsb));
-    rc = verify_device(v, static_cast<const uint64_t*>(dp.p), static_cast<const uint64_t*>(dsc.p),
-                       static_cast<const uint64_t*>(dy.p), static_cast<const uint64_t*>(dstm.p), nv, count, fs, dtr.p,
-                       static_cast<const uint64_t*>(dch.p), static_cast<uint32_t*>(dok.p), dws.p, wsb,
-                       static_cast<uint64_t*>(dos.p), static_cast<uint64_t*>(dres.p), st);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    HIPCHK(hipMemcpyAsync(out_ok, dok.p, count * 4, hipMemcpyDeviceToHost, st));
-    if (out_scalars) HIPCHK(hipMemcpyAsync(out_scalars, dos.p, count * (size_t)s.N * 32, hipMemcpyDeviceToHost, st));
-    if (out_result) HIPCHK(hipMemcpyAsync(out_result, dres.p, count * (size_t)WW * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    BPP_TRY(verify_device(v, dp.u64(), dsc.u64(), dy.u64(), dstm.u64(), nv, count, fs, dtr.p, dch.u64(), dok.u32(), dws.p, wsb,
+                          dos.u64(), dres.u64(), nullptr));
+    HIPCHK(dok.download(out_ok, count * 4));
+    if (out_scalars) HIPCHK(dos.download(out_scalars, count * (size_t)s.N * 32));
+    if (out_result) HIPCHK(dres.download(out_result, count * (size_t)WW * 4));
     return BPP_OK;
 }
 #endif  // BPP_IMPL_DEFINITIONS

@@ -317,33 +317,15 @@ int RecoverImpl<C>::recover_masks_mixed(bpp_verifier* v, const uint64_t* d_scala
     return BPP_OK;
 }
 
-// device copies of optional host buffers: null stays null
-static inline int upload_optional(const void* src, size_t bytes, DevBuf& d, const void*& out) {
-    out = nullptr;
-    if (!src) return BPP_OK;
-    HIPCHK(d.alloc(bytes));
-    HIPCHK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-    out = d.p;
-    return BPP_OK;
-}
-
 // what every host twin of a scan uploads of its block: proofs, commitments, index and amounts (n_amounts of them)
 struct BlockUpload {
-    DevBuf dpr, dcm, dix, dam;
-    const uint8_t *proofs = nullptr, *commitments = nullptr;
-    const uint64_t *index = nullptr, *amounts = nullptr;
+    DevBuf proofs, commitments, index, amounts;
     int upload(const MixedPlan& p, const uint8_t* h_proofs, const uint8_t* h_commitments, const uint64_t* h_index, size_t count,
                const uint64_t* h_amounts, size_t n_amounts) {
-        const void *pr, *cm, *ix, *am;
-        int rc;
-        if ((rc = upload_optional(h_proofs, p.proof_bytes, dpr, pr))) return rc;
-        if ((rc = upload_optional(h_commitments, p.comm_bytes, dcm, cm))) return rc;
-        if ((rc = upload_optional(h_index, count * 8, dix, ix))) return rc;
-        if ((rc = upload_optional(h_amounts, n_amounts * 8, dam, am))) return rc;
-        proofs = static_cast<const uint8_t*>(pr);
-        commitments = static_cast<const uint8_t*>(cm);
-        index = static_cast<const uint64_t*>(ix);
-        amounts = static_cast<const uint64_t*>(am);
+        HIPCHK(proofs.upload(h_proofs, p.proof_bytes));
+        HIPCHK(commitments.upload(h_commitments, p.comm_bytes));
+        HIPCHK(index.upload(h_index, count * 8));
+        HIPCHK(amounts.upload(h_amounts, n_amounts * 8));
         return BPP_OK;
     }
 };
@@ -359,19 +341,16 @@ int RecoverImpl<C>::recover_masks_mixed_host(bpp_verifier* v, const uint64_t* sc
     size_t nbl = 0;
     for (size_t i = 0; i < count; i++) nbl += pb_blind_elems(logn + (uint32_t)__builtin_ctz(m_of[i]));
     DevBuf dsc, dch, dix, dbl, dout, dws;
-    const void *p_sc, *p_ch, *p_ix, *p_bl;
-    if ((rc = upload_optional(scalars, count * 96, dsc, p_sc))) return rc;
-    if ((rc = upload_optional(challenges, p.chals * 32, dch, p_ch))) return rc;
-    if ((rc = upload_optional(index, count * 8, dix, p_ix))) return rc;
-    if ((rc = upload_optional(blinding, nbl * 32, dbl, p_bl))) return rc;
+    HIPCHK(dsc.upload(scalars, count * 96));
+    HIPCHK(dch.upload(challenges, p.chals * 32));
+    HIPCHK(dix.upload(index, count * 8));
+    HIPCHK(dbl.upload(blinding, nbl * 32));
     const size_t wsb = recover_workspace_bytes(v, m_of, count);
     HIPCHK(dout.alloc(count * 32));
     HIPCHK(dws.alloc(wsb));
-    const Blinding b{blind_key, index_base, static_cast<const uint64_t*>(p_ix), static_cast<const uint64_t*>(p_bl)};
-    rc = recover_masks_mixed(v, static_cast<const uint64_t*>(p_sc), m_of, count, static_cast<const uint64_t*>(p_ch), b,
-                             static_cast<uint64_t*>(dout.p), dws.p, wsb, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(out_masks, dout.p, count * 32, hipMemcpyDeviceToHost));
+    const Blinding b{blind_key, index_base, dix.u64(), dbl.u64()};
+    BPP_TRY(recover_masks_mixed(v, dsc.u64(), m_of, count, dch.u64(), b, dout.u64(), dws.p, wsb, nullptr));
+    HIPCHK(dout.download(out_masks, count * 32));
     return BPP_OK;
 }
 
@@ -452,20 +431,18 @@ int RecoverImpl<C>::scan_serialized_mixed_host(bpp_verifier* v, const uint8_t* p
     for (size_t i = 0; i < count; i++) nbl += pb_blind_elems(logn + (uint32_t)__builtin_ctz(m_of[i]));
     BlockUpload up;
     DevBuf dbl, dout, dst, dws;
-    const void* p_bl;
-    if ((rc = up.upload(p, proofs, commitments, index, count, amounts, count))) return rc;
-    if ((rc = upload_optional(blinding, nbl * 32, dbl, p_bl))) return rc;
+    BPP_TRY(up.upload(p, proofs, commitments, index, count, amounts, count));
+    HIPCHK(dbl.upload(blinding, nbl * 32));
     const size_t wsb = scan_layout(p, count).total;
     HIPCHK(dout.alloc(count * 32));
     HIPCHK(dst.alloc(count * 4));
     HIPCHK(dws.alloc(wsb));
-    const Blinding b{blind_key, index_base, up.index, static_cast<const uint64_t*>(p_bl)};
-    rc = scan_serialized_mixed(v, up.proofs, up.commitments, m_of, count, (flags & BPP_SER_TRANSCRIPT) != 0, version,
-                               (flags & BPP_PROVE_AMOUNT64) != 0, b, up.amounts, static_cast<uint64_t*>(dout.p), dst.u32(), dws.p,
-                               wsb, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(out_masks, dout.p, count * 32, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_status, dst.p, count * 4, hipMemcpyDeviceToHost));
+    const Blinding b{blind_key, index_base, up.index.u64(), dbl.u64()};
+    BPP_TRY(scan_serialized_mixed(v, up.proofs.u8(), up.commitments.u8(), m_of, count, (flags & BPP_SER_TRANSCRIPT) != 0, version,
+                                  (flags & BPP_PROVE_AMOUNT64) != 0, b, up.amounts.u64(), dout.u64(), dst.u32(), dws.p, wsb,
+                                  nullptr));
+    HIPCHK(dout.download(out_masks, count * 32));
+    HIPCHK(dst.download(out_status, count * 4));
     return BPP_OK;
 }
 #endif  // BPP_IMPL_DEFINITIONS

@@ -256,15 +256,6 @@ struct RecoverKeysImpl {
                          const uint64_t* amounts, uint64_t* out_masks, uint32_t* out_status);
 };
 
-// a host twin's copy of the keys (scan_host, find_host, the debug hook of tu_debug.hip): overwritten before it is freed, on
-// every way out
-struct KeyUpload {
-    DevBuf d;
-    ~KeyUpload() {
-        if (d.p) (void)hipMemset(d.p, 0, d.bytes);
-    }
-};
-
 #ifdef BPP_IMPL_DEFINITIONS
 template <class C>
 size_t RecoverKeysImpl<C>::workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
@@ -358,22 +349,19 @@ int RecoverKeysImpl<C>::scan_host(bpp_verifier* v, const uint8_t* proofs, const 
     int rc = mixed_plan_serialized(v->s, m_of, count, (size_t)container_point_bytes<C>(version), false, p);
     if (rc) return rc;
     const size_t pairs = n_keys * count;
-    KeyUpload dk;
+    DevBuf dk(true);   // the keys: wiped before they are freed, on every way out
     BlockUpload up;
     DevBuf dout, dst, dws;
-    const void* p_k;
-    if ((rc = up.upload(p, proofs, commitments, index, count, amounts, pairs))) return rc;
-    if ((rc = upload_optional(keys, n_keys * 32, dk.d, p_k))) return rc;
+    BPP_TRY(up.upload(p, proofs, commitments, index, count, amounts, pairs));
+    HIPCHK(dk.upload(keys, n_keys * 32));
     const size_t wsb = layout(v, p, count).total;
     HIPCHK(dout.alloc(pairs * 32));
     HIPCHK(dst.alloc(pairs * 4));
     HIPCHK(dws.alloc(wsb));
-    rc = scan(v, up.proofs, up.commitments, m_of, count, version, (flags & BPP_PROVE_AMOUNT64) != 0,
-              static_cast<const uint8_t*>(p_k), n_keys, index_base, up.index, up.amounts, static_cast<uint64_t*>(dout.p), dst.u32(),
-              dws.p, wsb, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(out_masks, dout.p, pairs * 32, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_status, dst.p, pairs * 4, hipMemcpyDeviceToHost));
+    BPP_TRY(scan(v, up.proofs.u8(), up.commitments.u8(), m_of, count, version, (flags & BPP_PROVE_AMOUNT64) != 0, dk.u8(), n_keys,
+                 index_base, up.index.u64(), up.amounts.u64(), dout.u64(), dst.u32(), dws.p, wsb, nullptr));
+    HIPCHK(dout.download(out_masks, pairs * 32));
+    HIPCHK(dst.download(out_status, pairs * 4));
     return BPP_OK;
 }
 #endif  // BPP_IMPL_DEFINITIONS

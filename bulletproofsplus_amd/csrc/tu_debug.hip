@@ -1,7 +1,8 @@
-// tu_debug.hip -- device-side unit-test hooks on RAW register images: the field operations at limbs the test chooses
+// tu_debug.hip -- the device-side unit-test hooks: the field and group primitives on canonical values
+// (bpp_debug_field_op / bpp_debug_point_op), and on RAW register images the field operations at limbs the test chooses
 // (field_raw_ops.hpp), the lazy mixed addition on a raw accumulator, and the scalar splits / digit recoding as the
 // device compiles them.  A translation unit of its own: none of this is compiled into the units of the hot kernels.
-// Like bpp_debug_field_op / bpp_debug_point_op (capi.hip) the entries are not part of include/bpp_amd.h.
+// The entries are not part of include/bpp_amd.h.
 // Every pointer is a host pointer -- except in bpp_debug_verifier_mulvec, the verifier's back end (VerifyImpl::run_stage) on
 // MulVec scalars the test chooses, which takes device buffers as bpp_verifier_run does and adds no kernel.  Its front half,
 // the scalar stage (launch_verify_scalars) on challenges the test chooses, is bpp_debug_verifier_scalars: host pointers again.
@@ -15,6 +16,61 @@
 #include "recover_keys.hpp"  // likewise: k_recover_coeffs and k_scan_keys live in tu_recover_keys_*.hip
 
 namespace bpp {
+
+template <class P>
+__global__ void __launch_bounds__(64) k_dbg_field(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t wa[P::N], wb[P::N], wr[P::N];
+    for (int t = 0; t < P::N; t++) {
+        wa[t] = a[i * P::N + t];
+        wb[t] = b[i * P::N + t];
+    }
+    Fe<P> x = fe_from_canonical<P>(wa), y = fe_from_canonical<P>(wb), r;
+    switch (op) {
+        case 0: r = fe_mul(x, y); break;
+        case 1: r = fe_add(x, y); break;
+        case 2: r = fe_sub(x, y); break;
+        case 3: r = fe_inv(x); break;
+        case 4: r = fe_sqr(x); break;
+        default: r = fe_neg(x); break;
+    }
+    fe_to_canonical(r, wr);
+    for (int t = 0; t < P::N; t++) out[i * P::N + t] = wr[t];
+}
+
+template <class C>
+__global__ void __launch_bounds__(64) k_dbg_point(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n) {
+    constexpr int WW = 2 * C::Fp::N + 2;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t wa[WW], wb[WW], wr[WW];
+    for (int t = 0; t < WW; t++) {
+        wa[t] = a[i * WW + t];
+        wb[t] = b[i * WW + t];
+    }
+    Aff<C> p, q;
+    aff_from_wire<C>(wa, p);
+    aff_from_wire<C>(wb, q);
+    Jac<C> r;
+    switch (op) {
+        case 0: r = jac_add(jac_from_aff(p), jac_from_aff(q)); break;
+        case 1: r = jac_madd(jac_from_aff(p), q); break;
+        case 2: r = jac_dbl(jac_from_aff(p)); break;
+        case 3: r = jac_madd(jac_dbl(jac_from_aff(p)), q); break;  // non-trivial Z
+        case 4: r = jac_add(jac_dbl(jac_from_aff(p)), jac_dbl(jac_from_aff(q))); break;
+        default: {  // XYZZ accumulator: inf + p + q + p
+            Xyzz<C> acc = xyzz_inf<C>();
+            acc = xyzz_madd(acc, p);
+            acc = xyzz_madd(acc, q);
+            acc = xyzz_madd(acc, p);
+            r = xyzz_to_jac(acc);
+            break;
+        }
+    }
+    aff_to_wire(jac_to_aff(r), wr);
+    for (int t = 0; t < WW; t++) out[i * WW + t] = wr[t];
+}
 
 template <class P, int G>
 __global__ void __launch_bounds__(64) k_dbg_field_raw(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c,
@@ -108,20 +164,14 @@ static int on_ctx_device(const bpp_ctx* ctx, size_t n, F&& f) noexcept {
     });
 }
 
-static int upload(DevBuf& d, const void* src, size_t bytes) {
-    HIPCHK(d.alloc(bytes));
-    if (bytes) HIPCHK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-    return BPP_OK;
-}
-
 template <class P>
 static int field_raw_op(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, size_t n, uint32_t* out) {
     const size_t in_bytes = n * P::NL * 4, out_bytes = n * raw_out_words(P::NL) * 4;
     DevBuf da, db, dc, dd, dout, dbad;
-    if (int rc = upload(da, a, in_bytes)) return rc;
-    if (int rc = upload(db, b, in_bytes)) return rc;
-    if (int rc = upload(dc, c, in_bytes)) return rc;
-    if (int rc = upload(dd, d, in_bytes)) return rc;
+    HIPCHK(da.upload(a, in_bytes));
+    HIPCHK(db.upload(b, in_bytes));
+    HIPCHK(dc.upload(c, in_bytes));
+    HIPCHK(dd.upload(d, in_bytes));
     HIPCHK(dout.alloc(out_bytes));
     HIPCHK(dbad.alloc(4));
     HIPCHK(hipMemset(dbad.p, 0, 4));
@@ -136,15 +186,61 @@ static int field_raw_op(int op, const uint32_t* a, const uint32_t* b, const uint
         HIPCHK(hipGetLastError());
     }
     uint32_t bad = 0;
-    HIPCHK(hipMemcpy(&bad, dbad.p, 4, hipMemcpyDeviceToHost));
+    HIPCHK(dbad.download(&bad, 4));
     if (bad) return fail(BPP_E_ARG, "unknown raw field op");
-    if (out_bytes) HIPCHK(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+    if (out_bytes) HIPCHK(dout.download(out, out_bytes));
+    return BPP_OK;
+}
+
+// field: 0 = base field, 1 = scalar field; a, b, out: n elements of P::N canonical words
+template <class P>
+static int field_op(int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out) {
+    DevBuf da, db, dout;
+    const size_t bytes = n * P::N * 4;
+    HIPCHK(da.upload(a, bytes));
+    HIPCHK(db.upload(b, bytes));
+    HIPCHK(dout.alloc(bytes));
+    hipLaunchKernelGGL(k_dbg_field<P>, dim3(cdiv(n, 64)), dim3(64), 0, nullptr, op, da.u32(), db.u32(), dout.u32(), n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(dout.download(out, bytes));
+    return BPP_OK;
+}
+
+template <class C>
+static int point_op(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {
+    DevBuf da, db, dout;
+    const size_t bytes = n * wire_words<C>() * 4;
+    HIPCHK(da.upload(a, bytes));
+    HIPCHK(db.upload(b, bytes));
+    HIPCHK(dout.alloc(bytes));
+    hipLaunchKernelGGL(k_dbg_point<C>, dim3(cdiv(n, 64)), dim3(64), 0, nullptr, op, da.u32(), db.u32(), dout.u32(), n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(dout.download(out, bytes));
     return BPP_OK;
 }
 
 }  // namespace bpp
 
 using namespace bpp;
+
+// The field and group primitives on canonical values (tests/ check them against a CPU checker).
+// field: 0 = base field, 1 = scalar field; op: 0 mul, 1 add, 2 sub, 3 inv, 4 sqr, 5 neg
+// a, b, out: n elements of N 32-bit words (N = 12 for BLS12-381 Fp, else 8), host pointers
+extern "C" int bpp_debug_field_op(bpp_ctx* ctx, int field, int op, const uint32_t* a, const uint32_t* b, size_t n,
+                                  uint32_t* out) {
+    if (!ctx || !a || !b || !out) return fail(BPP_E_ARG, "null argument");
+    return on_ctx_device(ctx, n, [&](auto cv) -> int {
+        using C = decltype(cv);
+        if (field == 0) return field_op<typename C::Fp>(op, a, b, n, out);
+        return field_op<typename C::Fr>(op, a, b, n, out);
+    });
+}
+// op: 0 add, 1 madd, 2 dbl(a), 3 madd(2a, b), 4 add(2a, 2b), 5 xyzz: inf + a + b + a; wire points, host pointers
+extern "C" int bpp_debug_point_op(bpp_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, size_t n,
+                                  uint64_t* out) {
+    if (!ctx || !a || !b || !out) return fail(BPP_E_ARG, "null argument");
+    return on_ctx_device(ctx, n, [&](auto cv) -> int { return point_op<decltype(cv)>(op, a, b, n, out); });
+}
 
 // field: 0 = base field, 1 = scalar field; op: a RawOp of field_raw_ops.hpp.  a, b, c, d: n operands of NL words each
 // (30-bit limbs, taken as given; every operation reads only the operands it has, but all four must be readable);
@@ -169,15 +265,15 @@ extern "C" int bpp_debug_madd_lazy_raw(bpp_ctx* ctx, const uint32_t* acc, const 
         using C = decltype(cv);
         constexpr int NL = C::Fp::NL;
         DevBuf dacc, dq, dneg, dout;
-        if (int rc = upload(dacc, acc, n * 4 * NL * 4)) return rc;
-        if (int rc = upload(dq, q, n * 2 * NL * 4)) return rc;
-        if (int rc = upload(dneg, neg, n * 4)) return rc;
+        HIPCHK(dacc.upload(acc, n * 4 * NL * 4));
+        HIPCHK(dq.upload(q, n * 2 * NL * 4));
+        HIPCHK(dneg.upload(neg, n * 4));
         HIPCHK(dout.alloc(n * 4 * NL * 4));
         if (n) {
             hipLaunchKernelGGL(k_dbg_madd_lazy_raw<C>, dim3(cdiv(n, 64)), dim3(64), 0, nullptr, dacc.u32(), dq.u32(), dneg.u32(),
                                dout.u32(), n);
             HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpy(out, dout.p, n * 4 * NL * 4, hipMemcpyDeviceToHost));
+            HIPCHK(dout.download(out, n * 4 * NL * 4));
         }
         return BPP_OK;
     });
@@ -215,12 +311,12 @@ extern "C" int bpp_debug_glv_op(bpp_ctx* ctx, int op, int window_bits, const uin
                 for (int j = 0; j < ROW; j++) out_layout[3 + j] = L.wc[j];
             }
             DevBuf din, dout;
-            if (int rc = upload(din, in, n * (GLV ? 4 : 8) * 4)) return rc;
+            HIPCHK(din.upload(in, n * (GLV ? 4 : 8) * 4));
             HIPCHK(dout.alloc(n * ROW * 4));
             if (n) {
                 hipLaunchKernelGGL((k_dbg_win_recode<NW, ROW>), dim3(cdiv(n, 64)), dim3(64), 0, nullptr, L, din.u32(), dout.u32(), n);
                 HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpy(out, dout.p, n * ROW * 4, hipMemcpyDeviceToHost));
+                HIPCHK(dout.download(out, n * ROW * 4));
             }
             return BPP_OK;
         } else if constexpr (!curve_has_glv<C>()) {
@@ -228,12 +324,12 @@ extern "C" int bpp_debug_glv_op(bpp_ctx* ctx, int op, int window_bits, const uin
         } else {
             if (op != 2 && C::ID != 0) return fail(BPP_E_ARG, "BLS12-381 only");
             DevBuf din, dout;
-            if (int rc = upload(din, in, n * 8 * 4)) return rc;
+            HIPCHK(din.upload(in, n * 8 * 4));
             HIPCHK(dout.alloc(n * GLV_SPLIT_OUT * 4));
             if (n) {
                 hipLaunchKernelGGL(k_dbg_glv_split<C>, dim3(cdiv(n, 64)), dim3(64), 0, nullptr, op, din.u32(), dout.u32(), n);
                 HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpy(out, dout.p, n * GLV_SPLIT_OUT * 4, hipMemcpyDeviceToHost));
+                HIPCHK(dout.download(out, n * GLV_SPLIT_OUT * 4));
             }
             return BPP_OK;
         }
@@ -270,20 +366,20 @@ extern "C" int bpp_debug_verifier_scalars(bpp_verifier* v, uint32_t m_view, cons
             const VerifyShape s = VerifyImpl<C>::class_shape(v, cls).s;
             const size_t ch_words = (size_t)(3 + s.k) * 8, out_bytes = count * (size_t)s.N * 32;
             DevBuf dps, dch, dprep, dout;
-            if (int rc = upload(dps, scalars3, count * 96)) return rc;
+            HIPCHK(dps.upload(scalars3, count * 96));
             if (challenges) {
-                if (int rc = upload(dch, challenges, count * ch_words * 4)) return rc;
+                HIPCHK(dch.upload(challenges, count * ch_words * 4));
             } else {
                 std::vector<uint32_t> lit;
                 default_challenges(s, lit);
-                if (int rc = upload(dch, lit.data(), lit.size() * 4)) return rc;
+                HIPCHK(dch.upload(lit.data(), lit.size() * 4));
             }
             HIPCHK(dprep.alloc(count * vs_prep_bytes<C>(s)));
             HIPCHK(dout.alloc(out_bytes));
             if (int rc = launch_verify_scalars<C>(s, dps.u32(), dch.u32(), challenges ? (uint32_t)ch_words : 0u, dout.u32(), count,
                                                   dprep.u32(), nullptr))
                 return rc;
-            HIPCHK(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+            HIPCHK(dout.download(out, out_bytes));
             return BPP_OK;
         });
     });
@@ -387,38 +483,36 @@ extern "C" int bpp_debug_scan_keys(bpp_verifier* v, uint32_t m_view, const uint6
             std::vector<uint32_t> rx(count * RX_WORDS, 0u);
             for (size_t i = 0; i < count; i++) rx[i * RX_WORDS + RX_CALLER] = caller ? caller[i] : (uint32_t)i;
             const std::vector<uint32_t> zeros(count, 0u);
-            DevBuf dsc, dch, drx, dst, dix, dco, dbad, dom, dos;
-            KeyUpload dk;
-            if (int rc = upload(dsc, scalars3, count * 96)) return rc;
-            if (int rc = upload(dch, challenges, count * (size_t)(3 + k) * 32)) return rc;
-            if (int rc = upload(drx, rx.data(), rx.size() * 4)) return rc;
-            if (int rc = upload(dst, status_in ? status_in : zeros.data(), count * 4)) return rc;
-            if (index)
-                if (int rc = upload(dix, index, total * 8)) return rc;
+            DevBuf dsc, dch, drx, dst, dix, dco, dbad, dom, dos, dk(true);   // dk: the keys, wiped before they are freed
+            HIPCHK(dsc.upload(scalars3, count * 96));
+            HIPCHK(dch.upload(challenges, count * (size_t)(3 + k) * 32));
+            HIPCHK(drx.upload(rx.data(), rx.size() * 4));
+            HIPCHK(dst.upload(status_in ? status_in : zeros.data(), count * 4));
+            HIPCHK(dix.upload(index, total * 8));   // null: no index
             HIPCHK(dco.alloc(count * ne * K::CW * 4));
             HIPCHK(dbad.alloc(count * 4));
             view.first = 0;
             view.count = count;
             view.pts = nullptr;
-            view.sc3 = static_cast<uint64_t*>(dsc.p);
-            view.challenges = static_cast<uint64_t*>(dch.p);
+            view.sc3 = dsc.u64();
+            view.challenges = dch.u64();
             if (n_keys) {
-                if (int rc = upload(dk.d, keys, n_keys * 32)) return rc;
-                if (int rc = upload(dom, out_masks, pairs * 32)) return rc;
-                if (int rc = upload(dos, out_status, pairs * 4)) return rc;
+                HIPCHK(dk.upload(keys, n_keys * 32));
+                HIPCHK(dom.upload(out_masks, pairs * 32));
+                HIPCHK(dos.upload(out_status, pairs * 4));
             }
-            ScanKeysJob j = K::call_job(static_cast<const uint8_t*>(dk.d.p), n_keys, index_base,
-                                        static_cast<const uint64_t*>(dix.p), dom.u32(), dos.u32(), total);
+            ScanKeysJob j = K::call_job(dk.u8(), n_keys, index_base,
+                                        dix.u64(), dom.u32(), dos.u32(), total);
             K::bind_class(view, drx.u32(), dst.u32(), dbad.u32(), dco.u32(), j);
             if (int rc = K::launch_coeffs(view, dco.u32(), dbad.u32(), nullptr)) return rc;
             if (n_keys)
                 if (int rc = K::launch_scan_keys(j, nullptr)) return rc;
             std::vector<uint32_t> co(count * ne * K::CW);
-            HIPCHK(hipMemcpy(co.data(), dco.p, co.size() * 4, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(out_bad, dbad.p, count * 4, hipMemcpyDeviceToHost));
+            HIPCHK(dco.download(co.data(), co.size() * 4));
+            HIPCHK(dbad.download(out_bad, count * 4));
             if (n_keys) {
-                HIPCHK(hipMemcpy(out_masks, dom.p, pairs * 32, hipMemcpyDeviceToHost));
-                HIPCHK(hipMemcpy(out_status, dos.p, pairs * 4, hipMemcpyDeviceToHost));
+                HIPCHK(dom.download(out_masks, pairs * 32));
+                HIPCHK(dos.download(out_status, pairs * 4));
             }
             uint32_t* oc = reinterpret_cast<uint32_t*>(out_coeffs);
             for (size_t i = 0; i < count * ne; i++) {

@@ -3,7 +3,7 @@
  * csrc/abi_guard.hpp built for the host (g++, under the sanitizers with BPP_HOST_SANITIZE=1): each kind of exception
    becomes its return code and text, a normal return passes through, a count of 2^32 or more is rejected.
  * capi.hip: every extern "C" definition routes its body through the guard or a guarded shim, except the few that cannot
-   throw, and none sets the device by hand.
+   throw, and none sets the device by hand.  It stages no buffer: the host forms do, through csrc/staging.hpp alone.
  * the ctypes binding (_lib.py) states every prototype of the header: arity, pointer or scalar, scalar width, return."""
 
 import ctypes
@@ -73,6 +73,37 @@ def test_every_entry_point_runs_under_the_guard():
         # before the shim only argument checks: nothing that can allocate, throw or reach the device
         head = body[:min(at)]
         assert not re.search(r"\bhip\w*\(|\bnew\b|std::|DevBuf|HIPCHK|\bImpl\b|Impl<", head), (name, head)
+
+
+CSRC = os.path.join(ROOT, "bulletproofsplus_amd", "csrc")
+
+
+def _csrc_sources():
+    """-> {file name: text} of the library's sources"""
+    return {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".hpp", ".h"))}
+
+
+def test_host_forms_stage_through_one_vocabulary():
+    src = _csrc_sources()
+    assert len(src) > 40 and "capi.hip" in src and "staging.hpp" in src
+    # capi.hip is the boundary: argument checks and shims, no buffer of its own
+    named = re.findall(r"DevBuf|hipMemcpy|hipMalloc|hipMemset", src["capi.hip"])
+    assert not named, ("capi.hip names", sorted(set(named)))
+    # one allocation site: DevBuf::alloc
+    sites = [(f, m.start()) for f, text in src.items() for m in re.finditer(r"hipMalloc\(", text)]
+    assert [f for f, _ in sites] == ["staging.hpp"], sites
+    text = src["staging.hpp"]
+    a = text.index("hipError_t alloc(size_t n) {")
+    assert a < sites[0][1] < text.index("}", a), "hipMalloc( outside DevBuf::alloc"
+    # no copy whose return code is thrown away
+    ignored = [(f, m.group(0)) for f, text in src.items() for m in re.finditer(r"\(void\)\s*hipMemcpy\w*", text)]
+    assert not ignored, ignored
+    # the debug kernels live in tu_debug.hip, not in the units of the hot MSM kernels
+    assert "k_dbg_" not in src["impl_msm.hpp"] and "k_dbg_field<" in src["tu_debug.hip"] and "k_dbg_point<" in src["tu_debug.hip"]
+    # the six copies of the staging rule are gone
+    for name in ("verify_staged", "prove_mixed_staged", "upload_optional", "KeyUpload", "wip_upload"):
+        assert not any(re.search(r"\b%s\b" % name, text) for text in src.values()), name
+    assert not re.search(r"\bint upload\(DevBuf", src["tu_debug.hip"])
 
 
 def _width(ct):

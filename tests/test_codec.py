@@ -155,3 +155,23 @@ def test_verify_serialized_proofs(cname):
     if not np.array_equal(nc, sc):
         assert eng.verify_compressed(enc, nc).tolist() == [2, 0, 0, 0]
         assert eng.verify_wire(recs, nc).tolist() == [0, 0, 0, 0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cname", ["bls12_381", "secp256k1"])
+def test_codec_host_forms_at_one_point_and_a_few(cname):
+    """bpp_points_compress / bpp_points_decompress on host pointers at n = 1 (a point, the point at infinity) and n = 5,
+    against pyref's encoder"""
+    need_gpu()
+    import bulletproofsplus_amd as B
+    curve, cid = CURVES[cname], O.CURVE_IDS[cname]
+    a = B.Arith.init(cname)
+    G = P.WeierstrassGroup(curve)
+    pts = [G.mul(G.base(), k) for k in (1, 2, 3, curve["r"] - 1)] + [None]
+    for sel in ([0], [4], [0, 1, 2, 3, 4]):
+        wire = O.points_to_wire(cid, [pts[i] for i in sel])
+        enc = B.compress_points(a, wire)
+        assert enc.shape == (len(sel), B.compressed_bytes(a))
+        assert [bytes(r) for r in enc] == [P.compress_point(curve, pts[i]) for i in sel], sel
+        back, ok = B.decompress_points(a, enc)
+        assert ok.tolist() == [0] * len(sel) and np.array_equal(back, wire), sel

@@ -386,6 +386,22 @@ def test_mirror_commitment_is_the_provers_point(cname):
     bv.close()
 
 
+@pytest.mark.parametrize("cname", ("bls12_381", "secp256k1", "ed25519"))
+def test_commit_host_twin_at_one_amount_and_a_few(cname):
+    """bpp_commit_batch on host pointers at count 1 and 5, with and without the flag, against the checker's v g + gamma h"""
+    need_gpu()
+    B, a, bv = _engine(cname, 8, 1)
+    cp = _corpus(cname, 8, 1)
+    vs, gs = [BIG, 5, (1 << 64) - 1, 0, 1 << 31], [cp.r - 3, 9, 77, 0, (cp.r - 1) // 2]
+    for count in (1, 5):
+        for amount64 in (False, True):
+            got = bv.commit_batch(vs[:count], gs[:count], amount64=amount64)
+            assert got.shape[0] == count
+            for j in range(count):
+                assert np.array_equal(got[j], _mul_add(cp, cp.gh, vs[j] if amount64 else _i32(vs[j]), gs[j])), (count, amount64, j)
+    bv.close()
+
+
 @pytest.mark.parametrize("cname", ("bls12_381", "secp256k1"))
 def test_single_call_takes_untruncated_commitments(cname):
     """RangeProof.prove with hand-made untruncated commitments: the first call with a key (no engine yet), the second (the

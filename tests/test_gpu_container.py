@@ -358,3 +358,28 @@ def test_container_mutations_statuses_match_restatement(cname, cid):
             assert got[i] == 1, (i, got[i])
     assert 10 < n_format < len(touched)        # both kinds occurred
     bv.close()
+
+
+@pytest.mark.parametrize("cname", ["bls12_381", "secp256k1", "ed25519"])
+def test_encode_decode_host_forms_at_one_proof_and_a_few(cname):
+    """bpp_proofs_encode_version / bpp_proofs_decode on host pointers at count = 1 and 5, (8, 2): the restatement's bytes,
+    proof by proof, and the way back"""
+    need_gpu()
+    import bulletproofsplus_amd as B
+    c = P.CURVES[cname]
+    n, m = 8, 2
+    a = B.Arith.init(cname)
+    bv = B.BatchVerifier(B.PublicKey.new(a, n * m), n, m, window_bits=4)
+    vals = [[9, 3], [255, 0], [1, 2], [200, 77], [0, 0]]
+    gams = [[5, 6], [7, 8], [9, 10], [11, 12], [13, 14]]
+    pts, scs, V = bv.prove_batch(vals, gams)
+    want = [P.encode_proof(c, n, m, P.prove_case(cname, n, v, g, shadow=False)[2]) for v, g in zip(vals, gams)]
+    for sel in ([0], [4], [0, 1, 2, 3, 4]):
+        blobs = B.encode_proofs(a, n, m, pts[sel], scs[sel])
+        assert blobs.shape == (len(sel), B.proof_bytes(a, n, m))
+        assert [bytes(b) for b in blobs] == [want[i] for i in sel], sel
+        dp, ds, st = B.decode_proofs(a, n, m, blobs)
+        assert st.tolist() == [0] * len(sel) and np.array_equal(ds, scs[sel]), sel
+        if cname != "ed25519":
+            assert np.array_equal(dp, pts[sel]), sel
+    bv.close()

@@ -199,6 +199,19 @@ def test_sealed_amounts(cname):
     bv.close()
 
 
+@pytest.mark.parametrize("count", (1, 5))
+def test_seal_host_twin_at_one_amount_and_a_few_with_and_without_the_index(count):
+    """bpp_amounts_seal on host pointers: the hashlib pad over index_base (index absent) and over an index list"""
+    need_gpu()
+    B, a, bv = TR._engine("secp256k1")
+    amounts = [(1 << 64) - 1, 0, 7, (1 << 31) + 5, 12345][:count]
+    index = [(1 << 63) + 9, 3, 0, (1 << 32) - 1, 77][:count]
+    base = (1 << 32) - 2
+    assert bv.seal_amounts(KEY, amounts, index_base=base).tolist() == FC.seal(KEY, amounts, range(base, base + count))
+    assert bv.seal_amounts(KEY, amounts, index=index).tolist() == FC.seal(KEY, amounts, index)
+    bv.close()
+
+
 # ---- order, boundaries and overflow --------------------------------------------------------------------------------------
 GRID_COUNT = 683   # 3 x 683 = 2049 pairs: eight compaction blocks of 256 and one pair more
 GRID_OWNED = {0: [0, 255, 256], 1: list(range(341, 597)), 2: [100, 682]}
@@ -379,6 +392,27 @@ def test_no_keys_is_still_a_verification(cname):
     torch.cuda.synchronize()
     assert d_ok.cpu().numpy().view(np.uint32).tolist() == blk["verdict"]
     assert d_n.cpu().numpy().view(np.uint32).tolist() == [0, GUARD]
+
+
+@pytest.mark.parametrize("cname", CURVES)
+def test_host_twin_at_one_proof_and_the_block_with_and_without_the_optional_inputs(cname):
+    """bpp_range_verify_find_serialized_mixed_keys on host pointers at one proof (owned, tampered, aggregated) and at the
+    block.  Present: keys, the index list, amounts in both forms, room for the hits -- the checker's verdicts and the hit
+    list ownership gives.  Absent: no keys, no index, no amounts, no hit buffer -- the same verdicts, nothing found."""
+    need_gpu()
+    blk = _block(cname, False, 1)
+    bv = blk["bv"]
+    for sel in ([OWN], [TAMPERED], [4], list(range(len(MS)))):
+        p_, c_, ms_ = b"".join(blk["pr"][j] for j in sel), b"".join(blk["cs"][j] for j in sel), [MS[j] for j in sel]
+        verdict = [blk["verdict"][j] for j in sel]
+        want = sorted((kn, sel.index(i), am, g) for kn, i, am, g in blk["hits"] if i in sel)
+        assert want or sel != [OWN]
+        for kw in (dict(amounts=[[blk["amounts"][j] for j in sel]] * len(KEYS)),
+                   dict(amounts=[blk["sealed"][j] for j in sel], sealed=True)):
+            ok, hits, found = bv.verify_find_serialized_mixed_keys(p_, c_, ms_, KEYS, index=[BASE + j for j in sel], **kw)
+            assert ok.tolist() == verdict and hits == want and found == len(want), (sel, kw.get("sealed"))
+        ok, hits, found = bv.verify_find_serialized_mixed_keys(p_, c_, ms_, (), index_base=BASE + sel[0], max_hits=0)
+        assert ok.tolist() == verdict and hits == [] and found == 0, sel
 
 
 def test_nothing_to_do_and_errors_that_need_an_engine():

@@ -361,6 +361,32 @@ def test_no_keys_is_still_a_verification(cname):
     assert ok.tolist() == [blk["verdict"][i] for i in agg] and hits == [] and found == 0 and n_cand == 0
 
 
+@pytest.mark.parametrize("cname", CURVES)
+def test_host_twin_at_one_proof_and_the_block_with_and_without_the_optional_inputs(cname):
+    """bpp_range_verify_find_tagged_serialized_mixed_keys on host pointers at one proof (owned, tampered, aggregated) and at
+    the block.  Present: keys, tags, the index list, amounts in both forms, room for the hits -- the checker's verdicts,
+    ownership's hits, hashlib's candidate count.  Absent keys (so no tags, no amounts, no index, no hit buffer are read):
+    the same verdicts, nothing found, no candidate."""
+    need_gpu()
+    blk = TF._block(cname, False, 1)
+    bv = blk["bv"]
+    tags = _maker_tags()
+    cands, _ = _tagged_hits(blk, KEYS, tags)
+    for sel in ([OWN], [TAMPERED], [4], list(range(len(MS)))):
+        p_, c_, ms_ = b"".join(blk["pr"][j] for j in sel), b"".join(blk["cs"][j] for j in sel), [MS[j] for j in sel]
+        verdict = [blk["verdict"][j] for j in sel]
+        want = sorted((kn, sel.index(i), am, g) for kn, i, am, g in blk["hits"] if i in sel)
+        n_want = len([1 for _, i in cands if i in sel])
+        for kw in (dict(amounts=[[blk["amounts"][j] for j in sel]] * len(KEYS)),
+                   dict(amounts=[blk["sealed"][j] for j in sel], sealed=True)):
+            ok, hits, found, n_cand = bv.verify_find_serialized_mixed_keys(p_, c_, ms_, KEYS, index=[BASE + j for j in sel],
+                                                                           tags=[tags[j] for j in sel], **kw)
+            assert ok.tolist() == verdict and hits == want and found == len(want) and n_cand == n_want, (sel, kw.get("sealed"))
+        ok, hits, found, n_cand = bv.verify_find_serialized_mixed_keys(p_, c_, ms_, (), index_base=BASE + sel[0], max_hits=0,
+                                                                       tags=[tags[j] for j in sel])
+        assert ok.tolist() == verdict and hits == [] and found == 0 and n_cand == 0, sel
+
+
 def test_nothing_to_do_and_errors_that_need_an_engine():
     """count = 0: BPP_OK, d_n_hits[0] = d_n_candidates[0] = 0 and nothing else written.  A workspace one byte short, an m_i
     above the engine's m: BPP_E_ARG, nothing enqueued, nothing written.  The size is the untagged one and the candidates'

@@ -469,3 +469,60 @@ def test_host_entries_and_wrappers_agree_with_the_device_entries(cname):
         ok = bv.verify_serialized_mixed(hraw, hcm, transcript=transcript)     # framed by proofs_scan
         assert set(ok.tolist()) == {0, 1}
     bv.close()
+
+
+@pytest.mark.parametrize("cname", CURVES)
+def test_host_twins_at_one_proof_and_the_block_against_the_oracle(cname):
+    """bpp_range_prove_batch_mixed / _serialized_mixed and the two mixed verify twins on host pointers, at one proof (m = 1,
+    m = 4) and at the block of mixed m_i.  Optional inputs absent: literal mode, no key, no challenges out -- the oracle's
+    proofs (pyref's on edwards25519) and their encoding byte for byte, the definition's verdicts.  Present (the Weierstrass
+    curves, where the C oracle proves under a transcript): the transcript, a blinding key at the caller's index, the
+    challenges out."""
+    need_gpu()
+    B, a, bv, cps = _setup(cname)
+    r = cps[CAP].r
+    vals, gams = _witness(MS, r)
+    ref = [cps[m].prove(vals[i], gams[i]) for i, m in enumerate(MS)]
+    enc = [VC.encode_case(cps[m], VC.Case("p", *ref[i]), 1) for i, m in enumerate(MS)]
+    want_ok = [cps[m].verdict(*ref[i]) for i, m in enumerate(MS)]
+    assert 0 in want_ok and 1 in want_ok
+    sels = ([0], [2], list(range(len(MS))))
+    assert MS[0] == 1 and MS[2] == 4
+    for sel in sels:
+        v_, g_, ms_ = [vals[i] for i in sel], [gams[i] for i in sel], [MS[i] for i in sel]
+        blob, comm = b"".join(enc[i][0] for i in sel), b"".join(enc[i][1] for i in sel)
+        hraw, hcm, hms = bv.prove_serialized_mixed(v_, g_)
+        assert bytes(hraw) == blob and bytes(hcm) == comm and hms.tolist() == ms_, sel
+        recs, hsc = bv.prove_batch_mixed(v_, g_)
+        for j, i in enumerate(sel):
+            assert np.array_equal(recs[j], np.concatenate([ref[i][0], ref[i][2]])) and np.array_equal(hsc[j], ref[i][1]), (sel, i)
+        exp = [want_ok[i] for i in sel]
+        assert bv.verify_wire_mixed([np.concatenate([ref[i][0], ref[i][2]]) for i in sel], np.stack([ref[i][1] for i in sel]),
+                                    ms_).tolist() == exp, sel
+        assert bv.verify_serialized_mixed(blob, comm, ms_).tolist() == exp, sel
+    if cname != "ed25519":
+        key = hashlib.sha256(b"host twins").digest()
+        base = (1 << 33) + 17
+        O.set_transcript(True)
+        try:
+            for sel in sels:
+                v_, g_, ms_ = [vals[i] for i in sel], [gams[i] for i in sel], [MS[i] for i in sel]
+                recs, hsc, hch = bv.prove_batch_mixed(v_, g_, transcript=True, blind_key=key, index_base=base + sel[0], challenges=True)
+                hraw, hcm, _ = bv.prove_serialized_mixed(v_, g_, transcript=True, blind_key=key, index_base=base + sel[0])
+                exp, blobs, comms = [], [], []
+                for j, i in enumerate(sel):
+                    m = MS[i]
+                    O.set_blinding(O.blinding_from_key(key, base + sel[0] + j, _k(m), r))
+                    opts, osc, oV = O.range_prove(cps[m].opk, N, vals[i], gams[i])
+                    assert np.array_equal(recs[j], np.concatenate([opts, oV])) and np.array_equal(hsc[j], osc), (sel, i)
+                    assert hch[j].shape == (3 + _k(m), 4)
+                    exp.append(int(O.range_verify(cps[m].opk, N, m, opts, osc, oV)))
+                    blob, comm = VC.encode_case(cps[m], VC.Case("p", opts, osc, oV), 1)
+                    blobs.append(blob)
+                    comms.append(comm)
+                assert bytes(hraw) == b"".join(blobs) and bytes(hcm) == b"".join(comms), sel
+                assert bv.verify_serialized_mixed(hraw, hcm, ms_, transcript=True).tolist() == exp, sel
+        finally:
+            O.set_blinding(None)
+            O.set_transcript(False)
+    bv.close()

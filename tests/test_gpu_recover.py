@@ -405,6 +405,46 @@ def test_scan_version_2_containers():
     bv.close()
 
 
+@pytest.mark.parametrize("cname", ("bls12_381", "secp256k1"))
+def test_host_twins_at_one_proof_and_a_small_block_with_and_without_the_optional_inputs(cname):
+    """bpp_range_recover_masks_mixed and bpp_range_scan_serialized_mixed on host pointers, at one proof and at a block of
+    mixed m_i: once with every optional input absent (literal challenges and blinding; no index, no amounts) and once with
+    them present (challenges, key and index list or a blinding buffer; amounts), against the checker's Gamma"""
+    need_gpu()
+    r = RC.ORDER[cname]
+    B, a, bv = _engine(cname)
+    # absent: the C oracle's reference-parity proofs
+    ms = [1, 4, 2, 1]
+    vals, gams = _inputs(cname, ms, N, 5900 + CID[cname])
+    proofs = [RC.oracle_proof(cname, N, v, g, False) for v, g in zip(vals, gams)]
+    gamma = [RC.gamma_of(r, g, p["ch"][1]) for p, g in zip(proofs, gams)]
+    raw = [B.encode_proofs(a, N, m, p["points"][None], p["scalars"][None]).tobytes() for m, p in zip(ms, proofs)]
+    cm = [B.compress_points(a, p["V"]).tobytes() for p in proofs]
+    for sel in ([0], [1], [0, 1, 2, 3]):
+        ms_s, want = [ms[i] for i in sel], [gamma[i] for i in sel]
+        assert bv.recover_masks(np.stack([proofs[i]["scalars"] for i in sel]), ms_s) == want, sel
+        st, got = bv.scan_serialized_mixed(b"".join(raw[i] for i in sel), b"".join(cm[i] for i in sel), ms_s)
+        assert st.tolist() == [3] * len(sel) and got == want, sel
+    # present, recovery: the transcript's challenges with the key and an index list, and with a blinding buffer
+    made = _made(cname)
+    want = [RC.gamma_of(r, g, ch[1]) for _, _, ch, _, g in made]
+    for sel in ([0], [3], [3, 0, 4, 1, 2]):
+        sc = O.scalars_to_wire([x for j in sel for x in made[j][1]]).reshape(-1, 3, 4)
+        ms_s, blocks = [MS[j] for j in sel], [O.scalars_to_wire(made[j][2]) for j in sel]
+        assert bv.recover_masks(sc, ms_s, blocks, blind_key=KEY, index=[BASE + j for j in sel]) == [want[j] for j in sel], sel
+        assert bv.recover_masks(sc, ms_s, blocks, blinding=[made[j][3] for j in sel]) == [want[j] for j in sel], sel
+    bv.close()
+    # present, scan: transcript, key, index list and candidate amounts
+    B, bv, raw, cm, amounts, status, masks, _ = _scan_block(cname, False, 1)
+    pr, cs = _split_bytes(B, bv.arith, raw, cm, SCAN_MS, 1)
+    for sel in ([OWN], [WRONG], [5, 0, 6, 3, 1, 4, 2]):
+        st, got = bv.scan_serialized_mixed(b"".join(pr[j] for j in sel), b"".join(cs[j] for j in sel), [SCAN_MS[j] for j in sel],
+                                           transcript=True, blind_key=KEY, index=[BASE + j for j in sel],
+                                           amounts=[amounts[j] for j in sel])
+        assert st.tolist() == [status[j] for j in sel] and got == [masks[j] for j in sel], sel
+    bv.close()
+
+
 def test_errors_that_need_an_engine():
     """an m_i above the engine's m (the text names i), a workspace smaller than the layout: BPP_E_ARG, nothing written"""
     torch = need_gpu()

@@ -200,6 +200,26 @@ def test_largest_slot_count():
     bv.close()
 
 
+@pytest.mark.parametrize("cname", CURVES)
+def test_host_twin_at_one_proof_and_the_block_with_and_without_index_and_amounts(cname):
+    """bpp_range_scan_serialized_mixed_keys on host pointers at one proof (a single output, an aggregated one) and at the
+    block: with the index list and the candidate amounts present, and with both absent (index_base alone: Gamma of every
+    pair, nothing confirmed) -- against the block's big-integer statuses and masks"""
+    need_gpu()
+    blk = _block(cname, False, 1)
+    bv, raw, cm = blk["bv"], blk["raw"], blk["cm"]
+    pr, cs = TR._split_bytes(blk["B"], bv.arith, raw, cm, SCAN_MS, 1)
+    for sel in ([OWN], [4], list(range(len(SCAN_MS)))):
+        p_, c_, ms_ = b"".join(pr[j] for j in sel), b"".join(cs[j] for j in sel), [SCAN_MS[j] for j in sel]
+        st, got = bv.scan_serialized_mixed_keys(p_, c_, ms_, KEYS, index=[BASE + j for j in sel],
+                                                amounts=[[blk["amounts"][j] for j in sel]] * len(KEYS))
+        assert st.tolist() == [[row[j] for j in sel] for row in blk["status"]], sel
+        assert got == [[row[j] for j in sel] for row in blk["masks"]], sel
+        st, got = bv.scan_serialized_mixed_keys(p_, c_, ms_, KEYS, index_base=BASE + sel[0])
+        assert st.tolist() == [[2 if j == DAMAGED else 3 for j in sel]] * len(KEYS), sel
+        assert got == [[0 if j == DAMAGED else row[j] for j in sel] for row in blk["gamma"]], sel
+
+
 def test_version_2_containers():
     need_gpu()
     blk = _block("bls12_381", True, 2)

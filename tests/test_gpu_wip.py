@@ -199,6 +199,61 @@ def test_transcript_continues_the_callers_state():
     assert ok.tolist() == [1, 1, 1]
 
 
+# ---- 3b. the host forms, with every optional buffer absent and with every one present ----------------------------------
+@pytest.mark.parametrize("count", [1, 3])
+def test_host_forms_with_and_without_the_optional_buffers(count):
+    """bpp_wip_prove_batch / bpp_wip_verify_batch (host pointers) at one proof and at a small block: first with no
+    transcript, no challenges and no optional output, then with all of them -- the prover against pyref, the verifier
+    against the verdicts pyref's proofs deserve and, in addition, against the device entry's scalars and sums"""
+    import ctypes
+    from bulletproofsplus_amd import _lib
+    torch = need_gpu()
+    cx = Ctx("secp256k1", 8, 1, 5)
+    nv, k = 1, cx.k
+    cases = [W.random_case(cx.pk, nv, 40 + i) for i in range(count)]
+    a, b, y, g = [c.a for c in cases], [c.b for c in cases], [c.y for c in cases], [c.gamma for c in cases]
+    stm = [c.statement() for c in cases]
+    mine = np.stack([np.concatenate([cx.wire([c.A_prime]), np.zeros((2 + 2 * k, cx.PW), np.uint64), cx.wire(c.V)]) for c in cases])
+
+    # absent: the literal challenges, verdicts alone
+    rec, sc, ch = cx.bv.wip_prove_batch(a, b, y, g, nv, points=mine)
+    for i, c in enumerate(cases):
+        pf = c.prove()
+        assert np.array_equal(rec[i, 1:3 + 2 * k], cx.wire([pf.A, pf.B] + list(pf.L_vec) + list(pf.R_vec))), i
+        assert O.wire_to_scalars(sc[i]) == [pf.r_prime, pf.s_prime, pf.d_prime], i
+        assert O.wire_to_scalars(ch[i]) == [99] + [7] * k
+    assert np.array_equal(rec[:, 0], mine[:, 0]) and np.array_equal(rec[:, 3 + 2 * k:], mine[:, 3 + 2 * k:])
+    # ... and without the challenges coming back (the wrapper always asks for them)
+    vp = lambda x: ctypes.c_void_p(x.ctypes.data)
+    av, bw = _rows_wire(a), _rows_wire(b)
+    yv, gv = O.scalars_to_wire(y), O.scalars_to_wire(g)
+    rec_raw, sc_raw = mine.copy(), np.zeros_like(sc)
+    assert _lib.lib().bpp_wip_prove_batch(cx.bv.handle, vp(av), vp(bw), vp(yv), vp(gv), count, nv, 0, None, None, 0, None,
+                                          vp(rec_raw), vp(sc_raw), None) == 0
+    assert np.array_equal(rec_raw, rec) and np.array_equal(sc_raw, sc)
+    assert cx.bv.wip_verify_batch(rec, sc, y, stm, nv).tolist() == [0] * count
+    bad = sc.copy()
+    bad[count - 1, 1, 0] ^= 1
+    assert cx.bv.wip_verify_batch(rec, bad, y, stm, nv).tolist() == [0] * (count - 1) + [1]
+
+    # present: the caller's transcript, the challenges out; the MulVec scalars and the sums out of the verifier
+    states = [hashlib.sha256(b"host form %d" % i).digest() for i in range(count)]
+    tr = np.frombuffer(b"".join(states), dtype=np.uint8).reshape(count, 32)
+    rec, sc, ch = cx.bv.wip_prove_batch(a, b, y, g, nv, points=mine, transcript=tr)
+    for i, c in enumerate(cases):
+        pf, es = _pyref_fs_prove(cx, c, states[i])
+        assert np.array_equal(rec[i, 1:3 + 2 * k], cx.wire([pf.A, pf.B] + list(pf.L_vec) + list(pf.R_vec))), i
+        assert O.wire_to_scalars(sc[i]) == [pf.r_prime, pf.s_prime, pf.d_prime], i
+        assert O.wire_to_scalars(ch[i]) == es, i
+    ok, osc, ores = cx.bv.wip_verify_batch(rec, sc, y, stm, nv, transcript=tr, want_scalars=True, want_result=True)
+    dok, dsc, dres = _verify_device(torch, cx, rec, sc, y, stm, nv, transcript=states)
+    assert ok.tolist() == dok.tolist() == [0] * count
+    assert np.array_equal(osc, dsc.reshape(osc.shape)) and np.array_equal(ores, dres.reshape(ores.shape))
+    assert all(O.wire_to_point(cx.cid, ores[i]) is None for i in range(count))       # an accepted proof sums to the identity
+    assert cx.bv.wip_verify_batch(rec, sc, y, stm, nv, challenges=[O.wire_to_scalars(c) for c in ch]).tolist() == [0] * count
+    assert cx.bv.wip_verify_batch(rec, sc, y, stm, nv).tolist() == [1] * count       # the literals are not these challenges
+
+
 # ---- 4. blinding -------------------------------------------------------------------------------------------------------
 def _with_blinding(bl, k, f):
     T = P.Transcript
