@@ -805,6 +805,97 @@ impl BatchVerifier {
             .collect();
         Ok((ok, hits, found as usize, candidates as usize))
     }
+    /// The sender's side of outputs with derived masks (include/bpp_amd.h: bpp_outputs_make): one recipient key and one
+    /// amount per OUTPUT, ms[i] outputs in proof i, whose blinding index is index[i] or index_base + i.  Result: the masks
+    /// (the gamma of the commit and prove calls; secret), the sealed amounts and the tags, one per output.
+    pub fn make_outputs(&self, keys: &[[u8; 32]], amounts: &[u64], ms: &[u32], index_base: u64, index: Option<&[u64]>)
+                        -> Result<(Vec<PrimeFieldElem>, Vec<u64>, Vec<u8>), ProofError> {
+        let n_out: usize = ms.iter().map(|&m| m as usize).sum();
+        if keys.len() != n_out || amounts.len() != n_out || index.map_or(false, |x| x.len() != ms.len())
+            || n_out > 0x7fff_ffff / 64 {
+            return Err(ProofError::FormatError);
+        }
+        if n_out == 0 {
+            return Ok((Vec::new(), Vec::new(), Vec::new()));
+        }
+        let (mut idx, mut place) = (Vec::with_capacity(n_out), Vec::with_capacity(n_out));
+        for (i, &m) in ms.iter().enumerate() {
+            for j in 0..m {
+                idx.push(index.map_or(index_base.wrapping_add(i as u64), |x| x[i]));
+                place.push(j);
+            }
+        }
+        let mut packed: Vec<u8> = keys.iter().flat_map(|k| k.iter().copied()).collect();
+        let mut masks = vec![0u64; n_out * 4];
+        let mut sealed = vec![0u64; n_out];
+        let mut tags = vec![0u8; n_out];
+        let rc = unsafe {
+            ffi::bpp_outputs_make(ctx(), packed.as_ptr(), idx.as_ptr(), place.as_ptr(), amounts.as_ptr(), n_out, masks.as_mut_ptr(),
+                                  sealed.as_mut_ptr(), tags.as_mut_ptr())
+        };
+        for b in packed.iter_mut() {
+            unsafe { std::ptr::write_volatile(b, 0) };   // the packed copy of the keys made here
+        }
+        assert!(rc == 0, "bpp_outputs_make: {}", rc);
+        Ok((masks.chunks(4).map(|w| PrimeFieldElem([w[0], w[1], w[2], w[3]])).collect(), sealed, tags))
+    }
+    /// Verifies a block and lists, per OUTPUT, what belongs to the keys, aggregated proofs included (include/bpp_amd.h:
+    /// bpp_range_verify_find_outputs_serialized_mixed_keys): `sealed` and `tags` hold one entry per output (the sum of
+    /// `ms`), in caller order, shared by all keys.  Result: the verdicts, the hits as (key number, output number, amount,
+    /// mask), the hits found and the pairs that passed the tag test.
+    pub fn verify_find_outputs_serialized_mixed_keys(&self, proofs: &[u8], commitments: &[u8], ms: &[u32], amount64: bool,
+                                                     keys: &[[u8; 32]], index_base: u64, index: Option<&[u64]>, sealed: &[u64],
+                                                     tags: &[u8], max_hits: usize)
+                                                     -> Result<(Vec<u32>, Vec<(u32, u32, u64, PrimeFieldElem)>, usize, usize), ProofError> {
+        let n = 1usize << (self.k - self.m.trailing_zeros() as usize);
+        let cb = unsafe { ffi::bpp_point_compressed_bytes(ffi::BPP_BLS12_381_G1) };
+        let (mut pbytes, mut cbytes, mut n_out) = (0usize, 0usize, 0usize);
+        for &mi in ms {
+            let mi = mi as usize;
+            if mi == 0 || !mi.is_power_of_two() || mi > self.m {
+                return Err(ProofError::FormatError);
+            }
+            pbytes += unsafe { ffi::bpp_proof_bytes(ffi::BPP_BLS12_381_G1, n, mi) };
+            cbytes += mi * cb;
+            n_out += mi;
+        }
+        let pairs = match keys.len().checked_mul(n_out) {
+            Some(p) if p <= (0x7fff_ffff / 64) => p,
+            _ => return Err(ProofError::FormatError),
+        };
+        if pbytes != proofs.len() || cbytes != commitments.len() || index.map_or(false, |x| x.len() != ms.len())
+            || sealed.len() != n_out || tags.len() != n_out {
+            return Err(ProofError::FormatError);
+        }
+        if ms.is_empty() {
+            return Ok((Vec::new(), Vec::new(), 0, 0));
+        }
+        let flags = ffi::BPP_SER_TRANSCRIPT | if amount64 { ffi::BPP_PROVE_AMOUNT64 } else { 0 };
+        let cap = max_hits.min(pairs);
+        let mut packed: Vec<u8> = keys.iter().flat_map(|k| k.iter().copied()).collect();
+        let mut ok = vec![0u32; ms.len()];
+        let mut rec = vec![0u32; cap * 12];
+        let (mut found, mut candidates) = (0u32, 0u32);
+        let rc = unsafe {
+            ffi::bpp_range_verify_find_outputs_serialized_mixed_keys(self.handle, proofs.as_ptr(), commitments.as_ptr(), ms.as_ptr(),
+                                                                     ms.len(), flags, packed.as_ptr(), keys.len(), index_base,
+                                                                     index.map_or(std::ptr::null(), |x| x.as_ptr()), sealed.as_ptr(),
+                                                                     tags.as_ptr(), ok.as_mut_ptr(),
+                                                                     if cap > 0 { rec.as_mut_ptr() } else { std::ptr::null_mut() },
+                                                                     cap, &mut found, &mut candidates)
+        };
+        for b in packed.iter_mut() {
+            unsafe { std::ptr::write_volatile(b, 0) };   // the packed copy of the keys made here
+        }
+        assert!(rc == 0, "bpp_range_verify_find_outputs_serialized_mixed_keys: {}", rc);
+        let hits = rec.chunks(12).take((found as usize).min(cap))
+            .map(|h| {
+                let w = |t: usize| h[4 + 2 * t] as u64 | (h[5 + 2 * t] as u64) << 32;
+                (h[0], h[1], h[2] as u64 | (h[3] as u64) << 32, PrimeFieldElem([w(0), w(1), w(2), w(3)]))
+            })
+            .collect();
+        Ok((ok, hits, found as usize, candidates as usize))
+    }
 }
 
 /// The cuts of a batch over `world` shards (include/bpp_amd.h: bpp_shard_cuts): shard r takes proofs

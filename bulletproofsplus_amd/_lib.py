@@ -62,6 +62,9 @@ EXPORTS = [
     "bpp_view_tags_device", "bpp_view_tags",
     "bpp_verify_find_tagged_workspace_bytes", "bpp_range_verify_find_tagged_serialized_mixed_keys_device",
     "bpp_range_verify_find_tagged_serialized_mixed_keys",
+    "bpp_outputs_make_device", "bpp_outputs_make",
+    "bpp_verify_find_outputs_workspace_bytes", "bpp_range_verify_find_outputs_serialized_mixed_keys_device",
+    "bpp_range_verify_find_outputs_serialized_mixed_keys",
     "bpp_wip_prover_workspace_bytes", "bpp_wip_prove_batch_device", "bpp_wip_verifier_workspace_bytes",
     "bpp_wip_verify_batch_device", "bpp_wip_prove_batch", "bpp_wip_verify_batch",
     "bpp_shard_cuts", "bpp_pool_create", "bpp_pool_destroy", "bpp_pool_size", "bpp_pool_device", "bpp_pool_verifier",
@@ -227,6 +230,14 @@ def lib():
                                                                                 vp, sz, vp, vp, vp, vp, sz, vp]
         L.bpp_range_verify_find_tagged_serialized_mixed_keys.argtypes = [vp, vp, vp, vp, sz, i32, vp, sz, u64, vp, vp, vp, vp, sz,
                                                                          vp, vp, vp]
+        L.bpp_outputs_make_device.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, vp]
+        L.bpp_outputs_make.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp]
+        L.bpp_verify_find_outputs_workspace_bytes.argtypes = [vp, vp, sz, sz]
+        L.bpp_verify_find_outputs_workspace_bytes.restype = sz
+        L.bpp_range_verify_find_outputs_serialized_mixed_keys_device.argtypes = [vp, vp, vp, vp, sz, i32, vp, sz, u64, vp, vp, vp,
+                                                                                 vp, vp, sz, vp, vp, vp, sz, vp]
+        L.bpp_range_verify_find_outputs_serialized_mixed_keys.argtypes = [vp, vp, vp, vp, sz, i32, vp, sz, u64, vp, vp, vp, vp,
+                                                                          vp, sz, vp, vp]
         L.bpp_proofs_scan.argtypes = [i32, sz, i32, vp, sz, vp, sz, vp]
         L.bpp_wip_prover_workspace_bytes.argtypes = [vp, sz]
         L.bpp_wip_prover_workspace_bytes.restype = sz

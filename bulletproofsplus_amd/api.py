@@ -1595,6 +1595,134 @@ class BatchVerifier:
         hits = [(int(r[0]), int(r[1]), int(r[2]) | int(r[3]) << 32, wire_to_int(np.ascontiguousarray(r[4:]).view(np.uint64))) for r in rec[:min(n, cap)]]
         return (ok, hits, n) if tg is None else (ok, hits, n, int(cands[0]))
 
+    # ---- outputs with masks derived from their recipients' keys, aggregated proofs included (include/bpp_amd.h) ----
+    def make_outputs_device(self, d_keys: int, d_index: int, d_j: int, d_amounts: int, n_out: int, d_out_masks: int = 0,
+                            d_out_sealed: int = 0, d_out_tags: int = 0, stream: int = 0):
+        """The sender's call over n_out resident outputs (bpp_outputs_make_device): d_keys n_out x 32 bytes (the recipient's
+        key of each), d_index n_out u64 (the blinding index of the output's proof), d_j n_out u32 (its place in the proof),
+        d_amounts n_out u64 -> d_out_masks n_out x 4 u64 (the d_gamma layout of commit_batch_device and the mixed prove
+        calls), d_out_sealed n_out u64, d_out_tags n_out bytes; each output may be 0 and is then skipped.  Only enqueues."""
+        check(_lib.lib().bpp_outputs_make_device(self.arith.handle, d_keys or None, d_index or None, d_j or None, d_amounts or None,
+                                                 n_out, d_out_masks or None, d_out_sealed or None, d_out_tags or None,
+                                                 stream or None), "bpp_outputs_make_device")
+
+    def make_outputs(self, keys, amounts, ms, index_base: int = 0, index=None):
+        """keys: one 32-byte recipient key per OUTPUT; amounts: one int below 2^64 per output; ms: the outputs per proof, in
+        order (sum(ms) outputs); index: None or one blinding index per PROOF -> (masks (n_out, 4) u64, sealed (n_out,) u64,
+        tags (n_out,) u8): output j of proof i under output_mask / output_pad / output_tag(key, index of i, j)
+        (bpp_outputs_make).  The masks are secret."""
+        m = [int(x) for x in ms]
+        keys = [bytes(k) for k in keys]
+        if any(len(k) != 32 for k in keys):
+            raise RuntimeError("make_outputs: every key is 32 bytes")
+        am = np.ascontiguousarray(np.asarray([int(x) for x in amounts], dtype=np.uint64))
+        n_out = sum(m)
+        if len(keys) != n_out or len(am) != n_out:
+            raise RuntimeError("make_outputs: one key and one amount per output, sum(ms) of them")
+        if index is not None:
+            pidx = np.asarray([int(x) for x in index], dtype=np.uint64)
+            if len(pidx) != len(m):
+                raise RuntimeError("make_outputs: one blinding index per proof")
+        else:
+            pidx = np.uint64(index_base) + np.arange(len(m), dtype=np.uint64)
+        reps = np.asarray(m, dtype=np.int64)
+        idx = np.ascontiguousarray(np.repeat(pidx, reps))
+        first = np.repeat(np.cumsum(reps) - reps, reps)
+        j = np.ascontiguousarray((np.arange(n_out, dtype=np.int64) - first).astype(np.uint32))
+        kb = np.frombuffer(b"".join(keys), dtype=np.uint8).copy() if n_out else None
+        masks = np.zeros((n_out, 4), dtype=np.uint64)
+        sealed = np.zeros(n_out, dtype=np.uint64)
+        tags = np.zeros(n_out, dtype=np.uint8)
+        if n_out:
+            check(_lib.lib().bpp_outputs_make(self.arith.handle, _ptr(kb), _ptr(idx), _ptr(j), _ptr(am), n_out, _ptr(masks),
+                                              _ptr(sealed), _ptr(tags)), "bpp_outputs_make")
+            kb[:] = 0   # the packed copy of the keys made here
+        return masks, sealed, tags
+
+    def verify_find_outputs_workspace_bytes(self, ms, n_keys: int) -> int:
+        """bytes of device workspace verify_find_outputs_serialized_mixed_keys_device needs (0: an m_i is not taken, or
+        n_keys x sum(ms) is over the bound)"""
+        m = self._ms(ms)
+        return _lib.lib().bpp_verify_find_outputs_workspace_bytes(self.handle, _ptr(m) if len(m) else None, len(m), n_keys)
+
+    def verify_find_outputs_serialized_mixed_keys_device(self, d_proofs: int, d_commitments: int, ms, d_keys: int, n_keys: int,
+                                                         d_sealed: int, d_tags: int, d_ok: int, d_hits: int, max_hits: int,
+                                                         d_n_hits: int, d_workspace: int, workspace_bytes: int, stream: int = 0,
+                                                         uncompressed: bool = False, amount64: bool = False, index_base: int = 0,
+                                                         d_index: int = 0, d_n_candidates: int = 0):
+        """Verifies a resident block (d_ok: verify_serialized_mixed_device's words under the transcript) and lists, per
+        OUTPUT, what belongs to the n_keys view keys at d_keys, aggregated proofs included.  d_sealed: sum(ms) u64 and
+        d_tags: sum(ms) bytes, per output in caller order, shared by all keys.  d_hits: max_hits records of 12 u32 [key
+        number, output number, amount lo, hi, mask as 8 words] in ascending (key number, output number); d_n_hits: one u32,
+        the hits found; d_n_candidates: 0 or one u32, the pairs that passed the tag test
+        (bpp_range_verify_find_outputs_serialized_mixed_keys_device)."""
+        m = self._ms(ms)
+        check(_lib.lib().bpp_range_verify_find_outputs_serialized_mixed_keys_device(
+            self.handle, d_proofs, d_commitments, _ptr(m) if len(m) else None, len(m),
+            1 | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0), d_keys or None, n_keys, ctypes.c_uint64(index_base),
+            d_index or None, d_sealed or None, d_tags or None, d_ok or None, d_hits or None, max_hits, d_n_hits or None,
+            d_n_candidates or None, d_workspace, workspace_bytes, stream or None),
+            "bpp_range_verify_find_outputs_serialized_mixed_keys_device")
+
+    def verify_find_outputs_serialized_mixed_keys(self, proofs, commitments, ms=None, keys=(), sealed=(), tags=(),
+                                                  uncompressed: bool = False, amount64: bool = False, index_base: int = 0,
+                                                  index=None, max_hits: int = None):
+        """proofs, commitments, ms, keys, index: as verify_find_serialized_mixed_keys; sealed, tags: one sealed amount and
+        one tag byte per OUTPUT (sum(ms) of each), in caller order -> (ok (count,) u32, hits, found, n_candidates): ok as
+        verify_serialized_mixed under the transcript; hits the list of (key_no, output_no, amount, mask) in ascending
+        (key_no, output_no), at most max_hits of them (None: room for every pair); found the number of hits there are;
+        n_candidates the pairs that passed the tag test (bpp_range_verify_find_outputs_serialized_mixed_keys).  With no
+        keys the block is verified all the same and no hit is listed."""
+        def flat(x):
+            return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
+        raw, cm = flat(proofs), flat(commitments)
+        version = 2 if uncompressed else 1
+        m = proofs_scan(self.arith, self.n, raw, version) if ms is None else self._ms(ms)
+        count = len(m)
+        n_out = int(m.sum()) if count else 0
+        keys = [bytes(k) for k in keys]
+        if any(len(k) != 32 for k in keys):
+            raise RuntimeError("verify_find_outputs_serialized_mixed_keys: every key is 32 bytes")
+        nk = len(keys)
+        if all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m):
+            pb = uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)
+            need = sum(proof_bytes(self.arith, self.n, int(x), version) for x in m)
+            if len(raw) != need:
+                raise RuntimeError("verify_find_outputs_serialized_mixed_keys: %d bytes of proofs, the shapes in ms need %d"
+                                   % (len(raw), need))
+            if len(cm) != n_out * pb:
+                raise RuntimeError("verify_find_outputs_serialized_mixed_keys: ms[i] commitments per proof")
+        idx = None
+        if index is not None:
+            idx = np.ascontiguousarray(np.asarray([int(x) for x in index], dtype=np.uint64))
+            if len(idx) != count:
+                raise RuntimeError("verify_find_outputs_serialized_mixed_keys: one blinding index per proof")
+        se = np.ascontiguousarray(np.asarray([int(x) for x in sealed], dtype=np.uint64).reshape(-1))
+        tg = flat(tags) if isinstance(tags, (bytes, bytearray, memoryview)) else \
+            np.ascontiguousarray(np.asarray([int(x) for x in tags], dtype=np.uint8).reshape(-1))
+        if nk and (len(se) != n_out or len(tg) != n_out):
+            raise RuntimeError("verify_find_outputs_serialized_mixed_keys: one sealed amount and one tag per output")
+        cap = nk * n_out if max_hits is None else int(max_hits)
+        kb = np.frombuffer(b"".join(keys), dtype=np.uint8).copy() if nk else None
+        ok = np.zeros(count, dtype=np.uint32)
+        rec = np.zeros((cap, 12), dtype=np.uint32)
+        found = np.zeros(1, dtype=np.uint32)
+        cands = np.zeros(1, dtype=np.uint32)
+        some = nk > 0 and count > 0
+        check(_lib.lib().bpp_range_verify_find_outputs_serialized_mixed_keys(
+            self.handle, _ptr(raw) if len(raw) else None, _ptr(cm) if len(cm) else None, _ptr(m) if count else None, count,
+            1 | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0), _ptr(kb) if kb is not None else None, nk,
+            ctypes.c_uint64(index_base), _ptr(idx) if idx is not None else None, _ptr(se) if some else None,
+            _ptr(tg) if some else None, _ptr(ok) if count else None, _ptr(rec) if cap else None, cap, _ptr(found), _ptr(cands)),
+            "bpp_range_verify_find_outputs_serialized_mixed_keys")
+        if kb is not None:
+            kb[:] = 0   # the packed copy of the keys made here
+        n = int(found[0])
+        hits = [(int(r[0]), int(r[1]), int(r[2]) | int(r[3]) << 32, wire_to_int(np.ascontiguousarray(r[4:]).view(np.uint64)))
+                for r in rec[:min(n, cap)]]
+        return ok, hits, n, int(cands[0])
+
 
 def shard_cuts(ms, count: int, world: int) -> np.ndarray:
     """bpp_shard_cuts: the world + 1 cuts of a batch of `count` proofs over `world` shards, shard r taking proofs

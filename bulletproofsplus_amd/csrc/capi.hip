@@ -13,6 +13,7 @@
 #include "literal.hpp"
 #include "recover.hpp"
 #include "find.hpp"
+#include "outputs.hpp"
 #include "recover_keys.hpp"
 
 using namespace bpp;
@@ -1319,6 +1320,117 @@ extern "C" int bpp_range_verify_find_tagged_serialized_mixed_keys(
     if (count == 0) return find_nothing(v, a, false, nullptr);
     if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int { return FindImpl<decltype(cv)>::find_host(v, a); });
+}
+
+// ---- outputs with masks derived from their recipients' keys: making them, and verifying a block while listing each
+// key's outputs, aggregated proofs included (outputs.hpp) ----
+namespace {
+// n_keys x n_out (n_out = sum m_i) within the bound the other entries put on n_keys x count, without a sum or a product
+// that can wrap; m_of is read only once count itself is within the bound
+bool out_pairs_bounded(const uint32_t* m_of, size_t count, size_t n_keys) noexcept {
+    const size_t bound = 0x7fffffffu / 64;
+    if (n_keys > bound || count > bound) return false;
+    size_t n_out = 0;
+    for (size_t i = 0; i < count; i++) {
+        n_out += m_of[i];   // each below 2^32, the sum so far at most the bound
+        if (n_out > bound) return false;
+    }
+    return n_keys == 0 || n_out <= bound / n_keys;
+}
+
+// the checks of the receiver's two entries; count = 0 passes them and is answered by find_nothing
+int outputs_args(const bpp_verifier* v, int flags, OutputsArgs& a, bool device, const void* d_workspace) noexcept {
+    if (!v || !a.n_hits) return fail(BPP_E_ARG, "null argument");
+    if (flags & BPP_FIND_AMOUNTS_SEALED) return fail(BPP_E_ARG, "BPP_FIND_AMOUNTS_SEALED is not taken: amounts are always sealed here");
+    if (flags & ~SCAN_FLAGS) return fail(BPP_E_ARG, "unknown flag");
+    a.version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
+    a.amount64 = (flags & BPP_PROVE_AMOUNT64) != 0;
+    if (a.count == 0) return BPP_OK;
+    if (!a.proofs || !a.commitments || !a.m_of || !a.ok || (device && !d_workspace)) return fail(BPP_E_ARG, "null argument");
+    if (a.n_keys && (!a.keys || !a.sealed || !a.tags || (!a.hits && a.max_hits))) return fail(BPP_E_ARG, "null argument");
+    if (device && a.n_keys && (reinterpret_cast<uintptr_t>(a.keys) & 3)) return fail(BPP_E_ARG, "d_keys must be 4-byte aligned");
+    return guarded([&]() -> int {
+        if (!out_pairs_bounded(a.m_of, a.count, a.n_keys)) return fail(BPP_E_ARG, "n_keys x n_out too large for one launch");
+        for (size_t i = 0; i < a.count; i++)
+            if (a.m_of[i] == 0 || (a.m_of[i] & (a.m_of[i] - 1)))
+                return fail(BPP_E_ARG, "m_of[" + std::to_string(i) + "] = " + std::to_string(a.m_of[i]) + ": not a power of two");
+        if (!(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, "the verdicts need BPP_SER_TRANSCRIPT");
+        return BPP_OK;
+    });
+}
+
+// what find_nothing reads of a find call: where the two counts go
+FindArgs counts_only(uint32_t* n_hits, uint32_t* n_candidates) noexcept {
+    FindArgs a = {};
+    a.n_hits = n_hits;
+    a.n_candidates = n_candidates;
+    return a;
+}
+
+// the checks of the sender's two entries; n_out = 0 passes them and is answered by the entry
+int outputs_make_args(const bpp_ctx* ctx, const void* keys, const void* index, const void* j, const void* amounts, size_t n_out,
+                      const void* out_masks, const void* out_sealed, const void* out_tags, bool device) noexcept {
+    if (!ctx) return fail(BPP_E_ARG, "null argument");
+    if (!out_masks && !out_sealed && !out_tags) return fail(BPP_E_ARG, "null argument: nothing to make");
+    if (n_out == 0) return BPP_OK;
+    if (!keys || !index || !j || !amounts) return fail(BPP_E_ARG, "null argument");
+    if (device && (reinterpret_cast<uintptr_t>(keys) & 3)) return fail(BPP_E_ARG, "d_keys must be 4-byte aligned");
+    if (n_out > 0x7fffffffu / 64) return fail(BPP_E_ARG, "n_out too large for one launch");
+    return BPP_OK;
+}
+}  // namespace
+
+extern "C" int bpp_outputs_make_device(bpp_ctx* ctx, const uint8_t* d_keys, const uint64_t* d_index, const uint32_t* d_j,
+                                       const uint64_t* d_amounts, size_t n_out, uint64_t* d_out_masks, uint64_t* d_out_sealed,
+                                       uint8_t* d_out_tags, void* stream) {
+    if (int rc = outputs_make_args(ctx, d_keys, d_index, d_j, d_amounts, n_out, d_out_masks, d_out_sealed, d_out_tags, true)) return rc;
+    if (n_out == 0) return BPP_OK;
+    return on_ctx(*ctx, {n_out, "n_out"}, [&](auto cv) -> int {
+        return OutputsImpl<decltype(cv)>::make(d_keys, d_index, d_j, d_amounts, n_out, d_out_masks, d_out_sealed, d_out_tags,
+                                               static_cast<hipStream_t>(stream));
+    });
+}
+
+// host buffers in, host masks, sealed amounts and tags out: the device path above between copies
+extern "C" int bpp_outputs_make(bpp_ctx* ctx, const uint8_t* keys, const uint64_t* index, const uint32_t* j, const uint64_t* amounts,
+                                size_t n_out, uint64_t* out_masks, uint64_t* out_sealed, uint8_t* out_tags) {
+    if (int rc = outputs_make_args(ctx, keys, index, j, amounts, n_out, out_masks, out_sealed, out_tags, false)) return rc;
+    if (n_out == 0) return BPP_OK;
+    return on_ctx(*ctx, {n_out, "n_out"}, [&](auto cv) -> int {
+        return OutputsImpl<decltype(cv)>::make_host(keys, index, j, amounts, n_out, out_masks, out_sealed, out_tags);
+    });
+}
+
+extern "C" size_t bpp_verify_find_outputs_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys) {
+    if ((count && !m_of) || !out_pairs_bounded(m_of, count, n_keys) || !m_of_wellformed(m_of, count)) return 0;
+    return size_for(v, [&](auto cv) { return OutputsImpl<decltype(cv)>::workspace_bytes(v, m_of, count, n_keys); });
+}
+
+extern "C" int bpp_range_verify_find_outputs_serialized_mixed_keys_device(
+    bpp_verifier* v, const void* d_proofs, const void* d_commitments, const uint32_t* m_of, size_t count, int flags,
+    const uint8_t* d_keys, size_t n_keys, uint64_t index_base, const uint64_t* d_index, const uint64_t* d_sealed,
+    const uint8_t* d_tags, uint32_t* d_ok, uint32_t* d_hits, size_t max_hits, uint32_t* d_n_hits, uint32_t* d_n_candidates,
+    void* d_workspace, size_t workspace_bytes, void* stream) {
+    OutputsArgs a{static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), m_of, count, d_keys, n_keys,
+                  index_base, d_index, d_sealed, d_tags, d_ok, d_hits, max_hits, d_n_hits, d_n_candidates};
+    if (int rc = outputs_args(v, flags, a, true, d_workspace)) return rc;
+    if (count == 0) return find_nothing(v, counts_only(d_n_hits, d_n_candidates), true, static_cast<hipStream_t>(stream));
+    if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return OutputsImpl<decltype(cv)>::find(v, a, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    });
+}
+
+// host buffers in (keys, index, sealed amounts and tags included), host verdicts, hit records and counts out
+extern "C" int bpp_range_verify_find_outputs_serialized_mixed_keys(
+    bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, const uint32_t* m_of, size_t count, int flags,
+    const uint8_t* keys, size_t n_keys, uint64_t index_base, const uint64_t* index, const uint64_t* sealed, const uint8_t* tags,
+    uint32_t* out_ok, uint32_t* out_hits, size_t max_hits, uint32_t* out_n_hits, uint32_t* out_n_candidates) {
+    OutputsArgs a{proofs, commitments, m_of, count, keys, n_keys, index_base, index, sealed, tags, out_ok, out_hits, max_hits,
+                  out_n_hits, out_n_candidates};
+    if (int rc = outputs_args(v, flags, a, false, nullptr)) return rc;
+    if (count == 0) return find_nothing(v, counts_only(out_n_hits, out_n_candidates), false, nullptr);
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int { return OutputsImpl<decltype(cv)>::find_host(v, a); });
 }
 
 // ---- the verifier pool: one batch sharded over the devices of a node (shard.hpp, pool.hpp; see include/bpp_amd.h) ----

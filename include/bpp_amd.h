@@ -874,6 +874,86 @@ int bpp_range_verify_find_tagged_serialized_mixed_keys(bpp_verifier *v, const ui
                                                        size_t max_hits, uint32_t *out_n_hits, const uint8_t *tags,
                                                        uint32_t *out_n_candidates);
 
+/* ---- outputs with DERIVED masks: finding each key's outputs INSIDE AGGREGATED PROOFS ----
+ * The calls above list single-output proofs, by rewinding them.  A real transaction is ONE aggregated proof over two or
+ * more outputs that belong to different people, and rewinding cannot serve it: an aggregated proof yields one
+ * Gamma = sum z^(2j) gamma_j, never the individual gamma_j, and its nonces come from one blinding key.  So here nothing is
+ * rewound.  The SENDER derives the mask of output j from the RECIPIENT's key and commits with it; the recipient derives it
+ * again and checks the commitment.  With
+ *     B(tag, idx, a, b) = SHA-256(key || tag (4 ASCII bytes) || idx as u64 LE || a as u32 LE || b as u32 LE)
+ * the 52-byte block of the blinding slots, the pad and the view tag (csrc/output_terms.hpp):
+ *     output_mask(key, idx, j) = (c0 + 2^256 c1) mod r, zero replaced by one; c_h = B("bppm", idx, j, h) read as a
+ *                                little-endian 256-bit integer
+ *     output_pad(key, idx, j)  = the first 8 bytes of B("bppa", idx, j, 0) as a little-endian uint64_t
+ *     output_tag(key, idx, j)  = the first byte of B("bppt", idx, j, 0)
+ * idx is the blinding index of the output's PROOF and THE INDEX RULE ABOVE HOLDS UNCHANGED: proof i has index d_index[i]
+ * when given, else index_base + i, and a key never meets the same (idx, j) twice.  j is the output's place in that proof,
+ * 0 <= j < m_i.  FOR j = 0 THE PAD AND THE TAG ARE BYTE FOR BYTE bpp_amounts_seal's pad AND bpp_view_tags's tag: a single
+ * output sealed and tagged with those calls is a valid output here.  The mask's tag "bppm" separates it from every
+ * blinding slot ("bppb"): the proof's own nonces stay the sender's business, under whatever key the sender proves.
+ *
+ * THE SENDER'S CALL, one lane per output:
+ *   d_keys      : n_out x 32 bytes (device, 4-byte aligned): the recipient's key of each output
+ *   d_index     : n_out x uint64_t: the blinding index of the output's proof
+ *   d_j         : n_out x uint32_t: the output's place in its proof
+ *   d_amounts   : n_out x uint64_t
+ *   d_out_masks : n_out x 4 uint64_t words, canonical, in exactly the d_gamma layout that bpp_commit_batch_device and the
+ *                 mixed prove calls read: they plug in without a copy
+ *   d_out_sealed: n_out x uint64_t: amount XOR output_pad
+ *   d_out_tags  : n_out bytes
+ * Any of the three outputs may be NULL and is then skipped; all three NULL is BPP_E_ARG.  A MASK IS SECRET: whoever holds
+ * it and the amount can open the commitment, and whoever holds (key, idx, j) holds the mask.  Errors: BPP_E_ARG for a
+ * NULL ctx, a NULL input, a d_keys that is not 4-byte aligned, n_out above 0x7fffffff / 64; n_out = 0 is BPP_OK.
+ * Asynchronous on `stream`, no workspace and no upload; the host twin takes host buffers, is synchronous and overwrites
+ * its device copies of the keys and the masks before freeing them. */
+int bpp_outputs_make_device(bpp_ctx *ctx, const uint8_t *d_keys, const uint64_t *d_index, const uint32_t *d_j,
+                            const uint64_t *d_amounts, size_t n_out, uint64_t *d_out_masks, uint64_t *d_out_sealed,
+                            uint8_t *d_out_tags, void *stream);
+int bpp_outputs_make(bpp_ctx *ctx, const uint8_t *keys, const uint64_t *index, const uint32_t *j, const uint64_t *amounts,
+                     size_t n_out, uint64_t *out_masks, uint64_t *out_sealed, uint8_t *out_tags);
+
+/* THE RECEIVER'S CALL: VERIFY a block and LIST, PER OUTPUT, what belongs to many view keys.  d_proofs, d_commitments, m_of,
+ * count, d_keys, n_keys, index_base, d_index, d_ok, d_hits, max_hits, d_n_hits, d_n_candidates, d_workspace,
+ * workspace_bytes and stream each mean what they mean in bpp_range_verify_find_tagged_serialized_mixed_keys_device.
+ *   flags    : BPP_SER_TRANSCRIPT (REQUIRED) | BPP_SER_UNCOMPRESSED | BPP_PROVE_AMOUNT64.  BPP_FIND_AMOUNTS_SEALED is NOT
+ *              accepted: amounts are always sealed here
+ *   d_sealed : n_out x uint64_t, n_out = sum of m_i
+ *   d_tags   : n_out bytes
+ * Both are per OUTPUT, packed in caller order: output j of proof i is output number o = (sum of m_i' over i' < i) + j.
+ * Both are SHARED BY ALL KEYS and REQUIRED when n_keys > 0.
+ * d_ok IS WORD FOR WORD WHAT bpp_range_verify_batch_serialized_mixed_device WRITES.  A CANDIDATE is a pair (key q, output
+ * o = (i, j)) with
+ *     d_ok[i] == 0,  output_tag(key_q, idx_i, j) == d_tags[o]
+ * and A HIT is a candidate with
+ *     V_{i,j} == v g + gamma h,  v = d_sealed[o] XOR output_pad(key_q, idx_i, j),  gamma = output_mask(key_q, idx_i, j)
+ * FOR EVERY m_i; the scalar on g is formed under the call's BPP_PROVE_AMOUNT64 as the commit calls form it.  A HIT IMPLIES
+ * A VERIFIED PROOF.  Hit records are the 12 words of the calls above, [key number q, output number o, amount lo, amount
+ * hi, gamma as 8 canonical words], IN ASCENDING (key number, output number) ORDER; max_hits and d_n_hits as there.
+ * d_n_candidates (may be NULL) is the sum over the block.  The pair bound is n_keys x n_out <= 0x7fffffff / 64, checked
+ * without overflow; bpp_verify_find_outputs_workspace_bytes(v, m_of, count, n_keys) is 0 beyond it and for an m_i that is
+ * not taken.
+ * THE KEY RULE, stronger here than above: no kernel of this call uses LDS or scratch, and nothing derived from a key
+ * reaches memory except the candidate bit (the match of a public byte), the hit bit, and a HIT's gamma and amount.  A
+ * non-hit's mask never leaves registers.  The host twin overwrites its copy of the keys before freeing it.
+ * Errors: those of the tagged call (d_sealed in the place of d_amounts), and BPP_E_ARG for BPP_FIND_AMOUNTS_SEALED;
+ * nothing is enqueued and nothing is written then.  count = 0 is BPP_OK with d_n_hits[0] = 0, and d_n_candidates[0] = 0
+ * when given; n_keys = 0 likewise, THE BLOCK VERIFIED ALL THE SAME (d_keys, d_sealed, d_tags, d_hits may be NULL).  The
+ * device call BLOCKS the host only while it uploads the per-proof index; the host twin is synchronous. */
+size_t bpp_verify_find_outputs_workspace_bytes(const bpp_verifier *v, const uint32_t *m_of, size_t count, size_t n_keys);
+int bpp_range_verify_find_outputs_serialized_mixed_keys_device(bpp_verifier *v, const void *d_proofs, const void *d_commitments,
+                                                               const uint32_t *m_of, size_t count, int flags,
+                                                               const uint8_t *d_keys, size_t n_keys, uint64_t index_base,
+                                                               const uint64_t *d_index, const uint64_t *d_sealed,
+                                                               const uint8_t *d_tags, uint32_t *d_ok, uint32_t *d_hits,
+                                                               size_t max_hits, uint32_t *d_n_hits, uint32_t *d_n_candidates,
+                                                               void *d_workspace, size_t workspace_bytes, void *stream);
+int bpp_range_verify_find_outputs_serialized_mixed_keys(bpp_verifier *v, const uint8_t *proofs, const uint8_t *commitments,
+                                                        const uint32_t *m_of, size_t count, int flags, const uint8_t *keys,
+                                                        size_t n_keys, uint64_t index_base, const uint64_t *index,
+                                                        const uint64_t *sealed, const uint8_t *tags, uint32_t *out_ok,
+                                                        uint32_t *out_hits, size_t max_hits, uint32_t *out_n_hits,
+                                                        uint32_t *out_n_candidates);
+
 /* ---- the weighted inner product argument as a seam of its own: WeightedInnerProductProof::{prove, verify} ----
  * Reference: src/weighted_inner_product_proof.rs:36-227 (prove), :238-328 (verify), :330-382 (verification_scalars).
  * An engine created for (n, m) proves and verifies the WIP relation over its key for ANY statement that ends in one; only

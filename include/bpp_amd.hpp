@@ -403,6 +403,86 @@ inline FindTaggedResult verify_find_tagged_serialized_mixed_keys(
     return r;
 }
 
+// The sender's side of outputs with derived masks (bpp_outputs_make): one recipient key, one amount per OUTPUT, ms[i] outputs
+// in proof i, whose blinding index is index[i] or index_base + i.  masks: 4 words per output, the gamma layout of the commit
+// and prove calls.  The masks are secret.
+struct MadeOutputs {
+    std::vector<uint64_t> masks, sealed;
+    std::vector<uint8_t> tags;
+};
+inline MadeOutputs make_outputs(bpp_ctx* ctx, const std::vector<std::array<uint8_t, 32>>& keys, const std::vector<uint64_t>& amounts,
+                                const std::vector<uint32_t>& ms, uint64_t index_base = 0, const std::vector<uint64_t>& index = {}) {
+    size_t n_out = 0;
+    for (uint32_t m : ms) n_out += m;
+    if (keys.size() != n_out || amounts.size() != n_out) throw std::logic_error("make_outputs: one key and one amount per output");
+    if (!index.empty() && index.size() != ms.size()) throw std::logic_error("make_outputs: one index per proof");
+    std::vector<uint64_t> idx(n_out + 1);
+    std::vector<uint32_t> place(n_out + 1);
+    std::vector<uint8_t> packed(n_out * 32 + 1);
+    for (size_t i = 0, o = 0; i < ms.size(); i++)
+        for (uint32_t j = 0; j < ms[i]; j++, o++) {
+            idx[o] = index.empty() ? index_base + i : index[i];
+            place[o] = j;
+            for (size_t t = 0; t < 32; t++) packed[o * 32 + t] = keys[o][t];
+        }
+    MadeOutputs r;
+    r.masks.assign(n_out * 4 + 1, 0);
+    r.sealed.assign(n_out + 1, 0);
+    r.tags.assign(n_out + 1, 0);
+    const int rc = bpp_outputs_make(ctx, packed.data(), idx.data(), place.data(), amounts.data(), n_out, r.masks.data(),
+                                    r.sealed.data(), r.tags.data());
+    for (volatile uint8_t& b : packed) b = 0;   // the packed copy of the keys made here
+    if (rc != BPP_OK) throw std::runtime_error(std::string("bpp_outputs_make: ") + bpp_last_error());
+    r.masks.resize(n_out * 4);
+    r.sealed.resize(n_out);
+    r.tags.resize(n_out);
+    return r;
+}
+
+// Verifies a block and lists, per OUTPUT, what belongs to the keys, aggregated proofs included
+// (bpp_range_verify_find_outputs_serialized_mixed_keys): sealed and tags hold one entry per output (sum of ms), in caller
+// order, shared by all keys.  A hit's `position` is its output number.
+inline FindTaggedResult verify_find_outputs_serialized_mixed_keys(
+    bpp_verifier* engine, const std::vector<uint8_t>& proofs, const std::vector<uint8_t>& commitments,
+    const std::vector<uint32_t>& ms, const std::vector<std::array<uint8_t, 32>>& keys, const std::vector<uint64_t>& sealed,
+    const std::vector<uint8_t>& tags, size_t max_hits, uint64_t index_base = 0, const std::vector<uint64_t>& index = {},
+    bool amount64 = false, bool uncompressed = false) {
+    size_t n_out = 0;
+    for (uint32_t m : ms) n_out += m;
+    const size_t pairs = keys.size() * n_out;
+    if (!index.empty() && index.size() != ms.size())
+        throw std::logic_error("verify_find_outputs_serialized_mixed_keys: one index per proof");
+    if (sealed.size() != n_out || tags.size() != n_out)
+        throw std::logic_error("verify_find_outputs_serialized_mixed_keys: one sealed amount and one tag per output");
+    const size_t cap = std::min(max_hits, pairs);
+    FindTaggedResult r;
+    r.ok.assign(ms.size() + 1, 0);
+    std::vector<uint32_t> rec(cap * 12 + 1);
+    std::vector<uint8_t> packed(keys.size() * 32 + 1);
+    for (size_t j = 0; j < keys.size(); j++)
+        for (size_t t = 0; t < 32; t++) packed[j * 32 + t] = keys[j][t];
+    const int flags = BPP_SER_TRANSCRIPT | (uncompressed ? BPP_SER_UNCOMPRESSED : 0) | (amount64 ? BPP_PROVE_AMOUNT64 : 0);
+    uint32_t found = 0, candidates = 0;
+    const int rc = bpp_range_verify_find_outputs_serialized_mixed_keys(
+        engine, proofs.data(), commitments.data(), ms.data(), ms.size(), flags, packed.data(), keys.size(), index_base,
+        index.empty() ? nullptr : index.data(), sealed.data(), tags.data(), r.ok.data(), rec.data(), cap, &found, &candidates);
+    for (volatile uint8_t& b : packed) b = 0;   // the packed copy of the keys made here
+    if (rc != BPP_OK)
+        throw std::runtime_error(std::string("bpp_range_verify_find_outputs_serialized_mixed_keys: ") + bpp_last_error());
+    r.ok.resize(ms.size());
+    r.found = found;
+    r.candidates = candidates;
+    r.hits.resize(std::min<size_t>(found, cap));
+    for (size_t h = 0; h < r.hits.size(); h++) {
+        const uint32_t* w = rec.data() + h * 12;
+        r.hits[h].key_no = w[0];
+        r.hits[h].position = w[1];
+        r.hits[h].amount = (uint64_t)w[2] | (uint64_t)w[3] << 32;
+        for (int t = 0; t < 4; t++) r.hits[h].mask.e[t] = (uint64_t)w[4 + 2 * t] | (uint64_t)w[5 + 2 * t] << 32;
+    }
+    return r;
+}
+
 // Verifier-side holder of the commitments.  It exists only in the reference's (stale) README
 // (README.md:47-55: RangeVerifier::new(), allocate(&prover.commitment_vec), proof.verify(.., &verifier));
 // the reference's code takes the commitment slice directly (range/mod.rs:57-62).  Both forms are offered.

@@ -27,8 +27,14 @@ alarm is raised only when the interpreter has control again, so run the whole to
            the host, on the `wallet` block with the owner's view tags, alternated repetition by repetition:
            medians, spreads, tagged / untagged with the per-repetition spread, and n_candidates / pairs.  Verdicts, hits and
            the candidate count (against hashlib) are checked.  Merged into --out under "find_tags".
+  outputs  (--find --outputs --keys K[,K..], default 16,64,256) bpp_range_verify_find_outputs_serialized_mixed_keys_device on
+           2^14 containers of m = 4 (2^16 outputs with derived masks, the owner's tags) against the tagged find call on the
+           `wallet` block of 2^16 single outputs, each also with n_keys = 0, alternated repetition by repetition (DESIGN.md
+           4m): medians, each call's key-dependent part (the call minus its own n_keys = 0 run) and the spread.  Hits and the
+           candidate count (against hashlib, every pair) are checked.  Merged into --out under "find_outputs".
 usage: timeout -k 10 1100 python tools/recover_bench.py [--reps 20] [--warmup 3] [--window 13] [--scale 1.0] [--legs sr]
-       [--blocks mixed,wallet] [--keys 1,4,16,64] [--find] [--tags] [--side both] [--out profiles/recover_bench.json]"""
+       [--blocks mixed,wallet] [--keys 1,4,16,64] [--find] [--tags] [--outputs] [--side both]
+       [--out profiles/recover_bench.json]"""
 import argparse
 import csv
 import hashlib
@@ -410,6 +416,136 @@ def tags_leg(torch, B, a, bv, ks, args, out):
         del d_keys, d_ws
 
 
+def output_tag(key, idx, j):
+    """the first byte of SHA-256(key || "bppt" || idx as u64 LE || j as u32 LE || 0), by hashlib"""
+    return hashlib.sha256(key + b"bppt" + struct.pack("<QII", idx, j, 0)).digest()[0]
+
+
+def outputs_leg(torch, B, a, bv, ks, args, out):
+    """the per-output find call on containers of m = 4 against the tagged find call on the wallet block of as many single
+    outputs, each also with n_keys = 0; key 0 owns every output of both blocks and made their tags"""
+    M = 4
+    ms1 = block_shapes("wallet", args.scale)
+    n_out = len(ms1) // M * M
+    ms1 = ms1[:n_out]
+    ms4 = np.full(n_out // M, M, dtype=np.uint32)
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    # the wallet block, sealed and tagged by the existing calls
+    d_p1, d_c1, d_a1 = step(600, lambda: make_block(torch, B, a, bv, ms1))
+    d_sealed1 = torch.zeros_like(d_a1)
+    bv.seal_amounts_device(KEY, d_a1.data_ptr(), n_out, d_sealed1.data_ptr(), st, index_base=BASE)
+    d_tags1 = torch.zeros((n_out,), dtype=torch.uint8, device=dev)
+    bv.view_tags_device(KEY, n_out, d_tags1.data_ptr(), st, index_base=BASE)
+    # the block of aggregated proofs: masks, sealed amounts and tags by the sender's call under key 0, proofs under a sender key
+    rng = np.random.default_rng(13)
+    vals = rng.integers(0, 1 << 31, size=n_out, dtype=np.uint64)
+    d_v = torch.from_numpy(vals.view(np.int64)).to(dev)
+    d_ok_keys = torch.from_numpy(np.frombuffer(KEY * n_out, dtype=np.uint8).copy()).to(dev)
+    d_ix = torch.from_numpy((np.uint64(BASE) + np.arange(n_out, dtype=np.uint64) // np.uint64(M)).view(np.int64)).to(dev)
+    d_j = torch.from_numpy((np.arange(n_out, dtype=np.uint32) % M).view(np.int32)).to(dev)
+    d_g = torch.zeros((n_out, 4), dtype=torch.int64, device=dev)
+    d_sealed4 = torch.zeros((n_out,), dtype=torch.int64, device=dev)
+    d_tags4 = torch.zeros((n_out,), dtype=torch.uint8, device=dev)
+    bv.make_outputs_device(d_ok_keys.data_ptr(), d_ix.data_ptr(), d_j.data_ptr(), d_v.data_ptr(), n_out, d_g.data_ptr(),
+                           d_sealed4.data_ptr(), d_tags4.data_ptr(), st)
+    pb = B.compressed_bytes(a)
+    d_p4 = torch.zeros(len(ms4) * B.proof_bytes(a, N, M), dtype=torch.uint8, device=dev)
+    d_c4 = torch.zeros(n_out * pb, dtype=torch.uint8, device=dev)
+    wsb = bv.prover_mixed_workspace_bytes(ms4, serialized=True)
+    d_pws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    sender = hashlib.sha256(b"recover_bench sender").digest()
+    step(600, lambda: (bv.prove_serialized_mixed_device(d_v.data_ptr(), d_g.data_ptr(), ms4, d_p4.data_ptr(), d_c4.data_ptr(),
+                                                        d_pws.data_ptr(), wsb, st, transcript=True, blind_key=sender,
+                                                        index_base=BASE), torch.cuda.synchronize()))
+    del d_pws, d_ok_keys
+    tags4 = d_tags4.cpu().numpy()
+    tags_are_hashlib = all(int(tags4[o]) == output_tag(KEY, BASE + o // M, o % M) for o in range(0, n_out, max(1, n_out // 256)))
+    max_hits = n_out
+    d_ok = torch.full((n_out,), 7, dtype=torch.int32, device=dev)
+    h_ok = torch.empty((n_out,), dtype=torch.int32, pin_memory=True)
+    d_hits = torch.zeros((max_hits, 12), dtype=torch.int32, device=dev)
+    h_hits = torch.empty((max_hits, 12), dtype=torch.int32, pin_memory=True)
+    d_n = torch.zeros((2,), dtype=torch.int32, device=dev)   # hits, candidates
+    out["find_outputs"] = {"outputs": n_out, "m": M, "containers": len(ms4), "single_block": "wallet", "max_hits": max_hits,
+                           "tags_are_hashlib": tags_are_hashlib, "by_keys": {}}
+    want = {"outputs": vals, "tagged": d_a1.cpu().numpy().view(np.uint64)}
+    for K in ks:
+        keys = [KEY] + [hashlib.sha256(b"recover_bench key %d" % j).digest() for j in range(1, K)]
+        d_keys = torch.from_numpy(np.frombuffer(b"".join(keys), dtype=np.uint8).copy()).to(dev)
+        osb, tsb = bv.verify_find_outputs_workspace_bytes(ms4, K), bv.verify_find_tagged_workspace_bytes(ms1, K)
+        d_ws = torch.empty(max(osb, tsb), dtype=torch.uint8, device=dev)
+        got = {}
+
+        def finish(name, count):
+            h_ok[:count].copy_(d_ok[:count], non_blocking=True)
+            got[name] = d_n.cpu().numpy().tolist()   # the counts first, then as many records
+            w = min(got[name][0], max_hits)
+            h_hits[:w].copy_(d_hits[:w], non_blocking=True)
+
+        def outputs(name, nk):
+            def run():
+                d_n.zero_()
+                bv.verify_find_outputs_serialized_mixed_keys_device(
+                    d_p4.data_ptr(), d_c4.data_ptr(), ms4, d_keys.data_ptr() if nk else 0, nk, d_sealed4.data_ptr() if nk else 0,
+                    d_tags4.data_ptr() if nk else 0, d_ok.data_ptr(), d_hits.data_ptr() if nk else 0, max_hits, d_n.data_ptr(),
+                    d_ws.data_ptr(), osb, st, index_base=BASE, d_n_candidates=d_n.data_ptr() + 4)
+                finish(name, len(ms4))
+            return run
+
+        def tagged(name, nk):
+            def run():
+                d_n.zero_()
+                bv.verify_find_serialized_mixed_keys_device(d_p1.data_ptr(), d_c1.data_ptr(), ms1, d_keys.data_ptr() if nk else 0, nk,
+                                                            d_sealed1.data_ptr() if nk else 0, d_ok.data_ptr(),
+                                                            d_hits.data_ptr() if nk else 0, max_hits, d_n.data_ptr(),
+                                                            d_ws.data_ptr(), tsb, st, sealed=True, index_base=BASE,
+                                                            d_tags=d_tags1.data_ptr() if nk else 0,
+                                                            d_n_candidates=d_n.data_ptr() + 4 if nk else 0)
+                finish(name, n_out)
+            return run
+
+        def check(name, count):
+            torch.cuda.synchronize()
+            hits = h_hits.numpy().view(np.uint32)
+            amounts = hits[:, 2].astype(np.uint64) | hits[:, 3].astype(np.uint64) << np.uint64(32)
+            return bool((h_ok.numpy()[:count] == 0).all() and got[name][0] == n_out and (hits[:, 0] == 0).all() and
+                        (hits[:, 1] == np.arange(n_out)).all() and (amounts == want[name]).all())
+
+        fns = [outputs("outputs", K), tagged("tagged", K), outputs("outputs_no_keys", 0), tagged("tagged_no_keys", 0)]
+        res = {"pairs": K * n_out, "outputs_workspace_bytes": osb, "tagged_workspace_bytes": tsb}
+        for name, f, count in (("tagged", fns[1], n_out), ("outputs", fns[0], len(ms4))):   # each once alone: that side's answer
+            h_hits.zero_()
+            step(300, f)
+            res[name + "_hits_as_expected"] = check(name, count)
+        # the candidate count of the new call against hashlib, every pair of the foreign keys
+        chance = sum(1 for k in keys[1:] for o in range(n_out) if output_tag(k, BASE + o // M, o % M) == int(tags4[o]))
+        res["n_candidates"] = got["outputs"][1]
+        res["n_candidates_hashlib"] = n_out + chance
+        res["candidates_as_expected"] = bool(got["outputs"][1] == n_out + chance)
+        res["tagged_n_candidates"] = got["tagged"][1]
+        ts = step(900, lambda: alternate(torch, fns, args.reps, args.warmup))
+        torch.cuda.synchronize()
+        for name, t in zip(("outputs", "tagged", "outputs_no_keys", "tagged_no_keys"), ts):
+            res[name] = stats(t)
+        med = [statistics.median(t) for t in ts]
+        key_part = {"outputs": med[0] - med[2], "tagged": med[1] - med[3]}
+        res["key_dependent_ms"] = key_part
+        res["key_dependent_per_rep"] = {"outputs": stats([x - y for x, y in zip(ts[0], ts[2])]),
+                                        "tagged": stats([x - y for x, y in zip(ts[1], ts[3])])}
+        spread = max(max(t) - min(t) for t in ts)
+        res["spread_between_repetitions_ms"] = spread
+        # the expectation of DESIGN 4m, not a gate
+        res["outputs_key_part_within_spread_of_tagged"] = bool(key_part["outputs"] <= key_part["tagged"] + spread)
+        out["find_outputs"]["by_keys"][str(K)] = res
+        print("outputs %d" % K, json.dumps(res), flush=True)
+        wrong = [c for c in ("tagged_hits_as_expected", "outputs_hits_as_expected", "candidates_as_expected")
+                 if res.get(c) is False] + ([] if tags_are_hashlib else ["tags_are_hashlib"])
+        if wrong:   # a run that computed something else is no measurement
+            raise RuntimeError("outputs leg, K = %d: %s" % (K, ", ".join(wrong)))
+        del d_keys, d_ws
+
+
 def merge_kernel_stats(args):
     """folds rocprofv3 k_kernel_stats.csv files (one per side) into the JSON at --out: no GPU"""
     with open(args.out) as f:
@@ -435,6 +571,7 @@ def main():
     ap.add_argument("--keys", default="")
     ap.add_argument("--find", action="store_true")
     ap.add_argument("--tags", action="store_true")
+    ap.add_argument("--outputs", action="store_true")
     ap.add_argument("--side", default="both", choices=("both", "many", "single", "fused", "today"))
     ap.add_argument("--kernel-stats", default="")
     ap.add_argument("--reps", type=int, default=20)
@@ -448,7 +585,8 @@ def main():
     if args.kernel_stats:
         return merge_kernel_stats(args)
     if args.find:
-        args.legs = "t" if args.tags else "f"   # --find: that leg alone, at --keys; with --tags the tagged call's
+        # --find: that leg alone, at --keys; with --tags the tagged call's, with --outputs the per-output call's
+        args.legs = "o" if args.outputs else "t" if args.tags else "f"
     elif args.keys and "k" not in args.legs:
         args.legs = "k"   # --keys alone: the many-key leg alone
     import torch
@@ -470,6 +608,8 @@ def main():
             find_leg(torch, B, a, bv, [int(x) for x in (args.keys or "1,16,64").split(",")], args, out)
         if "t" in args.legs:
             tags_leg(torch, B, a, bv, [int(x) for x in (args.keys or "1,16,64,256").split(",")], args, out)
+        if "o" in args.legs:
+            outputs_leg(torch, B, a, bv, [int(x) for x in (args.keys or "16,64,256").split(",")], args, out)
         out["complete"] = True
     except StepTimeout:
         out["stopped"] = "a step ran into its time limit"
@@ -479,7 +619,7 @@ def main():
         if args.find and os.path.exists(args.out):   # beside what the other legs recorded there
             with open(args.out) as f:
                 kept = json.load(f)
-            leg = "find_tags" if args.tags else "find"
+            leg = "find_outputs" if args.outputs else "find_tags" if args.tags else "find"
             kept[leg] = dict(out.get(leg, {}), reps=args.reps, warmup=args.warmup, window_bits=args.window,
                              scale=args.scale, device=out["device"], complete=out["complete"])
             out = kept
