@@ -274,6 +274,8 @@ def lib():
         L.bpp_debug_verifier_scalars.argtypes = [vp, ctypes.c_uint32, vp, vp, sz, vp]
         # ... and the many-key scan's two kernels on chosen proof scalars and challenges (host buffers, synchronous)
         L.bpp_debug_scan_keys.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, sz, sz, vp, sz, u64, vp, vp, vp, vp, vp]
+        # ... and the batched prover's whole kernels on chosen witnesses, blinding and challenges (host buffers, synchronous)
+        L.bpp_debug_prover_scalars.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp, sz, vp, vp, vp]
         _lib = L
     return _lib
 

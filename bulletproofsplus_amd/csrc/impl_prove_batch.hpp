@@ -99,11 +99,15 @@ struct ProveBatchImpl {
     // px (one class of a mixed block, ps its view; prover_batch.hpp PX_*): `count` entries by gathered position.  The
     // values, gammas, blinding scalars and challenge blocks are then the caller's PACKED buffers and each record,
     // commitments behind it, goes to wire point PX_REC of d_out_points (d_out_V is not used).
+    // d_challenges (fs = false and fixed strides alone; tu_debug.hip bpp_debug_prover_scalars): count x (3 + k) canonical
+    // scalars [y, z, e, e_1..e_k], a block per proof in place of the shape's literals.  y and every e_t non-zero: the whole
+    // kernels invert their product.
     static int prove_batch_device(bpp_verifier* v, const PassShape& ps, const uint64_t* d_values, const uint64_t* d_gammas,
                                   size_t count, uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_V, bool fs,
                                   uint64_t* d_out_challenges, void* d_workspace, size_t workspace_bytes, hipStream_t st,
                                   const uint8_t* blind_key = nullptr, uint64_t index_base = 0,
-                                  const uint64_t* d_blinding = nullptr, const uint32_t* px = nullptr, bool amount64 = false);
+                                  const uint64_t* d_blinding = nullptr, const uint32_t* px = nullptr, bool amount64 = false,
+                                  const uint64_t* d_challenges = nullptr);
     static int prove_batch_device(bpp_verifier* v, const uint64_t* d_values, const uint64_t* d_gammas, size_t count,
                                   uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_V, bool fs,
                                   uint64_t* d_out_challenges, void* d_workspace, size_t workspace_bytes, hipStream_t st,
@@ -249,11 +253,13 @@ int ProveBatchImpl<C>::prove_batch_device(bpp_verifier* v, const PassShape& ps, 
                                           const uint64_t* d_gammas, size_t count, uint64_t* d_out_points,
                                           uint64_t* d_out_scalars, uint64_t* d_out_V, bool fs, uint64_t* d_out_challenges,
                                           void* d_workspace, size_t workspace_bytes, hipStream_t st, const uint8_t* blind_key,
-                                          uint64_t index_base, const uint64_t* d_blinding, const uint32_t* px, bool amount64) {
+                                          uint64_t index_base, const uint64_t* d_blinding, const uint32_t* px, bool amount64,
+                                          const uint64_t* d_challenges) {
     const VerifyShape& s = ps.s;
     const uint32_t k = s.k, m = s.m, nvp = pb_num_vps(k, m);
     const ProveLayout L = prove_layout(s, count, px != nullptr);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
+    if (d_challenges && (fs || px)) return fail(BPP_E_ARG, "chosen challenges: literal mode, fixed strides");
     ProverConsts pc = literals();
     pc.alpha = m == 1 ? 7 : 33;         // range/mod.rs:94 / :256
     pc.amount64 = amount64 ? 1u : 0u;   // the commitments' scalar on g: the u64, not `v as i32` (range/prover.rs:37)
@@ -278,11 +284,13 @@ int ProveBatchImpl<C>::prove_batch_device(bpp_verifier* v, const PassShape& ps, 
         const uint32_t* blind = chunk_blinding(bl && !px ? bl + base * (size_t)pb_blind_elems(k) * 8 : bl ? W(L.blind) : nullptr,
                                                blind_key, px ? index_base : index_base + base, k, cnt, cpx, W(L.blind), st);
         // the transcript's challenges [y, z, e, e_1..e_k] are hashed into the caller's block when it has fixed strides; the
-        // kernels read those, chs words apart, or the shape's literals, one block for all
+        // kernels read those, chs words apart, or the shape's literals, one block for all -- or, in their place, the blocks
+        // a test chose (d_challenges)
         uint32_t* o_ch =
             d_out_challenges && !px ? reinterpret_cast<uint32_t*>(d_out_challenges) + base * (size_t)(3 + k) * 8 : W(L.ch);
-        const uint32_t* ch = fs ? o_ch : ps.challenges;
-        const uint32_t chs = fs ? (3 + k) * 8 : 0u;
+        const uint32_t* chosen = reinterpret_cast<const uint32_t*>(d_challenges);
+        const uint32_t* ch = fs ? o_ch : chosen ? chosen + base * (size_t)(3 + k) * 8 : ps.challenges;
+        const uint32_t chs = fs || chosen ? (3 + k) * 8 : 0u;
         const Chunk c{s, pc, L, ws, cnt, blind, cpx, o_pts, o_V, o_sc, o_ch, st, v->table.u32()};
         auto init = [&](uint32_t phase) {
             hipLaunchKernelGGL(k_pb_init<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, phase, fs ? 1u : 0u, vals, gams,

@@ -7,11 +7,14 @@
 // MulVec scalars the test chooses, which takes device buffers as bpp_verifier_run does and adds no kernel.  Its front half,
 // the scalar stage (launch_verify_scalars) on challenges the test chooses, is bpp_debug_verifier_scalars: host pointers again.
 // bpp_debug_scan_keys is that hook's counterpart for the many-key scan (recover_keys.hpp): a class of chosen proofs through
-// k_recover_coeffs and k_scan_keys, host pointers, no kernel of its own.
+// k_recover_coeffs and k_scan_keys, host pointers, no kernel of its own.  bpp_debug_prover_scalars is the batched prover's:
+// k_pb_init, k_pb_round and k_pb_final whole, on witnesses, blinding and challenges the test chooses, through
+// ProveBatchImpl::prove_batch_device -- host pointers, no kernel of its own.
 #include "host_util.hpp"
 
 #include "field_raw_ops.hpp"
 #include "fixed_glv.hpp"
+#include "impl_prove_batch.hpp"   // declarations only: the kernels of prover_batch.hpp live in tu_prove_*.hip
 #include "impl_verify.hpp"   // declarations only (no BPP_IMPL_DEFINITIONS): the kernels live in tu_verify_*.hip
 #include "recover_keys.hpp"  // likewise: k_recover_coeffs and k_scan_keys live in tu_recover_keys_*.hip
 
@@ -519,6 +522,73 @@ extern "C" int bpp_debug_scan_keys(bpp_verifier* v, uint32_t m_view, const uint6
                 Fe<P> f;
                 for (int t = 0; t < P::NL; t++) f.l[t] = co[i * K::CW + t];
                 fe_to_canonical(f, oc + i * 8);
+            }
+            return BPP_OK;
+        });
+    });
+}
+
+// The batched prover's scalar stage -- k_pb_init(PB_ALL), the k whole rounds and k_pb_final through
+// ProveBatchImpl::prove_batch_device's literal path (prove_layout, chunk_blinding, argument: the functions every prove entry
+// runs), then the prover's own MulVec over every virtual proof -- on witnesses, blinding and challenges the caller chooses.
+// Host pointers, synchronous, no kernel of its own.
+//   m_view: as for bpp_debug_verifier_mulvec above; k, m and N are that shape's.  flags: BPP_PROVE_AMOUNT64 or 0.
+//   values [count][m] u64 ; gammas [count][m][4] ; blinding [count][5 + 2k][4] (null: the literals), all canonical
+//   challenges [count][3 + k][4]: y, z, e, e_1..e_k per proof, canonical, read at stride 3 + k (null: the shape's literals,
+//     one block at stride 0).  y and every e_t must be NON-ZERO mod r: the whole kernels invert [y, e_1..e_k] with one
+//     batched inversion, so a single zero among them zeroes every inverse of the proof (the transcript halves call fe_inv
+//     per challenge; neither mode can meet a zero short of a zero hash).  z and e may be zero.
+//   out_vps [count][2k + 3 + m][N][4]: the virtual-proof scalar arrays as the kernels leave them (pb_num_vps's numbering,
+//     MulVec order, canonical; the H terms of range A are +1: k_fixed_msm negates the table entries instead)
+//   out_scalars3 [count][3][4]: r', s', delta' ; out_points (may be null) [count][3 + 2k + m] wire points: the record
+//     [A, wip.A, wip.B, L.., R..], then the commitments.  count: at most one chunk (prove_chunk).
+extern "C" int bpp_debug_prover_scalars(bpp_verifier* v, uint32_t m_view, uint32_t flags, const uint64_t* values,
+                                        const uint64_t* gammas, const uint64_t* blinding, const uint64_t* challenges, size_t count,
+                                        uint64_t* out_vps, uint64_t* out_scalars3, uint64_t* out_points) {
+    if (!v || !values || !gammas || !out_vps || !out_scalars3) return fail(BPP_E_ARG, "null argument");
+    if (flags & ~(uint32_t)BPP_PROVE_AMOUNT64) return fail(BPP_E_ARG, "flags: BPP_PROVE_AMOUNT64 or 0");
+    uint32_t cls = 0;
+    if (!debug_view_shape(v, m_view, cls)) return fail(BPP_E_ARG, "m_view must be 0 or a power of two below m");
+    if (count == 0) return BPP_OK;
+    if (count > 2048) return fail(BPP_E_ARG, "count beyond one chunk");   // prove_chunk's cap, before any product
+    return guarded(Count{count, "count"}, [&]() -> int {
+        HIPCHK(hipSetDevice(v->ctx.device));
+        return dispatch(v->ctx.curve, [&](auto cv) -> int {
+            using C = decltype(cv);
+            using PB = ProveBatchImpl<C>;
+            constexpr size_t WB = (size_t)PB::WW * 4;   // bytes of a wire point
+            const PassShape ps = VerifyImpl<C>::class_shape(v, cls);
+            const VerifyShape& s = ps.s;
+            const uint32_t k = s.k, m = s.m;
+            if (count > PB::prove_chunk(s, count)) return fail(BPP_E_ARG, "count beyond one chunk");
+            const typename PB::ProveLayout L = PB::prove_layout(s, count);
+            const size_t vps_bytes = count * (size_t)pb_num_vps(k, m) * s.N * 32;
+            const size_t rec_bytes = count * (size_t)(3 + 2 * k) * WB, V_bytes = count * (size_t)m * WB;
+            DevBuf dv, dg, dbl, dch, dpts, dV, dsc, dws;
+            HIPCHK(dv.upload(values, count * m * 8));
+            HIPCHK(dg.upload(gammas, count * (size_t)m * 32));
+            HIPCHK(dbl.upload(blinding, count * (size_t)pb_blind_elems(k) * 32));   // null: the literals
+            HIPCHK(dch.upload(challenges, count * (size_t)(3 + k) * 32));          // null: the shape's literals
+            HIPCHK(dpts.alloc(rec_bytes));
+            HIPCHK(dV.alloc(V_bytes));
+            HIPCHK(dsc.alloc(count * 96));
+            HIPCHK(dws.alloc(L.total));
+            BPP_TRY(PB::prove_batch_device(v, ps, dv.u64(), dg.u64(), count, dpts.u64(), dsc.u64(), dV.u64(), false, nullptr, dws.p,
+                                           L.total, nullptr, nullptr, 0, dbl.u64(), nullptr, (flags & BPP_PROVE_AMOUNT64) != 0,
+                                           dch.u64()));
+            HIPCHK(hipDeviceSynchronize());
+            HIPCHK(hipMemcpy(out_vps, dws.u8() + L.vps, vps_bytes, hipMemcpyDeviceToHost));
+            HIPCHK(dsc.download(out_scalars3, count * 96));
+            if (out_points) {
+                std::vector<uint8_t> rec(rec_bytes), V(V_bytes);
+                HIPCHK(dpts.download(rec.data(), rec_bytes));
+                HIPCHK(dV.download(V.data(), V_bytes));
+                uint8_t* o = reinterpret_cast<uint8_t*>(out_points);
+                const size_t rb = (size_t)(3 + 2 * k) * WB, vb = (size_t)m * WB;
+                for (size_t p = 0; p < count; p++) {
+                    std::memcpy(o + p * (rb + vb), rec.data() + p * rb, rb);
+                    std::memcpy(o + p * (rb + vb) + rb, V.data() + p * vb, vb);
+                }
             }
             return BPP_OK;
         });
