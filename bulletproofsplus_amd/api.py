@@ -19,6 +19,7 @@ beyond (de)serialisation.
 
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 
@@ -42,7 +43,73 @@ class VerificationError(ProofError):
 
 
 def _ptr(a):
+    """the one doorway from arrays to pointers (None stays None)"""
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _some(a):
+    """_ptr, with None for an empty array as well as for an absent one"""
+    return _ptr(a) if a is not None and len(a) else None
+
+
+def _flat_bytes(x) -> np.ndarray:
+    """bytes, or anything array-like, as one flat u8 array"""
+    return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else \
+        np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
+
+
+def _flags(transcript=False, uncompressed=False, amount64=False, sealed=False) -> int:
+    """the flag word of the serialized, prove, scan and find entries (include/bpp_amd.h)"""
+    return (1 if transcript else 0) | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0) | \
+        (AMOUNTS_SEALED if sealed else 0)
+
+
+def _index_arg(index, count, message: str):
+    """None, or one u64 per item: RuntimeError(message) when there are not `count` of them (count None: any number)"""
+    if index is None:
+        return None
+    idx = np.ascontiguousarray(np.asarray([int(x) for x in index], dtype=np.uint64))
+    if count is not None and len(idx) != count:
+        raise RuntimeError(message)
+    return idx
+
+
+def _amounts_arg(amounts, need=None, message: str = None, rows: bool = False) -> np.ndarray:
+    """amounts below 2^64 as one flat u64 array -- one list, or (rows) one list per key flattened key-major;
+    RuntimeError(message) when there are not `need` of them (need None: any number)"""
+    vals = [[int(x) for x in row] for row in amounts] if rows else [int(x) for x in amounts]
+    am = np.ascontiguousarray(np.asarray(vals, dtype=np.uint64).reshape(-1))
+    if need is not None and len(am) != need:
+        raise RuntimeError(message)
+    return am
+
+
+def _tags_arg(tags) -> np.ndarray:
+    """view-tag bytes (bytes, or a sequence of ints) as one flat u8 array"""
+    return _flat_bytes(tags) if isinstance(tags, (bytes, bytearray, memoryview)) else \
+        np.ascontiguousarray(np.asarray([int(x) for x in tags], dtype=np.uint8).reshape(-1))
+
+
+@contextlib.contextmanager
+def _packed_keys(where: str, keys):
+    """-> (the 32-byte keys packed into one u8 array, or None when there are none; their number).  The packed copy made
+    here is wiped on every way out, as the C++ host twins wipe theirs (csrc/staging.hpp)."""
+    keys = [bytes(k) for k in keys]
+    if any(len(k) != 32 for k in keys):
+        raise RuntimeError("%s: every key is 32 bytes" % where)
+    kb = np.frombuffer(b"".join(keys), dtype=np.uint8).copy() if keys else None
+    try:
+        yield kb, len(keys)
+    finally:
+        if kb is not None:
+            kb[:] = 0
+
+
+def _hits(rec, found: int) -> list:
+    """the find entries' 12-word records [key number, position, amount lo, hi, mask as 8 words], the first `found` that
+    were written -> [(key_no, position, amount, mask)]"""
+    return [(int(r[0]), int(r[1]), int(r[2]) | int(r[3]) << 32, wire_to_int(np.ascontiguousarray(r[4:]).view(np.uint64)))
+            for r in rec[:found]]
 
 
 def scalar_to_wire(x) -> np.ndarray:
@@ -295,13 +362,12 @@ def proofs_scan(arith, n: int, data, version: int = 1) -> np.ndarray:
     curve = getattr(arith, "curve", arith)
     if isinstance(curve, str):
         curve = CURVE_IDS[curve]
-    raw = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else \
-        np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    raw = _flat_bytes(data)
     shortest = _lib.lib().bpp_proof_bytes_version(curve, n, 1, version)   # bounds the count
     ms = np.zeros(len(raw) // shortest if shortest else 0, dtype=np.uint32)
     count = ctypes.c_size_t(0)
-    check(_lib.lib().bpp_proofs_scan(curve, n, version, _ptr(raw) if len(raw) else None, len(raw),
-                                     _ptr(ms) if len(ms) else None, len(ms), ctypes.byref(count)), "bpp_proofs_scan")
+    check(_lib.lib().bpp_proofs_scan(curve, n, version, _some(raw), len(raw), _some(ms), len(ms), ctypes.byref(count)),
+          "bpp_proofs_scan")
     return ms[:count.value]
 
 
@@ -601,7 +667,60 @@ def _weight_key_arg(weight_key, d_weights):
     return key
 
 
-class BatchVerifier:
+def _prover_key(blind_key, transcript):
+    """the provers' blinding key: None, or 32 bytes under the transcript"""
+    if blind_key is not None and (not transcript or len(blind_key) != 32):
+        raise ValueError("blind_key: 32 bytes, transcript mode only")
+
+
+class _Shapes:
+    """The shape arithmetic of an engine of capacity (n, m) over `arith`, and the front of the calls that take a block of
+    proofs of mixed aggregation sizes: what BatchVerifier and VerifierPool share.  Proof i has shape (n, ms[i]), ms[i] a
+    power of two <= m; an m_i the engine does not take is never an error here -- the checks that need the shapes are
+    skipped and the library reports it (BPP_E_ARG naming the proof)."""
+
+    def _ms(self, ms) -> np.ndarray:
+        return np.ascontiguousarray(ms, dtype=np.uint32).reshape(-1)
+
+    def _taken(self, ms) -> bool:
+        return all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in ms)
+
+    def _rounds(self, m_i: int) -> int:
+        """k = log2(n m_i), the folding rounds of a proof of shape (n, m_i)"""
+        return (self.n * m_i).bit_length() - 1
+
+    def mixed_points(self, m_i: int) -> int:
+        """wire points of a proof record of shape (n, m_i): 3 + 2 log2(n m_i) + m_i"""
+        return 3 + 2 * self._rounds(m_i) + m_i
+
+    def _wire_records(self, records) -> np.ndarray:
+        """a list of per-proof records, or one packed array -> the packed (points, PW) array"""
+        PW = self.arith.PW
+        if not isinstance(records, (list, tuple)):
+            pts = np.asarray(records, dtype=np.uint64).reshape(-1, PW)
+        elif len(records):
+            pts = np.concatenate([np.asarray(r, dtype=np.uint64).reshape(-1, PW) for r in records])
+        else:
+            pts = np.zeros((0, PW), dtype=np.uint64)
+        return np.ascontiguousarray(pts)
+
+    def _block(self, where: str, proofs, commitments, ms, uncompressed: bool):
+        """The front of every call that takes containers back to back and ms[i] encoded commitments per proof:
+        -> (raw u8, cm u8, ms u32, count), ms framed from the stream (proofs_scan) when None.  RuntimeError, prefixed
+        with `where`, when the byte counts are not the ones the shapes need."""
+        raw, cm = _flat_bytes(proofs), _flat_bytes(commitments)
+        version = 2 if uncompressed else 1
+        m = proofs_scan(self.arith, self.n, raw, version) if ms is None else self._ms(ms)
+        if self._taken(m):
+            need = sum(proof_bytes(self.arith, self.n, int(x), version) for x in m)
+            if len(raw) != need:
+                raise RuntimeError("%s: %d bytes of proofs, the shapes in ms need %d" % (where, len(raw), need))
+            if len(cm) != int(m.sum()) * (uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)):
+                raise RuntimeError("%s: ms[i] commitments per proof" % where)
+        return raw, cm, m, len(m)
+
+
+class BatchVerifier(_Shapes):
     """Device-resident batch verification of independent proofs for one (pk, n, m).
 
     ``verify_wire`` takes host arrays; ``run_device`` takes raw device pointers (e.g. torch tensors'
@@ -617,22 +736,21 @@ class BatchVerifier:
         H = np.ascontiguousarray(pk.H_vec)
         check(_lib.lib().bpp_verifier_create(pk.arith.handle, _ptr(pk.gh), _ptr(G), _ptr(H), n, m, window_bits,
                                              ctypes.byref(h)), "bpp_verifier_create")
-        self.handle = h
-        self.msm_len = _lib.lib().bpp_verifier_msm_len(h)
-        self.table_bytes = _lib.lib().bpp_verifier_table_bytes(h)
-        mn = n * m
-        self.k = mn.bit_length() - 1
-        self.points_per_proof = 3 + 2 * self.k + m
+        self._adopt(h)
+
+    def _adopt(self, handle):
+        self.handle = handle
+        self.msm_len = _lib.lib().bpp_verifier_msm_len(handle)
+        self.table_bytes = _lib.lib().bpp_verifier_table_bytes(handle)
+        self.k = self._rounds(self.m)
+        self.points_per_proof = self.mixed_points(self.m)
 
     @classmethod
     def _borrowed(cls, arith: Arith, handle, n: int, m: int, owner) -> "BatchVerifier":
         """a verifier that belongs to `owner` (a VerifierPool's shard): close() leaves it alone"""
         v = cls.__new__(cls)
-        v.arith, v.n, v.m, v.handle, v._owner = arith, n, m, handle, owner
-        v.msm_len = _lib.lib().bpp_verifier_msm_len(handle)
-        v.table_bytes = _lib.lib().bpp_verifier_table_bytes(handle)
-        v.k = (n * m).bit_length() - 1
-        v.points_per_proof = 3 + 2 * v.k + m
+        v.arith, v.n, v.m, v._owner = arith, n, m, owner
+        v._adopt(handle)
         return v
 
     def close(self):
@@ -685,7 +803,7 @@ class BatchVerifier:
             raise RuntimeError("verify_serialized: m commitments per proof")
         ok = np.zeros(raw.shape[0], dtype=np.uint32)
         check(_lib.lib().bpp_range_verify_batch_serialized(self.handle, _ptr(raw), _ptr(cm), raw.shape[0],
-                                                           (1 if transcript else 0) | (2 if uncompressed else 0), _ptr(ok)),
+                                                           _flags(transcript, uncompressed), _ptr(ok)),
               "bpp_range_verify_batch_serialized")
         return ok
 
@@ -697,7 +815,7 @@ class BatchVerifier:
         """verify_serialized with every buffer in HBM (raw device pointers), asynchronous on `stream`: containers and
         compressed (version 2: uncompressed) commitments in, per-proof status words (0 / 1 / 2) out"""
         check(_lib.lib().bpp_range_verify_batch_serialized_device(self.handle, d_proofs, d_commitments, count,
-                                                                  (1 if transcript else 0) | (2 if uncompressed else 0), d_ok, d_workspace,
+                                                                  _flags(transcript, uncompressed), d_ok, d_workspace,
                                                                   workspace_bytes, stream or None),
               "bpp_range_verify_batch_serialized_device")
 
@@ -712,8 +830,7 @@ class BatchVerifier:
         Synchronises the stream.  -> (groups that failed, proofs re-verified exactly)"""
         stats = (ctypes.c_uint64 * 2)()
         check(_lib.lib().bpp_range_verify_batch_serialized_grouped_device(
-            self.handle, d_proofs, d_commitments, count, (1 if transcript else 0) | (2 if uncompressed else 0),
-            _weight_key_arg(weight_key, 0),
+            self.handle, d_proofs, d_commitments, count, _flags(transcript, uncompressed), _weight_key_arg(weight_key, 0),
             ctypes.c_uint64(index_base), group, d_ok, stats, d_workspace, workspace_bytes, stream or None),
             "bpp_range_verify_batch_serialized_grouped_device")
         return int(stats[0]), int(stats[1])
@@ -810,14 +927,7 @@ class BatchVerifier:
         check(_lib.lib().bpp_verifier_derive_challenges(self.handle, d_points, count, d_challenges, stream or None),
               "bpp_verifier_derive_challenges")
 
-    # ---- mixed batches: proof i of shape (n, ms[i]), ms[i] a power of two <= m (include/bpp_amd.h) ----
-    def _ms(self, ms) -> np.ndarray:
-        return np.ascontiguousarray(ms, dtype=np.uint32).reshape(-1)
-
-    def mixed_points(self, m_i: int) -> int:
-        """wire points of a proof record of shape (n, m_i): 3 + 2 log2(n m_i) + m_i"""
-        return 3 + 2 * ((self.n * m_i).bit_length() - 1) + m_i
-
+    # ---- mixed batches: proof i of shape (n, ms[i]), ms[i] a power of two <= m (include/bpp_amd.h; _Shapes) ----
     def mixed_workspace_bytes(self, ms) -> int:
         """bytes of device workspace run_mixed_device / derive_challenges_mixed_device need (0: an m_i is not taken)"""
         m = self._ms(ms)
@@ -847,8 +957,7 @@ class BatchVerifier:
         ms: m_i per proof -> ok (count,) u32 (bpp_range_verify_batch_mixed)"""
         m = self._ms(ms)
         count = len(m)
-        # an m_i the verifier does not take is reported by the library (BPP_E_ARG naming the proof)
-        taken = all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m)
+        taken = self._taken(m)
         need = sum(self.mixed_points(int(x)) for x in m) if taken else None
         if isinstance(records, (list, tuple)):
             if len(records) != count:
@@ -856,11 +965,7 @@ class BatchVerifier:
             for i, (r, x) in enumerate(zip(records, m)):
                 if taken and np.asarray(r).reshape(-1, self.arith.PW).shape[0] != self.mixed_points(int(x)):
                     raise RuntimeError("verify_wire_mixed: record %d does not hold %d points" % (i, self.mixed_points(int(x))))
-            pts = (np.concatenate([np.asarray(r, dtype=np.uint64).reshape(-1, self.arith.PW) for r in records])
-                   if count else np.zeros((0, self.arith.PW), dtype=np.uint64))
-        else:
-            pts = np.asarray(records, dtype=np.uint64).reshape(-1, self.arith.PW)
-        pts = np.ascontiguousarray(pts)
+        pts = self._wire_records(records)
         if need is not None and pts.shape[0] != need:
             raise RuntimeError("verify_wire_mixed: %d wire points, the shapes in ms need %d" % (pts.shape[0], need))
         sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 3, 4)
@@ -886,7 +991,7 @@ class BatchVerifier:
         Blocks while it uploads the per-proof index, the rest is on `stream`."""
         m = self._ms(ms)
         check(_lib.lib().bpp_range_verify_batch_serialized_mixed_device(
-            self.handle, d_proofs, d_commitments, _ptr(m), len(m), (1 if transcript else 0) | (2 if uncompressed else 0),
+            self.handle, d_proofs, d_commitments, _ptr(m), len(m), _flags(transcript, uncompressed),
             d_ok, d_workspace, workspace_bytes, stream or None), "bpp_range_verify_batch_serialized_mixed_device")
 
     def verify_serialized_mixed(self, proofs, commitments, ms=None, transcript: bool = False,
@@ -894,25 +999,10 @@ class BatchVerifier:
         """proofs: the containers back to back (bytes or u8 array), commitments: ms[i] encoded points per proof back to
         back; ms: m_i per proof, or None to frame the stream first (proofs_scan; BppError when it cannot be framed)
         -> status (count,) u32: 0 Ok / 1 VerificationError / 2 FormatError"""
-        def flat(x):
-            return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else \
-                np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
-        raw, cm = flat(proofs), flat(commitments)
-        version = 2 if uncompressed else 1
-        m = proofs_scan(self.arith, self.n, raw, version) if ms is None else self._ms(ms)
-        count = len(m)
-        # an m_i the verifier does not take is reported by the library (BPP_E_ARG naming the proof)
-        if all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m):
-            pb = uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)
-            need = sum(proof_bytes(self.arith, self.n, int(x), version) for x in m)
-            if len(raw) != need:
-                raise RuntimeError("verify_serialized_mixed: %d bytes of proofs, the shapes in ms need %d" % (len(raw), need))
-            if len(cm) != int(m.sum()) * pb:
-                raise RuntimeError("verify_serialized_mixed: ms[i] commitments per proof")
+        raw, cm, m, count = self._block("verify_serialized_mixed", proofs, commitments, ms, uncompressed)
         ok = np.zeros(count, dtype=np.uint32)
         check(_lib.lib().bpp_range_verify_batch_serialized_mixed(
-            self.handle, _ptr(raw) if len(raw) else None, _ptr(cm) if len(cm) else None, _ptr(m) if count else None, count,
-            (1 if transcript else 0) | (2 if uncompressed else 0), _ptr(ok) if count else None),
+            self.handle, _some(raw), _some(cm), _some(m), count, _flags(transcript, uncompressed), _some(ok)),
             "bpp_range_verify_batch_serialized_mixed")
         return ok
 
@@ -952,7 +1042,7 @@ class BatchVerifier:
         m = self._ms(ms)
         stats = (ctypes.c_uint64 * 2)()
         check(_lib.lib().bpp_range_verify_batch_serialized_grouped_mixed_device(
-            self.handle, d_proofs, d_commitments, _ptr(m), len(m), (1 if transcript else 0) | (2 if uncompressed else 0),
+            self.handle, d_proofs, d_commitments, _ptr(m), len(m), _flags(transcript, uncompressed),
             _weight_key_arg(weight_key, 0), ctypes.c_uint64(index_base), group, d_ok, stats, d_workspace, workspace_bytes,
             stream or None), "bpp_range_verify_batch_serialized_grouped_mixed_device")
         return int(stats[0]), int(stats[1])
@@ -998,8 +1088,7 @@ class BatchVerifier:
         pts = np.zeros((count, 3 + 2 * self.k, PW), dtype=np.uint64)
         sc = np.zeros((count, 3, 4), dtype=np.uint64)
         V = np.zeros((count, self.m, PW), dtype=np.uint64)
-        if blind_key is not None and (not transcript or len(blind_key) != 32):
-            raise ValueError("blind_key: 32 bytes, transcript mode only")
+        _prover_key(blind_key, transcript)
         if transcript:
             check(_lib.lib().bpp_range_prove_batch_fs(self.handle, _ptr(vals), _ptr(gm), count, blind_key, index_base,
                                                       _ptr(pts), _ptr(sc), _ptr(V)), "bpp_range_prove_batch_fs")
@@ -1126,7 +1215,7 @@ class BatchVerifier:
                             amount64: bool = False):
         """RangeProver::commit (range/prover.rs:28-42) for `count` resident values and gammas over this engine's g and h:
         d_out_V receives count wire points.  amount64=False keeps the `v as i32` of prover.rs:37.  Only enqueues."""
-        check(_lib.lib().bpp_commit_batch_device(self.handle, d_values, d_gammas, count, AMOUNT64 if amount64 else 0, d_out_V,
+        check(_lib.lib().bpp_commit_batch_device(self.handle, d_values, d_gammas, count, _flags(amount64=amount64), d_out_V,
                                                  stream or None), "bpp_commit_batch_device")
 
     def commit_batch(self, values, gammas, amount64: bool = False) -> np.ndarray:
@@ -1142,8 +1231,8 @@ class BatchVerifier:
         if len(gm) != count:
             raise RuntimeError("one gamma per value")
         out = np.zeros((count, self.arith.PW), dtype=np.uint64)
-        check(_lib.lib().bpp_commit_batch(self.handle, _ptr(vals) if count else None, _ptr(gm) if count else None, count,
-                                          AMOUNT64 if amount64 else 0, _ptr(out) if count else None), "bpp_commit_batch")
+        check(_lib.lib().bpp_commit_batch(self.handle, _some(vals), _some(gm), count, _flags(amount64=amount64), _some(out)),
+              "bpp_commit_batch")
         return out
 
     # ---- proving blocks of mixed aggregation sizes: proof i has ms[i] values (include/bpp_amd.h) ----
@@ -1152,7 +1241,7 @@ class BatchVerifier:
         not taken)"""
         m = self._ms(ms)
         f = _lib.lib().bpp_prover_serialized_mixed_workspace_bytes if serialized else _lib.lib().bpp_prover_mixed_workspace_bytes
-        return f(self.handle, _ptr(m) if len(m) else None, len(m))
+        return f(self.handle, _some(m), len(m))
 
     def prove_mixed_device(self, d_values: int, d_gammas: int, ms, d_out_points: int, d_out_scalars: int, d_workspace: int,
                            workspace_bytes: int, stream: int = 0, transcript: bool = False, d_out_challenges: int = 0,
@@ -1164,8 +1253,7 @@ class BatchVerifier:
         amount64=True (BPP_PROVE_AMOUNT64): commitments over the whole 64-bit values, not `v as i32` (range/prover.rs:37)."""
         m = self._ms(ms)
         check(_lib.lib().bpp_range_prove_batch_mixed_device(
-            self.handle, d_values, d_gammas, _ptr(m) if len(m) else None, len(m),
-            (1 if transcript else 0) | (AMOUNT64 if amount64 else 0), blind_key,
+            self.handle, d_values, d_gammas, _some(m), len(m), _flags(transcript, amount64=amount64), blind_key,
             ctypes.c_uint64(index_base), d_blinding or None, d_out_points, d_out_scalars, d_out_challenges or None, d_workspace,
             workspace_bytes, stream or None), "bpp_range_prove_batch_mixed_device")
 
@@ -1177,8 +1265,7 @@ class BatchVerifier:
         commitments per proof: the two inputs of verify_serialized_mixed_device"""
         m = self._ms(ms)
         check(_lib.lib().bpp_range_prove_batch_serialized_mixed_device(
-            self.handle, d_values, d_gammas, _ptr(m) if len(m) else None, len(m),
-            (1 if transcript else 0) | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0), blind_key,
+            self.handle, d_values, d_gammas, _some(m), len(m), _flags(transcript, uncompressed, amount64), blind_key,
             ctypes.c_uint64(index_base), d_blinding or None,
             d_out_proofs, d_out_commitments, d_workspace, workspace_bytes, stream or None),
             "bpp_range_prove_batch_serialized_mixed_device")
@@ -1204,21 +1291,19 @@ class BatchVerifier:
         a dedicated (n, m_i) engine of the same key proves; scalars (count, 3, 4).  challenges=True: also the list of
         per-proof challenge blocks (3 + k_i, 4).  amount64=True (BPP_PROVE_AMOUNT64): each V is v g + gamma h over the whole
         64-bit value instead of the `v as i32` of range/prover.rs:37, so amounts of 2^31 and more prove and verify."""
-        if blind_key is not None and (not transcript or len(blind_key) != 32):
-            raise ValueError("blind_key: 32 bytes, transcript mode only")
+        _prover_key(blind_key, transcript)
         vals, gm, ms = self._mixed_inputs(values, gammas)
         count, PW = len(ms), self.arith.PW
-        taken = all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in ms)
+        taken = self._taken(ms)
         npts = [self.mixed_points(int(x)) if taken else 0 for x in ms]
-        nch = [3 + (self.n * int(x)).bit_length() - 1 if taken else 0 for x in ms]
+        nch = [3 + self._rounds(int(x)) if taken else 0 for x in ms]
         pts = np.zeros((max(sum(npts), 1), PW), dtype=np.uint64)
         sc = np.zeros((count, 3, 4), dtype=np.uint64)
         ch = np.zeros((max(sum(nch), 1), 4), dtype=np.uint64)
         check(_lib.lib().bpp_range_prove_batch_mixed(
-            self.handle, _ptr(vals) if len(vals) else None, _ptr(gm) if len(vals) else None, _ptr(ms) if count else None, count,
-            (1 if transcript else 0) | (AMOUNT64 if amount64 else 0), blind_key, ctypes.c_uint64(index_base), _ptr(pts),
-            _ptr(sc) if count else None,
-            _ptr(ch) if challenges else None), "bpp_range_prove_batch_mixed")
+            self.handle, _some(vals), _some(gm), _some(ms), count, _flags(transcript, amount64=amount64), blind_key,
+            ctypes.c_uint64(index_base), _ptr(pts), _some(sc), _ptr(ch) if challenges else None),
+            "bpp_range_prove_batch_mixed")
         po, co = np.concatenate([[0], np.cumsum(npts)]).astype(int), np.concatenate([[0], np.cumsum(nch)]).astype(int)
         recs = [pts[po[i]:po[i + 1]] for i in range(count)]
         if challenges:
@@ -1229,20 +1314,16 @@ class BatchVerifier:
                                uncompressed: bool = False, amount64: bool = False):
         """prove_batch_mixed as bytes -> (proofs, commitments, ms): the containers back to back in caller order, ms[i]
         encoded commitments per proof back to back -- what verify_serialized_mixed takes, and a stream proofs_scan frames"""
-        if blind_key is not None and (not transcript or len(blind_key) != 32):
-            raise ValueError("blind_key: 32 bytes, transcript mode only")
+        _prover_key(blind_key, transcript)
         vals, gm, ms = self._mixed_inputs(values, gammas)
         count, version = len(ms), 2 if uncompressed else 1
-        taken = all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in ms)
         pb = uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)
-        nbytes = sum(proof_bytes(self.arith, self.n, int(x), version) for x in ms) if taken and pb else 0
+        nbytes = sum(proof_bytes(self.arith, self.n, int(x), version) for x in ms) if self._taken(ms) and pb else 0
         raw = np.zeros(max(nbytes, 1), dtype=np.uint8)
         cm = np.zeros(max(int(ms.sum()) * pb, 1), dtype=np.uint8)
         check(_lib.lib().bpp_range_prove_batch_serialized_mixed(
-            self.handle, _ptr(vals) if len(vals) else None, _ptr(gm) if len(vals) else None, _ptr(ms) if count else None, count,
-            (1 if transcript else 0) | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0), blind_key,
-            ctypes.c_uint64(index_base), _ptr(raw), _ptr(cm)),
-            "bpp_range_prove_batch_serialized_mixed")
+            self.handle, _some(vals), _some(gm), _some(ms), count, _flags(transcript, uncompressed, amount64), blind_key,
+            ctypes.c_uint64(index_base), _ptr(raw), _ptr(cm)), "bpp_range_prove_batch_serialized_mixed")
         return raw[:nbytes].tobytes(), cm[:int(ms.sum()) * pb].tobytes(), ms
 
     # ---- mask recovery and scanning: the receiver's side (include/bpp_amd.h "mask recovery") ----
@@ -1250,18 +1331,14 @@ class BatchVerifier:
         """host-side blinding arguments of the recovery calls -> (key, index array or None, blinding array or None)"""
         if blind_key is not None and len(blind_key) != 32:
             raise ValueError("blind_key: 32 bytes")
-        idx = bl = None
-        if index is not None:
-            idx = np.ascontiguousarray(np.asarray([int(x) for x in index], dtype=np.uint64))
-            if len(idx) != count:
-                raise RuntimeError("one index per proof")
+        idx, bl = _index_arg(index, count, "one index per proof"), None
         if blinding is not None:
             if isinstance(blinding, np.ndarray) and blinding.dtype == np.uint64:
                 bl = np.ascontiguousarray(blinding).reshape(-1, 4)
             else:
                 bl = scalars_to_wire([int(x) for row in blinding for x in row])
-            if all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in ms):
-                need = sum(5 + 2 * ((self.n * int(x)).bit_length() - 1) for x in ms)
+            if self._taken(ms):
+                need = sum(5 + 2 * self._rounds(int(x)) for x in ms)
                 if len(bl) != need:
                     raise RuntimeError("blinding: 5 + 2 k_i scalars per proof (%d in all), got %d" % (need, len(bl)))
         return blind_key, idx, bl
@@ -1271,7 +1348,7 @@ class BatchVerifier:
         not taken)"""
         m = self._ms(ms)
         f = _lib.lib().bpp_scan_serialized_mixed_workspace_bytes if serialized else _lib.lib().bpp_recover_mixed_workspace_bytes
-        return f(self.handle, _ptr(m) if len(m) else None, len(m))
+        return f(self.handle, _some(m), len(m))
 
     def recover_masks_device(self, d_scalars: int, ms, d_out_masks: int, d_workspace: int, workspace_bytes: int,
                              stream: int = 0, d_challenges: int = 0, blind_key: bytes = None, index_base: int = 0,
@@ -1282,7 +1359,7 @@ class BatchVerifier:
         Gamma_i is the output's mask.  Not a verification.  d_out_masks: (count, 4) u64 in caller order."""
         m = self._ms(ms)
         check(_lib.lib().bpp_range_recover_masks_mixed_device(
-            self.handle, d_scalars, _ptr(m) if len(m) else None, len(m), d_challenges or None, blind_key,
+            self.handle, d_scalars, _some(m), len(m), d_challenges or None, blind_key,
             ctypes.c_uint64(index_base), d_index or None, d_blinding or None, d_out_masks, d_workspace, workspace_bytes,
             stream or None), "bpp_range_recover_masks_mixed_device")
 
@@ -1302,15 +1379,14 @@ class BatchVerifier:
             ch = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.uint64).reshape(-1, 4) for c in challenges])
                                       if isinstance(challenges, (list, tuple)) else
                                       np.asarray(challenges, dtype=np.uint64).reshape(-1, 4))
-            if all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m):
-                need = sum(3 + (self.n * int(x)).bit_length() - 1 for x in m)
+            if self._taken(m):
+                need = sum(3 + self._rounds(int(x)) for x in m)
                 if len(ch) != need:
                     raise RuntimeError("recover_masks: 3 + k_i challenges per proof (%d in all), got %d" % (need, len(ch)))
         out = np.zeros((count, 4), dtype=np.uint64)
         check(_lib.lib().bpp_range_recover_masks_mixed(
-            self.handle, _ptr(sc) if count else None, _ptr(m) if count else None, count, _ptr(ch) if ch is not None else None,
-            key, ctypes.c_uint64(index_base), _ptr(idx) if idx is not None else None, _ptr(bl) if bl is not None else None,
-            _ptr(out) if count else None), "bpp_range_recover_masks_mixed")
+            self.handle, _some(sc), _some(m), count, _ptr(ch), key, ctypes.c_uint64(index_base), _ptr(idx), _ptr(bl),
+            _some(out)), "bpp_range_recover_masks_mixed")
         return [wire_to_int(x) for x in out]
 
     def scan_serialized_mixed_device(self, d_proofs: int, d_commitments: int, ms, d_out_masks: int, d_status: int,
@@ -1323,8 +1399,7 @@ class BatchVerifier:
         zero) / 3 unconfirmed -- no amount, or ms[i] > 1 (Gamma as computed).  A scan is not a verification."""
         m = self._ms(ms)
         check(_lib.lib().bpp_range_scan_serialized_mixed_device(
-            self.handle, d_proofs, d_commitments, _ptr(m) if len(m) else None, len(m),
-            (1 if transcript else 0) | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0), blind_key,
+            self.handle, d_proofs, d_commitments, _some(m), len(m), _flags(transcript, uncompressed, amount64), blind_key,
             ctypes.c_uint64(index_base), d_index or None, d_blinding or None, d_amounts or None, d_out_masks, d_status,
             d_workspace, workspace_bytes, stream or None), "bpp_range_scan_serialized_mixed_device")
 
@@ -1333,33 +1408,15 @@ class BatchVerifier:
                               blinding=None, amounts=None):
         """proofs, commitments, ms: as verify_serialized_mixed; amounts: None or one candidate amount per proof (read for
         ms[i] = 1) -> (status (count,) u32, [Gamma_i] as ints); see scan_serialized_mixed_device for the status words"""
-        def flat(x):
-            return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else \
-                np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
-        raw, cm = flat(proofs), flat(commitments)
-        version = 2 if uncompressed else 1
-        m = proofs_scan(self.arith, self.n, raw, version) if ms is None else self._ms(ms)
-        count = len(m)
-        if all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m):
-            pb = uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)
-            need = sum(proof_bytes(self.arith, self.n, int(x), version) for x in m)
-            if len(raw) != need:
-                raise RuntimeError("scan_serialized_mixed: %d bytes of proofs, the shapes in ms need %d" % (len(raw), need))
-            if len(cm) != int(m.sum()) * pb:
-                raise RuntimeError("scan_serialized_mixed: ms[i] commitments per proof")
+        raw, cm, m, count = self._block("scan_serialized_mixed", proofs, commitments, ms, uncompressed)
         key, idx, bl = self._blinding_args(blind_key, index, blinding, count, m)
-        am = None
-        if amounts is not None:
-            am = np.ascontiguousarray(np.asarray([int(x) for x in amounts], dtype=np.uint64))
-            if len(am) != count:
-                raise RuntimeError("scan_serialized_mixed: one candidate amount per proof")
+        am = None if amounts is None else \
+            _amounts_arg(amounts, count, "scan_serialized_mixed: one candidate amount per proof")
         masks = np.zeros((count, 4), dtype=np.uint64)
         status = np.zeros(count, dtype=np.uint32)
         check(_lib.lib().bpp_range_scan_serialized_mixed(
-            self.handle, _ptr(raw) if len(raw) else None, _ptr(cm) if len(cm) else None, _ptr(m) if count else None, count,
-            (1 if transcript else 0) | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0), key,
-            ctypes.c_uint64(index_base), _ptr(idx) if idx is not None else None, _ptr(bl) if bl is not None else None,
-            _ptr(am) if am is not None else None, _ptr(masks) if count else None, _ptr(status) if count else None),
+            self.handle, _some(raw), _some(cm), _some(m), count, _flags(transcript, uncompressed, amount64), key,
+            ctypes.c_uint64(index_base), _ptr(idx), _ptr(bl), _ptr(am), _some(masks), _some(status)),
             "bpp_range_scan_serialized_mixed")
         return status, [wire_to_int(x) for x in masks]
 
@@ -1367,7 +1424,7 @@ class BatchVerifier:
         """bytes of device workspace scan_serialized_mixed_keys_device needs (0: an m_i is not taken, or n_keys x count is
         over the bound)"""
         m = self._ms(ms)
-        return _lib.lib().bpp_scan_serialized_mixed_keys_workspace_bytes(self.handle, _ptr(m) if len(m) else None, len(m), n_keys)
+        return _lib.lib().bpp_scan_serialized_mixed_keys_workspace_bytes(self.handle, _some(m), len(m), n_keys)
 
     def scan_serialized_mixed_keys_device(self, d_proofs: int, d_commitments: int, ms, d_keys: int, n_keys: int,
                                           d_out_masks: int, d_status: int, d_workspace: int, workspace_bytes: int,
@@ -1380,9 +1437,8 @@ class BatchVerifier:
         Every key is a view key; a scan is not a verification."""
         m = self._ms(ms)
         check(_lib.lib().bpp_range_scan_serialized_mixed_keys_device(
-            self.handle, d_proofs, d_commitments, _ptr(m) if len(m) else None, len(m),
-            (1 if transcript else 0) | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0), d_keys or None, n_keys,
-            ctypes.c_uint64(index_base), d_index or None, d_amounts or None, d_out_masks, d_status, d_workspace,
+            self.handle, d_proofs, d_commitments, _some(m), len(m), _flags(transcript, uncompressed, amount64), d_keys or None,
+            n_keys, ctypes.c_uint64(index_base), d_index or None, d_amounts or None, d_out_masks, d_status, d_workspace,
             workspace_bytes, stream or None), "bpp_range_scan_serialized_mixed_keys_device")
 
     def scan_serialized_mixed_keys(self, proofs, commitments, ms=None, keys=(), transcript: bool = True,
@@ -1391,46 +1447,19 @@ class BatchVerifier:
         """proofs, commitments, ms: as scan_serialized_mixed; keys: a list of 32-byte strings; index: None or one blinding
         index per proof, shared by all keys; amounts: None or K x count candidate amounts (amounts[j][i]: proof i under key
         j) -> (status (K, count) u32, masks: K lists of count ints) (bpp_range_scan_serialized_mixed_keys)"""
-        def flat(x):
-            return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else \
-                np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
-        raw, cm = flat(proofs), flat(commitments)
-        version = 2 if uncompressed else 1
-        m = proofs_scan(self.arith, self.n, raw, version) if ms is None else self._ms(ms)
-        count = len(m)
-        keys = [bytes(k) for k in keys]
-        if any(len(k) != 32 for k in keys):
-            raise RuntimeError("scan_serialized_mixed_keys: every key is 32 bytes")
-        nk = len(keys)
-        if all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m):
-            pb = uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)
-            need = sum(proof_bytes(self.arith, self.n, int(x), version) for x in m)
-            if len(raw) != need:
-                raise RuntimeError("scan_serialized_mixed_keys: %d bytes of proofs, the shapes in ms need %d" % (len(raw), need))
-            if len(cm) != int(m.sum()) * pb:
-                raise RuntimeError("scan_serialized_mixed_keys: ms[i] commitments per proof")
-        idx = None
-        if index is not None:
-            idx = np.ascontiguousarray(np.asarray([int(x) for x in index], dtype=np.uint64))
-            if len(idx) != count:
-                raise RuntimeError("scan_serialized_mixed_keys: one blinding index per proof")
-        am = None
-        if amounts is not None:
-            am = np.ascontiguousarray(np.asarray([[int(x) for x in row] for row in amounts], dtype=np.uint64).reshape(-1))
-            if len(am) != nk * count:
-                raise RuntimeError("scan_serialized_mixed_keys: K x count candidate amounts")
-        kb = np.frombuffer(b"".join(keys), dtype=np.uint8).copy() if nk else None
-        masks = np.zeros((nk, count, 4), dtype=np.uint64)
-        status = np.zeros((nk, count), dtype=np.uint32)
-        some = nk > 0 and count > 0
-        check(_lib.lib().bpp_range_scan_serialized_mixed_keys(
-            self.handle, _ptr(raw) if len(raw) else None, _ptr(cm) if len(cm) else None, _ptr(m) if count else None, count,
-            (1 if transcript else 0) | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0),
-            _ptr(kb) if kb is not None else None, nk, ctypes.c_uint64(index_base), _ptr(idx) if idx is not None else None,
-            _ptr(am) if am is not None and some else None, _ptr(masks) if some else None, _ptr(status) if some else None),
-            "bpp_range_scan_serialized_mixed_keys")
-        if kb is not None:
-            kb[:] = 0   # the packed copy of the keys made here
+        where = "scan_serialized_mixed_keys"
+        with _packed_keys(where, keys) as (kb, nk):
+            raw, cm, m, count = self._block(where, proofs, commitments, ms, uncompressed)
+            idx = _index_arg(index, count, where + ": one blinding index per proof")
+            am = None if amounts is None else \
+                _amounts_arg(amounts, nk * count, where + ": K x count candidate amounts", rows=True)
+            masks = np.zeros((nk, count, 4), dtype=np.uint64)
+            status = np.zeros((nk, count), dtype=np.uint32)
+            some = nk > 0 and count > 0
+            check(_lib.lib().bpp_range_scan_serialized_mixed_keys(
+                self.handle, _some(raw), _some(cm), _some(m), count, _flags(transcript, uncompressed, amount64), _ptr(kb), nk,
+                ctypes.c_uint64(index_base), _ptr(idx), _ptr(am) if some else None, _ptr(masks) if some else None,
+                _ptr(status) if some else None), "bpp_range_scan_serialized_mixed_keys")
         return status, [[wire_to_int(x) for x in row] for row in masks]
 
     # ---- sealed amounts; verifying a block and listing the outputs of many keys (include/bpp_amd.h) ----
@@ -1444,16 +1473,11 @@ class BatchVerifier:
     def seal_amounts(self, blind_key: bytes, amounts, index_base: int = 0, index=None) -> np.ndarray:
         """amounts: ints below 2^64; index: None or one blinding index per amount -> (count,) u64, amount XOR pad; applied
         to sealed amounts it opens them (bpp_amounts_seal)"""
-        am = np.ascontiguousarray(np.asarray([int(x) for x in amounts], dtype=np.uint64))
-        idx = None
-        if index is not None:
-            idx = np.ascontiguousarray(np.asarray([int(x) for x in index], dtype=np.uint64))
-            if len(idx) != len(am):
-                raise RuntimeError("seal_amounts: one blinding index per amount")
+        am = _amounts_arg(amounts)
+        idx = _index_arg(index, len(am), "seal_amounts: one blinding index per amount")
         out = np.zeros(len(am), dtype=np.uint64)
-        check(_lib.lib().bpp_amounts_seal(self.arith.handle, blind_key, ctypes.c_uint64(index_base),
-                                          _ptr(idx) if idx is not None else None, _ptr(am) if len(am) else None, len(am),
-                                          _ptr(out) if len(am) else None), "bpp_amounts_seal")
+        check(_lib.lib().bpp_amounts_seal(self.arith.handle, blind_key, ctypes.c_uint64(index_base), _ptr(idx), _some(am),
+                                          len(am), _some(out)), "bpp_amounts_seal")
         return out
 
     def view_tags_device(self, blind_key: bytes, count: int, d_out: int, stream: int = 0, index_base: int = 0, d_index: int = 0):
@@ -1465,16 +1489,10 @@ class BatchVerifier:
     def view_tags(self, blind_key: bytes, count: int = None, index_base: int = 0, index=None) -> np.ndarray:
         """count outputs from index_base, or one blinding index per output -> (count,) u8, the first byte of
         SHA-256(key || "bppt" || index || 0 || 0) (bpp_view_tags).  The tag authenticates nothing."""
-        idx = None
-        if index is not None:
-            idx = np.ascontiguousarray(np.asarray([int(x) for x in index], dtype=np.uint64))
-            if count is not None and len(idx) != count:
-                raise RuntimeError("view_tags: one blinding index per output")
-            count = len(idx)
-        count = int(count or 0)
+        idx = _index_arg(index, count, "view_tags: one blinding index per output")
+        count = int(count or 0) if idx is None else len(idx)
         out = np.zeros(count, dtype=np.uint8)
-        check(_lib.lib().bpp_view_tags(self.arith.handle, blind_key, ctypes.c_uint64(index_base),
-                                       _ptr(idx) if idx is not None and count else None, count, _ptr(out) if count else None),
+        check(_lib.lib().bpp_view_tags(self.arith.handle, blind_key, ctypes.c_uint64(index_base), _some(idx), count, _some(out)),
               "bpp_view_tags")
         return out
 
@@ -1482,13 +1500,13 @@ class BatchVerifier:
         """bytes of device workspace verify_find_serialized_mixed_keys_device needs when d_tags is given (0 where
         verify_find_workspace_bytes gives 0): room for every pair being a candidate"""
         m = self._ms(ms)
-        return _lib.lib().bpp_verify_find_tagged_workspace_bytes(self.handle, _ptr(m) if len(m) else None, len(m), n_keys)
+        return _lib.lib().bpp_verify_find_tagged_workspace_bytes(self.handle, _some(m), len(m), n_keys)
 
     def verify_find_workspace_bytes(self, ms, n_keys: int) -> int:
         """bytes of device workspace verify_find_serialized_mixed_keys_device needs (0: an m_i is not taken, or
         n_keys x count is over the bound); grows with n_keys"""
         m = self._ms(ms)
-        return _lib.lib().bpp_verify_find_serialized_mixed_keys_workspace_bytes(self.handle, _ptr(m) if len(m) else None, len(m),
+        return _lib.lib().bpp_verify_find_serialized_mixed_keys_workspace_bytes(self.handle, _some(m), len(m),
                                                                                 n_keys)
 
     def verify_find_serialized_mixed_keys_device(self, d_proofs: int, d_commitments: int, ms, d_keys: int, n_keys: int,
@@ -1506,19 +1524,17 @@ class BatchVerifier:
         its tag does not match, takes verify_find_tagged_workspace_bytes of workspace and writes the number of pairs that
         passed the tag test to d_n_candidates (one u32) when that is given."""
         m = self._ms(ms)
+        head = (self.handle, d_proofs, d_commitments, _some(m), len(m), _flags(True, uncompressed, amount64, sealed),
+                d_keys or None, n_keys, ctypes.c_uint64(index_base), d_index or None, d_amounts or None, d_ok or None,
+                d_hits or None, max_hits, d_n_hits or None)
+        tail = (d_workspace, workspace_bytes, stream or None)
         if d_tags:
-            check(_lib.lib().bpp_range_verify_find_tagged_serialized_mixed_keys_device(
-                self.handle, d_proofs, d_commitments, _ptr(m) if len(m) else None, len(m),
-                1 | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0) | (AMOUNTS_SEALED if sealed else 0), d_keys or None,
-                n_keys, ctypes.c_uint64(index_base), d_index or None, d_amounts or None, d_ok or None, d_hits or None, max_hits,
-                d_n_hits or None, d_tags, d_n_candidates or None, d_workspace, workspace_bytes, stream or None),
-                "bpp_range_verify_find_tagged_serialized_mixed_keys_device")
-            return
-        check(_lib.lib().bpp_range_verify_find_serialized_mixed_keys_device(
-            self.handle, d_proofs, d_commitments, _ptr(m) if len(m) else None, len(m),
-            1 | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0) | (AMOUNTS_SEALED if sealed else 0), d_keys or None,
-            n_keys, ctypes.c_uint64(index_base), d_index or None, d_amounts or None, d_ok or None, d_hits or None, max_hits,
-            d_n_hits or None, d_workspace, workspace_bytes, stream or None), "bpp_range_verify_find_serialized_mixed_keys_device")
+            check(_lib.lib().bpp_range_verify_find_tagged_serialized_mixed_keys_device(*head, d_tags, d_n_candidates or None,
+                                                                                       *tail),
+                  "bpp_range_verify_find_tagged_serialized_mixed_keys_device")
+        else:
+            check(_lib.lib().bpp_range_verify_find_serialized_mixed_keys_device(*head, *tail),
+                  "bpp_range_verify_find_serialized_mixed_keys_device")
 
     def verify_find_serialized_mixed_keys(self, proofs, commitments, ms=None, keys=(), amounts=(), sealed: bool = False,
                                           uncompressed: bool = False, amount64: bool = False, index_base: int = 0, index=None,
@@ -1531,69 +1547,37 @@ class BatchVerifier:
         and no hit is listed.  tags (None or 0: the untagged entry): one view-tag byte per proof, shared by all keys -- a pair
         whose tag does not match its key is ruled out after one hash, and the result is (ok, hits, found, candidates) with
         candidates the number of pairs that passed the tag test (bpp_range_verify_find_tagged_serialized_mixed_keys)."""
-        def flat(x):
-            return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else \
-                np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
-        raw, cm = flat(proofs), flat(commitments)
-        version = 2 if uncompressed else 1
-        m = proofs_scan(self.arith, self.n, raw, version) if ms is None else self._ms(ms)
-        count = len(m)
-        keys = [bytes(k) for k in keys]
-        if any(len(k) != 32 for k in keys):
-            raise RuntimeError("verify_find_serialized_mixed_keys: every key is 32 bytes")
-        nk = len(keys)
-        if all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m):
-            pb = uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)
-            need = sum(proof_bytes(self.arith, self.n, int(x), version) for x in m)
-            if len(raw) != need:
-                raise RuntimeError("verify_find_serialized_mixed_keys: %d bytes of proofs, the shapes in ms need %d" % (len(raw), need))
-            if len(cm) != int(m.sum()) * pb:
-                raise RuntimeError("verify_find_serialized_mixed_keys: ms[i] commitments per proof")
-        idx = None
-        if index is not None:
-            idx = np.ascontiguousarray(np.asarray([int(x) for x in index], dtype=np.uint64))
-            if len(idx) != count:
-                raise RuntimeError("verify_find_serialized_mixed_keys: one blinding index per proof")
-        if sealed:
-            am = np.ascontiguousarray(np.asarray([int(x) for x in amounts], dtype=np.uint64).reshape(-1))
-            if len(am) != count:
-                raise RuntimeError("verify_find_serialized_mixed_keys: one sealed amount per proof")
-        else:
-            am = np.ascontiguousarray(np.asarray([[int(x) for x in row] for row in amounts], dtype=np.uint64).reshape(-1))
-            if len(am) != nk * count:
-                raise RuntimeError("verify_find_serialized_mixed_keys: K x count candidate amounts")
-        tg = None
-        if tags is not None and not (isinstance(tags, int) and tags == 0):
-            tg = flat(tags) if isinstance(tags, (bytes, bytearray, memoryview)) else \
-                np.ascontiguousarray(np.asarray([int(x) for x in tags], dtype=np.uint8).reshape(-1))
-            if len(tg) != count:
-                raise RuntimeError("verify_find_serialized_mixed_keys: one view tag per proof")
-        cap = nk * count if max_hits is None else int(max_hits)
-        kb = np.frombuffer(b"".join(keys), dtype=np.uint8).copy() if nk else None
-        ok = np.zeros(count, dtype=np.uint32)
-        rec = np.zeros((cap, 12), dtype=np.uint32)
-        found = np.zeros(1, dtype=np.uint32)
-        cands = np.zeros(1, dtype=np.uint32)
-        some = nk > 0 and count > 0
-        if tg is not None:
-            check(_lib.lib().bpp_range_verify_find_tagged_serialized_mixed_keys(
-                self.handle, _ptr(raw) if len(raw) else None, _ptr(cm) if len(cm) else None, _ptr(m) if count else None, count,
-                1 | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0) | (AMOUNTS_SEALED if sealed else 0),
-                _ptr(kb) if kb is not None else None, nk, ctypes.c_uint64(index_base), _ptr(idx) if idx is not None else None,
-                _ptr(am) if some else None, _ptr(ok) if count else None, _ptr(rec) if cap else None, cap, _ptr(found),
-                _ptr(tg) if some else None, _ptr(cands)), "bpp_range_verify_find_tagged_serialized_mixed_keys")
-        else:
-            check(_lib.lib().bpp_range_verify_find_serialized_mixed_keys(
-                self.handle, _ptr(raw) if len(raw) else None, _ptr(cm) if len(cm) else None, _ptr(m) if count else None, count,
-                1 | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0) | (AMOUNTS_SEALED if sealed else 0),
-                _ptr(kb) if kb is not None else None, nk, ctypes.c_uint64(index_base), _ptr(idx) if idx is not None else None,
-                _ptr(am) if some else None, _ptr(ok) if count else None, _ptr(rec) if cap else None, cap, _ptr(found)),
-                "bpp_range_verify_find_serialized_mixed_keys")
-        if kb is not None:
-            kb[:] = 0   # the packed copy of the keys made here
+        where = "verify_find_serialized_mixed_keys"
+        with _packed_keys(where, keys) as (kb, nk):
+            raw, cm, m, count = self._block(where, proofs, commitments, ms, uncompressed)
+            idx = _index_arg(index, count, where + ": one blinding index per proof")
+            if sealed:
+                am = _amounts_arg(amounts, count, where + ": one sealed amount per proof")
+            else:
+                am = _amounts_arg(amounts, nk * count, where + ": K x count candidate amounts", rows=True)
+            tg = None
+            if tags is not None and not (isinstance(tags, int) and tags == 0):
+                tg = _tags_arg(tags)
+                if len(tg) != count:
+                    raise RuntimeError(where + ": one view tag per proof")
+            cap = nk * count if max_hits is None else int(max_hits)
+            ok = np.zeros(count, dtype=np.uint32)
+            rec = np.zeros((cap, 12), dtype=np.uint32)
+            found = np.zeros(1, dtype=np.uint32)
+            cands = np.zeros(1, dtype=np.uint32)
+            some = nk > 0 and count > 0
+            head = (self.handle, _some(raw), _some(cm), _some(m), count, _flags(True, uncompressed, amount64, sealed), _ptr(kb),
+                    nk, ctypes.c_uint64(index_base), _ptr(idx), _ptr(am) if some else None, _some(ok), _some(rec), cap,
+                    _ptr(found))
+            if tg is None:
+                check(_lib.lib().bpp_range_verify_find_serialized_mixed_keys(*head),
+                      "bpp_range_verify_find_serialized_mixed_keys")
+            else:
+                check(_lib.lib().bpp_range_verify_find_tagged_serialized_mixed_keys(*head, _ptr(tg) if some else None,
+                                                                                    _ptr(cands)),
+                      "bpp_range_verify_find_tagged_serialized_mixed_keys")
         n = int(found[0])
-        hits = [(int(r[0]), int(r[1]), int(r[2]) | int(r[3]) << 32, wire_to_int(np.ascontiguousarray(r[4:]).view(np.uint64))) for r in rec[:min(n, cap)]]
-        return (ok, hits, n) if tg is None else (ok, hits, n, int(cands[0]))
+        return (ok, _hits(rec, n), n) if tg is None else (ok, _hits(rec, n), n, int(cands[0]))
 
     # ---- outputs with masks derived from their recipients' keys, aggregated proofs included (include/bpp_amd.h) ----
     def make_outputs_device(self, d_keys: int, d_index: int, d_j: int, d_amounts: int, n_out: int, d_out_masks: int = 0,
@@ -1612,38 +1596,31 @@ class BatchVerifier:
         tags (n_out,) u8): output j of proof i under output_mask / output_pad / output_tag(key, index of i, j)
         (bpp_outputs_make).  The masks are secret."""
         m = [int(x) for x in ms]
-        keys = [bytes(k) for k in keys]
-        if any(len(k) != 32 for k in keys):
-            raise RuntimeError("make_outputs: every key is 32 bytes")
-        am = np.ascontiguousarray(np.asarray([int(x) for x in amounts], dtype=np.uint64))
-        n_out = sum(m)
-        if len(keys) != n_out or len(am) != n_out:
-            raise RuntimeError("make_outputs: one key and one amount per output, sum(ms) of them")
-        if index is not None:
-            pidx = np.asarray([int(x) for x in index], dtype=np.uint64)
-            if len(pidx) != len(m):
-                raise RuntimeError("make_outputs: one blinding index per proof")
-        else:
-            pidx = np.uint64(index_base) + np.arange(len(m), dtype=np.uint64)
-        reps = np.asarray(m, dtype=np.int64)
-        idx = np.ascontiguousarray(np.repeat(pidx, reps))
-        first = np.repeat(np.cumsum(reps) - reps, reps)
-        j = np.ascontiguousarray((np.arange(n_out, dtype=np.int64) - first).astype(np.uint32))
-        kb = np.frombuffer(b"".join(keys), dtype=np.uint8).copy() if n_out else None
-        masks = np.zeros((n_out, 4), dtype=np.uint64)
-        sealed = np.zeros(n_out, dtype=np.uint64)
-        tags = np.zeros(n_out, dtype=np.uint8)
-        if n_out:
-            check(_lib.lib().bpp_outputs_make(self.arith.handle, _ptr(kb), _ptr(idx), _ptr(j), _ptr(am), n_out, _ptr(masks),
-                                              _ptr(sealed), _ptr(tags)), "bpp_outputs_make")
-            kb[:] = 0   # the packed copy of the keys made here
+        with _packed_keys("make_outputs", keys) as (kb, nk):
+            am = _amounts_arg(amounts)
+            n_out = sum(m)
+            if nk != n_out or len(am) != n_out:
+                raise RuntimeError("make_outputs: one key and one amount per output, sum(ms) of them")
+            pidx = _index_arg(index, len(m), "make_outputs: one blinding index per proof")
+            if pidx is None:
+                pidx = np.uint64(index_base) + np.arange(len(m), dtype=np.uint64)
+            reps = np.asarray(m, dtype=np.int64)
+            idx = np.ascontiguousarray(np.repeat(pidx, reps))
+            first = np.repeat(np.cumsum(reps) - reps, reps)
+            j = np.ascontiguousarray((np.arange(n_out, dtype=np.int64) - first).astype(np.uint32))
+            masks = np.zeros((n_out, 4), dtype=np.uint64)
+            sealed = np.zeros(n_out, dtype=np.uint64)
+            tags = np.zeros(n_out, dtype=np.uint8)
+            if n_out:
+                check(_lib.lib().bpp_outputs_make(self.arith.handle, _ptr(kb), _ptr(idx), _ptr(j), _ptr(am), n_out, _ptr(masks),
+                                                  _ptr(sealed), _ptr(tags)), "bpp_outputs_make")
         return masks, sealed, tags
 
     def verify_find_outputs_workspace_bytes(self, ms, n_keys: int) -> int:
         """bytes of device workspace verify_find_outputs_serialized_mixed_keys_device needs (0: an m_i is not taken, or
         n_keys x sum(ms) is over the bound)"""
         m = self._ms(ms)
-        return _lib.lib().bpp_verify_find_outputs_workspace_bytes(self.handle, _ptr(m) if len(m) else None, len(m), n_keys)
+        return _lib.lib().bpp_verify_find_outputs_workspace_bytes(self.handle, _some(m), len(m), n_keys)
 
     def verify_find_outputs_serialized_mixed_keys_device(self, d_proofs: int, d_commitments: int, ms, d_keys: int, n_keys: int,
                                                          d_sealed: int, d_tags: int, d_ok: int, d_hits: int, max_hits: int,
@@ -1658,9 +1635,8 @@ class BatchVerifier:
         (bpp_range_verify_find_outputs_serialized_mixed_keys_device)."""
         m = self._ms(ms)
         check(_lib.lib().bpp_range_verify_find_outputs_serialized_mixed_keys_device(
-            self.handle, d_proofs, d_commitments, _ptr(m) if len(m) else None, len(m),
-            1 | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0), d_keys or None, n_keys, ctypes.c_uint64(index_base),
-            d_index or None, d_sealed or None, d_tags or None, d_ok or None, d_hits or None, max_hits, d_n_hits or None,
+            self.handle, d_proofs, d_commitments, _some(m), len(m), _flags(True, uncompressed, amount64), d_keys or None, n_keys,
+            ctypes.c_uint64(index_base), d_index or None, d_sealed or None, d_tags or None, d_ok or None, d_hits or None, max_hits, d_n_hits or None,
             d_n_candidates or None, d_workspace, workspace_bytes, stream or None),
             "bpp_range_verify_find_outputs_serialized_mixed_keys_device")
 
@@ -1673,55 +1649,26 @@ class BatchVerifier:
         (key_no, output_no), at most max_hits of them (None: room for every pair); found the number of hits there are;
         n_candidates the pairs that passed the tag test (bpp_range_verify_find_outputs_serialized_mixed_keys).  With no
         keys the block is verified all the same and no hit is listed."""
-        def flat(x):
-            return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else \
-                np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
-        raw, cm = flat(proofs), flat(commitments)
-        version = 2 if uncompressed else 1
-        m = proofs_scan(self.arith, self.n, raw, version) if ms is None else self._ms(ms)
-        count = len(m)
-        n_out = int(m.sum()) if count else 0
-        keys = [bytes(k) for k in keys]
-        if any(len(k) != 32 for k in keys):
-            raise RuntimeError("verify_find_outputs_serialized_mixed_keys: every key is 32 bytes")
-        nk = len(keys)
-        if all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m):
-            pb = uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)
-            need = sum(proof_bytes(self.arith, self.n, int(x), version) for x in m)
-            if len(raw) != need:
-                raise RuntimeError("verify_find_outputs_serialized_mixed_keys: %d bytes of proofs, the shapes in ms need %d"
-                                   % (len(raw), need))
-            if len(cm) != n_out * pb:
-                raise RuntimeError("verify_find_outputs_serialized_mixed_keys: ms[i] commitments per proof")
-        idx = None
-        if index is not None:
-            idx = np.ascontiguousarray(np.asarray([int(x) for x in index], dtype=np.uint64))
-            if len(idx) != count:
-                raise RuntimeError("verify_find_outputs_serialized_mixed_keys: one blinding index per proof")
-        se = np.ascontiguousarray(np.asarray([int(x) for x in sealed], dtype=np.uint64).reshape(-1))
-        tg = flat(tags) if isinstance(tags, (bytes, bytearray, memoryview)) else \
-            np.ascontiguousarray(np.asarray([int(x) for x in tags], dtype=np.uint8).reshape(-1))
-        if nk and (len(se) != n_out or len(tg) != n_out):
-            raise RuntimeError("verify_find_outputs_serialized_mixed_keys: one sealed amount and one tag per output")
-        cap = nk * n_out if max_hits is None else int(max_hits)
-        kb = np.frombuffer(b"".join(keys), dtype=np.uint8).copy() if nk else None
-        ok = np.zeros(count, dtype=np.uint32)
-        rec = np.zeros((cap, 12), dtype=np.uint32)
-        found = np.zeros(1, dtype=np.uint32)
-        cands = np.zeros(1, dtype=np.uint32)
-        some = nk > 0 and count > 0
-        check(_lib.lib().bpp_range_verify_find_outputs_serialized_mixed_keys(
-            self.handle, _ptr(raw) if len(raw) else None, _ptr(cm) if len(cm) else None, _ptr(m) if count else None, count,
-            1 | (2 if uncompressed else 0) | (AMOUNT64 if amount64 else 0), _ptr(kb) if kb is not None else None, nk,
-            ctypes.c_uint64(index_base), _ptr(idx) if idx is not None else None, _ptr(se) if some else None,
-            _ptr(tg) if some else None, _ptr(ok) if count else None, _ptr(rec) if cap else None, cap, _ptr(found), _ptr(cands)),
-            "bpp_range_verify_find_outputs_serialized_mixed_keys")
-        if kb is not None:
-            kb[:] = 0   # the packed copy of the keys made here
+        where = "verify_find_outputs_serialized_mixed_keys"
+        with _packed_keys(where, keys) as (kb, nk):
+            raw, cm, m, count = self._block(where, proofs, commitments, ms, uncompressed)
+            n_out = int(m.sum())
+            idx = _index_arg(index, count, where + ": one blinding index per proof")
+            se, tg = _amounts_arg(sealed), _tags_arg(tags)
+            if nk and (len(se) != n_out or len(tg) != n_out):
+                raise RuntimeError(where + ": one sealed amount and one tag per output")
+            cap = nk * n_out if max_hits is None else int(max_hits)
+            ok = np.zeros(count, dtype=np.uint32)
+            rec = np.zeros((cap, 12), dtype=np.uint32)
+            found = np.zeros(1, dtype=np.uint32)
+            cands = np.zeros(1, dtype=np.uint32)
+            some = nk > 0 and count > 0
+            check(_lib.lib().bpp_range_verify_find_outputs_serialized_mixed_keys(
+                self.handle, _some(raw), _some(cm), _some(m), count, _flags(True, uncompressed, amount64), _ptr(kb), nk,
+                ctypes.c_uint64(index_base), _ptr(idx), _ptr(se) if some else None, _ptr(tg) if some else None, _some(ok),
+                _some(rec), cap, _ptr(found), _ptr(cands)), "bpp_range_verify_find_outputs_serialized_mixed_keys")
         n = int(found[0])
-        hits = [(int(r[0]), int(r[1]), int(r[2]) | int(r[3]) << 32, wire_to_int(np.ascontiguousarray(r[4:]).view(np.uint64)))
-                for r in rec[:min(n, cap)]]
-        return ok, hits, n, int(cands[0])
+        return ok, _hits(rec, n), n, int(cands[0])
 
 
 def shard_cuts(ms, count: int, world: int) -> np.ndarray:
@@ -1732,11 +1679,11 @@ def shard_cuts(ms, count: int, world: int) -> np.ndarray:
     if m is not None and len(m) != count:
         raise ValueError("shard_cuts: one cost per proof")
     cuts = np.zeros(world + 1 if 0 < world <= 16 else 17, dtype=np.uintp)
-    check(_lib.lib().bpp_shard_cuts(_ptr(m) if m is not None and count else None, count, world, _ptr(cuts)), "bpp_shard_cuts")
+    check(_lib.lib().bpp_shard_cuts(_some(m), count, world, _ptr(cuts)), "bpp_shard_cuts")
     return cuts.astype(np.int64)
 
 
-class VerifierPool:
+class VerifierPool(_Shapes):
     """One batch sharded over several devices in ONE process (include/bpp_amd.h "verifier pool"): per entry of `devices`
     a context and a verifier of capacity (n, m) on that device, the batch cut by shard_cuts, the shards' passes run on a
     host thread each, verdicts in caller order.  An ordinal may repeat -- devices=(0, 0) exercises two shards on a one-GPU
@@ -1752,7 +1699,7 @@ class VerifierPool:
         h = ctypes.c_void_p()
         G = np.ascontiguousarray(pk.G_vec)
         H = np.ascontiguousarray(pk.H_vec)
-        check(_lib.lib().bpp_pool_create(pk.arith.curve, _ptr(dev) if len(dev) else None, len(dev), _ptr(pk.gh), _ptr(G),
+        check(_lib.lib().bpp_pool_create(pk.arith.curve, _some(dev), len(dev), _ptr(pk.gh), _ptr(G),
                                          _ptr(H), n, m, window_bits, ctypes.byref(h)), "bpp_pool_create")
         self.handle = h
         self.size = _lib.lib().bpp_pool_size(h)
@@ -1779,38 +1726,25 @@ class VerifierPool:
         """the cuts a verify call of this pool makes for a batch with aggregation sizes ms (None: uniform, `count` proofs)"""
         return shard_cuts(ms, len(ms) if ms is not None else count, self.size)
 
-    def _one(self) -> BatchVerifier:
-        v = BatchVerifier.__new__(BatchVerifier)   # the shape helpers of a verifier, no handle
-        v.arith, v.n, v.m, v.handle, v._owner = self.arith, self.n, self.m, None, self
-        return v
-
     def verify_wire_mixed(self, records, scalars, ms=None) -> np.ndarray:
         """BatchVerifier.verify_wire_mixed over the pool (bpp_pool_verify_mixed).  ms None: a uniform batch at the
         capacity shape, records (count, 3 + 2k + m, PW)."""
-        if isinstance(records, (list, tuple)):
-            pts = (np.concatenate([np.asarray(r, dtype=np.uint64).reshape(-1, self.arith.PW) for r in records])
-                   if len(records) else np.zeros((0, self.arith.PW), dtype=np.uint64))
-        else:
-            pts = np.asarray(records, dtype=np.uint64).reshape(-1, self.arith.PW)
-        pts = np.ascontiguousarray(pts)
+        pts = self._wire_records(records)
         sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 3, 4)
         count = sc.shape[0]
-        one = self._one()
         if ms is None:
             m = None
-            need = count * one.mixed_points(self.m)
+            need = count * self.mixed_points(self.m)
         else:
-            m = one._ms(ms)
+            m = self._ms(ms)
             if len(m) != count:
                 raise RuntimeError("verify_wire_mixed: one scalar triple per entry of ms")
-            # an m_i the pool does not take is reported by the library (BPP_E_ARG naming the proof)
-            taken = all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m)
-            need = sum(one.mixed_points(int(x)) for x in m) if taken else None
+            need = sum(self.mixed_points(int(x)) for x in m) if self._taken(m) else None
         if need is not None and pts.shape[0] != need:
             raise RuntimeError("verify_wire_mixed: %d wire points, the shapes need %d" % (pts.shape[0], need))
         ok = np.zeros(count, dtype=np.uint32)
-        check(_lib.lib().bpp_pool_verify_mixed(self.handle, _ptr(pts), _ptr(sc), _ptr(m) if m is not None else None, count,
-                                               _ptr(ok)), "bpp_pool_verify_mixed")
+        check(_lib.lib().bpp_pool_verify_mixed(self.handle, _ptr(pts), _ptr(sc), _ptr(m), count, _ptr(ok)),
+              "bpp_pool_verify_mixed")
         return ok
 
     def verify_serialized_mixed(self, proofs, commitments, ms=None, transcript: bool = False, uncompressed: bool = False,
@@ -1821,41 +1755,26 @@ class VerifierPool:
         weighted by PRF(weight_key, index_base + i) whatever the cut (weight_key None = os.urandom(32)); with
         return_stats -> (status, (groups that failed, proofs re-verified exactly)), summed over the shards -- the stats
         depend on the cut, the statuses do not."""
-        def flat(x):
-            return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else \
-                np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
-        raw, cm = flat(proofs), flat(commitments)
-        version = 2 if uncompressed else 1
-        m = proofs_scan(self.arith, self.n, raw, version) if ms is None else np.ascontiguousarray(ms, dtype=np.uint32).reshape(-1)
-        count = len(m)
-        if all(0 < int(x) <= self.m and not int(x) & (int(x) - 1) for x in m):
-            pb = uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)
-            need = sum(proof_bytes(self.arith, self.n, int(x), version) for x in m)
-            if len(raw) != need:
-                raise RuntimeError("verify_serialized_mixed: %d bytes of proofs, the shapes in ms need %d" % (len(raw), need))
-            if len(cm) != int(m.sum()) * pb:
-                raise RuntimeError("verify_serialized_mixed: ms[i] commitments per proof")
+        raw, cm, m, count = self._block("verify_serialized_mixed", proofs, commitments, ms, uncompressed)
         ok = np.zeros(count, dtype=np.uint32)
         stats = (ctypes.c_uint64 * 2)()
         check(_lib.lib().bpp_pool_verify_serialized_mixed(
-            self.handle, _ptr(raw) if len(raw) else None, _ptr(cm) if len(cm) else None, _ptr(m) if count else None, count,
-            (1 if transcript else 0) | (2 if uncompressed else 0), 1 if grouped else 0,
+            self.handle, _some(raw), _some(cm), _some(m), count, _flags(transcript, uncompressed), 1 if grouped else 0,
             _weight_key_arg(weight_key, 0) if grouped else None, ctypes.c_uint64(index_base), group if grouped else 0,
-            _ptr(ok) if count else None, stats), "bpp_pool_verify_serialized_mixed")
+            _some(ok), stats), "bpp_pool_verify_serialized_mixed")
         return (ok, (int(stats[0]), int(stats[1]))) if return_stats else ok
 
     def verify_combined(self, points, scalars, weight_key: bytes = None, index_base: int = 0) -> int:
         """The combined check of a uniform batch at the capacity shape over the pool (bpp_pool_verify_combined): every
         shard's weighted sum, one reduce on shard 0's device.  -> 0 iff the batch passes (an empty batch does)."""
-        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 3 + 2 * ((self.n * self.m).bit_length() - 1) + self.m,
-                                                                      self.arith.PW)
+        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, self.mixed_points(self.m), self.arith.PW)
         sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 3, 4)
         if sc.shape[0] != pts.shape[0]:
             raise RuntimeError("verify_combined: one scalar triple per proof record")
         ok = np.ones(1, dtype=np.uint32)
-        check(_lib.lib().bpp_pool_verify_combined(self.handle, _ptr(pts) if len(pts) else None, _ptr(sc) if len(sc) else None,
-                                                  pts.shape[0], _weight_key_arg(weight_key, 0), ctypes.c_uint64(index_base),
-                                                  _ptr(ok)), "bpp_pool_verify_combined")
+        check(_lib.lib().bpp_pool_verify_combined(self.handle, _some(pts), _some(sc), pts.shape[0],
+                                                  _weight_key_arg(weight_key, 0), ctypes.c_uint64(index_base), _ptr(ok)),
+              "bpp_pool_verify_combined")
         return int(ok[0])
 
 
