@@ -1002,21 +1002,26 @@ namespace {
 // What the recovery and scan calls can answer before the engine handle is read: an m_i no engine takes (zero, or not a
 // power of two; one above the engine's m is the plan's to name), the blinding rules, a workspace of no bytes.
 // Runs under the guard itself (the error text is built on the heap).
+// the first position whose m_i no engine takes, or count where there is none
+size_t first_bad_m(const uint32_t* m_of, size_t count) noexcept {
+    size_t i = 0;
+    while (i < count && m_of[i] != 0 && !(m_of[i] & (m_of[i] - 1))) i++;
+    return i;
+}
+bool m_of_wellformed(const uint32_t* m_of, size_t count) noexcept { return first_bad_m(m_of, count) == count; }
+// the same as an answer that names the position; for a caller under the guard
+int m_of_checked(const uint32_t* m_of, size_t count) {
+    const size_t i = first_bad_m(m_of, count);
+    if (i == count) return BPP_OK;
+    return fail(BPP_E_ARG, "m_of[" + std::to_string(i) + "] = " + std::to_string(m_of[i]) + ": not a power of two");
+}
 int recover_args(const uint32_t* m_of, size_t count, const uint8_t* blind_key, const void* index, const void* blinding) noexcept {
     return guarded([&]() -> int {
         if (blind_key && blinding) return fail(BPP_E_ARG, "blind_key and d_blinding are both given");
         if (index && !blind_key) return fail(BPP_E_ARG, "d_index is the index of a blind_key: it needs one");
         if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
-        for (size_t i = 0; i < count; i++)
-            if (m_of[i] == 0 || (m_of[i] & (m_of[i] - 1)))
-                return fail(BPP_E_ARG, "m_of[" + std::to_string(i) + "] = " + std::to_string(m_of[i]) + ": not a power of two");
-        return BPP_OK;
+        return m_of_checked(m_of, count);
     });
-}
-bool m_of_wellformed(const uint32_t* m_of, size_t count) noexcept {
-    for (size_t i = 0; i < count; i++)
-        if (m_of[i] == 0 || (m_of[i] & (m_of[i] - 1))) return false;
-    return true;
 }
 constexpr int SCAN_FLAGS = BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED | BPP_PROVE_AMOUNT64;
 }  // namespace
@@ -1103,19 +1108,32 @@ extern "C" int bpp_range_scan_serialized_mixed(bpp_verifier* v, const uint8_t* p
 
 // ---- scanning under many keys (recover_keys.hpp): the front and the inversions once, n_keys x count pairs ----
 namespace {
-// n_keys x count within the bound the other entries put on count alone, without forming a product that can wrap
-bool pairs_bounded(size_t n_keys, size_t count) noexcept {
-    const size_t bound = 0x7fffffffu / 64;
-    return n_keys <= bound && count <= bound && (n_keys == 0 || count <= bound / n_keys);
+constexpr size_t PAIR_BOUND = 0x7fffffffu / 64;
+// n_keys x units within the bound the other entries put on count alone, without forming a product that can wrap
+bool pairs_bounded(size_t n_keys, size_t units) noexcept {
+    return n_keys <= PAIR_BOUND && units <= PAIR_BOUND && (n_keys == 0 || units <= PAIR_BOUND / n_keys);
 }
-// what the many-key scan can answer before the engine handle is read (runs under the guard itself)
-int scan_keys_args(const uint32_t* m_of, size_t count, size_t n_keys, int flags) noexcept {
+// What each key of a call is paired with: the proofs of the block, or (per_output) their outputs, the sum of m_i.  No sum
+// that can wrap: m_of is read only once count itself is within the bound, and no further than the sum is.
+size_t pair_units(const uint32_t* m_of, size_t count, bool per_output) noexcept {
+    if (!per_output || count > PAIR_BOUND) return count;
+    size_t n_out = 0;
+    for (size_t i = 0; i < count && n_out <= PAIR_BOUND; i++) n_out += m_of[i];   // each below 2^32
+    return n_out;
+}
+// the two answers that name what a call pairs its keys with
+struct PairTexts {
+    const char *too_large, *transcript;
+};
+constexpr PairTexts PROOF_PAIRS = {"n_keys x count too large for one launch", "blinding needs BPP_SER_TRANSCRIPT"};
+constexpr PairTexts OUTPUT_PAIRS = {"n_keys x n_out too large for one launch", "the verdicts need BPP_SER_TRANSCRIPT"};
+// what the many-key scan and the find calls can answer before the engine handle is read (runs under the guard itself)
+int scan_keys_args(const uint32_t* m_of, size_t count, size_t n_keys, int flags, bool per_output = false) noexcept {
     return guarded([&]() -> int {
-        if (!pairs_bounded(n_keys, count)) return fail(BPP_E_ARG, "n_keys x count too large for one launch");
-        for (size_t i = 0; i < count; i++)
-            if (m_of[i] == 0 || (m_of[i] & (m_of[i] - 1)))
-                return fail(BPP_E_ARG, "m_of[" + std::to_string(i) + "] = " + std::to_string(m_of[i]) + ": not a power of two");
-        if (!(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
+        const PairTexts& text = per_output ? OUTPUT_PAIRS : PROOF_PAIRS;
+        if (!pairs_bounded(n_keys, pair_units(m_of, count, per_output))) return fail(BPP_E_ARG, text.too_large);
+        if (int rc = m_of_checked(m_of, count)) return rc;
+        if (!(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, text.transcript);
         return BPP_OK;
     });
 }
@@ -1195,19 +1213,22 @@ int find_nothing(const bpp_verifier* v, const FindArgs& a, bool device, hipStrea
     });
 }
 
-// The checks of the four find entries, tagged and untagged, that come before scan_keys_args; count = 0 passes them and is
+// The checks of the six find entries, whatever the mode, that come before scan_keys_args; count = 0 passes them and is
 // answered by find_nothing.  a holds the entry's pointers, the device's (device: with a workspace) or the host's, and leaves
 // with what the flags say.  Without keys the block is verified all the same: the call IS a verification, and ok is never
 // left unwritten.
 int find_args(const bpp_verifier* v, int flags, FindArgs& a, bool device, const void* d_workspace) noexcept {
+    const bool per_output = a.mode == FIND_PER_OUTPUT;
     if (!v || !a.n_hits) return fail(BPP_E_ARG, "null argument");
+    if (per_output && (flags & BPP_FIND_AMOUNTS_SEALED))
+        return fail(BPP_E_ARG, "BPP_FIND_AMOUNTS_SEALED is not taken: amounts are always sealed here");
     if (flags & ~FIND_FLAGS) return fail(BPP_E_ARG, "unknown flag");
     a.version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
     a.amount64 = (flags & BPP_PROVE_AMOUNT64) != 0;
-    a.sealed = (flags & BPP_FIND_AMOUNTS_SEALED) != 0;
+    a.sealed = per_output || (flags & BPP_FIND_AMOUNTS_SEALED) != 0;
     if (a.count == 0) return BPP_OK;
     if (!a.proofs || !a.commitments || !a.m_of || !a.ok || (device && !d_workspace)) return fail(BPP_E_ARG, "null argument");
-    if (a.n_keys && (!a.keys || !a.amounts || (a.tagged && !a.tags) || (!a.hits && a.max_hits)))
+    if (a.n_keys && (!a.keys || !a.amounts || (a.tagged() && !a.tags) || (!a.hits && a.max_hits)))
         return fail(BPP_E_ARG, "null argument");
     if (device && a.n_keys && (reinterpret_cast<uintptr_t>(a.keys) & 3)) return fail(BPP_E_ARG, "d_keys must be 4-byte aligned");
     return BPP_OK;
@@ -1253,12 +1274,12 @@ extern "C" int bpp_view_tags(bpp_ctx* ctx, const uint8_t* blind_key, uint64_t in
 extern "C" size_t bpp_verify_find_serialized_mixed_keys_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count,
                                                                         size_t n_keys) {
     if ((count && !m_of) || !pairs_bounded(n_keys, count) || !m_of_wellformed(m_of, count)) return 0;
-    return size_for(v, [&](auto cv) { return FindImpl<decltype(cv)>::workspace_bytes(v, m_of, count, n_keys, false); });
+    return size_for(v, [&](auto cv) { return FindImpl<decltype(cv)>::workspace_bytes(v, m_of, count, n_keys, FIND_REWIND); });
 }
 
 extern "C" size_t bpp_verify_find_tagged_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys) {
     if ((count && !m_of) || !pairs_bounded(n_keys, count) || !m_of_wellformed(m_of, count)) return 0;
-    return size_for(v, [&](auto cv) { return FindImpl<decltype(cv)>::workspace_bytes(v, m_of, count, n_keys, true); });
+    return size_for(v, [&](auto cv) { return FindImpl<decltype(cv)>::workspace_bytes(v, m_of, count, n_keys, FIND_REWIND_TAGGED); });
 }
 
 extern "C" int bpp_range_verify_find_serialized_mixed_keys_device(bpp_verifier* v, const void* d_proofs, const void* d_commitments,
@@ -1269,7 +1290,7 @@ extern "C" int bpp_range_verify_find_serialized_mixed_keys_device(bpp_verifier* 
                                                                   uint32_t* d_n_hits, void* d_workspace, size_t workspace_bytes,
                                                                   void* stream) {
     FindArgs a{static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), m_of, count, d_keys, n_keys,
-               index_base, d_index, d_amounts, d_ok, d_hits, max_hits, d_n_hits, false, nullptr, nullptr};
+               index_base, d_index, d_amounts, d_ok, d_hits, max_hits, d_n_hits, FIND_REWIND, nullptr, nullptr};
     if (int rc = find_args(v, flags, a, true, d_workspace)) return rc;
     if (count == 0) return find_nothing(v, a, true, static_cast<hipStream_t>(stream));
     if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
@@ -1286,7 +1307,7 @@ extern "C" int bpp_range_verify_find_serialized_mixed_keys(bpp_verifier* v, cons
                                                            const uint64_t* amounts, uint32_t* out_ok, uint32_t* out_hits,
                                                            size_t max_hits, uint32_t* out_n_hits) {
     FindArgs a{proofs, commitments, m_of,     count,    keys,       n_keys, index_base, index,
-               amounts, out_ok,     out_hits, max_hits, out_n_hits, false,  nullptr,    nullptr};
+               amounts, out_ok,     out_hits, max_hits, out_n_hits, FIND_REWIND, nullptr, nullptr};
     if (int rc = find_args(v, flags, a, false, nullptr)) return rc;
     if (count == 0) return find_nothing(v, a, false, nullptr);
     if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
@@ -1299,7 +1320,7 @@ extern "C" int bpp_range_verify_find_tagged_serialized_mixed_keys_device(
     uint32_t* d_hits, size_t max_hits, uint32_t* d_n_hits, const uint8_t* d_tags, uint32_t* d_n_candidates, void* d_workspace,
     size_t workspace_bytes, void* stream) {
     FindArgs a{static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), m_of, count, d_keys, n_keys,
-               index_base, d_index, d_amounts, d_ok, d_hits, max_hits, d_n_hits, true, d_tags, d_n_candidates};
+               index_base, d_index, d_amounts, d_ok, d_hits, max_hits, d_n_hits, FIND_REWIND_TAGGED, d_tags, d_n_candidates};
     if (int rc = find_args(v, flags, a, true, d_workspace)) return rc;
     if (count == 0) return find_nothing(v, a, true, static_cast<hipStream_t>(stream));
     if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
@@ -1315,7 +1336,7 @@ extern "C" int bpp_range_verify_find_tagged_serialized_mixed_keys(
     const uint8_t* keys, size_t n_keys, uint64_t index_base, const uint64_t* index, const uint64_t* amounts, uint32_t* out_ok,
     uint32_t* out_hits, size_t max_hits, uint32_t* out_n_hits, const uint8_t* tags, uint32_t* out_n_candidates) {
     FindArgs a{proofs, commitments, m_of,     count,    keys,       n_keys, index_base, index,
-               amounts, out_ok,     out_hits, max_hits, out_n_hits, true,   tags,       out_n_candidates};
+               amounts, out_ok,     out_hits, max_hits, out_n_hits, FIND_REWIND_TAGGED, tags, out_n_candidates};
     if (int rc = find_args(v, flags, a, false, nullptr)) return rc;
     if (count == 0) return find_nothing(v, a, false, nullptr);
     if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
@@ -1325,48 +1346,6 @@ extern "C" int bpp_range_verify_find_tagged_serialized_mixed_keys(
 // ---- outputs with masks derived from their recipients' keys: making them, and verifying a block while listing each
 // key's outputs, aggregated proofs included (outputs.hpp) ----
 namespace {
-// n_keys x n_out (n_out = sum m_i) within the bound the other entries put on n_keys x count, without a sum or a product
-// that can wrap; m_of is read only once count itself is within the bound
-bool out_pairs_bounded(const uint32_t* m_of, size_t count, size_t n_keys) noexcept {
-    const size_t bound = 0x7fffffffu / 64;
-    if (n_keys > bound || count > bound) return false;
-    size_t n_out = 0;
-    for (size_t i = 0; i < count; i++) {
-        n_out += m_of[i];   // each below 2^32, the sum so far at most the bound
-        if (n_out > bound) return false;
-    }
-    return n_keys == 0 || n_out <= bound / n_keys;
-}
-
-// the checks of the receiver's two entries; count = 0 passes them and is answered by find_nothing
-int outputs_args(const bpp_verifier* v, int flags, OutputsArgs& a, bool device, const void* d_workspace) noexcept {
-    if (!v || !a.n_hits) return fail(BPP_E_ARG, "null argument");
-    if (flags & BPP_FIND_AMOUNTS_SEALED) return fail(BPP_E_ARG, "BPP_FIND_AMOUNTS_SEALED is not taken: amounts are always sealed here");
-    if (flags & ~SCAN_FLAGS) return fail(BPP_E_ARG, "unknown flag");
-    a.version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
-    a.amount64 = (flags & BPP_PROVE_AMOUNT64) != 0;
-    if (a.count == 0) return BPP_OK;
-    if (!a.proofs || !a.commitments || !a.m_of || !a.ok || (device && !d_workspace)) return fail(BPP_E_ARG, "null argument");
-    if (a.n_keys && (!a.keys || !a.sealed || !a.tags || (!a.hits && a.max_hits))) return fail(BPP_E_ARG, "null argument");
-    if (device && a.n_keys && (reinterpret_cast<uintptr_t>(a.keys) & 3)) return fail(BPP_E_ARG, "d_keys must be 4-byte aligned");
-    return guarded([&]() -> int {
-        if (!out_pairs_bounded(a.m_of, a.count, a.n_keys)) return fail(BPP_E_ARG, "n_keys x n_out too large for one launch");
-        for (size_t i = 0; i < a.count; i++)
-            if (a.m_of[i] == 0 || (a.m_of[i] & (a.m_of[i] - 1)))
-                return fail(BPP_E_ARG, "m_of[" + std::to_string(i) + "] = " + std::to_string(a.m_of[i]) + ": not a power of two");
-        if (!(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, "the verdicts need BPP_SER_TRANSCRIPT");
-        return BPP_OK;
-    });
-}
-
-// what find_nothing reads of a find call: where the two counts go
-FindArgs counts_only(uint32_t* n_hits, uint32_t* n_candidates) noexcept {
-    FindArgs a = {};
-    a.n_hits = n_hits;
-    a.n_candidates = n_candidates;
-    return a;
-}
-
 // the checks of the sender's two entries; n_out = 0 passes them and is answered by the entry
 int outputs_make_args(const bpp_ctx* ctx, const void* keys, const void* index, const void* j, const void* amounts, size_t n_out,
                       const void* out_masks, const void* out_sealed, const void* out_tags, bool device) noexcept {
@@ -1402,7 +1381,7 @@ extern "C" int bpp_outputs_make(bpp_ctx* ctx, const uint8_t* keys, const uint64_
 }
 
 extern "C" size_t bpp_verify_find_outputs_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys) {
-    if ((count && !m_of) || !out_pairs_bounded(m_of, count, n_keys) || !m_of_wellformed(m_of, count)) return 0;
+    if ((count && !m_of) || !pairs_bounded(n_keys, pair_units(m_of, count, true)) || !m_of_wellformed(m_of, count)) return 0;
     return size_for(v, [&](auto cv) { return OutputsImpl<decltype(cv)>::workspace_bytes(v, m_of, count, n_keys); });
 }
 
@@ -1411,10 +1390,11 @@ extern "C" int bpp_range_verify_find_outputs_serialized_mixed_keys_device(
     const uint8_t* d_keys, size_t n_keys, uint64_t index_base, const uint64_t* d_index, const uint64_t* d_sealed,
     const uint8_t* d_tags, uint32_t* d_ok, uint32_t* d_hits, size_t max_hits, uint32_t* d_n_hits, uint32_t* d_n_candidates,
     void* d_workspace, size_t workspace_bytes, void* stream) {
-    OutputsArgs a{static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), m_of, count, d_keys, n_keys,
-                  index_base, d_index, d_sealed, d_tags, d_ok, d_hits, max_hits, d_n_hits, d_n_candidates};
-    if (int rc = outputs_args(v, flags, a, true, d_workspace)) return rc;
-    if (count == 0) return find_nothing(v, counts_only(d_n_hits, d_n_candidates), true, static_cast<hipStream_t>(stream));
+    FindArgs a{static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), m_of, count, d_keys, n_keys,
+               index_base, d_index, d_sealed, d_ok, d_hits, max_hits, d_n_hits, FIND_PER_OUTPUT, d_tags, d_n_candidates};
+    if (int rc = find_args(v, flags, a, true, d_workspace)) return rc;
+    if (count == 0) return find_nothing(v, a, true, static_cast<hipStream_t>(stream));
+    if (int rc = scan_keys_args(m_of, count, n_keys, flags, true)) return rc;
     if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
         return OutputsImpl<decltype(cv)>::find(v, a, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
@@ -1426,10 +1406,11 @@ extern "C" int bpp_range_verify_find_outputs_serialized_mixed_keys(
     bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, const uint32_t* m_of, size_t count, int flags,
     const uint8_t* keys, size_t n_keys, uint64_t index_base, const uint64_t* index, const uint64_t* sealed, const uint8_t* tags,
     uint32_t* out_ok, uint32_t* out_hits, size_t max_hits, uint32_t* out_n_hits, uint32_t* out_n_candidates) {
-    OutputsArgs a{proofs, commitments, m_of, count, keys, n_keys, index_base, index, sealed, tags, out_ok, out_hits, max_hits,
-                  out_n_hits, out_n_candidates};
-    if (int rc = outputs_args(v, flags, a, false, nullptr)) return rc;
-    if (count == 0) return find_nothing(v, counts_only(out_n_hits, out_n_candidates), false, nullptr);
+    FindArgs a{proofs, commitments, m_of,     count,    keys,       n_keys,          index_base, index,
+               sealed, out_ok,      out_hits, max_hits, out_n_hits, FIND_PER_OUTPUT, tags,       out_n_candidates};
+    if (int rc = find_args(v, flags, a, false, nullptr)) return rc;
+    if (count == 0) return find_nothing(v, a, false, nullptr);
+    if (int rc = scan_keys_args(m_of, count, n_keys, flags, true)) return rc;
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int { return OutputsImpl<decltype(cv)>::find_host(v, a); });
 }
 

@@ -1,53 +1,62 @@
-// find.hpp -- verifying a block of containers AND listing the outputs of many view keys in one call
-// (bpp_range_verify_find_serialized_mixed_keys*), the same call with one-byte view tags
-// (bpp_range_verify_find_tagged_serialized_mixed_keys*), sealing amounts (bpp_amounts_seal*) and making the tags
-// (bpp_view_tags*).  What a scanning service does with a block otherwise is two calls that share a front --
+// find.hpp -- verifying a block of containers AND listing the outputs of many view keys in one call: by rewinding its
+// single-output proofs (bpp_range_verify_find_serialized_mixed_keys*), the same with one-byte view tags
+// (bpp_range_verify_find_tagged_serialized_mixed_keys*), and -- the class step and its kernels in outputs.hpp -- per OUTPUT
+// by derived masks (bpp_range_verify_find_outputs_serialized_mixed_keys*); also sealing amounts (bpp_amounts_seal*) and
+// making the tags (bpp_view_tags*).  What a scanning service does with a block otherwise is two calls that share a front --
 // bpp_range_verify_batch_serialized_mixed_device, then bpp_range_scan_serialized_mixed_keys_device -- and a walk over the
 // scan's dense pair matrix; here the front (index upload, decode, membership test, challenges) runs once, the verdict gates
 // the confirmation, and the answer is the verdicts and a short ordered list of hits.  The untagged call pays 2k + 3 slot
 // expansions, as many products in Fr and a table walk for EVERY (key, single output) pair; in the tagged call a pair first
 // pays one SHA-256 compression -- view_tag(key, idx) against the byte the output carries -- and only the pairs that match,
-// the CANDIDATES, go on.  Verdicts, hit records, their order and the max_hits rule are the same in both.  One engine
-// (FindImpl::find, "tagged" a flag of its arguments), one instantiation per curve (tu_find_*.hip); find_terms.hpp has the
-// pad, the tag and the index arithmetic; what a pair's lanes compute (its Gamma, its confirmation) is recover_keys.hpp's.
+// the CANDIDATES, go on.  Verdicts, hit records, their order and the max_hits rule are the same in all three.  One engine
+// (FindEngine: the schedule, the workspace, the host twin) under three MODES of its arguments; what a mode does with a class
+// is its CLASS STEP, and a translation unit instantiates the engine with the step whose kernels it owns: RewindStep here
+// (tu_find_*.hip: both rewinding modes), OutputStep in outputs.hpp (tu_outputs_*.hip).  find_terms.hpp has the pad, the tag
+// and the index arithmetic; what a pair's lanes compute (its Gamma, its confirmation) is recover_keys.hpp's.
 //
-// Schedule, all on the caller's stream, no host synchronisation beyond the front's index upload: decode_front; the pair
-// words zeroed where a kernel below will not write them (untagged: those of aggregated proofs, so only when there are any;
-// tagged: every non-candidate's, so always); per class present derive_challenges and today's exact pass (VerifyImpl::run)
-// into front.ok; for the single-output class RecoverKeysImpl's bind_class and launch_coeffs (k_recover_coeffs) with Gamma
-// and the pair word pointed at the pair region of the workspace, then the class step below; k_mixed_status_scatter writes
-// d_ok; k_find_count, k_find_offsets, k_find_emit make the hit list.
-// The class step, untagged: k_scan_keys, then
+// A key is paired with the UNITS of the block: its caller positions when proofs are rewound, its caller output numbers
+// (the sum of m_i) per output.  The pair region lies key-major, [key][unit].
+// Schedule, all on the caller's stream, no host synchronisation beyond the front's index upload (per output its free word
+// carries each proof's first caller output number): decode_front; the pair words zeroed where no kernel below will write
+// them (untagged: those of aggregated proofs, so only when there are any; tagged: every non-candidate's, so always; per
+// output: every pair that does not become a hit, so whenever there are keys); per class present derive_challenges and
+// today's exact pass (VerifyImpl::run) into front.ok, then the mode's class step; k_mixed_status_scatter writes d_ok;
+// k_find_count, k_find_offsets, k_find_emit make the hit list.  A call without keys -- or, rewinding, without a
+// single-output proof -- takes no class step and lists nothing: verdicts, and zero counts.
+// The rewinding class steps take the single-output class alone: RecoverKeysImpl's bind_class and launch_coeffs
+// (k_recover_coeffs) with Gamma and the pair word pointed at the pair region of the workspace, then
+// untagged: k_scan_keys, then
 // k_find_confirm: one lane per (key, single-output proof) pair, numbered as k_scan_keys numbers them.  A lane whose proof
 // the pass did not accept, the decoder rejected or whose coefficients are undefined clears its pair (no hit, Gamma zero)
 // before it reads a key or a Gamma.  Otherwise the candidate amount (find_pair_amount) -- sealed mode: the key's words into
 // registers, the pad by amount_pad, amount = sealed XOR pad; else a load from the key-major array -- then pair_confirms.  A
 // hit keeps its Gamma and stores its amount; a miss has its Gamma zeroed.
-// The class step, tagged:
+// tagged: the candidate list (launch_candidates, which the per-output step uses too) --
 // k_find_tags: one 64-lane block per tile of FIND_TILE launch positions OF ONE KEY (find_terms.hpp), a lane per pair and
-// round.  A lane whose proof the pass did not accept, the decoder rejected or whose coefficients are undefined is no
-// candidate before it reads a key.  The others read the tile's key (uniform over the block: scalar loads), the index and
-// the tag byte of their caller position, and compress once.  The tile leaves its FIND_ROUNDS ballots and its count: ONE
-// BIT per pair instead of a flag word.
+// round (tag_tile: the tiling, the ballots and the count, around the kernel's candidate predicate).  A lane whose proof the
+// pass did not accept, the decoder rejected or whose coefficients are undefined is no candidate before it reads a key.  The
+// others read the tile's key (uniform over the block: scalar loads), the index and the tag byte of their caller position,
+// and compress once.  The tile leaves its FIND_ROUNDS ballots and its count: ONE BIT per pair instead of a flag word.
 // k_find_offsets scans the tile counts and leaves the candidate count in a workspace word.
-// k_find_list: the lanes of k_find_tags again, from the ballots: candidate number h of the call, in ascending key-major
-// pair number, to list[h].  No atomics; the same list from run to run.
-// k_find_scan_list: k_scan_keys's eight lanes per pair (pair_gamma), over the list: group g takes candidates g,
+// k_find_list: the lanes of the tag kernel again, from the ballots: candidate number h of the class, in ascending key-major
+// pair number, to list[h].  No atomics; the same list from run to run.  Where it is given a place it copies the count there:
+// the tagged call's n_candidates, its one class.
+// -- then k_find_scan_list: k_scan_keys's eight lanes per pair (pair_gamma), over the list: group g takes candidates g,
 // g + groups, .. below the count it READS FROM THE WORKSPACE; the grid is sized from n_keys x count alone, so the host never
 // learns the count.  Gamma goes to the pair's place in the key-major region.
 // k_find_confirm_list: k_find_confirm's lane, one per POSSIBLE pair (the stride over the list is one step: lanes at or
 // beyond the count end at once): candidate amount, pair_confirms; a hit sets its pair word and stores its amount, a miss has
 // its Gamma zeroed.
-// The compaction: the pair words lie key-major ([key][caller position]), so ascending position is ascending (key number,
-// caller position).  k_find_count: one 64-lane block per tile of FIND_TILE positions, a ballot per round, the tile's
-// count.  k_find_offsets: one wave scans the tile counts in place (exclusive) and writes the total to d_n_hits.
+// The compaction: the pair words lie key-major ([key][unit]), so ascending position is ascending (key number, caller
+// position or output number).  k_find_count: one 64-lane block per tile of FIND_TILE positions, a ballot per round, the
+// tile's count.  k_find_offsets: one wave scans the tile counts in place (exclusive) and writes the total to d_n_hits.
 // k_find_emit: the lanes of k_find_count again; a hit's place is its tile's offset, the ballots of the rounds before and
 // the lanes below it -- no atomics, and an order that does not depend on scheduling.  Records at or beyond max_hits are
 // not written.
-// The key rule: no LDS, no scratch in any kernel here.  Nothing derived from a key reaches memory but the candidate bit
-// (the match of a PUBLIC byte), the hit bit, Gamma of a pair that was scanned (zeroed on a miss: when the call ends no
-// Gamma of a pair that is not a hit is left in the workspace) and a hit's amount.  The Gamma and amount words of
-// non-candidates are never written.
+// The key rule: no LDS, no scratch in any kernel here.  A key's words go from its buffer into registers in one place
+// (load_key, recover_keys.hpp).  Nothing derived from a key reaches memory but the candidate bit (the match of a PUBLIC
+// byte), the hit bit, Gamma of a pair that was scanned (zeroed on a miss: when the call ends no Gamma of a pair that is not
+// a hit is left in the workspace) and a hit's amount.  The Gamma and amount words of non-candidates are never written.
 #pragma once
 #include "recover_keys.hpp"
 #include "find_terms.hpp"
@@ -64,8 +73,7 @@ __global__ void __launch_bounds__(FIND_BLOCK) k_amounts_seal(BlindKey key, uint6
     const size_t i = (size_t)blockIdx.x * FIND_BLOCK + threadIdx.x;
     if (i >= count) return;
     uint32_t kw[8];
-#pragma unroll
-    for (int w = 0; w < 8; w++) kw[w] = key.w[w];
+    load_key(key.w, 0, kw);
     out[i] = in[i] ^ amount_pad(kw, index ? index[i] : index_base + i);
 }
 
@@ -76,8 +84,7 @@ __global__ void __launch_bounds__(FIND_BLOCK) k_view_tags(BlindKey key, uint64_t
     const size_t i = (size_t)blockIdx.x * FIND_BLOCK + threadIdx.x;
     if (i >= count) return;
     uint32_t kw[8];
-#pragma unroll
-    for (int w = 0; w < 8; w++) kw[w] = key.w[w];
+    load_key(key.w, 0, kw);
     out[i] = view_tag(kw, index ? index[i] : index_base + i);
 }
 
@@ -201,28 +208,33 @@ struct TagJob {
     uint32_t* n_cand;       // one word
 };
 
-// tile blockIdx.x of the tag test; j as k_scan_keys takes it (count: the proofs of the single-output class)
-template <class C>
-__global__ void __launch_bounds__(FIND_BLOCK) k_find_tags(ScanKeysJob j, TagJob t) {
+// Tile blockIdx.x of a tag test, the body of its kernel: per round the lane's launch position, is_candidate(key number,
+// position) -- false for a position beyond the class -- the ballot, which lane 0 stores, and the count summed.
+template <class Pred>
+__device__ __forceinline__ void tag_tile(const TagJob& t, Pred is_candidate) {
     const uint32_t lane = threadIdx.x;
     const size_t tile = blockIdx.x;
     const size_t key_no = tag_tile_key(tile, t.per_key);
     uint32_t n = 0;
 #pragma unroll 1
     for (uint32_t r = 0; r < FIND_ROUNDS; r++) {
-        const size_t p = tag_launch_position(tile, t.per_key, r, lane);
-        bool cand = false;
-        if (p < j.count && !(t.ok[p] | j.status[p] | j.bad[p])) {   // a verified proof with a defined Gamma: only then a key is read
-            const size_t caller = j.rx[p * RX_WORDS + RX_CALLER];
-            uint32_t key[8];
-            const uint64_t idx = pair_key_index(j, key_no, caller, key);
-            cand = view_tag(key, idx) == t.tags[caller];
-        }
-        const uint64_t ballot = __ballot(cand);
+        const uint64_t ballot = __ballot(is_candidate(key_no, tag_launch_position(tile, t.per_key, r, lane)));
         if (lane == 0) t.ballots[tile * FIND_ROUNDS + r] = ballot;
         n += find_ballot_count(ballot);
     }
     if (lane == 0) t.tile_count[tile] = n;
+}
+
+// the tag test of the single-output class; j as k_scan_keys takes it (count: the proofs of the class)
+template <class C>
+__global__ void __launch_bounds__(FIND_BLOCK) k_find_tags(ScanKeysJob j, TagJob t) {
+    tag_tile(t, [&](size_t key_no, size_t p) {
+        if (p >= j.count || (t.ok[p] | j.status[p] | j.bad[p])) return false;   // a verified proof with a defined Gamma: only then a key is read
+        const size_t caller = j.rx[p * RX_WORDS + RX_CALLER];
+        uint32_t key[8];
+        const uint64_t idx = pair_key_index(j, key_no, caller, key);
+        return view_tag(key, idx) == t.tags[caller];
+    });
 }
 
 // the candidates of tile blockIdx.x to their places in the list; block 0 hands the count to the caller
@@ -283,9 +295,16 @@ __global__ void __launch_bounds__(FIND_BLOCK) k_find_confirm_list(VerifyShape s,
     }
 }
 
-// What a find call takes, tagged or not, in the C ABI's order.  For FindImpl::find the pointers are the device's (keys
+// how a call finds a key's outputs
+enum FindMode : uint32_t {
+    FIND_REWIND,          // single-output proofs are rewound under every key
+    FIND_REWIND_TAGGED,   // the same, for the pairs whose view tag matches
+    FIND_PER_OUTPUT,      // every output of every proof, by its derived mask (outputs.hpp)
+};
+
+// What a find call takes, in the C ABI's order but for the mode.  For a device entry the pointers are the device's (keys
 // 4-byte aligned), for find_host the host's.  n_keys = 0: the block is verified all the same (keys, amounts, tags unread),
-// no hit.
+// no hit.  Per output, amounts and tags go by caller OUTPUT number (sum of m_i of them) and amounts are always sealed.
 struct FindArgs {
     const uint8_t *proofs, *commitments;
     const uint32_t* m_of;   // host, always
@@ -294,58 +313,23 @@ struct FindArgs {
     size_t n_keys;
     uint64_t index_base;
     const uint64_t* index;     // count x u64 or null
-    const uint64_t* amounts;   // count x u64 (sealed) or n_keys x count
+    const uint64_t* amounts;   // one u64 per unit (sealed) or n_keys x count
     uint32_t* ok;              // count words
     uint32_t* hits;            // max_hits x FIND_HIT_WORDS words
     size_t max_hits;
     uint32_t* n_hits;          // one word
-    bool tagged;               // the tagged call: tags is read and n_candidates, where given, answered
-    const uint8_t* tags;       // count bytes by caller position
-    uint32_t* n_candidates;    // one word or null
+    FindMode mode;
+    const uint8_t* tags;       // one byte per unit; unread when rewinding untagged
+    uint32_t* n_candidates;    // one word or null; likewise
     uint32_t version = 1;      // what the call's flags say
     bool amount64 = false, sealed = false;
+    bool tagged() const { return mode != FIND_REWIND; }
 };
 
 template <class C>
 struct FindImpl {
-    using V = VerifyImpl<C>;
-    using K = RecoverKeysImpl<C>;
-    static constexpr int CW = coeff_words<typename C::Fr>();
-
-    // workspace = front (MixedFront, serialized form) | one class pass's workspace | the single-output class's coefficients
-    // and zero-challenge flags | the pair region, key-major over ALL caller positions (k_scan_keys addresses it so): Gamma,
-    // the pair word, the amounts of hits | the tile counts; tagged calls only: | the tag test's ballots and tile counts | the
-    // candidate list, with room for every pair | the candidate count.  A function of (m_of, count, n_keys, tagged) alone.
-    struct Layout {
-        typename V::MixedFront f;
-        size_t run, run_bytes, coeffs, bad, masks, hit, hit_amounts, tiles;
-        size_t ballots, tag_tiles, list, n_cand;   // tagged only
-        size_t total;
-    };
-    static Layout layout(const bpp_verifier* v, const MixedPlan& p, size_t count, size_t n_keys, bool tagged) {
-        Layout w = {};
-        WsCarver o;
-        const size_t pairs = n_keys * count;
-        w.f = V::carve_front(o, p, count, true);
-        w.run_bytes = V::class_run_max(v, p, V::pass_bytes);
-        w.run = o.take(w.run_bytes);
-        w.coeffs = o.take(p.count[0] ? p.count[0] * coeff_elems(V::class_shape(v, 0).s.k) * CW * 4 : 0);
-        w.bad = o.take(p.count[0] * 4);
-        w.masks = o.take(pairs * 32);
-        w.hit = o.take(pairs * 4);
-        w.hit_amounts = o.take(pairs * 8);
-        w.tiles = o.take(find_tiles(pairs) * 4);
-        if (tagged) {
-            const size_t tiles = tag_tiles(n_keys, p.count[0]);
-            w.ballots = o.take(tiles * FIND_ROUNDS * 8);
-            w.tag_tiles = o.take(tiles * 4);
-            w.list = o.take(n_keys * p.count[0] * 4);
-            w.n_cand = o.take(4);
-        }
-        w.total = o.total;
-        return w;
-    }
-    static size_t workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys, bool tagged);
+    // mode, a.mode: one of the rewinding two
+    static size_t workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys, FindMode mode);
     static int find(bpp_verifier* v, const FindArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st);
     static int find_host(bpp_verifier* v, const FindArgs& a);
     // blind_key: 32 bytes (host); d_index: count x u64 or null; d_in, d_out: count x u64 (may be the same buffer)
@@ -360,124 +344,238 @@ struct FindImpl {
 };
 
 #ifdef BPP_IMPL_DEFINITIONS
+// workspace = front (MixedFront, serialized form) | one class pass's workspace | rewinding only: the single-output class's
+// coefficients and zero-challenge flags | the pair region, key-major over ALL units (k_scan_keys addresses it so): Gamma,
+// the pair word, the amounts of hits | the compaction's tile counts; with tags only: | the tag test's ballots and tile
+// counts | the candidate list, each with room for the largest class that is listed | the candidate count, which like
+// them one class leaves to the next: the stream orders them.  A function of (m_of, count, n_keys, mode) alone.
 template <class C>
-size_t FindImpl<C>::workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys, bool tagged) {
-    MixedPlan p;
-    if (!V::container_shape_ok(v) || mixed_plan_serialized(v->s, m_of, count, max_point_bytes<C>(), false, p)) return 0;
-    return layout(v, p, count, n_keys, tagged).total;
-}
+struct FindLayout {
+    typename VerifyImpl<C>::MixedFront f;
+    size_t run, run_bytes, coeffs, bad, masks, hit, hit_amounts, tiles, ballots, tag_tiles, list, n_cand, total;
+    size_t units;   // what each key is paired with
+};
 
+// what a class step sees of a call in flight
 template <class C>
-int FindImpl<C>::find(bpp_verifier* v, const FindArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
-    if (int rc = V::container_args_ok(v, a.version)) return rc;
-    const size_t count = a.count, n_keys = a.n_keys;
-    MixedPlan p;
-    int rc = mixed_plan_serialized(v->s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), true, p);
-    if (rc) return rc;
-    const Layout L = layout(v, p, count, n_keys, a.tagged);
-    if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
-    const bool scan = n_keys != 0 && p.count[0] != 0;   // only single outputs are scanned: the other classes need not fit a lane group
-    if (scan && V::class_shape(v, 0).s.k + 2 > RECOVER_GROUP) return fail(BPP_E_ARG, "mask recovery takes shapes with log2(n m) <= 14");
-    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-    auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
-    const size_t pairs = n_keys * count;
-    rc = V::decode_front(p, L.f, count, a.proofs, a.commitments, a.version, ws, st);
-    if (rc) return rc;
-    // the pair words no kernel below writes (nor their Gamma and amount words, which nothing reads): untagged, those of
-    // aggregated proofs; tagged, those of every pair that is no candidate
-    if (scan && (a.tagged || p.count[0] != count)) HIPCHK(zero_words_async(W(L.hit), pairs * 4, st));
-    ScanKeysJob j = K::call_job(a.keys, n_keys, a.index_base, a.index, W(L.masks), W(L.hit), count);
-    rc = V::for_each_class(v, p, L.f, ws, [&](const typename V::ClassView& cv) {
-        int rc1 = V::derive_challenges(v, cv.ps, cv.pts, cv.count, cv.challenges, st);
-        if (rc1) return rc1;
-        rc1 = V::run(v, cv.ps, cv.pts, cv.sc3, cv.count, cv.challenges, W(L.f.ok) + cv.first, ws + L.run, L.run_bytes, nullptr,
-                     nullptr, st);
-        if (rc1 || cv.c != 0 || !scan) return rc1;
-        // the single-output class comes first in gathered order: launch position = gathered position
-        K::bind_class(cv, W(L.f.idx), W(L.f.status), W(L.bad), W(L.coeffs), j);
-        if ((rc1 = K::launch_coeffs(cv, W(L.coeffs), W(L.bad), st))) return rc1;
-        const FindJob f{W(L.f.ok) + cv.first, a.amounts, a.sealed ? 1u : 0u, a.amount64 ? 1u : 0u, reinterpret_cast<uint64_t*>(ws + L.hit_amounts)};
-        const uint32_t* records = reinterpret_cast<const uint32_t*>(cv.pts);
-        const uint32_t nv = cv.ps.s.NV, v0 = 3 + 2 * cv.ps.s.k;
-        const size_t pairs0 = n_keys * cv.count;
-        if (!a.tagged) {
-            if ((rc1 = K::launch_scan_keys(j, st))) return rc1;
-            hipLaunchKernelGGL(k_find_confirm<C>, dim3(cdiv(pairs0, FIND_BLOCK)), dim3(FIND_BLOCK), 0, st, v->s, v->table.u32(), j,
-                               f, records, nv, v0);
-            HIPCHK(hipGetLastError());
-            return BPP_OK;
-        }
-        const TagJob t{a.tags, f.ok, tag_tiles_per_key(cv.count), reinterpret_cast<uint64_t*>(ws + L.ballots), W(L.tag_tiles),
-                       W(L.list), W(L.n_cand)};
-        const size_t tiles = tag_tiles(n_keys, cv.count);
-        hipLaunchKernelGGL(k_find_tags<C>, dim3((unsigned)tiles), dim3(FIND_BLOCK), 0, st, j, t);
-        hipLaunchKernelGGL(k_find_offsets<C>, dim3(1), dim3(FIND_BLOCK), 0, st, t.tile_count, tiles, t.n_cand);
-        hipLaunchKernelGGL(k_find_list<C>, dim3((unsigned)tiles), dim3(FIND_BLOCK), 0, st, t, cv.count, a.n_candidates);
-        HIPCHK(hipGetLastError());
-        // the list kernels: grids sized for every pair a candidate, capped; they read the count on the device
-        const size_t scan_blocks = std::min<size_t>(cdiv(pairs0 * SCAN_GROUP, SCAN_BLOCK), FIND_LIST_BLOCKS);
-        hipLaunchKernelGGL(k_find_scan_list<C>, dim3((unsigned)scan_blocks), dim3(SCAN_BLOCK), 0, st, j, t.list, t.n_cand);
-        hipLaunchKernelGGL(k_find_confirm_list<C>, dim3(cdiv(pairs0, FIND_BLOCK)), dim3(FIND_BLOCK), 0, st, v->s, v->table.u32(),
-                           j, f, records, nv, v0, t.list, t.n_cand);
-        HIPCHK(hipGetLastError());
-        return BPP_OK;
-    });
-    if (rc) return rc;
-    if ((rc = V::scatter_verdicts(L.f, ws, a.ok, count, st))) return rc;
-    if (!scan) {   // no key, or nothing but aggregated proofs: verified, and no pair to test or list
-        HIPCHK(zero_words_async(a.n_hits, 4, st));
-        if (a.tagged && a.n_candidates) HIPCHK(zero_words_async(a.n_candidates, 4, st));
-        return BPP_OK;
-    }
-    const unsigned tiles = (unsigned)find_tiles(pairs);
-    hipLaunchKernelGGL(k_find_count<C>, dim3(tiles), dim3(FIND_BLOCK), 0, st, W(L.hit), pairs, W(L.tiles));
-    hipLaunchKernelGGL(k_find_offsets<C>, dim3(1), dim3(FIND_BLOCK), 0, st, W(L.tiles), (size_t)tiles, a.n_hits);
-    hipLaunchKernelGGL(k_find_emit<C>, dim3(tiles), dim3(FIND_BLOCK), 0, st, W(L.hit),
-                       reinterpret_cast<const uint64_t*>(ws + L.hit_amounts), W(L.masks), pairs, count, W(L.tiles), a.max_hits,
-                       a.hits);
+struct FindCall {
+    bpp_verifier* v;
+    const FindArgs& a;
+    const FindLayout<C>& L;
+    uint8_t* ws;
+    hipStream_t st;
+    uint32_t* W(size_t off) const { return reinterpret_cast<uint32_t*>(ws + off); }
+    uint64_t* hit_amounts() const { return reinterpret_cast<uint64_t*>(ws + L.hit_amounts); }
+};
+
+// The candidates of one class with `positions` launch positions per key: tag_kernel (tag_tile around its predicate) over
+// the tiles, their counts scanned, the list made.  ok: the class's verdicts; n_candidates: where k_find_list copies the
+// count, or null.  Returns, in t, what the kernels that walk the list read.
+template <class C, class Job>
+int launch_candidates(const FindCall<C>& c, void (*tag_kernel)(Job, TagJob), const Job& j, const uint32_t* ok, size_t positions,
+                      uint32_t* n_candidates, TagJob& t) {
+    t = TagJob{c.a.tags, ok, tag_tiles_per_key(positions), reinterpret_cast<uint64_t*>(c.ws + c.L.ballots), c.W(c.L.tag_tiles),
+               c.W(c.L.list), c.W(c.L.n_cand)};
+    const size_t tiles = tag_tiles(c.a.n_keys, positions);
+    hipLaunchKernelGGL(tag_kernel, dim3((unsigned)tiles), dim3(FIND_BLOCK), 0, c.st, j, t);
+    hipLaunchKernelGGL(k_find_offsets<C>, dim3(1), dim3(FIND_BLOCK), 0, c.st, t.tile_count, tiles, t.n_cand);
+    hipLaunchKernelGGL(k_find_list<C>, dim3((unsigned)tiles), dim3(FIND_BLOCK), 0, c.st, t, positions, n_candidates);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
 
-// host buffers in, host verdicts, hit records and counts out: find between copies
+// The schedule of the file head, once.  S is the class step and says what differs between the modes it serves:
+//   units(p, count)          what each key is paired with
+//   widest(p)                the most launch positions per key of a tag test: the room of the candidate list
+//   coeff_bytes, flag_bytes  its regions between the pass's workspace and the pair region
+//   lists(a, p)              whether the call has a pair to test at all
+//   open(v, a, lists, p)     what it refuses, and what it writes into the plan before the index is uploaded
+//   zero_pairs(a, p)         whether a listing call's pair words must be zeroed first
+//   begin(c), klass(c, cv)   of a listing call: once after the front, and after each class's pass
+template <class C, class S>
+struct FindEngine {
+    using V = VerifyImpl<C>;
+    using Layout = FindLayout<C>;
+    static Layout layout(const bpp_verifier* v, const MixedPlan& p, size_t count, size_t n_keys, FindMode mode) {
+        Layout w = {};
+        WsCarver o;
+        w.units = S::units(p, count);
+        const size_t pairs = n_keys * w.units;
+        w.f = V::carve_front(o, p, count, true);
+        w.run_bytes = V::class_run_max(v, p, V::pass_bytes);
+        w.run = o.take(w.run_bytes);
+        w.coeffs = o.take(S::coeff_bytes(v, p));
+        w.bad = o.take(S::flag_bytes(p));
+        w.masks = o.take(pairs * 32);
+        w.hit = o.take(pairs * 4);
+        w.hit_amounts = o.take(pairs * 8);
+        w.tiles = o.take(find_tiles(pairs) * 4);
+        if (mode != FIND_REWIND) {
+            const size_t widest = S::widest(p), tiles = tag_tiles(n_keys, widest);
+            w.ballots = o.take(tiles * FIND_ROUNDS * 8);
+            w.tag_tiles = o.take(tiles * 4);
+            w.list = o.take(n_keys * widest * 4);
+            w.n_cand = o.take(4);
+        }
+        w.total = o.total;
+        return w;
+    }
+
+    static size_t workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys, FindMode mode) {
+        MixedPlan p;
+        if (!V::container_shape_ok(v) || mixed_plan_serialized(v->s, m_of, count, max_point_bytes<C>(), false, p)) return 0;
+        return layout(v, p, count, n_keys, mode).total;
+    }
+
+    static int find(bpp_verifier* v, const FindArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
+        if (int rc = V::container_args_ok(v, a.version)) return rc;
+        const size_t count = a.count;
+        MixedPlan p;
+        int rc = mixed_plan_serialized(v->s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), true, p);
+        if (rc) return rc;
+        const Layout L = layout(v, p, count, a.n_keys, a.mode);
+        if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
+        const bool lists = S::lists(a, p);
+        if ((rc = S::open(v, a, lists, p))) return rc;
+        const FindCall<C> c{v, a, L, static_cast<uint8_t*>(d_workspace), st};
+        const size_t pairs = a.n_keys * L.units;
+        rc = V::decode_front(p, L.f, count, a.proofs, a.commitments, a.version, c.ws, st);
+        if (rc) return rc;
+        // the pair words no kernel below writes (nor their Gamma and amount words, which nothing reads)
+        if (lists && S::zero_pairs(a, p)) HIPCHK(zero_words_async(c.W(L.hit), pairs * 4, st));
+        S step;
+        if (lists && (rc = step.begin(c))) return rc;
+        rc = V::for_each_class(v, p, L.f, c.ws, [&](const typename V::ClassView& cv) {
+            int rc1 = V::derive_challenges(v, cv.ps, cv.pts, cv.count, cv.challenges, st);
+            if (rc1) return rc1;
+            rc1 = V::run(v, cv.ps, cv.pts, cv.sc3, cv.count, cv.challenges, c.W(L.f.ok) + cv.first, c.ws + L.run, L.run_bytes,
+                         nullptr, nullptr, st);
+            return rc1 || !lists ? rc1 : step.klass(c, cv);
+        });
+        if (rc) return rc;
+        if ((rc = V::scatter_verdicts(L.f, c.ws, a.ok, count, st))) return rc;
+        if (!lists) {   // verified, and no pair to test or list
+            HIPCHK(zero_words_async(a.n_hits, 4, st));
+            if (a.tagged() && a.n_candidates) HIPCHK(zero_words_async(a.n_candidates, 4, st));
+            return BPP_OK;
+        }
+        const unsigned tiles = (unsigned)find_tiles(pairs);
+        hipLaunchKernelGGL(k_find_count<C>, dim3(tiles), dim3(FIND_BLOCK), 0, st, c.W(L.hit), pairs, c.W(L.tiles));
+        hipLaunchKernelGGL(k_find_offsets<C>, dim3(1), dim3(FIND_BLOCK), 0, st, c.W(L.tiles), (size_t)tiles, a.n_hits);
+        hipLaunchKernelGGL(k_find_emit<C>, dim3(tiles), dim3(FIND_BLOCK), 0, st, c.W(L.hit), c.hit_amounts(), c.W(L.masks), pairs,
+                           L.units, c.W(L.tiles), a.max_hits, a.hits);
+        HIPCHK(hipGetLastError());
+        return BPP_OK;
+    }
+
+    // host buffers in, host verdicts, hit records and counts out: find between copies
+    static int find_host(bpp_verifier* v, const FindArgs& a) {
+        if (int rc = V::container_args_ok(v, a.version)) return rc;
+        MixedPlan p;
+        int rc = mixed_plan_serialized(v->s, a.m_of, a.count, (size_t)container_point_bytes<C>(a.version), false, p);
+        if (rc) return rc;
+        const size_t units = S::units(p, a.count), pairs = a.n_keys * units;
+        DevBuf dk(true);   // the keys: wiped before they are freed, on every way out
+        BlockUpload up;
+        DevBuf dtg, dok, dhits, dn, dws;
+        BPP_TRY(up.upload(p, a.proofs, a.commitments, a.index, a.count, a.amounts, a.sealed ? units : pairs));
+        if (a.tagged()) HIPCHK(dtg.upload(a.tags, units));
+        HIPCHK(dk.upload(a.keys, a.n_keys * 32));
+        const size_t wsb = layout(v, p, a.count, a.n_keys, a.mode).total;
+        FindArgs d = a;
+        d.proofs = up.proofs.u8();
+        d.commitments = up.commitments.u8();
+        d.index = up.index.u64();
+        d.amounts = up.amounts.u64();
+        d.keys = dk.u8();
+        d.tags = dtg.u8();
+        d.max_hits = std::min(a.max_hits, pairs);   // no more records than there are pairs can come back
+        HIPCHK(dok.alloc(a.count * 4));
+        HIPCHK(dhits.alloc(d.max_hits * FIND_HIT_WORDS * 4));
+        HIPCHK(dn.alloc(8));   // the hits found, the candidates
+        HIPCHK(dws.alloc(wsb));
+        d.ok = dok.u32();
+        d.hits = dhits.u32();
+        d.n_hits = dn.u32();
+        d.n_candidates = dn.u32() + 1;
+        BPP_TRY(find(v, d, dws.p, wsb, nullptr));
+        uint32_t found[2] = {0, 0};
+        HIPCHK(dn.download(found, a.tagged() ? 8 : 4));
+        HIPCHK(dok.download(a.ok, a.count * 4));
+        HIPCHK(dhits.download(a.hits, std::min<size_t>(found[0], d.max_hits) * FIND_HIT_WORDS * 4));
+        *a.n_hits = found[0];
+        if (a.tagged() && a.n_candidates) *a.n_candidates = found[1];
+        return BPP_OK;
+    }
+};
+
+// The class step of the two rewinding modes.  Only single outputs are scanned -- the other classes need not fit a lane
+// group -- and their class comes first in gathered order: launch position = gathered position.
+template <class C>
+struct RewindStep {
+    using V = VerifyImpl<C>;
+    using K = RecoverKeysImpl<C>;
+    static constexpr int CW = coeff_words<typename C::Fr>();
+    ScanKeysJob j;
+
+    static size_t units(const MixedPlan&, size_t count) { return count; }
+    static size_t widest(const MixedPlan& p) { return p.count[0]; }
+    static size_t coeff_bytes(const bpp_verifier* v, const MixedPlan& p) {
+        return p.count[0] ? p.count[0] * coeff_elems(V::class_shape(v, 0).s.k) * CW * 4 : 0;
+    }
+    static size_t flag_bytes(const MixedPlan& p) { return p.count[0] * 4; }
+    static bool lists(const FindArgs& a, const MixedPlan& p) { return a.n_keys != 0 && p.count[0] != 0; }
+    static int open(const bpp_verifier* v, const FindArgs&, bool lists, MixedPlan&) {
+        if (lists && V::class_shape(v, 0).s.k + 2 > RECOVER_GROUP) return fail(BPP_E_ARG, "mask recovery takes shapes with log2(n m) <= 14");
+        return BPP_OK;
+    }
+    // untagged, the pair words of aggregated proofs; tagged, those of every pair that is no candidate
+    static bool zero_pairs(const FindArgs& a, const MixedPlan& p) { return a.tagged() || p.count[0] != a.count; }
+    int begin(const FindCall<C>& c) {
+        j = K::call_job(c.a.keys, c.a.n_keys, c.a.index_base, c.a.index, c.W(c.L.masks), c.W(c.L.hit), c.a.count);
+        return BPP_OK;
+    }
+    int klass(const FindCall<C>& c, const typename V::ClassView& cv) {
+        if (cv.c != 0) return BPP_OK;
+        const FindArgs& a = c.a;
+        const FindLayout<C>& L = c.L;
+        K::bind_class(cv, c.W(L.f.idx), c.W(L.f.status), c.W(L.bad), c.W(L.coeffs), j);
+        BPP_TRY(K::launch_coeffs(cv, c.W(L.coeffs), c.W(L.bad), c.st));
+        const FindJob f{c.W(L.f.ok) + cv.first, a.amounts, a.sealed ? 1u : 0u, a.amount64 ? 1u : 0u, c.hit_amounts()};
+        const uint32_t* table = c.v->table.u32();
+        const uint32_t* records = reinterpret_cast<const uint32_t*>(cv.pts);
+        const uint32_t nv = cv.ps.s.NV, v0 = 3 + 2 * cv.ps.s.k;
+        const size_t pairs0 = a.n_keys * cv.count;
+        if (!a.tagged()) {
+            BPP_TRY(K::launch_scan_keys(j, c.st));
+            hipLaunchKernelGGL(k_find_confirm<C>, dim3(cdiv(pairs0, FIND_BLOCK)), dim3(FIND_BLOCK), 0, c.st, c.v->s, table, j, f,
+                               records, nv, v0);
+            HIPCHK(hipGetLastError());
+            return BPP_OK;
+        }
+        TagJob t;
+        BPP_TRY(launch_candidates<C>(c, k_find_tags<C>, j, f.ok, cv.count, a.n_candidates, t));
+        // the list kernels: grids sized for every pair a candidate, capped; they read the count on the device
+        const size_t scan_blocks = std::min<size_t>(cdiv(pairs0 * SCAN_GROUP, SCAN_BLOCK), FIND_LIST_BLOCKS);
+        hipLaunchKernelGGL(k_find_scan_list<C>, dim3((unsigned)scan_blocks), dim3(SCAN_BLOCK), 0, c.st, j, t.list, t.n_cand);
+        hipLaunchKernelGGL(k_find_confirm_list<C>, dim3(cdiv(pairs0, FIND_BLOCK)), dim3(FIND_BLOCK), 0, c.st, c.v->s, table, j, f,
+                           records, nv, v0, t.list, t.n_cand);
+        HIPCHK(hipGetLastError());
+        return BPP_OK;
+    }
+};
+
+template <class C>
+size_t FindImpl<C>::workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys, FindMode mode) {
+    return FindEngine<C, RewindStep<C>>::workspace_bytes(v, m_of, count, n_keys, mode);
+}
+template <class C>
+int FindImpl<C>::find(bpp_verifier* v, const FindArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
+    return FindEngine<C, RewindStep<C>>::find(v, a, d_workspace, workspace_bytes, st);
+}
 template <class C>
 int FindImpl<C>::find_host(bpp_verifier* v, const FindArgs& a) {
-    if (int rc = V::container_args_ok(v, a.version)) return rc;
-    MixedPlan p;
-    int rc = mixed_plan_serialized(v->s, a.m_of, a.count, (size_t)container_point_bytes<C>(a.version), false, p);
-    if (rc) return rc;
-    const size_t pairs = a.n_keys * a.count;
-    DevBuf dk(true);   // the keys: wiped before they are freed, on every way out
-    BlockUpload up;
-    DevBuf dtg, dok, dhits, dn, dws;
-    BPP_TRY(up.upload(p, a.proofs, a.commitments, a.index, a.count, a.amounts, a.sealed ? a.count : pairs));
-    if (a.tagged) HIPCHK(dtg.upload(a.tags, a.count));
-    HIPCHK(dk.upload(a.keys, a.n_keys * 32));
-    const size_t wsb = layout(v, p, a.count, a.n_keys, a.tagged).total;
-    FindArgs d = a;
-    d.proofs = up.proofs.u8();
-    d.commitments = up.commitments.u8();
-    d.index = up.index.u64();
-    d.amounts = up.amounts.u64();
-    d.keys = dk.u8();
-    d.tags = dtg.u8();
-    d.max_hits = std::min(a.max_hits, pairs);   // no more records than there are pairs can come back
-    HIPCHK(dok.alloc(a.count * 4));
-    HIPCHK(dhits.alloc(d.max_hits * FIND_HIT_WORDS * 4));
-    HIPCHK(dn.alloc(8));   // the hits found, the candidates
-    HIPCHK(dws.alloc(wsb));
-    d.ok = dok.u32();
-    d.hits = dhits.u32();
-    d.n_hits = dn.u32();
-    d.n_candidates = dn.u32() + 1;
-    BPP_TRY(find(v, d, dws.p, wsb, nullptr));
-    uint32_t found[2] = {0, 0};
-    HIPCHK(dn.download(found, a.tagged ? 8 : 4));
-    HIPCHK(dok.download(a.ok, a.count * 4));
-    HIPCHK(dhits.download(a.hits, std::min<size_t>(found[0], d.max_hits) * FIND_HIT_WORDS * 4));
-    *a.n_hits = found[0];
-    if (a.tagged && a.n_candidates) *a.n_candidates = found[1];
-    return BPP_OK;
+    return FindEngine<C, RewindStep<C>>::find_host(v, a);
 }
 
 template <class C>

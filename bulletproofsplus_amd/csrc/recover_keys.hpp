@@ -108,10 +108,15 @@ struct ScanKeysJob {
     size_t count, total;         // proofs of this class, proofs of the call
 };
 
+// key number key_no's eight words from a buffer of keys into registers: the one place a kernel reads a key
+__device__ __forceinline__ void load_key(const uint32_t* keys, size_t key_no, uint32_t key[8]) {
+#pragma unroll
+    for (int w = 0; w < 8; w++) key[w] = keys[key_no * 8 + w];
+}
+
 // key number key_no's words from the caller's buffer into registers; returns the blinding index of caller position `caller`
 __device__ __forceinline__ uint64_t pair_key_index(const ScanKeysJob& j, size_t key_no, size_t caller, uint32_t key[8]) {
-#pragma unroll
-    for (int w = 0; w < 8; w++) key[w] = j.keys[key_no * 8 + w];
+    load_key(j.keys, key_no, key);
     return j.index ? j.index[caller] : j.index_base + caller;
 }
 

@@ -73,10 +73,10 @@ def test_entries_run_under_the_guard():
         assert s in entries and any(shim in entries[s] for shim in G.SHIMS), s
     for s in FIND[1:]:
         assert '{count, "count"}' in entries[s], (s, "count is not bounded by the shim")
-        assert "outputs_args(" in entries[s], (s, "n_keys x n_out is not bounded before the engine is read")
+        assert re.search(r"scan_keys_args\([^()]*, true\)", entries[s]), (s, "n_keys x n_out is not bounded before the engine is read")
     for s in MAKE:
         assert '{n_out, "n_out"}' in entries[s], s
-    assert "out_pairs_bounded(" in entries[FIND[0]]
+    assert "pairs_bounded(n_keys, pair_units(m_of, count, true))" in entries[FIND[0]]
 
 
 def test_wrappers_exist():
