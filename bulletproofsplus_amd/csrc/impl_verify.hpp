@@ -62,22 +62,8 @@ struct bpp_verifier {
 
 namespace bpp {
 
-inline unsigned blocks_per_proof(const VerifyShape& s, size_t count) {
-    const unsigned maxb = cdiv(s.NF, FIXED_BLOCK);
-    // small batches: aim at ~2^18 resident threads; at least one block, at most one generator per thread
-    size_t tpp = ((size_t)1 << 18) / (count ? count : 1);
-    tpp = std::max<size_t>(FIXED_BLOCK, std::min<size_t>(tpp, s.NF));
-    const unsigned b_lat = cdiv(tpp, FIXED_BLOCK);
-    // large batches: the chip holds 1024 blocks at a time, and a launch of only a few such rounds ends with a
-    // long, mostly idle tail (8 rounds of 5 ms blocks: the last 3.5 ms ran 64 blocks).  Aim at >= 32 rounds,
-    // but keep at least four generators per lane so that a block's prologue stays amortised.
-    const unsigned b_thr = std::min<unsigned>(cdiv((size_t)32768, count ? count : 1),
-                                              std::max<unsigned>(1, s.NF / (FIXED_BLOCK * 4)));
-#ifdef BPP_FORCE_PER   // tuning builds only (A/B of the launch geometry on one box)
-    if (count >= 1024) return std::max(1u, std::min<unsigned>(BPP_FORCE_PER, maxb));
-#endif
-    return std::max(1u, std::min(std::max(b_lat, b_thr), maxb));
-}
+// the launch geometry of k_fixed_msm is fixed_plan.hpp's; the workspaces are sized by its blocks_per_proof
+inline unsigned blocks_per_proof(const VerifyShape& s, size_t count) { return blocks_per_proof(s.NF, count); }
 
 // The wave-per-proof (tree) Horner serves the batches too small to fill the chip: one block per proof, so that the
 // chains spread over the CUs (with two tree waves per block they slowed each other down: 5.8 ms for 2 proofs against
@@ -830,9 +816,9 @@ int VerifyImpl<C>::run_stage(bpp_verifier* v, const VerifyShape& s, const uint64
     // form costs ~0.09 us of chip time per proof on top of the fixed-generator work (~7 G mixed additions/s) -- measured
     // on (64,1): better at 4 096 proofs, worse at 8 192
     const uint32_t tree = horner_form(s, count);
-    // a launch whose blocks are all resident at once (<= 1024): only latency counts -- its blocks also sum their own
+    // a launch whose blocks are all resident at once (<= FIXED_RESIDENT): only latency counts -- its blocks also sum their own
     // partials (mode 3 of k_fixed_msm) and the points of a proof are dealt to VAR_GROUPS lanes per window
-    const bool lone = tree == 1 && count * bpp_ <= 1024;
+    const bool lone = tree == 1 && count * bpp_ <= FIXED_RESIDENT;
     const uint32_t vgroups = lone ? VAR_GROUPS : 1u;
     v->last_horner_form = lone ? 3u : tree;
     const size_t vlanes = count * (tree == 1 ? var_wsums<C>() * vgroups : var_windows<C>());
@@ -853,20 +839,24 @@ template <class C>
 int VerifyImpl<C>::finish(bpp_verifier* v, const VerifyShape& s, uint8_t* ws, const WsLayout& L, size_t count,
                           const uint32_t* w_sc, const uint32_t* w_vw, const uint32_t* w_bad, uint32_t* d_ok,
                           uint32_t* d_out_result, uint32_t tree, bool lone, hipStream_t st, hipEvent_t* ev) {
-    const unsigned bpp_ = blocks_per_proof(s, count);
+    // the plan (fixed_plan.hpp): bpp_ blocks per proof, but ONE for each of the first `longs` proofs of a large batch; the
+    // partials stay indexed by block, nblk of them in all (<= count * bpp_, what the workspace holds)
+    const FixedPlan plan = fixed_plan(s.NF, count, lone ? 3u : tree);
+    const unsigned bpp_ = plan.per;
+    const size_t longs = plan.long_count, shorts = count - longs, nblk = fixed_plan_blocks(plan, count);
     uint32_t* w_fp = reinterpret_cast<uint32_t*>(ws + L.fpart);
     uint32_t* w_vp = reinterpret_cast<uint32_t*>(ws + L.vpart);
     HIPCHK(mark(ev, 2 * BPP_STAGE_FIXED_MSM, st));
     const unsigned hb = tree == 1 ? (unsigned)count : cdiv(count, tree == 2 ? FIXED_BLOCK / 8 : FIXED_BLOCK);
     uint32_t* w_ft = reinterpret_cast<uint32_t*>(ws + L.fthread);
-    launch_fixed_msm<C, 0>((unsigned)(hb + count * bpp_), st, s, w_sc, v->table.u32(), w_ft, bpp_, hb, w_vw, w_vp, count,
-                           lone ? 3u : tree, VpSel{1u, 0u, 1u, 0u});
+    launch_fixed_msm<C, 0>((unsigned)(hb + nblk), st, s, w_sc, v->table.u32(), w_ft, bpp_, hb, w_vw, w_vp, count,
+                           lone ? 3u : tree, VpSel{1u, 0u, 1u, 0u, (uint32_t)longs});
     HIPCHK(mark(ev, 2 * BPP_STAGE_FIXED_MSM + 1, st));
     HIPCHK(mark(ev, 2 * BPP_STAGE_FINALIZE, st));
     // 128 per-thread partials per block -> 16 -> 4 (-> 4 per proof), every lane of the fold kernels busy;
     // k_finalize adds the rest
-    const unsigned folded = bpp_ * (FIXED_BLOCK / FOLD_GROUP);
-    const unsigned folded2 = folded / FOLD_GROUP2;
+    constexpr unsigned folded1 = FIXED_BLOCK / FOLD_GROUP, per_block = folded1 / FOLD_GROUP2;   // 16, 4 per block
+    const unsigned folded = bpp_ * folded1;
     uint32_t* w_fp2 = reinterpret_cast<uint32_t*>(ws + L.fpart2);
     if (tree == 1) {   // a small batch waits for latency, not throughput: one block per proof finishes the sum as a tree,
                        // over the per-block partials k_fixed_msm left (lone) or over the first fold pass's output
@@ -879,17 +869,21 @@ int VerifyImpl<C>::finish(bpp_verifier* v, const VerifyShape& s, uint8_t* ws, co
         HIPCHK(hipGetLastError());
         return BPP_OK;
     }
-    hipLaunchKernelGGL(k_partials_fold<C>, dim3(cdiv(count * folded, 64)), dim3(64), 0, st, w_ft, FOLD_GROUP, w_fp,
-                       count * folded);
-    hipLaunchKernelGGL(k_partials_fold<C>, dim3(cdiv(count * folded2, 64)), dim3(64), 0, st, w_fp, FOLD_GROUP2, w_fp2,
-                       count * folded2);
+    hipLaunchKernelGGL(k_partials_fold<C>, dim3(cdiv(nblk * folded1, 64)), dim3(64), 0, st, w_ft, FOLD_GROUP, w_fp,
+                       nblk * folded1);
+    // Second pass, 16 -> 4 per block.  A proof with one block is then where k_finalize wants it, so the long proofs' pass
+    // writes straight into the [count][4] array that the short proofs' third pass completes: no copy, one more launch.
+    uint32_t* w_fp3 = reinterpret_cast<uint32_t*>(ws + L.fpart3);
+    if (longs)
+        hipLaunchKernelGGL(k_partials_fold<C>, dim3(cdiv(longs * per_block, 64)), dim3(64), 0, st, w_fp, FOLD_GROUP2, w_fp3,
+                           longs * per_block);
+    hipLaunchKernelGGL(k_partials_fold<C>, dim3(cdiv(shorts * bpp_ * per_block, 64)), dim3(64), 0, st,
+                       w_fp + longs * folded1 * JW, FOLD_GROUP2, w_fp2, shorts * bpp_ * per_block);
     const uint32_t* w_last = w_fp2;
-    unsigned last = folded2;
+    const unsigned last = per_block;
     if (bpp_ > 1) {   // several blocks per proof: one more pass, so that k_finalize always sees 4 partials
-        uint32_t* w_fp3 = reinterpret_cast<uint32_t*>(ws + L.fpart3);
-        last = folded2 / bpp_;
-        hipLaunchKernelGGL(k_partials_fold<C>, dim3(cdiv(count * last, 64)), dim3(64), 0, st, w_fp2, bpp_, w_fp3,
-                           count * last);
+        hipLaunchKernelGGL(k_partials_fold<C>, dim3(cdiv(shorts * last, 64)), dim3(64), 0, st, w_fp2, bpp_,
+                           w_fp3 + longs * last * JW, shorts * last);
         w_last = w_fp3;
     }
     hipLaunchKernelGGL(k_finalize<C>, dim3(cdiv(count, 64)), dim3(64), 0, st, w_last, last, w_vp, 1u, w_bad, d_ok,

@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 #include "ec.hpp"
 #include "fixed_glv.hpp"
+#include "fixed_plan.hpp"
 #include "ed25519.hpp"
 #include "ristretto.hpp"
 #include "transcript.hpp"
@@ -42,7 +43,7 @@ namespace bpp {
 constexpr unsigned MSM_BLOCK = 64;
 constexpr unsigned VS_PB = 8;                 // proofs per block of k_vs_expand, 64 lanes each
 constexpr unsigned VS_BLOCK = VS_PB * 64;
-constexpr unsigned FIXED_BLOCK = 128;
+// FIXED_BLOCK (k_fixed_msm: 128) comes with the launch plan, fixed_plan.hpp
 constexpr unsigned VAR_BLOCK = 64;
 // Proof-point MSM: signed 4-bit windows.  Plain: 65 windows of a 260-bit value (scalar + bias).  BLS12-381 and secp256k1
 // split every scalar with the curve's endomorphism first (GLV, ec.hpp glv_split_signed: k = +-k1 +- k2 mu, the image of P
@@ -1056,14 +1057,20 @@ constexpr unsigned fixed_lds_bytes() {
 //   * a commitment has two terms (g, h);
 //   * range A has scalars +1 (on G_j) or -1 (on H_j): -1 is a full-width scalar, 15 mixed additions for what is one
 //     subtraction -- k_pb_init stores +1 there and this kernel negates the table entry instead.
+//
+// long_count (the verifier's large batches only, fixed_plan.hpp; 0 everywhere else): the first long_count proofs of the
+// launch have ONE block each, whatever `per` says -- the grid behind the Horner blocks is long_count blocks of one proof,
+// then `per` blocks for each of the other proofs (fixed_block_of).
 struct VpSel {
     uint32_t nvp, first, cnt, prover;
+    uint32_t long_count = 0;
 };
 
 // Fixed-generator part: for proof b, sum_f scalar_f * F_f through the window tables.
 // scalar + bias -> W windows -> signed digits (top window: unsigned; fixed_glv.hpp) -> one table gather and
 // one mixed addition per (generator, window).  No doublings, no buckets, no scatter: the 288 GB of HBM pay for
-// that.  partials: ROLE 0, 2: [count][per][blockDim.x] jacobians (one per thread, summed by k_partials_fold);
+// that.  partials: ROLE 0, 2: [block][blockDim.x] jacobians (one per thread, summed by k_partials_fold), block = proof *
+// per + part, or under a plan (VpSel::long_count) the long proofs' single blocks first;
 // ROLE 1: [count][per] (block sums: the combined check's single MulVec, whose handful of blocks is summed by one
 // lane).  ROLE also separates the launches in profiles: 0 = the batch verifier's hot path, 1 = combined check,
 // 2 = batched prover.
@@ -1119,19 +1126,21 @@ __global__ void __launch_bounds__(FIXED_BLOCK, fixed_waves<C>()) k_fixed_msm(Ver
         }
         return;
     }
-    // flat grid after the Horner blocks: block = proof * per + part   (`per` blocks share one proof's generators)
+    // flat grid after the Horner blocks: block = proof * per + part   (`per` blocks share one proof's generators), behind
+    // the sel.long_count proofs that have one block each (fixed_block_of)
 #ifdef BPP_XCD_REMAP   // tuning builds only (DESIGN "XCDs"): the `per` blocks of a proof on ONE XCD -- workgroups go to the 8 XCDs round-robin
     uint32_t bid = blockIdx.x - horner_blocks;
     {
         const uint32_t nb = gridDim.x - horner_blocks;
-        if (nb % 8 == 0 && horner_blocks % 8 == 0) bid = (bid % 8) * (nb / 8) + bid / 8;
+        if (sel.long_count == 0 && nb % 8 == 0 && horner_blocks % 8 == 0) bid = (bid % 8) * (nb / 8) + bid / 8;
     }
 #else
     const uint32_t bid = blockIdx.x - horner_blocks;
 #endif
-    const size_t b = bid / per;
-    const uint32_t part = bid % per;
-    const uint32_t* sc = scalars + ((b / sel.cnt) * sel.nvp + sel.first + b % sel.cnt) * (size_t)s.N * 8;
+    uint32_t b, part, per_here;
+    fixed_block_of(bid, per, sel.long_count, b, part, per_here);
+    per = per_here;   // from here on `per` is this block's own
+    const uint32_t* sc = scalars + ((size_t)(b / sel.cnt) * sel.nvp + sel.first + b % sel.cnt) * (size_t)s.N * 8;
     const uint32_t stride = per * blockDim.x;
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t* ring = lds + (threadIdx.x >> 6) * WAVE_WORDS;    // [slot][piece][lane][4 words]
