@@ -323,24 +323,84 @@ extern "C" int bpp_graph_launch(bpp_graph* g, void* stream) {
     });
 }
 
+// ---- the prover entries: the batched range prover (impl_prove_batch.hpp), here and under "proving blocks of mixed
+// aggregation sizes", and the seam's (impl_wip.hpp).  Each fills its record and passes prove_args ------------------------
+namespace {
+// the argument checks the four seam entries share; 0: go on
+int wip_args(size_t nv, int flags, bool have_transcript) {
+    if (nv > VS_MAXM) return fail(BPP_E_ARG, "nv exceeds the supported maximum (64)");
+    if (flags & ~BPP_SER_TRANSCRIPT) return fail(BPP_E_ARG, "unknown flag");
+    if ((flags & BPP_SER_TRANSCRIPT) && !have_transcript) return fail(BPP_E_ARG, "BPP_SER_TRANSCRIPT needs the transcript states");
+    return BPP_OK;
+}
+
+// What tells the prover entries' checks apart; the checks, their order and every other text are prove_args.
+struct ProveEntry {
+    int flags;          // the flags it takes (an entry without a flags argument says what its name says)
+    bool empty_first;   // a count of zero is answered ahead of the buffers, the blinding and the count (the mixed entries)
+    const char* both;   // what a blind_key beside blinding scalars is told; null: the blinding is not looked at here
+    bool one_launch;    // the count is bounded here (the mixed host forms: behind their plan likewise)
+};
+constexpr int PROVE_MIXED_FLAGS = BPP_SER_TRANSCRIPT | BPP_PROVE_AMOUNT64, PROVE_SER_FLAGS = PROVE_MIXED_FLAGS | BPP_SER_UNCOMPRESSED;
+constexpr const char* BOTH_MIXED = "blind_key and d_blinding are both given";
+constexpr ProveEntry PROVE_FIXED{BPP_SER_TRANSCRIPT, false, nullptr, false};
+constexpr ProveEntry PROVE_MIXED_DEVICE{PROVE_MIXED_FLAGS, true, BOTH_MIXED, true}, PROVE_MIXED_HOST{PROVE_MIXED_FLAGS, true, nullptr, false};
+constexpr ProveEntry PROVE_SER_DEVICE{PROVE_SER_FLAGS, true, BOTH_MIXED, true}, PROVE_SER_HOST{PROVE_SER_FLAGS, true, nullptr, false};
+constexpr ProveEntry PROVE_SEAM{BPP_SER_TRANSCRIPT, false, "give blind_key or d_blinding, not both", false};
+
+// the one decoding of an entry's flags into its record, behind the refusal of those it does not take
+int prove_flags(const ProveEntry& e, int flags, ProveArgs& a) noexcept {
+    if (flags & ~e.flags) return fail(BPP_E_ARG, "unknown flag");
+    a.fs = (flags & BPP_SER_TRANSCRIPT) != 0;
+    a.amount64 = (flags & BPP_PROVE_AMOUNT64) != 0;
+    a.version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
+    return BPP_OK;
+}
+int prove_flags(const ProveEntry&, int flags, WipProveArgs& a) noexcept {
+    if (int rc = wip_args(a.nv, flags, a.transcript != nullptr)) return rc;
+    a.fs = (flags & BPP_SER_TRANSCRIPT) != 0;
+    return BPP_OK;
+}
+
+// The checks of the ten prover entries.  a holds the entry's pointers and leaves with what the flags say; buffers: whether
+// every buffer that a count above zero reads or writes, the optional ones aside, is there (a device entry: the workspace
+// too).  A count of zero passes and is answered by the entry.
+template <class A>
+int prove_args(const bpp_verifier* engine, const ProveEntry& e, int flags, A& a, bool buffers) noexcept {
+    if (!engine || (!e.empty_first && !buffers)) return fail(BPP_E_ARG, "null argument");
+    if (int rc = prove_flags(e, flags, a)) return rc;
+    if (e.empty_first) {
+        if (a.count == 0) return BPP_OK;
+        if (!buffers) return fail(BPP_E_ARG, "null argument");
+    }
+    if (e.both) {
+        if (a.blind_key && a.blinding) return fail(BPP_E_ARG, e.both);
+        if ((a.blind_key || a.blinding) && !a.fs) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
+    }
+    if (e.one_launch && a.count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    return BPP_OK;
+}
+}  // namespace
+
 extern "C" int bpp_range_prove_batch(bpp_verifier* engine, const uint64_t* v, const uint64_t* gamma, size_t count,
                                      uint64_t* out_points, uint64_t* out_scalars, uint64_t* out_V) {
-    if (!engine || !v || !gamma || !out_points || !out_scalars) return fail(BPP_E_ARG, "null argument");
+    ProveArgs a;
+    a.values = v; a.gammas = gamma; a.count = count;
+    a.out_points = out_points; a.out_scalars = out_scalars; a.out_V = out_V;
+    if (int rc = prove_args(engine, PROVE_FIXED, 0, a, v && gamma && out_points && out_scalars)) return rc;
     if (count == 0) return BPP_OK;
-    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
-        return ProveBatchImpl<decltype(cv)>::prove_batch(engine, v, gamma, count, out_points, out_scalars, out_V, false);
-    });
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int { return ProveBatchImpl<decltype(cv)>::prove_host(engine, a); });
 }
 
 extern "C" int bpp_range_prove_batch_fs(bpp_verifier* engine, const uint64_t* v, const uint64_t* gamma, size_t count,
                                         const uint8_t* blind_key, uint64_t index_base, uint64_t* out_points,
                                         uint64_t* out_scalars, uint64_t* out_V) {
-    if (!engine || !v || !gamma || !out_points || !out_scalars) return fail(BPP_E_ARG, "null argument");
+    ProveArgs a;
+    a.values = v; a.gammas = gamma; a.count = count; a.blind_key = blind_key; a.index_base = index_base;
+    a.out_points = out_points; a.out_scalars = out_scalars; a.out_V = out_V;
+    if (int rc = prove_args(engine, PROVE_FIXED, BPP_SER_TRANSCRIPT, a, v && gamma && out_points && out_scalars)) return rc;
     if (count == 0) return BPP_OK;
-    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
-        return ProveBatchImpl<decltype(cv)>::prove_batch(engine, v, gamma, count, out_points, out_scalars, out_V, true, blind_key,
-                                                     index_base);
-    });
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int { return ProveBatchImpl<decltype(cv)>::prove_host(engine, a); });
 }
 
 extern "C" size_t bpp_prover_workspace_bytes(const bpp_verifier* engine, size_t count) {
@@ -350,45 +410,35 @@ extern "C" size_t bpp_prover_workspace_bytes(const bpp_verifier* engine, size_t 
 extern "C" int bpp_range_prove_batch_device(bpp_verifier* engine, const uint64_t* d_v, const uint64_t* d_gamma,
                                             size_t count, uint64_t* d_out_points, uint64_t* d_out_scalars,
                                             uint64_t* d_out_V, void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!engine || !d_v || !d_gamma || !d_out_points || !d_out_scalars || !d_workspace)
-        return fail(BPP_E_ARG, "null argument");
+    ProveArgs a;
+    a.values = d_v; a.gammas = d_gamma; a.count = count;
+    a.out_points = d_out_points; a.out_scalars = d_out_scalars; a.out_V = d_out_V;
+    if (int rc = prove_args(engine, PROVE_FIXED, 0, a, d_v && d_gamma && d_out_points && d_out_scalars && d_workspace)) return rc;
     if (count == 0) return BPP_OK;
     return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
-        return ProveBatchImpl<decltype(cv)>::prove_batch_device(engine, d_v, d_gamma, count, d_out_points, d_out_scalars,
-                                                            d_out_V, false, nullptr, d_workspace, workspace_bytes,
-                                                            static_cast<hipStream_t>(stream));
+        return ProveBatchImpl<decltype(cv)>::prove_device(engine, a, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
     });
 }
 
+// blind_key beside d_blinding is taken here: the buffer wins
 extern "C" int bpp_range_prove_batch_fs_device(bpp_verifier* engine, const uint64_t* d_v, const uint64_t* d_gamma,
                                                size_t count, const uint8_t* blind_key, uint64_t index_base,
                                                const uint64_t* d_blinding, uint64_t* d_out_points, uint64_t* d_out_scalars,
                                                uint64_t* d_out_V, uint64_t* d_out_challenges, void* d_workspace,
                                                size_t workspace_bytes, void* stream) {
-    if (!engine || !d_v || !d_gamma || !d_out_points || !d_out_scalars || !d_workspace)
-        return fail(BPP_E_ARG, "null argument");
+    ProveArgs a;
+    a.values = d_v; a.gammas = d_gamma; a.count = count;
+    a.blind_key = blind_key; a.index_base = index_base; a.blinding = d_blinding;
+    a.out_points = d_out_points; a.out_scalars = d_out_scalars; a.out_V = d_out_V; a.out_challenges = d_out_challenges;
+    if (int rc = prove_args(engine, PROVE_FIXED, BPP_SER_TRANSCRIPT, a, d_v && d_gamma && d_out_points && d_out_scalars && d_workspace))
+        return rc;
     if (count == 0) return BPP_OK;
     return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
-        return ProveBatchImpl<decltype(cv)>::prove_batch_device(engine, d_v, d_gamma, count, d_out_points, d_out_scalars,
-                                                            d_out_V, true, d_out_challenges, d_workspace, workspace_bytes,
-                                                            static_cast<hipStream_t>(stream), blind_key, index_base,
-                                                            d_blinding);
+        return ProveBatchImpl<decltype(cv)>::prove_device(engine, a, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
     });
 }
 
 // ---- the WIP seam (impl_wip.hpp) -------------------------------------------------------------------------
-// the argument checks the four entries share; 0: go on
-static int wip_args(size_t nv, int flags, bool have_transcript) {
-    if (nv > VS_MAXM) return fail(BPP_E_ARG, "nv exceeds the supported maximum (64)");
-    if (flags & ~BPP_SER_TRANSCRIPT) return fail(BPP_E_ARG, "unknown flag");
-    if ((flags & BPP_SER_TRANSCRIPT) && !have_transcript) return fail(BPP_E_ARG, "BPP_SER_TRANSCRIPT needs the transcript states");
-    return BPP_OK;
-}
-static int wip_blinding_args(int flags, const uint8_t* blind_key, const uint64_t* blinding) {
-    if (blind_key && blinding) return fail(BPP_E_ARG, "give blind_key or d_blinding, not both");
-    if ((blind_key || blinding) && !(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
-    return BPP_OK;
-}
 extern "C" size_t bpp_wip_prover_workspace_bytes(const bpp_verifier* engine, size_t count) {
     if (count >> 32) return 0;
     return size_for(engine, [&](auto cv) { return WipImpl<decltype(cv)>::prove_ws(engine, count).total; });
@@ -402,17 +452,15 @@ extern "C" int bpp_wip_prove_batch_device(bpp_verifier* engine, const uint64_t* 
                                           const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_blinding,
                                           uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_challenges,
                                           void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!engine || !d_a || !d_b || !d_y || !d_gamma || !d_out_points || !d_out_scalars || !d_workspace)
-        return fail(BPP_E_ARG, "null argument");
-    int rc = wip_args(nv, flags, d_transcript != nullptr);
-    if (!rc) rc = wip_blinding_args(flags, blind_key, d_blinding);
-    if (rc) return rc;
+    WipProveArgs a{d_a, d_b, d_y, d_gamma, count, nv};
+    a.transcript = d_transcript;
+    a.blind_key = blind_key; a.index_base = index_base; a.blinding = d_blinding;
+    a.points = d_out_points; a.out_scalars = d_out_scalars; a.out_challenges = d_out_challenges;
+    if (int rc = prove_args(engine, PROVE_SEAM, flags, a, d_a && d_b && d_y && d_gamma && d_out_points && d_out_scalars && d_workspace))
+        return rc;
     if (count == 0) return BPP_OK;
     return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
-        return WipImpl<decltype(cv)>::prove_device(engine, d_a, d_b, d_y, d_gamma, count, nv, (flags & BPP_SER_TRANSCRIPT) != 0,
-                                                   d_transcript, blind_key, index_base, d_blinding, d_out_points, d_out_scalars,
-                                                   d_out_challenges, d_workspace, workspace_bytes,
-                                                   static_cast<hipStream_t>(stream));
+        return WipImpl<decltype(cv)>::prove_device(engine, a, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
     });
 }
 extern "C" int bpp_wip_verify_batch_device(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars,
@@ -436,16 +484,13 @@ extern "C" int bpp_wip_prove_batch(bpp_verifier* engine, const uint64_t* a, cons
                                    const uint64_t* gamma, size_t count, size_t nv, int flags, const void* transcript,
                                    const uint8_t* blind_key, uint64_t index_base, const uint64_t* blinding, uint64_t* points,
                                    uint64_t* out_scalars, uint64_t* out_challenges) {
-    if (!engine || !a || !b || !y || !gamma || !points || !out_scalars) return fail(BPP_E_ARG, "null argument");
-    int rc = wip_args(nv, flags, transcript != nullptr);
-    if (!rc) rc = wip_blinding_args(flags, blind_key, blinding);
-    if (rc) return rc;
+    WipProveArgs w{a, b, y, gamma, count, nv};
+    w.transcript = transcript;
+    w.blind_key = blind_key; w.index_base = index_base; w.blinding = blinding;
+    w.points = points; w.out_scalars = out_scalars; w.out_challenges = out_challenges;
+    if (int rc = prove_args(engine, PROVE_SEAM, flags, w, a && b && y && gamma && points && out_scalars)) return rc;
     if (count == 0) return BPP_OK;
-    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
-        return WipImpl<decltype(cv)>::prove_host(engine, a, b, y, gamma, count, nv, (flags & BPP_SER_TRANSCRIPT) != 0,
-                                                 (flags & BPP_SER_TRANSCRIPT) ? transcript : nullptr, blind_key, index_base,
-                                                 blinding, points, out_scalars, out_challenges);
-    });
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int { return WipImpl<decltype(cv)>::prove_host(engine, w); });
 }
 extern "C" int bpp_wip_verify_batch(bpp_verifier* v, const uint64_t* points, const uint64_t* scalars, const uint64_t* y,
                                     const uint64_t* statement, size_t nv, size_t count, int flags, const void* transcript,
@@ -890,10 +935,10 @@ extern "C" int bpp_range_verify_batch_serialized_grouped_mixed_device(bpp_verifi
     });
 }
 
-// ---- proving blocks of mixed aggregation sizes (impl_prove_batch.hpp prove_mixed / prove_serialized_mixed) -----------
+// ---- proving blocks of mixed aggregation sizes (impl_prove_batch.hpp prove_mixed; the checks: prove_args above) ----------
 extern "C" size_t bpp_prover_mixed_workspace_bytes(const bpp_verifier* engine, const uint32_t* m_of, size_t count) {
     if ((count && !m_of) || count > 0x7fffffffu / 64) return 0;
-    return size_for(engine, [&](auto cv) { return ProveBatchImpl<decltype(cv)>::prove_mixed_workspace_bytes(engine, m_of, count); });
+    return size_for(engine, [&](auto cv) { return ProveBatchImpl<decltype(cv)>::prove_mixed_workspace_bytes(engine, m_of, count, false); });
 }
 
 extern "C" int bpp_range_prove_batch_mixed_device(bpp_verifier* engine, const uint64_t* d_v, const uint64_t* d_gamma,
@@ -901,24 +946,21 @@ extern "C" int bpp_range_prove_batch_mixed_device(bpp_verifier* engine, const ui
                                                   uint64_t index_base, const uint64_t* d_blinding, uint64_t* d_out_points,
                                                   uint64_t* d_out_scalars, uint64_t* d_out_challenges, void* d_workspace,
                                                   size_t workspace_bytes, void* stream) {
-    if (!engine) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_PROVE_AMOUNT64)) return fail(BPP_E_ARG, "unknown flag");
+    ProveArgs a;
+    a.values = d_v; a.gammas = d_gamma; a.m_of = m_of; a.count = count;
+    a.blind_key = blind_key; a.index_base = index_base; a.blinding = d_blinding;
+    a.out_points = d_out_points; a.out_scalars = d_out_scalars; a.out_challenges = d_out_challenges;
+    if (int rc = prove_args(engine, PROVE_MIXED_DEVICE, flags, a, d_v && d_gamma && m_of && d_out_points && d_out_scalars && d_workspace))
+        return rc;
     if (count == 0) return BPP_OK;
-    if (!d_v || !d_gamma || !m_of || !d_out_points || !d_out_scalars || !d_workspace) return fail(BPP_E_ARG, "null argument");
-    if (blind_key && d_blinding) return fail(BPP_E_ARG, "blind_key and d_blinding are both given");
-    if ((blind_key || d_blinding) && !(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
-    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
     return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
-        return ProveBatchImpl<decltype(cv)>::prove_mixed(engine, d_v, d_gamma, m_of, count, (flags & BPP_SER_TRANSCRIPT) != 0, blind_key,
-                                                     index_base, d_blinding, d_out_points, d_out_scalars, d_out_challenges,
-                                                     d_workspace, workspace_bytes, static_cast<hipStream_t>(stream),
-                                                     (flags & BPP_PROVE_AMOUNT64) != 0);
+        return ProveBatchImpl<decltype(cv)>::prove_device(engine, a, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
     });
 }
 
 extern "C" size_t bpp_prover_serialized_mixed_workspace_bytes(const bpp_verifier* engine, const uint32_t* m_of, size_t count) {
     if ((count && !m_of) || count > 0x7fffffffu / 64) return 0;
-    return size_for(engine, [&](auto cv) { return ProveBatchImpl<decltype(cv)>::prove_ser_mixed_workspace_bytes(engine, m_of, count); });
+    return size_for(engine, [&](auto cv) { return ProveBatchImpl<decltype(cv)>::prove_mixed_workspace_bytes(engine, m_of, count, true); });
 }
 
 extern "C" int bpp_range_prove_batch_serialized_mixed_device(bpp_verifier* engine, const uint64_t* d_v, const uint64_t* d_gamma,
@@ -927,19 +969,15 @@ extern "C" int bpp_range_prove_batch_serialized_mixed_device(bpp_verifier* engin
                                                              const uint64_t* d_blinding, void* d_out_proofs,
                                                              void* d_out_commitments, void* d_workspace, size_t workspace_bytes,
                                                              void* stream) {
-    if (!engine) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED | BPP_PROVE_AMOUNT64)) return fail(BPP_E_ARG, "unknown flag");
+    ProveArgs a;
+    a.values = d_v; a.gammas = d_gamma; a.m_of = m_of; a.count = count;
+    a.blind_key = blind_key; a.index_base = index_base; a.blinding = d_blinding;
+    a.out_proofs = static_cast<uint8_t*>(d_out_proofs); a.out_commitments = static_cast<uint8_t*>(d_out_commitments);
+    if (int rc = prove_args(engine, PROVE_SER_DEVICE, flags, a, d_v && d_gamma && m_of && d_out_proofs && d_out_commitments && d_workspace))
+        return rc;
     if (count == 0) return BPP_OK;
-    if (!d_v || !d_gamma || !m_of || !d_out_proofs || !d_out_commitments || !d_workspace) return fail(BPP_E_ARG, "null argument");
-    if (blind_key && d_blinding) return fail(BPP_E_ARG, "blind_key and d_blinding are both given");
-    if ((blind_key || d_blinding) && !(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
-    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
-    const uint32_t version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
     return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
-        return ProveBatchImpl<decltype(cv)>::prove_serialized_mixed(
-            engine, d_v, d_gamma, m_of, count, (flags & BPP_SER_TRANSCRIPT) != 0, blind_key, index_base, d_blinding,
-            static_cast<uint8_t*>(d_out_proofs), static_cast<uint8_t*>(d_out_commitments), d_workspace, workspace_bytes,
-            static_cast<hipStream_t>(stream), version, (flags & BPP_PROVE_AMOUNT64) != 0);
+        return ProveBatchImpl<decltype(cv)>::prove_device(engine, a, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
     });
 }
 
@@ -947,29 +985,24 @@ extern "C" int bpp_range_prove_batch_serialized_mixed_device(bpp_verifier* engin
 extern "C" int bpp_range_prove_batch_mixed(bpp_verifier* engine, const uint64_t* v, const uint64_t* gamma, const uint32_t* m_of,
                                            size_t count, int flags, const uint8_t* blind_key, uint64_t index_base,
                                            uint64_t* out_points, uint64_t* out_scalars, uint64_t* out_challenges) {
-    if (!engine) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_PROVE_AMOUNT64)) return fail(BPP_E_ARG, "unknown flag");
+    ProveArgs a;
+    a.values = v; a.gammas = gamma; a.m_of = m_of; a.count = count; a.blind_key = blind_key; a.index_base = index_base;
+    a.out_points = out_points; a.out_scalars = out_scalars; a.out_challenges = out_challenges;
+    if (int rc = prove_args(engine, PROVE_MIXED_HOST, flags, a, v && gamma && m_of && out_points && out_scalars)) return rc;
     if (count == 0) return BPP_OK;
-    if (!v || !gamma || !m_of || !out_points || !out_scalars) return fail(BPP_E_ARG, "null argument");
-    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
-        return ProveBatchImpl<decltype(cv)>::prove_mixed_host(engine, v, gamma, m_of, count, flags, blind_key, index_base,
-                                                              out_points, out_scalars, out_challenges);
-    });
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int { return ProveBatchImpl<decltype(cv)>::prove_host(engine, a); });
 }
 
 extern "C" int bpp_range_prove_batch_serialized_mixed(bpp_verifier* engine, const uint64_t* v, const uint64_t* gamma,
                                                       const uint32_t* m_of, size_t count, int flags, const uint8_t* blind_key,
                                                       uint64_t index_base, uint8_t* out_proofs, uint8_t* out_commitments) {
-    if (!engine) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED | BPP_PROVE_AMOUNT64)) return fail(BPP_E_ARG, "unknown flag");
+    ProveArgs a;
+    a.values = v; a.gammas = gamma; a.m_of = m_of; a.count = count; a.blind_key = blind_key; a.index_base = index_base;
+    a.out_proofs = out_proofs; a.out_commitments = out_commitments;
+    if (int rc = prove_args(engine, PROVE_SER_HOST, flags, a, v && gamma && m_of && out_proofs && out_commitments)) return rc;
     if (count == 0) return BPP_OK;
-    if (!v || !gamma || !m_of || !out_proofs || !out_commitments) return fail(BPP_E_ARG, "null argument");
-    const size_t cb = container_point_size(engine->ctx.curve, (flags & BPP_SER_UNCOMPRESSED) ? 2 : 1);
-    if (int rc = container_version_ok(cb)) return rc;
-    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
-        return ProveBatchImpl<decltype(cv)>::prove_serialized_mixed_host(engine, v, gamma, m_of, count, flags, blind_key,
-                                                                         index_base, out_proofs, out_commitments);
-    });
+    if (int rc = container_version_ok(container_point_size(engine->ctx.curve, (int)a.version))) return rc;
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int { return ProveBatchImpl<decltype(cv)>::prove_host(engine, a); });
 }
 
 // ---- commitments for a block of amounts through the engine's tables (commit.hpp; RangeProver::commit, range/prover.rs:28-42;

@@ -8,13 +8,54 @@
 
 namespace bpp {
 
+// What a prove call takes, in the C ABI's order.  For a device form the pointers are the device's, for prove_host the host's;
+// m_of and blind_key (32 bytes) are the host's always.
+//   m_of null : `count` proofs of the engine's own shape at fixed strides.  values: count x m u64 ; gammas: count x m scalars ;
+//     blinding: count x (5 + 2k) canonical scalars.  Written: out_points, count x (3 + 2k) wire points [A, wip.A, wip.B, L..,
+//     R..] ; out_scalars, count x 3 ; out_V (may be null), count x m wire points ; out_challenges (fs alone, may be null),
+//     count x (3 + k) scalars [y, z, e, e_1..e_k].
+//   m_of given: proof i has m_of[i] values (mixed.hpp prove_plan).  values, gammas, blinding (5 + 2 k_i scalars per proof) and
+//     out_challenges (3 + k_i) are packed in caller order.  Wire form: out_points, record i [A, wip.A, wip.B, L.., R.., V_0..]
+//     at wire point sum_{j<i} (3 + 2 k_j + m_j) -- run_mixed's d_points -- out_scalars, count x 3, and out_challenges (may be
+//     null).  Serialized form, which out_proofs selects: out_proofs, containers packed back to back (container i of
+//     container_bytes(k_i, version) bytes), and out_commitments, m_i encoded commitments per proof in a buffer of their own
+//     -- run_serialized_mixed's input -- and no other output.  out_V is read by neither.
+// fs = false: the reference's constant challenges, every MulVec of a chunk in ONE k_fixed_msm launch.  fs = true: challenges
+// from the transcript (transcript.hpp): A and the commitments first, then y, z, then the argument -- 3 + k smaller launches.
+// Blinding (prover_batch.hpp pb_blind): `blinding` (the device forms alone), or blind_key expanded on the device with proof
+// i's index index_base + i, or -- both null -- the reference's literals.
+struct ProveArgs {
+    const uint64_t *values = nullptr, *gammas = nullptr;
+    const uint32_t* m_of = nullptr;
+    size_t count = 0;
+    bool fs = false, amount64 = false;   // amount64: the commitments' scalar on g is the u64, not `v as i32`
+    uint32_t version = 1;                // of the containers
+    const uint8_t* blind_key = nullptr;
+    uint64_t index_base = 0;
+    const uint64_t* blinding = nullptr;
+    uint64_t *out_points = nullptr, *out_scalars = nullptr, *out_V = nullptr, *out_challenges = nullptr;
+    uint8_t *out_proofs = nullptr, *out_commitments = nullptr;
+    // Not the caller's: what prove_mixed tells prove_batch_device about one class of its block, and the debug hook's challenges.
+    struct Inner {
+        const PassShape* ps = nullptr;   // the shape proved: a prefix view (n, m') of the engine's tables -- the proofs of
+                                         // PublicKey::new(n m'); null: the engine's own
+        // (device) the class's `count` entries by gathered position (prover_batch.hpp PX_*).  values, gammas, blinding and
+        // out_challenges are then the block's PACKED buffers, and each record, commitments behind it, goes to wire point
+        // PX_REC of out_points.
+        const uint32_t* px = nullptr;
+        // (device; fs = false and fixed strides alone; tu_debug.hip bpp_debug_prover_scalars) count x (3 + k) canonical
+        // scalars [y, z, e, e_1..e_k], a block per proof in place of the shape's literals.  y and every e_t non-zero: the
+        // whole kernels invert their product.
+        const uint64_t* challenges = nullptr;
+    } in;
+};
+
 template <class C>
 struct ProveBatchImpl {
     using V = VerifyImpl<C>;
     static constexpr int JW = V::JW, WW = V::WW;
 
-    // Device-resident form: values, gammas, outputs and workspace are device buffers, nothing touches the host
-    // and nothing synchronises.  The batch is processed in chunks that reuse one workspace.
+    // The workspace of prove_batch_device: the batch is processed in chunks of `chunk` proofs that reuse it.
     struct ProveLayout {
         size_t a, b, cG, cH, pwy, con, vps, part, part1, part2, vout, trst, ch, blind, vals, gams, total;
         size_t chunk;
@@ -78,45 +119,31 @@ struct ProveBatchImpl {
     };
     // one MulVec launch over `sel` of every proof's virtual proofs, then their wire points into the records
     static void mulvec(const Chunk& c, VpSel sel);
-    // The chunk's blinding scalars.  slice: the chunk's part of the caller's buffer (a mixed block: gathered into w_blind
-    // already), else blind_key (32 bytes, host) expanded into w_blind by k_pb_blind -- proof p of the chunk with index
-    // `index` + p, or `index` + its PX_CALLER when there is a px -- else null: the literals.
-    static const uint32_t* chunk_blinding(const uint32_t* slice, const uint8_t* blind_key, uint64_t index, uint32_t k, size_t cnt,
-                                          const uint32_t* px, uint32_t* w_blind, hipStream_t st);
+    // The chunk's blinding scalars, c.blind.  It comes as the chunk's part of the caller's buffer (a mixed block: gathered into
+    // L.blind already) and stays; null, it becomes blind_key (32 bytes, host) expanded into L.blind by k_pb_blind -- proof p
+    // of the chunk with index `index` + p, or `index` + its PX_CALLER when there is a px -- or stays null: the literals.
+    static void chunk_blinding(Chunk& c, const uint8_t* blind_key, uint64_t index);
     // The argument on a chunk whose state the caller's first kernel has written (k_pb_init, k_wip_init): the k rounds and
     // the final step.  fs = false: every kernel whole, then ONE MulVec over `literal_sel`.  fs = true: each round's L_t, R_t
     // before e_t, wip.A and wip.B before e -- the kernels in halves around k + 1 MulVecs and the hashing into c.ch.
     static void argument(const Chunk& c, bool fs, VpSel literal_sel);
 
-    // The range prover.  d_values: count x m u64 ; d_gammas: count x m scalars ; d_out_points: count x (3 + 2k) wire points ;
-    // d_out_scalars: count x 3 scalars ; d_out_V: count x m wire points (may be null).
-    // fs = false: the reference's constant challenges, every MulVec of the batch in ONE k_fixed_msm launch.
-    // fs = true : challenges from the transcript (transcript.hpp): A and the commitments first, then y, z, then the argument
-    //             -- 3 + k smaller launches.  d_out_challenges (count x (3 + k) scalars, may be null): [y, z, e, e_1..e_k].
-    // Blinding (prover_batch.hpp pb_blind): d_blinding (count x (5 + 2k) canonical scalars), or blind_key (32 bytes, host)
-    // expanded on the device with the global proof index index_base + p, or -- both null -- the reference's literals.
-    // ps: the shape proved -- the engine's own, or a prefix view (n, m') of its tables: the proofs of PublicKey::new(n m').
-    // px (one class of a mixed block, ps its view; prover_batch.hpp PX_*): `count` entries by gathered position.  The
-    // values, gammas, blinding scalars and challenge blocks are then the caller's PACKED buffers and each record,
-    // commitments behind it, goes to wire point PX_REC of d_out_points (d_out_V is not used).
-    // d_challenges (fs = false and fixed strides alone; tu_debug.hip bpp_debug_prover_scalars): count x (3 + k) canonical
-    // scalars [y, z, e, e_1..e_k], a block per proof in place of the shape's literals.  y and every e_t non-zero: the whole
-    // kernels invert their product.
-    static int prove_batch_device(bpp_verifier* v, const PassShape& ps, const uint64_t* d_values, const uint64_t* d_gammas,
-                                  size_t count, uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_V, bool fs,
-                                  uint64_t* d_out_challenges, void* d_workspace, size_t workspace_bytes, hipStream_t st,
-                                  const uint8_t* blind_key = nullptr, uint64_t index_base = 0,
-                                  const uint64_t* d_blinding = nullptr, const uint32_t* px = nullptr, bool amount64 = false,
-                                  const uint64_t* d_challenges = nullptr);
-    static int prove_batch_device(bpp_verifier* v, const uint64_t* d_values, const uint64_t* d_gammas, size_t count,
-                                  uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_V, bool fs,
-                                  uint64_t* d_out_challenges, void* d_workspace, size_t workspace_bytes, hipStream_t st,
-                                  const uint8_t* blind_key = nullptr, uint64_t index_base = 0,
-                                  const uint64_t* d_blinding = nullptr, bool amount64 = false) {
-        return prove_batch_device(v, V::own(v), d_values, d_gammas, count, d_out_points, d_out_scalars, d_out_V, fs,
-                                  d_out_challenges, d_workspace, workspace_bytes, st, blind_key, index_base, d_blinding, nullptr,
-                                  amount64);
+    // ---- the device forms: every buffer of `a` and the workspace in HBM, nothing synchronises ---------------------------
+    // a.m_of null: prove_batch_device, else prove_mixed
+    static int prove_device(bpp_verifier* v, const ProveArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
+        return a.m_of ? prove_mixed(v, a, d_workspace, workspace_bytes, st)
+                      : prove_batch_device(v, a, d_workspace, workspace_bytes, st);
     }
+    // `a.count` proofs of one shape (a.in.ps), in chunks that reuse one workspace (prove_layout)
+    static int prove_batch_device(bpp_verifier* v, const ProveArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st);
+    // where one chunk reads its inputs and writes its outputs, and the blinding index of its first proof
+    struct ChunkIo {
+        const uint32_t* px;      // null: fixed strides
+        const uint64_t* vals;
+        const uint32_t *gams, *blinding;   // blinding: the caller's scalars for the chunk, or null
+        uint64_t index;
+        uint32_t *o_pts, *o_sc, *o_V, *o_ch;
+    };
 
     // ---- ... of a block of MIXED aggregation sizes (mixed.hpp prove_plan): proof i has m_of[i] values ---------------
     // workspace = the per-proof indices (PX_* | SX_*, by gathered position) | serialized form: the class regions of wire
@@ -134,58 +161,21 @@ struct ProveBatchImpl {
         w.total = o.total;
         return w;
     }
-    // 0 for an m_of the engine does not take
-    static size_t prove_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
+    // 0 for an m_of the engine does not take, or -- serialized -- an engine the container does not hold
+    static size_t prove_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, bool serialized) {
         MixedPlan p;
-        if (prove_plan(v->s, m_of, count, 0, false, p)) return 0;
-        return prove_mixed_layout(v, p, count, false).total;
+        if (serialized && !V::container_shape_ok(v)) return 0;
+        if (prove_plan(v->s, m_of, count, serialized ? max_point_bytes<C>() : 0, false, p)) return 0;
+        return prove_mixed_layout(v, p, count, serialized).total;
     }
-    static size_t prove_ser_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
-        MixedPlan p;
-        if (!V::container_shape_ok(v) || prove_plan(v->s, m_of, count, max_point_bytes<C>(), false, p)) return 0;
-        return prove_mixed_layout(v, p, count, true).total;
-    }
-    // d_values: sum m_i u64, d_gammas: sum m_i scalars, d_blinding (may be null): 5 + 2 k_i scalars per proof, all packed
-    // in caller order; m_of: host.  d_out_points: record i [A, wip.A, wip.B, L.., R.., V_0..] at wire point
-    // sum_{j<i} (3 + 2 k_j + m_j) -- run_mixed's d_points; d_out_scalars: count x 3; d_out_challenges (may be null): the
-    // packed 3 + k_i blocks.  Proof i's blinding index is index_base + i.  Uploads the per-proof index (blocking the host
-    // until the copy has read it), the rest is enqueued on st.
-    static int prove_mixed(bpp_verifier* v, const uint64_t* d_values, const uint64_t* d_gammas, const uint32_t* m_of,
-                           size_t count, bool fs, const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_blinding,
-                           uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_challenges, void* d_workspace,
-                           size_t workspace_bytes, hipStream_t st, bool amount64 = false);
-    // ... as containers packed back to back in caller order (container i of container_bytes(k_i, version) bytes) and
-    // m_i encoded commitments per proof in a buffer of their own: run_serialized_mixed's input
-    static int prove_serialized_mixed(bpp_verifier* v, const uint64_t* d_values, const uint64_t* d_gammas, const uint32_t* m_of,
-                                      size_t count, bool fs, const uint8_t* blind_key, uint64_t index_base,
-                                      const uint64_t* d_blinding, uint8_t* d_out_proofs, uint8_t* d_out_commitments,
-                                      void* d_workspace, size_t workspace_bytes, hipStream_t st, uint32_t version,
-                                      bool amount64 = false);
-    // the shared body: plan p (with its indices) and layout L in hand, every class present proved with its view
-    static int prove_mixed_classes(bpp_verifier* v, const MixedPlan& p, const ProveMixedLayout& L, const uint64_t* d_values,
-                                   const uint64_t* d_gammas, bool fs, const uint8_t* blind_key, uint64_t index_base,
-                                   const uint64_t* d_blinding, uint64_t* d_out_points, uint64_t* d_out_scalars,
-                                   uint64_t* d_out_challenges, uint8_t* ws, size_t workspace_bytes, hipStream_t st,
-                                   bool amount64 = false);
+    // Every class present proved with its view, one after the other on st.  Serialized: into the class regions of the
+    // workspace (the layout the mixed decoder writes); the encoder is the only kernel that touches the caller's byte buffers.
+    // Uploads the per-proof index (blocking the host until the copy has read it), the rest is enqueued on st.
+    static int prove_mixed(bpp_verifier* v, const ProveArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st);
 
-    // ---- host buffers in, host buffers out ------------------------------------------------------------------------------
-    static int prove_batch(bpp_verifier* v, const uint64_t* values, const uint64_t* gammas, size_t count,
-                           uint64_t* out_points, uint64_t* out_scalars, uint64_t* out_V, bool fs,
-                           const uint8_t* blind_key = nullptr, uint64_t index_base = 0, bool amount64 = false);
-    // bpp_range_prove_batch_mixed / _serialized_mixed past their argument checks (flags: BPP_SER_* | BPP_PROVE_AMOUNT64):
-    // the device forms above between copies, the sizes of every buffer from the plan
-    static int prove_mixed_host(bpp_verifier* v, const uint64_t* values, const uint64_t* gammas, const uint32_t* m_of,
-                                size_t count, int flags, const uint8_t* blind_key, uint64_t index_base, uint64_t* out_points,
-                                uint64_t* out_scalars, uint64_t* out_challenges);
-    static int prove_serialized_mixed_host(bpp_verifier* v, const uint64_t* values, const uint64_t* gammas, const uint32_t* m_of,
-                                           size_t count, int flags, const uint8_t* blind_key, uint64_t index_base,
-                                           uint8_t* out_proofs, uint8_t* out_commitments);
-    // the amounts (and gammas) of the block p
-    static size_t plan_values(const MixedPlan& p) {
-        size_t nval = 0;
-        for (uint32_t c = 0; c < MIXED_CLASSES; c++) nval += p.count[c] << c;
-        return nval;
-    }
+    // ---- host buffers in, host buffers out: prove_device on the null stream between copies, the size of every buffer from
+    // the shape or from the plan; whatever output is not null is downloaded ------------------------------------------------
+    static int prove_host(bpp_verifier* v, const ProveArgs& a);
 };
 
 // ---- definitions: compiled by tu_prove_*.hip alone (BPP_IMPL_DEFINITIONS); everybody else sees the `extern template` below ----
@@ -207,13 +197,14 @@ void ProveBatchImpl<C>::mulvec(const Chunk& c, VpSel sel) {
 }
 
 template <class C>
-const uint32_t* ProveBatchImpl<C>::chunk_blinding(const uint32_t* slice, const uint8_t* blind_key, uint64_t index, uint32_t k,
-                                                  size_t cnt, const uint32_t* px, uint32_t* w_blind, hipStream_t st) {
-    if (slice || !blind_key) return slice;
+void ProveBatchImpl<C>::chunk_blinding(Chunk& c, const uint8_t* blind_key, uint64_t index) {
+    if (c.blind || !blind_key) return;
     BlindKey bk;
     load_key_words(blind_key, bk.w);
-    hipLaunchKernelGGL(k_pb_blind<C>, dim3(cdiv(cnt * pb_blind_elems(k), 64)), dim3(64), 0, st, bk, index, k, w_blind, cnt, px);
-    return w_blind;
+    uint32_t* w_blind = c.w(c.L.blind);
+    hipLaunchKernelGGL(k_pb_blind<C>, dim3(cdiv(c.cnt * pb_blind_elems(c.s.k), 64)), dim3(64), 0, c.st, bk, index, c.s.k, w_blind,
+                       c.cnt, c.px);
+    c.blind = w_blind;
 }
 
 template <class C>
@@ -249,211 +240,166 @@ void ProveBatchImpl<C>::argument(const Chunk& c, bool fs, VpSel literal_sel) {
 }
 
 template <class C>
-int ProveBatchImpl<C>::prove_batch_device(bpp_verifier* v, const PassShape& ps, const uint64_t* d_values,
-                                          const uint64_t* d_gammas, size_t count, uint64_t* d_out_points,
-                                          uint64_t* d_out_scalars, uint64_t* d_out_V, bool fs, uint64_t* d_out_challenges,
-                                          void* d_workspace, size_t workspace_bytes, hipStream_t st, const uint8_t* blind_key,
-                                          uint64_t index_base, const uint64_t* d_blinding, const uint32_t* px, bool amount64,
-                                          const uint64_t* d_challenges) {
+int ProveBatchImpl<C>::prove_batch_device(bpp_verifier* v, const ProveArgs& a, void* d_workspace, size_t workspace_bytes,
+                                          hipStream_t st) {
+    const PassShape ps = a.in.ps ? *a.in.ps : V::own(v);
     const VerifyShape& s = ps.s;
     const uint32_t k = s.k, m = s.m, nvp = pb_num_vps(k, m);
-    const ProveLayout L = prove_layout(s, count, px != nullptr);
+    const uint32_t* px = a.in.px;
+    const ProveLayout L = prove_layout(s, a.count, px != nullptr);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
-    if (d_challenges && (fs || px)) return fail(BPP_E_ARG, "chosen challenges: literal mode, fixed strides");
+    if (a.in.challenges && (a.fs || px)) return fail(BPP_E_ARG, "chosen challenges: literal mode, fixed strides");
     ProverConsts pc = literals();
-    pc.alpha = m == 1 ? 7 : 33;         // range/mod.rs:94 / :256
-    pc.amount64 = amount64 ? 1u : 0u;   // the commitments' scalar on g: the u64, not `v as i32` (range/prover.rs:37)
+    pc.alpha = m == 1 ? 7 : 33;           // range/mod.rs:94 / :256
+    pc.amount64 = a.amount64 ? 1u : 0u;   // the commitments' scalar on g: the u64, not `v as i32` (range/prover.rs:37)
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
-    for (size_t base = 0; base < count; base += L.chunk) {
-        const size_t cnt = std::min(L.chunk, count - base);
-        const uint32_t* cpx = px ? px + base * PX_WORDS : nullptr;   // this chunk's entries of a mixed block
-        uint32_t* o_pts = reinterpret_cast<uint32_t*>(d_out_points) + (px ? 0 : base * (size_t)(3 + 2 * k) * WW);
-        uint32_t* o_sc = reinterpret_cast<uint32_t*>(d_out_scalars) + (px ? 0 : base * 24);
-        uint32_t* o_V = d_out_V && !px ? reinterpret_cast<uint32_t*>(d_out_V) + base * (size_t)m * WW : W(L.vout);
-        const uint64_t* vals = d_values + base * m;
-        const uint32_t* gams = reinterpret_cast<const uint32_t*>(d_gammas) + base * (size_t)m * 8;
-        if (px) {   // the chunk's inputs out of the caller's packed buffers
-            hipLaunchKernelGGL(k_pb_gather_mixed<C>, dim3((unsigned)cnt), dim3(64), 0, st, cpx, m, k, d_values, d_gammas,
-                               d_blinding, reinterpret_cast<uint64_t*>(ws + L.vals), reinterpret_cast<uint64_t*>(ws + L.gams),
+    auto U32 = [](uint64_t* q) { return reinterpret_cast<uint32_t*>(q); };
+    auto CU32 = [](const uint64_t* q) { return reinterpret_cast<const uint32_t*>(q); };
+    const size_t rec = (size_t)(3 + 2 * k) * WW, chal = (size_t)(3 + k) * 8, bl = (size_t)pb_blind_elems(k) * 8;   // words
+    for (size_t base = 0; base < a.count; base += L.chunk) {
+        const size_t cnt = std::min(L.chunk, a.count - base);
+        ChunkIo io;
+        if (px) {
+            // One class of a mixed block.  The chunk's inputs are gathered out of the caller's packed buffers; records
+            // (commitments behind them), triples and challenge blocks go through the index, whose PX_CALLER carries the
+            // proof's part of the blinding index.
+            const uint32_t* cpx = px + base * PX_WORDS;
+            uint64_t* g_vals = reinterpret_cast<uint64_t*>(ws + L.vals);
+            hipLaunchKernelGGL(k_pb_gather_mixed<C>, dim3((unsigned)cnt), dim3(64), 0, st, cpx, m, k, a.values, a.gammas,
+                               a.blinding, g_vals, reinterpret_cast<uint64_t*>(ws + L.gams),
                                reinterpret_cast<uint64_t*>(ws + L.blind));
-            vals = reinterpret_cast<const uint64_t*>(ws + L.vals);
-            gams = W(L.gams);
+            io = ChunkIo{cpx, g_vals, W(L.gams), a.blinding ? W(L.blind) : nullptr, a.index_base, U32(a.out_points),
+                         U32(a.out_scalars), W(L.vout), W(L.ch)};
+        } else {
+            // Fixed strides: the chunk's slice of every buffer; the commitments and the challenge blocks that the caller
+            // does not want stay in the workspace.
+            io = ChunkIo{nullptr,
+                         a.values + base * m,
+                         CU32(a.gammas) + base * (size_t)m * 8,
+                         a.blinding ? CU32(a.blinding) + base * bl : nullptr,
+                         a.index_base + base,
+                         U32(a.out_points) + base * rec,
+                         U32(a.out_scalars) + base * 24,
+                         a.out_V ? U32(a.out_V) + base * (size_t)m * WW : W(L.vout),
+                         a.out_challenges ? U32(a.out_challenges) + base * chal : W(L.ch)};
         }
-        const uint32_t* bl = reinterpret_cast<const uint32_t*>(d_blinding);   // a mixed block's: gathered into L.blind above
-        const uint32_t* blind = chunk_blinding(bl && !px ? bl + base * (size_t)pb_blind_elems(k) * 8 : bl ? W(L.blind) : nullptr,
-                                               blind_key, px ? index_base : index_base + base, k, cnt, cpx, W(L.blind), st);
-        // the transcript's challenges [y, z, e, e_1..e_k] are hashed into the caller's block when it has fixed strides; the
-        // kernels read those, chs words apart, or the shape's literals, one block for all -- or, in their place, the blocks
-        // a test chose (d_challenges)
-        uint32_t* o_ch =
-            d_out_challenges && !px ? reinterpret_cast<uint32_t*>(d_out_challenges) + base * (size_t)(3 + k) * 8 : W(L.ch);
-        const uint32_t* chosen = reinterpret_cast<const uint32_t*>(d_challenges);
-        const uint32_t* ch = fs ? o_ch : chosen ? chosen + base * (size_t)(3 + k) * 8 : ps.challenges;
-        const uint32_t chs = fs || chosen ? (3 + k) * 8 : 0u;
-        const Chunk c{s, pc, L, ws, cnt, blind, cpx, o_pts, o_V, o_sc, o_ch, st, v->table.u32()};
+        Chunk c{s, pc, L, ws, cnt, io.blinding, io.px, io.o_pts, io.o_V, io.o_sc, io.o_ch, st, v->table.u32()};
+        chunk_blinding(c, a.blind_key, io.index);
+        // the transcript's challenges [y, z, e, e_1..e_k] are hashed into io.o_ch; the kernels read those, chs words apart,
+        // or the shape's literals, one block for all -- or, in their place, the blocks a test chose (a.in.challenges)
+        const uint32_t* chosen = a.in.challenges ? CU32(a.in.challenges) + base * chal : nullptr;
+        const uint32_t* ch = a.fs ? io.o_ch : chosen ? chosen : ps.challenges;
+        const uint32_t chs = a.fs || chosen ? (uint32_t)chal : 0u;
         auto init = [&](uint32_t phase) {
-            hipLaunchKernelGGL(k_pb_init<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, blind, phase, fs ? 1u : 0u, vals, gams,
-                               ch, chs, W(L.a), W(L.b), W(L.cG), W(L.cH), W(L.pwy), W(L.con), W(L.vps));
+            hipLaunchKernelGGL(k_pb_init<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, pc, c.blind, phase, a.fs ? 1u : 0u, io.vals,
+                               io.gams, ch, chs, W(L.a), W(L.b), W(L.cG), W(L.cH), W(L.pwy), W(L.con), W(L.vps));
         };
-        init(fs ? PB_PRE : PB_ALL);
-        if (fs) {
+        init(a.fs ? PB_PRE : PB_ALL);
+        if (a.fs) {
             mulvec(c, VpSel{nvp, 0u, 1u, 1u});              // A
             mulvec(c, VpSel{nvp, 2 * k + 3, m, 1u});        // V_0 .. V_{m-1}
-            hipLaunchKernelGGL(k_pb_fs_yz<C>, dim3(cdiv(cnt, 64)), dim3(64), 0, st, s, ps.tr0, o_pts, o_V, W(L.trst), o_ch, cnt,
-                               cpx);
+            hipLaunchKernelGGL(k_pb_fs_yz<C>, dim3(cdiv(cnt, 64)), dim3(64), 0, st, s, ps.tr0, io.o_pts, io.o_V, W(L.trst),
+                               io.o_ch, cnt, io.px);
             init(PB_POST);
         }
-        argument(c, fs, VpSel{nvp, 0u, nvp, 1u});   // literal mode: every virtual proof of the chunk in one launch
-        if (px && d_out_challenges)   // a mixed block: the chunk's challenge blocks to their places in the packed buffer
-            hipLaunchKernelGGL(k_pb_challenges_out<C>, dim3((unsigned)cnt), dim3(64), 0, st, cpx, k,
-                               reinterpret_cast<const uint64_t*>(ch), chs / 2, d_out_challenges);
+        argument(c, a.fs, VpSel{nvp, 0u, nvp, 1u});   // literal mode: every virtual proof of the chunk in one launch
+        if (px && a.out_challenges)   // a mixed block: the chunk's challenge blocks to their places in the packed buffer
+            hipLaunchKernelGGL(k_pb_challenges_out<C>, dim3((unsigned)cnt), dim3(64), 0, st, io.px, k,
+                               reinterpret_cast<const uint64_t*>(ch), chs / 2, a.out_challenges);
     }
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
 
-// Every class present, one after the other on st, with its view and its slice of the index; the classes share L.run.
 template <class C>
-int ProveBatchImpl<C>::prove_mixed_classes(bpp_verifier* v, const MixedPlan& p, const ProveMixedLayout& L,
-                                           const uint64_t* d_values, const uint64_t* d_gammas, bool fs, const uint8_t* blind_key,
-                                           uint64_t index_base, const uint64_t* d_blinding, uint64_t* d_out_points,
-                                           uint64_t* d_out_scalars, uint64_t* d_out_challenges, uint8_t* ws,
-                                           size_t workspace_bytes, hipStream_t st, bool amount64) {
-    const size_t count = p.px.size() / PX_WORDS;
+int ProveBatchImpl<C>::prove_mixed(bpp_verifier* v, const ProveArgs& a, void* d_workspace, size_t workspace_bytes,
+                                   hipStream_t st) {
+    const bool serialized = a.out_proofs != nullptr;
+    if (serialized) BPP_TRY(V::container_args_ok(v, a.version));
+    const size_t count = a.count;
+    MixedPlan p;
+    BPP_TRY(prove_plan(v->s, a.m_of, count, serialized ? (size_t)container_point_bytes<C>(a.version) : 0, true, p));
+    const ProveMixedLayout L = prove_mixed_layout(v, p, count, serialized);
+    if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
+    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     uint32_t* w_idx = reinterpret_cast<uint32_t*>(ws + L.idx);
-    // pageable source: the copies have read it when the call returns
+    // pageable source: the copies have read it when the call returns, so the plan need only outlive these two enqueues
     HIPCHK(hipMemcpyAsync(w_idx, p.px.data(), p.px.size() * 4, hipMemcpyHostToDevice, st));
     if (!p.sidx.empty())
         HIPCHK(hipMemcpyAsync(w_idx + count * PX_WORDS, p.sidx.data(), p.sidx.size() * 4, hipMemcpyHostToDevice, st));
+    // what every class is told: the block's packed inputs and, of the outputs, what the index leads to
+    ProveArgs cls = a;
+    cls.m_of = nullptr;
+    cls.out_V = nullptr;
+    cls.out_proofs = cls.out_commitments = nullptr;
+    if (serialized) {
+        cls.out_points = reinterpret_cast<uint64_t*>(ws + L.records);
+        cls.out_scalars = reinterpret_cast<uint64_t*>(ws + L.scalars);
+        cls.out_challenges = nullptr;
+    }
     for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
         if (!p.count[c]) continue;
-        const int rc = prove_batch_device(v, V::class_shape(v, c), d_values, d_gammas, p.count[c], d_out_points, d_out_scalars,
-                                          nullptr, fs, d_out_challenges, ws + L.run, workspace_bytes - L.run, st, blind_key,
-                                          index_base, d_blinding, w_idx + p.first[c] * PX_WORDS, amount64);
-        if (rc) return rc;
+        const PassShape ps = V::class_shape(v, c);
+        cls.count = p.count[c];
+        cls.in.ps = &ps;
+        cls.in.px = w_idx + p.first[c] * PX_WORDS;
+        BPP_TRY(prove_batch_device(v, cls, ws + L.run, workspace_bytes - L.run, st));
     }
-    return BPP_OK;
-}
-
-template <class C>
-int ProveBatchImpl<C>::prove_mixed(bpp_verifier* v, const uint64_t* d_values, const uint64_t* d_gammas, const uint32_t* m_of,
-                                   size_t count, bool fs, const uint8_t* blind_key, uint64_t index_base,
-                                   const uint64_t* d_blinding, uint64_t* d_out_points, uint64_t* d_out_scalars,
-                                   uint64_t* d_out_challenges, void* d_workspace, size_t workspace_bytes, hipStream_t st,
-                                   bool amount64) {
-    MixedPlan p;
-    int rc = prove_plan(v->s, m_of, count, 0, true, p);
-    if (rc) return rc;
-    const ProveMixedLayout L = prove_mixed_layout(v, p, count, false);
-    if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
-    return prove_mixed_classes(v, p, L, d_values, d_gammas, fs, blind_key, index_base, d_blinding, d_out_points, d_out_scalars,
-                               d_out_challenges, static_cast<uint8_t*>(d_workspace), workspace_bytes, st, amount64);
-}
-
-// The classes are proved into the class regions of the workspace (the layout the mixed decoder writes); the encoder is the
-// only kernel that touches the caller's byte buffers.
-template <class C>
-int ProveBatchImpl<C>::prove_serialized_mixed(bpp_verifier* v, const uint64_t* d_values, const uint64_t* d_gammas,
-                                              const uint32_t* m_of, size_t count, bool fs, const uint8_t* blind_key,
-                                              uint64_t index_base, const uint64_t* d_blinding, uint8_t* d_out_proofs,
-                                              uint8_t* d_out_commitments, void* d_workspace, size_t workspace_bytes,
-                                              hipStream_t st, uint32_t version, bool amount64) {
-    if (int rc = V::container_args_ok(v, version)) return rc;
-    MixedPlan p;
-    int rc = prove_plan(v->s, m_of, count, (size_t)container_point_bytes<C>(version), true, p);
-    if (rc) return rc;
-    const ProveMixedLayout L = prove_mixed_layout(v, p, count, true);
-    if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
-    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-    rc = prove_mixed_classes(v, p, L, d_values, d_gammas, fs, blind_key, index_base, d_blinding,
-                             reinterpret_cast<uint64_t*>(ws + L.records), reinterpret_cast<uint64_t*>(ws + L.scalars), nullptr, ws,
-                             workspace_bytes, st, amount64);
-    if (rc) return rc;
+    if (!serialized) return BPP_OK;
     hipLaunchKernelGGL(k_container_encode_mixed<C>, dim3((unsigned)(p.lanes / SER_WAVE)), dim3(SER_WAVE), 0, st, p.classes,
-                       reinterpret_cast<const uint32_t*>(ws + L.idx) + count * PX_WORDS,
-                       reinterpret_cast<const uint32_t*>(ws + L.records), reinterpret_cast<const uint32_t*>(ws + L.scalars),
-                       d_out_proofs, d_out_commitments, version);
+                       w_idx + count * PX_WORDS, reinterpret_cast<const uint32_t*>(ws + L.records),
+                       reinterpret_cast<const uint32_t*>(ws + L.scalars), a.out_proofs, a.out_commitments, a.version);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
 
+// Staged as staging.hpp says.  A mixed block: the plan names the proof the engine does not take; a block that only the size
+// getter refuses (a count beyond one launch, an engine the container does not hold) is rejected as a whole, and the key
+// needs the transcript, as in the device entries.  hipDeviceSynchronize stands ahead of the downloads for every form.
 template <class C>
-int ProveBatchImpl<C>::prove_batch(bpp_verifier* v, const uint64_t* values, const uint64_t* gammas, size_t count,
-                                   uint64_t* out_points, uint64_t* out_scalars, uint64_t* out_V, bool fs,
-                                   const uint8_t* blind_key, uint64_t index_base, bool amount64) {
-    // (blocking copies through DevBuf where asynchronous ones on the null stream and a synchronise stood: the same
-    // transfers from and to pageable host memory, in the same order around the device form's launches)
+int ProveBatchImpl<C>::prove_host(bpp_verifier* v, const ProveArgs& a) {
     const VerifyShape& s = v->s;
-    const uint32_t k = s.k, m = s.m;
-    const ProveLayout L = prove_layout(s, count);
-    const size_t pts_bytes = count * (size_t)(3 + 2 * k) * WW * 4, V_bytes = count * (size_t)m * WW * 4;
-    DevBuf d_val, d_gam, d_pts, d_V, d_sc, d_ws;
-    HIPCHK(d_val.upload(values, count * m * 8));
-    BPP_TRY(upload_scalars<C>(gammas, count * m, d_gam, nullptr));
-    HIPCHK(d_pts.alloc(pts_bytes));
-    HIPCHK(d_V.alloc(V_bytes));
-    HIPCHK(d_sc.alloc(count * 3 * 32));
-    HIPCHK(d_ws.alloc(L.total));
-    BPP_TRY(prove_batch_device(v, d_val.u64(), d_gam.u64(), count, d_pts.u64(), d_sc.u64(), d_V.u64(), fs, nullptr, d_ws.p,
-                               L.total, nullptr, blind_key, index_base, nullptr, amount64));
-    HIPCHK(d_pts.download(out_points, pts_bytes));
-    HIPCHK(d_sc.download(out_scalars, count * 96));
-    if (out_V) HIPCHK(d_V.download(out_V, V_bytes));
-    return BPP_OK;
-}
-
-// The plan names the proof the engine does not take; a block that only the size getter refuses (a count beyond one launch,
-// an engine the container does not hold) is rejected as a whole.  The key needs the transcript, as in the device forms.
-template <class C>
-int ProveBatchImpl<C>::prove_mixed_host(bpp_verifier* v, const uint64_t* values, const uint64_t* gammas, const uint32_t* m_of,
-                                        size_t count, int flags, const uint8_t* blind_key, uint64_t index_base,
-                                        uint64_t* out_points, uint64_t* out_scalars, uint64_t* out_challenges) {
+    const size_t count = a.count;
+    const bool serialized = a.out_proofs != nullptr;
+    if (a.blinding) return fail(BPP_E_ARG, "the host forms take blind_key, not blinding scalars");
+    // a block at fixed strides, then a mixed one: amounts, wire points, challenges, workspace bytes
+    size_t nval = count * s.m, points = count * (size_t)(3 + 2 * s.k), chals = count * (size_t)(3 + s.k), wsb = 0;
     MixedPlan p;
-    if (int rc = mixed_plan(v->s, m_of, count, false, p)) return rc;
-    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "mixed block rejected");
-    const bool fs = (flags & BPP_SER_TRANSCRIPT) != 0;
-    if (blind_key && !fs) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
-    const size_t wsb = prove_mixed_layout(v, p, count, false).total, nval = plan_values(p);
-    DevBuf dv, dg, dpts, dsc, dch, dws;
-    HIPCHK(dv.upload(values, nval * 8));
-    BPP_TRY(upload_scalars<C>(gammas, nval, dg, nullptr));
-    HIPCHK(dpts.alloc(p.points * WW * 4));
-    HIPCHK(dsc.alloc(count * 96));
-    if (out_challenges) HIPCHK(dch.alloc(p.chals * 32));
+    if (a.m_of) {
+        BPP_TRY(serialized ? mixed_plan_serialized(s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), false, p)
+                           : mixed_plan(s, a.m_of, count, false, p));
+        if (count > 0x7fffffffu / 64 || (serialized && !prove_mixed_workspace_bytes(v, a.m_of, count, true)))
+            return fail(BPP_E_ARG, serialized ? "serialized mixed block rejected" : "mixed block rejected");
+        nval = 0;
+        for (uint32_t c = 0; c < MIXED_CLASSES; c++) nval += p.count[c] << c;
+        points = p.points;
+        chals = p.chals;
+        wsb = prove_mixed_layout(v, p, count, serialized).total;
+    } else {
+        wsb = prove_layout(s, count).total;
+    }
+    if (a.blind_key && !a.fs) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
+    struct Out {
+        void* host;
+        size_t bytes;
+        DevBuf d;
+    } outs[] = {{a.out_points, points * WW * 4}, {a.out_scalars, count * 96},    {a.out_V, count * (size_t)s.m * WW * 4},
+                {a.out_challenges, chals * 32}, {a.out_proofs, p.proof_bytes}, {a.out_commitments, p.comm_bytes}};
+    DevBuf dv, dg, dws;
+    HIPCHK(dv.upload(a.values, nval * 8));
+    BPP_TRY(upload_scalars<C>(a.gammas, nval, dg, nullptr));
+    for (Out& o : outs)
+        if (o.host) HIPCHK(o.d.alloc(o.bytes));
     HIPCHK(dws.alloc(wsb));
-    BPP_TRY(prove_mixed(v, dv.u64(), dg.u64(), m_of, count, fs, blind_key, index_base, nullptr, dpts.u64(), dsc.u64(), dch.u64(),
-                        dws.p, wsb, nullptr, (flags & BPP_PROVE_AMOUNT64) != 0));
+    ProveArgs d = a;
+    d.values = dv.u64(); d.gammas = dg.u64();
+    d.out_points = outs[0].d.u64(); d.out_scalars = outs[1].d.u64(); d.out_V = outs[2].d.u64();
+    d.out_challenges = outs[3].d.u64(); d.out_proofs = outs[4].d.u8(); d.out_commitments = outs[5].d.u8();
+    BPP_TRY(prove_device(v, d, dws.p, wsb, nullptr));
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(dpts.download(out_points, p.points * WW * 4));
-    HIPCHK(dsc.download(out_scalars, count * 96));
-    if (out_challenges) HIPCHK(dch.download(out_challenges, p.chals * 32));
-    return BPP_OK;
-}
-
-template <class C>
-int ProveBatchImpl<C>::prove_serialized_mixed_host(bpp_verifier* v, const uint64_t* values, const uint64_t* gammas,
-                                                   const uint32_t* m_of, size_t count, int flags, const uint8_t* blind_key,
-                                                   uint64_t index_base, uint8_t* out_proofs, uint8_t* out_commitments) {
-    const uint32_t version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
-    MixedPlan p;
-    if (int rc = mixed_plan_serialized(v->s, m_of, count, (size_t)container_point_bytes<C>(version), false, p)) return rc;
-    if (count > 0x7fffffffu / 64 || !prove_ser_mixed_workspace_bytes(v, m_of, count))
-        return fail(BPP_E_ARG, "serialized mixed block rejected");
-    const bool fs = (flags & BPP_SER_TRANSCRIPT) != 0;
-    if (blind_key && !fs) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
-    const size_t wsb = prove_mixed_layout(v, p, count, true).total, nval = plan_values(p);
-    DevBuf dv, dg, dpr, dcm, dws;
-    HIPCHK(dv.upload(values, nval * 8));
-    BPP_TRY(upload_scalars<C>(gammas, nval, dg, nullptr));
-    HIPCHK(dpr.alloc(p.proof_bytes));
-    HIPCHK(dcm.alloc(p.comm_bytes));
-    HIPCHK(dws.alloc(wsb));
-    BPP_TRY(prove_serialized_mixed(v, dv.u64(), dg.u64(), m_of, count, fs, blind_key, index_base, nullptr, dpr.u8(), dcm.u8(),
-                                   dws.p, wsb, nullptr, version, (flags & BPP_PROVE_AMOUNT64) != 0));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(dpr.download(out_proofs, p.proof_bytes));
-    HIPCHK(dcm.download(out_commitments, p.comm_bytes));
+    for (Out& o : outs)
+        if (o.host) HIPCHK(o.d.download(o.host, o.bytes));
     return BPP_OK;
 }
 #endif  // BPP_IMPL_DEFINITIONS

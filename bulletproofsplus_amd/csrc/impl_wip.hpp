@@ -14,6 +14,22 @@ namespace bpp {
 
 constexpr uint32_t WIP_E_ROUND = 7, WIP_E_FINAL = 99;   // wip.rs:131 / :353, :211 / :369
 
+// What a seam prove call takes, in the C ABI's order; the device's pointers for prove_device, the host's for prove_host
+// (blind_key, 32 bytes: the host's always).  a, b: count x len scalars ; y, gamma: count scalars ; transcript: count x 32
+// bytes of state, read when fs ; blinding: count x (5 + 2k) canonical scalars, or blind_key with proof i's index
+// index_base + i, or the literals.  points: count records of 3 + 2k + nv wire points, point 0 and the last nv of each the
+// caller's, the rest written ; out_scalars: count x 3 ; out_challenges (may be null): count x (1 + k), [e, e_1..e_k].
+struct WipProveArgs {
+    const uint64_t *a = nullptr, *b = nullptr, *y = nullptr, *gamma = nullptr;
+    size_t count = 0, nv = 0;
+    bool fs = false;
+    const void* transcript = nullptr;
+    const uint8_t* blind_key = nullptr;
+    uint64_t index_base = 0;
+    const uint64_t* blinding = nullptr;
+    uint64_t *points = nullptr, *out_scalars = nullptr, *out_challenges = nullptr;
+};
+
 template <class C>
 struct WipImpl {
     using V = VerifyImpl<C>;
@@ -49,15 +65,8 @@ struct WipImpl {
         w.total = o.total;
         return w;
     }
-    static int prove_device(bpp_verifier* v, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_y,
-                            const uint64_t* d_gamma, size_t count, size_t nv, bool fs, const void* d_transcript,
-                            const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_blinding, uint64_t* d_out_points,
-                            uint64_t* d_out_scalars, uint64_t* d_out_challenges, void* d_workspace, size_t workspace_bytes,
-                            hipStream_t st);
-    static int prove_host(bpp_verifier* v, const uint64_t* a, const uint64_t* b, const uint64_t* y, const uint64_t* gamma,
-                          size_t count, size_t nv, bool fs, const void* transcript, const uint8_t* blind_key,
-                          uint64_t index_base, const uint64_t* blinding, uint64_t* points, uint64_t* out_scalars,
-                          uint64_t* out_challenges);
+    static int prove_device(bpp_verifier* v, const WipProveArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st);
+    static int prove_host(bpp_verifier* v, const WipProveArgs& a);
 
     // ---- verifier: workspace = challenges derived from the transcript | the pass's workspace (ws_layout) ---------------
     struct VerifyWs {
@@ -83,47 +92,41 @@ struct WipImpl {
 
 #ifdef BPP_IMPL_DEFINITIONS
 template <class C>
-int WipImpl<C>::prove_device(bpp_verifier* v, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_y,
-                             const uint64_t* d_gamma, size_t count, size_t nv, bool fs, const void* d_transcript,
-                             const uint8_t* blind_key, uint64_t index_base, const uint64_t* d_blinding,
-                             uint64_t* d_out_points, uint64_t* d_out_scalars, uint64_t* d_out_challenges, void* d_workspace,
-                             size_t workspace_bytes, hipStream_t st) {
+int WipImpl<C>::prove_device(bpp_verifier* v, const WipProveArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
     const VerifyShape s = prove_shape(v);
     const uint32_t k = s.k;
     const uint32_t nvp = pb_num_vps(k, s.m);            // 2k + 3
-    const uint32_t rec_stride = 3 + 2 * k + (uint32_t)nv;
-    if ((count * rec_stride) >> 32) return fail(BPP_E_ARG, "count too large");
-    const ProveWs Lw = prove_ws(v, count);
+    const uint32_t rec_stride = 3 + 2 * k + (uint32_t)a.nv;
+    if ((a.count * rec_stride) >> 32) return fail(BPP_E_ARG, "count too large");
+    const ProveWs Lw = prove_ws(v, a.count);
     if (workspace_bytes < Lw.total) return fail(BPP_E_ARG, "workspace too small");
     const typename PB::ProveLayout& L = Lw.run;
     const ProverConsts pc = PB::literals();   // alpha and amount64 are the range statement's: not read, no commitment formed
     const WipLiterals lit{WIP_E_ROUND, WIP_E_FINAL};
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
+    auto U32 = [](const uint64_t* q) { return reinterpret_cast<const uint32_t*>(q); };
     uint32_t* px = W(Lw.px);
-    for (size_t base = 0; base < count; base += L.chunk) {
-        const size_t cnt = std::min(L.chunk, count - base);
+    for (size_t base = 0; base < a.count; base += L.chunk) {
+        const size_t cnt = std::min(L.chunk, a.count - base);
         hipLaunchKernelGGL(k_wip_px, dim3(cdiv(cnt, 256)), dim3(256), 0, st, px, base, rec_stride, cnt);
-        const uint32_t* slice =
-            d_blinding ? reinterpret_cast<const uint32_t*>(d_blinding) + base * (size_t)pb_blind_elems(k) * 8 : nullptr;
-        const uint32_t* blind = PB::chunk_blinding(slice, blind_key, index_base, k, cnt, px, W(L.blind), st);
-        hipLaunchKernelGGL(k_wip_init<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, lit, fs ? 1u : 0u,
-                           reinterpret_cast<const uint32_t*>(d_a) + base * (size_t)s.mn * 8,
-                           reinterpret_cast<const uint32_t*>(d_b) + base * (size_t)s.mn * 8,
-                           reinterpret_cast<const uint32_t*>(d_y) + base * 8,
-                           reinterpret_cast<const uint32_t*>(d_gamma) + base * 8, W(L.a), W(L.b), W(L.cG), W(L.cH), W(L.pwy),
-                           W(L.con), W(L.vps));
-        if (fs)
+        // records and triples go through px, whose PX_CALLER carries base + p; the challenges are hashed into the workspace's
+        // 3 + k blocks, the caller's are [e, e_1..e_k]
+        typename PB::Chunk c{s, pc, L, ws, cnt, a.blinding ? U32(a.blinding) + base * (size_t)pb_blind_elems(k) * 8 : nullptr,
+                             px, reinterpret_cast<uint32_t*>(a.points), nullptr, reinterpret_cast<uint32_t*>(a.out_scalars),
+                             W(L.ch), st, v->table.u32()};
+        PB::chunk_blinding(c, a.blind_key, a.index_base);
+        hipLaunchKernelGGL(k_wip_init<C>, dim3((unsigned)cnt), dim3(256), 0, st, s, lit, a.fs ? 1u : 0u,
+                           U32(a.a) + base * (size_t)s.mn * 8, U32(a.b) + base * (size_t)s.mn * 8, U32(a.y) + base * 8,
+                           U32(a.gamma) + base * 8, W(L.a), W(L.b), W(L.cG), W(L.cH), W(L.pwy), W(L.con), W(L.vps));
+        if (a.fs)
             hipLaunchKernelGGL(k_wip_fs_start<C>, dim3(cdiv(cnt, 64)), dim3(64), 0, st, s,
-                               static_cast<const uint8_t*>(d_transcript) + base * 32, W(L.trst), cnt);
-        // the challenges are hashed into the workspace's 3 + k blocks; the caller's are [e, e_1..e_k]
-        PB::argument(typename PB::Chunk{s, pc, L, ws, cnt, blind, px, reinterpret_cast<uint32_t*>(d_out_points), nullptr,
-                                        reinterpret_cast<uint32_t*>(d_out_scalars), W(L.ch), st, v->table.u32()},
-                     fs, VpSel{nvp, 1u, 2 * k + 2, 1u});   // literal mode: L_t, R_t, wip.A, wip.B, the virtual proofs that exist
-        if (d_out_challenges)
+                               static_cast<const uint8_t*>(a.transcript) + base * 32, W(L.trst), cnt);
+        PB::argument(c, a.fs, VpSel{nvp, 1u, 2 * k + 2, 1u});   // literal mode: L_t, R_t, wip.A, wip.B, the virtual proofs that exist
+        if (a.out_challenges)
             hipLaunchKernelGGL(k_wip_challenges_out<C>, dim3((unsigned)cnt), dim3(64), 0, st, k, lit,
-                               fs ? W(L.ch) : (const uint32_t*)nullptr,
-                               reinterpret_cast<uint32_t*>(d_out_challenges) + base * (size_t)(1 + k) * 8);
+                               a.fs ? W(L.ch) : (const uint32_t*)nullptr,
+                               reinterpret_cast<uint32_t*>(a.out_challenges) + base * (size_t)(1 + k) * 8);
     }
     HIPCHK(hipGetLastError());
     return BPP_OK;
@@ -166,30 +169,29 @@ int WipImpl<C>::verify_device(bpp_verifier* v, const uint64_t* d_points, const u
 // launches on the null stream are ordered between the copies as before.  A failed entry returns at once: the buffers'
 // hipFree waits for whatever was enqueued.
 template <class C>
-int WipImpl<C>::prove_host(bpp_verifier* v, const uint64_t* a, const uint64_t* b, const uint64_t* y, const uint64_t* gamma,
-                           size_t count, size_t nv, bool fs, const void* transcript, const uint8_t* blind_key,
-                           uint64_t index_base, const uint64_t* blinding, uint64_t* points, uint64_t* out_scalars,
-                           uint64_t* out_challenges) {
+int WipImpl<C>::prove_host(bpp_verifier* v, const WipProveArgs& a) {
     const VerifyShape s = prove_shape(v);
     const uint32_t k = s.k;
-    const size_t pts_bytes = count * (size_t)(3 + 2 * k + nv) * WW * 4, ch_bytes = count * (size_t)(1 + k) * 32;
+    const size_t count = a.count;
+    const size_t pts_bytes = count * (size_t)(3 + 2 * k + a.nv) * WW * 4, ch_bytes = count * (size_t)(1 + k) * 32;
     DevBuf da, db, dy, dg, dtr, dbl, dpts, dsc, dch, dws;
-    HIPCHK(da.upload(a, count * (size_t)s.mn * 32));
-    HIPCHK(db.upload(b, count * (size_t)s.mn * 32));
-    HIPCHK(dy.upload(y, count * 32));
-    HIPCHK(dg.upload(gamma, count * 32));
-    HIPCHK(dtr.upload(transcript, count * 32));
-    HIPCHK(dbl.upload(blinding, count * (size_t)pb_blind_elems(k) * 32));
-    HIPCHK(dpts.upload(points, pts_bytes));   // point 0 and the last nv of a record are the caller's
+    HIPCHK(da.upload(a.a, count * (size_t)s.mn * 32));
+    HIPCHK(db.upload(a.b, count * (size_t)s.mn * 32));
+    HIPCHK(dy.upload(a.y, count * 32));
+    HIPCHK(dg.upload(a.gamma, count * 32));
+    HIPCHK(dtr.upload(a.fs ? a.transcript : nullptr, count * 32));
+    HIPCHK(dbl.upload(a.blinding, count * (size_t)pb_blind_elems(k) * 32));
+    HIPCHK(dpts.upload(a.points, pts_bytes));   // point 0 and the last nv of a record are the caller's
     HIPCHK(dsc.alloc(count * 96));
-    if (out_challenges) HIPCHK(dch.alloc(ch_bytes));
+    if (a.out_challenges) HIPCHK(dch.alloc(ch_bytes));
     const size_t wsb = prove_ws(v, count).total;
     HIPCHK(dws.alloc(wsb));
-    BPP_TRY(prove_device(v, da.u64(), db.u64(), dy.u64(), dg.u64(), count, nv, fs, dtr.p, blind_key, index_base, dbl.u64(),
-                         dpts.u64(), dsc.u64(), dch.u64(), dws.p, wsb, nullptr));
-    HIPCHK(dpts.download(points, pts_bytes));
-    HIPCHK(dsc.download(out_scalars, count * 96));
-    if (out_challenges) HIPCHK(dch.download(out_challenges, ch_bytes));
+    const WipProveArgs d{da.u64(), db.u64(),    dy.u64(),     dg.u64(),  count,      a.nv,      a.fs,   // the record's order
+                         dtr.p,    a.blind_key, a.index_base, dbl.u64(), dpts.u64(), dsc.u64(), dch.u64()};
+    BPP_TRY(prove_device(v, d, dws.p, wsb, nullptr));
+    HIPCHK(dpts.download(a.points, pts_bytes));
+    HIPCHK(dsc.download(a.out_scalars, count * 96));
+    if (a.out_challenges) HIPCHK(dch.download(a.out_challenges, ch_bytes));
     return BPP_OK;
 }
 

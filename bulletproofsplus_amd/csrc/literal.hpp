@@ -144,9 +144,12 @@ int literal_prove(bpp_ctx* ctx, const uint64_t* gh, const uint64_t* G, const uin
         // ... first with the reference's own commitments, new(v as i32) g + gamma h (range/prover.rs:37), then with the
         // untruncated ones a caller with an amount of 2^31 or more has to bring (BPP_PROVE_AMOUNT64): in literal mode the
         // proof is a function of (v, gamma, V), so whichever form matches the caller's V is the fold-based path's output
+        ProveArgs a;   // literal mode, no blinding
+        a.values = v; a.gammas = gamma; a.count = 1;
+        a.out_points = pts.data(); a.out_scalars = sc.data(); a.out_V = myV.data();
         for (int amount64 = 0; amount64 < 2; amount64++) {
-            const int rc = ProveBatchImpl<C>::prove_batch(hit->v.get(), v, gamma, 1, pts.data(), sc.data(), myV.data(), false, nullptr,
-                                                          0, amount64 != 0);
+            a.amount64 = amount64 != 0;
+            const int rc = ProveBatchImpl<C>::prove_host(hit->v.get(), a);
             if (rc == BPP_OK && std::memcmp(myV.data(), V, m * pw * 8) == 0) {
                 std::memcpy(out_points, pts.data(), pts.size() * 8);
                 std::memcpy(out_scalars, sc.data(), 96);

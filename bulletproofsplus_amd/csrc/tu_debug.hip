@@ -573,9 +573,12 @@ extern "C" int bpp_debug_prover_scalars(bpp_verifier* v, uint32_t m_view, uint32
             HIPCHK(dV.alloc(V_bytes));
             HIPCHK(dsc.alloc(count * 96));
             HIPCHK(dws.alloc(L.total));
-            BPP_TRY(PB::prove_batch_device(v, ps, dv.u64(), dg.u64(), count, dpts.u64(), dsc.u64(), dV.u64(), false, nullptr, dws.p,
-                                           L.total, nullptr, nullptr, 0, dbl.u64(), nullptr, (flags & BPP_PROVE_AMOUNT64) != 0,
-                                           dch.u64()));
+            ProveArgs a;   // literal mode at fixed strides, on the view's shape and the caller's challenges
+            a.values = dv.u64(); a.gammas = dg.u64(); a.count = count;
+            a.amount64 = (flags & BPP_PROVE_AMOUNT64) != 0; a.blinding = dbl.u64();
+            a.out_points = dpts.u64(); a.out_scalars = dsc.u64(); a.out_V = dV.u64();
+            a.in.ps = &ps; a.in.challenges = dch.u64();
+            BPP_TRY(PB::prove_batch_device(v, a, dws.p, L.total, nullptr));
             HIPCHK(hipDeviceSynchronize());
             HIPCHK(hipMemcpy(out_vps, dws.u8() + L.vps, vps_bytes, hipMemcpyDeviceToHost));
             HIPCHK(dsc.download(out_scalars3, count * 96));
