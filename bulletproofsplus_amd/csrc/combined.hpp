@@ -36,6 +36,7 @@ constexpr int partial_words() {
 
 // weights[p]: Montgomery form, packed 8 words.  raw != null: w_p = raw[p] (16 bytes, little-endian);
 // else w_p = SHA-256(key[32] || "bppw" || (index_base + p) as u64 LE)[0..16) read little-endian.  0 -> 1.
+// (index_base + p wrapping past 2^64 is left unspecified and untested; tests/weight_cases.py restates the rest.)
 struct WeightKey {
     uint32_t w[8];   // the 32 key bytes as little-endian words
 };

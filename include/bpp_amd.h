@@ -295,7 +295,8 @@ int bpp_range_prove_batch_device(bpp_verifier *engine, const uint64_t *d_v, cons
  *                whole batch; or
  *   weight_key : 32 secret bytes (host pointer) from the OS CSPRNG, fresh per call or per verifier; the device
  *                expands w_p = SHA-256(key || "bppw" || (index_base + p) as u64)[0..16).  index_base is the GLOBAL index
- *                of this call's first proof, so ranks that share a key never share a weight.
+ *                of this call's first proof, so ranks that share a key never share a weight.  The 16 bytes are read
+ *                little-endian and 0 stands for 1 (d_weights likewise); index_base + p past 2^64 is left unspecified.
  * The caller falls back to bpp_verifier_run for the exact per-proof verdicts of the reference when the check fails.
  * It assumes proof points of the prime-order subgroup (bpp_proofs_decode checks that for serialized proofs).
  *   d_out_partial: bpp_verifier_partial_bytes() bytes -- this call's weighted sum (opaque jacobian image) followed by

@@ -43,10 +43,10 @@ def run_verifier_device(torch, bv, records, scalars, want_scalars=True, want_res
     return ok, os_, or_
 
 
-def run_combined_device(torch, bv, records, scalars, seed=12345, index_base=0, weights=None):
-    """Combined batch check on device -> (ok_flag, partial bytes as numpy uint8).  The 32-byte weight key is derived
-    from `seed` (tests want repeatable weights; production callers pass os.urandom(32)); weights: (count, 2) uint64
-    to supply the 128-bit weights directly."""
+def run_combined_device(torch, bv, records, scalars, seed=12345, index_base=0, weights=None, key=None):
+    """Combined batch check on device -> (ok_flag, partial bytes as numpy uint8).  The 32-byte weight key is `key`, or
+    derived from `seed` (tests want repeatable weights; production callers pass os.urandom(32)); weights: (count, 2)
+    uint64 to supply the 128-bit weights directly."""
     import hashlib
     dev = torch.device("cuda:0")
     count = records.shape[0]
@@ -56,7 +56,8 @@ def run_combined_device(torch, bv, records, scalars, seed=12345, index_base=0, w
     d_part = torch.zeros(bv.partial_bytes(), dtype=torch.uint8, device=dev)
     wsb = bv.combined_workspace_bytes(count)
     d_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    key = hashlib.sha256(b"test weight key %d" % seed).digest()
+    if key is None:
+        key = hashlib.sha256(b"test weight key %d" % seed).digest()
     d_w = None
     if weights is not None:
         d_w = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.uint64).view(np.int64)).to(dev)
@@ -67,9 +68,11 @@ def run_combined_device(torch, bv, records, scalars, seed=12345, index_base=0, w
     return int(d_ok.item()), d_part.cpu().numpy()
 
 
-def run_grouped_device(torch, bv, records, scalars, group, seed=12345, index_base=0, challenges=None):
-    """Grouped check on device -> (verdicts (count,) u32, groups failed, proofs re-verified exactly).  Weight key from
-    `seed` (repeatable; production callers pass os.urandom(32))."""
+def run_grouped_device(torch, bv, records, scalars, group, seed=12345, index_base=0, challenges=None, key=None, weights=None,
+                       halves=False):
+    """Grouped check on device -> (verdicts (count,) u32, groups failed, proofs re-verified exactly).  Weight key: `key`, or
+    from `seed` (repeatable; production callers pass os.urandom(32)); weights: (count, 2) uint64 to supply the 128-bit
+    weights directly.  halves: through bpp_verifier_grouped_begin / _finish instead of the one call."""
     import hashlib
     dev = torch.device("cuda:0")
     count = records.shape[0]
@@ -78,14 +81,23 @@ def run_grouped_device(torch, bv, records, scalars, group, seed=12345, index_bas
     d_ok = torch.full((max(count, 1),), 7, dtype=torch.int32, device=dev)
     wsb = bv.grouped_workspace_bytes(count, group)
     d_ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=dev)
-    key = hashlib.sha256(b"test weight key %d" % seed).digest()
+    if key is None:
+        key = hashlib.sha256(b"test weight key %d" % seed).digest()
     d_ch = None
     if challenges is not None:
         d_ch = torch.from_numpy(np.ascontiguousarray(challenges).view(np.int64)).to(dev)
-    failed, redone = bv.run_grouped_device(d_pts.data_ptr(), d_sc.data_ptr(), count, key, index_base, d_ok.data_ptr(),
-                                           d_ws.data_ptr(), wsb, group=group,
-                                           stream=torch.cuda.current_stream().cuda_stream,
-                                           d_challenges=d_ch.data_ptr() if d_ch is not None else 0)
+    d_w = None
+    if weights is not None:
+        d_w = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.uint64).view(np.int64)).to(dev)
+    kw = dict(group=group, stream=torch.cuda.current_stream().cuda_stream, d_challenges=d_ch.data_ptr() if d_ch is not None else 0)
+    if halves:
+        bv.grouped_begin_device(d_pts.data_ptr(), d_sc.data_ptr(), count, key, index_base, d_ok.data_ptr(), d_ws.data_ptr(), wsb,
+                                d_weights=d_w.data_ptr() if d_w is not None else 0, **kw)
+        failed, redone = bv.grouped_finish_device(d_pts.data_ptr(), d_sc.data_ptr(), count, d_ok.data_ptr(), d_ws.data_ptr(), wsb,
+                                                  **kw)
+    else:
+        failed, redone = bv.run_grouped_device(d_pts.data_ptr(), d_sc.data_ptr(), count, key, index_base, d_ok.data_ptr(),
+                                               d_ws.data_ptr(), wsb, d_weights=d_w.data_ptr() if d_w is not None else 0, **kw)
     torch.cuda.synchronize()
     return d_ok.cpu().numpy().astype(np.uint32)[:count], failed, redone
 
