@@ -276,6 +276,8 @@ def lib():
         L.bpp_debug_scan_keys.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, sz, sz, vp, sz, u64, vp, vp, vp, vp, vp]
         # ... and the batched prover's whole kernels on chosen witnesses, blinding and challenges (host buffers, synchronous)
         L.bpp_debug_prover_scalars.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp, sz, vp, vp, vp]
+        # ... and the verifier's window tables read back entry by entry (host buffers, synchronous)
+        L.bpp_debug_verifier_table.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
         _lib = L
     return _lib
 

@@ -38,6 +38,9 @@ struct bpp_verifier {
     std::vector<bpp::PassShape> views;
     bpp::DevBuf view_challenges;
     size_t table_bytes = 0;
+    // how create filled the tables: k_tbl_fill launches, and the runs of TBL_RUN entries each generator has (reported by
+    // tu_debug.hip bpp_debug_verifier_table; nothing in a pass reads them)
+    uint32_t table_slabs = 0, table_runs_per_generator = 0;
     // bpp_verifier_set_subgroup_check: wire points outside the prime-order subgroup count as invalid points (off by
     // default: the in-memory API takes points that are in the group by construction, as the reference's mcl values are)
     bool check_subgroup = false;
@@ -602,6 +605,12 @@ struct VerifyImpl {
 
     // d_partials: n partials as bpp_verifier_run_combined wrote them (jacobian + validity word each)
     static int sum_partials(const uint32_t* d_partials, size_t n, uint32_t* d_ok, hipStream_t st);
+
+    // Entries first .. first + count - 1 of table generator `generator` (table numbering; the caller has checked both
+    // against NF and per_f, and count > 0), to host buffers: out_raw [count][2N] the device words as they are stored (one
+    // copy, or null), out_wire [count][PW] the same slice through k_points_to_wire (or null).  Synchronous.
+    static int table_slice(const bpp_verifier* v, uint32_t generator, uint32_t first, uint32_t count, uint32_t* out_raw,
+                           uint64_t* out_wire);
 };
 
 // ---- definitions: compiled only by the translation unit that instantiates the struct (tu_*.hip defines
@@ -652,7 +661,9 @@ int VerifyImpl<C>::create(const bpp_ctx& ctx, const uint64_t* gh, const uint64_t
         const size_t total = (size_t)(f1 - f0) * runs_f;
         hipLaunchKernelGGL(k_tbl_fill<C>, dim3(cdiv(total, 64)), dim3(64), 0, nullptr, s, v->table.u32(),
                            tbl_scratch.u32(), f0, f1);
+        v->table_slabs++;
     }
+    v->table_runs_per_generator = runs_f;
     tr_initial_state<C>(s.n, s.m, reinterpret_cast<const uint32_t*>(fixed.data()), s.NF, v->tr0.st);
     std::vector<uint32_t> ch;
     default_challenges(s, ch);
@@ -688,6 +699,21 @@ int VerifyImpl<C>::create(const bpp_ctx& ctx, const uint64_t* gh, const uint64_t
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return fail(BPP_E_HIP, "table build failed: ", hipGetErrorString(e));
     *out = v.release();
+    return BPP_OK;
+}
+
+template <class C>
+int VerifyImpl<C>::table_slice(const bpp_verifier* v, uint32_t generator, uint32_t first, uint32_t count, uint32_t* out_raw,
+                               uint64_t* out_wire) {
+    const uint32_t* src = v->table.u32() + ((size_t)generator * v->s.per_f + first) * 2 * N;
+    if (out_raw) HIPCHK(hipMemcpy(out_raw, src, (size_t)count * 2 * N * 4, hipMemcpyDeviceToHost));
+    if (out_wire) {
+        DevBuf dw;
+        HIPCHK(dw.alloc((size_t)count * WW * 4));
+        hipLaunchKernelGGL(k_points_to_wire<C>, dim3(cdiv(count, 64)), dim3(64), 0, nullptr, src, dw.u32(), (size_t)count);
+        HIPCHK(hipGetLastError());
+        HIPCHK(dw.download(out_wire, (size_t)count * WW * 4));
+    }
     return BPP_OK;
 }
 

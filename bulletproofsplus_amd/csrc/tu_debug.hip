@@ -9,7 +9,9 @@
 // bpp_debug_scan_keys is that hook's counterpart for the many-key scan (recover_keys.hpp): a class of chosen proofs through
 // k_recover_coeffs and k_scan_keys, host pointers, no kernel of its own.  bpp_debug_prover_scalars is the batched prover's:
 // k_pb_init, k_pb_round and k_pb_final whole, on witnesses, blinding and challenges the test chooses, through
-// ProveBatchImpl::prove_batch_device -- host pointers, no kernel of its own.
+// ProveBatchImpl::prove_batch_device -- host pointers, no kernel of its own.  bpp_debug_verifier_table reads the verifier's
+// window tables back entry by entry, raw and through k_points_to_wire (VerifyImpl::table_slice) -- host pointers, no kernel
+// of its own.
 #include "host_util.hpp"
 
 #include "field_raw_ops.hpp"
@@ -594,6 +596,37 @@ extern "C" int bpp_debug_prover_scalars(bpp_verifier* v, uint32_t m_view, uint32
                 }
             }
             return BPP_OK;
+        });
+    });
+}
+
+// The verifier's window tables read back: entries first .. first + count - 1 of one generator, T[j][d] = d 2^(off_j) F at
+// entry went[j] + d - 1 (fixed_glv.hpp).  Host pointers, synchronous, no kernel of its own.
+//   generator: TABLE numbering, [0, NF) of the verifier's own shape (g, h, G_0.., H_0..); first + count <= per_f
+//   out_raw [count][2N] (may be null): the device words of the entries exactly as stored, one device-to-host copy
+//   out_wire [count][PW] (may be null): the same entries through k_points_to_wire
+//   out_layout (may be null): [W, top, per_f, glv, hgap, slabs, runs_per_generator], then wc[0..W), then went[0..W), as the
+//     verifier's shape carries them; slabs = the k_tbl_fill launches create made, runs_per_generator = the runs of TBL_RUN
+//     entries it gave each generator.  Written whatever count is.
+extern "C" int bpp_debug_verifier_table(bpp_verifier* v, uint32_t generator, uint32_t first, uint32_t count, uint32_t* out_raw,
+                                        uint64_t* out_wire, uint32_t* out_layout) {
+    if (!v) return fail(BPP_E_ARG, "null argument");
+    const VerifyShape& s = v->s;
+    if (generator >= s.NF) return fail(BPP_E_ARG, "generator beyond the table");
+    if (first > s.per_f || count > s.per_f - first) return fail(BPP_E_ARG, "entries beyond the generator's table");
+    return guarded([&]() -> int {
+        if (out_layout) {
+            const uint32_t head[7] = {s.W, s.top, s.per_f, s.glv, s.hgap, v->table_slabs, v->table_runs_per_generator};
+            std::memcpy(out_layout, head, sizeof head);
+            for (uint32_t j = 0; j < s.W; j++) {
+                out_layout[7 + j] = s.wc[j];
+                out_layout[7 + s.W + j] = s.went[j];
+            }
+        }
+        if (count == 0 || (!out_raw && !out_wire)) return BPP_OK;
+        HIPCHK(hipSetDevice(v->ctx.device));
+        return dispatch(v->ctx.curve, [&](auto cv) -> int {
+            return VerifyImpl<decltype(cv)>::table_slice(v, generator, first, count, out_raw, out_wire);
         });
     });
 }
