@@ -1,6 +1,8 @@
 // capi.hip -- the extern "C" boundary of libbpp_amd.so (declared in include/bpp_amd.h).  Thin: argument
 // checks, the entry shim, curve dispatch, then the per-curve implementations (impl_*.hpp, compiled in tu_*.hip) and the
-// literal single-call API (literal.hpp).  No buffer is staged here: the host forms live in the *Impl<C> structs as *_host.
+// literal single-call API (literal.hpp).  The verifier's and the prover's entries fill an argument record and pass ONE check
+// each (verify_args.hpp verify_args; prove_args below), which hold what tells their entries apart as data.  No buffer is
+// staged here: the host forms live in the *Impl<C> structs as *_host.
 // No CPU fallback: every entry point launches HIP kernels on the context's device.
 #include "codec.hpp"
 #include "commit.hpp"
@@ -60,6 +62,11 @@ template <class F>
 size_t size_for(const bpp_verifier* v, F&& f) {
     return size_for(v ? &v->ctx : nullptr, f);
 }
+// The verifier entries: each fills its record in the C ABI's order and passes verify_args (verify_args.hpp), which is told
+// this much of the handle and answers an empty batch itself.
+VerifierFacts facts(const bpp_verifier* v) { return v ? VerifierFacts{true, v->ctx.curve, v->s.n, v->s.m} : VerifierFacts{}; }
+int answered(int rc) { return rc == VERIFY_ANSWERED ? BPP_OK : rc; }
+hipStream_t hip(void* stream) { return static_cast<hipStream_t>(stream); }
 // mean milliseconds per stage over the first `passes` passes of an event ring: pass p's stage t runs from
 // ev[p * per_pass + t * step] to the event after it
 int stage_means(const hipEvent_t* ev, size_t passes, size_t per_pass, int stages, int step, float* out_ms) {
@@ -259,14 +266,11 @@ extern "C" int bpp_verifier_run(bpp_verifier* v, const uint64_t* d_points, const
                                 const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace,
                                 size_t workspace_bytes, uint64_t* d_out_scalars, uint64_t* d_out_result,
                                 void* stream) {
-    if (!v || !d_points || !d_scalars || !d_ok || !d_workspace) return fail(BPP_E_ARG, "null argument");
-    if (count == 0) return BPP_OK;
-    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
-    return on_ctx(v->ctx, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::run(v, d_points, d_scalars, count, d_challenges, d_ok, d_workspace,
-                                             workspace_bytes, d_out_scalars, d_out_result,
-                                             static_cast<hipStream_t>(stream));
-    });
+    VerifyArgs a;
+    a.points = d_points; a.scalars = d_scalars; a.count = count; a.challenges = d_challenges;
+    a.ok = d_ok; a.out_scalars = d_out_scalars; a.out_result = d_out_result;
+    if (int rc = verify_args(VERIFY_RUN, facts(v), 0, a, d_workspace)) return answered(rc);
+    return on_ctx(v->ctx, [&](auto cv) -> int { return VerifyImpl<decltype(cv)>::run(v, a, d_workspace, workspace_bytes, hip(stream)); });
 }
 
 // ---- one pass as a HIP graph: captured once, replayed over the same buffers -----------------------------------
@@ -283,17 +287,15 @@ extern "C" void bpp_graph_destroy(bpp_graph* g) { delete g; }
 extern "C" int bpp_verifier_graph_capture(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
                                           const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace,
                                           size_t workspace_bytes, bpp_graph** out) {
-    if (!v || !d_points || !d_scalars || !d_ok || !d_workspace || !out) return fail(BPP_E_ARG, "null argument");
-    if (count == 0 || count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count out of range");
+    VerifyArgs a;
+    a.points = d_points; a.scalars = d_scalars; a.count = count; a.challenges = d_challenges; a.ok = d_ok;
+    if (int rc = verify_args(VERIFY_GRAPH, facts(v), 0, a, out ? d_workspace : nullptr)) return rc;
     if (v->profiling) return fail(BPP_E_ARG, "switch the stage profiling off before capturing a pass");
     return on_ctx(v->ctx, [&](auto cv) -> int {
         hipStream_t cs = nullptr;
         HIPCHK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
         const std::unique_ptr<std::remove_pointer_t<hipStream_t>, decltype(&hipStreamDestroy)> own_cs(cs, hipStreamDestroy);
-        auto pass = [&] {
-            return VerifyImpl<decltype(cv)>::run(v, d_points, d_scalars, count, d_challenges, d_ok, d_workspace, workspace_bytes,
-                                                 nullptr, nullptr, cs);
-        };
+        auto pass = [&] { return VerifyImpl<decltype(cv)>::run(v, a, d_workspace, workspace_bytes, cs); };
         // one eager pass first: it checks the arguments and creates what a pass creates lazily (the side stream and its
         // events of a lone batch), which must not happen inside a capture
         int rc = pass();
@@ -519,55 +521,50 @@ extern "C" int bpp_verifier_run_combined(bpp_verifier* v, const uint64_t* d_poin
                                          size_t count, const uint64_t* d_challenges, const uint8_t* weight_key,
                                          uint64_t index_base, const uint64_t* d_weights, void* d_out_partial,
                                          uint32_t* d_ok, void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!v || !d_points || !d_scalars || !d_out_partial || !d_ok || !d_workspace) return fail(BPP_E_ARG, "null argument");
-    if (!weight_key && !d_weights) return fail(BPP_E_ARG, "the combined check needs a weight key or a weight buffer");
-    if (count == 0) return fail(BPP_E_ARG, "empty batch");
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::run_combined(v, d_points, d_scalars, count, d_challenges, weight_key, index_base,
-                                                      d_weights, static_cast<uint32_t*>(d_out_partial), d_ok, d_workspace,
-                                                      workspace_bytes, static_cast<hipStream_t>(stream));
-    });
+    VerifyArgs a;
+    a.points = d_points; a.scalars = d_scalars; a.count = count; a.challenges = d_challenges;
+    a.weight_key = weight_key; a.index_base = index_base; a.weights = d_weights;
+    a.ok = d_ok; a.out_partial = static_cast<uint32_t*>(d_out_partial);
+    if (int rc = verify_args(VERIFY_COMBINED, facts(v), 0, a, d_workspace)) return rc;
+    return on_ctx(v->ctx, [&](auto cv) -> int { return VerifyImpl<decltype(cv)>::run_combined(v, a, d_workspace, workspace_bytes, hip(stream)); });
 }
 // ---- grouped check: per-proof verdicts, one weighted check per group, exact pass over the failing groups ------
 extern "C" size_t bpp_verifier_grouped_workspace_bytes(const bpp_verifier* v, size_t count, uint32_t group) {
-    if (group < 2 || (group & (group - 1))) return 0;
+    if (!group_ok(group)) return 0;
     return size_for(v, [&](auto cv) { return VerifyImpl<decltype(cv)>::group_layout(v->s, count, group).total; });
 }
 extern "C" int bpp_verifier_run_grouped(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
                                         const uint64_t* d_challenges, const uint8_t* weight_key, uint64_t index_base,
                                         const uint64_t* d_weights, uint32_t group, uint32_t* d_out_verdicts,
                                         uint64_t* stats, void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!v || !d_out_verdicts || !d_workspace || (count && (!d_points || !d_scalars)))
-        return fail(BPP_E_ARG, "null argument");
-    if (!weight_key && !d_weights) return fail(BPP_E_ARG, "the grouped check needs a weight key or a weight buffer");
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::run_grouped(v, d_points, d_scalars, count, d_challenges, weight_key, index_base,
-                                                     d_weights, group, d_out_verdicts, stats, d_workspace, workspace_bytes,
-                                                     static_cast<hipStream_t>(stream));
-    });
+    VerifyArgs a;
+    a.points = d_points; a.scalars = d_scalars; a.count = count; a.challenges = d_challenges;
+    a.weight_key = weight_key; a.index_base = index_base; a.weights = d_weights; a.group = group;
+    a.ok = d_out_verdicts; a.stats = stats;
+    if (int rc = verify_args(VERIFY_GROUPED, facts(v), 0, a, d_workspace)) return rc;
+    return on_ctx(v->ctx, [&](auto cv) -> int { return VerifyImpl<decltype(cv)>::run_grouped(v, a, d_workspace, workspace_bytes, hip(stream)); });
 }
 // the grouped check in two calls (one host thread, several batches in flight)
 extern "C" int bpp_verifier_grouped_begin(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
                                           const uint64_t* d_challenges, const uint8_t* weight_key, uint64_t index_base,
                                           const uint64_t* d_weights, uint32_t group, uint32_t* d_out_verdicts,
                                           void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!v || !d_out_verdicts || !d_workspace || (count && (!d_points || !d_scalars)))
-        return fail(BPP_E_ARG, "null argument");
-    if (!weight_key && !d_weights) return fail(BPP_E_ARG, "the grouped check needs a weight key or a weight buffer");
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::grouped_begin(v, d_points, d_scalars, count, d_challenges, weight_key, index_base,
-                                                       d_weights, group, d_out_verdicts, d_workspace, workspace_bytes,
-                                                       static_cast<hipStream_t>(stream));
-    });
+    VerifyArgs a;
+    a.points = d_points; a.scalars = d_scalars; a.count = count; a.challenges = d_challenges;
+    a.weight_key = weight_key; a.index_base = index_base; a.weights = d_weights; a.group = group;
+    a.ok = d_out_verdicts;
+    if (int rc = verify_args(VERIFY_GROUPED, facts(v), 0, a, d_workspace)) return rc;
+    return on_ctx(v->ctx, [&](auto cv) -> int { return VerifyImpl<decltype(cv)>::grouped_begin(v, a, d_workspace, workspace_bytes, hip(stream)); });
 }
 extern "C" int bpp_verifier_grouped_finish(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
                                            const uint64_t* d_challenges, uint32_t group, uint32_t* d_out_verdicts,
                                            uint64_t* stats, void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!v || !d_out_verdicts || !d_workspace || (count && (!d_points || !d_scalars)))
-        return fail(BPP_E_ARG, "null argument");
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::grouped_finish(v, d_points, d_scalars, count, d_challenges, group, d_out_verdicts, stats,
-                                                        d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    VerifyArgs a;
+    a.points = d_points; a.scalars = d_scalars; a.count = count; a.challenges = d_challenges;
+    a.group = group; a.ok = d_out_verdicts; a.stats = stats;
+    if (int rc = verify_args(VERIFY_GROUPED_FINISH, facts(v), 0, a, d_workspace)) return rc;
+    return on_ctx(v->ctx, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::grouped_finish(v, a, d_workspace, workspace_bytes, hip(stream));
     });
 }
 extern "C" int bpp_verifier_sum_partials(bpp_verifier* v, const void* d_partials, size_t n, uint32_t* d_ok,
@@ -581,12 +578,10 @@ extern "C" int bpp_verifier_sum_partials(bpp_verifier* v, const void* d_partials
 
 extern "C" int bpp_verifier_derive_challenges(bpp_verifier* v, const uint64_t* d_points, size_t count,
                                               uint64_t* d_challenges, void* stream) {
-    if (!v || !d_points || !d_challenges) return fail(BPP_E_ARG, "null argument");
-    if (count == 0) return BPP_OK;
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::derive_challenges(v, d_points, count, d_challenges,
-                                                           static_cast<hipStream_t>(stream));
-    });
+    VerifyArgs a;
+    a.points = d_points; a.count = count; a.out_challenges = d_challenges;
+    if (int rc = verify_args(VERIFY_DERIVE, facts(v), 0, a, nullptr)) return answered(rc);
+    return on_ctx(v->ctx, [&](auto cv) -> int { return VerifyImpl<decltype(cv)>::derive_challenges(v, a, nullptr, 0, hip(stream)); });
 }
 
 extern "C" int bpp_verifier_set_subgroup_check(bpp_verifier* v, int on) {
@@ -623,11 +618,10 @@ extern "C" int bpp_verifier_profile(bpp_verifier* v, float* out_stage_ms, size_t
 
 extern "C" int bpp_range_verify_batch(bpp_verifier* v, const uint64_t* points, const uint64_t* scalars, size_t count,
                                       uint32_t* out_ok) {
-    if (!v || !points || !scalars || !out_ok) return fail(BPP_E_ARG, "null argument");
-    if (count == 0) return BPP_OK;
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::verify_batch_host(v, points, scalars, count, out_ok);
-    });
+    VerifyArgs a;
+    a.points = points; a.scalars = scalars; a.count = count; a.ok = out_ok;
+    if (int rc = verify_args(VERIFY_HOST, facts(v), 0, a, nullptr)) return answered(rc);
+    return on_ctx(v->ctx, [&](auto cv) -> int { return VerifyImpl<decltype(cv)>::verify_host(v, a, HOST_WIRE, 0); });
 }
 
 // ---- mixed batches: proof i of shape (n, m_i) against the verifier's (n, m) tables (mixed.hpp) ------------------
@@ -639,37 +633,30 @@ extern "C" size_t bpp_verifier_mixed_workspace_bytes(const bpp_verifier* v, cons
 extern "C" int bpp_verifier_run_mixed(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars,
                                       const uint32_t* m_of, size_t count, const uint64_t* d_challenges, uint32_t* d_ok,
                                       void* d_workspace, size_t workspace_bytes, uint64_t* d_out_result, void* stream) {
-    if (!v) return fail(BPP_E_ARG, "null argument");
-    if (count == 0) return BPP_OK;
-    if (!d_points || !d_scalars || !m_of || !d_ok || !d_workspace) return fail(BPP_E_ARG, "null argument");
-    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
-    return on_ctx(v->ctx, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::run_mixed(v, d_points, d_scalars, m_of, count, d_challenges, d_ok, d_workspace,
-                                                   workspace_bytes, d_out_result, static_cast<hipStream_t>(stream));
-    });
+    VerifyArgs a;
+    a.points = d_points; a.scalars = d_scalars; a.m_of = m_of; a.count = count; a.challenges = d_challenges;
+    a.ok = d_ok; a.out_result = d_out_result;
+    if (int rc = verify_args(VERIFY_MIXED, facts(v), 0, a, d_workspace)) return answered(rc);
+    return on_ctx(v->ctx, [&](auto cv) -> int { return VerifyImpl<decltype(cv)>::run_mixed(v, a, d_workspace, workspace_bytes, hip(stream)); });
 }
 
 extern "C" int bpp_verifier_derive_challenges_mixed(bpp_verifier* v, const uint64_t* d_points, const uint32_t* m_of,
                                                     size_t count, uint64_t* d_challenges, void* d_workspace,
                                                     size_t workspace_bytes, void* stream) {
-    if (!v) return fail(BPP_E_ARG, "null argument");
-    if (count == 0) return BPP_OK;
-    if (!d_points || !m_of || !d_challenges || !d_workspace) return fail(BPP_E_ARG, "null argument");
-    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    VerifyArgs a;
+    a.points = d_points; a.m_of = m_of; a.count = count; a.out_challenges = d_challenges;
+    if (int rc = verify_args(VERIFY_DERIVE_MIXED, facts(v), 0, a, d_workspace)) return answered(rc);
     return on_ctx(v->ctx, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::derive_challenges_mixed(v, d_points, m_of, count, d_challenges, d_workspace,
-                                                                 workspace_bytes, static_cast<hipStream_t>(stream));
+        return VerifyImpl<decltype(cv)>::derive_challenges_mixed(v, a, d_workspace, workspace_bytes, hip(stream));
     });
 }
 
 extern "C" int bpp_range_verify_batch_mixed(bpp_verifier* v, const uint64_t* points, const uint64_t* scalars,
                                             const uint32_t* m_of, size_t count, uint32_t* out_ok) {
-    if (!v) return fail(BPP_E_ARG, "null argument");
-    if (count == 0) return BPP_OK;
-    if (!points || !scalars || !m_of || !out_ok) return fail(BPP_E_ARG, "null argument");
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::verify_batch_mixed_host(v, points, scalars, m_of, count, out_ok);
-    });
+    VerifyArgs a;
+    a.points = points; a.scalars = scalars; a.m_of = m_of; a.count = count; a.ok = out_ok;
+    if (int rc = verify_args(VERIFY_HOST_MIXED, facts(v), 0, a, nullptr)) return answered(rc);
+    return on_ctx(v->ctx, [&](auto cv) -> int { return VerifyImpl<decltype(cv)>::verify_host(v, a, HOST_MIXED, 0); });
 }
 
 // ---- compressed point encodings (codec.hpp) ---------------------------------------------------------------
@@ -703,13 +690,10 @@ extern "C" int bpp_points_decompress_device(bpp_ctx* ctx, const void* d_in, size
 
 extern "C" int bpp_range_verify_batch_compressed(bpp_verifier* v, const uint8_t* records, const uint64_t* scalars,
                                                  size_t count, uint32_t* out_ok) {
-    if (!v || !records || !scalars || !out_ok) return fail(BPP_E_ARG, "null argument");
-    if (count == 0) return BPP_OK;
-    const size_t cb = bpp_point_compressed_bytes(v->ctx.curve);
-    if (cb == 0) return fail(BPP_E_ARG, "compressed encoding is not offered for this curve");
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::verify_batch_compressed_host(v, records, scalars, count, out_ok);
-    });
+    VerifyArgs a;
+    a.proofs = records; a.scalars = scalars; a.count = count; a.ok = out_ok;
+    if (int rc = verify_args(VERIFY_HOST_COMPRESSED, facts(v), 0, a, nullptr)) return answered(rc);
+    return on_ctx(v->ctx, [&](auto cv) -> int { return VerifyImpl<decltype(cv)>::verify_host(v, a, HOST_COMPRESSED, 0); });
 }
 
 // ---- serialized proofs (the container; see include/bpp_amd.h) -----------------------------------------------------
@@ -774,23 +758,18 @@ extern "C" size_t bpp_verifier_serialized_workspace_bytes(const bpp_verifier* v,
 extern "C" int bpp_range_verify_batch_serialized_device(bpp_verifier* v, const void* d_proofs, const void* d_commitments,
                                                         size_t count, int flags, uint32_t* d_ok, void* d_workspace,
                                                         size_t workspace_bytes, void* stream) {
-    if (!v || !d_proofs || !d_commitments || !d_ok || !d_workspace) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED)) return fail(BPP_E_ARG, "unknown flag");
-    const int transcript = flags & BPP_SER_TRANSCRIPT;
-    const uint32_t version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
-    if (count == 0) return BPP_OK;
-    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    VerifyArgs a;
+    a.proofs = static_cast<const uint8_t*>(d_proofs); a.commitments = static_cast<const uint8_t*>(d_commitments);
+    a.count = count; a.ok = d_ok;
+    if (int rc = verify_args(VERIFY_SER, facts(v), flags, a, d_workspace)) return answered(rc);
     return on_ctx(v->ctx, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::run_serialized(v, static_cast<const uint8_t*>(d_proofs),
-                                                        static_cast<const uint8_t*>(d_commitments), count, transcript != 0,
-                                                        d_ok, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream),
-                                                        version);
+        return VerifyImpl<decltype(cv)>::run_serialized(v, a, d_workspace, workspace_bytes, hip(stream));
     });
 }
 
 // the same with the grouped check behind the decoder (per-proof statuses; synchronises the stream)
 extern "C" size_t bpp_verifier_serialized_grouped_workspace_bytes(const bpp_verifier* v, size_t count, uint32_t group) {
-    if (group < 2 || (group & (group - 1))) return 0;
+    if (!group_ok(group)) return 0;
     return size_for(v, [&](auto cv) { return VerifyImpl<decltype(cv)>::ser_layout(v->s, count, group).total; });
 }
 extern "C" int bpp_range_verify_batch_serialized_grouped_device(bpp_verifier* v, const void* d_proofs, const void* d_commitments,
@@ -798,33 +777,22 @@ extern "C" int bpp_range_verify_batch_serialized_grouped_device(bpp_verifier* v,
                                                                 uint64_t index_base, uint32_t group, uint32_t* d_ok,
                                                                 uint64_t* stats, void* d_workspace, size_t workspace_bytes,
                                                                 void* stream) {
-    if (!v || !d_proofs || !d_commitments || !d_ok || !d_workspace || !weight_key) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED)) return fail(BPP_E_ARG, "unknown flag");
-    const int transcript = flags & BPP_SER_TRANSCRIPT;
-    const uint32_t version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
-    if (stats) stats[0] = stats[1] = 0;
-    if (count == 0) return BPP_OK;
-    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
+    VerifyArgs a;
+    a.proofs = static_cast<const uint8_t*>(d_proofs); a.commitments = static_cast<const uint8_t*>(d_commitments);
+    a.count = count; a.weight_key = weight_key; a.index_base = index_base; a.group = group; a.ok = d_ok; a.stats = stats;
+    if (int rc = verify_args(VERIFY_SER_GROUPED, facts(v), flags, a, d_workspace)) return answered(rc);
     return on_ctx(v->ctx, [&](auto cv) -> int {
-        using Impl = VerifyImpl<decltype(cv)>;
-        const typename Impl::GroupedArgs ga{weight_key, index_base, nullptr, group, stats};
-        return Impl::run_serialized(v, static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), count,
-                                    transcript != 0, d_ok, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream),
-                                    version, &ga);
+        return VerifyImpl<decltype(cv)>::run_serialized(v, a, d_workspace, workspace_bytes, hip(stream));
     });
 }
 
 // host buffers in, host verdicts out: the device path above between two copies
 extern "C" int bpp_range_verify_batch_serialized(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments,
                                                  size_t count, int flags, uint32_t* out_ok) {
-    if (!v || !proofs || !commitments || !out_ok) return fail(BPP_E_ARG, "null argument");
-    if (count == 0) return BPP_OK;
-    const VerifyShape& s = v->s;
-    if (bpp_proof_bytes_version(v->ctx.curve, s.n, s.m, (flags & BPP_SER_UNCOMPRESSED) ? 2 : 1) == 0 || s.n > 255 || s.m > 255)
-        return fail(BPP_E_ARG, "n*m must be a power of two (n, m <= 255)");
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::verify_batch_serialized_host(v, proofs, commitments, count, flags, out_ok);
-    });
+    VerifyArgs a;
+    a.proofs = proofs; a.commitments = commitments; a.count = count; a.ok = out_ok;
+    if (int rc = verify_args(VERIFY_HOST_SER, facts(v), flags, a, nullptr)) return answered(rc);
+    return on_ctx(v->ctx, [&](auto cv) -> int { return VerifyImpl<decltype(cv)>::verify_host(v, a, HOST_SERIALIZED, flags); });
 }
 
 // ---- serialized proofs of mixed aggregation sizes (mixed.hpp; the framing of a bare stream: container_scan.hpp) ----
@@ -844,47 +812,35 @@ extern "C" int bpp_proofs_scan(int curve_id, size_t n, int version, const uint8_
 }
 
 extern "C" size_t bpp_verifier_serialized_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
-    if ((count && !m_of) || count > 0x7fffffffu / 64) return 0;
+    if (!mixed_sizes_ok(m_of, count)) return 0;
     return size_for(v, [&](auto cv) { return VerifyImpl<decltype(cv)>::ser_mixed_workspace_bytes(v, m_of, count); });
 }
 
 extern "C" int bpp_range_verify_batch_serialized_mixed_device(bpp_verifier* v, const void* d_proofs, const void* d_commitments,
                                                               const uint32_t* m_of, size_t count, int flags, uint32_t* d_ok,
                                                               void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!v) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED)) return fail(BPP_E_ARG, "unknown flag");
-    if (count == 0) return BPP_OK;
-    if (!d_proofs || !d_commitments || !m_of || !d_ok || !d_workspace) return fail(BPP_E_ARG, "null argument");
-    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
-    const int transcript = flags & BPP_SER_TRANSCRIPT;
-    const uint32_t version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::run_serialized_mixed(v, static_cast<const uint8_t*>(d_proofs),
-                                                              static_cast<const uint8_t*>(d_commitments), m_of, count,
-                                                              transcript != 0, d_ok, d_workspace, workspace_bytes,
-                                                              static_cast<hipStream_t>(stream), version);
+    VerifyArgs a;
+    a.proofs = static_cast<const uint8_t*>(d_proofs); a.commitments = static_cast<const uint8_t*>(d_commitments);
+    a.m_of = m_of; a.count = count; a.ok = d_ok;
+    if (int rc = verify_args(VERIFY_SER_MIXED, facts(v), flags, a, d_workspace)) return answered(rc);
+    return on_ctx(v->ctx, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::run_serialized_mixed(v, a, d_workspace, workspace_bytes, hip(stream));
     });
 }
 
 // host buffers in, host verdicts out: the device path above between two copies
 extern "C" int bpp_range_verify_batch_serialized_mixed(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments,
                                                        const uint32_t* m_of, size_t count, int flags, uint32_t* out_ok) {
-    if (!v) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED)) return fail(BPP_E_ARG, "unknown flag");
-    if (count == 0) return BPP_OK;
-    if (!proofs || !commitments || !m_of || !out_ok) return fail(BPP_E_ARG, "null argument");
-    const int version = (flags & BPP_SER_UNCOMPRESSED) ? 2 : 1;
-    const size_t cb = container_point_size(v->ctx.curve, version);
-    if (int rc = container_version_ok(cb)) return rc;
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::verify_batch_serialized_mixed_host(v, proofs, commitments, m_of, count, flags, out_ok);
-    });
+    VerifyArgs a;
+    a.proofs = proofs; a.commitments = commitments; a.m_of = m_of; a.count = count; a.ok = out_ok;
+    if (int rc = verify_args(VERIFY_HOST_SER_MIXED, facts(v), flags, a, nullptr)) return answered(rc);
+    return on_ctx(v->ctx, [&](auto cv) -> int { return VerifyImpl<decltype(cv)>::verify_host(v, a, HOST_SERIALIZED_MIXED, flags); });
 }
 
 // ---- the grouped check over mixed batches, wire records and bytes (impl_verify.hpp "grouped check over a MIXED batch") ----
 extern "C" size_t bpp_verifier_grouped_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count,
                                                              uint32_t group) {
-    if ((count && !m_of) || count > 0x7fffffffu / 64) return 0;
+    if (!mixed_sizes_ok(m_of, count)) return 0;
     return size_for(v, [&](auto cv) { return VerifyImpl<decltype(cv)>::grouped_mixed_workspace_bytes(v, m_of, count, group); });
 }
 
@@ -893,22 +849,19 @@ extern "C" int bpp_verifier_run_grouped_mixed(bpp_verifier* v, const uint64_t* d
                                               const uint8_t* weight_key, uint64_t index_base, const uint64_t* d_weights,
                                               uint32_t group, uint32_t* d_out_verdicts, uint64_t* stats, void* d_workspace,
                                               size_t workspace_bytes, void* stream) {
-    if (!v) return fail(BPP_E_ARG, "null argument");
-    if (stats) stats[0] = stats[1] = 0;
-    if (count == 0) return BPP_OK;
-    if (!d_points || !d_scalars || !m_of || !d_out_verdicts || !d_workspace) return fail(BPP_E_ARG, "null argument");
-    if (!weight_key && !d_weights) return fail(BPP_E_ARG, "the grouped check needs a weight key or a weight buffer");
-    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::run_grouped_mixed(v, d_points, d_scalars, m_of, count, d_challenges, weight_key,
-                                                           index_base, d_weights, group, d_out_verdicts, stats, d_workspace,
-                                                           workspace_bytes, static_cast<hipStream_t>(stream));
+    VerifyArgs a;
+    a.points = d_points; a.scalars = d_scalars; a.m_of = m_of; a.count = count; a.challenges = d_challenges;
+    a.weight_key = weight_key; a.index_base = index_base; a.weights = d_weights; a.group = group;
+    a.ok = d_out_verdicts; a.stats = stats;
+    if (int rc = verify_args(VERIFY_GROUPED_MIXED, facts(v), 0, a, d_workspace)) return answered(rc);
+    return on_ctx(v->ctx, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::run_grouped_mixed(v, a, d_workspace, workspace_bytes, hip(stream));
     });
 }
 
 extern "C" size_t bpp_verifier_serialized_grouped_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of,
                                                                         size_t count, uint32_t group) {
-    if ((count && !m_of) || count > 0x7fffffffu / 64) return 0;
+    if (!mixed_sizes_ok(m_of, count)) return 0;
     return size_for(v, [&](auto cv) {
         return VerifyImpl<decltype(cv)>::ser_grouped_mixed_workspace_bytes(v, m_of, count, group);
     });
@@ -920,18 +873,13 @@ extern "C" int bpp_range_verify_batch_serialized_grouped_mixed_device(bpp_verifi
                                                                       uint64_t index_base, uint32_t group, uint32_t* d_ok,
                                                                       uint64_t* stats, void* d_workspace,
                                                                       size_t workspace_bytes, void* stream) {
-    if (!v) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~(BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED)) return fail(BPP_E_ARG, "unknown flag");
-    if (stats) stats[0] = stats[1] = 0;
-    if (count == 0) return BPP_OK;
-    if (!d_proofs || !d_commitments || !m_of || !d_ok || !d_workspace || !weight_key) return fail(BPP_E_ARG, "null argument");
-    if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
-    const int transcript = flags & BPP_SER_TRANSCRIPT;
-    const uint32_t version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return VerifyImpl<decltype(cv)>::run_serialized_grouped_mixed(
-            v, static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), m_of, count, transcript != 0,
-            weight_key, index_base, group, d_ok, stats, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream), version);
+    VerifyArgs a;
+    a.proofs = static_cast<const uint8_t*>(d_proofs); a.commitments = static_cast<const uint8_t*>(d_commitments);
+    a.m_of = m_of; a.count = count; a.weight_key = weight_key; a.index_base = index_base; a.group = group;
+    a.ok = d_ok; a.stats = stats;
+    if (int rc = verify_args(VERIFY_SER_GROUPED_MIXED, facts(v), flags, a, d_workspace)) return answered(rc);
+    return on_ctx(v->ctx, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::run_serialized_grouped_mixed(v, a, d_workspace, workspace_bytes, hip(stream));
     });
 }
 

@@ -49,10 +49,6 @@ template <class C>
 constexpr size_t max_point_bytes() {
     return uncompressed_bytes<C>() ? uncompressed_bytes<C>() : compressed_bytes<C>();
 }
-// every container entry point's version check; pb: the bytes of one point in the version asked for, 0 when there is none
-inline int container_version_ok(size_t pb) {
-    return pb ? BPP_OK : fail(BPP_E_ARG, "container version 2 (uncompressed points) is not offered for this curve");
-}
 
 // a^((p+1)/4): the square root of a quadratic residue when p = 3 mod 4; the caller checks the result by squaring.
 // Fixed 2-bit windows over the public constant P::SQRTW, most significant first, with the three table entries a, a^2,

@@ -13,6 +13,7 @@
 #include "host_util.hpp"
 #include "mixed.hpp"
 #include "pippenger.hpp"
+#include "verify_args.hpp"
 
 // stages of one pass, in launch order (bpp_verifier_profile reports one duration per stage)
 enum { BPP_STAGE_FROM_WIRE = 0, BPP_STAGE_SCALARS, BPP_STAGE_FIXED_MSM, BPP_STAGE_VAR_MSM, BPP_STAGE_FINALIZE,
@@ -82,6 +83,9 @@ struct WsLayout {
     size_t pts, bad, scalars, prep, fthread, fpart, fpart2, fpart3, vpart, vdig, vwsum, vtbl, vscr, total;
 };
 
+// the host forms of the verifier (VerifyImpl::verify_host)
+enum HostForm { HOST_WIRE, HOST_MIXED, HOST_COMPRESSED, HOST_SERIALIZED, HOST_SERIALIZED_MIXED };
+
 template <class C>
 struct VerifyImpl {
     static constexpr int N = C::Fp::N;
@@ -119,15 +123,15 @@ struct VerifyImpl {
         return c < v->views.size() ? v->views[c] : own(v);
     }
 
-    // one pass over `count` proofs of shape ps (run(v, ...): the verifier's own)
+    // The public forms take the call as a record (verify_args.hpp VerifyArgs: the argument conventions are its fields'), the
+    // workspace and the stream.  Beneath them the PassShape overloads of run and derive_challenges are the inner seam.
+    // one pass over `count` proofs of shape ps (run(v, a, ...): the verifier's own)
     static int run(bpp_verifier* v, const PassShape& ps, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
                    const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace, size_t workspace_bytes,
                    uint64_t* d_out_scalars, uint64_t* d_out_result, hipStream_t st);
-    static int run(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
-                   const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace, size_t workspace_bytes,
-                   uint64_t* d_out_scalars, uint64_t* d_out_result, hipStream_t st) {
-        return run(v, own(v), d_points, d_scalars, count, d_challenges, d_ok, d_workspace, workspace_bytes, d_out_scalars,
-                   d_out_result, st);
+    static int run(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
+        return run(v, own(v), a.points, a.scalars, a.count, a.challenges, a.ok, d_workspace, workspace_bytes, a.out_scalars,
+                   a.out_result, st);
     }
 
     // the range statement's scalar stage (run, begin_pass); d_challenges null: the shape's default ones for every proof
@@ -209,9 +213,8 @@ struct VerifyImpl {
 
     static int derive_challenges(bpp_verifier* v, const PassShape& ps, const uint64_t* d_points, size_t count,
                                  uint64_t* d_challenges, hipStream_t st);
-    static int derive_challenges(bpp_verifier* v, const uint64_t* d_points, size_t count, uint64_t* d_challenges,
-                                 hipStream_t st) {
-        return derive_challenges(v, own(v), d_points, count, d_challenges, st);
+    static int derive_challenges(bpp_verifier* v, const VerifyArgs& a, void*, size_t, hipStream_t st) {
+        return derive_challenges(v, own(v), a.points, a.count, a.out_challenges, st);
     }
 
     // ---- mixed batches (mixed.hpp): proof i of shape (n, m_i), m_i a power of two <= m ---------------------------
@@ -287,14 +290,10 @@ struct VerifyImpl {
         if (mixed_plan(v->s, m_of, count, false, p)) return 0;
         return mixed_layout(v, p, count).total;
     }
-    // d_challenges: NULL or 3 + k_i scalars per proof, packed in caller order; d_ok, d_out_result (may be NULL) in caller
-    // order.  Uploads the per-proof index (blocking the host until the copy has read it), the rest is enqueued on st.
-    static int run_mixed(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, const uint32_t* m_of,
-                         size_t count, const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace,
-                         size_t workspace_bytes, uint64_t* d_out_result, hipStream_t st);
-    // d_challenges: 3 + k_i scalars per proof, packed in caller order (the layout run_mixed takes)
-    static int derive_challenges_mixed(bpp_verifier* v, const uint64_t* d_points, const uint32_t* m_of, size_t count,
-                                       uint64_t* d_challenges, void* d_workspace, size_t workspace_bytes, hipStream_t st);
+    // Both upload the per-proof index (blocking the host until the copy has read it); the rest is enqueued on st.
+    static int run_mixed(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st);
+    static int derive_challenges_mixed(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes,
+                                       hipStream_t st);
 
     // ---- RangeProof::verify over SERIALIZED proofs resident in HBM (codec.hpp: the container) ---------------
     // what every serialized entry point asks of engine and container version (the size getters: of the engine alone)
@@ -319,20 +318,9 @@ struct VerifyImpl {
         w.total = o.total;
         return w;
     }
-    // the grouped check's arguments when it stands behind the decoder (run_serialized)
-    struct GroupedArgs {
-        const uint8_t* weight_key;
-        uint64_t index_base;
-        const uint64_t* d_weights;
-        uint32_t group;
-        uint64_t* h_stats;
-    };
-    // d_proofs: count x container_bytes ; d_commitments: count x m compressed points ; d_ok: 0 Ok / 1 VerificationError /
-    // 2 FormatError per proof.  Everything on `st`, no host synchronisation.
-    // grouped != null: verdicts through run_grouped (synchronises `st`)
-    static int run_serialized(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments, size_t count,
-                              bool transcript, uint32_t* d_ok, void* d_workspace, size_t workspace_bytes, hipStream_t st,
-                              uint32_t version = 1, const GroupedArgs* grouped = nullptr);
+    // Everything on `st`, no host synchronisation -- unless the record names a weight source: then the verdicts come
+    // through run_grouped (synchronises `st`)
+    static int run_serialized(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st);
 
     // ---- ... of MIXED aggregation sizes: the decoder writes each record into its class region (mixed.hpp) -------
     // workspace = front (the challenges in transcript mode) | one class pass's workspace
@@ -354,12 +342,9 @@ struct VerifyImpl {
         if (!container_shape_ok(v) || mixed_plan_serialized(v->s, m_of, count, max_point_bytes<C>(), false, p)) return 0;
         return ser_mixed_layout(v, p, count).total;
     }
-    // d_proofs: the containers packed back to back in caller order, container i of container_bytes(k_i, version) bytes;
-    // d_commitments: m_i encoded points per proof, packed in caller order; m_of: host; d_ok: caller order, 0 / 1 / 2.
     // Uploads the per-proof index (blocking the host until the copy has read it), the rest is enqueued on st.
-    static int run_serialized_mixed(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments,
-                                    const uint32_t* m_of, size_t count, bool transcript, uint32_t* d_ok, void* d_workspace,
-                                    size_t workspace_bytes, hipStream_t st, uint32_t version);
+    static int run_serialized_mixed(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes,
+                                    hipStream_t st);
 
     // ---- combined batch check (combined.hpp) ------------------------------------------------------------
     struct CombLayout {
@@ -389,11 +374,7 @@ struct VerifyImpl {
         return w;
     }
 
-    // d_out_partial: one jacobian (3N words, opaque to the caller) = this batch's weighted sum
-    static int run_combined(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
-                            const uint64_t* d_challenges, const uint8_t* weight_key, uint64_t index_base,
-                            const uint64_t* d_weights, uint32_t* d_out_partial, uint32_t* d_ok, void* d_workspace,
-                            size_t workspace_bytes, hipStream_t st);
+    static int run_combined(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st);
 
     // ---- grouped check (combined.hpp): per-proof verdicts from one weighted check per GROUP of proofs ------
     // the back of every grouped workspace, behind the proofs' window sums: their folds | per group the rows, invalid-point
@@ -452,26 +433,16 @@ struct VerifyImpl {
         w.total = o.total;
         return w;
     }
-    static bool group_ok(uint32_t group) { return group >= 2 && !(group & (group - 1)); }
     static int check_group(uint32_t group) {
         return group_ok(group) ? BPP_OK : fail(BPP_E_ARG, "group must be a power of two, at least 2");
     }
-    // d_out_verdicts: count words, 0 = Ok / 1 = VerificationError, as bpp_verifier_run writes them.  h_stats (host, may be
-    // null): [groups that failed their weighted check, proofs re-verified by the exact pass].  Synchronises `st`.
-    static int run_grouped(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
-                           const uint64_t* d_challenges, const uint8_t* weight_key, uint64_t index_base,
-                           const uint64_t* d_weights, uint32_t group, uint32_t* d_out_verdicts, uint64_t* h_stats,
-                           void* d_workspace, size_t workspace_bytes, hipStream_t st);
+    // The verdict words are those bpp_verifier_run writes.  Synchronises `st`.
+    static int run_grouped(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st);
     // the same in two calls, so that ONE host thread can keep several batches in flight (a stream and a workspace each):
     // grouped_begin only enqueues pass 1; grouped_finish (same buffers, same stream) synchronises, reads the groups' verdicts
     // and runs pass 2.  run_grouped = begin + finish.
-    static int grouped_begin(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
-                             const uint64_t* d_challenges, const uint8_t* weight_key, uint64_t index_base,
-                             const uint64_t* d_weights, uint32_t group, uint32_t* d_out_verdicts, void* d_workspace,
-                             size_t workspace_bytes, hipStream_t st);
-    static int grouped_finish(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
-                              const uint64_t* d_challenges, uint32_t group, uint32_t* d_out_verdicts, uint64_t* h_stats,
-                              void* d_workspace, size_t workspace_bytes, hipStream_t st);
+    static int grouped_begin(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st);
+    static int grouped_finish(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st);
     // the grouped back end (only enqueues), behind the writers of the rows B.grows and flags B.gbad: the window sums at
     // `vwsum` (`per` per proof) folded to one set per group, the batch verifier's last stages over G virtual proofs of shape
     // cap in Horner form `tree`, each group's verdict spread over its proofs into out_verdicts
@@ -568,18 +539,11 @@ struct VerifyImpl {
             return 0;
         return group_mixed_layout(v, p, count, group, true).total;
     }
-    // Input layout, m_of rules and errors: run_mixed's.  Weights (proof i of the CALLER's order gets PRF(key, index_base + i)
-    // or d_weights[i]), group, h_stats, verdict words and the stream synchronisation: run_grouped's.
-    static int run_grouped_mixed(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, const uint32_t* m_of,
-                                 size_t count, const uint64_t* d_challenges, const uint8_t* weight_key, uint64_t index_base,
-                                 const uint64_t* d_weights, uint32_t group, uint32_t* d_out_verdicts, uint64_t* h_stats,
-                                 void* d_workspace, size_t workspace_bytes, hipStream_t st);
-    // ... behind the decoder: run_serialized_mixed's front, d_ok 0 / 1 / 2 in caller order; a container the decoder rejects
-    // keeps FormatError and fails its group
-    static int run_serialized_grouped_mixed(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments,
-                                            const uint32_t* m_of, size_t count, bool transcript, const uint8_t* weight_key,
-                                            uint64_t index_base, uint32_t group, uint32_t* d_ok, uint64_t* h_stats,
-                                            void* d_workspace, size_t workspace_bytes, hipStream_t st, uint32_t version);
+    // m_of rules and errors: run_mixed's; verdict words and the stream synchronisation: run_grouped's
+    static int run_grouped_mixed(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st);
+    // ... behind the decoder: run_serialized_mixed's front; a container the decoder rejects keeps FormatError and fails its group
+    static int run_serialized_grouped_mixed(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes,
+                                            hipStream_t st);
     // the core of both, from the plan and the front L.f in the workspace (its challenges when with_challenges, its status
     // when with_status) and L.weights by gathered position: both passes; the verdicts are left in L.f.ok by GATHERED
     // position for the caller's scatter.  Synchronises `st`.
@@ -588,20 +552,12 @@ struct VerifyImpl {
                                   size_t workspace_bytes, hipStream_t st);
 
     // ---- host buffers in, host verdicts out (staging.hpp) ------------------------------------------------------------
-    // bpp_range_verify_batch, _mixed, _compressed, _serialized and _serialized_mixed past their argument checks: each is
-    // its device ENTRY (bpp_verifier_run, .._run_mixed, bpp_range_verify_batch_serialized[_mixed]_device) between copies,
-    // so the entry's own argument rules (count per launch, flags) hold here without a second copy of them
-    static int verify_batch_host(bpp_verifier* v, const uint64_t* points, const uint64_t* scalars, size_t count, uint32_t* out_ok);
-    static int verify_batch_mixed_host(bpp_verifier* v, const uint64_t* points, const uint64_t* scalars, const uint32_t* m_of,
-                                       size_t count, uint32_t* out_ok);
-    // records: NV compressed points per proof; a malformed encoding, a point outside the group or a non-canonical scalar
-    // makes the proof's verdict BPP_FORMAT_ERROR
-    static int verify_batch_compressed_host(bpp_verifier* v, const uint8_t* records, const uint64_t* scalars, size_t count,
-                                            uint32_t* out_ok);
-    static int verify_batch_serialized_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, size_t count,
-                                            int flags, uint32_t* out_ok);
-    static int verify_batch_serialized_mixed_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments,
-                                                  const uint32_t* m_of, size_t count, int flags, uint32_t* out_ok);
+    // bpp_range_verify_batch, _mixed, _compressed, _serialized and _serialized_mixed past their argument checks: the form's
+    // device ENTRY (bpp_verifier_run, .._run_mixed, bpp_range_verify_batch_serialized[_mixed]_device) between copies, so the
+    // entry's own argument rules (count per launch, flags: passed on as the caller gave them) hold here without a second
+    // copy of them.  HOST_COMPRESSED: a malformed encoding, a point outside the group or a non-canonical scalar makes the
+    // proof's verdict BPP_FORMAT_ERROR.
+    static int verify_host(bpp_verifier* v, const VerifyArgs& a, HostForm form, int flags);
 
     // d_partials: n partials as bpp_verifier_run_combined wrote them (jacobian + validity word each)
     static int sum_partials(const uint32_t* d_partials, size_t n, uint32_t* d_ok, hipStream_t st);
@@ -920,12 +876,13 @@ int VerifyImpl<C>::finish(bpp_verifier* v, const VerifyShape& s, uint8_t* ws, co
 }
 
 template <class C>
-int VerifyImpl<C>::run_serialized(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments, size_t count,
-                                  bool transcript, uint32_t* d_ok, void* d_workspace, size_t workspace_bytes,
-                                  hipStream_t st, uint32_t version, const GroupedArgs* grouped) {
+int VerifyImpl<C>::run_serialized(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes,
+                                  hipStream_t st) {
     const VerifyShape& s = v->s;
-    if (int rc = container_args_ok(v, version)) return rc;
-    const SerLayout L = ser_layout(s, count, grouped ? grouped->group : 0u);
+    const size_t count = a.count;
+    const bool grouped = a.weight_key || a.weights;
+    if (int rc = container_args_ok(v, a.version)) return rc;
+    const SerLayout L = ser_layout(s, count, grouped ? a.group : 0u);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     uint32_t* w_rec = reinterpret_cast<uint32_t*>(ws + L.records);
@@ -933,23 +890,24 @@ int VerifyImpl<C>::run_serialized(bpp_verifier* v, const uint8_t* d_proofs, cons
     uint32_t* w_st = reinterpret_cast<uint32_t*>(ws + L.status);
     uint64_t* w_ch = reinterpret_cast<uint64_t*>(ws + L.challenges);
     HIPCHK(zero_words_async(w_st, count * 4, st));
-    hipLaunchKernelGGL(k_container_decode<C>, dim3(cdiv(count * s.NV, 64)), dim3(64), 0, st, s, d_proofs, d_commitments,
-                       w_rec, w_sc, w_st, count, version);
+    hipLaunchKernelGGL(k_container_decode<C>, dim3(cdiv(count * s.NV, 64)), dim3(64), 0, st, s, a.proofs, a.commitments,
+                       w_rec, w_sc, w_st, count, a.version);
     if constexpr (C::ID == 0)   // cofactor > 1: membership of the prime-order subgroup
         hipLaunchKernelGGL(k_records_subgroup<C>, dim3(cdiv(count * s.NV, 64)), dim3(64), 0, st, w_rec, w_st, s.NV,
                            count * s.NV);
     HIPCHK(hipGetLastError());
-    if (transcript) {
-        int rc = derive_challenges(v, reinterpret_cast<const uint64_t*>(w_rec), count, w_ch, st);
+    VerifyArgs wire = a;   // the decoded batch: the weight source, group, verdicts and stats stay the caller's
+    wire.points = reinterpret_cast<const uint64_t*>(w_rec);
+    wire.scalars = reinterpret_cast<const uint64_t*>(w_sc);
+    wire.challenges = a.fs ? w_ch : nullptr;
+    if (a.fs) {
+        int rc = derive_challenges(v, own(v), wire.points, count, w_ch, st);
         if (rc) return rc;
     }
-    int rc = grouped ? run_grouped(v, reinterpret_cast<const uint64_t*>(w_rec), reinterpret_cast<const uint64_t*>(w_sc), count,
-                                   transcript ? w_ch : nullptr, grouped->weight_key, grouped->index_base, grouped->d_weights,
-                                   grouped->group, d_ok, grouped->h_stats, ws + L.run, workspace_bytes - L.run, st)
-                     : run(v, reinterpret_cast<const uint64_t*>(w_rec), reinterpret_cast<const uint64_t*>(w_sc), count,
-                           transcript ? w_ch : nullptr, d_ok, ws + L.run, workspace_bytes - L.run, nullptr, nullptr, st);
+    int rc = grouped ? run_grouped(v, wire, ws + L.run, workspace_bytes - L.run, st)
+                     : run(v, wire, ws + L.run, workspace_bytes - L.run, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_container_status<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, w_st, d_ok, count);
+    hipLaunchKernelGGL(k_container_status<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, w_st, a.ok, count);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
@@ -1006,42 +964,40 @@ int VerifyImpl<C>::scatter_verdicts(const MixedFront& front, uint8_t* ws, uint32
 // Gather, then today's pass over each class's contiguous region with the class's view (Horner form, lone batch and
 // blocks per proof follow the class's own count), then the verdicts and result points back into caller order.
 template <class C>
-int VerifyImpl<C>::run_mixed(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, const uint32_t* m_of,
-                             size_t count, const uint64_t* d_challenges, uint32_t* d_ok, void* d_workspace,
-                             size_t workspace_bytes, uint64_t* d_out_result, hipStream_t st) {
+int VerifyImpl<C>::run_mixed(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
+    const size_t count = a.count;
     MixedPlan p;
-    int rc = mixed_plan(v->s, m_of, count, true, p);
+    int rc = mixed_plan(v->s, a.m_of, count, true, p);
     if (rc) return rc;
     const MixedLayout L = mixed_layout(v, p, count);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-    rc = gather_front(p, L.f, count, d_points, d_scalars, d_challenges, ws, st);
+    rc = gather_front(p, L.f, count, a.points, a.scalars, a.challenges, ws, st);
     if (rc) return rc;
     uint32_t* w_ok = reinterpret_cast<uint32_t*>(ws + L.f.ok);
-    uint64_t* w_res = d_out_result ? reinterpret_cast<uint64_t*>(ws + L.result) : nullptr;
+    uint64_t* w_res = a.out_result ? reinterpret_cast<uint64_t*>(ws + L.result) : nullptr;
     rc = for_each_class(v, p, L.f, ws, [&](const ClassView& cv) {
-        return run(v, cv.ps, cv.pts, cv.sc3, cv.count, d_challenges ? cv.challenges : nullptr, w_ok + cv.first, ws + L.run,
+        return run(v, cv.ps, cv.pts, cv.sc3, cv.count, a.challenges ? cv.challenges : nullptr, w_ok + cv.first, ws + L.run,
                    workspace_bytes - L.run, nullptr, w_res ? w_res + cv.first * PW : nullptr, st);
     });
     if (rc) return rc;
     hipLaunchKernelGGL(k_mixed_scatter<C>, dim3(cdiv(count, 4)), dim3(256), 0, st,
-                       reinterpret_cast<const uint32_t*>(ws + L.f.idx), count, w_ok, w_res, nullptr, d_ok, d_out_result,
-                       nullptr);
+                       reinterpret_cast<const uint32_t*>(ws + L.f.idx), count, w_ok, w_res, nullptr, a.ok, a.out_result, nullptr);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
 
 template <class C>
-int VerifyImpl<C>::derive_challenges_mixed(bpp_verifier* v, const uint64_t* d_points, const uint32_t* m_of, size_t count,
-                                           uint64_t* d_challenges, void* d_workspace, size_t workspace_bytes,
+int VerifyImpl<C>::derive_challenges_mixed(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes,
                                            hipStream_t st) {
+    const size_t count = a.count;
     MixedPlan p;
-    int rc = mixed_plan(v->s, m_of, count, true, p);
+    int rc = mixed_plan(v->s, a.m_of, count, true, p);
     if (rc) return rc;
     const MixedLayout L = mixed_layout(v, p, count);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-    rc = gather_front(p, L.f, count, d_points, nullptr, nullptr, ws, st);   // the points only
+    rc = gather_front(p, L.f, count, a.points, nullptr, nullptr, ws, st);   // the points only
     if (rc) return rc;
     rc = for_each_class(v, p, L.f, ws, [&](const ClassView& cv) {
         return derive_challenges(v, cv.ps, cv.pts, cv.count, cv.challenges, st);
@@ -1049,7 +1005,7 @@ int VerifyImpl<C>::derive_challenges_mixed(bpp_verifier* v, const uint64_t* d_po
     if (rc) return rc;
     hipLaunchKernelGGL(k_mixed_scatter<C>, dim3(cdiv(count, 4)), dim3(256), 0, st,
                        reinterpret_cast<const uint32_t*>(ws + L.f.idx), count, nullptr, nullptr,
-                       reinterpret_cast<uint64_t*>(ws + L.f.challenges), nullptr, nullptr, d_challenges);
+                       reinterpret_cast<uint64_t*>(ws + L.f.challenges), nullptr, nullptr, a.out_challenges);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
@@ -1058,37 +1014,35 @@ int VerifyImpl<C>::derive_challenges_mixed(bpp_verifier* v, const uint64_t* d_po
 // pass with the class's view; decoder status and verdicts go back to caller order in one kernel.  A container whose
 // header names another shape than m_of[i] fails the header compare of ITS class: a FormatError of that proof only.
 template <class C>
-int VerifyImpl<C>::run_serialized_mixed(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments,
-                                        const uint32_t* m_of, size_t count, bool transcript, uint32_t* d_ok,
-                                        void* d_workspace, size_t workspace_bytes, hipStream_t st, uint32_t version) {
-    if (int rc = container_args_ok(v, version)) return rc;
+int VerifyImpl<C>::run_serialized_mixed(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes,
+                                        hipStream_t st) {
+    const size_t count = a.count;
+    if (int rc = container_args_ok(v, a.version)) return rc;
     MixedPlan p;
-    int rc = mixed_plan_serialized(v->s, m_of, count, (size_t)container_point_bytes<C>(version), true, p);
+    int rc = mixed_plan_serialized(v->s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), true, p);
     if (rc) return rc;
     const SerMixedLayout L = ser_mixed_layout(v, p, count);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
-    rc = decode_front(p, L.f, count, d_proofs, d_commitments, version, ws, st);
+    rc = decode_front(p, L.f, count, a.proofs, a.commitments, a.version, ws, st);
     if (rc) return rc;
     rc = for_each_class(v, p, L.f, ws, [&](const ClassView& cv) {
-        if (transcript) {
+        if (a.fs) {
             const int rc1 = derive_challenges(v, cv.ps, cv.pts, cv.count, cv.challenges, st);
             if (rc1) return rc1;
         }
-        return run(v, cv.ps, cv.pts, cv.sc3, cv.count, transcript ? cv.challenges : nullptr, W(L.f.ok) + cv.first, ws + L.run,
+        return run(v, cv.ps, cv.pts, cv.sc3, cv.count, a.fs ? cv.challenges : nullptr, W(L.f.ok) + cv.first, ws + L.run,
                    workspace_bytes - L.run, nullptr, nullptr, st);
     });
     if (rc) return rc;
-    return scatter_verdicts(L.f, ws, d_ok, count, st);
+    return scatter_verdicts(L.f, ws, a.ok, count, st);
 }
 
 template <class C>
-int VerifyImpl<C>::run_combined(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
-                        const uint64_t* d_challenges, const uint8_t* weight_key, uint64_t index_base,
-                        const uint64_t* d_weights, uint32_t* d_out_partial, uint32_t* d_ok, void* d_workspace,
-                        size_t workspace_bytes, hipStream_t st) {
+int VerifyImpl<C>::run_combined(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
     const VerifyShape& s = v->s;
+    const size_t count = a.count;
     const CombLayout L = comb_layout(s, count);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     if (count * s.NV >= ((size_t)1 << 30)) return fail(BPP_E_ARG, "count too large");
@@ -1099,9 +1053,9 @@ int VerifyImpl<C>::run_combined(bpp_verifier* v, const uint64_t* d_points, const
     uint32_t* w_fp = reinterpret_cast<uint32_t*>(ws + L.fpart);
     HIPCHK(zero_words_async(w_cs, (size_t)s.N * 32, st));
     std::unique_lock<std::mutex> aux_lock;
-    int rc = begin_pass(v, own(v), d_points, d_scalars, count, d_challenges, ws, L, w_sc, aux_lock, st, nullptr);
+    int rc = begin_pass(v, own(v), a.points, a.scalars, count, a.challenges, ws, L, w_sc, aux_lock, st, nullptr);
     if (rc) return rc;
-    rc = weighted_windows(v, own(v), ws, L, count, weight_key, index_base, d_weights, var_wsums<C>(), 1u, aux_lock, st,
+    rc = weighted_windows(v, own(v), ws, L, count, a.weight_key, a.index_base, a.weights, var_wsums<C>(), 1u, aux_lock, st,
                           [&](const uint32_t* w_wt) {
                               hipLaunchKernelGGL(k_comb_fixed<C>, dim3(s.NF), dim3(256), 0, st, s, w_sc, w_wt, count, w_cs);
                           });
@@ -1115,23 +1069,17 @@ int VerifyImpl<C>::run_combined(bpp_verifier* v, const uint64_t* d_points, const
     // leading block; the Horner result lands behind the block sums
     launch_fixed_msm<C, 1>(1 + L.fixed_blocks, st, s, w_cs, v->table.u32(), w_fp, L.fixed_blocks, 1u, cur,
                            w_fp + (size_t)L.fixed_blocks * JW, (size_t)1, 1u, VpSel{1u, 0u, 1u, 0u});
-    hipLaunchKernelGGL(k_comb_sum_partials<C>, dim3(1), dim3(64), 0, st, w_fp, L.fixed_blocks + 1, (uint32_t)JW, 0u, d_ok,
-                       d_out_partial);
-    hipLaunchKernelGGL(k_comb_verdict<C>, dim3(1), dim3(256), 0, st, d_out_partial, w_bad, count, d_ok);
+    hipLaunchKernelGGL(k_comb_sum_partials<C>, dim3(1), dim3(64), 0, st, w_fp, L.fixed_blocks + 1, (uint32_t)JW, 0u, a.ok,
+                       a.out_partial);
+    hipLaunchKernelGGL(k_comb_verdict<C>, dim3(1), dim3(256), 0, st, a.out_partial, w_bad, count, a.ok);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
 
 template <class C>
-int VerifyImpl<C>::run_grouped(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
-                               const uint64_t* d_challenges, const uint8_t* weight_key, uint64_t index_base,
-                               const uint64_t* d_weights, uint32_t group, uint32_t* d_out_verdicts, uint64_t* h_stats,
-                               void* d_workspace, size_t workspace_bytes, hipStream_t st) {
-    int rc = grouped_begin(v, d_points, d_scalars, count, d_challenges, weight_key, index_base, d_weights, group, d_out_verdicts,
-                           d_workspace, workspace_bytes, st);
-    if (rc) return rc;
-    return grouped_finish(v, d_points, d_scalars, count, d_challenges, group, d_out_verdicts, h_stats, d_workspace,
-                          workspace_bytes, st);
+int VerifyImpl<C>::run_grouped(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
+    if (int rc = grouped_begin(v, a, d_workspace, workspace_bytes, st)) return rc;
+    return grouped_finish(v, a, d_workspace, workspace_bytes, st);
 }
 
 template <class C>
@@ -1184,11 +1132,10 @@ int VerifyImpl<C>::exact_pass(bpp_verifier* v, const PassShape& ps, const uint64
 
 // pass 1 (only enqueues): one weighted check per group, through the batch verifier's own last stages at count = G
 template <class C>
-int VerifyImpl<C>::grouped_begin(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
-                                 const uint64_t* d_challenges, const uint8_t* weight_key, uint64_t index_base,
-                                 const uint64_t* d_weights, uint32_t group, uint32_t* d_out_verdicts, void* d_workspace,
-                                 size_t workspace_bytes, hipStream_t st) {
+int VerifyImpl<C>::grouped_begin(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
     const VerifyShape& s = v->s;
+    const size_t count = a.count;
+    const uint32_t group = a.group;
     if (int rc = check_group(group)) return rc;
     const GroupLayout L = group_layout(s, count, group);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
@@ -1199,11 +1146,11 @@ int VerifyImpl<C>::grouped_begin(bpp_verifier* v, const uint64_t* d_points, cons
     uint32_t *w_bad = W(L.bad), *w_sc = W(L.scalars), *w_rows = W(L.b.grows), *w_gbad = W(L.b.gbad);
     const size_t G = L.b.groups;
     std::unique_lock<std::mutex> aux_lock;
-    int rc = begin_pass(v, own(v), d_points, d_scalars, count, d_challenges, ws, L, w_sc, aux_lock, st, nullptr);
+    int rc = begin_pass(v, own(v), a.points, a.scalars, count, a.challenges, ws, L, w_sc, aux_lock, st, nullptr);
     if (rc) return rc;
     const uint32_t tree = horner_form(s, G);
     const uint32_t per = tree == 1 ? var_wsums<C>() : var_windows<C>();   // window sums per proof, in the layout the Horner form reads
-    rc = weighted_windows(v, own(v), ws, L, count, weight_key, index_base, d_weights, per, tree == 1 ? 1u : 0u, aux_lock, st,
+    rc = weighted_windows(v, own(v), ws, L, count, a.weight_key, a.index_base, a.weights, per, tree == 1 ? 1u : 0u, aux_lock, st,
                           [&](const uint32_t* w_wt) {
                               hipLaunchKernelGGL(k_comb_fixed_grouped<C>, dim3((unsigned)(G * cdiv(s.NF, 64))), dim3(64), 0,
                                                  st, s, w_sc, w_wt, count, group, w_rows);
@@ -1211,25 +1158,23 @@ int VerifyImpl<C>::grouped_begin(bpp_verifier* v, const uint64_t* d_points, cons
                                                  w_gbad, G);
                           });
     if (rc) return rc;
-    return group_back_end(v, s, ws, L.b, L.vwsum, per, tree, count, group, d_out_verdicts, st);
+    return group_back_end(v, s, ws, L.b, L.vwsum, per, tree, count, group, a.ok, st);
 }
 
 // the groups' verdicts come back to the host (synchronises `st`); pass 2: the proofs of the groups that failed, exactly,
 // through the per-proof path.  Same buffers and stream as the grouped_begin it completes.
 template <class C>
-int VerifyImpl<C>::grouped_finish(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars, size_t count,
-                                  const uint64_t* d_challenges, uint32_t group, uint32_t* d_out_verdicts, uint64_t* h_stats,
-                                  void* d_workspace, size_t workspace_bytes, hipStream_t st) {
-    if (int rc = check_group(group)) return rc;
-    const GroupLayout L = group_layout(v->s, count, group);
+int VerifyImpl<C>::grouped_finish(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
+    if (int rc = check_group(a.group)) return rc;
+    const GroupLayout L = group_layout(v->s, a.count, a.group);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
-    if (h_stats) h_stats[0] = h_stats[1] = 0;
-    if (count == 0) return BPP_OK;
+    if (a.stats) a.stats[0] = a.stats[1] = 0;
+    if (a.count == 0) return BPP_OK;
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     std::vector<uint32_t> list;
-    int rc = failing_groups(reinterpret_cast<const uint32_t*>(ws + L.b.gok), L.b.groups, group, count, h_stats, list, st);
+    int rc = failing_groups(reinterpret_cast<const uint32_t*>(ws + L.b.gok), L.b.groups, a.group, a.count, a.stats, list, st);
     if (rc) return rc;
-    return exact_pass(v, own(v), d_points, d_scalars, d_challenges, list, d_out_verdicts, ws, L.b, workspace_bytes, st);
+    return exact_pass(v, own(v), a.points, a.scalars, a.challenges, list, a.ok, ws, L.b, workspace_bytes, st);
 }
 
 // Pass 1: per class present, today's front end over the class's region with the class's view -- the proof points from the
@@ -1292,75 +1237,73 @@ int VerifyImpl<C>::grouped_mixed_core(bpp_verifier* v, const MixedPlan& p, size_
 }
 
 template <class C>
-int VerifyImpl<C>::run_grouped_mixed(bpp_verifier* v, const uint64_t* d_points, const uint64_t* d_scalars,
-                                     const uint32_t* m_of, size_t count, const uint64_t* d_challenges,
-                                     const uint8_t* weight_key, uint64_t index_base, const uint64_t* d_weights, uint32_t group,
-                                     uint32_t* d_out_verdicts, uint64_t* h_stats, void* d_workspace, size_t workspace_bytes,
+int VerifyImpl<C>::run_grouped_mixed(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes,
                                      hipStream_t st) {
+    const size_t count = a.count;
+    const uint32_t group = a.group;
     MixedPlan p;
-    int rc = mixed_plan(v->s, m_of, count, true, p);
+    int rc = mixed_plan(v->s, a.m_of, count, true, p);
     if (rc) return rc;
     rc = check_group(group);
     if (rc) return rc;
     const GroupMixedLayout L = group_mixed_layout(v, p, count, group, false);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
-    if (h_stats) h_stats[0] = h_stats[1] = 0;
+    if (a.stats) a.stats[0] = a.stats[1] = 0;
     if (count == 0) return BPP_OK;
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     uint32_t* w_idx = reinterpret_cast<uint32_t*>(ws + L.f.idx);
-    rc = gather_front(p, L.f, count, d_points, d_scalars, d_challenges, ws, st);
+    rc = gather_front(p, L.f, count, a.points, a.scalars, a.challenges, ws, st);
     if (rc) return rc;
     // one lane per caller position: its weight, stored at its gathered position
     WeightKey wk;
-    load_key_words(d_weights ? nullptr : weight_key, wk.w);
-    hipLaunchKernelGGL(k_comb_weights_mixed<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, wk, index_base,
-                       reinterpret_cast<const uint32_t*>(d_weights), w_idx, (uint32_t)MX_WORDS, (uint32_t)MX_WORDS,
+    load_key_words(a.weights ? nullptr : a.weight_key, wk.w);
+    hipLaunchKernelGGL(k_comb_weights_mixed<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, wk, a.index_base,
+                       reinterpret_cast<const uint32_t*>(a.weights), w_idx, (uint32_t)MX_WORDS, (uint32_t)MX_WORDS,
                        (uint32_t)MX_POS, reinterpret_cast<uint32_t*>(ws + L.weights), count);
     HIPCHK(hipGetLastError());
-    rc = grouped_mixed_core(v, p, count, group, d_challenges != nullptr, false, h_stats, ws, L, workspace_bytes, st);
+    rc = grouped_mixed_core(v, p, count, group, a.challenges != nullptr, false, a.stats, ws, L, workspace_bytes, st);
     if (rc) return rc;
     hipLaunchKernelGGL(k_mixed_scatter<C>, dim3(cdiv(count, 4)), dim3(256), 0, st, w_idx, count,
-                       reinterpret_cast<const uint32_t*>(ws + L.f.ok), nullptr, nullptr, d_out_verdicts, nullptr, nullptr);
+                       reinterpret_cast<const uint32_t*>(ws + L.f.ok), nullptr, nullptr, a.ok, nullptr, nullptr);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
 
 template <class C>
-int VerifyImpl<C>::run_serialized_grouped_mixed(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments,
-                                                const uint32_t* m_of, size_t count, bool transcript,
-                                                const uint8_t* weight_key, uint64_t index_base, uint32_t group, uint32_t* d_ok,
-                                                uint64_t* h_stats, void* d_workspace, size_t workspace_bytes, hipStream_t st,
-                                                uint32_t version) {
-    if (int rc = container_args_ok(v, version)) return rc;
+int VerifyImpl<C>::run_serialized_grouped_mixed(bpp_verifier* v, const VerifyArgs& a, void* d_workspace, size_t workspace_bytes,
+                                                hipStream_t st) {
+    const size_t count = a.count;
+    const uint32_t group = a.group;
+    if (int rc = container_args_ok(v, a.version)) return rc;
     MixedPlan p;
-    int rc = mixed_plan_serialized(v->s, m_of, count, (size_t)container_point_bytes<C>(version), true, p);
+    int rc = mixed_plan_serialized(v->s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), true, p);
     if (rc) return rc;
     rc = check_group(group);
     if (rc) return rc;
     const GroupMixedLayout L = group_mixed_layout(v, p, count, group, true);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
-    if (h_stats) h_stats[0] = h_stats[1] = 0;
+    if (a.stats) a.stats[0] = a.stats[1] = 0;
     if (count == 0) return BPP_OK;
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
-    rc = decode_front(p, L.f, count, d_proofs, d_commitments, version, ws, st);
+    rc = decode_front(p, L.f, count, a.proofs, a.commitments, a.version, ws, st);
     if (rc) return rc;
     // one lane per gathered position: the weight of its caller position
     WeightKey wk;
-    load_key_words(weight_key, wk.w);
-    hipLaunchKernelGGL(k_comb_weights_mixed<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, wk, index_base,
+    load_key_words(a.weight_key, wk.w);
+    hipLaunchKernelGGL(k_comb_weights_mixed<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, wk, a.index_base,
                        (const uint32_t*)nullptr, W(L.f.idx), (uint32_t)SX_WORDS, (uint32_t)SX_CALLER, (uint32_t)SX_WORDS,
                        W(L.weights), count);
     HIPCHK(hipGetLastError());
-    if (transcript) {
+    if (a.fs) {
         rc = for_each_class(v, p, L.f, ws, [&](const ClassView& cv) {
             return derive_challenges(v, cv.ps, cv.pts, cv.count, cv.challenges, st);
         });
         if (rc) return rc;
     }
-    rc = grouped_mixed_core(v, p, count, group, transcript, true, h_stats, ws, L, workspace_bytes, st);
+    rc = grouped_mixed_core(v, p, count, group, a.fs, true, a.stats, ws, L, workspace_bytes, st);
     if (rc) return rc;
-    return scatter_verdicts(L.f, ws, d_ok, count, st);
+    return scatter_verdicts(L.f, ws, a.ok, count, st);
 }
 
 template <class C>
@@ -1371,100 +1314,59 @@ int VerifyImpl<C>::sum_partials(const uint32_t* d_partials, size_t n, uint32_t* 
     return BPP_OK;
 }
 
+// 1. the byte sizes of the two inputs and of the workspace for the form, 2. upload, 3. the device entry, 4. download
 template <class C>
-int VerifyImpl<C>::verify_batch_host(bpp_verifier* v, const uint64_t* points, const uint64_t* scalars, size_t count,
-                                     uint32_t* out_ok) {
-    const size_t wsb = ws_layout(v->s, count).total;
-    DevBuf dp, ds, dok, dws;
-    HIPCHK(dp.upload(points, count * v->s.NV * WW * 4));
-    HIPCHK(ds.upload(scalars, count * 96));
-    HIPCHK(dok.alloc(count * 4));
-    HIPCHK(dws.alloc(wsb));
-    BPP_TRY(bpp_verifier_run(v, dp.u64(), ds.u64(), count, nullptr, dok.u32(), dws.p, wsb, nullptr, nullptr, nullptr));
-    HIPCHK(dok.download(out_ok, count * 4));
-    return BPP_OK;
-}
-
-template <class C>
-int VerifyImpl<C>::verify_batch_mixed_host(bpp_verifier* v, const uint64_t* points, const uint64_t* scalars, const uint32_t* m_of,
-                                           size_t count, uint32_t* out_ok) {
-    const size_t wsb = mixed_workspace_bytes(v, m_of, count);
-    if (!wsb) {   // an m_i the verifier does not take: the plan names the proof
-        MixedPlan p;
-        const int rc = mixed_plan(v->s, m_of, count, false, p);
-        return rc ? rc : fail(BPP_E_ARG, "mixed batch rejected");
+int VerifyImpl<C>::verify_host(bpp_verifier* v, const VerifyArgs& a, HostForm form, int flags) {
+    const VerifyShape& s = v->s;
+    const size_t count = a.count, npts = count * s.NV, cb = (size_t)container_point_bytes<C>(a.version);
+    size_t in0 = npts * WW * 4, in1 = count * 96, wsb = ws_layout(s, count).total;
+    MixedPlan p;
+    if (form == HOST_MIXED) {
+        wsb = mixed_workspace_bytes(v, a.m_of, count);
+        if (!wsb) {   // an m_i the verifier does not take: the plan names the proof
+            const int rc = mixed_plan(s, a.m_of, count, false, p);
+            return rc ? rc : fail(BPP_E_ARG, "mixed batch rejected");
+        }
+        const uint32_t logn = s.k - (uint32_t)__builtin_ctz(s.m);
+        in0 = 0;
+        for (size_t i = 0; i < count; i++) in0 += (size_t)(3 + 2 * (logn + (uint32_t)__builtin_ctz(a.m_of[i])) + a.m_of[i]) * WW * 4;
+    } else if (form == HOST_COMPRESSED) {
+        in0 = npts * compressed_bytes<C>();
+    } else if (form == HOST_SERIALIZED) {
+        in0 = count * container_bytes<C>(s.k, a.version), in1 = count * s.m * cb, wsb = ser_layout(s, count).total;
+    } else if (form == HOST_SERIALIZED_MIXED) {
+        wsb = bpp_verifier_serialized_mixed_workspace_bytes(v, a.m_of, count);
+        const int rc = mixed_plan_serialized(s, a.m_of, count, cb, false, p);   // its byte totals size the uploads
+        if (rc || !wsb) return rc ? rc : fail(BPP_E_ARG, "serialized mixed batch rejected");   // an m_i the verifier does not take
+        in0 = p.proof_bytes, in1 = p.comm_bytes;
     }
-    size_t npts = 0;
-    const uint32_t logn = v->s.k - (uint32_t)__builtin_ctz(v->s.m);
-    for (size_t i = 0; i < count; i++) npts += 3 + 2 * (logn + (uint32_t)__builtin_ctz(m_of[i])) + m_of[i];
-    DevBuf dp, ds, dok, dws;
-    HIPCHK(dp.upload(points, npts * WW * 4));
-    HIPCHK(ds.upload(scalars, count * 96));
+    DevBuf d0, d1, dok, dws, dp, dk;
+    HIPCHK(d0.upload(a.points ? (const void*)a.points : a.proofs, in0));
+    HIPCHK(d1.upload(a.scalars ? (const void*)a.scalars : a.commitments, in1));
     HIPCHK(dok.alloc(count * 4));
     HIPCHK(dws.alloc(wsb));
-    BPP_TRY(bpp_verifier_run_mixed(v, dp.u64(), ds.u64(), m_of, count, nullptr, dok.u32(), dws.p, wsb, nullptr, nullptr));
-    HIPCHK(dok.download(out_ok, count * 4));
-    return BPP_OK;
-}
-
-template <class C>
-int VerifyImpl<C>::verify_batch_compressed_host(bpp_verifier* v, const uint8_t* records, const uint64_t* scalars, size_t count,
-                                                uint32_t* out_ok) {
-    const size_t wsb = ws_layout(v->s, count).total, npts = count * v->s.NV;
+    if (form == HOST_COMPRESSED) {
+        HIPCHK(dp.alloc(npts * WW * 4));
+        HIPCHK(dk.alloc(npts * 4));
+        // the one wire entry point for points of unknown origin besides the container: reject what is outside the
+        // prime-order group too (the verifier's GLV evaluation equals s * P only there, include/bpp_amd.h)
+        BPP_TRY(bpp_points_decompress_device(&v->ctx, d0.p, npts, dp.u64(), dk.u32(), 1, nullptr));
+    }
+    const bool flat = form == HOST_WIRE || form == HOST_COMPRESSED;
+    BPP_TRY(flat ? bpp_verifier_run(v, form == HOST_WIRE ? d0.u64() : dp.u64(), d1.u64(), count, nullptr, dok.u32(), dws.p, wsb, nullptr, nullptr, nullptr)
+            : form == HOST_MIXED ? bpp_verifier_run_mixed(v, d0.u64(), d1.u64(), a.m_of, count, nullptr, dok.u32(), dws.p, wsb, nullptr, nullptr)
+            : form == HOST_SERIALIZED ? bpp_range_verify_batch_serialized_device(v, d0.p, d1.p, count, flags, dok.u32(), dws.p, wsb, nullptr)
+                                      : bpp_range_verify_batch_serialized_mixed_device(v, d0.p, d1.p, a.m_of, count, flags, dok.u32(), dws.p, wsb, nullptr));
+    HIPCHK(dok.download(a.ok, count * 4));
+    if (form != HOST_COMPRESSED) return BPP_OK;
     std::vector<uint32_t> bad(npts);
-    DevBuf db, ds, dp, dk, dok, dws;
-    HIPCHK(db.upload(records, npts * compressed_bytes<C>()));
-    HIPCHK(ds.upload(scalars, count * 96));
-    HIPCHK(dok.alloc(count * 4));
-    HIPCHK(dws.alloc(wsb));
-    HIPCHK(dp.alloc(npts * WW * 4));
-    HIPCHK(dk.alloc(npts * 4));
-    // the one wire entry point for points of unknown origin besides the container: reject what is outside the
-    // prime-order group too (the verifier's GLV evaluation equals s * P only there, include/bpp_amd.h)
-    BPP_TRY(bpp_points_decompress_device(&v->ctx, db.p, npts, dp.u64(), dk.u32(), 1, nullptr));
-    BPP_TRY(bpp_verifier_run(v, dp.u64(), ds.u64(), count, nullptr, dok.u32(), dws.p, wsb, nullptr, nullptr, nullptr));
     HIPCHK(dk.download(bad.data(), npts * 4));
-    HIPCHK(dok.download(out_ok, count * 4));
     for (size_t i = 0; i < npts; i++)
-        if (bad[i]) out_ok[i / v->s.NV] = BPP_FORMAT_ERROR;   // a malformed encoding / a point outside the group: ProofError::FormatError
+        if (bad[i]) a.ok[i / s.NV] = BPP_FORMAT_ERROR;   // a malformed encoding / a point outside the group: ProofError::FormatError
     // ... and so does a non-canonical scalar (r', s' or delta' >= the group order): a serialized proof has one encoding
     // (little-endian host: the u64 limbs are the bytes)
     for (size_t i = 0; i < count * 3; i++)
-        if (!scalar_is_canonical<C>(reinterpret_cast<const uint8_t*>(scalars + i * 4))) out_ok[i / 3] = BPP_FORMAT_ERROR;
-    return BPP_OK;
-}
-
-template <class C>
-int VerifyImpl<C>::verify_batch_serialized_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, size_t count,
-                                                int flags, uint32_t* out_ok) {
-    const uint32_t version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
-    const size_t pb = container_bytes<C>(v->s.k, version), cb = (size_t)container_point_bytes<C>(version);
-    const size_t wsb = ser_layout(v->s, count).total;
-    DevBuf dpr, dcm, dok, dws;
-    HIPCHK(dpr.upload(proofs, count * pb));
-    HIPCHK(dcm.upload(commitments, count * v->s.m * cb));
-    HIPCHK(dok.alloc(count * 4));
-    HIPCHK(dws.alloc(wsb));
-    BPP_TRY(bpp_range_verify_batch_serialized_device(v, dpr.p, dcm.p, count, flags, dok.u32(), dws.p, wsb, nullptr));
-    HIPCHK(dok.download(out_ok, count * 4));
-    return BPP_OK;
-}
-
-template <class C>
-int VerifyImpl<C>::verify_batch_serialized_mixed_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments,
-                                                      const uint32_t* m_of, size_t count, int flags, uint32_t* out_ok) {
-    const size_t cb = (size_t)container_point_bytes<C>((flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u);
-    const size_t wsb = bpp_verifier_serialized_mixed_workspace_bytes(v, m_of, count);
-    MixedPlan p;
-    const int rc = mixed_plan_serialized(v->s, m_of, count, cb, false, p);   // its byte totals size the uploads
-    if (rc || !wsb) return rc ? rc : fail(BPP_E_ARG, "serialized mixed batch rejected");   // an m_i the verifier does not take
-    DevBuf dpr, dcm, dok, dws;
-    HIPCHK(dpr.upload(proofs, p.proof_bytes));
-    HIPCHK(dcm.upload(commitments, p.comm_bytes));
-    HIPCHK(dok.alloc(count * 4));
-    HIPCHK(dws.alloc(wsb));
-    BPP_TRY(bpp_range_verify_batch_serialized_mixed_device(v, dpr.p, dcm.p, m_of, count, flags, dok.u32(), dws.p, wsb, nullptr));
-    HIPCHK(dok.download(out_ok, count * 4));
+        if (!scalar_is_canonical<C>(reinterpret_cast<const uint8_t*>(a.scalars + i * 4))) a.ok[i / 3] = BPP_FORMAT_ERROR;
     return BPP_OK;
 }
 
