@@ -896,6 +896,127 @@ impl BatchVerifier {
             .collect();
         Ok((ok, hits, found as usize, candidates as usize))
     }
+
+    /// The byte counts of a ragged block (include/bpp_amd.h: "proofs over ANY number of outputs"): proof i covers outs[i]
+    /// outputs, 1 <= outs[i] <= m, has the container of shape (n, 2^ceil(log2 outs[i])) and outs[i] encoded commitments.
+    /// -> (container bytes, commitment bytes, outputs); Err(FormatError) for a count that is not taken.
+    fn outs_bytes(&self, outs: &[u32]) -> Result<(usize, usize, usize), ProofError> {
+        let n = 1usize << (self.k - self.m.trailing_zeros() as usize);
+        let cb = unsafe { ffi::bpp_point_compressed_bytes(ffi::BPP_BLS12_381_G1) };
+        let ms = outs_shapes(outs, self.m)?;
+        let (mut pbytes, mut n_out) = (0usize, 0usize);
+        for (&mi, &o) in ms.iter().zip(outs) {
+            pbytes += unsafe { ffi::bpp_proof_bytes(ffi::BPP_BLS12_381_G1, n, mi as usize) };
+            n_out += o as usize;
+        }
+        Ok((pbytes, n_out * cb, n_out))
+    }
+    /// Proves a block whose proofs cover ANY number of outputs (include/bpp_amd.h: bpp_range_prove_batch_serialized_outs):
+    /// values[i], gammas[i] hold the 1..m values and masks of proof i, which is the proof of shape (n, 2^ceil(log2 len))
+    /// over them padded with zeros.  -> (containers back to back, outs[i] encoded commitments per proof back to back, outs).
+    pub fn prove_serialized_outputs(&self, values: &[Vec<u64>], gammas: &[Vec<PrimeFieldElem>], transcript: bool, amount64: bool)
+                                    -> Result<(Vec<u8>, Vec<u8>, Vec<u32>), ProofError> {
+        if values.len() != gammas.len() || values.iter().zip(gammas).any(|(v, g)| v.len() != g.len()) {
+            return Err(ProofError::FormatError);
+        }
+        let outs: Vec<u32> = values.iter().map(|v| v.len() as u32).collect();
+        let (pbytes, cbytes, _) = self.outs_bytes(&outs)?;
+        if outs.is_empty() {
+            return Ok((Vec::new(), Vec::new(), outs));
+        }
+        let vs: Vec<u64> = values.iter().flatten().copied().collect();
+        let gs: Vec<PrimeFieldElem> = gammas.iter().flatten().copied().collect();
+        let gw = flat_scalars(&gs);
+        let (mut proofs, mut commitments) = (vec![0u8; pbytes], vec![0u8; cbytes]);
+        let flags = if transcript { ffi::BPP_SER_TRANSCRIPT } else { 0 } | if amount64 { ffi::BPP_PROVE_AMOUNT64 } else { 0 };
+        let rc = unsafe {
+            ffi::bpp_range_prove_batch_serialized_outs(self.handle, vs.as_ptr(), gw.as_ptr(), outs.as_ptr(), outs.len(), flags,
+                                                       std::ptr::null(), 0, proofs.as_mut_ptr(), commitments.as_mut_ptr())
+        };
+        assert!(rc == 0, "bpp_range_prove_batch_serialized_outs: {}", rc);
+        Ok((proofs, commitments, outs))
+    }
+    /// Verifies such a block (include/bpp_amd.h: bpp_range_verify_batch_serialized_outs): `commitments` holds outs[i]
+    /// encoded points per proof; the padded ones are the identity and are not in the stream.  Err(FormatError) when a
+    /// count is not taken or a length is not what `outs` implies: nothing then reaches the engine.
+    pub fn verify_serialized_outputs(&self, proofs: &[u8], commitments: &[u8], outs: &[u32], transcript: bool)
+                                     -> Result<Vec<Result<(), ProofError>>, ProofError> {
+        let (pbytes, cbytes, _) = self.outs_bytes(outs)?;
+        if pbytes != proofs.len() || cbytes != commitments.len() {
+            return Err(ProofError::FormatError);
+        }
+        if outs.is_empty() {
+            return Ok(Vec::new());
+        }
+        let mut ok = vec![0u32; outs.len()];
+        let flags = if transcript { ffi::BPP_SER_TRANSCRIPT } else { 0 };
+        let rc = unsafe {
+            ffi::bpp_range_verify_batch_serialized_outs(self.handle, proofs.as_ptr(), commitments.as_ptr(), outs.as_ptr(), outs.len(),
+                                                        flags, ok.as_mut_ptr())
+        };
+        assert!(rc == 0, "bpp_range_verify_batch_serialized_outs: {}", rc);
+        Ok(ok.iter().map(|&v| match v {
+            0 => Ok(()),
+            2 => Err(ProofError::FormatError),
+            _ => Err(ProofError::VerificationError),
+        }).collect())
+    }
+    /// verify_find_outputs_serialized_mixed_keys over such a block (include/bpp_amd.h:
+    /// bpp_range_verify_find_outputs_serialized_outs_keys): `sealed` and `tags` hold one entry per REAL output (the sum of
+    /// `outs`), and the output numbers of the hits count real outputs only.
+    pub fn verify_find_outputs_serialized_outs_keys(&self, proofs: &[u8], commitments: &[u8], outs: &[u32], amount64: bool,
+                                                    keys: &[[u8; 32]], index_base: u64, index: Option<&[u64]>, sealed: &[u64],
+                                                    tags: &[u8], max_hits: usize)
+                                                    -> Result<(Vec<u32>, Vec<(u32, u32, u64, PrimeFieldElem)>, usize, usize), ProofError> {
+        let (pbytes, cbytes, n_out) = self.outs_bytes(outs)?;
+        let pairs = match keys.len().checked_mul(n_out) {
+            Some(p) if p <= (0x7fff_ffff / 64) => p,
+            _ => return Err(ProofError::FormatError),
+        };
+        if pbytes != proofs.len() || cbytes != commitments.len() || index.map_or(false, |x| x.len() != outs.len())
+            || sealed.len() != n_out || tags.len() != n_out {
+            return Err(ProofError::FormatError);
+        }
+        if outs.is_empty() {
+            return Ok((Vec::new(), Vec::new(), 0, 0));
+        }
+        let flags = ffi::BPP_SER_TRANSCRIPT | if amount64 { ffi::BPP_PROVE_AMOUNT64 } else { 0 };
+        let cap = max_hits.min(pairs);
+        let mut packed: Vec<u8> = keys.iter().flat_map(|k| k.iter().copied()).collect();
+        let mut ok = vec![0u32; outs.len()];
+        let mut rec = vec![0u32; cap * 12];
+        let (mut found, mut candidates) = (0u32, 0u32);
+        let rc = unsafe {
+            ffi::bpp_range_verify_find_outputs_serialized_outs_keys(self.handle, proofs.as_ptr(), commitments.as_ptr(), outs.as_ptr(),
+                                                                    outs.len(), flags, packed.as_ptr(), keys.len(), index_base,
+                                                                    index.map_or(std::ptr::null(), |x| x.as_ptr()), sealed.as_ptr(),
+                                                                    tags.as_ptr(), ok.as_mut_ptr(),
+                                                                    if cap > 0 { rec.as_mut_ptr() } else { std::ptr::null_mut() },
+                                                                    cap, &mut found, &mut candidates)
+        };
+        for b in packed.iter_mut() {
+            unsafe { std::ptr::write_volatile(b, 0) };   // the packed copy of the keys made here
+        }
+        assert!(rc == 0, "bpp_range_verify_find_outputs_serialized_outs_keys: {}", rc);
+        let hits = rec.chunks(12).take((found as usize).min(cap))
+            .map(|h| {
+                let w = |t: usize| h[4 + 2 * t] as u64 | (h[5 + 2 * t] as u64) << 32;
+                (h[0], h[1], h[2] as u64 | (h[3] as u64) << 32, PrimeFieldElem([w(0), w(1), w(2), w(3)]))
+            })
+            .collect();
+        Ok((ok, hits, found as usize, candidates as usize))
+    }
+}
+
+/// The aggregation sizes of proofs over `outs[i]` outputs for an engine of capacity `m` (include/bpp_amd.h:
+/// bpp_outs_shapes): 2^ceil(log2 outs[i]).  Err(FormatError) for a count of zero or above `m`.  Host code, no device.
+pub fn outs_shapes(outs: &[u32], m: usize) -> Result<Vec<u32>, ProofError> {
+    let mut ms = vec![0u32; outs.len()];
+    let rc = unsafe { ffi::bpp_outs_shapes(outs.as_ptr(), outs.len(), m, ms.as_mut_ptr()) };
+    if rc != 0 {
+        return Err(ProofError::FormatError);
+    }
+    Ok(ms)
 }
 
 /// The cuts of a batch over `world` shards (include/bpp_amd.h: bpp_shard_cuts): shard r takes proofs

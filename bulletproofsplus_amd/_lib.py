@@ -65,6 +65,14 @@ EXPORTS = [
     "bpp_outputs_make_device", "bpp_outputs_make",
     "bpp_verify_find_outputs_workspace_bytes", "bpp_range_verify_find_outputs_serialized_mixed_keys_device",
     "bpp_range_verify_find_outputs_serialized_mixed_keys",
+    "bpp_outs_shapes",
+    "bpp_prover_serialized_outs_workspace_bytes", "bpp_range_prove_batch_serialized_outs_device",
+    "bpp_range_prove_batch_serialized_outs",
+    "bpp_verifier_serialized_outs_workspace_bytes", "bpp_range_verify_batch_serialized_outs_device",
+    "bpp_range_verify_batch_serialized_outs",
+    "bpp_verifier_serialized_grouped_outs_workspace_bytes", "bpp_range_verify_batch_serialized_grouped_outs_device",
+    "bpp_verify_find_outputs_outs_workspace_bytes", "bpp_range_verify_find_outputs_serialized_outs_keys_device",
+    "bpp_range_verify_find_outputs_serialized_outs_keys",
     "bpp_wip_prover_workspace_bytes", "bpp_wip_prove_batch_device", "bpp_wip_verifier_workspace_bytes",
     "bpp_wip_verify_batch_device", "bpp_wip_prove_batch", "bpp_wip_verify_batch",
     "bpp_shard_cuts", "bpp_pool_create", "bpp_pool_destroy", "bpp_pool_size", "bpp_pool_device", "bpp_pool_verifier",
@@ -238,6 +246,23 @@ def lib():
                                                                                  vp, vp, sz, vp, vp, vp, sz, vp]
         L.bpp_range_verify_find_outputs_serialized_mixed_keys.argtypes = [vp, vp, vp, vp, sz, i32, vp, sz, u64, vp, vp, vp, vp,
                                                                           vp, sz, vp, vp]
+        # the ragged forms: the argument lists of the serialized mixed calls, outs_of in m_of's place
+        L.bpp_outs_shapes.argtypes = [vp, sz, sz, vp]
+        L.bpp_prover_serialized_outs_workspace_bytes.argtypes = L.bpp_prover_serialized_mixed_workspace_bytes.argtypes
+        L.bpp_prover_serialized_outs_workspace_bytes.restype = sz
+        L.bpp_range_prove_batch_serialized_outs_device.argtypes = L.bpp_range_prove_batch_serialized_mixed_device.argtypes
+        L.bpp_range_prove_batch_serialized_outs.argtypes = L.bpp_range_prove_batch_serialized_mixed.argtypes
+        L.bpp_verifier_serialized_outs_workspace_bytes.argtypes = L.bpp_verifier_serialized_mixed_workspace_bytes.argtypes
+        L.bpp_verifier_serialized_outs_workspace_bytes.restype = sz
+        L.bpp_range_verify_batch_serialized_outs_device.argtypes = L.bpp_range_verify_batch_serialized_mixed_device.argtypes
+        L.bpp_range_verify_batch_serialized_outs.argtypes = L.bpp_range_verify_batch_serialized_mixed.argtypes
+        L.bpp_verifier_serialized_grouped_outs_workspace_bytes.argtypes = L.bpp_verifier_serialized_grouped_mixed_workspace_bytes.argtypes
+        L.bpp_verifier_serialized_grouped_outs_workspace_bytes.restype = sz
+        L.bpp_range_verify_batch_serialized_grouped_outs_device.argtypes = L.bpp_range_verify_batch_serialized_grouped_mixed_device.argtypes
+        L.bpp_verify_find_outputs_outs_workspace_bytes.argtypes = L.bpp_verify_find_outputs_workspace_bytes.argtypes
+        L.bpp_verify_find_outputs_outs_workspace_bytes.restype = sz
+        L.bpp_range_verify_find_outputs_serialized_outs_keys_device.argtypes = L.bpp_range_verify_find_outputs_serialized_mixed_keys_device.argtypes
+        L.bpp_range_verify_find_outputs_serialized_outs_keys.argtypes = L.bpp_range_verify_find_outputs_serialized_mixed_keys.argtypes
         L.bpp_proofs_scan.argtypes = [i32, sz, i32, vp, sz, vp, sz, vp]
         L.bpp_wip_prover_workspace_bytes.argtypes = [vp, sz]
         L.bpp_wip_prover_workspace_bytes.restype = sz

@@ -1670,6 +1670,179 @@ class BatchVerifier(_Shapes):
         n = int(found[0])
         return ok, _hits(rec, n), n, int(cands[0])
 
+    # ---- proofs over any number of outputs (include/bpp_amd.h "proofs over ANY number of outputs") ----
+    def _outs(self, outs) -> np.ndarray:
+        return np.ascontiguousarray(outs, dtype=np.uint32).reshape(-1)
+
+    def _outs_taken(self, outs) -> bool:
+        return all(0 < int(x) <= self.m for x in outs)
+
+    def _outs_block(self, where: str, proofs, commitments, outs, uncompressed: bool):
+        """_block for a ragged block: containers of the shapes outs_shapes names, outs[i] encoded commitments per proof
+        -> (raw u8, cm u8, outs u32, count)"""
+        raw, cm, o = _flat_bytes(proofs), _flat_bytes(commitments), self._outs(outs)
+        if self._outs_taken(o):
+            version = 2 if uncompressed else 1
+            need = sum(proof_bytes(self.arith, self.n, int(x), version) for x in outs_shapes(o, self.m))
+            if len(raw) != need:
+                raise RuntimeError("%s: %d bytes of proofs, the shapes of outs need %d" % (where, len(raw), need))
+            if len(cm) != int(o.sum()) * (uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)):
+                raise RuntimeError("%s: outs[i] commitments per proof" % where)
+        return raw, cm, o, len(o)
+
+    def prover_serialized_outs_workspace_bytes(self, outs) -> int:
+        """bytes of device workspace prove_serialized_outputs_device needs (0: a count is not taken)"""
+        o = self._outs(outs)
+        return _lib.lib().bpp_prover_serialized_outs_workspace_bytes(self.handle, _some(o), len(o))
+
+    def prove_serialized_outputs_device(self, d_values: int, d_gammas: int, outs, d_out_proofs: int, d_out_commitments: int,
+                                        d_workspace: int, workspace_bytes: int, stream: int = 0, transcript: bool = False,
+                                        uncompressed: bool = False, blind_key: bytes = None, index_base: int = 0,
+                                        d_blinding: int = 0, amount64: bool = False):
+        """prove_serialized_mixed_device over a ragged block: proof i has outs[i] values and gammas (any count 1..m) at
+        d_values / d_gammas, sum(outs) in all, and gets the container of shape (n, outs_shapes(outs)[i]) and outs[i] encoded
+        commitments: the two inputs of verify_serialized_outputs_device"""
+        o = self._outs(outs)
+        check(_lib.lib().bpp_range_prove_batch_serialized_outs_device(
+            self.handle, d_values, d_gammas, _some(o), len(o), _flags(transcript, uncompressed, amount64), blind_key,
+            ctypes.c_uint64(index_base), d_blinding or None,
+            d_out_proofs, d_out_commitments, d_workspace, workspace_bytes, stream or None),
+            "bpp_range_prove_batch_serialized_outs_device")
+
+    def prove_serialized_outputs(self, values, gammas, transcript: bool = False, blind_key: bytes = None, index_base: int = 0,
+                                 uncompressed: bool = False, amount64: bool = False):
+        """values[i], gammas[i]: the values and gammas of proof i, ANY number 1..m of them -> (proofs, commitments, outs):
+        proof i is the proof of shape (n, M), M = 2^ceil(log2 outs[i]), over its values and gammas padded with zeros; the
+        containers back to back, outs[i] encoded commitments per proof back to back (the padded ones are the identity and
+        are not written) -- what verify_serialized_outputs takes"""
+        _prover_key(blind_key, transcript)
+        vals, gm, outs = self._mixed_inputs(values, gammas)
+        count, version = len(outs), 2 if uncompressed else 1
+        pb = uncompressed_bytes(self.arith) if uncompressed else compressed_bytes(self.arith)
+        taken = self._outs_taken(outs) and pb
+        nbytes = sum(proof_bytes(self.arith, self.n, int(x), version) for x in outs_shapes(outs, self.m)) if taken else 0
+        raw = np.zeros(max(nbytes, 1), dtype=np.uint8)
+        cm = np.zeros(max(int(outs.sum()) * pb, 1), dtype=np.uint8)
+        check(_lib.lib().bpp_range_prove_batch_serialized_outs(
+            self.handle, _some(vals), _some(gm), _some(outs), count, _flags(transcript, uncompressed, amount64), blind_key,
+            ctypes.c_uint64(index_base), _ptr(raw), _ptr(cm)), "bpp_range_prove_batch_serialized_outs")
+        return raw[:nbytes].tobytes(), cm[:int(outs.sum()) * pb].tobytes(), outs
+
+    def serialized_outs_workspace_bytes(self, outs, group: int = None) -> int:
+        """bytes of device workspace verify_serialized_outputs_device needs, with `group` for its grouped form (0: a count
+        or the group is not taken)"""
+        o = self._outs(outs)
+        if group is None:
+            return _lib.lib().bpp_verifier_serialized_outs_workspace_bytes(self.handle, _some(o), len(o))
+        return _lib.lib().bpp_verifier_serialized_grouped_outs_workspace_bytes(self.handle, _some(o), len(o), group)
+
+    def verify_serialized_outputs_device(self, d_proofs: int, d_commitments: int, outs, d_ok: int, d_workspace: int,
+                                         workspace_bytes: int, stream: int = 0, transcript: bool = False,
+                                         uncompressed: bool = False, group: int = None, weight_key: bytes = None,
+                                         index_base: int = 0):
+        """verify_serialized_mixed_device over a ragged block: container i of the shape outs_shapes names, outs[i] encoded
+        commitments per proof; the padded commitments are the identity and are neither read nor decompressed.  group given:
+        the grouped check behind the same front (weight_key, index_base as verify_serialized_grouped_mixed_device;
+        synchronises the stream) -> (groups that failed, proofs re-verified exactly), else None"""
+        o = self._outs(outs)
+        if group is None:
+            check(_lib.lib().bpp_range_verify_batch_serialized_outs_device(
+                self.handle, d_proofs, d_commitments, _some(o), len(o), _flags(transcript, uncompressed),
+                d_ok, d_workspace, workspace_bytes, stream or None), "bpp_range_verify_batch_serialized_outs_device")
+            return None
+        stats = (ctypes.c_uint64 * 2)()
+        check(_lib.lib().bpp_range_verify_batch_serialized_grouped_outs_device(
+            self.handle, d_proofs, d_commitments, _some(o), len(o), _flags(transcript, uncompressed),
+            _weight_key_arg(weight_key, 0), ctypes.c_uint64(index_base), group, d_ok, stats, d_workspace, workspace_bytes,
+            stream or None), "bpp_range_verify_batch_serialized_grouped_outs_device")
+        return int(stats[0]), int(stats[1])
+
+    def verify_serialized_outputs(self, proofs, commitments, outs, transcript: bool = False, uncompressed: bool = False,
+                                  group: int = None) -> np.ndarray:
+        """proofs: the containers back to back; commitments: outs[i] encoded points per proof back to back; outs: the
+        output count of each proof -> status (count,) u32: 0 Ok / 1 VerificationError / 2 FormatError.  group given: through
+        the grouped check (the device form between copies, under a fresh weight key)"""
+        raw, cm, o, count = self._outs_block("verify_serialized_outputs", proofs, commitments, outs, uncompressed)
+        ok = np.zeros(count, dtype=np.uint32)
+        if group is None:
+            check(_lib.lib().bpp_range_verify_batch_serialized_outs(
+                self.handle, _some(raw), _some(cm), _some(o), count, _flags(transcript, uncompressed), _some(ok)),
+                "bpp_range_verify_batch_serialized_outs")
+            return ok
+        if count == 0:
+            return ok
+        import torch
+        wsb = self.serialized_outs_workspace_bytes(o, group)
+        if not wsb:
+            check(_lib.lib().bpp_outs_shapes(_some(o), count, self.m, _some(np.zeros(count, dtype=np.uint32))), "bpp_outs_shapes")
+            raise RuntimeError("verify_serialized_outputs: group must be a power of two, at least 2")
+        dev = torch.device("cuda", self.arith.device)
+        d_raw = torch.from_numpy(raw.copy()).to(dev)
+        d_cm = torch.from_numpy(cm.copy()).to(dev)
+        d_ok = torch.zeros(count, dtype=torch.int32, device=dev)
+        d_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        self.verify_serialized_outputs_device(d_raw.data_ptr(), d_cm.data_ptr(), o, d_ok.data_ptr(), d_ws.data_ptr(), wsb,
+                                              transcript=transcript, uncompressed=uncompressed, group=group)
+        torch.cuda.synchronize(dev)
+        return d_ok.cpu().numpy().astype(np.uint32)
+
+    def verify_find_outputs_outs_workspace_bytes(self, outs, n_keys: int) -> int:
+        """bytes of device workspace verify_find_outputs_serialized_outs_keys_device needs (0: a count is not taken, or
+        n_keys x sum(outs) is over the bound)"""
+        o = self._outs(outs)
+        return _lib.lib().bpp_verify_find_outputs_outs_workspace_bytes(self.handle, _some(o), len(o), n_keys)
+
+    def verify_find_outputs_serialized_outs_keys_device(self, d_proofs: int, d_commitments: int, outs, d_keys: int, n_keys: int,
+                                                        d_sealed: int, d_tags: int, d_ok: int, d_hits: int, max_hits: int,
+                                                        d_n_hits: int, d_workspace: int, workspace_bytes: int, stream: int = 0,
+                                                        uncompressed: bool = False, amount64: bool = False, index_base: int = 0,
+                                                        d_index: int = 0, d_n_candidates: int = 0):
+        """verify_find_outputs_serialized_mixed_keys_device over a ragged block: d_sealed, d_tags per REAL output
+        (sum(outs) of each), output numbers in the hit records count real outputs only"""
+        o = self._outs(outs)
+        check(_lib.lib().bpp_range_verify_find_outputs_serialized_outs_keys_device(
+            self.handle, d_proofs, d_commitments, _some(o), len(o), _flags(True, uncompressed, amount64), d_keys or None, n_keys,
+            ctypes.c_uint64(index_base), d_index or None, d_sealed or None, d_tags or None, d_ok or None, d_hits or None, max_hits,
+            d_n_hits or None, d_n_candidates or None, d_workspace, workspace_bytes, stream or None),
+            "bpp_range_verify_find_outputs_serialized_outs_keys_device")
+
+    def verify_find_outputs_serialized_outs_keys(self, proofs, commitments, outs, keys=(), sealed=(), tags=(),
+                                                 uncompressed: bool = False, amount64: bool = False, index_base: int = 0,
+                                                 index=None, max_hits: int = None):
+        """verify_find_outputs_serialized_mixed_keys over a ragged block: outs[i] commitments, sealed amounts and tags per
+        proof, sum(outs) of each -> (ok, hits, found, n_candidates), output numbers counting real outputs only
+        (bpp_range_verify_find_outputs_serialized_outs_keys)"""
+        where = "verify_find_outputs_serialized_outs_keys"
+        with _packed_keys(where, keys) as (kb, nk):
+            raw, cm, o, count = self._outs_block(where, proofs, commitments, outs, uncompressed)
+            n_out = int(o.sum())
+            idx = _index_arg(index, count, where + ": one blinding index per proof")
+            se, tg = _amounts_arg(sealed), _tags_arg(tags)
+            if nk and (len(se) != n_out or len(tg) != n_out):
+                raise RuntimeError(where + ": one sealed amount and one tag per output")
+            cap = nk * n_out if max_hits is None else int(max_hits)
+            ok = np.zeros(count, dtype=np.uint32)
+            rec = np.zeros((cap, 12), dtype=np.uint32)
+            found = np.zeros(1, dtype=np.uint32)
+            cands = np.zeros(1, dtype=np.uint32)
+            some = nk > 0 and count > 0
+            check(_lib.lib().bpp_range_verify_find_outputs_serialized_outs_keys(
+                self.handle, _some(raw), _some(cm), _some(o), count, _flags(True, uncompressed, amount64), _ptr(kb), nk,
+                ctypes.c_uint64(index_base), _ptr(idx), _ptr(se) if some else None, _ptr(tg) if some else None, _some(ok),
+                _some(rec), cap, _ptr(found), _ptr(cands)), "bpp_range_verify_find_outputs_serialized_outs_keys")
+        n = int(found[0])
+        return ok, _hits(rec, n), n, int(cands[0])
+
+
+def outs_shapes(outs, m: int) -> np.ndarray:
+    """bpp_outs_shapes: the aggregation size of a proof over outs[i] outputs, 2^ceil(log2 outs[i]), for an engine of
+    capacity m; BppError naming i for a count of zero or above m.  Host only."""
+    o = np.ascontiguousarray(outs, dtype=np.uint32).reshape(-1)
+    ms = np.zeros(len(o), dtype=np.uint32)
+    check(_lib.lib().bpp_outs_shapes(_some(o), len(o), m, _some(ms)), "bpp_outs_shapes")
+    return ms
+
 
 def shard_cuts(ms, count: int, world: int) -> np.ndarray:
     """bpp_shard_cuts: the world + 1 cuts of a batch of `count` proofs over `world` shards, shard r taking proofs

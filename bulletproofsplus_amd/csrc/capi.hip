@@ -1208,7 +1208,7 @@ int find_args(const bpp_verifier* v, int flags, FindArgs& a, bool device, const 
     a.amount64 = (flags & BPP_PROVE_AMOUNT64) != 0;
     a.sealed = per_output || (flags & BPP_FIND_AMOUNTS_SEALED) != 0;
     if (a.count == 0) return BPP_OK;
-    if (!a.proofs || !a.commitments || !a.m_of || !a.ok || (device && !d_workspace)) return fail(BPP_E_ARG, "null argument");
+    if (!a.proofs || !a.commitments || (!a.m_of && !a.outs_of) || !a.ok || (device && !d_workspace)) return fail(BPP_E_ARG, "null argument");
     if (a.n_keys && (!a.keys || !a.amounts || (a.tagged() && !a.tags) || (!a.hits && a.max_hits)))
         return fail(BPP_E_ARG, "null argument");
     if (device && a.n_keys && (reinterpret_cast<uintptr_t>(a.keys) & 3)) return fail(BPP_E_ARG, "d_keys must be 4-byte aligned");
@@ -1392,6 +1392,166 @@ extern "C" int bpp_range_verify_find_outputs_serialized_mixed_keys(
     if (int rc = find_args(v, flags, a, false, nullptr)) return rc;
     if (count == 0) return find_nothing(v, a, false, nullptr);
     if (int rc = scan_keys_args(m_of, count, n_keys, flags, true)) return rc;
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int { return OutputsImpl<decltype(cv)>::find_host(v, a); });
+}
+
+// ---- proofs over any number of outputs (outs_plan.hpp): proof i covers outs_of[i] outputs, is the proof of shape
+// (n, 2^ceil(log2 outs_of[i])) over values and masks padded with zeros, and the streams carry the real outputs alone.  The
+// entries of the serialized mixed calls with outs_of in m_of's place: the same records, the same checks, the same fronts ----
+namespace {
+// a count no engine takes (zero, or above the largest class): the size getters answer 0 before the handle is read;
+// outs_of is read only once count itself is within one launch
+bool outs_wellformed(const uint32_t* outs_of, size_t count) noexcept {
+    if ((count && !outs_of) || count > ONE_LAUNCH) return false;
+    for (size_t i = 0; i < count; i++)
+        if (outs_of[i] == 0 || outs_of[i] > (1u << (OUTS_CLASSES - 1))) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" int bpp_outs_shapes(const uint32_t* outs_of, size_t count, size_t cap_m, uint32_t* m_of_out) {
+    if (count && (!outs_of || !m_of_out)) return fail(BPP_E_ARG, "null argument");
+    return guarded({count, "count"}, [&] { return outs_shapes(outs_of, count, cap_m, m_of_out); });
+}
+
+extern "C" size_t bpp_prover_serialized_outs_workspace_bytes(const bpp_verifier* engine, const uint32_t* outs_of, size_t count) {
+    if (!outs_wellformed(outs_of, count)) return 0;
+    return size_for(engine, [&](auto cv) {
+        return ProveBatchImpl<decltype(cv)>::prove_mixed_workspace_bytes(engine, nullptr, count, true, outs_of);
+    });
+}
+
+extern "C" int bpp_range_prove_batch_serialized_outs_device(bpp_verifier* engine, const uint64_t* d_v, const uint64_t* d_gamma,
+                                                            const uint32_t* outs_of, size_t count, int flags,
+                                                            const uint8_t* blind_key, uint64_t index_base,
+                                                            const uint64_t* d_blinding, void* d_out_proofs,
+                                                            void* d_out_commitments, void* d_workspace, size_t workspace_bytes,
+                                                            void* stream) {
+    ProveArgs a;
+    a.values = d_v; a.gammas = d_gamma; a.outs_of = outs_of; a.count = count;
+    a.blind_key = blind_key; a.index_base = index_base; a.blinding = d_blinding;
+    a.out_proofs = static_cast<uint8_t*>(d_out_proofs); a.out_commitments = static_cast<uint8_t*>(d_out_commitments);
+    if (int rc = prove_args(engine, PROVE_SER_DEVICE, flags, a, d_v && d_gamma && outs_of && d_out_proofs && d_out_commitments && d_workspace))
+        return rc;
+    if (count == 0) return BPP_OK;
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int {
+        return ProveBatchImpl<decltype(cv)>::prove_device(engine, a, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    });
+}
+
+// host buffers in, host buffers out: the device path above between copies
+extern "C" int bpp_range_prove_batch_serialized_outs(bpp_verifier* engine, const uint64_t* v, const uint64_t* gamma,
+                                                     const uint32_t* outs_of, size_t count, int flags, const uint8_t* blind_key,
+                                                     uint64_t index_base, uint8_t* out_proofs, uint8_t* out_commitments) {
+    ProveArgs a;
+    a.values = v; a.gammas = gamma; a.outs_of = outs_of; a.count = count; a.blind_key = blind_key; a.index_base = index_base;
+    a.out_proofs = out_proofs; a.out_commitments = out_commitments;
+    if (int rc = prove_args(engine, PROVE_SER_HOST, flags, a, v && gamma && outs_of && out_proofs && out_commitments)) return rc;
+    if (count == 0) return BPP_OK;
+    if (int rc = container_version_ok(container_point_size(engine->ctx.curve, (int)a.version))) return rc;
+    return on_ctx(engine->ctx, {count, "count"}, [&](auto cv) -> int { return ProveBatchImpl<decltype(cv)>::prove_host(engine, a); });
+}
+
+extern "C" size_t bpp_verifier_serialized_outs_workspace_bytes(const bpp_verifier* v, const uint32_t* outs_of, size_t count) {
+    if (!outs_wellformed(outs_of, count)) return 0;
+    return size_for(v, [&](auto cv) { return VerifyImpl<decltype(cv)>::ser_mixed_workspace_bytes(v, nullptr, count, outs_of); });
+}
+
+extern "C" int bpp_range_verify_batch_serialized_outs_device(bpp_verifier* v, const void* d_proofs, const void* d_commitments,
+                                                             const uint32_t* outs_of, size_t count, int flags, uint32_t* d_ok,
+                                                             void* d_workspace, size_t workspace_bytes, void* stream) {
+    VerifyArgs a;
+    a.proofs = static_cast<const uint8_t*>(d_proofs); a.commitments = static_cast<const uint8_t*>(d_commitments);
+    a.outs_of = outs_of; a.count = count; a.ok = d_ok;
+    if (int rc = verify_args(VERIFY_SER_MIXED, facts(v), flags, a, d_workspace)) return answered(rc);
+    return on_ctx(v->ctx, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::run_serialized_mixed(v, a, d_workspace, workspace_bytes, hip(stream));
+    });
+}
+
+// host buffers in, host verdicts out: the device path above between two copies
+extern "C" int bpp_range_verify_batch_serialized_outs(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments,
+                                                      const uint32_t* outs_of, size_t count, int flags, uint32_t* out_ok) {
+    VerifyArgs a;
+    a.proofs = proofs; a.commitments = commitments; a.outs_of = outs_of; a.count = count; a.ok = out_ok;
+    if (int rc = verify_args(VERIFY_HOST_SER_MIXED, facts(v), flags, a, nullptr)) return answered(rc);
+    return on_ctx(v->ctx, [&](auto cv) -> int { return VerifyImpl<decltype(cv)>::verify_host(v, a, HOST_SERIALIZED_MIXED, flags); });
+}
+
+extern "C" size_t bpp_verifier_serialized_grouped_outs_workspace_bytes(const bpp_verifier* v, const uint32_t* outs_of, size_t count,
+                                                                       uint32_t group) {
+    if (!outs_wellformed(outs_of, count)) return 0;
+    return size_for(v, [&](auto cv) {
+        return VerifyImpl<decltype(cv)>::ser_grouped_mixed_workspace_bytes(v, nullptr, count, group, outs_of);
+    });
+}
+
+extern "C" int bpp_range_verify_batch_serialized_grouped_outs_device(bpp_verifier* v, const void* d_proofs,
+                                                                     const void* d_commitments, const uint32_t* outs_of,
+                                                                     size_t count, int flags, const uint8_t* weight_key,
+                                                                     uint64_t index_base, uint32_t group, uint32_t* d_ok,
+                                                                     uint64_t* stats, void* d_workspace, size_t workspace_bytes,
+                                                                     void* stream) {
+    VerifyArgs a;
+    a.proofs = static_cast<const uint8_t*>(d_proofs); a.commitments = static_cast<const uint8_t*>(d_commitments);
+    a.outs_of = outs_of; a.count = count; a.weight_key = weight_key; a.index_base = index_base; a.group = group;
+    a.ok = d_ok; a.stats = stats;
+    if (int rc = verify_args(VERIFY_SER_GROUPED_MIXED, facts(v), flags, a, d_workspace)) return answered(rc);
+    return on_ctx(v->ctx, [&](auto cv) -> int {
+        return VerifyImpl<decltype(cv)>::run_serialized_grouped_mixed(v, a, d_workspace, workspace_bytes, hip(stream));
+    });
+}
+
+namespace {
+// the sum of outs_of, no further than the pair bound (no sum that can wrap: each count is below 2^32)
+size_t outs_units(const uint32_t* outs_of, size_t count) noexcept {
+    if (count > PAIR_BOUND) return count;
+    size_t n_out = 0;
+    for (size_t i = 0; i < count && n_out <= PAIR_BOUND; i++) n_out += outs_of[i];
+    return n_out;
+}
+// scan_keys_args for a ragged block: the counts themselves are the plan's to refuse, by name
+int find_outs_args(const uint32_t* outs_of, size_t count, size_t n_keys, int flags) noexcept {
+    if (!pairs_bounded(n_keys, outs_units(outs_of, count))) return fail(BPP_E_ARG, OUTPUT_PAIRS.too_large);
+    if (!(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, OUTPUT_PAIRS.transcript);
+    return BPP_OK;
+}
+}  // namespace
+
+extern "C" size_t bpp_verify_find_outputs_outs_workspace_bytes(const bpp_verifier* v, const uint32_t* outs_of, size_t count,
+                                                               size_t n_keys) {
+    if (!outs_wellformed(outs_of, count) || !pairs_bounded(n_keys, outs_units(outs_of, count))) return 0;
+    return size_for(v, [&](auto cv) { return OutputsImpl<decltype(cv)>::workspace_bytes(v, nullptr, count, n_keys, outs_of); });
+}
+
+extern "C" int bpp_range_verify_find_outputs_serialized_outs_keys_device(
+    bpp_verifier* v, const void* d_proofs, const void* d_commitments, const uint32_t* outs_of, size_t count, int flags,
+    const uint8_t* d_keys, size_t n_keys, uint64_t index_base, const uint64_t* d_index, const uint64_t* d_sealed,
+    const uint8_t* d_tags, uint32_t* d_ok, uint32_t* d_hits, size_t max_hits, uint32_t* d_n_hits, uint32_t* d_n_candidates,
+    void* d_workspace, size_t workspace_bytes, void* stream) {
+    FindArgs a{static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), nullptr, count, d_keys, n_keys,
+               index_base, d_index, d_sealed, d_ok, d_hits, max_hits, d_n_hits, FIND_PER_OUTPUT, d_tags, d_n_candidates};
+    a.outs_of = outs_of;
+    if (int rc = find_args(v, flags, a, true, d_workspace)) return rc;
+    if (count == 0) return find_nothing(v, a, true, static_cast<hipStream_t>(stream));
+    if (int rc = find_outs_args(outs_of, count, n_keys, flags)) return rc;
+    if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
+        return OutputsImpl<decltype(cv)>::find(v, a, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    });
+}
+
+// host buffers in (keys, index, sealed amounts and tags included), host verdicts, hit records and counts out
+extern "C" int bpp_range_verify_find_outputs_serialized_outs_keys(
+    bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, const uint32_t* outs_of, size_t count, int flags,
+    const uint8_t* keys, size_t n_keys, uint64_t index_base, const uint64_t* index, const uint64_t* sealed, const uint8_t* tags,
+    uint32_t* out_ok, uint32_t* out_hits, size_t max_hits, uint32_t* out_n_hits, uint32_t* out_n_candidates) {
+    FindArgs a{proofs, commitments, nullptr,  count,    keys,       n_keys,          index_base, index,
+               sealed, out_ok,      out_hits, max_hits, out_n_hits, FIND_PER_OUTPUT, tags,       out_n_candidates};
+    a.outs_of = outs_of;
+    if (int rc = find_args(v, flags, a, false, nullptr)) return rc;
+    if (count == 0) return find_nothing(v, a, false, nullptr);
+    if (int rc = find_outs_args(outs_of, count, n_keys, flags)) return rc;
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int { return OutputsImpl<decltype(cv)>::find_host(v, a); });
 }
 

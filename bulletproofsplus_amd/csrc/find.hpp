@@ -323,6 +323,9 @@ struct FindArgs {
     uint32_t* n_candidates;    // one word or null; likewise
     uint32_t version = 1;      // what the call's flags say
     bool amount64 = false, sealed = false;
+    // per output alone, in place of m_of: the ragged block (outs_plan.hpp) -- amounts and tags by REAL output number, the
+    // sum of outs_of[i] of them
+    const uint32_t* outs_of = nullptr;
     bool tagged() const { return mode != FIND_REWIND; }
 };
 
@@ -421,9 +424,10 @@ struct FindEngine {
         return w;
     }
 
-    static size_t workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys, FindMode mode) {
+    static size_t workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys, FindMode mode,
+                                  const uint32_t* outs_of = nullptr) {
         MixedPlan p;
-        if (!V::container_shape_ok(v) || mixed_plan_serialized(v->s, m_of, count, max_point_bytes<C>(), false, p)) return 0;
+        if (!V::container_shape_ok(v) || mixed_plan_serialized(v->s, m_of, count, max_point_bytes<C>(), false, p, outs_of)) return 0;
         return layout(v, p, count, n_keys, mode).total;
     }
 
@@ -431,7 +435,7 @@ struct FindEngine {
         if (int rc = V::container_args_ok(v, a.version)) return rc;
         const size_t count = a.count;
         MixedPlan p;
-        int rc = mixed_plan_serialized(v->s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), true, p);
+        int rc = mixed_plan_serialized(v->s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), true, p, a.outs_of);
         if (rc) return rc;
         const Layout L = layout(v, p, count, a.n_keys, a.mode);
         if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
@@ -472,7 +476,7 @@ struct FindEngine {
     static int find_host(bpp_verifier* v, const FindArgs& a) {
         if (int rc = V::container_args_ok(v, a.version)) return rc;
         MixedPlan p;
-        int rc = mixed_plan_serialized(v->s, a.m_of, a.count, (size_t)container_point_bytes<C>(a.version), false, p);
+        int rc = mixed_plan_serialized(v->s, a.m_of, a.count, (size_t)container_point_bytes<C>(a.version), false, p, a.outs_of);
         if (rc) return rc;
         const size_t units = S::units(p, a.count), pairs = a.n_keys * units;
         DevBuf dk(true);   // the keys: wiped before they are freed, on every way out

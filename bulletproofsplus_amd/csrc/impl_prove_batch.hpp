@@ -27,6 +27,9 @@ namespace bpp {
 struct ProveArgs {
     const uint64_t *values = nullptr, *gammas = nullptr;
     const uint32_t* m_of = nullptr;
+    // the serialized form's ragged block (outs_plan.hpp), in place of m_of: proof i has outs_of[i] values and gammas and is
+    // proved in the shape (n, 2^ceil(log2 outs_of[i])) over zeros in the other places; out_commitments gets outs_of[i] each
+    const uint32_t* outs_of = nullptr;
     size_t count = 0;
     bool fs = false, amount64 = false;   // amount64: the commitments' scalar on g is the u64, not `v as i32`
     uint32_t version = 1;                // of the containers
@@ -129,9 +132,9 @@ struct ProveBatchImpl {
     static void argument(const Chunk& c, bool fs, VpSel literal_sel);
 
     // ---- the device forms: every buffer of `a` and the workspace in HBM, nothing synchronises ---------------------------
-    // a.m_of null: prove_batch_device, else prove_mixed
+    // a.m_of and a.outs_of null: prove_batch_device, else prove_mixed
     static int prove_device(bpp_verifier* v, const ProveArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
-        return a.m_of ? prove_mixed(v, a, d_workspace, workspace_bytes, st)
+        return a.m_of || a.outs_of ? prove_mixed(v, a, d_workspace, workspace_bytes, st)
                       : prove_batch_device(v, a, d_workspace, workspace_bytes, st);
     }
     // `a.count` proofs of one shape (a.in.ps), in chunks that reuse one workspace (prove_layout)
@@ -162,10 +165,11 @@ struct ProveBatchImpl {
         return w;
     }
     // 0 for an m_of the engine does not take, or -- serialized -- an engine the container does not hold
-    static size_t prove_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, bool serialized) {
+    static size_t prove_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, bool serialized,
+                                              const uint32_t* outs_of = nullptr) {
         MixedPlan p;
         if (serialized && !V::container_shape_ok(v)) return 0;
-        if (prove_plan(v->s, m_of, count, serialized ? max_point_bytes<C>() : 0, false, p)) return 0;
+        if (prove_plan(v->s, m_of, count, serialized ? max_point_bytes<C>() : 0, false, p, outs_of)) return 0;
         return prove_mixed_layout(v, p, count, serialized).total;
     }
     // Every class present proved with its view, one after the other on st.  Serialized: into the class regions of the
@@ -319,7 +323,7 @@ int ProveBatchImpl<C>::prove_mixed(bpp_verifier* v, const ProveArgs& a, void* d_
     if (serialized) BPP_TRY(V::container_args_ok(v, a.version));
     const size_t count = a.count;
     MixedPlan p;
-    BPP_TRY(prove_plan(v->s, a.m_of, count, serialized ? (size_t)container_point_bytes<C>(a.version) : 0, true, p));
+    BPP_TRY(prove_plan(v->s, a.m_of, count, serialized ? (size_t)container_point_bytes<C>(a.version) : 0, true, p, a.outs_of));
     const ProveMixedLayout L = prove_mixed_layout(v, p, count, serialized);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
@@ -330,7 +334,7 @@ int ProveBatchImpl<C>::prove_mixed(bpp_verifier* v, const ProveArgs& a, void* d_
         HIPCHK(hipMemcpyAsync(w_idx + count * PX_WORDS, p.sidx.data(), p.sidx.size() * 4, hipMemcpyHostToDevice, st));
     // what every class is told: the block's packed inputs and, of the outputs, what the index leads to
     ProveArgs cls = a;
-    cls.m_of = nullptr;
+    cls.m_of = cls.outs_of = nullptr;
     cls.out_V = nullptr;
     cls.out_proofs = cls.out_commitments = nullptr;
     if (serialized) {
@@ -366,13 +370,14 @@ int ProveBatchImpl<C>::prove_host(bpp_verifier* v, const ProveArgs& a) {
     // a block at fixed strides, then a mixed one: amounts, wire points, challenges, workspace bytes
     size_t nval = count * s.m, points = count * (size_t)(3 + 2 * s.k), chals = count * (size_t)(3 + s.k), wsb = 0;
     MixedPlan p;
-    if (a.m_of) {
-        BPP_TRY(serialized ? mixed_plan_serialized(s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), false, p)
+    if (a.m_of || a.outs_of) {
+        BPP_TRY(serialized ? mixed_plan_serialized(s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), false, p, a.outs_of)
                            : mixed_plan(s, a.m_of, count, false, p));
-        if (count > 0x7fffffffu / 64 || (serialized && !prove_mixed_workspace_bytes(v, a.m_of, count, true)))
+        if (count > 0x7fffffffu / 64 || (serialized && !prove_mixed_workspace_bytes(v, a.m_of, count, true, a.outs_of)))
             return fail(BPP_E_ARG, serialized ? "serialized mixed block rejected" : "mixed block rejected");
         nval = 0;
         for (uint32_t c = 0; c < MIXED_CLASSES; c++) nval += p.count[c] << c;
+        if (a.outs_of) nval = p.n_out;   // a ragged block: the values and gammas of the outputs there are
         points = p.points;
         chals = p.chals;
         wsb = prove_mixed_layout(v, p, count, serialized).total;

@@ -337,9 +337,10 @@ struct VerifyImpl {
         return w;
     }
     // 0 for an m_of the verifier does not take (the larger point encoding sizes the byte-offset check)
-    static size_t ser_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
+    static size_t ser_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count,
+                                            const uint32_t* outs_of = nullptr) {
         MixedPlan p;
-        if (!container_shape_ok(v) || mixed_plan_serialized(v->s, m_of, count, max_point_bytes<C>(), false, p)) return 0;
+        if (!container_shape_ok(v) || mixed_plan_serialized(v->s, m_of, count, max_point_bytes<C>(), false, p, outs_of)) return 0;
         return ser_mixed_layout(v, p, count).total;
     }
     // Uploads the per-proof index (blocking the host until the copy has read it), the rest is enqueued on st.
@@ -532,10 +533,11 @@ struct VerifyImpl {
         if (!group_ok(group) || mixed_plan(v->s, m_of, count, false, p)) return 0;
         return group_mixed_layout(v, p, count, group, false).total;
     }
-    static size_t ser_grouped_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, uint32_t group) {
+    static size_t ser_grouped_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, uint32_t group,
+                                                    const uint32_t* outs_of = nullptr) {
         MixedPlan p;
         if (!group_ok(group) || !container_shape_ok(v) ||
-            mixed_plan_serialized(v->s, m_of, count, max_point_bytes<C>(), false, p))
+            mixed_plan_serialized(v->s, m_of, count, max_point_bytes<C>(), false, p, outs_of))
             return 0;
         return group_mixed_layout(v, p, count, group, true).total;
     }
@@ -1019,7 +1021,7 @@ int VerifyImpl<C>::run_serialized_mixed(bpp_verifier* v, const VerifyArgs& a, vo
     const size_t count = a.count;
     if (int rc = container_args_ok(v, a.version)) return rc;
     MixedPlan p;
-    int rc = mixed_plan_serialized(v->s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), true, p);
+    int rc = mixed_plan_serialized(v->s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), true, p, a.outs_of);
     if (rc) return rc;
     const SerMixedLayout L = ser_mixed_layout(v, p, count);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
@@ -1276,7 +1278,7 @@ int VerifyImpl<C>::run_serialized_grouped_mixed(bpp_verifier* v, const VerifyArg
     const uint32_t group = a.group;
     if (int rc = container_args_ok(v, a.version)) return rc;
     MixedPlan p;
-    int rc = mixed_plan_serialized(v->s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), true, p);
+    int rc = mixed_plan_serialized(v->s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), true, p, a.outs_of);
     if (rc) return rc;
     rc = check_group(group);
     if (rc) return rc;
@@ -1335,8 +1337,9 @@ int VerifyImpl<C>::verify_host(bpp_verifier* v, const VerifyArgs& a, HostForm fo
     } else if (form == HOST_SERIALIZED) {
         in0 = count * container_bytes<C>(s.k, a.version), in1 = count * s.m * cb, wsb = ser_layout(s, count).total;
     } else if (form == HOST_SERIALIZED_MIXED) {
-        wsb = bpp_verifier_serialized_mixed_workspace_bytes(v, a.m_of, count);
-        const int rc = mixed_plan_serialized(s, a.m_of, count, cb, false, p);   // its byte totals size the uploads
+        wsb = a.outs_of ? bpp_verifier_serialized_outs_workspace_bytes(v, a.outs_of, count)
+                        : bpp_verifier_serialized_mixed_workspace_bytes(v, a.m_of, count);
+        const int rc = mixed_plan_serialized(s, a.m_of, count, cb, false, p, a.outs_of);   // its byte totals size the uploads
         if (rc || !wsb) return rc ? rc : fail(BPP_E_ARG, "serialized mixed batch rejected");   // an m_i the verifier does not take
         in0 = p.proof_bytes, in1 = p.comm_bytes;
     }
@@ -1356,7 +1359,8 @@ int VerifyImpl<C>::verify_host(bpp_verifier* v, const VerifyArgs& a, HostForm fo
     BPP_TRY(flat ? bpp_verifier_run(v, form == HOST_WIRE ? d0.u64() : dp.u64(), d1.u64(), count, nullptr, dok.u32(), dws.p, wsb, nullptr, nullptr, nullptr)
             : form == HOST_MIXED ? bpp_verifier_run_mixed(v, d0.u64(), d1.u64(), a.m_of, count, nullptr, dok.u32(), dws.p, wsb, nullptr, nullptr)
             : form == HOST_SERIALIZED ? bpp_range_verify_batch_serialized_device(v, d0.p, d1.p, count, flags, dok.u32(), dws.p, wsb, nullptr)
-                                      : bpp_range_verify_batch_serialized_mixed_device(v, d0.p, d1.p, a.m_of, count, flags, dok.u32(), dws.p, wsb, nullptr));
+            : a.outs_of ? bpp_range_verify_batch_serialized_outs_device(v, d0.p, d1.p, a.outs_of, count, flags, dok.u32(), dws.p, wsb, nullptr)
+                        : bpp_range_verify_batch_serialized_mixed_device(v, d0.p, d1.p, a.m_of, count, flags, dok.u32(), dws.p, wsb, nullptr));
     HIPCHK(dok.download(a.ok, count * 4));
     if (form != HOST_COMPRESSED) return BPP_OK;
     std::vector<uint32_t> bad(npts);

@@ -14,6 +14,7 @@
 
 #include "codec.hpp"
 #include "host_util.hpp"
+#include "outs_plan.hpp"
 #include "prover_batch.hpp"
 
 namespace bpp {
@@ -24,6 +25,7 @@ namespace bpp {
 enum { MX_PT = 0, MX_GPT, MX_CH, MX_GCH, MX_POS, MX_NV, MX_NCH, MX_WORDS = 8 };
 constexpr unsigned MIXED_BLOCK = 128;
 constexpr int MIXED_CLASSES = 8;   // m' = 1, 2, 4, .. <= VS_MAXM
+static_assert(MIXED_CLASSES == OUTS_CLASSES, "outs_plan.hpp classes are the mixed classes");
 
 // one block per proof: its NV wire points, its scalar triple and (ch != null) its 3 + k challenges, copied as 64-bit
 // words by all the block's lanes (a (64,16) record on BLS12-381 is 507 words: four per lane)
@@ -73,8 +75,11 @@ __global__ void __launch_bounds__(256) k_mixed_scatter(const uint32_t* __restric
 
 // ---- serialized mixed batches: the decoder writes the class regions ------------------------------------------------
 // one entry per proof, by GATHERED position (built on the host, SX_WORDS 32-bit words): the byte offsets of its container
-// and of its commitments in the caller's packed buffers, and its caller position
-enum { SX_PROOF = 0, SX_COMM, SX_CALLER, SX_WORDS = 4 };
+// and of its commitments in the caller's packed buffers, and its caller position.  A RAGGED block (outs_of given, outs_plan.hpp:
+// proof i covers outs_of[i] <= 2^c outputs, its other commitments are the identity and are not in the stream): SX_COMM is the
+// ragged offset and SX_OUTS holds the count (outs_word); in any other block the kernels here leave that word unread, and
+// the callers that scan or find put their own there (recover.hpp RX_BLIND).
+enum { SX_PROOF = 0, SX_COMM, SX_CALLER, SX_OUTS, SX_WORDS = 4 };
 
 // The class regions as the decode kernels see them, passed by value.  One lane per record point in gathered order; each
 // class's lane range is padded to a multiple of the wave size, so a wave (= a block of these kernels) never straddles
@@ -85,8 +90,24 @@ struct SerClasses {
     uint32_t first[MIXED_CLASSES];      // first gathered position of the class
     uint32_t pt[MIXED_CLASSES];         // first gathered record point of the class
     uint32_t n, logn;
+    uint32_t ragged;                    // non-zero: SX_OUTS says how many of a proof's 2^c commitments the stream carries
 };
 constexpr uint32_t SER_WAVE = 64;
+static_assert(SER_WAVE == OUTS_WAVE && CONTAINER_HDR == OUTS_HDR, "outs_plan.hpp mirrors the decoder's geometry");
+
+// the commitments of the proof with index entry e that its stream carries; of the class's m the others are the identity
+__device__ __forceinline__ uint32_t ser_outs(const SerClasses& g, const uint32_t* __restrict__ e, uint32_t m) {
+    return g.ragged ? outs_word_count(e[SX_OUTS]) : m;
+}
+// the words the decoder writes for the encoding of the identity: the canonical infinity, on ristretto255 the
+// representative (0, 1) that rist_decode gives for 32 zero bytes
+template <class C>
+__device__ __forceinline__ void record_identity(uint32_t* __restrict__ w) {
+    constexpr int N = C::Fp::N;
+#pragma unroll
+    for (int t = 0; t < 2 * N + 2; t++) w[t] = 0;
+    w[C::ID == 2 ? N : 2 * N] = 1;
+}
 
 // a lane of the serialized mixed kernels: its class's shape (n, m, k, NV), the proof's gathered position, the point's
 // index in the record and among the gathered points; `live` false for a padding lane
@@ -123,7 +144,8 @@ __device__ __forceinline__ SerLane ser_lane(const SerClasses& g, uint32_t base, 
 
 // k_container_decode over a mixed batch: one lane per record point of all classes in gathered order.  The containers are
 // read where the caller packed them (idx: SX_PROOF / SX_COMM, lengths implied by m_of on the host, never by the bytes)
-// and decoded straight into the class regions; status words by gathered position.
+// and decoded straight into the class regions; status words by gathered position.  A commitment lane beyond the proof's
+// count (a ragged block) reads no byte and writes the identity's record words.
 template <class C>
 __global__ void __launch_bounds__(64, 2) k_container_decode_mixed(SerClasses g, const uint32_t* __restrict__ idx,
                                                                   const uint8_t* __restrict__ proofs,
@@ -136,10 +158,14 @@ __global__ void __launch_bounds__(64, 2) k_container_decode_mixed(SerClasses g, 
     const int CB = container_point_bytes<C>(version);
     const uint32_t* e = idx + (size_t)L.pos * SX_WORDS;
     const uint32_t npp = 3 + 2 * L.k;
+    uint32_t* w = records + (size_t)L.point * (2 * N + 2);
+    if (L.t >= npp + ser_outs(g, e, L.m)) {
+        record_identity<C>(w);
+        return;
+    }
     const uint8_t* rec = proofs + e[SX_PROOF];
     const uint8_t* src = L.t < npp ? rec + CONTAINER_HDR + (size_t)L.t * CB : commitments + e[SX_COMM] + (size_t)(L.t - npp) * CB;
-    if (!container_decode_lane<C>(rec, src, L.t, g.n, L.m, L.k, version, records + (size_t)L.point * (2 * N + 2),
-                                  scalars + (size_t)L.pos * 24))
+    if (!container_decode_lane<C>(rec, src, L.t, g.n, L.m, L.k, version, w, scalars + (size_t)L.pos * 24))
         atomicOr(status + L.pos, 1u);
 }
 
@@ -148,6 +174,7 @@ __global__ void __launch_bounds__(64, 2) k_container_decode_mixed(SerClasses g, 
 // others as commitment t - (3 + 2k) at SX_COMM -- and the lane of a proof's first point writes the 12-byte header and the
 // three scalars (scalars: by CALLER position, as k_pb_final leaves them for a mixed block).  Byte stores throughout: a
 // container starts wherever the ones before it end (a secp256k1 point is 33 bytes), and a lane's bytes are its own.
+// A commitment lane beyond the proof's count (a ragged block) writes nothing: its point is the identity by construction.
 template <class C>
 __global__ void __launch_bounds__(64, 2) k_container_encode_mixed(SerClasses g, const uint32_t* __restrict__ idx,
                                                                   const uint32_t* __restrict__ records,
@@ -160,6 +187,7 @@ __global__ void __launch_bounds__(64, 2) k_container_encode_mixed(SerClasses g, 
     const int CB = container_point_bytes<C>(version);
     const uint32_t* e = idx + (size_t)L.pos * SX_WORDS;
     const uint32_t npp = 3 + 2 * L.k;
+    if (L.t >= npp + ser_outs(g, e, L.m)) return;
     uint8_t* rec = proofs + e[SX_PROOF];
     uint8_t* dst = L.t < npp ? rec + CONTAINER_HDR + (size_t)L.t * CB : commitments + e[SX_COMM] + (size_t)(L.t - npp) * CB;
     const uint32_t* w = records + (size_t)L.point * (2 * N + 2);
@@ -180,7 +208,8 @@ __global__ void __launch_bounds__(64, 2) k_container_encode_mixed(SerClasses g, 
     }
 }
 
-// k_records_subgroup over the class regions (same lanes as k_container_decode_mixed): one launch for all classes
+// k_records_subgroup over the class regions (same lanes as k_container_decode_mixed): one launch for all classes.  The
+// padded lanes of a ragged block hold the infinity the decoder wrote: record_leaves_subgroup ends on its flag word.
 template <class C>
 __global__ void __launch_bounds__(64, 2) k_records_subgroup_mixed(SerClasses g, uint32_t* __restrict__ records,
                                                                   uint32_t* __restrict__ status) {
@@ -211,6 +240,7 @@ struct MixedPlan {
     // serialized form (mixed_plan_serialized): the packed input's sizes, the per-proof entries by gathered position
     // (SX_*), the lane ranges of the decode kernels
     size_t proof_bytes = 0, comm_bytes = 0, lanes = 0;
+    size_t n_out = 0;   // commitments the stream carries: the sum of m_i, of a ragged block the sum of outs_of[i]
     std::vector<uint32_t> sidx;
     SerClasses classes = {};
     // producing side (prove_plan): the prover's per-proof entries by gathered position (PX_*, prover_batch.hpp)
@@ -268,8 +298,15 @@ inline int mixed_plan(const VerifyShape& cap, const uint32_t* m_of, size_t count
 // mixed_plan for containers packed back to back in caller order (container i of hdr + (3 + 2 k_i) pb + 96 bytes, then
 // m_i encoded commitments of pb bytes each in a buffer of their own).  pb: bytes of an encoded point.  BPP_E_ARG also
 // for a batch whose byte offsets do not fit the 32-bit index.
+// outs_of given (m_of is then not read): a ragged block -- proof i has the shape of its class, m_i = 2^ceil(log2 outs_of[i]),
+// and outs_of[i] commitments in the stream (outs_plan.hpp, whose errors name outs_of[i]).
 inline int mixed_plan_serialized(const VerifyShape& cap, const uint32_t* m_of, size_t count, size_t pb, bool want_idx,
-                                 MixedPlan& p) {
+                                 MixedPlan& p, const uint32_t* outs_of = nullptr) {
+    OutsPlan ragged;
+    if (outs_of) {
+        if (int rc = outs_plan(cap.n, cap.m, outs_of, count, pb, ragged)) return rc;
+        m_of = ragged.m_of.data();
+    }
     int rc = mixed_plan(cap, m_of, count, false, p);
     if (rc) return rc;
     uint32_t logm = 0;
@@ -283,7 +320,7 @@ inline int mixed_plan_serialized(const VerifyShape& cap, const uint32_t* m_of, s
     size_t lanes = 0;
     for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
         p.proof_bytes += p.count[c] * cbytes(c);
-        p.comm_bytes += (p.count[c] << c) * pb;
+        p.n_out += p.count[c] << c;
         const size_t used = p.count[c] * nv(c);   // < 2^28 in all (mixed_plan)
         lanes += (used + SER_WAVE - 1) / SER_WAVE * SER_WAVE;
         g.lane_end[c] = (uint32_t)lanes;
@@ -292,7 +329,10 @@ inline int mixed_plan_serialized(const VerifyShape& cap, const uint32_t* m_of, s
         g.pt[c] = (uint32_t)p.pt[c];
     }
     p.lanes = lanes;
-    if ((p.proof_bytes | p.comm_bytes) >> 32) {   // name the first proof that ends beyond 4 GiB
+    g.ragged = outs_of ? 1u : 0u;
+    if (outs_of) p.n_out = ragged.n_out;
+    p.comm_bytes = p.n_out * pb;
+    if ((p.proof_bytes | p.comm_bytes) >> 32) {   // name the first proof that ends beyond 4 GiB (ragged: outs_plan has)
         size_t i = 0;
         for (size_t pr = 0, cm = 0; i < count; i++) {
             const uint32_t c = (uint32_t)__builtin_ctz(m_of[i]);
@@ -314,8 +354,9 @@ inline int mixed_plan_serialized(const VerifyShape& cap, const uint32_t* m_of, s
         e[SX_PROOF] = (uint32_t)src_pr;
         e[SX_COMM] = (uint32_t)src_cm;
         e[SX_CALLER] = (uint32_t)i;
+        if (outs_of) e[SX_OUTS] = outs_word(outs_of[i], 0);
         src_pr += cbytes(c);
-        src_cm += ((size_t)1 << c) * pb;
+        src_cm += (outs_of ? (size_t)outs_of[i] : (size_t)1 << c) * pb;
     }
     return BPP_OK;
 }
@@ -323,8 +364,11 @@ inline int mixed_plan_serialized(const VerifyShape& cap, const uint32_t* m_of, s
 // The plan of a block to PROVE: mixed_plan / mixed_plan_serialized (pb != 0: the containers' point size) and the prover's
 // index px by gathered position.  PX_REC: wire form -- the proof's record in the caller-order packed block (what
 // bpp_verifier_run_mixed reads as d_points); serialized form -- its record in the class regions.
-inline int prove_plan(const VerifyShape& cap, const uint32_t* m_of, size_t count, size_t pb, bool want_idx, MixedPlan& p) {
-    int rc = pb ? mixed_plan_serialized(cap, m_of, count, pb, want_idx, p) : mixed_plan(cap, m_of, count, false, p);
+// outs_of given (serialized form alone; m_of is then not read): a ragged block -- PX_VAL is the ragged offset, PX_OUTS the count.
+inline int prove_plan(const VerifyShape& cap, const uint32_t* m_of, size_t count, size_t pb, bool want_idx, MixedPlan& p,
+                      const uint32_t* outs_of = nullptr) {
+    if (outs_of && !pb) return fail(BPP_E_ARG, "outs_of: the serialized form alone");
+    int rc = pb ? mixed_plan_serialized(cap, m_of, count, pb, want_idx, p, outs_of) : mixed_plan(cap, m_of, count, false, p);
     if (rc || !want_idx) return rc;
     uint32_t logm = 0;
     while ((1u << logm) < cap.m) logm++;
@@ -334,8 +378,7 @@ inline int prove_plan(const VerifyShape& cap, const uint32_t* m_of, size_t count
     for (uint32_t c = 0; c < MIXED_CLASSES; c++) next[c] = p.first[c];
     size_t src_pt = 0, src_val = 0, src_bl = 0, src_ch = 0;
     for (size_t i = 0; i < count; i++) {
-        uint32_t c = 0;
-        while ((1u << c) < m_of[i]) c++;
+        const uint32_t c = outs_class(outs_of ? outs_of[i] : m_of[i]);
         const uint32_t k = logn + c;
         const size_t nv = 3 + 2 * (size_t)k + ((size_t)1 << c);
         const size_t pos = next[c]++;
@@ -345,8 +388,9 @@ inline int prove_plan(const VerifyShape& cap, const uint32_t* m_of, size_t count
         e[PX_VAL] = (uint32_t)src_val;
         e[PX_BLIND] = (uint32_t)src_bl;
         e[PX_CH] = (uint32_t)src_ch;
+        e[PX_OUTS] = outs_of ? outs_of[i] : 1u << c;
         src_pt += nv;
-        src_val += (size_t)1 << c;
+        src_val += e[PX_OUTS];
         src_bl += pb_blind_elems(k);
         src_ch += 3 + k;
     }

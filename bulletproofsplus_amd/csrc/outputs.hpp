@@ -9,8 +9,9 @@
 // k_outputs_make: one lane per output, its key from the caller's buffer into registers; mask, sealed amount, tag, each
 // skipped where its pointer is null.
 // The receiver's call is find.hpp's engine and schedule in its per-output mode (FindEngine with OutputStep, instantiated
-// here alone): the index's free word carries each proof's first caller output number, the pair words are zeroed whenever
-// there are keys, and after the pass of EVERY class present comes this class step --
+// here alone): the index's free word carries each proof's output count and first caller output number (outs_word,
+// outs_plan.hpp: the count is the class's m, or fewer in a ragged block, whose places from the count on are padding and no
+// pair), the pair words are zeroed whenever there are keys, and after the pass of EVERY class present comes this class step --
 // k_out_tags: k_find_tags's tiling (tag_tile) over the class's launch OUTPUT positions: one 64-lane block per tile of
 // FIND_TILE positions OF ONE KEY.  A lane whose proof the pass did not accept or the decoder rejected is no candidate before
 // it reads a key.  The others read the tile's key (uniform over the block), the proof's index and the output's tag byte, and
@@ -59,7 +60,8 @@ struct OutJob {
     const uint32_t* keys;      // the CALLER's buffer: n_keys x 8 little-endian words
     uint64_t index_base;
     const uint64_t* index;     // by caller PROOF position, or null: index_base + caller position
-    const uint32_t* rx;        // the class's entries by launch position: RX_CALLER, and in RX_BLIND the proof's first output number
+    const uint32_t* rx;        // the class's entries by launch position: RX_CALLER, and in RX_BLIND (= SX_OUTS) the outs_word of
+                               // the proof's output count and first caller output number
     const uint32_t* ok;        // the pass's verdicts, by launch position
     const uint32_t* status;    // the decoder's, by launch position
     const uint64_t* sealed;    // by caller output number
@@ -70,13 +72,18 @@ struct OutJob {
     uint64_t* hit_amounts;     // n_keys x total; written for hits only
 };
 
-// key number key_no's words into registers; returns the blinding index of the proof at launch position p and, in o, the
-// caller output number of its output `place`
-__device__ __forceinline__ uint64_t out_key_index(const OutJob& j, size_t key_no, size_t p, uint32_t place, uint32_t key[8],
-                                                  size_t& o) {
+// Whether the proof at launch position p has an output `place` at all: of a ragged block's proof the places from its count
+// on are padding, no pair -- decided on the index word alone, before a key is loaded or a byte of tags / sealed is read.
+// In o the caller output number.
+__device__ __forceinline__ bool out_exists(const OutJob& j, size_t p, uint32_t place, size_t& o) {
+    const uint32_t w = j.rx[p * RX_WORDS + RX_BLIND];
+    o = (size_t)outs_word_first(w) + place;
+    return place < outs_word_count(w);
+}
+// key number key_no's words into registers; returns the blinding index of the proof at launch position p
+__device__ __forceinline__ uint64_t out_key_index(const OutJob& j, size_t key_no, size_t p, uint32_t key[8]) {
     load_key(j.keys, key_no, key);
     const size_t caller = j.rx[p * RX_WORDS + RX_CALLER];
-    o = (size_t)j.rx[p * RX_WORDS + RX_BLIND] + place;
     return j.index ? j.index[caller] : j.index_base + caller;
 }
 
@@ -88,9 +95,10 @@ __global__ void __launch_bounds__(FIND_BLOCK) k_out_tags(OutJob j, TagJob t) {
         const size_t p = output_proof(x, j.logm);
         if (j.ok[p] | j.status[p]) return false;   // a verified proof: only then a key is read
         const uint32_t place = output_place(x, j.logm);
-        uint32_t key[8];
         size_t o;
-        const uint64_t idx = out_key_index(j, key_no, p, place, key, o);
+        if (!out_exists(j, p, place, o)) return false;
+        uint32_t key[8];
+        const uint64_t idx = out_key_index(j, key_no, p, key);
         return output_tag(key, idx, place) == j.tags[o];
     });
 }
@@ -113,9 +121,10 @@ __global__ void __launch_bounds__(FIND_BLOCK) k_out_confirm(VerifyShape s, const
     const size_t key_no = q / j.outs, x = q - key_no * j.outs;
     const size_t p = output_proof(x, j.logm);
     const uint32_t place = output_place(x, j.logm);
-    uint32_t key[8];
     size_t o;
-    const uint64_t idx = out_key_index(j, key_no, p, place, key, o);
+    if (!out_exists(j, p, place, o)) return;   // never a candidate (k_out_tags); the list holds none
+    uint32_t key[8];
+    const uint64_t idx = out_key_index(j, key_no, p, key);
     const uint64_t amount = j.sealed[o] ^ output_pad(key, idx, place);
     uint32_t kv[8], kg[8];
     commit_amount_scalar<C>(amount, amount64 != 0, kv);
@@ -132,7 +141,8 @@ __global__ void __launch_bounds__(FIND_BLOCK) k_out_confirm(VerifyShape s, const
 
 template <class C>
 struct OutputsImpl {
-    static size_t workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys);
+    static size_t workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys,
+                                  const uint32_t* outs_of = nullptr);
     // a.mode: FIND_PER_OUTPUT
     static int find(bpp_verifier* v, const FindArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st);
     static int find_host(bpp_verifier* v, const FindArgs& a);
@@ -150,11 +160,7 @@ struct OutputStep {
     using V = VerifyImpl<C>;
     OutJob j;
 
-    static size_t units(const MixedPlan& p, size_t) {
-        size_t n_out = 0;
-        for (uint32_t c = 0; c < MIXED_CLASSES; c++) n_out += output_class_outputs(p.count[c], c);
-        return n_out;
-    }
+    static size_t units(const MixedPlan& p, size_t) { return p.n_out; }   // the sum of m_i; ragged: of outs_of[i]
     static size_t widest(const MixedPlan& p) {
         size_t widest = 0;
         for (uint32_t c = 0; c < MIXED_CLASSES; c++) widest = std::max(widest, output_class_outputs(p.count[c], c));
@@ -163,13 +169,14 @@ struct OutputStep {
     static size_t coeff_bytes(const bpp_verifier*, const MixedPlan&) { return 0; }
     static size_t flag_bytes(const MixedPlan&) { return 0; }
     static bool lists(const FindArgs& a, const MixedPlan&) { return a.n_keys != 0; }
-    // each proof's first caller output number, into the free word of the decoder's index: no second upload
+    // each proof's output count and first caller output number (outs_word), into the decoder's index: no second upload
     static int open(const bpp_verifier*, const FindArgs& a, bool, MixedPlan& p) {
+        const uint32_t* outs = a.outs_of ? a.outs_of : a.m_of;
         std::vector<uint32_t> first(a.count);
         size_t o = 0;
         for (size_t i = 0; i < a.count; i++) {
-            first[i] = (uint32_t)o;
-            o += a.m_of[i];
+            first[i] = outs_word(outs[i], (uint32_t)o);
+            o += outs[i];
         }
         for (size_t pos = 0; pos < a.count; pos++) p.sidx[pos * SX_WORDS + RX_BLIND] = first[p.sidx[pos * SX_WORDS + SX_CALLER]];
         return BPP_OK;
@@ -208,8 +215,9 @@ struct OutputStep {
 };
 
 template <class C>
-size_t OutputsImpl<C>::workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys) {
-    return FindEngine<C, OutputStep<C>>::workspace_bytes(v, m_of, count, n_keys, FIND_PER_OUTPUT);
+size_t OutputsImpl<C>::workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count, size_t n_keys,
+                                       const uint32_t* outs_of) {
+    return FindEngine<C, OutputStep<C>>::workspace_bytes(v, m_of, count, n_keys, FIND_PER_OUTPUT, outs_of);
 }
 template <class C>
 int OutputsImpl<C>::find(bpp_verifier* v, const FindArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {

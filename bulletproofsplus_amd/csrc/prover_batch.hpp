@@ -41,7 +41,9 @@ struct ProverConsts {
 // out_points; the record is then the packed [A, wip.A, wip.B, L.., R.., V_0..V_{m-1}]), its position in the caller's
 // numbering (blinding index, scalar triple), and where its values, blinding scalars and challenge block sit in the
 // caller's packed buffers.  px == nullptr: the single-shape layouts (proof p at fixed strides), as before.
-enum { PX_REC = 0, PX_CALLER, PX_VAL, PX_BLIND, PX_CH, PX_WORDS = 8 };
+// PX_OUTS: how many values and masks the proof has at PX_VAL -- its class's m, or fewer in a ragged block (outs_plan.hpp),
+// whose proof is made over zeros in the other places.
+enum { PX_REC = 0, PX_CALLER, PX_VAL, PX_BLIND, PX_CH, PX_OUTS, PX_WORDS = 8 };
 // the record [A, wip.A, wip.B, L.., R..] of proof p and its commitments
 template <int WW, class T>
 __device__ __forceinline__ T* pb_record(T* out_points, const uint32_t* __restrict__ px, size_t p, uint32_t k) {
@@ -558,8 +560,8 @@ __global__ void __launch_bounds__(64) k_pb_fs_final(VerifyShape s, const uint32_
 }
 
 // ---- a mixed block: the inputs of one class's chunk out of the caller's packed buffers ---------------------------------
-// One wave per proof (px entry p): its m values and m gammas (40 m bytes) and, blinding != null, its 5 + 2k blinding scalars,
-// copied as 64-bit words to the fixed strides the kernels above read.
+// One wave per proof (px entry p): its PX_OUTS values and gammas (40 bytes each), zeros for the rest of the class's m places,
+// and, blinding != null, its 5 + 2k blinding scalars, as 64-bit words at the fixed strides the kernels above read.
 template <class C>
 __global__ void __launch_bounds__(64) k_pb_gather_mixed(const uint32_t* __restrict__ px, uint32_t m, uint32_t k,
                                                         const uint64_t* __restrict__ values, const uint64_t* __restrict__ gammas,
@@ -569,8 +571,9 @@ __global__ void __launch_bounds__(64) k_pb_gather_mixed(const uint32_t* __restri
     const uint32_t* e = px + p * PX_WORDS;
     const uint32_t lane = threadIdx.x;
     const size_t v0 = e[PX_VAL];
-    for (uint32_t w = lane; w < m; w += 64) out_values[p * m + w] = values[v0 + w];
-    for (uint32_t w = lane; w < 4 * m; w += 64) out_gammas[p * 4 * m + w] = gammas[v0 * 4 + w];
+    const uint32_t outs = e[PX_OUTS];
+    for (uint32_t w = lane; w < m; w += 64) out_values[p * m + w] = w < outs ? values[v0 + w] : 0;
+    for (uint32_t w = lane; w < 4 * m; w += 64) out_gammas[p * 4 * m + w] = w < 4 * outs ? gammas[v0 * 4 + w] : 0;
     if (blinding) {
         const uint32_t nb = pb_blind_elems(k) * 4;
         const size_t b0 = (size_t)e[PX_BLIND] * 4;

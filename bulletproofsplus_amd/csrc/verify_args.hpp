@@ -21,6 +21,9 @@ struct VerifyArgs {
     // null: every proof has the verifier's (n, m).  Else proof i has shape (n, m_of[i]), m_of[i] a power of two <= m; records,
     // containers, commitments and challenges are then PACKED back to back in caller order (mixed.hpp)
     const uint32_t* m_of = nullptr;
+    // the bytes entries' ragged form (outs_plan.hpp), in place of m_of: proof i covers outs_of[i] outputs, has the shape
+    // (n, 2^ceil(log2 outs_of[i])) and outs_of[i] encoded commitments in the stream; the others are the identity
+    const uint32_t* outs_of = nullptr;
     size_t count = 0;
     const uint64_t* challenges = nullptr;   // null (the shape's literals, or the transcript's when fs), or 3 + k_i scalars per proof
     bool fs = false;                        // BPP_SER_TRANSCRIPT: the challenges come from the transcript of each proof
@@ -116,7 +119,8 @@ constexpr int VERIFY_ANSWERED = 1;
 inline int verify_args(const VerifyEntry& e, const VerifierFacts& v, int flags, VerifyArgs& a, const void* workspace) noexcept {
     const unsigned need = (e.needs & INPUTS_IF_COUNT) && !a.count ? e.needs & ~(NEED_IN0 | NEED_IN1) : e.needs;
     const bool buffers = (!(need & NEED_IN0) || a.points || a.proofs) && (!(need & NEED_IN1) || a.scalars || a.commitments) &&
-                         (!(need & NEED_M_OF) || a.m_of) && (!(need & NEED_OK) || a.ok) && (!(need & NEED_WS) || workspace) &&
+                         (!(need & NEED_M_OF) || a.m_of || a.outs_of) &&
+                         (!(need & NEED_OK) || a.ok) && (!(need & NEED_WS) || workspace) &&
                          (!(need & NEED_PARTIAL) || a.out_partial) && (!(need & NEED_OUT_CHALLENGES) || a.out_challenges) &&
                          (!(need & NEED_KEY) || a.weight_key);
     if (!v.engine || (e.empty != EMPTY_FIRST && !buffers)) return fail(BPP_E_ARG, "null argument");

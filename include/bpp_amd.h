@@ -905,6 +905,8 @@ int bpp_range_verify_find_tagged_serialized_mixed_keys(bpp_verifier *v, const ui
  * Any of the three outputs may be NULL and is then skipped; all three NULL is BPP_E_ARG.  A MASK IS SECRET: whoever holds
  * it and the amount can open the commitment, and whoever holds (key, idx, j) holds the mask.  Errors: BPP_E_ARG for a
  * NULL ctx, a NULL input, a d_keys that is not 4-byte aligned, n_out above 0x7fffffff / 64; n_out = 0 is BPP_OK.
+ * A proof over any number of outputs (the *_outs* calls below) needs no other form of this call: it is per output, with
+ * j < outs_of[i], and a padded place has no output to make.
  * Asynchronous on `stream`, no workspace and no upload; the host twin takes host buffers, is synchronous and overwrites
  * its device copies of the keys and the masks before freeing them. */
 int bpp_outputs_make_device(bpp_ctx *ctx, const uint8_t *d_keys, const uint64_t *d_index, const uint32_t *d_j,
@@ -954,6 +956,80 @@ int bpp_range_verify_find_outputs_serialized_mixed_keys(bpp_verifier *v, const u
                                                         const uint64_t *sealed, const uint8_t *tags, uint32_t *out_ok,
                                                         uint32_t *out_hits, size_t max_hits, uint32_t *out_n_hits,
                                                         uint32_t *out_n_candidates);
+
+/* ---- proofs over ANY number of outputs (csrc/outs_plan.hpp) ----
+ * Transactions have 2, 3, 5, 6 .. outputs; the argument needs a power of two.  A proof over o outputs, 1 <= o <= the
+ * engine's m, IS the proof of shape (n, M), M = 2^ceil(log2 o), over the values v_0 .. v_{o-1}, 0, .., 0 and the masks
+ * gamma_0 .. gamma_{o-1}, 0, .., 0: its commitments V_o .. V_{M-1} are the identity.  No new protocol:
+ *   verdict    : RangeProof::verify(proof, PublicKey::new(n M), n, [V_0 .. V_{o-1}, identity x (M - o)]) -- exactly what
+ *                bpp_range_verify_batch_serialized_mixed_device gives for m_of[i] = M when the caller appends the identity's
+ *                encoding M - o times
+ *   transcript : M points under "V" as ever, a padded one as the canonical infinity
+ *   container  : byte for byte the container of shape (n, M); its header says m = M; bpp_proofs_scan returns M
+ *   the count  : framing.  It travels as the host array outs_of[count], the way m_of does, and the value, mask and
+ *                commitment streams carry outs_of[i] entries per proof, NOT M: sum of outs_of[i] in all, packed in caller order
+ * The calls below are the serialized mixed calls with outs_of in the place of m_of; every other argument, flag, verdict
+ * word and error is the one documented there.  The padded commitments are neither read nor decompressed nor tested for
+ * group membership, a padded place is never paired with a key, and no byte of d_sealed / d_tags stands for it.
+ * THE OUTPUT COUNT IS NOT AUTHENTICATED beyond this: a proof over [V_0, V_1, V_2] and the (n, 4) proof over
+ * [V_0, V_1, V_2, identity] are the same statement.  Whoever needs the count bound binds the transaction's output list
+ * outside the proof.  (Presented with outs = 3, a proof made over four real outputs is a VerificationError.)
+ * Errors in addition: BPP_E_ARG naming i for outs_of[i] = 0 or above the engine's m; nothing is enqueued or written then.
+ * Every *_workspace_bytes below is 0 for an outs_of that is not taken.
+ *
+ * bpp_outs_shapes: the rule as a function, for callers that frame streams.  Host only, no device, no context.
+ * m_of_out[i] = 2^ceil(log2 outs_of[i]); BPP_E_ARG naming i for outs_of[i] = 0 or above cap_m; count = 0 is BPP_OK.
+ * bpp_outputs_make* need no ragged form: they are per output, j < outs_of[i]. */
+int bpp_outs_shapes(const uint32_t *outs_of, size_t count, size_t cap_m, uint32_t *m_of_out);
+
+/* bpp_range_prove_batch_serialized_mixed[_device] over a ragged block: d_v, d_gamma hold sum(outs) entries, the commitment
+ * buffer gets sum(outs) encodings, the containers are those of the shapes bpp_outs_shapes names.  flags: BPP_SER_TRANSCRIPT |
+ * BPP_SER_UNCOMPRESSED | BPP_PROVE_AMOUNT64. */
+size_t bpp_prover_serialized_outs_workspace_bytes(const bpp_verifier *engine, const uint32_t *outs_of, size_t count);
+int bpp_range_prove_batch_serialized_outs_device(bpp_verifier *engine, const uint64_t *d_v, const uint64_t *d_gamma,
+                                                 const uint32_t *outs_of, size_t count, int flags, const uint8_t *blind_key,
+                                                 uint64_t index_base, const uint64_t *d_blinding, void *d_out_proofs,
+                                                 void *d_out_commitments, void *d_workspace, size_t workspace_bytes,
+                                                 void *stream);
+int bpp_range_prove_batch_serialized_outs(bpp_verifier *engine, const uint64_t *v, const uint64_t *gamma, const uint32_t *outs_of,
+                                          size_t count, int flags, const uint8_t *blind_key, uint64_t index_base,
+                                          uint8_t *out_proofs, uint8_t *out_commitments);
+
+/* bpp_range_verify_batch_serialized_mixed[_device] over a ragged block: d_ok is 0, 1 or 2 in caller order, FormatError first
+ * as there.  A container whose header m is not the M of outs_of[i] is a FormatError of that proof only. */
+size_t bpp_verifier_serialized_outs_workspace_bytes(const bpp_verifier *v, const uint32_t *outs_of, size_t count);
+int bpp_range_verify_batch_serialized_outs_device(bpp_verifier *v, const void *d_proofs, const void *d_commitments,
+                                                  const uint32_t *outs_of, size_t count, int flags, uint32_t *d_ok,
+                                                  void *d_workspace, size_t workspace_bytes, void *stream);
+int bpp_range_verify_batch_serialized_outs(bpp_verifier *v, const uint8_t *proofs, const uint8_t *commitments,
+                                           const uint32_t *outs_of, size_t count, int flags, uint32_t *out_ok);
+
+/* bpp_range_verify_batch_serialized_grouped_mixed_device over a ragged block: the same front, the grouped back end. */
+size_t bpp_verifier_serialized_grouped_outs_workspace_bytes(const bpp_verifier *v, const uint32_t *outs_of, size_t count,
+                                                            uint32_t group);
+int bpp_range_verify_batch_serialized_grouped_outs_device(bpp_verifier *v, const void *d_proofs, const void *d_commitments,
+                                                          const uint32_t *outs_of, size_t count, int flags,
+                                                          const uint8_t *weight_key, uint64_t index_base, uint32_t group,
+                                                          uint32_t *d_ok, uint64_t *stats, void *d_workspace,
+                                                          size_t workspace_bytes, void *stream);
+
+/* bpp_range_verify_find_outputs_serialized_mixed_keys[_device] over a ragged block: d_sealed and d_tags are per REAL output
+ * (sum of outs_of[i] entries), output numbers in hit records count real outputs only, o = (sum of outs_of[i'] over i' < i) + j
+ * with j < outs_of[i], and the pair bound is n_keys x sum(outs).  d_ok is word for word the verify call's above. */
+size_t bpp_verify_find_outputs_outs_workspace_bytes(const bpp_verifier *v, const uint32_t *outs_of, size_t count, size_t n_keys);
+int bpp_range_verify_find_outputs_serialized_outs_keys_device(bpp_verifier *v, const void *d_proofs, const void *d_commitments,
+                                                              const uint32_t *outs_of, size_t count, int flags,
+                                                              const uint8_t *d_keys, size_t n_keys, uint64_t index_base,
+                                                              const uint64_t *d_index, const uint64_t *d_sealed,
+                                                              const uint8_t *d_tags, uint32_t *d_ok, uint32_t *d_hits,
+                                                              size_t max_hits, uint32_t *d_n_hits, uint32_t *d_n_candidates,
+                                                              void *d_workspace, size_t workspace_bytes, void *stream);
+int bpp_range_verify_find_outputs_serialized_outs_keys(bpp_verifier *v, const uint8_t *proofs, const uint8_t *commitments,
+                                                       const uint32_t *outs_of, size_t count, int flags, const uint8_t *keys,
+                                                       size_t n_keys, uint64_t index_base, const uint64_t *index,
+                                                       const uint64_t *sealed, const uint8_t *tags, uint32_t *out_ok,
+                                                       uint32_t *out_hits, size_t max_hits, uint32_t *out_n_hits,
+                                                       uint32_t *out_n_candidates);
 
 /* ---- the weighted inner product argument as a seam of its own: WeightedInnerProductProof::{prove, verify} ----
  * Reference: src/weighted_inner_product_proof.rs:36-227 (prove), :238-328 (verify), :330-382 (verification_scalars).

@@ -483,6 +483,98 @@ inline FindTaggedResult verify_find_outputs_serialized_mixed_keys(
     return r;
 }
 
+// ---- proofs over ANY number of outputs (bpp_amd.h: the section of that name).  outs[i] in [1, m]: proof i is the proof of
+// shape (n, 2^ceil(log2 outs[i])) over its values and masks padded with zeros; the streams carry the real outputs alone.
+// The aggregation sizes of such a block, for an engine of capacity m (bpp_outs_shapes)
+inline std::vector<uint32_t> outs_shapes(const std::vector<uint32_t>& outs, size_t m) {
+    std::vector<uint32_t> ms(outs.size() + 1);
+    if (bpp_outs_shapes(outs.data(), outs.size(), m, ms.data()) != BPP_OK)
+        throw std::runtime_error(std::string("bpp_outs_shapes: ") + bpp_last_error());
+    ms.resize(outs.size());
+    return ms;
+}
+
+// Proves a ragged block (bpp_range_prove_batch_serialized_outs): values and gammas hold sum(outs) entries (gammas: 4 words
+// each).  proof_bytes, point_bytes: of the whole container stream and of one encoded point, as the caller frames them
+// (bpp_proof_bytes_version over outs_shapes; bpp_point_compressed_bytes / _uncompressed_bytes).
+struct ProvedOutputs {
+    std::vector<uint8_t> proofs, commitments;
+};
+inline ProvedOutputs prove_serialized_outputs(bpp_verifier* engine, const std::vector<uint64_t>& values,
+                                              const std::vector<uint64_t>& gammas, const std::vector<uint32_t>& outs,
+                                              size_t proof_bytes, size_t point_bytes, int flags = 0,
+                                              const uint8_t* blind_key = nullptr, uint64_t index_base = 0) {
+    size_t n_out = 0;
+    for (uint32_t o : outs) n_out += o;
+    if (values.size() != n_out || gammas.size() != n_out * 4)
+        throw std::logic_error("prove_serialized_outputs: one value and one gamma per output");
+    ProvedOutputs r;
+    r.proofs.assign(proof_bytes + 1, 0);
+    r.commitments.assign(n_out * point_bytes + 1, 0);
+    if (bpp_range_prove_batch_serialized_outs(engine, values.data(), gammas.data(), outs.data(), outs.size(), flags, blind_key,
+                                              index_base, r.proofs.data(), r.commitments.data()) != BPP_OK)
+        throw std::runtime_error(std::string("bpp_range_prove_batch_serialized_outs: ") + bpp_last_error());
+    r.proofs.resize(proof_bytes);
+    r.commitments.resize(n_out * point_bytes);
+    return r;
+}
+
+// Verifies a ragged block (bpp_range_verify_batch_serialized_outs): outs[i] encoded commitments per proof -> one status per
+// proof, 0 Ok / 1 VerificationError / 2 FormatError
+inline std::vector<uint32_t> verify_serialized_outputs(bpp_verifier* engine, const std::vector<uint8_t>& proofs,
+                                                       const std::vector<uint8_t>& commitments, const std::vector<uint32_t>& outs,
+                                                       int flags = 0) {
+    std::vector<uint32_t> ok(outs.size() + 1);
+    if (bpp_range_verify_batch_serialized_outs(engine, proofs.data(), commitments.data(), outs.data(), outs.size(), flags,
+                                               ok.data()) != BPP_OK)
+        throw std::runtime_error(std::string("bpp_range_verify_batch_serialized_outs: ") + bpp_last_error());
+    ok.resize(outs.size());
+    return ok;
+}
+
+// verify_find_outputs_serialized_mixed_keys over a ragged block (bpp_range_verify_find_outputs_serialized_outs_keys): sealed
+// and tags hold one entry per REAL output (sum of outs); a hit's `position` counts real outputs only
+inline FindTaggedResult verify_find_outputs_serialized_outs_keys(
+    bpp_verifier* engine, const std::vector<uint8_t>& proofs, const std::vector<uint8_t>& commitments,
+    const std::vector<uint32_t>& outs, const std::vector<std::array<uint8_t, 32>>& keys, const std::vector<uint64_t>& sealed,
+    const std::vector<uint8_t>& tags, size_t max_hits, uint64_t index_base = 0, const std::vector<uint64_t>& index = {},
+    bool amount64 = false, bool uncompressed = false) {
+    size_t n_out = 0;
+    for (uint32_t o : outs) n_out += o;
+    const size_t pairs = keys.size() * n_out;
+    if (!index.empty() && index.size() != outs.size())
+        throw std::logic_error("verify_find_outputs_serialized_outs_keys: one index per proof");
+    if (sealed.size() != n_out || tags.size() != n_out)
+        throw std::logic_error("verify_find_outputs_serialized_outs_keys: one sealed amount and one tag per output");
+    const size_t cap = std::min(max_hits, pairs);
+    FindTaggedResult r;
+    r.ok.assign(outs.size() + 1, 0);
+    std::vector<uint32_t> rec(cap * 12 + 1);
+    std::vector<uint8_t> packed(keys.size() * 32 + 1);
+    for (size_t j = 0; j < keys.size(); j++)
+        for (size_t t = 0; t < 32; t++) packed[j * 32 + t] = keys[j][t];
+    const int flags = BPP_SER_TRANSCRIPT | (uncompressed ? BPP_SER_UNCOMPRESSED : 0) | (amount64 ? BPP_PROVE_AMOUNT64 : 0);
+    uint32_t found = 0, candidates = 0;
+    const int rc = bpp_range_verify_find_outputs_serialized_outs_keys(
+        engine, proofs.data(), commitments.data(), outs.data(), outs.size(), flags, packed.data(), keys.size(), index_base,
+        index.empty() ? nullptr : index.data(), sealed.data(), tags.data(), r.ok.data(), rec.data(), cap, &found, &candidates);
+    for (volatile uint8_t& b : packed) b = 0;   // the packed copy of the keys made here
+    if (rc != BPP_OK)
+        throw std::runtime_error(std::string("bpp_range_verify_find_outputs_serialized_outs_keys: ") + bpp_last_error());
+    r.ok.resize(outs.size());
+    r.found = found;
+    r.candidates = candidates;
+    r.hits.resize(std::min<size_t>(found, cap));
+    for (size_t h = 0; h < r.hits.size(); h++) {
+        const uint32_t* w = rec.data() + h * 12;
+        r.hits[h].key_no = w[0];
+        r.hits[h].position = w[1];
+        r.hits[h].amount = (uint64_t)w[2] | (uint64_t)w[3] << 32;
+        for (int t = 0; t < 4; t++) r.hits[h].mask.e[t] = (uint64_t)w[4 + 2 * t] | (uint64_t)w[5 + 2 * t] << 32;
+    }
+    return r;
+}
+
 // Verifier-side holder of the commitments.  It exists only in the reference's (stale) README
 // (README.md:47-55: RangeVerifier::new(), allocate(&prover.commitment_vec), proof.verify(.., &verifier));
 // the reference's code takes the commitment slice directly (range/mod.rs:57-62).  Both forms are offered.
