@@ -1,7 +1,8 @@
 // capi.hip -- the extern "C" boundary of libbpp_amd.so (declared in include/bpp_amd.h).  Thin: argument
 // checks, the entry shim, curve dispatch, then the per-curve implementations (impl_*.hpp, compiled in tu_*.hip) and the
-// literal single-call API (literal.hpp).  The verifier's and the prover's entries fill an argument record and pass ONE check
-// each (verify_args.hpp verify_args; prove_args below), which hold what tells their entries apart as data.  No buffer is
+// literal single-call API (literal.hpp).  The verifier's, the prover's and the receiver's entries fill an argument record and
+// pass ONE check each (verify_args.hpp verify_args; prove_args below; scan_args.hpp scan_args for recovery and the scans,
+// find_args for verify-and-find), which hold what tells their entries apart as data.  No buffer is
 // staged here: the host forms live in the *Impl<C> structs as *_host.
 // No CPU fallback: every entry point launches HIP kernels on the context's device.
 #include "codec.hpp"
@@ -65,6 +66,7 @@ size_t size_for(const bpp_verifier* v, F&& f) {
 // The verifier entries: each fills its record in the C ABI's order and passes verify_args (verify_args.hpp), which is told
 // this much of the handle and answers an empty batch itself.
 VerifierFacts facts(const bpp_verifier* v) { return v ? VerifierFacts{true, v->ctx.curve, v->s.n, v->s.m} : VerifierFacts{}; }
+static_assert(SCAN_ANSWERED == VERIFY_ANSWERED, "answered() serves verify_args and scan_args");
 int answered(int rc) { return rc == VERIFY_ANSWERED ? BPP_OK : rc; }
 hipStream_t hip(void* stream) { return static_cast<hipStream_t>(stream); }
 // mean milliseconds per stage over the first `passes` passes of an event ring: pass p's stage t runs from
@@ -978,37 +980,11 @@ extern "C" int bpp_commit_batch(bpp_verifier* engine, const uint64_t* v, const u
     });
 }
 
-// ---- mask recovery and scanning (recover.hpp; the quantities inverted: range/mod.rs:159-172, wip.rs:94-95,175-227) ----
-namespace {
-// What the recovery and scan calls can answer before the engine handle is read: an m_i no engine takes (zero, or not a
-// power of two; one above the engine's m is the plan's to name), the blinding rules, a workspace of no bytes.
-// Runs under the guard itself (the error text is built on the heap).
-// the first position whose m_i no engine takes, or count where there is none
-size_t first_bad_m(const uint32_t* m_of, size_t count) noexcept {
-    size_t i = 0;
-    while (i < count && m_of[i] != 0 && !(m_of[i] & (m_of[i] - 1))) i++;
-    return i;
-}
-bool m_of_wellformed(const uint32_t* m_of, size_t count) noexcept { return first_bad_m(m_of, count) == count; }
-// the same as an answer that names the position; for a caller under the guard
-int m_of_checked(const uint32_t* m_of, size_t count) {
-    const size_t i = first_bad_m(m_of, count);
-    if (i == count) return BPP_OK;
-    return fail(BPP_E_ARG, "m_of[" + std::to_string(i) + "] = " + std::to_string(m_of[i]) + ": not a power of two");
-}
-int recover_args(const uint32_t* m_of, size_t count, const uint8_t* blind_key, const void* index, const void* blinding) noexcept {
-    return guarded([&]() -> int {
-        if (blind_key && blinding) return fail(BPP_E_ARG, "blind_key and d_blinding are both given");
-        if (index && !blind_key) return fail(BPP_E_ARG, "d_index is the index of a blind_key: it needs one");
-        if (count > 0x7fffffffu / 64) return fail(BPP_E_ARG, "count too large for one launch");
-        return m_of_checked(m_of, count);
-    });
-}
-constexpr int SCAN_FLAGS = BPP_SER_TRANSCRIPT | BPP_SER_UNCOMPRESSED | BPP_PROVE_AMOUNT64;
-}  // namespace
-
+// ---- mask recovery and scanning (recover.hpp; the quantities inverted: range/mod.rs:159-172, wip.rs:94-95,175-227), under
+// one key and under many (recover_keys.hpp: the front and the inversions once, n_keys x count pairs).  Each entry fills its
+// record and passes scan_args (scan_args.hpp), which answers an empty call itself ----
 extern "C" size_t bpp_recover_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
-    if ((count && !m_of) || count > 0x7fffffffu / 64 || !m_of_wellformed(m_of, count)) return 0;
+    if ((count && !m_of) || count > ONE_LAUNCH || !m_of_wellformed(m_of, count)) return 0;
     return size_for(v, [&](auto cv) { return RecoverImpl<decltype(cv)>::recover_workspace_bytes(v, m_of, count); });
 }
 
@@ -1016,16 +992,12 @@ extern "C" int bpp_range_recover_masks_mixed_device(bpp_verifier* v, const uint6
                                                     const uint64_t* d_challenges, const uint8_t* blind_key, uint64_t index_base,
                                                     const uint64_t* d_index, const uint64_t* d_blinding, uint64_t* d_out_masks,
                                                     void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!v) return fail(BPP_E_ARG, "null argument");
-    if (count == 0) return BPP_OK;
-    if (!d_scalars || !m_of || !d_out_masks || !d_workspace) return fail(BPP_E_ARG, "null argument");
-    if (int rc = recover_args(m_of, count, blind_key, d_index, d_blinding)) return rc;
-    if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
+    ScanArgs a;
+    a.scalars = d_scalars; a.m_of = m_of; a.count = count; a.challenges = d_challenges;
+    a.blind_key = blind_key; a.index_base = index_base; a.index = d_index; a.blinding = d_blinding; a.out_masks = d_out_masks;
+    if (int rc = scan_args(SCAN_RECOVER_DEVICE, v != nullptr, 0, a, d_workspace, workspace_bytes)) return answered(rc);
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        using R = RecoverImpl<decltype(cv)>;
-        return R::recover_masks_mixed(v, d_scalars, m_of, count, d_challenges,
-                                      typename R::Blinding{blind_key, index_base, d_index, d_blinding}, d_out_masks, d_workspace,
-                                      workspace_bytes, static_cast<hipStream_t>(stream));
+        return RecoverImpl<decltype(cv)>::recover_masks_mixed(v, a, d_workspace, workspace_bytes, hip(stream));
     });
 }
 
@@ -1033,18 +1005,15 @@ extern "C" int bpp_range_recover_masks_mixed_device(bpp_verifier* v, const uint6
 extern "C" int bpp_range_recover_masks_mixed(bpp_verifier* v, const uint64_t* scalars, const uint32_t* m_of, size_t count,
                                              const uint64_t* challenges, const uint8_t* blind_key, uint64_t index_base,
                                              const uint64_t* index, const uint64_t* blinding, uint64_t* out_masks) {
-    if (!v) return fail(BPP_E_ARG, "null argument");
-    if (count == 0) return BPP_OK;
-    if (!scalars || !m_of || !out_masks) return fail(BPP_E_ARG, "null argument");
-    if (int rc = recover_args(m_of, count, blind_key, index, blinding)) return rc;
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return RecoverImpl<decltype(cv)>::recover_masks_mixed_host(v, scalars, m_of, count, challenges, blind_key, index_base,
-                                                                   index, blinding, out_masks);
-    });
+    ScanArgs a;
+    a.scalars = scalars; a.m_of = m_of; a.count = count; a.challenges = challenges;
+    a.blind_key = blind_key; a.index_base = index_base; a.index = index; a.blinding = blinding; a.out_masks = out_masks;
+    if (int rc = scan_args(SCAN_RECOVER_HOST, v != nullptr, 0, a, nullptr, 0)) return answered(rc);
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int { return RecoverImpl<decltype(cv)>::recover_masks_mixed_host(v, a); });
 }
 
 extern "C" size_t bpp_scan_serialized_mixed_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count) {
-    if ((count && !m_of) || count > 0x7fffffffu / 64 || !m_of_wellformed(m_of, count)) return 0;
+    if ((count && !m_of) || count > ONE_LAUNCH || !m_of_wellformed(m_of, count)) return 0;
     return size_for(v, [&](auto cv) { return RecoverImpl<decltype(cv)>::scan_workspace_bytes(v, m_of, count); });
 }
 
@@ -1053,20 +1022,13 @@ extern "C" int bpp_range_scan_serialized_mixed_device(bpp_verifier* v, const voi
                                                       uint64_t index_base, const uint64_t* d_index, const uint64_t* d_blinding,
                                                       const uint64_t* d_amounts, uint64_t* d_out_masks, uint32_t* d_status,
                                                       void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!v) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~SCAN_FLAGS) return fail(BPP_E_ARG, "unknown flag");
-    if (count == 0) return BPP_OK;
-    if (!d_proofs || !d_commitments || !m_of || !d_out_masks || !d_status || !d_workspace) return fail(BPP_E_ARG, "null argument");
-    if (int rc = recover_args(m_of, count, blind_key, d_index, d_blinding)) return rc;
-    if ((blind_key || d_blinding) && !(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
-    if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
+    ScanArgs a;
+    a.proofs = static_cast<const uint8_t*>(d_proofs); a.commitments = static_cast<const uint8_t*>(d_commitments);
+    a.m_of = m_of; a.count = count; a.blind_key = blind_key; a.index_base = index_base; a.index = d_index; a.blinding = d_blinding;
+    a.amounts = d_amounts; a.out_masks = d_out_masks; a.out_status = d_status;
+    if (int rc = scan_args(SCAN_ONE_KEY_DEVICE, v != nullptr, flags, a, d_workspace, workspace_bytes)) return answered(rc);
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        using R = RecoverImpl<decltype(cv)>;
-        return R::scan_serialized_mixed(v, static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), m_of,
-                                        count, (flags & BPP_SER_TRANSCRIPT) != 0, (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u,
-                                        (flags & BPP_PROVE_AMOUNT64) != 0,
-                                        typename R::Blinding{blind_key, index_base, d_index, d_blinding}, d_amounts, d_out_masks,
-                                        d_status, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+        return RecoverImpl<decltype(cv)>::scan_serialized_mixed(v, a, d_workspace, workspace_bytes, hip(stream));
     });
 }
 
@@ -1075,50 +1037,13 @@ extern "C" int bpp_range_scan_serialized_mixed(bpp_verifier* v, const uint8_t* p
                                                const uint32_t* m_of, size_t count, int flags, const uint8_t* blind_key,
                                                uint64_t index_base, const uint64_t* index, const uint64_t* blinding,
                                                const uint64_t* amounts, uint64_t* out_masks, uint32_t* out_status) {
-    if (!v) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~SCAN_FLAGS) return fail(BPP_E_ARG, "unknown flag");
-    if (count == 0) return BPP_OK;
-    if (!proofs || !commitments || !m_of || !out_masks || !out_status) return fail(BPP_E_ARG, "null argument");
-    if (int rc = recover_args(m_of, count, blind_key, index, blinding)) return rc;
-    if ((blind_key || blinding) && !(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, "blinding needs BPP_SER_TRANSCRIPT");
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return RecoverImpl<decltype(cv)>::scan_serialized_mixed_host(v, proofs, commitments, m_of, count, flags, blind_key,
-                                                                     index_base, index, blinding, amounts, out_masks, out_status);
-    });
+    ScanArgs a;
+    a.proofs = proofs; a.commitments = commitments; a.m_of = m_of; a.count = count;
+    a.blind_key = blind_key; a.index_base = index_base; a.index = index; a.blinding = blinding;
+    a.amounts = amounts; a.out_masks = out_masks; a.out_status = out_status;
+    if (int rc = scan_args(SCAN_ONE_KEY_HOST, v != nullptr, flags, a, nullptr, 0)) return answered(rc);
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int { return RecoverImpl<decltype(cv)>::scan_serialized_mixed_host(v, a); });
 }
-
-// ---- scanning under many keys (recover_keys.hpp): the front and the inversions once, n_keys x count pairs ----
-namespace {
-constexpr size_t PAIR_BOUND = 0x7fffffffu / 64;
-// n_keys x units within the bound the other entries put on count alone, without forming a product that can wrap
-bool pairs_bounded(size_t n_keys, size_t units) noexcept {
-    return n_keys <= PAIR_BOUND && units <= PAIR_BOUND && (n_keys == 0 || units <= PAIR_BOUND / n_keys);
-}
-// What each key of a call is paired with: the proofs of the block, or (per_output) their outputs, the sum of m_i.  No sum
-// that can wrap: m_of is read only once count itself is within the bound, and no further than the sum is.
-size_t pair_units(const uint32_t* m_of, size_t count, bool per_output) noexcept {
-    if (!per_output || count > PAIR_BOUND) return count;
-    size_t n_out = 0;
-    for (size_t i = 0; i < count && n_out <= PAIR_BOUND; i++) n_out += m_of[i];   // each below 2^32
-    return n_out;
-}
-// the two answers that name what a call pairs its keys with
-struct PairTexts {
-    const char *too_large, *transcript;
-};
-constexpr PairTexts PROOF_PAIRS = {"n_keys x count too large for one launch", "blinding needs BPP_SER_TRANSCRIPT"};
-constexpr PairTexts OUTPUT_PAIRS = {"n_keys x n_out too large for one launch", "the verdicts need BPP_SER_TRANSCRIPT"};
-// what the many-key scan and the find calls can answer before the engine handle is read (runs under the guard itself)
-int scan_keys_args(const uint32_t* m_of, size_t count, size_t n_keys, int flags, bool per_output = false) noexcept {
-    return guarded([&]() -> int {
-        const PairTexts& text = per_output ? OUTPUT_PAIRS : PROOF_PAIRS;
-        if (!pairs_bounded(n_keys, pair_units(m_of, count, per_output))) return fail(BPP_E_ARG, text.too_large);
-        if (int rc = m_of_checked(m_of, count)) return rc;
-        if (!(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, text.transcript);
-        return BPP_OK;
-    });
-}
-}  // namespace
 
 extern "C" size_t bpp_scan_serialized_mixed_keys_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count,
                                                                  size_t n_keys) {
@@ -1131,20 +1056,13 @@ extern "C" int bpp_range_scan_serialized_mixed_keys_device(bpp_verifier* v, cons
                                                            size_t n_keys, uint64_t index_base, const uint64_t* d_index,
                                                            const uint64_t* d_amounts, uint64_t* d_out_masks, uint32_t* d_status,
                                                            void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!v) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~SCAN_FLAGS) return fail(BPP_E_ARG, "unknown flag");
-    if (count == 0 || n_keys == 0) return BPP_OK;
-    if (!d_proofs || !d_commitments || !m_of || !d_keys || !d_out_masks || !d_status || !d_workspace)
-        return fail(BPP_E_ARG, "null argument");
-    if (reinterpret_cast<uintptr_t>(d_keys) & 3) return fail(BPP_E_ARG, "d_keys must be 4-byte aligned");
-    if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
-    if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
+    ScanArgs a;
+    a.proofs = static_cast<const uint8_t*>(d_proofs); a.commitments = static_cast<const uint8_t*>(d_commitments);
+    a.m_of = m_of; a.count = count; a.keys = d_keys; a.n_keys = n_keys; a.index_base = index_base; a.index = d_index;
+    a.amounts = d_amounts; a.out_masks = d_out_masks; a.out_status = d_status;
+    if (int rc = scan_args(SCAN_MANY_KEYS_DEVICE, v != nullptr, flags, a, d_workspace, workspace_bytes)) return answered(rc);
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return RecoverKeysImpl<decltype(cv)>::scan(v, static_cast<const uint8_t*>(d_proofs),
-                                                   static_cast<const uint8_t*>(d_commitments), m_of, count,
-                                                   (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u, (flags & BPP_PROVE_AMOUNT64) != 0,
-                                                   d_keys, n_keys, index_base, d_index, d_amounts, d_out_masks, d_status,
-                                                   d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+        return RecoverKeysImpl<decltype(cv)>::scan(v, a, d_workspace, workspace_bytes, hip(stream));
     });
 }
 
@@ -1153,22 +1071,17 @@ extern "C" int bpp_range_scan_serialized_mixed_keys(bpp_verifier* v, const uint8
                                                     const uint32_t* m_of, size_t count, int flags, const uint8_t* keys,
                                                     size_t n_keys, uint64_t index_base, const uint64_t* index,
                                                     const uint64_t* amounts, uint64_t* out_masks, uint32_t* out_status) {
-    if (!v) return fail(BPP_E_ARG, "null argument");
-    if (flags & ~SCAN_FLAGS) return fail(BPP_E_ARG, "unknown flag");
-    if (count == 0 || n_keys == 0) return BPP_OK;
-    if (!proofs || !commitments || !m_of || !keys || !out_masks || !out_status) return fail(BPP_E_ARG, "null argument");
-    if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
-    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return RecoverKeysImpl<decltype(cv)>::scan_host(v, proofs, commitments, m_of, count, flags, keys, n_keys, index_base,
-                                                        index, amounts, out_masks, out_status);
-    });
+    ScanArgs a;
+    a.proofs = proofs; a.commitments = commitments; a.m_of = m_of; a.count = count;
+    a.keys = keys; a.n_keys = n_keys; a.index_base = index_base; a.index = index;
+    a.amounts = amounts; a.out_masks = out_masks; a.out_status = out_status;
+    if (int rc = scan_args(SCAN_MANY_KEYS_HOST, v != nullptr, flags, a, nullptr, 0)) return answered(rc);
+    return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int { return RecoverKeysImpl<decltype(cv)>::scan_host(v, a); });
 }
 
 // ---- sealed amounts, view tags, and verifying a block while listing the outputs of many keys, with tags or without
 // (find.hpp) ----
 namespace {
-constexpr int FIND_FLAGS = SCAN_FLAGS | BPP_FIND_AMOUNTS_SEALED;
-
 // The checks of the four entries that expand one key over `count` outputs (seal and tag, device and host); count = 0 passes
 // them and is answered by the entry.  buffers: whether every buffer that a count above zero reads or writes, the optional
 // index aside, is there.
@@ -1180,39 +1093,20 @@ int key_stream_args(const bpp_ctx* ctx, const uint8_t* blind_key, size_t count, 
     return BPP_OK;
 }
 
-// no proof: no verdict, no candidate, no hit -- the counts a find entry answers with, on the device or on the host
-int find_nothing(const bpp_verifier* v, const FindArgs& a, bool device, hipStream_t st) noexcept {
+// What a find entry returns when find_args (scan_args.hpp) did not say go on: its error, or for an empty call BPP_OK behind
+// the counts it answers with -- no proof: no verdict, no candidate, no hit -- zeroed on the device or on the host
+int find_nothing(int rc, const bpp_verifier* v, const FindArgs& a, bool device, void* stream) noexcept {
+    if (rc != SCAN_ANSWERED) return rc;
     if (!device) {
         *a.n_hits = 0;
         if (a.n_candidates) *a.n_candidates = 0;
         return BPP_OK;
     }
     return on_device(v->ctx.device, [&]() -> int {
-        HIPCHK(zero_words_async(a.n_hits, 4, st));
-        if (a.n_candidates) HIPCHK(zero_words_async(a.n_candidates, 4, st));
+        HIPCHK(zero_words_async(a.n_hits, 4, hip(stream)));
+        if (a.n_candidates) HIPCHK(zero_words_async(a.n_candidates, 4, hip(stream)));
         return BPP_OK;
     });
-}
-
-// The checks of the six find entries, whatever the mode, that come before scan_keys_args; count = 0 passes them and is
-// answered by find_nothing.  a holds the entry's pointers, the device's (device: with a workspace) or the host's, and leaves
-// with what the flags say.  Without keys the block is verified all the same: the call IS a verification, and ok is never
-// left unwritten.
-int find_args(const bpp_verifier* v, int flags, FindArgs& a, bool device, const void* d_workspace) noexcept {
-    const bool per_output = a.mode == FIND_PER_OUTPUT;
-    if (!v || !a.n_hits) return fail(BPP_E_ARG, "null argument");
-    if (per_output && (flags & BPP_FIND_AMOUNTS_SEALED))
-        return fail(BPP_E_ARG, "BPP_FIND_AMOUNTS_SEALED is not taken: amounts are always sealed here");
-    if (flags & ~FIND_FLAGS) return fail(BPP_E_ARG, "unknown flag");
-    a.version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
-    a.amount64 = (flags & BPP_PROVE_AMOUNT64) != 0;
-    a.sealed = per_output || (flags & BPP_FIND_AMOUNTS_SEALED) != 0;
-    if (a.count == 0) return BPP_OK;
-    if (!a.proofs || !a.commitments || (!a.m_of && !a.outs_of) || !a.ok || (device && !d_workspace)) return fail(BPP_E_ARG, "null argument");
-    if (a.n_keys && (!a.keys || !a.amounts || (a.tagged() && !a.tags) || (!a.hits && a.max_hits)))
-        return fail(BPP_E_ARG, "null argument");
-    if (device && a.n_keys && (reinterpret_cast<uintptr_t>(a.keys) & 3)) return fail(BPP_E_ARG, "d_keys must be 4-byte aligned");
-    return BPP_OK;
 }
 }  // namespace
 
@@ -1272,12 +1166,9 @@ extern "C" int bpp_range_verify_find_serialized_mixed_keys_device(bpp_verifier* 
                                                                   void* stream) {
     FindArgs a{static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), m_of, count, d_keys, n_keys,
                index_base, d_index, d_amounts, d_ok, d_hits, max_hits, d_n_hits, FIND_REWIND, nullptr, nullptr};
-    if (int rc = find_args(v, flags, a, true, d_workspace)) return rc;
-    if (count == 0) return find_nothing(v, a, true, static_cast<hipStream_t>(stream));
-    if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
-    if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
+    if (int rc = find_args(v != nullptr, flags, a, true, d_workspace, workspace_bytes)) return find_nothing(rc, v, a, true, stream);
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return FindImpl<decltype(cv)>::find(v, a, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+        return FindImpl<decltype(cv)>::find(v, a, d_workspace, workspace_bytes, hip(stream));
     });
 }
 
@@ -1289,9 +1180,7 @@ extern "C" int bpp_range_verify_find_serialized_mixed_keys(bpp_verifier* v, cons
                                                            size_t max_hits, uint32_t* out_n_hits) {
     FindArgs a{proofs, commitments, m_of,     count,    keys,       n_keys, index_base, index,
                amounts, out_ok,     out_hits, max_hits, out_n_hits, FIND_REWIND, nullptr, nullptr};
-    if (int rc = find_args(v, flags, a, false, nullptr)) return rc;
-    if (count == 0) return find_nothing(v, a, false, nullptr);
-    if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
+    if (int rc = find_args(v != nullptr, flags, a, false, nullptr, 0)) return find_nothing(rc, v, a, false, nullptr);
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int { return FindImpl<decltype(cv)>::find_host(v, a); });
 }
 
@@ -1302,12 +1191,9 @@ extern "C" int bpp_range_verify_find_tagged_serialized_mixed_keys_device(
     size_t workspace_bytes, void* stream) {
     FindArgs a{static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), m_of, count, d_keys, n_keys,
                index_base, d_index, d_amounts, d_ok, d_hits, max_hits, d_n_hits, FIND_REWIND_TAGGED, d_tags, d_n_candidates};
-    if (int rc = find_args(v, flags, a, true, d_workspace)) return rc;
-    if (count == 0) return find_nothing(v, a, true, static_cast<hipStream_t>(stream));
-    if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
-    if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
+    if (int rc = find_args(v != nullptr, flags, a, true, d_workspace, workspace_bytes)) return find_nothing(rc, v, a, true, stream);
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return FindImpl<decltype(cv)>::find(v, a, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+        return FindImpl<decltype(cv)>::find(v, a, d_workspace, workspace_bytes, hip(stream));
     });
 }
 
@@ -1318,9 +1204,7 @@ extern "C" int bpp_range_verify_find_tagged_serialized_mixed_keys(
     uint32_t* out_hits, size_t max_hits, uint32_t* out_n_hits, const uint8_t* tags, uint32_t* out_n_candidates) {
     FindArgs a{proofs, commitments, m_of,     count,    keys,       n_keys, index_base, index,
                amounts, out_ok,     out_hits, max_hits, out_n_hits, FIND_REWIND_TAGGED, tags, out_n_candidates};
-    if (int rc = find_args(v, flags, a, false, nullptr)) return rc;
-    if (count == 0) return find_nothing(v, a, false, nullptr);
-    if (int rc = scan_keys_args(m_of, count, n_keys, flags)) return rc;
+    if (int rc = find_args(v != nullptr, flags, a, false, nullptr, 0)) return find_nothing(rc, v, a, false, nullptr);
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int { return FindImpl<decltype(cv)>::find_host(v, a); });
 }
 
@@ -1373,12 +1257,9 @@ extern "C" int bpp_range_verify_find_outputs_serialized_mixed_keys_device(
     void* d_workspace, size_t workspace_bytes, void* stream) {
     FindArgs a{static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), m_of, count, d_keys, n_keys,
                index_base, d_index, d_sealed, d_ok, d_hits, max_hits, d_n_hits, FIND_PER_OUTPUT, d_tags, d_n_candidates};
-    if (int rc = find_args(v, flags, a, true, d_workspace)) return rc;
-    if (count == 0) return find_nothing(v, a, true, static_cast<hipStream_t>(stream));
-    if (int rc = scan_keys_args(m_of, count, n_keys, flags, true)) return rc;
-    if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
+    if (int rc = find_args(v != nullptr, flags, a, true, d_workspace, workspace_bytes)) return find_nothing(rc, v, a, true, stream);
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return OutputsImpl<decltype(cv)>::find(v, a, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+        return OutputsImpl<decltype(cv)>::find(v, a, d_workspace, workspace_bytes, hip(stream));
     });
 }
 
@@ -1389,26 +1270,13 @@ extern "C" int bpp_range_verify_find_outputs_serialized_mixed_keys(
     uint32_t* out_ok, uint32_t* out_hits, size_t max_hits, uint32_t* out_n_hits, uint32_t* out_n_candidates) {
     FindArgs a{proofs, commitments, m_of,     count,    keys,       n_keys,          index_base, index,
                sealed, out_ok,      out_hits, max_hits, out_n_hits, FIND_PER_OUTPUT, tags,       out_n_candidates};
-    if (int rc = find_args(v, flags, a, false, nullptr)) return rc;
-    if (count == 0) return find_nothing(v, a, false, nullptr);
-    if (int rc = scan_keys_args(m_of, count, n_keys, flags, true)) return rc;
+    if (int rc = find_args(v != nullptr, flags, a, false, nullptr, 0)) return find_nothing(rc, v, a, false, nullptr);
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int { return OutputsImpl<decltype(cv)>::find_host(v, a); });
 }
 
 // ---- proofs over any number of outputs (outs_plan.hpp): proof i covers outs_of[i] outputs, is the proof of shape
 // (n, 2^ceil(log2 outs_of[i])) over values and masks padded with zeros, and the streams carry the real outputs alone.  The
 // entries of the serialized mixed calls with outs_of in m_of's place: the same records, the same checks, the same fronts ----
-namespace {
-// a count no engine takes (zero, or above the largest class): the size getters answer 0 before the handle is read;
-// outs_of is read only once count itself is within one launch
-bool outs_wellformed(const uint32_t* outs_of, size_t count) noexcept {
-    if ((count && !outs_of) || count > ONE_LAUNCH) return false;
-    for (size_t i = 0; i < count; i++)
-        if (outs_of[i] == 0 || outs_of[i] > (1u << (OUTS_CLASSES - 1))) return false;
-    return true;
-}
-}  // namespace
-
 extern "C" int bpp_outs_shapes(const uint32_t* outs_of, size_t count, size_t cap_m, uint32_t* m_of_out) {
     if (count && (!outs_of || !m_of_out)) return fail(BPP_E_ARG, "null argument");
     return guarded({count, "count"}, [&] { return outs_shapes(outs_of, count, cap_m, m_of_out); });
@@ -1502,25 +1370,9 @@ extern "C" int bpp_range_verify_batch_serialized_grouped_outs_device(bpp_verifie
     });
 }
 
-namespace {
-// the sum of outs_of, no further than the pair bound (no sum that can wrap: each count is below 2^32)
-size_t outs_units(const uint32_t* outs_of, size_t count) noexcept {
-    if (count > PAIR_BOUND) return count;
-    size_t n_out = 0;
-    for (size_t i = 0; i < count && n_out <= PAIR_BOUND; i++) n_out += outs_of[i];
-    return n_out;
-}
-// scan_keys_args for a ragged block: the counts themselves are the plan's to refuse, by name
-int find_outs_args(const uint32_t* outs_of, size_t count, size_t n_keys, int flags) noexcept {
-    if (!pairs_bounded(n_keys, outs_units(outs_of, count))) return fail(BPP_E_ARG, OUTPUT_PAIRS.too_large);
-    if (!(flags & BPP_SER_TRANSCRIPT)) return fail(BPP_E_ARG, OUTPUT_PAIRS.transcript);
-    return BPP_OK;
-}
-}  // namespace
-
 extern "C" size_t bpp_verify_find_outputs_outs_workspace_bytes(const bpp_verifier* v, const uint32_t* outs_of, size_t count,
                                                                size_t n_keys) {
-    if (!outs_wellformed(outs_of, count) || !pairs_bounded(n_keys, outs_units(outs_of, count))) return 0;
+    if (!outs_wellformed(outs_of, count) || !pairs_bounded(n_keys, pair_units(outs_of, count, true))) return 0;
     return size_for(v, [&](auto cv) { return OutputsImpl<decltype(cv)>::workspace_bytes(v, nullptr, count, n_keys, outs_of); });
 }
 
@@ -1532,12 +1384,9 @@ extern "C" int bpp_range_verify_find_outputs_serialized_outs_keys_device(
     FindArgs a{static_cast<const uint8_t*>(d_proofs), static_cast<const uint8_t*>(d_commitments), nullptr, count, d_keys, n_keys,
                index_base, d_index, d_sealed, d_ok, d_hits, max_hits, d_n_hits, FIND_PER_OUTPUT, d_tags, d_n_candidates};
     a.outs_of = outs_of;
-    if (int rc = find_args(v, flags, a, true, d_workspace)) return rc;
-    if (count == 0) return find_nothing(v, a, true, static_cast<hipStream_t>(stream));
-    if (int rc = find_outs_args(outs_of, count, n_keys, flags)) return rc;
-    if (workspace_bytes == 0) return fail(BPP_E_ARG, "workspace too small");
+    if (int rc = find_args(v != nullptr, flags, a, true, d_workspace, workspace_bytes)) return find_nothing(rc, v, a, true, stream);
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int {
-        return OutputsImpl<decltype(cv)>::find(v, a, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+        return OutputsImpl<decltype(cv)>::find(v, a, d_workspace, workspace_bytes, hip(stream));
     });
 }
 
@@ -1549,9 +1398,7 @@ extern "C" int bpp_range_verify_find_outputs_serialized_outs_keys(
     FindArgs a{proofs, commitments, nullptr,  count,    keys,       n_keys,          index_base, index,
                sealed, out_ok,      out_hits, max_hits, out_n_hits, FIND_PER_OUTPUT, tags,       out_n_candidates};
     a.outs_of = outs_of;
-    if (int rc = find_args(v, flags, a, false, nullptr)) return rc;
-    if (count == 0) return find_nothing(v, a, false, nullptr);
-    if (int rc = find_outs_args(outs_of, count, n_keys, flags)) return rc;
+    if (int rc = find_args(v != nullptr, flags, a, false, nullptr, 0)) return find_nothing(rc, v, a, false, nullptr);
     return on_ctx(v->ctx, {count, "count"}, [&](auto cv) -> int { return OutputsImpl<decltype(cv)>::find_host(v, a); });
 }
 

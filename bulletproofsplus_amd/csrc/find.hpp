@@ -60,6 +60,7 @@
 #pragma once
 #include "recover_keys.hpp"
 #include "find_terms.hpp"
+#include "scan_args.hpp"   // FindArgs, FindMode
 
 namespace bpp {
 
@@ -295,40 +296,6 @@ __global__ void __launch_bounds__(FIND_BLOCK) k_find_confirm_list(VerifyShape s,
     }
 }
 
-// how a call finds a key's outputs
-enum FindMode : uint32_t {
-    FIND_REWIND,          // single-output proofs are rewound under every key
-    FIND_REWIND_TAGGED,   // the same, for the pairs whose view tag matches
-    FIND_PER_OUTPUT,      // every output of every proof, by its derived mask (outputs.hpp)
-};
-
-// What a find call takes, in the C ABI's order but for the mode.  For a device entry the pointers are the device's (keys
-// 4-byte aligned), for find_host the host's.  n_keys = 0: the block is verified all the same (keys, amounts, tags unread),
-// no hit.  Per output, amounts and tags go by caller OUTPUT number (sum of m_i of them) and amounts are always sealed.
-struct FindArgs {
-    const uint8_t *proofs, *commitments;
-    const uint32_t* m_of;   // host, always
-    size_t count;
-    const uint8_t* keys;   // n_keys x 32 bytes
-    size_t n_keys;
-    uint64_t index_base;
-    const uint64_t* index;     // count x u64 or null
-    const uint64_t* amounts;   // one u64 per unit (sealed) or n_keys x count
-    uint32_t* ok;              // count words
-    uint32_t* hits;            // max_hits x FIND_HIT_WORDS words
-    size_t max_hits;
-    uint32_t* n_hits;          // one word
-    FindMode mode;
-    const uint8_t* tags;       // one byte per unit; unread when rewinding untagged
-    uint32_t* n_candidates;    // one word or null; likewise
-    uint32_t version = 1;      // what the call's flags say
-    bool amount64 = false, sealed = false;
-    // per output alone, in place of m_of: the ragged block (outs_plan.hpp) -- amounts and tags by REAL output number, the
-    // sum of outs_of[i] of them
-    const uint32_t* outs_of = nullptr;
-    bool tagged() const { return mode != FIND_REWIND; }
-};
-
 template <class C>
 struct FindImpl {
     // mode, a.mode: one of the rewinding two
@@ -536,7 +503,9 @@ struct RewindStep {
     // untagged, the pair words of aggregated proofs; tagged, those of every pair that is no candidate
     static bool zero_pairs(const FindArgs& a, const MixedPlan& p) { return a.tagged() || p.count[0] != a.count; }
     int begin(const FindCall<C>& c) {
-        j = K::call_job(c.a.keys, c.a.n_keys, c.a.index_base, c.a.index, c.W(c.L.masks), c.W(c.L.hit), c.a.count);
+        j = K::call_job(c.a.keys, c.a.n_keys, c.a.index_base, c.a.index, c.a.count);
+        j.out_masks = c.W(c.L.masks);
+        j.out_status = c.W(c.L.hit);
         return BPP_OK;
     }
     int klass(const FindCall<C>& c, const typename V::ClassView& cv) {

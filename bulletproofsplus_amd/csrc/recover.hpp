@@ -17,8 +17,11 @@
 #pragma once
 #include "commit.hpp"
 #include "recover_terms.hpp"
+#include "scan_args.hpp"
 
 namespace bpp {
+
+static_assert(PAIR_BOUND == ONE_LAUNCH && OUTS_LARGEST == 1u << (OUTS_CLASSES - 1), "scan_args.hpp restates these to stay HIP-free");
 
 constexpr unsigned RECOVER_GROUP = 16;   // lanes per proof
 constexpr unsigned RECOVER_BLOCK = 64;
@@ -169,19 +172,13 @@ struct RecoverImpl {
     using V = VerifyImpl<C>;
     static constexpr int WW = 2 * C::Fp::N + 2;
 
-    // the blinding source of a call, as the entry points take it
-    struct Blinding {
-        const uint8_t* key;         // 32 bytes (host), or null
-        uint64_t index_base;
-        const uint64_t* d_index;    // count x u64 (device), or null
-        const uint64_t* d_blinding; // device, or null
-    };
     // the wire call's per-proof entries by gathered position, for a plan of mixed_plan
     static void build_rx(const VerifyShape& cap, const MixedPlan& p, const uint32_t* m_of, size_t count, std::vector<uint32_t>& rx);
-    // one class: count proofs of class c from gathered position first; the job's source, index and blinding from b
-    static int launch_recover(const bpp_verifier* v, uint32_t c, size_t first, size_t count, const Blinding& b,
-                              const uint32_t* d_rx, const uint32_t* triples, bool triples_by_caller, const uint32_t* ch,
-                              uint32_t ch_mode, uint32_t* out, bool out_by_caller, uint32_t* conf, hipStream_t st);
+    // the call's part of a job: the blinding source of the record (a.index, a.blinding: the device's)
+    static RecoverJob call_job(const ScanArgs& a);
+    // one class: count proofs of class c from gathered position first.  j: the call's part, the per-proof entries from
+    // gathered position 0 and the launch's buffers (triples, ch, out, conf and how they are addressed)
+    static int launch_recover(const bpp_verifier* v, uint32_t c, size_t first, size_t count, RecoverJob j, hipStream_t st);
     // a class of the plan whose term count does not fit a lane group: BPP_E_ARG (none with today's make_shape)
     static int check_classes(const bpp_verifier* v, const MixedPlan& p) {
         for (uint32_t c = 0; c < MIXED_CLASSES; c++)
@@ -193,17 +190,13 @@ struct RecoverImpl {
     // ---- recovery from wire data: triples and challenge blocks in caller order, no points --------------------------------
     // workspace = the per-proof entries.  0 for an m_of the verifier does not take.
     static size_t recover_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count);
-    // d_scalars: count x 3 ; d_challenges: the packed 3 + k_i blocks, or null: the literals of each proof's own shape;
-    // d_out_masks: count x 4 words of Gamma_i, caller order.  Uploads the per-proof entries (blocking the host until the copy
+    // a.scalars: count x 3 ; a.challenges: the packed 3 + k_i blocks, or null: the literals of each proof's own shape;
+    // a.out_masks: count x 4 words of Gamma_i, caller order.  Uploads the per-proof entries (blocking the host until the copy
     // has read them); per class present one launch of k_recover_masks that reads and writes the caller's buffers through
     // the entries -- nothing is gathered and nothing scattered.
-    static int recover_masks_mixed(bpp_verifier* v, const uint64_t* d_scalars, const uint32_t* m_of, size_t count,
-                                   const uint64_t* d_challenges, const Blinding& b, uint64_t* d_out_masks, void* d_workspace,
-                                   size_t workspace_bytes, hipStream_t st);
-    // host buffers in, host buffers out (blinding, index: host, may be null)
-    static int recover_masks_mixed_host(bpp_verifier* v, const uint64_t* scalars, const uint32_t* m_of, size_t count,
-                                        const uint64_t* challenges, const uint8_t* blind_key, uint64_t index_base,
-                                        const uint64_t* index, const uint64_t* blinding, uint64_t* out_masks);
+    static int recover_masks_mixed(bpp_verifier* v, const ScanArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st);
+    // host buffers in, host buffers out (blinding, index: host, may be null): the record with the device's pointers swapped in
+    static int recover_masks_mixed_host(bpp_verifier* v, const ScanArgs& a);
 
     // ---- scanning from bytes: run_serialized_mixed's front (decoder, membership test, challenges), then recovery and the
     // confirmation instead of the verifier's pass ----------------------------------------------------------------------
@@ -223,17 +216,23 @@ struct RecoverImpl {
         return w;
     }
     static size_t scan_workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count);
-    // d_proofs, d_commitments, m_of, version: run_serialized_mixed's; d_amounts: count x u64 by caller position, or null;
-    // d_out_masks: count x 4 words, d_status: count words, caller order
-    static int scan_serialized_mixed(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments, const uint32_t* m_of,
-                                     size_t count, bool transcript, uint32_t version, bool amount64, const Blinding& b,
-                                     const uint64_t* d_amounts, uint64_t* d_out_masks, uint32_t* d_status, void* d_workspace,
-                                     size_t workspace_bytes, hipStream_t st);
-    static int scan_serialized_mixed_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, const uint32_t* m_of,
-                                          size_t count, int flags, const uint8_t* blind_key, uint64_t index_base,
-                                          const uint64_t* index, const uint64_t* blinding, const uint64_t* amounts,
-                                          uint64_t* out_masks, uint32_t* out_status);
+    // a.proofs, a.commitments, a.m_of, a.version: run_serialized_mixed's; a.amounts: count x u64 by caller position, or null;
+    // a.out_masks: count x 4 words, a.out_status: count words, caller order
+    static int scan_serialized_mixed(bpp_verifier* v, const ScanArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st);
+    static int scan_serialized_mixed_host(bpp_verifier* v, const ScanArgs& a);
 };
+
+// Where proof i's blinding scalars sit in a call's packed buffer (in scalars: 5 + 2 k_i of them, k_i = log2(n m_i)): into
+// at[i] when at is given; returns their total.
+inline size_t blind_offsets(const VerifyShape& cap, const uint32_t* m_of, size_t count, uint32_t* at = nullptr) {
+    const uint32_t logn = cap.k - (uint32_t)__builtin_ctz(cap.m);
+    size_t total = 0;
+    for (size_t i = 0; i < count; i++) {
+        if (at) at[i] = (uint32_t)total;
+        total += pb_blind_elems(logn + (uint32_t)__builtin_ctz(m_of[i]));
+    }
+    return total;
+}
 
 #ifdef BPP_IMPL_DEFINITIONS
 template <class C>
@@ -241,43 +240,40 @@ void RecoverImpl<C>::build_rx(const VerifyShape& cap, const MixedPlan& p, const 
                               std::vector<uint32_t>& rx) {
     const uint32_t logn = cap.k - (uint32_t)__builtin_ctz(cap.m);
     rx.assign(count * RX_WORDS, 0u);
+    std::vector<uint32_t> at(count);
+    blind_offsets(cap, m_of, count, at.data());
     size_t next[MIXED_CLASSES];
     for (uint32_t c = 0; c < MIXED_CLASSES; c++) next[c] = p.first[c];
-    size_t src_bl = 0, src_ch = 0;
+    size_t src_ch = 0;
     for (size_t i = 0; i < count; i++) {
-        const uint32_t c = (uint32_t)__builtin_ctz(m_of[i]), k = logn + c;
+        const uint32_t c = (uint32_t)__builtin_ctz(m_of[i]);
         uint32_t* e = rx.data() + next[c]++ * RX_WORDS;
         e[RX_CALLER] = (uint32_t)i;
-        e[RX_BLIND] = (uint32_t)src_bl;
+        e[RX_BLIND] = at[i];
         e[RX_CH] = (uint32_t)src_ch;
-        src_bl += pb_blind_elems(k);
-        src_ch += 3 + k;
+        src_ch += 3 + logn + c;
     }
 }
 
 template <class C>
-int RecoverImpl<C>::launch_recover(const bpp_verifier* v, uint32_t c, size_t first, size_t count, const Blinding& b,
-                                   const uint32_t* d_rx, const uint32_t* triples, bool triples_by_caller, const uint32_t* ch,
-                                   uint32_t ch_mode, uint32_t* out, bool out_by_caller, uint32_t* conf, hipStream_t st) {
+RecoverJob RecoverImpl<C>::call_job(const ScanArgs& a) {
+    RecoverJob j = {};
+    load_key_words(a.blind_key, j.key.w);
+    j.have_key = a.blind_key ? 1u : 0u;
+    j.index_base = a.index_base;
+    j.index = a.index;
+    j.blinding = reinterpret_cast<const uint32_t*>(a.blinding);
+    return j;
+}
+
+template <class C>
+int RecoverImpl<C>::launch_recover(const bpp_verifier* v, uint32_t c, size_t first, size_t count, RecoverJob j, hipStream_t st) {
     const VerifyShape& s = V::class_shape(v, c).s;
-    RecoverJob j;
     j.k = s.k;
     j.m = s.m;
     // alpha: range/mod.rs:94 / :256 ; d_L, d_R: wip.rs:94-95 ; delta, eta: wip.rs:177-178
     j.lit = recover_literals(s.m == 1 ? 7 : 33, 4, 5, 88, 123);
-    load_key_words(b.key, j.key.w);
-    j.have_key = b.key ? 1u : 0u;
-    j.index_base = b.index_base;
-    j.index = b.d_index;
-    j.blinding = reinterpret_cast<const uint32_t*>(b.d_blinding);
-    j.rx = d_rx + first * RX_WORDS;
-    j.triples = triples;
-    j.triples_by_caller = triples_by_caller ? 1u : 0u;
-    j.ch = ch;
-    j.ch_mode = ch_mode;
-    j.out = out;
-    j.out_by_caller = out_by_caller ? 1u : 0u;
-    j.conf = conf;
+    j.rx += first * RX_WORDS;
     j.count = count;
     hipLaunchKernelGGL(k_recover_masks<C>, dim3(cdiv(count * RECOVER_GROUP, RECOVER_BLOCK)), dim3(RECOVER_BLOCK), 0, st, j);
     HIPCHK(hipGetLastError());
@@ -294,25 +290,29 @@ size_t RecoverImpl<C>::recover_workspace_bytes(const bpp_verifier* v, const uint
 }
 
 template <class C>
-int RecoverImpl<C>::recover_masks_mixed(bpp_verifier* v, const uint64_t* d_scalars, const uint32_t* m_of, size_t count,
-                                        const uint64_t* d_challenges, const Blinding& b, uint64_t* d_out_masks,
-                                        void* d_workspace, size_t workspace_bytes, hipStream_t st) {
+int RecoverImpl<C>::recover_masks_mixed(bpp_verifier* v, const ScanArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
     MixedPlan p;
-    int rc = mixed_plan(v->s, m_of, count, false, p);
+    int rc = mixed_plan(v->s, a.m_of, a.count, false, p);
     if (rc) return rc;
-    if (workspace_bytes < recover_workspace_bytes(v, m_of, count)) return fail(BPP_E_ARG, "workspace too small");
+    if (workspace_bytes < recover_workspace_bytes(v, a.m_of, a.count)) return fail(BPP_E_ARG, "workspace too small");
     if ((rc = check_classes(v, p))) return rc;
     std::vector<uint32_t> rx;
-    build_rx(v->s, p, m_of, count, rx);
+    build_rx(v->s, p, a.m_of, a.count, rx);
     uint32_t* d_rx = static_cast<uint32_t*>(d_workspace);
     // pageable source: the copy has read it when the call returns
     HIPCHK(hipMemcpyAsync(d_rx, rx.data(), rx.size() * 4, hipMemcpyHostToDevice, st));
+    // the launches read and write the caller's buffers, by caller position
+    RecoverJob j = call_job(a);
+    j.rx = d_rx;
+    j.triples = reinterpret_cast<const uint32_t*>(a.scalars);
+    j.triples_by_caller = 1u;
+    j.out = reinterpret_cast<uint32_t*>(a.out_masks);
+    j.out_by_caller = 1u;
+    j.ch_mode = a.challenges ? RCH_INDEXED : RCH_SHARED;
     for (uint32_t c = 0; c < MIXED_CLASSES; c++) {
         if (!p.count[c]) continue;
-        rc = launch_recover(v, c, p.first[c], p.count[c], b, d_rx, reinterpret_cast<const uint32_t*>(d_scalars), true,
-                            d_challenges ? reinterpret_cast<const uint32_t*>(d_challenges) : V::class_shape(v, c).challenges,
-                            d_challenges ? RCH_INDEXED : RCH_SHARED, reinterpret_cast<uint32_t*>(d_out_masks), true, nullptr, st);
-        if (rc) return rc;
+        j.ch = a.challenges ? reinterpret_cast<const uint32_t*>(a.challenges) : V::class_shape(v, c).challenges;
+        if ((rc = launch_recover(v, c, p.first[c], p.count[c], j, st))) return rc;
     }
     return BPP_OK;
 }
@@ -328,29 +328,39 @@ struct BlockUpload {
         HIPCHK(amounts.upload(h_amounts, n_amounts * 8));
         return BPP_OK;
     }
+    // a scan's record with what was uploaded in the host pointers' place
+    ScanArgs device_args(const ScanArgs& a) const {
+        ScanArgs d = a;
+        d.proofs = proofs.u8();
+        d.commitments = commitments.u8();
+        d.index = index.u64();
+        d.amounts = amounts.u64();
+        return d;
+    }
 };
 
 template <class C>
-int RecoverImpl<C>::recover_masks_mixed_host(bpp_verifier* v, const uint64_t* scalars, const uint32_t* m_of, size_t count,
-                                             const uint64_t* challenges, const uint8_t* blind_key, uint64_t index_base,
-                                             const uint64_t* index, const uint64_t* blinding, uint64_t* out_masks) {
+int RecoverImpl<C>::recover_masks_mixed_host(bpp_verifier* v, const ScanArgs& a) {
+    const size_t count = a.count;
     MixedPlan p;
-    int rc = mixed_plan(v->s, m_of, count, false, p);
+    int rc = mixed_plan(v->s, a.m_of, count, false, p);
     if (rc) return rc;
-    const uint32_t logn = v->s.k - (uint32_t)__builtin_ctz(v->s.m);
-    size_t nbl = 0;
-    for (size_t i = 0; i < count; i++) nbl += pb_blind_elems(logn + (uint32_t)__builtin_ctz(m_of[i]));
     DevBuf dsc, dch, dix, dbl, dout, dws;
-    HIPCHK(dsc.upload(scalars, count * 96));
-    HIPCHK(dch.upload(challenges, p.chals * 32));
-    HIPCHK(dix.upload(index, count * 8));
-    HIPCHK(dbl.upload(blinding, nbl * 32));
-    const size_t wsb = recover_workspace_bytes(v, m_of, count);
+    HIPCHK(dsc.upload(a.scalars, count * 96));
+    HIPCHK(dch.upload(a.challenges, p.chals * 32));
+    HIPCHK(dix.upload(a.index, count * 8));
+    HIPCHK(dbl.upload(a.blinding, blind_offsets(v->s, a.m_of, count) * 32));
+    const size_t wsb = recover_workspace_bytes(v, a.m_of, count);
     HIPCHK(dout.alloc(count * 32));
     HIPCHK(dws.alloc(wsb));
-    const Blinding b{blind_key, index_base, dix.u64(), dbl.u64()};
-    BPP_TRY(recover_masks_mixed(v, dsc.u64(), m_of, count, dch.u64(), b, dout.u64(), dws.p, wsb, nullptr));
-    HIPCHK(dout.download(out_masks, count * 32));
+    ScanArgs d = a;
+    d.scalars = dsc.u64();
+    d.challenges = dch.u64();
+    d.index = dix.u64();
+    d.blinding = dbl.u64();
+    d.out_masks = dout.u64();
+    BPP_TRY(recover_masks_mixed(v, d, dws.p, wsb, nullptr));
+    HIPCHK(dout.download(a.out_masks, count * 32));
     return BPP_OK;
 }
 
@@ -362,47 +372,45 @@ size_t RecoverImpl<C>::scan_workspace_bytes(const bpp_verifier* v, const uint32_
 }
 
 template <class C>
-int RecoverImpl<C>::scan_serialized_mixed(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments,
-                                          const uint32_t* m_of, size_t count, bool transcript, uint32_t version, bool amount64,
-                                          const Blinding& b, const uint64_t* d_amounts, uint64_t* d_out_masks,
-                                          uint32_t* d_status, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
-    if (int rc = V::container_args_ok(v, version)) return rc;
+int RecoverImpl<C>::scan_serialized_mixed(bpp_verifier* v, const ScanArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
+    if (int rc = V::container_args_ok(v, a.version)) return rc;
+    const size_t count = a.count;
     MixedPlan p;
-    int rc = mixed_plan_serialized(v->s, m_of, count, (size_t)container_point_bytes<C>(version), true, p);
+    int rc = mixed_plan_serialized(v->s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), true, p);
     if (rc) return rc;
     const ScanLayout L = scan_layout(p, count);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     if ((rc = check_classes(v, p))) return rc;
-    if (b.d_blinding) {   // where each proof's blinding scalars sit, into the free word of the decoder's index
-        const uint32_t logn = v->s.k - (uint32_t)__builtin_ctz(v->s.m);
+    if (a.blinding) {   // where each proof's blinding scalars sit, into the free word of the decoder's index
         std::vector<uint32_t> at(count);
-        size_t src_bl = 0;
-        for (size_t i = 0; i < count; i++) {
-            at[i] = (uint32_t)src_bl;
-            src_bl += pb_blind_elems(logn + (uint32_t)__builtin_ctz(m_of[i]));
-        }
+        blind_offsets(v->s, a.m_of, count, at.data());
         for (size_t pos = 0; pos < count; pos++) p.sidx[pos * SX_WORDS + RX_BLIND] = at[p.sidx[pos * SX_WORDS + SX_CALLER]];
     }
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
     const uint32_t* w_idx = W(L.f.idx);
-    rc = V::decode_front(p, L.f, count, d_proofs, d_commitments, version, ws, st);
+    rc = V::decode_front(p, L.f, count, a.proofs, a.commitments, a.version, ws, st);
     if (rc) return rc;
+    // the launches read the decoded class regions and write Gamma and the confirmation word, by launch position
+    RecoverJob j = call_job(a);
+    j.rx = w_idx;
+    j.ch_mode = a.fs ? RCH_STRIDED : RCH_SHARED;
     size_t n_conf = 0;
     rc = V::for_each_class(v, p, L.f, ws, [&](const typename V::ClassView& cv) {
-        if (transcript) {
+        if (a.fs) {
             const int rc1 = V::derive_challenges(v, cv.ps, cv.pts, cv.count, cv.challenges, st);
             if (rc1) return rc1;
         }
-        const int rc2 = launch_recover(v, cv.c, cv.first, cv.count, b, w_idx, reinterpret_cast<const uint32_t*>(cv.sc3), false,
-                                       transcript ? reinterpret_cast<const uint32_t*>(cv.challenges) : cv.ps.challenges,
-                                       transcript ? RCH_STRIDED : RCH_SHARED, W(L.masks) + cv.first * 8, false,
-                                       W(L.conf) + cv.first, st);
-        if (rc2 || cv.c != 0 || !d_amounts) return rc2;
+        j.triples = reinterpret_cast<const uint32_t*>(cv.sc3);
+        j.ch = a.fs ? reinterpret_cast<const uint32_t*>(cv.challenges) : cv.ps.challenges;
+        j.out = W(L.masks) + cv.first * 8;
+        j.conf = W(L.conf) + cv.first;
+        const int rc2 = launch_recover(v, cv.c, cv.first, cv.count, j, st);
+        if (rc2 || cv.c != 0 || !a.amounts) return rc2;
         // the single-output class comes first in gathered order: launch position = gathered position
         n_conf = cv.count;
         hipLaunchKernelGGL(k_recover_confirm<C>, dim3(cdiv(cv.count, COMMIT_BLOCK)), dim3(COMMIT_BLOCK), 0, st, v->s,
-                           v->table.u32(), w_idx, d_amounts, W(L.masks), amount64 ? 1u : 0u,
+                           v->table.u32(), w_idx, a.amounts, W(L.masks), a.amount64 ? 1u : 0u,
                            reinterpret_cast<const uint32_t*>(cv.pts), cv.ps.s.NV, 3 + 2 * cv.ps.s.k, W(L.f.status), W(L.conf),
                            cv.count);
         HIPCHK(hipGetLastError());
@@ -410,39 +418,33 @@ int RecoverImpl<C>::scan_serialized_mixed(bpp_verifier* v, const uint8_t* d_proo
     });
     if (rc) return rc;
     hipLaunchKernelGGL(k_recover_scatter<C>, dim3(cdiv(count, 256)), dim3(256), 0, st, w_idx, W(L.f.status), W(L.conf), n_conf,
-                       W(L.masks), reinterpret_cast<uint32_t*>(d_out_masks), d_status, count);
+                       W(L.masks), reinterpret_cast<uint32_t*>(a.out_masks), a.out_status, count);
     HIPCHK(hipGetLastError());
     return BPP_OK;
 }
 
 template <class C>
-int RecoverImpl<C>::scan_serialized_mixed_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments,
-                                               const uint32_t* m_of, size_t count, int flags, const uint8_t* blind_key,
-                                               uint64_t index_base, const uint64_t* index, const uint64_t* blinding,
-                                               const uint64_t* amounts, uint64_t* out_masks, uint32_t* out_status) {
-    const uint32_t version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
-    if (int rc = V::container_args_ok(v, version)) return rc;
-    const size_t cb = (size_t)container_point_bytes<C>(version);
+int RecoverImpl<C>::scan_serialized_mixed_host(bpp_verifier* v, const ScanArgs& a) {
+    if (int rc = V::container_args_ok(v, a.version)) return rc;
+    const size_t count = a.count;
     MixedPlan p;
-    int rc = mixed_plan_serialized(v->s, m_of, count, cb, false, p);
+    int rc = mixed_plan_serialized(v->s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), false, p);
     if (rc) return rc;
-    const uint32_t logn = v->s.k - (uint32_t)__builtin_ctz(v->s.m);
-    size_t nbl = 0;
-    for (size_t i = 0; i < count; i++) nbl += pb_blind_elems(logn + (uint32_t)__builtin_ctz(m_of[i]));
     BlockUpload up;
     DevBuf dbl, dout, dst, dws;
-    BPP_TRY(up.upload(p, proofs, commitments, index, count, amounts, count));
-    HIPCHK(dbl.upload(blinding, nbl * 32));
+    BPP_TRY(up.upload(p, a.proofs, a.commitments, a.index, count, a.amounts, count));
+    HIPCHK(dbl.upload(a.blinding, blind_offsets(v->s, a.m_of, count) * 32));
     const size_t wsb = scan_layout(p, count).total;
     HIPCHK(dout.alloc(count * 32));
     HIPCHK(dst.alloc(count * 4));
     HIPCHK(dws.alloc(wsb));
-    const Blinding b{blind_key, index_base, up.index.u64(), dbl.u64()};
-    BPP_TRY(scan_serialized_mixed(v, up.proofs.u8(), up.commitments.u8(), m_of, count, (flags & BPP_SER_TRANSCRIPT) != 0, version,
-                                  (flags & BPP_PROVE_AMOUNT64) != 0, b, up.amounts.u64(), dout.u64(), dst.u32(), dws.p, wsb,
-                                  nullptr));
-    HIPCHK(dout.download(out_masks, count * 32));
-    HIPCHK(dst.download(out_status, count * 4));
+    ScanArgs d = up.device_args(a);
+    d.blinding = dbl.u64();
+    d.out_masks = dout.u64();
+    d.out_status = dst.u32();
+    BPP_TRY(scan_serialized_mixed(v, d, dws.p, wsb, nullptr));
+    HIPCHK(dout.download(a.out_masks, count * 32));
+    HIPCHK(dst.download(a.out_status, count * 4));
     return BPP_OK;
 }
 #endif  // BPP_IMPL_DEFINITIONS

@@ -239,9 +239,9 @@ struct RecoverKeysImpl {
         return w;
     }
     static size_t workspace_bytes(const bpp_verifier* v, const uint32_t* m_of, size_t count);
-    // the call's part of the pair job: the keys, the index, where Gamma and the pair word go ([key][caller position]), total
-    static ScanKeysJob call_job(const uint8_t* d_keys, size_t n_keys, uint64_t index_base, const uint64_t* d_index,
-                                uint32_t* out_masks, uint32_t* out_status, size_t total);
+    // the call's part of the pair job: the keys, the index and total; where Gamma and the pair word go ([key][caller
+    // position]: out_masks, out_status) is the caller's to add
+    static ScanKeysJob call_job(const uint8_t* d_keys, size_t n_keys, uint64_t index_base, const uint64_t* d_index, size_t total);
     // One class of a call, in three steps (the find call, find.hpp, takes them apart).  bind_class: the class's part of j
     // (k, rx, coeffs, bad, status, count), which the confirmation that follows reads too; w_idx, w_status, w_bad: the call's,
     // from gathered position 0; coeffs: the class's.  launch_coeffs: k_recover_coeffs over its proofs, into the coeffs and
@@ -250,15 +250,10 @@ struct RecoverKeysImpl {
                            const uint32_t* coeffs, ScanKeysJob& j);
     static int launch_coeffs(const typename V::ClassView& cv, uint32_t* coeffs, uint32_t* w_bad, hipStream_t st);
     static int launch_scan_keys(const ScanKeysJob& j, hipStream_t st);
-    // d_keys: n_keys x 32 bytes (device, 4-byte aligned); d_index: count x u64 or null; d_amounts: n_keys x count or null;
-    // d_out_masks: n_keys x count x 4 words; d_status: n_keys x count words
-    static int scan(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments, const uint32_t* m_of, size_t count,
-                    uint32_t version, bool amount64, const uint8_t* d_keys, size_t n_keys, uint64_t index_base,
-                    const uint64_t* d_index, const uint64_t* d_amounts, uint64_t* d_out_masks, uint32_t* d_status,
-                    void* d_workspace, size_t workspace_bytes, hipStream_t st);
-    static int scan_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, const uint32_t* m_of, size_t count,
-                         int flags, const uint8_t* keys, size_t n_keys, uint64_t index_base, const uint64_t* index,
-                         const uint64_t* amounts, uint64_t* out_masks, uint32_t* out_status);
+    // a.keys: n_keys x 32 bytes (device, 4-byte aligned); a.index: count x u64 or null; a.amounts: n_keys x count or null;
+    // a.out_masks: n_keys x count x 4 words; a.out_status: n_keys x count words
+    static int scan(bpp_verifier* v, const ScanArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st);
+    static int scan_host(bpp_verifier* v, const ScanArgs& a);
 };
 
 #ifdef BPP_IMPL_DEFINITIONS
@@ -270,22 +265,22 @@ size_t RecoverKeysImpl<C>::workspace_bytes(const bpp_verifier* v, const uint32_t
 }
 
 template <class C>
-int RecoverKeysImpl<C>::scan(bpp_verifier* v, const uint8_t* d_proofs, const uint8_t* d_commitments, const uint32_t* m_of,
-                             size_t count, uint32_t version, bool amount64, const uint8_t* d_keys, size_t n_keys,
-                             uint64_t index_base, const uint64_t* d_index, const uint64_t* d_amounts, uint64_t* d_out_masks,
-                             uint32_t* d_status, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
-    if (int rc = V::container_args_ok(v, version)) return rc;
+int RecoverKeysImpl<C>::scan(bpp_verifier* v, const ScanArgs& a, void* d_workspace, size_t workspace_bytes, hipStream_t st) {
+    if (int rc = V::container_args_ok(v, a.version)) return rc;
+    const size_t count = a.count, n_keys = a.n_keys;
     MixedPlan p;
-    int rc = mixed_plan_serialized(v->s, m_of, count, (size_t)container_point_bytes<C>(version), true, p);
+    int rc = mixed_plan_serialized(v->s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), true, p);
     if (rc) return rc;
     const Layout L = layout(v, p, count);
     if (workspace_bytes < L.total) return fail(BPP_E_ARG, "workspace too small");
     if ((rc = R::check_classes(v, p))) return rc;
     uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     auto W = [&](size_t off) { return reinterpret_cast<uint32_t*>(ws + off); };
-    rc = V::decode_front(p, L.f, count, d_proofs, d_commitments, version, ws, st);
+    rc = V::decode_front(p, L.f, count, a.proofs, a.commitments, a.version, ws, st);
     if (rc) return rc;
-    ScanKeysJob j = call_job(d_keys, n_keys, index_base, d_index, reinterpret_cast<uint32_t*>(d_out_masks), d_status, count);
+    ScanKeysJob j = call_job(a.keys, n_keys, a.index_base, a.index, count);
+    j.out_masks = reinterpret_cast<uint32_t*>(a.out_masks);
+    j.out_status = a.out_status;
     return V::for_each_class(v, p, L.f, ws, [&](const typename V::ClassView& cv) {
         int rc1 = V::derive_challenges(v, cv.ps, cv.pts, cv.count, cv.challenges, st);
         if (rc1) return rc1;
@@ -293,10 +288,10 @@ int RecoverKeysImpl<C>::scan(bpp_verifier* v, const uint8_t* d_proofs, const uin
         bind_class(cv, W(L.f.idx), W(L.f.status), W(L.bad), coeffs, j);
         if ((rc1 = launch_coeffs(cv, coeffs, W(L.bad), st))) return rc1;
         if ((rc1 = launch_scan_keys(j, st))) return rc1;
-        if (cv.c != 0 || !d_amounts) return BPP_OK;
+        if (cv.c != 0 || !a.amounts) return BPP_OK;
         // the single-output class comes first in gathered order: launch position = gathered position
         hipLaunchKernelGGL(k_scan_keys_confirm<C>, dim3(cdiv(cv.count * n_keys, COMMIT_BLOCK)), dim3(COMMIT_BLOCK), 0, st, v->s,
-                           v->table.u32(), j, d_amounts, amount64 ? 1u : 0u, reinterpret_cast<const uint32_t*>(cv.pts),
+                           v->table.u32(), j, a.amounts, a.amount64 ? 1u : 0u, reinterpret_cast<const uint32_t*>(cv.pts),
                            cv.ps.s.NV, 3 + 2 * cv.ps.s.k);
         HIPCHK(hipGetLastError());
         return BPP_OK;
@@ -305,14 +300,12 @@ int RecoverKeysImpl<C>::scan(bpp_verifier* v, const uint8_t* d_proofs, const uin
 
 template <class C>
 ScanKeysJob RecoverKeysImpl<C>::call_job(const uint8_t* d_keys, size_t n_keys, uint64_t index_base, const uint64_t* d_index,
-                                         uint32_t* out_masks, uint32_t* out_status, size_t total) {
+                                         size_t total) {
     ScanKeysJob j = {};
     j.n_keys = (uint32_t)n_keys;
     j.keys = reinterpret_cast<const uint32_t*>(d_keys);
     j.index_base = index_base;
     j.index = d_index;
-    j.out_masks = out_masks;
-    j.out_status = out_status;
     j.total = total;
     return j;
 }
@@ -345,28 +338,29 @@ int RecoverKeysImpl<C>::launch_scan_keys(const ScanKeysJob& j, hipStream_t st) {
 }
 
 template <class C>
-int RecoverKeysImpl<C>::scan_host(bpp_verifier* v, const uint8_t* proofs, const uint8_t* commitments, const uint32_t* m_of,
-                                  size_t count, int flags, const uint8_t* keys, size_t n_keys, uint64_t index_base,
-                                  const uint64_t* index, const uint64_t* amounts, uint64_t* out_masks, uint32_t* out_status) {
-    const uint32_t version = (flags & BPP_SER_UNCOMPRESSED) ? 2u : 1u;
-    if (int rc = V::container_args_ok(v, version)) return rc;
+int RecoverKeysImpl<C>::scan_host(bpp_verifier* v, const ScanArgs& a) {
+    if (int rc = V::container_args_ok(v, a.version)) return rc;
+    const size_t count = a.count;
     MixedPlan p;
-    int rc = mixed_plan_serialized(v->s, m_of, count, (size_t)container_point_bytes<C>(version), false, p);
+    int rc = mixed_plan_serialized(v->s, a.m_of, count, (size_t)container_point_bytes<C>(a.version), false, p);
     if (rc) return rc;
-    const size_t pairs = n_keys * count;
+    const size_t pairs = a.n_keys * count;
     DevBuf dk(true);   // the keys: wiped before they are freed, on every way out
     BlockUpload up;
     DevBuf dout, dst, dws;
-    BPP_TRY(up.upload(p, proofs, commitments, index, count, amounts, pairs));
-    HIPCHK(dk.upload(keys, n_keys * 32));
+    BPP_TRY(up.upload(p, a.proofs, a.commitments, a.index, count, a.amounts, pairs));
+    HIPCHK(dk.upload(a.keys, a.n_keys * 32));
     const size_t wsb = layout(v, p, count).total;
     HIPCHK(dout.alloc(pairs * 32));
     HIPCHK(dst.alloc(pairs * 4));
     HIPCHK(dws.alloc(wsb));
-    BPP_TRY(scan(v, up.proofs.u8(), up.commitments.u8(), m_of, count, version, (flags & BPP_PROVE_AMOUNT64) != 0, dk.u8(), n_keys,
-                 index_base, up.index.u64(), up.amounts.u64(), dout.u64(), dst.u32(), dws.p, wsb, nullptr));
-    HIPCHK(dout.download(out_masks, pairs * 32));
-    HIPCHK(dst.download(out_status, pairs * 4));
+    ScanArgs d = up.device_args(a);
+    d.keys = dk.u8();
+    d.out_masks = dout.u64();
+    d.out_status = dst.u32();
+    BPP_TRY(scan(v, d, dws.p, wsb, nullptr));
+    HIPCHK(dout.download(a.out_masks, pairs * 32));
+    HIPCHK(dst.download(a.out_status, pairs * 4));
     return BPP_OK;
 }
 #endif  // BPP_IMPL_DEFINITIONS

@@ -506,8 +506,9 @@ extern "C" int bpp_debug_scan_keys(bpp_verifier* v, uint32_t m_view, const uint6
                 HIPCHK(dom.upload(out_masks, pairs * 32));
                 HIPCHK(dos.upload(out_status, pairs * 4));
             }
-            ScanKeysJob j = K::call_job(dk.u8(), n_keys, index_base,
-                                        dix.u64(), dom.u32(), dos.u32(), total);
+            ScanKeysJob j = K::call_job(dk.u8(), n_keys, index_base, dix.u64(), total);
+            j.out_masks = dom.u32();
+            j.out_status = dos.u32();
             K::bind_class(view, drx.u32(), dst.u32(), dbad.u32(), dco.u32(), j);
             if (int rc = K::launch_coeffs(view, dco.u32(), dbad.u32(), nullptr)) return rc;
             if (n_keys)

@@ -78,6 +78,13 @@ def test_every_entry_point_runs_under_the_guard():
 CSRC = os.path.join(ROOT, "bulletproofsplus_amd", "csrc")
 
 
+def _receiver_check(name):
+    """-> the body of scan_args or find_args, the one check in front of the receiver's entries (csrc/scan_args.hpp)"""
+    text = open(os.path.join(CSRC, "scan_args.hpp")).read()
+    at = text.index("inline int %s(" % name)
+    return text[at:text.index("\n}\n", at)]
+
+
 def _csrc_sources():
     """-> {file name: text} of the library's sources"""
     return {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".hpp", ".h"))}

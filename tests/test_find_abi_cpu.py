@@ -66,7 +66,8 @@ def test_entries_run_under_the_guard():
         if "workspace_bytes" not in s:
             assert '{count, "count"}' in entries[s], (s, "count is not bounded by the shim")
     for s in FIND[1:]:
-        assert "scan_keys_args(" in entries[s], (s, "n_keys x count is not bounded before the engine is read")
+        assert "find_args(" in entries[s] and "pairs_bounded(a.n_keys, pair_units(" in G._receiver_check("find_args"), \
+            (s, "n_keys x count is not bounded before the engine is read")
 
 
 def test_wrappers_exist():

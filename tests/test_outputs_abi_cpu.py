@@ -73,7 +73,10 @@ def test_entries_run_under_the_guard():
         assert s in entries and any(shim in entries[s] for shim in G.SHIMS), s
     for s in FIND[1:]:
         assert '{count, "count"}' in entries[s], (s, "count is not bounded by the shim")
-        assert re.search(r"scan_keys_args\([^()]*, true\)", entries[s]), (s, "n_keys x n_out is not bounded before the engine is read")
+        assert "FIND_PER_OUTPUT" in entries[s] and "find_args(" in entries[s], s
+        check = G._receiver_check("find_args")
+        assert "per_output = a.mode == FIND_PER_OUTPUT" in check and "pair_units(units_of, a.count, per_output)" in check, \
+            (s, "n_keys x n_out is not bounded before the engine is read")
     for s in MAKE:
         assert '{n_out, "n_out"}' in entries[s], s
     assert "pairs_bounded(n_keys, pair_units(m_of, count, true))" in entries[FIND[0]]

@@ -58,7 +58,8 @@ def test_entries_run_under_the_guard():
         assert s in entries and any(shim in entries[s] for shim in G.SHIMS), s
         if "workspace_bytes" not in s:
             assert '{count, "count"}' in entries[s], (s, "count is not bounded by the shim")
-            assert "scan_keys_args(" in entries[s], (s, "n_keys x count is not bounded before the engine is read")
+            assert "scan_args(SCAN_MANY_KEYS_" in entries[s] and "pairs_bounded(a.n_keys, a.count)" in G._receiver_check("scan_args"), \
+                (s, "n_keys x count is not bounded before the engine is read")
 
 
 def test_wrappers_exist():
